@@ -6,6 +6,8 @@ half-space construction -> 513-candidate sweep + selection (or LP) -> env update
 with the state resident in HBM when the timed region starts.
 
   python bench.py --gpus 1 --steps K --warmup W            (N>1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py ... --full                                (every other leg and check as well, see below)
+  python bench.py ... --dump-outputs DIR                    (the value leg's outputs after its last timed step)
 
 Workloads (BASELINE.json configs): c4 = circle N=100000 SCA (default: the configuration the metric's "N-agent circle at
 1/2/4/8 GPUs" clause names; it fits one GPU), c2 = circle N=1024 SCA, c3 = random N=4096 ORCA3D (c3lp: the Official LP),
@@ -20,10 +22,16 @@ Several GPUs: STRONG scaling by default -- the workload's N agents in total, sha
 GPUs), one all-gather of the moved 48-byte records per step, issued by the library's own RCCL communicator inside
 sca_run_steps.  `--scaling weak` keeps the workload's N per GPU instead.
 
-At --gpus 1 the JSON line also carries: `solver_only`, `grid_mode` (the same legs with SCA_NBR_GRID), `scale_model` (what
+A plain run sets up, warms up, times the --steps steps of the value leg and prints its line: nothing else is run.  With
+--full, at --gpus 1, the JSON line also carries: `solver_only`, `grid_mode` (the same legs with SCA_NBR_GRID), `scale_model` (what
 ONE rank of 2 / 4 / 8 executes per step -- the replicated neighbour structure over all N agents, everything else for N/G --
-timed on this GPU, and the speed-up it predicts), `extra_legs` (c2, c3, c3lp, c5: value, ms_per_step, max |dv| against the
-oracle) and `cpu_baseline`.
+timed on this GPU, and the speed-up it predicts), `value_parity`, `extra_legs` (c2, c3, c3lp, c5: value, ms_per_step, max |dv|
+against the oracle), `env_api` and `cpu_baseline`; at --gpus N it adds `other_exchange` when SCA_BENCH_BOTH_EXCHANGES is set.
+
+--dump-outputs DIR: after the timed steps, what the value leg computed in its last step -- the state sca_get_state hands a caller
+(pos, vel, heading, flags, total_dist, step_num) and the action rows of sca_get_actions -- as DIR/<name>.npy in float32 / float64
+(a seeded sample of the agents, listed in agent_index.npy, when the arrays would pass 64 MB).  The scenes are seeded: the same
+arguments give the same inputs on every run.
 
 Output (rank 0): the LAST stdout line is ONE compact JSON record, < 4 KB (compact_record: the contract's keys, `config`, `roofline`,
 `cpu_baseline`, one number per extra leg) -- the line the driver parses.  The full record (everything above) goes to bench_detail.json
@@ -476,6 +484,11 @@ def main():
     ap.add_argument('--emulate-rank-of', type=int, default=0, metavar='G',
                     help='1 GPU only: time what ONE rank of G executes per step (neighbour structure over all N, the rest for the '
                          'middle shard of N/G; the other records are copied over where the all-gather would deliver them)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline figure: the CPU baseline, solver_only, the other neighbour structure, scale_model, '
+                         'value_parity, extra_legs, env_api (and other_exchange with SCA_BENCH_BOTH_EXCHANGES); a plain run times the value leg alone')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write the state and action rows the value leg left after its last timed step as DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-extra', action='store_true', help='value leg only: no solver_only / grid_mode / scale_model / extra_legs')
     ap.add_argument('--no-extra-legs', action='store_true', help='skip the c2 / c3 / c3lp / c5 legs')
@@ -583,8 +596,11 @@ def main():
         tracked = vpref == 'dubins-device'
         main_leg = timed_leg(sol, scene, stepper, timer, args.steps, args.warmup, tracked)
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(sol, stepper, args.dump_outputs)
+
     other_exchange = None
-    if world > 1 and not share_gpu and exchange in ('torch', 'inlib') and os.environ.get('SCA_BENCH_BOTH_EXCHANGES') and vpref != 'dubins':
+    if args.full and world > 1 and not share_gpu and exchange in ('torch', 'inlib') and os.environ.get('SCA_BENCH_BOTH_EXCHANGES') and vpref != 'dubins':
         # the other way to run the step's all-gather, on a solver of its own, same leg: both lines on the first real lease
         other = 'inlib' if exchange == 'torch' else 'torch'
         sol2 = make_solver(S, scene, local_rank)
@@ -600,9 +616,9 @@ def main():
             other_exchange = {'exchange': other, 'error': 'the library could not create its RCCL communicator on every rank'}
         sol2.close()
     extras = {}
-    single = world == 1 and not args.no_extra and vpref != 'dubins'
+    single = args.full and world == 1 and not args.no_extra and vpref != 'dubins'
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # the CPU leg is a single-GPU (rank 0, N = 1) measurement
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:   # the CPU leg is a single-GPU (rank 0, N = 1) measurement
         cpu = cpu_baseline(scene, sol, S, tracked=tracked, warmup=max(2, args.warmup), mode=mode)
     if single:
         # the solver alone (v_pref from the straight-line rule): what north_star's path is without the tracker
@@ -688,6 +704,31 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 60 * 10 ** 6          # --dump-outputs: the arrays stay under 64 MB (decimal or binary) with their .npy headers
+
+
+def dump_outputs(sol, stepper, out_dir):
+    """--dump-outputs: the arrays a caller of the value leg receives after its last timed step (sca_get_state + sca_get_actions) as
+    <out_dir>/<name>.npy, float64 where the library hands out doubles or integers, float32 where it hands out floats or flags.  Several
+    ranks: rank 0 writes the rows of the agents it owns.  Over 64 MB in all: a fixed sample of the agents (seed 0, ascending ids)."""
+    st = sol.get_state()
+    arrays = {'pos': st['pos'], 'vel': st['vel'], 'heading': st['heading'], 'flags': st['flags'].astype(np.float32),
+              'total_dist': st['total_dist'], 'step_num': st['step_num'].astype(np.float64), 'action': sol.actions()}
+    n = sol.n
+    rows = np.arange(n)
+    if hasattr(stepper, 'owned') and getattr(stepper, 'world', 1) > 1 and not getattr(stepper, 'emulate', False):
+        rows = np.sort(stepper.owned()).astype(np.int64)
+    elif stepper.count < n:
+        rows = np.arange(stepper.begin, stepper.begin + stepper.count)
+    per_agent = sum(a.dtype.itemsize * (a.size // n) for a in arrays.values()) + 8
+    if per_agent * len(rows) > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(rows, DUMP_LIMIT_BYTES // per_agent, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a[rows]))
+    np.save(os.path.join(out_dir, 'agent_index.npy'), rows.astype(np.float64))
 
 
 def host_tracker_leg(sol, scene, S, timer, steps, warmup):

@@ -1,6 +1,7 @@
-"""bench.py's own code paths on the GPU box: the JSON contract of a single-GPU run (value_parity, cpu_baseline incl. the tracker
-pass), the --vpref dubins leg (it died with a KeyError behind the timed run), and the script as the driver launches it
-for eight ranks, sharing GPU 0 through its test hook so that the first real SCALE run cannot die on plumbing."""
+"""bench.py's own code paths on the GPU box: the JSON contract of a single-GPU run (with --full: value_parity, cpu_baseline incl. the
+tracker pass; without it: the value leg alone and its --dump-outputs), the --vpref dubins leg (it died with a KeyError
+behind the timed run), and the script as the driver launches it for eight ranks, sharing GPU 0 through its test hook so that the
+first real SCALE run cannot die on plumbing."""
 import json
 import os
 import subprocess
@@ -42,7 +43,7 @@ def _run(args, env=None, timeout=900, tmp=None):
 
 
 def test_single_gpu_json_line_small_swarm():
-    out = _run([os.path.join(ROOT, 'bench.py'), '--agents', '6000', '--steps', '5', '--warmup', '3'])
+    out = _run([os.path.join(ROOT, 'bench.py'), '--agents', '6000', '--steps', '5', '--warmup', '3', '--full'])
     assert out['metric'] == 'agent_steps_per_sec' and out['n_gpus'] == 1 and out['dtype'] == 'f64' and out['vs_baseline'] is None
     assert out['config']['agents'] == 6000 and out['config']['re_plans_timed'] > 0
     r = out['roofline']
@@ -63,6 +64,29 @@ def test_single_gpu_json_line_small_swarm():
     assert cc['kind'] == 'port' and cc['cores'] >= 1 and cc['value'] > 0 and cc['one_thread']['value'] > 0 and cc['reference_python']['value'] > 0
     assert c['max_abs_dv'] == 0.0 and c['rccl_ranks_seen'] == 1
     assert all(not isinstance(v, (dict, list)) for k in ('config', 'roofline') for v in c[k].values())
+
+
+def test_plain_run_times_the_value_leg_alone_and_dumps_its_outputs(tmp_path):
+    """without --full the run is set-up, warm-up, exactly --steps timed steps and the line: no CPU baseline, no other leg.
+    --dump-outputs writes the state and action rows the value leg left, and a second run with the same arguments starts from the same
+    inputs (the scenes are seeded), so both dumps are the same arrays."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f'dump{k}'
+        out = _run([os.path.join(ROOT, 'bench.py'), '--agents', '6000', '--steps', '7', '--warmup', '3', '--dump-outputs', str(d)], tmp=str(tmp_path))
+        assert out['steps'] == 7 and out['config']['agent_steps_timed'] == 6000 * 7 and out['ms_per_step'] > 0
+        assert abs(out['value'] - 6000 * 7 / (out['ms_per_step'] * 7e-3)) <= 1e-6 * out['value']
+        for key in ('cpu_baseline', 'solver_only', 'grid_mode', 'scale_model', 'value_parity', 'extra_legs', 'env_api'):
+            assert key not in out, key
+        arrays = {f.stem: np.load(f) for f in sorted(d.glob('*.npy'))}
+        assert set(arrays) == {'pos', 'vel', 'heading', 'flags', 'total_dist', 'step_num', 'action', 'agent_index'}
+        assert all(a.dtype in (np.float32, np.float64) and len(a) == 6000 for a in arrays.values())
+        assert arrays['pos'].shape == (6000, 3) and arrays['action'].shape == (6000, 7)
+        assert arrays['step_num'].max() == 3 + 7 and np.array_equal(arrays['agent_index'], np.arange(6000))
+        dumps.append(arrays)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
 
 
 def test_host_tracker_leg_prints_its_line():

@@ -185,6 +185,49 @@ def test_bench_self_launch_starts_torch_distributed_run_as_a_child_and_returns_i
         assert r.returncode != 0 and ('needs a GPU' in both or 'No HIP GPUs' in both or 'ProcessGroupNCCL' in both or 'NCCL' in both or 'CUDA' in both), both[-3000:]
 
 
+def test_bench_dump_outputs_writes_float_arrays_and_samples_past_64_mb(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array as float32 / float64 .npy, the rows of the agents the stepper owns, and a fixed seeded sample
+    of them (ascending ids, the same on every run) once the arrays would pass the size limit"""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class FakeSolver:
+        def __init__(self, n):
+            self.n = n
+
+        def get_state(self):
+            n = self.n
+            return dict(pos=np.arange(3 * n, dtype=np.float64).reshape(n, 3), vel=np.ones((n, 3), np.float32), heading=np.zeros((n, 3)),
+                        flags=np.arange(n, dtype=np.uint8), total_dist=np.arange(n, dtype=np.float64), step_num=np.full(n, 9, np.int32))
+
+        def actions(self):
+            return np.arange(7 * self.n, dtype=np.float32).reshape(self.n, 7)
+
+    class FakeStepper:
+        def __init__(self, begin, count):
+            self.begin, self.count = begin, count
+
+    sol = FakeSolver(1000)
+    bench.dump_outputs(sol, FakeStepper(0, 1000), str(tmp_path / 'all'))
+    got = {f.stem: np.load(f) for f in (tmp_path / 'all').glob('*.npy')}
+    assert set(got) == {'pos', 'vel', 'heading', 'flags', 'total_dist', 'step_num', 'action', 'agent_index'}
+    assert all(a.dtype in (np.float32, np.float64) and len(a) == 1000 for a in got.values())
+    assert np.array_equal(got['pos'], sol.get_state()['pos']) and np.array_equal(got['action'], sol.actions())
+    assert (got['step_num'] == 9).all() and np.array_equal(got['flags'], np.arange(1000, dtype=np.uint8).astype(np.float32))
+    bench.dump_outputs(sol, FakeStepper(250, 500), str(tmp_path / 'shard'))
+    assert np.array_equal(np.load(tmp_path / 'shard' / 'agent_index.npy'), np.arange(250, 750))
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 116 * 100)         # 116 bytes per agent: room for 100 of them
+    samples = []
+    for k in range(2):
+        bench.dump_outputs(sol, FakeStepper(0, 1000), str(tmp_path / f's{k}'))
+        idx = np.load(tmp_path / f's{k}' / 'agent_index.npy')
+        assert len(idx) == 100 and (np.diff(idx) > 0).all()
+        assert np.array_equal(np.load(tmp_path / f's{k}' / 'pos.npy'), sol.get_state()['pos'][idx.astype(np.int64)])
+        assert sum(f.stat().st_size for f in (tmp_path / f's{k}').glob('*.npy')) < 116 * 100 + 8 * 1024
+        samples.append(idx)
+    assert np.array_equal(samples[0], samples[1])
+
+
 def test_bench_compact_line_stays_under_4k_and_keeps_the_contract_keys():
     """the driver could not parse round 5's 24-KB stdout line.  bench.py's last stdout line is compact_record(out): run on the
     full record round 5 printed (profiles/r05_a_bench_c4_driver_cmd.json, 23.8 KB) it must stay under 4 KB and carry the contract's

@@ -34,7 +34,7 @@ for G in $GLIST; do
     [ -n "$AGENTS" ] && extra="$extra --agents $AGENTS"
     SCA_BENCH_BOTH_EXCHANGES=1 SCA_BENCH_DETAIL="$O/g${G}_${variant}_detail.json" MASTER_PORT=$port timeout 1800 \
       python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$G" --master-addr 127.0.0.1 --master-port $port bench.py \
-      --gpus "$G" --steps "$STEPS" --warmup "$WARM" $extra > "$O/g${G}_${variant}.out" 2> "$O/g${G}_${variant}.err"
+      --gpus "$G" --steps "$STEPS" --warmup "$WARM" --full $extra > "$O/g${G}_${variant}.out" 2> "$O/g${G}_${variant}.err"
     echo "G=$G $variant rc $? : $(grep '^{' "$O/g${G}_${variant}.out" | tail -1 | cut -c1-160)" | tee -a "$O/summary.txt"
   done
 done

@@ -15,7 +15,7 @@ cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r8gs_traced -- python3 $R/bench.py --workload c4 --emulate-rank-of 8 --nbr grid --vpref straight --steps 100 --warmup 10 > $O/r8gs_traced.json 2>> $O/err.txt
 cd $R
 # the extra legs incl. the held-out scene (the whole default command, as the driver runs it but with the default K / W)
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 find $O -name "*agent_info*" -delete
 find $O -name "*kernel_trace.csv" -size +20M -delete
 du -sh $O

@@ -14,5 +14,5 @@ for cfg in "c3 auto" "c3 kd" "c3 grid" "c3lp auto" "c2 kd" "c5 kd" "c4 kd"; do
 done
 python3 tools/device_timeline.py c4 --nbr grid --straight --steps 40 -o $O/tl_c4_grid_straight.json > $O/tl_c4_grid_straight.txt 2>&1
 cp /tmp/libsca_hip_product.so sca_amd/lib/libsca_hip.so
-python3 bench.py --no-cpu-baseline --no-weak-model > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full --no-cpu-baseline --no-weak-model > $O/bench_default.json 2> $O/bench_default.err
 head -30 $O/tl_c3_auto.txt

@@ -9,7 +9,7 @@ cd $R
 timeout 2400 python3 -m pytest tests -m gpu -q -x --timeout 1200 > $O/pytest.log 2>&1
 echo "pytest rc $?" >> $O/pytest.log
 tail -5 $O/pytest.log
-SCA_BENCH_DETAIL=$O/bench_detail.json python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.out 2> $O/bench_driver.err
+SCA_BENCH_DETAIL=$O/bench_detail.json python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.out 2> $O/bench_driver.err
 echo "bench rc $? bytes $(wc -c < $O/bench_driver.out)"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks_c4 -- python3 $R/bench.py --workload c4 --steps 30 --warmup 10 --no-extra --no-cpu-baseline > $O/ks_c4.out 2> $O/ks_c4.err

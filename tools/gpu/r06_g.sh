@@ -8,7 +8,7 @@ cd $R
 timeout 1500 python3 -m pytest tests -m gpu -q --timeout 400 > $O/pytest.log 2>&1
 echo "pytest rc $?" >> $O/pytest.log
 grep -E "FAILED|passed|failed|Timeout" $O/pytest.log | tail -20
-SCA_BENCH_DETAIL=$O/driver_detail.json timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver.out 2> $O/driver.err
+SCA_BENCH_DETAIL=$O/driver_detail.json timeout 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/driver.out 2> $O/driver.err
 echo "bench rc $? bytes $(wc -c < $O/driver.out)"; cat $O/driver.out
 for tag in tail notail; do
   if [ $tag = notail ]; then export SCA_AUTO_NO_TAIL=1; else unset SCA_AUTO_NO_TAIL; fi

@@ -6,8 +6,8 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r06_p
 mkdir -p $O
 cd $R
-SCA_BENCH_DETAIL=$O/bench_c4_driver_cmd_detail.json python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_c4_driver_cmd.json 2> $O/bench_driver.err
-SCA_BENCH_DETAIL=$O/bench_c4_default_detail.json python3 bench.py > $O/bench_c4_default.json 2> $O/bench_default.err
+SCA_BENCH_DETAIL=$O/bench_c4_driver_cmd_detail.json python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_c4_driver_cmd.json 2> $O/bench_driver.err
+SCA_BENCH_DETAIL=$O/bench_c4_default_detail.json python3 bench.py --full > $O/bench_c4_default.json 2> $O/bench_default.err
 SCA_BENCH_DETAIL=$O/r8gs_untraced_detail.json python3 bench.py --workload c4 --emulate-rank-of 8 --nbr grid --vpref straight --steps 100 --warmup 10 > $O/r8gs_untraced.json 2>> $O/err.txt
 cd /tmp && export TMPDIR=/tmp
 prof() {  # name, bench args...
