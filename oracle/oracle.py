@@ -20,8 +20,8 @@ FLAG_AT_GOAL, FLAG_COLLISION, FLAG_TIMEOUT = 1, 2, 4
 
 def build(force=False):
     so = os.path.join(_HERE, 'liboracle.so')
-    src = os.path.join(_HERE, 'sca_oracle.c')
-    if force or not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
+    srcs = [os.path.join(_HERE, f) for f in ('sca_oracle.c', 'sca_dubins_oracle.c', 'Makefile')]
+    if force or not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in srcs):
         subprocess.check_call(['make', '-C', _HERE, '-s'])
     return so
 
@@ -77,6 +77,23 @@ def lib():
         L.orc_env_update.restype = C.c_int
         L.orc_env_update.argtypes = [C.c_int, C.c_int, dp, fp, dp, dp, bp, dp, fp, dp, dp, ip, dp, dp]
         L.orc_num_threads.restype = C.c_int
+        i64p = C.POINTER(C.c_int64)
+        L.orc_dubins_plan.restype = C.c_int
+        L.orc_dubins_plan.argtypes = [dp, dp, C.c_double, C.c_double, C.c_double, dp, C.c_char_p, i64p, C.c_int, dp]
+        L.orc_dubins_plan_batch.restype = C.c_int
+        L.orc_dubins_plan_batch.argtypes = [C.c_int, dp, dp, dp, dp, dp, C.c_int]
+        L.orc_tracker_create.restype = C.c_void_p
+        L.orc_tracker_create.argtypes = [C.c_int, dp, dp, dp, bp, C.c_double, C.c_double, C.c_double, C.c_double]
+        L.orc_tracker_destroy.restype = None
+        L.orc_tracker_destroy.argtypes = [C.c_void_p]
+        L.orc_tracker_set_params.restype = C.c_int
+        L.orc_tracker_set_params.argtypes = [C.c_void_p, dp, dp, dp, dp]
+        L.orc_tracker_vpref.restype = C.c_int
+        L.orc_tracker_vpref.argtypes = [C.c_void_p, dp, fp, dp, bp, dp, dp, C.c_int]
+        L.orc_tracker_replans.restype = C.c_int
+        L.orc_tracker_replans.argtypes = [C.c_void_p, ip]
+        L.orc_tracker_debug.restype = C.c_int
+        L.orc_tracker_debug.argtypes = [C.c_void_p, C.c_int, dp]
         _LIB = L
     return _LIB
 
@@ -186,3 +203,122 @@ def env_update(pos, vel, heading, radius, flags, goal, action, total_dist, max_r
                             _p(action, C.c_float), _d(total_dist), _d(max_run_dist), _p(step_num, C.c_int32),
                             _d(obs_pos), _d(obs_radius))
     return dict(pos=pos, vel=vel, heading=heading, flags=flags, total_dist=total_dist, step_num=step_num, done=bool(done))
+
+
+# ---------------------------------------------------------------------------------------------------- Dubins planner / v_pref tracker
+# (sca_dubins_oracle.c: dubinsmaneuver2d.py / dubinsmaneuver3d.py / scaPolicy.py:92-104,243-338 on the host's libm)
+PLAN_FIELDS = ('length', 'h_r', 'h_t', 'h_p', 'h_q', 'v_r', 'v_t', 'v_p', 'v_q', 'sampling', 'count', 'iters')
+
+
+def dubins_plan(qi, qf, rmin=1.5, pitchlims=(-math.pi / 4, math.pi / 4), ks=()):
+    """dubinsmaneuver3d.dubinsmaneuver3d(qi, qf, Rmin, pitchlims): dict of PLAN_FIELDS + 'mode' (six letters) + 'samples' (the path
+    elements of the indices ks, [len(ks), 5]).  Raises when the reference would not return a plan."""
+    L = lib()
+    qi = np.ascontiguousarray(qi, np.float64)[:5].copy()
+    qf = np.ascontiguousarray(qf, np.float64)[:5].copy()
+    ks = np.ascontiguousarray(ks, np.int64).reshape(-1)
+    out = np.zeros(12)
+    mode = C.create_string_buffer(8)
+    samples = np.zeros((max(len(ks), 1), 5))
+    rc = L.orc_dubins_plan(_d(qi), _d(qf), float(rmin), float(pitchlims[0]), float(pitchlims[1]), _d(out), mode,
+                           _p(ks, C.c_int64), len(ks), _d(samples))
+    if rc != 0:
+        raise RuntimeError(f'orc_dubins_plan status {rc}')
+    r = dict(zip(PLAN_FIELDS, out.tolist()))
+    r['count'], r['iters'] = int(r['count']), int(r['iters'])
+    r['mode'] = mode.value.decode()
+    r['samples'] = samples[:len(ks)]
+    return r
+
+
+def dubins_plan_batch(q, rmin, pitch_lo, pitch_hi, nthreads=0):
+    """Many plans: q [n, 10] = qi[5] | qf[5]; rmin / pitch_lo / pitch_hi scalars or arrays of n.  Returns [n, 16]: PLAN_FIELDS, the two
+    words packed as 65536 c0 + 256 c1 + c2 (the product's debug record's form), the status (0 = a plan the reference would return), 0."""
+    L = lib()
+    q = np.ascontiguousarray(q, np.float64).reshape(-1, 10)
+    n = len(q)
+    r, lo, hi = (np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float64), (n,))) for a in (rmin, pitch_lo, pitch_hi))
+    out = np.zeros((n, 16))
+    L.orc_dubins_plan_batch(n, _d(q), _d(r), _d(lo), _d(hi), _d(out), int(nthreads))
+    return out
+
+
+class Tracker:
+    """The v_pref tracker of SCAPolicy / RVO3dDubinsPolicy, one state per agent (compute_v_pref, scaPolicy.py:264-338)."""
+
+    def __init__(self, goal, goal_heading, pref_speed, zaxis, turning_radius=1.5, pitchlims=(-math.pi / 4, math.pi / 4),
+                 neighbor_dist=10.0):
+        self.L = lib()
+        goal = np.ascontiguousarray(goal, np.float64).reshape(-1, 3)
+        self.n = n = len(goal)
+        gh = np.ascontiguousarray(goal_heading, np.float64).reshape(n, 3)
+        ps = np.ascontiguousarray(np.broadcast_to(np.asarray(pref_speed, np.float64), (n,)))
+        za = np.ascontiguousarray(zaxis, np.uint8).reshape(n)
+        self.h = self.L.orc_tracker_create(n, _d(goal), _d(gh), _d(ps), _p(za, C.c_uint8), float(turning_radius), float(pitchlims[0]),
+                                           float(pitchlims[1]), float(neighbor_dist))
+        if not self.h:
+            raise RuntimeError('orc_tracker_create failed')
+        self.nbr0 = np.full(n, -1.0)           # agent.neighbors[0][1] as the last policy pass left it (-1: empty)
+
+    def set_params(self, neighbor_dist=None, turning_radius=None, pitch_lo=None, pitch_hi=None):
+        """per-agent agent.neighborDist / turning_radius / pitchlims (arrays of n; None = the constructor's value)"""
+        keep = []
+
+        def arr(a):
+            if a is None:
+                return None
+            b = np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float64), (self.n,)))
+            keep.append(b)
+            return _d(b)
+        if self.L.orc_tracker_set_params(self.h, arr(neighbor_dist), arr(turning_radius), arr(pitch_lo), arr(pitch_hi)) != 0:
+            raise RuntimeError('orc_tracker_set_params failed')
+
+    def note_neighbors(self, nbr_valid, nbr_n, nbr_dsq):
+        """agent.neighbors[0] after a policy pass: only the agents whose list the pass recomputed (scaPolicy.py:45,108)"""
+        v = np.asarray(nbr_valid).astype(bool)
+        first = np.where(np.asarray(nbr_n) > 0, np.asarray(nbr_dsq)[:, 0], -1.0)
+        self.nbr0[v] = first[v]
+
+    def note_nbr0(self, nbr0):
+        """the same from the product's compact form (sca_get_nbr0: -2 = list untouched by the pass)"""
+        nbr0 = np.asarray(nbr0)
+        m = nbr0 > -2.0
+        self.nbr0[m] = nbr0[m]
+
+    def vpref(self, pos, vel, heading, active, nthreads=0):
+        """V_des of every active agent (rows of the others: nan).  Raises when an agent met a case where the reference raises or
+        loops forever."""
+        n = self.n
+        pos = np.ascontiguousarray(pos, np.float64).reshape(n, 3)
+        vel = np.ascontiguousarray(vel, np.float32).reshape(n, 3)
+        heading = np.ascontiguousarray(heading, np.float64).reshape(n, 3)
+        active = np.ascontiguousarray(active, np.uint8).reshape(n)
+        out = np.full((n, 3), np.nan)
+        bad = self.L.orc_tracker_vpref(self.h, _d(pos), _p(vel, C.c_float), _d(heading), _p(active, C.c_uint8), _d(self.nbr0), _d(out),
+                                       int(nthreads))
+        if bad != 0:
+            raise RuntimeError(f'oracle tracker: {bad} agents met a case the reference does not survive')
+        return out
+
+    def replans(self):
+        r = np.zeros(self.n, np.int32)
+        self.L.orc_tracker_replans(self.h, _p(r, C.c_int32))
+        return r
+
+    def debug(self, i):
+        """agent i's plan and tracking state in the layout of the product's sca_tracker_debug record"""
+        o = np.zeros(24)
+        if self.L.orc_tracker_debug(self.h, int(i), _d(o)) != 0:
+            raise IndexError(i)
+        return o
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.L.orc_tracker_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -4,8 +4,11 @@
 Two solvers step the same scene side by side:
   A  the product as bench.py's `value` leg runs it: the tracker inside every resident step (k_track_replan / k_replan* /
      k_track beside the kd build, the split solve, ...), state never leaves the device between steps;
-  B  the native HOST tracker (sca_tracker_vpref: glibc's libm, pinned bit for bit to the reference's recorded v_pref,
-     tests/test_tracker.py) feeding sca_set_vpref, one step at a time.
+  B  the native HOST tracker (sca_tracker_vpref: the same source, sca_dubins.hpp, compiled for the host -- on the same restated
+     glibc, sca_glibc_math.h, not on the running libm; pinned bit for bit to the reference's recorded v_pref, tests/test_tracker.py)
+     feeding sca_set_vpref, one step at a time.
+A fault that sca_dubins.hpp or sca_glibc_math.h carries into both builds passes this test; the independent check of the device tracker
+at these sizes is tests/test_gpu_tracker_oracle.py (the oracle's own restatement of the tracker, on the running libm).
 After every step: positions, velocities, headings, flags, the v_pref the pass used and the re-plan counters must be EQUAL.
 The velocities are the metric's `v_new`; B's are the reference's given its v_pref rule (every solver test), so A == B is the
 value leg's max |v_new - v_ref| = 0 on these scenes.  (Round 2 could only say "within 2e-5 on 99.9 % of the steps" and only
