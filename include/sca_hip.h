@@ -11,6 +11,7 @@
  *   sca_set_obstacles             Obstacle list + KDTree.buildObstacleTree    mamp/agents/obstacle.py:5-28, mamp/policies/kdTree.py:158-227
  *   sca_set_state / sca_get_state agent.pos/vel/heading/flags attribute reads  mamp/envs/mampenv.py:34-46
  *   sca_set_vpref                 SCA's Dubins-tracker output fed to intersect mamp/policies/sca/scaPolicy.py:32,264-338
+ *   sca_set_paths                 Agent.path + policy.get_trajectory/now_goal  mamp/agents/agent.py:44, rvo3dPolicy.py:71-85, orca3dPolicy.py:298-312
  *   sca_policy_pass               first loop of MACAEnv._take_action:          mamp/envs/mampenv.py:28-40
  *                                 KDTree.buildAgentTree                        mamp/policies/kdTree.py:56-122
  *                                 computeNeighbors / insert*Neighbor           mamp/policies/sca/scaPolicy.py:107-116, mamp/agents/agent.py:79-124
@@ -107,7 +108,8 @@ enum sca_error {
 void sca_default_params(sca_params *p);                 /* the version-100 entry point: writes the first 56 bytes only (struct_bytes = 0) */
 void sca_default_params_v2(sca_params *p, int32_t struct_bytes);   /* every field that fits into struct_bytes, and struct_bytes itself */
 #define SCA_DEFAULT_PARAMS(p) sca_default_params_v2((p), (int32_t)sizeof(sca_params))
-int sca_version(void);                     /* 102 (100: round 4; 101: dt_nominal appended to sca_params; 102: struct_bytes, sca_default_params_v2) */
+int sca_version(void);                     /* 103 (100: round 4; 101: dt_nominal appended to sca_params; 102: struct_bytes, sca_default_params_v2;
+                                              103: sca_set_paths / sca_get_path_state / sca_set_path_state, SCA_FORM_WAYPOINTS) */
 
 int sca_create(const sca_params *p, int device, int max_agents, int max_obstacles, sca_ctx **out);
 void sca_destroy(sca_ctx *ctx);
@@ -140,6 +142,27 @@ int sca_get_kd_perm(sca_ctx *ctx, int32_t *perm /*n*/);
 int sca_get_kd_tree(sca_ctx *ctx, double *tree_out /*(2n-1)*10*/);
 /* externally computed preferred velocity (SCA / RVO3D+Dubins); mode[i]=1 uses vpref[i], 0 = straight line */
 int sca_set_vpref(sca_ctx *ctx, const double *vpref /*n*3*/, const uint8_t *mode /*n*/);
+
+/* Waypoint lists = Agent.path (agent.py:44), followed as every policy's get_trajectory does at the head of find_next_action
+ * (rvo3dPolicy.py:71-85, srvo3dPolicy.py:71-85, scaPolicy.py:75-89, sca/rvo3dDubinsPolicy.py:73-87: l3norm; orca3dPolicy.py:298-312,
+ * orca3dPolicyOfficial.py:302-316: distance).  Agent i's list is points[3*offsets[i] .. 3*offsets[i+1]) in list order; list.pop() takes its
+ * LAST element.  Every pass, for every agent it serves (not at goal, collided or timed out), before anything reads v_pref (kernel k_waypoint):
+ * empty list -> now_goal = goal; otherwise now_goal = pop() if it is None, then one more pop() if the list is not empty and either
+ * l3norm(pos, now_goal) <= radius or l3norm(now_goal, goal) >= l3norm(pos, goal).  RVO3D / S-RVO3D / ORCA3D / ORCA3D-LP agents that have a
+ * path aim v_pref at now_goal (rvo3dPolicy.py:29,182-196; the reached(goal, pos, 0.2) test that zeroes it stays on the global goal); SCA and
+ * RVO3D+Dubins agents advance their list and keep the tracker's v_pref.
+ *   sca_set_paths       after sca_set_agents (SCA_ERR_STATE before; sca_set_agents clears the lists).  n must be the context's n, offsets[0] == 0,
+ *                       offsets never decrease, every point finite (SCA_ERR_ARG, nothing changed).  Resets every cursor to the full list and
+ *                       now_goal to None.  n == 0 or offsets == NULL: no lists (the passes launch nothing for them).  Under the cell-owner
+ *                       partition SCA_ERR_UNSUPPORTED (path state does not migrate with the agents), as is sca_partition_init with lists set.
+ *                       Contiguous shards (sca_set_shard, sca_comm_init): every rank advances the agents it owns.
+ *   sca_get/set_path_state  remaining[i] = elements still in agent i's list (its first remaining[i]), now_goal[i] = policy.now_goal (NaN x 3:
+ *                       None).  sca_set_state leaves both alone (the reference keeps now_goal on the policy object).  SCA_ERR_STATE without lists.
+ * While lists are set, sca_set_vpref refuses mode 1 for a straight-line agent that has a path (SCA_ERR_ARG), and a pass reports
+ * SCA_FORM_WAYPOINTS. */
+int sca_set_paths(sca_ctx *ctx, int n, const int32_t *offsets /*n+1*/, const double *points /*offsets[n]*3*/);
+int sca_get_path_state(sca_ctx *ctx, int32_t *remaining /*n, nullable*/, double *now_goal /*n*3, nullable*/);
+int sca_set_path_state(sca_ctx *ctx, const int32_t *remaining /*n*/, const double *now_goal /*n*3*/);
 
 /* the hot path ----------------------------------------------------------------------------------- */
 int sca_policy_pass(sca_ctx *ctx, int neighbor_mode);
@@ -244,7 +267,8 @@ int sca_last_exchange_ms(sca_ctx *ctx, float *exchange_ms);
  *   SCA_FORM_SOLVE_FB      k_solve_fb: small shards solve and finish their fallbacks in one launch (no k_fallback launch)
  *   SCA_FORM_ACTION_FB     k_action_fb: shards of up to 16 384 agents run the fallback sweep inside the epilogue's launch (no k_fallback launch)
  *   SCA_FORM_AUTO_TAIL     SCA_NBR_AUTO: the kd query of the listed agents ran inside the pass's grid query (its last workgroup, from the tree the pass's
- *                          build publishes): no k_neighbors_kd_auto launch, no stream wait in front of the solve */
+ *                          build publishes): no k_neighbors_kd_auto launch, no stream wait in front of the solve
+ *   SCA_FORM_WAYPOINTS     k_waypoint ran at the head of the pass (waypoint lists are set: sca_set_paths) */
 #define SCA_FORM_SOLVE_SPLIT 1
 #define SCA_FORM_TRACK_FUSED 2
 #define SCA_FORM_REPLAN_LANE 4
@@ -253,6 +277,7 @@ int sca_last_exchange_ms(sca_ctx *ctx, float *exchange_ms);
 #define SCA_FORM_SOLVE_FB 32
 #define SCA_FORM_ACTION_FB 64
 #define SCA_FORM_AUTO_TAIL 128
+#define SCA_FORM_WAYPOINTS 256
 int sca_last_pass_forms(sca_ctx *ctx, int *forms);
 /* SCA_NBR_AUTO statistics since the last reset: out4 = {AUTO passes, agents the grid query listed for the kd query (sum over the passes), the
  * largest list, passes in which somebody was listed}.  A pass with nobody listed never waits for the kd stream. */

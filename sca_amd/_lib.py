@@ -40,6 +40,9 @@ SIGNATURES = {
     'sca_get_kd_perm': (C.c_int, [C.c_void_p, ip]),
     'sca_get_kd_tree': (C.c_int, [C.c_void_p, dp]),
     'sca_set_vpref': (C.c_int, [C.c_void_p, dp, bp]),
+    'sca_set_paths': (C.c_int, [C.c_void_p, C.c_int, ip, dp]),
+    'sca_get_path_state': (C.c_int, [C.c_void_p, ip, dp]),
+    'sca_set_path_state': (C.c_int, [C.c_void_p, ip, dp]),
     'sca_policy_pass': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_get_actions': (C.c_int, [C.c_void_p, fp]),
     'sca_get_neighbors': (C.c_int, [C.c_void_p, ip, ip, bp, dp, bp]),

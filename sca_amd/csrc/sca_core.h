@@ -229,6 +229,43 @@ SCA_HD V3 straight_v_pref(V3 goal, V3 pos, double pref_speed, bool use_distance)
     if (l3norm(goal, pos) < 0.2) v = zero;                 // util.reached :23
     return trunc5(v);
 }
+// compute_v_pref(self.now_goal, agent) with the agent's waypoint in force (rvo3dPolicy.py:29,182-196; orca3dPolicy.py:49,348-362): the
+// direction and its norm aim at `aim` (policy.now_goal), the reached(..., 0.2) test that zeroes v_pref looks at the GLOBAL goal.  With
+// aim == goal this is straight_v_pref (which the kernels keep calling for agents without a path).
+SCA_HD V3 straight_v_pref2(V3 aim, V3 goal, V3 pos, double pref_speed, bool use_distance) {
+    V3 zero = v3(0, 0, 0);
+    V3 dif = aim - pos;
+    double nrm = use_distance ? distance5(dif, zero) : l3norm(dif, zero);
+    nrm = trunc5(nrm);
+    V3 v = v3(dif.x * pref_speed / nrm, dif.y * pref_speed / nrm, dif.z * pref_speed / nrm);
+    if (l3norm(goal, pos) < 0.2) v = zero;                 // util.reached :23, against agent.goal_global_frame
+    return trunc5(v);
+}
+
+// ---- waypoint lists (Agent.path, agent.py:44) --------------------------------------------------------
+// get_trajectory, the first statement of every policy's find_next_action: rvo3dPolicy.py:71-85, srvo3dPolicy.py:71-85, scaPolicy.py:75-89,
+// sca/rvo3dDubinsPolicy.py:73-87 measure with l3norm, orca3dPolicy.py:298-312 and orca3dPolicyOfficial.py:302-316 with distance()
+// (use_distance).  The list is pts[0 .. rem) in list order; list.pop() takes its LAST element.  now_goal with a NaN x is None (no
+// waypoint taken yet).  update_now_goal_dist is 1.0, so the reach test is against the agent's radius itself.  One call pops at most twice:
+// the first call takes a waypoint into now_goal and may at once replace it.  An empty list makes now_goal the goal -- so the waypoint
+// popped last is aimed at for exactly one pass.
+SCA_HD V3 waypoint_pop(const double *pts, int32_t &rem) {
+    rem--;
+    return v3(pts[3 * rem], pts[3 * rem + 1], pts[3 * rem + 2]);
+}
+SCA_HD V3 waypoint_advance(const double *pts, int32_t &rem, V3 now_goal, V3 pos, V3 goal, double radius, bool use_distance) {
+    if (rem <= 0) return goal;                                                       // `else: self.now_goal = agent.goal_global_frame`
+    if (now_goal.x != now_goal.x) now_goal = waypoint_pop(pts, rem);                 // `if self.now_goal is None` (NaN)
+    const double dis = use_distance ? distance5(pos, now_goal) : l3norm(pos, now_goal);
+    const double dis_goal = use_distance ? distance5(now_goal, goal) : l3norm(now_goal, goal);
+    const double dis_pos = use_distance ? distance5(pos, goal) : l3norm(pos, goal);
+    if (dis <= radius) {                                                             // reached the waypoint
+        if (rem > 0) now_goal = waypoint_pop(pts, rem);
+    } else if (dis_goal >= dis_pos) {                                                // the waypoint lies behind the agent
+        if (rem > 0) now_goal = waypoint_pop(pts, rem);
+    }
+    return now_goal;
+}
 
 // ---- posture constraint (util.py:6-20) -----------------------------------------------------------
 // Returns the clamped cosine; the caller compares it with Params::cos_heading_thr, which is the exact

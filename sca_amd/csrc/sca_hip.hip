@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -302,6 +303,12 @@ struct sca_ctx {
     // multi-GPU exchange inside the library (sca_comm_init): one ncclAllGather of the shard's moved records per step
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_nranks = 1;
+    // waypoint lists (Agent.path, sca_set_paths): while they are set, k_waypoint runs at the head of every pass
+    bool paths_on = false;
+    PathView path{};                    // device CSR + cursors + now_goal (sca_kernels.hip.h)
+    size_t path_pts_cap = 0;            // doubles path.pts holds
+    std::vector<int32_t> h_path_off;    // [n + 1] the CSR offsets as set
+    std::vector<uint8_t> h_path_vpref;  // [n] 1: a straight-line agent with a path -- k_waypoint writes its v_pref (vpref_mode = 1)
 };
 
 #define CHK(ctx, call)                                                                         \
@@ -361,7 +368,8 @@ void sca_default_params_v2(sca_params *p, int32_t struct_bytes) {
     if (has_dt) p->dt_nominal = 0.1;
 }
 void sca_default_params(sca_params *p) { sca_default_params_v2(p, 0); }
-int sca_version(void) { return 102; }   // 102: sca_params.struct_bytes + sca_default_params_v2, selftest codes 11-14, SCA_FORM_ACTION_FB / _AUTO_TAIL
+int sca_version(void) { return 103; }   // 103: sca_set_paths / sca_get_path_state / sca_set_path_state, SCA_FORM_WAYPOINTS
+                                        // 102: sca_params.struct_bytes + sca_default_params_v2, selftest codes 11-14, SCA_FORM_ACTION_FB / _AUTO_TAIL
 
 const char *sca_last_error(const sca_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
@@ -573,6 +581,7 @@ static int launch_tracker(sca_ctx *c, bool from_lists, bool in_pass);
 static int part_free(sca_ctx *c);
 static int part_classify(sca_ctx *c);
 static int agent_params_clear(sca_ctx *c);
+static int paths_clear(sca_ctx *c, bool reset_mode);
 static int tracker_free(sca_ctx *c) {
     if (!c->trk.st) { c->trk_on = false; return 0; }
     CHK(c, hipStreamSynchronize(c->stream));
@@ -903,6 +912,7 @@ void sca_destroy(sca_ctx *c) {
     if (c->comm) { (void)hipStreamSynchronize(c->stream); (void)g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
     (void)tracker_free(c);
     (void)part_free(c);
+    for (void *p : {(void *)c->path.off, (void *)c->path.pts, (void *)c->path.rem, (void *)c->path.now_goal}) if (p) (void)hipFree(p);
     if (c->h_done) { (void)hipHostFree(c->h_done); c->h_done = nullptr; }
     if (c->ap_dev) { (void)hipFree(c->ap_dev); (void)hipFree(c->ap_nd); c->ap_dev = nullptr; c->ap_nd = nullptr; }
     void *ptrs[] = {c->rec_own, c->rec_new_own, d.heading, d.goal, d.pref_speed, d.vpref_ext, d.total_dist, d.max_run_dist,
@@ -1053,6 +1063,7 @@ int sca_set_agents(sca_ctx *c, int n, const double *radius, const double *pref_s
     if (int r = tracker_free(c)) return r;                            // the tracker records belong to the old agent set
     if (int r = agent_params_clear(c)) return r;                      // ... and so do the agents' own solver attributes
     if (int r = part_free(c)) return r;                               // ... and so do the partition's lists
+    if (int r = paths_clear(c, false)) return r;                      // ... and so do the waypoint lists (vpref_mode is reset below)
     if (c->comm && n % c->comm_nranks) { c->err = "agent count must be a multiple of the communicator's rank count"; return SCA_ERR_ARG; }
     c->n = n; c->d.n = n; c->d.shard_begin = 0; c->d.shard_count = n;
     if (c->comm) { c->d.shard_count = n / c->comm_nranks; c->d.shard_begin = c->comm_rank * c->d.shard_count; }
@@ -1200,8 +1211,106 @@ int sca_get_kd_tree(sca_ctx *c, double *tree_out) {
 int sca_set_vpref(sca_ctx *c, const double *vpref, const uint8_t *mode) {
     API_ENTER(c);
     ARG(c, vpref && mode && c->agents_set);
+    if (c->paths_on)
+        for (int i = 0; i < c->n; i++)
+            if (mode[i] && c->h_path_vpref[i]) {
+                c->err = "sca_set_vpref: agent " + std::to_string(i) + " follows a waypoint list (sca_set_paths): its v_pref is its policy's, toward the waypoint";
+                return SCA_ERR_ARG;
+            }
     CHK(c, hipMemcpyAsync(c->d.vpref_ext, vpref, sizeof(double) * 3 * c->n, hipMemcpyHostToDevice, c->stream));
     CHK(c, hipMemcpyAsync(c->d.vpref_mode, mode, c->n, hipMemcpyHostToDevice, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- waypoint lists (Agent.path, agent.py:44; get_trajectory, e.g. rvo3dPolicy.py:71-85) ------------------------------------------------
+// reset_mode: the straight-line agents that had a path take v_pref from their policy's own rule again (k_waypoint set vpref_mode = 1 for them)
+static int paths_clear(sca_ctx *c, bool reset_mode) {
+    if (!c->paths_on) return 0;
+    CHK(c, hipStreamSynchronize(c->stream));
+    if (reset_mode && c->n > 0) {
+        std::vector<uint8_t> mode((size_t)c->n);
+        CHK(c, hipMemcpyAsync(mode.data(), c->d.vpref_mode, c->n, hipMemcpyDeviceToHost, c->stream));
+        CHK(c, hipStreamSynchronize(c->stream));
+        for (int i = 0; i < c->n; i++) if (c->h_path_vpref[i]) mode[i] = 0;
+        CHK(c, hipMemcpyAsync(c->d.vpref_mode, mode.data(), c->n, hipMemcpyHostToDevice, c->stream));
+        CHK(c, hipStreamSynchronize(c->stream));
+    }
+    c->paths_on = false;
+    c->h_path_off.clear(); c->h_path_vpref.clear();
+    return 0;
+}
+int sca_set_paths(sca_ctx *c, int n, const int32_t *offsets, const double *points) {
+    API_ENTER(c);
+    if (!c->agents_set) { c->err = "sca_set_agents first"; return SCA_ERR_STATE; }
+    if (n == 0 || !offsets) return paths_clear(c, true);
+    if (c->part_on) { c->err = "sca_set_paths under the cell-owner partition: path state does not migrate with the agents"; return SCA_ERR_UNSUPPORTED; }
+    if (n != c->n) { c->err = "sca_set_paths: n = " + std::to_string(n) + " is not the agent count " + std::to_string(c->n); return SCA_ERR_ARG; }
+    if (offsets[0] != 0) { c->err = "sca_set_paths: offsets[0] must be 0"; return SCA_ERR_ARG; }
+    for (int i = 0; i < n; i++)
+        if (offsets[i + 1] < offsets[i]) { c->err = "sca_set_paths: offsets decrease at agent " + std::to_string(i); return SCA_ERR_ARG; }
+    const size_t total = (size_t)offsets[n];
+    if (total > 0 && !points) { c->err = "sca_set_paths: points is NULL"; return SCA_ERR_ARG; }
+    for (size_t k = 0; k < 3 * total; k++)
+        if (!std::isfinite(points[k])) { c->err = "sca_set_paths: waypoint " + std::to_string(k / 3) + " is not finite"; return SCA_ERR_ARG; }
+    std::vector<uint8_t> pol((size_t)n);
+    CHK(c, hipStreamSynchronize(c->stream));
+    CHK(c, hipMemcpyAsync(pol.data(), c->d.policy, n, hipMemcpyDeviceToHost, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    if (int r = paths_clear(c, true)) return r;
+    PathView &w = c->path;
+    if (!w.off) {
+        CHK(c, hipMalloc((void **)&w.off, sizeof(int32_t) * ((size_t)c->max_n + 1)));
+        CHK(c, hipMalloc((void **)&w.rem, sizeof(int32_t) * (size_t)c->max_n));
+        CHK(c, hipMalloc((void **)&w.now_goal, sizeof(double) * 3 * (size_t)c->max_n));
+    }
+    if (3 * total > c->path_pts_cap || !w.pts) {
+        if (w.pts) { (void)hipFree((void *)w.pts); w.pts = nullptr; c->path_pts_cap = 0; }
+        CHK(c, hipMalloc((void **)&w.pts, sizeof(double) * std::max<size_t>(3 * total, 3)));
+        c->path_pts_cap = std::max<size_t>(3 * total, 3);
+    }
+    std::vector<int32_t> rem((size_t)n);
+    for (int i = 0; i < n; i++) rem[i] = offsets[i + 1] - offsets[i];
+    const std::vector<double> none(3 * (size_t)n, std::numeric_limits<double>::quiet_NaN());
+    CHK(c, hipMemcpyAsync((void *)w.off, offsets, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream));
+    if (total) CHK(c, hipMemcpyAsync((void *)w.pts, points, sizeof(double) * 3 * total, hipMemcpyHostToDevice, c->stream));
+    CHK(c, hipMemcpyAsync(w.rem, rem.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
+    CHK(c, hipMemcpyAsync(w.now_goal, none.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    c->h_path_off.assign(offsets, offsets + n + 1);
+    c->h_path_vpref.assign((size_t)n, 0);
+    for (int i = 0; i < n; i++)
+        c->h_path_vpref[i] = rem[i] > 0 && pol[i] != SCA_POLICY_SCA && pol[i] != SCA_POLICY_RVO3D_DUBINS;
+    c->paths_on = true;
+    return 0;
+}
+int sca_get_path_state(sca_ctx *c, int32_t *remaining, double *now_goal) {
+    API_ENTER(c);
+    if (!c->paths_on) { c->err = "no waypoint lists (sca_set_paths)"; return SCA_ERR_STATE; }
+    CHK(c, hipStreamSynchronize(c->stream));
+    if (remaining) CHK(c, hipMemcpyAsync(remaining, c->path.rem, sizeof(int32_t) * c->n, hipMemcpyDeviceToHost, c->stream));
+    if (now_goal) CHK(c, hipMemcpyAsync(now_goal, c->path.now_goal, sizeof(double) * 3 * c->n, hipMemcpyDeviceToHost, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+int sca_set_path_state(sca_ctx *c, const int32_t *remaining, const double *now_goal) {
+    API_ENTER(c);
+    if (!c->paths_on) { c->err = "no waypoint lists (sca_set_paths)"; return SCA_ERR_STATE; }
+    ARG(c, remaining && now_goal);
+    const int n = c->n;
+    for (int i = 0; i < n; i++) {
+        if (remaining[i] < 0 || remaining[i] > c->h_path_off[i + 1] - c->h_path_off[i]) {
+            c->err = "sca_set_path_state: remaining[" + std::to_string(i) + "] is outside 0 .. the length of the agent's list"; return SCA_ERR_ARG;
+        }
+        const double *g = now_goal + 3 * (size_t)i;
+        const bool none = std::isnan(g[0]) && std::isnan(g[1]) && std::isnan(g[2]);
+        if (!none && !(std::isfinite(g[0]) && std::isfinite(g[1]) && std::isfinite(g[2]))) {
+            c->err = "sca_set_path_state: now_goal of agent " + std::to_string(i) + " is neither finite nor all NaN (None)"; return SCA_ERR_ARG;
+        }
+    }
+    CHK(c, hipStreamSynchronize(c->stream));
+    CHK(c, hipMemcpyAsync(c->path.rem, remaining, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
+    CHK(c, hipMemcpyAsync(c->path.now_goal, now_goal, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
     CHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -1693,6 +1802,15 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
     //   side: [wait fork] K0 ...... K1 (k_solve_sweep) [join]
     // (round 1 had the re-plans on the side stream: the fork and the join then sat on the critical path, ~40 us per step)
     c->nbr_stream = overlap ? c->trk_stream : c->stream;
+    // waypoint lists: get_trajectory (the head of every find_next_action) on the main stream, in front of the fork below and of the AUTO
+    // build's -- so in front of every prologue site on every stream (k_kd_gather / the grid's first kernel on either stream, k_prep, k_solve*,
+    // track_store).  sca_run_steps records no fork on the previous step's last kernel while paths are set (fork_ready is false here then);
+    // an AUTO build enqueued ahead (aux) computes no prologue.
+    if (c->paths_on) {
+        if (fork_ready) { c->err = "internal: a fork recorded ahead of k_waypoint"; return SCA_ERR_STATE; }
+        if (d.shard_count > 0) hipLaunchKernelGGL(k_waypoint, dim3((d.shard_count + 255) / 256), dim3(256), 0, c->stream, c->d, c->path);
+        c->forms |= SCA_FORM_WAYPOINTS;
+    }
     const unsigned parity_now = (unsigned)c->trk.parity;
     if (overlap) {
         if (!fork_ready) CHK(c, hipEventRecord(c->trk_fork, c->stream));   // (fork_ready: it rode on the previous step's last kernel, sca_run_steps)
@@ -2067,7 +2185,8 @@ static int run_steps_loop(sca_ctx *c, int steps, int neighbor_mode, bool lazy) {
             continue;
         }
         // the next pass's fork (tracker in the pass, its neighbour branch on the side stream) rides on this step's last kernel
-        c->finish_stop = s + 1 < steps && c->ext_stop && c->trk_on && c->trk_in_pass && !c->trk_serial && c->trk_fork ? c->trk_fork : nullptr;
+        // (not while waypoint lists are set: the next pass's k_waypoint must come before its fork)
+        c->finish_stop = s + 1 < steps && c->ext_stop && c->trk_on && c->trk_in_pass && !c->trk_serial && c->trk_fork && !c->paths_on ? c->trk_fork : nullptr;
         const int rf = launch_collide_finish(c, false);
         c->fork_ready = rf == 0 && c->finish_stop != nullptr;
         c->finish_stop = nullptr;
@@ -2250,6 +2369,7 @@ int sca_partition_init(sca_ctx *c, int rank, int nranks, int axis, const double 
     ARG(c, nranks >= 1 && rank >= 0 && rank < nranks && axis >= 0 && axis <= 2 && cap_halo >= 0 && cap_mig >= 0);
     if (!c->agents_set || !c->state_set) { c->err = "sca_set_agents and sca_set_state (the complete state, on every rank) first"; return SCA_ERR_STATE; }
     if (c->comm) { c->err = "sca_partition_init with an active communicator (the all-gather mode)"; return SCA_ERR_STATE; }
+    if (c->paths_on) { c->err = "sca_partition_init with waypoint lists set (sca_set_paths): path state does not migrate with the agents"; return SCA_ERR_UNSUPPORTED; }
     if (int r = part_free(c)) return r;
     const int n = c->n;
     const double inv_cell = grid_inv_cell(c->P.neighbor_dist);

@@ -1791,6 +1791,41 @@ __global__ __launch_bounds__(64) void k_lp(DeviceView d, Params Pctx, const int3
     if (st) atomicOr(&d.status[agent], st);
 }
 
+// Waypoint lists (Agent.path, agent.py:44), set by sca_set_paths: agent i's list is pts[3 * off[i] .. 3 * off[i + 1]) in list order, of
+// which the first rem[i] are still in it; now_goal [n * 3] is policy.now_goal (NaN: None).  Kept out of DeviceView: no other kernel reads it.
+struct PathView {
+    const int32_t *off;      // [n + 1]
+    const double *pts;       // [3 * off[n]]
+    int32_t *rem;            // [n]
+    double *now_goal;        // [n * 3]
+};
+// get_trajectory of the agents this pass serves (mampenv.py:35), one lane per agent, on the pass's main stream in front of everything that
+// reads v_pref.  The straight-line agents that have a path get compute_v_pref(now_goal, agent) through the external channel (vpref_ext,
+// vpref_mode = 1), so every prologue site reads it as it reads a fed v_pref; the tracked agents' lists advance and their v_pref stays the
+// tracker's (scaPolicy.py:26-29 computes v_pref without now_goal).
+__global__ __launch_bounds__(256) void k_waypoint(DeviceView d, PathView w) {
+    const int agent = d.shard_begin + (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (agent >= d.shard_begin + d.shard_count) return;
+    const PubRec me = d.rec[agent];
+    if (me.flags & (FLAG_AT_GOAL | FLAG_COLLISION | FLAG_TIMEOUT)) return;
+    const int pol = d.policy[agent];
+    const bool orca = (pol == POL_ORCA || pol == POL_ORCA_LP);
+    const V3 pA = v3(me.px, me.py, me.pz);
+    const V3 goal = v3(d.goal[agent * 3], d.goal[agent * 3 + 1], d.goal[agent * 3 + 2]);
+    const int o = w.off[agent];
+    const bool has_path = w.off[agent + 1] > o;
+    int32_t rem = w.rem[agent];
+    V3 ng = v3(w.now_goal[agent * 3], w.now_goal[agent * 3 + 1], w.now_goal[agent * 3 + 2]);
+    ng = waypoint_advance(w.pts + 3 * (size_t)o, rem, ng, pA, goal, me.radius, orca);
+    w.rem[agent] = rem;
+    w.now_goal[agent * 3] = ng.x; w.now_goal[agent * 3 + 1] = ng.y; w.now_goal[agent * 3 + 2] = ng.z;
+    if (has_path && pol != POL_SCA && pol != POL_RVO_DUBINS) {
+        const V3 vp = straight_v_pref2(ng, goal, pA, d.pref_speed[agent], orca);
+        d.vpref_ext[agent * 3] = vp.x; d.vpref_ext[agent * 3 + 1] = vp.y; d.vpref_ext[agent * 3 + 2] = vp.z;
+        d.vpref_mode[agent] = 1;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_prep(DeviceView d, Params P) {
     const int agent = blockIdx.x * blockDim.x + threadIdx.x;
     if (agent == 0) *d.fb_count = 0;                                       // start of a pass: empty fallback list

@@ -18,8 +18,9 @@ returning (full tensor, this rank's slice) -- tests drive the same class on CPU 
 
 class ShardedStepper:
     def __init__(self, solver, rank=0, world=1, torch_mod=None, dist_mod=None, mode=0, staged=False, force_exchange=False,
-                 inlib=False, unique_id=None):
-        """staged=True exchanges through host memory (for backends without GPU collectives, e.g. gloo when several
+                 inlib=False, unique_id=None, paths=None):
+        """paths: one waypoint list per agent (Agent.path; solver.set_paths) -- every rank holds all of them and advances its own shard's.
+        staged=True exchanges through host memory (for backends without GPU collectives, e.g. gloo when several
         ranks share one GPU in tests); the default hands the device buffers to the collective directly (RCCL).
         inlib=True: the library's own RCCL communicator (unique_id: the 128 bytes of rank 0's comm_unique_id())."""
         self.staged = staged
@@ -46,6 +47,8 @@ class ShardedStepper:
                 self._setup_exchange()
         else:
             self.begin, self.count = 0, n
+        if paths is not None:
+            solver.set_paths(paths)
 
     def _setup_exchange(self):
         sol = self.sol
@@ -130,10 +133,15 @@ class PartitionedStepper:
     Every rank must hold the complete state when this is constructed (sca_set_state); afterwards a rank's per-agent arrays are
     meaningful for `owned()` only."""
 
-    def __init__(self, solver, rank, world, torch_mod, dist_mod, axis=0, cuts=None, staged=False, cap_halo=0, cap_mig=0, emulate=False):
-        """emulate=True (measurements on one GPU): this rank of `world` alone -- its messages go nowhere and empty ones arrive, so
+    def __init__(self, solver, rank, world, torch_mod, dist_mod, axis=0, cuts=None, staged=False, cap_halo=0, cap_mig=0, emulate=False,
+                 paths=None):
+        """paths: refused (ValueError) unless empty -- waypoint state does not migrate with the agents between slabs (the library refuses
+        sca_partition_init with lists set as well).
+        emulate=True (measurements on one GPU): this rank of `world` alone -- its messages go nowhere and empty ones arrive, so
         the halo copies are gone after the first step and agents that leave are lost; what the rank executes per step is what it
         would execute in company."""
+        if paths is not None and any(len(p) for p in paths):
+            raise ValueError('PartitionedStepper: waypoint lists (Agent.path) are not supported under the cell-owner partition')
         self.emulate = bool(emulate)
         if self.emulate:
             solver.set_shard_emulation(True)

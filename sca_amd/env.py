@@ -21,6 +21,10 @@ Differences that matter:
     is used and `env.dubins_tracker` is False;
   * the solver attributes of agent.py:24-41 -- turning_radius and pitchlims included -- are read off the agents in set_agents and travel per
     agent where the agents differ;
+  * Agent.path (agent.py:44) is followed on the device (k_waypoint, see include/sca_hip.h sca_set_paths): the lists are uploaded by
+    set_agents; `agent.path` then reads the env's mirror (the agent's own list, shortened in place to what the reference's pops leave,
+    refreshed on first read after a step) and `agent.policy.now_goal` the device's now_goal (None before the first pass).  ASSIGNING
+    `agent.path = [...]` after set_agents takes effect at the next step; editing the list in place (append, insert, pop) is NOT tracked;
   * history logging (agent.py:126-147, pandas) and the per-step prints are not reproduced.
 There is no CPU path: constructing the env without a GPU raises.
 """
@@ -40,17 +44,32 @@ class _Policy:
     needs_external_vpref = False
 
     def __init__(self):                      # constructible with no arguments (agent.py:11 `policy()`)
+        self._env = None
+        self._agent_id = None
         self.now_goal = None
         self.type = 'internal'
-        self._env = None
+
+    @property
+    def now_goal(self):
+        """get_trajectory's current target (rvo3dPolicy.py:71-85): with waypoint lists in the env, the device's (None before the first pass)"""
+        env = self._env
+        if env is not None and env._paths_on and self._agent_id is not None:
+            return env._now_goal_of(self._agent_id)
+        return self._now_goal
+
+    @now_goal.setter
+    def now_goal(self, value):
+        self._now_goal = value
 
     def find_next_action(self, dict_comm, agent, kdTree):
         """Single-agent entry point of the reference API.  Runs the batched policy pass of the owning env (cached per
         step) and returns this agent's [vx, vy, vz, speed, d_yaw, d_pitch, d_roll]."""
         if self._env is None:
             raise RuntimeError('policy is not attached to a MACAEnv (call env.set_agents first)')
-        self.now_goal = agent.goal_global_frame          # get_trajectory: agent.path is always empty (scaPolicy.py:89)
-        return self._env._policy_row(agent.id)
+        row = self._env._policy_row(agent.id)
+        if not self._env._paths_on:
+            self.now_goal = agent.goal_global_frame      # get_trajectory with an empty agent.path (scaPolicy.py:89)
+        return row
 
 
 class SCAPolicy(_Policy):
@@ -124,7 +143,7 @@ class Agent:
         self.timeHorizon = 10.0
         self.maxSpeed = 1.0
         self.dt_nominal = DT
-        self.path = []
+        self._path = []
         self._v_pref = np.zeros(3)
         self.is_obstacle = False
         d = float(np.sqrt(((self.initial_pos[:3] - self.goal_pos[:3]) ** 2).sum()))
@@ -180,6 +199,22 @@ class Agent:
         if r is None:
             r = self._row_heading = env._mirror['heading'][self.id]
         return r
+
+    @property
+    def path(self):
+        """agent.path (agent.py:44): the waypoint list get_trajectory pops from the end.  Attached to an env with lists, the list object is
+        shortened in place to what the device's passes have left of it (on first read after a step)."""
+        env = self._env
+        if env is not None and env._paths_on and env._path_stale:
+            env._refresh_paths()
+        return self._path
+
+    @path.setter
+    def path(self, value):
+        self._path = value
+        env = self._env
+        if env is not None:
+            env._path_assigned.add(self.id)               # uploaded in front of the next step
 
     @property
     def total_time(self):
@@ -266,6 +301,10 @@ class MACAEnv:
         self._time_cum = [0.0]          # [s] = seconds of policy wall time per served agent over the first s env steps
         self._active = 0                # agents the next step will serve
         self._vpref_cache = None
+        self._paths_on = False          # waypoint lists on the device (Agent.path)
+        self._path_stale = False        # ... and the host mirrors (agents' lists, _path_ng) behind it
+        self._path_assigned = set()     # agents whose .path was assigned since the last upload
+        self._path_ng = None
 
     def set_agents(self, agents, obstacles=None):
         if obstacles is None:
@@ -322,6 +361,11 @@ class MACAEnv:
             a._env = self
             a._row_pos = a._row_vel = a._row_heading = None        # (row views belong to the mirrors of the env they were made for)
             a.policy._env = self
+            a.policy._agent_id = a.id
+        self._paths_on = False
+        self._path_stale = False
+        self._path_assigned = set(range(n))
+        self._sync_paths()
         self.kdTree = _KdTreeView(self)
         self._row_cache = None
         self._nbr_cache = None
@@ -354,13 +398,51 @@ class MACAEnv:
     total_dist = property(lambda self: self._state('total_dist'))
     step_num = property(lambda self: self._state('step_num'))
 
+    # ---- waypoint lists (Agent.path): uploaded when assigned, mirrored lazily -----------------------------------------------
+    def _refresh_paths(self, skip=()):
+        rem, self._path_ng = self.solver.get_path_state()
+        for i, a in enumerate(self.agents):
+            if i not in skip and len(a._path) > rem[i]:
+                del a._path[int(rem[i]):]                         # what list.pop() from the end has left
+        self._path_stale = False
+
+    def _sync_paths(self):
+        """Uploads the agents' lists when one was assigned since the last upload: the others keep their place and every now_goal its value."""
+        if not self._path_assigned:
+            return
+        assigned, self._path_assigned = self._path_assigned, set()
+        lists = [a._path for a in self.agents]
+        n = len(lists)
+        if self._paths_on:
+            self._refresh_paths(skip=assigned)
+            ng = self._path_ng.copy()
+        else:
+            if not any(len(p) for p in lists):
+                return
+            ng = np.full((n, 3), np.nan)
+            served = self.step_num > 0                             # agents that ran get_trajectory already hold now_goal = goal
+            ng[served] = self.goal[served]
+        self.solver.set_paths([[list(map(float, w[:3])) for w in p] for p in lists])
+        self.solver.set_path_state(np.array([len(p) for p in lists], np.int32), ng)
+        self._paths_on = True
+        self._path_ng = ng
+        self._path_stale = False
+
+    def _now_goal_of(self, i):
+        if self._path_stale:
+            self._refresh_paths()
+        g = self._path_ng[i]
+        return None if np.isnan(g[0]) else g.copy()
+
     # ---- one step = MACAEnv.step (mampenv.py:22-25) ---------------------------------------------------------------------
     def _policy_pass(self):
+        self._sync_paths()
         if self._row_cache is None:
             if self.v_pref_fn is not None and self._ext.any():
                 vp = np.asarray(self.v_pref_fn(self), dtype=np.float64).reshape(len(self.agents), 3)
                 self.solver.set_vpref(vp, self._ext.astype(np.uint8))
             self.solver.policy_pass(self.neighbor_mode)
+            self._path_stale = self._paths_on
             self._row_cache = self.solver.actions()
             self._nbr_cache = None
             if self.v_pref_fn is not None:
@@ -400,6 +482,7 @@ class MACAEnv:
         of _take_action, mampenv.py:27-49) is one resident library call and nothing but the done count comes back: the
         per-agent attributes are read from the device the next time somebody looks at them."""
         import time
+        self._sync_paths()
         t0 = time.perf_counter()
         served = max(1, self._active)
         if self._row_cache is None and self.v_pref_fn is None:
@@ -414,6 +497,7 @@ class MACAEnv:
             self._active = self.solver.active_count()
         self._time_cum.append(self._time_cum[-1] + t_policy / served)
         self._stale = True
+        self._path_stale = self._paths_on
         self._row_cache = None
         self._vpref_cache = None
         return done

@@ -14,6 +14,7 @@ POL_SCA, POL_RVO3D, POL_SRVO3D, POL_ORCA3D, POL_ORCA3D_LP, POL_RVO3D_DUBINS = ra
 FLAG_AT_GOAL, FLAG_COLLISION, FLAG_TIMEOUT = 1, 2, 4
 NBR_KDTREE, NBR_GRID, NBR_KDTREE_HOSTBUILD, NBR_AUTO = 0, 1, 2, 3
 FORM_SOLVE_SPLIT, FORM_TRACK_FUSED, FORM_REPLAN_LANE, FORM_REPLAN_FEW, FORM_LP_LANE, FORM_SOLVE_FB, FORM_ACTION_FB, FORM_AUTO_TAIL = 1, 2, 4, 8, 16, 32, 64, 128   # sca_last_pass_forms
+FORM_WAYPOINTS = 256                                          # k_waypoint ran (waypoint lists are set)
 K = _lib.K
 
 
@@ -136,6 +137,28 @@ class BatchedSolver:
         vpref = _lib.as_d(np.nan_to_num(vpref)).reshape(self.n, 3)
         mode = np.ascontiguousarray(np.broadcast_to(mode, (self.n,)), np.uint8)
         self._chk(self.L.sca_set_vpref(self.ctx, _lib.ptr(vpref, C.c_double), _lib.ptr(mode, C.c_uint8)), 'sca_set_vpref')
+
+    # ---- waypoint lists: Agent.path + policy.now_goal (agent.py:44, get_trajectory e.g. rvo3dPolicy.py:71-85) --------------------
+    def set_paths(self, paths):
+        """One list of [x, y, z] waypoints per agent (list order; the reference pops from the end), or None / [] for no lists at all.
+        Resets every cursor and now_goal (None).  After set_agents."""
+        if paths is None or len(paths) == 0:
+            self._chk(self.L.sca_set_paths(self.ctx, 0, None, None), 'sca_set_paths')
+            return
+        off, pts = paths_csr(paths)
+        self._chk(self.L.sca_set_paths(self.ctx, len(paths), _lib.ptr(off, C.c_int32), _lib.ptr(pts, C.c_double)), 'sca_set_paths')
+
+    def get_path_state(self):
+        """(remaining [n] int32: elements still in each list, now_goal [n, 3]: NaN rows = None)"""
+        rem = np.zeros(self.n, np.int32)
+        ng = np.zeros((self.n, 3))
+        self._chk(self.L.sca_get_path_state(self.ctx, _lib.ptr(rem, C.c_int32), _lib.ptr(ng, C.c_double)), 'sca_get_path_state')
+        return rem, ng
+
+    def set_path_state(self, remaining, now_goal):
+        rem = np.ascontiguousarray(remaining, np.int32).reshape(self.n)
+        ng = _lib.as_d(now_goal).reshape(self.n, 3)
+        self._chk(self.L.sca_set_path_state(self.ctx, _lib.ptr(rem, C.c_int32), _lib.ptr(ng, C.c_double)), 'sca_set_path_state')
 
     # ---- SCA's v_pref tracker on the device (scaPolicy.py:264-338) ---------------------------------------
     def device_tracker_enable(self, goal_heading, turning_radius=1.5, pitchlims=(-math.pi / 4, math.pi / 4), in_pass=True):
@@ -371,6 +394,18 @@ class BatchedSolver:
 
     def comm_destroy(self):
         self._chk(self.L.sca_comm_destroy(self.ctx), 'sca_comm_destroy')
+
+
+def paths_csr(paths):
+    """Per-agent waypoint lists -> (offsets [n + 1] int32, points [total, 3] float64), the form sca_set_paths takes."""
+    lens = [len(p) for p in paths]
+    off = np.zeros(len(paths) + 1, np.int32)
+    off[1:] = np.cumsum(lens)
+    pts = np.zeros((int(off[-1]), 3))
+    for i, p in enumerate(paths):
+        if lens[i]:
+            pts[off[i]:off[i + 1]] = np.asarray(p, dtype=np.float64).reshape(lens[i], 3)
+    return off, pts
 
 
 def zaxis_flags(start, goal):
