@@ -19,6 +19,7 @@
  *                                                                              orca3dPolicy.py:38-120,400-439, orca3dPolicyOfficial.py:37-300
  *   sca_env_update                second loop of _take_action + is_done        mamp/envs/mampenv.py:42-59,61-105
  *   sca_run_steps                 `while ...: env.step(actions)`               run_example/run_sca.py:174-178
+ *   sca_step_host                 _take_action whole, the env owning the state mamp/envs/mampenv.py:27-59
  */
 #ifndef SCA_HIP_H
 #define SCA_HIP_H
@@ -183,6 +184,53 @@ int sca_run_steps(sca_ctx *ctx, int steps, int neighbor_mode);
  * agents on the library's second stream -- the next sca_env_step copes with that as the steps inside sca_run_steps do, and EVERY other
  * entry point that takes the context first puts that stream in front of the context's (so whatever is read between steps is final). */
 int sca_env_step(sca_ctx *ctx, int neighbor_mode, int *active);
+
+/* The same step for a host that OWNS the state (the reference's own mampenv.py stays in charge and calls the library from _take_action,
+ * mampenv.py:27-59): a page-locked state block of the library's that the caller reads and writes in place, and ONE call that steps from it
+ * and into it -- instead of sca_set_state -> sca_policy_pass -> sca_get_actions -> sca_env_update -> sca_get_state (five synchronisations,
+ * every array a pageable copy of its own, the record transposition on one host thread).  Those five calls stay valid and may be mixed with
+ * this one; sca_version() is unchanged (callers detect the feature by the symbol).
+ *   sca_host_state_layout  byte offsets of the nine sections for n agents, in the struct's order, and the block's size: the up-going sections
+ *                       (state, then v_pref) first and contiguous, the down-only action rows last, every section on a 64-byte boundary.  Pure
+ *                       host arithmetic, no GPU.  n <= 0 or a NULL pointer: SCA_ERR_ARG.
+ *   sca_host_state_get  after sca_set_agents (SCA_ERR_STATE before).  The first call allocates one page-locked block sized for sca_create's
+ *                       max_agents, mapped into the device's address space; it lives until sca_destroy and is never reallocated, so a
+ *                       stale pointer is never dangling.  The pointers handed out follow the layout of the CURRENT n: fetch the struct again
+ *                       after a sca_set_agents with another n.  struct_bytes = sizeof(sca_host_state) as the caller compiled it (the sca_params
+ *                       convention): at least the two leading integers, at most this library's struct, else SCA_ERR_ARG; only the pointers that
+ *                       fit are written.  The block starts zeroed.
+ *   sca_step_host       one step of the env loop.  in_mask says what the caller wrote since the last call: SCA_HOST_IN_STATE takes the six in/out
+ *                       arrays (= sca_set_state, total_dist and step_num included; `radius` stays as sca_set_agents put it), SCA_HOST_IN_VPREF
+ *                       takes vpref / vpref_mode (= sca_set_vpref, including its refusal of a non-zero mode for a straight-line agent that follows
+ *                       a waypoint list).  k_host_ingest reads what was written out of the block across the link, one resident step (sca_env_step's),
+ *                       k_host_egress writes the state and the action sections into the block (the caller's v_pref sections are never written),
+ *                       the active count comes down in the same round trip, ONE synchronisation.  (SCA_HOST_STEP_STAGED=1 in the environment of
+ *                       sca_create: a device staging buffer of the block's size instead -- one copy up, the kernels on the copy, two copies down;
+ *                       measured slower at N = 1024, 4096 and 100 000, kept for A/B runs.)  On return the block holds the state after the step and the action rows (the rows of
+ *                       sca_get_actions) the step integrated; *active = sca_env_step's.  in_mask == 0: the host only reads; it writes when it has
+ *                       something to say (teleports, retirements).  Everything is enqueued on the context's current stream (sca_set_stream).
+ *                       SCA_ERR_STATE: no agents; no state yet and no SCA_HOST_IN_STATE; in_mask != 0 before any sca_host_state_get (nothing can
+ *                       have been written); a shard (sca_set_shard with count < n).  SCA_ERR_UNSUPPORTED: a communicator (sca_comm_init), the
+ *                       cell-owner partition (the block is the whole swarm's state on one rank), a neighbor_mode outside sca_neighbor_mode.
+ *                       SCA_ERR_ARG: active == NULL, unknown bits in in_mask.  A refused call has changed nothing. */
+typedef struct sca_host_state {          /* pointers into ONE page-locked allocation of the library's; rows of agent i at index i */
+    int32_t struct_bytes, n;             /* n of the last sca_set_agents */
+    double  *pos;                        /* n*3  in/out */
+    float   *vel;                        /* n*3  in/out */
+    double  *heading;                    /* n*3  in/out */
+    uint8_t *flags;                      /* n    in/out */
+    double  *total_dist;                 /* n    in/out */
+    int32_t *step_num;                   /* n    in/out */
+    double  *vpref;                      /* n*3  in     */
+    uint8_t *vpref_mode;                 /* n    in     */
+    float   *action;                     /* n*7  out: the rows of sca_get_actions */
+} sca_host_state;
+#define SCA_HOST_IN_STATE 1
+#define SCA_HOST_IN_VPREF 2
+int sca_host_state_layout(int n, int64_t *offsets /*9, in the struct's order*/, int64_t *total_bytes);
+int sca_host_state_get(sca_ctx *ctx, sca_host_state *out, int32_t struct_bytes);
+int sca_step_host(sca_ctx *ctx, int neighbor_mode, uint32_t in_mask, int *active);
+
 int sca_synchronize(sca_ctx *ctx);
 /* number of this rank's agents that are not done (at goal, collided or timed out) after the last env update; 0 == the
  * `all(agent.is_run_done)` of MACAEnv.is_done (mampenv.py:51-59).  Synchronises; reports a failed device kd build. */

@@ -23,6 +23,15 @@ class Params(C.Structure):
                 ('max_neighbors', C.c_int32), ('struct_bytes', C.c_int32), ('dt_nominal', C.c_double)]
 
 
+class HostState(C.Structure):
+    """sca_host_state: pointers into the library's page-locked state block (sca_host_state_get), rows of agent i at index i"""
+    _fields_ = [('struct_bytes', C.c_int32), ('n', C.c_int32), ('pos', dp), ('vel', fp), ('heading', dp), ('flags', bp), ('total_dist', dp),
+                ('step_num', ip), ('vpref', dp), ('vpref_mode', bp), ('action', fp)]
+
+
+HOST_IN_STATE, HOST_IN_VPREF = 1, 2                               # SCA_HOST_IN_*
+
+
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against include/sca_hip.h
 SIGNATURES = {
     'sca_default_params': (None, [C.c_void_p]),                   # (version-100 form: 56 bytes)
@@ -51,6 +60,9 @@ SIGNATURES = {
     'sca_env_update': (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     'sca_run_steps': (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     'sca_env_step': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    'sca_host_state_layout': (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'sca_host_state_get': (C.c_int, [C.c_void_p, C.POINTER(HostState), C.c_int32]),
+    'sca_step_host': (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_int)]),
     'sca_synchronize': (C.c_int, [C.c_void_p]),
     'sca_active_count': (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     'sca_set_shard': (C.c_int, [C.c_void_p, C.c_int, C.c_int]),

@@ -538,4 +538,32 @@ SCA_HD uint32_t pack_key(double k_num, int idx) {
     return ((uint32_t)k << 10) | (uint32_t)idx;
 }
 
+// ---- pinned host state block (sca_host_state, include/sca_hip.h) -----------------------------------------
+// The ONE place the block's layout is computed: sca_host_state_layout on the host, k_host_ingest / k_host_egress on the device
+// (sca_hostio.hip.h) and the host-compiled harness of tests/test_host_step_cpu.py all call it.  Sections in the struct's order, rows of
+// agent i at index i (AoS, the arrays agent.pos / vel_global_frame / heading ... of mampenv.py:27-59 make when stacked), every section on
+// a 64-byte boundary: the up-going ones first (state, then v_pref) and contiguous up to that padding -- one copy takes them up --, the
+// down-only action rows last.
+enum HostSection : int { HS_POS = 0, HS_VEL, HS_HEADING, HS_FLAGS, HS_TOTAL_DIST, HS_STEP_NUM, HS_VPREF, HS_VPREF_MODE, HS_ACTION, HS_SECTIONS };
+constexpr int64_t HS_ALIGN = 64;
+struct HostLayout {
+    int64_t off[HS_SECTIONS];
+    int64_t total;
+};
+SCA_HD int64_t host_section_row_bytes(int s) {
+    // pos f64 x 3, vel f32 x 3, heading f64 x 3, flags u8, total_dist f64, step_num i32, vpref f64 x 3, vpref_mode u8, action f32 x 7
+    return s == HS_POS || s == HS_HEADING || s == HS_VPREF ? 24 : s == HS_VEL ? 12 : s == HS_TOTAL_DIST ? 8 : s == HS_STEP_NUM ? 4
+           : s == HS_ACTION ? 28 : 1;
+}
+SCA_HD HostLayout host_state_layout(int n) {
+    HostLayout L;
+    int64_t at = 0;
+    for (int s = 0; s < HS_SECTIONS; s++) {
+        L.off[s] = at;
+        at += (host_section_row_bytes(s) * (int64_t)n + HS_ALIGN - 1) / HS_ALIGN * HS_ALIGN;
+    }
+    L.total = at;
+    return L;
+}
+
 }  // namespace sca

@@ -22,6 +22,7 @@
 #include "sca_dubins.hpp"
 #include "sca_tracker.hip.h"
 #include "sca_partition.hip.h"
+#include "sca_hostio.hip.h"
 
 using namespace sca;
 
@@ -309,6 +310,12 @@ struct sca_ctx {
     size_t path_pts_cap = 0;            // doubles path.pts holds
     std::vector<int32_t> h_path_off;    // [n + 1] the CSR offsets as set
     std::vector<uint8_t> h_path_vpref;  // [n] 1: a straight-line agent with a path -- k_waypoint writes its v_pref (vpref_mode = 1)
+    // pinned host state block (sca_host_state_get / sca_step_host): allocated once for max_n, freed by sca_destroy
+    uint8_t *hs_host = nullptr;         // page-locked, the caller reads and writes it in place
+    bool hs_staged = false;             // SCA_HOST_STEP_STAGED=1 (A/B measurements, tests): the block crosses the link as copies into / out of a device staging buffer
+                                        // and the two kernels work on that.  Default: they read and write the page-locked block across the link themselves
+                                        // -- faster at N = 1024, 4096 and 100 000 by more than the spread (profiles/host_step_cost.json)
+    uint8_t *hs_dev = nullptr;          // ... the staging buffer of the staged form: same size and layout
 };
 
 #define CHK(ctx, call)                                                                         \
@@ -802,6 +809,7 @@ int sca_create(const sca_params *p, int device, int max_agents, int max_obstacle
     c->auto_no_tail = std::getenv("SCA_AUTO_NO_TAIL") != nullptr;
     if (const char *e = std::getenv("SCA_AUTO_TAIL_MAX")) c->auto_tail_max = std::max(0, std::atoi(e));
     if (const char *e = std::getenv("SCA_SOLVE_SPLIT")) c->solve_split = std::atoi(e) != 0;
+    if (const char *e = std::getenv("SCA_HOST_STEP_STAGED")) c->hs_staged = std::atoi(e) != 0;
     if (const char *e = std::getenv("SCA_KD_NOHINT")) c->kd_nohint = std::atoi(e) != 0;
     if (const char *e = std::getenv("SCA_KD_TAIL_LEVEL")) c->kd_tail_level = std::atoi(e);
     if (const char *e = std::getenv("SCA_KD_TOP")) c->kd_top = std::atoi(e) != 0;
@@ -914,6 +922,8 @@ void sca_destroy(sca_ctx *c) {
     (void)part_free(c);
     for (void *p : {(void *)c->path.off, (void *)c->path.pts, (void *)c->path.rem, (void *)c->path.now_goal}) if (p) (void)hipFree(p);
     if (c->h_done) { (void)hipHostFree(c->h_done); c->h_done = nullptr; }
+    if (c->hs_host) { (void)hipHostFree(c->hs_host); c->hs_host = nullptr; }
+    if (c->hs_dev) { (void)hipFree(c->hs_dev); c->hs_dev = nullptr; }
     if (c->ap_dev) { (void)hipFree(c->ap_dev); (void)hipFree(c->ap_nd); c->ap_dev = nullptr; c->ap_nd = nullptr; }
     void *ptrs[] = {c->rec_own, c->rec_new_own, d.heading, d.goal, d.pref_speed, d.vpref_ext, d.total_dist, d.max_run_dist,
                     d.step_num, d.vpref_mode, d.policy, d.zaxis, d.obs, d.obs_sorted, d.awide, d.owide, d.atree, d.aperm, d.otree, d.operm, d.nbr_n,
@@ -2201,6 +2211,103 @@ int sca_env_step(sca_ctx *c, int neighbor_mode, int *active) {
     if (int r = run_steps_guarded(c, 1, neighbor_mode, true)) return r;
     // (the kd build's error word is read from the context's stream: a build still running on kd_stream is seen one step later)
     return read_active(c, active, c->perm_on_device);
+}
+// ---- the env loop with the host as the owner of the state (mampenv.py:27-59): a pinned state block and one call per step ------------------
+int sca_host_state_layout(int n, int64_t *offsets, int64_t *total_bytes) {
+    if (n <= 0 || !offsets || !total_bytes) return SCA_ERR_ARG;
+    const HostLayout L = host_state_layout(n);
+    for (int s = 0; s < HS_SECTIONS; s++) offsets[s] = L.off[s];
+    *total_bytes = L.total;
+    return 0;
+}
+static int host_block_alloc(sca_ctx *c) {
+    if (c->hs_host && (c->hs_dev || !c->hs_staged)) return 0;
+    const size_t bytes = (size_t)host_state_layout(c->max_n).total;       // (every section grows with n: the layout of any n <= max_n fits)
+    if (!c->hs_host) {                                                    // mapped into the device's address space and coherent: the kernels access it
+        CHK(c, hipHostMalloc((void **)&c->hs_host, bytes, hipHostMallocMapped | hipHostMallocCoherent));
+        std::memset(c->hs_host, 0, bytes);
+    }
+    if (c->hs_staged && !c->hs_dev) {
+        CHK(c, hipMalloc((void **)&c->hs_dev, bytes));
+        CHK(c, hipMemsetAsync(c->hs_dev, 0, bytes, c->stream));
+    }
+    return 0;
+}
+int sca_host_state_get(sca_ctx *c, sca_host_state *out, int32_t struct_bytes) {
+    API_ENTER(c);
+    ARG(c, out);
+    if (struct_bytes < (int32_t)offsetof(sca_host_state, pos) || struct_bytes > (int32_t)sizeof(sca_host_state)) {
+        c->err = "sca_host_state_get: struct_bytes must be sizeof(sca_host_state) as the caller compiled it (" +
+                 std::to_string(offsetof(sca_host_state, pos)) + " .. " + std::to_string(sizeof(sca_host_state)) + ")";
+        return SCA_ERR_ARG;
+    }
+    if (!c->agents_set) { c->err = "sca_host_state_get: sca_set_agents first (the block's layout is that of the current n)"; return SCA_ERR_STATE; }
+    if (int r = host_block_alloc(c)) return r;
+    const HostLayout L = host_state_layout(c->n);
+    sca_host_state h;
+    std::memset(&h, 0, sizeof h);
+    h.struct_bytes = struct_bytes; h.n = c->n;
+    uint8_t *b = c->hs_host;
+    h.pos = (double *)(b + L.off[HS_POS]); h.vel = (float *)(b + L.off[HS_VEL]); h.heading = (double *)(b + L.off[HS_HEADING]);
+    h.flags = b + L.off[HS_FLAGS]; h.total_dist = (double *)(b + L.off[HS_TOTAL_DIST]); h.step_num = (int32_t *)(b + L.off[HS_STEP_NUM]);
+    h.vpref = (double *)(b + L.off[HS_VPREF]); h.vpref_mode = b + L.off[HS_VPREF_MODE]; h.action = (float *)(b + L.off[HS_ACTION]);
+    // only the members that fit entirely into the caller's struct
+    size_t fit = offsetof(sca_host_state, pos);
+    while (fit + sizeof(void *) <= (size_t)struct_bytes) fit += sizeof(void *);
+    std::memcpy(out, &h, fit);
+    return 0;
+}
+int sca_step_host(sca_ctx *c, int neighbor_mode, uint32_t in_mask, int *active) {
+    API_ENTER(c);                                                         // (the block replaces or reads state: an AUTO pass's kd stream is joined first)
+    ARG(c, active);
+    ARG(c, (in_mask & ~(uint32_t)(SCA_HOST_IN_STATE | SCA_HOST_IN_VPREF)) == 0);
+    if (!c->agents_set) { c->err = "sca_step_host: sca_set_agents first"; return SCA_ERR_STATE; }
+    if (neighbor_mode < SCA_NBR_KDTREE || neighbor_mode > SCA_NBR_AUTO) { c->err = "sca_step_host: neighbor mode not available in this build"; return SCA_ERR_UNSUPPORTED; }
+    if (c->comm) { c->err = "sca_step_host with an active communicator: the block is the whole swarm's state on one rank (sca_comm_destroy first)"; return SCA_ERR_UNSUPPORTED; }
+    if (c->part_on) { c->err = "sca_step_host under the cell-owner partition: the block is the whole swarm's state on one rank (sca_partition_disable first)"; return SCA_ERR_UNSUPPORTED; }
+    if (c->d.shard_count < c->n) { c->err = "sca_step_host on a shard (sca_set_shard with count < n): the block is the whole swarm's state on one rank"; return SCA_ERR_STATE; }
+    if (!(in_mask & SCA_HOST_IN_STATE) && !c->state_set) { c->err = "sca_step_host: no state yet -- write the block and pass SCA_HOST_IN_STATE (or sca_set_state first)"; return SCA_ERR_STATE; }
+    if (in_mask && !c->hs_host) { c->err = "sca_step_host: sca_host_state_get first -- nothing can have been written to a block nobody has fetched"; return SCA_ERR_STATE; }
+    if (int r = host_block_alloc(c)) return r;
+    const int n = c->n;
+    const HostLayout L = host_state_layout(n);
+    if ((in_mask & SCA_HOST_IN_VPREF) && c->paths_on) {                    // sca_set_vpref's rule, on the block's vpref_mode
+        const uint8_t *mode = c->hs_host + L.off[HS_VPREF_MODE];
+        for (int i = 0; i < n; i++)
+            if (mode[i] && c->h_path_vpref[i]) {
+                c->err = "sca_set_vpref: agent " + std::to_string(i) + " follows a waypoint list (sca_set_paths): its v_pref is its policy's, toward the waypoint";
+                return SCA_ERR_ARG;
+            }
+    }
+    const HostIoDev io{c->d.rec, c->d.heading, c->d.total_dist, c->d.step_num, c->d.vpref_ext, c->d.vpref_mode, c->d.action};
+    const dim3 grid((n + HIO_TILE - 1) / HIO_TILE), block(HIO_TILE);
+    uint8_t *blk = c->hs_staged ? c->hs_dev : c->hs_host;               // what the two kernels read and write
+    if (in_mask) {
+        // (staged form: the up-going sections are contiguous, [pos .. step_num] [vpref, vpref_mode] -- one copy takes what was written)
+        const int64_t lo = (in_mask & SCA_HOST_IN_STATE) ? L.off[HS_POS] : L.off[HS_VPREF];
+        const int64_t hi = (in_mask & SCA_HOST_IN_VPREF) ? L.off[HS_ACTION] : L.off[HS_VPREF];
+        if ((in_mask & SCA_HOST_IN_STATE) && !c->state_set)               // the first state of this agent set: `radius` reaches the device with it
+            CHK(c, hipMemcpyAsync(c->d.rec, c->h_rec.data(), sizeof(PubRec) * n, hipMemcpyHostToDevice, c->stream));
+        if (c->hs_staged) CHK(c, hipMemcpyAsync(c->hs_dev + lo, c->hs_host + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_host_ingest, grid, block, 0, c->stream, io, (const uint8_t *)blk, n, in_mask);
+        CHK(c, hipGetLastError());
+        if (in_mask & SCA_HOST_IN_STATE) {                                 // sca_set_state's bookkeeping (no host mirror of the positions is kept)
+            c->kd_single_hint = 0; c->kd_gen++;
+            c->kd_ahead = false; c->kdq_last = -1; c->auto_backoff = 0;
+            c->h_pos_valid = false;
+            c->near_valid = false;
+            c->state_set = true; c->state_fresh = true;
+        }
+    }
+    if (int r = run_steps_guarded(c, 1, neighbor_mode, false)) return r;  // integrate fused into the pass, k_collide_finish; joins the kd stream
+    HostIoDev out = io;
+    out.rec = c->d.rec;                                                   // (the step swapped the record arrays: the moved ones are current)
+    hipLaunchKernelGGL(k_host_egress, grid, block, 0, c->stream, out, blk, n);
+    CHK(c, hipGetLastError());
+    // (staged form, down: the state sections and the action rows; the caller's v_pref sections between them are never written)
+    if (c->hs_staged) CHK(c, hipMemcpyAsync(c->hs_host + L.off[HS_POS], c->hs_dev + L.off[HS_POS], (size_t)(L.off[HS_VPREF] - L.off[HS_POS]), hipMemcpyDeviceToHost, c->stream));
+    if (c->hs_staged) CHK(c, hipMemcpyAsync(c->hs_host + L.off[HS_ACTION], c->hs_dev + L.off[HS_ACTION], (size_t)(L.total - L.off[HS_ACTION]), hipMemcpyDeviceToHost, c->stream));
+    return read_active(c, active, c->perm_on_device);                     // ... and the count (and the kd build's error word): the call's one synchronisation
 }
 int sca_set_shard_emulation(sca_ctx *c, int on) {
     API_ENTER(c);

@@ -22,6 +22,12 @@ class ScaError(RuntimeError):
     pass
 
 
+class _BlockOwner:
+    """What a view of the host state block holds on to: the solver, whose context owns the page-locked memory."""
+    def __init__(self, solver):
+        self.solver = solver
+
+
 class BatchedSolver:
     def __init__(self, max_agents, max_obstacles=0, device=0, params=None):
         self.L = _lib.lib()
@@ -40,11 +46,13 @@ class BatchedSolver:
             raise ScaError(f'sca_create: {msg} (rc={rc})')
         self.n = 0
         self.m = 0
+        self._host_state = None
 
     def close(self):
         if getattr(self, 'ctx', None):
-            self.L.sca_destroy(self.ctx)
+            self.L.sca_destroy(self.ctx)                          # (frees the host state block: views of it must not be used after close())
             self.ctx = None
+        self._host_state = None
 
     def __del__(self):
         try:
@@ -73,6 +81,7 @@ class BatchedSolver:
         zaxis = np.zeros(n, np.uint8) if zaxis is None else np.ascontiguousarray(zaxis, np.uint8)
         mrd = np.full(n, np.inf) if max_run_dist is None else _lib.as_d(max_run_dist).reshape(n)
         self.n = n
+        self._host_state = None                                   # the block's layout follows n: host_state() fetches it again
         self._chk(self.L.sca_set_agents(self.ctx, n, _lib.ptr(radius, C.c_double), _lib.ptr(pref_speed, C.c_double),
                                         _lib.ptr(goal, C.c_double), _lib.ptr(policy, C.c_uint8),
                                         _lib.ptr(zaxis, C.c_uint8), _lib.ptr(mrd, C.c_double)), 'sca_set_agents')
@@ -214,6 +223,39 @@ class BatchedSolver:
         """One resident step + the agents still running after it (MACAEnv.step in one library call; synchronises)."""
         v = C.c_int(0)
         self._chk(self.L.sca_env_step(self.ctx, int(mode), C.byref(v)), 'sca_env_step')
+        return int(v.value)
+
+    # ---- the env loop with the HOST as the owner of the state (mampenv.py:27-59): pinned state block + one call per step ------------
+    def host_state(self):
+        """The library's page-locked state block as a dict of numpy VIEWS (no copies): pos (n, 3) f64, vel (n, 3) f32, heading (n, 3) f64,
+        flags (n,) u8, total_dist (n,) f64, step_num (n,) i32 -- read and written in place --, vpref (n, 3) f64, vpref_mode (n,) u8 -- written --,
+        action (n, 7) f32 -- read.  Made once per set_agents and cached; the views keep the solver (and with it the block) alive."""
+        if self._host_state is None:
+            h = _lib.HostState()
+            self._chk(self.L.sca_host_state_get(self.ctx, C.byref(h), C.sizeof(h)), 'sca_host_state_get')
+            n = h.n
+            owner = _BlockOwner(self)
+
+            def view(p, ct, dt, shape):
+                count = int(np.prod(shape))
+                buf = (ct * count).from_address(C.addressof(p.contents))
+                buf._sca_owner = owner                            # (numpy keeps `buf` as the array's base: the solver outlives the view)
+                return np.frombuffer(buf, dtype=dt, count=count).reshape(shape)
+            self._host_state = dict(
+                pos=view(h.pos, C.c_double, np.float64, (n, 3)), vel=view(h.vel, C.c_float, np.float32, (n, 3)),
+                heading=view(h.heading, C.c_double, np.float64, (n, 3)), flags=view(h.flags, C.c_uint8, np.uint8, (n,)),
+                total_dist=view(h.total_dist, C.c_double, np.float64, (n,)), step_num=view(h.step_num, C.c_int32, np.int32, (n,)),
+                vpref=view(h.vpref, C.c_double, np.float64, (n, 3)), vpref_mode=view(h.vpref_mode, C.c_uint8, np.uint8, (n,)),
+                action=view(h.action, C.c_float, np.float32, (n, 7)))
+        return self._host_state
+
+    def step_host(self, mode=NBR_KDTREE, state=True, vpref=False):
+        """One env step from the block and into it (sca_step_host): state=True takes the six in/out arrays of host_state() as written,
+        vpref=True takes vpref / vpref_mode; afterwards the block holds the state after the step and the action rows.  Returns the number
+        of agents still running (0 == MACAEnv.is_done)."""
+        v = C.c_int(0)
+        mask = (_lib.HOST_IN_STATE if state else 0) | (_lib.HOST_IN_VPREF if vpref else 0)
+        self._chk(self.L.sca_step_host(self.ctx, int(mode), mask, C.byref(v)), 'sca_step_host')
         return int(v.value)
 
     def synchronize(self):
