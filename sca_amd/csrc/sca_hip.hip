@@ -23,6 +23,7 @@
 #include "sca_tracker.hip.h"
 #include "sca_partition.hip.h"
 #include "sca_hostio.hip.h"
+#include "sca_forms.h"
 
 using namespace sca;
 
@@ -197,16 +198,8 @@ struct sca_ctx {
     bool kd_ev_pending = false;
     unsigned kd_builds = 0;             // device builds so far: the level statistics are read back every 8th
     unsigned kd_gen = 0, kd_ev_gen = 0; // positions replaced from outside (sca_set_state ...): statistics of older trees do not apply
-    bool kd_nohint = false;             // SCA_KD_NOHINT=1: ignore the statistics of earlier builds (diagnostics)
-    int action_fb_max = 0;              // shards up to this many agents run the fallback sweep inside the epilogue's launch (k_action_fb; SCA_ACTION_FB_MAX)
-    int solve_fb_max = 0;               // shards up to this many agents solve and fall back in one launch (SCA_SOLVE_FB_MAX; default: two wavefronts per SIMD)
-    bool kd_top = true;                 // SCA_KD_TOP=0: trees of <= KT_M members through the level passes as well (tests, measurements)
-    int kd_tail_level = -1;             // SCA_KD_TAIL_LEVEL=l: the level at which the tail launch takes over (tuning / tests; -1: from the statistics)
     int kd_single_hint = 0;             // 1 + first level whose nodes all fit one chunk in an earlier build (0: unknown)
     unsigned kd_token = 0;              // launch token of the chained scan (never reused)
-    int solve_split = -1;               // k_solve in two launches (k_solve_sweep beside the re-plans, k_solve_pick4 behind them): -1 when the
-                                        // tracker is overlapped, 0 never, 1 always (SCA_SOLVE_SPLIT; the parity tests run both)
-    int k1_force = -1;                  // K1 variant: -1 choose by shard size, 0 one agent per wavefront, 1 four (k_neighbors_kd4)
     bool perm_on_device = false;        // the live agentIDs permutation is d.aperm (device build) rather than h_perm
     bool agents_set = false, state_set = false;
     bool state_fresh = false;           // flags came from sca_set_state: the next env update checks arrived agents against obstacles once
@@ -233,8 +226,6 @@ struct sca_ctx {
     double *trk_R_pa = nullptr;         // [n] agent.turning_radius (device), for the decision
     uint8_t *trk_cls = nullptr;         // [n] the agent's class (device)
     double *trk_plo_pa = nullptr, *trk_phi_pa = nullptr;   // [n] agent.pitchlims (device): the per-agent form (more than TRK_MAX_CLASSES classes)
-    int auto_div = 8;                   // SCA_NBR_AUTO backs off to the plain kd pass (for 256 passes) once the grid query lists more than 1 / auto_div of the
-                                        // shard for the kd query (SCA_AUTO_BACKOFF_DIV: measurements)
     bool trk_many = false;              // the per-agent form: every re-plan by a wavefront of its own, which reads ITS agent's three values
     double trk_enable_vals[3] = {1.5, 0, 0};   // (turning radius, pitch_lo, pitch_hi) of sca_device_tracker_enable: what "back to one value" restores
     int *trk_host_count = nullptr;      // pinned: the re-plan count of an earlier pass, copied back without ever being waited for
@@ -255,10 +246,9 @@ struct sca_ctx {
     int part_known[2] = {0, 0};          // the last exact counts the host has seen, and how many commits ago
     int part_age = 0, part_copy_age = 0;
     uint8_t *part_scratch[2] = {nullptr, nullptr};   // outgoing messages of a rank that runs alone (sca_run_steps: one rank, or emulation)
-    int cus = 256, simds = 1024;         // the device's compute units / SIMDs (hipDeviceProp): every launch heuristic below is stated in
-                                        // wavefronts per SIMD and scaled with them; the figures were measured on a 256-CU MI355X
+    int cus = 256, simds = 1024;         // the device's compute units / SIMDs (hipDeviceProp)
+    Tunables tun{};                     // every threshold and switch the environment sets (sca_forms.h)
     int kd_rank_capacity = 1 << 30;     // workgroups of k_kd_lv_rank the device holds at once (occupancy x CUs)
-    bool kd_force_ticket = false;
     // SCA_NBR_AUTO: the grid query for everybody, the kd query for the agents it lists; the kd BUILD (the permutation is history: it
     // runs every step) on a stream of its own beside the grid build and query
     hipStream_t kd_stream = nullptr;
@@ -267,15 +257,11 @@ struct sca_ctx {
     int *auto_ticket = nullptr;         // k_neighbors_kd_auto's last-workgroup ticket
     unsigned *auto_busy = nullptr;      // device word, bit 0: somebody is listed for the kd query and it has not answered yet (hipStreamWaitValue32)
     unsigned auto_seq = 0;
-    bool auto_waitvalue = true;         // SCA_AUTO_EVENT_WAIT=1: an event wait behind the kd query instead (the build is then on every pass's path)
+    bool auto_waitvalue = true;         // false once hipStreamWaitValue32 was refused: an event wait behind the kd query instead (the build is then on every pass's path)
     hipEvent_t ev_auto_kdq[4] = {nullptr, nullptr, nullptr, nullptr};   // [seq & 3] behind the kd query of pass seq (a launch on kd_stream) or, in the
                                                          // launch-free form, behind its build's last kernel; the pass two on reuses the list: [(seq - 2) & 3]
     unsigned *auto_sync = nullptr;      // device words of the launch-free form (KdTail): [0] k_kd_block's ticket, [1] the last pass whose tree is complete, [2] the grid query's ticket
-    bool auto_tail_ok = false;          // the tail form is available (with the wait-value form of the pass's wait; SCA_AUTO_NO_TAIL=1, read at sca_create: never)
-    bool auto_no_tail = false;
-    int auto_tail_max = 0;              // ... and taken while the list lengths that come back stay at or below this (SCA_AUTO_TAIL_MAX).  0: while NOBODY is
-                                        // listed -- one workgroup answering even a handful of agents per pass lost against the launch form over a
-                                        // whole c3 episode (3000 steps: 0.172 ms per step at 32, 0.121-0.125 at 8, 0.099-0.101 at 0, 0.104 launch form)
+    bool auto_tail_ok = false;          // the tail form is available (with the wait-value form of the pass's wait; Tunables::auto_no_tail: never)
     unsigned kd_tail_seq = 0;           // the pass whose build was enqueued in the tail form (0: none)
     bool kdq_on_kd_stream[4] = {false, false, false, false};   // [seq & 3]: pass seq's kd query was a launch on kd_stream (its list's next user must wait for it)
     KdTail kd_tail_arg = {};            // what the build being enqueued hands its k_kd_block (seq = 0 outside an AUTO build)
@@ -291,16 +277,10 @@ struct sca_ctx {
     bool auto_ran = false, auto_fits = false;   // the last pass was an AUTO pass / the grid's candidate lists cover the collision reach
     bool kd_ahead = false;              // the kd build of the NEXT pass is already enqueued on kd_stream (sca_run_steps, behind the integrate stage)
     unsigned auto_passes = 0;
-    bool ext_stop = true;               // the fork / join / hand-over events as stop events of the kernels they follow (LAUNCH_REC); SCA_EXT_STOP=0: records
     hipEvent_t action_stop = nullptr;   // sca_run_steps: the event to record behind this pass's k_action (the moved positions), if any
     hipEvent_t finish_stop = nullptr;   // sca_run_steps: the event to record behind the step's last kernel (the next pass's fork), if any
     bool fork_ready = false;            // ... it was: the pass that follows at once does not record its fork
-    int kd_wave_cap = 0;                // largest subtree handed to k_kd_block (SCA_KD_WAVE_CAP: 256 .. 1536); 0: chosen per pass
-    bool trk_group_fuse = true;         // k_track_group (decision + 64-lane search in one launch) for shards of <= TRK_SPEC4_MAX agents; SCA_TRACKER_NOGROUPFUSE=1: never
-    bool trk_fuse = true;               // k_track_replan allowed (SCA_TRACKER_NOFUSE switches it off: A/B measurements, tests)
     unsigned prof_tick = 0;             // with profiling on, every 16th pass carries the event pairs (six records, ~35 us on that pass)
-    bool trk_serial = false;            // SCA_TRACKER_SERIAL=1: everything on one stream (diagnostics)
-    bool trk_quad = true;               // SCA_TRACKER_NOQUAD=1: lane-per-plan kernel only (diagnostics)
     // multi-GPU exchange inside the library (sca_comm_init): one ncclAllGather of the shard's moved records per step
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_nranks = 1;
@@ -312,10 +292,7 @@ struct sca_ctx {
     std::vector<uint8_t> h_path_vpref;  // [n] 1: a straight-line agent with a path -- k_waypoint writes its v_pref (vpref_mode = 1)
     // pinned host state block (sca_host_state_get / sca_step_host): allocated once for max_n, freed by sca_destroy
     uint8_t *hs_host = nullptr;         // page-locked, the caller reads and writes it in place
-    bool hs_staged = false;             // SCA_HOST_STEP_STAGED=1 (A/B measurements, tests): the block crosses the link as copies into / out of a device staging buffer
-                                        // and the two kernels work on that.  Default: they read and write the page-locked block across the link themselves
-                                        // -- faster at N = 1024, 4096 and 100 000 by more than the spread (profiles/host_step_cost.json)
-    uint8_t *hs_dev = nullptr;          // ... the staging buffer of the staged form: same size and layout
+    uint8_t *hs_dev = nullptr;          // the staging buffer of the staged form (Tunables::hs_staged): same size and layout
 };
 
 #define CHK(ctx, call)                                                                         \
@@ -335,7 +312,7 @@ struct sca_ctx {
 // the queue instead of a dispatch and a barrier packet
 #define LAUNCH_REC(ctx, ev, kern, grid, block, stream, ...)                                                            \
     do {                                                                                                               \
-        if ((ctx)->ext_stop) hipExtLaunchKernelGGL(kern, grid, block, 0, stream, nullptr, ev, 0, __VA_ARGS__);         \
+        if ((ctx)->tun.ext_stop) hipExtLaunchKernelGGL(kern, grid, block, 0, stream, nullptr, ev, 0, __VA_ARGS__);         \
         else { hipLaunchKernelGGL(kern, grid, block, 0, stream, __VA_ARGS__); CHK(ctx, hipEventRecord(ev, stream)); }  \
     } while (0)
 // ... with an event only if there is one (`ev` may be null: a plain launch)
@@ -581,10 +558,8 @@ int sca_selftest_dubins_words(int n, const double *alpha, const double *beta, co
     return 0;
 }
 
-// A threshold measured on the 256-CU part (1024 SIMDs), scaled to this device: they are all "so many wavefronts per SIMD".
-static inline int per_simd(const sca_ctx *c, long long at_1024_simds) { return (int)std::min<long long>(INT_MAX, at_1024_simds * c->simds / 1024); }
 // ---- the same tracker on the device (sca_tracker.hip.h) ---------------------------------------------------------------
-static int launch_tracker(sca_ctx *c, bool from_lists, bool in_pass);
+static int launch_tracker(sca_ctx *c, bool from_lists, bool in_pass, int &forms);
 static int part_free(sca_ctx *c);
 static int part_classify(sca_ctx *c);
 static int agent_params_clear(sca_ctx *c);
@@ -667,14 +642,7 @@ int sca_device_tracker_enable(sca_ctx *c, const double *goal_heading, double tur
     c->trk_on = true; c->trk_in_pass = in_pass != 0;
     c->d.trk_nbr0 = c->trk_in_pass ? c->trk.nbr0 : nullptr;
     c->trk_passes = 0;
-    c->trk_serial = getenv("SCA_TRACKER_SERIAL") != nullptr;
-    c->trk_quad = getenv("SCA_TRACKER_NOQUAD") == nullptr;
-    c->trk_group_fuse = getenv("SCA_TRACKER_NOGROUPFUSE") == nullptr;   // k_track_group for shards of <= TRK_SPEC4_MAX agents
-    c->trk_fuse = getenv("SCA_TRACKER_FUSE") != nullptr;          // k_track_replan (no list, hence no ordering by expected length): opt-in since round 3
-    c->trk.mid_max = getenv("SCA_TRK_MID_MAX") ? atoi(getenv("SCA_TRK_MID_MAX")) : per_simd(c, TRK_MID_MAX);
-    c->trk.spec2_max = getenv("SCA_TRK_SPEC2_MAX") ? atoi(getenv("SCA_TRK_SPEC2_MAX")) : per_simd(c, TRK_SPEC2_MAX);
-    c->trk.spec3_max = getenv("SCA_TRK_SPEC3_MAX") ? atoi(getenv("SCA_TRK_SPEC3_MAX")) : per_simd(c, TRK_SPEC3_MAX);
-    c->trk.spec4_max = getenv("SCA_TRK_SPEC4_MAX") ? atoi(getenv("SCA_TRK_SPEC4_MAX")) : per_simd(c, TRK_SPEC4_MAX);
+    tunables_from_env(c->tun, c->simds, TUN_AT_TRACKER);
     return 0;
 }
 // agent.turning_radius / agent.pitchlims per agent (scaPolicy.py:95,272,302 read the agent's own).  Arrays of n, any of them NULL = the value of
@@ -749,7 +717,9 @@ int sca_device_tracker_vpref(sca_ctx *c, const double *nbr0_dsq, double *vpref_o
     API_ENTER(c);
     if (!c->trk_on || !c->state_set) { c->err = "sca_device_tracker_enable and sca_set_state first"; return SCA_ERR_STATE; }
     if (nbr0_dsq) CHK(c, hipMemcpyAsync(c->trk.nbr0, nbr0_dsq, sizeof(double) * c->n, hipMemcpyHostToDevice, c->stream));
-    if (int r = launch_tracker(c, nbr0_dsq == nullptr, false)) return r;
+    int forms = 0;
+    if (int r = launch_tracker(c, nbr0_dsq == nullptr, false, forms)) return r;
+    c->forms |= forms;
     if (vpref_out) CHK(c, hipMemcpyAsync(vpref_out, c->d.vpref_ext, sizeof(double) * 3 * c->n, hipMemcpyDeviceToHost, c->stream));
     CHK(c, hipStreamSynchronize(c->stream));
     return 0;
@@ -804,18 +774,6 @@ int sca_create(const sca_params *p, int device, int max_agents, int max_obstacle
     c->P.range_sq = sca_gm::g_pow2(c->P.neighbor_dist);                 // neighborDist ** 2 (scaPolicy.py:112): glibc's pow, restated
     c->P.cos_heading_thr = cos_threshold(p->max_heading_change);
     c->P_ctx = c->P;
-    if (const char *e = std::getenv("SCA_K1_PACKED")) c->k1_force = std::atoi(e) != 0;    // A/B switch for measurements
-    if (const char *e = std::getenv("SCA_AUTO_BACKOFF_DIV")) c->auto_div = std::min(64, std::max(1, std::atoi(e)));
-    c->auto_no_tail = std::getenv("SCA_AUTO_NO_TAIL") != nullptr;
-    if (const char *e = std::getenv("SCA_AUTO_TAIL_MAX")) c->auto_tail_max = std::max(0, std::atoi(e));
-    if (const char *e = std::getenv("SCA_SOLVE_SPLIT")) c->solve_split = std::atoi(e) != 0;
-    if (const char *e = std::getenv("SCA_HOST_STEP_STAGED")) c->hs_staged = std::atoi(e) != 0;
-    if (const char *e = std::getenv("SCA_KD_NOHINT")) c->kd_nohint = std::atoi(e) != 0;
-    if (const char *e = std::getenv("SCA_KD_TAIL_LEVEL")) c->kd_tail_level = std::atoi(e);
-    if (const char *e = std::getenv("SCA_KD_TOP")) c->kd_top = std::atoi(e) != 0;
-    if (const char *e = std::getenv("SCA_EXT_STOP")) c->ext_stop = std::atoi(e) != 0;
-    if (const char *e = std::getenv("SCA_KD_TICKET")) c->kd_force_ticket = std::atoi(e) != 0;
-    if (const char *e = std::getenv("SCA_KD_WAVE_CAP")) c->kd_wave_cap = std::min(KD_WAVE_CAP, std::max(2 * KD_WAVE_FLOOR, std::atoi(e)));
     int ndev = 0;
     CHK(c, hipGetDeviceCount(&ndev));
     if (ndev <= 0) { c->err = "no HIP device: libsca_hip has no CPU path"; return SCA_ERR_HIP; }
@@ -827,8 +785,7 @@ int sca_create(const sca_params *p, int device, int max_agents, int max_obstacle
         CHK(c, hipGetDeviceProperties(&prop, device));
         c->cus = std::max(1, prop.multiProcessorCount);
         c->simds = 4 * c->cus;
-        c->solve_fb_max = std::getenv("SCA_SOLVE_FB_MAX") ? std::atoi(std::getenv("SCA_SOLVE_FB_MAX")) : per_simd(c, 2048);
-        c->action_fb_max = std::getenv("SCA_ACTION_FB_MAX") ? std::atoi(std::getenv("SCA_ACTION_FB_MAX")) : per_simd(c, 16384);
+        tunables_from_env(c->tun, c->simds, TUN_AT_CREATE);
         int per_cu = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_kd_lv_rank<false>, KD_LV_T, 0) == hipSuccess && per_cu > 0)
             c->kd_rank_capacity = per_cu * c->cus;
@@ -1356,32 +1313,27 @@ static int build_agent_tree(sca_ctx *c) {
 // that finishes every small subtree.  Everything is enqueued on the context's stream; nothing comes back to the host.
 static int build_agent_tree_device(sca_ctx *c, hipStream_t ks, const DeviceView &d) {
     const int n = c->n;
-    // (no size limit: a level with more chunks than the chip holds at once takes its chunks by arrival, k_kd_lv_rank<true>; rounds
-    // 1-2 refused more than 256 CUs x 4 workgroups x KD_CHUNK = 2 097 152 agents, with the CU count as a literal)
+    // poll: the level statistics of an earlier build, if they have arrived (never waited for)
+    if (c->kd_ev_pending && hipEventQuery(c->kd_ev) == hipSuccess) {
+        if (c->kd_ev_gen == c->kd_gen) {
+            int depth = 0;
+            while (depth < KD_MAX_LEVELS && c->kd_host_counts[depth] > 0) depth++;
+            const int *nch = c->kd_host_counts + KD_MAX_LEVELS + 2;
+            int single = depth;
+            while (single > 0 && nch[single - 1] == c->kd_host_counts[single - 1]) single--;
+            c->kd_single_hint = c->kd_host_counts[KD_MAX_LEVELS + 1] ? 0 : single + 1;        // 1-based
+        }                                                                                     // (else stale: positions replaced since)
+        c->kd_ev_pending = false;
+    }
+    // plan (no size limit: a level with more chunks than the chip holds at once takes its chunks by arrival, k_kd_lv_rank<true>)
+    const KdBuildPlan B = plan_kd_build(c->tun, n, c->trk_on && c->trk_in_pass && ks != c->stream, c->kd_single_hint, c->kd.chunk_cap, c->kd_rank_capacity);
+    if (B.top && KT_M / (B.wave_max + 1) >= KT_NODES) { c->err = "k_kd_top: wave_max below its table bound"; return SCA_ERR_STATE; }   // (static_assert'ed unreachable)
+    // enqueue
     if (!c->perm_on_device) {
         CHK(c, hipMemcpyAsync(d.aperm, c->h_perm.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ks));
         c->perm_on_device = true;
     }
-    // size of the subtrees handed to k_kd_block: 1.25 x the average node size of the first level that fits (n / 2^k), so that
-    // the nodes of that level -- all within a few per cent of the average -- are on one side of it
-    // Subtrees of up to 1536 members (one workgroup of 12 wavefronts each) when the build has the chip to itself; up to 1024 when it
-    // runs beside the tracker's re-plans (a side stream): twice as many, smaller workgroups spread over twice as many CUs, each
-    // competing with fewer re-plan wavefronts -- measured at c5 (N = 16 384, 16 subtrees of ~1024 against 32 of ~512): step 0.284
-    // -> 0.268 ms; c3 (no tracker, 4 against 8 subtrees) the other way round: 0.127 against 0.129
-    // a tree of up to KT_M members: its top by one workgroup in LDS (k_kd_top), which is cheap enough per level to go one level
-    // further down than the level passes would -- subtrees of ~512 instead of ~1024 members for k_kd_block
-    // (not beside the tracker's re-plans, whose ~250-register wavefronts sit on every SIMD: a workgroup of sixteen wavefronts and 139 KB
-    // of LDS then waits for room and for issue slots -- measured as a middle tier under the level passes: 60 us instead of 30 at c5)
-    const bool beside = c->trk_on && c->trk_in_pass && ks != c->stream;
-    const bool top = c->kd_top && n <= KT_M && c->kd_tail_level < 0 && !beside;
-    const int cap = c->kd_wave_cap > 0 ? c->kd_wave_cap : (top ? 768 : (beside ? 1024 : KD_WAVE_CAP));
-    int wave_max = (n <= 1024 && cap >= 1024) ? 1024 : cap; // a tree that fits one workgroup: the smaller one if it can
-    if (n > cap) {
-        double sz = (double)n;
-        while (sz > cap / 1.25) sz *= 0.5;
-        wave_max = std::min(cap, std::max(cap / 2 + 1, (int)std::ceil(1.25 * sz)));
-    }
-    c->kd.wave_max = wave_max;
+    c->kd.wave_max = B.wave_max;
     hipEvent_t kb0 = nullptr, kb1 = nullptr;                            // profiling: the build's device time on the stream it runs on, every 16th build
     if (c->profiling && (c->kd_builds & 15u) == 0 && c->pool_kd_used + 2 <= 2 * 1024) {
         for (hipEvent_t *ev : {&kb0, &kb1}) {
@@ -1390,65 +1342,36 @@ static int build_agent_tree_device(sca_ctx *c, hipStream_t ks, const DeviceView 
         }
         CHK(c, hipEventRecord(kb0, ks));
     }
-    if (top && KT_M / (wave_max + 1) >= KT_NODES) { c->err = "k_kd_top: wave_max below its table bound"; return SCA_ERR_STATE; }   // (static_assert'ed unreachable)
     if (c->kd.aux) {                                                    // SCA_NBR_AUTO: the last kernel of the build that reads the record buffer
         LAUNCH_REC(c, c->ev_auto_gather[c->auto_builds & 1u], k_kd_gather, dim3((n + 255) / 256), dim3(256), ks, d, c->kd, c->P);
         c->auto_builds++;
     } else hipLaunchKernelGGL(k_kd_gather, dim3((n + 255) / 256), dim3(256), 0, ks, d, c->kd, c->P);
-    int levels = 0;
-    if (n > wave_max && top) {
-        hipLaunchKernelGGL(k_kd_top, dim3(1), dim3(KT_T), 0, ks, d, c->kd);
-        levels = 1;
-    } else if (n > wave_max) {
-        // Level passes: two launches per level (rank | swap) while the nodes span several chunks, then ONE launch
-        // (k_kd_level_tail) in which every remaining node's workgroup finishes its whole subtree down to wave_max.  Where the
-        // switch happens only sets the speed -- the tail handles any node size and any depth -- so it is taken from the
-        // statistics of an earlier build when they have arrived (the first level whose nodes all fit one chunk), otherwise
-        // from the balanced tree.
-        int first_single = 1;
-        while (((long long)KD_CHUNK << first_single) < n) first_single++;       // n / 2^l <= KD_CHUNK
-        first_single += 1;                                                      // uneven midpoint splits
-        if (c->kd_ev_pending && hipEventQuery(c->kd_ev) == hipSuccess && c->kd_ev_gen != c->kd_gen) c->kd_ev_pending = false;   // stale
-        if (c->kd_ev_pending && hipEventQuery(c->kd_ev) == hipSuccess) {
-            int depth = 0;
-            while (depth < KD_MAX_LEVELS && c->kd_host_counts[depth] > 0) depth++;
-            const int *nch = c->kd_host_counts + KD_MAX_LEVELS + 2;
-            int single = depth;
-            while (single > 0 && nch[single - 1] == c->kd_host_counts[single - 1]) single--;
-            c->kd_single_hint = c->kd_host_counts[KD_MAX_LEVELS + 1] ? 0 : single + 1;        // 1-based
-            c->kd_ev_pending = false;
+    if (B.top && B.levels) hipLaunchKernelGGL(k_kd_top, dim3(1), dim3(KT_T), 0, ks, d, c->kd);
+    if (B.level_passes) {
+        for (int l = 0; l < B.first_single; l++) {
+            if (B.ticket) hipLaunchKernelGGL(k_kd_lv_rank<true>, dim3(B.grid), dim3(KD_LV_T), 0, ks, c->kd, l, ++c->kd_token);
+            else hipLaunchKernelGGL(k_kd_lv_rank<false>, dim3(B.grid), dim3(KD_LV_T), 0, ks, c->kd, l, ++c->kd_token);
+            hipLaunchKernelGGL(k_kd_lv_swap, dim3(B.grid), dim3(KD_LV_T + 64), 0, ks, d, c->kd, l);   // + the bookkeeping wavefront
         }
-        if (c->kd_single_hint > 0 && !c->kd_nohint) first_single = c->kd_single_hint - 1;
-        if (c->kd_tail_level >= 0) first_single = c->kd_tail_level;
-        first_single = std::min(first_single, KD_MAX_LEVELS - 2);
-        levels = first_single + 1;
-        const int grid = std::min(c->kd.chunk_cap, n / KD_CHUNK + n / (wave_max / 2 + 1) + 8);   // >= chunks of any level of n agents (a node of the level passes has > wave_max members... its children > 0)
-        for (int l = 0; l < first_single; l++) {
-            // chunk by arrival once a level can have more chunks than are resident at once (k_kd_lv_rank); SCA_KD_TICKET=1 forces it (tests)
-            if (grid > c->kd_rank_capacity || c->kd_force_ticket)
-                hipLaunchKernelGGL(k_kd_lv_rank<true>, dim3(grid), dim3(KD_LV_T), 0, ks, c->kd, l, ++c->kd_token);
-            else
-                hipLaunchKernelGGL(k_kd_lv_rank<false>, dim3(grid), dim3(KD_LV_T), 0, ks, c->kd, l, ++c->kd_token);
-            hipLaunchKernelGGL(k_kd_lv_swap, dim3(grid), dim3(KD_LV_T + 64), 0, ks, d, c->kd, l);   // + the bookkeeping wavefront
-        }
-        hipLaunchKernelGGL(k_kd_level_tail, dim3(grid), dim3(KD_LV_T), 0, ks, d, c->kd, first_single, ++c->kd_token);
+        hipLaunchKernelGGL(k_kd_level_tail, dim3(B.grid), dim3(KD_LV_T), 0, ks, d, c->kd, B.first_single, ++c->kd_token);
     }
-
-    const int sgrid = std::max(1, std::min(1024, 4 * n / wave_max + 2));
-    // one workgroup per subtree, in LDS: the smallest form that holds wave_max members (two positions per thread)
-    // (LAUNCH_OPT: an AUTO build in the tail form records the pass's kd-query event behind this kernel)
-    if (wave_max <= 256) LAUNCH_OPT(c, c->kd_block_stop, (k_kd_block<256, 128>), dim3(sgrid), dim3(128), ks, d, c->kd, levels, c->kd_tail_arg);
-    else if (wave_max <= 512) LAUNCH_OPT(c, c->kd_block_stop, (k_kd_block<512, 256>), dim3(sgrid), dim3(256), ks, d, c->kd, levels, c->kd_tail_arg);
-    else if (wave_max <= 768) LAUNCH_OPT(c, c->kd_block_stop, (k_kd_block<768, 384>), dim3(sgrid), dim3(384), ks, d, c->kd, levels, c->kd_tail_arg);
-    else if (wave_max <= 1024) LAUNCH_OPT(c, c->kd_block_stop, (k_kd_block<1024, 512>), dim3(sgrid), dim3(512), ks, d, c->kd, levels, c->kd_tail_arg);
-    else if (wave_max <= 1280) LAUNCH_OPT(c, c->kd_block_stop, (k_kd_block<1280, 640>), dim3(sgrid), dim3(640), ks, d, c->kd, levels, c->kd_tail_arg);
-    else LAUNCH_OPT(c, c->kd_block_stop, (k_kd_block<KD_WAVE_CAP, KD_WAVE_CAP / 2>), dim3(sgrid), dim3(KD_WAVE_CAP / 2), ks, d, c->kd, levels, c->kd_tail_arg);
+    // one workgroup per subtree, in LDS (LAUNCH_OPT: an AUTO build in the tail form records the pass's kd-query event behind this kernel)
+#define KD_BLOCK(M) LAUNCH_OPT(c, c->kd_block_stop, (k_kd_block<M, M / 2>), dim3(B.sgrid), dim3(M / 2), ks, d, c->kd, B.levels, c->kd_tail_arg)
+    switch (B.block) {
+    case 256: KD_BLOCK(256); break;
+    case 512: KD_BLOCK(512); break;
+    case 768: KD_BLOCK(768); break;
+    case 1024: KD_BLOCK(1024); break;
+    case 1280: KD_BLOCK(1280); break;
+    default: KD_BLOCK(KD_WAVE_CAP);
+    }
+#undef KD_BLOCK
     CHK(c, hipGetLastError());
     if (kb1) CHK(c, hipEventRecord(kb1, ks));
     // the tree's depth profile changes slowly: one small readback (a copy sits in the stream between the build and K1) every
     // 8th build, every build while no hint exists yet
     c->kd_builds++;
-    if (n > wave_max && !top && !c->kd_ev_pending && (c->kd_single_hint == 0 || (c->kd_builds & 7u) == 0)) {
+    if (B.level_passes && !c->kd_ev_pending && (c->kd_single_hint == 0 || (c->kd_builds & 7u) == 0)) {
         CHK(c, hipMemcpyAsync(c->kd_host_counts, c->kd.counts, sizeof(int) * (2 * KD_MAX_LEVELS + 3), hipMemcpyDeviceToHost, ks));
         CHK(c, hipEventRecord(c->kd_ev, ks));
         c->kd_ev_pending = true;
@@ -1502,45 +1425,22 @@ static int pool_event(sca_ctx *c, hipEvent_t *out) {
 // in_pass = true (a policy pass with the tracker inside): agent.neighbors[0] comes from trk.nbr0, which the previous pass's
 // epilogue saved -- so nothing here reads the neighbour lists, and the neighbour query of this pass may run beside it.
 // in_pass = false (sca_device_tracker_vpref): from the lists as they are (from_lists) or from what the caller uploaded.
-static int launch_tracker(sca_ctx *c, bool from_lists, bool in_pass) {
+// `forms`: the SCA_FORM_* bits of what was launched.
+static int launch_tracker(sca_ctx *c, bool from_lists, bool in_pass, int &forms) {
     const int cnt = c->d.shard_count;
+    // poll: the re-plan count of an earlier pass (copied back on the side stream, never waited for -- except the first count of an episode,
+    // once: a caller that enqueues a long burst of steps runs far ahead of the device, and without it the whole burst would be launched
+    // with the forms of "count unknown")
+    if (c->trk_count_pending && c->trk_last_count < 0) CHK(c, hipEventSynchronize(c->trk_count_ev));
+    if (c->trk_count_pending && hipEventQuery(c->trk_count_ev) == hipSuccess) { c->trk_last_count = c->trk_host_count[0]; c->trk_count_pending = false; }
+    // plan
+    const ReplanPlan R = plan_replans(c->tun, cnt, c->trk_last_count, c->trk_many, in_pass, c->part_on);
+    forms = R.forms;
+    // enqueue
     TrackDev K = c->trk;
     K.nbr0_from_lists = (from_lists && !in_pass) ? 1 : 0;
     if (!in_pass) K.prep = 0;
-    // The device-side count of this pass decides which re-plan kernel does the work: every launched kernel reads it and returns
-    // unless it falls into its range (lo, hi].  Launching all five every pass would cost four empty launches on the critical
-    // path; the count of an earlier pass (copied back on the side stream, never waited for) says
-    // which of them can be left out -- the ranges of those that are launched are widened so that every count is still somebody's
-    // (a count that jumps is then re-planned by a form that is slower for it, never by nobody).  When nearly the whole shard
-    // re-plans in the lane-per-plan form, k_track's list is not worth its launch either: k_track_replan does both.
-    // (the first count of an episode is waited for once: a caller that enqueues a long burst of steps runs far ahead of the device,
-    // and without it the whole burst would be launched with the forms of "count unknown")
-    if (c->trk_count_pending && c->trk_last_count < 0) CHK(c, hipEventSynchronize(c->trk_count_ev));
-    if (c->trk_count_pending && hipEventQuery(c->trk_count_ev) == hipSuccess) { c->trk_last_count = c->trk_host_count[0]; c->trk_count_pending = false; }
-    // forms 0..3: k_replan_group<64 / 32 / 16 / 4> with the natural ranges (up[i - 1], up[i]]; form 4: one lane per plan, above
-    const int lc = c->trk_last_count;
-    const bool known = lc >= 0;
-    int up[5] = {K.spec4_max, K.spec3_max, K.spec2_max, K.mid_max, INT_MAX};
-    for (int i = 1; i < 4; i++) up[i] = std::max(up[i], up[i - 1]);
-    bool want[5];
-    int nwant = 0;
-    for (int i = 0; i < 5; i++) {
-        const long long lower = i ? up[i - 1] : -1, upper = up[i];
-        const bool possible = cnt > lower && upper > lower && (i == 4 || c->trk_quad);
-        want[i] = possible && (!known || (lc > lower - lower / 4 && (i == 4 || lc <= upper + upper / 4)));
-        nwant += want[i];
-    }
-    if (!c->trk_quad) { for (int i = 0; i < 4; i++) want[i] = false; want[4] = true; nwant = 1; }
-    if (nwant == 0) { want[4] = true; nwant = 1; }
-    // the per-agent form (more classes of (turning radius, pitch limits) than launches are worth): a wavefront per plan at ANY count
-    if (c->trk_many) { want[0] = true; for (int i = 1; i < 5; i++) want[i] = false; nwant = 1; }
-    const bool lane = want[4];
-    const bool fused = in_pass && lane && nwant == 1 && c->trk_fuse && !c->part_on && (long long)lc * 4 >= (long long)cnt * 3;
-    // a shard of so few agents that each can have a wavefront (and a SIMD): decision and search in one launch (k_track_group)
-    const bool group_fused = in_pass && (c->trk_quad || c->trk_many) && c->trk_group_fuse && !c->part_on && cnt <= K.spec4_max;
-    if (group_fused) c->forms |= SCA_FORM_TRACK_FUSED | SCA_FORM_REPLAN_FEW;
-    else c->forms |= (fused ? SCA_FORM_TRACK_FUSED : 0) | (nwant > (lane ? 1 : 0) ? SCA_FORM_REPLAN_FEW : 0) | (lane ? SCA_FORM_REPLAN_LANE : 0);
-    if (!fused && !group_fused) hipLaunchKernelGGL(k_track, dim3((cnt + 255) / 256), dim3(256), 0, c->stream, c->d, c->trk_view, K);
+    if (!R.fused && !R.group_fused) hipLaunchKernelGGL(k_track, dim3((cnt + 255) / 256), dim3(256), 0, c->stream, c->d, c->trk_view, K);
     hipStream_t rs = c->stream;
     hipEvent_t t0 = nullptr, t1 = nullptr;
     if (c->profiling && (c->prof_tick & 15u) == 0 && c->pool_trk_used + 2 <= 2 * 4096) {
@@ -1554,81 +1454,30 @@ static int launch_tracker(sca_ctx *c, bool from_lists, bool in_pass) {
     // launches once per class of equal values, each with ITS values in the view's scalars; an agent of another class leaves at once
     const int nclass = c->trk_classes.empty() ? 1 : (int)c->trk_classes.size();
     for (int cl = 0; cl < nclass; cl++) {
-    sca_dubins::TrackView V = c->trk_view;
-    if (!c->trk_classes.empty()) { V.class_id = cl; V.turning_radius = c->trk_classes[cl][0]; V.pitch_lo = c->trk_classes[cl][1]; V.pitch_hi = c->trk_classes[cl][2]; }
-    if (group_fused) {
-        K.lo = -1; K.hi = INT_MAX;
-        hipLaunchKernelGGL(k_track_group, dim3((unsigned)(((long long)cnt * 64 + TRK_GROUP_THREADS - 1) / TRK_GROUP_THREADS)), dim3(TRK_GROUP_THREADS), 0,
-                           rs, c->d, V, K);
-    } else if (fused) {
-        K.lo = -1; K.hi = INT_MAX;
-        hipLaunchKernelGGL(k_track_replan, dim3((cnt + TRK_REPLAN_LANES - 1) / TRK_REPLAN_LANES), dim3(TRK_REPLAN_LANES), 0, rs, c->d,
-                           V, K);
-    } else {
-        int prev_up = -1, left = nwant;
-        for (int i = 0; i < 5; i++) {
-            if (!want[i]) continue;
-            left--;
-            K.lo = prev_up; K.hi = left ? up[i] : INT_MAX;               // the first launched form starts at 0, the last one takes the rest
-            prev_up = up[i];
-            const int top = K.hi == INT_MAX ? cnt : std::min(cnt, up[i]);  // plans this launch must be able to hold
-            if (top <= 0) continue;                                        // (a range moved to nothing by the tuning switches)
+        sca_dubins::TrackView V = c->trk_view;
+        if (!c->trk_classes.empty()) { V.class_id = cl; V.turning_radius = c->trk_classes[cl][0]; V.pitch_lo = c->trk_classes[cl][1]; V.pitch_hi = c->trk_classes[cl][2]; }
+        for (int i = 0; i < R.n; i++) {
+            const ReplanLaunch &L = R.launch[i];
+            K.lo = L.lo; K.hi = L.hi;
             // workgroups of four wavefronts, one per SIMD of a CU: the forms need <= 256 registers, so a SIMD can hold two of
             // their wavefronts, and with one-wavefront workgroups the dispatcher doubles some SIMDs up while others stay empty
-            const dim3 blk(TRK_GROUP_THREADS);
-            const auto blocks = [&](int lanes) { return dim3((unsigned)(((long long)top * lanes + TRK_GROUP_THREADS - 1) / TRK_GROUP_THREADS)); };
-            switch (i) {
-            case 0: hipLaunchKernelGGL(k_replan_group<64>, blocks(64), blk, 0, rs, c->d, V, K); break;
-            case 1: hipLaunchKernelGGL(k_replan_group<32>, blocks(32), blk, 0, rs, c->d, V, K); break;
-            case 2: hipLaunchKernelGGL(k_replan_group<16>, blocks(16), blk, 0, rs, c->d, V, K); break;
-            case 3: hipLaunchKernelGGL(k_replan_group<4>, blocks(4), blk, 0, rs, c->d, V, K); break;
-            default:
-                hipLaunchKernelGGL(k_replan, dim3((cnt + TRK_REPLAN_LANES - 1) / TRK_REPLAN_LANES), dim3(TRK_REPLAN_LANES), 0, rs, c->d,
-                                   V, K);
+            static_assert(TRK_GROUP_THREADS == TRK_REPLAN_LANES, "one workgroup size for every re-plan kernel");
+            const dim3 blk(TRK_GROUP_THREADS), grid((unsigned)(((long long)L.plans * L.lanes + TRK_GROUP_THREADS - 1) / TRK_GROUP_THREADS));
+            switch (L.kernel) {
+            case RP_GROUP64: hipLaunchKernelGGL(k_replan_group<64>, grid, blk, 0, rs, c->d, V, K); break;
+            case RP_GROUP32: hipLaunchKernelGGL(k_replan_group<32>, grid, blk, 0, rs, c->d, V, K); break;
+            case RP_GROUP16: hipLaunchKernelGGL(k_replan_group<16>, grid, blk, 0, rs, c->d, V, K); break;
+            case RP_GROUP4: hipLaunchKernelGGL(k_replan_group<4>, grid, blk, 0, rs, c->d, V, K); break;
+            case RP_LANE: hipLaunchKernelGGL(k_replan, grid, blk, 0, rs, c->d, V, K); break;
+            case RP_TRACK_GROUP: hipLaunchKernelGGL(k_track_group, grid, blk, 0, rs, c->d, V, K); break;
+            default: hipLaunchKernelGGL(k_track_replan, grid, blk, 0, rs, c->d, V, K);
             }
         }
-    }
     }
     if (t1) CHK(c, hipEventRecord(t1, rs));
     CHK(c, hipGetLastError());
     c->trk.parity = (c->trk.parity + 1) & 3;
     return 0;
-}
-
-// K3 form for this pass: one lane per agent (k_lp) once the shard has enough LP agents to fill the chip that way -- measured:
-// 100 000 agents 65 vs 106 us, 4096 agents 23 vs 12 us (a lane alone needs ~12 us for its 16 planes and the LP) --, else the
-// wave-per-agent form inside k_solve.  SCA_LP_FORM=lane|wave forces one (A/B measurements).
-constexpr int LP_LANE_MIN = 16384;              // one lane per LP agent once they fill the chip: 16 agents per SIMD
-static void choose_lp_form(sca_ctx *c, int &lo, int &hi) {
-    if (c->part_on) {
-        // ownership is dynamic: the LP kernels walk all owned agents and skip the others (the share of LP agents decides the form)
-        lo = 0; hi = c->h_lp_list.empty() ? 0 : c->d.shard_count;
-        c->d.lp_kernel = ((long long)c->h_lp_list.size() / std::max(1, c->part_nranks) >= per_simd(c, LP_LANE_MIN)) ? 1 : 0;
-        return;
-    }
-    const auto b = std::lower_bound(c->h_lp_list.begin(), c->h_lp_list.end(), c->d.shard_begin);
-    const auto e = std::lower_bound(c->h_lp_list.begin(), c->h_lp_list.end(), c->d.shard_begin + c->d.shard_count);
-    lo = (int)(b - c->h_lp_list.begin()); hi = (int)(e - c->h_lp_list.begin());
-    const char *f = getenv("SCA_LP_FORM");
-    c->d.lp_kernel = (hi - lo >= per_simd(c, LP_LANE_MIN)) ? 1 : 0;
-    if (f && f[0] == 'l') c->d.lp_kernel = hi > lo ? 1 : 0;
-    if (f && f[0] == 'w') c->d.lp_kernel = 0;
-}
-
-// k_solve as k_solve_sweep (beside the re-plans) + k_solve_pick4 (behind them)?  It pays while the re-plans are the longer
-// branch of the pass: the lane-per-plan kernel takes ~0.2 + 0.235 * (wavefronts per SIMD, rounded up) ms whatever the
-// count inside a round, the neighbour chain grows with the shard.  Measured on the circle (96 % of the agents re-plan per
-// step), shard sizes 24 576 ... 262 144: a gain of 5-10 % of the step up to 61 440 agents in the first round and up to
-// ~114 000 in the second, a loss of 3-7 % elsewhere (the sweep then lengthens the branch that already ends last).
-static bool choose_solve_split(const sca_ctx *c, bool overlap, int cnt) {
-    if (c->solve_split >= 0) return c->solve_split != 0;
-    if (!overlap) return false;
-    const int est = c->trk_last_count >= 0 ? c->trk_last_count : cnt;    // re-plans of a recent pass (all agents before the first readback)
-    if (est <= c->trk.mid_max) return false;      // the many-lanes-per-plan forms: short re-plans, nothing to hide behind (measured equal
-                                                  // with and without at 18 000 .. 30 000 agents)
-    const int per_round = 64 * c->simds;          // plans of the lane-per-plan kernel that are one wavefront per SIMD
-    const int rounds = (est + per_round - 1) / per_round;
-    return rounds == 1 ? cnt <= per_simd(c, 61440) : (rounds == 2 ? cnt <= per_simd(c, 114688) : false);
 }
 
 // SCA_NBR_AUTO's resources, on first use
@@ -1671,9 +1520,8 @@ static int auto_prepare(sca_ctx *c) {
     for (hipEvent_t &e : c->ev_auto_gather) CHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     for (hipEvent_t &e : c->ev_auto_kdq) CHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     c->auto_seq = 0; c->auto_builds = 0;
-    c->auto_waitvalue = getenv("SCA_AUTO_EVENT_WAIT") == nullptr;
-    c->auto_tail_ok = false;
-    c->auto_tail_ok = c->auto_waitvalue && !c->auto_no_tail;
+    c->auto_waitvalue = true;
+    c->auto_tail_ok = !c->tun.auto_no_tail;
     c->kd_tail_seq = 0;
 
     CHK(c, hipHostMalloc((void **)&c->kdq_host, sizeof(int)));
@@ -1699,7 +1547,7 @@ static int auto_enqueue_kd_build(sca_ctx *c, hipEvent_t after, const PubRec *pos
     const unsigned seq = c->auto_seq + 1;
     c->kd_tail_arg = KdTail{};
     c->kd_block_stop = nullptr;
-    if (c->auto_tail_ok && c->auto_waitvalue && seq != 0 && c->kdq_last >= 0 && c->kdq_last <= c->auto_tail_max) {
+    if (auto_tail_form(c->auto_tail_ok, c->auto_waitvalue, seq, c->kdq_last, c->tun.auto_tail_max)) {
         // (the list of this parity was last read by the kd query of two passes ago, whose event slot is about to be recorded anew: the
         // pass's stream waits for it HERE instead of in front of its grid build)
         // (... if that query was a launch on kd_stream; in the launch-free form it ran inside the pass's own grid query, on this stream)
@@ -1730,11 +1578,6 @@ static int auto_join(sca_ctx *c) {
     c->auto_unjoined = false;
     return 0;
 }
-// will the next pass of an SCA_NBR_AUTO run be an AUTO pass (and not a plain kd pass)?  Decides whether its tree may be built ahead.
-static bool auto_next(const sca_ctx *c) {
-    return c->auto_fits && c->auto_backoff == 0 && !c->part_on && !(c->trk_on && c->trk_in_pass) &&
-           !(c->kdq_last >= 0 && (long long)c->kdq_last * c->auto_div > (long long)c->d.shard_count);
-}
 
 static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) {
     const bool fork_ready = c->fork_ready;
@@ -1742,46 +1585,47 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
 #ifdef SCA_TIMELINE
     c->d.tl_step++;
 #endif
-    // SCA_NBR_AUTO resolves to a plain kd pass where it cannot help (the cell-owner partition has its own structures; the grid's
-    // candidate lists need the collision reach inside one cell) or where the grid keeps listing a large part of the swarm for the kd
-    // query anyway (a lattice of identical cells: ties everywhere) -- it is tried again every 256 passes
+    // the tracker's re-plans overlap the device kd build and the neighbour query; the per-agent prologue (which reads
+    // v_pref) of the tracker's agents then moves from k_kd_gather to the tracker's kernels (track_store)
+    const bool tracked = c->trk_on && c->trk_in_pass;
+    // SCA_NBR_AUTO: an AUTO pass, or a plain kd pass where that cannot help (plan_auto; the cell-owner partition has its own structures)
     bool auto_mode = false;
+    int kdq_blocks = KDQ_BLOCKS;
     if (mode == SCA_NBR_AUTO) {
         double ar, orr;
         collide_reach(c, ar, orr);
         const bool fits = c->max_radius + ar <= c->P.neighbor_dist && c->max_radius + orr <= c->P.neighbor_dist;
         if (c->part_on) { c->err = "the cell-owner partition is a mode of SCA_NBR_GRID"; return SCA_ERR_UNSUPPORTED; }
         if (int r = auto_prepare(c)) return r;
-        if (c->kdq_pending && hipEventQuery(c->ev_auto_cnt) == hipSuccess) { c->kdq_last = c->kdq_host[0]; c->kdq_pending = false; }
-        // (a tree built ahead for this pass -- sca_run_steps, see there -- makes it an AUTO pass whatever the counts say: the build
-        // must not run twice; sca_run_steps only builds ahead when auto_next() holds)
-        if (!c->kd_ahead && c->auto_backoff == 0 && c->kdq_last >= 0 && (long long)c->kdq_last * c->auto_div > (long long)c->d.shard_count) { c->auto_backoff = 256; c->kdq_last = -1; }
-        // (a pass with the tracker inside runs its whole neighbour branch beside the re-plans already: nothing to gain, a grid build to lose)
-        const bool tracked_pass = c->trk_on && c->trk_in_pass;
-        if (!c->kd_ahead && (!fits || tracked_pass || c->auto_backoff > 0)) {
-            if (c->auto_backoff > 0) c->auto_backoff--;
-            mode = SCA_NBR_KDTREE;
-        } else auto_mode = true;
+        if (c->kdq_pending && hipEventQuery(c->ev_auto_cnt) == hipSuccess) { c->kdq_last = c->kdq_host[0]; c->kdq_pending = false; }   // poll
+        // (sca_run_steps only builds ahead when auto_next() holds)
+        const AutoPlan A = plan_auto(fits, tracked, c->kd_ahead, c->kdq_last, c->tun.auto_div, c->auto_backoff, c->d.shard_count);
+        c->auto_backoff = A.auto_backoff; c->kdq_last = A.kdq_last; kdq_blocks = A.kdq_blocks;
+        auto_mode = A.auto_pass;
+        if (!auto_mode) mode = SCA_NBR_KDTREE;
         c->auto_fits = fits;
     }
     const bool kd_prebuilt = auto_mode && c->kd_ahead;
     c->kd_ahead = false;
     c->auto_ran = auto_mode;
     if (!auto_mode) { if (int r = auto_join(c)) return r; }            // (a pass that builds its tree in place: kd_stream must be through)
-    int lp_lo = 0, lp_hi = 0;
-    choose_lp_form(c, lp_lo, lp_hi);
     const DeviceView &d = c->d;
+    const int cnt = d.shard_count;
+    // the shard's LP agents: [lp_lo, lp_hi) of lp_ids (under the partition ownership is dynamic: the LP kernels walk all owned agents and skip the others)
+    int lp_lo = 0, lp_hi = c->h_lp_list.empty() ? 0 : cnt;
     const int32_t *lp_ids = c->part_on ? d.own : c->lp_list;
-    // the tracker's re-plans overlap the device kd build and the neighbour query; the per-agent prologue (which reads
-    // v_pref) of the tracker's agents then moves from k_kd_gather to the tracker's kernels (track_store)
-    const bool tracked = c->trk_on && c->trk_in_pass;
-    const bool overlap = tracked && (mode == SCA_NBR_KDTREE || mode == SCA_NBR_GRID || auto_mode) && !c->trk_serial;
-    // k_solve's v_pref-independent half right behind the neighbour query, i.e. beside the re-plans when they are overlapped
-    bool split = choose_solve_split(c, overlap, d.shard_count);
-    // k_solve that finishes its own fallbacks (k_solve_fb): while all the shard's wavefronts are resident at once even at the fallback
-    // sweep's 252 registers (two per SIMD), and nobody else feeds the fallback list (k_lp does)
-    const bool solve_fb = !split && lp_hi == lp_lo && !c->part_on && d.shard_count <= c->solve_fb_max;
-    if (split && !c->d.sw_slot) {
+    if (!c->part_on) {
+        lp_lo = (int)(std::lower_bound(c->h_lp_list.begin(), c->h_lp_list.end(), d.shard_begin) - c->h_lp_list.begin());
+        lp_hi = (int)(std::lower_bound(c->h_lp_list.begin(), c->h_lp_list.end(), d.shard_begin + cnt) - c->h_lp_list.begin());
+    }
+    const bool overlap = tracked && (mode == SCA_NBR_KDTREE || mode == SCA_NBR_GRID || auto_mode);
+    // plan: K1's form, k_solve's (its v_pref-independent half right behind the neighbour query, i.e. beside the re-plans when they are
+    // overlapped; or the form that finishes its own fallbacks), K3's and the epilogue's
+    const auto plan = [&](bool no_scratch) {
+        return plan_solve(c->tun, c->simds, cnt, c->part_on, c->part_nranks, (long long)c->h_lp_list.size(), lp_hi - lp_lo, overlap, c->trk_last_count, no_scratch);
+    };
+    SolvePlan S = plan(false);
+    if (S.split && !c->d.sw_slot) {
         // scratch of the two-launch solve (cones + survivor lists, ~2 KB per agent): all three buffers or none, and a pass that
         // cannot have them runs the one-launch k_solve instead of failing
         const size_t N = (size_t)c->max_n;
@@ -1790,10 +1634,11 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
                         hipMalloc((void **)&b, sizeof(uint16_t) * N * 512) == hipSuccess &&
                         hipMalloc((void **)&e, sizeof(int32_t) * N) == hipSuccess;
         if (ok) { c->d.sw_slot = a; c->d.sw_surv = b; c->d.sw_n = e; }
-        else { (void)hipGetLastError(); if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (e) (void)hipFree(e); split = false; }
+        else { (void)hipGetLastError(); if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (e) (void)hipFree(e); S = plan(true); }
     }
-    c->forms = (split ? SCA_FORM_SOLVE_SPLIT : 0);
-    if (split && lp_hi > lp_lo) c->d.lp_kernel = 1;                     // k_solve_pick4 carries no LP: its agents go to k_lp
+    const bool split = S.split, solve_fb = S.solve_fb;
+    c->d.lp_kernel = S.lp_kernel;
+    int forms = S.forms | (c->paths_on ? SCA_FORM_WAYPOINTS : 0);     // (the waypoint bit is state, not a choice)
     c->kd.skip_prep = overlap ? 1 : 0;
     c->grid.skip_prep = overlap ? 1 : 0;
     if (mode == SCA_NBR_GRID) {
@@ -1810,7 +1655,6 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
     // saved, not from the lists K1 overwrites -- run beside them on trk_stream:
     //   main: [fork] k_track re-plans (or k_track_replan) ........ [wait join] k_solve / k_solve_pick4 ...
     //   side: [wait fork] K0 ...... K1 (k_solve_sweep) [join]
-    // (round 1 had the re-plans on the side stream: the fork and the join then sat on the critical path, ~40 us per step)
     c->nbr_stream = overlap ? c->trk_stream : c->stream;
     // waypoint lists: get_trajectory (the head of every find_next_action) on the main stream, in front of the fork below and of the AUTO
     // build's -- so in front of every prologue site on every stream (k_kd_gather / the grid's first kernel on either stream, k_prep, k_solve*,
@@ -1819,7 +1663,6 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
     if (c->paths_on) {
         if (fork_ready) { c->err = "internal: a fork recorded ahead of k_waypoint"; return SCA_ERR_STATE; }
         if (d.shard_count > 0) hipLaunchKernelGGL(k_waypoint, dim3((d.shard_count + 255) / 256), dim3(256), 0, c->stream, c->d, c->path);
-        c->forms |= SCA_FORM_WAYPOINTS;
     }
     const unsigned parity_now = (unsigned)c->trk.parity;
     if (overlap) {
@@ -1833,10 +1676,10 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
     }
     c->trk.prep = overlap ? 1 : 0;
     c->trk.P = c->P;
-    if (tracked) { if (int r = launch_tracker(c, true, true)) return r; }
+    if (tracked) { int f = 0; if (int r = launch_tracker(c, true, true, f)) return r; forms |= f; }
     c->nbr_mode = auto_mode ? (int)SCA_NBR_GRID : mode;               // (what K4's fallback looks into: the grid in an AUTO pass)
     if (auto_mode) {
-        c->d.kdq_cap = std::max(1, c->d.shard_count / c->auto_div);
+        c->d.kdq_cap = std::max(1, c->d.shard_count / c->tun.auto_div);
         {   // this pass's list (the previous pass's kd query may still be looking at the other one's length)
             const unsigned par = (c->auto_seq + 1) & 1u;
             c->d.kdq_list = c->kdq_list + (size_t)par * c->max_n;
@@ -1858,7 +1701,6 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
         if (int r = build_agent_tree(c)) return r;
         hipLaunchKernelGGL(k_prep, dim3((c->n + 255) / 256), dim3(256), 0, c->stream, c->d, c->P);
     } else { c->err = "neighbor mode not available in this build"; return SCA_ERR_UNSUPPORTED; }
-    const int cnt = d.shard_count;
     hipStream_t ns = c->nbr_stream;
     hipEvent_t e0 = c->ev[0], e1 = c->ev[1], e2 = c->ev[2], e3 = c->ev[3];
     const bool prof = !timed && c->profiling && (c->prof_tick++ & 15u) == 0 && c->pool_used + 4 <= 4 * 4096;
@@ -1866,65 +1708,53 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
     if (timed || prof) CHK(c, hipEventRecord(e0, ns));
     double agent_reach, obs_reach;
     collide_reach(c, agent_reach, obs_reach);
-    // packed K1 (4 agents per wavefront) wins once the shard fills the chip (measured: 2.3x at 16k agents, equal at 6000);
-    // below that the one-agent-per-wave form with its record stack has the shorter critical path (4096 random: 30 % faster)
-    const bool packed = c->k1_force < 0 ? cnt >= per_simd(c, 6144) : c->k1_force != 0;   // four agents per wavefront once that still fills the SIMDs
     // (overlapped: the join rides on the side stream's last kernel -- the neighbour query, or the sweep behind it)
-    const hipEvent_t k1_stop = overlap && !split && c->ext_stop ? c->trk_join : nullptr;
-    const hipEvent_t sweep_stop = overlap && split && c->ext_stop ? c->trk_join : nullptr;
+    const hipEvent_t k1_stop = overlap && !split && c->tun.ext_stop ? c->trk_join : nullptr;
+    const hipEvent_t sweep_stop = overlap && split && c->tun.ext_stop ? c->trk_join : nullptr;
     const bool obs = d.m > 0;                                           // (scenes without obstacles: the K1 forms without the obstacle phase, see neighbors_one)
+    // (the launch-free form: the grid query's last workgroup answers whoever is listed, from the tree its pass's build publishes)
+    const bool tail = auto_mode && c->kd_tail_seq == c->auto_seq + 1 && c->kd_tail_seq != 0;
+    const dim3 k1p_grid((cnt + K1P_WAVES * K1P_APW - 1) / (K1P_WAVES * K1P_APW)), k1p_block(K1P_WAVES * 64);
     if (auto_mode) {
-        const int per_block = K1P_WAVES * K1P_APW;
-        // (the launch-free form: the grid query's last workgroup answers whoever is listed, from the tree its pass's build publishes; d is c->d)
-        c->d.auto_sync = c->kd_tail_seq == c->auto_seq + 1 && c->kd_tail_seq != 0 ? c->auto_sync : nullptr;
+        c->d.auto_sync = tail ? c->auto_sync : nullptr;                 // (d is c->d)
         c->d.auto_pass_seq = c->auto_seq + 1;
         c->d.auto_err = c->kd.counts + KD_MAX_LEVELS + 1;
-        if (obs) LAUNCH_REC(c, c->ev_auto_k1g, (k_neighbors_grid<true, true>), dim3((cnt + per_block - 1) / per_block), dim3(K1P_WAVES * 64), ns, d, c->grid,
-                            c->P, agent_reach, obs_reach, c->max_radius);
-        else LAUNCH_REC(c, c->ev_auto_k1g, (k_neighbors_grid<true, false>), dim3((cnt + per_block - 1) / per_block), dim3(K1P_WAVES * 64), ns, d, c->grid,
-                        c->P, agent_reach, obs_reach, c->max_radius);
+        const auto k1 = obs ? k_neighbors_grid<true, true> : k_neighbors_grid<true, false>;
+        LAUNCH_REC(c, c->ev_auto_k1g, k1, k1p_grid, k1p_block, ns, d, c->grid, c->P, agent_reach, obs_reach, c->max_radius);
     } else if (mode == SCA_NBR_GRID) {
-        const int per_block = K1P_WAVES * K1P_APW;
-        if (obs) LAUNCH_OPT(c, k1_stop, (k_neighbors_grid<false, true>), dim3((cnt + per_block - 1) / per_block), dim3(K1P_WAVES * 64), ns, d, c->grid,
-                            c->P, agent_reach, obs_reach, c->max_radius);
-        else LAUNCH_OPT(c, k1_stop, (k_neighbors_grid<false, false>), dim3((cnt + per_block - 1) / per_block), dim3(K1P_WAVES * 64), ns, d, c->grid,
-                        c->P, agent_reach, obs_reach, c->max_radius);
-    } else if (packed) {
-        const int per_block = K1P_WAVES * K1P_APW;
-        if (obs) LAUNCH_OPT(c, k1_stop, k_neighbors_kd4<true>, dim3((cnt + per_block - 1) / per_block), dim3(K1P_WAVES * 64), ns, d, c->P,
-                            agent_reach, obs_reach, c->max_radius);
-        else LAUNCH_OPT(c, k1_stop, k_neighbors_kd4<false>, dim3((cnt + per_block - 1) / per_block), dim3(K1P_WAVES * 64), ns, d, c->P,
-                        agent_reach, obs_reach, c->max_radius);
-    } else
-        if (obs) LAUNCH_OPT(c, k1_stop, k_neighbors_kd<true>, dim3(std::min((cnt + K1_WAVES - 1) / K1_WAVES, MAX_GRID)), dim3(K1_WAVES * 64),
-                            ns, d, c->P, agent_reach, obs_reach, c->max_radius);
-        else LAUNCH_OPT(c, k1_stop, k_neighbors_kd<false>, dim3(std::min((cnt + K1_WAVES - 1) / K1_WAVES, MAX_GRID)), dim3(K1_WAVES * 64),
-                        ns, d, c->P, agent_reach, obs_reach, c->max_radius);
+        const auto k1 = obs ? k_neighbors_grid<false, true> : k_neighbors_grid<false, false>;
+        LAUNCH_OPT(c, k1_stop, k1, k1p_grid, k1p_block, ns, d, c->grid, c->P, agent_reach, obs_reach, c->max_radius);
+    } else if (S.packed) {
+        const auto k1 = obs ? k_neighbors_kd4<true> : k_neighbors_kd4<false>;
+        LAUNCH_OPT(c, k1_stop, k1, k1p_grid, k1p_block, ns, d, c->P, agent_reach, obs_reach, c->max_radius);
+    } else {
+        const auto k1 = obs ? k_neighbors_kd<true> : k_neighbors_kd<false>;
+        LAUNCH_OPT(c, k1_stop, k1, dim3(std::min((cnt + K1_WAVES - 1) / K1_WAVES, MAX_GRID)), dim3(K1_WAVES * 64), ns, d, c->P, agent_reach, obs_reach, c->max_radius);
+    }
     c->near_valid = true;
     if ((timed || prof) && !auto_mode) CHK(c, hipEventRecord(e1, ns));    // [e0, e1] = K1
     if (auto_mode) {
         // the agents the grid query listed (more than max_neighbors in range, equal distances) get the kd-tree's answer: behind the
         // build on kd_stream, and nothing reads a list before that query is through
         const unsigned seq = ++c->auto_seq;                            // (its parity picks the list; it may wrap)
-        if (c->kd_tail_seq == seq && seq != 0) {
+        c->kdq_on_kd_stream[seq & 3u] = !tail;
+        if (tail) {
             // the launch-free form: the grid query's own last workgroup has answered the listed agents from this pass's tree (KdTail) -- no
             // launch, no cross-stream wait on the build's stream, no stream wait operation on this one
-            c->forms |= SCA_FORM_AUTO_TAIL;
-            c->kdq_on_kd_stream[seq & 3u] = false;
+            forms |= SCA_FORM_AUTO_TAIL;
         } else {
-            c->kdq_on_kd_stream[seq & 3u] = true;
             CHK(c, hipStreamWaitEvent(c->kd_stream, c->ev_auto_k1g, 0));     // (recorded behind the grid query above)
             // (ev_auto_kdq: also "the last kd query": auto_join and the event form of the wait)
-            LAUNCH_REC(c, c->ev_auto_kdq[seq & 3u], k_neighbors_kd_auto, dim3(c->kdq_last >= 0 && c->kdq_last <= KDQ_BLOCKS_FEW * K1_WAVES ? KDQ_BLOCKS_FEW : KDQ_BLOCKS),
-                       dim3(K1_WAVES * 64), c->kd_stream, d, c->P, agent_reach, obs_reach, c->max_radius, c->auto_ticket);
+            LAUNCH_REC(c, c->ev_auto_kdq[seq & 3u], k_neighbors_kd_auto, dim3(kdq_blocks), dim3(K1_WAVES * 64), c->kd_stream, d, c->P, agent_reach, obs_reach, c->max_radius, c->auto_ticket);
         }
+        // (ADVICE.md questions this copy's place on kd_stream, behind the build: moving it is a behaviour change for a pull request of its own)
         if (!c->kdq_pending && (c->auto_passes++ & 3u) == 0) {       // how many were listed: for later passes' choice, never waited for
             CHK(c, hipMemcpyAsync(c->kdq_host, d.kdq_count, sizeof(int), hipMemcpyDeviceToHost, c->kd_stream));
             CHK(c, hipEventRecord(c->ev_auto_cnt, c->kd_stream));
             c->kdq_pending = true;
         }
         c->ev_auto_kd = c->ev_auto_kdq[seq & 3u];
-        if (c->forms & SCA_FORM_AUTO_TAIL) {
+        if (tail) {
             // (the launch-free form: the lists are final when the grid query's launch ends -- its last workgroup answered whoever was listed)
         } else if (c->auto_waitvalue) {
             // lists final: at once when the grid query listed nobody, else behind the kd query (see k_neighbors_kd_auto)
@@ -1957,18 +1787,14 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
         const int per_block = SOLVE_WAVES * PICK_APW;
         hipLaunchKernelGGL(k_solve_pick4, dim3((cnt + per_block - 1) / per_block), dim3(SOLVE_WAVES * 64), 0, c->stream, d, c->P);
     }
-    else if (solve_fb) {
-        hipLaunchKernelGGL(k_solve_fb, dim3((cnt + SOLVE_WAVES - 1) / SOLVE_WAVES), dim3(SOLVE_WAVES * 64), 0, c->stream, d, c->P);
-        c->forms |= SCA_FORM_SOLVE_FB;
-    }
+    else if (solve_fb) hipLaunchKernelGGL(k_solve_fb, dim3((cnt + SOLVE_WAVES - 1) / SOLVE_WAVES), dim3(SOLVE_WAVES * 64), 0, c->stream, d, c->P);
     else {
         hipLaunchKernelGGL(k_solve, dim3((cnt + SOLVE_WAVES - 1) / SOLVE_WAVES), dim3(SOLVE_WAVES * 64), 0, c->stream, d, c->P);
-        if (!d.lp_kernel && lp_hi > lp_lo)                            // K3, one wavefront per LP agent (few of them)
+        if (S.lpw)                                                    // K3, one wavefront per LP agent (few of them)
             hipLaunchKernelGGL(k_solve_lpw, dim3((lp_hi - lp_lo + SOLVE_WAVES - 1) / SOLVE_WAVES), dim3(SOLVE_WAVES * 64), 0, c->stream, d, c->P,
                                lp_ids, lp_lo, lp_hi);
     }
-    if (d.lp_kernel) c->forms |= SCA_FORM_LP_LANE;
-    if (d.lp_kernel)                                                  // K3: the LP agents of the shard, one lane each
+    if (S.lp_kernel)                                                  // K3: the LP agents of the shard, one lane each
         hipLaunchKernelGGL(k_lp, dim3((lp_hi - lp_lo + 63) / 64), dim3(64), 0, c->stream, d, c->P, lp_ids, lp_lo, lp_hi);
     if (timed || prof) CHK(c, hipEventRecord(e3, c->stream));         // [e2, e3] = k_solve (+ k_lp) (what rocprofv3 reports for them)
     // the agents without any suitable candidate (rare; one wavefront each), then the epilogue (one lane per agent)
@@ -1980,19 +1806,17 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
         c->auto_unjoined = true;                                        // (ii) see auto_join
     }
     // (small shards: the fallback sweep rides in the epilogue's launch -- k_action_fb -- instead of in front of it)
-    const bool action_fb = !solve_fb && cnt <= c->action_fb_max;
-    if (action_fb) c->forms |= SCA_FORM_ACTION_FB;
-    if (fuse_integrate) {
-        if (action_fb) LAUNCH_OPT(c, c->action_stop, k_action_fb<true>, dim3(ablocks + FB_BLOCKS_SMALL), dim3(SOLVE_WAVES * 64), c->stream, d, c->P, ablocks);
-        else {
-            if (!solve_fb) hipLaunchKernelGGL(k_fallback<true>, dim3(FB_BLOCKS), dim3(SOLVE_WAVES * 64), 0, c->stream, d, c->P);
-            LAUNCH_OPT(c, c->action_stop, k_action<true>, dim3(ablocks), dim3(256), c->stream, d, c->P);
-        }
-    } else if (action_fb) hipLaunchKernelGGL(k_action_fb<false>, dim3(ablocks + FB_BLOCKS_SMALL), dim3(SOLVE_WAVES * 64), 0, c->stream, d, c->P, ablocks);
-    else {
-        if (!solve_fb) hipLaunchKernelGGL(k_fallback<false>, dim3(FB_BLOCKS), dim3(SOLVE_WAVES * 64), 0, c->stream, d, c->P);
-        hipLaunchKernelGGL(k_action<false>, dim3(ablocks), dim3(256), 0, c->stream, d, c->P);
+    const hipEvent_t action_stop = fuse_integrate ? c->action_stop : nullptr;
+    if (S.action_fb) {
+        const auto k = fuse_integrate ? k_action_fb<true> : k_action_fb<false>;
+        LAUNCH_OPT(c, action_stop, k, dim3(ablocks + FB_BLOCKS_SMALL), dim3(SOLVE_WAVES * 64), c->stream, d, c->P, ablocks);
+    } else {
+        const auto kf = fuse_integrate ? k_fallback<true> : k_fallback<false>;
+        const auto ka = fuse_integrate ? k_action<true> : k_action<false>;
+        if (!solve_fb) hipLaunchKernelGGL(kf, dim3(FB_BLOCKS), dim3(SOLVE_WAVES * 64), 0, c->stream, d, c->P);
+        LAUNCH_OPT(c, action_stop, ka, dim3(ablocks), dim3(256), c->stream, d, c->P);
     }
+    c->forms = forms;
     CHK(c, hipGetLastError());
     if (fuse_integrate && c->d.hist) c->d.hist_row++;
     return 0;
@@ -2161,7 +1985,7 @@ static int run_steps_loop(sca_ctx *c, int steps, int neighbor_mode, bool lazy) {
     if (c->part_on && neighbor_mode != SCA_NBR_GRID) { c->err = "the cell-owner partition is a mode of SCA_NBR_GRID"; return SCA_ERR_UNSUPPORTED; }
     for (int s = 0; s < steps; s++) {
         // (SCA_NBR_AUTO, another step to follow: the moved positions' event rides on k_action -- the next pass's kd build waits on it)
-        c->action_stop = neighbor_mode == SCA_NBR_AUTO && s + 1 < steps && c->kd_stream && c->ext_stop && !c->comm && c->d.shard_count == c->n
+        c->action_stop = neighbor_mode == SCA_NBR_AUTO && s + 1 < steps && c->kd_stream && c->tun.ext_stop && !c->comm && c->d.shard_count == c->n
                              ? c->ev_auto_moved : nullptr;                      // (a shard: the records of the others arrive after k_action)
         const int rp = launch_policy(c, neighbor_mode, false, true);           // integrate fused into k_solve
         const bool moved_recorded = c->action_stop != nullptr;
@@ -2178,7 +2002,8 @@ static int run_steps_loop(sca_ctx *c, int steps, int neighbor_mode, bool lazy) {
             if (b > 0) CHK(c, hipMemcpyAsync(c->d.rec_new, c->d.rec, sizeof(PubRec) * (size_t)b, hipMemcpyDeviceToDevice, c->stream));
             if (e < c->n) CHK(c, hipMemcpyAsync(c->d.rec_new + e, c->d.rec + e, sizeof(PubRec) * (size_t)(c->n - e), hipMemcpyDeviceToDevice, c->stream));
         }
-        if (neighbor_mode == SCA_NBR_AUTO && c->auto_ran && s + 1 < steps && auto_next(c)) {
+        if (neighbor_mode == SCA_NBR_AUTO && c->auto_ran && s + 1 < steps &&
+            auto_next(c->auto_fits, c->trk_on && c->trk_in_pass, c->part_on, c->kdq_last, c->tun.auto_div, c->auto_backoff, c->d.shard_count)) {
             // SCA_NBR_AUTO: the NEXT pass's kd build needs the moved positions only -- k_collide_finish changes flags, and in an
             // AUTO pass its fallback looks into the grid, not into the tree -- so it starts here, beside the collision check and the
             // next pass's grid build and query.  Only inside one call: a caller who reads the permutation between calls sees as many
@@ -2196,7 +2021,7 @@ static int run_steps_loop(sca_ctx *c, int steps, int neighbor_mode, bool lazy) {
         }
         // the next pass's fork (tracker in the pass, its neighbour branch on the side stream) rides on this step's last kernel
         // (not while waypoint lists are set: the next pass's k_waypoint must come before its fork)
-        c->finish_stop = s + 1 < steps && c->ext_stop && c->trk_on && c->trk_in_pass && !c->trk_serial && c->trk_fork && !c->paths_on ? c->trk_fork : nullptr;
+        c->finish_stop = s + 1 < steps && c->tun.ext_stop && c->trk_on && c->trk_in_pass && c->trk_fork && !c->paths_on ? c->trk_fork : nullptr;
         const int rf = launch_collide_finish(c, false);
         c->fork_ready = rf == 0 && c->finish_stop != nullptr;
         c->finish_stop = nullptr;
@@ -2221,13 +2046,13 @@ int sca_host_state_layout(int n, int64_t *offsets, int64_t *total_bytes) {
     return 0;
 }
 static int host_block_alloc(sca_ctx *c) {
-    if (c->hs_host && (c->hs_dev || !c->hs_staged)) return 0;
+    if (c->hs_host && (c->hs_dev || !c->tun.hs_staged)) return 0;
     const size_t bytes = (size_t)host_state_layout(c->max_n).total;       // (every section grows with n: the layout of any n <= max_n fits)
     if (!c->hs_host) {                                                    // mapped into the device's address space and coherent: the kernels access it
         CHK(c, hipHostMalloc((void **)&c->hs_host, bytes, hipHostMallocMapped | hipHostMallocCoherent));
         std::memset(c->hs_host, 0, bytes);
     }
-    if (c->hs_staged && !c->hs_dev) {
+    if (c->tun.hs_staged && !c->hs_dev) {
         CHK(c, hipMalloc((void **)&c->hs_dev, bytes));
         CHK(c, hipMemsetAsync(c->hs_dev, 0, bytes, c->stream));
     }
@@ -2281,14 +2106,14 @@ int sca_step_host(sca_ctx *c, int neighbor_mode, uint32_t in_mask, int *active) 
     }
     const HostIoDev io{c->d.rec, c->d.heading, c->d.total_dist, c->d.step_num, c->d.vpref_ext, c->d.vpref_mode, c->d.action};
     const dim3 grid((n + HIO_TILE - 1) / HIO_TILE), block(HIO_TILE);
-    uint8_t *blk = c->hs_staged ? c->hs_dev : c->hs_host;               // what the two kernels read and write
+    uint8_t *blk = c->tun.hs_staged ? c->hs_dev : c->hs_host;               // what the two kernels read and write
     if (in_mask) {
         // (staged form: the up-going sections are contiguous, [pos .. step_num] [vpref, vpref_mode] -- one copy takes what was written)
         const int64_t lo = (in_mask & SCA_HOST_IN_STATE) ? L.off[HS_POS] : L.off[HS_VPREF];
         const int64_t hi = (in_mask & SCA_HOST_IN_VPREF) ? L.off[HS_ACTION] : L.off[HS_VPREF];
         if ((in_mask & SCA_HOST_IN_STATE) && !c->state_set)               // the first state of this agent set: `radius` reaches the device with it
             CHK(c, hipMemcpyAsync(c->d.rec, c->h_rec.data(), sizeof(PubRec) * n, hipMemcpyHostToDevice, c->stream));
-        if (c->hs_staged) CHK(c, hipMemcpyAsync(c->hs_dev + lo, c->hs_host + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, c->stream));
+        if (c->tun.hs_staged) CHK(c, hipMemcpyAsync(c->hs_dev + lo, c->hs_host + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(k_host_ingest, grid, block, 0, c->stream, io, (const uint8_t *)blk, n, in_mask);
         CHK(c, hipGetLastError());
         if (in_mask & SCA_HOST_IN_STATE) {                                 // sca_set_state's bookkeeping (no host mirror of the positions is kept)
@@ -2305,8 +2130,8 @@ int sca_step_host(sca_ctx *c, int neighbor_mode, uint32_t in_mask, int *active) 
     hipLaunchKernelGGL(k_host_egress, grid, block, 0, c->stream, out, blk, n);
     CHK(c, hipGetLastError());
     // (staged form, down: the state sections and the action rows; the caller's v_pref sections between them are never written)
-    if (c->hs_staged) CHK(c, hipMemcpyAsync(c->hs_host + L.off[HS_POS], c->hs_dev + L.off[HS_POS], (size_t)(L.off[HS_VPREF] - L.off[HS_POS]), hipMemcpyDeviceToHost, c->stream));
-    if (c->hs_staged) CHK(c, hipMemcpyAsync(c->hs_host + L.off[HS_ACTION], c->hs_dev + L.off[HS_ACTION], (size_t)(L.total - L.off[HS_ACTION]), hipMemcpyDeviceToHost, c->stream));
+    if (c->tun.hs_staged) CHK(c, hipMemcpyAsync(c->hs_host + L.off[HS_POS], c->hs_dev + L.off[HS_POS], (size_t)(L.off[HS_VPREF] - L.off[HS_POS]), hipMemcpyDeviceToHost, c->stream));
+    if (c->tun.hs_staged) CHK(c, hipMemcpyAsync(c->hs_host + L.off[HS_ACTION], c->hs_dev + L.off[HS_ACTION], (size_t)(L.total - L.off[HS_ACTION]), hipMemcpyDeviceToHost, c->stream));
     return read_active(c, active, c->perm_on_device);                     // ... and the count (and the kd build's error word): the call's one synchronisation
 }
 int sca_set_shard_emulation(sca_ctx *c, int on) {

@@ -39,14 +39,7 @@ namespace sca {
 #define SCA_KD_SETPRIO() ((void)0)
 #endif
 
-// A node of <= wave_max members (KdScratch::wave_max, chosen per build) is finished, whole subtree, by ONE WORKGROUP in LDS
-// (k_kd_block).  The host picks it between these bounds so that the node sizes of a level (n / 2^k, within a few per cent)
-// do not straddle it: with a fixed 1024 the 4096- and 16384-agent trees needed a whole level pass for the half of their
-// ~1024-member nodes that were a little larger.
-constexpr int KD_WAVE_MIN = 768, KD_WAVE_CAP = 1536;   // the defaults; SCA_KD_WAVE_CAP picks a smaller workgroup form (sca_ctx::kd_wave_cap)
-constexpr int KD_WAVE_FLOOR = 128;                     // tables are sized for subtrees handed over at this size or above
-constexpr int KD_MAX_LEVELS = 40;
-constexpr int KD_CHUNK = 2048;         // positions per workgroup in the level passes over larger nodes
+// (KD_WAVE_MIN / KD_WAVE_CAP / KD_WAVE_FLOOR, KD_MAX_LEVELS, KD_CHUNK and KT_M: sca_constants.h -- the host sizes its launches with them)
 
 // why a build reported failure (bits of counts[KD_MAX_LEVELS + 1]; sticky across builds until sca_synchronize reports them)
 enum { KD_ERR_SPIN = 1, KD_ERR_CHUNKS = 4, KD_ERR_JOBS = 8, KD_ERR_LEVELS = 16, KD_ERR_BLOCK = 128 };
@@ -96,7 +89,7 @@ struct KdScratch {
 // other CUs: one spinning workgroup starves nobody) the word comes.  (The first version had it the other way round -- the BUILD's last
 // workgroup waited for the grid query, a LATER launch -- and the suite that takes four minutes took fifteen: a kernel that waits for a
 // launch behind it in a shared hardware queue waits for ever.)  The host takes this form while the list lengths that come back say
-// "nobody" (sca_hip.hip: auto_tail_max = 0); a list that appears is answered here by this one workgroup for the few passes until the
+// "nobody" (sca_forms.h: auto_tail_max = 0); a list that appears is answered here by this one workgroup for the few passes until the
 // host has seen its length, then by the launch form with its 64 .. 1024 workgroups.
 struct KdTail {
     unsigned seq;             // the pass this build belongs to (sca_ctx::auto_seq of its grid query); 0: publish nothing
@@ -862,7 +855,7 @@ __global__ __launch_bounds__(KBT) void k_kd_block(DeviceView d, KdScratch s, int
 #ifndef SCA_KT_THREADS
 #define SCA_KT_THREADS 1024
 #endif
-constexpr int KT_M = 4096, KT_T = SCA_KT_THREADS, KT_E = KT_M / KT_T, KT_NODES = 32;
+constexpr int KT_T = SCA_KT_THREADS, KT_E = KT_M / KT_T, KT_NODES = 32;
 // A node of the top has more than wave_max members, and wave_max >= cap / 2 + 1 >= KD_WAVE_FLOOR + 1 (build_agent_tree_device; SCA_KD_WAVE_CAP
 // is clamped to 2 * KD_WAVE_FLOOR): a level of the top therefore holds at most KT_M / (KD_WAVE_FLOOR + 2) nodes, and a thread's KT_E consecutive
 // positions lie in at most two of them.  The host checks the same bound with the pass's actual wave_max before it takes this path.

@@ -19,6 +19,7 @@
 #include <limits.h>
 
 #include "sca_core.h"
+#include "sca_constants.h"
 
 namespace sca {
 
@@ -311,7 +312,6 @@ __device__ __forceinline__ double wave_min(double v) {
 // are fetched and measured by 10 lanes at once, and the bounded sorted neighbour list of agent.py:87-99
 // is kept one entry per lane (lanes 0..15) so that an insertion is one ballot + one lane shift.
 constexpr int KD_STACK = 64;
-constexpr int K1_WAVES = 4;
 constexpr int NEAR_MAX = 8;
 
 struct WaveList {            // entry k of the sorted list lives in lane k
@@ -569,7 +569,6 @@ __global__ __launch_bounds__(K1_WAVES * 64) void k_neighbors_kd(DeviceView d, Pa
 // for the bit to be clear with hipStreamWaitValue32: a wait that costs nothing when nobody was listed, which is what keeps the kd
 // build (beside, on its own stream) off the pass's critical path in the common case.  (Until late in round 4 a word counting passes,
 // and a one-lane launch behind the grid query to advance it when nobody was listed: 4 us + its gap on every pass's path.)
-constexpr int KDQ_BLOCKS = 1024, KDQ_BLOCKS_FEW = 64;   // (the few: while the counts that came back say a wavefront each is enough -- an empty launch of 64 workgroups is half as long)
 __global__ __launch_bounds__(K1_WAVES * 64) void k_neighbors_kd_auto(DeviceView d, Params P, double agent_reach, double obs_reach,
                                                                      double max_radius, int *ticket) {
     SCA_TL(d, TL_NBR_KD_AUTO);

@@ -43,8 +43,6 @@ struct TrackDev {
     int lo, hi;                   // this launch takes the pass when lo < (re-plans of the pass) <= hi; the launches of a pass cover every count
     int prep;                     // 1: the kernels also write the solve's per-agent prologue (inside a pass whose neighbour branch overlaps)
     Params P;
-    int mid_max;                  // TRK_MID_MAX unless overridden (SCA_TRK_MID_MAX, tuning): the quad form's upper end
-    int spec2_max, spec3_max, spec4_max;   // TRK_SPEC*_MAX unless overridden (SCA_TRK_SPEC2_MAX ..., tuning)
 };
 
 // Which kernel re-plans a pass, by the pass's re-plan count (read on the device; the host launches the kernels whose range a recent
@@ -72,7 +70,6 @@ __device__ __forceinline__ int trk_list_agent(const int32_t *list, const int32_t
     }
     return list[rem];
 }
-constexpr int TRK_MID_MAX = 32768;
 constexpr int TRK_REPLAN_LANES = 256;     // four wavefronts per workgroup = one per SIMD of a CU: the dispatcher then loads the SIMDs evenly
                                           // (65 536 plans as 1024 one-wave workgroups: 0.63 ms, some SIMDs drew two; as 256 of these: 0.44)
                                           // and, above one wave per SIMD, doubles up whole CUs, which leaves the others room for the
@@ -514,9 +511,7 @@ __device__ __forceinline__ sca_dubins::Plan3D plan3d_quad(const double qi[5], co
 // reference's own planner on 256 recorded searches) follow the likely continuations up to twelve steps deep, one tree per context =
 // (kind of the current run of verdicts, its length, the lengths of the two runs before it): 6.6 - 7.5 steps per round with 15 candidates
 // on held-out searches, 4.7 - 5.4 with 7, 2.6 - 2.7 with 3.  A quad finds its candidate by walking its node's path from the round's (b, step).
-constexpr int TRK_SPEC2_MAX = 8192;        // <= this many re-plans in the pass: 3 candidates per round, 16 lanes per plan (2048 wavefronts: two per SIMD)
-constexpr int TRK_SPEC3_MAX = 4096;        // <= this many: 7 per round, 32 lanes per plan (2048 wavefronts)
-constexpr int TRK_SPEC4_MAX = 1024;        // <= this many: 15 per round, a whole wavefront per plan -- and a SIMD per wavefront (the kernel sits at the 256-register edge)
+// (TRK_SPEC2_MAX / TRK_SPEC3_MAX / TRK_SPEC4_MAX, the counts up to which 16 / 32 / 64 lanes per plan are launched: sca_constants.h)
 
 #if defined(SCA_KT_TIMING)   // debug builds: workgroup 0 / thread 0's clock over the pieces of a speculative search, summed over its rounds (tools/phase_clocks.py)
 #define KG_ADD(k) do { if (blockIdx.x == 0 && threadIdx.x == 0) { const long long t_ = wall_clock64(); sca_dubins::g_td_ticks[16 + (k)] += (int)(t_ - sca_dubins::g_td_last); sca_dubins::g_td_last = t_; } } while (0)

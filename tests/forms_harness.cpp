@@ -1,0 +1,77 @@
+// Test-only: the form decisions of the host side (sca_amd/csrc/sca_forms.h) behind a C interface for tests/test_forms_cpu.py.  Plain C++, no
+// HIP.  A Tunables travels as its ints, in the order of the TUNABLES table.  Not part of the product (sca_amd never loads it).
+#include <cstring>
+
+#include "sca_forms.h"
+
+using namespace sca;
+
+constexpr int NTUN = (int)(sizeof(TUNABLES) / sizeof(TUNABLES[0]));
+static_assert(sizeof(Tunables) == NTUN * sizeof(int), "one table row per member");
+
+static Tunables tun_of(const int *v) {
+    Tunables t{};
+    for (int i = 0; i < NTUN; i++) t.*TUNABLES[i].member = v[i];
+    return t;
+}
+
+extern "C" {
+
+int forms_tunable_count(void) { return NTUN; }
+const char *forms_tunable_name(int i) { return TUNABLES[i].name; }
+// what sca_create followed by sca_device_tracker_enable would hold in the environment of the moment
+void forms_tunables_from_env(int simds, int *out) {
+    Tunables t{};
+    tunables_from_env(t, simds, TUN_AT_CREATE);
+    tunables_from_env(t, simds, TUN_AT_TRACKER);
+    for (int i = 0; i < NTUN; i++) out[i] = t.*TUNABLES[i].member;
+}
+// only the rows of sca_device_tracker_enable are read again: the others keep what `inout` holds
+void forms_tunables_tracker_again(int simds, int *inout) {
+    Tunables t = tun_of(inout);
+    tunables_from_env(t, simds, TUN_AT_TRACKER);
+    for (int i = 0; i < NTUN; i++) inout[i] = t.*TUNABLES[i].member;
+}
+void forms_constants(int *out7) {
+    const int v[7] = {KD_WAVE_CAP, KD_WAVE_FLOOR, KD_CHUNK, KD_MAX_LEVELS, KT_M, KDQ_BLOCKS, KDQ_BLOCKS_FEW};
+    std::memcpy(out7, v, sizeof(v));
+}
+
+void forms_plan_auto(int fits, int tracked, int kd_ahead, int kdq_last, int auto_div, int auto_backoff, int shard_count, int *out4) {
+    const AutoPlan p = plan_auto(fits, tracked, kd_ahead, kdq_last, auto_div, auto_backoff, shard_count);
+    out4[0] = p.auto_pass; out4[1] = p.auto_backoff; out4[2] = p.kdq_last; out4[3] = p.kdq_blocks;
+}
+int forms_auto_next(int fits, int tracked, int part_on, int kdq_last, int auto_div, int auto_backoff, int shard_count) {
+    return auto_next(fits, tracked, part_on, kdq_last, auto_div, auto_backoff, shard_count);
+}
+int forms_auto_tail_form(int tail_ok, int waitvalue, unsigned seq, int kdq_last, int auto_tail_max) {
+    return auto_tail_form(tail_ok, waitvalue, seq, kdq_last, auto_tail_max);
+}
+
+int forms_choose_solve_split(const int *tun, int simds, int overlap, int cnt, int trk_last_count) {
+    return choose_solve_split(tun_of(tun), simds, overlap, cnt, trk_last_count);
+}
+void forms_plan_solve(const int *tun, int simds, int cnt, int part_on, int part_nranks, long long lp_total, int lp_in_shard, int overlap,
+                      int trk_last_count, int no_sweep_scratch, int *out7) {
+    const SolvePlan p = plan_solve(tun_of(tun), simds, cnt, part_on, part_nranks, lp_total, lp_in_shard, overlap, trk_last_count, no_sweep_scratch);
+    out7[0] = p.packed; out7[1] = p.split; out7[2] = p.solve_fb; out7[3] = p.lpw; out7[4] = p.lp_kernel; out7[5] = p.action_fb; out7[6] = p.forms;
+}
+
+// out: fused, group_fused, forms, n, then n x (kernel, lo, hi, plans, lanes)
+void forms_plan_replans(const int *tun, int cnt, int last_count, int trk_many, int in_pass, int part_on, int *out29) {
+    const ReplanPlan p = plan_replans(tun_of(tun), cnt, last_count, trk_many, in_pass, part_on);
+    out29[0] = p.fused; out29[1] = p.group_fused; out29[2] = p.forms; out29[3] = p.n;
+    for (int i = 0; i < p.n; i++) {
+        const ReplanLaunch &l = p.launch[i];
+        const int v[5] = {l.kernel, l.lo, l.hi, l.plans, l.lanes};
+        std::memcpy(out29 + 4 + 5 * i, v, sizeof(v));
+    }
+}
+
+void forms_plan_kd_build(const int *tun, int n, int beside, int single_hint, int chunk_cap, int rank_capacity, int *out9) {
+    const KdBuildPlan p = plan_kd_build(tun_of(tun), n, beside, single_hint, chunk_cap, rank_capacity);
+    const int v[9] = {p.top, p.wave_max, p.block, p.level_passes, p.first_single, p.grid, p.ticket, p.levels, p.sgrid};
+    std::memcpy(out9, v, sizeof(v));
+}
+
+}  // extern "C"

@@ -1,0 +1,306 @@
+"""The host side's form decisions (sca_amd/csrc/sca_forms.h) without a GPU: which kernels a pass runs at which shard size, SIMD count and
+read-back count.  tests/forms_harness.cpp puts the plan functions behind a C interface.  Every expectation below is a literal worked out by
+hand from the documented thresholds (1024 SIMDs unless a row says otherwise) -- none comes from the code under test."""
+import ctypes as C
+import itertools
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BUILD = os.path.join(ROOT, 'tests', '_build')
+CSRC = os.path.join(ROOT, 'sca_amd', 'csrc')
+INT_MAX = 2 ** 31 - 1
+SPLIT, TRACK_FUSED, LANE, FEW, LP_LANE, SOLVE_FB, ACTION_FB = 1, 2, 4, 8, 16, 32, 64          # include/sca_hip.h
+G64, G32, G16, G4, RP_LANE, TRACK_GROUP, TRACK_REPLAN = range(7)                               # ReplanKernel
+
+DEFAULTS_1024 = {'SCA_K1_PACKED': -1, 'SCA_AUTO_BACKOFF_DIV': 8, 'SCA_AUTO_NO_TAIL': 0, 'SCA_AUTO_TAIL_MAX': 0, 'SCA_SOLVE_SPLIT': -1,
+                 'SCA_HOST_STEP_STAGED': 0, 'SCA_KD_TOP': 1, 'SCA_EXT_STOP': 1, 'SCA_KD_TICKET': 0, 'SCA_KD_WAVE_CAP': 0,
+                 'SCA_SOLVE_FB_MAX': 2048, 'SCA_ACTION_FB_MAX': 16384, 'SCA_LP_FORM': -1, 'SCA_TRACKER_FUSE': 0, 'SCA_TRACKER_NOGROUPFUSE': 1,
+                 'SCA_TRK_SPEC4_MAX': 1024, 'SCA_TRK_SPEC3_MAX': 4096, 'SCA_TRK_SPEC2_MAX': 8192, 'SCA_TRK_MID_MAX': 32768}
+REMOVED = ('SCA_TRACKER_SERIAL', 'SCA_TRACKER_NOQUAD', 'SCA_KD_NOHINT', 'SCA_KD_TAIL_LEVEL', 'SCA_AUTO_EVENT_WAIT', 'SCA_TRACKER_NOFUSE')
+
+
+@pytest.fixture(scope='module')
+def H():
+    out = os.path.join(BUILD, 'libforms_harness.so')
+    src = os.path.join(ROOT, 'tests', 'forms_harness.cpp')
+    deps = [src, os.path.join(ROOT, 'include', 'sca_hip.h'), os.path.join(CSRC, 'sca_forms.h'), os.path.join(CSRC, 'sca_constants.h')]
+    os.makedirs(BUILD, exist_ok=True)
+    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(f) for f in deps):
+        # (no ROCm include path: the header must be plain C++)
+        subprocess.check_call(['g++', '-std=c++17', '-O1', '-Wall', '-Wextra', '-Werror', '-fPIC', '-shared', '-I' + CSRC, '-o', out, src])
+    h = C.CDLL(out)
+    h.forms_tunable_name.restype = C.c_char_p
+    h.forms_plan_solve.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    return h
+
+
+@pytest.fixture()
+def clean_env(monkeypatch):
+    for k in list(os.environ):
+        if k.startswith('SCA_'):
+            monkeypatch.delenv(k)
+    return monkeypatch
+
+
+def names(H):
+    return [H.forms_tunable_name(i).decode() for i in range(H.forms_tunable_count())]
+
+
+def from_env(H, simds=1024):
+    out = (C.c_int * H.forms_tunable_count())()
+    H.forms_tunables_from_env(simds, out)
+    return dict(zip(names(H), out))
+
+
+def tun(H, **over):
+    """the defaults at 1024 SIMDs as the harness wants them, with overrides by environment name"""
+    d = dict(DEFAULTS_1024, **{'SCA_' + k: v for k, v in over.items()})
+    return (C.c_int * len(d))(*[d[k] for k in names(H)])
+
+
+def solve(H, cnt, simds=1024, part_on=0, nranks=1, lp_total=0, lp=0, overlap=0, last=-1, no_scratch=0, t=None, **over):
+    out = (C.c_int * 7)()
+    H.forms_plan_solve(t or tun(H, **over), simds, cnt, part_on, nranks, lp_total, lp, overlap, last, no_scratch, out)
+    return dict(zip(('packed', 'split', 'solve_fb', 'lpw', 'lp_kernel', 'action_fb', 'forms'), out))
+
+
+def replans(H, cnt, last, many=0, in_pass=1, part_on=0, **over):
+    out = (C.c_int * 29)()
+    H.forms_plan_replans(tun(H, **over), cnt, last, many, in_pass, part_on, out)
+    return {'fused': out[0], 'group_fused': out[1], 'forms': out[2], 'launches': [tuple(out[4 + 5 * i:9 + 5 * i]) for i in range(out[3])]}
+
+
+def kd(H, n, beside=0, hint=0, chunk_cap=1 << 30, rank_cap=1 << 30, t=None, **over):
+    out = (C.c_int * 9)()
+    H.forms_plan_kd_build(t or tun(H, **over), n, beside, hint, chunk_cap, rank_cap, out)
+    return dict(zip(('top', 'wave_max', 'block', 'level_passes', 'first_single', 'grid', 'ticket', 'levels', 'sgrid'), out))
+
+
+def auto(H, fits=1, tracked=0, ahead=0, kdq_last=-1, div=8, backoff=0, shard=100000):
+    out = (C.c_int * 4)()
+    H.forms_plan_auto(fits, tracked, ahead, kdq_last, div, backoff, shard, out)
+    return tuple(out)                                                                          # (AUTO pass, auto_backoff, kdq_last, kdq blocks)
+
+
+# ---- the tunables ------------------------------------------------------------------------------------------------------------------------------
+
+def test_the_table_lists_exactly_the_documented_switches_with_their_defaults(H, clean_env):
+    assert from_env(H) == DEFAULTS_1024
+    half = from_env(H, 512)                                                                    # "so many wavefronts per SIMD"
+    assert {k: v for k, v in half.items() if v != DEFAULTS_1024[k]} == {
+        'SCA_SOLVE_FB_MAX': 1024, 'SCA_ACTION_FB_MAX': 8192, 'SCA_TRK_SPEC4_MAX': 512, 'SCA_TRK_SPEC3_MAX': 2048, 'SCA_TRK_SPEC2_MAX': 4096,
+        'SCA_TRK_MID_MAX': 16384}
+    k = (C.c_int * 7)()
+    H.forms_constants(k)
+    assert tuple(k) == (1536, 128, 2048, 40, 4096, 1024, 64)
+
+
+def test_every_switch_parses_as_documented(H, clean_env):
+    def one(name, value, simds=1024):
+        clean_env.setenv(name, value)
+        got = from_env(H, simds)
+        clean_env.delenv(name)
+        assert {k for k, v in got.items() if v != DEFAULTS_1024[k]} <= {name}                  # no switch moves another
+        return got[name]
+    for name in ('SCA_K1_PACKED', 'SCA_SOLVE_SPLIT', 'SCA_HOST_STEP_STAGED', 'SCA_KD_TOP', 'SCA_EXT_STOP', 'SCA_KD_TICKET'):
+        assert (one(name, '0'), one(name, '1'), one(name, '7')) == (0, 1, 1), name
+    assert (one('SCA_AUTO_NO_TAIL', '1'), one('SCA_AUTO_NO_TAIL', '0'), one('SCA_AUTO_NO_TAIL', '')) == (1, 1, 1)      # being set is the switch
+    assert (one('SCA_TRACKER_FUSE', '1'), one('SCA_TRACKER_FUSE', '0')) == (1, 1)
+    assert (one('SCA_TRACKER_NOGROUPFUSE', '1'), one('SCA_TRACKER_NOGROUPFUSE', '0')) == (0, 0)
+    assert [one('SCA_AUTO_BACKOFF_DIV', v) for v in ('0', '1', '4', '64', '65')] == [1, 1, 4, 64, 64]
+    assert [one('SCA_AUTO_TAIL_MAX', v) for v in ('-3', '0', '32')] == [0, 0, 32]
+    assert [one('SCA_KD_WAVE_CAP', v) for v in ('100', '256', '512', '1536', '5000')] == [256, 256, 512, 1536, 1536]
+    assert [one('SCA_LP_FORM', v) for v in ('lane', 'wave', 'l', 'w', 'other')] == [1, 0, 1, 0, -1]
+    for name in ('SCA_SOLVE_FB_MAX', 'SCA_ACTION_FB_MAX', 'SCA_TRK_SPEC4_MAX', 'SCA_TRK_SPEC3_MAX', 'SCA_TRK_SPEC2_MAX', 'SCA_TRK_MID_MAX'):
+        assert [one(name, v) for v in ('0', '1000000', '-1')] == [0, 1000000, -1], name        # as given: not clamped
+
+
+def test_a_switch_keeps_the_moment_at_which_it_is_read(H, clean_env):
+    """the tracker's rows are read again by every sca_device_tracker_enable, the solver's only by sca_create"""
+    t = tun(H)
+    clean_env.setenv('SCA_TRACKER_FUSE', '1')
+    clean_env.setenv('SCA_TRK_MID_MAX', '0')
+    clean_env.setenv('SCA_SOLVE_SPLIT', '1')
+    clean_env.setenv('SCA_LP_FORM', 'lane')
+    H.forms_tunables_tracker_again(1024, t)
+    got = dict(zip(names(H), t))
+    assert {k: v for k, v in got.items() if v != DEFAULTS_1024[k]} == {'SCA_TRACKER_FUSE': 1, 'SCA_TRK_MID_MAX': 0}
+    clean_env.delenv('SCA_TRACKER_FUSE')
+    H.forms_tunables_tracker_again(1024, t)
+    assert dict(zip(names(H), t))['SCA_TRACKER_FUSE'] == 0
+
+
+def test_the_host_reads_the_environment_in_one_place_and_the_documents_name_the_switches_that_exist(H):
+    src = open(os.path.join(CSRC, 'sca_hip.hip')).read()
+    assert re.findall(r'getenv\("(\w+)"\)', src) == ['SCA_QUIET'] and src.count('getenv') == 1
+    assert src.count('tunables_from_env(') == 2                                                # sca_create, sca_device_tracker_enable
+    doc = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
+    for name in names(H):
+        assert name in doc, name
+    product = doc + src + open(os.path.join(CSRC, 'sca_forms.h')).read()
+    for name in REMOVED:
+        assert name not in product, name
+
+
+# ---- the solve and its neighbours ---------------------------------------------------------------------------------------------------------------
+
+def test_packed_k1_from_six_wavefronts_of_four_agents_per_simd(H):
+    assert [solve(H, n)['packed'] for n in (6143, 6144)] == [0, 1]
+    assert [solve(H, n, simds=512)['packed'] for n in (3071, 3072)] == [0, 1]
+    assert [solve(H, n, K1_PACKED=f)['packed'] for n, f in ((100000, 0), (10, 1))] == [0, 1]
+
+
+def test_solve_fb_and_action_fb(H):
+    assert [solve(H, n)['solve_fb'] for n in (1, 2048, 2049)] == [1, 1, 0]
+    assert [solve(H, n, simds=512, t=tun(H, SOLVE_FB_MAX=1024, ACTION_FB_MAX=8192))['solve_fb'] for n in (1024, 1025)] == [1, 0]
+    assert solve(H, 2048, lp=1, lp_total=1)['solve_fb'] == 0                                   # somebody else feeds the fallback list
+    assert solve(H, 2048, SOLVE_SPLIT=1)['solve_fb'] == 0
+    assert solve(H, 2048, SOLVE_SPLIT=1, no_scratch=1) == dict(packed=0, split=0, solve_fb=0, lpw=0, lp_kernel=0, action_fb=1, forms=ACTION_FB)
+    assert solve(H, 2048, part_on=1, nranks=2)['solve_fb'] == 0
+    assert [(solve(H, n)['action_fb'], solve(H, n)['forms']) for n in (2048, 2049, 16384, 16385)] == [(0, SOLVE_FB), (1, ACTION_FB), (1, ACTION_FB), (0, 0)]
+    assert solve(H, 2048, SOLVE_FB_MAX=0)['forms'] == ACTION_FB and solve(H, 2048, SOLVE_FB_MAX=0, ACTION_FB_MAX=0)['forms'] == 0
+
+
+def test_lp_form(H):
+    assert [solve(H, 100000, lp=k, lp_total=k)['lp_kernel'] for k in (0, 16383, 16384)] == [0, 0, 1]
+    assert [solve(H, 100000, simds=512, lp=k, lp_total=k)['lp_kernel'] for k in (8191, 8192)] == [0, 1]
+    assert solve(H, 100000, lp=16383, lp_total=16383) == dict(packed=1, split=0, solve_fb=0, lpw=1, lp_kernel=0, action_fb=0, forms=0)
+    assert solve(H, 100000, lp=16384, lp_total=16384) == dict(packed=1, split=0, solve_fb=0, lpw=0, lp_kernel=1, action_fb=0, forms=LP_LANE)
+    # the partition: the LP agents of the whole swarm per rank; the range the kernels walk (lp) is the owned agents
+    assert [solve(H, 50000, part_on=1, nranks=2, lp_total=k, lp=50000)['lp_kernel'] for k in (32767, 32768)] == [0, 1]
+    assert solve(H, 50000, part_on=1, nranks=2, lp_total=32768, lp=50000, LP_FORM=0)['lp_kernel'] == 1      # SCA_LP_FORM is a switch of the shard rule
+    # a split pass: k_solve_pick4 carries no LP
+    assert solve(H, 30000, lp=5, lp_total=5, SOLVE_SPLIT=1) == dict(packed=1, split=1, solve_fb=0, lpw=0, lp_kernel=1, action_fb=0, forms=SPLIT | LP_LANE)
+    assert solve(H, 30000, lp=0, SOLVE_SPLIT=1)['lp_kernel'] == 0
+    assert [solve(H, 30000, lp=k, lp_total=k, LP_FORM=1)['lp_kernel'] for k in (0, 5)] == [0, 1]
+    assert solve(H, 30000, lp=20000, lp_total=20000, LP_FORM=0) == dict(packed=1, split=0, solve_fb=0, lpw=1, lp_kernel=0, action_fb=0, forms=0)
+
+
+def test_choose_solve_split(H):
+    def split(cnt, last, overlap=1, simds=1024, **over):
+        return H.forms_choose_solve_split(tun(H, **over), simds, overlap, cnt, last)
+    assert [split(50000, 40000, SOLVE_SPLIT=v, overlap=o) for v in (0, 1) for o in (0, 1)] == [0, 0, 1, 1]
+    assert split(50000, 40000, overlap=0) == 0
+    assert [split(50000, e) for e in (32768, 32769)] == [0, 1]                                 # the many-lanes-per-plan forms: nothing to hide behind
+    assert [split(n, 32769) for n in (61440, 61441)] == [1, 0] and [split(n, 65536) for n in (61440, 61441)] == [1, 0]      # one round
+    assert [split(n, 65537) for n in (61441, 114688, 114689)] == [1, 1, 0] and split(114688, 131072) == 1                   # two
+    assert [split(n, 131073) for n in (50000, 114688, 200000)] == [0, 0, 0]                                                 # three
+    assert [split(n, -1) for n in (32768, 32769, 61440, 61441, 65536, 65537, 114688, 114689, 131073)] == [0, 1, 1, 0, 0, 1, 1, 0, 0]
+    half = dict(TRK_MID_MAX=16384)
+    assert [split(n, e, simds=512, **half) for n, e in ((30000, 16384), (30720, 16385), (30721, 16385), (57344, 32769), (57345, 32769))] == [0, 1, 0, 1, 0]
+    assert solve(H, 50000, overlap=1, last=40000)['forms'] == SPLIT and solve(H, 50000, overlap=0, last=40000)['forms'] == 0
+
+
+# ---- the tracker's re-plans -----------------------------------------------------------------------------------------------------------------------
+
+def test_replans_count_unknown_launches_every_possible_form_with_its_natural_range(H):
+    assert replans(H, 100000, -1) == dict(fused=0, group_fused=0, forms=FEW | LANE, launches=[
+        (G64, -1, 1024, 1024, 64), (G32, 1024, 4096, 4096, 32), (G16, 4096, 8192, 8192, 16), (G4, 8192, 32768, 32768, 4), (RP_LANE, 32768, INT_MAX, 100000, 1)])
+    assert replans(H, 5000, -1) == dict(fused=0, group_fused=0, forms=FEW, launches=[
+        (G64, -1, 1024, 1024, 64), (G32, 1024, 4096, 4096, 32), (G16, 4096, INT_MAX, 5000, 16)])
+    assert replans(H, 5000, -1, in_pass=0)['launches'] == replans(H, 5000, -1)['launches']
+
+
+def test_replans_known_count_hysteresis_of_a_quarter_on_both_sides(H):
+    r = lambda last, cnt=100000, **kw: replans(H, cnt, last, **kw)
+    assert r(5000) == dict(fused=0, group_fused=0, forms=FEW, launches=[(G32, -1, 4096, 4096, 32), (G16, 4096, INT_MAX, 100000, 16)])
+    assert [[l[0] for l in r(v)['launches']] for v in (5120, 5121)] == [[G32, G16], [G16]]                  # 4096 + 1024
+    assert [[l[0] for l in r(v)['launches']] for v in (3072, 3073)] == [[G32], [G32, G16]]                  # 4096 - 1024
+    assert r(3072)['launches'] == [(G32, -1, INT_MAX, 100000, 32)]
+    assert [[l[0] for l in r(v)['launches']] for v in (0, 768, 769, 1280, 1281)] == [[G64], [G64], [G64, G32], [G64, G32], [G32]]
+    assert [[l[0] for l in r(v)['launches']] for v in (24576, 24577, 40960, 40961)] == [[G4], [G4, RP_LANE], [G4, RP_LANE], [RP_LANE]]
+    assert r(24577) == dict(fused=0, group_fused=0, forms=FEW | LANE, launches=[(G4, -1, 32768, 32768, 4), (RP_LANE, 32768, INT_MAX, 100000, 1)])
+    assert r(90000) == dict(fused=0, group_fused=0, forms=LANE, launches=[(RP_LANE, -1, INT_MAX, 100000, 1)])
+    assert r(90000, cnt=20000)['launches'] == [(RP_LANE, -1, INT_MAX, 20000, 1)]               # no form is possible AND wanted: the lane form takes all
+
+
+def test_replans_fused_forms(H):
+    lane_alone = [(TRACK_REPLAN, -1, INT_MAX, 100000, 1)]
+    assert replans(H, 100000, 75000, TRACKER_FUSE=1) == dict(fused=1, group_fused=0, forms=TRACK_FUSED | LANE, launches=lane_alone)
+    assert replans(H, 100000, 74999, TRACKER_FUSE=1)['fused'] == 0                              # 3/4 of the shard
+    assert replans(H, 100000, 40000, TRACKER_FUSE=1)['fused'] == 0                              # not in lane form ALONE (k_replan_group<4> is launched too)
+    assert replans(H, 100000, 75000)['fused'] == 0                                              # opt-in
+    assert replans(H, 100000, 75000, TRACKER_FUSE=1, in_pass=0)['fused'] == 0
+    assert replans(H, 100000, 75000, TRACKER_FUSE=1, part_on=1)['fused'] == 0
+    assert replans(H, 100000, -1, TRACKER_FUSE=1)['fused'] == 0
+    for last in (-1, 0, 1024):
+        assert replans(H, 1024, last) == dict(fused=0, group_fused=1, forms=TRACK_FUSED | FEW, launches=[(TRACK_GROUP, -1, INT_MAX, 1024, 64)])
+    assert replans(H, 1025, -1)['group_fused'] == 0
+    assert replans(H, 1024, -1, TRACKER_NOGROUPFUSE=0)['group_fused'] == 0
+    assert replans(H, 1024, -1, in_pass=0)['group_fused'] == 0 and replans(H, 1024, -1, part_on=1)['group_fused'] == 0
+    assert replans(H, 2048, -1, TRK_SPEC4_MAX=2048)['group_fused'] == 1
+    # the per-agent form: a wavefront per plan at any count
+    assert replans(H, 100000, 90000, many=1, TRACKER_FUSE=1) == dict(fused=0, group_fused=0, forms=FEW, launches=[(G64, -1, INT_MAX, 100000, 64)])
+    assert replans(H, 100000, -1, many=1)['launches'] == [(G64, -1, INT_MAX, 100000, 64)]
+    assert replans(H, 500, 3, many=1)['launches'] == [(TRACK_GROUP, -1, INT_MAX, 500, 64)]
+
+
+def test_replans_every_count_is_exactly_one_launchs(H):
+    """over a grid of shard sizes, read-back counts and bounds (the tests' forcing values and non-monotone ones among them): the launched
+    ranges start at -1, end at INT_MAX, and every count 1 .. cnt falls into exactly one of them, whose grid holds it"""
+    bounds = [(1024, 4096, 8192, 32768), (0, 0, 0, 0), (1000000,) * 4, (0, 1000000, 1000000, 1000000), (0, 0, 1000000, 1000000),
+              (0, 0, 0, 1000000), (4096, 1024, 8192, 2048), (512, 2048, 4096, 16384), (-5, 7, 7, 9), (1, 2, 3, 4), (32768, 8192, 4096, 1024)]
+    cnts = (1, 2, 5, 100, 1024, 1025, 5000, 40000, 100000, 2000000)
+    lasts = (-1, 0, 1, 3, 768, 769, 1280, 1281, 3072, 5121, 8192, 24577, 40961, 99999, 1999999)
+    checked = 0
+    for (s4, s3, s2, mid), cnt, last, many, fuse in itertools.product(bounds, cnts, lasts, (0, 1), (0, 1)):
+        r = replans(H, cnt, last, many=many, TRK_SPEC4_MAX=s4, TRK_SPEC3_MAX=s3, TRK_SPEC2_MAX=s2, TRK_MID_MAX=mid, TRACKER_FUSE=fuse, TRACKER_NOGROUPFUSE=0)
+        L = r['launches']
+        ctx = (s4, s3, s2, mid, cnt, last, many, fuse, L)
+        assert 1 <= len(L) <= 5 and L[-1][2] == INT_MAX, ctx
+        assert L[0][1] <= 0, ctx                                   # (-1, or the bound of a range that could only hold the count 0: nothing to launch)
+        for a, b in zip(L, L[1:]):
+            assert a[2] == b[1] and a[1] < a[2], ctx               # contiguous: so exactly one range holds each count above the first lo
+        for k, lo, hi, plans, lanes in L:
+            assert plans >= min(cnt, hi) and lanes == (64, 32, 16, 4, 1, 64, 1)[k], ctx
+        checked += 1
+    assert checked == len(bounds) * len(cnts) * len(lasts) * 4
+
+
+# ---- SCA_NBR_AUTO ------------------------------------------------------------------------------------------------------------------------------------
+
+def test_plan_auto(H):
+    assert auto(H, kdq_last=125, shard=1000) == (1, 0, 125, 64)                                 # 125 * 8 = 1000: not MORE than the shard
+    assert auto(H, kdq_last=126, shard=1000) == (0, 255, -1, 1024)                              # back-off: this pass is the first of 256 kd passes
+    assert auto(H, kdq_last=126, shard=1000, ahead=1) == (1, 0, 126, 64)                        # a tree was built ahead: an AUTO pass whatever the counts say
+    assert auto(H, kdq_last=300, shard=1000, div=1) == (1, 0, 300, 1024) and auto(H, kdq_last=300, shard=1000, div=4) == (0, 255, -1, 1024)
+    assert auto(H, backoff=5) == (0, 4, -1, 1024) and auto(H, backoff=1) == (0, 0, -1, 1024) and auto(H, backoff=0) == (1, 0, -1, 1024)
+    assert auto(H, backoff=5, kdq_last=10**6) == (0, 4, 10**6, 1024)                            # (already backing off: the count is kept)
+    assert auto(H, backoff=5, ahead=1) == (1, 5, -1, 1024)
+    assert auto(H, fits=0) == (0, 0, -1, 1024) and auto(H, tracked=1) == (0, 0, -1, 1024)
+    assert auto(H, fits=0, ahead=1)[0] == 1 and auto(H, tracked=1, ahead=1)[0] == 1
+    assert [auto(H, kdq_last=k)[3] for k in (-1, 0, 1, 256, 257, 12500)] == [1024, 64, 64, 64, 1024, 1024]
+    nxt = lambda fits=1, tracked=0, part=0, last=-1, div=8, backoff=0, shard=1000: H.forms_auto_next(fits, tracked, part, last, div, backoff, shard)
+    assert [nxt(), nxt(fits=0), nxt(tracked=1), nxt(part=1), nxt(backoff=1), nxt(last=125), nxt(last=126)] == [1, 0, 0, 0, 0, 1, 0]
+    tail = lambda ok=1, wv=1, seq=7, last=0, mx=0: H.forms_auto_tail_form(ok, wv, seq, last, mx)
+    assert [tail(), tail(last=-1), tail(last=1), tail(ok=0), tail(wv=0), tail(seq=0)] == [1, 0, 0, 0, 0, 0]
+    assert [tail(last=k, mx=8) for k in (-1, 0, 8, 9)] == [0, 1, 1, 0]
+
+
+# ---- the kd build -----------------------------------------------------------------------------------------------------------------------------------
+
+def test_plan_kd_build(H, clean_env):
+    P = lambda top, wave_max, block, level_passes, first_single, grid, ticket, levels, sgrid: dict(
+        top=top, wave_max=wave_max, block=block, level_passes=level_passes, first_single=first_single, grid=grid, ticket=ticket, levels=levels, sgrid=sgrid)
+    assert kd(H, 700) == P(1, 768, 768, 0, 0, 0, 0, 0, 5)                                       # one workgroup: no top, no level passes
+    assert kd(H, 1000) == P(1, 625, 768, 0, 0, 0, 0, 1, 8)                                      # k_kd_top, cap 768: 1.25 x 500
+    assert kd(H, 1000, beside=1) == P(0, 1024, 1024, 0, 0, 0, 0, 0, 5)                          # beside the re-plans: cap 1024, the tree fits one workgroup
+    assert kd(H, 4096) == P(1, 640, 768, 0, 0, 0, 0, 1, 27)                                     # 1.25 x 512
+    assert kd(H, 4097)['top'] == 0
+    assert kd(H, 16384, beside=1) == P(0, 640, 768, 1, 4, 8 + 51 + 8, 0, 5, 104)
+    assert kd(H, 100000) == P(0, 977, 1024, 1, 7, 48 + 204 + 8, 0, 8, 411)                      # 1.25 x 781.25
+    assert kd(H, 4096, KD_TOP=0) == P(0, 1280, 1280, 1, 2, 2 + 6 + 8, 0, 3, 14)                 # 1.25 x 1024, cap 1536
+    assert [(kd(H, 100000, hint=h)['first_single'], kd(H, 100000, hint=h)['levels']) for h in (0, 1, 5, 39, 100)] == [(7, 8), (0, 1), (4, 5), (38, 39), (38, 39)]
+    assert kd(H, 100000, hint=5) == dict(kd(H, 100000), first_single=4, levels=5)               # only where the tail launch takes over
+    assert [kd(H, 100000, chunk_cap=1 << 30, rank_cap=r)['ticket'] for r in (259, 260)] == [1, 0]
+    assert kd(H, 100000, KD_TICKET=1)['ticket'] == 1 and kd(H, 100000, chunk_cap=100)['grid'] == 100
+    for env, cap, wave_max, block in (('100', 256, 245, 256), ('512', 512, 489, 512), ('5000', 1536, 977, 1024)):      # 1.25 x 195.3125 / 390.625 / 781.25
+        clean_env.setenv('SCA_KD_WAVE_CAP', env)
+        t = from_env(H)
+        assert t['SCA_KD_WAVE_CAP'] == cap
+        got = kd(H, 100000, t=(C.c_int * len(t))(*t.values()))
+        assert (got['wave_max'], got['block']) == (wave_max, block), env

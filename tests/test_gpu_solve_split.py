@@ -171,9 +171,9 @@ def test_long_tracked_episode_all_forms_against_the_plain_ones(S, monkeypatch):
     sols = []
     for plain in (True, False):
         if plain:
-            monkeypatch.setenv('SCA_SOLVE_SPLIT', '0'); monkeypatch.setenv('SCA_TRACKER_NOFUSE', '1'); monkeypatch.delenv('SCA_TRACKER_FUSE', raising=False)
+            monkeypatch.setenv('SCA_SOLVE_SPLIT', '0'); monkeypatch.delenv('SCA_TRACKER_FUSE', raising=False)
         else:                                          # (the fused tracker kernel is opt-in since round 3: covered here)
-            monkeypatch.delenv('SCA_SOLVE_SPLIT', raising=False); monkeypatch.delenv('SCA_TRACKER_NOFUSE', raising=False); monkeypatch.setenv('SCA_TRACKER_FUSE', '1')
+            monkeypatch.delenv('SCA_SOLVE_SPLIT', raising=False); monkeypatch.setenv('SCA_TRACKER_FUSE', '1')
         sol = S.BatchedSolver(max_agents=n)
         sol.set_obstacles(np.zeros((0, 3)), np.zeros(0))
         sol.set_agents(np.full(n, 0.5), np.ones(n), sc['goal'][:, :3], policy, S.zaxis_flags(sc['start'], sc['goal']),
