@@ -1,0 +1,53 @@
+#!/usr/bin/env python3
+"""Many small episodes as ONE batch: the six policies x circle / random scenes of 100 drones, stepped by one context (sca_amd.scenes),
+one metrics row per scene -- what a loop over the reference's run_example/run_*.py scripts produces, scene by scene.
+
+    python examples/run_scenes.py
+    python examples/run_scenes.py --agents 50 --seeds 8 --max-steps 3000
+"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from sca_amd import env as E, metrics, scenarios                      # noqa: E402
+from sca_amd.scenes import SceneBatch                                 # noqa: E402
+
+POLICIES = {'sca': E.SCAPolicy, 'rvo': E.RVO3DPolicy, 'srvo': E.SRVO3DPolicy, 'orca': E.ORCA3DPolicy, 'orca-lp': E.ORCA3DPolicyOfficial,
+            'rvo-dubins': E.RVO3dDubinsPolicy}
+
+
+def build_agents(sc, policy):
+    return [E.Agent(start_pos=list(sc['start'][i]), goal_pos=list(sc['goal'][i]), vel=[0.0, 0.0, 0.0], radius=0.5, pref_speed=1.0,
+                    policy=policy, id=i) for i in range(len(sc['start']))]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--agents', type=int, default=100)
+    ap.add_argument('--seeds', type=int, default=3, help='random scenes per policy (beside one circle scene)')
+    ap.add_argument('--max-steps', type=int, default=20000)
+    args = ap.parse_args()
+
+    names, scenes = [], []
+    for pname, pol in POLICIES.items():
+        names.append((pname, 'circle'))
+        scenes.append(build_agents(scenarios.circle(args.agents), pol))
+        for seed in range(args.seeds):
+            names.append((pname, 'random seed %d' % seed))
+            scenes.append(build_agents(scenarios.random_cube(args.agents, seed=seed), pol))
+    batch = SceneBatch(scenes, [], device_tracker=True)
+    t0, steps = time.time(), 0
+    while steps < args.max_steps and not batch.step():
+        steps += 1
+    print('%d scenes, %d agents: %d batch steps, %.2f s' % (len(batch), sum(len(s) for s in scenes), steps + 1, time.time() - t0))
+    for s, (pname, what) in enumerate(names):
+        m = metrics.episode_metrics(batch.env(s))
+        print('%-10s %-14s steps %5d %s  ' % (pname, what, batch.steps[s], 'done' if batch.done[s] else 'RUNNING') +
+              '  '.join('%s %.4g' % (k, m[k]) for k in ('SuccessRate', 'ExtraTime', 'ExtraDistance', 'AverageSpeed')))
+    batch.close()
+
+
+if __name__ == '__main__':
+    main()

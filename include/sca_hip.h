@@ -165,6 +165,30 @@ int sca_set_paths(sca_ctx *ctx, int n, const int32_t *offsets /*n+1*/, const dou
 int sca_get_path_state(sca_ctx *ctx, int32_t *remaining /*n, nullable*/, double *now_goal /*n*3, nullable*/);
 int sca_set_path_state(sca_ctx *ctx, const int32_t *remaining /*n*/, const double *now_goal /*n*3*/);
 
+/* Scene batches: ONE context steps many isolated episodes.  Scene s is the contiguous agent range [offsets[s], offsets[s+1]); agents of
+ * different scenes never appear in each other's neighbour lists or collision tests, every scene has its own kd-tree, its own carried
+ * permutation and its own `done`, and for every scene every value the context produces is bit for bit what a context holding that scene
+ * alone produces.  Obstacles (sca_set_obstacles) are shared by all scenes; everything per agent (sca_set_agent_params, the device tracker,
+ * sca_set_paths, the history log, sca_step_host) works as without scenes.  sca_version() is unchanged: detect the feature by the symbol.
+ *   sca_set_scenes      after sca_set_agents (SCA_ERR_STATE before; sca_set_agents clears the scenes).  offsets[0] == 0, strictly increasing,
+ *                       offsets[nscenes] == n (SCA_ERR_ARG); every scene at most 1536 agents, KD_WAVE_CAP -- a scene's tree is built by one
+ *                       workgroup (SCA_ERR_UNSUPPORTED, the message names the limit).  nscenes == 0 or offsets == NULL: no scenes, a plain
+ *                       context again.  Resets the permutation to the identity (per scene 0 .. n_s-1 in scene-local terms) and the per-scene
+ *                       counters.  A refused call has changed nothing.
+ *   sca_get_scene_state active[s]: agents of scene s the next step would serve; steps[s]: steps taken while scene s was live = the number
+ *                       of env.step() calls the reference's `while not env.step()` makes for that scene; it stops counting when active[s]
+ *                       reaches 0.  Kept on the device, read back only by this call (one synchronisation).  SCA_ERR_STATE without scenes or state.
+ * With scenes set: sca_env_step / sca_step_host / sca_active_count / sca_env_update report the sum over the scenes, so `while (active)` runs
+ * until the last scene is done; a finished scene is inert (all its agents are flagged, its state -- velocities, step_num and headings
+ * included, which a running env's update would still touch for a done agent -- and its permutation stay what they were at its last step,
+ * its action rows are zero).  sca_get_kd_perm / sca_set_kd_perm carry GLOBAL ids: within scene s the
+ * values are offsets[s] + the scene's own permutation, and sca_set_kd_perm refuses (SCA_ERR_ARG) a permutation that moves an id out of its
+ * scene.  Neighbour modes: SCA_NBR_KDTREE is the scene form and SCA_NBR_AUTO resolves to it; SCA_NBR_GRID and SCA_NBR_KDTREE_HOSTBUILD are
+ * SCA_ERR_UNSUPPORTED.  Also SCA_ERR_UNSUPPORTED with scenes set -- and sca_set_scenes while they are active --: sca_set_shard (other than
+ * the whole range), sca_comm_init, sca_partition_init, sca_get_kd_tree.  A pass reports SCA_FORM_SCENES. */
+int sca_set_scenes(sca_ctx *ctx, int nscenes, const int32_t *offsets /*nscenes+1*/);
+int sca_get_scene_state(sca_ctx *ctx, int32_t *active /*nscenes, nullable*/, int32_t *steps /*nscenes, nullable*/);
+
 /* the hot path ----------------------------------------------------------------------------------- */
 int sca_policy_pass(sca_ctx *ctx, int neighbor_mode);
 int sca_get_actions(sca_ctx *ctx, float *action /*n*7*/);
@@ -316,7 +340,8 @@ int sca_last_exchange_ms(sca_ctx *ctx, float *exchange_ms);
  *   SCA_FORM_ACTION_FB     k_action_fb: shards of up to 16 384 agents run the fallback sweep inside the epilogue's launch (no k_fallback launch)
  *   SCA_FORM_AUTO_TAIL     SCA_NBR_AUTO: the kd query of the listed agents ran inside the pass's grid query (its last workgroup, from the tree the pass's
  *                          build publishes): no k_neighbors_kd_auto launch, no stream wait in front of the solve
- *   SCA_FORM_WAYPOINTS     k_waypoint ran at the head of the pass (waypoint lists are set: sca_set_paths) */
+ *   SCA_FORM_WAYPOINTS     k_waypoint ran at the head of the pass (waypoint lists are set: sca_set_paths)
+ *   SCA_FORM_SCENES        scenes are set (sca_set_scenes): the forest build and the scene forms of the neighbour query ran */
 #define SCA_FORM_SOLVE_SPLIT 1
 #define SCA_FORM_TRACK_FUSED 2
 #define SCA_FORM_REPLAN_LANE 4
@@ -326,6 +351,7 @@ int sca_last_exchange_ms(sca_ctx *ctx, float *exchange_ms);
 #define SCA_FORM_ACTION_FB 64
 #define SCA_FORM_AUTO_TAIL 128
 #define SCA_FORM_WAYPOINTS 256
+#define SCA_FORM_SCENES 512
 int sca_last_pass_forms(sca_ctx *ctx, int *forms);
 /* SCA_NBR_AUTO statistics since the last reset: out4 = {AUTO passes, agents the grid query listed for the kd query (sum over the passes), the
  * largest list, passes in which somebody was listed}.  A pass with nobody listed never waits for the kd stream. */

@@ -51,6 +51,8 @@ SIGNATURES = {
     'sca_set_vpref': (C.c_int, [C.c_void_p, dp, bp]),
     'sca_set_paths': (C.c_int, [C.c_void_p, C.c_int, ip, dp]),
     'sca_get_path_state': (C.c_int, [C.c_void_p, ip, dp]),
+    'sca_set_scenes': (C.c_int, [C.c_void_p, C.c_int, ip]),
+    'sca_get_scene_state': (C.c_int, [C.c_void_p, ip, ip]),
     'sca_set_path_state': (C.c_int, [C.c_void_p, ip, dp]),
     'sca_policy_pass': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_get_actions': (C.c_int, [C.c_void_p, fp]),

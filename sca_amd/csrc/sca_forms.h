@@ -292,4 +292,18 @@ inline KdBuildPlan plan_kd_build(const Tunables &t, int n, bool beside, int sing
     return p;
 }
 
+// The forest of a context with scenes (sca_set_scenes): every scene is a root job of k_kd_block -- no top, no level passes.  The instance is
+// the smallest that holds the largest scene, one workgroup per scene up to the grid cap of the plain build, strided beyond it.
+constexpr int KD_FOREST_GRID_MAX = 1024;
+struct KdForestPlan {
+    int block;            // the k_kd_block<block, block / 2> instance
+    int grid;             // its workgroups
+};
+inline KdForestPlan plan_kd_forest(int largest_scene, int nscenes) {
+    KdForestPlan p{};
+    p.block = largest_scene <= 256 ? 256 : largest_scene <= 512 ? 512 : largest_scene <= 768 ? 768 : largest_scene <= 1024 ? 1024 : largest_scene <= 1280 ? 1280 : KD_WAVE_CAP;
+    p.grid = std::max(1, std::min(KD_FOREST_GRID_MAX, nscenes));
+    return p;
+}
+
 }  // namespace sca

@@ -24,6 +24,8 @@
 #include "sca_partition.hip.h"
 #include "sca_hostio.hip.h"
 #include "sca_forms.h"
+#include "sca_scenes.h"
+#include "sca_scenes.hip.h"
 
 using namespace sca;
 
@@ -293,6 +295,14 @@ struct sca_ctx {
     // pinned host state block (sca_host_state_get / sca_step_host): allocated once for max_n, freed by sca_destroy
     uint8_t *hs_host = nullptr;         // page-locked, the caller reads and writes it in place
     uint8_t *hs_dev = nullptr;          // the staging buffer of the staged form (Tunables::hs_staged): same size and layout
+    // scene batches (sca_set_scenes, sca_scenes.hip.h): while they are set a pass builds a forest and runs the scene forms of K1 and K4
+    bool scenes_on = false;
+    SceneView scn{};                    // device arrays; live | prev | steps are one allocation (scene_counters)
+    int32_t *scene_counters = nullptr;  // [nscenes * (SCENE_LINE + 2)]
+    std::vector<int32_t> h_scene_off;   // [nscenes + 1] the offsets as set
+    int scene_largest = 0;              // agents of the largest scene: picks the k_kd_block instance
+    bool scene_live_valid = false;      // SceneView::live describes the current records (else: k_scene_recount before anybody reads it)
+    bool scene_begun = false;           // a policy pass has opened a step (scene_begin_one) that no env update has closed yet
 };
 
 #define CHK(ctx, call)                                                                         \
@@ -878,6 +888,7 @@ void sca_destroy(sca_ctx *c) {
     (void)tracker_free(c);
     (void)part_free(c);
     for (void *p : {(void *)c->path.off, (void *)c->path.pts, (void *)c->path.rem, (void *)c->path.now_goal}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->scn.scene_of, (void *)c->scn.offsets, (void *)c->scene_counters, (void *)c->scn.heading_keep}) if (p) (void)hipFree(p);
     if (c->h_done) { (void)hipHostFree(c->h_done); c->h_done = nullptr; }
     if (c->hs_host) { (void)hipHostFree(c->hs_host); c->hs_host = nullptr; }
     if (c->hs_dev) { (void)hipFree(c->hs_dev); c->hs_dev = nullptr; }
@@ -1016,6 +1027,7 @@ int sca_set_agent_params(sca_ctx *c, int n, const double *neighbor_dist, const i
     return 0;
 }
 
+static int scenes_clear(sca_ctx *c);
 int sca_set_agents(sca_ctx *c, int n, const double *radius, const double *pref_speed, const double *goal,
                    const uint8_t *policy, const uint8_t *zaxis, const double *max_run_dist) {
     API_ENTER(c);
@@ -1031,6 +1043,7 @@ int sca_set_agents(sca_ctx *c, int n, const double *radius, const double *pref_s
     if (int r = agent_params_clear(c)) return r;                      // ... and so do the agents' own solver attributes
     if (int r = part_free(c)) return r;                               // ... and so do the partition's lists
     if (int r = paths_clear(c, false)) return r;                      // ... and so do the waypoint lists (vpref_mode is reset below)
+    if (int r = scenes_clear(c)) return r;                            // ... and so do the scenes
     if (c->comm && n % c->comm_nranks) { c->err = "agent count must be a multiple of the communicator's rank count"; return SCA_ERR_ARG; }
     c->n = n; c->d.n = n; c->d.shard_begin = 0; c->d.shard_count = n;
     if (c->comm) { c->d.shard_count = n / c->comm_nranks; c->d.shard_begin = c->comm_rank * c->d.shard_count; }
@@ -1089,6 +1102,7 @@ int sca_set_state(sca_ctx *c, const double *pos, const float *vel, const double 
     if (step_num) CHK(c, hipMemcpyAsync(c->d.step_num, step_num, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
     CHK(c, hipStreamSynchronize(c->stream));
     c->state_set = true; c->state_fresh = true;
+    c->scene_live_valid = false; c->scene_begun = false;
     if (c->part_on) return part_classify(c);                              // a complete state again: ownership follows from it
     return 0;
 }
@@ -1121,6 +1135,13 @@ int sca_get_state(sca_ctx *c, double *pos, float *vel, double *heading, uint8_t 
 int sca_set_kd_perm(sca_ctx *c, const int32_t *perm) {
     API_ENTER(c);
     ARG(c, perm && c->agents_set);
+    if (c->scenes_on) {
+        const int at = scenes_perm_fault(c->scn.nscenes, c->h_scene_off.data(), perm);
+        if (at >= 0) {
+            c->err = "sca_set_kd_perm: position " + std::to_string(at) + " holds agent " + std::to_string(perm[at]) + ", which is not of that position's scene (sca_set_scenes)";
+            return SCA_ERR_ARG;
+        }
+    }
     c->h_perm.assign(perm, perm + c->n);
     c->perm_on_device = false;
     return 0;
@@ -1139,6 +1160,7 @@ int sca_get_kd_perm(sca_ctx *c, int32_t *perm) {
 int sca_get_kd_tree(sca_ctx *c, double *tree_out) {
     API_ENTER(c);
     ARG(c, tree_out && c->agents_set);
+    if (c->scenes_on) { c->err = "sca_get_kd_tree with scenes set (sca_set_scenes): the context holds a forest, one tree per scene"; return SCA_ERR_UNSUPPORTED; }
     const int n = c->n;
     std::vector<KdNode> t((size_t)2 * n, KdNode{});
     if (!c->perm_on_device) {
@@ -1282,6 +1304,87 @@ int sca_set_path_state(sca_ctx *c, const int32_t *remaining, const double *now_g
     return 0;
 }
 
+// ---- scene batches (sca_scenes.h: the rules; sca_scenes.hip.h: the kernels) -----------------------------------------------------------------
+static int scenes_clear(sca_ctx *c) {
+    if (!c->scenes_on) return 0;
+    CHK(c, hipStreamSynchronize(c->stream));
+    c->scenes_on = false;
+    c->h_scene_off.clear();
+    c->scene_largest = 0; c->scene_live_valid = false; c->scene_begun = false;
+    return 0;
+}
+int sca_set_scenes(sca_ctx *c, int nscenes, const int32_t *offsets) {
+    API_ENTER(c);
+    if (!c->agents_set) { c->err = "sca_set_agents first"; return SCA_ERR_STATE; }
+    const int n = c->n;
+    const SceneCheck k = scenes_check(n, nscenes, offsets);
+    if (k.fault != SCENES_OK && k.fault != SCENES_NONE) {
+        const std::string at = k.scene >= 0 ? " (scene " + std::to_string(k.scene) + ")" : "";
+        switch (k.fault) {
+        case SCENES_BAD_COUNT: c->err = "sca_set_scenes: nscenes must be 0 .. the agent count " + std::to_string(n); break;
+        case SCENES_BAD_START: c->err = "sca_set_scenes: offsets[0] must be 0"; break;
+        case SCENES_NOT_INCREASING: c->err = "sca_set_scenes: offsets must increase strictly -- no empty scene" + at; break;
+        case SCENES_BAD_END: c->err = "sca_set_scenes: offsets[nscenes] must be the agent count " + std::to_string(n) + at; break;
+        default: c->err = "sca_set_scenes: a scene of " + std::to_string(k.largest) + " agents" + at + ": a scene holds at most KD_WAVE_CAP = " + std::to_string(KD_WAVE_CAP) + " (its tree is one workgroup's)";
+        }
+        return scenes_error_code(k.fault);
+    }
+    if (k.fault == SCENES_NONE) return scenes_clear(c);
+    if (c->comm) { c->err = "sca_set_scenes with an active communicator (sca_comm_init): scenes are one rank's"; return SCA_ERR_UNSUPPORTED; }
+    if (c->part_on) { c->err = "sca_set_scenes under the cell-owner partition (sca_partition_init): a mode of SCA_NBR_GRID, which has no scene form"; return SCA_ERR_UNSUPPORTED; }
+    if (c->d.shard_begin != 0 || c->d.shard_count != n) { c->err = "sca_set_scenes on a shard (sca_set_shard): scenes are stepped by one rank, whole"; return SCA_ERR_UNSUPPORTED; }
+    CHK(c, hipStreamSynchronize(c->stream));
+    for (void *p : {(void *)c->scn.scene_of, (void *)c->scn.offsets, (void *)c->scene_counters, (void *)c->scn.heading_keep}) if (p) (void)hipFree(p);
+    c->scn = SceneView{}; c->scene_counters = nullptr; c->scenes_on = false;
+    int32_t *so = nullptr, *off = nullptr;
+    CHK(c, hipMalloc((void **)&so, sizeof(int32_t) * (size_t)n));
+    c->scn.scene_of = so;
+    CHK(c, hipMalloc((void **)&off, sizeof(int32_t) * ((size_t)nscenes + 1)));
+    c->scn.offsets = off;
+    const size_t words = (size_t)nscenes * (SCENE_LINE + 2);
+    CHK(c, hipMalloc((void **)&c->scene_counters, sizeof(int32_t) * words));
+    c->scn.live = c->scene_counters; c->scn.prev = c->scene_counters + (size_t)nscenes * SCENE_LINE; c->scn.steps = c->scn.prev + nscenes;
+    c->scn.nscenes = nscenes;
+    CHK(c, hipMalloc((void **)&c->scn.heading_keep, sizeof(double) * 3 * (size_t)n));       // (written by k_scene_recount before any step reads it)
+    std::vector<int32_t> of((size_t)n);
+    for (int sc = 0; sc < nscenes; sc++) for (int a = offsets[sc]; a < offsets[sc + 1]; a++) of[a] = sc;
+    CHK(c, hipMemcpyAsync(so, of.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    CHK(c, hipMemcpyAsync(off, offsets, sizeof(int32_t) * ((size_t)nscenes + 1), hipMemcpyHostToDevice, c->stream));
+    CHK(c, hipMemsetAsync(c->scene_counters, 0, sizeof(int32_t) * words, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    c->h_scene_off.assign(offsets, offsets + nscenes + 1);
+    c->scene_largest = k.largest;
+    for (int i = 0; i < n; i++) c->h_perm[i] = i;                     // every scene's kdTree.agentIDs starts as 0 .. n_s - 1 (kdTree.py:43-45)
+    c->perm_on_device = false;
+    c->scene_live_valid = false; c->scene_begun = false;
+    c->kd_single_hint = 0; c->kd_gen++; c->kd_ahead = false; c->kdq_last = -1; c->auto_backoff = 0; c->near_valid = false;
+    c->nbr_mode = SCA_NBR_KDTREE;
+    c->scenes_on = true;
+    return 0;
+}
+// SceneView::live from the records, where the state came from outside since the last env update (on `s`, which the records are final on)
+static int scenes_recount(sca_ctx *c, hipStream_t s) {
+    if (c->scene_live_valid) return 0;
+    hipLaunchKernelGGL(k_scene_recount, dim3((c->scn.nscenes + 3) / 4), dim3(256), 0, s, c->d, c->scn);
+    CHK(c, hipGetLastError());
+    c->scene_live_valid = true;
+    return 0;
+}
+int sca_get_scene_state(sca_ctx *c, int32_t *active, int32_t *steps) {
+    API_ENTER(c);
+    if (!c->scenes_on) { c->err = "no scenes (sca_set_scenes)"; return SCA_ERR_STATE; }
+    if (!c->state_set) { c->err = "sca_set_state first"; return SCA_ERR_STATE; }
+    const int B = c->scn.nscenes;
+    if (!c->scene_begun) { if (int r = scenes_recount(c, c->stream)) return r; }
+    std::vector<int32_t> h((size_t)B * (SCENE_LINE + 2));
+    CHK(c, hipMemcpyAsync(h.data(), c->scene_counters, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    // (between a policy pass and its env update the step under way has emptied `live`: what it found is in `prev`)
+    if (active) for (int sc = 0; sc < B; sc++) active[sc] = c->scene_begun ? h[(size_t)B * SCENE_LINE + sc] : h[(size_t)sc * SCENE_LINE];
+    if (steps) for (int sc = 0; sc < B; sc++) steps[sc] = h[(size_t)B * (SCENE_LINE + 1) + sc];
+    return 0;
+}
+
 // KDTree.buildAgentTree (mampenv.py:28) on the HOST from a position read-back (SCA_NBR_KDTREE_HOSTBUILD: the A/B reference of
 // the device build below, which is what SCA_NBR_KDTREE runs).
 static int build_agent_tree(sca_ctx *c) {
@@ -1326,7 +1429,13 @@ static int build_agent_tree_device(sca_ctx *c, hipStream_t ks, const DeviceView 
         c->kd_ev_pending = false;
     }
     // plan (no size limit: a level with more chunks than the chip holds at once takes its chunks by arrival, k_kd_lv_rank<true>)
-    const KdBuildPlan B = plan_kd_build(c->tun, n, c->trk_on && c->trk_in_pass && ks != c->stream, c->kd_single_hint, c->kd.chunk_cap, c->kd_rank_capacity);
+    // (scenes: the forest plan -- every scene a root job of k_kd_block, no top, no level passes, no statistics)
+    KdBuildPlan B{};
+    if (c->scenes_on) {
+        const KdForestPlan F = plan_kd_forest(c->scene_largest, c->scn.nscenes);
+        B.wave_max = F.block; B.block = F.block; B.sgrid = F.grid;
+        if (int r = scenes_recount(c, ks)) return r;                   // (a state from outside: the live counts the step opens with)
+    } else B = plan_kd_build(c->tun, n, c->trk_on && c->trk_in_pass && ks != c->stream, c->kd_single_hint, c->kd.chunk_cap, c->kd_rank_capacity);
     if (B.top && KT_M / (B.wave_max + 1) >= KT_NODES) { c->err = "k_kd_top: wave_max below its table bound"; return SCA_ERR_STATE; }   // (static_assert'ed unreachable)
     // enqueue
     if (!c->perm_on_device) {
@@ -1346,6 +1455,11 @@ static int build_agent_tree_device(sca_ctx *c, hipStream_t ks, const DeviceView 
         LAUNCH_REC(c, c->ev_auto_gather[c->auto_builds & 1u], k_kd_gather, dim3((n + 255) / 256), dim3(256), ks, d, c->kd, c->P);
         c->auto_builds++;
     } else hipLaunchKernelGGL(k_kd_gather, dim3((n + 255) / 256), dim3(256), 0, ks, d, c->kd, c->P);
+    if (c->scenes_on) {
+        // the forest's job table behind the gather (which rewrites the single root job and the counts on every build); opens the step
+        hipLaunchKernelGGL(k_kd_scene_jobs, dim3((c->scn.nscenes + 255) / 256), dim3(256), 0, ks, c->kd, c->scn, c->scene_begun ? 0 : 1);
+        c->scene_begun = true;
+    }
     if (B.top && B.levels) hipLaunchKernelGGL(k_kd_top, dim3(1), dim3(KT_T), 0, ks, d, c->kd);
     if (B.level_passes) {
         for (int l = 0; l < B.first_single; l++) {
@@ -1591,10 +1705,15 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
     // SCA_NBR_AUTO: an AUTO pass, or a plain kd pass where that cannot help (plan_auto; the cell-owner partition has its own structures)
     bool auto_mode = false;
     int kdq_blocks = KDQ_BLOCKS;
+    if (c->scenes_on && scenes_neighbor_mode(mode) < 0) {
+        c->err = "scenes are set (sca_set_scenes): the scene form of the neighbour search is SCA_NBR_KDTREE (SCA_NBR_AUTO resolves to it)";
+        return SCA_ERR_UNSUPPORTED;
+    }
     if (mode == SCA_NBR_AUTO) {
         double ar, orr;
         collide_reach(c, ar, orr);
-        const bool fits = c->max_radius + ar <= c->P.neighbor_dist && c->max_radius + orr <= c->P.neighbor_dist;
+        // (scenes: the grid's cell key carries no scene id -- one more place where it cannot help)
+        const bool fits = !c->scenes_on && c->max_radius + ar <= c->P.neighbor_dist && c->max_radius + orr <= c->P.neighbor_dist;
         if (c->part_on) { c->err = "the cell-owner partition is a mode of SCA_NBR_GRID"; return SCA_ERR_UNSUPPORTED; }
         if (int r = auto_prepare(c)) return r;
         if (c->kdq_pending && hipEventQuery(c->ev_auto_cnt) == hipSuccess) { c->kdq_last = c->kdq_host[0]; c->kdq_pending = false; }   // poll
@@ -1638,7 +1757,7 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
     }
     const bool split = S.split, solve_fb = S.solve_fb;
     c->d.lp_kernel = S.lp_kernel;
-    int forms = S.forms | (c->paths_on ? SCA_FORM_WAYPOINTS : 0);     // (the waypoint bit is state, not a choice)
+    int forms = S.forms | (c->paths_on ? SCA_FORM_WAYPOINTS : 0) | (c->scenes_on ? SCA_FORM_SCENES : 0);     // (the waypoint and scene bits are state, not a choice)
     c->kd.skip_prep = overlap ? 1 : 0;
     c->grid.skip_prep = overlap ? 1 : 0;
     if (mode == SCA_NBR_GRID) {
@@ -1724,6 +1843,12 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
     } else if (mode == SCA_NBR_GRID) {
         const auto k1 = obs ? k_neighbors_grid<false, true> : k_neighbors_grid<false, false>;
         LAUNCH_OPT(c, k1_stop, k1, k1p_grid, k1p_block, ns, d, c->grid, c->P, agent_reach, obs_reach, c->max_radius);
+    } else if (c->scenes_on && S.packed) {
+        const auto k1 = obs ? k_neighbors_kd4_scenes<true> : k_neighbors_kd4_scenes<false>;
+        LAUNCH_OPT(c, k1_stop, k1, k1p_grid, k1p_block, ns, d, c->P, agent_reach, obs_reach, c->max_radius, c->scn);
+    } else if (c->scenes_on) {
+        const auto k1 = obs ? k_neighbors_kd_scenes<true> : k_neighbors_kd_scenes<false>;
+        LAUNCH_OPT(c, k1_stop, k1, dim3(std::min((cnt + K1_WAVES - 1) / K1_WAVES, MAX_GRID)), dim3(K1_WAVES * 64), ns, d, c->P, agent_reach, obs_reach, c->max_radius, c->scn);
     } else if (S.packed) {
         const auto k1 = obs ? k_neighbors_kd4<true> : k_neighbors_kd4<false>;
         LAUNCH_OPT(c, k1_stop, k1, k1p_grid, k1p_block, ns, d, c->P, agent_reach, obs_reach, c->max_radius);
@@ -1843,13 +1968,20 @@ static int launch_collide_finish(sca_ctx *c, bool timed) {
         c->nbr_stream = c->stream;
         if (int r = build_agent_grid_device(c)) return r;
     }
+    if (c->scenes_on && !c->scene_begun) {                                // no policy pass before: the update opens the step itself
+        if (int r = scenes_recount(c, c->stream)) return r;
+        hipLaunchKernelGGL(k_scene_begin, dim3((c->scn.nscenes + 255) / 256), dim3(256), 0, c->stream, c->scn);
+    }
     c->near_valid = false;
     const dim3 k4grid((cnt + K4_WAVES * K4_APW - 1) / (K4_WAVES * K4_APW));
     // (the event that rides on the step's last kernel, if sca_run_steps asked for one: the next pass's fork)
     const bool others = c->part_on || cnt < d.n;
     const hipEvent_t k4_stop = others ? nullptr : c->finish_stop, others_stop = others ? c->finish_stop : nullptr;
     const int fresh = c->state_fresh ? 1 : 0;
-    if (c->nbr_mode == SCA_NBR_GRID)
+    if (c->scenes_on) {
+        LAUNCH_OPT(c, k4_stop, k_collide_finish_scenes, k4grid, dim3(K4_WAVES * 64), c->stream, d, c->P, agent_reach, obs_reach, fresh, c->scn);
+        c->scene_begun = false; c->scene_live_valid = true;
+    } else if (c->nbr_mode == SCA_NBR_GRID)
         LAUNCH_OPT(c, k4_stop, k_collide_finish_grid, k4grid, dim3(K4_WAVES * 64), c->stream, d, c->grid, c->P, agent_reach, obs_reach, fresh);
     else
         LAUNCH_OPT(c, k4_stop, k_collide_finish, k4grid, dim3(K4_WAVES * 64), c->stream, d, c->P, agent_reach, obs_reach, fresh);
@@ -2122,6 +2254,7 @@ int sca_step_host(sca_ctx *c, int neighbor_mode, uint32_t in_mask, int *active) 
             c->h_pos_valid = false;
             c->near_valid = false;
             c->state_set = true; c->state_fresh = true;
+            c->scene_live_valid = false; c->scene_begun = false;
         }
     }
     if (int r = run_steps_guarded(c, 1, neighbor_mode, false)) return r;  // integrate fused into the pass, k_collide_finish; joins the kd stream
@@ -2194,6 +2327,7 @@ int sca_comm_init(sca_ctx *c, int rank, int nranks, const void *unique_id) {
     if (!c->agents_set) { c->err = "sca_set_agents first"; return SCA_ERR_STATE; }
     if (c->comm) { c->err = "communicator already initialised (sca_comm_destroy first)"; return SCA_ERR_STATE; }
     if (c->part_on) { c->err = "sca_comm_init with the cell-owner partition active"; return SCA_ERR_STATE; }
+    if (c->scenes_on) { c->err = "sca_comm_init with scenes set (sca_set_scenes): scenes are one rank's"; return SCA_ERR_UNSUPPORTED; }
     if (c->n % nranks) { c->err = "agent count must be a multiple of the rank count"; return SCA_ERR_ARG; }
     if (const char *e = rccl_load()) { c->err = e; return SCA_ERR_UNSUPPORTED; }
     CHK(c, hipSetDevice(c->device));
@@ -2301,6 +2435,7 @@ int sca_partition_init(sca_ctx *c, int rank, int nranks, int axis, const double 
     ARG(c, nranks >= 1 && rank >= 0 && rank < nranks && axis >= 0 && axis <= 2 && cap_halo >= 0 && cap_mig >= 0);
     if (!c->agents_set || !c->state_set) { c->err = "sca_set_agents and sca_set_state (the complete state, on every rank) first"; return SCA_ERR_STATE; }
     if (c->comm) { c->err = "sca_partition_init with an active communicator (the all-gather mode)"; return SCA_ERR_STATE; }
+    if (c->scenes_on) { c->err = "sca_partition_init with scenes set (sca_set_scenes): a mode of SCA_NBR_GRID, which has no scene form"; return SCA_ERR_UNSUPPORTED; }
     if (c->paths_on) { c->err = "sca_partition_init with waypoint lists set (sca_set_paths): path state does not migrate with the agents"; return SCA_ERR_UNSUPPORTED; }
     if (int r = part_free(c)) return r;
     const int n = c->n;
@@ -2698,6 +2833,7 @@ int sca_set_shard(sca_ctx *c, int begin, int count) {
     // with a communicator the shard IS rank * n / nranks: the in-place ncclAllGather of sca_run_steps relies on it
     if (c->part_on) { c->err = "sca_set_shard with the cell-owner partition active (sca_partition_disable first)"; return SCA_ERR_STATE; }
     if (c->comm) { c->err = "sca_set_shard with an active communicator (the shard follows from rank / nranks; sca_comm_destroy first)"; return SCA_ERR_STATE; }
+    if (c->scenes_on && (begin != 0 || count != c->n)) { c->err = "sca_set_shard with scenes set (sca_set_scenes): scenes are stepped by one rank, whole"; return SCA_ERR_UNSUPPORTED; }
     c->d.shard_begin = begin; c->d.shard_count = count;
     c->kd_ahead = false; c->kdq_last = -1; c->auto_backoff = 0;           // another shard: the AUTO passes' counts described the old one
     return 0;

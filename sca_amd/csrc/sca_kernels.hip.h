@@ -344,9 +344,9 @@ __device__ __forceinline__ double box_dist_sq(const KdWide &w, int side, V3 p) {
 }
 
 template <class LeafFn>
-__device__ __forceinline__ int kd_traverse(const KdWide *tree, V3 p, double rangeSq, int *stack, int lane, LeafFn leaf) {
+__device__ __forceinline__ int kd_traverse(const KdWide *tree, V3 p, double rangeSq, int *stack, int lane, LeafFn leaf, int root = 0) {
     int sp = 0, st = 0;
-    int node = 0;
+    int node = root;                                                  // (a scene's own tree in a forest: SceneView)
     bool have = true;
     while (have) {
         node = __builtin_amdgcn_readfirstlane(node);
@@ -389,7 +389,7 @@ __device__ __forceinline__ int hi32(double v) { return (int)(unsigned)((unsigned
 // one, which goes onto a stack of RECORDS in LDS -- popping it later costs an LDS read instead of another trip to the L2.
 constexpr int KD_RSTACK = 48;
 template <class LeafFn>
-__device__ __forceinline__ int kd_traverse_rec(const KdWide *tree, V3 p, double rangeSq, double (*rstack)[16], int lane, LeafFn leaf) {
+__device__ __forceinline__ int kd_traverse_rec(const KdWide *tree, V3 p, double rangeSq, double (*rstack)[16], int lane, LeafFn leaf, int root = 0) {
     const double *wd = (const double *)tree;
     const int gl = lane & 15, row = lane >> 4;
     const int tk = gl >= 2 ? (gl - 2) >> 2 : 0;                       // which box term this lane squares (see k_neighbors_kd4)
@@ -397,7 +397,7 @@ __device__ __forceinline__ int kd_traverse_rec(const KdWide *tree, V3 p, double 
     const bool t_live = gl >= 2 && gl < 14;
     const double pk = tk == 0 ? p.x : (tk == 1 ? p.y : p.z);
     int sp = 0, st = 0;
-    double w = lane < 16 ? wd[lane] : 0.0;                            // the root's record
+    double w = lane < 16 ? wd[(size_t)root * 16 + lane] : 0.0;        // the root's record (a scene's own tree in a forest: SceneView)
     bool have = true;
     while (have) {
         const double h0 = readlane_f64(w, 0), h1 = readlane_f64(w, 1);
@@ -445,7 +445,7 @@ __device__ __forceinline__ int kd_traverse_rec(const KdWide *tree, V3 p, double 
 // 80 VGPRs in k_neighbors_kd4) a scene WITHOUT obstacles should not pay for: the host launches the <false> form there (no obstacle code).
 template <bool HAS_OBS = true>
 __device__ __forceinline__ void neighbors_one(const DeviceView &d, const Params &P, double agent_reach, double obs_reach,
-                                              double max_radius, double (*rstack)[16], int agent, int lane) {
+                                              double max_radius, double (*rstack)[16], int agent, int lane, int aroot = 0) {
     const PubRec me = d.rec[agent];
     int st = 0;
     bool skip = (me.flags & (FLAG_AT_GOAL | FLAG_COLLISION | FLAG_TIMEOUT)) != 0;   // mampenv.py:35
@@ -533,7 +533,7 @@ __device__ __forceinline__ void neighbors_one(const DeviceView &d, const Params 
             if (cb) { if (!coll) { coll = true; L.cnt = 0; } wave_insert(L, lane, maxn, ib, db); }
             else if (!coll) wave_insert(L, lane, maxn, ib, db);
         }
-    });
+    }, aroot);
     if (lane < K_MAX) {
         d.nbr_id[agent * K_MAX + lane] = (lane < L.cnt) ? L.id : -1;
         d.nbr_dsq[agent * K_MAX + lane] = (lane < L.cnt) ? L.dsq : 0.0;
@@ -619,12 +619,12 @@ constexpr int K1P_APW = 4;
 #else
 #define SCA_K1_SETPRIO() ((void)0)
 #endif
-template <bool HAS_OBS>
-__global__ __launch_bounds__(K1P_WAVES * 64) void k_neighbors_kd4(DeviceView d, Params P, double agent_reach, double obs_reach,
-                                                                 double max_radius) {
-    SCA_TL(d, TL_NBR_KD);
-    SCA_K1_SETPRIO();
-    __shared__ int stacks[K1P_WAVES][K1P_APW][KD_STACK];
+// Where an agent's traversal of the agent tree starts: record 0 -- or, in a context that holds many scenes (sca_set_scenes), the root of the
+// agent's own scene in the forest (k_neighbors_kd4_scenes, sca_scenes.hip.h).  The obstacle tree is shared and always starts at 0.
+struct RootZero { __device__ __forceinline__ int operator()(int) const { return 0; } };
+template <bool HAS_OBS, class RootFn>
+__device__ __forceinline__ void neighbors_kd4_body(const DeviceView &d, const Params &P, double agent_reach, double obs_reach, double max_radius,
+                                                   int (*stacks)[K1P_APW][KD_STACK], RootFn root_of) {
     const int lane = threadIdx.x & 63;
     const int wid = threadIdx.x >> 6;
     const int g = lane >> 4, gl = lane & 15, gshift = g << 4;
@@ -653,6 +653,7 @@ __global__ __launch_bounds__(K1P_WAVES * 64) void k_neighbors_kd4(DeviceView d, 
     double Ld = 0.0; int Li = -1; int cnt = 0; bool coll = false; int near_cnt = 0;
     int *near_out = d.near_id + (size_t)agent * NEAR_MAX;
     int *stack = stacks[wid][g];
+    const int aroot = root_of(agent);
 
     // (HAS_OBS = false, launched for scenes without obstacles, keeps the loop's shape -- the obstacle phase stays in the code, with x * x,
     // and is never taken: without it the compiler turned 1.2 M scalar instructions per launch into 6.7 M vector ones at c4, PMC-measured)
@@ -660,7 +661,7 @@ __global__ __launch_bounds__(K1P_WAVES * 64) void k_neighbors_kd4(DeviceView d, 
         const bool ob = phase == 0;
         if (ob && d.m <= 0) continue;
         const double *wd = (const double *)(ob ? d.owide : d.awide);
-        int node = 0, sp = 0;
+        int node = ob ? 0 : aroot, sp = 0;
         bool have = !skip;
         while (__any(have)) {
             const double w = have ? wd[(size_t)node * 16 + gl] : 0.0;
@@ -772,6 +773,14 @@ __global__ __launch_bounds__(K1P_WAVES * 64) void k_neighbors_kd4(DeviceView d, 
         const bool complete = near_cnt <= NEAR_MAX && reach_a * reach_a <= rangeSq && reach_o * reach_o <= rangeSq;
         d.near_n[agent] = complete ? near_cnt : -1;
     }
+}
+template <bool HAS_OBS>
+__global__ __launch_bounds__(K1P_WAVES * 64) void k_neighbors_kd4(DeviceView d, Params P, double agent_reach, double obs_reach,
+                                                                 double max_radius) {
+    SCA_TL(d, TL_NBR_KD);
+    SCA_K1_SETPRIO();
+    __shared__ int stacks[K1P_WAVES][K1P_APW][KD_STACK];
+    neighbors_kd4_body<HAS_OBS>(d, P, agent_reach, obs_reach, max_radius, stacks, RootZero());
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2000,7 +2009,7 @@ __device__ __forceinline__ CollideCtx collide_ctx(const DeviceView &d, int agent
 }
 // whole wavefront, one agent: range queries in both trees (wave-uniform agent)
 __device__ __forceinline__ bool collide_traverse(const DeviceView &d, double agent_reach, double obs_reach, int *stack, int agent, int lane,
-                                                 bool obstacles_only) {
+                                                 bool obstacles_only, int aroot = 0) {
     PubRec me_old;
     const CollideCtx c = collide_ctx(d, agent, me_old);
     bool hit = false;
@@ -2014,7 +2023,7 @@ __device__ __forceinline__ bool collide_traverse(const DeviceView &d, double age
     const double rq = c.me.radius + agent_reach;
     kd_traverse(d.awide, c.p_old, rq * rq, stack, lane, [&](int begin, int end) {
         if (lane < end - begin) { const int j = d.aperm[begin + lane]; if (j != agent) hit = hit || collide_agent(d, c, j); }
-    });
+    }, aroot);
     return __ballot(hit) != 0;
 }
 
@@ -2024,8 +2033,11 @@ static_assert(NEAR_MAX == 8, "k_collide_finish packs 8 lanes per agent");
 
 // traverse(agent, obstacles_only) -> wave-uniform "touches something": the whole-wavefront fallback for one agent (kd-trees
 // here, the grid in sca_grid.hip.h)
-template <class Traverse>
-__device__ __forceinline__ void collide_finish_body(const DeviceView &d, const Params &P, int check_arrived, Traverse traverse) {
+// count(head, live, agent): called by EVERY lane once the flags are committed -- head: the lane that stands for an existing agent, live: that
+// agent is not done.  A context with scenes counts per scene there (k_collide_finish_scenes); everybody else passes nothing.
+struct CountNone { __device__ __forceinline__ void operator()(bool, bool, int) const {} };
+template <class Traverse, class Count = CountNone>
+__device__ __forceinline__ void collide_finish_body(const DeviceView &d, const Params &P, int check_arrived, Traverse traverse, Count count = Count()) {
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int sub = lane & (NEAR_MAX - 1), grp = lane / NEAR_MAX;
@@ -2058,6 +2070,7 @@ __device__ __forceinline__ void collide_finish_body(const DeviceView &d, const P
         const bool r = traverse(ag, obs_only);
         if (lane / NEAR_MAX == l0 / NEAR_MAX) any = r;
     }
+    bool live = false;
     if (exists && sub == 0) {
         uint32_t f = c.me.flags;
         if (any) f |= FLAG_COLLISION;
@@ -2065,8 +2078,10 @@ __device__ __forceinline__ void collide_finish_body(const DeviceView &d, const P
         const V3 g = v3(d.goal[agent * 3], d.goal[agent * 3 + 1], d.goal[agent * 3 + 2]);
         if (l3norm(c.p, g) <= P.near_goal_threshold) f |= FLAG_AT_GOAL;                   // mampenv.py:53-54
         d.rec_new[agent].flags = f;
-        if (!(f & (FLAG_AT_GOAL | FLAG_COLLISION | FLAG_TIMEOUT))) atomicAdd(&d.done_count[(agent & 255) * 32], 1);
+        live = !(f & (FLAG_AT_GOAL | FLAG_COLLISION | FLAG_TIMEOUT));
+        if (live) atomicAdd(&d.done_count[(agent & 255) * 32], 1);
     }
+    count(exists && sub == 0, live, agent);
 }
 
 __global__ __launch_bounds__(K4_WAVES * 64) void k_collide_finish(DeviceView d, Params P, double agent_reach, double obs_reach,

@@ -1,0 +1,143 @@
+// sca_scenes.hip.h -- scene batches (sca_set_scenes): many isolated episodes stepped by one context's passes.
+//
+// Scene s is the contiguous agent range [offsets[s], offsets[s + 1]).  Everything per agent in a pass (prologue, solve, LP, tracker, epilogue,
+// integrate) neither knows nor cares which scene an agent belongs to and is launched unchanged on the whole range.  Three places do care,
+// and their scene forms live here:
+//   the kd-tree     a FOREST: scene s is one root job of k_kd_block, its nodes numbered from 2 * offsets[s] (kdTree.py:60-122 numbers a
+//                   subtree contiguously from its root: k members occupy 2k - 1 nodes, so the ranges are disjoint inside awide[2n]); a job
+//                   only permutes inside [begin, end), so the permutation never leaves a scene -- k_kd_scene_jobs writes the job table behind
+//                   the unchanged k_kd_gather
+//   the two queries k_neighbors_kd_scenes / k_neighbors_kd4_scenes start an agent's traversal of the agent tree at its scene's root; the
+//                   obstacle tree is shared and starts at 0
+//   collide / done  k_collide_finish_scenes: the bootstrap traversal from the scene's root, and the live count per scene as well as in total
+// A context without scenes launches none of these, and SceneView is an argument of these kernels only (as PathView is of k_waypoint's).
+#pragma once
+#include "sca_kdbuild.hip.h"
+
+namespace sca {
+
+struct SceneView {
+    const int32_t *scene_of;  // [n] the agent's scene
+    const int32_t *offsets;   // [nscenes + 1]
+    int32_t *live;            // [nscenes * 32] agents of the scene that are not done after the last env update, ONE 128-BYTE LINE PER SCENE
+                              // (atomics serialise per line at the L2, DeviceView::done_count) -- and a wavefront adds its agents of a scene at once
+    int32_t *prev;            // [nscenes] `live` as the step that is under way found it (between a policy pass and its env update)
+    int32_t *steps;           // [nscenes] steps taken while the scene was live
+    double *heading_keep;     // [n * 3] the headings as the last step of a LIVE scene left them: what a finished scene's agents get back (SceneCount)
+    int nscenes;
+};
+constexpr int SCENE_LINE = 32;           // int32 per counter line
+
+__device__ __forceinline__ int scene_root(const SceneView &v, int agent) { return 2 * v.offsets[v.scene_of[agent]]; }
+struct SceneRoot {
+    const SceneView &v;
+    __device__ __forceinline__ int operator()(int agent) const { return scene_root(v, agent); }
+};
+
+// start of a step, one thread per scene: a scene that is live when a step begins has taken that step (the reference's `while not env.step()`
+// calls env.step() done_step + 1 times); the live counter starts from zero for this step's k_collide_finish_scenes
+__device__ __forceinline__ void scene_begin_one(const SceneView &v, int s) {
+    const int was = v.live[s * SCENE_LINE];
+    v.prev[s] = was;
+    if (was > 0) v.steps[s] += 1;
+    v.live[s * SCENE_LINE] = 0;
+}
+__global__ __launch_bounds__(256) void k_scene_begin(SceneView v) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < v.nscenes) scene_begin_one(v, s);
+}
+
+// The forest's job table, behind k_kd_gather (which rewrites the single root job, the counts and the root's chunk records on every build):
+// one root job per scene and nothing for the level passes.  begin: this build opens a step (scene_begin_one).
+__global__ __launch_bounds__(256) void k_kd_scene_jobs(KdScratch s, SceneView v, int begin) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t == 0) { s.counts[0] = 0; s.nchunks[0] = 0; s.counts[KD_MAX_LEVELS] = v.nscenes; }
+    if (t >= v.nscenes) return;
+    KdJob j; j.begin = v.offsets[t]; j.end = v.offsets[t + 1]; j.node = 2 * j.begin; j.pad = -1;     // pad = -1: a root, no parent record
+    s.small[t] = j;
+    if (begin) scene_begin_one(v, t);
+}
+
+// the live counters from the records themselves (a state that came from outside: sca_set_scenes, sca_set_state, the host state block), one
+// wavefront per scene
+__global__ __launch_bounds__(256) void k_scene_recount(DeviceView d, SceneView v) {
+    const int lane = threadIdx.x & 63;
+    const int s = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (s >= v.nscenes) return;
+    int cnt = 0;
+    for (int a = v.offsets[s] + lane; a < v.offsets[s + 1]; a += 64) {
+        cnt += (d.rec[a].flags & (FLAG_AT_GOAL | FLAG_COLLISION | FLAG_TIMEOUT)) ? 0 : 1;
+        for (int k = 0; k < 3; k++) v.heading_keep[a * 3 + k] = d.heading[a * 3 + k];
+    }
+    cnt = wave_sum_i32(cnt);
+    if (lane == 0) v.live[s * SCENE_LINE] = cnt;
+}
+
+template <bool HAS_OBS>
+__global__ __launch_bounds__(K1_WAVES * 64) void k_neighbors_kd_scenes(DeviceView d, Params P, double agent_reach, double obs_reach,
+                                                                       double max_radius, SceneView v) {
+    SCA_TL(d, TL_NBR_KD);
+    __shared__ double rstacks[K1_WAVES][KD_RSTACK][16];
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (int i = blockIdx.x * K1_WAVES + wid; i < d.shard_count; i += gridDim.x * K1_WAVES) {
+        const int agent = d.shard_begin + i;
+        neighbors_one<HAS_OBS>(d, P, agent_reach, obs_reach, max_radius, rstacks[wid], agent, lane, __builtin_amdgcn_readfirstlane(scene_root(v, agent)));
+    }
+}
+
+template <bool HAS_OBS>
+__global__ __launch_bounds__(K1P_WAVES * 64) void k_neighbors_kd4_scenes(DeviceView d, Params P, double agent_reach, double obs_reach,
+                                                                        double max_radius, SceneView v) {
+    SCA_TL(d, TL_NBR_KD);
+    SCA_K1_SETPRIO();
+    __shared__ int stacks[K1P_WAVES][K1P_APW][KD_STACK];
+    neighbors_kd4_body<HAS_OBS>(d, P, agent_reach, obs_reach, max_radius, stacks, SceneRoot{v});
+}
+
+// The wavefront's K4_APW agents are consecutive ids, so those of one scene are consecutive groups: the first head lane of every run of
+// equal scenes adds the run's live agents to the scene's line in one atomic.
+// A FINISHED scene stays what its last step left.  The reference stops calling env.step() for it; here its agents, all flagged, still pass
+// through update_velocitie with a zero action row like the done agents of a live scene (mampenv.py:42-49: velocity zeroed, step_num
+// advanced unless at the goal, heading through pi_2_pi once more, and a timed-out agent may still gain the collision flag).  So for a scene
+// that had nobody live when the step began, the head lane takes all of that back: the old record whole, step_num, and the heading kept
+// from the last step the scene was live in.
+struct SceneCount {
+    const DeviceView &d;
+    const SceneView &v;
+    __device__ __forceinline__ void operator()(bool head, bool live, int agent) const {
+        const int lane = threadIdx.x & 63;
+        const int sc = head ? v.scene_of[agent] : -1;
+        if (head) {
+            if (v.prev[sc] == 0) {
+                const PubRec old = d.rec[agent];
+                d.rec_new[agent] = old;
+                if (!(old.flags & FLAG_AT_GOAL)) d.step_num[agent] -= 1;
+                for (int k = 0; k < 3; k++) d.heading[agent * 3 + k] = v.heading_keep[agent * 3 + k];
+            } else {
+                for (int k = 0; k < 3; k++) v.heading_keep[agent * 3 + k] = d.heading[agent * 3 + k];
+            }
+        }
+        int mine = 0;
+        bool first = head;
+#pragma unroll
+        for (int g = 0; g < K4_APW; g++) {
+            const int sg = __shfl(sc, g * NEAR_MAX);
+            const int lg = __shfl((int)live, g * NEAR_MAX);
+            if (sg == sc) { mine += lg; if (g * NEAR_MAX < lane) first = false; }
+        }
+        if (first && mine > 0) atomicAdd(&v.live[sc * SCENE_LINE], mine);
+    }
+};
+__global__ __launch_bounds__(K4_WAVES * 64) void k_collide_finish_scenes(DeviceView d, Params P, double agent_reach, double obs_reach,
+                                                                       int check_arrived, SceneView v) {
+    SCA_TL(d, TL_COLLIDE);
+    __shared__ int stacks[K4_WAVES][KD_STACK];
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    collide_finish_body(d, P, check_arrived, [&](int ag, bool obs_only) {
+        return collide_traverse(d, agent_reach, obs_reach, stacks[wid], ag, lane, obs_only, __builtin_amdgcn_readfirstlane(scene_root(v, ag)));
+    }, SceneCount{d, v});
+}
+
+}  // namespace sca

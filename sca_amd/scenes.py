@@ -1,0 +1,255 @@
+"""SceneBatch: many isolated episodes stepped by ONE library context (include/sca_hip.h, sca_set_scenes).
+
+The reference's users run many small episodes -- a paper's table is policies x scenarios x seeds, each a scene of 14-100 drones -- and a small
+scene alone is a chain of dependent dispatches, not work for the chip.  A SceneBatch holds B such scenes in one context: every scene has its
+own kd-tree, its own carried permutation and its own `done`, agents of different scenes never meet, and every value of a scene is bit for
+bit what a MACAEnv holding that scene alone produces.  Obstacles are shared by all scenes.
+
+    batch = SceneBatch([build_agents(seed) for seed in seeds], obstacles, device_tracker=True)   # each list numbered 0 .. n_s - 1
+    while not batch.step():
+        pass
+    rows = [metrics.episode_metrics(batch.env(s)) for s in range(len(batch))]
+
+`batch.env(s)` is a view with the surface the reference's callers and sca_amd.metrics read of a MACAEnv: `.agents`, `.obstacles`,
+`.kdTree.agentIDs` (scene-local ids); the agents' attributes (pos_global_frame, is_at_goal, total_dist, path, policy.now_goal, ...) read the
+batch's host mirrors at offsets[s] + id.  A host-side v_pref_fn is not supported: SCA / RVO3D+Dubins agents take v_pref from the device
+tracker (device_tracker=True), or from the straight-line rule without it, as in MACAEnv.
+"""
+import time
+
+import numpy as np
+
+from . import solver as S
+
+_ATTRS = dict(neighbor_dist=('neighborDist', float), max_neighbors=('maxNeighbors', int), time_step=('timeStep', float),
+              time_horizon=('timeHorizon', float), max_speed=('maxSpeed', float), max_heading_change=('max_heading_change', float),
+              dt_nominal=('dt_nominal', float))
+
+
+class _SceneKdTree:
+    """kdTree.agentIDs of one scene, in the scene's own ids (the context carries global ids: offsets[s] + these)"""
+
+    def __init__(self, view):
+        self._view = view
+        self.max_leaf_size = 10
+
+    @property
+    def agentIDs(self):
+        v = self._view
+        return list(v._batch.solver.get_kd_perm()[v._lo:v._hi] - v._lo)
+
+
+class _Assigned:
+    """agent.path = [...] after the batch was built: the batch uploads the lists in front of its next step"""
+
+    def __init__(self, view):
+        self._view = view
+
+    def add(self, i):
+        self._view._batch._path_assigned.add(self._view._lo + i)
+
+
+class SceneEnv:
+    """One scene of a SceneBatch with a MACAEnv's read surface.  Agents index it with their scene-local id."""
+
+    def __init__(self, batch, s, agents, lo, hi):
+        self._batch, self.scene, self.agents, self._lo, self._hi = batch, s, agents, lo, hi
+        self.obstacles = batch.obstacles
+        self.kdTree = _SceneKdTree(self)
+        self._mirror = {k: v[lo:hi] for k, v in batch._mirror.items()}       # views: refreshed in place by the batch
+        self.goal = batch.goal[lo:hi]
+        self._time_cum = [0.0]
+        self._path_assigned = _Assigned(self)
+        self.device_tracker = batch.device_tracker
+
+    _stale = property(lambda self: self._batch._stale)
+    _paths_on = property(lambda self: self._batch._paths_on)
+    _path_stale = property(lambda self: self._batch._path_stale)
+
+    def _state(self, name):
+        self._batch._state(name)
+        return self._mirror[name]
+
+    pos = property(lambda self: self._state('pos'))
+    vel = property(lambda self: self._state('vel'))
+    heading = property(lambda self: self._state('heading'))
+    flags = property(lambda self: self._state('flags'))
+    total_dist = property(lambda self: self._state('total_dist'))
+    step_num = property(lambda self: self._state('step_num'))
+    done = property(lambda self: bool(self._batch.done[self.scene]))
+    steps = property(lambda self: int(self._batch.steps[self.scene]))
+
+    def _refresh_paths(self):
+        self._batch._refresh_paths()
+
+    def _now_goal_of(self, i):
+        return self._batch._now_goal_of(self._lo + i)
+
+    def _vpref_of(self, i):
+        return self._batch._vpref_of(self._lo + i)
+
+    def _policy_row(self, i):
+        raise RuntimeError('a SceneBatch serves every agent of every scene in batch.step(): there is no single-agent find_next_action')
+
+    def _neighbors_of(self, i):
+        b = self._batch
+        if b._nbr_cache is None:
+            b._nbr_cache = b.solver.neighbors()
+        nb, g = b._nbr_cache, self._lo + i
+        out = []
+        for k in range(int(nb['nbr_n'][g])):
+            j = int(nb['nbr_id'][g, k])
+            out.append((self.obstacles[j] if nb['nbr_kind'][g, k] else self.agents[j - self._lo], float(nb['nbr_dsq'][g, k])))
+        return out
+
+
+class SceneBatch:
+    def __init__(self, scenes, obstacles=(), neighbor_mode=S.NBR_KDTREE, device_tracker=False, history_capacity=0, device=0):
+        scenes = [list(a) for a in scenes]
+        if not scenes or any(len(a) == 0 for a in scenes):
+            raise ValueError('a SceneBatch needs at least one scene and no empty one')
+        for s, agents in enumerate(scenes):
+            for i, a in enumerate(agents):
+                if a.id != i:
+                    raise ValueError(f'scene {s}: agent.id must equal its index in its scene (kdTree.py:64), as for an env of its own')
+        self.obstacles = list(obstacles)
+        self.neighbor_mode = neighbor_mode
+        self.device_tracker = bool(device_tracker)
+        self.offsets = np.concatenate([[0], np.cumsum([len(a) for a in scenes])]).astype(np.int32)
+        flat = [a for agents in scenes for a in agents]
+        n, m, B = len(flat), len(self.obstacles), len(scenes)
+        self._mirror = dict(pos=np.array([a._pos for a in flat], dtype=np.float64).reshape(n, 3),
+                            vel=np.array([a._vel for a in flat], dtype=np.float32).reshape(n, 3),
+                            heading=np.array([a._heading for a in flat], dtype=np.float64).reshape(n, 3),
+                            flags=np.zeros(n, np.uint8), total_dist=np.zeros(n), step_num=np.zeros(n, np.int32))
+        self._stale = False
+        self.goal = np.array([a.goal_global_frame for a in flat], dtype=np.float64).reshape(n, 3)
+        self.policy_ids = np.array([a.policy.policy_id for a in flat], np.uint8)
+        self._ext = np.array([a.policy.needs_external_vpref for a in flat], bool)
+        start = np.array([a.initial_pos for a in flat], dtype=np.float64)
+        goal6 = np.array([a.goal_pos for a in flat], dtype=np.float64)
+        # the solver attributes of agent.py:24-41, as MACAEnv.set_agents hands them over: one value per context where all agents of all
+        # scenes agree, per agent where they differ
+        params, per_agent = {}, {}
+        for name, (attr, conv) in _ATTRS.items():
+            vals = [conv(getattr(a, attr)) for a in flat]
+            params[name] = vals[0]
+            if any(v != vals[0] for v in vals):
+                per_agent[name] = vals
+        sol = self.solver = S.BatchedSolver(max_agents=n, max_obstacles=max(m, 1), device=device, params=params)
+        sol.set_obstacles(np.array([o.pos_global_frame for o in self.obstacles], dtype=np.float64).reshape(m, 3),
+                          np.array([o.radius for o in self.obstacles], dtype=np.float64))
+        sol.set_agents([a.radius for a in flat], [a.pref_speed for a in flat], self.goal, self.policy_ids, S.zaxis_flags(start, goal6),
+                       [a.max_run_dist for a in flat])
+        if per_agent:
+            sol.set_agent_params(**per_agent)
+        sol.set_scenes(self.offsets)
+        sol.set_state(self._mirror['pos'], self._mirror['vel'], self._mirror['heading'], self._mirror['flags'])
+        if self.device_tracker and self._ext.any():
+            tracked = [a for a in flat if a.policy.needs_external_vpref]
+            trip = [(float(a.turning_radius), float(a.pitchlims[0]), float(a.pitchlims[1])) for a in flat]
+            first = (float(tracked[0].turning_radius), float(tracked[0].pitchlims[0]), float(tracked[0].pitchlims[1]))
+            sol.device_tracker_enable(goal6[:, 3:6], turning_radius=first[0], pitchlims=(first[1], first[2]))
+            if any((float(a.turning_radius), float(a.pitchlims[0]), float(a.pitchlims[1])) != first for a in tracked):
+                sol.device_tracker_set_agent_params([t[0] for t in trip], [t[1] for t in trip], [t[2] for t in trip])
+        self._flat = flat
+        self._envs = [SceneEnv(self, s, scenes[s], int(self.offsets[s]), int(self.offsets[s + 1])) for s in range(B)]
+        for view in self._envs:
+            for a in view.agents:
+                a._env = view
+                a._row_pos = a._row_vel = a._row_heading = None
+                a.policy._env = view
+                a.policy._agent_id = a.id
+        self._paths_on = False
+        self._path_stale = False
+        self._path_ng = None
+        self._path_assigned = set(range(n))
+        self._sync_paths()
+        self._nbr_cache = None
+        self._vpref_cache = None
+        self.active = np.diff(self.offsets).astype(np.int32)          # agents of each scene the next step will serve
+        self.steps = np.zeros(B, np.int32)                            # steps each scene has taken while it was live
+        if history_capacity:
+            sol.history_enable(int(history_capacity))
+
+    def __len__(self):
+        return len(self._envs)
+
+    def env(self, s):
+        return self._envs[s]
+
+    @property
+    def done(self):
+        return self.active == 0
+
+    def close(self):
+        self.solver.close()
+
+    # ---- host mirrors, refreshed in place on first use after a step ------------------------------------------------------------------
+    def _state(self, name):
+        if self._stale:
+            st = self.solver.get_state()
+            for k in self._mirror:
+                self._mirror[k][...] = st[k]
+            self._stale = False
+        return self._mirror[name]
+
+    def _vpref_of(self, g):
+        if self._vpref_cache is None:
+            self._vpref_cache = np.nan_to_num(self.solver.diag()['vpref'])
+        return self._vpref_cache[g]
+
+    # ---- waypoint lists (Agent.path), as in MACAEnv -----------------------------------------------------------------------------------
+    def _refresh_paths(self, skip=()):
+        rem, self._path_ng = self.solver.get_path_state()
+        for g, a in enumerate(self._flat):
+            if g not in skip and len(a._path) > rem[g]:
+                del a._path[int(rem[g]):]
+        self._path_stale = False
+
+    def _sync_paths(self):
+        if not self._path_assigned:
+            return
+        assigned, self._path_assigned = self._path_assigned, set()
+        lists = [a._path for a in self._flat]
+        n = len(lists)
+        if self._paths_on:
+            self._refresh_paths(skip=assigned)
+            ng = self._path_ng.copy()
+        else:
+            if not any(len(p) for p in lists):
+                return
+            ng = np.full((n, 3), np.nan)
+            served = self._state('step_num') > 0
+            ng[served] = self.goal[served]
+        self.solver.set_paths([[list(map(float, w[:3])) for w in p] for p in lists])
+        self.solver.set_path_state(np.array([len(p) for p in lists], np.int32), ng)
+        self._paths_on = True
+        self._path_ng = ng
+        self._path_stale = False
+
+    def _now_goal_of(self, g):
+        if self._path_stale:
+            self._refresh_paths()
+        v = self._path_ng[g]
+        return None if np.isnan(v[0]) else v.copy()
+
+    # ---- one step of every live scene ------------------------------------------------------------------------------------------------------
+    def step(self, actions=None):
+        """One resident step of all scenes (finished scenes are inert).  True when every scene is done."""
+        self._sync_paths()
+        t0 = time.perf_counter()
+        live = self.active > 0
+        served = max(1, int(self.active.sum()))
+        total = self.solver.env_step(self.neighbor_mode)
+        share = (time.perf_counter() - t0) / served               # a step's policy wall time, shared among the agents it served
+        st = self.solver.scene_state()
+        self.active, self.steps = st['active'], st['steps']
+        for view, was in zip(self._envs, live):
+            if was:
+                view._time_cum.append(view._time_cum[-1] + share)
+        self._stale = True
+        self._path_stale = self._paths_on
+        self._nbr_cache = None
+        self._vpref_cache = None
+        return total == 0

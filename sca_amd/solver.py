@@ -15,6 +15,7 @@ FLAG_AT_GOAL, FLAG_COLLISION, FLAG_TIMEOUT = 1, 2, 4
 NBR_KDTREE, NBR_GRID, NBR_KDTREE_HOSTBUILD, NBR_AUTO = 0, 1, 2, 3
 FORM_SOLVE_SPLIT, FORM_TRACK_FUSED, FORM_REPLAN_LANE, FORM_REPLAN_FEW, FORM_LP_LANE, FORM_SOLVE_FB, FORM_ACTION_FB, FORM_AUTO_TAIL = 1, 2, 4, 8, 16, 32, 64, 128   # sca_last_pass_forms
 FORM_WAYPOINTS = 256                                          # k_waypoint ran (waypoint lists are set)
+FORM_SCENES = 512                                             # scenes are set: forest build, scene forms of K1 / K4
 K = _lib.K
 
 
@@ -46,6 +47,7 @@ class BatchedSolver:
             raise ScaError(f'sca_create: {msg} (rc={rc})')
         self.n = 0
         self.m = 0
+        self.nscenes = 0
         self._host_state = None
 
     def close(self):
@@ -82,6 +84,7 @@ class BatchedSolver:
         mrd = np.full(n, np.inf) if max_run_dist is None else _lib.as_d(max_run_dist).reshape(n)
         self.n = n
         self._host_state = None                                   # the block's layout follows n: host_state() fetches it again
+        self.nscenes = 0                                          # (sca_set_agents clears the scenes)
         self._chk(self.L.sca_set_agents(self.ctx, n, _lib.ptr(radius, C.c_double), _lib.ptr(pref_speed, C.c_double),
                                         _lib.ptr(goal, C.c_double), _lib.ptr(policy, C.c_uint8),
                                         _lib.ptr(zaxis, C.c_uint8), _lib.ptr(mrd, C.c_double)), 'sca_set_agents')
@@ -168,6 +171,25 @@ class BatchedSolver:
         rem = np.ascontiguousarray(remaining, np.int32).reshape(self.n)
         ng = _lib.as_d(now_goal).reshape(self.n, 3)
         self._chk(self.L.sca_set_path_state(self.ctx, _lib.ptr(rem, C.c_int32), _lib.ptr(ng, C.c_double)), 'sca_set_path_state')
+
+    # ---- scene batches: many isolated episodes in one context (sca_set_scenes) ------------------------------------------
+    def set_scenes(self, offsets):
+        """Scene s = agents [offsets[s], offsets[s + 1]); None / [] for a plain context again.  After set_agents; resets the kd permutation to
+        the identity and the per-scene counters.  A scene holds at most 1536 agents."""
+        if offsets is None or len(offsets) == 0:
+            self._chk(self.L.sca_set_scenes(self.ctx, 0, None), 'sca_set_scenes')
+            self.nscenes = 0
+            return
+        off = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+        self._chk(self.L.sca_set_scenes(self.ctx, len(off) - 1, _lib.ptr(off, C.c_int32)), 'sca_set_scenes')
+        self.nscenes = len(off) - 1
+
+    def scene_state(self):
+        """dict(active [B] int32: agents of each scene the next step would serve, steps [B] int32: steps taken while the scene was live)"""
+        b = self.nscenes
+        out = dict(active=np.zeros(b, np.int32), steps=np.zeros(b, np.int32))
+        self._chk(self.L.sca_get_scene_state(self.ctx, _lib.ptr(out['active'], C.c_int32), _lib.ptr(out['steps'], C.c_int32)), 'sca_get_scene_state')
+        return out
 
     # ---- SCA's v_pref tracker on the device (scaPolicy.py:264-338) ---------------------------------------
     def device_tracker_enable(self, goal_heading, turning_radius=1.5, pitchlims=(-math.pi / 4, math.pi / 4), in_pass=True):

@@ -1,0 +1,160 @@
+#!/usr/bin/env python
+"""What B small episodes cost as ONE batch (sca_set_scenes) against B contexts of one scene each.  ONE process, the legs alternated; every
+window starts from the scenes' start states, runs `--warm` untimed steps and then times the SAME `--window` steps in every leg -- the host clock
+around sca_env_step, which ends in its own synchronise.
+
+    python tools/bench/scenes_cost.py --root /path/to/parent/checkout              # all workloads, merged into profiles/scenes_cost.json
+    python tools/bench/scenes_cost.py --scenes 256 --policy sca --root ...          # one workload (entries are merged per workload)
+
+workloads: B x 100-agent circle scenes, B in --scenes (default 1,16,256,1024), once ORCA3D (untracked) and once SCA with the device tracker
+legs
+    batch             one context holding the B scenes, one sca_env_step per step
+    one_by_one        the same scenes through B contexts of one scene each, by the library of --root (the parent commit's checkout, loaded
+                      beside this one): per step the wall time of all B sca_env_step calls.  Left out without --root.
+    one_by_one_here   the same with this checkout's library: should equal one_by_one within the spread -- if not, something existing moved
+Per leg: the median step time of each of the `--alternations` windows, their min-max (the spread); per workload: agent-steps/s of the batch and
+the ratio one_by_one / batch with the condition "beats it by more than the two spreads together"."""
+import argparse
+import importlib
+import importlib.util
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(os.path.dirname(HERE))
+SCENE_AGENTS = 100
+POLICY = {'orca': 3, 'sca': 0}
+
+
+def load_package(root, alias):
+    """<root>/sca_amd under the module name `alias`: two checkouts' libraries side by side in one process"""
+    pkg = os.path.join(os.path.abspath(root), 'sca_amd')
+    spec = importlib.util.spec_from_file_location(alias, os.path.join(pkg, '__init__.py'), submodule_search_locations=[pkg])
+    mod = importlib.util.module_from_spec(spec)
+    sys.modules[alias] = mod
+    spec.loader.exec_module(mod)
+    return importlib.import_module(alias + '.solver'), importlib.import_module(alias + '.scenarios')
+
+
+def make_context(S, scenarios, sc, copies, policy, scenes):
+    n1 = len(sc['start'])
+    n = n1 * copies
+    tile = lambda a: np.tile(a, (copies,) + (1,) * (a.ndim - 1))
+    sol = S.BatchedSolver(max_agents=n, max_obstacles=1)
+    sol.set_obstacles(np.zeros((0, 3)), np.zeros(0))
+    sol.set_agents(np.full(n, 0.5), np.ones(n), tile(sc['goal'][:, :3]), np.full(n, POLICY[policy], np.uint8), tile(S.zaxis_flags(sc['start'], sc['goal'])),
+                   tile(scenarios.max_run_dist(sc['start'], sc['goal'])))
+    if scenes:
+        sol.set_scenes(np.arange(copies + 1, dtype=np.int32) * n1)
+    start = tile(sc['start'])
+
+    def reset():
+        sol.set_state(start[:, :3], np.zeros((n, 3), np.float32), start[:, 3:6], np.zeros(n, np.uint8), np.zeros(n), np.zeros(n, np.int32))
+        sol.set_kd_perm(np.arange(n, dtype=np.int32))
+        if policy == 'sca':
+            sol.device_tracker_enable(tile(sc['goal'][:, 3:6]))
+    return sol, reset
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--scenes', default='1,16,256,1024')
+    ap.add_argument('--policy', default='orca,sca')
+    ap.add_argument('--window', type=int, default=200)
+    ap.add_argument('--warm', type=int, default=5)
+    ap.add_argument('--alternations', type=int, default=5)
+    ap.add_argument('--root', default=None, help="the parent commit's checkout (built): the one_by_one leg runs its library")
+    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'scenes_cost.json'))
+    args = ap.parse_args()
+
+    sys.path.insert(0, REPO)
+    from sca_amd import scenarios, solver as S
+    Sp = scp = None
+    if args.root:
+        assert os.path.abspath(args.root) != REPO
+        Sp, scp = load_package(args.root, 'sca_amd_parent')
+        assert Sp._lib._build.LIB != S._lib._build.LIB
+    KD = S.NBR_KDTREE
+    sc = scenarios.circle(SCENE_AGENTS)
+    steps_total = args.warm + args.window
+
+    for policy in [p for p in args.policy.split(',') if p]:
+        for B in [int(x) for x in args.scenes.split(',') if x]:
+            legs = {}
+            batch, batch_reset = make_context(S, scenarios, sc, B, policy, True)
+            legs['batch'] = ([batch], [batch_reset])
+            if Sp is not None:
+                made = [make_context(Sp, scp, sc, 1, policy, False) for _ in range(B)]
+                legs['one_by_one'] = ([m[0] for m in made], [m[1] for m in made])
+            made = [make_context(S, scenarios, sc, 1, policy, False) for _ in range(B)]
+            legs['one_by_one_here'] = ([m[0] for m in made], [m[1] for m in made])
+
+            def run(leg):
+                sols, resets = legs[leg]
+                for r in resets:
+                    r()
+                dts = np.zeros(args.window)
+                active = 0
+                for k in range(steps_total):
+                    t0 = time.perf_counter()
+                    active = 0
+                    for sol in sols:
+                        active += sol.env_step(KD)
+                    if k >= args.warm:
+                        dts[k - args.warm] = time.perf_counter() - t0
+                return dts, active
+
+            rows = {leg: dict(median_ms=[], mean_ms=[], active_at_end=[]) for leg in legs}
+            for leg in legs:                                      # code objects, pinned buffers, the allocator: once per leg, untimed
+                run(leg)
+            for _ in range(args.alternations):
+                for leg in legs:
+                    dts, active = run(leg)
+                    rows[leg]['median_ms'].append(float(np.median(dts)) * 1e3)
+                    rows[leg]['mean_ms'].append(float(dts.mean()) * 1e3)
+                    rows[leg]['active_at_end'].append(active)
+            assert len({tuple(r['active_at_end']) for r in rows.values()}) == 1, rows      # every leg walked through the same steps
+            for r in rows.values():
+                r['ms_per_step'] = float(np.median(r['median_ms']))
+                r['spread_ms'] = [min(r['median_ms']), max(r['median_ms'])]
+            n = B * SCENE_AGENTS
+            entry = {'workload': '%d x circle of %d, %s' % (B, SCENE_AGENTS, 'SCA + device tracker' if policy == 'sca' else 'ORCA3D'),
+                     'scenes': B, 'agents': n, 'warm_steps': args.warm, 'window_steps': args.window, 'alternations': args.alternations, 'legs': rows,
+                     'batch_agent_steps_per_s': n / (rows['batch']['ms_per_step'] * 1e-3)}
+            ref = 'one_by_one' if 'one_by_one' in rows else 'one_by_one_here'
+            a, b = rows[ref], rows['batch']
+            margin = (a['spread_ms'][1] - a['spread_ms'][0]) + (b['spread_ms'][1] - b['spread_ms'][0])
+            entry['verdict'] = {'against': ref, 'ratio_one_by_one_over_batch': a['ms_per_step'] / b['ms_per_step'],
+                                'one_by_one_minus_batch_ms': a['ms_per_step'] - b['ms_per_step'], 'sum_of_spreads_ms': margin,
+                                'batch_faster_by_more_than_the_spreads': bool(a['ms_per_step'] - b['ms_per_step'] > margin),
+                                'batch_within_the_spreads': bool(abs(a['ms_per_step'] - b['ms_per_step']) <= margin)}
+            if 'one_by_one' in rows:
+                h = rows['one_by_one_here']
+                m2 = (a['spread_ms'][1] - a['spread_ms'][0]) + (h['spread_ms'][1] - h['spread_ms'][0])
+                entry['existing_path'] = {'here_minus_parent_ms': h['ms_per_step'] - a['ms_per_step'], 'sum_of_spreads_ms': m2,
+                                          'within_the_spreads': bool(abs(h['ms_per_step'] - a['ms_per_step']) <= m2)}
+            try:
+                with open(args.out) as f:
+                    doc = json.load(f)
+            except (OSError, ValueError):
+                doc = {'tool': 'tools/bench/scenes_cost.py', 'unit': 'ms per step of all B scenes; median_ms: the median step time of each window', 'workloads': {}}
+            doc['workloads']['%s_x%d' % (policy, B)] = entry
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, 'w') as f:
+                json.dump(doc, f, indent=1, sort_keys=True)
+                f.write('\n')
+            for leg, r in rows.items():
+                print('%-5s B=%-5d %-16s %9.4f ms/step  spread %.4f .. %.4f  active at end %s' % (policy, B, leg, r['ms_per_step'], r['spread_ms'][0],
+                                                                                                r['spread_ms'][1], r['active_at_end'][-1]), flush=True)
+            print(policy, B, 'agent-steps/s %.3g' % entry['batch_agent_steps_per_s'], json.dumps(entry['verdict']), json.dumps(entry.get('existing_path')), flush=True)
+            for sols, _ in legs.values():
+                for sol in sols:
+                    sol.close()
+
+
+if __name__ == '__main__':
+    main()
