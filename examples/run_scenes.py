@@ -4,6 +4,8 @@ one metrics row per scene -- what a loop over the reference's run_example/run_*.
 
     python examples/run_scenes.py
     python examples/run_scenes.py --agents 50 --seeds 8 --max-steps 3000
+    python examples/run_scenes.py --obstacles          # ... and a take-off/landing scene (16 drones, 8 spheres) per policy in the same batch:
+                                                       # every scene meets its own obstacles only (SceneBatch(scene_obstacles=...))
 """
 import argparse
 import os
@@ -28,16 +30,24 @@ def main():
     ap.add_argument('--agents', type=int, default=100)
     ap.add_argument('--seeds', type=int, default=3, help='random scenes per policy (beside one circle scene)')
     ap.add_argument('--max-steps', type=int, default=20000)
+    ap.add_argument('--obstacles', action='store_true', help='add a take-off/landing scene with its 8 spheres per policy (one obstacle list per scene)')
     args = ap.parse_args()
 
-    names, scenes = [], []
+    names, scenes, obstacles = [], [], []
     for pname, pol in POLICIES.items():
         names.append((pname, 'circle'))
         scenes.append(build_agents(scenarios.circle(args.agents), pol))
         for seed in range(args.seeds):
             names.append((pname, 'random seed %d' % seed))
             scenes.append(build_agents(scenarios.random_cube(args.agents, seed=seed), pol))
-    batch = SceneBatch(scenes, [], device_tracker=True)
+        obstacles += [[] for _ in range(1 + args.seeds)]
+        if args.obstacles:
+            sc = scenarios.takeoff_landing(16)
+            names.append((pname, 'take-off'))
+            scenes.append(build_agents(sc, pol))
+            obstacles.append([E.Obstacle(pos=list(p), shape_dict={'shape': 'sphere', 'feature': float(r)}, id=i)
+                              for i, (p, r) in enumerate(zip(sc['obs_pos'], sc['obs_radius']))])
+    batch = SceneBatch(scenes, scene_obstacles=obstacles, device_tracker=True) if args.obstacles else SceneBatch(scenes, [], device_tracker=True)
     t0, steps = time.time(), 0
     while steps < args.max_steps and not batch.step():
         steps += 1

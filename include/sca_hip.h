@@ -168,8 +168,8 @@ int sca_set_path_state(sca_ctx *ctx, const int32_t *remaining /*n*/, const doubl
 /* Scene batches: ONE context steps many isolated episodes.  Scene s is the contiguous agent range [offsets[s], offsets[s+1]); agents of
  * different scenes never appear in each other's neighbour lists or collision tests, every scene has its own kd-tree, its own carried
  * permutation and its own `done`, and for every scene every value the context produces is bit for bit what a context holding that scene
- * alone produces.  Obstacles (sca_set_obstacles) are shared by all scenes; everything per agent (sca_set_agent_params, the device tracker,
- * sca_set_paths, the history log, sca_step_host) works as without scenes.  sca_version() is unchanged: detect the feature by the symbol.
+ * alone produces.  Obstacles are either one set shared by all scenes (sca_set_obstacles) or one set per scene (sca_set_scene_obstacles,
+ * below); everything per agent (sca_set_agent_params, the device tracker, sca_set_paths, the history log, sca_step_host) works as without scenes.  sca_version() is unchanged: detect the feature by the symbol.
  *   sca_set_scenes      after sca_set_agents (SCA_ERR_STATE before; sca_set_agents clears the scenes).  offsets[0] == 0, strictly increasing,
  *                       offsets[nscenes] == n (SCA_ERR_ARG); every scene at most 1536 agents, KD_WAVE_CAP -- a scene's tree is built by one
  *                       workgroup (SCA_ERR_UNSUPPORTED, the message names the limit).  nscenes == 0 or offsets == NULL: no scenes, a plain
@@ -188,6 +188,21 @@ int sca_set_path_state(sca_ctx *ctx, const int32_t *remaining /*n*/, const doubl
  * the whole range), sca_comm_init, sca_partition_init, sca_get_kd_tree.  A pass reports SCA_FORM_SCENES. */
 int sca_set_scenes(sca_ctx *ctx, int nscenes, const int32_t *offsets /*nscenes+1*/);
 int sca_get_scene_state(sca_ctx *ctx, int32_t *active /*nscenes, nullable*/, int32_t *steps /*nscenes, nullable*/);
+
+/* Every scene its own obstacle set: scene s meets obstacles [obs_offsets[s], obs_offsets[s+1]) and no others; a scene may have none.  The
+ * scene contract extends to them: for every scene every value (state, float32 action rows, neighbour lists and their distSq, diagnostics,
+ * kd permutation, tracker and waypoint results) is bit for bit what a context holding that scene alone with that obstacle set produces --
+ * the library keeps one obstacle tree per scene, built over that scene's obstacles alone.  Obstacle ids reported by sca_get_neighbors are
+ * GLOBAL (obs_offsets[s] + the scene's own id), as agent ids are.  Detect the feature by the symbol (sca_version() is unchanged).
+ *   order      after sca_set_scenes; SCA_ERR_STATE before it (or after whatever cleared the scenes).
+ *   refusals   SCA_ERR_ARG: nscenes different from the context's, obs_offsets NULL, obs_offsets[0] != 0, decreasing offsets, a total
+ *              obs_offsets[nscenes] above sca_create's max_obstacles, pos or radius NULL with a positive total.  A refused call has changed nothing.
+ *   lifetime   a later sca_set_obstacles puts the context back on one shared set.  Whatever drops or redefines the scenes -- sca_set_agents,
+ *              sca_set_scenes, sca_set_scenes(0, NULL) -- also drops the per-scene sets and LEAVES THE CONTEXT WITHOUT OBSTACLES (a shared
+ *              set that was replaced by per-scene sets does not come back): set obstacles again afterwards.  A total of 0 is "no obstacles".
+ * A pass with per-scene sets reports SCA_FORM_SCENE_OBSTACLES beside SCA_FORM_SCENES; a context with scenes and a shared set does not. */
+int sca_set_scene_obstacles(sca_ctx *ctx, int nscenes, const int32_t *obs_offsets /*nscenes+1*/,
+                            const double *pos /*obs_offsets[nscenes]*3*/, const double *radius /*obs_offsets[nscenes]*/);
 
 /* the hot path ----------------------------------------------------------------------------------- */
 int sca_policy_pass(sca_ctx *ctx, int neighbor_mode);
@@ -341,7 +356,8 @@ int sca_last_exchange_ms(sca_ctx *ctx, float *exchange_ms);
  *   SCA_FORM_AUTO_TAIL     SCA_NBR_AUTO: the kd query of the listed agents ran inside the pass's grid query (its last workgroup, from the tree the pass's
  *                          build publishes): no k_neighbors_kd_auto launch, no stream wait in front of the solve
  *   SCA_FORM_WAYPOINTS     k_waypoint ran at the head of the pass (waypoint lists are set: sca_set_paths)
- *   SCA_FORM_SCENES        scenes are set (sca_set_scenes): the forest build and the scene forms of the neighbour query ran */
+ *   SCA_FORM_SCENES        scenes are set (sca_set_scenes): the forest build and the scene forms of the neighbour query ran
+ *   SCA_FORM_SCENE_OBSTACLES  ... with one obstacle set per scene (sca_set_scene_obstacles): the obstacle walks started at each scene's own root */
 #define SCA_FORM_SOLVE_SPLIT 1
 #define SCA_FORM_TRACK_FUSED 2
 #define SCA_FORM_REPLAN_LANE 4
@@ -352,6 +368,7 @@ int sca_last_exchange_ms(sca_ctx *ctx, float *exchange_ms);
 #define SCA_FORM_AUTO_TAIL 128
 #define SCA_FORM_WAYPOINTS 256
 #define SCA_FORM_SCENES 512
+#define SCA_FORM_SCENE_OBSTACLES 1024
 int sca_last_pass_forms(sca_ctx *ctx, int *forms);
 /* SCA_NBR_AUTO statistics since the last reset: out4 = {AUTO passes, agents the grid query listed for the kd query (sum over the passes), the
  * largest list, passes in which somebody was listed}.  A pass with nobody listed never waits for the kd stream. */

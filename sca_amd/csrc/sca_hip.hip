@@ -303,6 +303,10 @@ struct sca_ctx {
     int scene_largest = 0;              // agents of the largest scene: picks the k_kd_block instance
     bool scene_live_valid = false;      // SceneView::live describes the current records (else: k_scene_recount before anybody reads it)
     bool scene_begun = false;           // a policy pass has opened a step (scene_begin_one) that no env update has closed yet
+    // one obstacle set per scene (sca_set_scene_obstacles): d.obs .. d.owide hold a forest, K1 and K4 run their per-scene-obstacle forms
+    bool scene_obs_on = false;
+    SceneObsView sov{};                 // device array [nscenes]
+    std::vector<int32_t> h_obs_off;     // [nscenes + 1] the obstacle offsets as set
 };
 
 #define CHK(ctx, call)                                                                         \
@@ -889,6 +893,7 @@ void sca_destroy(sca_ctx *c) {
     (void)part_free(c);
     for (void *p : {(void *)c->path.off, (void *)c->path.pts, (void *)c->path.rem, (void *)c->path.now_goal}) if (p) (void)hipFree(p);
     for (void *p : {(void *)c->scn.scene_of, (void *)c->scn.offsets, (void *)c->scene_counters, (void *)c->scn.heading_keep}) if (p) (void)hipFree(p);
+    if (c->sov.oroot) (void)hipFree((void *)c->sov.oroot);
     if (c->h_done) { (void)hipHostFree(c->h_done); c->h_done = nullptr; }
     if (c->hs_host) { (void)hipHostFree(c->hs_host); c->hs_host = nullptr; }
     if (c->hs_dev) { (void)hipFree(c->hs_dev); c->hs_dev = nullptr; }
@@ -923,10 +928,12 @@ void sca_destroy(sca_ctx *c) {
     delete c;
 }
 
+static int scene_obstacles_drop(sca_ctx *c);
 int sca_set_obstacles(sca_ctx *c, int m, const double *pos, const double *radius) {
     API_ENTER(c);
     ARG(c, m >= 0 && m <= c->max_m);
     ARG(c, m == 0 || (pos && radius));
+    if (int r = scene_obstacles_drop(c)) return r;                     // one shared set again (sca_set_scene_obstacles)
     c->m = m; c->d.m = m;
     c->max_obs_radius = 0;
     for (int i = 0; i < m; i++) c->max_obs_radius = std::max(c->max_obs_radius, radius[i]);
@@ -1305,8 +1312,22 @@ int sca_set_path_state(sca_ctx *c, const int32_t *remaining, const double *now_g
 }
 
 // ---- scene batches (sca_scenes.h: the rules; sca_scenes.hip.h: the kernels) -----------------------------------------------------------------
+// The per-scene obstacle sets go with the scenes they were cut for -- and the context is left without obstacles: the shared set they
+// replaced is not kept.
+static int scene_obstacles_drop(sca_ctx *c) {
+    if (!c->scene_obs_on) return 0;
+    CHK(c, hipStreamSynchronize(c->stream));
+    if (c->sov.oroot) (void)hipFree((void *)c->sov.oroot);
+    c->sov = SceneObsView{};
+    c->h_obs_off.clear();
+    c->scene_obs_on = false;
+    c->m = 0; c->d.m = 0; c->max_obs_radius = 0;
+    c->near_valid = false;
+    return 0;
+}
 static int scenes_clear(sca_ctx *c) {
     if (!c->scenes_on) return 0;
+    if (int r = scene_obstacles_drop(c)) return r;
     CHK(c, hipStreamSynchronize(c->stream));
     c->scenes_on = false;
     c->h_scene_off.clear();
@@ -1334,6 +1355,7 @@ int sca_set_scenes(sca_ctx *c, int nscenes, const int32_t *offsets) {
     if (c->part_on) { c->err = "sca_set_scenes under the cell-owner partition (sca_partition_init): a mode of SCA_NBR_GRID, which has no scene form"; return SCA_ERR_UNSUPPORTED; }
     if (c->d.shard_begin != 0 || c->d.shard_count != n) { c->err = "sca_set_scenes on a shard (sca_set_shard): scenes are stepped by one rank, whole"; return SCA_ERR_UNSUPPORTED; }
     CHK(c, hipStreamSynchronize(c->stream));
+    if (int r = scene_obstacles_drop(c)) return r;                    // (cut for the scenes that go)
     for (void *p : {(void *)c->scn.scene_of, (void *)c->scn.offsets, (void *)c->scene_counters, (void *)c->scn.heading_keep}) if (p) (void)hipFree(p);
     c->scn = SceneView{}; c->scene_counters = nullptr; c->scenes_on = false;
     int32_t *so = nullptr, *off = nullptr;
@@ -1360,6 +1382,69 @@ int sca_set_scenes(sca_ctx *c, int nscenes, const int32_t *offsets) {
     c->kd_single_hint = 0; c->kd_gen++; c->kd_ahead = false; c->kdq_last = -1; c->auto_backoff = 0; c->near_valid = false;
     c->nbr_mode = SCA_NBR_KDTREE;
     c->scenes_on = true;
+    return 0;
+}
+// One obstacle set per scene.  The reference builds a scene's obstacle tree once, over its own obstacles (mampenv.py:20, kdTree.py:162-227):
+// here the same routine runs per scene on that scene's obstacles alone, with local ids -- so the tree, the leaf order and with them every
+// list and every distSq are the single-scene context's -- and the trees are laid side by side (scene_obstacle_shift, sca_scenes.h).
+// max_obs_radius, and with it the collision reach, stays one value per context: a conservative filter, as max_radius is for scenes.
+int sca_set_scene_obstacles(sca_ctx *c, int nscenes, const int32_t *obs_offsets, const double *pos, const double *radius) {
+    API_ENTER(c);
+    if (!c->scenes_on) { c->err = "sca_set_scene_obstacles: no scenes -- sca_set_scenes first"; return SCA_ERR_STATE; }
+    const int B = c->scn.nscenes;
+    const SceneObsCheck k = scene_obstacles_check(B, c->max_m, nscenes, obs_offsets, pos != nullptr, radius != nullptr);
+    if (k.fault != SCENE_OBS_OK) {
+        switch (k.fault) {
+        case SCENE_OBS_BAD_COUNT: c->err = "sca_set_scene_obstacles: nscenes = " + std::to_string(nscenes) + ", the context holds " + std::to_string(B) + " scenes (sca_set_scenes)"; break;
+        case SCENE_OBS_NO_OFFSETS: c->err = "sca_set_scene_obstacles: obs_offsets is NULL"; break;
+        case SCENE_OBS_BAD_START: c->err = "sca_set_scene_obstacles: obs_offsets[0] must be 0"; break;
+        case SCENE_OBS_DECREASING: c->err = "sca_set_scene_obstacles: obs_offsets must not decrease (scene " + std::to_string(k.scene) + ")"; break;
+        case SCENE_OBS_TOO_MANY: c->err = "sca_set_scene_obstacles: " + std::to_string(k.total) + " obstacles in all, sca_create's max_obstacles is " + std::to_string(c->max_m); break;
+        default: c->err = "sca_set_scene_obstacles: pos and radius must not be NULL with " + std::to_string(k.total) + " obstacles";
+        }
+        return scene_obstacles_error_code(k.fault);
+    }
+    const int M = k.total;
+    CHK(c, hipStreamSynchronize(c->stream));
+    if (M == 0) {                                                     // "no obstacles": the forms of a context without any
+        if (int r = scene_obstacles_drop(c)) return r;
+        c->m = 0; c->d.m = 0; c->max_obs_radius = 0; c->near_valid = false;
+        return 0;
+    }
+    std::vector<ObsRec> h((size_t)M), sorted((size_t)M);
+    double max_r = 0;
+    for (int i = 0; i < M; i++) { h[i].px = pos[3 * i]; h[i].py = pos[3 * i + 1]; h[i].pz = pos[3 * i + 2]; h[i].radius = radius[i]; max_r = std::max(max_r, radius[i]); }
+    std::vector<int32_t> perm((size_t)M), roots((size_t)B);
+    std::vector<KdNode> forest(2 * (size_t)M, KdNode{}), tree;
+    std::vector<KdWide> wforest(2 * (size_t)M, KdWide{}), wide;
+    for (int sc = 0; sc < B; sc++) {
+        const int lo = obs_offsets[sc], ms = obs_offsets[sc + 1] - lo;
+        roots[sc] = scene_obstacle_root(obs_offsets, sc);
+        if (ms == 0) continue;
+        std::vector<int32_t> local((size_t)ms);
+        for (int i = 0; i < ms; i++) local[i] = i;                     // kdTree.py:51-52, the scene's own ids
+        kd_build_host(ms, pos + 3 * (size_t)lo, local.data(), tree);
+        kd_widen_host(ms, tree, wide);
+        scene_obstacle_shift(tree.data(), 2 * ms - 1, lo, MAX_LEAF);
+        scene_obstacle_shift(wide.data(), 2 * ms - 1, lo, MAX_LEAF);
+        for (int i = 0; i < 2 * ms - 1; i++) { forest[2 * (size_t)lo + i] = tree[i]; wforest[2 * (size_t)lo + i] = wide[i]; }
+        for (int i = 0; i < ms; i++) { perm[lo + i] = lo + local[i]; sorted[lo + i] = h[lo + local[i]]; }      // global ids, as the agents' permutation carries
+    }
+    int32_t *dr = nullptr;
+    CHK(c, hipMalloc((void **)&dr, sizeof(int32_t) * (size_t)B));
+    if (c->sov.oroot) (void)hipFree((void *)c->sov.oroot);
+    c->sov.oroot = dr;
+    CHK(c, hipMemcpyAsync(dr, roots.data(), sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, c->stream));
+    CHK(c, hipMemcpyAsync(c->d.obs, h.data(), sizeof(ObsRec) * (size_t)M, hipMemcpyHostToDevice, c->stream));
+    CHK(c, hipMemcpyAsync(c->d.operm, perm.data(), sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice, c->stream));
+    CHK(c, hipMemcpyAsync(c->d.otree, forest.data(), sizeof(KdNode) * 2 * (size_t)M, hipMemcpyHostToDevice, c->stream));
+    CHK(c, hipMemcpyAsync(c->d.owide, wforest.data(), sizeof(KdWide) * 2 * (size_t)M, hipMemcpyHostToDevice, c->stream));
+    CHK(c, hipMemcpyAsync(c->d.obs_sorted, sorted.data(), sizeof(ObsRec) * (size_t)M, hipMemcpyHostToDevice, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    c->m = M; c->d.m = M; c->max_obs_radius = max_r;
+    c->h_obs_off.assign(obs_offsets, obs_offsets + B + 1);
+    c->near_valid = false;
+    c->scene_obs_on = true;
     return 0;
 }
 // SceneView::live from the records, where the state came from outside since the last env update (on `s`, which the records are final on)
@@ -1757,7 +1842,8 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
     }
     const bool split = S.split, solve_fb = S.solve_fb;
     c->d.lp_kernel = S.lp_kernel;
-    int forms = S.forms | (c->paths_on ? SCA_FORM_WAYPOINTS : 0) | (c->scenes_on ? SCA_FORM_SCENES : 0);     // (the waypoint and scene bits are state, not a choice)
+    int forms = S.forms | (c->paths_on ? SCA_FORM_WAYPOINTS : 0) | (c->scenes_on ? SCA_FORM_SCENES : 0) |
+                (c->scene_obs_on ? SCA_FORM_SCENE_OBSTACLES : 0);     // (the waypoint and scene bits are state, not a choice)
     c->kd.skip_prep = overlap ? 1 : 0;
     c->grid.skip_prep = overlap ? 1 : 0;
     if (mode == SCA_NBR_GRID) {
@@ -1843,6 +1929,10 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
     } else if (mode == SCA_NBR_GRID) {
         const auto k1 = obs ? k_neighbors_grid<false, true> : k_neighbors_grid<false, false>;
         LAUNCH_OPT(c, k1_stop, k1, k1p_grid, k1p_block, ns, d, c->grid, c->P, agent_reach, obs_reach, c->max_radius);
+    } else if (c->scene_obs_on && S.packed) {                         // (scene_obs_on: scenes are set, and there is at least one obstacle)
+        LAUNCH_OPT(c, k1_stop, k_neighbors_kd4_scene_obs, k1p_grid, k1p_block, ns, d, c->P, agent_reach, obs_reach, c->max_radius, c->scn, c->sov);
+    } else if (c->scene_obs_on) {
+        LAUNCH_OPT(c, k1_stop, k_neighbors_kd_scene_obs, dim3(std::min((cnt + K1_WAVES - 1) / K1_WAVES, MAX_GRID)), dim3(K1_WAVES * 64), ns, d, c->P, agent_reach, obs_reach, c->max_radius, c->scn, c->sov);
     } else if (c->scenes_on && S.packed) {
         const auto k1 = obs ? k_neighbors_kd4_scenes<true> : k_neighbors_kd4_scenes<false>;
         LAUNCH_OPT(c, k1_stop, k1, k1p_grid, k1p_block, ns, d, c->P, agent_reach, obs_reach, c->max_radius, c->scn);
@@ -1978,7 +2068,10 @@ static int launch_collide_finish(sca_ctx *c, bool timed) {
     const bool others = c->part_on || cnt < d.n;
     const hipEvent_t k4_stop = others ? nullptr : c->finish_stop, others_stop = others ? c->finish_stop : nullptr;
     const int fresh = c->state_fresh ? 1 : 0;
-    if (c->scenes_on) {
+    if (c->scene_obs_on) {
+        LAUNCH_OPT(c, k4_stop, k_collide_finish_scene_obs, k4grid, dim3(K4_WAVES * 64), c->stream, d, c->P, agent_reach, obs_reach, fresh, c->scn, c->sov);
+        c->scene_begun = false; c->scene_live_valid = true;
+    } else if (c->scenes_on) {
         LAUNCH_OPT(c, k4_stop, k_collide_finish_scenes, k4grid, dim3(K4_WAVES * 64), c->stream, d, c->P, agent_reach, obs_reach, fresh, c->scn);
         c->scene_begun = false; c->scene_live_valid = true;
     } else if (c->nbr_mode == SCA_NBR_GRID)

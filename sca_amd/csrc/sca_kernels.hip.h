@@ -445,7 +445,7 @@ __device__ __forceinline__ int kd_traverse_rec(const KdWide *tree, V3 p, double 
 // 80 VGPRs in k_neighbors_kd4) a scene WITHOUT obstacles should not pay for: the host launches the <false> form there (no obstacle code).
 template <bool HAS_OBS = true>
 __device__ __forceinline__ void neighbors_one(const DeviceView &d, const Params &P, double agent_reach, double obs_reach,
-                                              double max_radius, double (*rstack)[16], int agent, int lane, int aroot = 0) {
+                                              double max_radius, double (*rstack)[16], int agent, int lane, int aroot = 0, int oroot = 0) {
     const PubRec me = d.rec[agent];
     int st = 0;
     bool skip = (me.flags & (FLAG_AT_GOAL | FLAG_COLLISION | FLAG_TIMEOUT)) != 0;   // mampenv.py:35
@@ -468,7 +468,8 @@ __device__ __forceinline__ void neighbors_one(const DeviceView &d, const Params 
     WaveList L; L.dsq = 0.0; L.id = -1; L.cnt = 0;
     bool coll = false;
     // obstacles first (scaPolicy.py:114-116), agent.py:101-124
-    if (HAS_OBS && d.m > 0) {
+    // (oroot: 0 -- or, with one obstacle set per scene, the root of the scene's own obstacle tree, < 0: the scene has none; wave-uniform)
+    if (HAS_OBS && d.m > 0 && oroot >= 0) {
         st |= kd_traverse_rec(d.owide, pA, rangeSq, rstack, lane, [&](int begin, int end) {
             const bool valid = lane < end - begin;
             int o = 0; double distSq = 0.0; bool c = false, r = false, nr = false;
@@ -500,7 +501,7 @@ __device__ __forceinline__ void neighbors_one(const DeviceView &d, const Params 
                 if (cb) { if (!coll) { coll = true; L.cnt = 0; } wave_insert(L, lane, maxn, ib, db); }
                 else if (!coll) wave_insert(L, lane, maxn, ib, db);
             }
-        });
+        }, oroot);
     }
     // other agents, agent.py:79-99
     // leaf members are contiguous in position order: ids and coordinates come in one coalesced round trip; the other
@@ -620,8 +621,12 @@ constexpr int K1P_APW = 4;
 #define SCA_K1_SETPRIO() ((void)0)
 #endif
 // Where an agent's traversal of the agent tree starts: record 0 -- or, in a context that holds many scenes (sca_set_scenes), the root of the
-// agent's own scene in the forest (k_neighbors_kd4_scenes, sca_scenes.hip.h).  The obstacle tree is shared and always starts at 0.
-struct RootZero { __device__ __forceinline__ int operator()(int) const { return 0; } };
+// agent's own scene in the forest (k_neighbors_kd4_scenes, sca_scenes.hip.h).  obstacles(agent): the same for the obstacle tree -- 0 for a
+// shared set, the scene's own root with one set per scene (k_neighbors_kd4_scene_obs), < 0: the agent's scene has none, no walk.
+struct RootZero {
+    __device__ __forceinline__ int operator()(int) const { return 0; }
+    __device__ __forceinline__ int obstacles(int) const { return 0; }
+};
 template <bool HAS_OBS, class RootFn>
 __device__ __forceinline__ void neighbors_kd4_body(const DeviceView &d, const Params &P, double agent_reach, double obs_reach, double max_radius,
                                                    int (*stacks)[K1P_APW][KD_STACK], RootFn root_of) {
@@ -654,6 +659,7 @@ __device__ __forceinline__ void neighbors_kd4_body(const DeviceView &d, const Pa
     int *near_out = d.near_id + (size_t)agent * NEAR_MAX;
     int *stack = stacks[wid][g];
     const int aroot = root_of(agent);
+    const int oroot = root_of.obstacles(agent);                     // (row-uniform: the 16 lanes of a group share their agent)
 
     // (HAS_OBS = false, launched for scenes without obstacles, keeps the loop's shape -- the obstacle phase stays in the code, with x * x,
     // and is never taken: without it the compiler turned 1.2 M scalar instructions per launch into 6.7 M vector ones at c4, PMC-measured)
@@ -661,8 +667,8 @@ __device__ __forceinline__ void neighbors_kd4_body(const DeviceView &d, const Pa
         const bool ob = phase == 0;
         if (ob && d.m <= 0) continue;
         const double *wd = (const double *)(ob ? d.owide : d.awide);
-        int node = ob ? 0 : aroot, sp = 0;
-        bool have = !skip;
+        int node = ob ? oroot : aroot, sp = 0;
+        bool have = !skip && !(ob && oroot < 0);
         while (__any(have)) {
             const double w = have ? wd[(size_t)node * 16 + gl] : 0.0;
             const double h0 = row_bcast_d<0>(w), h1 = row_bcast_d<1>(w);
@@ -2009,15 +2015,15 @@ __device__ __forceinline__ CollideCtx collide_ctx(const DeviceView &d, int agent
 }
 // whole wavefront, one agent: range queries in both trees (wave-uniform agent)
 __device__ __forceinline__ bool collide_traverse(const DeviceView &d, double agent_reach, double obs_reach, int *stack, int agent, int lane,
-                                                 bool obstacles_only, int aroot = 0) {
+                                                 bool obstacles_only, int aroot = 0, int oroot = 0) {
     PubRec me_old;
     const CollideCtx c = collide_ctx(d, agent, me_old);
     bool hit = false;
-    if (d.m > 0) {
+    if (d.m > 0 && oroot >= 0) {                                     // (oroot: as in neighbors_one)
         const double rq = c.me.radius + obs_reach;
         kd_traverse(d.owide, c.p, rq * rq, stack, lane, [&](int begin, int end) {
             if (lane < end - begin) hit = hit || collide_obstacle(d, c, d.operm[begin + lane]);
-        });
+        }, oroot);
     }
     if (obstacles_only) return __ballot(hit) != 0;                   // wave-uniform
     const double rq = c.me.radius + agent_reach;

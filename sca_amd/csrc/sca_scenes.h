@@ -57,4 +57,54 @@ inline int scenes_neighbor_mode(int requested) {
     return requested == SCA_NBR_KDTREE || requested == SCA_NBR_AUTO ? (int)SCA_NBR_KDTREE : -1;
 }
 
+// ---- per-scene obstacle sets (sca_set_scene_obstacles) ---------------------------------------------------------------------------------------
+// Scene s meets obstacles [obs_offsets[s], obs_offsets[s + 1]) and no others; a scene may have none.  The obstacle tree becomes a forest
+// like the agents': one tree per scene, built over that scene's obstacles alone with local ids 0 .. m_s - 1 (what makes every value the
+// single-scene context's), laid side by side in otree[2M] / owide[2M] with scene s's nodes numbered from 2 * obs_offsets[s] (a tree over k
+// members occupies 2k - 1 nodes: the ranges are disjoint).
+enum SceneObsFault {
+    SCENE_OBS_OK = 0,
+    SCENE_OBS_BAD_COUNT,    // nscenes is not the context's scene count
+    SCENE_OBS_NO_OFFSETS,   // obs_offsets == NULL
+    SCENE_OBS_BAD_START,    // obs_offsets[0] != 0
+    SCENE_OBS_DECREASING,   // obs_offsets[s + 1] < obs_offsets[s] (equal is fine: a scene without obstacles)
+    SCENE_OBS_TOO_MANY,     // obs_offsets[nscenes] > sca_create's max_obstacles
+    SCENE_OBS_NO_ARRAYS     // a positive total with pos == NULL or radius == NULL
+};
+// fault: which rule failed; scene: the first scene that breaks it (-1: none in particular); total: obs_offsets[nscenes] (SCENE_OBS_OK, _TOO_MANY, _NO_ARRAYS)
+struct SceneObsCheck { SceneObsFault fault; int scene; int total; };
+inline SceneObsCheck scene_obstacles_check(int ctx_nscenes, int max_obstacles, int nscenes, const int32_t *obs_offsets, bool have_pos, bool have_radius) {
+    if (nscenes != ctx_nscenes || nscenes <= 0) return {SCENE_OBS_BAD_COUNT, -1, 0};
+    if (obs_offsets == nullptr) return {SCENE_OBS_NO_OFFSETS, -1, 0};
+    if (obs_offsets[0] != 0) return {SCENE_OBS_BAD_START, 0, 0};
+    for (int s = 0; s < nscenes; s++)
+        if (obs_offsets[s + 1] < obs_offsets[s]) return {SCENE_OBS_DECREASING, s, 0};
+    const int total = obs_offsets[nscenes];
+    if (total > max_obstacles) return {SCENE_OBS_TOO_MANY, -1, total};
+    if (total > 0 && !(have_pos && have_radius)) return {SCENE_OBS_NO_ARRAYS, -1, total};
+    return {SCENE_OBS_OK, -1, total};
+}
+// what sca_set_scene_obstacles returns for a fault
+inline int scene_obstacles_error_code(SceneObsFault f) { return f == SCENE_OBS_OK ? SCA_OK : SCA_ERR_ARG; }
+
+// where scene s's obstacle walks start: the root record of its tree in the forest, -1: the scene has no obstacles (no walk at all)
+inline int scene_obstacle_root(const int32_t *obs_offsets, int s) {
+    return obs_offsets[s + 1] - obs_offsets[s] > 0 ? 2 * obs_offsets[s] : -1;
+}
+
+// A tree built over one scene's obstacles alone (nodes numbered from 0, members 0 .. m_s - 1; Node: begin, end, left, right) as it stands
+// in the forest: member ranges shifted by obs_begin = obs_offsets[s], child links by the node base 2 * obs_begin.  A leaf (at most max_leaf
+// members, kdTree.py:53) keeps its links at 0, the "no children" the build writes; unused records (begin == end) stay as they are.  The
+// caller copies nodes[i] to 2 * obs_begin + i.
+template <class Node>
+inline void scene_obstacle_shift(Node *nodes, int nnodes, int obs_begin, int max_leaf) {
+    for (int i = 0; i < nnodes; i++) {
+        Node &nd = nodes[i];
+        if (nd.end == nd.begin) continue;
+        const bool inner = nd.end - nd.begin > max_leaf;
+        nd.begin += obs_begin; nd.end += obs_begin;
+        if (inner) { nd.left += 2 * obs_begin; nd.right += 2 * obs_begin; }
+    }
+}
+
 }  // namespace sca

@@ -7,10 +7,15 @@
 //                   subtree contiguously from its root: k members occupy 2k - 1 nodes, so the ranges are disjoint inside awide[2n]); a job
 //                   only permutes inside [begin, end), so the permutation never leaves a scene -- k_kd_scene_jobs writes the job table behind
 //                   the unchanged k_kd_gather
-//   the two queries k_neighbors_kd_scenes / k_neighbors_kd4_scenes start an agent's traversal of the agent tree at its scene's root; the
-//                   obstacle tree is shared and starts at 0
+//   the two queries k_neighbors_kd_scenes / k_neighbors_kd4_scenes start an agent's traversal of the agent tree at its scene's root; a
+//                   shared obstacle tree (sca_set_obstacles) starts at 0
 //   collide / done  k_collide_finish_scenes: the bootstrap traversal from the scene's root, and the live count per scene as well as in total
 // A context without scenes launches none of these, and SceneView is an argument of these kernels only (as PathView is of k_waypoint's).
+//
+// One obstacle set per scene (sca_set_scene_obstacles): the obstacle tree is a forest too, built on the host (sca_scenes.h), and the
+// three kernels above have a form each -- k_neighbors_kd_scene_obs / k_neighbors_kd4_scene_obs / k_collide_finish_scene_obs -- whose
+// obstacle walks start at the scene's own obstacle root, or do not happen for a scene without obstacles.  The roots travel in SceneObsView,
+// an argument of these three only: a context with a shared set launches exactly what it launched before.
 #pragma once
 #include "sca_kdbuild.hip.h"
 
@@ -32,6 +37,19 @@ __device__ __forceinline__ int scene_root(const SceneView &v, int agent) { retur
 struct SceneRoot {
     const SceneView &v;
     __device__ __forceinline__ int operator()(int agent) const { return scene_root(v, agent); }
+    __device__ __forceinline__ int obstacles(int) const { return 0; }
+};
+
+struct SceneObsView {
+    const int32_t *oroot;     // [nscenes] record of owide / otree the scene's obstacle walks start at (2 * obs_offsets[s]), -1: the scene has no obstacles
+};
+// two dependent loads per agent (its scene, the scene's root); every lane that serves an agent reads the same words
+__device__ __forceinline__ int scene_obs_root(const SceneView &v, const SceneObsView &o, int agent) { return o.oroot[v.scene_of[agent]]; }
+struct SceneObsRoot {
+    const SceneView &v;
+    const SceneObsView &o;
+    __device__ __forceinline__ int operator()(int agent) const { return scene_root(v, agent); }
+    __device__ __forceinline__ int obstacles(int agent) const { return scene_obs_root(v, o, agent); }
 };
 
 // start of a step, one thread per scene: a scene that is live when a step begins has taken that step (the reference's `while not env.step()`
@@ -137,6 +155,44 @@ __global__ __launch_bounds__(K4_WAVES * 64) void k_collide_finish_scenes(DeviceV
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     collide_finish_body(d, P, check_arrived, [&](int ag, bool obs_only) {
         return collide_traverse(d, agent_reach, obs_reach, stacks[wid], ag, lane, obs_only, __builtin_amdgcn_readfirstlane(scene_root(v, ag)));
+    }, SceneCount{d, v});
+}
+
+// ---- one obstacle set per scene: the three scene kernels with the obstacle walks rooted per scene --------------------------------------------
+// (launched only while per-scene sets with at least one obstacle are set: always the form with the obstacle phase)
+__global__ __launch_bounds__(K1_WAVES * 64) void k_neighbors_kd_scene_obs(DeviceView d, Params P, double agent_reach, double obs_reach,
+                                                                          double max_radius, SceneView v, SceneObsView o) {
+    SCA_TL(d, TL_NBR_KD);
+    __shared__ double rstacks[K1_WAVES][KD_RSTACK][16];
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (int i = blockIdx.x * K1_WAVES + wid; i < d.shard_count; i += gridDim.x * K1_WAVES) {
+        const int agent = d.shard_begin + i;
+        // both roots in scalar registers: the obstacle phase is taken or skipped by the whole wavefront
+        neighbors_one<true>(d, P, agent_reach, obs_reach, max_radius, rstacks[wid], agent, lane, __builtin_amdgcn_readfirstlane(scene_root(v, agent)),
+                            __builtin_amdgcn_readfirstlane(scene_obs_root(v, o, agent)));
+    }
+}
+
+// four agents per wavefront: a 16-lane group whose scene has no obstacles enters the obstacle phase with nothing to do (the loop keeps its
+// shape, see neighbors_kd4_body)
+__global__ __launch_bounds__(K1P_WAVES * 64) void k_neighbors_kd4_scene_obs(DeviceView d, Params P, double agent_reach, double obs_reach,
+                                                                           double max_radius, SceneView v, SceneObsView o) {
+    SCA_TL(d, TL_NBR_KD);
+    SCA_K1_SETPRIO();
+    __shared__ int stacks[K1P_WAVES][K1P_APW][KD_STACK];
+    neighbors_kd4_body<true>(d, P, agent_reach, obs_reach, max_radius, stacks, SceneObsRoot{v, o});
+}
+
+__global__ __launch_bounds__(K4_WAVES * 64) void k_collide_finish_scene_obs(DeviceView d, Params P, double agent_reach, double obs_reach,
+                                                                          int check_arrived, SceneView v, SceneObsView o) {
+    SCA_TL(d, TL_COLLIDE);
+    __shared__ int stacks[K4_WAVES][KD_STACK];
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    collide_finish_body(d, P, check_arrived, [&](int ag, bool obs_only) {
+        return collide_traverse(d, agent_reach, obs_reach, stacks[wid], ag, lane, obs_only, __builtin_amdgcn_readfirstlane(scene_root(v, ag)),
+                                __builtin_amdgcn_readfirstlane(scene_obs_root(v, o, ag)));
     }, SceneCount{d, v});
 }
 

@@ -3,15 +3,19 @@
 The reference's users run many small episodes -- a paper's table is policies x scenarios x seeds, each a scene of 14-100 drones -- and a small
 scene alone is a chain of dependent dispatches, not work for the chip.  A SceneBatch holds B such scenes in one context: every scene has its
 own kd-tree, its own carried permutation and its own `done`, agents of different scenes never meet, and every value of a scene is bit for
-bit what a MACAEnv holding that scene alone produces.  Obstacles are shared by all scenes.
+bit what a MACAEnv holding that scene alone produces.  Obstacles are either one list shared by all scenes (`obstacles`) or one list per
+scene (`scene_obstacles`, sca_set_scene_obstacles): then every scene meets its own obstacles and no others -- an open circle, a take-off
+field with its spheres and two seeds of an obstacle scenario share one batch -- and is still bit for bit the MACAEnv of that scene alone.
 
     batch = SceneBatch([build_agents(seed) for seed in seeds], obstacles, device_tracker=True)   # each list numbered 0 .. n_s - 1
     while not batch.step():
         pass
     rows = [metrics.episode_metrics(batch.env(s)) for s in range(len(batch))]
 
-`batch.env(s)` is a view with the surface the reference's callers and sca_amd.metrics read of a MACAEnv: `.agents`, `.obstacles`,
-`.kdTree.agentIDs` (scene-local ids); the agents' attributes (pos_global_frame, is_at_goal, total_dist, path, policy.now_goal, ...) read the
+    batch = SceneBatch(scenes, scene_obstacles=[[], spheres, other_spheres], device_tracker=True)     # one list of Obstacle per scene
+
+`batch.env(s)` is a view with the surface the reference's callers and sca_amd.metrics read of a MACAEnv: `.agents`, `.obstacles` (the
+scene's own list where there is one per scene), `.kdTree.agentIDs` (scene-local ids); the agents' attributes (pos_global_frame, is_at_goal, total_dist, path, policy.now_goal, ...) read the
 batch's host mirrors at offsets[s] + id.  A host-side v_pref_fn is not supported: SCA / RVO3D+Dubins agents take v_pref from the device
 tracker (device_tracker=True), or from the straight-line rule without it, as in MACAEnv.
 """
@@ -54,7 +58,8 @@ class SceneEnv:
 
     def __init__(self, batch, s, agents, lo, hi):
         self._batch, self.scene, self.agents, self._lo, self._hi = batch, s, agents, lo, hi
-        self.obstacles = batch.obstacles
+        self._obs_lo = 0 if batch.scene_obstacles is None else int(batch.obstacle_offsets[s])      # the context's obstacle ids are global
+        self.obstacles = batch.obstacles if batch.scene_obstacles is None else batch.scene_obstacles[s]
         self.kdTree = _SceneKdTree(self)
         self._mirror = {k: v[lo:hi] for k, v in batch._mirror.items()}       # views: refreshed in place by the batch
         self.goal = batch.goal[lo:hi]
@@ -99,12 +104,12 @@ class SceneEnv:
         out = []
         for k in range(int(nb['nbr_n'][g])):
             j = int(nb['nbr_id'][g, k])
-            out.append((self.obstacles[j] if nb['nbr_kind'][g, k] else self.agents[j - self._lo], float(nb['nbr_dsq'][g, k])))
+            out.append((self.obstacles[j - self._obs_lo] if nb['nbr_kind'][g, k] else self.agents[j - self._lo], float(nb['nbr_dsq'][g, k])))
         return out
 
 
 class SceneBatch:
-    def __init__(self, scenes, obstacles=(), neighbor_mode=S.NBR_KDTREE, device_tracker=False, history_capacity=0, device=0):
+    def __init__(self, scenes, obstacles=(), scene_obstacles=None, neighbor_mode=S.NBR_KDTREE, device_tracker=False, history_capacity=0, device=0):
         scenes = [list(a) for a in scenes]
         if not scenes or any(len(a) == 0 for a in scenes):
             raise ValueError('a SceneBatch needs at least one scene and no empty one')
@@ -113,11 +118,18 @@ class SceneBatch:
                 if a.id != i:
                     raise ValueError(f'scene {s}: agent.id must equal its index in its scene (kdTree.py:64), as for an env of its own')
         self.obstacles = list(obstacles)
+        self.scene_obstacles = None if scene_obstacles is None else [list(o) for o in scene_obstacles]
+        if self.scene_obstacles is not None:
+            if self.obstacles:
+                raise ValueError('a SceneBatch takes either `obstacles` (one list shared by all scenes) or `scene_obstacles` (one list per scene)')
+            if len(self.scene_obstacles) != len(scenes):
+                raise ValueError(f'scene_obstacles: {len(self.scene_obstacles)} lists for {len(scenes)} scenes')
+            self.obstacle_offsets = np.concatenate([[0], np.cumsum([len(o) for o in self.scene_obstacles])]).astype(np.int32)
         self.neighbor_mode = neighbor_mode
         self.device_tracker = bool(device_tracker)
         self.offsets = np.concatenate([[0], np.cumsum([len(a) for a in scenes])]).astype(np.int32)
         flat = [a for agents in scenes for a in agents]
-        n, m, B = len(flat), len(self.obstacles), len(scenes)
+        n, m, B = len(flat), len(self.obstacles) if self.scene_obstacles is None else int(self.obstacle_offsets[-1]), len(scenes)
         self._mirror = dict(pos=np.array([a._pos for a in flat], dtype=np.float64).reshape(n, 3),
                             vel=np.array([a._vel for a in flat], dtype=np.float32).reshape(n, 3),
                             heading=np.array([a._heading for a in flat], dtype=np.float64).reshape(n, 3),
@@ -137,13 +149,17 @@ class SceneBatch:
             if any(v != vals[0] for v in vals):
                 per_agent[name] = vals
         sol = self.solver = S.BatchedSolver(max_agents=n, max_obstacles=max(m, 1), device=device, params=params)
-        sol.set_obstacles(np.array([o.pos_global_frame for o in self.obstacles], dtype=np.float64).reshape(m, 3),
-                          np.array([o.radius for o in self.obstacles], dtype=np.float64))
+        if self.scene_obstacles is None:
+            sol.set_obstacles(np.array([o.pos_global_frame for o in self.obstacles], dtype=np.float64).reshape(m, 3),
+                              np.array([o.radius for o in self.obstacles], dtype=np.float64))
         sol.set_agents([a.radius for a in flat], [a.pref_speed for a in flat], self.goal, self.policy_ids, S.zaxis_flags(start, goal6),
                        [a.max_run_dist for a in flat])
         if per_agent:
             sol.set_agent_params(**per_agent)
         sol.set_scenes(self.offsets)
+        if self.scene_obstacles is not None:
+            sol.set_scene_obstacles([(np.array([o.pos_global_frame for o in obs], dtype=np.float64).reshape(len(obs), 3),
+                                      np.array([o.radius for o in obs], dtype=np.float64)) for obs in self.scene_obstacles])
         sol.set_state(self._mirror['pos'], self._mirror['vel'], self._mirror['heading'], self._mirror['flags'])
         if self.device_tracker and self._ext.any():
             tracked = [a for a in flat if a.policy.needs_external_vpref]

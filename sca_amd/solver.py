@@ -16,6 +16,7 @@ NBR_KDTREE, NBR_GRID, NBR_KDTREE_HOSTBUILD, NBR_AUTO = 0, 1, 2, 3
 FORM_SOLVE_SPLIT, FORM_TRACK_FUSED, FORM_REPLAN_LANE, FORM_REPLAN_FEW, FORM_LP_LANE, FORM_SOLVE_FB, FORM_ACTION_FB, FORM_AUTO_TAIL = 1, 2, 4, 8, 16, 32, 64, 128   # sca_last_pass_forms
 FORM_WAYPOINTS = 256                                          # k_waypoint ran (waypoint lists are set)
 FORM_SCENES = 512                                             # scenes are set: forest build, scene forms of K1 / K4
+FORM_SCENE_OBSTACLES = 1024                                   # ... with one obstacle set per scene (set_scene_obstacles)
 K = _lib.K
 
 
@@ -183,6 +184,27 @@ class BatchedSolver:
         off = np.ascontiguousarray(offsets, np.int32).reshape(-1)
         self._chk(self.L.sca_set_scenes(self.ctx, len(off) - 1, _lib.ptr(off, C.c_int32)), 'sca_set_scenes')
         self.nscenes = len(off) - 1
+
+    def set_scene_obstacles(self, lists):
+        """One (pos [m_s, 3], radius [m_s]) pair per scene: scene s meets its own obstacles and no others (m_s may be 0).  After set_scenes;
+        a later set_obstacles puts the context back on one shared set, and whatever clears or redefines the scenes (set_agents, set_scenes)
+        leaves it without obstacles.  Obstacle ids in neighbors() are global: scene_obstacle_offsets[s] + the scene's own id."""
+        if len(lists) != self.nscenes:
+            raise ValueError(f'set_scene_obstacles: {len(lists)} obstacle sets for {self.nscenes} scenes')
+        radius = [_lib.as_d(r).reshape(-1) for _, r in lists]
+        pos = [_lib.as_d(p) for p, _ in lists]
+        for s, (p, r) in enumerate(zip(pos, radius)):
+            if p.size != 3 * len(r):
+                raise ValueError(f'set_scene_obstacles: scene {s} has {p.size} coordinates for {len(r)} radii')
+        pos = [p.reshape(len(r), 3) for p, r in zip(pos, radius)]
+        off = np.zeros(len(lists) + 1, np.int32)
+        off[1:] = np.cumsum([len(r) for r in radius])
+        allp = np.ascontiguousarray(np.concatenate(pos)) if len(pos) else np.zeros((0, 3))
+        allr = np.ascontiguousarray(np.concatenate(radius)) if len(radius) else np.zeros(0)
+        self._chk(self.L.sca_set_scene_obstacles(self.ctx, len(lists), _lib.ptr(off, C.c_int32), _lib.ptr(allp, C.c_double), _lib.ptr(allr, C.c_double)),
+                  'sca_set_scene_obstacles')
+        self.m = int(off[-1])
+        self.scene_obstacle_offsets = off
 
     def scene_state(self):
         """dict(active [B] int32: agents of each scene the next step would serve, steps [B] int32: steps taken while the scene was live)"""

@@ -13,7 +13,17 @@ legs
                       beside this one): per step the wall time of all B sca_env_step calls.  Left out without --root.
     one_by_one_here   the same with this checkout's library: should equal one_by_one within the spread -- if not, something existing moved
 Per leg: the median step time of each of the `--alternations` windows, their min-max (the spread); per workload: agent-steps/s of the batch and
-the ratio one_by_one / batch with the condition "beats it by more than the two spreads together"."""
+the ratio one_by_one / batch with the condition "beats it by more than the two spreads together".
+
+    python tools/bench/scenes_cost.py --obstacles --root /path/to/parent/checkout   # per-scene obstacle sets, into profiles/scene_obstacles_cost.json
+
+--obstacles: what one obstacle set per scene (sca_set_scene_obstacles) costs.  B copies of the take-off/landing scene (16 drones, 8 spheres; SCA
+with the device tracker), legs
+    scene_sets        one batch, every scene with its own copy of the 8 spheres (the obstacle forest, the per-scene-obstacle kernel forms)
+    shared_set        the same batch with ONE shared set of the 8 spheres, by the library of --root: the same values (the copies coincide), the same
+                      launch count.  Left out without --root.
+    shared_set_here   the same with this checkout's library: should equal shared_set within the spread
+and the difference scene_sets - shared_set is the feature's cost (expected: two dependent loads per agent)."""
 import argparse
 import importlib
 import importlib.util
@@ -60,6 +70,123 @@ def make_context(S, scenarios, sc, copies, policy, scenes):
     return sol, reset
 
 
+def make_obstacle_context(S, scenarios, copies, per_scene):
+    """`copies` take-off/landing scenes in one batch: per_scene -- every scene its own copy of the 8 spheres, else one shared set"""
+    sc = scenarios.takeoff_landing(16)
+    n1, m1 = len(sc['start']), len(sc['obs_radius'])
+    n = n1 * copies
+    tile = lambda a: np.tile(a, (copies,) + (1,) * (a.ndim - 1))
+    sol = S.BatchedSolver(max_agents=n, max_obstacles=m1 * copies if per_scene else m1)
+    if not per_scene:
+        sol.set_obstacles(sc['obs_pos'], sc['obs_radius'])
+    sol.set_agents(np.full(n, 0.5), np.ones(n), tile(sc['goal'][:, :3]), np.zeros(n, np.uint8), tile(S.zaxis_flags(sc['start'], sc['goal'])),
+                   tile(scenarios.max_run_dist(sc['start'], sc['goal'])))
+    sol.set_scenes(np.arange(copies + 1, dtype=np.int32) * n1)
+    if per_scene:
+        sol.set_scene_obstacles([(sc['obs_pos'], sc['obs_radius'])] * copies)
+    start = tile(sc['start'])
+
+    def reset():
+        sol.set_state(start[:, :3], np.zeros((n, 3), np.float32), start[:, 3:6], np.zeros(n, np.uint8), np.zeros(n), np.zeros(n, np.int32))
+        sol.set_kd_perm(np.arange(n, dtype=np.int32))
+        sol.device_tracker_enable(tile(sc['goal'][:, 3:6]))
+    return sol, reset, n1
+
+
+def host():
+    """where the numbers were taken: the machine's name and the device's"""
+    import platform
+    out = {'hostname': platform.node()}
+    try:
+        import torch
+        out['gpu'] = torch.cuda.get_device_name(0)
+    except Exception as e:                                        # (the numbers stand without the device's name)
+        out['gpu'] = 'unknown (%s)' % type(e).__name__
+    return out
+
+
+def time_legs(legs, args, mode):
+    """every leg once untimed, then `--alternations` rounds of all legs in turn; per leg the median step time of every window"""
+    steps_total = args.warm + args.window
+
+    def run(leg):
+        sols, resets = legs[leg]
+        for r in resets:
+            r()
+        dts = np.zeros(args.window)
+        active = 0
+        for k in range(steps_total):
+            t0 = time.perf_counter()
+            active = 0
+            for sol in sols:
+                active += sol.env_step(mode)
+            if k >= args.warm:
+                dts[k - args.warm] = time.perf_counter() - t0
+        return dts, active
+
+    rows = {leg: dict(median_ms=[], mean_ms=[], active_at_end=[]) for leg in legs}
+    for leg in legs:                                              # code objects, pinned buffers, the allocator: once per leg, untimed
+        run(leg)
+    for _ in range(args.alternations):
+        for leg in legs:
+            dts, active = run(leg)
+            rows[leg]['median_ms'].append(float(np.median(dts)) * 1e3)
+            rows[leg]['mean_ms'].append(float(dts.mean()) * 1e3)
+            rows[leg]['active_at_end'].append(active)
+    assert len({tuple(r['active_at_end']) for r in rows.values()}) == 1, rows      # every leg walked through the same steps
+    for r in rows.values():
+        r['ms_per_step'] = float(np.median(r['median_ms']))
+        r['spread_ms'] = [min(r['median_ms']), max(r['median_ms'])]
+    return rows
+
+
+def obstacle_workloads(args, S, scenarios, Sp, scp):
+    out = args.out if args.out_given else os.path.join(REPO, 'profiles', 'scene_obstacles_cost.json')
+    for B in [int(x) for x in args.scenes.split(',') if x]:
+        legs = {}
+        sol, reset, n1 = make_obstacle_context(S, scenarios, B, True)
+        legs['scene_sets'] = ([sol], [reset])
+        if Sp is not None:
+            sol, reset, _ = make_obstacle_context(Sp, scp, B, False)
+            legs['shared_set'] = ([sol], [reset])
+        sol, reset, _ = make_obstacle_context(S, scenarios, B, False)
+        legs['shared_set_here'] = ([sol], [reset])
+        rows = time_legs(legs, args, S.NBR_KDTREE)
+        states = {leg: sols[0].get_state() for leg, (sols, _) in legs.items()}     # the same values: every leg ended on the same state
+        for leg, st in states.items():
+            for key in st:
+                assert np.array_equal(st[key], states['scene_sets'][key]), (leg, key)
+        n = B * n1
+        ref = 'shared_set' if 'shared_set' in rows else 'shared_set_here'
+        a, b = rows['scene_sets'], rows[ref]
+        margin = (a['spread_ms'][1] - a['spread_ms'][0]) + (b['spread_ms'][1] - b['spread_ms'][0])
+        entry = {'workload': '%d x take-off/landing scene of %d drones and 8 spheres, SCA + device tracker' % (B, n1), 'scenes': B, 'agents': n,
+                 'obstacles_per_scene': 8, 'warm_steps': args.warm, 'window_steps': args.window, 'alternations': args.alternations, 'legs': rows,
+                 'scene_sets_agent_steps_per_s': n / (a['ms_per_step'] * 1e-3),
+                 'cost': {'against': ref, 'scene_sets_minus_shared_set_ms': a['ms_per_step'] - b['ms_per_step'],
+                          'ratio_scene_sets_over_shared_set': a['ms_per_step'] / b['ms_per_step'], 'sum_of_spreads_ms': margin,
+                          'within_the_spreads': bool(abs(a['ms_per_step'] - b['ms_per_step']) <= margin)}}
+        try:
+            with open(out) as f:
+                doc = json.load(f)
+        except (OSError, ValueError):
+            doc = {'tool': 'tools/bench/scenes_cost.py --obstacles', 'unit': 'ms per step of all B scenes; median_ms: the median step time of each window',
+                   'workloads': {}}
+        doc['host'] = host()
+        doc['workloads']['takeoff_x%d' % B] = entry
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, 'w') as f:
+            json.dump(doc, f, indent=1, sort_keys=True)
+            f.write('\n')
+        for leg, r in rows.items():
+            print('takeoff B=%-5d %-16s %9.4f ms/step  spread %.4f .. %.4f  active at end %s' % (B, leg, r['ms_per_step'], r['spread_ms'][0], r['spread_ms'][1],
+                                                                                             r['active_at_end'][-1]), flush=True)
+        print('takeoff', B, json.dumps(entry['cost']), flush=True)
+        for sols, _ in legs.values():
+            for sol in sols:
+                sol.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--scenes', default='1,16,256,1024')
@@ -68,8 +195,12 @@ def main():
     ap.add_argument('--warm', type=int, default=5)
     ap.add_argument('--alternations', type=int, default=5)
     ap.add_argument('--root', default=None, help="the parent commit's checkout (built): the one_by_one leg runs its library")
-    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'scenes_cost.json'))
+    ap.add_argument('--out', default=None, help='default: profiles/scenes_cost.json (profiles/scene_obstacles_cost.json with --obstacles)')
+    ap.add_argument('--obstacles', action='store_true', help='the per-scene obstacle sets against one shared set, instead of the batch against B contexts')
     args = ap.parse_args()
+    args.out_given = args.out is not None
+    if not args.out_given:
+        args.out = os.path.join(REPO, 'profiles', 'scenes_cost.json')
 
     sys.path.insert(0, REPO)
     from sca_amd import scenarios, solver as S
@@ -78,9 +209,10 @@ def main():
         assert os.path.abspath(args.root) != REPO
         Sp, scp = load_package(args.root, 'sca_amd_parent')
         assert Sp._lib._build.LIB != S._lib._build.LIB
+    if args.obstacles:
+        return obstacle_workloads(args, S, scenarios, Sp, scp)
     KD = S.NBR_KDTREE
     sc = scenarios.circle(SCENE_AGENTS)
-    steps_total = args.warm + args.window
 
     for policy in [p for p in args.policy.split(',') if p]:
         for B in [int(x) for x in args.scenes.split(',') if x]:
@@ -93,34 +225,7 @@ def main():
             made = [make_context(S, scenarios, sc, 1, policy, False) for _ in range(B)]
             legs['one_by_one_here'] = ([m[0] for m in made], [m[1] for m in made])
 
-            def run(leg):
-                sols, resets = legs[leg]
-                for r in resets:
-                    r()
-                dts = np.zeros(args.window)
-                active = 0
-                for k in range(steps_total):
-                    t0 = time.perf_counter()
-                    active = 0
-                    for sol in sols:
-                        active += sol.env_step(KD)
-                    if k >= args.warm:
-                        dts[k - args.warm] = time.perf_counter() - t0
-                return dts, active
-
-            rows = {leg: dict(median_ms=[], mean_ms=[], active_at_end=[]) for leg in legs}
-            for leg in legs:                                      # code objects, pinned buffers, the allocator: once per leg, untimed
-                run(leg)
-            for _ in range(args.alternations):
-                for leg in legs:
-                    dts, active = run(leg)
-                    rows[leg]['median_ms'].append(float(np.median(dts)) * 1e3)
-                    rows[leg]['mean_ms'].append(float(dts.mean()) * 1e3)
-                    rows[leg]['active_at_end'].append(active)
-            assert len({tuple(r['active_at_end']) for r in rows.values()}) == 1, rows      # every leg walked through the same steps
-            for r in rows.values():
-                r['ms_per_step'] = float(np.median(r['median_ms']))
-                r['spread_ms'] = [min(r['median_ms']), max(r['median_ms'])]
+            rows = time_legs(legs, args, KD)
             n = B * SCENE_AGENTS
             entry = {'workload': '%d x circle of %d, %s' % (B, SCENE_AGENTS, 'SCA + device tracker' if policy == 'sca' else 'ORCA3D'),
                      'scenes': B, 'agents': n, 'warm_steps': args.warm, 'window_steps': args.window, 'alternations': args.alternations, 'legs': rows,
