@@ -6,6 +6,8 @@ one metrics row per scene -- what a loop over the reference's run_example/run_*.
     python examples/run_scenes.py --agents 50 --seeds 8 --max-steps 3000
     python examples/run_scenes.py --obstacles          # ... and a take-off/landing scene (16 drones, 8 spheres) per policy in the same batch:
                                                        # every scene meets its own obstacles only (SceneBatch(scene_obstacles=...))
+    python examples/run_scenes.py --seeds 8 --slots 16 # the same table -- policies x (circle + 8 seeds) -- as a QUEUE streamed through 16 slots
+                                                       # (scenes.run_episodes): a slot that finishes restarts with the next episode
 """
 import argparse
 import os
@@ -14,7 +16,7 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sca_amd import env as E, metrics, scenarios                      # noqa: E402
-from sca_amd.scenes import SceneBatch                                 # noqa: E402
+from sca_amd.scenes import SceneBatch, run_episodes                   # noqa: E402
 
 POLICIES = {'sca': E.SCAPolicy, 'rvo': E.RVO3DPolicy, 'srvo': E.SRVO3DPolicy, 'orca': E.ORCA3DPolicy, 'orca-lp': E.ORCA3DPolicyOfficial,
             'rvo-dubins': E.RVO3dDubinsPolicy}
@@ -31,7 +33,10 @@ def main():
     ap.add_argument('--seeds', type=int, default=3, help='random scenes per policy (beside one circle scene)')
     ap.add_argument('--max-steps', type=int, default=20000)
     ap.add_argument('--obstacles', action='store_true', help='add a take-off/landing scene with its 8 spheres per policy (one obstacle list per scene)')
+    ap.add_argument('--slots', type=int, default=0, help='stream the table through this many slots instead of holding it as one batch')
     args = ap.parse_args()
+    if args.slots and args.obstacles:
+        ap.error('--slots streams episodes that share one obstacle list: not with --obstacles')
 
     names, scenes, obstacles = [], [], []
     for pname, pol in POLICIES.items():
@@ -47,6 +52,17 @@ def main():
             scenes.append(build_agents(sc, pol))
             obstacles.append([E.Obstacle(pos=list(p), shape_dict={'shape': 'sphere', 'feature': float(r)}, id=i)
                               for i, (p, r) in enumerate(zip(sc['obs_pos'], sc['obs_radius']))])
+    if args.slots:
+        t0, stats = time.time(), {}
+
+        def row(r):
+            pname, what = names[r['episode']]
+            print('%-10s %-14s slot %3d steps %5d  ' % (pname, what, r['slot'], r['steps']) +
+                  '  '.join('%s %.4g' % (k, r['metrics'][k]) for k in ('SuccessRate', 'ExtraTime', 'ExtraDistance', 'AverageSpeed')), flush=True)
+        run_episodes(scenes, args.slots, device_tracker=True, on_done=row, max_steps=args.max_steps, stats=stats)
+        print('%d episodes through %d slots: %d batch steps, mean live fraction %.2f, %.2f s' %
+              (len(scenes), args.slots, stats['batch_steps'], stats['live_fraction'], time.time() - t0))
+        return
     batch = SceneBatch(scenes, scene_obstacles=obstacles, device_tracker=True) if args.obstacles else SceneBatch(scenes, [], device_tracker=True)
     t0, steps = time.time(), 0
     while steps < args.max_steps and not batch.step():

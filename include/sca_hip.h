@@ -204,6 +204,35 @@ int sca_get_scene_state(sca_ctx *ctx, int32_t *active /*nscenes, nullable*/, int
 int sca_set_scene_obstacles(sca_ctx *ctx, int nscenes, const int32_t *obs_offsets /*nscenes+1*/,
                             const double *pos /*obs_offsets[nscenes]*3*/, const double *radius /*obs_offsets[nscenes]*/);
 
+/* Restarting scenes in place: a new episode into a slot while the other slots keep running, so that a queue of any length streams through
+ * B slots.  T is the total agent count of the named scenes; the arrays are packed in the order of scene_ids, each scene's rows in its own
+ * agent order.  After the call every named scene is what a context holding that episode alone is right after sca_set_agents +
+ * sca_set_state (zero flags, zero total_dist, zero step_num, identity permutation) and, with the device tracker on, after
+ * sca_device_tracker_enable; from there on every value of the scene (state, float32 action rows, neighbour lists and their distSq,
+ * diagnostics, status, the scene-local permutation, tracker v_pref, plans and re-plan counts) is bit for bit that context's.  Every scene not
+ * named is untouched: its values before, at and after the call are what they would have been without it.  A scene may be restarted whether
+ * it is finished or live.  Detect the feature by the symbol (sca_version() is unchanged).
+ *   reset      the scene's records (position, velocity, flags 0, radius), heading, total_dist, step_num, the constants that were passed
+ *              (goal, pref_speed, max_run_dist, policy, zaxis), v_pref (0; taken from the tracker exactly by SCA / RVO3D+Dubins agents while
+ *              one is enabled), the scene's slice of the kd permutation (identity), its neighbour lists, the tracker's records and
+ *              goal_heading, and the scene's counters: steps[s] = 0, active[s] = n_s -- sca_env_step / sca_step_host / sca_active_count
+ *              count the scene again, and a batch that had reached 0 comes back to life.
+ *   kept       the slot's agent count, its obstacle set (shared or per scene), its per-agent solver attributes (sca_set_agent_params) and
+ *              its per-agent tracker attributes; every array passed as NULL (vel: zero).
+ *   refusals   SCA_ERR_STATE: no scenes, no state yet, between a policy pass and its env update.  SCA_ERR_ARG: count <= 0 or scene_ids
+ *              NULL, an id outside 0 .. nscenes-1, a repeated id, pos or heading NULL, any number that is not finite, a policy above
+ *              SCA_POLICY_RVO3D_DUBINS, a radius / pref_speed / max_run_dist that is not positive, goal_heading without a device tracker.
+ *              SCA_ERR_UNSUPPORTED: waypoint lists are set (sca_set_paths: one block for all agents), or a policy that moves an agent
+ *              between tracked (SCA, RVO3D+Dubins) and untracked while per-agent tracker attributes are set (their classes are cut by
+ *              policy).  A refused call has changed nothing.
+ *   cost       one kernel launch and one stream synchronisation however many scenes are named (one more small copy where a policy changed
+ *              the ORCA3D-LP list); the arrays travel through a page-locked block of the library's own, allocated once. */
+int sca_restart_scenes(sca_ctx *ctx, int count, const int32_t *scene_ids /*count*/,
+                       const double *pos /*T*3*/, const float *vel /*T*3, nullable: zero*/, const double *heading /*T*3*/,
+                       const double *radius, const double *pref_speed, const double *goal /*T*3*/, const uint8_t *policy,
+                       const uint8_t *zaxis, const double *max_run_dist,      /* each T, each nullable: keep the slot's */
+                       const double *goal_heading /*T*3, nullable: keep the slot's*/);
+
 /* the hot path ----------------------------------------------------------------------------------- */
 int sca_policy_pass(sca_ctx *ctx, int neighbor_mode);
 int sca_get_actions(sca_ctx *ctx, float *action /*n*7*/);

@@ -54,6 +54,7 @@ SIGNATURES = {
     'sca_set_scenes': (C.c_int, [C.c_void_p, C.c_int, ip]),
     'sca_get_scene_state': (C.c_int, [C.c_void_p, ip, ip]),
     'sca_set_scene_obstacles': (C.c_int, [C.c_void_p, C.c_int, ip, dp, dp]),
+    'sca_restart_scenes': (C.c_int, [C.c_void_p, C.c_int, ip, dp, fp, dp, dp, dp, dp, bp, bp, dp, dp]),
     'sca_set_path_state': (C.c_int, [C.c_void_p, ip, dp]),
     'sca_policy_pass': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_get_actions': (C.c_int, [C.c_void_p, fp]),

@@ -307,6 +307,10 @@ struct sca_ctx {
     bool scene_obs_on = false;
     SceneObsView sov{};                 // device array [nscenes]
     std::vector<int32_t> h_obs_off;     // [nscenes + 1] the obstacle offsets as set
+    // restarting scenes in place (sca_restart_scenes): the caller's arrays travel through a page-locked block, allocated once for max_n
+    uint8_t *rs_host = nullptr;         // page-locked staging block (RestartLayout of max_n, sca_scenes.h), freed by sca_destroy
+    std::vector<uint8_t> h_policy;      // [n] the agents' policies as they stand (sca_set_agents, sca_restart_scenes)
+    sca_dubins::AgentTrack *trk_init = nullptr;   // one default-constructed tracker record on the device (sca_device_tracker_enable)
 };
 
 #define CHK(ctx, call)                                                                         \
@@ -583,6 +587,7 @@ static int tracker_free(sca_ctx *c) {
     CHK(c, hipStreamSynchronize(c->stream));
     (void)hipFree(c->trk.st); (void)hipFree(c->trk.nbr0); (void)hipFree(c->trk.list); (void)hipFree(c->trk.count); (void)hipFree(c->trk.bcount);
     (void)hipFree(c->trk_goal_heading);
+    if (c->trk_init) { (void)hipFree(c->trk_init); c->trk_init = nullptr; }
     if (c->trk_R_pa) { (void)hipFree(c->trk_R_pa); c->trk_R_pa = nullptr; }
     if (c->trk_cls) { (void)hipFree(c->trk_cls); c->trk_cls = nullptr; }
     if (c->trk_plo_pa) { (void)hipFree(c->trk_plo_pa); c->trk_plo_pa = nullptr; }
@@ -617,6 +622,7 @@ int sca_device_tracker_enable(sca_ctx *c, const double *goal_heading, double tur
     CHK(c, hipMalloc((void **)&c->trk.bcount, sizeof(int32_t) * 4 * TRK_BUCKETS));
     c->trk.n = n;
     CHK(c, hipMalloc((void **)&c->trk_goal_heading, sizeof(double) * 3 * n));
+    CHK(c, hipMalloc((void **)&c->trk_init, sizeof(sca_dubins::AgentTrack)));     // what a restarted scene's records go back to (k_scene_restart)
     CHK(c, hipStreamCreateWithFlags(&c->trk_stream, hipStreamNonBlocking));
     CHK(c, hipEventCreateWithFlags(&c->trk_fork, hipEventDisableTiming));
     CHK(c, hipEventCreateWithFlags(&c->trk_join, hipEventDisableTiming));
@@ -628,6 +634,7 @@ int sca_device_tracker_enable(sca_ctx *c, const double *goal_heading, double tur
     std::vector<uint8_t> pol((size_t)n), mode((size_t)n);
     CHK(c, hipMemcpyAsync(pol.data(), c->d.policy, n, hipMemcpyDeviceToHost, c->stream));
     CHK(c, hipMemcpyAsync(c->trk.st, init.data(), sizeof(sca_dubins::AgentTrack) * n, hipMemcpyHostToDevice, c->stream));
+    CHK(c, hipMemcpyAsync(c->trk_init, init.data(), sizeof(sca_dubins::AgentTrack), hipMemcpyHostToDevice, c->stream));
     CHK(c, hipMemcpyAsync(c->trk.nbr0, nb.data(), sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
     CHK(c, hipMemcpyAsync(c->trk_goal_heading, goal_heading, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
     CHK(c, hipMemsetAsync(c->trk.count, 0, sizeof(int32_t) * 4, c->stream));
@@ -897,6 +904,7 @@ void sca_destroy(sca_ctx *c) {
     if (c->h_done) { (void)hipHostFree(c->h_done); c->h_done = nullptr; }
     if (c->hs_host) { (void)hipHostFree(c->hs_host); c->hs_host = nullptr; }
     if (c->hs_dev) { (void)hipFree(c->hs_dev); c->hs_dev = nullptr; }
+    if (c->rs_host) { (void)hipHostFree(c->rs_host); c->rs_host = nullptr; }
     if (c->ap_dev) { (void)hipFree(c->ap_dev); (void)hipFree(c->ap_nd); c->ap_dev = nullptr; c->ap_nd = nullptr; }
     void *ptrs[] = {c->rec_own, c->rec_new_own, d.heading, d.goal, d.pref_speed, d.vpref_ext, d.total_dist, d.max_run_dist,
                     d.step_num, d.vpref_mode, d.policy, d.zaxis, d.obs, d.obs_sorted, d.awide, d.owide, d.atree, d.aperm, d.otree, d.operm, d.nbr_n,
@@ -1061,6 +1069,7 @@ int sca_set_agents(sca_ctx *c, int n, const double *radius, const double *pref_s
         c->max_radius = std::max(c->max_radius, radius[i]);
         c->max_pref_speed = std::max(c->max_pref_speed, pref_speed[i]);
     }
+    c->h_policy.assign(policy, policy + n);
     c->h_lp_list.clear();
     for (int i = 0; i < n; i++) if (policy[i] == SCA_POLICY_ORCA3D_LP) c->h_lp_list.push_back(i);
     c->d.lp_kernel = 0;                                               // decided per pass from the shard's LP agent count
@@ -1467,6 +1476,114 @@ int sca_get_scene_state(sca_ctx *c, int32_t *active, int32_t *steps) {
     // (between a policy pass and its env update the step under way has emptied `live`: what it found is in `prev`)
     if (active) for (int sc = 0; sc < B; sc++) active[sc] = c->scene_begun ? h[(size_t)B * SCENE_LINE + sc] : h[(size_t)sc * SCENE_LINE];
     if (steps) for (int sc = 0; sc < B; sc++) steps[sc] = h[(size_t)B * (SCENE_LINE + 1) + sc];
+    return 0;
+}
+
+// A new episode into a slot while the other slots keep running (include/sca_hip.h).  The rules are scene_restart_check's (sca_scenes.h); the
+// caller's arrays are copied into the page-locked staging block, ONE launch of k_scene_restart (a workgroup per named scene) reads it across
+// the link and writes every per-agent array of the named scenes, and the call's one synchronisation follows that launch: the block may be
+// written again when the call returns.  Nothing context-wide is reset -- see DESIGN.md section 5 for trk.parity, trk_passes, kd_single_hint
+// and state_fresh.
+int sca_restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const double *pos, const float *vel, const double *heading,
+                       const double *radius, const double *pref_speed, const double *goal, const uint8_t *policy, const uint8_t *zaxis,
+                       const double *max_run_dist, const double *goal_heading) {
+    API_ENTER(c);
+    const RestartArgs A{count, scene_ids, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading};
+    const RestartCtx X{c->scenes_on ? c->scn.nscenes : 0, c->scenes_on ? c->h_scene_off.data() : nullptr, c->state_set, c->scene_begun, c->trk_on,
+                       c->paths_on, c->trk_on && c->trk_view.R_pa != nullptr, c->h_policy.data()};
+    const RestartCheck k = scene_restart_check(X, A);
+    if (k.fault != RESTART_OK) {
+        const std::string at = std::to_string(k.entry);
+        switch (k.fault) {
+        case RESTART_NO_SCENES: c->err = "sca_restart_scenes: no scenes -- sca_set_scenes first"; break;
+        case RESTART_NO_STATE: c->err = "sca_restart_scenes: no state yet -- sca_set_state first"; break;
+        case RESTART_MID_STEP: c->err = "sca_restart_scenes between a policy pass and its env update: finish the step first"; break;
+        case RESTART_BAD_COUNT: c->err = "sca_restart_scenes: count must be positive and scene_ids not NULL"; break;
+        case RESTART_BAD_ID: c->err = "sca_restart_scenes: scene_ids[" + at + "] = " + std::to_string(scene_ids[k.entry]) + " is not a scene of this context (0 .. " + std::to_string(c->scn.nscenes - 1) + ")"; break;
+        case RESTART_REPEATED_ID: c->err = "sca_restart_scenes: scene_ids[" + at + "] = " + std::to_string(scene_ids[k.entry]) + " is named twice"; break;
+        case RESTART_NO_ARRAYS: c->err = "sca_restart_scenes: pos and heading must not be NULL"; break;
+        case RESTART_NOT_FINITE: c->err = "sca_restart_scenes: row " + at + " holds a number that is not finite"; break;
+        case RESTART_BAD_POLICY: c->err = "sca_restart_scenes: row " + at + " has a policy above SCA_POLICY_RVO3D_DUBINS"; break;
+        case RESTART_NOT_POSITIVE: c->err = "sca_restart_scenes: row " + at + " has a radius, pref_speed or max_run_dist that is not positive"; break;
+        case RESTART_GOAL_HEADING: c->err = "sca_restart_scenes: goal_heading without a device tracker (sca_device_tracker_enable)"; break;
+        case RESTART_PATHS: c->err = "sca_restart_scenes with waypoint lists set (sca_set_paths): the lists are one block, replacing a scene's lists is not available"; break;
+        default: c->err = "sca_restart_scenes: row " + at + " changes an agent between a tracked and an untracked policy while per-agent tracker attributes are set "
+                          "(sca_device_tracker_set_agent_params): the tracker's classes are cut by policy";
+        }
+        return scene_restart_error_code(k.fault);
+    }
+    const int T = k.total;
+    const RestartLayout L = scene_restart_layout(c->max_n);
+    if (!c->rs_host) {                                                    // mapped and coherent, as the host state block is: the kernel reads it in place
+        CHK(c, hipHostMalloc((void **)&c->rs_host, (size_t)L.total, hipHostMallocMapped | hipHostMallocCoherent));
+        std::memset(c->rs_host, 0, (size_t)L.total);
+    }
+    uint8_t *b = c->rs_host;
+    int32_t *ids = (int32_t *)(b + L.off[RS_IDS]), *start = (int32_t *)(b + L.off[RS_START]);
+    uint8_t *pol = b + L.off[RS_POLICY], *mode = b + L.off[RS_VPREF_MODE];
+    bool policy_changed = false;
+    for (int e = 0, r = 0; e < count; e++) {
+        const int lo = c->h_scene_off[scene_ids[e]], hi = c->h_scene_off[scene_ids[e] + 1];
+        ids[e] = scene_ids[e]; start[e] = r;
+        for (int a = lo; a < hi; a++, r++) {
+            const uint8_t p = policy ? policy[r] : c->h_policy[a];
+            policy_changed = policy_changed || p != c->h_policy[a];
+            pol[r] = p;
+            mode[r] = c->trk_on && restart_policy_tracked(p) ? 1 : 0;      // sca_device_tracker_enable's rule; 0 without a tracker (sca_set_agents')
+        }
+    }
+    std::memcpy(b + L.off[RS_POS], pos, sizeof(double) * 3 * (size_t)T);
+    std::memcpy(b + L.off[RS_HEADING], heading, sizeof(double) * 3 * (size_t)T);
+    if (vel) std::memcpy(b + L.off[RS_VEL], vel, sizeof(float) * 3 * (size_t)T); else std::memset(b + L.off[RS_VEL], 0, sizeof(float) * 3 * (size_t)T);
+    uint32_t has = 0;
+    const auto put = [&](int sec, const void *src, size_t bytes, uint32_t bit) { if (src) { std::memcpy(b + L.off[sec], src, bytes); has |= bit; } };
+    put(RS_GOAL, goal, sizeof(double) * 3 * (size_t)T, RESTART_HAS_GOAL);
+    put(RS_GOAL_HEADING, goal_heading, sizeof(double) * 3 * (size_t)T, RESTART_HAS_GOAL_HEADING);
+    put(RS_RADIUS, radius, sizeof(double) * (size_t)T, RESTART_HAS_RADIUS);
+    put(RS_PREF_SPEED, pref_speed, sizeof(double) * (size_t)T, RESTART_HAS_PREF_SPEED);
+    put(RS_MAX_RUN_DIST, max_run_dist, sizeof(double) * (size_t)T, RESTART_HAS_MAX_RUN_DIST);
+    put(RS_ZAXIS, zaxis, (size_t)T, RESTART_HAS_ZAXIS);
+    RestartDev d{};
+    d.rec = c->d.rec;
+    d.heading = c->d.heading; d.heading_keep = c->scn.heading_keep; d.total_dist = c->d.total_dist; d.goal = c->d.goal;
+    d.pref_speed = c->d.pref_speed; d.max_run_dist = c->d.max_run_dist; d.vpref_ext = c->d.vpref_ext; d.step_num = c->d.step_num;
+    d.policy = c->d.policy; d.zaxis = c->d.zaxis; d.vpref_mode = c->d.vpref_mode; d.nbr_valid = c->d.nbr_valid;
+    d.aperm = c->d.aperm; d.nbr_n = c->d.nbr_n; d.near_n = c->d.near_n; d.done_count = c->d.done_count;
+    d.offsets = c->scn.offsets; d.live = c->scn.live; d.prev = c->scn.prev; d.steps = c->scn.steps;
+    if (c->trk_on) {
+        static_assert(sizeof(sca_dubins::AgentTrack) % 4 == 0, "k_scene_restart copies the tracker record as 4-byte words");
+        d.trk_nbr0 = c->trk.nbr0; d.trk_goal_heading = c->trk_goal_heading;
+        d.trk_st = (restart_u32 *)c->trk.st; d.trk_init = (const restart_u32 *)c->trk_init; d.trk_words = (int)(sizeof(sca_dubins::AgentTrack) / 4);
+    }
+    hipLaunchKernelGGL(k_scene_restart, dim3(count), dim3(RESTART_T), 0, c->stream, d, (const uint8_t *)b, L, has);
+    CHK(c, hipGetLastError());
+    std::vector<int32_t> lp_new;                                       // K3's list: the ORCA3D-LP agents, ascending ids (the block holds the named scenes' policies)
+    if (policy_changed) {
+        std::vector<uint8_t> now = c->h_policy;
+        for (int e = 0; e < count; e++)
+            for (int a = c->h_scene_off[scene_ids[e]], r = start[e]; a < c->h_scene_off[scene_ids[e] + 1]; a++, r++) now[a] = pol[r];
+        for (int i = 0; i < c->n; i++) if (now[i] == SCA_POLICY_ORCA3D_LP) lp_new.push_back(i);
+        if (!lp_new.empty())
+            CHK(c, hipMemcpyAsync(c->lp_list, lp_new.data(), sizeof(int32_t) * lp_new.size(), hipMemcpyHostToDevice, c->stream));
+    }
+    CHK(c, hipStreamSynchronize(c->stream));
+    // the device has the new episodes: now the host mirrors follow (a call that failed above has left them alone) -- policies, the radius a
+    // later sca_set_state uploads, the kd permutation while the host holds it; the maxima only grow (conservative filters).  "A refused call
+    // changes nothing" is about the refusals above.  A runtime error of the list copy or the synchronisation behind the launch is not one: the
+    // device may then hold the new episode while h_policy, h_rec and h_perm hold the old -- as after any failed HIP call, the context is to
+    // be set up again (sca_set_agents), not stepped on.
+    for (int e = 0; e < count; e++)
+        for (int a = c->h_scene_off[scene_ids[e]], r = start[e]; a < c->h_scene_off[scene_ids[e] + 1]; a++, r++) {
+            c->h_policy[a] = pol[r];
+            if (radius) { c->h_rec[a].radius = radius[r]; c->max_radius = std::max(c->max_radius, radius[r]); }
+            if (pref_speed) c->max_pref_speed = std::max(c->max_pref_speed, pref_speed[r]);
+            c->h_perm[a] = a;
+        }
+    if (policy_changed) c->h_lp_list.swap(lp_new);
+    c->h_pos_valid = false;                                            // (no host mirror of the positions is kept, as in sca_step_host)
+    c->near_valid = false;
+    // (scene_live_valid stays what it is: the kernel wrote the named scenes' counters itself, and where the others' are stale the recount
+    // that is due anyway finds n_s live agents in a restarted scene too)
     return 0;
 }
 

@@ -4,7 +4,9 @@
 // One context holds B scenes; scene s is the contiguous agent range [offsets[s], offsets[s + 1]).  Each scene is one job of k_kd_block
 // (its whole tree by one workgroup in LDS), hence at most KD_WAVE_CAP agents per scene.
 #pragma once
+#include <cstddef>
 #include <cstdint>
+#include <vector>
 
 #include "../../include/sca_hip.h"
 #include "sca_constants.h"
@@ -106,5 +108,113 @@ inline void scene_obstacle_shift(Node *nodes, int nnodes, int obs_begin, int max
         if (inner) { nd.left += 2 * obs_begin; nd.right += 2 * obs_begin; }
     }
 }
+
+// ---- restarting scenes in place (sca_restart_scenes) ------------------------------------------------------------------------------------------
+// A restart puts a new episode into a slot: the named scenes get new start states and constants, every other scene is untouched.  The
+// caller's arrays are packed in the order of scene_ids -- T rows in all, scene_ids[b]'s rows from the sum of the sizes before it.
+enum RestartFault {
+    RESTART_OK = 0,
+    RESTART_NO_SCENES,      // the context holds no scenes                                                     } SCA_ERR_STATE
+    RESTART_NO_STATE,       // no state yet (sca_set_state / the host block)                                   }
+    RESTART_MID_STEP,       // between a policy pass and its env update                                        }
+    RESTART_BAD_COUNT,      // count <= 0 or scene_ids == NULL                                                 } SCA_ERR_ARG
+    RESTART_BAD_ID,         // an id outside 0 .. nscenes - 1 (entry: its index in scene_ids)                  }
+    RESTART_REPEATED_ID,    // an id named twice (entry: the index of the second mention)                      }
+    RESTART_NO_ARRAYS,      // pos or heading NULL                                                             }
+    RESTART_NOT_FINITE,     // a number that is not finite (entry: the packed row)                             }
+    RESTART_BAD_POLICY,     // a policy above SCA_POLICY_RVO3D_DUBINS (entry: the packed row)                  }
+    RESTART_NOT_POSITIVE,   // radius, pref_speed or max_run_dist <= 0 (entry: the packed row)                 }
+    RESTART_GOAL_HEADING,   // goal_heading passed while no device tracker is enabled                          }
+    RESTART_PATHS,          // waypoint lists are set: one CSR block, replacing a scene's lists is not built   } SCA_ERR_UNSUPPORTED
+    RESTART_TRACKED_CHANGE  // a policy that changes an agent's tracked / untracked status while per-agent     }
+                            // tracker attributes are set: the tracker's classes are cut by policy (entry: the packed row)
+};
+// the caller's arguments, as sca_restart_scenes takes them
+struct RestartArgs {
+    int count; const int32_t *scene_ids;
+    const double *pos; const float *vel; const double *heading, *radius, *pref_speed, *goal; const uint8_t *policy, *zaxis;
+    const double *max_run_dist, *goal_heading;
+};
+// what the rules read of the context
+struct RestartCtx {
+    int nscenes; const int32_t *offsets;       // 0 / NULL: no scenes
+    bool state_set, scene_begun, tracker_on, paths_on, tracker_per_agent;
+    const uint8_t *policy_now;                 // [n] the agents' policies as they stand
+};
+// fault: which rule failed; entry: where (-1: nowhere in particular); total: T, the rows the arrays hold (RESTART_OK and every fault found after the ids)
+struct RestartCheck { RestartFault fault; int entry; int total; };
+inline bool restart_policy_tracked(int pol) { return pol == SCA_POLICY_SCA || pol == SCA_POLICY_RVO3D_DUBINS; }
+inline bool restart_finite(double x) { return x - x == 0.0; }       // (no <cmath>: false for NaN and both infinities)
+inline RestartCheck scene_restart_check(const RestartCtx &C, const RestartArgs &A) {
+    if (C.nscenes <= 0 || C.offsets == nullptr) return {RESTART_NO_SCENES, -1, 0};
+    if (!C.state_set) return {RESTART_NO_STATE, -1, 0};
+    if (C.scene_begun) return {RESTART_MID_STEP, -1, 0};
+    if (A.count <= 0 || A.scene_ids == nullptr) return {RESTART_BAD_COUNT, -1, 0};
+    int total = 0;
+    std::vector<uint8_t> named((std::size_t)C.nscenes, (uint8_t)0);      // one mark per scene: thousands of small scenes may be named at once
+    for (int b = 0; b < A.count; b++) {
+        const int s = A.scene_ids[b];
+        if (s < 0 || s >= C.nscenes) return {RESTART_BAD_ID, b, 0};
+        if (named[s]) return {RESTART_REPEATED_ID, b, 0};
+        named[s] = 1;
+        total += C.offsets[s + 1] - C.offsets[s];
+    }
+    if (A.pos == nullptr || A.heading == nullptr) return {RESTART_NO_ARRAYS, -1, total};
+    for (int r = 0; r < total; r++) {
+        bool ok = true;
+        for (int k = 0; k < 3; k++) {
+            ok = ok && restart_finite(A.pos[3 * r + k]) && restart_finite(A.heading[3 * r + k]);
+            if (A.vel) ok = ok && restart_finite((double)A.vel[3 * r + k]);
+            if (A.goal) ok = ok && restart_finite(A.goal[3 * r + k]);
+            if (A.goal_heading) ok = ok && restart_finite(A.goal_heading[3 * r + k]);
+        }
+        if (A.radius) ok = ok && restart_finite(A.radius[r]);
+        if (A.pref_speed) ok = ok && restart_finite(A.pref_speed[r]);
+        if (A.max_run_dist) ok = ok && restart_finite(A.max_run_dist[r]);
+        if (!ok) return {RESTART_NOT_FINITE, r, total};
+    }
+    if (A.policy) for (int r = 0; r < total; r++) if (A.policy[r] > SCA_POLICY_RVO3D_DUBINS) return {RESTART_BAD_POLICY, r, total};
+    for (int r = 0; r < total; r++)
+        if ((A.radius && !(A.radius[r] > 0.0)) || (A.pref_speed && !(A.pref_speed[r] > 0.0)) || (A.max_run_dist && !(A.max_run_dist[r] > 0.0)))
+            return {RESTART_NOT_POSITIVE, r, total};
+    if (A.goal_heading && !C.tracker_on) return {RESTART_GOAL_HEADING, -1, total};
+    if (C.paths_on) return {RESTART_PATHS, -1, total};
+    if (A.policy && C.tracker_per_agent) {
+        int r = 0;
+        for (int b = 0; b < A.count; b++)
+            for (int a = C.offsets[A.scene_ids[b]]; a < C.offsets[A.scene_ids[b] + 1]; a++, r++)
+                if (restart_policy_tracked(A.policy[r]) != restart_policy_tracked(C.policy_now[a])) return {RESTART_TRACKED_CHANGE, r, total};
+    }
+    return {RESTART_OK, -1, total};
+}
+// what sca_restart_scenes returns for a fault
+inline int scene_restart_error_code(RestartFault f) {
+    return f == RESTART_OK ? SCA_OK : f <= RESTART_MID_STEP ? SCA_ERR_STATE : f <= RESTART_GOAL_HEADING ? SCA_ERR_ARG : SCA_ERR_UNSUPPORTED;
+}
+
+// The page-locked staging block sca_restart_scenes copies the caller's arrays into and k_scene_restart reads across the link: one section
+// per array, each sized for `cap` rows (sca_create's max_agents: T and the scene count are at most that) and aligned to 64 bytes, as the
+// host state block's are (host_state_layout, sca_core.h).
+enum RestartSection : int { RS_IDS = 0, RS_START, RS_POS, RS_HEADING, RS_GOAL, RS_GOAL_HEADING, RS_RADIUS, RS_PREF_SPEED, RS_MAX_RUN_DIST, RS_VEL,
+                            RS_POLICY, RS_ZAXIS, RS_VPREF_MODE, RS_SECTIONS };
+constexpr int64_t RS_ALIGN = 64;
+struct RestartLayout { int64_t off[RS_SECTIONS]; int64_t total; };
+inline int64_t restart_section_row_bytes(int s) {
+    // ids / start i32 (one per named scene); pos, heading, goal, goal_heading f64 x 3; radius, pref_speed, max_run_dist f64; vel f32 x 3; the rest u8
+    return s == RS_IDS || s == RS_START ? 4 : s >= RS_POS && s <= RS_GOAL_HEADING ? 24 : s >= RS_RADIUS && s <= RS_MAX_RUN_DIST ? 8 : s == RS_VEL ? 12 : 1;
+}
+inline RestartLayout scene_restart_layout(int cap) {
+    RestartLayout L;
+    int64_t at = 0;
+    for (int s = 0; s < RS_SECTIONS; s++) {
+        L.off[s] = at;
+        at += (restart_section_row_bytes(s) * (int64_t)cap + RS_ALIGN - 1) / RS_ALIGN * RS_ALIGN;
+    }
+    L.total = at;
+    return L;
+}
+// which of the optional arrays the block carries (the others keep the slot's values)
+constexpr uint32_t RESTART_HAS_RADIUS = 1, RESTART_HAS_PREF_SPEED = 2, RESTART_HAS_GOAL = 4, RESTART_HAS_ZAXIS = 8, RESTART_HAS_MAX_RUN_DIST = 16,
+                   RESTART_HAS_GOAL_HEADING = 32;
 
 }  // namespace sca

@@ -18,6 +18,7 @@
 // an argument of these three only: a context with a shared set launches exactly what it launched before.
 #pragma once
 #include "sca_kdbuild.hip.h"
+#include "sca_scenes.h"
 
 namespace sca {
 
@@ -89,6 +90,75 @@ __global__ __launch_bounds__(256) void k_scene_recount(DeviceView d, SceneView v
     }
     cnt = wave_sum_i32(cnt);
     if (lane == 0) v.live[s * SCENE_LINE] = cnt;
+}
+
+// ---- restarting scenes in place (sca_restart_scenes) ------------------------------------------------------------------------------------------
+// One workgroup per named scene, striding over the scene's agents; the new episode is read across the link from the library's page-locked
+// staging block (RestartLayout, sca_scenes.h), as k_host_ingest reads the host state block.  Afterwards every per-agent word of the scene
+// that a later pass READS BEFORE IT WRITES is what sca_set_agents + sca_set_state (+ sca_device_tracker_enable) leave in a context of that
+// episode alone -- the arrays are listed in DESIGN.md section 5 with the reason for each.  Words of other scenes are not touched: the only
+// shared words written are the step counters of K4 (done_count: an agent that was done counts as running again).
+typedef uint32_t __attribute__((may_alias)) restart_u32;
+struct RestartDev {
+    // the arrays of DeviceView / SceneView / TrackDev a restart writes
+    PubRec *rec;
+    double *heading, *heading_keep, *total_dist, *goal, *pref_speed, *max_run_dist, *vpref_ext;
+    int32_t *step_num;
+    uint8_t *policy, *zaxis, *vpref_mode, *nbr_valid;
+    int32_t *aperm, *nbr_n, *near_n, *done_count;
+    const int32_t *offsets;
+    int32_t *live, *prev, *steps;
+    // the device tracker's, null without one
+    double *trk_nbr0, *trk_goal_heading;
+    restart_u32 *trk_st;            // the AgentTrack records as 4-byte words
+    const restart_u32 *trk_init;    // one default-constructed record
+    int trk_words;                  // sizeof(AgentTrack) / 4
+};
+constexpr int RESTART_T = 256;
+__global__ __launch_bounds__(RESTART_T) void k_scene_restart(RestartDev d, const uint8_t *blk, RestartLayout L, uint32_t has) {
+    const int b = (int)blockIdx.x, t = (int)threadIdx.x;
+    const int s = ((const int32_t *)(blk + L.off[RS_IDS]))[b];
+    const int row0 = ((const int32_t *)(blk + L.off[RS_START]))[b];
+    const int lo = d.offsets[s], ns = d.offsets[s + 1] - lo;
+    const double *pos = (const double *)(blk + L.off[RS_POS]) + 3 * (int64_t)row0;
+    const double *head = (const double *)(blk + L.off[RS_HEADING]) + 3 * (int64_t)row0;
+    const double *goal = (const double *)(blk + L.off[RS_GOAL]) + 3 * (int64_t)row0;
+    const double *gh = (const double *)(blk + L.off[RS_GOAL_HEADING]) + 3 * (int64_t)row0;
+    const float *vel = (const float *)(blk + L.off[RS_VEL]) + 3 * (int64_t)row0;
+    // three-component rows: consecutive lanes read and write consecutive words
+    for (int w = t; w < 3 * ns; w += RESTART_T) {
+        const int64_t g = 3 * (int64_t)lo + w;
+        const double h = head[w];
+        d.heading[g] = h; d.heading_keep[g] = h;
+        d.vpref_ext[g] = 0.0;
+        if (has & RESTART_HAS_GOAL) d.goal[g] = goal[w];
+        if ((has & RESTART_HAS_GOAL_HEADING) && d.trk_goal_heading) d.trk_goal_heading[g] = gh[w];
+    }
+    for (int i = t; i < ns; i += RESTART_T) {
+        const int a = lo + i, r = row0 + i;
+        const PubRec old = d.rec[a];
+        PubRec nw;
+        nw.px = pos[3 * i]; nw.py = pos[3 * i + 1]; nw.pz = pos[3 * i + 2];
+        nw.vx = vel[3 * i]; nw.vy = vel[3 * i + 1]; nw.vz = vel[3 * i + 2];
+        nw.flags = 0u;
+        nw.radius = (has & RESTART_HAS_RADIUS) ? ((const double *)(blk + L.off[RS_RADIUS]))[r] : old.radius;
+        d.rec[a] = nw;
+        // K4's counters of the last step: an agent that was done runs again (sca_active_count between steps).  Right while the counters
+        // describe the last step's records; directly behind sca_set_state they are zero until the first step recounts
+        if (old.flags & (FLAG_AT_GOAL | FLAG_COLLISION | FLAG_TIMEOUT)) atomicAdd(&d.done_count[(a & 255) * 32], 1);
+        d.total_dist[a] = 0.0; d.step_num[a] = 0;
+        if (has & RESTART_HAS_PREF_SPEED) d.pref_speed[a] = ((const double *)(blk + L.off[RS_PREF_SPEED]))[r];
+        if (has & RESTART_HAS_MAX_RUN_DIST) d.max_run_dist[a] = ((const double *)(blk + L.off[RS_MAX_RUN_DIST]))[r];
+        d.policy[a] = (blk + L.off[RS_POLICY])[r];
+        if (has & RESTART_HAS_ZAXIS) d.zaxis[a] = (blk + L.off[RS_ZAXIS])[r];
+        d.vpref_mode[a] = (blk + L.off[RS_VPREF_MODE])[r];
+        d.aperm[a] = a;                                                // the scene's kdTree.agentIDs starts as 0 .. n_s - 1 again
+        d.nbr_n[a] = 0; d.nbr_valid[a] = 0; d.near_n[a] = -1;
+        if (d.trk_nbr0) d.trk_nbr0[a] = -1.0;
+    }
+    if (d.trk_st)                                                      // the AgentTrack records, word by word from the one initial record
+        for (int64_t w = t; w < (int64_t)ns * d.trk_words; w += RESTART_T) d.trk_st[(int64_t)lo * d.trk_words + w] = d.trk_init[w % d.trk_words];
+    if (t == 0) { d.live[s * SCENE_LINE] = ns; d.prev[s] = ns; d.steps[s] = 0; }
 }
 
 template <bool HAS_OBS>

@@ -23,6 +23,7 @@ import time
 
 import numpy as np
 
+from . import metrics
 from . import solver as S
 
 _ATTRS = dict(neighbor_dist=('neighborDist', float), max_neighbors=('maxNeighbors', int), time_step=('timeStep', float),
@@ -161,6 +162,7 @@ class SceneBatch:
             sol.set_scene_obstacles([(np.array([o.pos_global_frame for o in obs], dtype=np.float64).reshape(len(obs), 3),
                                       np.array([o.radius for o in obs], dtype=np.float64)) for obs in self.scene_obstacles])
         sol.set_state(self._mirror['pos'], self._mirror['vel'], self._mirror['heading'], self._mirror['flags'])
+        self._trk_on, self._trk_first, self._trk_trip = False, None, None     # what restart() holds a new agent's planner attributes against
         if self.device_tracker and self._ext.any():
             tracked = [a for a in flat if a.policy.needs_external_vpref]
             trip = [(float(a.turning_radius), float(a.pitchlims[0]), float(a.pitchlims[1])) for a in flat]
@@ -168,6 +170,8 @@ class SceneBatch:
             sol.device_tracker_enable(goal6[:, 3:6], turning_radius=first[0], pitchlims=(first[1], first[2]))
             if any((float(a.turning_radius), float(a.pitchlims[0]), float(a.pitchlims[1])) != first for a in tracked):
                 sol.device_tracker_set_agent_params([t[0] for t in trip], [t[1] for t in trip], [t[2] for t in trip])
+                self._trk_trip = trip
+            self._trk_on, self._trk_first = True, first
         self._flat = flat
         self._envs = [SceneEnv(self, s, scenes[s], int(self.offsets[s]), int(self.offsets[s + 1])) for s in range(B)]
         for view in self._envs:
@@ -250,6 +254,73 @@ class SceneBatch:
         v = self._path_ng[g]
         return None if np.isnan(v[0]) else v.copy()
 
+    # ---- a new episode into a slot while the others keep running (sca_restart_scenes) -------------------------------------------------------
+    def restart(self, scenes):
+        """{s: agents}: scene s starts over with the new Agent list (numbered 0 .. n_s - 1, the slot's count), every other scene is untouched.
+        A slot keeps its size, its obstacles and its per-agent solver and planner attributes: ValueError, before any device call, for an
+        agent whose attributes differ from the slot's, or that carries a path.  From here on the scene is bit for bit the MACAEnv of the new
+        episode alone, like a scene of a fresh batch."""
+        items = sorted((int(s), list(agents)) for s, agents in dict(scenes).items())
+        if not items:
+            return
+        if self._paths_on:
+            raise ValueError('restart: waypoint lists are set in this batch (they are one block for all scenes)')
+        for s, agents in items:
+            if not 0 <= s < len(self._envs):
+                raise ValueError(f'restart: no scene {s} in a batch of {len(self._envs)}')
+            lo, hi = int(self.offsets[s]), int(self.offsets[s + 1])
+            if len(agents) != hi - lo:
+                raise ValueError(f'restart: scene {s} holds {hi - lo} agents, the new episode has {len(agents)} (a slot keeps its size)')
+            for i, (a, old) in enumerate(zip(agents, self._flat[lo:hi])):
+                if a.id != i:
+                    raise ValueError(f'restart: scene {s}: agent.id must equal its index in its scene')
+                if len(a._path):
+                    raise ValueError(f'restart: scene {s}, agent {i} carries a path: waypoint lists cannot be replaced per scene')
+                for name, (attr, conv) in _ATTRS.items():
+                    if conv(getattr(a, attr)) != conv(getattr(old, attr)):
+                        raise ValueError(f"restart: scene {s}, agent {i}: {attr} differs from the slot's (a slot keeps its solver attributes)")
+                if self._trk_trip is not None and bool(a.policy.needs_external_vpref) != bool(old.policy.needs_external_vpref):
+                    raise ValueError(f'restart: scene {s}, agent {i} changes between a tracked (SCA, RVO3D+Dubins) and an untracked policy while the '
+                                     "batch carries planner attributes per agent: the tracker's classes are cut by policy")
+                if a.policy.needs_external_vpref and self.device_tracker:
+                    if not self._trk_on:
+                        raise ValueError(f'restart: scene {s}, agent {i} needs the device tracker, which a batch built without such agents has not enabled')
+                    trip = (float(a.turning_radius), float(a.pitchlims[0]), float(a.pitchlims[1]))
+                    if trip != (self._trk_first if self._trk_trip is None else self._trk_trip[lo + i]):
+                        raise ValueError(f"restart: scene {s}, agent {i}: turning_radius / pitchlims differ from the slot's (a slot keeps its planner attributes)")
+        flat = [a for _, agents in items for a in agents]
+        T = len(flat)
+        start = np.array([a.initial_pos for a in flat], dtype=np.float64).reshape(T, 6)
+        goal6 = np.array([a.goal_pos for a in flat], dtype=np.float64).reshape(T, 6)
+        goal = np.array([a.goal_global_frame for a in flat], dtype=np.float64).reshape(T, 3)
+        policy = np.array([a.policy.policy_id for a in flat], np.uint8)
+        self.solver.restart_scenes([s for s, _ in items], np.array([a._pos for a in flat], dtype=np.float64).reshape(T, 3),
+                                   np.array([a._heading for a in flat], dtype=np.float64).reshape(T, 3),
+                                   vel=np.array([a._vel for a in flat], dtype=np.float32).reshape(T, 3), radius=[a.radius for a in flat],
+                                   pref_speed=[a.pref_speed for a in flat], goal=goal, policy=policy, zaxis=S.zaxis_flags(start, goal6),
+                                   max_run_dist=[a.max_run_dist for a in flat], goal_heading=goal6[:, 3:6] if self._trk_on else None)
+        at = 0
+        for s, agents in items:
+            lo, hi = int(self.offsets[s]), int(self.offsets[s + 1])
+            view = self._envs[s]
+            self._flat[lo:hi] = agents
+            view.agents = agents
+            self.goal[lo:hi] = goal[at:at + hi - lo]                 # (view.goal is a view of these rows)
+            self.policy_ids[lo:hi] = policy[at:at + hi - lo]
+            self._ext[lo:hi] = [a.policy.needs_external_vpref for a in agents]
+            view._time_cum = [0.0]
+            for a in agents:
+                a._env = view
+                a._row_pos = a._row_vel = a._row_heading = None
+                a.policy._env = view
+                a.policy._agent_id = a.id
+            at += hi - lo
+        self._stale = True                                           # the mirrors (views of the batch's arrays) refresh in place on first use
+        self._nbr_cache = None
+        self._vpref_cache = None
+        st = self.solver.scene_state()
+        self.active, self.steps = st['active'], st['steps']
+
     # ---- one step of every live scene ------------------------------------------------------------------------------------------------------
     def step(self, actions=None):
         """One resident step of all scenes (finished scenes are inert).  True when every scene is done."""
@@ -269,3 +340,79 @@ class SceneBatch:
         self._nbr_cache = None
         self._vpref_cache = None
         return total == 0
+
+
+# ---- a queue of any length through B slots -----------------------------------------------------------------------------------------------
+def plan_slots(sizes, slots):
+    """Which queue entries the slots start with: entry i in slot i, after one slot has been reserved for every distinct agent count in the
+    queue (a slot keeps its size, so a count without a slot could never run).  Returns the entries in slot order -- min(slots, len(sizes))
+    of them; ValueError when there are fewer slots than distinct counts."""
+    sizes = [int(n) for n in sizes]
+    first = {}
+    for i, n in enumerate(sizes):
+        first.setdefault(n, i)
+    if slots < len(first):
+        raise ValueError(f'{slots} slots for a queue with {len(first)} distinct agent counts: every count needs a slot of its own')
+    chosen = set(first.values())
+    for i in range(len(sizes)):
+        if len(chosen) >= min(slots, len(sizes)):
+            break
+        chosen.add(i)
+    return sorted(chosen)
+
+
+def next_episode(slot_size, pending_sizes):
+    """The position in `pending_sizes` (the agent counts of the episodes not started yet, in queue order) of the episode a finished slot of
+    `slot_size` agents takes: the first of its size; None when there is none -- the slot then stays done."""
+    for k, n in enumerate(pending_sizes):
+        if int(n) == int(slot_size):
+            return k
+    return None
+
+
+def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=None, max_steps=None, stats=None):
+    """Streams a queue of episodes (Agent lists, each numbered 0 .. n - 1) through `slots` scenes of ONE SceneBatch: when a scene finishes,
+    its metrics, step count and final state are taken and the slot restarts with the next episode of its size (SceneBatch.restart), while
+    the other slots keep running.  Obstacles are one list shared by all episodes.  Returns one dict per episode in queue order:
+    episode, slot, metrics (metrics.episode_metrics), steps, state (pos, vel, heading, flags, total_dist, step_num); on_done(result) is
+    called as each finishes.  With device_tracker, the tracker is enabled by the episodes the slots START with: a queue whose first tracked
+    (SCA, RVO3D+Dubins) episode comes later is refused here, before the first step (ValueError).  An episode that a slot cannot take (SceneBatch.restart's
+    rules: a path, other solver or planner attributes) raises when its turn comes.  The dict of an episode that max_steps cut short is None.  `stats`, a dict, receives batch_steps, agent_steps
+    (agents served, summed over the steps) and live_fraction (their mean share of the batch's agents per step)."""
+    episodes = [list(e) for e in episodes]
+    sizes = [len(e) for e in episodes]
+    holding = plan_slots(sizes, slots)
+    batch_agents = sum(sizes[i] for i in holding)               # the slots keep their sizes: the batch's agent count, for live_fraction
+    pending = [i for i in range(len(episodes)) if i not in set(holding)]
+    tracked = [any(a.policy.needs_external_vpref for a in e) for e in episodes]
+    if device_tracker and any(tracked[i] for i in pending) and not any(tracked[i] for i in holding):
+        raise ValueError('run_episodes: episode %d needs the device tracker, but none of the episodes the slots start with does, so the batch '
+                         'would run without one: put a tracked episode among the first %d' % (min(i for i in pending if tracked[i]), len(holding)))
+    batch = SceneBatch([episodes[i] for i in holding], obstacles, device_tracker=device_tracker)
+    results = [None] * len(episodes)
+    batch_steps = served = 0
+    try:
+        while any(h is not None for h in holding) and (max_steps is None or batch_steps < max_steps):
+            served += int(batch.active.sum())
+            batch.step()
+            batch_steps += 1
+            refill = {}
+            for s, i in enumerate(holding):
+                if i is None or not batch.done[s]:
+                    continue
+                lo, hi = int(batch.offsets[s]), int(batch.offsets[s + 1])
+                results[i] = dict(episode=i, slot=s, metrics=metrics.episode_metrics(batch.env(s)), steps=int(batch.steps[s]),
+                                  state={k: batch._state(k)[lo:hi].copy() for k in batch._mirror})
+                if on_done is not None:
+                    on_done(results[i])
+                k = next_episode(sizes[i], [sizes[j] for j in pending])
+                holding[s] = None if k is None else pending.pop(k)
+                if holding[s] is not None:
+                    refill[s] = episodes[holding[s]]
+            if refill:
+                batch.restart(refill)
+    finally:
+        batch.close()
+    if stats is not None:
+        stats.update(batch_steps=batch_steps, agent_steps=served, live_fraction=served / max(1, batch_steps * batch_agents))
+    return results

@@ -49,6 +49,7 @@ class BatchedSolver:
         self.n = 0
         self.m = 0
         self.nscenes = 0
+        self.scene_offsets = None
         self._host_state = None
 
     def close(self):
@@ -86,6 +87,7 @@ class BatchedSolver:
         self.n = n
         self._host_state = None                                   # the block's layout follows n: host_state() fetches it again
         self.nscenes = 0                                          # (sca_set_agents clears the scenes)
+        self.scene_offsets = None
         self._chk(self.L.sca_set_agents(self.ctx, n, _lib.ptr(radius, C.c_double), _lib.ptr(pref_speed, C.c_double),
                                         _lib.ptr(goal, C.c_double), _lib.ptr(policy, C.c_uint8),
                                         _lib.ptr(zaxis, C.c_uint8), _lib.ptr(mrd, C.c_double)), 'sca_set_agents')
@@ -180,10 +182,12 @@ class BatchedSolver:
         if offsets is None or len(offsets) == 0:
             self._chk(self.L.sca_set_scenes(self.ctx, 0, None), 'sca_set_scenes')
             self.nscenes = 0
+            self.scene_offsets = None
             return
         off = np.ascontiguousarray(offsets, np.int32).reshape(-1)
         self._chk(self.L.sca_set_scenes(self.ctx, len(off) - 1, _lib.ptr(off, C.c_int32)), 'sca_set_scenes')
         self.nscenes = len(off) - 1
+        self.scene_offsets = off.copy()
 
     def set_scene_obstacles(self, lists):
         """One (pos [m_s, 3], radius [m_s]) pair per scene: scene s meets its own obstacles and no others (m_s may be 0).  After set_scenes;
@@ -205,6 +209,36 @@ class BatchedSolver:
                   'sca_set_scene_obstacles')
         self.m = int(off[-1])
         self.scene_obstacle_offsets = off
+
+    def restart_scenes(self, ids, pos, heading, vel=None, radius=None, pref_speed=None, goal=None, policy=None, zaxis=None, max_run_dist=None,
+                       goal_heading=None):
+        """New episodes into the scenes `ids` while the others keep running (sca_restart_scenes).  The arrays hold T rows, the named scenes'
+        agents in the order of `ids`; None keeps the slot's values (vel: zero).  Afterwards each named scene is what a context of that
+        episode alone is after set_agents + set_state (+ device_tracker_enable); its agent count, obstacle set and per-agent attributes stay."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        keep = [ids]
+        # T, where the ids name scenes of this context (else the library refuses the call before it reads an array): every array is held
+        # against it here, because the library cannot know how long the caller's buffers are
+        off = self.scene_offsets
+        T = None
+        if off is not None and len(ids) and ids.min() >= 0 and ids.max() < self.nscenes:
+            T = int((off[ids + 1] - off[ids]).sum())
+
+        def arr(a, dt, ct, cols):
+            if a is None:
+                return None
+            b = np.ascontiguousarray(a, dt)
+            if T is not None and b.size != T * (cols or 1):
+                raise ValueError(f'restart_scenes: an array of {b.size} values where the named scenes hold {T} agents x {cols or 1}')
+            b = b.reshape((-1, cols) if cols else (-1,))
+            keep.append(b)
+            return _lib.ptr(b, ct)
+        d3 = lambda a: arr(a, np.float64, C.c_double, 3)
+        d1 = lambda a: arr(a, np.float64, C.c_double, 0)
+        u1 = lambda a: arr(a, np.uint8, C.c_uint8, 0)
+        self._chk(self.L.sca_restart_scenes(self.ctx, len(ids), _lib.ptr(ids, C.c_int32), d3(pos), arr(vel, np.float32, C.c_float, 3), d3(heading),
+                                            d1(radius), d1(pref_speed), d3(goal), u1(policy), u1(zaxis), d1(max_run_dist), d3(goal_heading)),
+                  'sca_restart_scenes')
 
     def scene_state(self):
         """dict(active [B] int32: agents of each scene the next step would serve, steps [B] int32: steps taken while the scene was live)"""
@@ -250,6 +284,12 @@ class BatchedSolver:
         r = np.zeros(self.n, np.int32)
         self._chk(self.L.sca_device_tracker_replans(self.ctx, _lib.ptr(r, C.c_int32)), 'sca_device_tracker_replans')
         return r
+
+    def device_tracker_debug(self, agent):
+        """The device tracker's record of one agent as 24 doubles (sca_device_tracker_debug: the plan, its cursor, now_goal, v_pref, re-plans)"""
+        out = np.zeros(24)
+        self._chk(self.L.sca_device_tracker_debug(self.ctx, int(agent), _lib.ptr(out, C.c_double)), 'sca_device_tracker_debug')
+        return out
 
     # ---- hot path --------------------------------------------------------------------------------------
     def policy_pass(self, mode=NBR_KDTREE):
