@@ -296,19 +296,24 @@ struct sca_ctx {
     uint8_t *hs_host = nullptr;         // page-locked, the caller reads and writes it in place
     uint8_t *hs_dev = nullptr;          // the staging buffer of the staged form (Tunables::hs_staged): same size and layout
     // scene batches (sca_set_scenes, sca_scenes.hip.h): while they are set a pass builds a forest and runs the scene forms of K1 and K4
-    bool scenes_on = false;
-    SceneView scn{};                    // device arrays; live | prev | steps are one allocation (scene_counters)
-    int32_t *scene_counters = nullptr;  // [nscenes * (SCENE_LINE + 2)]
-    std::vector<int32_t> h_scene_off;   // [nscenes + 1] the offsets as set
-    int scene_largest = 0;              // agents of the largest scene: picks the k_kd_block instance
-    bool scene_live_valid = false;      // SceneView::live describes the current records (else: k_scene_recount before anybody reads it)
-    bool scene_begun = false;           // a policy pass has opened a step (scene_begin_one) that no env update has closed yet
-    // one obstacle set per scene (sca_set_scene_obstacles): d.obs .. d.owide hold a forest, K1 and K4 run their per-scene-obstacle forms
-    bool scene_obs_on = false;
-    SceneObsView sov{};                 // device array [nscenes]
-    std::vector<int32_t> h_obs_off;     // [nscenes + 1] the obstacle offsets as set
-    // restarting scenes in place (sca_restart_scenes): the caller's arrays travel through a page-locked block, allocated once for max_n
-    uint8_t *rs_host = nullptr;         // page-locked staging block (RestartLayout of max_n, sca_scenes.h), freed by sca_destroy
+    struct Scenes {
+        bool on = false;
+        SceneView v{};                  // device arrays; live | prev | steps are one allocation (counters)
+        int32_t *counters = nullptr;    // [nscenes * (SCENE_LINE + 2)]
+        std::vector<int32_t> h_off;     // [nscenes + 1] the offsets as set
+        int largest = 0;                // agents of the largest scene: picks the k_kd_block instance
+        bool live_valid = false;        // SceneView::live describes the current records (else: k_scene_recount before anybody reads it)
+        bool begun = false;             // a policy pass has opened a step (scene_begin_one) that no env update has closed yet
+        bool obs_on = false;            // one obstacle set per scene (sca_set_scene_obstacles): d.obs .. d.owide hold a forest, K1 and K4 run their SceneObsRoots instances
+        SceneObsView ov{};              // device array [nscenes]
+        std::vector<int32_t> h_obs_off; // [nscenes + 1] the obstacle offsets as set
+        uint8_t *rs_host = nullptr;     // sca_restart_scenes' page-locked staging block (RestartLayout of max_n, sca_scenes.h), allocated on first use
+        void release() {                // the device and page-locked allocations, behind a synchronised stream; the flags and host vectors stay
+            for (void *p : {(void *)v.scene_of, (void *)v.offsets, (void *)counters, (void *)v.heading_keep, (void *)ov.oroot}) if (p) (void)hipFree(p);
+            if (rs_host) (void)hipHostFree(rs_host);
+            v = SceneView{}; counters = nullptr; ov = SceneObsView{}; rs_host = nullptr;
+        }
+    } scenes;
     std::vector<uint8_t> h_policy;      // [n] the agents' policies as they stand (sca_set_agents, sca_restart_scenes)
     sca_dubins::AgentTrack *trk_init = nullptr;   // one default-constructed tracker record on the device (sca_device_tracker_enable)
 };
@@ -899,12 +904,10 @@ void sca_destroy(sca_ctx *c) {
     (void)tracker_free(c);
     (void)part_free(c);
     for (void *p : {(void *)c->path.off, (void *)c->path.pts, (void *)c->path.rem, (void *)c->path.now_goal}) if (p) (void)hipFree(p);
-    for (void *p : {(void *)c->scn.scene_of, (void *)c->scn.offsets, (void *)c->scene_counters, (void *)c->scn.heading_keep}) if (p) (void)hipFree(p);
-    if (c->sov.oroot) (void)hipFree((void *)c->sov.oroot);
+    c->scenes.release();
     if (c->h_done) { (void)hipHostFree(c->h_done); c->h_done = nullptr; }
     if (c->hs_host) { (void)hipHostFree(c->hs_host); c->hs_host = nullptr; }
     if (c->hs_dev) { (void)hipFree(c->hs_dev); c->hs_dev = nullptr; }
-    if (c->rs_host) { (void)hipHostFree(c->rs_host); c->rs_host = nullptr; }
     if (c->ap_dev) { (void)hipFree(c->ap_dev); (void)hipFree(c->ap_nd); c->ap_dev = nullptr; c->ap_nd = nullptr; }
     void *ptrs[] = {c->rec_own, c->rec_new_own, d.heading, d.goal, d.pref_speed, d.vpref_ext, d.total_dist, d.max_run_dist,
                     d.step_num, d.vpref_mode, d.policy, d.zaxis, d.obs, d.obs_sorted, d.awide, d.owide, d.atree, d.aperm, d.otree, d.operm, d.nbr_n,
@@ -1118,7 +1121,7 @@ int sca_set_state(sca_ctx *c, const double *pos, const float *vel, const double 
     if (step_num) CHK(c, hipMemcpyAsync(c->d.step_num, step_num, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
     CHK(c, hipStreamSynchronize(c->stream));
     c->state_set = true; c->state_fresh = true;
-    c->scene_live_valid = false; c->scene_begun = false;
+    c->scenes.live_valid = false; c->scenes.begun = false;
     if (c->part_on) return part_classify(c);                              // a complete state again: ownership follows from it
     return 0;
 }
@@ -1151,8 +1154,8 @@ int sca_get_state(sca_ctx *c, double *pos, float *vel, double *heading, uint8_t 
 int sca_set_kd_perm(sca_ctx *c, const int32_t *perm) {
     API_ENTER(c);
     ARG(c, perm && c->agents_set);
-    if (c->scenes_on) {
-        const int at = scenes_perm_fault(c->scn.nscenes, c->h_scene_off.data(), perm);
+    if (c->scenes.on) {
+        const int at = scenes_perm_fault(c->scenes.v.nscenes, c->scenes.h_off.data(), perm);
         if (at >= 0) {
             c->err = "sca_set_kd_perm: position " + std::to_string(at) + " holds agent " + std::to_string(perm[at]) + ", which is not of that position's scene (sca_set_scenes)";
             return SCA_ERR_ARG;
@@ -1176,7 +1179,7 @@ int sca_get_kd_perm(sca_ctx *c, int32_t *perm) {
 int sca_get_kd_tree(sca_ctx *c, double *tree_out) {
     API_ENTER(c);
     ARG(c, tree_out && c->agents_set);
-    if (c->scenes_on) { c->err = "sca_get_kd_tree with scenes set (sca_set_scenes): the context holds a forest, one tree per scene"; return SCA_ERR_UNSUPPORTED; }
+    if (c->scenes.on) { c->err = "sca_get_kd_tree with scenes set (sca_set_scenes): the context holds a forest, one tree per scene"; return SCA_ERR_UNSUPPORTED; }
     const int n = c->n;
     std::vector<KdNode> t((size_t)2 * n, KdNode{});
     if (!c->perm_on_device) {
@@ -1324,23 +1327,23 @@ int sca_set_path_state(sca_ctx *c, const int32_t *remaining, const double *now_g
 // The per-scene obstacle sets go with the scenes they were cut for -- and the context is left without obstacles: the shared set they
 // replaced is not kept.
 static int scene_obstacles_drop(sca_ctx *c) {
-    if (!c->scene_obs_on) return 0;
+    if (!c->scenes.obs_on) return 0;
     CHK(c, hipStreamSynchronize(c->stream));
-    if (c->sov.oroot) (void)hipFree((void *)c->sov.oroot);
-    c->sov = SceneObsView{};
-    c->h_obs_off.clear();
-    c->scene_obs_on = false;
+    if (c->scenes.ov.oroot) (void)hipFree((void *)c->scenes.ov.oroot);
+    c->scenes.ov = SceneObsView{};
+    c->scenes.h_obs_off.clear();
+    c->scenes.obs_on = false;
     c->m = 0; c->d.m = 0; c->max_obs_radius = 0;
     c->near_valid = false;
     return 0;
 }
 static int scenes_clear(sca_ctx *c) {
-    if (!c->scenes_on) return 0;
+    if (!c->scenes.on) return 0;
     if (int r = scene_obstacles_drop(c)) return r;
     CHK(c, hipStreamSynchronize(c->stream));
-    c->scenes_on = false;
-    c->h_scene_off.clear();
-    c->scene_largest = 0; c->scene_live_valid = false; c->scene_begun = false;
+    c->scenes.on = false;
+    c->scenes.h_off.clear();
+    c->scenes.largest = 0; c->scenes.live_valid = false; c->scenes.begun = false;
     return 0;
 }
 int sca_set_scenes(sca_ctx *c, int nscenes, const int32_t *offsets) {
@@ -1365,32 +1368,31 @@ int sca_set_scenes(sca_ctx *c, int nscenes, const int32_t *offsets) {
     if (c->d.shard_begin != 0 || c->d.shard_count != n) { c->err = "sca_set_scenes on a shard (sca_set_shard): scenes are stepped by one rank, whole"; return SCA_ERR_UNSUPPORTED; }
     CHK(c, hipStreamSynchronize(c->stream));
     if (int r = scene_obstacles_drop(c)) return r;                    // (cut for the scenes that go)
-    for (void *p : {(void *)c->scn.scene_of, (void *)c->scn.offsets, (void *)c->scene_counters, (void *)c->scn.heading_keep}) if (p) (void)hipFree(p);
-    c->scn = SceneView{}; c->scene_counters = nullptr; c->scenes_on = false;
+    c->scenes.release(); c->scenes.on = false;
     int32_t *so = nullptr, *off = nullptr;
     CHK(c, hipMalloc((void **)&so, sizeof(int32_t) * (size_t)n));
-    c->scn.scene_of = so;
+    c->scenes.v.scene_of = so;
     CHK(c, hipMalloc((void **)&off, sizeof(int32_t) * ((size_t)nscenes + 1)));
-    c->scn.offsets = off;
+    c->scenes.v.offsets = off;
     const size_t words = (size_t)nscenes * (SCENE_LINE + 2);
-    CHK(c, hipMalloc((void **)&c->scene_counters, sizeof(int32_t) * words));
-    c->scn.live = c->scene_counters; c->scn.prev = c->scene_counters + (size_t)nscenes * SCENE_LINE; c->scn.steps = c->scn.prev + nscenes;
-    c->scn.nscenes = nscenes;
-    CHK(c, hipMalloc((void **)&c->scn.heading_keep, sizeof(double) * 3 * (size_t)n));       // (written by k_scene_recount before any step reads it)
+    CHK(c, hipMalloc((void **)&c->scenes.counters, sizeof(int32_t) * words));
+    c->scenes.v.live = c->scenes.counters; c->scenes.v.prev = c->scenes.counters + (size_t)nscenes * SCENE_LINE; c->scenes.v.steps = c->scenes.v.prev + nscenes;
+    c->scenes.v.nscenes = nscenes;
+    CHK(c, hipMalloc((void **)&c->scenes.v.heading_keep, sizeof(double) * 3 * (size_t)n));       // (written by k_scene_recount before any step reads it)
     std::vector<int32_t> of((size_t)n);
     for (int sc = 0; sc < nscenes; sc++) for (int a = offsets[sc]; a < offsets[sc + 1]; a++) of[a] = sc;
     CHK(c, hipMemcpyAsync(so, of.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     CHK(c, hipMemcpyAsync(off, offsets, sizeof(int32_t) * ((size_t)nscenes + 1), hipMemcpyHostToDevice, c->stream));
-    CHK(c, hipMemsetAsync(c->scene_counters, 0, sizeof(int32_t) * words, c->stream));
+    CHK(c, hipMemsetAsync(c->scenes.counters, 0, sizeof(int32_t) * words, c->stream));
     CHK(c, hipStreamSynchronize(c->stream));
-    c->h_scene_off.assign(offsets, offsets + nscenes + 1);
-    c->scene_largest = k.largest;
+    c->scenes.h_off.assign(offsets, offsets + nscenes + 1);
+    c->scenes.largest = k.largest;
     for (int i = 0; i < n; i++) c->h_perm[i] = i;                     // every scene's kdTree.agentIDs starts as 0 .. n_s - 1 (kdTree.py:43-45)
     c->perm_on_device = false;
-    c->scene_live_valid = false; c->scene_begun = false;
+    c->scenes.live_valid = false; c->scenes.begun = false;
     c->kd_single_hint = 0; c->kd_gen++; c->kd_ahead = false; c->kdq_last = -1; c->auto_backoff = 0; c->near_valid = false;
     c->nbr_mode = SCA_NBR_KDTREE;
-    c->scenes_on = true;
+    c->scenes.on = true;
     return 0;
 }
 // One obstacle set per scene.  The reference builds a scene's obstacle tree once, over its own obstacles (mampenv.py:20, kdTree.py:162-227):
@@ -1399,8 +1401,8 @@ int sca_set_scenes(sca_ctx *c, int nscenes, const int32_t *offsets) {
 // max_obs_radius, and with it the collision reach, stays one value per context: a conservative filter, as max_radius is for scenes.
 int sca_set_scene_obstacles(sca_ctx *c, int nscenes, const int32_t *obs_offsets, const double *pos, const double *radius) {
     API_ENTER(c);
-    if (!c->scenes_on) { c->err = "sca_set_scene_obstacles: no scenes -- sca_set_scenes first"; return SCA_ERR_STATE; }
-    const int B = c->scn.nscenes;
+    if (!c->scenes.on) { c->err = "sca_set_scene_obstacles: no scenes -- sca_set_scenes first"; return SCA_ERR_STATE; }
+    const int B = c->scenes.v.nscenes;
     const SceneObsCheck k = scene_obstacles_check(B, c->max_m, nscenes, obs_offsets, pos != nullptr, radius != nullptr);
     if (k.fault != SCENE_OBS_OK) {
         switch (k.fault) {
@@ -1441,8 +1443,8 @@ int sca_set_scene_obstacles(sca_ctx *c, int nscenes, const int32_t *obs_offsets,
     }
     int32_t *dr = nullptr;
     CHK(c, hipMalloc((void **)&dr, sizeof(int32_t) * (size_t)B));
-    if (c->sov.oroot) (void)hipFree((void *)c->sov.oroot);
-    c->sov.oroot = dr;
+    if (c->scenes.ov.oroot) (void)hipFree((void *)c->scenes.ov.oroot);
+    c->scenes.ov.oroot = dr;
     CHK(c, hipMemcpyAsync(dr, roots.data(), sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, c->stream));
     CHK(c, hipMemcpyAsync(c->d.obs, h.data(), sizeof(ObsRec) * (size_t)M, hipMemcpyHostToDevice, c->stream));
     CHK(c, hipMemcpyAsync(c->d.operm, perm.data(), sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice, c->stream));
@@ -1451,30 +1453,30 @@ int sca_set_scene_obstacles(sca_ctx *c, int nscenes, const int32_t *obs_offsets,
     CHK(c, hipMemcpyAsync(c->d.obs_sorted, sorted.data(), sizeof(ObsRec) * (size_t)M, hipMemcpyHostToDevice, c->stream));
     CHK(c, hipStreamSynchronize(c->stream));
     c->m = M; c->d.m = M; c->max_obs_radius = max_r;
-    c->h_obs_off.assign(obs_offsets, obs_offsets + B + 1);
+    c->scenes.h_obs_off.assign(obs_offsets, obs_offsets + B + 1);
     c->near_valid = false;
-    c->scene_obs_on = true;
+    c->scenes.obs_on = true;
     return 0;
 }
 // SceneView::live from the records, where the state came from outside since the last env update (on `s`, which the records are final on)
 static int scenes_recount(sca_ctx *c, hipStream_t s) {
-    if (c->scene_live_valid) return 0;
-    hipLaunchKernelGGL(k_scene_recount, dim3((c->scn.nscenes + 3) / 4), dim3(256), 0, s, c->d, c->scn);
+    if (c->scenes.live_valid) return 0;
+    hipLaunchKernelGGL(k_scene_recount, dim3((c->scenes.v.nscenes + 3) / 4), dim3(256), 0, s, c->d, c->scenes.v);
     CHK(c, hipGetLastError());
-    c->scene_live_valid = true;
+    c->scenes.live_valid = true;
     return 0;
 }
 int sca_get_scene_state(sca_ctx *c, int32_t *active, int32_t *steps) {
     API_ENTER(c);
-    if (!c->scenes_on) { c->err = "no scenes (sca_set_scenes)"; return SCA_ERR_STATE; }
+    if (!c->scenes.on) { c->err = "no scenes (sca_set_scenes)"; return SCA_ERR_STATE; }
     if (!c->state_set) { c->err = "sca_set_state first"; return SCA_ERR_STATE; }
-    const int B = c->scn.nscenes;
-    if (!c->scene_begun) { if (int r = scenes_recount(c, c->stream)) return r; }
+    const int B = c->scenes.v.nscenes;
+    if (!c->scenes.begun) { if (int r = scenes_recount(c, c->stream)) return r; }
     std::vector<int32_t> h((size_t)B * (SCENE_LINE + 2));
-    CHK(c, hipMemcpyAsync(h.data(), c->scene_counters, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, c->stream));
+    CHK(c, hipMemcpyAsync(h.data(), c->scenes.counters, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, c->stream));
     CHK(c, hipStreamSynchronize(c->stream));
     // (between a policy pass and its env update the step under way has emptied `live`: what it found is in `prev`)
-    if (active) for (int sc = 0; sc < B; sc++) active[sc] = c->scene_begun ? h[(size_t)B * SCENE_LINE + sc] : h[(size_t)sc * SCENE_LINE];
+    if (active) for (int sc = 0; sc < B; sc++) active[sc] = c->scenes.begun ? h[(size_t)B * SCENE_LINE + sc] : h[(size_t)sc * SCENE_LINE];
     if (steps) for (int sc = 0; sc < B; sc++) steps[sc] = h[(size_t)B * (SCENE_LINE + 1) + sc];
     return 0;
 }
@@ -1489,7 +1491,7 @@ int sca_restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const do
                        const double *max_run_dist, const double *goal_heading) {
     API_ENTER(c);
     const RestartArgs A{count, scene_ids, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading};
-    const RestartCtx X{c->scenes_on ? c->scn.nscenes : 0, c->scenes_on ? c->h_scene_off.data() : nullptr, c->state_set, c->scene_begun, c->trk_on,
+    const RestartCtx X{c->scenes.on ? c->scenes.v.nscenes : 0, c->scenes.on ? c->scenes.h_off.data() : nullptr, c->state_set, c->scenes.begun, c->trk_on,
                        c->paths_on, c->trk_on && c->trk_view.R_pa != nullptr, c->h_policy.data()};
     const RestartCheck k = scene_restart_check(X, A);
     if (k.fault != RESTART_OK) {
@@ -1499,7 +1501,7 @@ int sca_restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const do
         case RESTART_NO_STATE: c->err = "sca_restart_scenes: no state yet -- sca_set_state first"; break;
         case RESTART_MID_STEP: c->err = "sca_restart_scenes between a policy pass and its env update: finish the step first"; break;
         case RESTART_BAD_COUNT: c->err = "sca_restart_scenes: count must be positive and scene_ids not NULL"; break;
-        case RESTART_BAD_ID: c->err = "sca_restart_scenes: scene_ids[" + at + "] = " + std::to_string(scene_ids[k.entry]) + " is not a scene of this context (0 .. " + std::to_string(c->scn.nscenes - 1) + ")"; break;
+        case RESTART_BAD_ID: c->err = "sca_restart_scenes: scene_ids[" + at + "] = " + std::to_string(scene_ids[k.entry]) + " is not a scene of this context (0 .. " + std::to_string(c->scenes.v.nscenes - 1) + ")"; break;
         case RESTART_REPEATED_ID: c->err = "sca_restart_scenes: scene_ids[" + at + "] = " + std::to_string(scene_ids[k.entry]) + " is named twice"; break;
         case RESTART_NO_ARRAYS: c->err = "sca_restart_scenes: pos and heading must not be NULL"; break;
         case RESTART_NOT_FINITE: c->err = "sca_restart_scenes: row " + at + " holds a number that is not finite"; break;
@@ -1514,16 +1516,16 @@ int sca_restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const do
     }
     const int T = k.total;
     const RestartLayout L = scene_restart_layout(c->max_n);
-    if (!c->rs_host) {                                                    // mapped and coherent, as the host state block is: the kernel reads it in place
-        CHK(c, hipHostMalloc((void **)&c->rs_host, (size_t)L.total, hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(c->rs_host, 0, (size_t)L.total);
+    if (!c->scenes.rs_host) {                                                    // mapped and coherent, as the host state block is: the kernel reads it in place
+        CHK(c, hipHostMalloc((void **)&c->scenes.rs_host, (size_t)L.total, hipHostMallocMapped | hipHostMallocCoherent));
+        std::memset(c->scenes.rs_host, 0, (size_t)L.total);
     }
-    uint8_t *b = c->rs_host;
+    uint8_t *b = c->scenes.rs_host;
     int32_t *ids = (int32_t *)(b + L.off[RS_IDS]), *start = (int32_t *)(b + L.off[RS_START]);
     uint8_t *pol = b + L.off[RS_POLICY], *mode = b + L.off[RS_VPREF_MODE];
     bool policy_changed = false;
     for (int e = 0, r = 0; e < count; e++) {
-        const int lo = c->h_scene_off[scene_ids[e]], hi = c->h_scene_off[scene_ids[e] + 1];
+        const int lo = c->scenes.h_off[scene_ids[e]], hi = c->scenes.h_off[scene_ids[e] + 1];
         ids[e] = scene_ids[e]; start[e] = r;
         for (int a = lo; a < hi; a++, r++) {
             const uint8_t p = policy ? policy[r] : c->h_policy[a];
@@ -1545,11 +1547,11 @@ int sca_restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const do
     put(RS_ZAXIS, zaxis, (size_t)T, RESTART_HAS_ZAXIS);
     RestartDev d{};
     d.rec = c->d.rec;
-    d.heading = c->d.heading; d.heading_keep = c->scn.heading_keep; d.total_dist = c->d.total_dist; d.goal = c->d.goal;
+    d.heading = c->d.heading; d.heading_keep = c->scenes.v.heading_keep; d.total_dist = c->d.total_dist; d.goal = c->d.goal;
     d.pref_speed = c->d.pref_speed; d.max_run_dist = c->d.max_run_dist; d.vpref_ext = c->d.vpref_ext; d.step_num = c->d.step_num;
     d.policy = c->d.policy; d.zaxis = c->d.zaxis; d.vpref_mode = c->d.vpref_mode; d.nbr_valid = c->d.nbr_valid;
     d.aperm = c->d.aperm; d.nbr_n = c->d.nbr_n; d.near_n = c->d.near_n; d.done_count = c->d.done_count;
-    d.offsets = c->scn.offsets; d.live = c->scn.live; d.prev = c->scn.prev; d.steps = c->scn.steps;
+    d.offsets = c->scenes.v.offsets; d.live = c->scenes.v.live; d.prev = c->scenes.v.prev; d.steps = c->scenes.v.steps;
     if (c->trk_on) {
         static_assert(sizeof(sca_dubins::AgentTrack) % 4 == 0, "k_scene_restart copies the tracker record as 4-byte words");
         d.trk_nbr0 = c->trk.nbr0; d.trk_goal_heading = c->trk_goal_heading;
@@ -1561,7 +1563,7 @@ int sca_restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const do
     if (policy_changed) {
         std::vector<uint8_t> now = c->h_policy;
         for (int e = 0; e < count; e++)
-            for (int a = c->h_scene_off[scene_ids[e]], r = start[e]; a < c->h_scene_off[scene_ids[e] + 1]; a++, r++) now[a] = pol[r];
+            for (int a = c->scenes.h_off[scene_ids[e]], r = start[e]; a < c->scenes.h_off[scene_ids[e] + 1]; a++, r++) now[a] = pol[r];
         for (int i = 0; i < c->n; i++) if (now[i] == SCA_POLICY_ORCA3D_LP) lp_new.push_back(i);
         if (!lp_new.empty())
             CHK(c, hipMemcpyAsync(c->lp_list, lp_new.data(), sizeof(int32_t) * lp_new.size(), hipMemcpyHostToDevice, c->stream));
@@ -1573,7 +1575,7 @@ int sca_restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const do
     // device may then hold the new episode while h_policy, h_rec and h_perm hold the old -- as after any failed HIP call, the context is to
     // be set up again (sca_set_agents), not stepped on.
     for (int e = 0; e < count; e++)
-        for (int a = c->h_scene_off[scene_ids[e]], r = start[e]; a < c->h_scene_off[scene_ids[e] + 1]; a++, r++) {
+        for (int a = c->scenes.h_off[scene_ids[e]], r = start[e]; a < c->scenes.h_off[scene_ids[e] + 1]; a++, r++) {
             c->h_policy[a] = pol[r];
             if (radius) { c->h_rec[a].radius = radius[r]; c->max_radius = std::max(c->max_radius, radius[r]); }
             if (pref_speed) c->max_pref_speed = std::max(c->max_pref_speed, pref_speed[r]);
@@ -1633,8 +1635,8 @@ static int build_agent_tree_device(sca_ctx *c, hipStream_t ks, const DeviceView 
     // plan (no size limit: a level with more chunks than the chip holds at once takes its chunks by arrival, k_kd_lv_rank<true>)
     // (scenes: the forest plan -- every scene a root job of k_kd_block, no top, no level passes, no statistics)
     KdBuildPlan B{};
-    if (c->scenes_on) {
-        const KdForestPlan F = plan_kd_forest(c->scene_largest, c->scn.nscenes);
+    if (c->scenes.on) {
+        const KdForestPlan F = plan_kd_forest(c->scenes.largest, c->scenes.v.nscenes);
         B.wave_max = F.block; B.block = F.block; B.sgrid = F.grid;
         if (int r = scenes_recount(c, ks)) return r;                   // (a state from outside: the live counts the step opens with)
     } else B = plan_kd_build(c->tun, n, c->trk_on && c->trk_in_pass && ks != c->stream, c->kd_single_hint, c->kd.chunk_cap, c->kd_rank_capacity);
@@ -1657,10 +1659,10 @@ static int build_agent_tree_device(sca_ctx *c, hipStream_t ks, const DeviceView 
         LAUNCH_REC(c, c->ev_auto_gather[c->auto_builds & 1u], k_kd_gather, dim3((n + 255) / 256), dim3(256), ks, d, c->kd, c->P);
         c->auto_builds++;
     } else hipLaunchKernelGGL(k_kd_gather, dim3((n + 255) / 256), dim3(256), 0, ks, d, c->kd, c->P);
-    if (c->scenes_on) {
+    if (c->scenes.on) {
         // the forest's job table behind the gather (which rewrites the single root job and the counts on every build); opens the step
-        hipLaunchKernelGGL(k_kd_scene_jobs, dim3((c->scn.nscenes + 255) / 256), dim3(256), 0, ks, c->kd, c->scn, c->scene_begun ? 0 : 1);
-        c->scene_begun = true;
+        hipLaunchKernelGGL(k_kd_scene_jobs, dim3((c->scenes.v.nscenes + 255) / 256), dim3(256), 0, ks, c->kd, c->scenes.v, c->scenes.begun ? 0 : 1);
+        c->scenes.begun = true;
     }
     if (B.top && B.levels) hipLaunchKernelGGL(k_kd_top, dim3(1), dim3(KT_T), 0, ks, d, c->kd);
     if (B.level_passes) {
@@ -1907,7 +1909,7 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
     // SCA_NBR_AUTO: an AUTO pass, or a plain kd pass where that cannot help (plan_auto; the cell-owner partition has its own structures)
     bool auto_mode = false;
     int kdq_blocks = KDQ_BLOCKS;
-    if (c->scenes_on && scenes_neighbor_mode(mode) < 0) {
+    if (c->scenes.on && scenes_neighbor_mode(mode) < 0) {
         c->err = "scenes are set (sca_set_scenes): the scene form of the neighbour search is SCA_NBR_KDTREE (SCA_NBR_AUTO resolves to it)";
         return SCA_ERR_UNSUPPORTED;
     }
@@ -1915,7 +1917,7 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
         double ar, orr;
         collide_reach(c, ar, orr);
         // (scenes: the grid's cell key carries no scene id -- one more place where it cannot help)
-        const bool fits = !c->scenes_on && c->max_radius + ar <= c->P.neighbor_dist && c->max_radius + orr <= c->P.neighbor_dist;
+        const bool fits = !c->scenes.on && c->max_radius + ar <= c->P.neighbor_dist && c->max_radius + orr <= c->P.neighbor_dist;
         if (c->part_on) { c->err = "the cell-owner partition is a mode of SCA_NBR_GRID"; return SCA_ERR_UNSUPPORTED; }
         if (int r = auto_prepare(c)) return r;
         if (c->kdq_pending && hipEventQuery(c->ev_auto_cnt) == hipSuccess) { c->kdq_last = c->kdq_host[0]; c->kdq_pending = false; }   // poll
@@ -1959,8 +1961,8 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
     }
     const bool split = S.split, solve_fb = S.solve_fb;
     c->d.lp_kernel = S.lp_kernel;
-    int forms = S.forms | (c->paths_on ? SCA_FORM_WAYPOINTS : 0) | (c->scenes_on ? SCA_FORM_SCENES : 0) |
-                (c->scene_obs_on ? SCA_FORM_SCENE_OBSTACLES : 0);     // (the waypoint and scene bits are state, not a choice)
+    int forms = S.forms | (c->paths_on ? SCA_FORM_WAYPOINTS : 0) | (c->scenes.on ? SCA_FORM_SCENES : 0) |
+                (c->scenes.obs_on ? SCA_FORM_SCENE_OBSTACLES : 0);     // (the waypoint and scene bits are state, not a choice)
     c->kd.skip_prep = overlap ? 1 : 0;
     c->grid.skip_prep = overlap ? 1 : 0;
     if (mode == SCA_NBR_GRID) {
@@ -2046,16 +2048,14 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
     } else if (mode == SCA_NBR_GRID) {
         const auto k1 = obs ? k_neighbors_grid<false, true> : k_neighbors_grid<false, false>;
         LAUNCH_OPT(c, k1_stop, k1, k1p_grid, k1p_block, ns, d, c->grid, c->P, agent_reach, obs_reach, c->max_radius);
-    } else if (c->scene_obs_on && S.packed) {                         // (scene_obs_on: scenes are set, and there is at least one obstacle)
-        LAUNCH_OPT(c, k1_stop, k_neighbors_kd4_scene_obs, k1p_grid, k1p_block, ns, d, c->P, agent_reach, obs_reach, c->max_radius, c->scn, c->sov);
-    } else if (c->scene_obs_on) {
-        LAUNCH_OPT(c, k1_stop, k_neighbors_kd_scene_obs, dim3(std::min((cnt + K1_WAVES - 1) / K1_WAVES, MAX_GRID)), dim3(K1_WAVES * 64), ns, d, c->P, agent_reach, obs_reach, c->max_radius, c->scn, c->sov);
-    } else if (c->scenes_on && S.packed) {
-        const auto k1 = obs ? k_neighbors_kd4_scenes<true> : k_neighbors_kd4_scenes<false>;
-        LAUNCH_OPT(c, k1_stop, k1, k1p_grid, k1p_block, ns, d, c->P, agent_reach, obs_reach, c->max_radius, c->scn);
-    } else if (c->scenes_on) {
-        const auto k1 = obs ? k_neighbors_kd_scenes<true> : k_neighbors_kd_scenes<false>;
-        LAUNCH_OPT(c, k1_stop, k1, dim3(std::min((cnt + K1_WAVES - 1) / K1_WAVES, MAX_GRID)), dim3(K1_WAVES * 64), ns, d, c->P, agent_reach, obs_reach, c->max_radius, c->scn);
+    } else if (c->scenes.on) {                                          // (obs_on: per-scene sets with at least one obstacle, always the obstacle phase)
+        const auto k1 = [&](auto roots, auto has_obs) -> int {          // Roots and HAS_OBS picked once, then the packed or the unpacked form
+            const auto kd4 = k_neighbors_kd4_scenes<decltype(has_obs)::value, decltype(roots)>, kd = k_neighbors_kd_scenes<decltype(has_obs)::value, decltype(roots)>;
+            if (S.packed) LAUNCH_OPT(c, k1_stop, kd4, k1p_grid, k1p_block, ns, d, c->P, agent_reach, obs_reach, c->max_radius, roots);
+            else LAUNCH_OPT(c, k1_stop, kd, dim3(std::min((cnt + K1_WAVES - 1) / K1_WAVES, MAX_GRID)), dim3(K1_WAVES * 64), ns, d, c->P, agent_reach, obs_reach, c->max_radius, roots);
+            return 0;
+        };
+        if (int r = c->scenes.obs_on ? k1(SceneObsRoots{c->scenes.v, c->scenes.ov}, std::true_type()) : obs ? k1(SceneRoots{c->scenes.v}, std::true_type()) : k1(SceneRoots{c->scenes.v}, std::false_type())) return r;
     } else if (S.packed) {
         const auto k1 = obs ? k_neighbors_kd4<true> : k_neighbors_kd4<false>;
         LAUNCH_OPT(c, k1_stop, k1, k1p_grid, k1p_block, ns, d, c->P, agent_reach, obs_reach, c->max_radius);
@@ -2175,9 +2175,9 @@ static int launch_collide_finish(sca_ctx *c, bool timed) {
         c->nbr_stream = c->stream;
         if (int r = build_agent_grid_device(c)) return r;
     }
-    if (c->scenes_on && !c->scene_begun) {                                // no policy pass before: the update opens the step itself
+    if (c->scenes.on && !c->scenes.begun) {                                // no policy pass before: the update opens the step itself
         if (int r = scenes_recount(c, c->stream)) return r;
-        hipLaunchKernelGGL(k_scene_begin, dim3((c->scn.nscenes + 255) / 256), dim3(256), 0, c->stream, c->scn);
+        hipLaunchKernelGGL(k_scene_begin, dim3((c->scenes.v.nscenes + 255) / 256), dim3(256), 0, c->stream, c->scenes.v);
     }
     c->near_valid = false;
     const dim3 k4grid((cnt + K4_WAVES * K4_APW - 1) / (K4_WAVES * K4_APW));
@@ -2185,12 +2185,10 @@ static int launch_collide_finish(sca_ctx *c, bool timed) {
     const bool others = c->part_on || cnt < d.n;
     const hipEvent_t k4_stop = others ? nullptr : c->finish_stop, others_stop = others ? c->finish_stop : nullptr;
     const int fresh = c->state_fresh ? 1 : 0;
-    if (c->scene_obs_on) {
-        LAUNCH_OPT(c, k4_stop, k_collide_finish_scene_obs, k4grid, dim3(K4_WAVES * 64), c->stream, d, c->P, agent_reach, obs_reach, fresh, c->scn, c->sov);
-        c->scene_begun = false; c->scene_live_valid = true;
-    } else if (c->scenes_on) {
-        LAUNCH_OPT(c, k4_stop, k_collide_finish_scenes, k4grid, dim3(K4_WAVES * 64), c->stream, d, c->P, agent_reach, obs_reach, fresh, c->scn);
-        c->scene_begun = false; c->scene_live_valid = true;
+    if (c->scenes.on) {
+        if (c->scenes.obs_on) LAUNCH_OPT(c, k4_stop, k_collide_finish_scenes<SceneObsRoots>, k4grid, dim3(K4_WAVES * 64), c->stream, d, c->P, agent_reach, obs_reach, fresh, SceneObsRoots{c->scenes.v, c->scenes.ov});
+        else LAUNCH_OPT(c, k4_stop, k_collide_finish_scenes<SceneRoots>, k4grid, dim3(K4_WAVES * 64), c->stream, d, c->P, agent_reach, obs_reach, fresh, SceneRoots{c->scenes.v});
+        c->scenes.begun = false; c->scenes.live_valid = true;
     } else if (c->nbr_mode == SCA_NBR_GRID)
         LAUNCH_OPT(c, k4_stop, k_collide_finish_grid, k4grid, dim3(K4_WAVES * 64), c->stream, d, c->grid, c->P, agent_reach, obs_reach, fresh);
     else
@@ -2464,7 +2462,7 @@ int sca_step_host(sca_ctx *c, int neighbor_mode, uint32_t in_mask, int *active) 
             c->h_pos_valid = false;
             c->near_valid = false;
             c->state_set = true; c->state_fresh = true;
-            c->scene_live_valid = false; c->scene_begun = false;
+            c->scenes.live_valid = false; c->scenes.begun = false;
         }
     }
     if (int r = run_steps_guarded(c, 1, neighbor_mode, false)) return r;  // integrate fused into the pass, k_collide_finish; joins the kd stream
@@ -2537,7 +2535,7 @@ int sca_comm_init(sca_ctx *c, int rank, int nranks, const void *unique_id) {
     if (!c->agents_set) { c->err = "sca_set_agents first"; return SCA_ERR_STATE; }
     if (c->comm) { c->err = "communicator already initialised (sca_comm_destroy first)"; return SCA_ERR_STATE; }
     if (c->part_on) { c->err = "sca_comm_init with the cell-owner partition active"; return SCA_ERR_STATE; }
-    if (c->scenes_on) { c->err = "sca_comm_init with scenes set (sca_set_scenes): scenes are one rank's"; return SCA_ERR_UNSUPPORTED; }
+    if (c->scenes.on) { c->err = "sca_comm_init with scenes set (sca_set_scenes): scenes are one rank's"; return SCA_ERR_UNSUPPORTED; }
     if (c->n % nranks) { c->err = "agent count must be a multiple of the rank count"; return SCA_ERR_ARG; }
     if (const char *e = rccl_load()) { c->err = e; return SCA_ERR_UNSUPPORTED; }
     CHK(c, hipSetDevice(c->device));
@@ -2645,7 +2643,7 @@ int sca_partition_init(sca_ctx *c, int rank, int nranks, int axis, const double 
     ARG(c, nranks >= 1 && rank >= 0 && rank < nranks && axis >= 0 && axis <= 2 && cap_halo >= 0 && cap_mig >= 0);
     if (!c->agents_set || !c->state_set) { c->err = "sca_set_agents and sca_set_state (the complete state, on every rank) first"; return SCA_ERR_STATE; }
     if (c->comm) { c->err = "sca_partition_init with an active communicator (the all-gather mode)"; return SCA_ERR_STATE; }
-    if (c->scenes_on) { c->err = "sca_partition_init with scenes set (sca_set_scenes): a mode of SCA_NBR_GRID, which has no scene form"; return SCA_ERR_UNSUPPORTED; }
+    if (c->scenes.on) { c->err = "sca_partition_init with scenes set (sca_set_scenes): a mode of SCA_NBR_GRID, which has no scene form"; return SCA_ERR_UNSUPPORTED; }
     if (c->paths_on) { c->err = "sca_partition_init with waypoint lists set (sca_set_paths): path state does not migrate with the agents"; return SCA_ERR_UNSUPPORTED; }
     if (int r = part_free(c)) return r;
     const int n = c->n;
@@ -3043,7 +3041,7 @@ int sca_set_shard(sca_ctx *c, int begin, int count) {
     // with a communicator the shard IS rank * n / nranks: the in-place ncclAllGather of sca_run_steps relies on it
     if (c->part_on) { c->err = "sca_set_shard with the cell-owner partition active (sca_partition_disable first)"; return SCA_ERR_STATE; }
     if (c->comm) { c->err = "sca_set_shard with an active communicator (the shard follows from rank / nranks; sca_comm_destroy first)"; return SCA_ERR_STATE; }
-    if (c->scenes_on && (begin != 0 || count != c->n)) { c->err = "sca_set_shard with scenes set (sca_set_scenes): scenes are stepped by one rank, whole"; return SCA_ERR_UNSUPPORTED; }
+    if (c->scenes.on && (begin != 0 || count != c->n)) { c->err = "sca_set_shard with scenes set (sca_set_scenes): scenes are stepped by one rank, whole"; return SCA_ERR_UNSUPPORTED; }
     c->d.shard_begin = begin; c->d.shard_count = count;
     c->kd_ahead = false; c->kdq_last = -1; c->auto_backoff = 0;           // another shard: the AUTO passes' counts described the old one
     return 0;

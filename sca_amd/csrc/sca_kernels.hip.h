@@ -621,8 +621,8 @@ constexpr int K1P_APW = 4;
 #define SCA_K1_SETPRIO() ((void)0)
 #endif
 // Where an agent's traversal of the agent tree starts: record 0 -- or, in a context that holds many scenes (sca_set_scenes), the root of the
-// agent's own scene in the forest (k_neighbors_kd4_scenes, sca_scenes.hip.h).  obstacles(agent): the same for the obstacle tree -- 0 for a
-// shared set, the scene's own root with one set per scene (k_neighbors_kd4_scene_obs), < 0: the agent's scene has none, no walk.
+// agent's own scene in the forest (SceneRoots / SceneObsRoots of k_neighbors_kd4_scenes, sca_scenes.hip.h).  obstacles(agent): the same for the
+// obstacle tree -- 0 for a shared set, the scene's own root with one set per scene (SceneObsRoots), < 0: the agent's scene has none, no walk.
 struct RootZero {
     __device__ __forceinline__ int operator()(int) const { return 0; }
     __device__ __forceinline__ int obstacles(int) const { return 0; }

@@ -7,15 +7,15 @@
 //                   subtree contiguously from its root: k members occupy 2k - 1 nodes, so the ranges are disjoint inside awide[2n]); a job
 //                   only permutes inside [begin, end), so the permutation never leaves a scene -- k_kd_scene_jobs writes the job table behind
 //                   the unchanged k_kd_gather
-//   the two queries k_neighbors_kd_scenes / k_neighbors_kd4_scenes start an agent's traversal of the agent tree at its scene's root; a
-//                   shared obstacle tree (sca_set_obstacles) starts at 0
-//   collide / done  k_collide_finish_scenes: the bootstrap traversal from the scene's root, and the live count per scene as well as in total
+//   the two queries k_neighbors_kd_scenes<HAS_OBS, Roots> / k_neighbors_kd4_scenes<HAS_OBS, Roots> start an agent's traversal of the agent
+//                   tree at its scene's root; a shared obstacle tree (sca_set_obstacles) starts at 0
+//   collide / done  k_collide_finish_scenes<Roots>: the bootstrap traversal from the scene's root, and the live count per scene as well as in total
 // A context without scenes launches none of these, and SceneView is an argument of these kernels only (as PathView is of k_waypoint's).
 //
 // One obstacle set per scene (sca_set_scene_obstacles): the obstacle tree is a forest too, built on the host (sca_scenes.h), and the
-// three kernels above have a form each -- k_neighbors_kd_scene_obs / k_neighbors_kd4_scene_obs / k_collide_finish_scene_obs -- whose
-// obstacle walks start at the scene's own obstacle root, or do not happen for a scene without obstacles.  The roots travel in SceneObsView,
-// an argument of these three only: a context with a shared set launches exactly what it launched before.
+// three kernels above are templated on where an agent's walks start: SceneRoots (the scene's agent root, obstacle walks from 0) or
+// SceneObsRoots, whose obstacle walks start at the scene's own obstacle root, or do not happen for a scene without obstacles.  Those roots
+// travel in SceneObsView, a member of SceneObsRoots only: a context with a shared set runs the SceneRoots instances, the code it ran before.
 #pragma once
 #include "sca_kdbuild.hip.h"
 #include "sca_scenes.h"
@@ -34,23 +34,21 @@ struct SceneView {
 };
 constexpr int SCENE_LINE = 32;           // int32 per counter line
 
-__device__ __forceinline__ int scene_root(const SceneView &v, int agent) { return 2 * v.offsets[v.scene_of[agent]]; }
-struct SceneRoot {
-    const SceneView &v;
-    __device__ __forceinline__ int operator()(int agent) const { return scene_root(v, agent); }
-    __device__ __forceinline__ int obstacles(int) const { return 0; }
-};
-
 struct SceneObsView {
     const int32_t *oroot;     // [nscenes] record of owide / otree the scene's obstacle walks start at (2 * obs_offsets[s]), -1: the scene has no obstacles
 };
-// two dependent loads per agent (its scene, the scene's root); every lane that serves an agent reads the same words
-__device__ __forceinline__ int scene_obs_root(const SceneView &v, const SceneObsView &o, int agent) { return o.oroot[v.scene_of[agent]]; }
-struct SceneObsRoot {
-    const SceneView &v;
-    const SceneObsView &o;
-    __device__ __forceinline__ int operator()(int agent) const { return scene_root(v, agent); }
-    __device__ __forceinline__ int obstacles(int agent) const { return scene_obs_root(v, o, agent); }
+// Where an agent's walks start (RootZero, sca_kernels.hip.h): one kernel argument, by value.  Two dependent loads per agent and root (its
+// scene, the scene's root); every lane that serves an agent reads the same words.
+struct SceneRoots {           // one obstacle set shared by all scenes, or none
+    SceneView v;
+    __device__ __forceinline__ int operator()(int agent) const { return 2 * v.offsets[v.scene_of[agent]]; }
+    __device__ __forceinline__ int obstacles(int) const { return 0; }
+};
+struct SceneObsRoots {        // one obstacle set per scene (sca_set_scene_obstacles)
+    SceneView v;
+    SceneObsView o;
+    __device__ __forceinline__ int operator()(int agent) const { return 2 * v.offsets[v.scene_of[agent]]; }
+    __device__ __forceinline__ int obstacles(int agent) const { return o.oroot[v.scene_of[agent]]; }
 };
 
 // start of a step, one thread per scene: a scene that is live when a step begins has taken that step (the reference's `while not env.step()`
@@ -161,26 +159,31 @@ __global__ __launch_bounds__(RESTART_T) void k_scene_restart(RestartDev d, const
     if (t == 0) { d.live[s * SCENE_LINE] = ns; d.prev[s] = ns; d.steps[s] = 0; }
 }
 
-template <bool HAS_OBS>
+// The wavefront-per-agent forms keep both roots in scalar registers: the obstacle phase is taken or skipped by the whole wavefront (the
+// constant 0 of SceneRoots folds away).
+template <bool HAS_OBS, class Roots>
 __global__ __launch_bounds__(K1_WAVES * 64) void k_neighbors_kd_scenes(DeviceView d, Params P, double agent_reach, double obs_reach,
-                                                                       double max_radius, SceneView v) {
+                                                                       double max_radius, Roots r) {
     SCA_TL(d, TL_NBR_KD);
     __shared__ double rstacks[K1_WAVES][KD_RSTACK][16];
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     for (int i = blockIdx.x * K1_WAVES + wid; i < d.shard_count; i += gridDim.x * K1_WAVES) {
         const int agent = d.shard_begin + i;
-        neighbors_one<HAS_OBS>(d, P, agent_reach, obs_reach, max_radius, rstacks[wid], agent, lane, __builtin_amdgcn_readfirstlane(scene_root(v, agent)));
+        neighbors_one<HAS_OBS>(d, P, agent_reach, obs_reach, max_radius, rstacks[wid], agent, lane, __builtin_amdgcn_readfirstlane(r(agent)),
+                               __builtin_amdgcn_readfirstlane(r.obstacles(agent)));
     }
 }
 
-template <bool HAS_OBS>
+// four agents per wavefront: a 16-lane group whose scene has no obstacles enters the obstacle phase with nothing to do (the loop keeps its
+// shape, see neighbors_kd4_body)
+template <bool HAS_OBS, class Roots>
 __global__ __launch_bounds__(K1P_WAVES * 64) void k_neighbors_kd4_scenes(DeviceView d, Params P, double agent_reach, double obs_reach,
-                                                                        double max_radius, SceneView v) {
+                                                                        double max_radius, Roots r) {
     SCA_TL(d, TL_NBR_KD);
     SCA_K1_SETPRIO();
     __shared__ int stacks[K1P_WAVES][K1P_APW][KD_STACK];
-    neighbors_kd4_body<HAS_OBS>(d, P, agent_reach, obs_reach, max_radius, stacks, SceneRoot{v});
+    neighbors_kd4_body<HAS_OBS>(d, P, agent_reach, obs_reach, max_radius, stacks, r);
 }
 
 // The wavefront's K4_APW agents are consecutive ids, so those of one scene are consecutive groups: the first head lane of every run of
@@ -217,53 +220,17 @@ struct SceneCount {
         if (first && mine > 0) atomicAdd(&v.live[sc * SCENE_LINE], mine);
     }
 };
+template <class Roots>
 __global__ __launch_bounds__(K4_WAVES * 64) void k_collide_finish_scenes(DeviceView d, Params P, double agent_reach, double obs_reach,
-                                                                       int check_arrived, SceneView v) {
+                                                                       int check_arrived, Roots r) {
     SCA_TL(d, TL_COLLIDE);
     __shared__ int stacks[K4_WAVES][KD_STACK];
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     collide_finish_body(d, P, check_arrived, [&](int ag, bool obs_only) {
-        return collide_traverse(d, agent_reach, obs_reach, stacks[wid], ag, lane, obs_only, __builtin_amdgcn_readfirstlane(scene_root(v, ag)));
-    }, SceneCount{d, v});
-}
-
-// ---- one obstacle set per scene: the three scene kernels with the obstacle walks rooted per scene --------------------------------------------
-// (launched only while per-scene sets with at least one obstacle are set: always the form with the obstacle phase)
-__global__ __launch_bounds__(K1_WAVES * 64) void k_neighbors_kd_scene_obs(DeviceView d, Params P, double agent_reach, double obs_reach,
-                                                                          double max_radius, SceneView v, SceneObsView o) {
-    SCA_TL(d, TL_NBR_KD);
-    __shared__ double rstacks[K1_WAVES][KD_RSTACK][16];
-    const int lane = threadIdx.x & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    for (int i = blockIdx.x * K1_WAVES + wid; i < d.shard_count; i += gridDim.x * K1_WAVES) {
-        const int agent = d.shard_begin + i;
-        // both roots in scalar registers: the obstacle phase is taken or skipped by the whole wavefront
-        neighbors_one<true>(d, P, agent_reach, obs_reach, max_radius, rstacks[wid], agent, lane, __builtin_amdgcn_readfirstlane(scene_root(v, agent)),
-                            __builtin_amdgcn_readfirstlane(scene_obs_root(v, o, agent)));
-    }
-}
-
-// four agents per wavefront: a 16-lane group whose scene has no obstacles enters the obstacle phase with nothing to do (the loop keeps its
-// shape, see neighbors_kd4_body)
-__global__ __launch_bounds__(K1P_WAVES * 64) void k_neighbors_kd4_scene_obs(DeviceView d, Params P, double agent_reach, double obs_reach,
-                                                                           double max_radius, SceneView v, SceneObsView o) {
-    SCA_TL(d, TL_NBR_KD);
-    SCA_K1_SETPRIO();
-    __shared__ int stacks[K1P_WAVES][K1P_APW][KD_STACK];
-    neighbors_kd4_body<true>(d, P, agent_reach, obs_reach, max_radius, stacks, SceneObsRoot{v, o});
-}
-
-__global__ __launch_bounds__(K4_WAVES * 64) void k_collide_finish_scene_obs(DeviceView d, Params P, double agent_reach, double obs_reach,
-                                                                          int check_arrived, SceneView v, SceneObsView o) {
-    SCA_TL(d, TL_COLLIDE);
-    __shared__ int stacks[K4_WAVES][KD_STACK];
-    const int lane = threadIdx.x & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    collide_finish_body(d, P, check_arrived, [&](int ag, bool obs_only) {
-        return collide_traverse(d, agent_reach, obs_reach, stacks[wid], ag, lane, obs_only, __builtin_amdgcn_readfirstlane(scene_root(v, ag)),
-                                __builtin_amdgcn_readfirstlane(scene_obs_root(v, o, ag)));
-    }, SceneCount{d, v});
+        return collide_traverse(d, agent_reach, obs_reach, stacks[wid], ag, lane, obs_only, __builtin_amdgcn_readfirstlane(r(ag)),
+                                __builtin_amdgcn_readfirstlane(r.obstacles(ag)));
+    }, SceneCount{d, r.v});
 }
 
 }  // namespace sca

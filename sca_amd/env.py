@@ -281,7 +281,158 @@ class _KdTreeView:
         return list(self._env.solver.get_kd_perm())
 
 
-class MACAEnv:
+# the solver attributes the reference keeps per Agent (agent.py:24-41) and its policies read per call (scaPolicy.py:95,112,272,302, util.py:8,17,
+# orca3dPolicyOfficial.py:44,98,108, agent.py:87-99, mampenv.py:90-92): sca_params field -> (Agent attribute, type)
+_ATTRS = dict(neighbor_dist=('neighborDist', float), max_neighbors=('maxNeighbors', int), time_step=('timeStep', float),
+              time_horizon=('timeHorizon', float), max_speed=('maxSpeed', float), max_heading_change=('max_heading_change', float),
+              dt_nominal=('dt_nominal', float))
+
+
+def _planner_triple(a):
+    """the planner's attributes (agent.turning_radius, agent.pitchlims: scaPolicy.py:95,272,302)"""
+    return float(a.turning_radius), float(a.pitchlims[0]), float(a.pitchlims[1])
+
+
+def _obstacle_arrays(obstacles):
+    return (np.array([o.pos_global_frame for o in obstacles], dtype=np.float64).reshape(len(obstacles), 3),
+            np.array([o.radius for o in obstacles], dtype=np.float64))
+
+
+def _bind(agents, env):
+    for a in agents:
+        a._env = env
+        a._row_pos = a._row_vel = a._row_heading = None        # (row views belong to the mirrors of the env they were made for)
+        a.policy._env = env
+        a.policy._agent_id = a.id
+
+
+class _FlatAgents:
+    """What MACAEnv and SceneBatch (scenes.py) share: a flat list of agents on one solver context -- the host mirrors, the hand-over of the
+    agents' attributes, the device tracker's rule, the waypoint lists and the decoding of the neighbour lists."""
+
+    def _create(self, flat, device, max_obstacles, obstacles=None, before_state=None):
+        """Solver context for the agents of `flat`, in the order of calls a context wants: sca_create, the shared `obstacles` (None: the caller
+        sets its own in `before_state`), the agents, per-agent attributes, before_state(), the state, the device tracker."""
+        n = len(flat)
+        self._flat = flat
+        self._mirror = dict(pos=np.array([a._pos for a in flat], dtype=np.float64).reshape(n, 3),
+                            vel=np.array([a._vel for a in flat], dtype=np.float32).reshape(n, 3),
+                            heading=np.array([a._heading for a in flat], dtype=np.float64).reshape(n, 3),
+                            flags=np.zeros(n, np.uint8), total_dist=np.zeros(n), step_num=np.zeros(n, np.int32))
+        self._stale = False
+        self.goal = np.array([a.goal_global_frame for a in flat], dtype=np.float64).reshape(n, 3)
+        self.policy_ids = np.array([a.policy.policy_id for a in flat], np.uint8)
+        self._ext = np.array([a.policy.needs_external_vpref for a in flat], bool)
+        start = np.array([a.initial_pos for a in flat], dtype=np.float64)
+        goal6 = np.array([a.goal_pos for a in flat], dtype=np.float64)
+        # Attributes all agents agree on become the context's sca_params; the ones that differ from agent to agent go to the device as
+        # per-agent arrays (sca_set_agent_params), the context keeping the first agent's value as its default.
+        params, per_agent = {}, {}
+        for name, (attr, conv) in _ATTRS.items():
+            vals = [conv(getattr(a, attr)) for a in flat]
+            params[name] = vals[0]
+            if any(v != vals[0] for v in vals):
+                per_agent[name] = vals
+        sol = self.solver = S.BatchedSolver(max_agents=n, max_obstacles=max(max_obstacles, 1), device=device, params=params)
+        if obstacles is not None:
+            sol.set_obstacles(*_obstacle_arrays(obstacles))
+        sol.set_agents([a.radius for a in flat], [a.pref_speed for a in flat], self.goal, self.policy_ids, S.zaxis_flags(start, goal6),
+                       [a.max_run_dist for a in flat])
+        if per_agent:
+            sol.set_agent_params(**per_agent)
+        if before_state is not None:
+            before_state()
+        sol.set_state(self._mirror['pos'], self._mirror['vel'], self._mirror['heading'], self._mirror['flags'])
+        # the first tracked agent's planner attributes become the tracker's defaults, and where the tracked agents differ every agent's own go
+        # over (classes of equal values on the device).  _trk_*: what a later agent of a slot is held against (SceneBatch.restart)
+        self._trk_on, self._trk_first, self._trk_trip = False, None, None
+        if self.device_tracker and self._ext.any():
+            trip = [_planner_triple(a) for a in flat]
+            first = trip[int(np.argmax(self._ext))]
+            sol.device_tracker_enable(goal6[:, 3:6], turning_radius=first[0], pitchlims=(first[1], first[2]))
+            if any(t != first for t, ext in zip(trip, self._ext) if ext):
+                sol.device_tracker_set_agent_params([t[0] for t in trip], [t[1] for t in trip], [t[2] for t in trip])
+                self._trk_trip = trip
+            self._trk_on, self._trk_first = True, first
+        return sorted(per_agent)
+
+    def _planner_of(self, i):
+        """the planner attributes the device tracker holds for agent i"""
+        return self._trk_first if self._trk_trip is None else self._trk_trip[i]
+
+    def _reset_paths(self):
+        self._paths_on = False          # waypoint lists on the device (Agent.path)
+        self._path_stale = False        # ... and the host mirrors (agents' lists, _path_ng) behind it
+        self._path_assigned = set(range(len(self._flat)))     # agents whose .path was assigned since the last upload
+        self._path_ng = None
+        self._sync_paths()
+        self._nbr_cache = None
+        self._vpref_cache = None
+
+    # ---- host mirrors of the device state, refreshed in place on first use after a step (the reference's per-agent attributes) -------
+    def _state(self, name):
+        if self._stale:
+            st = self.solver.get_state()
+            for k in self._mirror:
+                self._mirror[k][...] = st[k]
+            self._stale = False
+        return self._mirror[name]
+
+    def _vpref_of(self, i):
+        if self._vpref_cache is None:
+            self._vpref_cache = np.nan_to_num(self.solver.diag()['vpref'])
+        return self._vpref_cache[i]
+
+    def _neighbors(self, i, agents, obstacles, lo=0, obs_lo=0):
+        """[(object, distSq)] of agent i of the context; `agents` and `obstacles` start at the context's ids lo and obs_lo"""
+        if self._nbr_cache is None:
+            self._nbr_cache = self.solver.neighbors()
+        nb = self._nbr_cache
+        out = []
+        for k in range(int(nb['nbr_n'][i])):
+            j = int(nb['nbr_id'][i, k])
+            obj = obstacles[j - obs_lo] if nb['nbr_kind'][i, k] else agents[j - lo]
+            out.append((obj, float(nb['nbr_dsq'][i, k])))
+        return out
+
+    # ---- waypoint lists (Agent.path): uploaded when assigned, mirrored lazily -----------------------------------------------
+    def _refresh_paths(self, skip=()):
+        rem, self._path_ng = self.solver.get_path_state()
+        for i, a in enumerate(self._flat):
+            if i not in skip and len(a._path) > rem[i]:
+                del a._path[int(rem[i]):]                         # what list.pop() from the end has left
+        self._path_stale = False
+
+    def _sync_paths(self):
+        """Uploads the agents' lists when one was assigned since the last upload: the others keep their place and every now_goal its value."""
+        if not self._path_assigned:
+            return
+        assigned, self._path_assigned = self._path_assigned, set()
+        lists = [a._path for a in self._flat]
+        n = len(lists)
+        if self._paths_on:
+            self._refresh_paths(skip=assigned)
+            ng = self._path_ng.copy()
+        else:
+            if not any(len(p) for p in lists):
+                return
+            ng = np.full((n, 3), np.nan)
+            served = self._state('step_num') > 0                   # agents that ran get_trajectory already hold now_goal = goal
+            ng[served] = self.goal[served]
+        self.solver.set_paths([[list(map(float, w[:3])) for w in p] for p in lists])
+        self.solver.set_path_state(np.array([len(p) for p in lists], np.int32), ng)
+        self._paths_on = True
+        self._path_ng = ng
+        self._path_stale = False
+
+    def _now_goal_of(self, i):
+        if self._path_stale:
+            self._refresh_paths()
+        g = self._path_ng[i]
+        return None if np.isnan(g[0]) else g.copy()
+
+
+class MACAEnv(_FlatAgents):
     def __init__(self, v_pref_fn=None, device=0, neighbor_mode=S.NBR_KDTREE, history_capacity=0, device_tracker=False):
         self.agents = None
         self.obstacles = []
@@ -301,10 +452,9 @@ class MACAEnv:
         self._time_cum = [0.0]          # [s] = seconds of policy wall time per served agent over the first s env steps
         self._active = 0                # agents the next step will serve
         self._vpref_cache = None
-        self._paths_on = False          # waypoint lists on the device (Agent.path)
-        self._path_stale = False        # ... and the host mirrors (agents' lists, _path_ng) behind it
-        self._path_assigned = set()     # agents whose .path was assigned since the last upload
-        self._path_ng = None
+        self._paths_on = False
+        self._path_stale = False
+        self._path_assigned = set()
 
     def set_agents(self, agents, obstacles=None):
         if obstacles is None:
@@ -314,64 +464,17 @@ class MACAEnv:
                 raise ValueError('agent.id must equal its list index (kdTree.py:64)')
         self.agents = agents
         self.obstacles = obstacles
-        n, m = len(agents), len(obstacles)
-        self._mirror = dict(pos=np.array([a._pos for a in agents], dtype=np.float64).reshape(n, 3),
-                            vel=np.array([a._vel for a in agents], dtype=np.float32).reshape(n, 3),
-                            heading=np.array([a._heading for a in agents], dtype=np.float64).reshape(n, 3),
-                            flags=np.zeros(n, np.uint8), total_dist=np.zeros(n), step_num=np.zeros(n, np.int32))
-        self._stale = False
-        self.goal = np.array([a.goal_global_frame for a in agents], dtype=np.float64).reshape(n, 3)
-        self.policy_ids = np.array([a.policy.policy_id for a in agents], np.uint8)
-        self._ext = np.array([a.policy.needs_external_vpref for a in agents], bool)
-        start = np.array([a.initial_pos for a in agents], dtype=np.float64)
-        goal6 = np.array([a.goal_pos for a in agents], dtype=np.float64)
-        # the solver attributes the reference keeps per Agent (agent.py:24-41) and its policies read per call (scaPolicy.py:95,112,272,302,
-        # util.py:8,17, orca3dPolicyOfficial.py:44,98,108, agent.py:87-99, mampenv.py:90-92): a context holds one value of each
-        # Attributes all agents agree on become the context's sca_params; the ones that differ from agent to agent go to the device as
-        # per-agent arrays (sca_set_agent_params), the context keeping the first agent's value as its default.
-        attr_of = dict(neighbor_dist=('neighborDist', float), max_neighbors=('maxNeighbors', int), time_step=('timeStep', float),
-                       time_horizon=('timeHorizon', float), max_speed=('maxSpeed', float), max_heading_change=('max_heading_change', float),
-                       dt_nominal=('dt_nominal', float))
-        params, per_agent = {}, {}
-        for name, (attr, conv) in attr_of.items():
-            vals = [conv(getattr(a, attr)) for a in agents]
-            params[name] = vals[0]
-            if any(v != vals[0] for v in vals):
-                per_agent[name] = vals
-        self.solver = S.BatchedSolver(max_agents=n, max_obstacles=max(m, 1), device=self.device, params=params)
-        self.solver.set_obstacles(np.array([o.pos_global_frame for o in obstacles], dtype=np.float64).reshape(m, 3),
-                                  np.array([o.radius for o in obstacles], dtype=np.float64))
-        self.solver.set_agents([a.radius for a in agents], [a.pref_speed for a in agents], self.goal, self.policy_ids,
-                               S.zaxis_flags(start, goal6), [a.max_run_dist for a in agents])
-        if per_agent:
-            self.solver.set_agent_params(**per_agent)
-        self.per_agent_attributes = sorted(per_agent)             # which attributes the agents disagree on (empty: one value per context)
-        self.solver.set_state(self.pos, self.vel, self.heading, self.flags)
-        if self.device_tracker and self._ext.any():
-            # the planner's attributes (agent.turning_radius, agent.pitchlims: scaPolicy.py:95,272,302): the first tracked agent's become the
-            # tracker's defaults, and where the tracked agents differ every agent's own go over (classes of equal values on the device)
-            tracked = [a for a in agents if a.policy.needs_external_vpref]
-            trip = [(float(a.turning_radius), float(a.pitchlims[0]), float(a.pitchlims[1])) for a in agents]
-            first = (float(tracked[0].turning_radius), float(tracked[0].pitchlims[0]), float(tracked[0].pitchlims[1]))
-            self.solver.device_tracker_enable(goal6[:, 3:6], turning_radius=first[0], pitchlims=(first[1], first[2]))
-            if any((float(a.turning_radius), float(a.pitchlims[0]), float(a.pitchlims[1])) != first for a in tracked):
-                self.solver.device_tracker_set_agent_params([t[0] for t in trip], [t[1] for t in trip], [t[2] for t in trip])
-                self.per_agent_attributes = sorted(self.per_agent_attributes + ['turning_radius / pitchlims'])
-        for a in agents:
-            a._env = self
-            a._row_pos = a._row_vel = a._row_heading = None        # (row views belong to the mirrors of the env they were made for)
-            a.policy._env = self
-            a.policy._agent_id = a.id
-        self._paths_on = False
-        self._path_stale = False
-        self._path_assigned = set(range(n))
-        self._sync_paths()
+        n = len(agents)
+        # which attributes the agents disagree on (empty: one value per context)
+        self.per_agent_attributes = self._create(agents, self.device, len(obstacles), obstacles)
+        if self._trk_trip is not None:
+            self.per_agent_attributes = sorted(self.per_agent_attributes + ['turning_radius / pitchlims'])
+        _bind(agents, self)
+        self._reset_paths()
         self.kdTree = _KdTreeView(self)
         self._row_cache = None
-        self._nbr_cache = None
         self._time_cum = [0.0]
         self._active = n
-        self._vpref_cache = None
         # the log costs 64 B x rows x agents of HBM up front: cap it to a budget instead of failing in hipMalloc
         if self.history_capacity and 64 * self.history_capacity * n > self.history_budget_bytes:
             capped = max(1, self.history_budget_bytes // (64 * n))
@@ -382,57 +485,12 @@ class MACAEnv:
         if self.history_capacity:
             self.solver.history_enable(self.history_capacity)
 
-    # ---- host mirrors of the device state, refreshed on first use after a step (the reference's per-agent attributes) -------
-    def _state(self, name):
-        if self._stale:
-            st = self.solver.get_state()
-            for k in self._mirror:
-                self._mirror[k][...] = st[k]
-            self._stale = False
-        return self._mirror[name]
-
     pos = property(lambda self: self._state('pos'))
     vel = property(lambda self: self._state('vel'))
     heading = property(lambda self: self._state('heading'))
     flags = property(lambda self: self._state('flags'))
     total_dist = property(lambda self: self._state('total_dist'))
     step_num = property(lambda self: self._state('step_num'))
-
-    # ---- waypoint lists (Agent.path): uploaded when assigned, mirrored lazily -----------------------------------------------
-    def _refresh_paths(self, skip=()):
-        rem, self._path_ng = self.solver.get_path_state()
-        for i, a in enumerate(self.agents):
-            if i not in skip and len(a._path) > rem[i]:
-                del a._path[int(rem[i]):]                         # what list.pop() from the end has left
-        self._path_stale = False
-
-    def _sync_paths(self):
-        """Uploads the agents' lists when one was assigned since the last upload: the others keep their place and every now_goal its value."""
-        if not self._path_assigned:
-            return
-        assigned, self._path_assigned = self._path_assigned, set()
-        lists = [a._path for a in self.agents]
-        n = len(lists)
-        if self._paths_on:
-            self._refresh_paths(skip=assigned)
-            ng = self._path_ng.copy()
-        else:
-            if not any(len(p) for p in lists):
-                return
-            ng = np.full((n, 3), np.nan)
-            served = self.step_num > 0                             # agents that ran get_trajectory already hold now_goal = goal
-            ng[served] = self.goal[served]
-        self.solver.set_paths([[list(map(float, w[:3])) for w in p] for p in lists])
-        self.solver.set_path_state(np.array([len(p) for p in lists], np.int32), ng)
-        self._paths_on = True
-        self._path_ng = ng
-        self._path_stale = False
-
-    def _now_goal_of(self, i):
-        if self._path_stale:
-            self._refresh_paths()
-        g = self._path_ng[i]
-        return None if np.isnan(g[0]) else g.copy()
 
     # ---- one step = MACAEnv.step (mampenv.py:22-25) ---------------------------------------------------------------------
     def _policy_pass(self):
@@ -461,21 +519,8 @@ class MACAEnv:
     def _policy_row(self, i):
         return list(self._policy_pass()[i])
 
-    def _vpref_of(self, i):
-        if self._vpref_cache is None:
-            self._vpref_cache = np.nan_to_num(self.solver.diag()['vpref'])
-        return self._vpref_cache[i]
-
     def _neighbors_of(self, i):
-        if self._nbr_cache is None:
-            self._nbr_cache = self.solver.neighbors()
-        nb = self._nbr_cache
-        out = []
-        for k in range(int(nb['nbr_n'][i])):
-            j = int(nb['nbr_id'][i, k])
-            obj = self.obstacles[j] if nb['nbr_kind'][i, k] else self.agents[j]
-            out.append((obj, float(nb['nbr_dsq'][i, k])))
-        return out
+        return self._neighbors(i, self.agents, self.obstacles)
 
     def step(self, actions=None):
         """`actions` is ignored, as in the reference (mampenv.py:22).  Without a host-side v_pref_fn the whole step (both loops

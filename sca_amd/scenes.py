@@ -25,10 +25,7 @@ import numpy as np
 
 from . import metrics
 from . import solver as S
-
-_ATTRS = dict(neighbor_dist=('neighborDist', float), max_neighbors=('maxNeighbors', int), time_step=('timeStep', float),
-              time_horizon=('timeHorizon', float), max_speed=('maxSpeed', float), max_heading_change=('max_heading_change', float),
-              dt_nominal=('dt_nominal', float))
+from .env import _ATTRS, _FlatAgents, _bind, _obstacle_arrays, _planner_triple
 
 
 class _SceneKdTree:
@@ -98,18 +95,10 @@ class SceneEnv:
         raise RuntimeError('a SceneBatch serves every agent of every scene in batch.step(): there is no single-agent find_next_action')
 
     def _neighbors_of(self, i):
-        b = self._batch
-        if b._nbr_cache is None:
-            b._nbr_cache = b.solver.neighbors()
-        nb, g = b._nbr_cache, self._lo + i
-        out = []
-        for k in range(int(nb['nbr_n'][g])):
-            j = int(nb['nbr_id'][g, k])
-            out.append((self.obstacles[j - self._obs_lo] if nb['nbr_kind'][g, k] else self.agents[j - self._lo], float(nb['nbr_dsq'][g, k])))
-        return out
+        return self._batch._neighbors(self._lo + i, self.agents, self.obstacles, self._lo, self._obs_lo)
 
 
-class SceneBatch:
+class SceneBatch(_FlatAgents):
     def __init__(self, scenes, obstacles=(), scene_obstacles=None, neighbor_mode=S.NBR_KDTREE, device_tracker=False, history_capacity=0, device=0):
         scenes = [list(a) for a in scenes]
         if not scenes or any(len(a) == 0 for a in scenes):
@@ -130,67 +119,23 @@ class SceneBatch:
         self.device_tracker = bool(device_tracker)
         self.offsets = np.concatenate([[0], np.cumsum([len(a) for a in scenes])]).astype(np.int32)
         flat = [a for agents in scenes for a in agents]
-        n, m, B = len(flat), len(self.obstacles) if self.scene_obstacles is None else int(self.obstacle_offsets[-1]), len(scenes)
-        self._mirror = dict(pos=np.array([a._pos for a in flat], dtype=np.float64).reshape(n, 3),
-                            vel=np.array([a._vel for a in flat], dtype=np.float32).reshape(n, 3),
-                            heading=np.array([a._heading for a in flat], dtype=np.float64).reshape(n, 3),
-                            flags=np.zeros(n, np.uint8), total_dist=np.zeros(n), step_num=np.zeros(n, np.int32))
-        self._stale = False
-        self.goal = np.array([a.goal_global_frame for a in flat], dtype=np.float64).reshape(n, 3)
-        self.policy_ids = np.array([a.policy.policy_id for a in flat], np.uint8)
-        self._ext = np.array([a.policy.needs_external_vpref for a in flat], bool)
-        start = np.array([a.initial_pos for a in flat], dtype=np.float64)
-        goal6 = np.array([a.goal_pos for a in flat], dtype=np.float64)
-        # the solver attributes of agent.py:24-41, as MACAEnv.set_agents hands them over: one value per context where all agents of all
-        # scenes agree, per agent where they differ
-        params, per_agent = {}, {}
-        for name, (attr, conv) in _ATTRS.items():
-            vals = [conv(getattr(a, attr)) for a in flat]
-            params[name] = vals[0]
-            if any(v != vals[0] for v in vals):
-                per_agent[name] = vals
-        sol = self.solver = S.BatchedSolver(max_agents=n, max_obstacles=max(m, 1), device=device, params=params)
-        if self.scene_obstacles is None:
-            sol.set_obstacles(np.array([o.pos_global_frame for o in self.obstacles], dtype=np.float64).reshape(m, 3),
-                              np.array([o.radius for o in self.obstacles], dtype=np.float64))
-        sol.set_agents([a.radius for a in flat], [a.pref_speed for a in flat], self.goal, self.policy_ids, S.zaxis_flags(start, goal6),
-                       [a.max_run_dist for a in flat])
-        if per_agent:
-            sol.set_agent_params(**per_agent)
-        sol.set_scenes(self.offsets)
-        if self.scene_obstacles is not None:
-            sol.set_scene_obstacles([(np.array([o.pos_global_frame for o in obs], dtype=np.float64).reshape(len(obs), 3),
-                                      np.array([o.radius for o in obs], dtype=np.float64)) for obs in self.scene_obstacles])
-        sol.set_state(self._mirror['pos'], self._mirror['vel'], self._mirror['heading'], self._mirror['flags'])
-        self._trk_on, self._trk_first, self._trk_trip = False, None, None     # what restart() holds a new agent's planner attributes against
-        if self.device_tracker and self._ext.any():
-            tracked = [a for a in flat if a.policy.needs_external_vpref]
-            trip = [(float(a.turning_radius), float(a.pitchlims[0]), float(a.pitchlims[1])) for a in flat]
-            first = (float(tracked[0].turning_radius), float(tracked[0].pitchlims[0]), float(tracked[0].pitchlims[1]))
-            sol.device_tracker_enable(goal6[:, 3:6], turning_radius=first[0], pitchlims=(first[1], first[2]))
-            if any((float(a.turning_radius), float(a.pitchlims[0]), float(a.pitchlims[1])) != first for a in tracked):
-                sol.device_tracker_set_agent_params([t[0] for t in trip], [t[1] for t in trip], [t[2] for t in trip])
-                self._trk_trip = trip
-            self._trk_on, self._trk_first = True, first
-        self._flat = flat
+        B = len(scenes)
+
+        def set_scenes():                                             # between the agents' attributes and the state
+            self.solver.set_scenes(self.offsets)
+            if self.scene_obstacles is not None:
+                self.solver.set_scene_obstacles([_obstacle_arrays(obs) for obs in self.scene_obstacles])
+
+        shared = self.scene_obstacles is None
+        self._create(flat, device, len(self.obstacles) if shared else int(self.obstacle_offsets[-1]), self.obstacles if shared else None, set_scenes)
         self._envs = [SceneEnv(self, s, scenes[s], int(self.offsets[s]), int(self.offsets[s + 1])) for s in range(B)]
         for view in self._envs:
-            for a in view.agents:
-                a._env = view
-                a._row_pos = a._row_vel = a._row_heading = None
-                a.policy._env = view
-                a.policy._agent_id = a.id
-        self._paths_on = False
-        self._path_stale = False
-        self._path_ng = None
-        self._path_assigned = set(range(n))
-        self._sync_paths()
-        self._nbr_cache = None
-        self._vpref_cache = None
+            _bind(view.agents, view)
+        self._reset_paths()
         self.active = np.diff(self.offsets).astype(np.int32)          # agents of each scene the next step will serve
         self.steps = np.zeros(B, np.int32)                            # steps each scene has taken while it was live
         if history_capacity:
-            sol.history_enable(int(history_capacity))
+            self.solver.history_enable(int(history_capacity))
 
     def __len__(self):
         return len(self._envs)
@@ -204,55 +149,6 @@ class SceneBatch:
 
     def close(self):
         self.solver.close()
-
-    # ---- host mirrors, refreshed in place on first use after a step ------------------------------------------------------------------
-    def _state(self, name):
-        if self._stale:
-            st = self.solver.get_state()
-            for k in self._mirror:
-                self._mirror[k][...] = st[k]
-            self._stale = False
-        return self._mirror[name]
-
-    def _vpref_of(self, g):
-        if self._vpref_cache is None:
-            self._vpref_cache = np.nan_to_num(self.solver.diag()['vpref'])
-        return self._vpref_cache[g]
-
-    # ---- waypoint lists (Agent.path), as in MACAEnv -----------------------------------------------------------------------------------
-    def _refresh_paths(self, skip=()):
-        rem, self._path_ng = self.solver.get_path_state()
-        for g, a in enumerate(self._flat):
-            if g not in skip and len(a._path) > rem[g]:
-                del a._path[int(rem[g]):]
-        self._path_stale = False
-
-    def _sync_paths(self):
-        if not self._path_assigned:
-            return
-        assigned, self._path_assigned = self._path_assigned, set()
-        lists = [a._path for a in self._flat]
-        n = len(lists)
-        if self._paths_on:
-            self._refresh_paths(skip=assigned)
-            ng = self._path_ng.copy()
-        else:
-            if not any(len(p) for p in lists):
-                return
-            ng = np.full((n, 3), np.nan)
-            served = self._state('step_num') > 0
-            ng[served] = self.goal[served]
-        self.solver.set_paths([[list(map(float, w[:3])) for w in p] for p in lists])
-        self.solver.set_path_state(np.array([len(p) for p in lists], np.int32), ng)
-        self._paths_on = True
-        self._path_ng = ng
-        self._path_stale = False
-
-    def _now_goal_of(self, g):
-        if self._path_stale:
-            self._refresh_paths()
-        v = self._path_ng[g]
-        return None if np.isnan(v[0]) else v.copy()
 
     # ---- a new episode into a slot while the others keep running (sca_restart_scenes) -------------------------------------------------------
     def restart(self, scenes):
@@ -285,8 +181,7 @@ class SceneBatch:
                 if a.policy.needs_external_vpref and self.device_tracker:
                     if not self._trk_on:
                         raise ValueError(f'restart: scene {s}, agent {i} needs the device tracker, which a batch built without such agents has not enabled')
-                    trip = (float(a.turning_radius), float(a.pitchlims[0]), float(a.pitchlims[1]))
-                    if trip != (self._trk_first if self._trk_trip is None else self._trk_trip[lo + i]):
+                    if _planner_triple(a) != self._planner_of(lo + i):
                         raise ValueError(f"restart: scene {s}, agent {i}: turning_radius / pitchlims differ from the slot's (a slot keeps its planner attributes)")
         flat = [a for _, agents in items for a in agents]
         T = len(flat)
@@ -309,11 +204,7 @@ class SceneBatch:
             self.policy_ids[lo:hi] = policy[at:at + hi - lo]
             self._ext[lo:hi] = [a.policy.needs_external_vpref for a in agents]
             view._time_cum = [0.0]
-            for a in agents:
-                a._env = view
-                a._row_pos = a._row_vel = a._row_heading = None
-                a.policy._env = view
-                a.policy._agent_id = a.id
+            _bind(agents, view)
             at += hi - lo
         self._stale = True                                           # the mirrors (views of the batch's arrays) refresh in place on first use
         self._nbr_cache = None

@@ -1,6 +1,7 @@
-"""Helpers of tests/test_gpu_scene_restart.py and tests/test_gpu_scene_stream.py: recorded episodes as the slots of one context, where a slot
-may be given another recorded episode while the batch runs (sca_restart_scenes).  Every slot is held against the reference's records of the
-episode it holds AT THAT MOMENT, counted from the step the episode was put in."""
+"""Helpers of the scene tests (tests/test_gpu_scene*.py).  load_any, everything and assert_scene_equals_alone serve all of them; Slots is
+test_gpu_scene_restart.py's: recorded episodes as the slots of one context, where a slot may be given another recorded episode while the
+batch runs (sca_restart_scenes).  Every slot is held against the reference's records of the episode it holds AT THAT MOMENT, counted from
+the step the episode was put in."""
 import os
 
 import numpy as np

@@ -5,13 +5,11 @@ import ctypes as C
 import itertools
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, 'tests', '_build')
-CSRC = os.path.join(ROOT, 'sca_amd', 'csrc')
+from harness_util import CSRC, ROOT, load_harness
+
 INT_MAX = 2 ** 31 - 1
 SPLIT, TRACK_FUSED, LANE, FEW, LP_LANE, SOLVE_FB, ACTION_FB = 1, 2, 4, 8, 16, 32, 64          # include/sca_hip.h
 G64, G32, G16, G4, RP_LANE, TRACK_GROUP, TRACK_REPLAN = range(7)                               # ReplanKernel
@@ -25,14 +23,7 @@ REMOVED = ('SCA_TRACKER_SERIAL', 'SCA_TRACKER_NOQUAD', 'SCA_KD_NOHINT', 'SCA_KD_
 
 @pytest.fixture(scope='module')
 def H():
-    out = os.path.join(BUILD, 'libforms_harness.so')
-    src = os.path.join(ROOT, 'tests', 'forms_harness.cpp')
-    deps = [src, os.path.join(ROOT, 'include', 'sca_hip.h'), os.path.join(CSRC, 'sca_forms.h'), os.path.join(CSRC, 'sca_constants.h')]
-    os.makedirs(BUILD, exist_ok=True)
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(f) for f in deps):
-        # (no ROCm include path: the header must be plain C++)
-        subprocess.check_call(['g++', '-std=c++17', '-O1', '-Wall', '-Wextra', '-Werror', '-fPIC', '-shared', '-I' + CSRC, '-o', out, src])
-    h = C.CDLL(out)
+    h = load_harness('forms_harness', ('sca_forms.h',))
     h.forms_tunable_name.restype = C.c_char_p
     h.forms_plan_solve.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     return h

@@ -11,6 +11,7 @@ import pytest
 import test_gpu_parity as TP
 import test_gpu_scenes as TS
 from golden_util import fixture_agent_params, fixture_params, fixture_tracker_agent_params, static_inputs
+from scene_util import assert_scene_equals_alone, everything
 
 pytestmark = pytest.mark.gpu
 
@@ -196,29 +197,6 @@ def _context(S, scenes, obstacles, mode='scene', max_obstacles=None, tracker=Tru
     return sol, off
 
 
-def _everything(sol):
-    out = dict(sol.get_state())
-    out['action'] = sol.actions()
-    out['perm'] = sol.get_kd_perm()
-    nb = sol.neighbors()
-    out.update({k: nb[k] for k in ('nbr_n', 'nbr_id', 'nbr_kind', 'nbr_dsq', 'nbr_valid')})
-    d = sol.diag()
-    out.update(diag=d['diag'], status=d['status'], vpref=d['vpref'])
-    return out
-
-
-def _assert_scene_equals_alone(got, lo, hi, obs_lo, alone, ctx):
-    """agents [lo, hi) of a batch against a context that holds them alone: ids are global in the batch (agents + lo, obstacles + obs_lo)"""
-    for key, want in alone.items():
-        have = got[key][lo:hi]
-        if key == 'perm':
-            have = have - lo
-        elif key == 'nbr_id':
-            kind = got['nbr_kind'][lo:hi]
-            have = have - np.where(have >= 0, np.where(kind == 1, obs_lo, lo), 0)
-        assert np.array_equal(have, want, equal_nan=key == 'vpref'), ctx + (key,)
-
-
 def test_obstacles_do_not_leak_between_scenes(S):
     """three scenes with identical agents: obstacles on the straight lines to the goals, none, a different set -- each equals a context
     holding it alone over 40 steps, and the first two differ from each other"""
@@ -241,9 +219,9 @@ def test_obstacles_do_not_leak_between_scenes(S):
         for x in [sol] + alone:
             x.run_steps(1, S.NBR_KDTREE)
             x.synchronize()
-        got = _everything(sol)
+        got = everything(sol)
         for s in range(3):
-            _assert_scene_equals_alone(got, int(off[s]), int(off[s + 1]), obs_off[s], _everything(alone[s]), ('leak', 'step', t, 'scene', s))
+            assert_scene_equals_alone(got, int(off[s]), int(off[s + 1]), obs_off[s], everything(alone[s]), ('leak', 'step', t, 'scene', s))
         differ = differ or not np.array_equal(got['pos'][0:12], got['pos'][12:24])
     assert differ, 'the scene with obstacles on the lines to the goals moved exactly like the one without any'
     assert sol.pass_forms() & S.FORM_SCENE_OBSTACLES
@@ -444,7 +422,7 @@ def _lifetime_scenes(S):
 def _run(S, sol, steps=8):
     sol.run_steps(steps, S.NBR_KDTREE)
     sol.synchronize()
-    return _everything(sol)
+    return everything(sol)
 
 
 def _same(a, b, ctx):

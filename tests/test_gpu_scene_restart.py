@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from scene_restart_util import Slots, assert_scene_equals_alone, everything, load_any
+from scene_util import Slots, assert_scene_equals_alone, everything, load_any
 
 pytestmark = pytest.mark.gpu
 

@@ -4,12 +4,12 @@ is bit for bit what a context holding that scene alone produces, i.e. the refere
 only: free-running from the scenario's start state, nothing fed from the fixtures, every scene compared after every step it has a record
 of.  No tolerance anywhere."""
 import math
-import os
 
 import numpy as np
 import pytest
 
-from golden_util import GOLDEN, fixture_agent_params, fixture_params, fixture_tracker_agent_params, static_inputs
+from golden_util import fixture_agent_params, fixture_params, fixture_tracker_agent_params, static_inputs
+from scene_util import load_any
 
 pytestmark = pytest.mark.gpu
 
@@ -26,10 +26,6 @@ TRK_DEFAULTS = dict(turning_radius=1.5, pitch_lo=-math.pi / 4, pitch_hi=math.pi 
 def S():
     import sca_amd.solver as S
     return S
-
-
-def load_any(name):
-    return dict(np.load(os.path.join(GOLDEN, name + '.npz'), allow_pickle=False))
 
 
 class Batch:

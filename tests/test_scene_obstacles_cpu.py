@@ -1,31 +1,22 @@
 """The host-side rules of per-scene obstacle sets (sca_set_scene_obstacles) without a GPU: the offsets check and its error codes, the
-per-scene obstacle root, and the shift of a single-scene tree into the forest (sca_scenes.h), behind tests/scene_obstacles_harness.cpp.
+per-scene obstacle root, and the shift of a single-scene tree into the forest (sca_scenes.h), behind tests/scenes_harness.cpp.
 As in tests/test_scenes_cpu.py every expectation is a literal worked out by hand from the documented rules -- none comes from the code
 under test."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, 'tests', '_build')
-CSRC = os.path.join(ROOT, 'sca_amd', 'csrc')
+from harness_util import ROOT, load_harness
+
 OK, BAD_COUNT, NO_OFFSETS, BAD_START, DECREASING, TOO_MANY, NO_ARRAYS = range(7)               # SceneObsFault
 ERR_ARG = -1                                                                                  # include/sca_hip.h
 
 
 @pytest.fixture(scope='module')
 def H():
-    out = os.path.join(BUILD, 'libscene_obstacles_harness.so')
-    src = os.path.join(ROOT, 'tests', 'scene_obstacles_harness.cpp')
-    deps = [src, os.path.join(ROOT, 'include', 'sca_hip.h')] + [os.path.join(CSRC, f) for f in ('sca_scenes.h', 'sca_constants.h')]
-    os.makedirs(BUILD, exist_ok=True)
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(f) for f in deps):
-        # (no ROCm include path: the header must be plain C++)
-        subprocess.check_call(['g++', '-std=c++17', '-O1', '-Wall', '-Wextra', '-Werror', '-fPIC', '-shared', '-I' + CSRC, '-o', out, src])
-    return C.CDLL(out)
+    return load_harness('scenes_harness', ('sca_forms.h', 'sca_scenes.h'))
 
 
 def i32(a):

@@ -1,16 +1,13 @@
 """The host-side rules of sca_restart_scenes without a GPU: scene_restart_check (every fault with the entry it names, T for a valid list) and
-the staging block's layout (sca_scenes.h), behind tests/scene_restart_harness.cpp.  Every expectation is a literal worked out by hand from
+the staging block's layout (sca_scenes.h), behind tests/scenes_harness.cpp.  Every expectation is a literal worked out by hand from
 the rules in include/sca_hip.h -- none comes from the code under test."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, 'tests', '_build')
-CSRC = os.path.join(ROOT, 'sca_amd', 'csrc')
+from harness_util import load_harness
+
 (OK, NO_SCENES, NO_STATE, MID_STEP, BAD_COUNT, BAD_ID, REPEATED_ID, NO_ARRAYS, NOT_FINITE, BAD_POLICY, NOT_POSITIVE, GOAL_HEADING, PATHS,
  TRACKED_CHANGE) = range(14)                                        # RestartFault
 ERR_ARG, ERR_STATE, ERR_UNSUPPORTED = -1, -3, -5                   # include/sca_hip.h
@@ -21,14 +18,7 @@ POLICY_NOW = [0, 1, 2, 3, 4, 5, 0, 1, 2, 3]
 
 @pytest.fixture(scope='module')
 def H():
-    out = os.path.join(BUILD, 'libscene_restart_harness.so')
-    src = os.path.join(ROOT, 'tests', 'scene_restart_harness.cpp')
-    deps = [src, os.path.join(ROOT, 'include', 'sca_hip.h')] + [os.path.join(CSRC, f) for f in ('sca_scenes.h', 'sca_constants.h')]
-    os.makedirs(BUILD, exist_ok=True)
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(f) for f in deps):
-        # (no ROCm include path: the header must be plain C++)
-        subprocess.check_call(['g++', '-std=c++17', '-O1', '-Wall', '-Wextra', '-Werror', '-fPIC', '-shared', '-I' + CSRC, '-o', out, src])
-    return C.CDLL(out)
+    return load_harness('scenes_harness', ('sca_forms.h', 'sca_scenes.h'))
 
 
 def episode(T):

@@ -2,15 +2,12 @@
 permutation checks and the neighbour-mode mapping (sca_scenes.h), behind tests/scenes_harness.cpp.  As in tests/test_forms_cpu.py every
 expectation is a literal worked out by hand from the documented rules -- none comes from the code under test."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, 'tests', '_build')
-CSRC = os.path.join(ROOT, 'sca_amd', 'csrc')
+from harness_util import load_harness
+
 OK, NONE, BAD_COUNT, BAD_START, NOT_INCREASING, BAD_END, TOO_LARGE = range(7)                 # SceneFault
 ERR_ARG, ERR_UNSUPPORTED = -1, -5                                                             # include/sca_hip.h
 NBR_KDTREE, NBR_GRID, NBR_HOSTBUILD, NBR_AUTO = 0, 1, 2, 3
@@ -18,14 +15,7 @@ NBR_KDTREE, NBR_GRID, NBR_HOSTBUILD, NBR_AUTO = 0, 1, 2, 3
 
 @pytest.fixture(scope='module')
 def H():
-    out = os.path.join(BUILD, 'libscenes_harness.so')
-    src = os.path.join(ROOT, 'tests', 'scenes_harness.cpp')
-    deps = [src, os.path.join(ROOT, 'include', 'sca_hip.h')] + [os.path.join(CSRC, f) for f in ('sca_forms.h', 'sca_scenes.h', 'sca_constants.h')]
-    os.makedirs(BUILD, exist_ok=True)
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(f) for f in deps):
-        # (no ROCm include path: the headers must be plain C++)
-        subprocess.check_call(['g++', '-std=c++17', '-O1', '-Wall', '-Wextra', '-Werror', '-fPIC', '-shared', '-I' + CSRC, '-o', out, src])
-    return C.CDLL(out)
+    return load_harness('scenes_harness', ('sca_forms.h', 'sca_scenes.h'))
 
 
 def i32(a):

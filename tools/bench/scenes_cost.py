@@ -12,6 +12,9 @@ legs
     one_by_one        the same scenes through B contexts of one scene each, by the library of --root (the parent commit's checkout, loaded
                       beside this one): per step the wall time of all B sca_env_step calls.  Left out without --root.
     one_by_one_here   the same with this checkout's library: should equal one_by_one within the spread -- if not, something existing moved
+    batch_root        the same batch through the library of --root: what a change to the scene path itself is held against -- `batch` must not
+                      be above it by more than the two legs' spreads together (entry `batch_path`).  Left out without --root.
+                      --batch-only leaves the one_by_one legs out (B contexts cost minutes at B = 1024).
 Per leg: the median step time of each of the `--alternations` windows, their min-max (the spread); per workload: agent-steps/s of the batch and
 the ratio one_by_one / batch with the condition "beats it by more than the two spreads together".
 
@@ -23,6 +26,7 @@ with the device tracker), legs
     shared_set        the same batch with ONE shared set of the 8 spheres, by the library of --root: the same values (the copies coincide), the same
                       launch count.  Left out without --root.
     shared_set_here   the same with this checkout's library: should equal shared_set within the spread
+    batch_root        scene_sets through the library of --root, as above.  Left out without --root.
 and the difference scene_sets - shared_set is the feature's cost (expected: two dependent loads per agent)."""
 import argparse
 import importlib
@@ -140,6 +144,14 @@ def time_legs(legs, args, mode):
     return rows
 
 
+def batch_path(rows):
+    """the scene path of this checkout against the same batch through --root's library: not slower beyond the two spreads together"""
+    a, b = rows['batch' if 'batch' in rows else 'scene_sets'], rows['batch_root']
+    margin = (a['spread_ms'][1] - a['spread_ms'][0]) + (b['spread_ms'][1] - b['spread_ms'][0])
+    return {'here_minus_root_ms': a['ms_per_step'] - b['ms_per_step'], 'here_over_root': a['ms_per_step'] / b['ms_per_step'], 'sum_of_spreads_ms': margin,
+            'not_above_root_by_more_than_the_spreads': bool(a['ms_per_step'] - b['ms_per_step'] <= margin)}
+
+
 def obstacle_workloads(args, S, scenarios, Sp, scp):
     out = args.out if args.out_given else os.path.join(REPO, 'profiles', 'scene_obstacles_cost.json')
     for B in [int(x) for x in args.scenes.split(',') if x]:
@@ -147,6 +159,8 @@ def obstacle_workloads(args, S, scenarios, Sp, scp):
         sol, reset, n1 = make_obstacle_context(S, scenarios, B, True)
         legs['scene_sets'] = ([sol], [reset])
         if Sp is not None:
+            sol, reset, _ = make_obstacle_context(Sp, scp, B, True)
+            legs['batch_root'] = ([sol], [reset])
             sol, reset, _ = make_obstacle_context(Sp, scp, B, False)
             legs['shared_set'] = ([sol], [reset])
         sol, reset, _ = make_obstacle_context(S, scenarios, B, False)
@@ -166,6 +180,8 @@ def obstacle_workloads(args, S, scenarios, Sp, scp):
                  'cost': {'against': ref, 'scene_sets_minus_shared_set_ms': a['ms_per_step'] - b['ms_per_step'],
                           'ratio_scene_sets_over_shared_set': a['ms_per_step'] / b['ms_per_step'], 'sum_of_spreads_ms': margin,
                           'within_the_spreads': bool(abs(a['ms_per_step'] - b['ms_per_step']) <= margin)}}
+        if 'batch_root' in rows:
+            entry['batch_path'] = batch_path(rows)
         try:
             with open(out) as f:
                 doc = json.load(f)
@@ -181,7 +197,7 @@ def obstacle_workloads(args, S, scenarios, Sp, scp):
         for leg, r in rows.items():
             print('takeoff B=%-5d %-16s %9.4f ms/step  spread %.4f .. %.4f  active at end %s' % (B, leg, r['ms_per_step'], r['spread_ms'][0], r['spread_ms'][1],
                                                                                              r['active_at_end'][-1]), flush=True)
-        print('takeoff', B, json.dumps(entry['cost']), flush=True)
+        print('takeoff', B, json.dumps(entry['cost']), json.dumps(entry.get('batch_path')), flush=True)
         for sols, _ in legs.values():
             for sol in sols:
                 sol.close()
@@ -196,6 +212,7 @@ def main():
     ap.add_argument('--alternations', type=int, default=5)
     ap.add_argument('--root', default=None, help="the parent commit's checkout (built): the one_by_one leg runs its library")
     ap.add_argument('--out', default=None, help='default: profiles/scenes_cost.json (profiles/scene_obstacles_cost.json with --obstacles)')
+    ap.add_argument('--batch-only', action='store_true', help='without the one_by_one legs: the batch against batch_root alone (needs --root)')
     ap.add_argument('--obstacles', action='store_true', help='the per-scene obstacle sets against one shared set, instead of the batch against B contexts')
     args = ap.parse_args()
     args.out_given = args.out is not None
@@ -205,6 +222,7 @@ def main():
     sys.path.insert(0, REPO)
     from sca_amd import scenarios, solver as S
     Sp = scp = None
+    assert args.root or not args.batch_only, '--batch-only compares with the library of --root'
     if args.root:
         assert os.path.abspath(args.root) != REPO
         Sp, scp = load_package(args.root, 'sca_amd_parent')
@@ -220,28 +238,35 @@ def main():
             batch, batch_reset = make_context(S, scenarios, sc, B, policy, True)
             legs['batch'] = ([batch], [batch_reset])
             if Sp is not None:
+                sol, reset = make_context(Sp, scp, sc, B, policy, True)
+                legs['batch_root'] = ([sol], [reset])
+            if Sp is not None and not args.batch_only:
                 made = [make_context(Sp, scp, sc, 1, policy, False) for _ in range(B)]
                 legs['one_by_one'] = ([m[0] for m in made], [m[1] for m in made])
-            made = [make_context(S, scenarios, sc, 1, policy, False) for _ in range(B)]
-            legs['one_by_one_here'] = ([m[0] for m in made], [m[1] for m in made])
+            if not args.batch_only:
+                made = [make_context(S, scenarios, sc, 1, policy, False) for _ in range(B)]
+                legs['one_by_one_here'] = ([m[0] for m in made], [m[1] for m in made])
 
             rows = time_legs(legs, args, KD)
             n = B * SCENE_AGENTS
             entry = {'workload': '%d x circle of %d, %s' % (B, SCENE_AGENTS, 'SCA + device tracker' if policy == 'sca' else 'ORCA3D'),
                      'scenes': B, 'agents': n, 'warm_steps': args.warm, 'window_steps': args.window, 'alternations': args.alternations, 'legs': rows,
                      'batch_agent_steps_per_s': n / (rows['batch']['ms_per_step'] * 1e-3)}
-            ref = 'one_by_one' if 'one_by_one' in rows else 'one_by_one_here'
-            a, b = rows[ref], rows['batch']
-            margin = (a['spread_ms'][1] - a['spread_ms'][0]) + (b['spread_ms'][1] - b['spread_ms'][0])
-            entry['verdict'] = {'against': ref, 'ratio_one_by_one_over_batch': a['ms_per_step'] / b['ms_per_step'],
-                                'one_by_one_minus_batch_ms': a['ms_per_step'] - b['ms_per_step'], 'sum_of_spreads_ms': margin,
-                                'batch_faster_by_more_than_the_spreads': bool(a['ms_per_step'] - b['ms_per_step'] > margin),
-                                'batch_within_the_spreads': bool(abs(a['ms_per_step'] - b['ms_per_step']) <= margin)}
-            if 'one_by_one' in rows:
-                h = rows['one_by_one_here']
-                m2 = (a['spread_ms'][1] - a['spread_ms'][0]) + (h['spread_ms'][1] - h['spread_ms'][0])
-                entry['existing_path'] = {'here_minus_parent_ms': h['ms_per_step'] - a['ms_per_step'], 'sum_of_spreads_ms': m2,
-                                          'within_the_spreads': bool(abs(h['ms_per_step'] - a['ms_per_step']) <= m2)}
+            if 'batch_root' in rows:
+                entry['batch_path'] = batch_path(rows)
+            if not args.batch_only:
+                ref = 'one_by_one' if 'one_by_one' in rows else 'one_by_one_here'
+                a, b = rows[ref], rows['batch']
+                margin = (a['spread_ms'][1] - a['spread_ms'][0]) + (b['spread_ms'][1] - b['spread_ms'][0])
+                entry['verdict'] = {'against': ref, 'ratio_one_by_one_over_batch': a['ms_per_step'] / b['ms_per_step'],
+                                    'one_by_one_minus_batch_ms': a['ms_per_step'] - b['ms_per_step'], 'sum_of_spreads_ms': margin,
+                                    'batch_faster_by_more_than_the_spreads': bool(a['ms_per_step'] - b['ms_per_step'] > margin),
+                                    'batch_within_the_spreads': bool(abs(a['ms_per_step'] - b['ms_per_step']) <= margin)}
+                if 'one_by_one' in rows:
+                    h = rows['one_by_one_here']
+                    m2 = (a['spread_ms'][1] - a['spread_ms'][0]) + (h['spread_ms'][1] - h['spread_ms'][0])
+                    entry['existing_path'] = {'here_minus_parent_ms': h['ms_per_step'] - a['ms_per_step'], 'sum_of_spreads_ms': m2,
+                                              'within_the_spreads': bool(abs(h['ms_per_step'] - a['ms_per_step']) <= m2)}
             try:
                 with open(args.out) as f:
                     doc = json.load(f)
@@ -255,7 +280,8 @@ def main():
             for leg, r in rows.items():
                 print('%-5s B=%-5d %-16s %9.4f ms/step  spread %.4f .. %.4f  active at end %s' % (policy, B, leg, r['ms_per_step'], r['spread_ms'][0],
                                                                                                 r['spread_ms'][1], r['active_at_end'][-1]), flush=True)
-            print(policy, B, 'agent-steps/s %.3g' % entry['batch_agent_steps_per_s'], json.dumps(entry['verdict']), json.dumps(entry.get('existing_path')), flush=True)
+            print(policy, B, 'agent-steps/s %.3g' % entry['batch_agent_steps_per_s'], json.dumps(entry.get('verdict')), json.dumps(entry.get('existing_path')),
+                  json.dumps(entry.get('batch_path')), flush=True)
             for sols, _ in legs.values():
                 for sol in sols:
                     sol.close()
