@@ -1,9 +1,16 @@
 """Stress beyond the test suite (needs a GPU; test infrastructure: it drives the oracle, hence it lives under tests/): random scenes at the
-sizes where the library switches kernel forms -- 1 .. 40 000 agents across k_solve_fb (<= 2048), k_kd_top (<= 4096), k_neighbors_kd / kd4
-(6144), k_action_fb / k_lp (16 384) -- all six policies mixed or one policy for everybody, obstacles, agents done from the start, dense and
+sizes where the library switches kernel forms BY ITSELF -- 1 .. 40 000 agents across k_solve_fb (<= 2048), k_kd_top (<= 4096), k_neighbors_kd /
+kd4 (6144), k_action_fb / k_lp (16 384) -- all six policies mixed or one policy for everybody, obstacles, agents done from the start, dense and
 sparse boxes, SCA_NBR_KDTREE and SCA_NBR_AUTO, FREE-RUNNING from the scene's state: after every resident step flags, step counts, the kd
-permutation, float32 velocities, positions, headings and travelled distance must EQUAL the oracle's (tests/test_gpu_parity.py's fuzz family,
-whose scenes stop at 1600 agents and 6 steps).
+permutation, float32 velocities, positions, headings and travelled distance must EQUAL the oracle's.
+
+What of this is in the suite: tests/test_gpu_form_fuzz.py runs the fuzz scenes of tests/form_fuzz.py (up to 1600 agents, 6 steps) through every
+form of sca_forms.h, forced by its switches -- packed K1, the two-launch solve, k_lp, k_fallback + k_action, k_solve_fb, the kd level
+passes, and the combination a large shard runs --, with the action rows, neighbour lists and diagnostics compared as well and the form bits
+asserted; and one real switch at default tunables, scenes drawn as below (0.05 agents per cubic metre, 40 obstacles, mixed policies) of 2047 /
+2049 and 6143 / 6145 agents, two steps.  What stays this script's own: the larger sizes (the 16 384 switch of k_action_fb / k_lp, 25 000 and
+40 000 agents: the oracle needs a minute and more per scene there), longer runs (up to 12 steps), the densities 0.002 and 0.2, 400 obstacles,
+one policy for everybody, and the random draw of all of it by the seed given.
 
     python tests/fuzz_oracle.py <seed> <scenes> [max agents per cubic metre: 0.2 (default; the oracle needs minutes for the largest dense scenes), 0.02]
 """

@@ -7,6 +7,7 @@ travelled distance after update_velocitie (sin / cos / ** 2): since round 6 ever
 import numpy as np
 import pytest
 
+from form_fuzz import per_agent_attributes, random_scene as _random_scene          # the corpus, shared with tests/test_gpu_form_fuzz.py
 from golden_util import episode_fixtures, fixture_agent_params, fixture_params, load, static_inputs
 
 pytestmark = pytest.mark.gpu
@@ -572,8 +573,8 @@ def test_unsupported_pref_speed_is_reported_not_hidden(S):
 @pytest.mark.parametrize('name', ['F5_rvo_dense80', 'F5_orcalp_packed60', 'F5_srvo_packed60', 'F4_mixed_takeoff16',
                                   'F9_hetero_mixed60', 'F3_orca_random100', 'F2_sca_circle100'])
 def test_packed_k1_variant_vs_golden(S, name, monkeypatch):
-    """The four-agents-per-wavefront neighbour kernel (normally chosen for shards >= 8192 agents) forced on the small
-    golden scenes: dense clusters (>16 in range, collisions), obstacles, heterogeneous radii."""
+    """The four-agents-per-wavefront neighbour kernel (normally chosen for shards >= 6144 agents at 1024 SIMDs) forced on the
+    small golden scenes: dense clusters (>16 in range, collisions), obstacles, heterogeneous radii."""
     monkeypatch.setenv('SCA_K1_PACKED', '1')
     fx = load(name)
     st = static_inputs(fx)
@@ -702,38 +703,6 @@ def test_env_step_one_call_path_equals_per_agent_api_path(S):
     assert runs[0][-1][4] == 40
 
 
-def _random_scene(seed):
-    """A random scene for the fuzz test: any agent count, obstacles, mixed policies, agents that are done from the start,
-    dense boxes (collisions, > 16 in range), agents on the ground, zero velocities, goals straight above the start."""
-    rng = np.random.default_rng(seed)
-    n = int(rng.choice([1, 2, 3, 9, 17, 33, 64, 100, 257, 400, 900, 1600]))
-    m = int(rng.choice([0, 0, 1, 5, 30]))
-    side = float(rng.choice([4.0, 10.0, 30.0, 80.0]))
-    pos = rng.uniform(-side, side, (n, 3))
-    pos[:, 2] = np.abs(pos[:, 2]) + rng.choice([0.0, 1.0, 20.0])
-    goal = rng.uniform(-side, side, (n, 3))
-    goal[:, 2] = np.abs(goal[:, 2]) + 1.0
-    if rng.random() < 0.3:
-        goal[: n // 2, :2] = pos[: n // 2, :2]                             # is_zAxis agents (scaPolicy.py:188-190)
-    head = np.zeros((n, 3))
-    head[:, 0] = rng.uniform(0, 2 * np.pi, n)
-    head[:, 1] = rng.uniform(-0.5, 0.5, n)
-    v = rng.normal(0, 1, (n, 3))
-    v /= np.linalg.norm(v, axis=1, keepdims=True)
-    v *= rng.uniform(0, 1, (n, 1))
-    if rng.random() < 0.3:
-        v[rng.random(n) < 0.3] = 0.0                                       # bootstrap branch for some
-    policy = rng.integers(0, 6, n).astype(np.uint8)
-    flags = ((rng.random(n) < 0.1) * rng.choice([1, 2, 4], n)).astype(np.uint8)
-    obs_pos = rng.uniform(-side, side, (m, 3))
-    obs_pos[:, 2] = np.abs(obs_pos[:, 2])
-    vpx = np.trunc(rng.normal(0, 0.6, (n, 3)) * 1e5) / 1e5                 # "tracker output" for SCA / RVO3D+Dubins
-    return dict(n=n, m=m, pos=pos, goal=goal, heading=head, vel=v.astype(np.float32), radius=rng.choice([0.3, 0.5, 1.0], n),
-                pref_speed=rng.choice([1.0, 1.0, 0.8, 1.5], n), policy=policy, flags=flags, obs_pos=obs_pos,
-                obs_radius=rng.choice([0.2, 1.0, 2.0], m), vpref=vpx, vmode=np.isin(policy, (0, 5)).astype(np.uint8),
-                max_run_dist=3.0 * np.linalg.norm(pos - goal, axis=1) + 1.0)
-
-
 @pytest.mark.parametrize('block', range(6))
 def test_random_scenes_every_step_matches_oracle(S, oracle, block):
     """Fuzz: 20 random scenes per block, 6 steps each, FREE-RUNNING from the scene's state (round 5 re-synchronised every step to the
@@ -786,20 +755,13 @@ def test_random_scenes_with_per_agent_attributes_match_oracle(S, oracle, block, 
     scene, one non-default value of each for the whole scene (sca_params).  20 scenes per block, 5 steps each, every step from the oracle's
     state; kd-tree and SCA_NBR_AUTO (whose grid takes the LARGEST neighborDist for its cells and falls back to the kd-tree where the smallest
     cannot hold the collision reach)."""
-    import math
     steps = 5
     nbr = S.NBR_AUTO if mode == 'auto' else S.NBR_KDTREE
     try:
         for seed in range(1000 + 20 * block, 1000 + 20 * block + 20):
             s = _random_scene(seed)
             n = s['n']
-            rng = np.random.default_rng(77 + seed)
-            mhc = rng.choice([0.3, math.pi / 6, math.pi / 4, 1.2, math.pi / 2], n)
-            per = dict(neighbor_dist=rng.choice([1.5, 2.5, 4.0, 10.0, 15.0, 30.0], n), max_neighbors=rng.choice([1, 2, 4, 8, 12, 16], n).astype(np.int32),
-                       time_step=rng.choice([0.05, 0.1, 0.2], n), time_horizon=rng.choice([1.0, 3.0, 10.0, 20.0], n), max_speed=rng.choice([0.7, 1.0, 1.5, 3.0], n),
-                       max_heading_change=mhc, dt_nominal=rng.choice([0.05, 0.1], n))
-            uniform = seed % 3 == 0
-            params = {k: (int(v[0]) if k == 'max_neighbors' else float(v[0])) for k, v in per.items()} if uniform else {}
+            per, params, uniform = per_agent_attributes(seed, n)
             start6 = np.concatenate([s['pos'], s['heading']], 1)
             goal6 = np.concatenate([s['goal'], np.zeros((n, 3))], 1)
             zaxis = S.zaxis_flags(start6, goal6)

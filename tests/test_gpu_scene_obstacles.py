@@ -287,47 +287,40 @@ def _random_obstacles(nscenes):
     return out
 
 
-def test_random_scenes_with_their_own_obstacles_against_the_oracle(S, oracle):
+@pytest.mark.parametrize('packed', [0, 1])
+def test_random_scenes_with_their_own_obstacles_against_the_oracle(S, oracle, packed, monkeypatch):
     """64 seeded scenes (sizes as in test_gpu_scenes.test_random_scenes_against_the_oracle), each with its own 0 / 1 / 2 / 10 / 11 / 21 / 300
-    obstacles, mixed policies, 6 free-running steps: every scene against the oracle run on that scene alone with its own obstacles"""
+    obstacles, mixed policies, 6 free-running steps: every scene against the oracle run on that scene alone with its own obstacles.  In both
+    K1 scene forms (SCA_K1_PACKED: 1 is what 6884 agents run by default -- a wavefront's four groups can belong to four scenes, some of them
+    without obstacles --, 0 is k_neighbors_kd_scenes)."""
+    monkeypatch.setenv('SCA_K1_PACKED', str(packed))                 # read by sca_create
     scenes, sizes, _, _ = TS._random_scenes(S)
     obstacles = _random_obstacles(len(scenes))
     assert sorted({len(r) for _, r in obstacles}) == OBS_COUNTS
     sol, off = _context(S, scenes, obstacles)
     obs_off = np.concatenate([[0], np.cumsum([len(r) for _, r in obstacles])]).astype(np.int32)
-    ref = []
-    for sc in scenes:
-        m = sc['n']
-        ref.append(dict(pos=sc['start'][:, :3].copy(), vel=np.zeros((m, 3), np.float32), head=sc['start'][:, 3:6].copy(), flags=np.zeros(m, np.uint8),
-                        td=np.zeros(m), sn=np.zeros(m, np.int32), perm=np.arange(m, dtype=np.int32), ext=np.isin(sc['policy'], (0, 5)),
-                        tr=oracle.Tracker(np.ascontiguousarray(sc['goal'][:, :3]), sc['goal'][:, 3:6], np.ones(m), sc['zaxis'])))
+    ref = TS.oracle_scene_runs(oracle, 'own obstacles', scenes, obstacles, stop_when_done=True)
     saw_obstacle_neighbour, finished = set(), set()
     for t in range(6):
         sol.run_steps(1, S.NBR_KDTREE)
         sol.synchronize()
         assert sol.pass_forms() & S.FORM_SCENE_OBSTACLES
         g, a, vd, perm, nb = sol.get_state(), sol.actions(), sol.diag()['vpref'], sol.get_kd_perm(), sol.neighbors()
-        for s, (sc, r) in enumerate(zip(scenes, ref)):
+        for s, sc in enumerate(scenes):
             m, sl, lo, olo = sc['n'], slice(int(off[s]), int(off[s + 1])), int(off[s]), int(obs_off[s])
             obs_pos, obs_radius = obstacles[s]
-            if (r['flags'] & 7).all():
+            r = ref[s]['steps'][t]
+            if r is None:
                 # every agent is done: the reference's `while not env.step()` has stopped calling env.step() for this scene, and in the
                 # batch it is inert -- its state what its last step left, its action rows zero
+                r = ref[s]['last']
                 finished.add(s)
                 assert not a[sl].any(), ('finished scene', s, 'step', t, 'action')
                 assert np.array_equal(perm[sl] - lo, r['perm']), ('finished scene', s, 'step', t, 'perm')
                 for key, want in (('pos', r['pos']), ('vel', r['vel']), ('heading', r['head']), ('flags', r['flags']), ('total_dist', r['td']), ('step_num', r['sn'])):
                     assert np.array_equal(g[key][sl], want), ('finished scene', s, 'step', t, key)
                 continue
-            radius, ps, goal = np.full(m, 0.5), np.ones(m), np.ascontiguousarray(sc['goal'][:, :3])
-            active = ((r['flags'] & 7) == 0) & r['ext']
-            vp = r['tr'].vpref(r['pos'], r['vel'], r['head'], active.astype(np.uint8), nthreads=16)
-            p = oracle.policy_step(r['pos'], r['vel'], r['head'], radius, ps, r['flags'], goal, sc['policy'], sc['zaxis'], vp, r['ext'].astype(np.uint8),
-                                   r['perm'], obs_pos, obs_radius, nthreads=16)
-            r['tr'].note_neighbors(p['nbr_valid'], p['nbr_n'], p['nbr_dsq'])
-            r['perm'] = p['perm']
-            u = oracle.env_update(r['pos'], r['vel'], r['head'], radius, p['flags'], goal, p['action'], r['td'], sc['mrd'], r['sn'], obs_pos, obs_radius)
-            r['pos'], r['vel'], r['head'], r['flags'], r['td'], r['sn'] = u['pos'], u['vel'], u['heading'], u['flags'], u['total_dist'], u['step_num']
+            p, active = r['p'], r['active']
             ctx = ('scene', s, 'size', m, 'obstacles', len(obs_radius), 'step', t)
             assert np.array_equal(a[sl], p['action']), ctx + ('action',)
             valid = p['nbr_valid'].astype(bool)
@@ -351,8 +344,7 @@ def test_random_scenes_with_their_own_obstacles_against_the_oracle(S, oracle):
     rd = sol.device_tracker_replans()
     for s, r in enumerate(ref):
         sl = slice(int(off[s]), int(off[s + 1]))
-        assert np.array_equal(rd[sl][r['ext']], r['tr'].replans()[r['ext']]), ('re-plans', s)
-        r['tr'].close()
+        assert np.array_equal(rd[sl][r['ext']], r['replans'][r['ext']]), ('re-plans', s)
     sol.close()
 
 

@@ -245,9 +245,50 @@ def _random_scenes(S):
     return scenes, sizes, obs_pos, obs_radius
 
 
-def test_random_scenes_against_the_oracle(S, oracle):
+_ORACLE_RUNS = {}
+
+
+def oracle_scene_runs(oracle, key, scenes, obstacle_sets, steps=6, stop_when_done=False):
+    """Every scene alone through the oracle (policy_step / env_update / Tracker), `steps` free-running steps, made once per `key` and shared by
+    the K1 forms that are compared with it.  Per scene: `steps` (one dict per step: p = policy_step's result, active = the tracked agents it
+    served, and the state after the step -- or, with stop_when_done, None from the step on at which every agent was done: the reference's
+    `while not env.step()` has stopped by then), `last` (the state the scene ended on), ext and the tracker's re-plan counts."""
+    if key in _ORACLE_RUNS:
+        return _ORACLE_RUNS[key]
+    out = []
+    for sc, (obs_pos, obs_radius) in zip(scenes, obstacle_sets):
+        m = sc['n']
+        r = dict(pos=sc['start'][:, :3].copy(), vel=np.zeros((m, 3), np.float32), head=sc['start'][:, 3:6].copy(), flags=np.zeros(m, np.uint8),
+                 td=np.zeros(m), sn=np.zeros(m, np.int32), perm=np.arange(m, dtype=np.int32))
+        ext = np.isin(sc['policy'], (0, 5))
+        tr = oracle.Tracker(np.ascontiguousarray(sc['goal'][:, :3]), sc['goal'][:, 3:6], np.ones(m), sc['zaxis'])
+        radius, ps, goal = np.full(m, 0.5), np.ones(m), np.ascontiguousarray(sc['goal'][:, :3])
+        rows = []
+        for t in range(steps):
+            if stop_when_done and (r['flags'] & 7).all():
+                rows.append(None)
+                continue
+            active = ((r['flags'] & 7) == 0) & ext
+            vp = tr.vpref(r['pos'], r['vel'], r['head'], active.astype(np.uint8), nthreads=16)
+            p = oracle.policy_step(r['pos'], r['vel'], r['head'], radius, ps, r['flags'], goal, sc['policy'], sc['zaxis'], vp, ext.astype(np.uint8),
+                                   r['perm'], obs_pos, obs_radius, nthreads=16)
+            tr.note_neighbors(p['nbr_valid'], p['nbr_n'], p['nbr_dsq'])
+            u = oracle.env_update(r['pos'], r['vel'], r['head'], radius, p['flags'], goal, p['action'], r['td'], sc['mrd'], r['sn'], obs_pos, obs_radius)
+            r = dict(pos=u['pos'], vel=u['vel'], head=u['heading'], flags=u['flags'], td=u['total_dist'], sn=u['step_num'], perm=p['perm'])
+            rows.append(dict(r, p=p, active=active))
+        out.append(dict(steps=rows, last=r, ext=ext, replans=tr.replans()))
+        tr.close()
+    _ORACLE_RUNS[key] = out
+    return out
+
+
+@pytest.mark.parametrize('packed', [0, 1])
+def test_random_scenes_against_the_oracle(S, oracle, packed, monkeypatch):
     """64 seeded scenes of sizes at the leaf boundary, the block instances' edges and the cap, mixed policies, shared obstacles, 6 free-running
-    steps: every scene against the oracle run on that scene alone (policy_step / env_update / Tracker), equality."""
+    steps: every scene against the oracle run on that scene alone (policy_step / env_update / Tracker), equality.  In both K1 scene forms:
+    the 6884 agents are a packed pass by default (k_neighbors_kd4_scenes: the scenes of 1, 2 and 3 agents share their wavefront with other
+    scenes' groups), SCA_K1_PACKED=0 sends them through k_neighbors_kd_scenes."""
+    monkeypatch.setenv('SCA_K1_PACKED', str(packed))                 # read by sca_create
     scenes, sizes, obs_pos, obs_radius = _random_scenes(S)
     off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
     n = int(off[-1])
@@ -259,27 +300,15 @@ def test_random_scenes_against_the_oracle(S, oracle):
     sol.set_scenes(off)
     sol.device_tracker_enable(goal6[:, 3:6], in_pass=True)
     sol.set_state(start[:, :3], np.zeros((n, 3), np.float32), start[:, 3:6], np.zeros(n, np.uint8))
-    ref = []
-    for sc in scenes:
-        m = sc['n']
-        ref.append(dict(pos=sc['start'][:, :3].copy(), vel=np.zeros((m, 3), np.float32), head=sc['start'][:, 3:6].copy(), flags=np.zeros(m, np.uint8),
-                        td=np.zeros(m), sn=np.zeros(m, np.int32), perm=np.arange(m, dtype=np.int32), ext=np.isin(sc['policy'], (0, 5)),
-                        tr=oracle.Tracker(np.ascontiguousarray(sc['goal'][:, :3]), sc['goal'][:, 3:6], np.ones(m), sc['zaxis'])))
+    ref = oracle_scene_runs(oracle, 'shared obstacles', scenes, [(obs_pos, obs_radius)] * len(scenes))
     for t in range(6):
         sol.run_steps(1, S.NBR_KDTREE)
         sol.synchronize()
         g, a, vd, perm, nb = sol.get_state(), sol.actions(), sol.diag()['vpref'], sol.get_kd_perm(), sol.neighbors()
-        for s, (sc, r) in enumerate(zip(scenes, ref)):
+        for s, sc in enumerate(scenes):
             m, sl, lo = sc['n'], slice(int(off[s]), int(off[s + 1])), int(off[s])
-            radius, ps, goal = np.full(m, 0.5), np.ones(m), np.ascontiguousarray(sc['goal'][:, :3])
-            active = ((r['flags'] & 7) == 0) & r['ext']
-            vp = r['tr'].vpref(r['pos'], r['vel'], r['head'], active.astype(np.uint8), nthreads=16)
-            p = oracle.policy_step(r['pos'], r['vel'], r['head'], radius, ps, r['flags'], goal, sc['policy'], sc['zaxis'], vp, r['ext'].astype(np.uint8),
-                                   r['perm'], obs_pos, obs_radius, nthreads=16)
-            r['tr'].note_neighbors(p['nbr_valid'], p['nbr_n'], p['nbr_dsq'])
-            r['perm'] = p['perm']
-            u = oracle.env_update(r['pos'], r['vel'], r['head'], radius, p['flags'], goal, p['action'], r['td'], sc['mrd'], r['sn'], obs_pos, obs_radius)
-            r['pos'], r['vel'], r['head'], r['flags'], r['td'], r['sn'] = u['pos'], u['vel'], u['heading'], u['flags'], u['total_dist'], u['step_num']
+            r = ref[s]['steps'][t]
+            p, active = r['p'], r['active']
             ctx = ('scene', s, 'size', m, 'step', t)
             assert np.array_equal(a[sl], p['action']), ctx + ('action',)
             valid = p['nbr_valid'].astype(bool)
@@ -296,8 +325,7 @@ def test_random_scenes_against_the_oracle(S, oracle):
     rd = sol.device_tracker_replans()
     for s, r in enumerate(ref):
         sl = slice(int(off[s]), int(off[s + 1]))
-        assert np.array_equal(rd[sl][r['ext']], r['tr'].replans()[r['ext']]), ('re-plans', s)
-        r['tr'].close()
+        assert np.array_equal(rd[sl][r['ext']], r['replans'][r['ext']]), ('re-plans', s)
     sol.close()
 
 
