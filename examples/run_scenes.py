@@ -8,6 +8,8 @@ one metrics row per scene -- what a loop over the reference's run_example/run_*.
                                                        # every scene meets its own obstacles only (SceneBatch(scene_obstacles=...))
     python examples/run_scenes.py --seeds 8 --slots 16 # the same table -- policies x (circle + 8 seeds) -- as a QUEUE streamed through 16 slots
                                                        # (scenes.run_episodes): a slot that finishes restarts with the next episode
+    python examples/run_scenes.py --seeds 2 --slots 8 --log-dir out    # ... and one folder per episode under out/: env_cfg.json + trajs.npz, what
+                                                       # run_example/run_*.py write (the log per scene, SceneBatch(scene_history=...))
 """
 import argparse
 import os
@@ -34,6 +36,7 @@ def main():
     ap.add_argument('--max-steps', type=int, default=20000)
     ap.add_argument('--obstacles', action='store_true', help='add a take-off/landing scene with its 8 spheres per policy (one obstacle list per scene)')
     ap.add_argument('--slots', type=int, default=0, help='stream the table through this many slots instead of holding it as one batch')
+    ap.add_argument('--log-dir', default=None, help='write one folder per episode here: env_cfg.json + trajs.npz (the first --max-steps steps of each)')
     args = ap.parse_args()
     if args.slots and args.obstacles:
         ap.error('--slots streams episodes that share one obstacle list: not with --obstacles')
@@ -52,6 +55,9 @@ def main():
             scenes.append(build_agents(sc, pol))
             obstacles.append([E.Obstacle(pos=list(p), shape_dict={'shape': 'sphere', 'feature': float(r)}, id=i)
                               for i, (p, r) in enumerate(zip(sc['obs_pos'], sc['obs_radius']))])
+    def folder(k):
+        return os.path.join(args.log_dir, '%03d_%s_%s' % (k, names[k][0], names[k][1].replace(' ', '_')))
+
     if args.slots:
         t0, stats = time.time(), {}
 
@@ -59,11 +65,18 @@ def main():
             pname, what = names[r['episode']]
             print('%-10s %-14s slot %3d steps %5d  ' % (pname, what, r['slot'], r['steps']) +
                   '  '.join('%s %.4g' % (k, r['metrics'][k]) for k in ('SuccessRate', 'ExtraTime', 'ExtraDistance', 'AverageSpeed')), flush=True)
-        run_episodes(scenes, args.slots, device_tracker=True, on_done=row, max_steps=args.max_steps, stats=stats)
+            if args.log_dir:
+                metrics.write_log_files(folder(r['episode']), scenes[r['episode']], r['trajectories'], r['info'], xlsx=False)
+                if r['rows_dropped']:
+                    print('    (the log holds the first %d steps: %d more did not fit --max-steps rows)' % (r['trajectories'].shape[1], r['rows_dropped']))
+        run_episodes(scenes, args.slots, device_tracker=True, on_done=row, max_steps=args.max_steps, stats=stats,
+                     history_rows=args.max_steps if args.log_dir else 0)
         print('%d episodes through %d slots: %d batch steps, mean live fraction %.2f, %.2f s' %
               (len(scenes), args.slots, stats['batch_steps'], stats['live_fraction'], time.time() - t0))
         return
-    batch = SceneBatch(scenes, scene_obstacles=obstacles, device_tracker=True) if args.obstacles else SceneBatch(scenes, [], device_tracker=True)
+    rows = args.max_steps if args.log_dir else 0
+    batch = SceneBatch(scenes, scene_obstacles=obstacles, device_tracker=True, scene_history=rows) if args.obstacles else \
+        SceneBatch(scenes, [], device_tracker=True, scene_history=rows)
     t0, steps = time.time(), 0
     while steps < args.max_steps and not batch.step():
         steps += 1
@@ -72,6 +85,8 @@ def main():
         m = metrics.episode_metrics(batch.env(s))
         print('%-10s %-14s steps %5d %s  ' % (pname, what, batch.steps[s], 'done' if batch.done[s] else 'RUNNING') +
               '  '.join('%s %.4g' % (k, m[k]) for k in ('SuccessRate', 'ExtraTime', 'ExtraDistance', 'AverageSpeed')))
+        if args.log_dir:
+            metrics.write_episode_log(batch.env(s), folder(s), xlsx=False)
     batch.close()
 
 

@@ -169,7 +169,10 @@ int sca_set_path_state(sca_ctx *ctx, const int32_t *remaining /*n*/, const doubl
  * different scenes never appear in each other's neighbour lists or collision tests, every scene has its own kd-tree, its own carried
  * permutation and its own `done`, and for every scene every value the context produces is bit for bit what a context holding that scene
  * alone produces.  Obstacles are either one set shared by all scenes (sca_set_obstacles) or one set per scene (sca_set_scene_obstacles,
- * below); everything per agent (sca_set_agent_params, the device tracker, sca_set_paths, the history log, sca_step_host) works as without scenes.  sca_version() is unchanged: detect the feature by the symbol.
+ * below); everything per agent (sca_set_agent_params, the device tracker, sca_set_paths, sca_step_host) works as without scenes.  The
+ * context-wide history log (sca_history_enable) records every agent on every CONTEXT step, finished scenes included (a finished scene's
+ * agents still pass through the integrate stage with a zero action): for per-episode trajectories use the log per scene,
+ * sca_scene_history_enable below.  sca_version() is unchanged: detect the feature by the symbol.
  *   sca_set_scenes      after sca_set_agents (SCA_ERR_STATE before; sca_set_agents clears the scenes).  offsets[0] == 0, strictly increasing,
  *                       offsets[nscenes] == n (SCA_ERR_ARG); every scene at most 1536 agents, KD_WAVE_CAP -- a scene's tree is built by one
  *                       workgroup (SCA_ERR_UNSUPPORTED, the message names the limit).  nscenes == 0 or offsets == NULL: no scenes, a plain
@@ -232,6 +235,33 @@ int sca_restart_scenes(sca_ctx *ctx, int count, const int32_t *scene_ids /*count
                        const double *radius, const double *pref_speed, const double *goal /*T*3*/, const uint8_t *policy,
                        const uint8_t *zaxis, const double *max_run_dist,      /* each T, each nullable: keep the slot's */
                        const double *goal_heading /*T*3, nullable: keep the slot's*/);
+
+/* A trajectory log per scene = every episode's Agent.history_info.  Row r of scene s is the scene's r-th own step (r = steps[s] - 1 while
+ * that step runs), written only for steps the scene was live at their beginning, so a finished scene gains no row while the others run on,
+ * and the log starts over at row 0 when the scene is restarted.  For every scene the rows are bit for bit the rows sca_get_history gives
+ * for a context that holds that episode alone with sca_history_enable, and no other scene's log can tell that a scene finished,
+ * overflowed or was restarted.  Written by one kernel of its own in front of the step's last one, in every step form (sca_env_step,
+ * sca_run_steps, sca_step_host, sca_policy_pass + sca_env_update, an sca_env_update alone); a context without the log enqueues what it
+ * did.  The context-wide log (sca_history_enable) is independent and may be on at the same time.  64 bytes per agent per row, allocated
+ * up front: capacity_rows x n x 64 bytes.  Detect the feature by the symbol (sca_version() is unchanged).
+ *   sca_scene_history_enable  capacity_rows is PER SCENE; 0 frees the log.  SCA_ERR_STATE: no scenes, between a policy pass and its env
+ *              update, or (capacity > 0) a scene that has taken a step already -- enable the log behind sca_set_scenes / sca_set_state,
+ *              before the first step: rows are indexed by the scene's own step count, and rows that were never written must not be
+ *              reported as logged.  SCA_ERR_ARG: a negative capacity.  A refused call has changed nothing.
+ *   sca_scene_history_rows    rows_logged[s] = min(steps[s], capacity), rows_dropped[s] = max(0, steps[s] - capacity): steps beyond the
+ *              capacity are counted, never written.  One synchronisation for all scenes.  (Between a policy pass and its env update the
+ *              step under way is not counted: its row is not written yet.)
+ *   sca_get_scene_history     a window of rows and SCENE-LOCAL agents of one scene, [row][agent][3] like sca_get_history: one contiguous
+ *              device-to-host copy.  Any output pointer may be NULL.
+ *   refusals of the two       SCA_ERR_STATE: no scenes, or the log is not enabled.  SCA_ERR_ARG: a scene outside 0 .. nscenes-1, a row window
+ *              outside [0, rows_logged[scene]), an agent window outside the scene.
+ *   lifetime   whatever drops or redefines the scenes -- sca_set_agents, sca_set_scenes, sca_set_scenes(0, NULL) -- frees the log, as it
+ *              drops the per-scene obstacle sets.  sca_restart_scenes keeps the allocation and starts the named scenes' logs over (stale
+ *              rows of the episode before are beyond rows_logged).  sca_set_state leaves steps[s] alone, so the log goes on. */
+int sca_scene_history_enable(sca_ctx *ctx, int capacity_rows);
+int sca_scene_history_rows(sca_ctx *ctx, int32_t *rows_logged /*nscenes, nullable*/, int32_t *rows_dropped /*nscenes, nullable*/);
+int sca_get_scene_history(sca_ctx *ctx, int scene, int first_row, int nrows, int agent_begin, int agent_count,
+                          double *pos, double *heading, float *vel);
 
 /* the hot path ----------------------------------------------------------------------------------- */
 int sca_policy_pass(sca_ctx *ctx, int neighbor_mode);

@@ -55,6 +55,9 @@ SIGNATURES = {
     'sca_get_scene_state': (C.c_int, [C.c_void_p, ip, ip]),
     'sca_set_scene_obstacles': (C.c_int, [C.c_void_p, C.c_int, ip, dp, dp]),
     'sca_restart_scenes': (C.c_int, [C.c_void_p, C.c_int, ip, dp, fp, dp, dp, dp, dp, bp, bp, dp, dp]),
+    'sca_scene_history_enable': (C.c_int, [C.c_void_p, C.c_int]),
+    'sca_scene_history_rows': (C.c_int, [C.c_void_p, ip, ip]),
+    'sca_get_scene_history': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, fp]),
     'sca_set_path_state': (C.c_int, [C.c_void_p, ip, dp]),
     'sca_policy_pass': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_get_actions': (C.c_int, [C.c_void_p, fp]),

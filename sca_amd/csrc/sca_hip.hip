@@ -308,10 +308,11 @@ struct sca_ctx {
         SceneObsView ov{};              // device array [nscenes]
         std::vector<int32_t> h_obs_off; // [nscenes + 1] the obstacle offsets as set
         uint8_t *rs_host = nullptr;     // sca_restart_scenes' page-locked staging block (RestartLayout of max_n, sca_scenes.h), allocated on first use
+        SceneLogView log{};             // the trajectory log per scene (sca_scene_history_enable), rows null: off -- a step then enqueues nothing for it
         void release() {                // the device and page-locked allocations, behind a synchronised stream; the flags and host vectors stay
-            for (void *p : {(void *)v.scene_of, (void *)v.offsets, (void *)counters, (void *)v.heading_keep, (void *)ov.oroot}) if (p) (void)hipFree(p);
+            for (void *p : {(void *)v.scene_of, (void *)v.offsets, (void *)counters, (void *)v.heading_keep, (void *)ov.oroot, (void *)log.rows}) if (p) (void)hipFree(p);
             if (rs_host) (void)hipHostFree(rs_host);
-            v = SceneView{}; counters = nullptr; ov = SceneObsView{}; rs_host = nullptr;
+            v = SceneView{}; counters = nullptr; ov = SceneObsView{}; rs_host = nullptr; log = SceneLogView{};
         }
     } scenes;
     std::vector<uint8_t> h_policy;      // [n] the agents' policies as they stand (sca_set_agents, sca_restart_scenes)
@@ -1337,9 +1338,18 @@ static int scene_obstacles_drop(sca_ctx *c) {
     c->near_valid = false;
     return 0;
 }
+// ... and so does the log per scene: its layout is cut by the scenes' offsets
+static int scene_log_drop(sca_ctx *c) {
+    if (!c->scenes.log.rows) return 0;
+    CHK(c, hipStreamSynchronize(c->stream));
+    (void)hipFree(c->scenes.log.rows);
+    c->scenes.log = SceneLogView{};
+    return 0;
+}
 static int scenes_clear(sca_ctx *c) {
     if (!c->scenes.on) return 0;
     if (int r = scene_obstacles_drop(c)) return r;
+    if (int r = scene_log_drop(c)) return r;
     CHK(c, hipStreamSynchronize(c->stream));
     c->scenes.on = false;
     c->scenes.h_off.clear();
@@ -2180,6 +2190,8 @@ static int launch_collide_finish(sca_ctx *c, bool timed) {
         hipLaunchKernelGGL(k_scene_begin, dim3((c->scenes.v.nscenes + 255) / 256), dim3(256), 0, c->stream, c->scenes.v);
     }
     c->near_valid = false;
+    if (c->scenes.on && c->scenes.log.rows)                                // the scene log's row of this step: behind k_scene_begin, in front of the step's last kernel
+        hipLaunchKernelGGL(k_scene_log, dim3((unsigned)((4 * (int64_t)d.n + SCENE_LOG_T - 1) / SCENE_LOG_T)), dim3(SCENE_LOG_T), 0, c->stream, d, c->scenes.v, c->scenes.log);
     const dim3 k4grid((cnt + K4_WAVES * K4_APW - 1) / (K4_WAVES * K4_APW));
     // (the event that rides on the step's last kernel, if sca_run_steps asked for one: the next pass's fork)
     const bool others = c->part_on || cnt < d.n;
@@ -2982,6 +2994,83 @@ int sca_get_history(sca_ctx *c, int first_row, int nrows, int agent_begin, int a
         if (heading) { heading[3 * i] = h.a; heading[3 * i + 1] = h.b; heading[3 * i + 2] = h.g; }
         if (vel) { vel[3 * i] = h.vx; vel[3 * i + 1] = h.vy; vel[3 * i + 2] = h.vz; }
     }
+    return 0;
+}
+
+// ---- a trajectory log per scene (include/sca_hip.h; the rules and the layout are sca_scenes.h's, the kernel is k_scene_log) ------------------
+// the scenes' step counts as far as their rows are written: between a policy pass and its env update a live scene's counter is one ahead
+// of its log (scene_begin_one has counted the step, k_scene_log has not run).  One copy, one synchronisation.
+static int scene_log_steps(sca_ctx *c, std::vector<int32_t> &steps) {
+    const int B = c->scenes.v.nscenes;
+    std::vector<int32_t> h(2 * (size_t)B);                                 // prev | steps stand side by side behind the live lines
+    CHK(c, hipMemcpyAsync(h.data(), c->scenes.v.prev, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    steps.assign(h.begin() + B, h.end());
+    if (c->scenes.begun) for (int s = 0; s < B; s++) if (h[s] > 0) steps[s] -= 1;
+    return 0;
+}
+static int scene_log_refuse(sca_ctx *c, const char *who, const SceneLogCheck &k) {
+    switch (k.fault) {
+    case SCENE_LOG_OK: return 0;
+    case SCENE_LOG_NO_SCENES: c->err = std::string(who) + ": no scenes -- sca_set_scenes first"; break;
+    case SCENE_LOG_MID_STEP: c->err = std::string(who) + " between a policy pass and its env update: finish the step first"; break;
+    case SCENE_LOG_STEPPED: c->err = std::string(who) + ": scene " + std::to_string(k.scene) + " has taken a step already -- enable the log behind sca_set_scenes / sca_set_state, before the first step"; break;
+    case SCENE_LOG_OFF: c->err = std::string(who) + ": sca_scene_history_enable first"; break;
+    case SCENE_LOG_BAD_CAPACITY: c->err = std::string(who) + ": capacity_rows must not be negative"; break;
+    case SCENE_LOG_BAD_SCENE: c->err = std::string(who) + ": scene " + std::to_string(k.scene) + " is not a scene of this context (0 .. " + std::to_string(c->scenes.v.nscenes - 1) + ")"; break;
+    case SCENE_LOG_BAD_ROWS: c->err = std::string(who) + ": row window outside the rows scene " + std::to_string(k.scene) + " has logged"; break;
+    default: c->err = std::string(who) + ": agent window outside scene " + std::to_string(k.scene);
+    }
+    return scene_log_error_code(k.fault);
+}
+int sca_scene_history_enable(sca_ctx *c, int capacity_rows) {
+    API_ENTER(c);
+    const int B = c->scenes.on ? c->scenes.v.nscenes : 0;
+    std::vector<int32_t> steps;
+    if (B > 0 && !c->scenes.begun && capacity_rows > 0) { if (int r = scene_log_steps(c, steps)) return r; }
+    if (int r = scene_log_refuse(c, "sca_scene_history_enable", scene_log_enable_check(B, c->scenes.begun, steps.data(), capacity_rows))) return r;
+    HistRow *rows = nullptr;
+    if (capacity_rows > 0) CHK(c, hipMalloc((void **)&rows, (size_t)scene_log_bytes(capacity_rows, c->n)));   // (before the old log goes: a refused call changes nothing)
+    if (int r = scene_log_drop(c)) { if (rows) (void)hipFree(rows); return r; }
+    c->scenes.log.rows = rows; c->scenes.log.capacity = rows ? capacity_rows : 0;
+    return 0;
+}
+int sca_scene_history_rows(sca_ctx *c, int32_t *rows_logged, int32_t *rows_dropped) {
+    API_ENTER(c);
+    const int B = c->scenes.on ? c->scenes.v.nscenes : 0;
+    if (int r = scene_log_refuse(c, "sca_scene_history_rows", scene_log_check(B, nullptr, c->scenes.log.rows != nullptr, c->scenes.log.capacity, false, 0, 0, 0, 0, 0, 0))) return r;
+    std::vector<int32_t> steps;
+    if (int r = scene_log_steps(c, steps)) return r;
+    for (int s = 0; s < B; s++) {
+        if (rows_logged) rows_logged[s] = scene_log_rows_logged(steps[s], c->scenes.log.capacity);
+        if (rows_dropped) rows_dropped[s] = scene_log_rows_dropped(steps[s], c->scenes.log.capacity);
+    }
+    return 0;
+}
+int sca_get_scene_history(sca_ctx *c, int scene, int first_row, int nrows, int agent_begin, int agent_count, double *pos, double *heading, float *vel) {
+    API_ENTER(c);
+    const int B = c->scenes.on ? c->scenes.v.nscenes : 0;
+    const SceneLogView &L = c->scenes.log;
+    const int32_t *off = c->scenes.h_off.data();
+    // the faults that need no device value first (an empty row window passes this round), then the row window against the scene's step count
+    if (int r = scene_log_refuse(c, "sca_get_scene_history", scene_log_check(B, off, L.rows != nullptr, L.capacity, true, scene, 0, 0, 0, agent_begin, agent_count))) return r;
+    std::vector<int32_t> steps;
+    if (int r = scene_log_steps(c, steps)) return r;
+    if (int r = scene_log_refuse(c, "sca_get_scene_history", scene_log_check(B, off, true, L.capacity, true, scene, steps[scene], first_row, nrows, agent_begin, agent_count))) return r;
+    if (nrows == 0 || agent_count == 0) return 0;
+    // rows [first_row, first_row + nrows) of the scene are one contiguous range; the agent window is cut out of it while unpacking
+    const int lo = off[scene], ns = off[scene + 1] - lo;
+    std::vector<HistRow> tmp((size_t)nrows * ns);
+    CHK(c, hipMemcpyAsync(tmp.data(), L.rows + scene_log_index(L.capacity, lo, ns, first_row, 0), sizeof(HistRow) * tmp.size(), hipMemcpyDeviceToHost, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    for (int r = 0; r < nrows; r++)
+        for (int a = 0; a < agent_count; a++) {
+            const HistRow &h = tmp[(size_t)r * ns + agent_begin + a];
+            const size_t i = (size_t)r * agent_count + a;
+            if (pos) { pos[3 * i] = h.px; pos[3 * i + 1] = h.py; pos[3 * i + 2] = h.pz; }
+            if (heading) { heading[3 * i] = h.a; heading[3 * i + 1] = h.b; heading[3 * i + 2] = h.g; }
+            if (vel) { vel[3 * i] = h.vx; vel[3 * i + 1] = h.vy; vel[3 * i + 2] = h.vz; }
+        }
     return 0;
 }
 

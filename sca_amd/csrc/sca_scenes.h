@@ -217,4 +217,63 @@ inline RestartLayout scene_restart_layout(int cap) {
 constexpr uint32_t RESTART_HAS_RADIUS = 1, RESTART_HAS_PREF_SPEED = 2, RESTART_HAS_GOAL = 4, RESTART_HAS_ZAXIS = 8, RESTART_HAS_MAX_RUN_DIST = 16,
                    RESTART_HAS_GOAL_HEADING = 32;
 
+// ---- a trajectory log per scene (sca_scene_history_enable) -------------------------------------------------------------------------------------
+// One allocation of capacity x n rows of SCENE_LOG_ROW_BYTES (HistRow, sca_kernels.hip.h).  Scene s owns rows [capacity * offsets[s],
+// capacity * offsets[s + 1]); inside its part the layout is [row][agent] with pitch n_s, so any window of rows of one scene is one contiguous
+// range.  Row r of a scene is the scene's r-th own step (steps[s] - 1 while that step runs): a restart, which zeroes steps[s], starts the log
+// over, and rows of the episode before are simply beyond rows_logged.  Everything in int64_t: capacity x n passes 2^31 long before the log
+// passes the memory of a device.
+constexpr int64_t SCENE_LOG_ROW_BYTES = 64;
+// where row r of scene-local agent i stands, in rows from the allocation's start (scene_begin = offsets[s], scene_size = n_s).  The kernel
+// that writes and the host that reads back both call this.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int64_t scene_log_index(int capacity, int scene_begin, int scene_size, int r, int i) {
+    return (int64_t)capacity * (int64_t)scene_begin + (int64_t)r * (int64_t)scene_size + (int64_t)i;
+}
+inline int64_t scene_log_bytes(int capacity, int n) { return SCENE_LOG_ROW_BYTES * (int64_t)capacity * (int64_t)n; }
+// Steps beyond the capacity are counted, never written.
+inline int scene_log_rows_logged(int steps, int capacity) { return steps < capacity ? steps : capacity; }
+inline int scene_log_rows_dropped(int steps, int capacity) { return steps > capacity ? steps - capacity : 0; }
+
+enum SceneLogFault {
+    SCENE_LOG_OK = 0,
+    SCENE_LOG_NO_SCENES,    // the context holds no scenes                                                     } SCA_ERR_STATE
+    SCENE_LOG_MID_STEP,     // between a policy pass and its env update                                        }
+    SCENE_LOG_STEPPED,      // enable: a scene has taken a step already (scene: the first such)                }
+    SCENE_LOG_OFF,          // rows / read-back: the log is not enabled                                        }
+    SCENE_LOG_BAD_CAPACITY, // enable: a negative capacity                                                     } SCA_ERR_ARG
+    SCENE_LOG_BAD_SCENE,    // read-back: a scene outside 0 .. nscenes - 1                                     }
+    SCENE_LOG_BAD_ROWS,     // read-back: a row window outside [0, rows_logged[scene])                         }
+    SCENE_LOG_BAD_AGENTS    // read-back: an agent window outside the scene                                    }
+};
+struct SceneLogCheck { SceneLogFault fault; int scene; };
+// sca_scene_history_enable.  steps: [nscenes] the scenes' step counters as they stand (may be NULL where capacity <= 0 or there are no
+// scenes: it is read last).  Rows are indexed by a scene's own step count, so a log enabled behind a step would report rows it never wrote;
+// capacity 0 only frees and may come at any step count.
+inline SceneLogCheck scene_log_enable_check(int nscenes, bool scene_begun, const int32_t *steps, int capacity) {
+    if (nscenes <= 0) return {SCENE_LOG_NO_SCENES, -1};
+    if (scene_begun) return {SCENE_LOG_MID_STEP, -1};
+    if (capacity < 0) return {SCENE_LOG_BAD_CAPACITY, -1};
+    if (capacity > 0)
+        for (int s = 0; s < nscenes; s++) if (steps[s] > 0) return {SCENE_LOG_STEPPED, s};
+    return {SCENE_LOG_OK, -1};
+}
+// sca_scene_history_rows (window == false: the scene and the windows are not looked at) and sca_get_scene_history.  offsets: checked by
+// scenes_check; steps_of_scene: steps[scene] where the scene is valid (read by the caller behind the checks that need no device value --
+// pass 0 for a first round of them).
+inline SceneLogCheck scene_log_check(int nscenes, const int32_t *offsets, bool enabled, int capacity, bool window, int scene, int steps_of_scene,
+                                     int first_row, int nrows, int agent_begin, int agent_count) {
+    if (nscenes <= 0) return {SCENE_LOG_NO_SCENES, -1};
+    if (!enabled) return {SCENE_LOG_OFF, -1};
+    if (!window) return {SCENE_LOG_OK, -1};
+    if (scene < 0 || scene >= nscenes) return {SCENE_LOG_BAD_SCENE, scene};
+    const int64_t have = scene_log_rows_logged(steps_of_scene, capacity), size = (int64_t)offsets[scene + 1] - offsets[scene];
+    if (agent_begin < 0 || agent_count < 0 || (int64_t)agent_begin + agent_count > size) return {SCENE_LOG_BAD_AGENTS, scene};
+    if (first_row < 0 || nrows < 0 || (int64_t)first_row + nrows > have) return {SCENE_LOG_BAD_ROWS, scene};
+    return {SCENE_LOG_OK, scene};
+}
+inline int scene_log_error_code(SceneLogFault f) { return f == SCENE_LOG_OK ? SCA_OK : f <= SCENE_LOG_OFF ? SCA_ERR_STATE : SCA_ERR_ARG; }
+
 }  // namespace sca

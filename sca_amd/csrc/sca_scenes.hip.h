@@ -233,4 +233,36 @@ __global__ __launch_bounds__(K4_WAVES * 64) void k_collide_finish_scenes(DeviceV
     }, SceneCount{d, r.v});
 }
 
+// ---- a trajectory log per scene (sca_scene_history_enable; the layout and its index are sca_scenes.h's) -------------------------------------
+// Enqueued in front of k_collide_finish_scenes, the one place every step form passes through: d.rec_new holds the moved records with the
+// flags the agents entered the step with, d.heading the integrated angles, prev / steps are final for the step -- the fields integrate_agent
+// puts into a HistRow of the context-wide log.  A scene that had nobody live when the step began writes nothing (the reference stopped
+// calling env.step() for it), nor does a step beyond the capacity; either way no other scene's rows are touched.
+// Four lanes per row, one 16-byte quarter each: a wavefront's store covers 1 KB of consecutive bytes while its 16 agents are of one scene
+// (agents of a scene are consecutive in a row of the log).
+static_assert(sizeof(HistRow) == SCENE_LOG_ROW_BYTES, "the scene log's rows are HistRow");
+struct SceneLogView {
+    HistRow *rows;            // [capacity * n]
+    int capacity;             // rows per scene
+};
+typedef double __attribute__((ext_vector_type(2), may_alias)) scene_log_quarter;
+constexpr int SCENE_LOG_T = 256;
+__global__ __launch_bounds__(SCENE_LOG_T) void k_scene_log(DeviceView d, SceneView v, SceneLogView L) {
+    const int t = blockIdx.x * SCENE_LOG_T + threadIdx.x;
+    const int agent = t >> 2, q = t & 3;
+    if (agent >= d.n) return;
+    const int s = v.scene_of[agent];
+    if (v.prev[s] == 0) return;
+    const int row = v.steps[s] - 1;
+    if (row < 0 || row >= L.capacity) return;
+    const int lo = v.offsets[s];
+    const PubRec *r = d.rec_new + agent;
+    scene_log_quarter w;
+    if (q == 0) { w.x = r->px; w.y = r->py; }                                      // HistRow: px py | pz a | b g | vx vy vz flags
+    else if (q == 1) { w.x = r->pz; w.y = d.heading[agent * 3 + 0]; }
+    else if (q == 2) { w.x = d.heading[agent * 3 + 1]; w.y = d.heading[agent * 3 + 2]; }
+    else __builtin_memcpy(&w, &r->vx, 16);                                         // vx vy vz flags stand in PubRec as they do in HistRow
+    reinterpret_cast<scene_log_quarter *>(L.rows + scene_log_index(L.capacity, lo, v.offsets[s + 1] - lo, row, agent - lo))[q] = w;
+}
+
 }  // namespace sca

@@ -6,7 +6,7 @@
     visualization/draw_episode.py:17-32 reads (`all_agent_info`, `all_obstacle`).
   * `trajectories(env)`     — `agent.history_info` (agent.py:75-77,126-148): the 13 ANIMATION_COLUMNS per agent per env step,
     read back from the log the integrate kernel keeps in HBM (`sca_history_enable`), so a resident run needs no per-step
-    readback.
+    readback.  For one scene of a SceneBatch (`batch.env(s)`) the rows come from the log per scene (`sca_scene_history_enable`).
   * `write_episode_log(env, dir)` — `env_cfg.json` + `trajs.npz` (one [rows, 13] array per agent under the reference's
     sheet name `agent<id>`); `trajs.xlsx` as well when openpyxl is importable (it is what the reference writes).
 
@@ -82,11 +82,14 @@ def episode_info(env, total_policy_time_s=None):
     return info
 
 
-def trajectories(env, agent_begin=0, agent_count=None):
-    """[agents, rows, 13] array of the ANIMATION_COLUMNS, read from the device log (needs MACAEnv(history_capacity=...))."""
-    rows, dropped = env.solver.history_rows()
-    if dropped:
-        raise RuntimeError(f'{dropped} env steps did not fit the trajectory log: raise history_capacity')
+def trajectories(env, agent_begin=0, agent_count=None, rows=None):
+    """[agents, rows, 13] array of the ANIMATION_COLUMNS, read from the device log (needs MACAEnv(history_capacity=...), or, for a scene view
+    `batch.env(s)`, SceneBatch(scene_history=...): then the rows are that scene's own steps).  rows: the first `rows` logged rows, whether or not later steps were
+    dropped (default: all of them, RuntimeError when steps were dropped)."""
+    if rows is None:
+        rows, dropped = env.solver.history_rows()
+        if dropped:
+            raise RuntimeError(f'{dropped} env steps did not fit the trajectory log: raise history_capacity')
     n = len(env.agents)
     if agent_count is None:
         agent_count = n - agent_begin
@@ -101,27 +104,33 @@ def trajectories(env, agent_begin=0, agent_count=None):
 
 
 def write_episode_log(env, log_dir, total_policy_time_s=None, xlsx=None):
-    """Writes what run_sca.py:181-259 writes: the trajectories and env_cfg.json.  Returns the paths."""
+    """Writes what run_sca.py:181-259 writes: the trajectories and env_cfg.json.  Returns the paths.  env: a MACAEnv, or one scene of a
+    SceneBatch (`batch.env(s)`)."""
+    return write_log_files(log_dir, env.agents, trajectories(env), episode_info(env, total_policy_time_s), xlsx)
+
+
+def write_log_files(log_dir, agents, traj, info, xlsx=None):
+    """The files of write_episode_log from their contents: traj [agents, rows, 13] (trajectories), info (episode_info).  What a caller
+    that was handed both -- scenes.run_episodes(history_rows=...) -- writes an episode's folder with."""
     os.makedirs(log_dir, exist_ok=True)
     paths = {}
-    traj = trajectories(env)
     paths['trajs'] = os.path.join(log_dir, 'trajs.npz')
     np.savez_compressed(paths['trajs'], columns=np.array(ANIMATION_COLUMNS),
-                        **{'agent' + str(a.id): traj[i] for i, a in enumerate(env.agents)})
+                        **{'agent' + str(a.id): traj[i] for i, a in enumerate(agents)})
     if xlsx is None or xlsx:
         try:
             import openpyxl  # noqa: F401
             import pandas as pd
             paths['xlsx'] = os.path.join(log_dir, 'trajs.xlsx')
             with pd.ExcelWriter(paths['xlsx']) as writer:
-                for i, a in enumerate(env.agents):
+                for i, a in enumerate(agents):
                     pd.DataFrame(traj[i], columns=ANIMATION_COLUMNS).to_excel(writer, sheet_name='agent' + str(a.id))
         except ImportError:
             if xlsx:
                 raise
     paths['env_cfg'] = os.path.join(log_dir, 'env_cfg.json')
     with open(paths['env_cfg'], 'w') as f:
-        f.write(json.dumps(episode_info(env, total_policy_time_s), indent=4))
+        f.write(json.dumps(info, indent=4))
     return paths
 
 

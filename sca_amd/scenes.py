@@ -41,6 +41,20 @@ class _SceneKdTree:
         return list(v._batch.solver.get_kd_perm()[v._lo:v._hi] - v._lo)
 
 
+class _SceneLog:
+    """What sca_amd.metrics reads of an env's `.solver`: the trajectory log of ONE scene, in the scene's own agents (sca_scene_history_*)"""
+
+    def __init__(self, view):
+        self._view = view
+
+    def history_rows(self):
+        rows = self._view._batch.solver.scene_history_rows()
+        return int(rows['logged'][self._view.scene]), int(rows['dropped'][self._view.scene])
+
+    def history(self, first_row=0, nrows=None, agent_begin=0, agent_count=None):
+        return self._view._batch.solver.scene_history(self._view.scene, first_row, nrows, agent_begin, agent_count)
+
+
 class _Assigned:
     """agent.path = [...] after the batch was built: the batch uploads the lists in front of its next step"""
 
@@ -64,6 +78,7 @@ class SceneEnv:
         self._time_cum = [0.0]
         self._path_assigned = _Assigned(self)
         self.device_tracker = batch.device_tracker
+        self.solver = _SceneLog(self)                               # (metrics.trajectories / write_episode_log: needs SceneBatch(scene_history=rows))
 
     _stale = property(lambda self: self._batch._stale)
     _paths_on = property(lambda self: self._batch._paths_on)
@@ -99,7 +114,7 @@ class SceneEnv:
 
 
 class SceneBatch(_FlatAgents):
-    def __init__(self, scenes, obstacles=(), scene_obstacles=None, neighbor_mode=S.NBR_KDTREE, device_tracker=False, history_capacity=0, device=0):
+    def __init__(self, scenes, obstacles=(), scene_obstacles=None, neighbor_mode=S.NBR_KDTREE, device_tracker=False, history_capacity=0, scene_history=0, device=0):
         scenes = [list(a) for a in scenes]
         if not scenes or any(len(a) == 0 for a in scenes):
             raise ValueError('a SceneBatch needs at least one scene and no empty one')
@@ -136,6 +151,19 @@ class SceneBatch(_FlatAgents):
         self.steps = np.zeros(B, np.int32)                            # steps each scene has taken while it was live
         if history_capacity:
             self.solver.history_enable(int(history_capacity))
+        # scene_history: rows PER SCENE of the log per scene (metrics.trajectories(batch.env(s))); history_capacity above stays the
+        # context-wide log, a row per batch step.  64 B x rows x agents of HBM up front: capped to a budget, as MACAEnv caps its log
+        self.scene_history = int(scene_history)
+        self.history_budget_bytes = 64 << 30
+        n = len(flat)
+        if self.scene_history and 64 * self.scene_history * n > self.history_budget_bytes:
+            capped = max(1, self.history_budget_bytes // (64 * n))
+            import warnings
+            warnings.warn(f'scene_history {self.scene_history} x {n} agents x 64 B exceeds the {self.history_budget_bytes >> 30} GiB '
+                          f'budget: keeping the first {capped} steps of every scene (later steps are counted as dropped)')
+            self.scene_history = capped
+        if self.scene_history:
+            self.solver.scene_history_enable(self.scene_history)
 
     def __len__(self):
         return len(self._envs)
@@ -261,7 +289,7 @@ def next_episode(slot_size, pending_sizes):
     return None
 
 
-def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=None, max_steps=None, stats=None):
+def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=None, max_steps=None, stats=None, history_rows=0):
     """Streams a queue of episodes (Agent lists, each numbered 0 .. n - 1) through `slots` scenes of ONE SceneBatch: when a scene finishes,
     its metrics, step count and final state are taken and the slot restarts with the next episode of its size (SceneBatch.restart), while
     the other slots keep running.  Obstacles are one list shared by all episodes.  Returns one dict per episode in queue order:
@@ -269,7 +297,11 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
     called as each finishes.  With device_tracker, the tracker is enabled by the episodes the slots START with: a queue whose first tracked
     (SCA, RVO3D+Dubins) episode comes later is refused here, before the first step (ValueError).  An episode that a slot cannot take (SceneBatch.restart's
     rules: a path, other solver or planner attributes) raises when its turn comes.  The dict of an episode that max_steps cut short is None.  `stats`, a dict, receives batch_steps, agent_steps
-    (agents served, summed over the steps) and live_fraction (their mean share of the batch's agents per step)."""
+    (agents served, summed over the steps) and live_fraction (their mean share of the batch's agents per step).  history_rows=K keeps a trajectory
+    log of K rows per slot (SceneBatch(scene_history=K)): every result gains `trajectories` ([n, rows, 13], metrics.ANIMATION_COLUMNS, the
+    episode's first K steps at most), `rows_dropped` (its steps beyond K) and `info` (metrics.episode_info: with the trajectories, what
+    metrics.write_log_files writes an episode's folder from), read when the slot finishes, before it is refilled; an episode
+    longer than K does not stop the queue."""
     episodes = [list(e) for e in episodes]
     sizes = [len(e) for e in episodes]
     holding = plan_slots(sizes, slots)
@@ -279,7 +311,7 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
     if device_tracker and any(tracked[i] for i in pending) and not any(tracked[i] for i in holding):
         raise ValueError('run_episodes: episode %d needs the device tracker, but none of the episodes the slots start with does, so the batch '
                          'would run without one: put a tracked episode among the first %d' % (min(i for i in pending if tracked[i]), len(holding)))
-    batch = SceneBatch([episodes[i] for i in holding], obstacles, device_tracker=device_tracker)
+    batch = SceneBatch([episodes[i] for i in holding], obstacles, device_tracker=device_tracker, scene_history=history_rows)
     results = [None] * len(episodes)
     batch_steps = served = 0
     try:
@@ -294,6 +326,10 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
                 lo, hi = int(batch.offsets[s]), int(batch.offsets[s + 1])
                 results[i] = dict(episode=i, slot=s, metrics=metrics.episode_metrics(batch.env(s)), steps=int(batch.steps[s]),
                                   state={k: batch._state(k)[lo:hi].copy() for k in batch._mirror})
+                if batch.scene_history:
+                    view = batch.env(s)
+                    rows, dropped = view.solver.history_rows()
+                    results[i].update(trajectories=metrics.trajectories(view, rows=rows), rows_dropped=dropped, info=metrics.episode_info(view))
                 if on_done is not None:
                     on_done(results[i])
                 k = next_episode(sizes[i], [sizes[j] for j in pending])

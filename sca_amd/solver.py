@@ -247,6 +247,34 @@ class BatchedSolver:
         self._chk(self.L.sca_get_scene_state(self.ctx, _lib.ptr(out['active'], C.c_int32), _lib.ptr(out['steps'], C.c_int32)), 'sca_get_scene_state')
         return out
 
+    # ---- a trajectory log per scene (sca_scene_history_enable) -----------------------------------------------------------
+    def scene_history_enable(self, rows):
+        """`rows` per scene (0 frees the log).  Behind set_scenes / set_state, before the first step.  Row r of a scene is its r-th own step:
+        a finished scene gains no row, a restarted one starts over at row 0."""
+        self._chk(self.L.sca_scene_history_enable(self.ctx, int(rows)), 'sca_scene_history_enable')
+
+    def scene_history_rows(self):
+        """dict(logged [B] int32, dropped [B] int32): steps beyond the capacity are counted, never written"""
+        b = self.nscenes
+        out = dict(logged=np.zeros(b, np.int32), dropped=np.zeros(b, np.int32))
+        self._chk(self.L.sca_scene_history_rows(self.ctx, _lib.ptr(out['logged'], C.c_int32), _lib.ptr(out['dropped'], C.c_int32)), 'sca_scene_history_rows')
+        return out
+
+    def scene_history(self, scene, first_row=0, nrows=None, agent_begin=0, agent_count=None):
+        """Rows [first_row, first_row+nrows) of scene-local agents [agent_begin, +agent_count) of one scene: dict of [nrows, agents, 3] arrays."""
+        scene = int(scene)
+        inside = self.scene_offsets is not None and 0 <= scene < self.nscenes
+        if nrows is None:
+            nrows = int(self.scene_history_rows()['logged'][scene]) - first_row if inside else 0
+        if agent_count is None:
+            agent_count = int(self.scene_offsets[scene + 1] - self.scene_offsets[scene]) - agent_begin if inside else 0
+        shape = (max(0, int(nrows)), max(0, int(agent_count)), 3)                # (a window the library will refuse still gets arrays it could fill)
+        out = dict(pos=np.zeros(shape), heading=np.zeros(shape), vel=np.zeros(shape, np.float32))
+        self._chk(self.L.sca_get_scene_history(self.ctx, scene, int(first_row), int(nrows), int(agent_begin), int(agent_count),
+                                               _lib.ptr(out['pos'], C.c_double), _lib.ptr(out['heading'], C.c_double),
+                                               _lib.ptr(out['vel'], C.c_float)), 'sca_get_scene_history')
+        return out
+
     # ---- SCA's v_pref tracker on the device (scaPolicy.py:264-338) ---------------------------------------
     def device_tracker_enable(self, goal_heading, turning_radius=1.5, pitchlims=(-math.pi / 4, math.pi / 4), in_pass=True):
         """From now on the SCA / RVO3D+Dubins agents take v_pref from the device tracker: inside every policy pass

@@ -27,7 +27,16 @@ with the device tracker), legs
                       launch count.  Left out without --root.
     shared_set_here   the same with this checkout's library: should equal shared_set within the spread
     batch_root        scene_sets through the library of --root, as above.  Left out without --root.
-and the difference scene_sets - shared_set is the feature's cost (expected: two dependent loads per agent)."""
+and the difference scene_sets - shared_set is the feature's cost (expected: two dependent loads per agent).
+
+    python tools/bench/scenes_cost.py --log --scenes 16,256,1024                    # the log per scene, into profiles/scene_log_cost.json
+
+--log: what the trajectory log per scene (sca_scene_history_enable) costs.  The circle workloads above, legs
+    log_off           the batch without the log: what the parent commit ran -- held against the `batch` leg of profiles/scenes_cost.json, the
+                      parent's figure for the same shapes (entry `log_off_against_parent`: within the two spreads together, or the log-off path moved)
+    log_on            the same batch with a log of warm + window rows per scene: one more dispatch per step (k_scene_log), 64 B per live agent
+Both legs are this build's; every window starts from sca_set_scenes (new step counters: the log starts at row 0) and the start states.  Beside
+them the wall time of reading one scene's whole log back (sca_get_scene_history), next to a step of the same batch."""
 import argparse
 import importlib
 import importlib.util
@@ -203,6 +212,78 @@ def obstacle_workloads(args, S, scenarios, Sp, scp):
                 sol.close()
 
 
+def log_workloads(args, S, scenarios):
+    out = args.out if args.out_given else os.path.join(REPO, 'profiles', 'scene_log_cost.json')
+    try:
+        with open(os.path.join(REPO, 'profiles', 'scenes_cost.json')) as f:
+            parent = json.load(f)['workloads']
+    except (OSError, ValueError, KeyError):
+        parent = {}
+    sc = scenarios.circle(SCENE_AGENTS)
+    rows_cap = args.warm + args.window
+    for policy in [p for p in args.policy.split(',') if p]:
+        for B in [int(x) for x in args.scenes.split(',') if x]:
+            legs = {}
+            off = np.arange(B + 1, dtype=np.int32) * SCENE_AGENTS
+            for leg, on in (('log_off', False), ('log_on', True)):
+                sol, reset_state = make_context(S, scenarios, sc, B, policy, True)
+
+                def reset(sol=sol, reset_state=reset_state, on=on):
+                    sol.set_scenes(off)                               # new step counters (sca_set_state leaves them alone); frees the log
+                    if on:
+                        sol.scene_history_enable(rows_cap)
+                    reset_state()
+                legs[leg] = ([sol], [reset])
+            rows = time_legs(legs, args, S.NBR_KDTREE)
+            states = {leg: sols[0].get_state() for leg, (sols, _) in legs.items()}     # the log changes no value
+            for key in states['log_off']:
+                assert np.array_equal(states['log_on'][key], states['log_off'][key]), key
+            on_sol = legs['log_on'][0][0]
+            logged = on_sol.scene_history_rows()
+            assert not logged['dropped'].any()
+            # one scene's whole log back to the host, beside a step of this batch
+            reads = []
+            for _ in range(20):
+                t0 = time.perf_counter()
+                h = on_sol.scene_history(B // 2)
+                reads.append(time.perf_counter() - t0)
+            a, b = rows['log_on'], rows['log_off']
+            margin = (a['spread_ms'][1] - a['spread_ms'][0]) + (b['spread_ms'][1] - b['spread_ms'][0])
+            n = B * SCENE_AGENTS
+            entry = {'workload': '%d x circle of %d, %s' % (B, SCENE_AGENTS, 'SCA + device tracker' if policy == 'sca' else 'ORCA3D'),
+                     'scenes': B, 'agents': n, 'warm_steps': args.warm, 'window_steps': args.window, 'alternations': args.alternations, 'legs': rows,
+                     'log_rows_per_scene': rows_cap, 'log_bytes': 64 * rows_cap * n,
+                     'cost': {'log_on_minus_log_off_us': 1e3 * (a['ms_per_step'] - b['ms_per_step']), 'ratio_log_on_over_log_off': a['ms_per_step'] / b['ms_per_step'],
+                              'sum_of_spreads_us': 1e3 * margin, 'within_the_spreads': bool(abs(a['ms_per_step'] - b['ms_per_step']) <= margin),
+                              'bytes_per_step': 64 * n},
+                     'readback_one_scene': {'rows': int(h['pos'].shape[0]), 'agents': int(h['pos'].shape[1]), 'bytes': 64 * int(h['pos'].shape[0]) * int(h['pos'].shape[1]),
+                                            'median_ms': float(np.median(reads)) * 1e3, 'min_ms': float(min(reads)) * 1e3,
+                                            'note': 'sca_scene_history_rows + sca_get_scene_history + the unpack into three numpy arrays'}}
+            p = parent.get('%s_x%d' % (policy, B), {}).get('legs', {}).get('batch')
+            if p is not None:
+                m2 = (p['spread_ms'][1] - p['spread_ms'][0]) + (b['spread_ms'][1] - b['spread_ms'][0])
+                entry['log_off_against_parent'] = {'parent_batch_ms': p['ms_per_step'], 'parent_spread_ms': p['spread_ms'], 'log_off_minus_parent_ms': b['ms_per_step'] - p['ms_per_step'],
+                                                   'sum_of_spreads_ms': m2, 'within_the_spreads': bool(abs(b['ms_per_step'] - p['ms_per_step']) <= m2)}
+            try:
+                with open(out) as f:
+                    doc = json.load(f)
+            except (OSError, ValueError):
+                doc = {'tool': 'tools/bench/scenes_cost.py --log', 'unit': 'ms per step of all B scenes; median_ms: the median step time of each window', 'workloads': {}}
+            doc['host'] = host()
+            doc['workloads']['%s_x%d' % (policy, B)] = entry
+            os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+            with open(out, 'w') as f:
+                json.dump(doc, f, indent=1, sort_keys=True)
+                f.write('\n')
+            for leg, r in rows.items():
+                print('%-5s B=%-5d %-16s %9.4f ms/step  spread %.4f .. %.4f  active at end %s' % (policy, B, leg, r['ms_per_step'], r['spread_ms'][0],
+                                                                                                r['spread_ms'][1], r['active_at_end'][-1]), flush=True)
+            print(policy, B, json.dumps(entry['cost']), json.dumps(entry['readback_one_scene']), json.dumps(entry.get('log_off_against_parent')), flush=True)
+            for sols, _ in legs.values():
+                for sol in sols:
+                    sol.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--scenes', default='1,16,256,1024')
@@ -214,6 +295,7 @@ def main():
     ap.add_argument('--out', default=None, help='default: profiles/scenes_cost.json (profiles/scene_obstacles_cost.json with --obstacles)')
     ap.add_argument('--batch-only', action='store_true', help='without the one_by_one legs: the batch against batch_root alone (needs --root)')
     ap.add_argument('--obstacles', action='store_true', help='the per-scene obstacle sets against one shared set, instead of the batch against B contexts')
+    ap.add_argument('--log', action='store_true', help='the trajectory log per scene off and on in this build, into profiles/scene_log_cost.json')
     args = ap.parse_args()
     args.out_given = args.out is not None
     if not args.out_given:
@@ -229,6 +311,8 @@ def main():
         assert Sp._lib._build.LIB != S._lib._build.LIB
     if args.obstacles:
         return obstacle_workloads(args, S, scenarios, Sp, scp)
+    if args.log:
+        return log_workloads(args, S, scenarios)
     KD = S.NBR_KDTREE
     sc = scenarios.circle(SCENE_AGENTS)
 
