@@ -10,6 +10,9 @@ one metrics row per scene -- what a loop over the reference's run_example/run_*.
                                                        # (scenes.run_episodes): a slot that finishes restarts with the next episode
     python examples/run_scenes.py --seeds 2 --slots 8 --log-dir out    # ... and one folder per episode under out/: env_cfg.json + trajs.npz, what
                                                        # run_example/run_*.py write (the log per scene, SceneBatch(scene_history=...))
+    python examples/run_scenes.py --sizes 20,50,100 --slots 16 --capacity max   # the scenarios at several drone counts through ONE queue: every
+                                                       # slot holds up to the largest count and takes the next episode that fits
+                                                       # (without --capacity a slot keeps its size: one slot at least per count)
 """
 import argparse
 import os
@@ -36,19 +39,32 @@ def main():
     ap.add_argument('--max-steps', type=int, default=20000)
     ap.add_argument('--obstacles', action='store_true', help='add a take-off/landing scene with its 8 spheres per policy (one obstacle list per scene)')
     ap.add_argument('--slots', type=int, default=0, help='stream the table through this many slots instead of holding it as one batch')
+    ap.add_argument('--sizes', default=None, help='drone counts, e.g. 20,50,100: every scenario at each of them (instead of --agents)')
+    ap.add_argument('--capacity', default=None, help="with --slots: 'max' makes every slot hold up to the largest episode, so a slot takes any "
+                                                     'episode of the queue; a number is the capacity of every slot')
     ap.add_argument('--log-dir', default=None, help='write one folder per episode here: env_cfg.json + trajs.npz (the first --max-steps steps of each)')
     args = ap.parse_args()
     if args.slots and args.obstacles:
         ap.error('--slots streams episodes that share one obstacle list: not with --obstacles')
 
+    if args.capacity and not args.slots:
+        ap.error('--capacity is about the slots of a streamed queue: give --slots')
+    counts = [int(v) for v in args.sizes.split(',')] if args.sizes else [args.agents]
+    many = len(counts) > 1
+    if many and not args.slots:
+        ap.error('--sizes with several counts streams one queue: give --slots (and --capacity max)')
+    capacities = None if not args.capacity else 'max' if args.capacity == 'max' else [int(args.capacity)] * args.slots
+
     names, scenes, obstacles = [], [], []
     for pname, pol in POLICIES.items():
-        names.append((pname, 'circle'))
-        scenes.append(build_agents(scenarios.circle(args.agents), pol))
-        for seed in range(args.seeds):
-            names.append((pname, 'random seed %d' % seed))
-            scenes.append(build_agents(scenarios.random_cube(args.agents, seed=seed), pol))
-        obstacles += [[] for _ in range(1 + args.seeds)]
+        for n in counts:
+            tag = ' x%d' % n if many else ''
+            names.append((pname, 'circle' + tag))
+            scenes.append(build_agents(scenarios.circle(n), pol))
+            for seed in range(args.seeds):
+                names.append((pname, 'random seed %d' % seed + tag))
+                scenes.append(build_agents(scenarios.random_cube(n, seed=seed), pol))
+            obstacles += [[] for _ in range(1 + args.seeds)]
         if args.obstacles:
             sc = scenarios.takeoff_landing(16)
             names.append((pname, 'take-off'))
@@ -63,14 +79,14 @@ def main():
 
         def row(r):
             pname, what = names[r['episode']]
-            print('%-10s %-14s slot %3d steps %5d  ' % (pname, what, r['slot'], r['steps']) +
+            print('%-10s %-20s slot %3d steps %5d  ' % (pname, what, r['slot'], r['steps']) +
                   '  '.join('%s %.4g' % (k, r['metrics'][k]) for k in ('SuccessRate', 'ExtraTime', 'ExtraDistance', 'AverageSpeed')), flush=True)
             if args.log_dir:
                 metrics.write_log_files(folder(r['episode']), scenes[r['episode']], r['trajectories'], r['info'], xlsx=False)
                 if r['rows_dropped']:
                     print('    (the log holds the first %d steps: %d more did not fit --max-steps rows)' % (r['trajectories'].shape[1], r['rows_dropped']))
         run_episodes(scenes, args.slots, device_tracker=True, on_done=row, max_steps=args.max_steps, stats=stats,
-                     history_rows=args.max_steps if args.log_dir else 0)
+                     history_rows=args.max_steps if args.log_dir else 0, capacities=capacities)
         print('%d episodes through %d slots: %d batch steps, mean live fraction %.2f, %.2f s' %
               (len(scenes), args.slots, stats['batch_steps'], stats['live_fraction'], time.time() - t0))
         return

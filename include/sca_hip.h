@@ -236,6 +236,41 @@ int sca_restart_scenes(sca_ctx *ctx, int count, const int32_t *scene_ids /*count
                        const uint8_t *zaxis, const double *max_run_dist,      /* each T, each nullable: keep the slot's */
                        const double *goal_heading /*T*3, nullable: keep the slot's*/);
 
+/* Slots of a capacity: a scene's range [offsets[s], offsets[s+1]) is its CAPACITY, and the scene holds size[s] agents, 1 <= size[s] <=
+ * capacity, in the first size[s] rows of the range; the rows behind them are VACANT.  So a slot takes any episode that fits it, and a queue
+ * that mixes 14-, 50- and 100-agent episodes streams through one set of slots.  The scene contract extends: a slot that holds an n-agent
+ * episode is bit for bit what a context holding that episode alone is (state, float32 action rows, neighbour lists and their distSq,
+ * diagnostics, the scene-local permutation, tracker records and re-plan counts, the rows of the log per scene), and no other scene can
+ * tell.  Detect the feature by the symbol (sca_version() is unchanged).
+ *   sca_restart_scenes_sized  sca_restart_scenes with sizes[b] rows for scene scene_ids[b]: T is the sum of the sizes, the arrays are packed in
+ *              the order of scene_ids.  sizes == NULL: every named scene is filled to its capacity -- the call is then exactly
+ *              sca_restart_scenes (which, on a scene that holds fewer agents, fills it to its capacity too).  A slot may shrink or grow from
+ *              one restart to the next, whether it is finished or live.  Same cost: one kernel launch and one synchronisation however many
+ *              scenes are named.  Refusals: sca_restart_scenes', each with its code, and SCA_ERR_ARG for a size < 1 or above the slot's
+ *              capacity (the message names the entry).  A refused call has changed nothing.
+ *   sca_get_scene_sizes       size[s] of every scene.  sca_set_scenes sets every size to its capacity; sca_set_agents and
+ *              sca_set_scenes(0, NULL) drop the sizes with the scenes.  SCA_ERR_STATE without scenes.  A context that never calls the sized
+ *              restart has every scene full and behaves, and enqueues, exactly as before.
+ *   vacant rows   belong to the library.  The read-backs over the whole range (sca_get_state, sca_get_kd_perm, sca_get_actions,
+ *              sca_get_neighbors, sca_get_diag) still cover them: a vacant row reads flags SCA at-goal | collision (3), zero velocity, zero
+ *              heading, zero total_dist and step_num, the position and radius of whoever stood there last, a zero action row, an empty
+ *              neighbour list, the diagnostics of a done agent (-1), and the identity in the permutation (perm[a] == a; the occupied
+ *              rows are a permutation of [offsets[s], offsets[s] + size[s])).  They stay exactly so from one restart to the next: a vacant
+ *              row is in no tree, no neighbour or near list, no collision test, no tracker list and not in the ORCA3D-LP list, and is never
+ *              counted in active[s] or by sca_active_count.  It keeps its per-agent attributes (sca_set_agent_params, tracker
+ *              attributes) and constants for the episode that occupies it next.
+ *   refused meanwhile   while ANY scene is below its capacity, the entry points that take a whole-context state from outside return
+ *              SCA_ERR_UNSUPPORTED and change nothing: sca_set_state, sca_set_kd_perm, and sca_step_host with its host state block (whose
+ *              rows cannot say which are vacant).  They work again once every slot is filled to its capacity.
+ *   the log per scene   keeps its layout (pitch = capacity, so a full slot reads as before); sca_get_scene_history bounds the agent window by
+ *              the scene's current size (SCA_ERR_ARG beyond it): vacant rows are never reported. */
+int sca_restart_scenes_sized(sca_ctx *ctx, int count, const int32_t *scene_ids /*count*/, const int32_t *sizes /*count, nullable: capacities*/,
+                             const double *pos /*T*3*/, const float *vel /*T*3, nullable: zero*/, const double *heading /*T*3*/,
+                             const double *radius, const double *pref_speed, const double *goal /*T*3*/, const uint8_t *policy,
+                             const uint8_t *zaxis, const double *max_run_dist,      /* each T, each nullable: keep the slot's */
+                             const double *goal_heading /*T*3, nullable: keep the slot's*/);
+int sca_get_scene_sizes(sca_ctx *ctx, int32_t *size /*nscenes*/);
+
 /* A trajectory log per scene = every episode's Agent.history_info.  Row r of scene s is the scene's r-th own step (r = steps[s] - 1 while
  * that step runs), written only for steps the scene was live at their beginning, so a finished scene gains no row while the others run on,
  * and the log starts over at row 0 when the scene is restarted.  For every scene the rows are bit for bit the rows sca_get_history gives

@@ -55,6 +55,8 @@ SIGNATURES = {
     'sca_get_scene_state': (C.c_int, [C.c_void_p, ip, ip]),
     'sca_set_scene_obstacles': (C.c_int, [C.c_void_p, C.c_int, ip, dp, dp]),
     'sca_restart_scenes': (C.c_int, [C.c_void_p, C.c_int, ip, dp, fp, dp, dp, dp, dp, bp, bp, dp, dp]),
+    'sca_restart_scenes_sized': (C.c_int, [C.c_void_p, C.c_int, ip, ip, dp, fp, dp, dp, dp, dp, bp, bp, dp, dp]),
+    'sca_get_scene_sizes': (C.c_int, [C.c_void_p, ip]),
     'sca_scene_history_enable': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_scene_history_rows': (C.c_int, [C.c_void_p, ip, ip]),
     'sca_get_scene_history': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, fp]),

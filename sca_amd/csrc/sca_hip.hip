@@ -301,6 +301,9 @@ struct sca_ctx {
         SceneView v{};                  // device arrays; live | prev | steps are one allocation (counters)
         int32_t *counters = nullptr;    // [nscenes * (SCENE_LINE + 2)]
         std::vector<int32_t> h_off;     // [nscenes + 1] the offsets as set
+        int32_t *size = nullptr;        // device [nscenes]: the agents a scene holds in the first rows of its range (k_kd_scene_jobs, k_scene_restart_sized)
+        std::vector<int32_t> h_size;    // ... and the host's copy; the range's length until sca_restart_scenes_sized says otherwise
+        bool partial = false;           // scenes_any_partial(h_size): a whole-context state from outside is refused meanwhile
         int largest = 0;                // agents of the largest scene: picks the k_kd_block instance
         bool live_valid = false;        // SceneView::live describes the current records (else: k_scene_recount before anybody reads it)
         bool begun = false;             // a policy pass has opened a step (scene_begin_one) that no env update has closed yet
@@ -310,9 +313,9 @@ struct sca_ctx {
         uint8_t *rs_host = nullptr;     // sca_restart_scenes' page-locked staging block (RestartLayout of max_n, sca_scenes.h), allocated on first use
         SceneLogView log{};             // the trajectory log per scene (sca_scene_history_enable), rows null: off -- a step then enqueues nothing for it
         void release() {                // the device and page-locked allocations, behind a synchronised stream; the flags and host vectors stay
-            for (void *p : {(void *)v.scene_of, (void *)v.offsets, (void *)counters, (void *)v.heading_keep, (void *)ov.oroot, (void *)log.rows}) if (p) (void)hipFree(p);
+            for (void *p : {(void *)v.scene_of, (void *)v.offsets, (void *)counters, (void *)v.heading_keep, (void *)ov.oroot, (void *)log.rows, (void *)size}) if (p) (void)hipFree(p);
             if (rs_host) (void)hipHostFree(rs_host);
-            v = SceneView{}; counters = nullptr; ov = SceneObsView{}; rs_host = nullptr; log = SceneLogView{};
+            v = SceneView{}; counters = nullptr; size = nullptr; ov = SceneObsView{}; rs_host = nullptr; log = SceneLogView{};
         }
     } scenes;
     std::vector<uint8_t> h_policy;      // [n] the agents' policies as they stand (sca_set_agents, sca_restart_scenes)
@@ -1047,6 +1050,13 @@ int sca_set_agent_params(sca_ctx *c, int n, const double *neighbor_dist, const i
 }
 
 static int scenes_clear(sca_ctx *c);
+// a whole-context state from outside while a scene is below its capacity (sca_restart_scenes_sized): the vacant rows are the library's
+static int scenes_refuse_partial(sca_ctx *c, const char *who) {
+    if (!c->scenes.on || !c->scenes.partial) return 0;
+    c->err = std::string(who) + ": a scene holds fewer agents than its capacity (sca_restart_scenes_sized) -- the rows behind them are vacant, and a state "
+             "for the whole range cannot say so; fill every slot to its capacity first";
+    return SCA_ERR_UNSUPPORTED;
+}
 int sca_set_agents(sca_ctx *c, int n, const double *radius, const double *pref_speed, const double *goal,
                    const uint8_t *policy, const uint8_t *zaxis, const double *max_run_dist) {
     API_ENTER(c);
@@ -1103,6 +1113,7 @@ int sca_set_state(sca_ctx *c, const double *pos, const float *vel, const double 
     API_ENTER(c);
     if (!c->agents_set) { c->err = "sca_set_agents first"; return SCA_ERR_STATE; }
     ARG(c, pos && vel && heading && flags);
+    if (int r = scenes_refuse_partial(c, "sca_set_state")) return r;
     const int n = c->n;
     for (int i = 0; i < n; i++) {
         PubRec &r = c->h_rec[i];
@@ -1155,6 +1166,7 @@ int sca_get_state(sca_ctx *c, double *pos, float *vel, double *heading, uint8_t 
 int sca_set_kd_perm(sca_ctx *c, const int32_t *perm) {
     API_ENTER(c);
     ARG(c, perm && c->agents_set);
+    if (int r = scenes_refuse_partial(c, "sca_set_kd_perm")) return r;
     if (c->scenes.on) {
         const int at = scenes_perm_fault(c->scenes.v.nscenes, c->scenes.h_off.data(), perm);
         if (at >= 0) {
@@ -1353,6 +1365,7 @@ static int scenes_clear(sca_ctx *c) {
     CHK(c, hipStreamSynchronize(c->stream));
     c->scenes.on = false;
     c->scenes.h_off.clear();
+    c->scenes.h_size.clear(); c->scenes.partial = false;
     c->scenes.largest = 0; c->scenes.live_valid = false; c->scenes.begun = false;
     return 0;
 }
@@ -1389,13 +1402,18 @@ int sca_set_scenes(sca_ctx *c, int nscenes, const int32_t *offsets) {
     c->scenes.v.live = c->scenes.counters; c->scenes.v.prev = c->scenes.counters + (size_t)nscenes * SCENE_LINE; c->scenes.v.steps = c->scenes.v.prev + nscenes;
     c->scenes.v.nscenes = nscenes;
     CHK(c, hipMalloc((void **)&c->scenes.v.heading_keep, sizeof(double) * 3 * (size_t)n));       // (written by k_scene_recount before any step reads it)
+    CHK(c, hipMalloc((void **)&c->scenes.size, sizeof(int32_t) * (size_t)nscenes));
+    std::vector<int32_t> full((size_t)nscenes);                      // every scene starts filled to its capacity
+    for (int sc = 0; sc < nscenes; sc++) full[sc] = offsets[sc + 1] - offsets[sc];
     std::vector<int32_t> of((size_t)n);
     for (int sc = 0; sc < nscenes; sc++) for (int a = offsets[sc]; a < offsets[sc + 1]; a++) of[a] = sc;
     CHK(c, hipMemcpyAsync(so, of.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     CHK(c, hipMemcpyAsync(off, offsets, sizeof(int32_t) * ((size_t)nscenes + 1), hipMemcpyHostToDevice, c->stream));
     CHK(c, hipMemsetAsync(c->scenes.counters, 0, sizeof(int32_t) * words, c->stream));
+    CHK(c, hipMemcpyAsync(c->scenes.size, full.data(), sizeof(int32_t) * (size_t)nscenes, hipMemcpyHostToDevice, c->stream));
     CHK(c, hipStreamSynchronize(c->stream));
     c->scenes.h_off.assign(offsets, offsets + nscenes + 1);
+    c->scenes.h_size.swap(full); c->scenes.partial = false;
     c->scenes.largest = k.largest;
     for (int i = 0; i < n; i++) c->h_perm[i] = i;                     // every scene's kdTree.agentIDs starts as 0 .. n_s - 1 (kdTree.py:43-45)
     c->perm_on_device = false;
@@ -1496,11 +1514,15 @@ int sca_get_scene_state(sca_ctx *c, int32_t *active, int32_t *steps) {
 // the link and writes every per-agent array of the named scenes, and the call's one synchronisation follows that launch: the block may be
 // written again when the call returns.  Nothing context-wide is reset -- see DESIGN.md section 5 for trk.parity, trk_passes, kd_single_hint
 // and state_fresh.
-int sca_restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const double *pos, const float *vel, const double *heading,
-                       const double *radius, const double *pref_speed, const double *goal, const uint8_t *policy, const uint8_t *zaxis,
-                       const double *max_run_dist, const double *goal_heading) {
-    API_ENTER(c);
-    const RestartArgs A{count, scene_ids, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading};
+// sizes (sca_restart_scenes_sized): the rows each named scene brings, NULL: its capacity.  A call that leaves every scene of the context
+// full -- every call of a context that never uses sizes -- launches k_scene_restart, as before; as soon as a named scene is or becomes
+// partial it is k_scene_restart_sized, which also vacates the rows behind the episode and writes the device's size[s].  Either way one
+// launch and one synchronisation.
+static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const int32_t *sizes, const double *pos, const float *vel, const double *heading,
+                          const double *radius, const double *pref_speed, const double *goal, const uint8_t *policy, const uint8_t *zaxis,
+                          const double *max_run_dist, const double *goal_heading) {
+    RestartArgs A{count, scene_ids, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading};
+    A.sizes = sizes;
     const RestartCtx X{c->scenes.on ? c->scenes.v.nscenes : 0, c->scenes.on ? c->scenes.h_off.data() : nullptr, c->state_set, c->scenes.begun, c->trk_on,
                        c->paths_on, c->trk_on && c->trk_view.R_pa != nullptr, c->h_policy.data()};
     const RestartCheck k = scene_restart_check(X, A);
@@ -1518,6 +1540,8 @@ int sca_restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const do
         case RESTART_BAD_POLICY: c->err = "sca_restart_scenes: row " + at + " has a policy above SCA_POLICY_RVO3D_DUBINS"; break;
         case RESTART_NOT_POSITIVE: c->err = "sca_restart_scenes: row " + at + " has a radius, pref_speed or max_run_dist that is not positive"; break;
         case RESTART_GOAL_HEADING: c->err = "sca_restart_scenes: goal_heading without a device tracker (sca_device_tracker_enable)"; break;
+        case RESTART_BAD_SIZE: c->err = "sca_restart_scenes_sized: sizes[" + at + "] = " + std::to_string(sizes[k.entry]) + ": scene " + std::to_string(scene_ids[k.entry]) + " holds 1 .. " +
+                                        std::to_string(c->scenes.h_off[scene_ids[k.entry] + 1] - c->scenes.h_off[scene_ids[k.entry]]) + " agents (its capacity)"; break;
         case RESTART_PATHS: c->err = "sca_restart_scenes with waypoint lists set (sca_set_paths): the lists are one block, replacing a scene's lists is not available"; break;
         default: c->err = "sca_restart_scenes: row " + at + " changes an agent between a tracked and an untracked policy while per-agent tracker attributes are set "
                           "(sca_device_tracker_set_agent_params): the tracker's classes are cut by policy";
@@ -1526,18 +1550,23 @@ int sca_restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const do
     }
     const int T = k.total;
     const RestartLayout L = scene_restart_layout(c->max_n);
+    const size_t blk_bytes = (size_t)L.total + sizeof(int32_t) * (size_t)c->max_n;  // behind the layout's sections: the named scenes' new sizes
     if (!c->scenes.rs_host) {                                                    // mapped and coherent, as the host state block is: the kernel reads it in place
-        CHK(c, hipHostMalloc((void **)&c->scenes.rs_host, (size_t)L.total, hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(c->scenes.rs_host, 0, (size_t)L.total);
+        CHK(c, hipHostMalloc((void **)&c->scenes.rs_host, blk_bytes, hipHostMallocMapped | hipHostMallocCoherent));
+        std::memset(c->scenes.rs_host, 0, blk_bytes);
     }
     uint8_t *b = c->scenes.rs_host;
-    int32_t *ids = (int32_t *)(b + L.off[RS_IDS]), *start = (int32_t *)(b + L.off[RS_START]);
+    int32_t *ids = (int32_t *)(b + L.off[RS_IDS]), *start = (int32_t *)(b + L.off[RS_START]), *new_size = (int32_t *)(b + L.total);
     uint8_t *pol = b + L.off[RS_POLICY], *mode = b + L.off[RS_VPREF_MODE];
-    bool policy_changed = false;
-    for (int e = 0, r = 0; e < count; e++) {
-        const int lo = c->scenes.h_off[scene_ids[e]], hi = c->scenes.h_off[scene_ids[e] + 1];
-        ids[e] = scene_ids[e]; start[e] = r;
-        for (int a = lo; a < hi; a++, r++) {
+    const int32_t *off = c->scenes.h_off.data();
+    scene_restart_starts(count, off, scene_ids, sizes, start);
+    bool policy_changed = false, size_changed = false, sized = c->scenes.partial;
+    for (int e = 0; e < count; e++) {
+        const int lo = off[scene_ids[e]], ns = scene_restart_rows(off, scene_ids, sizes, e);
+        ids[e] = scene_ids[e]; new_size[e] = ns;
+        size_changed = size_changed || ns != c->scenes.h_size[scene_ids[e]];
+        sized = sized || ns != off[scene_ids[e] + 1] - lo;
+        for (int a = lo, r = start[e]; a < lo + ns; a++, r++) {
             const uint8_t p = policy ? policy[r] : c->h_policy[a];
             policy_changed = policy_changed || p != c->h_policy[a];
             pol[r] = p;
@@ -1567,14 +1596,18 @@ int sca_restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const do
         d.trk_nbr0 = c->trk.nbr0; d.trk_goal_heading = c->trk_goal_heading;
         d.trk_st = (restart_u32 *)c->trk.st; d.trk_init = (const restart_u32 *)c->trk_init; d.trk_words = (int)(sizeof(sca_dubins::AgentTrack) / 4);
     }
-    hipLaunchKernelGGL(k_scene_restart, dim3(count), dim3(RESTART_T), 0, c->stream, d, (const uint8_t *)b, L, has);
+    if (sized) hipLaunchKernelGGL(k_scene_restart_sized, dim3(count), dim3(RESTART_T), 0, c->stream, d, (const uint8_t *)b, L, has, (const int32_t *)new_size, c->scenes.size);
+    else hipLaunchKernelGGL(k_scene_restart, dim3(count), dim3(RESTART_T), 0, c->stream, d, (const uint8_t *)b, L, has);
     CHK(c, hipGetLastError());
     std::vector<int32_t> lp_new;                                       // K3's list: the ORCA3D-LP agents, ascending ids (the block holds the named scenes' policies)
-    if (policy_changed) {
+    std::vector<int32_t> size_now = c->scenes.h_size;                  // ... of the rows that are occupied: a vacant row keeps its policy and is in no list
+    for (int e = 0; e < count; e++) size_now[scene_ids[e]] = new_size[e];
+    if (policy_changed || size_changed) {
         std::vector<uint8_t> now = c->h_policy;
         for (int e = 0; e < count; e++)
-            for (int a = c->scenes.h_off[scene_ids[e]], r = start[e]; a < c->scenes.h_off[scene_ids[e] + 1]; a++, r++) now[a] = pol[r];
-        for (int i = 0; i < c->n; i++) if (now[i] == SCA_POLICY_ORCA3D_LP) lp_new.push_back(i);
+            for (int a = off[scene_ids[e]], r = start[e]; a < off[scene_ids[e]] + new_size[e]; a++, r++) now[a] = pol[r];
+        for (int sc = 0; sc < c->scenes.v.nscenes; sc++)
+            for (int i = off[sc]; i < off[sc] + size_now[sc]; i++) if (now[i] == SCA_POLICY_ORCA3D_LP) lp_new.push_back(i);
         if (!lp_new.empty())
             CHK(c, hipMemcpyAsync(c->lp_list, lp_new.data(), sizeof(int32_t) * lp_new.size(), hipMemcpyHostToDevice, c->stream));
     }
@@ -1584,18 +1617,40 @@ int sca_restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const do
     // changes nothing" is about the refusals above.  A runtime error of the list copy or the synchronisation behind the launch is not one: the
     // device may then hold the new episode while h_policy, h_rec and h_perm hold the old -- as after any failed HIP call, the context is to
     // be set up again (sca_set_agents), not stepped on.
-    for (int e = 0; e < count; e++)
-        for (int a = c->scenes.h_off[scene_ids[e]], r = start[e]; a < c->scenes.h_off[scene_ids[e] + 1]; a++, r++) {
+    for (int e = 0; e < count; e++) {
+        for (int a = off[scene_ids[e]], r = start[e]; a < off[scene_ids[e]] + new_size[e]; a++, r++) {
             c->h_policy[a] = pol[r];
             if (radius) { c->h_rec[a].radius = radius[r]; c->max_radius = std::max(c->max_radius, radius[r]); }
             if (pref_speed) c->max_pref_speed = std::max(c->max_pref_speed, pref_speed[r]);
-            c->h_perm[a] = a;
         }
-    if (policy_changed) c->h_lp_list.swap(lp_new);
+        for (int a = off[scene_ids[e]]; a < off[scene_ids[e] + 1]; a++) c->h_perm[a] = a;        // (the vacant rows' too: the identity over the capacity)
+    }
+    if (policy_changed || size_changed) c->h_lp_list.swap(lp_new);
+    c->scenes.h_size.swap(size_now);
+    c->scenes.partial = scenes_any_partial(c->scenes.v.nscenes, off, c->scenes.h_size.data());
     c->h_pos_valid = false;                                            // (no host mirror of the positions is kept, as in sca_step_host)
     c->near_valid = false;
     // (scene_live_valid stays what it is: the kernel wrote the named scenes' counters itself, and where the others' are stale the recount
     // that is due anyway finds n_s live agents in a restarted scene too)
+    return 0;
+}
+int sca_restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const double *pos, const float *vel, const double *heading,
+                       const double *radius, const double *pref_speed, const double *goal, const uint8_t *policy, const uint8_t *zaxis,
+                       const double *max_run_dist, const double *goal_heading) {
+    API_ENTER(c);
+    return restart_scenes(c, count, scene_ids, nullptr, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading);
+}
+int sca_restart_scenes_sized(sca_ctx *c, int count, const int32_t *scene_ids, const int32_t *sizes, const double *pos, const float *vel,
+                             const double *heading, const double *radius, const double *pref_speed, const double *goal, const uint8_t *policy,
+                             const uint8_t *zaxis, const double *max_run_dist, const double *goal_heading) {
+    API_ENTER(c);
+    return restart_scenes(c, count, scene_ids, sizes, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading);
+}
+int sca_get_scene_sizes(sca_ctx *c, int32_t *size) {
+    API_ENTER(c);
+    ARG(c, size);
+    if (!c->scenes.on) { c->err = "no scenes (sca_set_scenes)"; return SCA_ERR_STATE; }
+    std::memcpy(size, c->scenes.h_size.data(), sizeof(int32_t) * c->scenes.h_size.size());
     return 0;
 }
 
@@ -1671,7 +1726,7 @@ static int build_agent_tree_device(sca_ctx *c, hipStream_t ks, const DeviceView 
     } else hipLaunchKernelGGL(k_kd_gather, dim3((n + 255) / 256), dim3(256), 0, ks, d, c->kd, c->P);
     if (c->scenes.on) {
         // the forest's job table behind the gather (which rewrites the single root job and the counts on every build); opens the step
-        hipLaunchKernelGGL(k_kd_scene_jobs, dim3((c->scenes.v.nscenes + 255) / 256), dim3(256), 0, ks, c->kd, c->scenes.v, c->scenes.begun ? 0 : 1);
+        hipLaunchKernelGGL(k_kd_scene_jobs, dim3((c->scenes.v.nscenes + 255) / 256), dim3(256), 0, ks, c->kd, c->scenes.v, (const int32_t *)c->scenes.size, c->scenes.begun ? 0 : 1);
         c->scenes.begun = true;
     }
     if (B.top && B.levels) hipLaunchKernelGGL(k_kd_top, dim3(1), dim3(KT_T), 0, ks, d, c->kd);
@@ -2443,6 +2498,7 @@ int sca_step_host(sca_ctx *c, int neighbor_mode, uint32_t in_mask, int *active) 
     if (c->comm) { c->err = "sca_step_host with an active communicator: the block is the whole swarm's state on one rank (sca_comm_destroy first)"; return SCA_ERR_UNSUPPORTED; }
     if (c->part_on) { c->err = "sca_step_host under the cell-owner partition: the block is the whole swarm's state on one rank (sca_partition_disable first)"; return SCA_ERR_UNSUPPORTED; }
     if (c->d.shard_count < c->n) { c->err = "sca_step_host on a shard (sca_set_shard with count < n): the block is the whole swarm's state on one rank"; return SCA_ERR_STATE; }
+    if (int r = scenes_refuse_partial(c, "sca_step_host")) return r;
     if (!(in_mask & SCA_HOST_IN_STATE) && !c->state_set) { c->err = "sca_step_host: no state yet -- write the block and pass SCA_HOST_IN_STATE (or sca_set_state first)"; return SCA_ERR_STATE; }
     if (in_mask && !c->hs_host) { c->err = "sca_step_host: sca_host_state_get first -- nothing can have been written to a block nobody has fetched"; return SCA_ERR_STATE; }
     if (int r = host_block_alloc(c)) return r;
@@ -3019,7 +3075,7 @@ static int scene_log_refuse(sca_ctx *c, const char *who, const SceneLogCheck &k)
     case SCENE_LOG_BAD_CAPACITY: c->err = std::string(who) + ": capacity_rows must not be negative"; break;
     case SCENE_LOG_BAD_SCENE: c->err = std::string(who) + ": scene " + std::to_string(k.scene) + " is not a scene of this context (0 .. " + std::to_string(c->scenes.v.nscenes - 1) + ")"; break;
     case SCENE_LOG_BAD_ROWS: c->err = std::string(who) + ": row window outside the rows scene " + std::to_string(k.scene) + " has logged"; break;
-    default: c->err = std::string(who) + ": agent window outside scene " + std::to_string(k.scene);
+    default: c->err = std::string(who) + ": agent window outside the agents scene " + std::to_string(k.scene) + " holds";
     }
     return scene_log_error_code(k.fault);
 }
@@ -3053,10 +3109,10 @@ int sca_get_scene_history(sca_ctx *c, int scene, int first_row, int nrows, int a
     const SceneLogView &L = c->scenes.log;
     const int32_t *off = c->scenes.h_off.data();
     // the faults that need no device value first (an empty row window passes this round), then the row window against the scene's step count
-    if (int r = scene_log_refuse(c, "sca_get_scene_history", scene_log_check(B, off, L.rows != nullptr, L.capacity, true, scene, 0, 0, 0, agent_begin, agent_count))) return r;
+    if (int r = scene_log_refuse(c, "sca_get_scene_history", scene_log_check(B, off, L.rows != nullptr, L.capacity, true, scene, 0, 0, 0, agent_begin, agent_count, c->scenes.h_size.data()))) return r;
     std::vector<int32_t> steps;
     if (int r = scene_log_steps(c, steps)) return r;
-    if (int r = scene_log_refuse(c, "sca_get_scene_history", scene_log_check(B, off, true, L.capacity, true, scene, steps[scene], first_row, nrows, agent_begin, agent_count))) return r;
+    if (int r = scene_log_refuse(c, "sca_get_scene_history", scene_log_check(B, off, true, L.capacity, true, scene, steps[scene], first_row, nrows, agent_begin, agent_count, c->scenes.h_size.data()))) return r;
     if (nrows == 0 || agent_count == 0) return 0;
     // rows [first_row, first_row + nrows) of the scene are one contiguous range; the agent window is cut out of it while unpacking
     const int lo = off[scene], ns = off[scene + 1] - lo;

@@ -126,14 +126,17 @@ enum RestartFault {
     RESTART_NOT_POSITIVE,   // radius, pref_speed or max_run_dist <= 0 (entry: the packed row)                 }
     RESTART_GOAL_HEADING,   // goal_heading passed while no device tracker is enabled                          }
     RESTART_PATHS,          // waypoint lists are set: one CSR block, replacing a scene's lists is not built   } SCA_ERR_UNSUPPORTED
-    RESTART_TRACKED_CHANGE  // a policy that changes an agent's tracked / untracked status while per-agent     }
+    RESTART_TRACKED_CHANGE, // a policy that changes an agent's tracked / untracked status while per-agent     }
                             // tracker attributes are set: the tracker's classes are cut by policy (entry: the packed row)
+    RESTART_BAD_SIZE        // sca_restart_scenes_sized: a size < 1 or above the slot's capacity (entry: its      SCA_ERR_ARG
+                            // index in sizes); checked with the ids, last in the enum to keep the numbering
 };
 // the caller's arguments, as sca_restart_scenes takes them
 struct RestartArgs {
     int count; const int32_t *scene_ids;
     const double *pos; const float *vel; const double *heading, *radius, *pref_speed, *goal; const uint8_t *policy, *zaxis;
     const double *max_run_dist, *goal_heading;
+    const int32_t *sizes = nullptr;            // [count] sca_restart_scenes_sized: the rows each named scene brings; NULL: its capacity
 };
 // what the rules read of the context
 struct RestartCtx {
@@ -145,20 +148,47 @@ struct RestartCtx {
 struct RestartCheck { RestartFault fault; int entry; int total; };
 inline bool restart_policy_tracked(int pol) { return pol == SCA_POLICY_SCA || pol == SCA_POLICY_RVO3D_DUBINS; }
 inline bool restart_finite(double x) { return x - x == 0.0; }       // (no <cmath>: false for NaN and both infinities)
+
+// ---- slots of a capacity (sca_restart_scenes_sized) -------------------------------------------------------------------------------------------
+// Scene s keeps its range [offsets[s], offsets[s + 1]) as a CAPACITY and holds size[s] agents, 1 <= size[s] <= capacity, in its first
+// size[s] rows; the rows behind them are vacant.  A context that never calls the sized restart has size[s] == capacity throughout.
+inline bool scene_size_ok(int size, int capacity) { return size >= 1 && size <= capacity; }
+// the rows the b-th named scene brings: sizes[b], or the slot's capacity where sizes == NULL (ids: checked by the caller)
+inline int scene_restart_rows(const int32_t *offsets, const int32_t *scene_ids, const int32_t *sizes, int b) {
+    return sizes ? sizes[b] : offsets[scene_ids[b] + 1] - offsets[scene_ids[b]];
+}
+// the packed row each named scene's arrays start at -- the prefix sum of the rows before it -- into start[count] (may be NULL); returns T
+inline int scene_restart_starts(int count, const int32_t *offsets, const int32_t *scene_ids, const int32_t *sizes, int32_t *start) {
+    int total = 0;
+    for (int b = 0; b < count; b++) {
+        if (start) start[b] = total;
+        total += scene_restart_rows(offsets, scene_ids, sizes, b);
+    }
+    return total;
+}
+// is any scene below its capacity?  While one is, a whole-context state from outside (sca_set_state, sca_set_kd_perm, sca_step_host) is refused
+inline bool scenes_any_partial(int nscenes, const int32_t *offsets, const int32_t *size) {
+    for (int s = 0; s < nscenes; s++) if (size[s] != offsets[s + 1] - offsets[s]) return true;
+    return false;
+}
+// the log's agent window lies inside the rows the scene occupies (the log's pitch stays the capacity)
+inline bool scene_log_agents_ok(int size, int agent_begin, int agent_count) {
+    return agent_begin >= 0 && agent_count >= 0 && (int64_t)agent_begin + agent_count <= (int64_t)size;
+}
 inline RestartCheck scene_restart_check(const RestartCtx &C, const RestartArgs &A) {
     if (C.nscenes <= 0 || C.offsets == nullptr) return {RESTART_NO_SCENES, -1, 0};
     if (!C.state_set) return {RESTART_NO_STATE, -1, 0};
     if (C.scene_begun) return {RESTART_MID_STEP, -1, 0};
     if (A.count <= 0 || A.scene_ids == nullptr) return {RESTART_BAD_COUNT, -1, 0};
-    int total = 0;
     std::vector<uint8_t> named((std::size_t)C.nscenes, (uint8_t)0);      // one mark per scene: thousands of small scenes may be named at once
     for (int b = 0; b < A.count; b++) {
         const int s = A.scene_ids[b];
         if (s < 0 || s >= C.nscenes) return {RESTART_BAD_ID, b, 0};
         if (named[s]) return {RESTART_REPEATED_ID, b, 0};
         named[s] = 1;
-        total += C.offsets[s + 1] - C.offsets[s];
+        if (A.sizes && !scene_size_ok(A.sizes[b], C.offsets[s + 1] - C.offsets[s])) return {RESTART_BAD_SIZE, b, 0};
     }
+    const int total = scene_restart_starts(A.count, C.offsets, A.scene_ids, A.sizes, nullptr);
     if (A.pos == nullptr || A.heading == nullptr) return {RESTART_NO_ARRAYS, -1, total};
     for (int r = 0; r < total; r++) {
         bool ok = true;
@@ -182,14 +212,14 @@ inline RestartCheck scene_restart_check(const RestartCtx &C, const RestartArgs &
     if (A.policy && C.tracker_per_agent) {
         int r = 0;
         for (int b = 0; b < A.count; b++)
-            for (int a = C.offsets[A.scene_ids[b]]; a < C.offsets[A.scene_ids[b] + 1]; a++, r++)
+            for (int a = C.offsets[A.scene_ids[b]], end = a + scene_restart_rows(C.offsets, A.scene_ids, A.sizes, b); a < end; a++, r++)
                 if (restart_policy_tracked(A.policy[r]) != restart_policy_tracked(C.policy_now[a])) return {RESTART_TRACKED_CHANGE, r, total};
     }
     return {RESTART_OK, -1, total};
 }
 // what sca_restart_scenes returns for a fault
 inline int scene_restart_error_code(RestartFault f) {
-    return f == RESTART_OK ? SCA_OK : f <= RESTART_MID_STEP ? SCA_ERR_STATE : f <= RESTART_GOAL_HEADING ? SCA_ERR_ARG : SCA_ERR_UNSUPPORTED;
+    return f == RESTART_OK ? SCA_OK : f <= RESTART_MID_STEP ? SCA_ERR_STATE : f <= RESTART_GOAL_HEADING || f == RESTART_BAD_SIZE ? SCA_ERR_ARG : SCA_ERR_UNSUPPORTED;
 }
 
 // The page-locked staging block sca_restart_scenes copies the caller's arrays into and k_scene_restart reads across the link: one section
@@ -263,14 +293,15 @@ inline SceneLogCheck scene_log_enable_check(int nscenes, bool scene_begun, const
 // sca_scene_history_rows (window == false: the scene and the windows are not looked at) and sca_get_scene_history.  offsets: checked by
 // scenes_check; steps_of_scene: steps[scene] where the scene is valid (read by the caller behind the checks that need no device value --
 // pass 0 for a first round of them).
+// size: [nscenes] the agents each scene holds (sca_restart_scenes_sized), NULL: every scene is full.
 inline SceneLogCheck scene_log_check(int nscenes, const int32_t *offsets, bool enabled, int capacity, bool window, int scene, int steps_of_scene,
-                                     int first_row, int nrows, int agent_begin, int agent_count) {
+                                     int first_row, int nrows, int agent_begin, int agent_count, const int32_t *size = nullptr) {
     if (nscenes <= 0) return {SCENE_LOG_NO_SCENES, -1};
     if (!enabled) return {SCENE_LOG_OFF, -1};
     if (!window) return {SCENE_LOG_OK, -1};
     if (scene < 0 || scene >= nscenes) return {SCENE_LOG_BAD_SCENE, scene};
-    const int64_t have = scene_log_rows_logged(steps_of_scene, capacity), size = (int64_t)offsets[scene + 1] - offsets[scene];
-    if (agent_begin < 0 || agent_count < 0 || (int64_t)agent_begin + agent_count > size) return {SCENE_LOG_BAD_AGENTS, scene};
+    const int64_t have = scene_log_rows_logged(steps_of_scene, capacity);
+    if (!scene_log_agents_ok(size ? size[scene] : offsets[scene + 1] - offsets[scene], agent_begin, agent_count)) return {SCENE_LOG_BAD_AGENTS, scene};
     if (first_row < 0 || nrows < 0 || (int64_t)first_row + nrows > have) return {SCENE_LOG_BAD_ROWS, scene};
     return {SCENE_LOG_OK, scene};
 }

@@ -65,12 +65,14 @@ __global__ __launch_bounds__(256) void k_scene_begin(SceneView v) {
 }
 
 // The forest's job table, behind k_kd_gather (which rewrites the single root job, the counts and the root's chunk records on every build):
-// one root job per scene and nothing for the level passes.  begin: this build opens a step (scene_begin_one).
-__global__ __launch_bounds__(256) void k_kd_scene_jobs(KdScratch s, SceneView v, int begin) {
+// one root job per scene and nothing for the level passes.  begin: this build opens a step (scene_begin_one).  size: [nscenes] the agents a
+// scene holds in the first rows of its range (sca_restart_scenes_sized; the range's length where it is full) -- the rows behind them are in
+// no tree.  An argument of its own: SceneView travels by value to the K1 and K4 scene kernels, which do not need it.
+__global__ __launch_bounds__(256) void k_kd_scene_jobs(KdScratch s, SceneView v, const int32_t *size, int begin) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t == 0) { s.counts[0] = 0; s.nchunks[0] = 0; s.counts[KD_MAX_LEVELS] = v.nscenes; }
     if (t >= v.nscenes) return;
-    KdJob j; j.begin = v.offsets[t]; j.end = v.offsets[t + 1]; j.node = 2 * j.begin; j.pad = -1;     // pad = -1: a root, no parent record
+    KdJob j; j.begin = v.offsets[t]; j.end = j.begin + size[t]; j.node = 2 * j.begin; j.pad = -1;     // pad = -1: a root, no parent record
     s.small[t] = j;
     if (begin) scene_begin_one(v, t);
 }
@@ -113,11 +115,8 @@ struct RestartDev {
     int trk_words;                  // sizeof(AgentTrack) / 4
 };
 constexpr int RESTART_T = 256;
-__global__ __launch_bounds__(RESTART_T) void k_scene_restart(RestartDev d, const uint8_t *blk, RestartLayout L, uint32_t has) {
-    const int b = (int)blockIdx.x, t = (int)threadIdx.x;
-    const int s = ((const int32_t *)(blk + L.off[RS_IDS]))[b];
-    const int row0 = ((const int32_t *)(blk + L.off[RS_START]))[b];
-    const int lo = d.offsets[s], ns = d.offsets[s + 1] - lo;
+// rows [lo, lo + ns) of a named scene from the block's rows row0 .. row0 + ns - 1: what a restart writes for a row an agent occupies
+__device__ __forceinline__ void scene_restart_fill(const RestartDev &d, const uint8_t *blk, const RestartLayout &L, uint32_t has, int row0, int lo, int ns, int t) {
     const double *pos = (const double *)(blk + L.off[RS_POS]) + 3 * (int64_t)row0;
     const double *head = (const double *)(blk + L.off[RS_HEADING]) + 3 * (int64_t)row0;
     const double *goal = (const double *)(blk + L.off[RS_GOAL]) + 3 * (int64_t)row0;
@@ -156,7 +155,52 @@ __global__ __launch_bounds__(RESTART_T) void k_scene_restart(RestartDev d, const
     }
     if (d.trk_st)                                                      // the AgentTrack records, word by word from the one initial record
         for (int64_t w = t; w < (int64_t)ns * d.trk_words; w += RESTART_T) d.trk_st[(int64_t)lo * d.trk_words + w] = d.trk_init[w % d.trk_words];
+}
+__global__ __launch_bounds__(RESTART_T) void k_scene_restart(RestartDev d, const uint8_t *blk, RestartLayout L, uint32_t has) {
+    const int b = (int)blockIdx.x, t = (int)threadIdx.x;
+    const int s = ((const int32_t *)(blk + L.off[RS_IDS]))[b];
+    const int row0 = ((const int32_t *)(blk + L.off[RS_START]))[b];
+    const int lo = d.offsets[s], ns = d.offsets[s + 1] - lo;
+    scene_restart_fill(d, blk, L, has, row0, lo, ns, t);
     if (t == 0) { d.live[s * SCENE_LINE] = ns; d.prev[s] = ns; d.steps[s] = 0; }
+}
+
+// Slots of a capacity (sca_restart_scenes_sized): the named scene takes new_size[b] agents into its first rows, and the rows behind them,
+// up to the capacity offsets[s + 1], are VACATED.  A vacant row is an agent that is settled for good, by the rule collide_finish_body
+// already has: flags FLAG_AT_GOAL | FLAG_COLLISION.  Every policy kernel skips it (mampenv.py:35) and its action row stays zero; K4 never
+// traverses for it (settled, and not `arrived_only`, which asks for FLAG_AT_GOAL alone) and cannot add a flag (total_dist 0 never passes
+// max_run_dist); the integrate stage leaves its position, a zero heading (pi_2_pi(0) = 0), total_dist and -- at its goal -- step_num as
+// they are; the tracker does not own it (tracker_owns wants flags 0).  It stands in no tree: k_kd_scene_jobs ends the scene's job at
+// size[s], so nobody's neighbour list, near list or collision walk can hold it, and the permutation behind the job stays the identity this
+// kernel writes.  The row keeps its position, radius and constants (goal, pref_speed, max_run_dist, policy, zaxis, v_pref mode): valid
+// numbers for the passes that still read them, replaced when an episode occupies the row again.
+// done_count (live agents of the last step): an occupied row that was done counts again (scene_restart_fill), a vacated row that was
+// running no longer does; done -> vacant and running -> occupied change nothing.
+__device__ __forceinline__ void scene_restart_vacate(const RestartDev &d, int lo, int hi, int t) {
+    for (int64_t g = 3 * (int64_t)lo + t; g < 3 * (int64_t)hi; g += RESTART_T) { d.heading[g] = 0.0; d.heading_keep[g] = 0.0; d.vpref_ext[g] = 0.0; }
+    for (int a = lo + t; a < hi; a += RESTART_T) {
+        PubRec *r = d.rec + a;                                         // (position and radius stay)
+        if (!(r->flags & (FLAG_AT_GOAL | FLAG_COLLISION | FLAG_TIMEOUT))) atomicAdd(&d.done_count[(a & 255) * 32], -1);
+        r->vx = 0.0f; r->vy = 0.0f; r->vz = 0.0f;
+        r->flags = FLAG_AT_GOAL | FLAG_COLLISION;
+        d.total_dist[a] = 0.0; d.step_num[a] = 0;
+        d.aperm[a] = a;
+        d.nbr_n[a] = 0; d.nbr_valid[a] = 0; d.near_n[a] = -1;
+        if (d.trk_nbr0) d.trk_nbr0[a] = -1.0;
+    }
+    if (d.trk_st)
+        for (int64_t w = (int64_t)lo * d.trk_words + t; w < (int64_t)hi * d.trk_words; w += RESTART_T) d.trk_st[w] = d.trk_init[w % d.trk_words];
+}
+// new_size: [count] in the order of the block's ids (host memory, read across the link like the block); size: [nscenes] the device's sizes,
+// which k_kd_scene_jobs reads.  The host has checked 1 <= new_size[b] <= capacity (scene_restart_check).
+__global__ __launch_bounds__(RESTART_T) void k_scene_restart_sized(RestartDev d, const uint8_t *blk, RestartLayout L, uint32_t has, const int32_t *new_size, int32_t *size) {
+    const int b = (int)blockIdx.x, t = (int)threadIdx.x;
+    const int s = ((const int32_t *)(blk + L.off[RS_IDS]))[b];
+    const int row0 = ((const int32_t *)(blk + L.off[RS_START]))[b];
+    const int lo = d.offsets[s], hi = d.offsets[s + 1], ns = new_size[b];
+    scene_restart_fill(d, blk, L, has, row0, lo, ns, t);
+    scene_restart_vacate(d, lo + ns, hi, t);
+    if (t == 0) { d.live[s * SCENE_LINE] = ns; d.prev[s] = ns; d.steps[s] = 0; size[s] = ns; }
 }
 
 // The wavefront-per-agent forms keep both roots in scalar registers: the obstacle phase is taken or skipped by the whole wavefront (the

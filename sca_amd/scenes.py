@@ -16,9 +16,11 @@ field with its spheres and two seeds of an obstacle scenario share one batch -- 
 
 `batch.env(s)` is a view with the surface the reference's callers and sca_amd.metrics read of a MACAEnv: `.agents`, `.obstacles` (the
 scene's own list where there is one per scene), `.kdTree.agentIDs` (scene-local ids); the agents' attributes (pos_global_frame, is_at_goal, total_dist, path, policy.now_goal, ...) read the
-batch's host mirrors at offsets[s] + id.  A host-side v_pref_fn is not supported: SCA / RVO3D+Dubins agents take v_pref from the device
+batch's host mirrors at offsets[s] + id.  With `capacities` a scene's range is a capacity: the slot holds any episode of 1 .. capacity agents in
+the first rows of its range (SceneBatch.restart takes any such episode), and the view follows the episode's size.  A host-side v_pref_fn is not supported: SCA / RVO3D+Dubins agents take v_pref from the device
 tracker (device_tracker=True), or from the straight-line rule without it, as in MACAEnv.
 """
+import copy
 import time
 
 import numpy as np
@@ -69,16 +71,21 @@ class SceneEnv:
     """One scene of a SceneBatch with a MACAEnv's read surface.  Agents index it with their scene-local id."""
 
     def __init__(self, batch, s, agents, lo, hi):
-        self._batch, self.scene, self.agents, self._lo, self._hi = batch, s, agents, lo, hi
+        self._batch, self.scene, self._lo = batch, s, lo
         self._obs_lo = 0 if batch.scene_obstacles is None else int(batch.obstacle_offsets[s])      # the context's obstacle ids are global
         self.obstacles = batch.obstacles if batch.scene_obstacles is None else batch.scene_obstacles[s]
         self.kdTree = _SceneKdTree(self)
-        self._mirror = {k: v[lo:hi] for k, v in batch._mirror.items()}       # views: refreshed in place by the batch
-        self.goal = batch.goal[lo:hi]
+        self._occupy(agents, hi)
         self._time_cum = [0.0]
         self._path_assigned = _Assigned(self)
         self.device_tracker = batch.device_tracker
         self.solver = _SceneLog(self)                               # (metrics.trajectories / write_episode_log: needs SceneBatch(scene_history=rows))
+
+    def _occupy(self, agents, hi):
+        """the episode the slot holds: rows [lo, hi) of the batch's arrays, the first len(agents) of the slot's capacity"""
+        self.agents, self._hi = agents, hi
+        self._mirror = {k: v[self._lo:hi] for k, v in self._batch._mirror.items()}       # views: refreshed in place by the batch
+        self.goal = self._batch.goal[self._lo:hi]
 
     _stale = property(lambda self: self._batch._stale)
     _paths_on = property(lambda self: self._batch._paths_on)
@@ -114,7 +121,12 @@ class SceneEnv:
 
 
 class SceneBatch(_FlatAgents):
-    def __init__(self, scenes, obstacles=(), scene_obstacles=None, neighbor_mode=S.NBR_KDTREE, device_tracker=False, history_capacity=0, scene_history=0, device=0):
+    def __init__(self, scenes, obstacles=(), scene_obstacles=None, neighbor_mode=S.NBR_KDTREE, device_tracker=False, history_capacity=0, scene_history=0, device=0,
+                 capacities=None):
+        """capacities: one agent capacity per scene, each >= len(scene) (None: the scene's own length).  Scene s then owns capacities[s] rows
+        of the context and holds its episode in the first of them; the rows behind are vacant (sca_restart_scenes_sized), and a later
+        restart may bring any episode of 1 .. capacities[s] agents (without `capacities` a slot keeps its size).  The spare rows are set up as copies of the scene's last agent, so a slot's
+        solver and planner attributes are those of the episode it started with."""
         scenes = [list(a) for a in scenes]
         if not scenes or any(len(a) == 0 for a in scenes):
             raise ValueError('a SceneBatch needs at least one scene and no empty one')
@@ -132,8 +144,19 @@ class SceneBatch(_FlatAgents):
             self.obstacle_offsets = np.concatenate([[0], np.cumsum([len(o) for o in self.scene_obstacles])]).astype(np.int32)
         self.neighbor_mode = neighbor_mode
         self.device_tracker = bool(device_tracker)
-        self.offsets = np.concatenate([[0], np.cumsum([len(a) for a in scenes])]).astype(np.int32)
-        flat = [a for agents in scenes for a in agents]
+        self.capacity_slots = capacities is not None               # else: a slot keeps its size, as a batch always did
+        self.sizes = np.array([len(a) for a in scenes], np.int32)   # agents each scene holds ...
+        caps = self.sizes.copy() if capacities is None else np.array([int(c) for c in capacities], np.int32)
+        if len(caps) != len(scenes) or (caps < self.sizes).any():
+            raise ValueError(f'capacities: one per scene, each at least the scene\'s agent count ({list(self.sizes)}), got {list(caps)}')
+        self.offsets = np.concatenate([[0], np.cumsum(caps)]).astype(np.int32)          # ... in the first rows of its range, its capacity
+        flat = []
+        for agents, cap in zip(scenes, caps):
+            flat.extend(agents)
+            for i in range(len(agents), int(cap)):                  # spare rows: valid constants and the slot's attributes, vacated below
+                pad = copy.copy(agents[-1])
+                pad.id, pad._path = i, []
+                flat.append(pad)
         B = len(scenes)
 
         def set_scenes():                                             # between the agents' attributes and the state
@@ -143,11 +166,14 @@ class SceneBatch(_FlatAgents):
 
         shared = self.scene_obstacles is None
         self._create(flat, device, len(self.obstacles) if shared else int(self.obstacle_offsets[-1]), self.obstacles if shared else None, set_scenes)
-        self._envs = [SceneEnv(self, s, scenes[s], int(self.offsets[s]), int(self.offsets[s + 1])) for s in range(B)]
+        self._envs = [SceneEnv(self, s, scenes[s], int(self.offsets[s]), int(self.offsets[s]) + len(scenes[s])) for s in range(B)]
         for view in self._envs:
             _bind(view.agents, view)
         self._reset_paths()
-        self.active = np.diff(self.offsets).astype(np.int32)          # agents of each scene the next step will serve
+        spare = [(s, scenes[s]) for s in range(B) if caps[s] > self.sizes[s]]
+        if spare:                                                     # one sized restart before the first step vacates the spare rows
+            self._send_restart(spare)
+        self.active = self.sizes.copy()                               # agents of each scene the next step will serve
         self.steps = np.zeros(B, np.int32)                            # steps each scene has taken while it was live
         if history_capacity:
             self.solver.history_enable(int(history_capacity))
@@ -180,10 +206,10 @@ class SceneBatch(_FlatAgents):
 
     # ---- a new episode into a slot while the others keep running (sca_restart_scenes) -------------------------------------------------------
     def restart(self, scenes):
-        """{s: agents}: scene s starts over with the new Agent list (numbered 0 .. n_s - 1, the slot's count), every other scene is untouched.
-        A slot keeps its size, its obstacles and its per-agent solver and planner attributes: ValueError, before any device call, for an
-        agent whose attributes differ from the slot's, or that carries a path.  From here on the scene is bit for bit the MACAEnv of the new
-        episode alone, like a scene of a fresh batch."""
+        """{s: agents}: scene s starts over with the new Agent list (numbered 0 .. n - 1; n is the slot's count, or, in a batch built with
+        `capacities`, any 1 <= n <= the slot's capacity), every other scene is untouched.  A slot keeps its capacity, its obstacles and its per-agent solver and planner attributes: ValueError, before any device
+        call, for an episode that does not fit, an agent whose attributes differ from its row's, or one that carries a path.  From here on
+        the scene is bit for bit the MACAEnv of the new episode alone, like a scene of a fresh batch."""
         items = sorted((int(s), list(agents)) for s, agents in dict(scenes).items())
         if not items:
             return
@@ -193,9 +219,12 @@ class SceneBatch(_FlatAgents):
             if not 0 <= s < len(self._envs):
                 raise ValueError(f'restart: no scene {s} in a batch of {len(self._envs)}')
             lo, hi = int(self.offsets[s]), int(self.offsets[s + 1])
-            if len(agents) != hi - lo:
-                raise ValueError(f'restart: scene {s} holds {hi - lo} agents, the new episode has {len(agents)} (a slot keeps its size)')
-            for i, (a, old) in enumerate(zip(agents, self._flat[lo:hi])):
+            if not self.capacity_slots and len(agents) != hi - lo:
+                raise ValueError(f'restart: scene {s} holds {hi - lo} agents, the new episode has {len(agents)} (a slot keeps its size; '
+                                 'SceneBatch(capacities=...) makes slots that take any episode that fits)')
+            if not 1 <= len(agents) <= hi - lo:
+                raise ValueError(f'restart: scene {s} holds 1 .. {hi - lo} agents, the new episode has {len(agents)} (a slot keeps its capacity)')
+            for i, (a, old) in enumerate(zip(agents, self._flat[lo:hi])):     # (over the rows the episode occupies)
                 if a.id != i:
                     raise ValueError(f'restart: scene {s}: agent.id must equal its index in its scene')
                 if len(a._path):
@@ -211,34 +240,44 @@ class SceneBatch(_FlatAgents):
                         raise ValueError(f'restart: scene {s}, agent {i} needs the device tracker, which a batch built without such agents has not enabled')
                     if _planner_triple(a) != self._planner_of(lo + i):
                         raise ValueError(f"restart: scene {s}, agent {i}: turning_radius / pitchlims differ from the slot's (a slot keeps its planner attributes)")
+        self._send_restart(items)
+        for s, agents in items:
+            lo = int(self.offsets[s])
+            view = self._envs[s]
+            self._flat[lo:lo + len(agents)] = agents                 # (the rows behind keep the agents that carry the slot's attributes)
+            view._occupy(agents, lo + len(agents))
+            view._time_cum = [0.0]
+            _bind(agents, view)
+        self._stale = True                                           # the mirrors (views of the batch's arrays) refresh in place on first use
+        self._nbr_cache = None
+        self._vpref_cache = None
+        st = self.solver.scene_state()
+        self.active, self.steps = st['active'], st['steps']
+
+    def _send_restart(self, items):
+        """the episodes' arrays to the device (one call), and the batch's per-agent host arrays behind them"""
         flat = [a for _, agents in items for a in agents]
         T = len(flat)
         start = np.array([a.initial_pos for a in flat], dtype=np.float64).reshape(T, 6)
         goal6 = np.array([a.goal_pos for a in flat], dtype=np.float64).reshape(T, 6)
         goal = np.array([a.goal_global_frame for a in flat], dtype=np.float64).reshape(T, 3)
         policy = np.array([a.policy.policy_id for a in flat], np.uint8)
+        # (a batch whose slots are all full, before and after, makes the plain call: sca_restart_scenes)
+        full = all(len(agents) == self.offsets[s + 1] - self.offsets[s] for s, agents in items) and (self.sizes == np.diff(self.offsets)).all()
         self.solver.restart_scenes([s for s, _ in items], np.array([a._pos for a in flat], dtype=np.float64).reshape(T, 3),
                                    np.array([a._heading for a in flat], dtype=np.float64).reshape(T, 3),
                                    vel=np.array([a._vel for a in flat], dtype=np.float32).reshape(T, 3), radius=[a.radius for a in flat],
                                    pref_speed=[a.pref_speed for a in flat], goal=goal, policy=policy, zaxis=S.zaxis_flags(start, goal6),
-                                   max_run_dist=[a.max_run_dist for a in flat], goal_heading=goal6[:, 3:6] if self._trk_on else None)
+                                   max_run_dist=[a.max_run_dist for a in flat], goal_heading=goal6[:, 3:6] if self._trk_on else None,
+                                   sizes=None if full else [len(agents) for _, agents in items])
         at = 0
         for s, agents in items:
-            lo, hi = int(self.offsets[s]), int(self.offsets[s + 1])
-            view = self._envs[s]
-            self._flat[lo:hi] = agents
-            view.agents = agents
-            self.goal[lo:hi] = goal[at:at + hi - lo]                 # (view.goal is a view of these rows)
-            self.policy_ids[lo:hi] = policy[at:at + hi - lo]
-            self._ext[lo:hi] = [a.policy.needs_external_vpref for a in agents]
-            view._time_cum = [0.0]
-            _bind(agents, view)
-            at += hi - lo
-        self._stale = True                                           # the mirrors (views of the batch's arrays) refresh in place on first use
-        self._nbr_cache = None
-        self._vpref_cache = None
-        st = self.solver.scene_state()
-        self.active, self.steps = st['active'], st['steps']
+            lo, n = int(self.offsets[s]), len(agents)
+            self.goal[lo:lo + n] = goal[at:at + n]                   # (view.goal is a view of these rows)
+            self.policy_ids[lo:lo + n] = policy[at:at + n]
+            self._ext[lo:lo + n] = [a.policy.needs_external_vpref for a in agents]
+            self.sizes[s] = n
+            at += n
 
     # ---- one step of every live scene ------------------------------------------------------------------------------------------------------
     def step(self, actions=None):
@@ -289,7 +328,54 @@ def next_episode(slot_size, pending_sizes):
     return None
 
 
-def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=None, max_steps=None, stats=None, history_rows=0):
+def next_fitting(capacity, pending_sizes):
+    """The position in `pending_sizes` of the episode a finished slot of `capacity` agent rows takes: the first, in queue order, that fits
+    (1 .. capacity agents); None when there is none -- the slot then stays done."""
+    for k, n in enumerate(pending_sizes):
+        if int(n) <= int(capacity):
+            return k
+    return None
+
+
+def plan_capacity_slots(sizes, capacities):
+    """Which queue entry every slot starts with when slot s holds any episode of up to capacities[s] agents: the slots choose in their own
+    order, each the first entry in queue order that fits it and that no earlier slot took (next_fitting).  Returns one entry per slot, None
+    for a slot no remaining entry fits -- it never will, the queue only shrinks.  ValueError when some episode fits no slot at all."""
+    sizes, capacities = [int(n) for n in sizes], [int(c) for c in capacities]
+    if not capacities or min(capacities) < 1:
+        raise ValueError(f'slot capacities must be positive, got {capacities}')
+    for i, n in enumerate(sizes):
+        if n > max(capacities):
+            raise ValueError(f'episode {i} has {n} agents and fits no slot (capacities {capacities})')
+    pending = list(range(len(sizes)))
+    holding = []
+    for cap in capacities:
+        k = next_fitting(cap, [sizes[j] for j in pending])
+        holding.append(None if k is None else pending.pop(k))
+    return holding
+
+
+def plan_queue(sizes, slots, capacities=None):
+    """(holding, slot_capacities): the queue entry each slot of the batch starts with and the agent rows it owns.  capacities None: slots of
+    fixed size (plan_slots: a slot takes episodes of exactly its own count); 'max': `slots` slots that each hold the largest episode; a
+    list: one capacity per slot.  Slots that would start empty are left out of the batch."""
+    sizes = [int(n) for n in sizes]
+    if capacities is None:
+        holding = plan_slots(sizes, slots)
+        return holding, [sizes[i] for i in holding]
+    if isinstance(capacities, str):
+        if capacities != 'max':
+            raise ValueError(f"capacities: None, 'max' or a list of slot capacities, got {capacities!r}")
+        capacities = [max(sizes)] * int(slots)
+    capacities = [int(c) for c in capacities]
+    if len(capacities) != int(slots):
+        raise ValueError(f'{len(capacities)} capacities for {slots} slots')
+    holding = plan_capacity_slots(sizes, capacities)
+    used = [s for s, i in enumerate(holding) if i is not None]
+    return [holding[s] for s in used], [capacities[s] for s in used]
+
+
+def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=None, max_steps=None, stats=None, history_rows=0, capacities=None):
     """Streams a queue of episodes (Agent lists, each numbered 0 .. n - 1) through `slots` scenes of ONE SceneBatch: when a scene finishes,
     its metrics, step count and final state are taken and the slot restarts with the next episode of its size (SceneBatch.restart), while
     the other slots keep running.  Obstacles are one list shared by all episodes.  Returns one dict per episode in queue order:
@@ -301,17 +387,21 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
     log of K rows per slot (SceneBatch(scene_history=K)): every result gains `trajectories` ([n, rows, 13], metrics.ANIMATION_COLUMNS, the
     episode's first K steps at most), `rows_dropped` (its steps beyond K) and `info` (metrics.episode_info: with the trajectories, what
     metrics.write_log_files writes an episode's folder from), read when the slot finishes, before it is refilled; an episode
-    longer than K does not stop the queue."""
+    longer than K does not stop the queue.  capacities='max' (or a list, one agent capacity per slot) makes the slots CAPACITY slots: a slot
+    starts with, and later takes, the first pending episode in queue order that fits it, whatever its agent count (plan_capacity_slots,
+    next_fitting), so a queue that mixes counts streams through one set of slots; ValueError before the first step when an episode fits no
+    slot.  live_fraction then counts the slots' capacities as the batch's agent rows."""
     episodes = [list(e) for e in episodes]
     sizes = [len(e) for e in episodes]
-    holding = plan_slots(sizes, slots)
-    batch_agents = sum(sizes[i] for i in holding)               # the slots keep their sizes: the batch's agent count, for live_fraction
+    holding, caps = plan_queue(sizes, slots, capacities)
+    batch_agents = sum(caps)                                    # the slots keep their rows: the batch's agent count, for live_fraction
     pending = [i for i in range(len(episodes)) if i not in set(holding)]
     tracked = [any(a.policy.needs_external_vpref for a in e) for e in episodes]
     if device_tracker and any(tracked[i] for i in pending) and not any(tracked[i] for i in holding):
         raise ValueError('run_episodes: episode %d needs the device tracker, but none of the episodes the slots start with does, so the batch '
                          'would run without one: put a tracked episode among the first %d' % (min(i for i in pending if tracked[i]), len(holding)))
-    batch = SceneBatch([episodes[i] for i in holding], obstacles, device_tracker=device_tracker, scene_history=history_rows)
+    batch = SceneBatch([episodes[i] for i in holding], obstacles, device_tracker=device_tracker, scene_history=history_rows,
+                       capacities=None if capacities is None else caps)
     results = [None] * len(episodes)
     batch_steps = served = 0
     try:
@@ -323,7 +413,7 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
             for s, i in enumerate(holding):
                 if i is None or not batch.done[s]:
                     continue
-                lo, hi = int(batch.offsets[s]), int(batch.offsets[s + 1])
+                lo, hi = int(batch.offsets[s]), int(batch.offsets[s]) + int(batch.sizes[s])
                 results[i] = dict(episode=i, slot=s, metrics=metrics.episode_metrics(batch.env(s)), steps=int(batch.steps[s]),
                                   state={k: batch._state(k)[lo:hi].copy() for k in batch._mirror})
                 if batch.scene_history:
@@ -332,7 +422,8 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
                     results[i].update(trajectories=metrics.trajectories(view, rows=rows), rows_dropped=dropped, info=metrics.episode_info(view))
                 if on_done is not None:
                     on_done(results[i])
-                k = next_episode(sizes[i], [sizes[j] for j in pending])
+                left = [sizes[j] for j in pending]
+                k = next_episode(sizes[i], left) if capacities is None else next_fitting(caps[s], left)
                 holding[s] = None if k is None else pending.pop(k)
                 if holding[s] is not None:
                     refill[s] = episodes[holding[s]]

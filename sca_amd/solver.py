@@ -211,18 +211,27 @@ class BatchedSolver:
         self.scene_obstacle_offsets = off
 
     def restart_scenes(self, ids, pos, heading, vel=None, radius=None, pref_speed=None, goal=None, policy=None, zaxis=None, max_run_dist=None,
-                       goal_heading=None):
+                       goal_heading=None, sizes=None):
         """New episodes into the scenes `ids` while the others keep running (sca_restart_scenes).  The arrays hold T rows, the named scenes'
         agents in the order of `ids`; None keeps the slot's values (vel: zero).  Afterwards each named scene is what a context of that
-        episode alone is after set_agents + set_state (+ device_tracker_enable); its agent count, obstacle set and per-agent attributes stay."""
+        episode alone is after set_agents + set_state (+ device_tracker_enable); its obstacle set and per-agent attributes stay.
+        sizes (sca_restart_scenes_sized): the agents each named scene takes, 1 .. its capacity (the length of its range) -- T is their sum,
+        and the rows of the range behind them are vacant; None fills every named scene to its capacity."""
         ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
         keep = [ids]
+        if sizes is not None:
+            sizes = np.ascontiguousarray(sizes, np.int32).reshape(-1)
+            if len(sizes) != len(ids):
+                raise ValueError(f'restart_scenes: {len(sizes)} sizes for {len(ids)} scenes')
+            keep.append(sizes)
         # T, where the ids name scenes of this context (else the library refuses the call before it reads an array): every array is held
         # against it here, because the library cannot know how long the caller's buffers are
         off = self.scene_offsets
         T = None
         if off is not None and len(ids) and ids.min() >= 0 and ids.max() < self.nscenes:
             T = int((off[ids + 1] - off[ids]).sum())
+            if sizes is not None and sizes.min() >= 1 and (sizes <= off[ids + 1] - off[ids]).all():
+                T = int(sizes.sum())                               # (else the library refuses the call, naming the entry)
 
         def arr(a, dt, ct, cols):
             if a is None:
@@ -236,9 +245,20 @@ class BatchedSolver:
         d3 = lambda a: arr(a, np.float64, C.c_double, 3)
         d1 = lambda a: arr(a, np.float64, C.c_double, 0)
         u1 = lambda a: arr(a, np.uint8, C.c_uint8, 0)
-        self._chk(self.L.sca_restart_scenes(self.ctx, len(ids), _lib.ptr(ids, C.c_int32), d3(pos), arr(vel, np.float32, C.c_float, 3), d3(heading),
-                                            d1(radius), d1(pref_speed), d3(goal), u1(policy), u1(zaxis), d1(max_run_dist), d3(goal_heading)),
-                  'sca_restart_scenes')
+        rest = (d3(pos), arr(vel, np.float32, C.c_float, 3), d3(heading), d1(radius), d1(pref_speed), d3(goal), u1(policy), u1(zaxis), d1(max_run_dist),
+                d3(goal_heading))
+        if sizes is None:
+            self._chk(self.L.sca_restart_scenes(self.ctx, len(ids), _lib.ptr(ids, C.c_int32), *rest), 'sca_restart_scenes')
+        else:
+            self._chk(self.L.sca_restart_scenes_sized(self.ctx, len(ids), _lib.ptr(ids, C.c_int32), _lib.ptr(sizes, C.c_int32), *rest),
+                      'sca_restart_scenes_sized')
+
+    def scene_sizes(self):
+        """[B] int32: the agents each scene holds, in the first rows of its range (sca_get_scene_sizes); the range's length unless a sized
+        restart said otherwise"""
+        out = np.zeros(self.nscenes, np.int32)
+        self._chk(self.L.sca_get_scene_sizes(self.ctx, _lib.ptr(out, C.c_int32)), 'sca_get_scene_sizes')
+        return out
 
     def scene_state(self):
         """dict(active [B] int32: agents of each scene the next step would serve, steps [B] int32: steps taken while the scene was live)"""
@@ -267,7 +287,7 @@ class BatchedSolver:
         if nrows is None:
             nrows = int(self.scene_history_rows()['logged'][scene]) - first_row if inside else 0
         if agent_count is None:
-            agent_count = int(self.scene_offsets[scene + 1] - self.scene_offsets[scene]) - agent_begin if inside else 0
+            agent_count = int(self.scene_sizes()[scene]) - agent_begin if inside else 0
         shape = (max(0, int(nrows)), max(0, int(agent_count)), 3)                # (a window the library will refuse still gets arrays it could fill)
         out = dict(pos=np.zeros(shape), heading=np.zeros(shape), vel=np.zeros(shape, np.float32))
         self._chk(self.L.sca_get_scene_history(self.ctx, scene, int(first_row), int(nrows), int(agent_begin), int(agent_count),
