@@ -13,6 +13,8 @@ one metrics row per scene -- what a loop over the reference's run_example/run_*.
     python examples/run_scenes.py --sizes 20,50,100 --slots 16 --capacity max   # the scenarios at several drone counts through ONE queue: every
                                                        # slot holds up to the largest count and takes the next episode that fits
                                                        # (without --capacity a slot keeps its size: one slot at least per count)
+    python examples/run_scenes.py --seeds 8 --slots 16 --harvest      # the streamed queue with the finished scenes handed over by the step that
+                                                       # finishes them (sca_scene_harvest_enable): the same rows, one synchronisation a step
 """
 import argparse
 import os
@@ -42,6 +44,7 @@ def main():
     ap.add_argument('--sizes', default=None, help='drone counts, e.g. 20,50,100: every scenario at each of them (instead of --agents)')
     ap.add_argument('--capacity', default=None, help="with --slots: 'max' makes every slot hold up to the largest episode, so a slot takes any "
                                                      'episode of the queue; a number is the capacity of every slot')
+    ap.add_argument('--harvest', action='store_true', help='with --slots: finished scenes hand over their result with the step (run_episodes(harvest=True))')
     ap.add_argument('--log-dir', default=None, help='write one folder per episode here: env_cfg.json + trajs.npz (the first --max-steps steps of each)')
     args = ap.parse_args()
     if args.slots and args.obstacles:
@@ -49,6 +52,8 @@ def main():
 
     if args.capacity and not args.slots:
         ap.error('--capacity is about the slots of a streamed queue: give --slots')
+    if args.harvest and not args.slots:
+        ap.error('--harvest is about the streamed queue: give --slots')
     counts = [int(v) for v in args.sizes.split(',')] if args.sizes else [args.agents]
     many = len(counts) > 1
     if many and not args.slots:
@@ -86,7 +91,7 @@ def main():
                 if r['rows_dropped']:
                     print('    (the log holds the first %d steps: %d more did not fit --max-steps rows)' % (r['trajectories'].shape[1], r['rows_dropped']))
         run_episodes(scenes, args.slots, device_tracker=True, on_done=row, max_steps=args.max_steps, stats=stats,
-                     history_rows=args.max_steps if args.log_dir else 0, capacities=capacities)
+                     history_rows=args.max_steps if args.log_dir else 0, capacities=capacities, harvest=args.harvest)
         print('%d episodes through %d slots: %d batch steps, mean live fraction %.2f, %.2f s' %
               (len(scenes), args.slots, stats['batch_steps'], stats['live_fraction'], time.time() - t0))
         return

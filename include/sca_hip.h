@@ -229,7 +229,9 @@ int sca_set_scene_obstacles(sca_ctx *ctx, int nscenes, const int32_t *obs_offset
  *              between tracked (SCA, RVO3D+Dubins) and untracked while per-agent tracker attributes are set (their classes are cut by
  *              policy).  A refused call has changed nothing.
  *   cost       one kernel launch and one stream synchronisation however many scenes are named (one more small copy where a policy changed
- *              the ORCA3D-LP list); the arrays travel through a page-locked block of the library's own, allocated once. */
+ *              the ORCA3D-LP list); the arrays travel through a page-locked block of the library's own, allocated once.
+ *   harvest    with sca_scene_harvest_enable on, the call clears the `fresh` word of every named scene: a harvest that was not collected
+ *              (sca_scene_harvest_collect) before its scene is restarted is gone. */
 int sca_restart_scenes(sca_ctx *ctx, int count, const int32_t *scene_ids /*count*/,
                        const double *pos /*T*3*/, const float *vel /*T*3, nullable: zero*/, const double *heading /*T*3*/,
                        const double *radius, const double *pref_speed, const double *goal /*T*3*/, const uint8_t *policy,
@@ -297,6 +299,65 @@ int sca_scene_history_enable(sca_ctx *ctx, int capacity_rows);
 int sca_scene_history_rows(sca_ctx *ctx, int32_t *rows_logged /*nscenes, nullable*/, int32_t *rows_dropped /*nscenes, nullable*/);
 int sca_get_scene_history(sca_ctx *ctx, int scene, int first_row, int nrows, int agent_begin, int agent_count,
                           double *pos, double *heading, float *vel);
+
+/* Finished scenes hand over their result WITH THE STEP.  With the harvest enabled a step enqueues one more kernel behind its last one
+ * (k_scene_harvest, a workgroup per scene) that writes into ONE page-locked block of the library's, readable after the synchronisation the
+ * step makes anyway: every scene's counters on every step (what sca_get_scene_state reads after a step), and, for a scene that FINISHED IN
+ * THAT STEP (agents live when the step began, none after it), the scene's occupied rows in the columns of sca_get_state plus one
+ * sca_scene_summary.  So the host learns which scenes are done and takes their final state without sca_get_scene_state's second
+ * synchronisation and without sca_get_state's read-back of the whole context.  Every scene has a fixed place in the block -- counters[2 s],
+ * summary[s], rows offsets[s] + i: the index the rows have in sca_get_state -- so nothing depends on the order scenes finish in, and a scene
+ * finishes at most once between two restarts, so nothing is overwritten unread.  Works behind every step form (sca_env_step, sca_run_steps
+ * -- a burst accumulates --, sca_step_begin / sca_step_end, sca_policy_pass + sca_env_update, sca_step_host).  A context without the harvest
+ * enqueues exactly what it did; sca_get_scene_state and sca_get_state are unchanged.  Detect the feature by the symbol.
+ *   sca_scene_harvest_layout  byte offsets of the eight sections (the order of sca_scene_harvest's pointers), each on a 128-byte boundary,
+ *              and the block's size, for nscenes scenes over n agent rows.  Pure host arithmetic.  SCA_ERR_ARG: nscenes <= 0, n < nscenes,
+ *              a NULL pointer.
+ *   sca_scene_harvest_enable  on != 0: allocates the block (mapped, coherent, zeroed), fills the counters from the scenes as they stand
+ *              (where a state is set) and starts batch_step at 0; enabling again starts over with a fresh block.  on == 0 frees it.
+ *              SCA_ERR_STATE: no scenes, or between a policy pass and its env update.  Whatever clears or redefines the scenes
+ *              (sca_set_agents, sca_set_scenes) drops the harvest, as it drops the log per scene: pointers handed out are then stale.
+ *   sca_scene_harvest_get     pointers into the block and its counts.  struct_bytes = sizeof(sca_scene_harvest) as the caller compiled it
+ *              (sca_host_state_get's rule: at least the leading integers, at most this library's struct, else SCA_ERR_ARG; only the
+ *              pointers that fit are written).  SCA_ERR_STATE: no scenes, harvest not enabled.
+ *   sca_scene_harvest_collect one stream synchronisation (free directly after sca_env_step), then a host scan of the nscenes `fresh` words:
+ *              the scenes that finished since the previous collect, in ascending (batch_step, scene id), into scene_ids[nscenes]; *count
+ *              of them.  Their `fresh` words are cleared; their rows and summaries stay readable until the scene is restarted or finishes
+ *              again.  SCA_ERR_STATE: no scenes, not enabled.  SCA_ERR_ARG: a NULL pointer.
+ *   fresh words cleared without a collect: sca_restart_scenes[_sized] clears those of the named scenes (behind the call's own
+ *              synchronisation, when no step is in flight) -- an UNCOLLECTED harvest of a restarted scene is gone, collect before you
+ *              restart; sca_set_state and sca_step_host with SCA_HOST_IN_STATE clear all of them (a state from outside: nothing that
+ *              finished before it is reported after it).
+ *   counters   live / steps of every scene after the last env update (at enable: as the scenes stand).  Between a policy pass and its env
+ *              update, and behind sca_restart_scenes or sca_set_state, they are still the last update's: sca_get_scene_state knows better
+ *              then.
+ *   batch_step counts the context's env updates since the harvest was enabled, the first being 1. */
+typedef struct sca_scene_summary {       /* 64 bytes */
+    int32_t fresh;                       /* 1: written since the last collect / restart of this scene */
+    int32_t steps;                       /* the scene's own step count when it finished */
+    int32_t batch_step;                  /* the env update (since enable, from 1) it finished in */
+    int32_t arrived, collided, timed_out;/* occupied rows by flag (a row may count in more than one) */
+    int32_t successful_num;              /* rows with neither the collision nor the timeout flag */
+    int32_t reserved0;
+    int64_t all_step_num;                /* sum of step_num over the successful rows */
+    double  all_distance;                /* sum of total_dist over the successful rows, added in ascending row order from 0.0 */
+    int64_t reserved1[2];
+} sca_scene_summary;
+typedef struct sca_scene_harvest {       /* pointers into ONE page-locked allocation of the library's */
+    int32_t struct_bytes, nscenes, n, reserved;
+    int32_t *counters;                   /* nscenes*2: live, steps -- every step */
+    sca_scene_summary *summary;          /* nscenes */
+    double  *pos;                        /* n*3  } rows offsets[s] .. offsets[s] + size[s] - 1 of a finished scene; */
+    float   *vel;                        /* n*3  } other rows are never written                                    */
+    double  *heading;                    /* n*3  } */
+    uint8_t *flags;                      /* n    } */
+    double  *total_dist;                 /* n    } */
+    int32_t *step_num;                   /* n    } */
+} sca_scene_harvest;
+int sca_scene_harvest_layout(int nscenes, int n, int64_t *offsets /*8, in the struct's order*/, int64_t *total_bytes);
+int sca_scene_harvest_enable(sca_ctx *ctx, int on);
+int sca_scene_harvest_get(sca_ctx *ctx, sca_scene_harvest *out, int32_t struct_bytes);
+int sca_scene_harvest_collect(sca_ctx *ctx, int32_t *scene_ids /*nscenes*/, int32_t *count);
 
 /* the hot path ----------------------------------------------------------------------------------- */
 int sca_policy_pass(sca_ctx *ctx, int neighbor_mode);

@@ -32,6 +32,24 @@ class HostState(C.Structure):
 HOST_IN_STATE, HOST_IN_VPREF = 1, 2                               # SCA_HOST_IN_*
 
 
+class SceneSummary(C.Structure):
+    """sca_scene_summary: what k_scene_harvest writes for a scene in the step it finishes in (64 bytes)"""
+    _fields_ = [('fresh', C.c_int32), ('steps', C.c_int32), ('batch_step', C.c_int32), ('arrived', C.c_int32), ('collided', C.c_int32),
+                ('timed_out', C.c_int32), ('successful_num', C.c_int32), ('reserved0', C.c_int32), ('all_step_num', C.c_int64),
+                ('all_distance', C.c_double), ('reserved1', C.c_int64 * 2)]
+
+
+SUMMARY_DTYPE = np.dtype([('fresh', np.int32), ('steps', np.int32), ('batch_step', np.int32), ('arrived', np.int32), ('collided', np.int32),
+                          ('timed_out', np.int32), ('successful_num', np.int32), ('reserved0', np.int32), ('all_step_num', np.int64),
+                          ('all_distance', np.float64), ('reserved1', np.int64, (2,))])
+
+
+class SceneHarvest(C.Structure):
+    """sca_scene_harvest: pointers into the library's page-locked harvest block (sca_scene_harvest_get)"""
+    _fields_ = [('struct_bytes', C.c_int32), ('nscenes', C.c_int32), ('n', C.c_int32), ('reserved', C.c_int32), ('counters', ip),
+                ('summary', C.POINTER(SceneSummary)), ('pos', dp), ('vel', fp), ('heading', dp), ('flags', bp), ('total_dist', dp), ('step_num', ip)]
+
+
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against include/sca_hip.h
 SIGNATURES = {
     'sca_default_params': (None, [C.c_void_p]),                   # (version-100 form: 56 bytes)
@@ -60,6 +78,10 @@ SIGNATURES = {
     'sca_scene_history_enable': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_scene_history_rows': (C.c_int, [C.c_void_p, ip, ip]),
     'sca_get_scene_history': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, fp]),
+    'sca_scene_harvest_layout': (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'sca_scene_harvest_enable': (C.c_int, [C.c_void_p, C.c_int]),
+    'sca_scene_harvest_get': (C.c_int, [C.c_void_p, C.POINTER(SceneHarvest), C.c_int32]),
+    'sca_scene_harvest_collect': (C.c_int, [C.c_void_p, ip, C.POINTER(C.c_int32)]),
     'sca_set_path_state': (C.c_int, [C.c_void_p, ip, dp]),
     'sca_policy_pass': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_get_actions': (C.c_int, [C.c_void_p, fp]),

@@ -312,10 +312,14 @@ struct sca_ctx {
         std::vector<int32_t> h_obs_off; // [nscenes + 1] the obstacle offsets as set
         uint8_t *rs_host = nullptr;     // sca_restart_scenes' page-locked staging block (RestartLayout of max_n, sca_scenes.h), allocated on first use
         SceneLogView log{};             // the trajectory log per scene (sca_scene_history_enable), rows null: off -- a step then enqueues nothing for it
+        uint8_t *hv_host = nullptr;     // the harvest block (sca_scene_harvest_enable; HarvestLayout of nscenes and n, sca_scenes.h), null: off -- a step then enqueues nothing for it
+        HarvestLayout hv_layout{};
+        int32_t hv_batch_step = 0;      // env updates enqueued since the harvest was enabled
         void release() {                // the device and page-locked allocations, behind a synchronised stream; the flags and host vectors stay
             for (void *p : {(void *)v.scene_of, (void *)v.offsets, (void *)counters, (void *)v.heading_keep, (void *)ov.oroot, (void *)log.rows, (void *)size}) if (p) (void)hipFree(p);
             if (rs_host) (void)hipHostFree(rs_host);
-            v = SceneView{}; counters = nullptr; size = nullptr; ov = SceneObsView{}; rs_host = nullptr; log = SceneLogView{};
+            if (hv_host) (void)hipHostFree(hv_host);
+            v = SceneView{}; counters = nullptr; size = nullptr; ov = SceneObsView{}; rs_host = nullptr; log = SceneLogView{}; hv_host = nullptr;
         }
     } scenes;
     std::vector<uint8_t> h_policy;      // [n] the agents' policies as they stand (sca_set_agents, sca_restart_scenes)
@@ -1050,6 +1054,7 @@ int sca_set_agent_params(sca_ctx *c, int n, const double *neighbor_dist, const i
 }
 
 static int scenes_clear(sca_ctx *c);
+static void scene_harvest_clear_fresh(sca_ctx *c, int count, const int32_t *scene_ids);
 // a whole-context state from outside while a scene is below its capacity (sca_restart_scenes_sized): the vacant rows are the library's
 static int scenes_refuse_partial(sca_ctx *c, const char *who) {
     if (!c->scenes.on || !c->scenes.partial) return 0;
@@ -1134,6 +1139,7 @@ int sca_set_state(sca_ctx *c, const double *pos, const float *vel, const double 
     CHK(c, hipStreamSynchronize(c->stream));
     c->state_set = true; c->state_fresh = true;
     c->scenes.live_valid = false; c->scenes.begun = false;
+    scene_harvest_clear_fresh(c, 0, nullptr);                             // (a state from outside: nothing that finished before it is reported after it)
     if (c->part_on) return part_classify(c);                              // a complete state again: ownership follows from it
     return 0;
 }
@@ -1358,10 +1364,27 @@ static int scene_log_drop(sca_ctx *c) {
     c->scenes.log = SceneLogView{};
     return 0;
 }
+// ... and the harvest block: its places are cut by the scenes' offsets too
+static int scene_harvest_drop(sca_ctx *c) {
+    if (!c->scenes.hv_host) return 0;
+    CHK(c, hipStreamSynchronize(c->stream));
+    (void)hipHostFree(c->scenes.hv_host);
+    c->scenes.hv_host = nullptr;
+    return 0;
+}
+// the `fresh` words of the harvest, all of them or those of the named scenes.  Host stores into the block: only behind a synchronised
+// stream, when no k_scene_harvest is in flight.
+static void scene_harvest_clear_fresh(sca_ctx *c, int count, const int32_t *scene_ids) {
+    if (!c->scenes.hv_host) return;
+    sca_scene_summary *sum = (sca_scene_summary *)(c->scenes.hv_host + c->scenes.hv_layout.off[HV_SUMMARY]);
+    if (scene_ids) for (int e = 0; e < count; e++) sum[scene_ids[e]].fresh = 0;
+    else for (int s = 0; s < c->scenes.v.nscenes; s++) sum[s].fresh = 0;
+}
 static int scenes_clear(sca_ctx *c) {
     if (!c->scenes.on) return 0;
     if (int r = scene_obstacles_drop(c)) return r;
     if (int r = scene_log_drop(c)) return r;
+    if (int r = scene_harvest_drop(c)) return r;
     CHK(c, hipStreamSynchronize(c->stream));
     c->scenes.on = false;
     c->scenes.h_off.clear();
@@ -1628,6 +1651,7 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
     if (policy_changed || size_changed) c->h_lp_list.swap(lp_new);
     c->scenes.h_size.swap(size_now);
     c->scenes.partial = scenes_any_partial(c->scenes.v.nscenes, off, c->scenes.h_size.data());
+    scene_harvest_clear_fresh(c, count, scene_ids);                    // an uncollected harvest of a restarted scene is gone (behind the synchronisation above)
     c->h_pos_valid = false;                                            // (no host mirror of the positions is kept, as in sca_step_host)
     c->near_valid = false;
     // (scene_live_valid stays what it is: the kernel wrote the named scenes' counters itself, and where the others' are stale the recount
@@ -2250,12 +2274,19 @@ static int launch_collide_finish(sca_ctx *c, bool timed) {
     const dim3 k4grid((cnt + K4_WAVES * K4_APW - 1) / (K4_WAVES * K4_APW));
     // (the event that rides on the step's last kernel, if sca_run_steps asked for one: the next pass's fork)
     const bool others = c->part_on || cnt < d.n;
-    const hipEvent_t k4_stop = others ? nullptr : c->finish_stop, others_stop = others ? c->finish_stop : nullptr;
+    // (with the harvest the step's last kernel is k_scene_harvest, and the event rides on that one)
+    const bool harvest = c->scenes.on && c->scenes.hv_host != nullptr;
+    const hipEvent_t last_stop = others ? nullptr : c->finish_stop, others_stop = others ? c->finish_stop : nullptr;
+    const hipEvent_t k4_stop = harvest ? nullptr : last_stop;
     const int fresh = c->state_fresh ? 1 : 0;
     if (c->scenes.on) {
         if (c->scenes.obs_on) LAUNCH_OPT(c, k4_stop, k_collide_finish_scenes<SceneObsRoots>, k4grid, dim3(K4_WAVES * 64), c->stream, d, c->P, agent_reach, obs_reach, fresh, SceneObsRoots{c->scenes.v, c->scenes.ov});
         else LAUNCH_OPT(c, k4_stop, k_collide_finish_scenes<SceneRoots>, k4grid, dim3(K4_WAVES * 64), c->stream, d, c->P, agent_reach, obs_reach, fresh, SceneRoots{c->scenes.v});
         c->scenes.begun = false; c->scenes.live_valid = true;
+        if (harvest) {                                                      // d.rec_new: what K4 just wrote, the current records behind the swap below
+            const HarvestDev h{d.rec_new, d.heading, d.total_dist, d.step_num, c->scenes.size, c->scenes.hv_host, c->scenes.hv_layout, ++c->scenes.hv_batch_step};
+            LAUNCH_OPT(c, last_stop, k_scene_harvest, dim3(c->scenes.v.nscenes), dim3(HARVEST_T), c->stream, c->scenes.v, h);
+        }
     } else if (c->nbr_mode == SCA_NBR_GRID)
         LAUNCH_OPT(c, k4_stop, k_collide_finish_grid, k4grid, dim3(K4_WAVES * 64), c->stream, d, c->grid, c->P, agent_reach, obs_reach, fresh);
     else
@@ -2515,6 +2546,10 @@ int sca_step_host(sca_ctx *c, int neighbor_mode, uint32_t in_mask, int *active) 
     const HostIoDev io{c->d.rec, c->d.heading, c->d.total_dist, c->d.step_num, c->d.vpref_ext, c->d.vpref_mode, c->d.action};
     const dim3 grid((n + HIO_TILE - 1) / HIO_TILE), block(HIO_TILE);
     uint8_t *blk = c->tun.hs_staged ? c->hs_dev : c->hs_host;               // what the two kernels read and write
+    if ((in_mask & SCA_HOST_IN_STATE) && c->scenes.hv_host) {              // sca_set_state's rule for the harvest; the words are the host's to
+        CHK(c, hipStreamSynchronize(c->stream));                           // write only while no step is in flight (idle behind a sca_step_host)
+        scene_harvest_clear_fresh(c, 0, nullptr);
+    }
     if (in_mask) {
         // (staged form: the up-going sections are contiguous, [pos .. step_num] [vpref, vpref_mode] -- one copy takes what was written)
         const int64_t lo = (in_mask & SCA_HOST_IN_STATE) ? L.off[HS_POS] : L.off[HS_VPREF];
@@ -3127,6 +3162,74 @@ int sca_get_scene_history(sca_ctx *c, int scene, int first_row, int nrows, int a
             if (heading) { heading[3 * i] = h.a; heading[3 * i + 1] = h.b; heading[3 * i + 2] = h.g; }
             if (vel) { vel[3 * i] = h.vx; vel[3 * i + 1] = h.vy; vel[3 * i + 2] = h.vz; }
         }
+    return 0;
+}
+
+// ---- finished scenes hand over their result with the step (include/sca_hip.h; the rules and the layout are sca_scenes.h's, the kernel is
+// k_scene_harvest, enqueued by launch_collide_finish) ------------------------------------------------------------------------------------------
+static int scene_harvest_refuse(sca_ctx *c, const char *who, HarvestFault f) {
+    switch (f) {
+    case HARVEST_OK: return 0;
+    case HARVEST_NO_SCENES: c->err = std::string(who) + ": no scenes -- sca_set_scenes first"; break;
+    case HARVEST_MID_STEP: c->err = std::string(who) + " between a policy pass and its env update: finish the step first"; break;
+    case HARVEST_OFF: c->err = std::string(who) + ": sca_scene_harvest_enable first"; break;
+    case HARVEST_NO_OUT: c->err = std::string(who) + ": an output pointer is NULL"; break;
+    default: c->err = std::string(who) + ": struct_bytes must be sizeof(sca_scene_harvest) as the caller compiled it (" +
+                      std::to_string(offsetof(sca_scene_harvest, counters)) + " .. " + std::to_string(sizeof(sca_scene_harvest)) + ")";
+    }
+    return scene_harvest_error_code(f);
+}
+int sca_scene_harvest_layout(int nscenes, int n, int64_t *offsets, int64_t *total_bytes) {
+    if (nscenes <= 0 || n < nscenes || !offsets || !total_bytes) return SCA_ERR_ARG;
+    const HarvestLayout L = scene_harvest_layout(nscenes, n);
+    for (int s = 0; s < HV_SECTIONS; s++) offsets[s] = L.off[s];
+    *total_bytes = L.total;
+    return 0;
+}
+int sca_scene_harvest_enable(sca_ctx *c, int on) {
+    API_ENTER(c);
+    const int B = c->scenes.on ? c->scenes.v.nscenes : 0;
+    if (int r = scene_harvest_refuse(c, "sca_scene_harvest_enable", scene_harvest_check(HARVEST_ENABLE, B, c->scenes.begun, c->scenes.hv_host != nullptr, true, 0))) return r;
+    if (!on) return scene_harvest_drop(c);
+    const HarvestLayout L = scene_harvest_layout(B, c->n);
+    uint8_t *blk = nullptr;                                               // (before the old block goes: a call that fails here changes nothing)
+    CHK(c, hipHostMalloc((void **)&blk, (size_t)L.total, hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(blk, 0, (size_t)L.total);
+    if (c->state_set) {                                                   // the counters as the scenes stand: what a step's k_scene_harvest writes from then on
+        std::vector<int32_t> live((size_t)B), steps((size_t)B);
+        if (int r = sca_get_scene_state(c, live.data(), steps.data())) { (void)hipHostFree(blk); return r; }
+        int32_t *cnt = (int32_t *)(blk + L.off[HV_COUNTERS]);
+        for (int s = 0; s < B; s++) { cnt[2 * s] = live[s]; cnt[2 * s + 1] = steps[s]; }
+    }
+    if (int r = scene_harvest_drop(c)) { (void)hipHostFree(blk); return r; }
+    c->scenes.hv_host = blk; c->scenes.hv_layout = L; c->scenes.hv_batch_step = 0;
+    return 0;
+}
+int sca_scene_harvest_get(sca_ctx *c, sca_scene_harvest *out, int32_t struct_bytes) {
+    API_ENTER(c);
+    const int B = c->scenes.on ? c->scenes.v.nscenes : 0;
+    if (int r = scene_harvest_refuse(c, "sca_scene_harvest_get", scene_harvest_check(HARVEST_GET, B, c->scenes.begun, c->scenes.hv_host != nullptr, out != nullptr, struct_bytes))) return r;
+    const HarvestLayout &L = c->scenes.hv_layout;
+    uint8_t *b = c->scenes.hv_host;
+    sca_scene_harvest h;
+    std::memset(&h, 0, sizeof h);
+    h.struct_bytes = struct_bytes; h.nscenes = B; h.n = c->n;
+    h.counters = (int32_t *)(b + L.off[HV_COUNTERS]); h.summary = (sca_scene_summary *)(b + L.off[HV_SUMMARY]);
+    h.pos = (double *)(b + L.off[HV_POS]); h.vel = (float *)(b + L.off[HV_VEL]); h.heading = (double *)(b + L.off[HV_HEADING]);
+    h.flags = b + L.off[HV_FLAGS]; h.total_dist = (double *)(b + L.off[HV_TOTAL_DIST]); h.step_num = (int32_t *)(b + L.off[HV_STEP_NUM]);
+    size_t fit = offsetof(sca_scene_harvest, counters);                  // only the members that fit entirely into the caller's struct
+    while (fit + sizeof(void *) <= (size_t)struct_bytes) fit += sizeof(void *);
+    std::memcpy(out, &h, fit);
+    return 0;
+}
+int sca_scene_harvest_collect(sca_ctx *c, int32_t *scene_ids, int32_t *count) {
+    API_ENTER(c);
+    const int B = c->scenes.on ? c->scenes.v.nscenes : 0;
+    if (int r = scene_harvest_refuse(c, "sca_scene_harvest_collect", scene_harvest_check(HARVEST_COLLECT, B, c->scenes.begun, c->scenes.hv_host != nullptr, scene_ids && count, 0))) return r;
+    CHK(c, hipStreamSynchronize(c->stream));                              // (nothing to wait for directly behind sca_env_step)
+    sca_scene_summary *sum = (sca_scene_summary *)(c->scenes.hv_host + c->scenes.hv_layout.off[HV_SUMMARY]);
+    *count = scene_harvest_order(B, sum, scene_ids);
+    scene_harvest_clear_fresh(c, *count, scene_ids);
     return 0;
 }
 

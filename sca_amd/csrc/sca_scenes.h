@@ -4,6 +4,7 @@
 // One context holds B scenes; scene s is the contiguous agent range [offsets[s], offsets[s + 1]).  Each scene is one job of k_kd_block
 // (its whole tree by one workgroup in LDS), hence at most KD_WAVE_CAP agents per scene.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
@@ -306,5 +307,61 @@ inline SceneLogCheck scene_log_check(int nscenes, const int32_t *offsets, bool e
     return {SCENE_LOG_OK, scene};
 }
 inline int scene_log_error_code(SceneLogFault f) { return f == SCENE_LOG_OK ? SCA_OK : f <= SCENE_LOG_OFF ? SCA_ERR_STATE : SCA_ERR_ARG; }
+
+// ---- finished scenes hand over their result with the step (sca_scene_harvest_enable) -----------------------------------------------------------
+// One page-locked block of the library's, written by k_scene_harvest, the last kernel of a step: every scene's `live` and `steps` counters
+// on every step, and for a scene that finished in the step its occupied rows (the columns of sca_get_state) and one sca_scene_summary.
+// Every scene writes at ITS OWN place -- counters 2 s, summary s, rows offsets[s] + i, the index the rows have in the context -- so there is
+// no cursor, no atomic and no order that depends on scheduling, and since a scene finishes at most once between two restarts nothing is
+// ever overwritten before the host had its chance to read it.  Sections in the order of sca_scene_harvest's pointers, each on a 128-byte
+// boundary (a line of the link's writes is never shared by two sections).
+enum HarvestSection : int { HV_COUNTERS = 0, HV_SUMMARY, HV_POS, HV_VEL, HV_HEADING, HV_FLAGS, HV_TOTAL_DIST, HV_STEP_NUM, HV_SECTIONS };
+constexpr int64_t HV_ALIGN = 128;
+static_assert(sizeof(sca_scene_summary) == 64, "one summary record is half a 128-byte line");
+struct HarvestLayout { int64_t off[HV_SECTIONS]; int64_t total; };
+// counters: live, steps (i32 x 2) and the summary per SCENE; the rest per AGENT ROW, as in the host state block (host_section_row_bytes)
+inline int64_t harvest_section_bytes(int s, int nscenes, int n) {
+    return s == HV_COUNTERS ? 8 * (int64_t)nscenes : s == HV_SUMMARY ? (int64_t)sizeof(sca_scene_summary) * nscenes
+           : (s == HV_POS || s == HV_HEADING ? 24 : s == HV_VEL ? 12 : s == HV_TOTAL_DIST ? 8 : s == HV_STEP_NUM ? 4 : 1) * (int64_t)n;
+}
+inline HarvestLayout scene_harvest_layout(int nscenes, int n) {
+    HarvestLayout L;
+    int64_t at = 0;
+    for (int s = 0; s < HV_SECTIONS; s++) {
+        L.off[s] = at;
+        at += (harvest_section_bytes(s, nscenes, n) + HV_ALIGN - 1) / HV_ALIGN * HV_ALIGN;
+    }
+    L.total = at;
+    return L;
+}
+
+enum HarvestFault {
+    HARVEST_OK = 0,
+    HARVEST_NO_SCENES,      // the context holds no scenes                                                     } SCA_ERR_STATE
+    HARVEST_MID_STEP,       // enable / disable between a policy pass and its env update                       }
+    HARVEST_OFF,            // get / collect: the harvest is not enabled                                       }
+    HARVEST_NO_OUT,         // get / collect: an output pointer is NULL                                        } SCA_ERR_ARG
+    HARVEST_BAD_STRUCT      // get: struct_bytes outside [the leading integers, the library's struct]          }
+};
+enum HarvestOp { HARVEST_ENABLE = 0, HARVEST_GET, HARVEST_COLLECT };        // (enable: on or off, the rules are the same)
+// struct_bytes is looked at for HARVEST_GET only: at least sca_scene_harvest's leading integers, at most the struct (sca_host_state_get's rule)
+inline HarvestFault scene_harvest_check(HarvestOp op, int nscenes, bool scene_begun, bool enabled, bool have_out, int struct_bytes) {
+    if (nscenes <= 0) return HARVEST_NO_SCENES;
+    if (op == HARVEST_ENABLE) return scene_begun ? HARVEST_MID_STEP : HARVEST_OK;
+    if (!enabled) return HARVEST_OFF;
+    if (!have_out) return HARVEST_NO_OUT;
+    if (op == HARVEST_GET && (struct_bytes < (int)offsetof(sca_scene_harvest, counters) || struct_bytes > (int)sizeof(sca_scene_harvest))) return HARVEST_BAD_STRUCT;
+    return HARVEST_OK;
+}
+inline int scene_harvest_error_code(HarvestFault f) { return f == HARVEST_OK ? SCA_OK : f <= HARVEST_OFF ? SCA_ERR_STATE : SCA_ERR_ARG; }
+
+// sca_scene_harvest_collect's answer from the summaries as they stand: the scenes whose `fresh` word is set, ascending (batch_step, scene
+// id), into ids[nscenes]; returns how many.  Reads only (the caller clears the words).
+inline int scene_harvest_order(int nscenes, const sca_scene_summary *sum, int32_t *ids) {
+    int count = 0;
+    for (int s = 0; s < nscenes; s++) if (sum[s].fresh) ids[count++] = s;
+    std::stable_sort(ids, ids + count, [sum](int32_t a, int32_t b) { return sum[a].batch_step < sum[b].batch_step; });   // stable: ids of one batch step stay ascending
+    return count;
+}
 
 }  // namespace sca

@@ -309,4 +309,88 @@ __global__ __launch_bounds__(SCENE_LOG_T) void k_scene_log(DeviceView d, SceneVi
     reinterpret_cast<scene_log_quarter *>(L.rows + scene_log_index(L.capacity, lo, v.offsets[s + 1] - lo, row, agent - lo))[q] = w;
 }
 
+// ---- finished scenes hand over their result with the step (sca_scene_harvest_enable; the block's layout is sca_scenes.h's) -------------------
+// Enqueued BEHIND k_collide_finish_scenes, the last kernel of a step in every step form: live[s] is the step's final count, prev[s] what the
+// step found, and the records K4 wrote (`rec`: the buffer the host swaps in behind this launch) carry the final flags.  One workgroup per
+// scene.  Its counters go into the block on every step; everything else only in the one step per episode the scene finishes in -- a
+// finished scene has prev == 0 on every later step until a restart makes it live again -- so the block's rows and summary of a scene are
+// written at most once between two restarts.  Rows behind size[s] (vacant, sca_restart_scenes_sized) are never touched, nor is anything of
+// another scene: the flag bytes of a scene that does not begin or end on a 4-byte boundary are written as bytes at its edges.
+// The block is host memory: every section is written as consecutive 4-byte words (16 flag bytes per lane in the interior) by consecutive
+// lanes, as k_host_egress writes the host state block.
+struct HarvestDev {
+    const PubRec *rec;        // [n] the records this step's K4 wrote
+    const double *heading;    // [n*3]
+    const double *total_dist; // [n]
+    const int32_t *step_num;  // [n]
+    const int32_t *size;      // [nscenes] the rows each scene occupies (k_kd_scene_jobs' array)
+    uint8_t *blk;             // the page-locked block
+    HarvestLayout L;
+    int32_t batch_step;       // the context's env updates since the harvest was enabled, this one included
+};
+typedef uint32_t __attribute__((may_alias)) harvest_u32;
+constexpr int HARVEST_T = 256;
+__global__ __launch_bounds__(HARVEST_T) void k_scene_harvest(SceneView v, HarvestDev h) {
+    const int s = (int)blockIdx.x, t = (int)threadIdx.x;
+    const int live = v.live[s * SCENE_LINE], steps = v.steps[s];
+    if (t < 2) ((int32_t *)(h.blk + h.L.off[HV_COUNTERS]))[2 * s + t] = t == 0 ? live : steps;
+    if (!(v.prev[s] > 0 && live == 0)) return;                              // (uniform over the workgroup)
+    const int lo = v.offsets[s], ns = h.size[s];
+    const harvest_u32 *rec = (const harvest_u32 *)(h.rec + lo);             // 12 words per record: px py pz (0-5), vx vy vz (6-8), flags (9)
+    constexpr int RW = (int)(sizeof(PubRec) / 4);
+    static_assert(sizeof(PubRec) == 48, "k_scene_harvest reads the records as 12 words");
+    harvest_u32 *pos = (harvest_u32 *)(h.blk + h.L.off[HV_POS]) + 6 * (int64_t)lo;
+    for (int w = t; w < 6 * ns; w += HARVEST_T) pos[w] = rec[(w / 6) * RW + w % 6];
+    harvest_u32 *vel = (harvest_u32 *)(h.blk + h.L.off[HV_VEL]) + 3 * (int64_t)lo;
+    for (int w = t; w < 3 * ns; w += HARVEST_T) vel[w] = rec[(w / 3) * RW + 6 + w % 3];
+    harvest_u32 *head = (harvest_u32 *)(h.blk + h.L.off[HV_HEADING]) + 6 * (int64_t)lo;
+    const harvest_u32 *head_in = (const harvest_u32 *)(h.heading + 3 * (int64_t)lo);
+    for (int w = t; w < 6 * ns; w += HARVEST_T) head[w] = head_in[w];
+    harvest_u32 *td = (harvest_u32 *)(h.blk + h.L.off[HV_TOTAL_DIST]) + 2 * (int64_t)lo;
+    const harvest_u32 *td_in = (const harvest_u32 *)(h.total_dist + lo);
+    for (int w = t; w < 2 * ns; w += HARVEST_T) td[w] = td_in[w];
+    int32_t *sn = (int32_t *)(h.blk + h.L.off[HV_STEP_NUM]) + lo;
+    for (int i = t; i < ns; i += HARVEST_T) sn[i] = h.step_num[lo + i];
+    // flags, (uint8_t)rec.flags as sca_get_state gives them: bytes up to the first 4-byte boundary of the section, words, bytes behind the last
+    uint8_t *fl = h.blk + h.L.off[HV_FLAGS] + lo;
+    const int head_bytes = min(ns, (4 - (lo & 3)) & 3), words = (ns - head_bytes) / 4;
+    for (int w = t; w < words; w += HARVEST_T) {
+        uint32_t x = 0;
+        for (int b = 0; b < 4; b++) x |= (rec[(head_bytes + 4 * w + b) * RW + 9] & 0xffu) << (8 * b);
+        ((harvest_u32 *)(fl + head_bytes))[w] = x;
+    }
+    for (int i = t; i < ns - 4 * words; i += HARVEST_T) {
+        const int a = i < head_bytes ? i : 4 * words + i;
+        fl[a] = (uint8_t)rec[a * RW + 9];
+    }
+    // the summary: counts and the integer sum through LDS, the distance by one lane in ascending row order (metrics.episode_metrics adds
+    // Python floats in that order, and the sum of doubles depends on it)
+    __shared__ int cnt[4];
+    __shared__ unsigned long long step_sum;
+    if (t < 4) cnt[t] = 0;
+    if (t == 0) step_sum = 0ull;
+    __syncthreads();
+    int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+    long long st = 0;
+    for (int i = t; i < ns; i += HARVEST_T) {
+        const uint32_t f = rec[i * RW + 9];
+        c0 += (f & FLAG_AT_GOAL) ? 1 : 0; c1 += (f & FLAG_COLLISION) ? 1 : 0; c2 += (f & FLAG_TIMEOUT) ? 1 : 0;
+        if (!(f & (FLAG_COLLISION | FLAG_TIMEOUT))) { c3 += 1; st += h.step_num[lo + i]; }
+    }
+    if (c0) atomicAdd(&cnt[0], c0);
+    if (c1) atomicAdd(&cnt[1], c1);
+    if (c2) atomicAdd(&cnt[2], c2);
+    if (c3) { atomicAdd(&cnt[3], c3); atomicAdd(&step_sum, (unsigned long long)st); }
+    __syncthreads();
+    if (t != 0) return;
+    double dist = 0.0;
+    for (int i = 0; i < ns; i++)
+        if (!(rec[i * RW + 9] & (FLAG_COLLISION | FLAG_TIMEOUT))) dist += h.total_dist[lo + i];
+    sca_scene_summary r;
+    r.fresh = 1; r.steps = steps; r.batch_step = h.batch_step;
+    r.arrived = cnt[0]; r.collided = cnt[1]; r.timed_out = cnt[2]; r.successful_num = cnt[3]; r.reserved0 = 0;
+    r.all_step_num = (int64_t)step_sum; r.all_distance = dist; r.reserved1[0] = 0; r.reserved1[1] = 0;
+    ((sca_scene_summary *)(h.blk + h.L.off[HV_SUMMARY]))[s] = r;
+}
+
 }  // namespace sca

@@ -55,12 +55,44 @@ def episode_metrics(env, total_policy_time_s=None):
     return out
 
 
-def episode_info(env, total_policy_time_s=None):
-    """The `info_dict_to_visualize` of run_sca.py:199-259."""
+def episode_metrics_from_harvest(agents, harvested, total_policy_time_s):
+    """episode_metrics(batch.env(s)) -- same keys, same values -- from what the step that finished the scene handed over
+    (SceneBatch.harvested(s)) instead of a read-back of the batch: successful_num, all_distance and all_step_num are the summary's (the
+    device adds the distances in agent order, as the loop above does), the straight distances and the desired steps are the agents' host
+    constants, masked by the harvested flags and summed in agent order.  total_policy_time_s: the episode's policy wall time (there is
+    no agent.total_time without the batch's mirrors; scenes.run_episodes passes the same sum)."""
+    from . import solver as S
+    summary, flags = harvested['summary'], harvested['flags']
+    n = len(agents)
+    num = int(summary['successful_num'])
+    straight = 0.0
+    desire = 0
+    for a, f in zip(agents, flags):
+        if not (int(f) & (S.FLAG_COLLISION | S.FLAG_TIMEOUT)):
+            straight += a.straight_path_length
+            desire += a.desire_steps
+    dist = float(summary['all_distance'])
+    steps = int(summary['all_step_num'])
+    out = {
+        'successful_num': num, 'all_straight_distance': straight, 'all_distance': dist, 'all_desire_step_num': desire,
+        'all_step_num': steps, 'SuccessRate': num / n,
+        'ExtraTime': ((steps - desire) * DT) / num if num else float('nan'),
+        'ExtraDistance': (dist - straight) / num if num else float('nan'),
+        'AverageSpeed': dist / steps / DT if steps else float('nan'),
+    }
+    if steps:
+        out['AverageCost'] = 1000 * total_policy_time_s / steps
+    return out
+
+
+def episode_info(env, total_policy_time_s=None, m=None):
+    """The `info_dict_to_visualize` of run_sca.py:199-259.  m: the episode's metrics where the caller has them already
+    (episode_metrics_from_harvest, with total_policy_time_s): nothing is read of the agents' state then."""
     if total_policy_time_s is None:                      # run_sca.py:241: all_compute_time sums agent.total_time
         ok = [(not a.is_collision) and (not a.is_out_of_max_time) for a in env.agents]
         total_policy_time_s = sum(a.total_time for a, k in zip(env.agents, ok) if k)
-    m = episode_metrics(env, total_policy_time_s)
+    if m is None:
+        m = episode_metrics(env, total_policy_time_s)
     info = {
         'all_agent_info': [{'id': a.id, 'gp': a.group, 'radius': a.radius, 'goal_pos': np.asarray(a.goal_global_frame).tolist()}
                            for a in env.agents],

@@ -122,8 +122,11 @@ class SceneEnv:
 
 class SceneBatch(_FlatAgents):
     def __init__(self, scenes, obstacles=(), scene_obstacles=None, neighbor_mode=S.NBR_KDTREE, device_tracker=False, history_capacity=0, scene_history=0, device=0,
-                 capacities=None):
-        """capacities: one agent capacity per scene, each >= len(scene) (None: the scene's own length).  Scene s then owns capacities[s] rows
+                 capacities=None, harvest=False):
+        """harvest: finished scenes hand over their result with the step (sca_scene_harvest_enable): step() reads `active` / `steps` from the
+        harvest block behind the step's own synchronisation instead of a second read-back, finished() names the scenes that ended since it
+        was last called and harvested(s) gives a finished scene's final rows and summary without a read-back of the batch.
+        capacities: one agent capacity per scene, each >= len(scene) (None: the scene's own length).  Scene s then owns capacities[s] rows
         of the context and holds its episode in the first of them; the rows behind are vacant (sca_restart_scenes_sized), and a later
         restart may bring any episode of 1 .. capacities[s] agents (without `capacities` a slot keeps its size).  The spare rows are set up as copies of the scene's last agent, so a slot's
         solver and planner attributes are those of the episode it started with."""
@@ -190,6 +193,10 @@ class SceneBatch(_FlatAgents):
             self.scene_history = capped
         if self.scene_history:
             self.solver.scene_history_enable(self.scene_history)
+        self.harvest = bool(harvest)
+        if self.harvest:
+            self.solver.scene_harvest_enable()
+            self._harvest = self.solver.scene_harvest()           # views of the block: read behind a step's synchronisation
 
     def __len__(self):
         return len(self._envs)
@@ -202,7 +209,31 @@ class SceneBatch(_FlatAgents):
         return self.active == 0
 
     def close(self):
+        self._harvest = None
         self.solver.close()
+
+    # ---- finished scenes hand over their result with the step (SceneBatch(harvest=True)) ----------------------------------------------------
+    def finished(self):
+        """the scenes that finished since the last call, in the order they finished (batch step, then scene id)"""
+        if not self.harvest:
+            raise RuntimeError('finished(): a SceneBatch(harvest=True) hands finished scenes over; this one was built without')
+        return self.solver.scene_harvest_collect()
+
+    def harvested(self, s):
+        """dict(pos, vel, heading, flags, total_dist, step_num, summary) of a finished scene: its occupied rows as the step that finished it
+        left them (what solver.get_state() gives for them) and the device's summary (steps, batch_step, arrived, collided, timed_out,
+        successful_num, all_step_num, all_distance).  Copies: the block's rows are overwritten when the slot finishes again.  Take them
+        before the scene is restarted."""
+        if not self.harvest:
+            raise RuntimeError('harvested(): a SceneBatch(harvest=True) hands finished scenes over; this one was built without')
+        s = int(s)
+        lo = int(self.offsets[s])
+        hi = lo + int(self.sizes[s])
+        out = {k: self._harvest[k][lo:hi].copy() for k in self._mirror}
+        rec = self._harvest['summary'][s]
+        out['summary'] = {k: rec[k].item() for k in ('steps', 'batch_step', 'arrived', 'collided', 'timed_out', 'successful_num', 'all_step_num',
+                                                     'all_distance')}
+        return out
 
     # ---- a new episode into a slot while the others keep running (sca_restart_scenes) -------------------------------------------------------
     def restart(self, scenes):
@@ -251,8 +282,12 @@ class SceneBatch(_FlatAgents):
         self._stale = True                                           # the mirrors (views of the batch's arrays) refresh in place on first use
         self._nbr_cache = None
         self._vpref_cache = None
-        st = self.solver.scene_state()
-        self.active, self.steps = st['active'], st['steps']
+        if self.harvest:                                             # what the restart leaves, without a read-back: all of the episode live, no step taken
+            for s, agents in items:
+                self.active[s], self.steps[s] = len(agents), 0
+        else:
+            st = self.solver.scene_state()
+            self.active, self.steps = st['active'], st['steps']
 
     def _send_restart(self, items):
         """the episodes' arrays to the device (one call), and the batch's per-agent host arrays behind them"""
@@ -288,8 +323,11 @@ class SceneBatch(_FlatAgents):
         served = max(1, int(self.active.sum()))
         total = self.solver.env_step(self.neighbor_mode)
         share = (time.perf_counter() - t0) / served               # a step's policy wall time, shared among the agents it served
-        st = self.solver.scene_state()
-        self.active, self.steps = st['active'], st['steps']
+        if self.harvest:                                          # written by the step's last kernel, readable behind env_step's synchronisation
+            self.active, self.steps = self._harvest['active'].copy(), self._harvest['steps'].copy()
+        else:
+            st = self.solver.scene_state()
+            self.active, self.steps = st['active'], st['steps']
         for view, was in zip(self._envs, live):
             if was:
                 view._time_cum.append(view._time_cum[-1] + share)
@@ -375,7 +413,15 @@ def plan_queue(sizes, slots, capacities=None):
     return [holding[s] for s in used], [capacities[s] for s in used]
 
 
-def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=None, max_steps=None, stats=None, history_rows=0, capacities=None):
+def _harvest_policy_time(view, h):
+    """what episode_metrics sums by default -- agent.total_time over the successful agents, in agent order -- from the harvested rows"""
+    cum = view._time_cum
+    ok = (h['flags'] & (S.FLAG_COLLISION | S.FLAG_TIMEOUT)) == 0
+    return sum(cum[min(int(k), len(cum) - 1)] for k, good in zip(h['step_num'], ok) if good)
+
+
+def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=None, max_steps=None, stats=None, history_rows=0, capacities=None,
+                 harvest=False):
     """Streams a queue of episodes (Agent lists, each numbered 0 .. n - 1) through `slots` scenes of ONE SceneBatch: when a scene finishes,
     its metrics, step count and final state are taken and the slot restarts with the next episode of its size (SceneBatch.restart), while
     the other slots keep running.  Obstacles are one list shared by all episodes.  Returns one dict per episode in queue order:
@@ -390,7 +436,9 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
     longer than K does not stop the queue.  capacities='max' (or a list, one agent capacity per slot) makes the slots CAPACITY slots: a slot
     starts with, and later takes, the first pending episode in queue order that fits it, whatever its agent count (plan_capacity_slots,
     next_fitting), so a queue that mixes counts streams through one set of slots; ValueError before the first step when an episode fits no
-    slot.  live_fraction then counts the slots' capacities as the batch's agent rows."""
+    slot.  live_fraction then counts the slots' capacities as the batch's agent rows.  harvest=True: the same results, on_done order and
+    stats, taken from what the finishing step itself handed over (SceneBatch(harvest=True): finished() / harvested()) -- one
+    synchronisation per step and, per finished episode, its own rows instead of a read-back of the whole batch."""
     episodes = [list(e) for e in episodes]
     sizes = [len(e) for e in episodes]
     holding, caps = plan_queue(sizes, slots, capacities)
@@ -401,7 +449,7 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
         raise ValueError('run_episodes: episode %d needs the device tracker, but none of the episodes the slots start with does, so the batch '
                          'would run without one: put a tracked episode among the first %d' % (min(i for i in pending if tracked[i]), len(holding)))
     batch = SceneBatch([episodes[i] for i in holding], obstacles, device_tracker=device_tracker, scene_history=history_rows,
-                       capacities=None if capacities is None else caps)
+                       capacities=None if capacities is None else caps, harvest=harvest)
     results = [None] * len(episodes)
     batch_steps = served = 0
     try:
@@ -410,16 +458,23 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
             batch.step()
             batch_steps += 1
             refill = {}
-            for s, i in enumerate(holding):
-                if i is None or not batch.done[s]:
-                    continue
-                lo, hi = int(batch.offsets[s]), int(batch.offsets[s]) + int(batch.sizes[s])
-                results[i] = dict(episode=i, slot=s, metrics=metrics.episode_metrics(batch.env(s)), steps=int(batch.steps[s]),
-                                  state={k: batch._state(k)[lo:hi].copy() for k in batch._mirror})
+            # (one step per collect: finished() is in slot order, as the scan of batch.done is)
+            for s in (batch.finished() if harvest else [s for s, i in enumerate(holding) if i is not None and batch.done[s]]):
+                i = holding[s]
+                view, info_args = batch.env(s), {}
+                if harvest:
+                    h = batch.harvested(s)
+                    t_policy = _harvest_policy_time(view, h)
+                    m = metrics.episode_metrics_from_harvest(episodes[i], h, t_policy)
+                    results[i] = dict(episode=i, slot=s, metrics=m, steps=int(h['summary']['steps']), state={k: h[k] for k in batch._mirror})
+                    info_args = dict(total_policy_time_s=t_policy, m=m)
+                else:
+                    lo, hi = int(batch.offsets[s]), int(batch.offsets[s]) + int(batch.sizes[s])
+                    results[i] = dict(episode=i, slot=s, metrics=metrics.episode_metrics(view), steps=int(batch.steps[s]),
+                                      state={k: batch._state(k)[lo:hi].copy() for k in batch._mirror})
                 if batch.scene_history:
-                    view = batch.env(s)
                     rows, dropped = view.solver.history_rows()
-                    results[i].update(trajectories=metrics.trajectories(view, rows=rows), rows_dropped=dropped, info=metrics.episode_info(view))
+                    results[i].update(trajectories=metrics.trajectories(view, rows=rows), rows_dropped=dropped, info=metrics.episode_info(view, **info_args))
                 if on_done is not None:
                     on_done(results[i])
                 left = [sizes[j] for j in pending]

@@ -51,12 +51,14 @@ class BatchedSolver:
         self.nscenes = 0
         self.scene_offsets = None
         self._host_state = None
+        self._harvest = None
 
     def close(self):
         if getattr(self, 'ctx', None):
             self.L.sca_destroy(self.ctx)                          # (frees the host state block: views of it must not be used after close())
             self.ctx = None
         self._host_state = None
+        self._harvest = None
 
     def __del__(self):
         try:
@@ -88,6 +90,7 @@ class BatchedSolver:
         self._host_state = None                                   # the block's layout follows n: host_state() fetches it again
         self.nscenes = 0                                          # (sca_set_agents clears the scenes)
         self.scene_offsets = None
+        self._harvest = None                                      # (... and with them the harvest block)
         self._chk(self.L.sca_set_agents(self.ctx, n, _lib.ptr(radius, C.c_double), _lib.ptr(pref_speed, C.c_double),
                                         _lib.ptr(goal, C.c_double), _lib.ptr(policy, C.c_uint8),
                                         _lib.ptr(zaxis, C.c_uint8), _lib.ptr(mrd, C.c_double)), 'sca_set_agents')
@@ -179,6 +182,7 @@ class BatchedSolver:
     def set_scenes(self, offsets):
         """Scene s = agents [offsets[s], offsets[s + 1]); None / [] for a plain context again.  After set_agents; resets the kd permutation to
         the identity and the per-scene counters.  A scene holds at most 1536 agents."""
+        self._harvest = None                                      # (redefining or clearing the scenes drops the harvest block)
         if offsets is None or len(offsets) == 0:
             self._chk(self.L.sca_set_scenes(self.ctx, 0, None), 'sca_set_scenes')
             self.nscenes = 0
@@ -294,6 +298,46 @@ class BatchedSolver:
                                                _lib.ptr(out['pos'], C.c_double), _lib.ptr(out['heading'], C.c_double),
                                                _lib.ptr(out['vel'], C.c_float)), 'sca_get_scene_history')
         return out
+
+    # ---- finished scenes hand over their result with the step (sca_scene_harvest_enable) ----------------------------------
+    def scene_harvest_enable(self, on=True):
+        """From now on every step ends with k_scene_harvest: the scenes' counters, and the rows and summary of every scene that finished in
+        the step, stand in a page-locked block after the step's own synchronisation (scene_harvest(), scene_harvest_collect()).  on=False
+        frees the block: views handed out before must not be used any more."""
+        self._harvest = None
+        self._chk(self.L.sca_scene_harvest_enable(self.ctx, 1 if on else 0), 'sca_scene_harvest_enable')
+
+    def scene_harvest(self):
+        """The harvest block as a dict of numpy VIEWS (no copies), made once per scene_harvest_enable: active, steps (B,) i32 -- every step --;
+        summary (B,) records (_lib.SUMMARY_DTYPE); pos (n, 3) f64, vel (n, 3) f32, heading (n, 3) f64, flags (n,) u8, total_dist (n,) f64,
+        step_num (n,) i32 -- rows [offsets[s], offsets[s] + size[s]) of a scene once it has finished, valid until it is restarted or finishes
+        again.  The views keep the solver alive; set_agents, set_scenes, scene_harvest_enable and close() free the block under them."""
+        if self._harvest is None:
+            h = _lib.SceneHarvest()
+            self._chk(self.L.sca_scene_harvest_get(self.ctx, C.byref(h), C.sizeof(h)), 'sca_scene_harvest_get')
+            n, b = h.n, h.nscenes
+            owner = _BlockOwner(self)
+
+            def view(p, ct, dt, shape):
+                count = int(np.prod(shape))
+                buf = (ct * count).from_address(C.addressof(p.contents))
+                buf._sca_owner = owner
+                return np.frombuffer(buf, dtype=dt, count=count).reshape(shape)
+            counters = view(h.counters, C.c_int32, np.int32, (b, 2))
+            self._harvest = dict(
+                active=counters[:, 0], steps=counters[:, 1], summary=view(h.summary, _lib.SceneSummary, _lib.SUMMARY_DTYPE, (b,)),
+                pos=view(h.pos, C.c_double, np.float64, (n, 3)), vel=view(h.vel, C.c_float, np.float32, (n, 3)),
+                heading=view(h.heading, C.c_double, np.float64, (n, 3)), flags=view(h.flags, C.c_uint8, np.uint8, (n,)),
+                total_dist=view(h.total_dist, C.c_double, np.float64, (n,)), step_num=view(h.step_num, C.c_int32, np.int32, (n,)))
+        return self._harvest
+
+    def scene_harvest_collect(self):
+        """The scenes that finished since the last call, a list of ids in ascending (batch step, id); synchronises the context's stream
+        (nothing to wait for directly behind env_step).  An uncollected scene that is restarted is never reported."""
+        ids = np.zeros(max(1, self.nscenes), np.int32)
+        count = C.c_int32(0)
+        self._chk(self.L.sca_scene_harvest_collect(self.ctx, _lib.ptr(ids, C.c_int32), C.byref(count)), 'sca_scene_harvest_collect')
+        return [int(s) for s in ids[:count.value]]
 
     # ---- SCA's v_pref tracker on the device (scaPolicy.py:264-338) ---------------------------------------
     def device_tracker_enable(self, goal_heading, turning_radius=1.5, pitchlims=(-math.pi / 4, math.pi / 4), in_pass=True):

@@ -25,7 +25,22 @@ the same B slots in the two ways scenes.run_episodes has, alternated:
               exhausted idle to the end
     capacity  capacities='max': every slot holds up to the largest count and takes the first pending episode (sca_restart_scenes_sized)
 Identical final states per episode in both legs (asserted); per leg episodes/s, batch steps and the live fraction (agents served / batch steps x
-the batch's agent rows).  Beside them one sized restart call naming 1 and B / 4 scenes of that batch."""
+the batch's agent rows).  Beside them one sized restart call naming 1 and B / 4 scenes of that batch.
+
+    python tools/bench/scene_refill_cost.py --harvest                             # 64 slots / 256 episodes -> profiles/scene_harvest_cost.json
+    python tools/bench/scene_refill_cost.py --harvest --slots 1024 --waves 4      # 1024 slots / 4096 episodes, added to the same file
+    python tools/bench/scene_refill_cost.py --harvest --parent-json parent.json   # ... held against the parent commit's `stream` windows
+
+--harvest: the same queue streamed with run_episodes(harvest=False) and run_episodes(harvest=True), alternated:
+    stream    the finished scene's state is cut out of a read-back of the whole batch, active / steps come with a second synchronisation
+    harvest   the step that finishes a scene hands its rows and summary over (sca_scene_harvest_enable)
+Identical final states per episode in both legs (asserted).  Per leg, beside the figures above: ms per batch step, the library's
+synchronisations per batch step (counted per call: sca_env_step 1, sca_get_scene_state 1, sca_get_state 2, sca_scene_harvest_collect 1 -- on
+a stream sca_env_step has just drained --, sca_restart_scenes 1) and the bytes that crossed the link per finished episode for its result
+(sca_get_state: 84 B for every agent row of the batch, once per step in which a scene finished; the harvest: 77 B per row of the episode
+and its 64-byte summary).  --parent-json: a scene_refill_cost.json written by the PARENT commit's tool on the same machine (same --slots,
+--waves; --alternations 5); its `stream` windows are copied into the record, with whether this build's harvest=False leg lies inside their
+min .. max.  The file keeps one entry per --slots under `runs`."""
 import argparse
 import json
 import os
@@ -48,10 +63,14 @@ def main():
     ap.add_argument('--episode-cap', type=int, default=4000, help='candidate episodes that have not ended after this many steps are left out of the queue')
     ap.add_argument('--mixed', action='store_true', help='a queue of mixed agent counts: fixed-size slots against capacity slots')
     ap.add_argument('--sizes', default='20,50,100', help='--mixed: the agent counts the episodes are drawn from')
+    ap.add_argument('--harvest', action='store_true', help='the streamed queue with and without the scene harvest')
+    ap.add_argument('--parent-json', default=None, help="--harvest: the parent commit's scene_refill_cost.json of the same queue on the same machine")
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    if args.harvest and args.mixed:
+        ap.error('--harvest and --mixed are two comparisons: one at a time')
     if args.out is None:
-        args.out = os.path.join(REPO, 'profiles', 'scene_sizes_cost.json' if args.mixed else 'scene_refill_cost.json')
+        args.out = os.path.join(REPO, 'profiles', 'scene_harvest_cost.json' if args.harvest else 'scene_sizes_cost.json' if args.mixed else 'scene_refill_cost.json')
     sys.path.insert(0, REPO)
     from sca_amd import env as E, scenarios, scenes, solver as sol_mod
     pols = [E.SCAPolicy, E.RVO3DPolicy, E.SRVO3DPolicy, E.ORCA3DPolicy, E.ORCA3DPolicyOfficial, E.RVO3dDubinsPolicy]
@@ -101,14 +120,42 @@ def main():
             batch.close()
         return time.perf_counter() - t0, states, dict(batch_steps=steps, agent_steps=served, live_fraction=served / (steps * B * n1))
 
-    def run_stream(capacities=None):
+    # --harvest: the library calls that synchronise, counted at the solver's methods while a leg runs (weights: synchronisations per call)
+    SYNCS = dict(env_step=1, scene_state=1, get_state=2, scene_harvest_collect=1, restart_scenes=1)
+
+    def counted(fn):
+        calls = {k: 0 for k in SYNCS}
+        keep = {k: getattr(sol_mod.BatchedSolver, k) for k in SYNCS}
+
+        def wrap(name, inner):
+            def method(self, *a, **kw):
+                calls[name] += 1
+                return inner(self, *a, **kw)
+            return method
+        for k, inner in keep.items():
+            setattr(sol_mod.BatchedSolver, k, wrap(k, inner))
+        try:
+            return fn(), calls
+        finally:
+            for k, inner in keep.items():
+                setattr(sol_mod.BatchedSolver, k, inner)
+
+    def run_stream(capacities=None, harvest=None):
         eps = queue()
         stats = {}
+        kw = {} if harvest is None else dict(harvest=harvest)
         t0 = time.perf_counter()
-        res = scenes.run_episodes(eps, B, device_tracker=True, max_steps=args.max_steps, stats=stats, capacities=capacities)
-        return time.perf_counter() - t0, [r['state'] for r in res], stats
+        res, calls = counted(lambda: scenes.run_episodes(eps, B, device_tracker=True, max_steps=args.max_steps, stats=stats, capacities=capacities, **kw))
+        wall = time.perf_counter() - t0
+        if harvest is not None:
+            rows = sum(len(r['state']['flags']) for r in res)
+            stats['calls'] = calls
+            stats['syncs_per_batch_step'] = sum(SYNCS[k] * v for k, v in calls.items()) / stats['batch_steps']
+            stats['readback_bytes_per_episode'] = (77 * rows + 64 * len(res)) / len(res) if harvest else 84 * B * n1 * calls['get_state'] / len(res)
+        return wall, [r['state'] for r in res], stats
 
-    legs = {'fixed': run_stream, 'capacity': lambda: run_stream('max')} if args.mixed else {'waves': run_waves, 'stream': run_stream}
+    legs = {'fixed': run_stream, 'capacity': lambda: run_stream('max')} if args.mixed else \
+        {'stream': lambda: run_stream(harvest=False), 'harvest': lambda: run_stream(harvest=True)} if args.harvest else {'waves': run_waves, 'stream': run_stream}
     walls = {k: [] for k in legs}
     stats, first = {}, None
     for _ in range(args.alternations):
@@ -155,7 +202,7 @@ def main():
     restart = {'scenes_1_ms': restart_ms(1), 'scenes_%d_ms' % max(1, B // 4): restart_ms(max(1, B // 4)), 'step_ms': float(np.median(t_step)) * 1e3}
     batch.close()
 
-    doc = {'tool': 'tools/bench/scene_refill_cost.py' + (' --mixed' if args.mixed else ''), 'slots': B, 'episodes': count,
+    doc = {'tool': 'tools/bench/scene_refill_cost.py' + (' --mixed' if args.mixed else ' --harvest' if args.harvest else ''), 'slots': B, 'episodes': count,
            'agents_per_episode': {str(n): int((size_of[chosen] == n).sum()) for n in choices} if args.mixed else n1, 'alternations': args.alternations,
            'episode_cap': args.episode_cap, 'last_seed': chosen[-1], 'seeds_left_out_no_end_within_cap': left_out,
            'policies': 'SCA, RVO3D, S-RVO3D, ORCA3D, ORCA3D-LP, RVO3D+Dubins in turn; seeded random scenes; device tracker in the pass',
@@ -165,16 +212,35 @@ def main():
         st = stats[name]
         doc['legs'][name] = {'wall_s': wall, 'wall_s_all': walls[name], 'episodes_per_s': count / wall, 'agent_steps_per_s': st['agent_steps'] / wall,
                              'batch_steps': st['batch_steps'], 'agent_steps': st['agent_steps'], 'mean_live_fraction': st['live_fraction']}
-    ratio = 'capacity_over_fixed_episodes_per_s' if args.mixed else 'stream_over_waves_episodes_per_s'
-    over, under = ('capacity', 'fixed') if args.mixed else ('stream', 'waves')
+        if args.harvest:
+            doc['legs'][name].update(ms_per_batch_step=1e3 * wall / st['batch_steps'], syncs_per_batch_step=st['syncs_per_batch_step'],
+                                     readback_bytes_per_episode=st['readback_bytes_per_episode'], library_calls=st['calls'])
+    ratio = 'capacity_over_fixed_episodes_per_s' if args.mixed else 'harvest_over_stream_episodes_per_s' if args.harvest else 'stream_over_waves_episodes_per_s'
+    over, under = ('capacity', 'fixed') if args.mixed else ('harvest', 'stream') if args.harvest else ('stream', 'waves')
     doc[ratio] = doc['legs'][over]['episodes_per_s'] / doc['legs'][under]['episodes_per_s']
+    if args.harvest and args.parent_json:
+        with open(args.parent_json) as f:
+            parent = json.load(f)
+        assert (parent['slots'], parent['episodes'], parent['last_seed']) == (B, count, chosen[-1]), 'the parent ran another queue'
+        windows = parent['legs']['stream']['wall_s_all']
+        mine = doc['legs']['stream']['wall_s']
+        doc['parent_commit_stream'] = {'wall_s_all': windows, 'wall_s': parent['legs']['stream']['wall_s'], 'min_s': min(windows), 'max_s': max(windows),
+                                       'this_build_stream_wall_s': mine, 'inside_parent_spread': bool(min(windows) <= mine <= max(windows))}
+    if args.harvest:                                                 # one entry per --slots in the file
+        runs = {}
+        if os.path.exists(args.out):
+            with open(args.out) as f:
+                runs = json.load(f).get('runs', {})
+        runs[str(B)] = doc
+        doc = {'tool': 'tools/bench/scene_refill_cost.py --harvest', 'runs': runs}
     if args.mixed:
         doc['restart_call']['note'] = 'sca_restart_scenes_sized, the named slots of capacity %d taking the queue\'s next episodes' % cap
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as f:
         json.dump(doc, f, indent=1, sort_keys=True)
         f.write('\n')
-    print(json.dumps({k: doc[k] for k in ('legs', 'restart_call', ratio)}), flush=True)
+    shown = doc['runs'][str(B)] if args.harvest else doc
+    print(json.dumps({k: shown[k] for k in ('legs', 'restart_call', ratio, 'parent_commit_stream') if k in shown}), flush=True)
 
 
 if __name__ == '__main__':
