@@ -72,8 +72,11 @@ enum sca_neighbor_mode {
     SCA_NBR_GRID = 1,             /* uniform hashed grid, cells of neighbor_dist, rebuilt every step by a counting sort (three short
                                      launches instead of ~17 dependent tree levels; what multi-GPU runs want).  Lists hold the
                                      reference's (object, distSq) pairs whenever <= max_neighbors objects are in range; entries of
-                                     equal distSq are ordered obstacles first, then by agent id (the reference: kd visit order);
-                                     with more in range the 16 nearest are kept and SCA_ST_NBR_OVERFLOW is raised */
+                                     equal distSq are ordered obstacles first -- two obstacles in the order the obstacle tree's query
+                                     (kdTree.py:232-262) meets them --, then agents by id (the reference: kd visit order); with more in
+                                     range the agent's max_neighbors nearest in that order are kept and SCA_ST_NBR_OVERFLOW is raised
+                                     (after a collision: more than max_neighbors colliding objects; the bit may also stand on an agent
+                                     whose list was full before the pass met its first colliding object) */
     SCA_NBR_KDTREE_HOSTBUILD = 2, /* same tree built on the host from a position read-back (debug / A-B reference) */
     SCA_NBR_AUTO = 3              /* the reference's lists, entry for entry, at the grid's price: the grid query for every agent, and the
                                      kd query (kdTree.py:124-156) for the agents whose list the grid cannot give exactly -- more than

@@ -71,6 +71,8 @@ def lib():
         L.orc_set_dt_nominal.argtypes = [C.c_double]
         L.orc_set_agent_params.restype = None
         L.orc_set_agent_params.argtypes = [C.c_int, dp, ip, dp, dp, dp, dp, dp]
+        L.orc_set_list_rule.restype = None
+        L.orc_set_list_rule.argtypes = [C.c_int]
         L.orc_policy_step.restype = C.c_int
         L.orc_policy_step.argtypes = [C.c_int, C.c_int, dp, fp, dp, dp, dp, bp, dp, bp, bp, dp, bp, ip, dp, dp, dp, fp,
                                       ip, ip, bp, dp, bp, dp, ip, ip, C.c_int]
@@ -132,6 +134,15 @@ def set_agent_params(n=0, neighbor_dist=None, max_neighbors=None, time_step=None
     L.orc_set_agent_params(int(n), arr(neighbor_dist, np.float64, C.c_double), arr(max_neighbors, np.int32, C.c_int32), arr(time_step, np.float64, C.c_double),
                            arr(time_horizon, np.float64, C.c_double), arr(max_speed, np.float64, C.c_double), arr(max_heading_change, np.float64, C.c_double),
                            arr(dt_nominal, np.float64, C.c_double))
+
+
+def set_list_rule(rule=0):
+    """Which lists policy_step builds (process-wide).  0: the reference's -- kd visit order, the last entry popped when the list is full.
+    1: the rule SCA_NBR_GRID documents -- sorted by (distSq, obstacles first, agent id), the nearest max_neighbors kept, status bit 32 where
+    more objects were admitted than the list holds; everything behind the list (cones, planes, sweep, LP) is the same code."""
+    if rule not in (0, 1):
+        raise ValueError(f'unknown list rule {rule!r}')
+    lib().orc_set_list_rule(int(rule))
 
 
 def _p(a, t):

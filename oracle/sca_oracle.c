@@ -37,7 +37,7 @@
 
 enum { POL_SCA = 0, POL_RVO = 1, POL_SRVO = 2, POL_ORCA = 3, POL_ORCA_LP = 4, POL_RVO_DUBINS = 5 };
 enum { FLAG_AT_GOAL = 1, FLAG_COLLISION = 2, FLAG_TIMEOUT = 4 };
-enum { ST_ACOS_DOMAIN = 1, ST_SQRT_DOMAIN = 2, ST_BAD_PREF_SPEED = 4, ST_DIV_ZERO = 8 };
+enum { ST_ACOS_DOMAIN = 1, ST_SQRT_DOMAIN = 2, ST_BAD_PREF_SPEED = 4, ST_DIV_ZERO = 8, ST_NBR_OVERFLOW = 32 };   /* 32: list rule 1 only */
 
 /* solver parameters: agent.py:27-36 */
 typedef struct {
@@ -308,10 +308,41 @@ static void nbr_insert_sorted(NbrList *L, int id, int kind, double dsq) {
     L->n++;
 }
 
+/* The second list rule (orc_set_list_rule): 0 = the reference's, above -- kd visit order, neighbors.pop() when full.  1 = the rule
+ * SCA_NBR_GRID documents (include/sca_hip.h, the head of sca_grid.hip.h), which is nothing of the reference's: the list is ordered by
+ * (distSq; at equal distSq obstacles before agents; agents by id), two obstacles of one distSq stay in the obstacle tree's visit order,
+ * and a full list keeps its first max_neighbors entries in that order -- the nearest.  The admission tests (distances, collision rule)
+ * are those of insert_agent_neighbor / insert_obstacle_neighbor either way. */
+static int g_list_rule = 0;
+void orc_set_list_rule(int rule) { g_list_rule = rule; }
+
+/* does the listed entry k come before a new (kind, id, dsq)?  An obstacle already listed stays in front of an obstacle that is visited later. */
+static int nbr_precedes(const NbrList *L, int k, int id, int kind, double dsq) {
+    if (L->dsq[k] != dsq) return L->dsq[k] < dsq;
+    if (L->kind[k]) return 1;
+    return !kind && L->id[k] < id;
+}
+static void nbr_insert_ranked(NbrList *L, int id, int kind, double dsq) {
+    int at = 0;
+    while (at < L->n && nbr_precedes(L, at, id, kind, dsq)) at++;       /* behind every entry that precedes it */
+    if (L->n == g_par.max_neighbors) {
+        if (at >= g_par.max_neighbors) return;                            /* its place is beyond the list: dropped */
+        L->n--;                                                           /* otherwise the last entry makes room */
+    }
+    for (int j = L->n; j > at; j--) { L->id[j] = L->id[j - 1]; L->kind[j] = L->kind[j - 1]; L->dsq[j] = L->dsq[j - 1]; }
+    L->id[at] = id; L->kind[at] = (uint8_t)kind; L->dsq[at] = dsq;
+    L->n++;
+}
+
 typedef struct {
     int self; const double *pos; const double *radius; const double *opos; const double *oradius;
     int is_collision; NbrList *L;
+    int admitted;                 /* rule 1: the objects admitted since the list was last cleared */
 } Query;
+static void nbr_admit(Query *q, int id, int kind, double dsq) {
+    if (g_list_rule == 1) { q->admitted++; nbr_insert_ranked(q->L, id, kind, dsq); }
+    else nbr_insert_sorted(q->L, id, kind, dsq);
+}
 
 /* agent.py:79-99 insertAgentNeighbor.  rangeSq is passed by value in Python, so the callee's
  * `rangeSq = self.neighbors[-1][1]` never reaches the tree query: the range stays constant. */
@@ -319,10 +350,10 @@ static void insert_agent_neighbor(Query *q, int other, double rangeSq) {
     if (q->self == other) return;
     double distSq = orc_l3normsq(&q->pos[3 * q->self], &q->pos[3 * other]);
     if (distSq < sqr(q->radius[q->self] + q->radius[other]) && distSq < rangeSq) {
-        if (!q->is_collision) { q->is_collision = 1; q->L->n = 0; }
-        nbr_insert_sorted(q->L, other, 0, distSq);
+        if (!q->is_collision) { q->is_collision = 1; q->L->n = 0; q->admitted = 0; }
+        nbr_admit(q, other, 0, distSq);
     } else if (!q->is_collision && distSq < rangeSq) {
-        nbr_insert_sorted(q->L, other, 0, distSq);
+        nbr_admit(q, other, 0, distSq);
     }
 }
 /* agent.py:101-124 insertObstacleNeighbor */
@@ -330,10 +361,10 @@ static void insert_obstacle_neighbor(Query *q, int ob, double rangeSq) {
     double distSq1 = orc_l3normsq(&q->pos[3 * q->self], &q->opos[3 * ob]);
     double distSq = pow(orc_l3norm(&q->pos[3 * q->self], &q->opos[3 * ob]) - q->oradius[ob], 2.0);
     if (distSq1 < sqr(q->radius[q->self] + q->oradius[ob]) && distSq < rangeSq) {
-        if (!q->is_collision) { q->is_collision = 1; q->L->n = 0; }
-        nbr_insert_sorted(q->L, ob, 1, distSq);
+        if (!q->is_collision) { q->is_collision = 1; q->L->n = 0; q->admitted = 0; }
+        nbr_admit(q, ob, 1, distSq);
     } else if (!q->is_collision && distSq < rangeSq) {
-        nbr_insert_sorted(q->L, ob, 1, distSq);
+        nbr_admit(q, ob, 1, distSq);
     }
 }
 static double box_dist_sq(const Node *c, const double *p) {
@@ -369,6 +400,12 @@ static void kd_query(const Node *tree, const int *ids, Query *q, double rangeSq,
             }
         }
     }
+}
+
+/* the agents of a query: through their tree, or (rule 1, which knows no agent tree) every id in turn */
+static void visit_agents(const Node *tree, const int *ids, Query *q, double rangeSq, int n) {
+    if (g_list_rule == 1) for (int j = 0; j < n; j++) insert_agent_neighbor(q, j, rangeSq);
+    else kd_query(tree, ids, q, rangeSq, 0, 0);
 }
 
 /* standalone kd build for tests: returns node count used is implicit; tree_out = (2n-1) * 10 doubles */
@@ -787,25 +824,26 @@ int orc_policy_step(int n, int m, const double *pos, const float *vel, const dou
         else straight_v_pref(&goal[3 * i], pA, pref_speed[i], pol == POL_ORCA || pol == POL_ORCA_LP, vpref, raw);
         for (int k = 0; k < 3; k++) vpref_used[3 * i + k] = vpref[k];
         NbrList L; L.n = 0;
-        Query q = {i, pos, radius, obs_pos, obs_radius, 0, &L};
+        Query q = {i, pos, radius, obs_pos, obs_radius, 0, &L, 0};
         double vpost[3];
         int is_orca = (pol == POL_ORCA || pol == POL_ORCA_LP);
         int first_step;
         if (is_orca) {
             /* orca3dPolicy.py:51-53: neighbours are computed before the first-step test */
             if (otree) kd_query(otree, oids, &q, rangeSq, 0, 1);
-            kd_query(atree, aids, &q, rangeSq, 0, 0);
+            visit_agents(atree, aids, &q, rangeSq, n);
             nbr_valid[i] = 1;
             first_step = distance_f32_zero(vA) <= 1e-5;
         } else {
             first_step = l3norm_f32_zero(vA) <= 1e-5;                   /* scaPolicy.py:34 */
             if (!first_step) {
                 if (otree) kd_query(otree, oids, &q, rangeSq, 0, 1);     /* scaPolicy.py:114 obstacles first */
-                kd_query(atree, aids, &q, rangeSq, 0, 0);
+                visit_agents(atree, aids, &q, rangeSq, n);
                 nbr_valid[i] = 1;
             }
         }
         if (q.is_collision) flags[i] |= FLAG_COLLISION;
+        if (g_list_rule == 1 && q.admitted > g_par.max_neighbors) st |= ST_NBR_OVERFLOW;   /* more admitted than the list holds */
         nbr_n[i] = L.n;
         for (int k = 0; k < L.n; k++) {
             nbr_id[K_MAX * i + k] = L.id[k]; nbr_kind[K_MAX * i + k] = L.kind[k]; nbr_dsq[K_MAX * i + k] = L.dsq[k];

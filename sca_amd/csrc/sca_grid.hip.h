@@ -8,10 +8,15 @@
 // distSq; which objects those are does not depend on the visit order as long as no more than maxNeighbors are in range, so
 // for such agents the grid's list holds the same (object, distSq) pairs as the reference's.  Two things do depend on the
 // kd-tree's visit order and are therefore NOT reproduced:
-//   * the order of entries with EQUAL rounded distSq (here: obstacles first, in obstacle-tree order, then agents by id);
-//     it matters to nobody but the LP of orca3dPolicyOfficial.py, whose plane order is the list order;
-//   * which 16 survive when more than 16 are in range (agent.py:87-90 evicts by visit order): the grid keeps
-//     the 16 nearest and raises SCA_ST_NBR_OVERFLOW in the agent's status word.
+//   * the order of entries with EQUAL rounded distSq (here: obstacles first -- two obstacles of one distSq in the order the
+//     obstacle tree's query meets them --, then agents by id); it matters to nobody but the LP of orca3dPolicyOfficial.py, whose
+//     plane order is the list order;
+//   * which entries survive when more than the agent's maxNeighbors are in range (agent.py:87-90 evicts by visit order, SURVEY.md
+//     8-a4): the grid keeps the maxNeighbors nearest -- the first maxNeighbors of the order above, an entry whose place is beyond
+//     them is dropped -- and raises SCA_ST_NBR_OVERFLOW in the agent's status word.  The bit says "more objects admitted than the
+//     list holds"; on an agent that collides in this pass it may also stand because the list was full before the first colliding
+//     object was met.
+// This rule is restated on the CPU as the oracle's list rule 1 (oracle/sca_oracle.c); tests/test_gpu_grid_fuzz.py compares every row.
 // The collision rule (first colliding object clears the list, afterwards only colliding objects are admitted, agent.py:82-99)
 // leaves "all colliding objects in range" whatever the order: reproduced exactly.
 // Obstacles keep their kd-tree (built once on the host, kdTree.py:158-227): the obstacle part of a list is the reference's.
@@ -187,7 +192,7 @@ __device__ __forceinline__ void neighbors_grid_body(const DeviceView &d, const G
     int *stack = stacks[wid][grp];
 
     // one object in range of the group's agent: the list stays sorted by (distSq, obstacles before agents, id); a full list
-    // keeps its 16 smallest and says so
+    // keeps its maxn smallest and says so
     auto member = [&](bool act, bool cb, double db, int ib) {
         if (act && cb && !coll) { coll = true; cnt = 0; }                            // agent.py:83-85
         bool ins = act && (cb || !coll);

@@ -120,12 +120,13 @@ _RUNS = collections.OrderedDict()
 _RUNS_MAX = 3 * BLOCK                          # the rows of one block run one after the other: a block or two stay, the rest goes
 
 
-def oracle_run(oracle, scene, steps, per_agent=None):
+def oracle_run(oracle, scene, steps, per_agent=None, list_rule=0):
     """The free-running oracle trajectory of a scene: policy_step then env_update per step, from the scene's own state.  One dict per step:
     action, nbr_valid, nbr_n, nbr_id, nbr_kind, nbr_dsq, diag, perm, `before` (the flags the step started from), `flags_policy` (the flags after
-    the policy pass) and the state after the step (STATE_KEYS).  per_agent: what per_agent_attributes returned.  Memoised per scene and variant: every form row of a block compares
-    against one run.  The arrays are shared: nobody writes to them."""
-    key = scene['key'] + (per_agent is not None,)
+    the policy pass) and the state after the step (STATE_KEYS).  per_agent: what per_agent_attributes returned.  list_rule: 0 the reference's lists
+    (what SCA_NBR_KDTREE and SCA_NBR_AUTO return), 1 the lists SCA_NBR_GRID documents (oracle.set_list_rule); `status` then carries bit 32 on the
+    rows that overflowed.  Memoised per scene and variant: every form row of a block compares against one run.  The arrays are shared: nobody writes to them."""
+    key = scene['key'] + (per_agent is not None,) + (('rule', list_rule) if list_rule else ())
     have = _RUNS.get(key)
     if have is not None and len(have) >= steps:
         _RUNS.move_to_end(key)
@@ -136,6 +137,7 @@ def oracle_run(oracle, scene, steps, per_agent=None):
     td, sn, perm = np.zeros(n), np.zeros(n, np.int32), np.arange(n, dtype=np.int32)
     out = []
     try:
+        oracle.set_list_rule(list_rule)
         if per_agent is not None:
             per, params, uniform = per_agent
             oracle.set_params(**params)
@@ -149,7 +151,7 @@ def oracle_run(oracle, scene, steps, per_agent=None):
             perm = r['perm']
             u = oracle.env_update(p, ve, he, s['radius'], r['flags'], s['goal'], r['action'], td, s['max_run_dist'], sn,
                                   s['obs_pos'], s['obs_radius'])
-            step = {k: r[k] for k in ('action', 'nbr_valid', 'nbr_n', 'nbr_id', 'nbr_kind', 'nbr_dsq', 'diag', 'perm')}
+            step = {k: r[k] for k in ('action', 'nbr_valid', 'nbr_n', 'nbr_id', 'nbr_kind', 'nbr_dsq', 'diag', 'perm', 'status')}
             step['before'], step['flags_policy'] = fl, r['flags']
             p, ve, he, fl, td, sn = u['pos'], u['vel'], u['heading'], u['flags'], u['total_dist'], u['step_num']
             step.update(pos=p, vel=ve, heading=he, flags=fl, total_dist=td, step_num=sn)
@@ -157,6 +159,7 @@ def oracle_run(oracle, scene, steps, per_agent=None):
     finally:
         oracle.set_params()
         oracle.set_agent_params()
+        oracle.set_list_rule(0)
     _RUNS[key] = out
     while len(_RUNS) > _RUNS_MAX:
         _RUNS.popitem(last=False)

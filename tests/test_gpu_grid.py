@@ -107,16 +107,24 @@ def test_grid_pass_vs_golden(S, name):
     sol.close()
 
 
-def brute_lists(pos, radius, active_rows):
-    """true 16 nearest agents of each row by the reference's rounded distSq (util.py:100), ties by id; no obstacles"""
+def brute_lists(pos, radius, active_rows, range_sq=100.0, collide=False):
+    """every agent in range of each row by the reference's rounded distSq (util.py:100), nearest first, ties by id; no obstacles.  range_sq: one
+    value or one per agent.  collide: the collision rule of agent.py:82-99 -- with an agent closer than the two radii in range, only such agents."""
+    import math
     out = {}
+    range_sq = np.broadcast_to(np.asarray(range_sq, np.float64), (len(pos),))
     for i in active_rows:
         d = pos - pos[i]
         s = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]
         s = s + d[:, 2] * d[:, 2]
         dsq = np.rint(s * 1e5) / 1e5
         dsq[i] = np.inf
-        inr = np.nonzero(dsq < 100.0)[0]
+        inr = np.nonzero(dsq < range_sq[i])[0]
+        if collide:
+            reach = np.array([math.pow(radius[i] + radius[j], 2.0) for j in inr])        # util.py:84 sqr
+            hit = dsq[inr] < reach
+            if hit.any():
+                inr = inr[hit]
         order = inr[np.lexsort((inr, dsq[inr]))]
         out[i] = (order, dsq[order])
     return out

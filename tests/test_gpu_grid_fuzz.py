@@ -1,0 +1,171 @@
+"""SCA_NBR_GRID on the random-scene corpus and beyond the first overflow, against an oracle of its own list rule (-m gpu).
+
+The grid's contract (include/sca_hip.h, the head of sca_grid.hip.h) is deterministic: lists sorted by (distSq, obstacles first, agent id), the
+nearest max_neighbors kept, the collision rule order-free.  oracle.set_list_rule(1) computes exactly that in front of the unchanged rest of the
+policy pass (tests/test_grid_rule_cpu.py pins it to the reference's rule and to an all-pairs search), so every row has an expected list and an
+expected action row, overflowed or not.  Here the fuzz scenes of tests/form_fuzz.py run free for six resident steps in SCA_NBR_GRID, one
+context per scene; after every step flags, step counts, float32 velocities, positions, headings, travelled distance, the action rows, the
+lists entry for entry in the grid's own order and the decisions' diagnostics EQUAL the rule-1 oracle's.  No row is left out, nothing is sorted,
+no tolerance.  The kd permutation is not compared: the grid builds no tree.
+
+Status words: no bit outside 32 | 64 | 128; SCA_ST_NBR_OVERFLOW wherever the oracle sets it, and beyond that only on rows whose collision
+flag this very pass raised (the kernel may have seen a full list before it met the first colliding object; the oracle counts what is admitted
+after it).
+
+Legs: the plain scenes at the default forms and under the `large_shard` row (overflowed lists are what feeds the fallback launch and the
+two-launch solve), the per-agent scenes at the default forms (max_neighbors 1 .. 16 and neighbor_dist per agent), two plain blocks behind the
+one-rank cell-owner partition, and two episodes that go on long after their first overflow."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import form_fuzz as F
+from test_forms_cpu import H, from_env, solve                                       # noqa: F401 (H: fixture)
+from test_gpu_form_fuzz import S, SOLVE_BITS, row_env, simds                        # noqa: F401 (fixtures)
+from test_grid_rule_cpu import GRID_MAY_REFUSE
+
+pytestmark = pytest.mark.gpu
+
+STEPS = 6
+OVERFLOW = 32
+K = F.K
+
+
+def planned(H, simds, scene, part_on=0):
+    """plan_solve for this scene under the environment of the moment"""
+    t = from_env(H, simds)
+    lp = int((scene['policy'] == 4).sum())
+    return solve(H, scene['n'], simds=simds, part_on=part_on, nranks=1, lp=lp, lp_total=lp, t=(C.c_int * len(t))(*t.values()))
+
+
+def run_grid_against_oracle(S, oracle, scene, steps, per_agent, plan, ctx, partition=False, may_refuse=False):
+    """One context, `steps` resident steps in SCA_NBR_GRID, everything compared with the rule-1 oracle after each.  Returns None where the
+    library refused the scene at its first pass (may_refuse), else the overflowed rows the oracle had per step."""
+    s, n = scene, scene['n']
+    ref = F.oracle_run(oracle, s, steps, per_agent, list_rule=1)
+    params = per_agent[1] if per_agent else None
+    sol = S.BatchedSolver(max_agents=n, max_obstacles=max(1, s['m']), params=params)
+    overflowed = []
+    try:
+        sol.set_obstacles(s['obs_pos'], s['obs_radius'])
+        sol.set_agents(s['radius'], s['pref_speed'], s['goal'], s['policy'], F.zaxis_of(s), s['max_run_dist'])
+        if per_agent and not per_agent[2]:
+            sol.set_agent_params(**per_agent[0])
+        sol.set_vpref(s['vpref'], s['vmode'])
+        sol.set_state(s['pos'], s['vel'], s['heading'], s['flags'], np.zeros(n), np.zeros(n, np.int32))
+        if partition:
+            sol.partition_init(0, 1, axis=0)
+            assert sol.partition_counts() == (n, 0), ctx
+        lp = s['policy'] == 4
+        col = np.arange(K)[None, :]
+        for t, r in enumerate(ref):
+            at = ctx + ('n', n, 'step', t)
+            try:
+                sol.run_steps(1, S.NBR_GRID)
+            except S.ScaError as e:
+                assert may_refuse and t == 0 and 'SCA_NBR_GRID needs' in str(e), at + (str(e),)
+                return None
+            sol.synchronize()
+            if partition:
+                assert sol.partition_counts() == (n, 0), at
+            forms = sol.pass_forms()
+            assert (forms & SOLVE_BITS) == plan['forms'], at + ('forms', forms, plan)
+            g = sol.get_state()
+            assert np.array_equal(g['flags'], r['flags']), at + ('flags', np.flatnonzero(g['flags'] != r['flags'])[:8])
+            assert np.array_equal(g['step_num'], r['step_num']), at + ('step_num',)
+            assert np.array_equal(g['vel'], r['vel']), at + ('vel', np.flatnonzero((g['vel'] != r['vel']).any(axis=1))[:8])
+            for k in ('pos', 'heading', 'total_dist'):
+                assert np.array_equal(g[k], r[k]), at + (k,)
+            a = sol.actions()
+            assert np.array_equal(a, r['action']), at + ('action', np.flatnonzero((a != r['action']).any(axis=1))[:8])
+            nb = sol.neighbors()
+            valid = r['nbr_valid'].astype(bool)
+            assert np.array_equal(nb['nbr_valid'].astype(bool), valid), at + ('nbr_valid',)
+            assert np.array_equal(nb['nbr_n'][valid], r['nbr_n'][valid]), at + ('nbr_n', np.flatnonzero(valid & (nb['nbr_n'] != r['nbr_n']))[:8])
+            live = valid[:, None] & (col < r['nbr_n'][:, None])
+            for k in ('nbr_id', 'nbr_kind', 'nbr_dsq'):
+                differ = live & (nb[k] != r[k])
+                assert not differ.any(), at + (k, np.flatnonzero(differ.any(axis=1))[:8])
+            dg = sol.diag()
+            assert np.array_equal(dg['diag'][:, :2], r['diag'][:, :2]), at + ('n_suit / fallback', np.flatnonzero((dg['diag'][:, :2] != r['diag'][:, :2]).any(axis=1))[:8])
+            assert np.array_equal(dg['diag'][lp, 3:5], r['diag'][lp, 3:5]), at + ('planeFail / lp4',)
+            st = dg['status']
+            assert not (st & ~(OVERFLOW | 64 | 128)).any(), at + ('status bits', np.flatnonzero(st & ~(OVERFLOW | 64 | 128))[:8])
+            over, over_ref = (st & OVERFLOW) != 0, (r['status'] & OVERFLOW) != 0
+            assert not (over_ref & ~over).any(), at + ('overflow not reported', np.flatnonzero(over_ref & ~over)[:8])
+            collided_now = ((r['flags_policy'] & 2) != 0) & ((r['before'] & 2) == 0)
+            assert not (over & ~over_ref & ~collided_now).any(), at + ('spurious overflow', np.flatnonzero(over & ~over_ref & ~collided_now)[:8])
+            overflowed.append(int((over_ref & valid).sum()))
+    finally:
+        sol.close()
+    return overflowed
+
+
+def _legs():
+    """block-major: the legs of a block one after the other share its oracle runs (form_fuzz.oracle_run keeps a block or two)"""
+    out = []
+    for b in range(len(F.PLAIN_SEEDS) // F.BLOCK):
+        for leg in ('default', 'large_shard') + (('partition',) if b in (0, 3) else ()):
+            out.append(pytest.param(leg, b, id='%s-%d' % (leg, b)))
+    return out
+
+
+@pytest.mark.parametrize('leg,block', _legs())
+def test_grid_on_the_plain_scenes(S, H, oracle, simds, row_env, leg, block):
+    """20 scenes of the plain corpus (seeds 0-119): n = 1 .. 1600 with ragged 16-lane groups, 4 m boxes with far more than 16 in range and
+    more than max_neighbors colliding, 80 m boxes around the origin (cells below zero, a thousand cells in a few thousand buckets), obstacles"""
+    row_env('large_shard' if leg == 'large_shard' else 'solve_fb')                  # (`solve_fb`: no switch set)
+    seen = 0
+    for seed in F.PLAIN_SEEDS[F.BLOCK * block: F.BLOCK * (block + 1)]:
+        s = F.random_scene(seed)
+        plan = planned(H, simds, s, part_on=int(leg == 'partition'))
+        if leg == 'large_shard':
+            assert plan['forms'] == (S.FORM_SOLVE_SPLIT | (S.FORM_LP_LANE if (s['policy'] == 4).any() else 0)), (seed, plan)
+        seen += sum(run_grid_against_oracle(S, oracle, s, STEPS, None, plan, (leg, 'seed', seed), partition=leg == 'partition'))
+    assert seen > 0, (leg, block)
+
+
+@pytest.mark.parametrize('block', range(len(F.PER_AGENT_SEEDS) // F.BLOCK))
+def test_grid_on_the_scenes_with_per_agent_attributes(S, H, oracle, simds, row_env, block):
+    """20 scenes of the per-agent corpus (seeds 1000-1059): max_neighbors 1 .. 16 and neighbor_dist per agent (or one value of each per scene).
+    The library may refuse a scene whose largest neighbor_dist cannot hold the collision check's partners -- those of GRID_MAY_REFUSE
+    (tests/test_grid_rule_cpu.py derives the set from the corpus) and no other."""
+    row_env('solve_fb')
+    seen, refused = 0, []
+    for seed in F.PER_AGENT_SEEDS[F.BLOCK * block: F.BLOCK * (block + 1)]:
+        s = F.random_scene(seed)
+        pa = F.per_agent_attributes(seed, s['n'])
+        got = run_grid_against_oracle(S, oracle, s, STEPS, pa, planned(H, simds, s), ('per_agent', 'seed', seed), may_refuse=seed in GRID_MAY_REFUSE)
+        if got is None:
+            refused.append(seed)
+        else:
+            seen += sum(got)
+    assert set(refused) <= set(GRID_MAY_REFUSE), refused                              # (every other scene ran: a refusal there fails inside)
+    assert seen > 0, block
+
+
+def _episode(kind):
+    from sca_amd import scenarios
+    if kind == 'takeoff':                                                            # test_gpu_grid's episode: overflows from step 3 on
+        n = 1024
+        sc = scenarios.takeoff_landing(n)
+        policy = np.where(np.arange(n) % 2 == 0, 0, 2).astype(np.uint8)
+    else:                                                                            # test_gpu_auto's dense blob: ~40 agents within neighborDist
+        from test_gpu_auto import _scene
+        sc, policy, n = _scene('dense', 600, 5)
+    return dict(n=n, m=len(sc['obs_radius']), pos=sc['start'][:, :3].copy(), goal=sc['goal'][:, :3].copy(), heading=sc['start'][:, 3:6].copy(),
+                vel=np.zeros((n, 3), np.float32), radius=np.full(n, 0.5), pref_speed=np.ones(n), policy=policy, flags=np.zeros(n, np.uint8),
+                obs_pos=sc['obs_pos'].reshape(-1, 3), obs_radius=sc['obs_radius'], vpref=np.zeros((n, 3)), vmode=np.zeros(n, np.uint8),
+                max_run_dist=scenarios.max_run_dist(sc['start'], sc['goal']), key=('episode', kind))
+
+
+@pytest.mark.parametrize('kind,steps', [('takeoff', 40), ('dense', 12)])
+def test_grid_episode_beyond_the_first_overflow(S, H, oracle, simds, row_env, kind, steps):
+    """scenarios.takeoff_landing(1024), policies 0 / 2 alternating (a lattice of identical cells: equal distances everywhere, 8 obstacles per
+    cell), 40 steps, and the 600-agent dense blob, 12 steps: the comparison with the kd-tree run ends at the first overflow (step 3 of the
+    take-off); this one goes on, every row at every step"""
+    row_env('solve_fb')
+    s = _episode(kind)
+    got = run_grid_against_oracle(S, oracle, s, steps, None, planned(H, simds, s), (kind,))
+    assert sum(got[4:]) > 0, got
