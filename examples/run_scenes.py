@@ -13,6 +13,10 @@ one metrics row per scene -- what a loop over the reference's run_example/run_*.
     python examples/run_scenes.py --sizes 20,50,100 --slots 16 --capacity max   # the scenarios at several drone counts through ONE queue: every
                                                        # slot holds up to the largest count and takes the next episode that fits
                                                        # (without --capacity a slot keeps its size: one slot at least per count)
+    python examples/run_scenes.py --obstacles --seeds 8 --slots 16    # the obstacle scenarios as ONE queue: every episode brings its own
+                                                       # obstacles into the slot it takes (run_episodes(episode_obstacles=...)) -- the
+                                                       # random scenes 1-5 spheres that differ per seed, the take-off field its 8, and
+                                                       # with --map <binvox> the exp3 search among the map's spheres
     python examples/run_scenes.py --seeds 8 --slots 16 --harvest      # the streamed queue with the finished scenes handed over by the step that
                                                        # finishes them (sca_scene_harvest_enable): the same rows, one synchronisation a step
 """
@@ -21,8 +25,10 @@ import os
 import sys
 import time
 
+import numpy as np
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from sca_amd import env as E, metrics, scenarios                      # noqa: E402
+from sca_amd import env as E, metrics, read_map, scenarios            # noqa: E402
 from sca_amd.scenes import SceneBatch, run_episodes                   # noqa: E402
 
 POLICIES = {'sca': E.SCAPolicy, 'rvo': E.RVO3DPolicy, 'srvo': E.SRVO3DPolicy, 'orca': E.ORCA3DPolicy, 'orca-lp': E.ORCA3DPolicyOfficial,
@@ -34,12 +40,31 @@ def build_agents(sc, policy):
                     policy=policy, id=i) for i in range(len(sc['start']))]
 
 
+def spheres(pos, radius):
+    return [E.Obstacle(pos=list(p), shape_dict={'shape': 'sphere', 'feature': float(r)}, id=i) for i, (p, r) in enumerate(zip(pos, radius))]
+
+
+def random_spheres(sc, seed):
+    """1-5 spheres of radius 1 that differ per seed, inside the box of the scene's starts, none within 3 m of a start or a goal"""
+    rng = np.random.default_rng(1000 + seed)
+    lo, hi = sc['start'][:, :3].min(0), sc['start'][:, :3].max(0)
+    ends = np.concatenate([sc['start'][:, :3], sc['goal'][:, :3]])
+    out = []
+    while len(out) < 1 + seed % 5:
+        p = rng.uniform(lo, hi)
+        if np.linalg.norm(ends - p, axis=1).min() > 3.0:
+            out.append(p)
+    return spheres(out, [1.0] * len(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--agents', type=int, default=100)
     ap.add_argument('--seeds', type=int, default=3, help='random scenes per policy (beside one circle scene)')
     ap.add_argument('--max-steps', type=int, default=20000)
-    ap.add_argument('--obstacles', action='store_true', help='add a take-off/landing scene with its 8 spheres per policy (one obstacle list per scene)')
+    ap.add_argument('--obstacles', action='store_true', help='add a take-off/landing scene with its 8 spheres per policy (one obstacle list per scene); '
+                                                             'with --slots also 1-5 spheres per random scene, and the exp3 search where --map is given')
+    ap.add_argument('--map', default=None, help='with --obstacles --slots: binvox map of the exp3 scenario (16 drones among its spheres), as for run_sca.py')
     ap.add_argument('--slots', type=int, default=0, help='stream the table through this many slots instead of holding it as one batch')
     ap.add_argument('--sizes', default=None, help='drone counts, e.g. 20,50,100: every scenario at each of them (instead of --agents)')
     ap.add_argument('--capacity', default=None, help="with --slots: 'max' makes every slot hold up to the largest episode, so a slot takes any "
@@ -47,9 +72,8 @@ def main():
     ap.add_argument('--harvest', action='store_true', help='with --slots: finished scenes hand over their result with the step (run_episodes(harvest=True))')
     ap.add_argument('--log-dir', default=None, help='write one folder per episode here: env_cfg.json + trajs.npz (the first --max-steps steps of each)')
     args = ap.parse_args()
-    if args.slots and args.obstacles:
-        ap.error('--slots streams episodes that share one obstacle list: not with --obstacles')
-
+    if args.map and not (args.slots and args.obstacles):
+        ap.error('--map adds the exp3 episodes to the streamed obstacle queue: give --obstacles and --slots')
     if args.capacity and not args.slots:
         ap.error('--capacity is about the slots of a streamed queue: give --slots')
     if args.harvest and not args.slots:
@@ -68,14 +92,19 @@ def main():
             scenes.append(build_agents(scenarios.circle(n), pol))
             for seed in range(args.seeds):
                 names.append((pname, 'random seed %d' % seed + tag))
-                scenes.append(build_agents(scenarios.random_cube(n, seed=seed), pol))
-            obstacles += [[] for _ in range(1 + args.seeds)]
+                sc = scenarios.random_cube(n, seed=seed)
+                scenes.append(build_agents(sc, pol))
+                obstacles.append(random_spheres(sc, seed) if args.obstacles and args.slots else [])
+            obstacles.insert(len(obstacles) - args.seeds, [])         # (the circle: open)
         if args.obstacles:
             sc = scenarios.takeoff_landing(16)
             names.append((pname, 'take-off'))
             scenes.append(build_agents(sc, pol))
-            obstacles.append([E.Obstacle(pos=list(p), shape_dict={'shape': 'sphere', 'feature': float(r)}, id=i)
-                              for i, (p, r) in enumerate(zip(sc['obs_pos'], sc['obs_radius']))])
+            obstacles.append(spheres(sc['obs_pos'], sc['obs_radius']))
+        if args.map:
+            names.append((pname, 'exp3'))
+            scenes.append(build_agents(scenarios.spawn_n_drones(16), pol))
+            obstacles.append(read_map.read_obstacle(center=(35, 30), environ='exp3', obs_path=args.map))
     def folder(k):
         return os.path.join(args.log_dir, '%03d_%s_%s' % (k, names[k][0], names[k][1].replace(' ', '_')))
 
@@ -91,7 +120,8 @@ def main():
                 if r['rows_dropped']:
                     print('    (the log holds the first %d steps: %d more did not fit --max-steps rows)' % (r['trajectories'].shape[1], r['rows_dropped']))
         run_episodes(scenes, args.slots, device_tracker=True, on_done=row, max_steps=args.max_steps, stats=stats,
-                     history_rows=args.max_steps if args.log_dir else 0, capacities=capacities, harvest=args.harvest)
+                     history_rows=args.max_steps if args.log_dir else 0, capacities=capacities, harvest=args.harvest,
+                     episode_obstacles=obstacles if args.obstacles else None)
         print('%d episodes through %d slots: %d batch steps, mean live fraction %.2f, %.2f s' %
               (len(scenes), args.slots, stats['batch_steps'], stats['live_fraction'], time.time() - t0))
         return

@@ -223,8 +223,9 @@ int sca_set_scene_obstacles(sca_ctx *ctx, int nscenes, const int32_t *obs_offset
  *              one is enabled), the scene's slice of the kd permutation (identity), its neighbour lists, the tracker's records and
  *              goal_heading, and the scene's counters: steps[s] = 0, active[s] = n_s -- sca_env_step / sca_step_host / sca_active_count
  *              count the scene again, and a batch that had reached 0 comes back to life.
- *   kept       the slot's agent count, its obstacle set (shared or per scene), its per-agent solver attributes (sca_set_agent_params) and
- *              its per-agent tracker attributes; every array passed as NULL (vel: zero).
+ *   kept       the slot's agent count, its per-agent solver attributes (sca_set_agent_params) and its per-agent tracker attributes; every
+ *              array passed as NULL (vel: zero).  The obstacles the scene meets stay too -- unless the restart brings the episode's own
+ *              (sca_restart_scenes_obstacles, below).
  *   refusals   SCA_ERR_STATE: no scenes, no state yet, between a policy pass and its env update.  SCA_ERR_ARG: count <= 0 or scene_ids
  *              NULL, an id outside 0 .. nscenes-1, a repeated id, pos or heading NULL, any number that is not finite, a policy above
  *              SCA_POLICY_RVO3D_DUBINS, a radius / pref_speed / max_run_dist that is not positive, goal_heading without a device tracker.
@@ -275,6 +276,51 @@ int sca_restart_scenes_sized(sca_ctx *ctx, int count, const int32_t *scene_ids /
                              const uint8_t *zaxis, const double *max_run_dist,      /* each T, each nullable: keep the slot's */
                              const double *goal_heading /*T*3, nullable: keep the slot's*/);
 int sca_get_scene_sizes(sca_ctx *ctx, int32_t *size /*nscenes*/);
+
+/* Obstacle slots: a scene's obstacle range becomes a CAPACITY, as its agent range did with sca_restart_scenes_sized, so that a restarted
+ * slot takes the episode's own obstacles -- the take-off field's 8 spheres, the 1491 of a map, the 1-5 of a random scene -- and a queue
+ * that mixes such episodes streams through one set of slots.  Detect the feature by the symbol (sca_version() is unchanged).
+ *   sca_set_scene_obstacle_slots   scene s owns obstacle rows [cap_offsets[s], cap_offsets[s+1]) and holds counts[s] obstacles, 0 <=
+ *              counts[s] <= capacity, in the first of them; pos and radius are packed densely in scene order (sum(counts) rows).  counts ==
+ *              NULL: every slot starts empty.  The scene's tree is the one sca_set_scene_obstacles builds -- the same host routine over that
+ *              scene's obstacles alone with local ids -- standing at node record 2 * cap_offsets[s]; a tree over k obstacles has 2k - 1
+ *              nodes, so it always fits the 2 x capacity records of the range.  An empty slot has no tree and no obstacle walk happens for
+ *              its agents.  Obstacle ids in neighbour lists are GLOBAL: cap_offsets[s] + the scene's own id.  With every count equal to its
+ *              capacity the context is left exactly as sca_set_scene_obstacles(nscenes, cap_offsets, pos, radius) leaves it; that call in
+ *              turn leaves slots that are full.  A pass reports SCA_FORM_SCENE_OBSTACLES, also while every slot is empty.
+ *   order, lifetime   as sca_set_scene_obstacles: after sca_set_scenes (SCA_ERR_STATE before); a later sca_set_obstacles or
+ *              sca_set_scene_obstacles replaces the slots; whatever drops or redefines the scenes drops them and leaves the context without
+ *              obstacles.
+ *   refusals   SCA_ERR_ARG: nscenes different from the context's, cap_offsets NULL, cap_offsets[0] != 0, decreasing offsets, a total
+ *              capacity above sca_create's max_obstacles, a count outside 0 .. capacity, a position that is not finite, a radius that is
+ *              not positive, pos or radius NULL with a positive sum of counts.  A refused call has changed nothing.
+ *   sca_get_scene_obstacle_counts  the obstacles each scene holds and its capacity (either pointer may be NULL).  SCA_ERR_STATE without
+ *              scenes or without per-scene sets.
+ *   sca_restart_scenes_obstacles   sca_restart_scenes_sized (sizes == NULL: capacities) that also brings the episodes' obstacles.
+ *              obs_counts == NULL: exactly sca_restart_scenes_sized.  obs_counts[e] == -1: scene scene_ids[e] KEEPS its set -- seeds that
+ *              share a map: nothing is rebuilt and nothing is staged for it.  0 .. capacity: the scene's set is REPLACED by the next
+ *              obs_counts[e] rows of obs_pos / obs_radius, which hold the replaced scenes' obstacles packed in the order of scene_ids.
+ *              The scene contract extends: after the call a named scene is bit for bit a context that holds that episode alone after
+ *              sca_set_agents + sca_set_obstacles(that set) + sca_set_state (+ the tracker's enable) -- state, float32 action rows,
+ *              neighbour lists with their distSq and global obstacle ids, diagnostics, status, permutation, tracker records, the rows of
+ *              the log per scene and the harvest -- and no other scene can tell the call happened.  Rows and tree records of the slot behind
+ *              the new count keep what an earlier set left and are unreachable.
+ *              Refusals: those of sca_restart_scenes_sized, and SCA_ERR_STATE for a count >= 0 while the context has no per-scene sets;
+ *              SCA_ERR_ARG for a count below -1 or above the slot's capacity, an obstacle position that is not finite, a radius that is
+ *              not positive, obs_pos or obs_radius NULL with a positive total (each message names the entry).  A refused call has changed
+ *              nothing, obstacles included.
+ *              Cost: still one kernel launch and one stream synchronisation however many scenes are named; the replaced scenes' trees are
+ *              built on the host into the page-locked block and copied to their place by that launch. */
+int sca_set_scene_obstacle_slots(sca_ctx *ctx, int nscenes, const int32_t *cap_offsets /*nscenes+1*/,
+                                 const int32_t *counts /*nscenes, nullable: every slot empty*/,
+                                 const double *pos /*sum(counts)*3*/, const double *radius /*sum(counts)*/);
+int sca_get_scene_obstacle_counts(sca_ctx *ctx, int32_t *counts /*nscenes, nullable*/, int32_t *capacities /*nscenes, nullable*/);
+int sca_restart_scenes_obstacles(sca_ctx *ctx, int count, const int32_t *scene_ids /*count*/, const int32_t *sizes /*count, nullable: capacities*/,
+                                 const int32_t *obs_counts /*count, nullable*/, const double *obs_pos, const double *obs_radius,
+                                 const double *pos /*T*3*/, const float *vel /*T*3, nullable: zero*/, const double *heading /*T*3*/,
+                                 const double *radius, const double *pref_speed, const double *goal /*T*3*/, const uint8_t *policy,
+                                 const uint8_t *zaxis, const double *max_run_dist,      /* each T, each nullable: keep the slot's */
+                                 const double *goal_heading /*T*3, nullable: keep the slot's*/);
 
 /* A trajectory log per scene = every episode's Agent.history_info.  Row r of scene s is the scene's r-th own step (r = steps[s] - 1 while
  * that step runs), written only for steps the scene was live at their beginning, so a finished scene gains no row while the others run on,

@@ -75,6 +75,9 @@ SIGNATURES = {
     'sca_restart_scenes': (C.c_int, [C.c_void_p, C.c_int, ip, dp, fp, dp, dp, dp, dp, bp, bp, dp, dp]),
     'sca_restart_scenes_sized': (C.c_int, [C.c_void_p, C.c_int, ip, ip, dp, fp, dp, dp, dp, dp, bp, bp, dp, dp]),
     'sca_get_scene_sizes': (C.c_int, [C.c_void_p, ip]),
+    'sca_set_scene_obstacle_slots': (C.c_int, [C.c_void_p, C.c_int, ip, ip, dp, dp]),
+    'sca_get_scene_obstacle_counts': (C.c_int, [C.c_void_p, ip, ip]),
+    'sca_restart_scenes_obstacles': (C.c_int, [C.c_void_p, C.c_int, ip, ip, ip, dp, dp, dp, fp, dp, dp, dp, dp, bp, bp, dp, dp]),
     'sca_scene_history_enable': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_scene_history_rows': (C.c_int, [C.c_void_p, ip, ip]),
     'sca_get_scene_history': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, fp]),

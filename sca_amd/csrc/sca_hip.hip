@@ -309,7 +309,8 @@ struct sca_ctx {
         bool begun = false;             // a policy pass has opened a step (scene_begin_one) that no env update has closed yet
         bool obs_on = false;            // one obstacle set per scene (sca_set_scene_obstacles): d.obs .. d.owide hold a forest, K1 and K4 run their SceneObsRoots instances
         SceneObsView ov{};              // device array [nscenes]
-        std::vector<int32_t> h_obs_off; // [nscenes + 1] the obstacle offsets as set
+        std::vector<int32_t> h_obs_off; // [nscenes + 1] the obstacle offsets as set: each scene's range is its capacity (sca_set_scene_obstacle_slots)
+        std::vector<int32_t> h_obs_count; // [nscenes] the obstacles each scene holds in the first rows of its range; the device's copy stands behind ov.oroot
         uint8_t *rs_host = nullptr;     // sca_restart_scenes' page-locked staging block (RestartLayout of max_n, sca_scenes.h), allocated on first use
         SceneLogView log{};             // the trajectory log per scene (sca_scene_history_enable), rows null: off -- a step then enqueues nothing for it
         uint8_t *hv_host = nullptr;     // the harvest block (sca_scene_harvest_enable; HarvestLayout of nscenes and n, sca_scenes.h), null: off -- a step then enqueues nothing for it
@@ -1350,7 +1351,7 @@ static int scene_obstacles_drop(sca_ctx *c) {
     CHK(c, hipStreamSynchronize(c->stream));
     if (c->scenes.ov.oroot) (void)hipFree((void *)c->scenes.ov.oroot);
     c->scenes.ov = SceneObsView{};
-    c->scenes.h_obs_off.clear();
+    c->scenes.h_obs_off.clear(); c->scenes.h_obs_count.clear();
     c->scenes.obs_on = false;
     c->m = 0; c->d.m = 0; c->max_obs_radius = 0;
     c->near_valid = false;
@@ -1446,6 +1447,62 @@ int sca_set_scenes(sca_ctx *c, int nscenes, const int32_t *offsets) {
     c->scenes.on = true;
     return 0;
 }
+// One scene's part of the obstacle forest, by the routine sca_set_obstacles uses on that scene's `ms` obstacles alone with local ids, as
+// it stands at obstacle base `lo` (scene_obstacle_shift): sca_set_scene_obstacles, sca_set_scene_obstacle_slots and the restart that
+// brings obstacles all build through here, into the forest's arrays or into the restart's staging block.  rec / sorted / perm: [ms];
+// tree / wide: [2 ms - 1], to stand at record 2 * lo.  perm carries global ids (lo + local), as the agents' permutation does.
+static void scene_obstacle_build(int lo, int ms, const double *pos, const double *radius, ObsRec *rec, ObsRec *sorted, int32_t *perm, KdNode *tree_out, KdWide *wide_out) {
+    if (ms <= 0) return;
+    std::vector<KdNode> tree;
+    std::vector<KdWide> wide;
+    std::vector<int32_t> local((size_t)ms);
+    for (int i = 0; i < ms; i++) { rec[i].px = pos[3 * i]; rec[i].py = pos[3 * i + 1]; rec[i].pz = pos[3 * i + 2]; rec[i].radius = radius[i]; }
+    for (int i = 0; i < ms; i++) local[i] = i;                         // kdTree.py:51-52, the scene's own ids
+    kd_build_host(ms, pos, local.data(), tree);
+    kd_widen_host(ms, tree, wide);
+    scene_obstacle_shift(tree.data(), 2 * ms - 1, lo, MAX_LEAF);
+    scene_obstacle_shift(wide.data(), 2 * ms - 1, lo, MAX_LEAF);
+    for (int i = 0; i < 2 * ms - 1; i++) { tree_out[i] = tree[i]; wide_out[i] = wide[i]; }
+    for (int i = 0; i < ms; i++) { perm[i] = lo + local[i]; sorted[i] = rec[local[i]]; }
+}
+// The whole forest from the host: scene sc owns rows [off[sc], off[sc + 1]) and holds counts[sc] obstacles in the first of them (NULL:
+// every range is full); pos / radius are packed densely in scene order.  The arguments are checked, the stream is synchronised.
+static int scene_obstacles_install(sca_ctx *c, const int32_t *off, const int32_t *counts, const double *pos, const double *radius) {
+    const int B = c->scenes.v.nscenes, M = off[B];
+    std::vector<ObsRec> h((size_t)M, ObsRec{}), sorted((size_t)M, ObsRec{});
+    std::vector<int32_t> perm((size_t)M, 0), roots(2 * (size_t)B);    // roots | counts, one upload
+    std::vector<KdNode> forest(2 * (size_t)M, KdNode{});
+    std::vector<KdWide> wforest(2 * (size_t)M, KdWide{});
+    double max_r = 0;
+    size_t at = 0;
+    for (int sc = 0; sc < B; sc++) {
+        const int lo = off[sc], ms = counts ? counts[sc] : off[sc + 1] - lo;
+        roots[sc] = ms > 0 ? 2 * lo : -1;                              // (scene_obstacle_root / obstacle_slot_root)
+        roots[(size_t)B + sc] = ms;
+        scene_obstacle_build(lo, ms, pos + 3 * at, radius + at, h.data() + lo, sorted.data() + lo, perm.data() + lo, forest.data() + 2 * (size_t)lo, wforest.data() + 2 * (size_t)lo);
+        for (int i = 0; i < ms; i++) max_r = std::max(max_r, radius[at + i]);
+        at += (size_t)ms;
+    }
+    int32_t *dr = nullptr;
+    CHK(c, hipMalloc((void **)&dr, sizeof(int32_t) * 2 * (size_t)B));
+    if (c->scenes.ov.oroot) (void)hipFree((void *)c->scenes.ov.oroot);
+    c->scenes.ov.oroot = dr;
+    CHK(c, hipMemcpyAsync(dr, roots.data(), sizeof(int32_t) * 2 * (size_t)B, hipMemcpyHostToDevice, c->stream));
+    if (M > 0) {
+        CHK(c, hipMemcpyAsync(c->d.obs, h.data(), sizeof(ObsRec) * (size_t)M, hipMemcpyHostToDevice, c->stream));
+        CHK(c, hipMemcpyAsync(c->d.operm, perm.data(), sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice, c->stream));
+        CHK(c, hipMemcpyAsync(c->d.otree, forest.data(), sizeof(KdNode) * 2 * (size_t)M, hipMemcpyHostToDevice, c->stream));
+        CHK(c, hipMemcpyAsync(c->d.owide, wforest.data(), sizeof(KdWide) * 2 * (size_t)M, hipMemcpyHostToDevice, c->stream));
+        CHK(c, hipMemcpyAsync(c->d.obs_sorted, sorted.data(), sizeof(ObsRec) * (size_t)M, hipMemcpyHostToDevice, c->stream));
+    }
+    CHK(c, hipStreamSynchronize(c->stream));
+    c->m = M; c->d.m = M; c->max_obs_radius = max_r;
+    c->scenes.h_obs_off.assign(off, off + B + 1);
+    c->scenes.h_obs_count.assign(roots.begin() + B, roots.end());
+    c->near_valid = false;
+    c->scenes.obs_on = true;
+    return 0;
+}
 // One obstacle set per scene.  The reference builds a scene's obstacle tree once, over its own obstacles (mampenv.py:20, kdTree.py:162-227):
 // here the same routine runs per scene on that scene's obstacles alone, with local ids -- so the tree, the leaf order and with them every
 // list and every distSq are the single-scene context's -- and the trees are laid side by side (scene_obstacle_shift, sca_scenes.h).
@@ -1473,40 +1530,46 @@ int sca_set_scene_obstacles(sca_ctx *c, int nscenes, const int32_t *obs_offsets,
         c->m = 0; c->d.m = 0; c->max_obs_radius = 0; c->near_valid = false;
         return 0;
     }
-    std::vector<ObsRec> h((size_t)M), sorted((size_t)M);
-    double max_r = 0;
-    for (int i = 0; i < M; i++) { h[i].px = pos[3 * i]; h[i].py = pos[3 * i + 1]; h[i].pz = pos[3 * i + 2]; h[i].radius = radius[i]; max_r = std::max(max_r, radius[i]); }
-    std::vector<int32_t> perm((size_t)M), roots((size_t)B);
-    std::vector<KdNode> forest(2 * (size_t)M, KdNode{}), tree;
-    std::vector<KdWide> wforest(2 * (size_t)M, KdWide{}), wide;
-    for (int sc = 0; sc < B; sc++) {
-        const int lo = obs_offsets[sc], ms = obs_offsets[sc + 1] - lo;
-        roots[sc] = scene_obstacle_root(obs_offsets, sc);
-        if (ms == 0) continue;
-        std::vector<int32_t> local((size_t)ms);
-        for (int i = 0; i < ms; i++) local[i] = i;                     // kdTree.py:51-52, the scene's own ids
-        kd_build_host(ms, pos + 3 * (size_t)lo, local.data(), tree);
-        kd_widen_host(ms, tree, wide);
-        scene_obstacle_shift(tree.data(), 2 * ms - 1, lo, MAX_LEAF);
-        scene_obstacle_shift(wide.data(), 2 * ms - 1, lo, MAX_LEAF);
-        for (int i = 0; i < 2 * ms - 1; i++) { forest[2 * (size_t)lo + i] = tree[i]; wforest[2 * (size_t)lo + i] = wide[i]; }
-        for (int i = 0; i < ms; i++) { perm[lo + i] = lo + local[i]; sorted[lo + i] = h[lo + local[i]]; }      // global ids, as the agents' permutation carries
+    return scene_obstacles_install(c, obs_offsets, nullptr, pos, radius);
+}
+// Obstacle slots (include/sca_hip.h): the same forest with every scene's range a capacity.  The rules are obstacle_slots_check's.
+int sca_set_scene_obstacle_slots(sca_ctx *c, int nscenes, const int32_t *cap_offsets, const int32_t *counts, const double *pos, const double *radius) {
+    API_ENTER(c);
+    if (!c->scenes.on) { c->err = "sca_set_scene_obstacle_slots: no scenes -- sca_set_scenes first"; return SCA_ERR_STATE; }
+    const int B = c->scenes.v.nscenes;
+    const ObsSlotCheck k = obstacle_slots_check(B, c->max_m, nscenes, cap_offsets, counts, pos, radius);
+    if (k.fault != OBS_SLOT_OK) {
+        const std::string sc = std::to_string(k.scene), row = std::to_string(k.row);
+        switch (k.fault) {
+        case OBS_SLOT_OFFSETS:
+            switch (k.offsets) {
+            case SCENE_OBS_BAD_COUNT: c->err = "sca_set_scene_obstacle_slots: nscenes = " + std::to_string(nscenes) + ", the context holds " + std::to_string(B) + " scenes (sca_set_scenes)"; break;
+            case SCENE_OBS_NO_OFFSETS: c->err = "sca_set_scene_obstacle_slots: cap_offsets is NULL"; break;
+            case SCENE_OBS_BAD_START: c->err = "sca_set_scene_obstacle_slots: cap_offsets[0] must be 0"; break;
+            case SCENE_OBS_DECREASING: c->err = "sca_set_scene_obstacle_slots: cap_offsets must not decrease (scene " + sc + ")"; break;
+            default: c->err = "sca_set_scene_obstacle_slots: a capacity of " + std::to_string(k.capacity) + " obstacles in all, sca_create's max_obstacles is " + std::to_string(c->max_m);
+            }
+            break;
+        case OBS_SLOT_BAD_COUNT: c->err = "sca_set_scene_obstacle_slots: counts[" + sc + "] = " + std::to_string(counts[k.scene]) + ": the slot holds 0 .. " +
+                                          std::to_string(cap_offsets[k.scene + 1] - cap_offsets[k.scene]) + " obstacles (its capacity)"; break;
+        case OBS_SLOT_NO_ARRAYS: c->err = "sca_set_scene_obstacle_slots: pos and radius must not be NULL with " + std::to_string(k.total) + " obstacles"; break;
+        case OBS_SLOT_NOT_FINITE: c->err = "sca_set_scene_obstacle_slots: obstacle row " + row + " (scene " + sc + ") has a position that is not finite"; break;
+        default: c->err = "sca_set_scene_obstacle_slots: obstacle row " + row + " (scene " + sc + ") has a radius that is not positive";
+        }
+        return obstacle_slots_error_code(k.fault);
     }
-    int32_t *dr = nullptr;
-    CHK(c, hipMalloc((void **)&dr, sizeof(int32_t) * (size_t)B));
-    if (c->scenes.ov.oroot) (void)hipFree((void *)c->scenes.ov.oroot);
-    c->scenes.ov.oroot = dr;
-    CHK(c, hipMemcpyAsync(dr, roots.data(), sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, c->stream));
-    CHK(c, hipMemcpyAsync(c->d.obs, h.data(), sizeof(ObsRec) * (size_t)M, hipMemcpyHostToDevice, c->stream));
-    CHK(c, hipMemcpyAsync(c->d.operm, perm.data(), sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice, c->stream));
-    CHK(c, hipMemcpyAsync(c->d.otree, forest.data(), sizeof(KdNode) * 2 * (size_t)M, hipMemcpyHostToDevice, c->stream));
-    CHK(c, hipMemcpyAsync(c->d.owide, wforest.data(), sizeof(KdWide) * 2 * (size_t)M, hipMemcpyHostToDevice, c->stream));
-    CHK(c, hipMemcpyAsync(c->d.obs_sorted, sorted.data(), sizeof(ObsRec) * (size_t)M, hipMemcpyHostToDevice, c->stream));
     CHK(c, hipStreamSynchronize(c->stream));
-    c->m = M; c->d.m = M; c->max_obs_radius = max_r;
-    c->scenes.h_obs_off.assign(obs_offsets, obs_offsets + B + 1);
-    c->near_valid = false;
-    c->scenes.obs_on = true;
+    const std::vector<int32_t> none((size_t)B, 0);
+    return scene_obstacles_install(c, cap_offsets, counts ? counts : none.data(), pos, radius);
+}
+int sca_get_scene_obstacle_counts(sca_ctx *c, int32_t *counts, int32_t *capacities) {
+    API_ENTER(c);
+    if (!c->scenes.on) { c->err = "sca_get_scene_obstacle_counts: no scenes (sca_set_scenes)"; return SCA_ERR_STATE; }
+    if (!c->scenes.obs_on) { c->err = "sca_get_scene_obstacle_counts: no obstacle set per scene (sca_set_scene_obstacle_slots, sca_set_scene_obstacles)"; return SCA_ERR_STATE; }
+    for (int sc = 0; sc < c->scenes.v.nscenes; sc++) {
+        if (counts) counts[sc] = c->scenes.h_obs_count[sc];
+        if (capacities) capacities[sc] = c->scenes.h_obs_off[sc + 1] - c->scenes.h_obs_off[sc];
+    }
     return 0;
 }
 // SceneView::live from the records, where the state came from outside since the last env update (on `s`, which the records are final on)
@@ -1541,9 +1604,15 @@ int sca_get_scene_state(sca_ctx *c, int32_t *active, int32_t *steps) {
 // full -- every call of a context that never uses sizes -- launches k_scene_restart, as before; as soon as a named scene is or becomes
 // partial it is k_scene_restart_sized, which also vacates the rows behind the episode and writes the device's size[s].  Either way one
 // launch and one synchronisation.
+// obs_counts (sca_restart_scenes_obstacles): per named scene -1, the slot keeps its obstacle set, or 0 .. its obstacle capacity, the set is
+// replaced by the next rows of obs_pos / obs_radius (restart_obstacles_check).  The named scenes' trees are built here, by the routine that
+// built the forest (scene_obstacle_build), straight into the block's obstacle sections, and the one launch is k_scene_restart_obs, which
+// copies them to the scene's place and rewrites its root.  With no set replaced -- NULL, or -1 throughout -- nothing of this is staged and
+// the launch is the kernel it was.
 static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const int32_t *sizes, const double *pos, const float *vel, const double *heading,
                           const double *radius, const double *pref_speed, const double *goal, const uint8_t *policy, const uint8_t *zaxis,
-                          const double *max_run_dist, const double *goal_heading) {
+                          const double *max_run_dist, const double *goal_heading,
+                          const int32_t *obs_counts = nullptr, const double *obs_pos = nullptr, const double *obs_radius = nullptr) {
     RestartArgs A{count, scene_ids, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading};
     A.sizes = sizes;
     const RestartCtx X{c->scenes.on ? c->scenes.v.nscenes : 0, c->scenes.on ? c->scenes.h_off.data() : nullptr, c->state_set, c->scenes.begun, c->trk_on,
@@ -1571,9 +1640,24 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
         }
         return scene_restart_error_code(k.fault);
     }
+    const RestartObsCheck ko = restart_obstacles_check(c->scenes.obs_on, c->scenes.h_obs_off.data(), count, scene_ids, obs_counts, obs_pos, obs_radius);
+    if (ko.fault != RESTART_OBS_OK) {
+        const std::string at = std::to_string(ko.entry);
+        switch (ko.fault) {
+        case RESTART_OBS_NO_SLOTS: c->err = "sca_restart_scenes_obstacles: obs_counts[" + at + "] = " + std::to_string(obs_counts[ko.entry]) + " but the context has no obstacle slots -- sca_set_scene_obstacle_slots first"; break;
+        case RESTART_OBS_BAD_COUNT: c->err = "sca_restart_scenes_obstacles: obs_counts[" + at + "] = " + std::to_string(obs_counts[ko.entry]) + ": scene " + std::to_string(scene_ids[ko.entry]) +
+                                             " keeps its set (-1) or takes 0 .. its obstacle capacity" + (c->scenes.obs_on ? " " + std::to_string(c->scenes.h_obs_off[scene_ids[ko.entry] + 1] - c->scenes.h_obs_off[scene_ids[ko.entry]]) : std::string()); break;
+        case RESTART_OBS_NO_ARRAYS: c->err = "sca_restart_scenes_obstacles: obs_pos and obs_radius must not be NULL with " + std::to_string(ko.total) + " obstacles"; break;
+        case RESTART_OBS_NOT_FINITE: c->err = "sca_restart_scenes_obstacles: obstacle row " + at + " has a position that is not finite"; break;
+        default: c->err = "sca_restart_scenes_obstacles: obstacle row " + at + " has a radius that is not positive";
+        }
+        return restart_obstacles_error_code(ko.fault);
+    }
     const int T = k.total;
     const RestartLayout L = scene_restart_layout(c->max_n);
-    const size_t blk_bytes = (size_t)L.total + sizeof(int32_t) * (size_t)c->max_n;  // behind the layout's sections: the named scenes' new sizes
+    const size_t sizes_end = (size_t)L.total + sizeof(int32_t) * (size_t)c->max_n;  // behind the layout's sections: the named scenes' new sizes ...
+    const RestartObsLayout OL = restart_obstacles_layout((int64_t)sizes_end, c->max_n, c->max_m);      // ... and behind those the obstacle sections
+    const size_t blk_bytes = (size_t)OL.total;
     if (!c->scenes.rs_host) {                                                    // mapped and coherent, as the host state block is: the kernel reads it in place
         CHK(c, hipHostMalloc((void **)&c->scenes.rs_host, blk_bytes, hipHostMallocMapped | hipHostMallocCoherent));
         std::memset(c->scenes.rs_host, 0, blk_bytes);
@@ -1607,6 +1691,23 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
     put(RS_PREF_SPEED, pref_speed, sizeof(double) * (size_t)T, RESTART_HAS_PREF_SPEED);
     put(RS_MAX_RUN_DIST, max_run_dist, sizeof(double) * (size_t)T, RESTART_HAS_MAX_RUN_DIST);
     put(RS_ZAXIS, zaxis, (size_t)T, RESTART_HAS_ZAXIS);
+    double obs_max_r = 0;
+    if (ko.replaced > 0) {                                             // the replaced scenes' trees, built where the kernel reads them
+        int32_t *head = (int32_t *)(b + OL.off[RO_HEAD]);
+        ObsRec *rec = (ObsRec *)(b + OL.off[RO_REC]), *sorted = (ObsRec *)(b + OL.off[RO_SORTED]);
+        int32_t *perm = (int32_t *)(b + OL.off[RO_PERM]);
+        KdNode *tree = (KdNode *)(b + OL.off[RO_TREE]);
+        KdWide *wide = (KdWide *)(b + OL.off[RO_WIDE]);
+        int at = 0;                                                    // at most max_obstacles in all: the named scenes' capacities are disjoint ranges
+        for (int e = 0; e < count; e++) {
+            const int ms = obs_counts[e], base = c->scenes.h_obs_off[scene_ids[e]];
+            head[RO_HEAD_WORDS * e] = ms; head[RO_HEAD_WORDS * e + 1] = base; head[RO_HEAD_WORDS * e + 2] = at; head[RO_HEAD_WORDS * e + 3] = ms > 0 ? 2 * base : -1;
+            if (ms <= 0) continue;
+            scene_obstacle_build(base, ms, obs_pos + 3 * (size_t)at, obs_radius + at, rec + at, sorted + at, perm + at, tree + 2 * (size_t)at, wide + 2 * (size_t)at);
+            for (int i = 0; i < ms; i++) obs_max_r = std::max(obs_max_r, obs_radius[at + i]);
+            at += ms;
+        }
+    }
     RestartDev d{};
     d.rec = c->d.rec;
     d.heading = c->d.heading; d.heading_keep = c->scenes.v.heading_keep; d.total_dist = c->d.total_dist; d.goal = c->d.goal;
@@ -1619,7 +1720,13 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
         d.trk_nbr0 = c->trk.nbr0; d.trk_goal_heading = c->trk_goal_heading;
         d.trk_st = (restart_u32 *)c->trk.st; d.trk_init = (const restart_u32 *)c->trk_init; d.trk_words = (int)(sizeof(sca_dubins::AgentTrack) / 4);
     }
-    if (sized) hipLaunchKernelGGL(k_scene_restart_sized, dim3(count), dim3(RESTART_T), 0, c->stream, d, (const uint8_t *)b, L, has, (const int32_t *)new_size, c->scenes.size);
+    // k_scene_restart_obs writes the named scenes' parts of the forest on c->stream, behind every reader of it: a step's K1 and K4 run on
+    // c->stream or, where the tracker overlaps, K1 on trk_stream -- and the step joins trk_stream back into c->stream before it ends, so
+    // whatever was enqueued by an earlier call stands in front of this launch in stream order.
+    if (ko.replaced > 0) {
+        const RestartObsDev o{c->d.obs, c->d.obs_sorted, c->d.operm, c->d.otree, c->d.owide, (int32_t *)c->scenes.ov.oroot, (int32_t *)c->scenes.ov.oroot + c->scenes.v.nscenes};
+        hipLaunchKernelGGL(k_scene_restart_obs, dim3(count), dim3(RESTART_T), 0, c->stream, d, (const uint8_t *)b, L, has, (const int32_t *)new_size, c->scenes.size, o, OL);
+    } else if (sized) hipLaunchKernelGGL(k_scene_restart_sized, dim3(count), dim3(RESTART_T), 0, c->stream, d, (const uint8_t *)b, L, has, (const int32_t *)new_size, c->scenes.size);
     else hipLaunchKernelGGL(k_scene_restart, dim3(count), dim3(RESTART_T), 0, c->stream, d, (const uint8_t *)b, L, has);
     CHK(c, hipGetLastError());
     std::vector<int32_t> lp_new;                                       // K3's list: the ORCA3D-LP agents, ascending ids (the block holds the named scenes' policies)
@@ -1650,6 +1757,10 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
     }
     if (policy_changed || size_changed) c->h_lp_list.swap(lp_new);
     c->scenes.h_size.swap(size_now);
+    if (ko.replaced > 0) {
+        for (int e = 0; e < count; e++) if (obs_counts[e] >= 0) c->scenes.h_obs_count[scene_ids[e]] = obs_counts[e];
+        c->max_obs_radius = std::max(c->max_obs_radius, obs_max_r);    // only grows: a conservative filter (sca_set_scene_obstacles)
+    }
     c->scenes.partial = scenes_any_partial(c->scenes.v.nscenes, off, c->scenes.h_size.data());
     scene_harvest_clear_fresh(c, count, scene_ids);                    // an uncollected harvest of a restarted scene is gone (behind the synchronisation above)
     c->h_pos_valid = false;                                            // (no host mirror of the positions is kept, as in sca_step_host)
@@ -1669,6 +1780,13 @@ int sca_restart_scenes_sized(sca_ctx *c, int count, const int32_t *scene_ids, co
                              const uint8_t *zaxis, const double *max_run_dist, const double *goal_heading) {
     API_ENTER(c);
     return restart_scenes(c, count, scene_ids, sizes, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading);
+}
+int sca_restart_scenes_obstacles(sca_ctx *c, int count, const int32_t *scene_ids, const int32_t *sizes, const int32_t *obs_counts, const double *obs_pos,
+                                 const double *obs_radius, const double *pos, const float *vel, const double *heading, const double *radius,
+                                 const double *pref_speed, const double *goal, const uint8_t *policy, const uint8_t *zaxis, const double *max_run_dist,
+                                 const double *goal_heading) {
+    API_ENTER(c);
+    return restart_scenes(c, count, scene_ids, sizes, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading, obs_counts, obs_pos, obs_radius);
 }
 int sca_get_scene_sizes(sca_ctx *c, int32_t *size) {
     API_ENTER(c);

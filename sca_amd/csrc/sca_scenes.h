@@ -248,6 +248,112 @@ inline RestartLayout scene_restart_layout(int cap) {
 constexpr uint32_t RESTART_HAS_RADIUS = 1, RESTART_HAS_PREF_SPEED = 2, RESTART_HAS_GOAL = 4, RESTART_HAS_ZAXIS = 8, RESTART_HAS_MAX_RUN_DIST = 16,
                    RESTART_HAS_GOAL_HEADING = 32;
 
+// ---- obstacle slots (sca_set_scene_obstacle_slots) ------------------------------------------------------------------------------------------------
+// Scene s's obstacle range [cap_offsets[s], cap_offsets[s + 1]) is a CAPACITY, as its agent range is with sca_restart_scenes_sized: it holds
+// counts[s] obstacles, 0 <= counts[s] <= capacity, in its first rows, and its tree -- 2 counts[s] - 1 nodes numbered from 2 * cap_offsets[s]
+// -- always fits the 2 x capacity node records of the range.  The offsets obey scene_obstacles_check's rules; pos / radius are packed
+// densely in scene order (sum(counts) rows).
+enum ObsSlotFault {
+    OBS_SLOT_OK = 0,
+    OBS_SLOT_OFFSETS,       // a rule of scene_obstacles_check (its fault is reported beside this one)
+    OBS_SLOT_BAD_COUNT,     // counts[s] outside 0 .. capacity (scene: s)
+    OBS_SLOT_NO_ARRAYS,     // a positive sum of counts with pos == NULL or radius == NULL
+    OBS_SLOT_NOT_FINITE,    // a position that is not finite (scene: its scene, row: the packed row)
+    OBS_SLOT_BAD_RADIUS     // a radius that is not positive -- NaN included (scene, row as above)
+};
+// offsets: scene_obstacles_check's answer (SCENE_OBS_OK unless fault == OBS_SLOT_OFFSETS); total: sum(counts) where the counts passed; capacity: cap_offsets[nscenes]
+struct ObsSlotCheck { ObsSlotFault fault; SceneObsFault offsets; int scene; int row; int total; int capacity; };
+inline bool obs_slot_count_ok(int count, int capacity) { return count >= 0 && count <= capacity; }
+// the first packed row whose position is not finite (*bad_radius = false) or whose radius is not positive (*bad_radius = true), -1: none
+inline int obstacle_rows_fault(int rows, const double *pos, const double *radius, bool *bad_radius) {
+    for (int r = 0; r < rows; r++) {
+        if (!(restart_finite(pos[3 * r]) && restart_finite(pos[3 * r + 1]) && restart_finite(pos[3 * r + 2]))) { *bad_radius = false; return r; }
+        if (!(radius[r] > 0.0) || !restart_finite(radius[r])) { *bad_radius = true; return r; }
+    }
+    return -1;
+}
+inline ObsSlotCheck obstacle_slots_check(int ctx_nscenes, int max_obstacles, int nscenes, const int32_t *cap_offsets, const int32_t *counts,
+                                         const double *pos, const double *radius) {
+    const SceneObsCheck o = scene_obstacles_check(ctx_nscenes, max_obstacles, nscenes, cap_offsets, true, true);
+    if (o.fault != SCENE_OBS_OK) return {OBS_SLOT_OFFSETS, o.fault, o.scene, -1, 0, o.total};
+    int total = 0;
+    if (counts)
+        for (int s = 0; s < nscenes; s++) {
+            if (!obs_slot_count_ok(counts[s], cap_offsets[s + 1] - cap_offsets[s])) return {OBS_SLOT_BAD_COUNT, SCENE_OBS_OK, s, -1, 0, o.total};
+            total += counts[s];                                         // (at most max_obstacles: no overflow)
+        }
+    if (total > 0 && !(pos && radius)) return {OBS_SLOT_NO_ARRAYS, SCENE_OBS_OK, -1, -1, total, o.total};
+    bool bad_radius = false;
+    const int r = total > 0 ? obstacle_rows_fault(total, pos, radius, &bad_radius) : -1;
+    if (r >= 0) {
+        int s = 0;
+        for (int before = 0; before + counts[s] <= r; before += counts[s], s++) {}
+        return {bad_radius ? OBS_SLOT_BAD_RADIUS : OBS_SLOT_NOT_FINITE, SCENE_OBS_OK, s, r, total, o.total};
+    }
+    return {OBS_SLOT_OK, SCENE_OBS_OK, -1, -1, total, o.total};
+}
+inline int obstacle_slots_error_code(ObsSlotFault f) { return f == OBS_SLOT_OK ? SCA_OK : SCA_ERR_ARG; }
+// where a slot's walks start: its first node record, -1 while it is empty
+inline int obstacle_slot_root(const int32_t *cap_offsets, const int32_t *counts, int s) { return counts[s] > 0 ? 2 * cap_offsets[s] : -1; }
+
+// ---- a restart that brings obstacles (sca_restart_scenes_obstacles) -------------------------------------------------------------------------------
+// obs_counts[e] for scene scene_ids[e]: -1 keeps the slot's set, 0 .. capacity replaces it; the replaced scenes' obstacles are packed in
+// the order of scene_ids.  Looked at behind scene_restart_check (the ids are valid then).
+enum RestartObsFault {
+    RESTART_OBS_OK = 0,
+    RESTART_OBS_NO_SLOTS,   // a count >= 0 while the context has no obstacle slots (entry: its index)         SCA_ERR_STATE
+    RESTART_OBS_BAD_COUNT,  // a count below -1 or above the slot's capacity (entry: its index)                } SCA_ERR_ARG
+    RESTART_OBS_NO_ARRAYS,  // obs_pos or obs_radius NULL with a positive total                                }
+    RESTART_OBS_NOT_FINITE, // an obstacle position that is not finite (entry: the packed obstacle row)        }
+    RESTART_OBS_BAD_RADIUS  // an obstacle radius that is not positive (entry: the packed obstacle row)        }
+};
+// total: the obstacle rows the arrays hold; replaced: the entries with a count >= 0 (RESTART_OBS_OK)
+struct RestartObsCheck { RestartObsFault fault; int entry; int total; int replaced; };
+inline RestartObsCheck restart_obstacles_check(bool slots_on, const int32_t *cap_offsets, int count, const int32_t *scene_ids, const int32_t *obs_counts,
+                                               const double *obs_pos, const double *obs_radius) {
+    if (obs_counts == nullptr) return {RESTART_OBS_OK, -1, 0, 0};
+    int total = 0, replaced = 0;
+    for (int e = 0; e < count; e++) {
+        const int k = obs_counts[e];
+        if (k < -1) return {RESTART_OBS_BAD_COUNT, e, 0, 0};
+        if (k == -1) continue;
+        if (!slots_on) return {RESTART_OBS_NO_SLOTS, e, 0, 0};
+        if (k > cap_offsets[scene_ids[e] + 1] - cap_offsets[scene_ids[e]]) return {RESTART_OBS_BAD_COUNT, e, 0, 0};
+        total += k; replaced++;
+    }
+    if (total > 0 && !(obs_pos && obs_radius)) return {RESTART_OBS_NO_ARRAYS, -1, total, replaced};
+    bool bad_radius = false;
+    const int r = total > 0 ? obstacle_rows_fault(total, obs_pos, obs_radius, &bad_radius) : -1;
+    if (r >= 0) return {bad_radius ? RESTART_OBS_BAD_RADIUS : RESTART_OBS_NOT_FINITE, r, total, replaced};
+    return {RESTART_OBS_OK, -1, total, replaced};
+}
+inline int restart_obstacles_error_code(RestartObsFault f) { return f == RESTART_OBS_OK ? SCA_OK : f == RESTART_OBS_NO_SLOTS ? SCA_ERR_STATE : SCA_ERR_ARG; }
+
+// The obstacle sections of the restart's page-locked block, behind the agent sections and the new sizes: per named scene four words
+// (count or -1, the scene's obstacle base, where its rows start in the packed sections, its new root), then the packed ObsRec rows, the
+// sorted rows, the permutation with global ids, and the KdNode / KdWide records -- two per obstacle row, a tree over k rows at records
+// [2 * start, 2 * start + 2k - 1).  Every section starts on a 64-byte boundary and every record is a multiple of 16 bytes, so a record is
+// read as whole 16-byte pieces; the sizes depend on sca_create's max_agents (at most that many scenes) and max_obstacles alone.
+enum RestartObsSection : int { RO_HEAD = 0, RO_REC, RO_SORTED, RO_PERM, RO_TREE, RO_WIDE, RO_SECTIONS };
+constexpr int RO_HEAD_WORDS = 4;            // count, base, start, root
+constexpr int64_t RO_REC_BYTES = 32, RO_TREE_BYTES = 64, RO_WIDE_BYTES = 128;
+struct RestartObsLayout { int64_t off[RO_SECTIONS]; int64_t total; };
+inline int64_t restart_obs_section_bytes(int s, int max_n, int max_obstacles) {
+    return s == RO_HEAD ? 4 * RO_HEAD_WORDS * (int64_t)max_n : s == RO_REC || s == RO_SORTED ? RO_REC_BYTES * max_obstacles : s == RO_PERM ? 4 * (int64_t)max_obstacles
+           : (s == RO_TREE ? RO_TREE_BYTES : RO_WIDE_BYTES) * 2 * (int64_t)max_obstacles;
+}
+// begin: where the sections start in the block (a multiple of RS_ALIGN is kept one)
+inline RestartObsLayout restart_obstacles_layout(int64_t begin, int max_n, int max_obstacles) {
+    RestartObsLayout L;
+    int64_t at = (begin + RS_ALIGN - 1) / RS_ALIGN * RS_ALIGN;
+    for (int s = 0; s < RO_SECTIONS; s++) {
+        L.off[s] = at;
+        at += (restart_obs_section_bytes(s, max_n, max_obstacles) + RS_ALIGN - 1) / RS_ALIGN * RS_ALIGN;
+    }
+    L.total = at;
+    return L;
+}
+
 // ---- a trajectory log per scene (sca_scene_history_enable) -------------------------------------------------------------------------------------
 // One allocation of capacity x n rows of SCENE_LOG_ROW_BYTES (HistRow, sca_kernels.hip.h).  Scene s owns rows [capacity * offsets[s],
 // capacity * offsets[s + 1]); inside its part the layout is [row][agent] with pitch n_s, so any window of rows of one scene is one contiguous

@@ -16,6 +16,9 @@
 // three kernels above are templated on where an agent's walks start: SceneRoots (the scene's agent root, obstacle walks from 0) or
 // SceneObsRoots, whose obstacle walks start at the scene's own obstacle root, or do not happen for a scene without obstacles.  Those roots
 // travel in SceneObsView, a member of SceneObsRoots only: a context with a shared set runs the SceneRoots instances, the code it ran before.
+// Obstacle slots (sca_set_scene_obstacle_slots): a scene's obstacle range is a capacity, and since the walks start at a root word they load
+// and reach obstacles only through the tree's links, a restart that brings obstacles (k_scene_restart_obs) installs a new tree into the
+// scene's part of the forest and rewrites that word -- the three kernels above do not change.
 #pragma once
 #include "sca_kdbuild.hip.h"
 #include "sca_scenes.h"
@@ -36,6 +39,7 @@ constexpr int SCENE_LINE = 32;           // int32 per counter line
 
 struct SceneObsView {
     const int32_t *oroot;     // [nscenes] record of owide / otree the scene's obstacle walks start at (2 * obs_offsets[s]), -1: the scene has no obstacles
+                              // (behind it in the same allocation: [nscenes] the obstacles each scene holds, which no kernel of a step reads)
 };
 // Where an agent's walks start (RootZero, sca_kernels.hip.h): one kernel argument, by value.  Two dependent loads per agent and root (its
 // scene, the scene's root); every lane that serves an agent reads the same words.
@@ -201,6 +205,51 @@ __global__ __launch_bounds__(RESTART_T) void k_scene_restart_sized(RestartDev d,
     scene_restart_fill(d, blk, L, has, row0, lo, ns, t);
     scene_restart_vacate(d, lo + ns, hi, t);
     if (t == 0) { d.live[s * SCENE_LINE] = ns; d.prev[s] = ns; d.steps[s] = 0; size[s] = ns; }
+}
+
+// A restart that brings obstacles (sca_restart_scenes_obstacles): the launch used whenever a named scene replaces its obstacle set -- the
+// agent rows by the functions above (a full slot vacates an empty range and writes the size it has), then, for a scene whose head words
+// say so, its part of the obstacle forest from the block's obstacle sections (RestartObsLayout, sca_scenes.h): records, sorted records,
+// permutation, both node arrays, and last the root word the scene's walks start at and the count.  Every word written lies in the named
+// scene's rows [base, base + k) or node records [2 base, 2 base + 2k - 1), inside its capacity (the host checked k against it); rows and
+// records behind them keep what an earlier set left -- no link of the new tree leads there, and the root is the only way in.  No atomics.
+// The 32-, 64- and 128-byte records travel as 16-byte pieces, consecutive lanes on consecutive pieces: a wavefront's load covers 1 KB of
+// consecutive bytes of the block across the link, and its store the same in device memory.
+typedef uint32_t __attribute__((ext_vector_type(4), may_alias)) restart_piece;
+static_assert(sizeof(ObsRec) == RO_REC_BYTES && sizeof(KdNode) == RO_TREE_BYTES && sizeof(KdWide) == RO_WIDE_BYTES, "RestartObsLayout's records");
+struct RestartObsDev {
+    ObsRec *obs, *obs_sorted;     // [M]
+    int32_t *operm;               // [M]
+    KdNode *otree;                // [2M]
+    KdWide *owide;                // [2M]
+    int32_t *oroot, *ocount;      // [nscenes]
+};
+__device__ __forceinline__ void scene_restart_pieces(void *dst, const void *src, int64_t pieces, int t) {
+    restart_piece *to = (restart_piece *)dst;
+    const restart_piece *from = (const restart_piece *)src;
+    for (int64_t w = t; w < pieces; w += RESTART_T) to[w] = from[w];
+}
+__global__ __launch_bounds__(RESTART_T) void k_scene_restart_obs(RestartDev d, const uint8_t *blk, RestartLayout L, uint32_t has, const int32_t *new_size, int32_t *size,
+                                                                 RestartObsDev o, RestartObsLayout OL) {
+    const int b = (int)blockIdx.x, t = (int)threadIdx.x;
+    const int s = ((const int32_t *)(blk + L.off[RS_IDS]))[b];
+    const int row0 = ((const int32_t *)(blk + L.off[RS_START]))[b];
+    const int lo = d.offsets[s], hi = d.offsets[s + 1], ns = new_size[b];
+    scene_restart_fill(d, blk, L, has, row0, lo, ns, t);
+    scene_restart_vacate(d, lo + ns, hi, t);
+    if (t == 0) { d.live[s * SCENE_LINE] = ns; d.prev[s] = ns; d.steps[s] = 0; size[s] = ns; }
+    const int32_t *head = (const int32_t *)(blk + OL.off[RO_HEAD]) + RO_HEAD_WORDS * b;
+    const int k = head[0];
+    if (k < 0) return;                                                 // this scene keeps its set (uniform over the workgroup)
+    const int64_t base = head[1], st = head[2];
+    const int64_t nodes = k > 0 ? 2 * (int64_t)k - 1 : 0;
+    scene_restart_pieces(o.obs + base, blk + OL.off[RO_REC] + RO_REC_BYTES * st, k * (RO_REC_BYTES / 16), t);
+    scene_restart_pieces(o.obs_sorted + base, blk + OL.off[RO_SORTED] + RO_REC_BYTES * st, k * (RO_REC_BYTES / 16), t);
+    const int32_t *perm = (const int32_t *)(blk + OL.off[RO_PERM]) + st;
+    for (int i = t; i < k; i += RESTART_T) o.operm[base + i] = perm[i];
+    scene_restart_pieces(o.otree + 2 * base, blk + OL.off[RO_TREE] + RO_TREE_BYTES * 2 * st, nodes * (RO_TREE_BYTES / 16), t);
+    scene_restart_pieces(o.owide + 2 * base, blk + OL.off[RO_WIDE] + RO_WIDE_BYTES * 2 * st, nodes * (RO_WIDE_BYTES / 16), t);
+    if (t == 0) { o.oroot[s] = head[3]; o.ocount[s] = k; }
 }
 
 // The wavefront-per-agent forms keep both roots in scalar registers: the obstacle phase is taken or skipped by the whole wavefront (the

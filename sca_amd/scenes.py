@@ -6,6 +6,9 @@ own kd-tree, its own carried permutation and its own `done`, agents of different
 bit what a MACAEnv holding that scene alone produces.  Obstacles are either one list shared by all scenes (`obstacles`) or one list per
 scene (`scene_obstacles`, sca_set_scene_obstacles): then every scene meets its own obstacles and no others -- an open circle, a take-off
 field with its spheres and two seeds of an obstacle scenario share one batch -- and is still bit for bit the MACAEnv of that scene alone.
+With `obstacle_capacities` a scene's obstacle range is a capacity too (sca_set_scene_obstacle_slots): SceneBatch.restart(..., obstacles=...)
+then brings a new episode's own obstacles into the slot, and run_episodes(episode_obstacles=...) streams a queue whose episodes differ in
+their obstacles.
 
     batch = SceneBatch([build_agents(seed) for seed in seeds], obstacles, device_tracker=True)   # each list numbered 0 .. n_s - 1
     while not batch.step():
@@ -73,7 +76,7 @@ class SceneEnv:
     def __init__(self, batch, s, agents, lo, hi):
         self._batch, self.scene, self._lo = batch, s, lo
         self._obs_lo = 0 if batch.scene_obstacles is None else int(batch.obstacle_offsets[s])      # the context's obstacle ids are global
-        self.obstacles = batch.obstacles if batch.scene_obstacles is None else batch.scene_obstacles[s]
+        self.obstacles = batch.obstacles if batch.scene_obstacles is None else batch.scene_obstacles[s]    # (restart(obstacles=...) replaces the list)
         self.kdTree = _SceneKdTree(self)
         self._occupy(agents, hi)
         self._time_cum = [0.0]
@@ -122,8 +125,12 @@ class SceneEnv:
 
 class SceneBatch(_FlatAgents):
     def __init__(self, scenes, obstacles=(), scene_obstacles=None, neighbor_mode=S.NBR_KDTREE, device_tracker=False, history_capacity=0, scene_history=0, device=0,
-                 capacities=None, harvest=False):
-        """harvest: finished scenes hand over their result with the step (sca_scene_harvest_enable): step() reads `active` / `steps` from the
+                 capacities=None, harvest=False, obstacle_capacities=None):
+        """obstacle_capacities: one obstacle capacity per scene, each >= len(scene_obstacles[s]), or 'max' (every slot holds the largest
+        list); None: none.  The scenes' obstacle ranges are then OBSTACLE SLOTS (sca_set_scene_obstacle_slots): the initial lists
+        (scene_obstacles; None: every slot starts empty) go through the slots call, and restart(..., obstacles={s: [...]}) brings a new
+        episode's own list of up to that many obstacles into a slot.
+        harvest: finished scenes hand over their result with the step (sca_scene_harvest_enable): step() reads `active` / `steps` from the
         harvest block behind the step's own synchronisation instead of a second read-back, finished() names the scenes that ended since it
         was last called and harvested(s) gives a finished scene's final rows and summary without a read-back of the batch.
         capacities: one agent capacity per scene, each >= len(scene) (None: the scene's own length).  Scene s then owns capacities[s] rows
@@ -139,12 +146,23 @@ class SceneBatch(_FlatAgents):
                     raise ValueError(f'scene {s}: agent.id must equal its index in its scene (kdTree.py:64), as for an env of its own')
         self.obstacles = list(obstacles)
         self.scene_obstacles = None if scene_obstacles is None else [list(o) for o in scene_obstacles]
+        self.obstacle_slots = obstacle_capacities is not None
+        if self.obstacle_slots and self.scene_obstacles is None:
+            self.scene_obstacles = [[] for _ in scenes]
         if self.scene_obstacles is not None:
             if self.obstacles:
                 raise ValueError('a SceneBatch takes either `obstacles` (one list shared by all scenes) or `scene_obstacles` (one list per scene)')
             if len(self.scene_obstacles) != len(scenes):
                 raise ValueError(f'scene_obstacles: {len(self.scene_obstacles)} lists for {len(scenes)} scenes')
-            self.obstacle_offsets = np.concatenate([[0], np.cumsum([len(o) for o in self.scene_obstacles])]).astype(np.int32)
+            held = [len(o) for o in self.scene_obstacles]
+            if isinstance(obstacle_capacities, str):
+                if obstacle_capacities != 'max':
+                    raise ValueError(f"obstacle_capacities: None, 'max' or one capacity per scene, got {obstacle_capacities!r}")
+                obstacle_capacities = [max(held)] * len(scenes)
+            ocaps = held if obstacle_capacities is None else [int(c) for c in obstacle_capacities]
+            if len(ocaps) != len(scenes) or any(c < m for c, m in zip(ocaps, held)):
+                raise ValueError(f"obstacle_capacities: one per scene, each at least the scene's obstacle count ({held}), got {ocaps}")
+            self.obstacle_offsets = np.concatenate([[0], np.cumsum(ocaps)]).astype(np.int32)     # a scene's range: its capacity where there are slots
         self.neighbor_mode = neighbor_mode
         self.device_tracker = bool(device_tracker)
         self.capacity_slots = capacities is not None               # else: a slot keeps its size, as a batch always did
@@ -164,7 +182,9 @@ class SceneBatch(_FlatAgents):
 
         def set_scenes():                                             # between the agents' attributes and the state
             self.solver.set_scenes(self.offsets)
-            if self.scene_obstacles is not None:
+            if self.obstacle_slots:
+                self.solver.set_scene_obstacle_slots(np.diff(self.obstacle_offsets), [_obstacle_arrays(obs) for obs in self.scene_obstacles])
+            elif self.scene_obstacles is not None:
                 self.solver.set_scene_obstacles([_obstacle_arrays(obs) for obs in self.scene_obstacles])
 
         shared = self.scene_obstacles is None
@@ -236,12 +256,27 @@ class SceneBatch(_FlatAgents):
         return out
 
     # ---- a new episode into a slot while the others keep running (sca_restart_scenes) -------------------------------------------------------
-    def restart(self, scenes):
+    def restart(self, scenes, obstacles=None):
         """{s: agents}: scene s starts over with the new Agent list (numbered 0 .. n - 1; n is the slot's count, or, in a batch built with
-        `capacities`, any 1 <= n <= the slot's capacity), every other scene is untouched.  A slot keeps its capacity, its obstacles and its per-agent solver and planner attributes: ValueError, before any device
+        `capacities`, any 1 <= n <= the slot's capacity), every other scene is untouched.  A slot keeps its capacity, its obstacles (unless
+        `obstacles` brings new ones) and its per-agent solver and planner attributes: ValueError, before any device
         call, for an episode that does not fit, an agent whose attributes differ from its row's, or one that carries a path.  From here on
-        the scene is bit for bit the MACAEnv of the new episode alone, like a scene of a fresh batch."""
+        the scene is bit for bit the MACAEnv of the new episode alone, like a scene of a fresh batch.
+        obstacles ({s: [Obstacle, ...]}, a batch built with obstacle_capacities): the restarted scene s meets this list from now on (at
+        most its obstacle capacity; [] for none) -- bit for bit the MACAEnv of the new episode with that list --; a restarted scene absent
+        from it keeps its list.  ValueError before any device call for a list above the slot's capacity, a scene that is not restarted, or
+        `obstacles` on a batch without obstacle slots."""
         items = sorted((int(s), list(agents)) for s, agents in dict(scenes).items())
+        new_obs = None if obstacles is None else {int(s): list(o) for s, o in dict(obstacles).items()}
+        if new_obs is not None:
+            if not self.obstacle_slots:
+                raise ValueError('restart: obstacles for a batch without obstacle slots (SceneBatch(obstacle_capacities=...))')
+            for s, obs in new_obs.items():
+                if s not in dict(items):
+                    raise ValueError(f'restart: obstacles for scene {s}, which is not restarted')
+                cap = int(self.obstacle_offsets[s + 1] - self.obstacle_offsets[s])
+                if len(obs) > cap:
+                    raise ValueError(f'restart: scene {s} holds up to {cap} obstacles, the new episode brings {len(obs)} (a slot keeps its obstacle capacity)')
         if not items:
             return
         if self._paths_on:
@@ -271,10 +306,12 @@ class SceneBatch(_FlatAgents):
                         raise ValueError(f'restart: scene {s}, agent {i} needs the device tracker, which a batch built without such agents has not enabled')
                     if _planner_triple(a) != self._planner_of(lo + i):
                         raise ValueError(f"restart: scene {s}, agent {i}: turning_radius / pitchlims differ from the slot's (a slot keeps its planner attributes)")
-        self._send_restart(items)
+        self._send_restart(items, new_obs)
         for s, agents in items:
             lo = int(self.offsets[s])
             view = self._envs[s]
+            if new_obs and s in new_obs:
+                self.scene_obstacles[s] = view.obstacles = new_obs[s]
             self._flat[lo:lo + len(agents)] = agents                 # (the rows behind keep the agents that carry the slot's attributes)
             view._occupy(agents, lo + len(agents))
             view._time_cum = [0.0]
@@ -289,7 +326,7 @@ class SceneBatch(_FlatAgents):
             st = self.solver.scene_state()
             self.active, self.steps = st['active'], st['steps']
 
-    def _send_restart(self, items):
+    def _send_restart(self, items, new_obs=None):
         """the episodes' arrays to the device (one call), and the batch's per-agent host arrays behind them"""
         flat = [a for _, agents in items for a in agents]
         T = len(flat)
@@ -304,7 +341,8 @@ class SceneBatch(_FlatAgents):
                                    vel=np.array([a._vel for a in flat], dtype=np.float32).reshape(T, 3), radius=[a.radius for a in flat],
                                    pref_speed=[a.pref_speed for a in flat], goal=goal, policy=policy, zaxis=S.zaxis_flags(start, goal6),
                                    max_run_dist=[a.max_run_dist for a in flat], goal_heading=goal6[:, 3:6] if self._trk_on else None,
-                                   sizes=None if full else [len(agents) for _, agents in items])
+                                   sizes=None if full else [len(agents) for _, agents in items],
+                                   obstacles=[_obstacle_arrays(new_obs[s]) if s in new_obs else None for s, _ in items] if new_obs else None)
         at = 0
         for s, agents in items:
             lo, n = int(self.offsets[s]), len(agents)
@@ -375,6 +413,33 @@ def next_fitting(capacity, pending_sizes):
     return None
 
 
+def next_fitting2(capacity, obs_capacity, pending):
+    """next_fitting over both capacities: `pending` holds (agents, obstacles) per episode not started yet, in queue order; the position of
+    the first that fits a slot of `capacity` agent rows AND `obs_capacity` obstacle rows, None when there is none."""
+    for k, (n, m) in enumerate(pending):
+        if int(n) <= int(capacity) and int(m) <= int(obs_capacity):
+            return k
+    return None
+
+
+def plan_capacity_slots2(sizes, capacities):
+    """plan_capacity_slots over both capacities: sizes = [(agents, obstacles)] per episode, capacities = [(agent rows, obstacle rows)] per
+    slot.  One entry per slot (None: nothing fits it); ValueError when some episode fits no slot at all."""
+    sizes = [(int(n), int(m)) for n, m in sizes]
+    capacities = [(int(c), int(oc)) for c, oc in capacities]
+    if not capacities or min(c for c, _ in capacities) < 1 or min(oc for _, oc in capacities) < 0:
+        raise ValueError(f'slot capacities must be positive (obstacles: not negative), got {capacities}')
+    for i, (n, m) in enumerate(sizes):
+        if not any(n <= c and m <= oc for c, oc in capacities):
+            raise ValueError(f'episode {i} has {n} agents and {m} obstacles and fits no slot (capacities {capacities})')
+    pending = list(range(len(sizes)))
+    holding = []
+    for c, oc in capacities:
+        k = next_fitting2(c, oc, [sizes[j] for j in pending])
+        holding.append(None if k is None else pending.pop(k))
+    return holding
+
+
 def plan_capacity_slots(sizes, capacities):
     """Which queue entry every slot starts with when slot s holds any episode of up to capacities[s] agents: the slots choose in their own
     order, each the first entry in queue order that fits it and that no earlier slot took (next_fitting).  Returns one entry per slot, None
@@ -421,10 +486,15 @@ def _harvest_policy_time(view, h):
 
 
 def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=None, max_steps=None, stats=None, history_rows=0, capacities=None,
-                 harvest=False):
+                 harvest=False, episode_obstacles=None, obstacle_capacities='max'):
     """Streams a queue of episodes (Agent lists, each numbered 0 .. n - 1) through `slots` scenes of ONE SceneBatch: when a scene finishes,
     its metrics, step count and final state are taken and the slot restarts with the next episode of its size (SceneBatch.restart), while
-    the other slots keep running.  Obstacles are one list shared by all episodes.  Returns one dict per episode in queue order:
+    the other slots keep running.  Obstacles are one list shared by all episodes (`obstacles`), or -- mutually exclusive with it --
+    episode_obstacles, one list of Obstacle per episode: every episode then brings its own obstacles into its slot (obstacle slots,
+    SceneBatch(obstacle_capacities=...)), and a finished slot takes the first pending episode that fits BOTH its agent and its obstacle
+    capacity (next_fitting2).  obstacle_capacities: 'max' sizes every slot for the largest list in the queue; a list gives one obstacle
+    capacity per slot (ValueError up front when some episode fits no slot).  Without `capacities` the slots' agent capacities are those
+    of 'max' as well: a queue with per-episode obstacles always runs on capacity slots.  Returns one dict per episode in queue order:
     episode, slot, metrics (metrics.episode_metrics), steps, state (pos, vel, heading, flags, total_dist, step_num); on_done(result) is
     called as each finishes.  With device_tracker, the tracker is enabled by the episodes the slots START with: a queue whose first tracked
     (SCA, RVO3D+Dubins) episode comes later is refused here, before the first step (ValueError).  An episode that a slot cannot take (SceneBatch.restart's
@@ -441,7 +511,27 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
     synchronisation per step and, per finished episode, its own rows instead of a read-back of the whole batch."""
     episodes = [list(e) for e in episodes]
     sizes = [len(e) for e in episodes]
-    holding, caps = plan_queue(sizes, slots, capacities)
+    ocaps = None
+    if episode_obstacles is not None:
+        if len(obstacles):
+            raise ValueError('run_episodes: either `obstacles` (one list shared by all episodes) or `episode_obstacles` (one list per episode)')
+        episode_obstacles = [list(o) for o in episode_obstacles]
+        if len(episode_obstacles) != len(episodes):
+            raise ValueError(f'run_episodes: {len(episode_obstacles)} obstacle lists for {len(episodes)} episodes')
+        osizes = [len(o) for o in episode_obstacles]
+        capacities = 'max' if capacities is None else capacities
+        acaps = [max(sizes)] * int(slots) if isinstance(capacities, str) and capacities == 'max' else capacities
+        ocaps = [max(osizes)] * int(slots) if isinstance(obstacle_capacities, str) and obstacle_capacities == 'max' else obstacle_capacities
+        if isinstance(acaps, str) or isinstance(ocaps, str) or ocaps is None:
+            raise ValueError(f"run_episodes: capacities and obstacle_capacities are 'max' or one capacity per slot, got {capacities!r} and {obstacle_capacities!r}")
+        if len(acaps) != int(slots) or len(ocaps) != int(slots):
+            raise ValueError(f'run_episodes: {len(acaps)} agent and {len(ocaps)} obstacle capacities for {slots} slots')
+        both = list(zip(sizes, osizes))
+        holding = plan_capacity_slots2(both, list(zip(acaps, ocaps)))
+        used = [s for s, i in enumerate(holding) if i is not None]         # slots that would start empty are left out of the batch
+        holding, caps, ocaps = [holding[s] for s in used], [int(acaps[s]) for s in used], [int(ocaps[s]) for s in used]
+    else:
+        holding, caps = plan_queue(sizes, slots, capacities)
     batch_agents = sum(caps)                                    # the slots keep their rows: the batch's agent count, for live_fraction
     pending = [i for i in range(len(episodes)) if i not in set(holding)]
     tracked = [any(a.policy.needs_external_vpref for a in e) for e in episodes]
@@ -449,7 +539,8 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
         raise ValueError('run_episodes: episode %d needs the device tracker, but none of the episodes the slots start with does, so the batch '
                          'would run without one: put a tracked episode among the first %d' % (min(i for i in pending if tracked[i]), len(holding)))
     batch = SceneBatch([episodes[i] for i in holding], obstacles, device_tracker=device_tracker, scene_history=history_rows,
-                       capacities=None if capacities is None else caps, harvest=harvest)
+                       capacities=None if capacities is None else caps, harvest=harvest,
+                       scene_obstacles=None if ocaps is None else [episode_obstacles[i] for i in holding], obstacle_capacities=ocaps)
     results = [None] * len(episodes)
     batch_steps = served = 0
     try:
@@ -457,7 +548,7 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
             served += int(batch.active.sum())
             batch.step()
             batch_steps += 1
-            refill = {}
+            refill, refill_obs = {}, {}
             # (one step per collect: finished() is in slot order, as the scan of batch.done is)
             for s in (batch.finished() if harvest else [s for s, i in enumerate(holding) if i is not None and batch.done[s]]):
                 i = holding[s]
@@ -478,12 +569,17 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
                 if on_done is not None:
                     on_done(results[i])
                 left = [sizes[j] for j in pending]
-                k = next_episode(sizes[i], left) if capacities is None else next_fitting(caps[s], left)
+                if ocaps is not None:
+                    k = next_fitting2(caps[s], ocaps[s], [both[j] for j in pending])
+                else:
+                    k = next_episode(sizes[i], left) if capacities is None else next_fitting(caps[s], left)
                 holding[s] = None if k is None else pending.pop(k)
                 if holding[s] is not None:
                     refill[s] = episodes[holding[s]]
+                    if ocaps is not None:
+                        refill_obs[s] = episode_obstacles[holding[s]]
             if refill:
-                batch.restart(refill)
+                batch.restart(refill, obstacles=refill_obs if ocaps is not None else None)
     finally:
         batch.close()
     if stats is not None:

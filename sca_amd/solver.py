@@ -214,15 +214,62 @@ class BatchedSolver:
         self.m = int(off[-1])
         self.scene_obstacle_offsets = off
 
+    def set_scene_obstacle_slots(self, capacities, sets=None):
+        """Obstacle slots (sca_set_scene_obstacle_slots): scene s may hold up to capacities[s] obstacles and starts with sets[s] = (pos
+        [m_s, 3], radius [m_s]), m_s <= capacities[s]; None (for the list or an entry): empty.  A later restart_scenes(obstacles=...) replaces
+        a scene's set.  Obstacle ids in neighbors() are global: scene_obstacle_offsets[s] + the scene's own id."""
+        caps = np.ascontiguousarray(capacities, np.int64).reshape(-1)
+        if len(caps) != self.nscenes:
+            raise ValueError(f'set_scene_obstacle_slots: {len(caps)} capacities for {self.nscenes} scenes')
+        if sets is not None and len(sets) != self.nscenes:
+            raise ValueError(f'set_scene_obstacle_slots: {len(sets)} obstacle sets for {self.nscenes} scenes')
+        off = np.zeros(len(caps) + 1, np.int32)
+        off[1:] = np.cumsum(caps)
+        counts, allp, allr = self._pack_obstacle_sets(sets if sets is not None else [None] * len(caps), 'set_scene_obstacle_slots')
+        counts = np.maximum(counts, 0)                            # (None: empty)
+        self._chk(self.L.sca_set_scene_obstacle_slots(self.ctx, len(caps), _lib.ptr(off, C.c_int32), _lib.ptr(counts, C.c_int32),
+                                                      _lib.ptr(allp, C.c_double), _lib.ptr(allr, C.c_double)), 'sca_set_scene_obstacle_slots')
+        self.m = int(off[-1])
+        self.scene_obstacle_offsets = off
+
+    @staticmethod
+    def _pack_obstacle_sets(sets, who):
+        """counts [len(sets)] int32 (-1 for None), pos [sum, 3], radius [sum]: the sets packed in order"""
+        counts = np.full(len(sets), -1, np.int32)
+        pos, radius = [np.zeros((0, 3))], [np.zeros(0)]
+        for e, st in enumerate(sets):
+            if st is None:
+                continue
+            r = _lib.as_d(st[1]).reshape(-1)
+            p = _lib.as_d(st[0])
+            if p.size != 3 * len(r):
+                raise ValueError(f'{who}: set {e} has {p.size} coordinates for {len(r)} radii')
+            counts[e] = len(r)
+            pos.append(p.reshape(len(r), 3))
+            radius.append(r)
+        return counts, np.ascontiguousarray(np.concatenate(pos)), np.ascontiguousarray(np.concatenate(radius))
+
+    def scene_obstacle_counts(self):
+        """dict(counts [B] int32: the obstacles each scene holds, capacities [B] int32) (sca_get_scene_obstacle_counts)"""
+        out = dict(counts=np.zeros(self.nscenes, np.int32), capacities=np.zeros(self.nscenes, np.int32))
+        self._chk(self.L.sca_get_scene_obstacle_counts(self.ctx, _lib.ptr(out['counts'], C.c_int32), _lib.ptr(out['capacities'], C.c_int32)),
+                  'sca_get_scene_obstacle_counts')
+        return out
+
     def restart_scenes(self, ids, pos, heading, vel=None, radius=None, pref_speed=None, goal=None, policy=None, zaxis=None, max_run_dist=None,
-                       goal_heading=None, sizes=None):
+                       goal_heading=None, sizes=None, obstacles=None):
         """New episodes into the scenes `ids` while the others keep running (sca_restart_scenes).  The arrays hold T rows, the named scenes'
         agents in the order of `ids`; None keeps the slot's values (vel: zero).  Afterwards each named scene is what a context of that
-        episode alone is after set_agents + set_state (+ device_tracker_enable); its obstacle set and per-agent attributes stay.
+        episode alone is after set_agents + set_state (+ device_tracker_enable); its per-agent attributes stay, and its obstacle set unless
+        `obstacles` replaces it.
         sizes (sca_restart_scenes_sized): the agents each named scene takes, 1 .. its capacity (the length of its range) -- T is their sum,
-        and the rows of the range behind them are vacant; None fills every named scene to its capacity."""
+        and the rows of the range behind them are vacant; None fills every named scene to its capacity.
+        obstacles (sca_restart_scenes_obstacles; obstacle slots set): per named scene None -- it keeps its set -- or (pos [m, 3], radius [m])
+        with m at most the slot's obstacle capacity -- its set is replaced.  None: every named scene keeps its set."""
         ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
         keep = [ids]
+        if obstacles is not None and len(obstacles) != len(ids):
+            raise ValueError(f'restart_scenes: {len(obstacles)} obstacle sets for {len(ids)} scenes')
         if sizes is not None:
             sizes = np.ascontiguousarray(sizes, np.int32).reshape(-1)
             if len(sizes) != len(ids):
@@ -251,7 +298,12 @@ class BatchedSolver:
         u1 = lambda a: arr(a, np.uint8, C.c_uint8, 0)
         rest = (d3(pos), arr(vel, np.float32, C.c_float, 3), d3(heading), d1(radius), d1(pref_speed), d3(goal), u1(policy), u1(zaxis), d1(max_run_dist),
                 d3(goal_heading))
-        if sizes is None:
+        if obstacles is not None:
+            ocnt, opos, orad = self._pack_obstacle_sets(obstacles, 'restart_scenes')
+            self._chk(self.L.sca_restart_scenes_obstacles(self.ctx, len(ids), _lib.ptr(ids, C.c_int32), None if sizes is None else _lib.ptr(sizes, C.c_int32),
+                                                          _lib.ptr(ocnt, C.c_int32), _lib.ptr(opos, C.c_double), _lib.ptr(orad, C.c_double), *rest),
+                      'sca_restart_scenes_obstacles')
+        elif sizes is None:
             self._chk(self.L.sca_restart_scenes(self.ctx, len(ids), _lib.ptr(ids, C.c_int32), *rest), 'sca_restart_scenes')
         else:
             self._chk(self.L.sca_restart_scenes_sized(self.ctx, len(ids), _lib.ptr(ids, C.c_int32), _lib.ptr(sizes, C.c_int32), *rest),

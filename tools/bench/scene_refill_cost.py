@@ -40,7 +40,18 @@ a stream sca_env_step has just drained --, sca_restart_scenes 1) and the bytes t
 (sca_get_state: 84 B for every agent row of the batch, once per step in which a scene finished; the harvest: 77 B per row of the episode
 and its 64-byte summary).  --parent-json: a scene_refill_cost.json written by the PARENT commit's tool on the same machine (same --slots,
 --waves; --alternations 5); its `stream` windows are copied into the record, with whether this build's harvest=False leg lies inside their
-min .. max.  The file keeps one entry per --slots under `runs`."""
+min .. max.  The file keeps one entry per --slots under `runs`.
+
+    python tools/bench/scene_refill_cost.py --episode-obstacles   # 256 episodes of 100 drones, 64 slots -> profiles/scene_obstacle_refill_cost.json
+
+--episode-obstacles: every episode brings its own obstacle list -- a third of the queue none, a third 8 spheres, a third 1-5 spheres, all
+seeded per episode (candidate c: c mod 3) -- and the queue runs in the two ways there are, alternated:
+    waves     fresh SceneBatch(scene_obstacles=...) B at a time: the only way such a queue could run before the obstacle slots
+    stream    run_episodes(episode_obstacles=..., obstacle_capacities='max'): a finished slot takes the next episode AND its obstacles
+              (sca_restart_scenes_obstacles)
+Identical final states per episode in both legs (asserted).  Beside them, on one batch of B slots (slot 0 of obstacle capacity 1491, the
+others 8), the wall time of one restart call: sca_restart_scenes_sized naming 1 and B / 4 scenes, sca_restart_scenes_obstacles naming the
+same scenes with 8 obstacles each, with -1 (keep) for each, and naming slot 0 with 1491 obstacles."""
 import argparse
 import json
 import os
@@ -64,20 +75,22 @@ def main():
     ap.add_argument('--mixed', action='store_true', help='a queue of mixed agent counts: fixed-size slots against capacity slots')
     ap.add_argument('--sizes', default='20,50,100', help='--mixed: the agent counts the episodes are drawn from')
     ap.add_argument('--harvest', action='store_true', help='the streamed queue with and without the scene harvest')
+    ap.add_argument('--episode-obstacles', action='store_true', help='a queue whose episodes bring their own obstacles: waves of fresh batches against the streamed queue')
     ap.add_argument('--parent-json', default=None, help="--harvest: the parent commit's scene_refill_cost.json of the same queue on the same machine")
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
-    if args.harvest and args.mixed:
-        ap.error('--harvest and --mixed are two comparisons: one at a time')
+    if args.harvest + args.mixed + args.episode_obstacles > 1:
+        ap.error('--harvest, --mixed and --episode-obstacles are three comparisons: one at a time')
     if args.out is None:
-        args.out = os.path.join(REPO, 'profiles', 'scene_harvest_cost.json' if args.harvest else 'scene_sizes_cost.json' if args.mixed else 'scene_refill_cost.json')
+        args.out = os.path.join(REPO, 'profiles', 'scene_harvest_cost.json' if args.harvest else 'scene_sizes_cost.json' if args.mixed else
+                                'scene_obstacle_refill_cost.json' if args.episode_obstacles else 'scene_refill_cost.json')
     sys.path.insert(0, REPO)
     from sca_amd import env as E, scenarios, scenes, solver as sol_mod
     pols = [E.SCAPolicy, E.RVO3DPolicy, E.SRVO3DPolicy, E.ORCA3DPolicy, E.ORCA3DPolicyOfficial, E.RVO3dDubinsPolicy]
     B, n1 = args.slots, args.agents
     count = B * args.waves
 
-    candidates = list(range(count + max(8, count // 8)))
+    candidates = list(range(count + max(8, count // (2 if args.episode_obstacles else 8))))      # (spheres in the way: more episodes without an end)
     choices = [int(v) for v in args.sizes.split(',')] if args.mixed else [n1]
     size_of = np.random.default_rng(2024).choice(choices, size=len(candidates))      # the agent count of candidate c
 
@@ -87,8 +100,31 @@ def main():
         return [E.Agent(start_pos=list(sc['start'][i]), goal_pos=list(sc['goal'][i]), vel=[0.0, 0.0, 0.0], radius=0.5, pref_speed=1.0,
                         policy=pols[c % len(pols)], id=i) for i in range(n)]
 
+    def spheres(pos, radius):
+        return [E.Obstacle(pos=list(map(float, p)), shape_dict={'shape': 'sphere', 'feature': float(r)}, id=i) for i, (p, r) in enumerate(zip(pos, radius))]
+
+    def obstacles_of(c):
+        """--episode-obstacles: candidate c's own list -- none, 8 or 1-5 spheres of radius 1 (c mod 3) inside the scene's cube, none within
+        3 m of a start or a goal"""
+        m = (0, 8, 1 + (c // 3) % 5)[c % 3]
+        sc = scenarios.random_cube(int(size_of[c]), seed=c)
+        ends = np.concatenate([sc['start'][:, :3], sc['goal'][:, :3]])
+        lo, hi = ends.min(0), ends.max(0)
+        rng, pts = np.random.default_rng(10 ** 6 + c), []
+        while len(pts) < m:
+            q = rng.uniform(lo, hi)
+            if np.linalg.norm(ends - q, axis=1).min() > 3.0:
+                pts.append(q)
+        return spheres(pts, [1.0] * m)
+
+    def batch_of(cs, eps=None, **kw):
+        eps = [episode(c) for c in cs] if eps is None else eps
+        if args.episode_obstacles:
+            return scenes.SceneBatch(eps, scene_obstacles=[obstacles_of(c) for c in cs], device_tracker=True, **kw)
+        return scenes.SceneBatch(eps, [], device_tracker=True, **kw)
+
     # the candidates that end: all of them as one batch, untimed
-    batch = scenes.SceneBatch([episode(c) for c in candidates], [], device_tracker=True)
+    batch = batch_of(candidates)
     for _ in range(args.episode_cap):
         if batch.step():
             break
@@ -107,7 +143,7 @@ def main():
         t0 = time.perf_counter()
         states, steps, served = [], 0, 0
         for w in range(0, count, B):
-            batch = scenes.SceneBatch(eps[w:w + B], [], device_tracker=True)
+            batch = batch_of(chosen[w:w + B], eps[w:w + B])
             done = False
             while not done:
                 served += int(batch.active.sum())
@@ -144,6 +180,8 @@ def main():
         eps = queue()
         stats = {}
         kw = {} if harvest is None else dict(harvest=harvest)
+        if args.episode_obstacles:
+            kw.update(episode_obstacles=[obstacles_of(c) for c in chosen], obstacle_capacities='max')
         t0 = time.perf_counter()
         res, calls = counted(lambda: scenes.run_episodes(eps, B, device_tracker=True, max_steps=args.max_steps, stats=stats, capacities=capacities, **kw))
         wall = time.perf_counter() - t0
@@ -173,7 +211,10 @@ def main():
     # one restart call beside one step of the same batch (--mixed: slots of the largest count, the restarts sized)
     eps = queue()
     cap = max(choices)
-    batch = scenes.SceneBatch(eps[:B], [], device_tracker=True, capacities=[cap] * B if args.mixed else None)
+    if args.episode_obstacles:                                       # slot 0 may hold a map's worth of obstacles, the others a field's
+        batch = batch_of(chosen[:B], eps[:B], obstacle_capacities=[1491] + [8] * (B - 1))
+    else:
+        batch = scenes.SceneBatch(eps[:B], [], device_tracker=True, capacities=[cap] * B if args.mixed else None)
     for _ in range(20):
         batch.step()
     sol = batch.solver
@@ -183,7 +224,7 @@ def main():
         sol.env_step(batch.neighbor_mode)
         t_step.append(time.perf_counter() - t0)
 
-    def restart_ms(k):
+    def restart_ms(k, obstacles=None):
         ids = list(range(k))
         flat = [a for s in ids for a in eps[B + s]]
         T = len(flat)
@@ -196,13 +237,25 @@ def main():
         ts = []
         for _ in range(30):
             t0 = time.perf_counter()
-            sol.restart_scenes(ids, pos, head, sizes=[len(eps[B + s]) for s in ids] if args.mixed else None, **kw)
+            sol.restart_scenes(ids, pos, head, sizes=[len(eps[B + s]) for s in ids] if args.mixed else None, obstacles=obstacles, **kw)
             ts.append(time.perf_counter() - t0)
         return float(np.median(ts)) * 1e3
     restart = {'scenes_1_ms': restart_ms(1), 'scenes_%d_ms' % max(1, B // 4): restart_ms(max(1, B // 4)), 'step_ms': float(np.median(t_step)) * 1e3}
+    if args.episode_obstacles:
+        rng = np.random.default_rng(7)
+        eight = lambda: (rng.uniform(-20.0, 20.0, (8, 3)) + [0.0, 0.0, 30.0], np.ones(8))
+        many = (rng.uniform(-40.0, 40.0, (1491, 3)) * [1.0, 1.0, 0.05], np.full(1491, 0.2))      # a map's worth, on the ground below the scene
+        q = max(1, B // 4)
+        restart = {'step_ms': restart['step_ms'], 'sized': {'scenes_1_ms': restart['scenes_1_ms'], 'scenes_%d_ms' % q: restart['scenes_%d_ms' % q]},
+                   'obstacles_8_each': {'scenes_1_ms': restart_ms(1, [eight()]), 'scenes_%d_ms' % q: restart_ms(q, [eight() for _ in range(q)])},
+                   'keep': {'scenes_1_ms': restart_ms(1, [None]), 'scenes_%d_ms' % q: restart_ms(q, [None] * q)},
+                   'obstacles_1491': {'scenes_1_ms': restart_ms(1, [many])},
+                   'note': 'sca_restart_scenes_sized / sca_restart_scenes_obstacles on one batch of %d slots, slot 0 of obstacle capacity 1491, the others 8; '
+                           'median of 30 calls, wall time around the call' % B}
     batch.close()
 
-    doc = {'tool': 'tools/bench/scene_refill_cost.py' + (' --mixed' if args.mixed else ' --harvest' if args.harvest else ''), 'slots': B, 'episodes': count,
+    doc = {'tool': 'tools/bench/scene_refill_cost.py' + (' --mixed' if args.mixed else ' --harvest' if args.harvest else ' --episode-obstacles' if args.episode_obstacles else ''),
+           'slots': B, 'episodes': count,
            'agents_per_episode': {str(n): int((size_of[chosen] == n).sum()) for n in choices} if args.mixed else n1, 'alternations': args.alternations,
            'episode_cap': args.episode_cap, 'last_seed': chosen[-1], 'seeds_left_out_no_end_within_cap': left_out,
            'policies': 'SCA, RVO3D, S-RVO3D, ORCA3D, ORCA3D-LP, RVO3D+Dubins in turn; seeded random scenes; device tracker in the pass',
@@ -215,6 +268,8 @@ def main():
         if args.harvest:
             doc['legs'][name].update(ms_per_batch_step=1e3 * wall / st['batch_steps'], syncs_per_batch_step=st['syncs_per_batch_step'],
                                      readback_bytes_per_episode=st['readback_bytes_per_episode'], library_calls=st['calls'])
+    if args.episode_obstacles:
+        doc['obstacles_per_episode'] = {str(m): int(sum(len(obstacles_of(c)) == m for c in chosen)) for m in (0, 1, 2, 3, 4, 5, 8)}
     ratio = 'capacity_over_fixed_episodes_per_s' if args.mixed else 'harvest_over_stream_episodes_per_s' if args.harvest else 'stream_over_waves_episodes_per_s'
     over, under = ('capacity', 'fixed') if args.mixed else ('harvest', 'stream') if args.harvest else ('stream', 'waves')
     doc[ratio] = doc['legs'][over]['episodes_per_s'] / doc['legs'][under]['episodes_per_s']
