@@ -256,7 +256,8 @@ int sca_restart_scenes(sca_ctx *ctx, int count, const int32_t *scene_ids /*count
  *              capacity (the message names the entry).  A refused call has changed nothing.
  *   sca_get_scene_sizes       size[s] of every scene.  sca_set_scenes sets every size to its capacity; sca_set_agents and
  *              sca_set_scenes(0, NULL) drop the sizes with the scenes.  SCA_ERR_STATE without scenes.  A context that never calls the sized
- *              restart has every scene full and behaves, and enqueues, exactly as before.
+ *              restart has every scene full and behaves exactly as before (the one restart kernel serves all three entry points: on a
+ *              full scene it vacates an empty range and rewrites the size the scene has).
  *   vacant rows   belong to the library.  The read-backs over the whole range (sca_get_state, sca_get_kd_perm, sca_get_actions,
  *              sca_get_neighbors, sca_get_diag) still cover them: a vacant row reads flags SCA at-goal | collision (3), zero velocity, zero
  *              heading, zero total_dist and step_num, the position and radius of whoever stood there last, a zero action row, an empty
@@ -298,7 +299,7 @@ int sca_get_scene_sizes(sca_ctx *ctx, int32_t *size /*nscenes*/);
  *              scenes or without per-scene sets.
  *   sca_restart_scenes_obstacles   sca_restart_scenes_sized (sizes == NULL: capacities) that also brings the episodes' obstacles.
  *              obs_counts == NULL: exactly sca_restart_scenes_sized.  obs_counts[e] == -1: scene scene_ids[e] KEEPS its set -- seeds that
- *              share a map: nothing is rebuilt and nothing is staged for it.  0 .. capacity: the scene's set is REPLACED by the next
+ *              share a map: nothing is rebuilt and nothing but its head word, which says so, is staged for it.  0 .. capacity: the scene's set is REPLACED by the next
  *              obs_counts[e] rows of obs_pos / obs_radius, which hold the replaced scenes' obstacles packed in the order of scene_ids.
  *              The scene contract extends: after the call a named scene is bit for bit a context that holds that episode alone after
  *              sca_set_agents + sca_set_obstacles(that set) + sca_set_state (+ the tracker's enable) -- state, float32 action rows,
@@ -310,7 +311,9 @@ int sca_get_scene_sizes(sca_ctx *ctx, int32_t *size /*nscenes*/);
  *              not positive, obs_pos or obs_radius NULL with a positive total (each message names the entry).  A refused call has changed
  *              nothing, obstacles included.
  *              Cost: still one kernel launch and one stream synchronisation however many scenes are named; the replaced scenes' trees are
- *              built on the host into the page-locked block and copied to their place by that launch. */
+ *              built on the host into the page-locked block and copied to their place by that launch.  It is the launch of
+ *              sca_restart_scenes and sca_restart_scenes_sized too: one kernel, of which a scene filled to its capacity and a scene that
+ *              keeps its set are the degenerate cases (an empty range to vacate; a return behind the agent rows). */
 int sca_set_scene_obstacle_slots(sca_ctx *ctx, int nscenes, const int32_t *cap_offsets /*nscenes+1*/,
                                  const int32_t *counts /*nscenes, nullable: every slot empty*/,
                                  const double *pos /*sum(counts)*3*/, const double *radius /*sum(counts)*/);

@@ -301,7 +301,7 @@ struct sca_ctx {
         SceneView v{};                  // device arrays; live | prev | steps are one allocation (counters)
         int32_t *counters = nullptr;    // [nscenes * (SCENE_LINE + 2)]
         std::vector<int32_t> h_off;     // [nscenes + 1] the offsets as set
-        int32_t *size = nullptr;        // device [nscenes]: the agents a scene holds in the first rows of its range (k_kd_scene_jobs, k_scene_restart_sized)
+        int32_t *size = nullptr;        // device [nscenes]: the agents a scene holds in the first rows of its range (k_kd_scene_jobs, k_scene_restart)
         std::vector<int32_t> h_size;    // ... and the host's copy; the range's length until sca_restart_scenes_sized says otherwise
         bool partial = false;           // scenes_any_partial(h_size): a whole-context state from outside is refused meanwhile
         int largest = 0;                // agents of the largest scene: picks the k_kd_block instance
@@ -1600,15 +1600,14 @@ int sca_get_scene_state(sca_ctx *c, int32_t *active, int32_t *steps) {
 // the link and writes every per-agent array of the named scenes, and the call's one synchronisation follows that launch: the block may be
 // written again when the call returns.  Nothing context-wide is reset -- see DESIGN.md section 5 for trk.parity, trk_passes, kd_single_hint
 // and state_fresh.
-// sizes (sca_restart_scenes_sized): the rows each named scene brings, NULL: its capacity.  A call that leaves every scene of the context
-// full -- every call of a context that never uses sizes -- launches k_scene_restart, as before; as soon as a named scene is or becomes
-// partial it is k_scene_restart_sized, which also vacates the rows behind the episode and writes the device's size[s].  Either way one
-// launch and one synchronisation.
+// sizes (sca_restart_scenes_sized): the rows each named scene brings, NULL: its capacity.  The kernel also vacates the rows behind the
+// episode and writes the device's size[s]: for a scene that fills its capacity an empty range and the value it holds.
 // obs_counts (sca_restart_scenes_obstacles): per named scene -1, the slot keeps its obstacle set, or 0 .. its obstacle capacity, the set is
 // replaced by the next rows of obs_pos / obs_radius (restart_obstacles_check).  The named scenes' trees are built here, by the routine that
-// built the forest (scene_obstacle_build), straight into the block's obstacle sections, and the one launch is k_scene_restart_obs, which
-// copies them to the scene's place and rewrites its root.  With no set replaced -- NULL, or -1 throughout -- nothing of this is staged and
-// the launch is the kernel it was.
+// built the forest (scene_obstacle_build), straight into the block's obstacle sections, and the kernel copies them to the scene's place
+// and rewrites its root.  Every named scene gets its head words on every call: count -1 -- NULL, or the entry says so -- and the kernel
+// returns behind the scene's agent rows.  So the three entry points are one launch of one kernel, and the two narrower ones its
+// degenerate cases.
 static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const int32_t *sizes, const double *pos, const float *vel, const double *heading,
                           const double *radius, const double *pref_speed, const double *goal, const uint8_t *policy, const uint8_t *zaxis,
                           const double *max_run_dist, const double *goal_heading,
@@ -1667,12 +1666,11 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
     uint8_t *pol = b + L.off[RS_POLICY], *mode = b + L.off[RS_VPREF_MODE];
     const int32_t *off = c->scenes.h_off.data();
     scene_restart_starts(count, off, scene_ids, sizes, start);
-    bool policy_changed = false, size_changed = false, sized = c->scenes.partial;
+    bool policy_changed = false, size_changed = false;
     for (int e = 0; e < count; e++) {
         const int lo = off[scene_ids[e]], ns = scene_restart_rows(off, scene_ids, sizes, e);
         ids[e] = scene_ids[e]; new_size[e] = ns;
         size_changed = size_changed || ns != c->scenes.h_size[scene_ids[e]];
-        sized = sized || ns != off[scene_ids[e] + 1] - lo;
         for (int a = lo, r = start[e]; a < lo + ns; a++, r++) {
             const uint8_t p = policy ? policy[r] : c->h_policy[a];
             policy_changed = policy_changed || p != c->h_policy[a];
@@ -1692,7 +1690,7 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
     put(RS_MAX_RUN_DIST, max_run_dist, sizeof(double) * (size_t)T, RESTART_HAS_MAX_RUN_DIST);
     put(RS_ZAXIS, zaxis, (size_t)T, RESTART_HAS_ZAXIS);
     double obs_max_r = 0;
-    if (ko.replaced > 0) {                                             // the replaced scenes' trees, built where the kernel reads them
+    {                                                                  // every named scene's head words, and the replaced scenes' trees, built where the kernel reads them
         int32_t *head = (int32_t *)(b + OL.off[RO_HEAD]);
         ObsRec *rec = (ObsRec *)(b + OL.off[RO_REC]), *sorted = (ObsRec *)(b + OL.off[RO_SORTED]);
         int32_t *perm = (int32_t *)(b + OL.off[RO_PERM]);
@@ -1700,7 +1698,8 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
         KdWide *wide = (KdWide *)(b + OL.off[RO_WIDE]);
         int at = 0;                                                    // at most max_obstacles in all: the named scenes' capacities are disjoint ranges
         for (int e = 0; e < count; e++) {
-            const int ms = obs_counts[e], base = c->scenes.h_obs_off[scene_ids[e]];
+            const int ms = obs_counts ? obs_counts[e] : -1;            // -1: the scene keeps its set, and the words behind the count are not read
+            const int base = ms >= 0 ? c->scenes.h_obs_off[scene_ids[e]] : 0;
             head[RO_HEAD_WORDS * e] = ms; head[RO_HEAD_WORDS * e + 1] = base; head[RO_HEAD_WORDS * e + 2] = at; head[RO_HEAD_WORDS * e + 3] = ms > 0 ? 2 * base : -1;
             if (ms <= 0) continue;
             scene_obstacle_build(base, ms, obs_pos + 3 * (size_t)at, obs_radius + at, rec + at, sorted + at, perm + at, tree + 2 * (size_t)at, wide + 2 * (size_t)at);
@@ -1720,14 +1719,13 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
         d.trk_nbr0 = c->trk.nbr0; d.trk_goal_heading = c->trk_goal_heading;
         d.trk_st = (restart_u32 *)c->trk.st; d.trk_init = (const restart_u32 *)c->trk_init; d.trk_words = (int)(sizeof(sca_dubins::AgentTrack) / 4);
     }
-    // k_scene_restart_obs writes the named scenes' parts of the forest on c->stream, behind every reader of it: a step's K1 and K4 run on
+    // The kernel writes the named scenes' parts of the forest on c->stream, behind every reader of it: a step's K1 and K4 run on
     // c->stream or, where the tracker overlaps, K1 on trk_stream -- and the step joins trk_stream back into c->stream before it ends, so
-    // whatever was enqueued by an earlier call stands in front of this launch in stream order.
-    if (ko.replaced > 0) {
-        const RestartObsDev o{c->d.obs, c->d.obs_sorted, c->d.operm, c->d.otree, c->d.owide, (int32_t *)c->scenes.ov.oroot, (int32_t *)c->scenes.ov.oroot + c->scenes.v.nscenes};
-        hipLaunchKernelGGL(k_scene_restart_obs, dim3(count), dim3(RESTART_T), 0, c->stream, d, (const uint8_t *)b, L, has, (const int32_t *)new_size, c->scenes.size, o, OL);
-    } else if (sized) hipLaunchKernelGGL(k_scene_restart_sized, dim3(count), dim3(RESTART_T), 0, c->stream, d, (const uint8_t *)b, L, has, (const int32_t *)new_size, c->scenes.size);
-    else hipLaunchKernelGGL(k_scene_restart, dim3(count), dim3(RESTART_T), 0, c->stream, d, (const uint8_t *)b, L, has);
+    // whatever was enqueued by an earlier call stands in front of this launch in stream order.  Without a set per scene the forest's
+    // pointers are null: restart_obstacles_check has refused every count >= 0, so the kernel returns before it reads them.
+    RestartObsDev o{};
+    if (c->scenes.obs_on) o = RestartObsDev{c->d.obs, c->d.obs_sorted, c->d.operm, c->d.otree, c->d.owide, (int32_t *)c->scenes.ov.oroot, (int32_t *)c->scenes.ov.oroot + c->scenes.v.nscenes};
+    hipLaunchKernelGGL(k_scene_restart, dim3(count), dim3(RESTART_T), 0, c->stream, d, (const uint8_t *)b, L, has, (const int32_t *)new_size, c->scenes.size, o, OL);
     CHK(c, hipGetLastError());
     std::vector<int32_t> lp_new;                                       // K3's list: the ORCA3D-LP agents, ascending ids (the block holds the named scenes' policies)
     std::vector<int32_t> size_now = c->scenes.h_size;                  // ... of the rows that are occupied: a vacant row keeps its policy and is in no list

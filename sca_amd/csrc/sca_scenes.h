@@ -330,7 +330,8 @@ inline RestartObsCheck restart_obstacles_check(bool slots_on, const int32_t *cap
 inline int restart_obstacles_error_code(RestartObsFault f) { return f == RESTART_OBS_OK ? SCA_OK : f == RESTART_OBS_NO_SLOTS ? SCA_ERR_STATE : SCA_ERR_ARG; }
 
 // The obstacle sections of the restart's page-locked block, behind the agent sections and the new sizes: per named scene four words
-// (count or -1, the scene's obstacle base, where its rows start in the packed sections, its new root), then the packed ObsRec rows, the
+// (count or -1, the scene's obstacle base, where its rows start in the packed sections, its new root; behind a count of -1 -- the scene
+// keeps its set, and the context may have no set per scene -- the base is 0 and the kernel reads none of the three), then the packed ObsRec rows, the
 // sorted rows, the permutation with global ids, and the KdNode / KdWide records -- two per obstacle row, a tree over k rows at records
 // [2 * start, 2 * start + 2k - 1).  Every section starts on a 64-byte boundary and every record is a multiple of 16 bytes, so a record is
 // read as whole 16-byte pieces; the sizes depend on sca_create's max_agents (at most that many scenes) and max_obstacles alone.

@@ -17,8 +17,10 @@
 // SceneObsRoots, whose obstacle walks start at the scene's own obstacle root, or do not happen for a scene without obstacles.  Those roots
 // travel in SceneObsView, a member of SceneObsRoots only: a context with a shared set runs the SceneRoots instances, the code it ran before.
 // Obstacle slots (sca_set_scene_obstacle_slots): a scene's obstacle range is a capacity, and since the walks start at a root word they load
-// and reach obstacles only through the tree's links, a restart that brings obstacles (k_scene_restart_obs) installs a new tree into the
-// scene's part of the forest and rewrites that word -- the three kernels above do not change.
+// and reach obstacles only through the tree's links, a restart that brings obstacles (k_scene_restart) installs a new tree into the
+// scene's part of the forest and rewrites that word -- the three kernels above do not change.  k_scene_restart is the ONE restart kernel,
+// behind sca_restart_scenes, _sized and _obstacles alike: a scene filled to its capacity vacates an empty range, a scene that keeps its
+// obstacle set returns behind its agent rows, so the narrower calls are degenerate cases of the widest and need no kernels of their own.
 #pragma once
 #include "sca_kdbuild.hip.h"
 #include "sca_scenes.h"
@@ -160,14 +162,6 @@ __device__ __forceinline__ void scene_restart_fill(const RestartDev &d, const ui
     if (d.trk_st)                                                      // the AgentTrack records, word by word from the one initial record
         for (int64_t w = t; w < (int64_t)ns * d.trk_words; w += RESTART_T) d.trk_st[(int64_t)lo * d.trk_words + w] = d.trk_init[w % d.trk_words];
 }
-__global__ __launch_bounds__(RESTART_T) void k_scene_restart(RestartDev d, const uint8_t *blk, RestartLayout L, uint32_t has) {
-    const int b = (int)blockIdx.x, t = (int)threadIdx.x;
-    const int s = ((const int32_t *)(blk + L.off[RS_IDS]))[b];
-    const int row0 = ((const int32_t *)(blk + L.off[RS_START]))[b];
-    const int lo = d.offsets[s], ns = d.offsets[s + 1] - lo;
-    scene_restart_fill(d, blk, L, has, row0, lo, ns, t);
-    if (t == 0) { d.live[s * SCENE_LINE] = ns; d.prev[s] = ns; d.steps[s] = 0; }
-}
 
 // Slots of a capacity (sca_restart_scenes_sized): the named scene takes new_size[b] agents into its first rows, and the rows behind them,
 // up to the capacity offsets[s + 1], are VACATED.  A vacant row is an agent that is settled for good, by the rule collide_finish_body
@@ -195,24 +189,17 @@ __device__ __forceinline__ void scene_restart_vacate(const RestartDev &d, int lo
     if (d.trk_st)
         for (int64_t w = (int64_t)lo * d.trk_words + t; w < (int64_t)hi * d.trk_words; w += RESTART_T) d.trk_st[w] = d.trk_init[w % d.trk_words];
 }
-// new_size: [count] in the order of the block's ids (host memory, read across the link like the block); size: [nscenes] the device's sizes,
-// which k_kd_scene_jobs reads.  The host has checked 1 <= new_size[b] <= capacity (scene_restart_check).
-__global__ __launch_bounds__(RESTART_T) void k_scene_restart_sized(RestartDev d, const uint8_t *blk, RestartLayout L, uint32_t has, const int32_t *new_size, int32_t *size) {
-    const int b = (int)blockIdx.x, t = (int)threadIdx.x;
-    const int s = ((const int32_t *)(blk + L.off[RS_IDS]))[b];
-    const int row0 = ((const int32_t *)(blk + L.off[RS_START]))[b];
-    const int lo = d.offsets[s], hi = d.offsets[s + 1], ns = new_size[b];
-    scene_restart_fill(d, blk, L, has, row0, lo, ns, t);
-    scene_restart_vacate(d, lo + ns, hi, t);
-    if (t == 0) { d.live[s * SCENE_LINE] = ns; d.prev[s] = ns; d.steps[s] = 0; size[s] = ns; }
-}
-
-// A restart that brings obstacles (sca_restart_scenes_obstacles): the launch used whenever a named scene replaces its obstacle set -- the
-// agent rows by the functions above (a full slot vacates an empty range and writes the size it has), then, for a scene whose head words
+// The one restart kernel, behind all three entry points.  new_size: [count] the rows each named scene brings, in the order of the block's
+// ids (host memory, read across the link like the block); size: [nscenes] the device's sizes, which k_kd_scene_jobs reads.  The host has
+// checked 1 <= new_size[b] <= capacity (scene_restart_check).  The agent rows by the functions above, then, for a scene whose head words
 // say so, its part of the obstacle forest from the block's obstacle sections (RestartObsLayout, sca_scenes.h): records, sorted records,
-// permutation, both node arrays, and last the root word the scene's walks start at and the count.  Every word written lies in the named
-// scene's rows [base, base + k) or node records [2 base, 2 base + 2k - 1), inside its capacity (the host checked k against it); rows and
-// records behind them keep what an earlier set left -- no link of the new tree leads there, and the root is the only way in.  No atomics.
+// permutation, both node arrays, and last the root word the scene's walks start at and the count.  One kernel suffices because the two
+// narrower calls are its degenerate cases, bit for bit: a scene that fills its capacity (sca_restart_scenes) vacates an empty range and
+// writes the size it has, and a scene that keeps its set (head count -1: every scene of a call without obs_counts) returns behind the agent
+// rows, before anything of RestartObsDev is read -- whose pointers are null in a context without a set per scene.
+// Every obstacle word written lies in the named scene's rows [base, base + k) or node records [2 base, 2 base + 2k - 1), inside its
+// capacity (the host checked k against it); rows and records behind them keep what an earlier set left -- no link of the new tree leads
+// there, and the root is the only way in.  No atomics.
 // The 32-, 64- and 128-byte records travel as 16-byte pieces, consecutive lanes on consecutive pieces: a wavefront's load covers 1 KB of
 // consecutive bytes of the block across the link, and its store the same in device memory.
 typedef uint32_t __attribute__((ext_vector_type(4), may_alias)) restart_piece;
@@ -229,8 +216,8 @@ __device__ __forceinline__ void scene_restart_pieces(void *dst, const void *src,
     const restart_piece *from = (const restart_piece *)src;
     for (int64_t w = t; w < pieces; w += RESTART_T) to[w] = from[w];
 }
-__global__ __launch_bounds__(RESTART_T) void k_scene_restart_obs(RestartDev d, const uint8_t *blk, RestartLayout L, uint32_t has, const int32_t *new_size, int32_t *size,
-                                                                 RestartObsDev o, RestartObsLayout OL) {
+__global__ __launch_bounds__(RESTART_T) void k_scene_restart(RestartDev d, const uint8_t *blk, RestartLayout L, uint32_t has, const int32_t *new_size, int32_t *size,
+                                                             RestartObsDev o, RestartObsLayout OL) {
     const int b = (int)blockIdx.x, t = (int)threadIdx.x;
     const int s = ((const int32_t *)(blk + L.off[RS_IDS]))[b];
     const int row0 = ((const int32_t *)(blk + L.off[RS_START]))[b];

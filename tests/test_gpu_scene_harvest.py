@@ -13,8 +13,7 @@ import math
 import numpy as np
 import pytest
 
-from scene_sizes_util import context, partial_batch, sized_restart
-from scene_util import Slots, everything
+from scene_util import Slots, assert_summary, context, everything, loop_summary, partial_batch, rc_of, restart_all
 
 pytestmark = pytest.mark.gpu
 
@@ -29,12 +28,6 @@ SENTINEL = dict(pos=-7.25, vel=-3.5, heading=-9.125, flags=0xAB, total_dist=-11.
 def S():
     import sca_amd.solver as S
     return S
-
-
-def _rc(S, fn):
-    with pytest.raises(S.ScaError) as e:
-        fn()
-    return int(str(e.value).rsplit('rc=', 1)[1].rstrip(')'))
 
 
 def lattice_scene(S, n, reach, pos=None, max_run_dist=None):
@@ -75,25 +68,6 @@ def assert_rows(got, st, lo, hi, ctx):
 def assert_sentinel(hv, lo, hi, ctx):
     for k, v in SENTINEL.items():
         assert (hv[k][lo:hi] == np.array(v).astype(hv[k].dtype)).all(), ctx + ('rows nobody may write', k)
-
-
-def loop_summary(st, lo, hi):
-    """metrics.episode_metrics' loop over sca_get_state: Python ints and floats, agent order"""
-    f = st['flags'][lo:hi]
-    num, dist, steps = 0, 0.0, 0
-    for i in range(lo, hi):
-        if not (int(st['flags'][i]) & 6):
-            num += 1
-            dist += float(st['total_dist'][i])
-            steps += int(st['step_num'][i])
-    return dict(arrived=int(((f & 1) != 0).sum()), collided=int(((f & 2) != 0).sum()), timed_out=int(((f & 4) != 0).sum()), successful_num=num,
-                all_step_num=steps, all_distance=dist)
-
-
-def assert_summary(rec, want, steps, batch_step, ctx):
-    for k, v in want.items():
-        assert rec[k].item() == v, ctx + (k, rec[k].item(), v)
-    assert (int(rec['steps']), int(rec['batch_step'])) == (steps, batch_step), ctx + ('steps / batch_step', int(rec['steps']), int(rec['batch_step']))
 
 
 def assert_counters(sol, hv, ctx):
@@ -327,14 +301,14 @@ def test_fresh_words_cleared_without_a_collect(S):
     sol.run_steps(3, S.NBR_KDTREE)
     sol.synchronize()
     assert hv['summary']['fresh'].tolist() == [1, 1, 0]
-    sized_restart(sol, [1], [eps[1]], sizes=None, tracker=False)
+    restart_all(sol, [1], [eps[1]], tracker=False)
     assert hv['summary']['fresh'].tolist() == [1, 0, 0]             # an uncollected harvest of a restarted scene is gone
     assert sol.scene_harvest_collect() == [0]
     sol.run_steps(3, S.NBR_KDTREE)                                  # batch steps 4 .. 6: the restarted scene ends in 6, after its own 3; so does scene 2
     assert sol.scene_harvest_collect() == [1, 2]
     assert hv['summary']['steps'].tolist() == [3, 3, 6] and hv['summary']['batch_step'].tolist() == [3, 6, 6]
     # sca_set_state: all of them
-    sized_restart(sol, [0, 1], [eps[0], eps[1]], sizes=None, tracker=False)
+    restart_all(sol, [0, 1], [eps[0], eps[1]], tracker=False)
     sol.run_steps(3, S.NBR_KDTREE)
     sol.synchronize()
     assert hv['summary']['fresh'].tolist() == [1, 1, 0]
@@ -344,7 +318,7 @@ def test_fresh_words_cleared_without_a_collect(S):
     sol.env_step(S.NBR_KDTREE)                                      # scenes that came in finished never finish
     assert sol.scene_harvest_collect() == [] and not hv['active'].any()
     # sca_step_host with SCA_HOST_IN_STATE: all of them, before the step's own harvest
-    sized_restart(sol, [0, 2], [eps[0], eps[2]], sizes=None, tracker=False)
+    restart_all(sol, [0, 2], [eps[0], eps[2]], tracker=False)
     sol.run_steps(3, S.NBR_KDTREE)
     sol.synchronize()
     assert hv['summary']['fresh'].tolist() == [1, 0, 0]
@@ -379,7 +353,7 @@ def test_refusals_and_lifetime(S):
     # not enabled
     assert L.sca_scene_harvest_get(ctx, C.byref(h), C.sizeof(h)) == ERR_STATE
     assert L.sca_scene_harvest_collect(ctx, i32(ids), C.byref(count)) == ERR_STATE
-    assert _rc(S, sol.scene_harvest) == ERR_STATE and _rc(S, sol.scene_harvest_collect) == ERR_STATE
+    assert rc_of(S, sol.scene_harvest) == ERR_STATE and rc_of(S, sol.scene_harvest_collect) == ERR_STATE
     assert L.sca_scene_harvest_enable(ctx, 0) == 0                  # off while off: nothing to free
     # between a policy pass and its env update
     sol.policy_pass(S.NBR_KDTREE)
@@ -410,7 +384,7 @@ def test_refusals_and_lifetime(S):
     assert hv['steps'].tolist() == [2, 2] and hv['summary']['batch_step'].tolist() == [0, 0]
     # disable, step without, enable again: batch_step counts from the second enable
     sol.scene_harvest_enable(False)
-    assert _rc(S, sol.scene_harvest_collect) == ERR_STATE
+    assert rc_of(S, sol.scene_harvest_collect) == ERR_STATE
     sol.env_step(S.NBR_KDTREE)                                      # scene 0 (0.7 m: 3 steps) finishes unobserved
     hv = enable(sol)
     assert hv['active'].tolist() == [0, 1] and hv['steps'].tolist() == [3, 3] and sol.scene_harvest_collect() == []      # (scene 1: the two agents 0.7 m from their goals arrived too)

@@ -10,7 +10,7 @@ import json
 import numpy as np
 import pytest
 
-from scene_util import everything, load_any
+from scene_util import agents_of, everything, load_any, restart_all
 
 pytestmark = pytest.mark.gpu
 
@@ -66,7 +66,9 @@ def offsets(scenes):
 
 
 def context(S, scenes, as_scenes):
-    """the scenes side by side in one context (as_scenes) or, for a list of one, the plain context that holds the episode alone"""
+    """the scenes side by side in one context (as_scenes) or, for a list of one, the plain context that holds the episode alone.  Not
+    scene_util.context: this one sets an empty shared obstacle set, makes scenes only where asked, enables the tracker only where a tracked
+    policy is present, passes total_dist and step_num with the state, sets the permutation, and returns the solver alone."""
     n = int(sum(s['n'] for s in scenes))
     sol = S.BatchedSolver(max_agents=n, max_obstacles=1)
     sol.set_obstacles(np.zeros((0, 3)), np.zeros(0))
@@ -211,15 +213,6 @@ def test_the_references_own_log(tmp_path):
     batch.close()
 
 
-def restart(sol, plan, tracker=True):
-    """{slot: scene}: one sca_restart_scenes call with every array passed"""
-    ids = sorted(plan)
-    eps = [plan[s] for s in ids]
-    sol.restart_scenes(ids, cat(eps, 'pos'), cat(eps, 'heading'), vel=cat(eps, 'vel'), radius=cat(eps, 'radius'), pref_speed=cat(eps, 'pref_speed'),
-                       goal=cat(eps, 'goal'), policy=cat(eps, 'policy'), zaxis=cat(eps, 'zaxis'), max_run_dist=cat(eps, 'max_run_dist'),
-                       goal_heading=cat(eps, 'goal_heading') if tracker else None)
-
-
 def test_restart_starts_the_log_over(S):
     """Three slots.  Slot 1 is replaced in flight at batch step 10, slot 0 -- which finished by itself before -- is refilled at step 12; after
     15 more steps slot 1's and slot 0's logs are the new episodes' logs alone from row 0, slot 2's is its uninterrupted one."""
@@ -235,14 +228,14 @@ def test_restart_starts_the_log_over(S):
     assert sol.scene_history_rows()['logged'].tolist() == [done0, 10, 10]
     before0 = sol.scene_history(0)
     assert_log_equals(before0, solo(S, first[0], done0), ('slot 0 before the refill',))
-    restart(sol, {1: new1})
+    restart_all(sol, [1], [new1])
     assert sol.scene_history_rows()['logged'].tolist() == [done0, 0, 10]                            # the log starts over
     with pytest.raises(S.ScaError):
         sol.scene_history(1, first_row=0, nrows=1)                                                  # stale rows are beyond rows_logged
     assert_log_equals(sol.scene_history(0), before0, ('slot 0 behind the restart of slot 1',))
     for t in range(2):
         run_steps_1(S, sol)
-    restart(sol, {0: new0})
+    restart_all(sol, [0], [new0])
     for t in range(13):
         run_steps_1(S, sol)
     st, rows = sol.scene_state(), sol.scene_history_rows()
@@ -461,13 +454,9 @@ def test_run_episodes_hands_the_trajectories_over():
     circ = scenarios.circle(12, rad=5.0, z=12.0)
     wide = scenarios.circle(12, rad=12.0, z=12.0)                    # 24 m to fly at 0.1 m per step: more than K steps
 
-    def agents(sc, policy):
-        return [E.Agent(start_pos=list(sc['start'][i]), goal_pos=list(sc['goal'][i]), vel=[0.0, 0.0, 0.0], radius=0.5, pref_speed=1.0, policy=policy, id=i)
-                for i in range(12)]
-
     def queue():
-        return [agents(circ, E.SCAPolicy), agents(circ, E.RVO3DPolicy), agents(wide, E.ORCA3DPolicy), agents(circ, E.ORCA3DPolicy),
-                agents(circ, E.RVO3dDubinsPolicy), agents(circ, E.SRVO3DPolicy)]
+        return [agents_of(circ, E.SCAPolicy), agents_of(circ, E.RVO3DPolicy), agents_of(wide, E.ORCA3DPolicy), agents_of(circ, E.ORCA3DPolicy),
+                agents_of(circ, E.RVO3dDubinsPolicy), agents_of(circ, E.SRVO3DPolicy)]
 
     got = scenes.run_episodes(queue(), 2, device_tracker=True, history_rows=K, max_steps=5000)
     assert all(r is not None for r in got) and [r['episode'] for r in got] == list(range(6))          # the queue completes

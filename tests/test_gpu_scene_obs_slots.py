@@ -9,10 +9,8 @@ import json
 import numpy as np
 import pytest
 
-from scene_sizes_util import (NO_OBSTACLES, SizedSlots, assert_slots_equal_alone, circle_scene, context, padded, recorded_arrays, sized_restart,
-                              tracked)
-from scene_util import assert_scene_equals_alone, everything, load_any
-from test_gpu_scene_harvest import assert_summary, loop_summary
+from scene_util import (NO_OBSTACLES, SizedSlots, agents_of, assert_scene_equals_alone, assert_slots_equal_alone, assert_summary, circle_scene, context,
+                        everything, load_any, loop_summary, padded, recorded_arrays, restart_all, same, step_all, tracked)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,38 +25,8 @@ def S():
     return S
 
 
-def _step(S, *sols, k=1):
-    for x in sols:
-        x.run_steps(k, S.NBR_KDTREE)
-        x.synchronize()
-
-
-def _same(a, b, ctx, keys=None):
-    for key in (keys or a):
-        if key == 'track':
-            for i in a[key]:
-                assert np.array_equal(a[key][i], b[key][i], equal_nan=True), ctx + (key, i)
-        else:
-            assert np.array_equal(a[key], b[key], equal_nan=True), ctx + (key,)
-
-
 def own_set(ep):
     return ep['obs_pos'], ep['obs_radius']
-
-
-def slot_context(S, eps, obs_caps, sets=None, tracker=True, max_obstacles=None):
-    """scene_sizes_util.context with obstacle SLOTS: scene s full with eps[s], obs_caps[s] obstacle rows holding sets[s] (None: empty)"""
-    off = np.concatenate([[0], np.cumsum([e['n'] for e in eps])]).astype(np.int32)
-    n = int(off[-1])
-    cat = lambda key: np.concatenate([e[key] for e in eps])
-    sol = S.BatchedSolver(max_agents=n, max_obstacles=max(int(sum(obs_caps)), 1) if max_obstacles is None else max_obstacles)
-    sol.set_agents(cat('radius'), cat('pref_speed'), cat('goal'), cat('policy'), cat('zaxis'), cat('max_run_dist'))
-    sol.set_scenes(off)
-    sol.set_scene_obstacle_slots(obs_caps, sets)
-    if tracker:
-        sol.device_tracker_enable(cat('goal_heading'), in_pass=True)
-    sol.set_state(cat('pos'), cat('vel'), cat('heading'), np.zeros(n, np.uint8))
-    return sol, off
 
 
 def alone(S, ep, obstacles=NO_OBSTACLES, tracker=True, history=0):
@@ -104,11 +72,6 @@ def assert_beside(sol, off, held, beside, ctx, obs_lo):
     return got
 
 
-def obs_restart(sol, ids, eps, sets, **kw):
-    """one sca_restart_scenes_obstacles call: scene ids[b] takes episode eps[b] and the obstacle set sets[b] (None: it keeps its own)"""
-    sized_restart(sol, ids, eps, obstacles=list(sets), **kw)
-
-
 def spheres(seed, m, radius=0.3, spread=2.0, z=10.0):
     """m seeded spheres around the middle of the hand-made circles (radius 3 .. 4 at z = 10): none touches a start position"""
     rng = np.random.default_rng(seed)
@@ -139,7 +102,7 @@ def batch_of_test_1(S, slots=True):
     eps = [recorded_arrays(load_any(n)) for n in BATCH]
     sets = [own_set(e) for e in eps]
     if slots:
-        sol, off = slot_context(S, eps, [len(r) for _, r in sets], sets)
+        sol, off = context(S, eps, obstacles=sets, obs_slots=[len(r) for _, r in sets])
     else:
         sol, off = context(S, eps, obstacles=sets)
     return sol, off, eps, sets
@@ -161,14 +124,14 @@ def test_slots_equal_sets(S):
     oc = a.scene_obstacle_counts()                                   # sca_set_scene_obstacles leaves slots that are full
     assert oc['counts'].tolist() == [8, 8, 4, 0] and oc['capacities'].tolist() == [8, 8, 4, 0]
     ids = all_tracked(off, eps)
-    _same(everything(a, ids), everything(b, ids), ('before the first step',))
+    same(everything(a, ids), everything(b, ids), ('before the first step',))
     saw_obstacle = False
     for t in range(600):
         left = a.env_step(S.NBR_KDTREE)
         assert b.env_step(S.NBR_KDTREE) == left
         some = ids if t % 25 == 0 or left == 0 else ()               # (a tracker record is a read-back per agent: every 25th step and at the end)
         ea, eb = everything(a, some), everything(b, some)
-        _same(ea, eb, ('slots against sets', 'step', t))
+        same(ea, eb, ('slots against sets', 'step', t))
         assert a.pass_forms() == b.pass_forms() and a.pass_forms() & S.FORM_SCENE_OBSTACLES
         saw_obstacle = saw_obstacle or bool((ea['nbr_kind'] == 1).any())
         if left == 0:
@@ -200,9 +163,10 @@ class ObsSlots(SizedSlots):
         self.fx = [load_any(x) for x in names]
         ep = [recorded_arrays(f) for f in self.fx]
         self.tracker = True
-        self.sol, self.off = slot_context(S, [padded(e, c) for e, c in zip(ep, agent_caps)], obs_caps, [own_set(e) for e in ep], max_obstacles=max_obstacles)
+        self.sol, self.off = context(S, [padded(e, c) for e, c in zip(ep, agent_caps)], obstacles=[own_set(e) for e in ep], obs_slots=obs_caps,
+                                     max_obstacles=max_obstacles)
         self.obs_off = np.concatenate([[0], np.cumsum(obs_caps)]).astype(np.int32)
-        sized_restart(self.sol, list(range(self.B)), ep)             # vacates the rows behind the episodes; no obstacle argument: the sets stay
+        restart_all(self.sol, list(range(self.B)), ep, sizes='own')  # vacates the rows behind the episodes; no obstacle argument: the sets stay
         self.size = np.array([e['n'] for e in ep])
         self.held = ep
         self.n = int(self.off[-1])
@@ -215,7 +179,7 @@ class ObsSlots(SizedSlots):
         ids = sorted(plan)
         fx = {s: load_any(plan[s]) for s in ids}
         ep = [recorded_arrays(fx[s]) for s in ids]
-        obs_restart(self.sol, ids, ep, [own_set(e) for e in ep])
+        restart_all(self.sol, ids, ep, sizes='own', obstacles=[own_set(e) for e in ep])
         for s, e in zip(ids, ep):
             self.fx[s], self.names[s], self.t0[s], self.steps_want[s], self.size[s], self.held[s] = fx[s], plan[s], self.t, 0, e['n'], e
         self._bind()
@@ -306,13 +270,13 @@ def test_count_edges_against_a_context_alone(S):
     sca_set_obstacles of that set."""
     other, other_set = circle_scene(S, 6, MIX, rad=4.0), spheres(5, 5)
     first = circle_scene(S, 4, MIX[:4], rad=3.0)
-    sol, off = slot_context(S, [other, first], [5, 23], [other_set, None])
+    sol, off = context(S, [other, first], obstacles=[other_set, None], obs_slots=[5, 23])
     beside = Lockstep(S, alone(S, other, other_set))
     saw = set()
     for k, m in enumerate((0, 1, 10, 11, 21, 23, 1)):
         ep = circle_scene(S, 4, np.roll(MIX, k)[:4], rad=3.0, turn=k)
         new = spheres(100 + k, m)
-        obs_restart(sol, [1], [ep], [new])
+        restart_all(sol, [1], [ep], sizes='own', obstacles=[new])
         oc = sol.scene_obstacle_counts()
         assert oc['counts'].tolist() == [5, m] and oc['capacities'].tolist() == [5, 23]
         solo = Lockstep(S, alone(S, ep, new))
@@ -348,13 +312,13 @@ def test_through_the_ghost(S, order):
     middle, far = _ghost_sets()
     ep = circle_scene(S, 4, [3, 1, 2, 4], rad=3.0)
     free = alone(S, ep)
-    _step(S, free, k=40)
+    step_all(S, free, k=40)
     want_free = everything(free)
     sets = [middle, far] if order == 'sphere first' else [far, middle]
-    sol, off = slot_context(S, [ep], [12], [sets[0]])
+    sol, off = context(S, [ep], obstacles=[sets[0]], obs_slots=[12])
     for k, now in enumerate(sets):
         if k:
-            obs_restart(sol, [0], [ep], [now])
+            restart_all(sol, [0], [ep], sizes='own', obstacles=[now])
             assert sol.scene_obstacle_counts()['counts'].tolist() == [len(now[1])]
         solo = Lockstep(S, alone(S, ep, now))
         saw_obstacle = False
@@ -368,7 +332,7 @@ def test_through_the_ghost(S, order):
         else:
             assert not saw_obstacle
             assert solo.steps == 40                                  # (nobody within 6 m of a goal 40 steps in: both ran all of them)
-            _same(got, want_free, (order, 'against the obstacle-free context'), keys=[k_ for k_ in want_free if k_ != 'track'])
+            same(got, want_free, (order, 'against the obstacle-free context'), keys=[k_ for k_ in want_free if k_ != 'track'])
         solo.sol.close()
     sol.close(); free.close()
 
@@ -380,9 +344,9 @@ def test_keep(S):
     batches = [batch_of_test_1(S) for _ in range(3)]
     off, eps = batches[0][1], batches[0][2]
     for sol, *_ in batches:
-        _step(S, sol, k=5)
-    sized_restart(batches[0][0], [1, 3], [new, eps[3]])
-    obs_restart(batches[1][0], [1, 3], [new, eps[3]], [None, None])
+        step_all(S, sol, k=5)
+    restart_all(batches[0][0], [1, 3], [new, eps[3]], sizes='own')
+    restart_all(batches[1][0], [1, 3], [new, eps[3]], sizes='own', obstacles=[None, None])
     both = {k: np.concatenate([new[k], eps[3][k]]) for k in new if k not in ('n', 'obs_pos', 'obs_radius')}
     rc, msg = raw_restart(batches[2][0], [1, 3], both, sizes=[16, 8], obs_counts=None)
     assert rc == 0, msg
@@ -390,10 +354,10 @@ def test_keep(S):
     for t in range(11):
         want = everything(batches[0][0], ids)
         for k, (sol, *_) in enumerate(batches[1:]):
-            _same(want, everything(sol, ids), ('keep', ('-1', 'NULL')[k], 'step', t))
+            same(want, everything(sol, ids), ('keep', ('-1', 'NULL')[k], 'step', t))
             assert sol.scene_obstacle_counts()['counts'].tolist() == [8, 8, 4, 0]
         for sol, *_ in batches:
-            _step(S, sol)
+            step_all(S, sol)
     for sol, *_ in batches:
         sol.close()
 
@@ -407,7 +371,7 @@ def test_no_other_scene_can_tell(S):
     ids = [int(off[s]) + i for s in (0, 2, 3) for i in tracked(eps[s])]
     for t in range(20):
         if t == 7:
-            obs_restart(a, [1], [new], [new_set])
+            restart_all(a, [1], [new], sizes='own', obstacles=[new_set])
             assert a.scene_obstacle_counts()['counts'].tolist() == [8, 6, 4, 0] and b.scene_obstacle_counts()['counts'].tolist() == [8, 8, 4, 0]
         ea, eb = everything(a, ids), everything(b, ids)
         for s in (0, 2, 3):
@@ -420,7 +384,7 @@ def test_no_other_scene_can_tell(S):
                     assert np.array_equal(ea[key][sl], eb[key][sl], equal_nan=True), ('scene', s, 'step', t, key)
         if t >= 7:
             assert not np.array_equal(ea['pos'][16:32], eb['pos'][16:32])
-        _step(S, a, b)
+        step_all(S, a, b)
     a.close(); b.close()
 
 
@@ -431,11 +395,11 @@ def test_the_filter_stays_a_filter(S):
     big_ep, small_ep = circle_scene(S, 6, MIX, rad=9.0), circle_scene(S, 8, np.resize(MIX, 8), rad=3.0)
     big = (np.array([[0.0, 0.0, 10.0], [0.0, 0.0, 17.0]]), np.full(2, 3.0))
     small = spheres(3, 9, radius=0.2, spread=2.2)
-    sol, off = slot_context(S, [big_ep, small_ep], [4, 9])
-    _step(S, sol, k=3)
-    obs_restart(sol, [0], [big_ep], [big])
-    _step(S, sol, k=2)
-    obs_restart(sol, [1], [small_ep], [small])
+    sol, off = context(S, [big_ep, small_ep], obs_slots=[4, 9])
+    step_all(S, sol, k=3)
+    restart_all(sol, [0], [big_ep], sizes='own', obstacles=[big])
+    step_all(S, sol, k=2)
+    restart_all(sol, [1], [small_ep], sizes='own', obstacles=[small])
     solo, beside = Lockstep(S, alone(S, small_ep, small)), Lockstep(S, alone(S, big_ep, big))
     beside.step(2)
     saw = False
@@ -461,10 +425,10 @@ def test_every_step_form_behind_an_obstacle_restart(S):
     results = {}
     for name, form in forms.items():
         sol, off, eps, _ = batch_of_test_1(S)
-        _step(S, sol, k=4)
+        step_all(S, sol, k=4)
         if name == 'step_host':
             h = sol.host_state()
-        obs_restart(sol, [1], [new], [new_set])
+        restart_all(sol, [1], [new], sizes='own', obstacles=[new_set])
         if name == 'step_host':
             st = sol.get_state()
             for k in ('pos', 'heading', 'flags', 'total_dist', 'step_num', 'vel'):
@@ -474,11 +438,11 @@ def test_every_step_form_behind_an_obstacle_restart(S):
         assert sol.pass_forms() & S.FORM_SCENE_OBSTACLES and sol.scene_state()['steps'].tolist() == [9, 5, 9, 9], name
         sol.close()
     solo = alone(S, new, new_set)
-    _step(S, solo, k=5)
+    step_all(S, solo, k=5)
     assert_scene_equals_alone(results['env_step'], 16, 32, 8, everything(solo), ('env_step', 'scene 1 alone'))
     solo.close()
     for name in ('run_steps', 'split', 'step_host'):
-        _same(results['env_step'], results[name], ('step form', name), keys=('pos', 'vel', 'heading', 'flags', 'total_dist', 'step_num', 'perm', 'action'))
+        same(results['env_step'], results[name], ('step form', name), keys=('pos', 'vel', 'heading', 'flags', 'total_dist', 'step_num', 'perm', 'action'))
 
 
 # ---- 9 ---------------------------------------------------------------------------------------------------------------------------------------
@@ -504,17 +468,17 @@ def test_refusals_change_nothing(S):
     from sca_amd import _lib
     eps = [circle_scene(S, 6, MIX, rad=4.0), circle_scene(S, 4, MIX[:4], rad=3.0)]
     sets = [spheres(31, 3), spheres(32, 2)]
-    sol, off = slot_context(S, eps, [5, 4], sets, max_obstacles=9)
-    twin = slot_context(S, eps, [5, 4], sets, max_obstacles=9)[0]
+    sol, off = context(S, eps, obstacles=sets, obs_slots=[5, 4], max_obstacles=9)
+    twin = context(S, eps, obstacles=sets, obs_slots=[5, 4], max_obstacles=9)[0]
     pos, rad = np.concatenate([p for p, _ in sets]), np.concatenate([r for _, r in sets])
 
     def unchanged(ctx):
-        _same(everything(twin), everything(sol), ctx)
+        same(everything(twin), everything(sol), ctx)
         ca, cb = twin.scene_obstacle_counts(), sol.scene_obstacle_counts()
         assert ca['counts'].tolist() == cb['counts'].tolist() == [3, 2] and cb['capacities'].tolist() == [5, 4], ctx
         for t in range(3):
-            _step(S, sol, twin)
-            _same(everything(twin), everything(sol), ctx + ('step', t))
+            step_all(S, sol, twin)
+            same(everything(twin), everything(sol), ctx + ('step', t))
 
     def slots(offsets, counts, nscenes=None, p=pos, r=rad):
         o = None if offsets is None else np.ascontiguousarray(offsets, np.int32)
@@ -557,12 +521,12 @@ def test_refusals_change_nothing(S):
     assert rc == ERR_STATE and 'no obstacle slots' in msg and 'obs_counts[0] = 0' in msg, (rc, msg)
     with pytest.raises(S.ScaError):
         bare.scene_obstacle_counts()
-    _same(everything(twin), everything(bare), ('no slots',))
+    same(everything(twin), everything(bare), ('no slots',))
     assert raw_restart(bare, [1], ep, sizes=[4], obs_counts=[-1])[0] == 0
-    sized_restart(twin, [1], [ep])
+    restart_all(twin, [1], [ep], sizes='own')
     for t in range(3):
-        _step(S, bare, twin)
-        _same(everything(twin), everything(bare), ('keep without slots', t))
+        step_all(S, bare, twin)
+        same(everything(twin), everything(bare), ('keep without slots', t))
     bare.set_scenes(None)
     o, c = np.array([0, 5, 9], np.int32), np.array([3, 2], np.int32)
     rc = bare.L.sca_set_scene_obstacle_slots(bare.ctx, 2, _lib.ptr(o, C.c_int32), _lib.ptr(c, C.c_int32), _lib.ptr(pos, C.c_double), _lib.ptr(rad, C.c_double))
@@ -574,9 +538,9 @@ def test_lifetime_of_the_slots(S):
     """all slots empty keeps the forest forms and walks nothing; sca_set_scene_obstacles and sca_set_obstacles replace the slots; whatever
     redefines the scenes drops them"""
     eps = [circle_scene(S, 6, MIX, rad=4.0), circle_scene(S, 4, MIX[:4], rad=3.0)]
-    sol, off = slot_context(S, eps, [5, 4])                          # every slot empty
+    sol, off = context(S, eps, obs_slots=[5, 4])                          # every slot empty
     free = [alone(S, e) for e in eps]
-    _step(S, sol, *free, k=6)
+    step_all(S, sol, *free, k=6)
     assert sol.pass_forms() & S.FORM_SCENE_OBSTACLES and not free[0].pass_forms() & S.FORM_SCENE_OBSTACLES
     assert sol.scene_obstacle_counts()['counts'].tolist() == [0, 0]
     assert_slots_equal_alone(sol, off, dict(enumerate(eps)), dict(enumerate(free)), ('empty slots',), obs_lo={0: 0, 1: 5})
@@ -599,12 +563,6 @@ def test_lifetime_of_the_slots(S):
 def _obstacles(pos, radius):
     from sca_amd import env as E
     return [E.Obstacle(pos=list(map(float, p)), shape_dict={'shape': 'sphere', 'feature': float(r)}, id=i) for i, (p, r) in enumerate(zip(pos, radius))]
-
-
-def _agents(sc, policy):
-    from sca_amd import env as E
-    return [E.Agent(start_pos=list(sc['start'][i]), goal_pos=list(sc['goal'][i]), vel=[0.0, 0.0, 0.0], radius=0.5, pref_speed=1.0, policy=policy, id=i)
-            for i in range(len(sc['start']))]
 
 
 def _queue():
@@ -641,7 +599,7 @@ def queue_alone():
     out = []
     for sc, policy, obs in _queue():
         env = E.MACAEnv(device_tracker=True)
-        env.set_agents(_agents(sc, policy), obstacles=_obstacles(*obs))
+        env.set_agents(agents_of(sc, policy), obstacles=_obstacles(*obs))
         steps = 1
         while not env.step({}) and steps < 4000:
             steps += 1
@@ -657,7 +615,7 @@ def test_run_episodes_with_episode_obstacles(queue_alone, harvest):
     specs = _queue()
     assert sorted({len(o[1]) for _, _, o in specs}) == [0, 2, 3, 4, 8]
     done, stats = [], {}
-    results = run_episodes([_agents(sc, p) for sc, p, _ in specs], 3, device_tracker=True, episode_obstacles=[_obstacles(*o) for _, _, o in specs],
+    results = run_episodes([agents_of(sc, p) for sc, p, _ in specs], 3, device_tracker=True, episode_obstacles=[_obstacles(*o) for _, _, o in specs],
                            obstacle_capacities='max', harvest=harvest, on_done=lambda r: done.append(r['episode']), stats=stats, max_steps=12000)
     assert sorted(done) == list(range(9)) and stats['batch_steps'] > 0
     for i, (r, want) in enumerate(zip(results, queue_alone)):
@@ -669,9 +627,9 @@ def test_run_episodes_with_episode_obstacles(queue_alone, harvest):
                 a, b = r['metrics'][key], want['metrics'][key]
                 assert a == b or (a != a and b != b), (i, key, a, b)
     with pytest.raises(ValueError):
-        run_episodes([_agents(sc, p) for sc, p, _ in specs], 3, _obstacles([[0, 0, 5]], [1.0]), episode_obstacles=[[] for _ in specs])
+        run_episodes([agents_of(sc, p) for sc, p, _ in specs], 3, _obstacles([[0, 0, 5]], [1.0]), episode_obstacles=[[] for _ in specs])
     with pytest.raises(ValueError, match='fits no slot'):
-        run_episodes([_agents(sc, p) for sc, p, _ in specs], 3, episode_obstacles=[_obstacles(*o) for _, _, o in specs], obstacle_capacities=[4, 4, 4])
+        run_episodes([agents_of(sc, p) for sc, p, _ in specs], 3, episode_obstacles=[_obstacles(*o) for _, _, o in specs], obstacle_capacities=[4, 4, 4])
 
 
 def test_scene_batch_restart_with_obstacles(tmp_path):
@@ -681,19 +639,19 @@ def test_scene_batch_restart_with_obstacles(tmp_path):
     from sca_amd.scenes import SceneBatch
     specs = _queue()
     (sc0, p0, o0), (sc1, p1, o1), (sc2, p2, o2) = specs[1], specs[2], specs[3]         # 8, 3 and 4 obstacles
-    batch = SceneBatch([_agents(sc0, p0), _agents(sc1, p1)], scene_obstacles=[_obstacles(*o0), _obstacles(*o1)], obstacle_capacities=[8, 4], device_tracker=True,
+    batch = SceneBatch([agents_of(sc0, p0), agents_of(sc1, p1)], scene_obstacles=[_obstacles(*o0), _obstacles(*o1)], obstacle_capacities=[8, 4], device_tracker=True,
                        scene_history=8)
-    plain = SceneBatch([_agents(sc0, p0), _agents(sc1, p1)], scene_obstacles=[_obstacles(*o0), _obstacles(*o1)], device_tracker=True)
+    plain = SceneBatch([agents_of(sc0, p0), agents_of(sc1, p1)], scene_obstacles=[_obstacles(*o0), _obstacles(*o1)], device_tracker=True)
     for _ in range(3):
         batch.step()
         plain.step()
     before = {k: v.copy() for k, v in batch.solver.get_state().items()}
     with pytest.raises(ValueError, match='holds up to 4 obstacles'):
-        batch.restart({1: _agents(sc0, p1)}, obstacles={1: _obstacles(*o0)})
+        batch.restart({1: agents_of(sc0, p1)}, obstacles={1: _obstacles(*o0)})
     with pytest.raises(ValueError, match='not restarted'):
-        batch.restart({1: _agents(sc2, p1)}, obstacles={0: _obstacles(*o2)})
+        batch.restart({1: agents_of(sc2, p1)}, obstacles={0: _obstacles(*o2)})
     with pytest.raises(ValueError, match='without obstacle slots'):
-        plain.restart({1: _agents(sc2, p1)}, obstacles={1: _obstacles(*o2)})
+        plain.restart({1: agents_of(sc2, p1)}, obstacles={1: _obstacles(*o2)})
     for b_, want in ((batch, before), (plain, before)):
         st = b_.solver.get_state()
         for k in want:
@@ -701,10 +659,10 @@ def test_scene_batch_restart_with_obstacles(tmp_path):
         assert len(b_.env(1).obstacles) == 3
     assert batch.solver.scene_obstacle_counts()['counts'].tolist() == [8, 3]
     new = _obstacles(*o2)
-    batch.restart({1: _agents(sc2, p1)}, obstacles={1: new})
+    batch.restart({1: agents_of(sc2, p1)}, obstacles={1: new})
     assert batch.solver.scene_obstacle_counts()['counts'].tolist() == [8, 4] and batch.env(1).obstacles == new and batch.env(1)._obs_lo == 8
     env = E.MACAEnv(device_tracker=True)
-    env.set_agents(_agents(sc2, p1), obstacles=_obstacles(*o2))
+    env.set_agents(agents_of(sc2, p1), obstacles=_obstacles(*o2))
     for t in range(6):
         batch.step()
         env.step({})
@@ -718,6 +676,61 @@ def test_scene_batch_restart_with_obstacles(tmp_path):
     paths = metrics.write_episode_log(batch.env(1), str(tmp_path / 'refilled'), xlsx=False)
     listed = json.load(open(paths['env_cfg']))['all_obstacle']
     assert [o['position'] for o in listed] == [list(o.pos) for o in new] and len(listed) == 4
-    batch.restart({1: _agents(sc1, p1)})                             # absent from `obstacles`: the slot keeps its list
+    batch.restart({1: agents_of(sc1, p1)})                             # absent from `obstacles`: the slot keeps its list
     assert batch.env(1).obstacles == new and batch.solver.scene_obstacle_counts()['counts'].tolist() == [8, 4]
     env.solver.close(); batch.close(); plain.close()
+
+
+# ---- 13: one kernel behind the three entry points -----------------------------------------------------------------------------------------------
+def test_one_kernel_behind_the_three_entry_points(S):
+    """k_scene_restart serves sca_restart_scenes, sca_restart_scenes_sized and sca_restart_scenes_obstacles alike.  The same restart of
+    scene 1 of three 12-agent circles (the six policies, the tracker on) through each of them -- sizes = the capacity, obs_counts = [-1] --
+    on a context without any obstacle arrays and on one whose obstacle slots of capacity 4 hold 3 spheres each.  Behind each of 5 steps
+    the slot is a fresh context of the new episode alone with the slot's set, every value of everything(), and on the slots context its
+    lists hold obstacles of its own set.  Directly behind the call it is that context in what a restart resets (include/sca_hip.h: state,
+    permutation, empty neighbour lists, tracker records and re-plan counts, counters) -- action rows, list entries and diagnostics are the
+    last pass's output until the next pass, and a fresh context has had none.  Scenes 0 and 2 are those of a twin batch that was never
+    restarted, at the call and at every step, and the obstacle counts stay."""
+    mix = np.resize(MIX, 12)
+    first, new = circle_scene(S, 12, mix, rad=4.0), circle_scene(S, 12, mix[::-1], rad=4.0, turn=2)
+    sets = [spheres(50 + s, 3) for s in range(3)]
+    ways = dict(plain={}, sized=dict(sizes=[12]), keep=dict(sizes=[12], obstacles=[None]))
+    for where, kw in (('no obstacles', {}), ('slots', dict(obstacles=sets, obs_slots=[4] * 3))):
+        for way, how in ways.items():
+            sol, off = context(S, [first] * 3, **kw)
+            twin = context(S, [first] * 3, **kw)[0]
+            solo = alone(S, new, sets[1] if kw else NO_OBSTACLES)
+            step_all(S, sol, twin, k=5)
+            restart_all(sol, [1], [new], **how)
+            others = [int(off[s]) + a for s in (0, 2) for a in tracked(first)]
+            saw_obstacle = False
+            for t in range(6):
+                ctx = (where, way, 'step', t)
+                if t:
+                    step_all(S, sol, twin, solo)
+                    got = assert_slots_equal_alone(sol, off, {1: new}, {1: solo}, ctx, obs_lo={1: 4 if kw else 0})
+                    listed = got['nbr_id'][12:24][got['nbr_kind'][12:24] == 1]
+                    assert ((listed >= 4) & (listed < 7)).all(), ctx + ('an obstacle id outside the slot\'s set',)
+                    saw_obstacle = saw_obstacle or len(listed) > 0
+                else:
+                    got = dict(sol.get_state(), perm=sol.get_kd_perm() - 12, nbr_n=sol.neighbors()['nbr_n'], replans=sol.device_tracker_replans())
+                    want = dict(solo.get_state(), perm=solo.get_kd_perm(), nbr_n=solo.neighbors()['nbr_n'], replans=solo.device_tracker_replans())
+                    for key in want:
+                        assert np.array_equal(got[key][12:24], want[key]), ctx + ('behind the call', key)
+                    for a in tracked(new):
+                        assert np.array_equal(sol.device_tracker_debug(12 + int(a)), solo.device_tracker_debug(int(a)), equal_nan=True), ctx + ('behind the call', 'tracker record', a)
+                ea, eb = everything(sol, others), everything(twin, others)
+                for s in (0, 2):
+                    sl = slice(int(off[s]), int(off[s + 1]))
+                    for key in ea:
+                        if key == 'track':
+                            for i in ea[key]:
+                                assert np.array_equal(ea[key][i], eb[key][i], equal_nan=True), ctx + ('scene', s, key, i)
+                        else:
+                            assert np.array_equal(ea[key][sl], eb[key][sl], equal_nan=True), ctx + ('scene', s, key)
+                if kw:
+                    assert sol.scene_obstacle_counts()['counts'].tolist() == [3, 3, 3], ctx
+                assert sol.scene_state()['steps'].tolist() == [5 + t, t, 5 + t] and sol.scene_sizes().tolist() == [12, 12, 12], ctx
+            assert saw_obstacle == bool(kw), (where, way, 'an obstacle of the slot\'s own set in a list of the restarted scene')
+            for x in (sol, twin, solo):
+                x.close()

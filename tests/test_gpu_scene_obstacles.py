@@ -11,7 +11,7 @@ import pytest
 import test_gpu_parity as TP
 import test_gpu_scenes as TS
 from golden_util import fixture_agent_params, fixture_params, fixture_tracker_agent_params, static_inputs
-from scene_util import assert_scene_equals_alone, everything
+from scene_util import agents_of, assert_scene_equals_alone, everything, load_any, oracle_scene_runs, random_scenes, same
 
 pytestmark = pytest.mark.gpu
 
@@ -36,7 +36,7 @@ class ObsBatch(TS.Batch):
 
     def __init__(self, S, names, tracker=True, mode='scene'):
         self.S, self.names = S, list(names)
-        self.fx = [TS.load_any(n) for n in self.names]
+        self.fx = [load_any(n) for n in self.names]
         self.st = [static_inputs(f) for f in self.fx]
         sizes = [len(s['radius']) for s in self.st]
         self.off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
@@ -101,7 +101,7 @@ def test_the_reference_set():
     """what the batch below consists of: 22 episodes among obstacles (their recorded sets: 17 distinct ones of 1 .. 1491 obstacles -- six
     episodes share the take-off field's 8 spheres) and the obstacle-free ones"""
     names = reference_names()
-    fx = [TS.load_any(n) for n in names]
+    fx = [load_any(n) for n in names]
     with_obs = [n for n, f in zip(names, fx) if len(f['obs_radius'])]
     assert len(with_obs) == 22
     assert len({(f['obs_pos'].tobytes(), f['obs_radius'].tobytes()) for f in fx if len(f['obs_radius'])}) == 17
@@ -146,7 +146,7 @@ def test_packed_form_reversed_and_replicated(S):
     """the same batch in reverse order, as many copies as make 6144 agents (the packed query form, four agents per wavefront): steps 0-3
     and 39 against the fixtures, every copy against copy 0"""
     names = reference_names()[::-1]
-    one = sum(len(TS.load_any(n)['radius']) for n in names)
+    one = sum(len(load_any(n)['radius']) for n in names)
     copies = -(-6144 // one)
     b = ObsBatch(S, names * copies)
     assert b.n == one * copies >= 6144 and copies >= 2
@@ -276,7 +276,7 @@ OBS_COUNTS = [0, 1, 2, 10, 11, 21, 300]                           # none, one no
 
 def _random_obstacles(nscenes):
     """one seeded obstacle set per scene, the counts of OBS_COUNTS in turn (scene s: OBS_COUNTS[(s + s // 7) % 7], so that every scene size
-    class meets several counts); around the small scenes' volume (tests/test_gpu_scenes.py::_random_scenes), the 300 spread wider"""
+    class meets several counts); around the small scenes' volume (scene_util.random_scenes), the 300 spread wider"""
     rng = np.random.default_rng(777)
     out = []
     for s in range(nscenes):
@@ -294,12 +294,12 @@ def test_random_scenes_with_their_own_obstacles_against_the_oracle(S, oracle, pa
     K1 scene forms (SCA_K1_PACKED: 1 is what 6884 agents run by default -- a wavefront's four groups can belong to four scenes, some of them
     without obstacles --, 0 is k_neighbors_kd_scenes)."""
     monkeypatch.setenv('SCA_K1_PACKED', str(packed))                 # read by sca_create
-    scenes, sizes, _, _ = TS._random_scenes(S)
+    scenes, sizes, _, _ = random_scenes(S)
     obstacles = _random_obstacles(len(scenes))
     assert sorted({len(r) for _, r in obstacles}) == OBS_COUNTS
     sol, off = _context(S, scenes, obstacles)
     obs_off = np.concatenate([[0], np.cumsum([len(r) for _, r in obstacles])]).astype(np.int32)
-    ref = TS.oracle_scene_runs(oracle, 'own obstacles', scenes, obstacles, stop_when_done=True)
+    ref = oracle_scene_runs(oracle, 'own obstacles', scenes, obstacles, stop_when_done=True)
     saw_obstacle_neighbour, finished = set(), set()
     for t in range(6):
         sol.run_steps(1, S.NBR_KDTREE)
@@ -417,11 +417,6 @@ def _run(S, sol, steps=8):
     return everything(sol)
 
 
-def _same(a, b, ctx):
-    for key in a:
-        assert np.array_equal(a[key], b[key], equal_nan=key == 'vpref'), (ctx, key)
-
-
 def _restart(sol, scenes):
     start = np.concatenate([sc['start'] for sc in scenes])
     n = len(start)
@@ -462,7 +457,7 @@ def test_refusals_change_nothing(S):
     # ... and the context is what it was: the sets of the accepted call, as in a fresh context
     _restart(sol, scenes)
     fresh = _context(S, scenes, sets, tracker=False)[0]
-    _same(_run(S, sol), _run(S, fresh), 'after the refusals')
+    same(_run(S, sol), _run(S, fresh), ('after the refusals',), nan_keys=('vpref',))
     assert sol.pass_forms() & S.FORM_SCENE_OBSTACLES
     sol.close(); fresh.close()
 
@@ -476,7 +471,7 @@ def test_lifetime_of_the_per_scene_sets(S):
     sol.set_obstacles(*shared)
     _restart(sol, scenes)
     fresh = _context(S, scenes, shared, mode='shared', max_obstacles=16, tracker=False)[0]
-    _same(_run(S, sol), _run(S, fresh), 'back on a shared set')
+    same(_run(S, sol), _run(S, fresh), ('back on a shared set',), nan_keys=('vpref',))
     assert sol.pass_forms() & S.FORM_SCENES and not sol.pass_forms() & S.FORM_SCENE_OBSTACLES
     assert fresh.pass_forms() & S.FORM_SCENES and not fresh.pass_forms() & S.FORM_SCENE_OBSTACLES     # scenes + a shared set: what it reported before
     fresh.close()
@@ -501,13 +496,13 @@ def test_lifetime_of_the_per_scene_sets(S):
             sol.set_scenes(None)
             sol.set_scenes(off)
         _restart(sol, scenes)
-        _same(_run(S, sol), want, how)
+        same(_run(S, sol), want, (how,), nan_keys=('vpref',))
         assert sol.pass_forms() & S.FORM_SCENES and not sol.pass_forms() & S.FORM_SCENE_OBSTACLES, how
         sol.set_scene_obstacles(sets)                             # (and on again for the next way of dropping them)
     # a total of 0 is "no obstacles"
     sol.set_scene_obstacles([(np.zeros((0, 3)), np.zeros(0))] * 3)
     _restart(sol, scenes)
-    _same(_run(S, sol), want, 'a total of 0')
+    same(_run(S, sol), want, ('a total of 0',), nan_keys=('vpref',))
     assert not sol.pass_forms() & S.FORM_SCENE_OBSTACLES
     sol.close(); bare.close()
 
@@ -521,20 +516,17 @@ def test_scene_batch_with_scene_obstacles_equals_separate_envs(S):
     def spheres(pos, radius):
         return [E.Obstacle(pos=list(map(float, p)), shape_dict={'shape': 'sphere', 'feature': float(r)}, id=i) for i, (p, r) in enumerate(zip(pos, radius))]
 
-    def agents(sc, policy):
-        return [E.Agent(start_pos=list(sc['start'][i]), goal_pos=list(sc['goal'][i]), vel=[0.0, 0.0, 0.0], radius=0.5, pref_speed=1.0,
-                        policy=policy, id=i) for i in range(len(sc['start']))]
     tk = scenarios.takeoff_landing(16)
     assert len(tk['obs_radius']) == 8
     few = ([[1.5, 0.5, 10.0], [-2.0, 1.0, 10.5], [0.0, -2.5, 9.5]], [0.7, 0.5, 0.9])
     spec = [(scenarios.circle(12), E.RVO3DPolicy, ([], [])), (tk, E.SCAPolicy, (tk['obs_pos'], tk['obs_radius'])), (scenarios.circle(10), E.ORCA3DPolicy, few)]
     with pytest.raises(ValueError):
-        SceneBatch([agents(sc, p) for sc, p, _ in spec], spheres(*few), scene_obstacles=[spheres(*o) for _, _, o in spec])
-    batch = SceneBatch([agents(sc, p) for sc, p, _ in spec], scene_obstacles=[spheres(*o) for _, _, o in spec], device_tracker=True)
+        SceneBatch([agents_of(sc, p) for sc, p, _ in spec], spheres(*few), scene_obstacles=[spheres(*o) for _, _, o in spec])
+    batch = SceneBatch([agents_of(sc, p) for sc, p, _ in spec], scene_obstacles=[spheres(*o) for _, _, o in spec], device_tracker=True)
     envs = []
     for sc, p, o in spec:
         env = E.MACAEnv(device_tracker=True)
-        env.set_agents(agents(sc, p), obstacles=spheres(*o))
+        env.set_agents(agents_of(sc, p), obstacles=spheres(*o))
         envs.append(env)
     counts, done_env = [0, 0, 0], [False, False, False]
     saw_obstacle = False

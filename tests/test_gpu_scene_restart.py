@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from scene_util import Slots, assert_scene_equals_alone, everything, load_any
+from scene_util import Slots, assert_scene_equals_alone, circle_scene, context, everything, load_any, observe, rc_of, restart_all
 
 pytestmark = pytest.mark.gpu
 
@@ -30,12 +30,6 @@ PLAN = {3: 'F3_orca_random100',        # RVO3D+Dubins (tracked)  -> ORCA (untrac
 def S():
     import sca_amd.solver as S
     return S
-
-
-def _rc(S, fn):
-    with pytest.raises(S.ScaError) as e:
-        fn()
-    return int(str(e.value).rsplit('rc=', 1)[1].rstrip(')'))
 
 
 def _beside(S, b, solos):
@@ -97,41 +91,6 @@ def test_restart_after_a_natural_finish_with_obstacles_and_the_tracker(S):
     solo.sol.close()
 
 
-def _circle_scene(S, n, policy, rad=None, turn=0):
-    from sca_amd import scenarios
-    sc = scenarios.circle(n, rad=rad)
-    start, goal = np.roll(sc['start'], turn, axis=0), np.roll(sc['goal'], turn, axis=0)
-    return dict(n=n, pos=start[:, :3], heading=start[:, 3:6], vel=np.zeros((n, 3), np.float32), radius=np.full(n, 0.5), pref_speed=np.ones(n),
-                goal=goal[:, :3], policy=np.broadcast_to(np.asarray(policy, np.uint8), (n,)).copy(), zaxis=S.zaxis_flags(start, goal),
-                max_run_dist=scenarios.max_run_dist(start, goal), goal_heading=goal[:, 3:6])
-
-
-def _context(S, eps, obstacles=None, shared=None):
-    """episodes (dicts of _circle_scene / episode_arrays) as the scenes of one context; obstacles: one (pos, radius) per scene"""
-    off = np.concatenate([[0], np.cumsum([e['n'] for e in eps])]).astype(np.int32)
-    n = int(off[-1])
-    cat = lambda key: np.concatenate([e[key] for e in eps])
-    m = sum(len(r) for _, r in obstacles) if obstacles else (len(shared[1]) if shared else 0)
-    sol = S.BatchedSolver(max_agents=n, max_obstacles=max(m, 1))
-    if shared:
-        sol.set_obstacles(*shared)
-    sol.set_agents(cat('radius'), cat('pref_speed'), cat('goal'), cat('policy'), cat('zaxis'), cat('max_run_dist'))
-    sol.set_scenes(off)
-    if obstacles:
-        sol.set_scene_obstacles(obstacles)
-    sol.device_tracker_enable(cat('goal_heading'), in_pass=True)
-    sol.set_state(cat('pos'), cat('vel'), cat('heading'), np.zeros(n, np.uint8))
-    return sol, off
-
-
-def _restart(sol, ids, eps, **drop):
-    cat = lambda key: np.concatenate([e[key] for e in eps])
-    kw = dict(vel=cat('vel'), radius=cat('radius'), pref_speed=cat('pref_speed'), goal=cat('goal'), policy=cat('policy'), zaxis=cat('zaxis'),
-              max_run_dist=cat('max_run_dist'), goal_heading=cat('goal_heading'))
-    kw.update(drop)
-    sol.restart_scenes(ids, cat('pos'), cat('heading'), **kw)
-
-
 MIX = np.array([0, 1, 2, 3, 4, 5] * 2, np.uint8)
 
 
@@ -139,21 +98,21 @@ def test_per_scene_obstacle_sets(S):
     """three scenes with their own spheres / none / other spheres; after 15 steps the scene WITHOUT obstacles and the last one, whose
     obstacle ids start at 12, are given another episode: both equal a fresh context of that episode alone with the slot's obstacle set for 30
     steps, the first equals its own context straight through, and the neighbours' obstacle ids stay global"""
-    first = _circle_scene(S, 12, MIX)
+    first = circle_scene(S, 12, MIX)
     unit = first['goal'] - first['pos']
     unit /= np.linalg.norm(unit, axis=1)[:, None]
     sets = [(np.round(first['pos'] + 3.0 * unit, 2), np.full(12, 0.6)), (np.zeros((0, 3)), np.zeros(0)),
             (np.round(first['pos'] + 5.0 * unit + [0.0, 0.0, 0.4], 2)[::2], np.full(6, 0.9))]
     obs_off = [0, 12, 12, 18]
-    sol, off = _context(S, [first] * 3, obstacles=sets)
-    alone = {0: _context(S, [first], obstacles=[sets[0]])[0]}
+    sol, off = context(S, [first] * 3, obstacles=sets)
+    alone = {0: context(S, [first], obstacles=[sets[0]])[0]}
     for x in [sol, alone[0]]:
         x.run_steps(15, S.NBR_KDTREE)
         x.synchronize()
-    new = {2: _circle_scene(S, 12, MIX[::-1], turn=3), 1: _circle_scene(S, 12, np.roll(MIX, 1), rad=3.0, turn=5)}
-    _restart(sol, [2, 1], [new[2], new[1]])                         # (named out of order: the arrays follow scene_ids)
+    new = {2: circle_scene(S, 12, MIX[::-1], turn=3), 1: circle_scene(S, 12, np.roll(MIX, 1), rad=3.0, turn=5)}
+    restart_all(sol, [2, 1], [new[2], new[1]])                         # (named out of order: the arrays follow scene_ids)
     for s in (1, 2):
-        alone[s] = _context(S, [new[s]], obstacles=[sets[s]])[0]
+        alone[s] = context(S, [new[s]], obstacles=[sets[s]])[0]
     seen_obstacle = {0: False, 1: False, 2: False}
     for t in range(30):
         for x in [sol] + list(alone.values()):
@@ -174,13 +133,13 @@ def test_per_scene_obstacle_sets(S):
 def test_other_entry_points(S):
     """after a restart: sca_run_steps(k) with no synchronisation in between gives what k single steps give (and what the episode alone gives);
     sca_step_host with in_mask == 0 leaves the block holding the restarted state's successor and its action rows"""
-    first, new = _circle_scene(S, 12, MIX), _circle_scene(S, 12, MIX[::-1], rad=3.5, turn=2)
-    ctxs = [_context(S, [first] * 3)[0] for _ in range(3)]
+    first, new = circle_scene(S, 12, MIX), circle_scene(S, 12, MIX[::-1], rad=3.5, turn=2)
+    ctxs = [context(S, [first] * 3)[0] for _ in range(3)]
     for x in ctxs:
         x.host_state()
         x.run_steps(8, S.NBR_KDTREE)
-        _restart(x, [1], [new])
-    solo = _context(S, [new])[0]
+        restart_all(x, [1], [new])
+    solo = context(S, [new])[0]
     burst, single, host = ctxs
     burst.run_steps(6, S.NBR_KDTREE)
     for _ in range(6):
@@ -192,7 +151,7 @@ def test_other_entry_points(S):
         assert np.array_equal(a[key], b_[key], equal_nan=True), ('burst against single steps', key)
     assert_scene_equals_alone(a, 12, 24, 0, everything(solo), ('burst against the episode alone',))
     # the host block
-    solo1 = _context(S, [new])[0]
+    solo1 = context(S, [new])[0]
     solo1.run_steps(1, S.NBR_KDTREE)
     active = host.step_host(S.NBR_KDTREE, state=False)
     blk, want, st = host.host_state(), solo1.get_state(), host.get_state()
@@ -206,23 +165,16 @@ def test_other_entry_points(S):
         x.close()
 
 
-def _observe(sol):
-    out = dict(sol.get_state())
-    out['perm'] = sol.get_kd_perm()
-    out.update(sol.scene_state())
-    return out
-
-
 def test_refusals_change_nothing(S):
-    first, new = _circle_scene(S, 12, MIX), _circle_scene(S, 12, MIX[::-1], turn=2)
-    sol, _ = _context(S, [first] * 3)
+    first, new = circle_scene(S, 12, MIX), circle_scene(S, 12, MIX[::-1], turn=2)
+    sol, _ = context(S, [first] * 3)
     sol.run_steps(5, S.NBR_KDTREE)
-    before = _observe(sol)
+    before = observe(sol)
 
     def refused(code, ids=(1,), eps=None, **kw):
         eps = [new] * len(ids) if eps is None else eps
-        assert _rc(S, lambda: _restart(sol, list(ids), eps, **kw)) == code, (code, ids, sorted(kw))
-        after = _observe(sol)
+        assert rc_of(S, lambda: restart_all(sol, list(ids), eps, **kw)) == code, (code, ids, sorted(kw))
+        after = observe(sol)
         for key in before:
             assert np.array_equal(before[key], after[key]), ('a refused call changed', key, ids, sorted(kw))
     bad = lambda key, value, row=5, col=None: {key: _with(new[key], row, col, value)}
@@ -244,23 +196,23 @@ def test_refusals_change_nothing(S):
     assert raw(ids.ctypes.data_as(C.POINTER(C.c_int32)), None, dp(h)) == ERR_ARG
     assert raw(ids.ctypes.data_as(C.POINTER(C.c_int32)), dp(p), None) == ERR_ARG
     assert raw(None, dp(p), dp(h)) == ERR_ARG                        # scene_ids NULL
-    assert _rc(S, lambda: sol.restart_scenes([1], _with(new['pos'], 0, 2, np.nan), new['heading'])) == ERR_ARG
-    assert _rc(S, lambda: sol.restart_scenes([1], new['pos'], _with(new['heading'], 3, 0, np.inf))) == ERR_ARG
-    after = _observe(sol)
+    assert rc_of(S, lambda: sol.restart_scenes([1], _with(new['pos'], 0, 2, np.nan), new['heading'])) == ERR_ARG
+    assert rc_of(S, lambda: sol.restart_scenes([1], new['pos'], _with(new['heading'], 3, 0, np.inf))) == ERR_ARG
+    after = observe(sol)
     for key in before:
         assert np.array_equal(before[key], after[key]), key
     # between a policy pass and its env update
     sol.policy_pass(S.NBR_KDTREE)
-    mid = _observe(sol)
-    assert _rc(S, lambda: _restart(sol, [1], [new])) == ERR_STATE
-    for key, v in _observe(sol).items():
+    mid = observe(sol)
+    assert rc_of(S, lambda: restart_all(sol, [1], [new])) == ERR_STATE
+    for key, v in observe(sol).items():
         assert np.array_equal(mid[key], v), key
     sol.env_update()
     # per-agent tracker attributes: a policy array that moves an agent between tracked and untracked is refused, one that does not is taken
     sol.device_tracker_set_agent_params(turning_radius=np.where(np.arange(36) % 2, 1.5, 2.0))
-    before = _observe(sol)
+    before = observe(sol)
     refused(ERR_UNSUPPORTED, policy=np.roll(MIX, 1))                 # agent 1: RVO -> SCA, untracked -> tracked
-    _restart(sol, [1], [new])                                        # MIX reversed: SCA <-> RVO3D+Dubins only, tracked stays tracked
+    restart_all(sol, [1], [new])                                        # MIX reversed: SCA <-> RVO3D+Dubins only, tracked stays tracked
     assert sol.scene_state()['steps'].tolist() == [6, 0, 6]
     sol.close()
 
@@ -276,39 +228,39 @@ def _with(a, row, col, value):
 
 def test_refusals_by_state(S):
     """no scenes, no state yet, goal_heading without a tracker, waypoint lists set"""
-    first, new = _circle_scene(S, 12, MIX), _circle_scene(S, 12, MIX[::-1], turn=2)
+    first, new = circle_scene(S, 12, MIX), circle_scene(S, 12, MIX[::-1], turn=2)
     n = 24
     cat = lambda key: np.concatenate([first[key]] * 2)
     sol = S.BatchedSolver(max_agents=n, max_obstacles=1)
     sol.set_agents(cat('radius'), cat('pref_speed'), cat('goal'), cat('policy'), cat('zaxis'), cat('max_run_dist'))
     sol.set_state(cat('pos'), cat('vel'), cat('heading'), np.zeros(n, np.uint8))
     plain = dict(sol.get_state(), perm=sol.get_kd_perm())
-    assert _rc(S, lambda: _restart(sol, [0], [new], goal_heading=None)) == ERR_STATE          # no scenes
+    assert rc_of(S, lambda: restart_all(sol, [0], [new], goal_heading=None)) == ERR_STATE          # no scenes
     for key, v in dict(sol.get_state(), perm=sol.get_kd_perm()).items():
         assert np.array_equal(plain[key], v), key
-    assert _rc(S, sol.scene_state) == ERR_STATE                                               # (still none)
+    assert rc_of(S, sol.scene_state) == ERR_STATE                                               # (still none)
     sol.set_agents(cat('radius'), cat('pref_speed'), cat('goal'), cat('policy'), cat('zaxis'), cat('max_run_dist'))
     sol.set_scenes([0, 12, 24])
     perm = sol.get_kd_perm()
-    assert _rc(S, lambda: _restart(sol, [0], [new], goal_heading=None)) == ERR_STATE          # no state yet
+    assert rc_of(S, lambda: restart_all(sol, [0], [new], goal_heading=None)) == ERR_STATE          # no state yet
     assert np.array_equal(perm, sol.get_kd_perm())
-    assert _rc(S, sol.get_state) == ERR_STATE and _rc(S, sol.scene_state) == ERR_STATE        # (still no state: nothing to compare but the permutation)
+    assert rc_of(S, sol.get_state) == ERR_STATE and rc_of(S, sol.scene_state) == ERR_STATE        # (still no state: nothing to compare but the permutation)
     sol.set_state(cat('pos'), cat('vel'), cat('heading'), np.zeros(n, np.uint8))
     sol.run_steps(3, S.NBR_KDTREE)
-    before = _observe(sol)
-    assert _rc(S, lambda: _restart(sol, [0], [new])) == ERR_ARG                               # goal_heading, and no tracker is enabled
+    before = observe(sol)
+    assert rc_of(S, lambda: restart_all(sol, [0], [new])) == ERR_ARG                               # goal_heading, and no tracker is enabled
     sol.set_paths([[[1.0, 2.0, 10.0]]] + [[] for _ in range(n - 1)])
-    assert _rc(S, lambda: _restart(sol, [0], [new], goal_heading=None)) == ERR_UNSUPPORTED    # waypoint lists are set
-    after = _observe(sol)
+    assert rc_of(S, lambda: restart_all(sol, [0], [new], goal_heading=None)) == ERR_UNSUPPORTED    # waypoint lists are set
+    after = observe(sol)
     for key in before:
         assert np.array_equal(before[key], after[key]), key
     sol.set_paths(None)
     with pytest.raises(ValueError):                                                           # the binding holds every array against T
-        _restart(sol, [0], [new], goal_heading=None, radius=new['radius'][:11])
+        restart_all(sol, [0], [new], goal_heading=None, radius=new['radius'][:11])
     with pytest.raises(ValueError):
         sol.restart_scenes([0, 1], new['pos'], new['heading'])
-    for key, v in _observe(sol).items():
+    for key, v in observe(sol).items():
         assert np.array_equal(before[key], v), key
-    _restart(sol, [0], [new], goal_heading=None)                                              # ... and without them it is taken
+    restart_all(sol, [0], [new], goal_heading=None)                                              # ... and without them it is taken
     assert sol.scene_state()['steps'].tolist() == [0, 3]
     sol.close()

@@ -6,9 +6,8 @@ its records; the vacant rows are held against what include/sca_hip.h says they r
 import numpy as np
 import pytest
 
-from scene_sizes_util import (NO_OBSTACLES, SizedSlots, alone, assert_slots_equal_alone, assert_vacant, circle_scene, context, padded,
-                              partial_batch, sized_restart)
-from scene_util import everything, load_any
+from scene_util import (NO_OBSTACLES, SizedSlots, alone, assert_slots_equal_alone, assert_vacant, circle_scene, context, everything, load_any, observe,
+                        padded, partial_batch, rc_of, restart_all, step_all)
 
 pytestmark = pytest.mark.gpu
 
@@ -21,18 +20,6 @@ MIX = np.array([0, 1, 2, 3, 4, 5], np.uint8)
 def S():
     import sca_amd.solver as S
     return S
-
-
-def _rc(S, fn):
-    with pytest.raises(S.ScaError) as e:
-        fn()
-    return int(str(e.value).rsplit('rc=', 1)[1].rstrip(')'))
-
-
-def _step(S, *sols, k=1):
-    for x in sols:
-        x.run_steps(k, S.NBR_KDTREE)
-        x.synchronize()
 
 
 def _mix(n, shift=0):
@@ -61,7 +48,7 @@ def test_recorded_episodes_into_larger_slots(S):
     obs_lo = {1: 0, 2: 14}
 
     def beside(t):
-        _step(S, *(x for x, _ in solos.values()))
+        step_all(S, *(x for x, _ in solos.values()))
         got = assert_slots_equal_alone(b.sol, b.off, {s: e for s, (_, e) in solos.items()}, {s: x for s, (x, _) in solos.items()},
                                        ('beside', 'batch step', t), obs_lo=obs_lo)
         assert_vacant(got, b.off, b.size, ('batch step', t))
@@ -96,7 +83,7 @@ def test_boundary_sizes(S):
     solos = {s: context(S, [e])[0] for s, e in enumerate(eps)}
     held = dict(enumerate(eps))
     for t in range(12):
-        _step(S, sol, *solos.values())
+        step_all(S, sol, *solos.values())
         got = assert_slots_equal_alone(sol, off, held, solos, ('boundary sizes', 'step', t))
         assert_vacant(got, off, SIZES, ('boundary sizes', 'step', t))
         assert sol.active_count() == sum(x.active_count() for x in solos.values())
@@ -115,7 +102,7 @@ def test_vacant_rows_are_inert_and_invisible(S):
     sol, off = context(S, [other, big])
     lo, hi = int(off[1]), int(off[2])
     for _ in range(40):                                             # 100 steps at a time until the scene is done (40 m at 0.1 m a step, and the detours)
-        _step(S, sol, k=100)
+        step_all(S, sol, k=100)
         if sol.scene_state()['active'][1] == 0:
             break
     st = sol.get_state()
@@ -123,13 +110,13 @@ def test_vacant_rows_are_inert_and_invisible(S):
     arrived = st['pos'][lo + 50:hi][(st['flags'][lo + 50:hi] & 1) == 1]        # rows that will be vacant, at their goals on the circle
     on_top = (np.linalg.norm(small['pos'][:, None] - arrived[None], axis=2) < 1.0).any(axis=1).sum()
     assert on_top >= 10, on_top                                    # new agents start within touching distance (2 radii) of them
-    sized_restart(sol, [1], [small])
+    restart_all(sol, [1], [small], sizes='own')
     left = everything(sol)
     vac = slice(lo + 50, hi)
     assert np.array_equal(left['pos'][vac], st['pos'][vac])         # a vacant row keeps the position of whoever stood there
     solo = context(S, [small])[0]
     for t in range(30):
-        _step(S, sol, solo)
+        step_all(S, sol, solo)
         got = assert_slots_equal_alone(sol, off, {1: small}, {1: solo}, ('on top of vacant rows', 'step', t))
         assert_vacant(got, off, [12, 50], ('step', t))
         for key in ('nbr_id',):
@@ -150,7 +137,7 @@ def test_every_step_form_behind_a_sized_restart(S):
                  run_steps=lambda x: (x.run_steps(6, S.NBR_KDTREE), x.synchronize()),
                  split=lambda x: [(x.policy_pass(S.NBR_KDTREE), x.env_update()) for _ in range(6)])
     solos = {s: context(S, [e])[0] for s, e in enumerate(eps)}
-    _step(S, *solos.values(), k=6)
+    step_all(S, *solos.values(), k=6)
     results = {}
     for name, form in forms.items():
         sol, off = partial_batch(S, eps, 12)
@@ -171,28 +158,28 @@ def test_the_log_per_scene(S):
     full, first, second = circle_scene(S, 12, _mix(12)), circle_scene(S, 9, _mix(9, 1), rad=3.0), circle_scene(S, 5, _mix(5, 2), rad=2.5, turn=1)
     sol, off = context(S, [full, padded(first, 12)])
     sol.scene_history_enable(16)
-    sized_restart(sol, [1], [first])
+    restart_all(sol, [1], [first], sizes='own')
     solos = []
     for e in (full, first, second):
         x = context(S, [e])[0]
         x.history_enable(16)
         solos.append(x)
-    _step(S, sol, solos[0], solos[1], k=4)
+    step_all(S, sol, solos[0], solos[1], k=4)
     same = lambda a, b: all(np.array_equal(a[k], b[k]) for k in ('pos', 'heading', 'vel'))
     assert sol.scene_history_rows()['logged'].tolist() == [4, 4]
     assert same(sol.scene_history(1), solos[1].history()) and sol.scene_history(1)['pos'].shape == (4, 9, 3)
     assert same(sol.scene_history(1, 1, 2, 3, 6), solos[1].history(1, 2, 3, 6))
-    assert _rc(S, lambda: sol.scene_history(1, 0, 4, 0, 10)) == ERR_ARG          # size + 1
-    assert _rc(S, lambda: sol.scene_history(1, 0, 4, 9, 1)) == ERR_ARG
+    assert rc_of(S, lambda: sol.scene_history(1, 0, 4, 0, 10)) == ERR_ARG          # size + 1
+    assert rc_of(S, lambda: sol.scene_history(1, 0, 4, 9, 1)) == ERR_ARG
     before = sol.scene_history(0)
-    sized_restart(sol, [1], [second])                                # shrink 9 -> 5 while the slot is running
+    restart_all(sol, [1], [second], sizes='own')                  # shrink 9 -> 5 while the slot is running
     assert sol.scene_history_rows()['logged'].tolist() == [4, 0]
     assert same(sol.scene_history(0), before)
-    _step(S, sol, solos[0], solos[2], k=3)
+    step_all(S, sol, solos[0], solos[2], k=3)
     assert sol.scene_history_rows()['logged'].tolist() == [7, 3]
     assert same(sol.scene_history(1), solos[2].history()) and sol.scene_history(1)['pos'].shape == (3, 5, 3)
     assert same(sol.scene_history(0), solos[0].history())
-    assert _rc(S, lambda: sol.scene_history(1, 0, 3, 0, 6)) == ERR_ARG
+    assert rc_of(S, lambda: sol.scene_history(1, 0, 3, 0, 6)) == ERR_ARG
     for x in [sol] + solos:
         x.close()
 
@@ -205,13 +192,13 @@ def test_per_scene_obstacle_sets(S):
     circle = circle_scene(S, 24, SCA, rad=8.0)
     b = SizedSlots(S, [circle, circle], obstacles=[spheres, NO_OBSTACLES])
     other = context(S, [circle])[0]
-    b.run_and_check(5, after_step=lambda t: _step(S, other), label='two circles')
+    b.run_and_check(5, after_step=lambda t: step_all(S, other), label='two circles')
     b.restart({0: 'F4_sca_takeoff16'})
     assert b.sol.scene_sizes().tolist() == [16, 24]
     solo, ep = alone(S, 'F4_sca_takeoff16')
 
     def beside(t):
-        _step(S, solo, other)
+        step_all(S, solo, other)
         got = assert_slots_equal_alone(b.sol, b.off, {0: ep, 1: circle}, {0: solo, 1: other}, ('take-off field', 'batch step', t), obs_lo={0: 0, 1: 8})
         assert_vacant(got, b.off, [16, 24], ('batch step', t))
     compared = b.run_and_check(40, after_step=beside, label='take-off episode in a slot of 24')
@@ -220,27 +207,19 @@ def test_per_scene_obstacle_sets(S):
         x.close()
 
 
-def _observe(sol):
-    out = dict(sol.get_state())
-    out['perm'] = sol.get_kd_perm()
-    out.update(sol.scene_state())
-    out['sizes'] = sol.scene_sizes()
-    return out
-
-
 def test_refusals_and_equivalence(S):
     first, new, small = circle_scene(S, 12, _mix(12)), circle_scene(S, 12, _mix(12, 3), turn=2), circle_scene(S, 7, _mix(7, 1), rad=3.0)
     sol, off = context(S, [first] * 3)
     twin, _ = context(S, [first] * 3)
-    _step(S, sol, twin, k=5)
-    before = _observe(sol)
+    step_all(S, sol, twin, k=5)
+    before = observe(sol)
     for size in (0, 13, -1):                                         # size 0, capacity + 1 (the arrays hold the capacity's 12 rows: the library decides)
-        assert _rc(S, lambda: sized_restart(sol, [1], [new], sizes=[size])) == ERR_ARG, size
-        after = _observe(sol)
+        assert rc_of(S, lambda: restart_all(sol, [1], [new], sizes=[size])) == ERR_ARG, size
+        after = observe(sol)
         for key in before:
             assert np.array_equal(before[key], after[key]), ('a refused call changed', key, size)
     # sizes == NULL is sca_restart_scenes
-    sized_restart(sol, [2, 0], [new, new], sizes=None)
+    restart_all(sol, [2, 0], [new, new])
     cat = lambda key: np.concatenate([new[key], new[key]])
     twin.restart_scenes([2, 0], cat('pos'), cat('heading'), vel=cat('vel'), radius=cat('radius'), pref_speed=cat('pref_speed'), goal=cat('goal'),
                         policy=cat('policy'), zaxis=cat('zaxis'), max_run_dist=cat('max_run_dist'), goal_heading=cat('goal_heading'))
@@ -249,28 +228,28 @@ def test_refusals_and_equivalence(S):
         for key in a:
             assert np.array_equal(a[key], b_[key], equal_nan=True), ('sizes == NULL against sca_restart_scenes', key, k)
         assert sol.scene_sizes().tolist() == [12, 12, 12] and sol.active_count() == twin.active_count()
-        _step(S, sol, twin, k=3)
+        step_all(S, sol, twin, k=3)
     twin.close()
     # a partial slot: the entry points that take a whole-context state from outside are refused, and nothing changes
     st, perm = sol.get_state(), sol.get_kd_perm()
     sol.host_state()
-    sized_restart(sol, [1], [small])
+    restart_all(sol, [1], [small], sizes='own')
     assert sol.scene_sizes().tolist() == [12, 7, 12]
-    partial = _observe(sol)
-    assert _rc(S, lambda: sol.set_state(st['pos'], st['vel'], st['heading'], st['flags'], st['total_dist'], st['step_num'])) == ERR_UNSUPPORTED
-    assert _rc(S, lambda: sol.set_kd_perm(perm)) == ERR_UNSUPPORTED
-    assert _rc(S, lambda: sol.step_host(S.NBR_KDTREE, state=False)) == ERR_UNSUPPORTED
-    for key, v in _observe(sol).items():
+    partial = observe(sol)
+    assert rc_of(S, lambda: sol.set_state(st['pos'], st['vel'], st['heading'], st['flags'], st['total_dist'], st['step_num'])) == ERR_UNSUPPORTED
+    assert rc_of(S, lambda: sol.set_kd_perm(perm)) == ERR_UNSUPPORTED
+    assert rc_of(S, lambda: sol.step_host(S.NBR_KDTREE, state=False)) == ERR_UNSUPPORTED
+    for key, v in observe(sol).items():
         assert np.array_equal(partial[key], v), key
     # every slot full again: they work
-    sized_restart(sol, [1], [new])                                   # (sizes [12]: the capacity)
+    restart_all(sol, [1], [new], sizes='own')                     # (sizes [12]: the capacity)
     assert sol.scene_sizes().tolist() == [12, 12, 12]
     st, perm = sol.get_state(), sol.get_kd_perm()
     sol.set_state(st['pos'], st['vel'], st['heading'], st['flags'], st['total_dist'], st['step_num'])
     sol.set_kd_perm(perm)
     assert sol.step_host(S.NBR_KDTREE, state=False) == sol.active_count()
     # ... and sca_restart_scenes itself fills a partial slot to its capacity
-    sized_restart(sol, [0], [small])
+    restart_all(sol, [0], [small], sizes='own')
     sol.restart_scenes([0], new['pos'], new['heading'])
     assert sol.scene_sizes().tolist() == [12, 12, 12] and sol.scene_state()['active'][0] == 12
     sol.set_kd_perm(sol.get_kd_perm())
@@ -278,7 +257,7 @@ def test_refusals_and_equivalence(S):
     sol.set_scenes(off)
     assert sol.scene_sizes().tolist() == [12, 12, 12]
     sol.set_scenes(None)
-    assert _rc(S, sol.scene_sizes) == -3
+    assert rc_of(S, sol.scene_sizes) == -3
     sol.close()
 
 

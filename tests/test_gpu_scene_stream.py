@@ -4,6 +4,8 @@ states must be equal: a slot that is refilled in the middle of a batch is, from 
 import numpy as np
 import pytest
 
+from scene_util import agents_of
+
 pytestmark = pytest.mark.gpu
 
 WALL = ('AverageCost',)                                             # wall time of the policy calls: differs from run to run
@@ -15,12 +17,6 @@ def mods():
     return E, metrics, scenarios, scenes
 
 
-def _agents(E, sc, policy, count=None):
-    n = len(sc['start']) if count is None else count
-    return [E.Agent(start_pos=list(sc['start'][i]), goal_pos=list(sc['goal'][i]), vel=[0.0, 0.0, 0.0], radius=0.5, pref_speed=1.0,
-                    policy=policy, id=i) for i in range(n)]
-
-
 def _queue(E, scenarios):
     """14 episodes: the take-off/landing scene and a circle of 16 for each of the six policies, and two circles of 14 at the end; all among
     the take-off field's 8 spheres.  A fresh list of Agent objects at every call."""
@@ -28,8 +24,8 @@ def _queue(E, scenarios):
     take, circ, c14 = scenarios.takeoff_landing(16), scenarios.circle(16, rad=6.0, z=12.0), scenarios.circle(14, rad=5.0, z=12.0)
     eps = []
     for p in pols:
-        eps += [_agents(E, take, p), _agents(E, circ, p)]
-    eps += [_agents(E, c14, E.SCAPolicy), _agents(E, c14, E.ORCA3DPolicy)]
+        eps += [agents_of(take, p), agents_of(circ, p)]
+    eps += [agents_of(c14, E.SCAPolicy), agents_of(c14, E.ORCA3DPolicy)]
     obstacles = [E.Obstacle(pos=list(p), shape_dict={'shape': 'sphere', 'feature': float(r)}, id=i)
                  for i, (p, r) in enumerate(zip(take['obs_pos'], take['obs_radius']))]
     return eps, obstacles
@@ -99,13 +95,13 @@ def test_restart_rebinds_the_views_and_refuses_what_a_slot_cannot_hold(mods):
     batch.step()
     assert batch.steps.tolist() == [21, 1, 21] and new[3].step_num == 1
     before = {k: batch._state(k).copy() for k in batch._mirror}
-    path = _agents(E, scenarios.circle(16), E.RVO3DPolicy)
+    path = agents_of(scenarios.circle(16), E.RVO3DPolicy)
     path[2].path = [[0.0, 0.0, 10.0]]
-    other = _agents(E, scenarios.circle(16), E.RVO3DPolicy)
+    other = agents_of(scenarios.circle(16), E.RVO3DPolicy)
     other[4].neighborDist = 7.0
-    turn = _agents(E, scenarios.circle(16), E.SCAPolicy)
+    turn = agents_of(scenarios.circle(16), E.SCAPolicy)
     turn[1].turning_radius = 2.5
-    ids = _agents(E, scenarios.circle(16), E.RVO3DPolicy)
+    ids = agents_of(scenarios.circle(16), E.RVO3DPolicy)
     ids[0].id = 1
     for bad in ({0: path}, {0: other}, {0: turn}, {0: ids}, {0: eps[12]}, {3: eps[6]}):
         with pytest.raises(ValueError):
@@ -124,16 +120,16 @@ def test_what_the_queue_and_the_planner_attributes_refuse(mods):
     mixed = [E.Agent(start_pos=list(sc['start'][i]), goal_pos=list(sc['goal'][i]), vel=[0.0, 0.0, 0.0], radius=0.5, pref_speed=1.0,
                      policy=E.SCAPolicy if i % 2 else E.RVO3DPolicy, id=i) for i in range(16)]
     mixed[1].turning_radius = 2.0                                                                # (two classes: the attributes go per agent)
-    batch = scenes.SceneBatch([mixed, _agents(E, sc, E.RVO3DPolicy)], [], device_tracker=True)
+    batch = scenes.SceneBatch([mixed, agents_of(sc, E.RVO3DPolicy)], [], device_tracker=True)
     batch.step()
     before = batch.solver.get_state()
     with pytest.raises(ValueError):
-        batch.restart({1: _agents(E, sc, E.SCAPolicy)})                                          # untracked rows become tracked
+        batch.restart({1: agents_of(sc, E.SCAPolicy)})                                          # untracked rows become tracked
     with pytest.raises(ValueError):
-        batch.restart({0: _agents(E, sc, E.RVO3DPolicy)})                                        # tracked rows become untracked
+        batch.restart({0: agents_of(sc, E.RVO3DPolicy)})                                        # tracked rows become untracked
     for k, v in batch.solver.get_state().items():
         assert np.array_equal(before[k], v), k
-    batch.restart({1: _agents(E, sc, E.ORCA3DPolicy)})                                           # untracked stays untracked: taken
+    batch.restart({1: agents_of(sc, E.ORCA3DPolicy)})                                           # untracked stays untracked: taken
     assert batch.steps.tolist() == [1, 0]
     batch.close()
     eps, obstacles = _queue(E, scenarios)

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from golden_util import fixture_agent_params, fixture_params, fixture_tracker_agent_params, static_inputs
-from scene_util import load_any
+from scene_util import load_any, oracle_scene_runs, random_scenes
 
 pytestmark = pytest.mark.gpu
 
@@ -217,71 +217,6 @@ def test_560_scenes_packed_query_and_strided_forest(S):
     b.sol.close()
 
 
-SIZES = [1, 2, 3, 9, 10, 11, 20, 21, 257, 1023, 1024, 1025, 1536]
-
-
-def _random_scenes(S):
-    """64 scenes: every size of SIZES once, the rest drawn from the small ones; mixed policies; six shared obstacles"""
-    from sca_amd import scenarios
-    rng = np.random.default_rng(2024)
-    sizes = SIZES + [int(x) for x in rng.choice(SIZES[:9], 64 - len(SIZES))]
-    obs_pos = np.round(rng.uniform(-8, 8, (6, 3)) + [0, 0, 12.0], 2)
-    obs_radius = np.full(6, 1.0)
-    scenes = []
-    for s, size in enumerate(sizes):
-        if size >= 257:
-            sc = scenarios.circle(size) if s % 2 else scenarios.random_cube(size, seed=s)
-        else:
-            # small scenes: a few metres apart, so that neighbours, obstacles and collisions happen within the six steps
-            pos = np.round(rng.uniform(-6, 6, (size, 3)) * [1, 1, 0.5] + [0, 0, 12.0], 2)
-            goal = np.round(-pos * [1, 1, 0] + [0, 0, 1] * pos + rng.uniform(-1, 1, (size, 3)), 2)
-            start = np.zeros((size, 6)); start[:, :3] = pos
-            start[:, 3] = np.arctan2(goal[:, 1] - pos[:, 1], goal[:, 0] - pos[:, 0])
-            g6 = np.zeros((size, 6)); g6[:, :3] = goal
-            sc = dict(start=start, goal=g6)
-        policy = rng.integers(0, 6, size).astype(np.uint8) if s % 3 else np.full(size, s % 6, np.uint8)
-        scenes.append(dict(start=sc['start'], goal=sc['goal'], policy=policy, zaxis=S.zaxis_flags(sc['start'], sc['goal']),
-                           mrd=scenarios.max_run_dist(sc['start'], sc['goal']), n=size))
-    return scenes, sizes, obs_pos, obs_radius
-
-
-_ORACLE_RUNS = {}
-
-
-def oracle_scene_runs(oracle, key, scenes, obstacle_sets, steps=6, stop_when_done=False):
-    """Every scene alone through the oracle (policy_step / env_update / Tracker), `steps` free-running steps, made once per `key` and shared by
-    the K1 forms that are compared with it.  Per scene: `steps` (one dict per step: p = policy_step's result, active = the tracked agents it
-    served, and the state after the step -- or, with stop_when_done, None from the step on at which every agent was done: the reference's
-    `while not env.step()` has stopped by then), `last` (the state the scene ended on), ext and the tracker's re-plan counts."""
-    if key in _ORACLE_RUNS:
-        return _ORACLE_RUNS[key]
-    out = []
-    for sc, (obs_pos, obs_radius) in zip(scenes, obstacle_sets):
-        m = sc['n']
-        r = dict(pos=sc['start'][:, :3].copy(), vel=np.zeros((m, 3), np.float32), head=sc['start'][:, 3:6].copy(), flags=np.zeros(m, np.uint8),
-                 td=np.zeros(m), sn=np.zeros(m, np.int32), perm=np.arange(m, dtype=np.int32))
-        ext = np.isin(sc['policy'], (0, 5))
-        tr = oracle.Tracker(np.ascontiguousarray(sc['goal'][:, :3]), sc['goal'][:, 3:6], np.ones(m), sc['zaxis'])
-        radius, ps, goal = np.full(m, 0.5), np.ones(m), np.ascontiguousarray(sc['goal'][:, :3])
-        rows = []
-        for t in range(steps):
-            if stop_when_done and (r['flags'] & 7).all():
-                rows.append(None)
-                continue
-            active = ((r['flags'] & 7) == 0) & ext
-            vp = tr.vpref(r['pos'], r['vel'], r['head'], active.astype(np.uint8), nthreads=16)
-            p = oracle.policy_step(r['pos'], r['vel'], r['head'], radius, ps, r['flags'], goal, sc['policy'], sc['zaxis'], vp, ext.astype(np.uint8),
-                                   r['perm'], obs_pos, obs_radius, nthreads=16)
-            tr.note_neighbors(p['nbr_valid'], p['nbr_n'], p['nbr_dsq'])
-            u = oracle.env_update(r['pos'], r['vel'], r['head'], radius, p['flags'], goal, p['action'], r['td'], sc['mrd'], r['sn'], obs_pos, obs_radius)
-            r = dict(pos=u['pos'], vel=u['vel'], head=u['heading'], flags=u['flags'], td=u['total_dist'], sn=u['step_num'], perm=p['perm'])
-            rows.append(dict(r, p=p, active=active))
-        out.append(dict(steps=rows, last=r, ext=ext, replans=tr.replans()))
-        tr.close()
-    _ORACLE_RUNS[key] = out
-    return out
-
-
 @pytest.mark.parametrize('packed', [0, 1])
 def test_random_scenes_against_the_oracle(S, oracle, packed, monkeypatch):
     """64 seeded scenes of sizes at the leaf boundary, the block instances' edges and the cap, mixed policies, shared obstacles, 6 free-running
@@ -289,7 +224,7 @@ def test_random_scenes_against_the_oracle(S, oracle, packed, monkeypatch):
     the 6884 agents are a packed pass by default (k_neighbors_kd4_scenes: the scenes of 1, 2 and 3 agents share their wavefront with other
     scenes' groups), SCA_K1_PACKED=0 sends them through k_neighbors_kd_scenes."""
     monkeypatch.setenv('SCA_K1_PACKED', str(packed))                 # read by sca_create
-    scenes, sizes, obs_pos, obs_radius = _random_scenes(S)
+    scenes, sizes, obs_pos, obs_radius = random_scenes(S)
     off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
     n = int(off[-1])
     cat = lambda key: np.concatenate([sc[key] for sc in scenes])
