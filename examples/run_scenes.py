@@ -19,6 +19,11 @@ one metrics row per scene -- what a loop over the reference's run_example/run_*.
                                                        # with --map <binvox> the exp3 search among the map's spheres
     python examples/run_scenes.py --seeds 8 --slots 16 --harvest      # the streamed queue with the finished scenes handed over by the step that
                                                        # finishes them (sca_scene_harvest_enable): the same rows, one synchronisation a step
+    python examples/run_scenes.py --sweep neighborDist=5,10,15 --seeds 4 --slots 16    # a PARAMETER TABLE as one queue: every scenario at
+                                                       # every value of one Agent attribute (neighborDist, maxNeighbors, timeStep, timeHorizon,
+                                                       # maxSpeed, max_heading_change, dt_nominal, turning_radius); a slot takes the episode's
+                                                       # own attributes with the restart (run_episodes(attributes=True)); one row per episode,
+                                                       # the value in the row
 """
 import argparse
 import os
@@ -30,6 +35,9 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sca_amd import env as E, metrics, read_map, scenarios            # noqa: E402
 from sca_amd.scenes import SceneBatch, run_episodes                   # noqa: E402
+
+SWEEPABLE = {'neighborDist': float, 'maxNeighbors': int, 'timeStep': float, 'timeHorizon': float, 'maxSpeed': float, 'max_heading_change': float,
+             'dt_nominal': float, 'turning_radius': float}        # the Agent attributes a slot takes with a restart (agent.py:24-41)
 
 POLICIES = {'sca': E.SCAPolicy, 'rvo': E.RVO3DPolicy, 'srvo': E.SRVO3DPolicy, 'orca': E.ORCA3DPolicy, 'orca-lp': E.ORCA3DPolicyOfficial,
             'rvo-dubins': E.RVO3dDubinsPolicy}
@@ -70,6 +78,8 @@ def main():
     ap.add_argument('--capacity', default=None, help="with --slots: 'max' makes every slot hold up to the largest episode, so a slot takes any "
                                                      'episode of the queue; a number is the capacity of every slot')
     ap.add_argument('--harvest', action='store_true', help='with --slots: finished scenes hand over their result with the step (run_episodes(harvest=True))')
+    ap.add_argument('--sweep', default=None, help='with --slots: NAME=v1,v2,...: every scenario once per value of this Agent attribute (%s), '
+                                                  'all of them one queue' % ', '.join(SWEEPABLE))
     ap.add_argument('--log-dir', default=None, help='write one folder per episode here: env_cfg.json + trajs.npz (the first --max-steps steps of each)')
     args = ap.parse_args()
     if args.map and not (args.slots and args.obstacles):
@@ -78,6 +88,14 @@ def main():
         ap.error('--capacity is about the slots of a streamed queue: give --slots')
     if args.harvest and not args.slots:
         ap.error('--harvest is about the streamed queue: give --slots')
+    sweep_name, sweep_values = None, [None]
+    if args.sweep:
+        if not args.slots:
+            ap.error('--sweep streams a parameter table as one queue: give --slots')
+        sweep_name, _, vals = args.sweep.partition('=')
+        if sweep_name not in SWEEPABLE or not vals:
+            ap.error('--sweep NAME=v1,v2,... with NAME one of ' + ', '.join(SWEEPABLE))
+        sweep_values = [SWEEPABLE[sweep_name](v) for v in vals.split(',')]
     counts = [int(v) for v in args.sizes.split(',')] if args.sizes else [args.agents]
     many = len(counts) > 1
     if many and not args.slots:
@@ -105,6 +123,18 @@ def main():
             names.append((pname, 'exp3'))
             scenes.append(build_agents(scenarios.spawn_n_drones(16), pol))
             obstacles.append(read_map.read_obstacle(center=(35, 30), environ='exp3', obs_path=args.map))
+    if sweep_name:                                                    # the table once per value: fresh Agent objects, the value on every agent
+        base_names, base_scenes, base_obstacles = names, scenes, obstacles
+        names, scenes, obstacles = [], [], []
+        for v in sweep_values:
+            for (pname, what), agents, obs in zip(base_names, base_scenes, base_obstacles):
+                fresh = [E.Agent(start_pos=list(a.initial_pos), goal_pos=list(a.goal_pos), vel=[0.0, 0.0, 0.0], radius=a.radius, pref_speed=a.pref_speed,
+                                 policy=type(a.policy), id=a.id) for a in agents]
+                for a in fresh:
+                    setattr(a, sweep_name, v)
+                names.append((pname, '%s %s=%g' % (what, sweep_name, v)))
+                scenes.append(fresh)
+                obstacles.append(obs)
     def folder(k):
         return os.path.join(args.log_dir, '%03d_%s_%s' % (k, names[k][0], names[k][1].replace(' ', '_')))
 
@@ -113,7 +143,7 @@ def main():
 
         def row(r):
             pname, what = names[r['episode']]
-            print('%-10s %-20s slot %3d steps %5d  ' % (pname, what, r['slot'], r['steps']) +
+            print('%-10s %-*s slot %3d steps %5d  ' % (pname, 40 if sweep_name else 20, what, r['slot'], r['steps']) +
                   '  '.join('%s %.4g' % (k, r['metrics'][k]) for k in ('SuccessRate', 'ExtraTime', 'ExtraDistance', 'AverageSpeed')), flush=True)
             if args.log_dir:
                 metrics.write_log_files(folder(r['episode']), scenes[r['episode']], r['trajectories'], r['info'], xlsx=False)
@@ -121,7 +151,7 @@ def main():
                     print('    (the log holds the first %d steps: %d more did not fit --max-steps rows)' % (r['trajectories'].shape[1], r['rows_dropped']))
         run_episodes(scenes, args.slots, device_tracker=True, on_done=row, max_steps=args.max_steps, stats=stats,
                      history_rows=args.max_steps if args.log_dir else 0, capacities=capacities, harvest=args.harvest,
-                     episode_obstacles=obstacles if args.obstacles else None)
+                     episode_obstacles=obstacles if args.obstacles else None, attributes=bool(sweep_name))
         print('%d episodes through %d slots: %d batch steps, mean live fraction %.2f, %.2f s' %
               (len(scenes), args.slots, stats['batch_steps'], stats['live_fraction'], time.time() - t0))
         return

@@ -223,8 +223,8 @@ int sca_set_scene_obstacles(sca_ctx *ctx, int nscenes, const int32_t *obs_offset
  *              one is enabled), the scene's slice of the kd permutation (identity), its neighbour lists, the tracker's records and
  *              goal_heading, and the scene's counters: steps[s] = 0, active[s] = n_s -- sca_env_step / sca_step_host / sca_active_count
  *              count the scene again, and a batch that had reached 0 comes back to life.
- *   kept       the slot's agent count, its per-agent solver attributes (sca_set_agent_params) and its per-agent tracker attributes; every
- *              array passed as NULL (vel: zero).  The obstacles the scene meets stay too -- unless the restart brings the episode's own
+ *   kept       the slot's agent count, its per-agent solver attributes (sca_set_agent_params) and its per-agent tracker attributes --
+ *              unless the restart brings the episode's own (sca_restart_scenes_attrs, below); every array passed as NULL (vel: zero).  The obstacles the scene meets stay too -- unless the restart brings the episode's own
  *              (sca_restart_scenes_obstacles, below).
  *   refusals   SCA_ERR_STATE: no scenes, no state yet, between a policy pass and its env update.  SCA_ERR_ARG: count <= 0 or scene_ids
  *              NULL, an id outside 0 .. nscenes-1, a repeated id, pos or heading NULL, any number that is not finite, a policy above
@@ -324,6 +324,47 @@ int sca_restart_scenes_obstacles(sca_ctx *ctx, int count, const int32_t *scene_i
                                  const double *radius, const double *pref_speed, const double *goal /*T*3*/, const uint8_t *policy,
                                  const uint8_t *zaxis, const double *max_run_dist,      /* each T, each nullable: keep the slot's */
                                  const double *goal_heading /*T*3, nullable: keep the slot's*/);
+
+/* A restarted slot takes the episode's own ATTRIBUTES: the solver attributes the reference keeps on every Agent (agent.py:24-41,
+ * sca_set_agent_params) and the planner's (turning_radius, pitchlims; sca_device_tracker_set_agent_params), so that a parameter study --
+ * a sweep of neighbour distance, neighbour count, time horizon or turning radius across seeds -- streams through one set of slots.
+ * Detect the feature by the symbol (sca_version() is unchanged).
+ *   sca_restart_scenes_attrs   sca_restart_scenes_obstacles plus a descriptor.  attrs == NULL: exactly sca_restart_scenes_obstacles -- the
+ *              slot keeps its attributes, and the tracked <-> untracked refusal stays.  attrs != NULL: the named scenes' occupied rows take
+ *              the arrays' values, T rows each, packed like pos.  A NULL array inside the struct means the value a context alone would
+ *              have for every named row -- sca_create's sca_params value, sca_device_tracker_enable's value -- NOT what the row had before
+ *              (as in sca_set_agent_params).  Planner entries of untracked rows are ignored.  A policy that moves an agent between tracked
+ *              and untracked is accepted: the tracker's classes are recomputed after every such call over the occupied tracked rows.
+ *              The scene contract extends: after the call a named scene is bit for bit a context that holds that episode alone after
+ *              sca_set_agents + sca_set_agent_params(those arrays) + sca_set_obstacles + sca_set_state + sca_device_tracker_enable +
+ *              sca_device_tracker_set_agent_params(those arrays) -- state, float32 action rows, neighbour lists with their distSq,
+ *              diagnostics, status, permutation, tracker records, plans and re-plan counts, the rows of the log per scene and the harvest
+ *              -- and no other scene can tell the call happened.  Vacant rows keep their attributes.
+ *   struct_bytes   sizeof(sca_restart_attrs) as the caller compiled it: members behind it read as NULL.  reserved: 0.
+ *   refusals   those of sca_restart_scenes_obstacles, and SCA_ERR_ARG for a struct_bytes below the two leading integers, above the
+ *              library's struct or cutting a pointer in two; reserved != 0; planner arrays while no device tracker is enabled; a row whose
+ *              solver attributes break sca_set_agent_params' rules or, for a tracked row, whose planner attributes break
+ *              sca_device_tracker_set_agent_params' (the message names the packed row).  A refused call has changed nothing.
+ *   cost       one kernel launch and one stream synchronisation however many scenes are named.  The first call that brings attributes
+ *              into a context without per-agent arrays allocates them and fills every row with the context's own values, from which the
+ *              rows of the other scenes compute the bits they computed before.  One more small copy (the class bytes, one per agent)
+ *              where the call takes the tracker back from the per-agent form to classes. */
+typedef struct sca_restart_attrs {
+    int32_t struct_bytes;            /* sizeof as the caller compiled it */
+    int32_t reserved;                /* 0 */
+    /* each T rows packed like pos; NULL = the CONTEXT's sca_params value for every named row */
+    const double *neighbor_dist; const int32_t *max_neighbors; const double *time_step, *time_horizon,
+                 *max_speed, *max_heading_change, *dt_nominal;
+    /* each T rows; NULL = sca_device_tracker_enable's value for every named row; ignored for untracked rows */
+    const double *turning_radius, *pitch_lo, *pitch_hi;
+} sca_restart_attrs;
+int sca_restart_scenes_attrs(sca_ctx *ctx, int count, const int32_t *scene_ids /*count*/, const int32_t *sizes /*count, nullable: capacities*/,
+                             const int32_t *obs_counts /*count, nullable*/, const double *obs_pos, const double *obs_radius,
+                             const sca_restart_attrs *attrs /*nullable: the slots keep their attributes*/,
+                             const double *pos /*T*3*/, const float *vel /*T*3, nullable: zero*/, const double *heading /*T*3*/,
+                             const double *radius, const double *pref_speed, const double *goal /*T*3*/, const uint8_t *policy,
+                             const uint8_t *zaxis, const double *max_run_dist,      /* each T, each nullable: keep the slot's */
+                             const double *goal_heading /*T*3, nullable: keep the slot's*/);
 
 /* A trajectory log per scene = every episode's Agent.history_info.  Row r of scene s is the scene's r-th own step (r = steps[s] - 1 while
  * that step runs), written only for steps the scene was live at their beginning, so a finished scene gains no row while the others run on,

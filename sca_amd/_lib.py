@@ -50,6 +50,13 @@ class SceneHarvest(C.Structure):
                 ('summary', C.POINTER(SceneSummary)), ('pos', dp), ('vel', fp), ('heading', dp), ('flags', bp), ('total_dist', dp), ('step_num', ip)]
 
 
+class RestartAttrs(C.Structure):
+    """sca_restart_attrs: the attributes a restarted scene's episode brings (sca_restart_scenes_attrs); a NULL array = the context's value"""
+    _fields_ = [('struct_bytes', C.c_int32), ('reserved', C.c_int32), ('neighbor_dist', dp), ('max_neighbors', ip), ('time_step', dp),
+                ('time_horizon', dp), ('max_speed', dp), ('max_heading_change', dp), ('dt_nominal', dp), ('turning_radius', dp), ('pitch_lo', dp),
+                ('pitch_hi', dp)]
+
+
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against include/sca_hip.h
 SIGNATURES = {
     'sca_default_params': (None, [C.c_void_p]),                   # (version-100 form: 56 bytes)
@@ -78,6 +85,7 @@ SIGNATURES = {
     'sca_set_scene_obstacle_slots': (C.c_int, [C.c_void_p, C.c_int, ip, ip, dp, dp]),
     'sca_get_scene_obstacle_counts': (C.c_int, [C.c_void_p, ip, ip]),
     'sca_restart_scenes_obstacles': (C.c_int, [C.c_void_p, C.c_int, ip, ip, ip, dp, dp, dp, fp, dp, dp, dp, dp, bp, bp, dp, dp]),
+    'sca_restart_scenes_attrs': (C.c_int, [C.c_void_p, C.c_int, ip, ip, ip, dp, dp, C.POINTER(RestartAttrs), dp, fp, dp, dp, dp, dp, bp, bp, dp, dp]),
     'sca_scene_history_enable': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_scene_history_rows': (C.c_int, [C.c_void_p, ip, ip]),
     'sca_get_scene_history': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, fp]),

@@ -325,6 +325,11 @@ struct sca_ctx {
     } scenes;
     std::vector<uint8_t> h_policy;      // [n] the agents' policies as they stand (sca_set_agents, sca_restart_scenes)
     sca_dubins::AgentTrack *trk_init = nullptr;   // one default-constructed tracker record on the device (sca_device_tracker_enable)
+    // a restart that brings attributes (sca_restart_scenes_attrs): host mirrors of the planner's per-row arrays and the class table
+    std::vector<TrackTriple> h_trk_trip;    // [n] (turning radius, pitch_lo, pitch_hi) per row as the device holds them; empty: one value per context
+    std::vector<uint8_t> h_trk_cls;         // [n] trk_cls as the device holds it
+    ClassTable trk_table;                   // the classes in use over the occupied tracked rows (scene_class_table)
+    bool trk_attr_on = false;               // the table governs trk_classes / trk_many / the view (since the first restart that brought planner attributes)
 };
 
 #define CHK(ctx, call)                                                                         \
@@ -608,6 +613,7 @@ static int tracker_free(sca_ctx *c) {
     if (c->trk_phi_pa) { (void)hipFree(c->trk_phi_pa); c->trk_phi_pa = nullptr; }
     c->trk_many = false;
     c->trk_classes.clear();
+    c->trk_attr_on = false; c->h_trk_trip.clear(); c->h_trk_cls.clear(); c->trk_table = ClassTable{};
     if (c->trk_stream) { (void)hipStreamSynchronize(c->trk_stream); (void)hipStreamDestroy(c->trk_stream); c->trk_stream = nullptr; }
     if (c->trk_fork) { (void)hipEventDestroy(c->trk_fork); c->trk_fork = nullptr; }
     if (c->trk_join) { (void)hipEventDestroy(c->trk_join); c->trk_join = nullptr; }
@@ -687,6 +693,7 @@ int sca_device_tracker_enable(sca_ctx *c, const double *goal_heading, double tur
 // PER-AGENT form -- every re-plan gets a wavefront of its own (k_replan_group<64> / k_track_group at any count), which loads ITS agent's
 // three values into scalar registers; slower than the lane-per-plan forms for large counts, never refused.
 constexpr size_t TRK_MAX_CLASSES = 16;
+static_assert(TRK_MAX_CLASSES == (size_t)TRK_CLASS_CAP, "scene_class_table deals the classes sca_device_tracker_set_agent_params deals");
 int sca_device_tracker_set_agent_params(sca_ctx *c, int n, const double *turning_radius, const double *pitch_lo, const double *pitch_hi) {
     API_ENTER(c);
     if (!c->trk_on) { c->err = "sca_device_tracker_enable first"; return SCA_ERR_STATE; }
@@ -697,6 +704,7 @@ int sca_device_tracker_set_agent_params(sca_ctx *c, int n, const double *turning
     c->trk_classes.clear();
     c->trk_many = false;
     c->trk_view.R_pa = nullptr; c->trk_view.plo_pa = nullptr; c->trk_view.phi_pa = nullptr; c->trk_view.cls = nullptr; c->trk_view.class_id = 0;
+    c->trk_attr_on = false; c->h_trk_trip.clear(); c->h_trk_cls.clear(); c->trk_table = ClassTable{};   // (a later attribute restart starts from this call's values)
     if (!turning_radius && !pitch_lo && !pitch_hi) return 0;
     ARG(c, n == c->n);
     // tracked = by POLICY, as the kernels decide it (tracker_owns), not by the v_pref mode of the moment (sca_set_vpref may change that later)
@@ -724,6 +732,8 @@ int sca_device_tracker_set_agent_params(sca_ctx *c, int n, const double *turning
         cls[i] = (uint8_t)k;
     }
     if (!c->trk_R_pa) { CHK(c, hipMalloc((void **)&c->trk_R_pa, sizeof(double) * (size_t)c->max_n)); CHK(c, hipMalloc((void **)&c->trk_cls, (size_t)c->max_n)); }
+    c->h_trk_trip.resize((size_t)n);
+    for (int i = 0; i < n; i++) c->h_trk_trip[i] = TrackTriple{R[i], LO[i], HI[i]};
     CHK(c, hipMemcpy(c->trk_R_pa, R.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
     c->trk_view.R_pa = c->trk_R_pa;
     if (many) {
@@ -1611,11 +1621,13 @@ int sca_get_scene_state(sca_ctx *c, int32_t *active, int32_t *steps) {
 static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const int32_t *sizes, const double *pos, const float *vel, const double *heading,
                           const double *radius, const double *pref_speed, const double *goal, const uint8_t *policy, const uint8_t *zaxis,
                           const double *max_run_dist, const double *goal_heading,
-                          const int32_t *obs_counts = nullptr, const double *obs_pos = nullptr, const double *obs_radius = nullptr) {
+                          const int32_t *obs_counts = nullptr, const double *obs_pos = nullptr, const double *obs_radius = nullptr,
+                          const sca_restart_attrs *attrs = nullptr) {
     RestartArgs A{count, scene_ids, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading};
     A.sizes = sizes;
+    // (with `attrs` a policy may move an agent between tracked and untracked: the classes are recomputed below, not cut by policy)
     const RestartCtx X{c->scenes.on ? c->scenes.v.nscenes : 0, c->scenes.on ? c->scenes.h_off.data() : nullptr, c->state_set, c->scenes.begun, c->trk_on,
-                       c->paths_on, c->trk_on && c->trk_view.R_pa != nullptr, c->h_policy.data()};
+                       c->paths_on, !attrs && c->trk_on && c->trk_view.R_pa != nullptr, c->h_policy.data()};
     const RestartCheck k = scene_restart_check(X, A);
     if (k.fault != RESTART_OK) {
         const std::string at = std::to_string(k.entry);
@@ -1652,11 +1664,30 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
         }
         return restart_obstacles_error_code(ko.fault);
     }
+    RestartAttrs RA;                                                   // every member NULL without `attrs`
+    if (attrs) {
+        const AttrDefaults D{c->P_ctx.neighbor_dist, c->P_ctx.time_step, c->P_ctx.time_horizon, c->P_ctx.max_speed, c->P_ctx.max_heading_change, c->P_ctx.dt_nominal,
+                             c->P_ctx.max_neighbors, c->trk_enable_vals[0], c->trk_enable_vals[1], c->trk_enable_vals[2]};
+        const RestartAttrCheck ka = restart_attrs_check(X, A, attrs, D, &RA);
+        if (ka.fault != RESTART_ATTR_OK) {
+            const std::string at = std::to_string(ka.entry);
+            switch (ka.fault) {
+            case RESTART_ATTR_STRUCT: c->err = "sca_restart_scenes_attrs: attrs->struct_bytes = " + std::to_string(attrs->struct_bytes) + " is not a size of sca_restart_attrs (" +
+                                               std::to_string(RESTART_ATTR_HEAD_BYTES) + " .. " + std::to_string(sizeof(sca_restart_attrs)) + ", whole pointers)"; break;
+            case RESTART_ATTR_RESERVED: c->err = "sca_restart_scenes_attrs: attrs->reserved must be 0"; break;
+            case RESTART_ATTR_NO_TRACKER: c->err = "sca_restart_scenes_attrs: turning_radius / pitch_lo / pitch_hi without a device tracker (sca_device_tracker_enable)"; break;
+            case RESTART_ATTR_SOLVER: c->err = "sca_restart_scenes_attrs: row " + at + " has an attribute out of range (see sca_params)"; break;
+            default: c->err = "sca_restart_scenes_attrs: row " + at + " has a turning radius / pitch limits out of range (R > 0, pitch_lo < pitch_hi)";
+            }
+            return restart_attrs_error_code(ka.fault);
+        }
+    }
     const int T = k.total;
     const RestartLayout L = scene_restart_layout(c->max_n);
     const size_t sizes_end = (size_t)L.total + sizeof(int32_t) * (size_t)c->max_n;  // behind the layout's sections: the named scenes' new sizes ...
     const RestartObsLayout OL = restart_obstacles_layout((int64_t)sizes_end, c->max_n, c->max_m);      // ... and behind those the obstacle sections
-    const size_t blk_bytes = (size_t)OL.total;
+    const RestartAttrLayout AL = restart_attrs_layout(OL.total, c->max_n);                             // ... and behind those the attribute sections
+    const size_t blk_bytes = (size_t)AL.total;
     if (!c->scenes.rs_host) {                                                    // mapped and coherent, as the host state block is: the kernel reads it in place
         CHK(c, hipHostMalloc((void **)&c->scenes.rs_host, blk_bytes, hipHostMallocMapped | hipHostMallocCoherent));
         std::memset(c->scenes.rs_host, 0, blk_bytes);
@@ -1707,6 +1738,109 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
             at += ms;
         }
     }
+    // ---- the episodes' attributes (sca_restart_scenes_attrs) ----
+    // Solver attributes travel when the call names any, or when the context carries per-agent arrays already (a NULL array then means the
+    // context's value, which the rows must take); planner attributes likewise, with a tracker.  A context without per-agent arrays whose
+    // call names none has nothing to write: every row computes from Params / the view's scalars, which ARE the context's values.
+    const int n_all = c->n;
+    const bool send_solver = attrs && (RA.solver() || c->ap_dev);
+    const bool send_planner = attrs && c->trk_on && (RA.planner() || c->trk_attr_on || c->trk_view.R_pa);
+    std::vector<AgentPar> ap_fill;                                     // first use: every row with the context's own values (alive until the synchronisation)
+    std::vector<double> nd_fill, trk_fill[3];
+    bool ap_first = false, cls_whole = false;
+    double env_nd = 0, env_ms = 0, env_dt = 0;
+    if (send_solver) {
+        if (!c->ap_dev) {
+            // From here on every agent of the context reads d.ap[a] instead of Params: the rows of the scenes that are not named get the
+            // record Params stands for -- range_sq and cos_heading_thr as sca_create derived them -- and so compute the bits they computed
+            // before.  Enqueued in front of the launch, and d.ap / nd_per_agent point at the arrays only behind the fill.
+            AgentPar a0;
+            a0.neighbor_dist = c->P_ctx.neighbor_dist; a0.time_step = c->P_ctx.time_step; a0.time_horizon = c->P_ctx.time_horizon; a0.max_speed = c->P_ctx.max_speed;
+            a0.cos_heading_thr = c->P_ctx.cos_heading_thr; a0.dt_nominal = c->P_ctx.dt_nominal; a0.max_neighbors = c->P_ctx.max_neighbors; a0.pad = 0;
+            a0.range_sq = sca_gm::g_pow2(a0.neighbor_dist);
+            ap_fill.assign((size_t)c->max_n, a0); nd_fill.assign((size_t)c->max_n, a0.neighbor_dist);
+            CHK(c, hipMalloc((void **)&c->ap_dev, sizeof(AgentPar) * (size_t)c->max_n));
+            CHK(c, hipMalloc((void **)&c->ap_nd, sizeof(double) * (size_t)c->max_n));
+            CHK(c, hipMemcpyAsync(c->ap_dev, ap_fill.data(), sizeof(AgentPar) * (size_t)c->max_n, hipMemcpyHostToDevice, c->stream));
+            CHK(c, hipMemcpyAsync(c->ap_nd, nd_fill.data(), sizeof(double) * (size_t)c->max_n, hipMemcpyHostToDevice, c->stream));
+            ap_first = true;
+        }
+        AgentPar *par = (AgentPar *)(b + AL.off[RA_PAR]);
+        double *ndv = (double *)(b + AL.off[RA_ND]);
+        std::vector<std::pair<double, double>> thr_cache;              // (max_heading_change, its cosine threshold): few distinct values
+        for (int r = 0; r < T; r++) {                                  // the derived fields exactly as sca_set_agent_params derives them
+            AgentPar a;
+            a.neighbor_dist = RA.neighbor_dist ? RA.neighbor_dist[r] : c->P_ctx.neighbor_dist;
+            a.time_step = RA.time_step ? RA.time_step[r] : c->P_ctx.time_step;
+            a.time_horizon = RA.time_horizon ? RA.time_horizon[r] : c->P_ctx.time_horizon;
+            a.max_speed = RA.max_speed ? RA.max_speed[r] : c->P_ctx.max_speed;
+            a.dt_nominal = RA.dt_nominal ? RA.dt_nominal[r] : c->P_ctx.dt_nominal;
+            a.max_neighbors = RA.max_neighbors ? RA.max_neighbors[r] : c->P_ctx.max_neighbors;
+            a.pad = 0;
+            a.range_sq = sca_gm::g_pow2(a.neighbor_dist);
+            a.cos_heading_thr = c->P_ctx.cos_heading_thr;
+            if (RA.max_heading_change) {
+                const double mhc = RA.max_heading_change[r];
+                bool hit = false;
+                for (auto &e : thr_cache) if (e.first == mhc) { a.cos_heading_thr = e.second; hit = true; break; }
+                if (!hit) { a.cos_heading_thr = cos_threshold(mhc); thr_cache.push_back({mhc, a.cos_heading_thr}); }
+            }
+            par[r] = a; ndv[r] = a.neighbor_dist;
+            env_nd = std::max(env_nd, a.neighbor_dist); env_ms = std::max(env_ms, a.max_speed); env_dt = std::max(env_dt, a.dt_nominal);
+        }
+        has |= RESTART_HAS_ATTRS;
+    }
+    // the planner's per-row triples and the classes: worked out on copies, which replace the context's behind the synchronisation
+    std::vector<TrackTriple> trip_new;
+    std::vector<uint8_t> cls_new;
+    ClassTable table_new = c->trk_table;
+    ClassUpdate cu{0, false, false};
+    const bool table_on = send_planner || (c->trk_on && c->trk_attr_on);         // (a call without `attrs` still changes which rows are occupied)
+    if (table_on) {
+        const TrackTriple def{c->trk_enable_vals[0], c->trk_enable_vals[1], c->trk_enable_vals[2]};
+        trip_new = c->h_trk_trip; cls_new = c->h_trk_cls;
+        trip_new.resize((size_t)n_all, def); cls_new.resize((size_t)n_all, 0);
+        std::vector<uint8_t> pol_after = c->h_policy, travels((size_t)n_all, 0);
+        std::vector<int32_t> size_after = c->scenes.h_size;
+        double *trip = (double *)(b + AL.off[RA_TRIPLE]);
+        for (int e = 0; e < count; e++) {
+            size_after[scene_ids[e]] = new_size[e];
+            for (int a = off[scene_ids[e]], r = start[e]; a < off[scene_ids[e]] + new_size[e]; a++, r++) {
+                pol_after[a] = pol[r];
+                if (!send_planner) continue;
+                trip_new[a] = TrackTriple{RA.turning_radius ? RA.turning_radius[r] : def.R, RA.pitch_lo ? RA.pitch_lo[r] : def.lo, RA.pitch_hi ? RA.pitch_hi[r] : def.hi};
+                trip[3 * r] = trip_new[a].R; trip[3 * r + 1] = trip_new[a].lo; trip[3 * r + 2] = trip_new[a].hi;
+                travels[a] = 1;
+            }
+        }
+        if (!c->trk_attr_on) table_new.many = true;                   // first use: whatever classes an earlier call dealt, the table starts afresh
+        cu = scene_class_table(table_new, c->scenes.v.nscenes, off, size_after.data(), pol_after.data(), trip_new.data(), cls_new.data(), travels.data());
+        cls_whole = cu.moved || !c->trk_attr_on;                      // (first use: the device's bytes are an earlier call's, or none)
+        if (send_planner) {
+            uint8_t *cl = b + AL.off[RA_CLASS];
+            for (int e = 0; e < count; e++)
+                for (int a = off[scene_ids[e]], r = start[e]; a < off[scene_ids[e]] + new_size[e]; a++, r++) cl[r] = cls_new[a];
+            has |= RESTART_HAS_PLANNER;
+        }
+        if (!c->trk_attr_on) {
+            // first use: the four per-row arrays exist from here on and are current for EVERY row -- the per-agent form (more classes than
+            // launches are worth) reads them the moment the count passes the cap.  The rows of this call are overwritten by the launch.
+            if (!c->trk_R_pa) { CHK(c, hipMalloc((void **)&c->trk_R_pa, sizeof(double) * (size_t)c->max_n)); CHK(c, hipMalloc((void **)&c->trk_cls, (size_t)c->max_n)); }
+            if (!c->trk_plo_pa) {
+                CHK(c, hipMalloc((void **)&c->trk_plo_pa, sizeof(double) * (size_t)c->max_n));
+                CHK(c, hipMalloc((void **)&c->trk_phi_pa, sizeof(double) * (size_t)c->max_n));
+            }
+            for (auto &v : trk_fill) v.resize((size_t)n_all);
+            for (int a = 0; a < n_all; a++) {
+                const TrackTriple &x = trip_new[a];
+                trk_fill[0][a] = x.R; trk_fill[1][a] = x.lo; trk_fill[2][a] = x.hi;
+            }
+            CHK(c, hipMemcpyAsync(c->trk_R_pa, trk_fill[0].data(), sizeof(double) * (size_t)n_all, hipMemcpyHostToDevice, c->stream));
+            CHK(c, hipMemcpyAsync(c->trk_plo_pa, trk_fill[1].data(), sizeof(double) * (size_t)n_all, hipMemcpyHostToDevice, c->stream));
+            CHK(c, hipMemcpyAsync(c->trk_phi_pa, trk_fill[2].data(), sizeof(double) * (size_t)n_all, hipMemcpyHostToDevice, c->stream));
+        }
+    }
+    RestartAttrDev at_dev{c->ap_dev, c->ap_nd, c->trk_R_pa, c->trk_plo_pa, c->trk_phi_pa, c->trk_cls};
     RestartDev d{};
     d.rec = c->d.rec;
     d.heading = c->d.heading; d.heading_keep = c->scenes.v.heading_keep; d.total_dist = c->d.total_dist; d.goal = c->d.goal;
@@ -1725,8 +1859,11 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
     // pointers are null: restart_obstacles_check has refused every count >= 0, so the kernel returns before it reads them.
     RestartObsDev o{};
     if (c->scenes.obs_on) o = RestartObsDev{c->d.obs, c->d.obs_sorted, c->d.operm, c->d.otree, c->d.owide, (int32_t *)c->scenes.ov.oroot, (int32_t *)c->scenes.ov.oroot + c->scenes.v.nscenes};
-    hipLaunchKernelGGL(k_scene_restart, dim3(count), dim3(RESTART_T), 0, c->stream, d, (const uint8_t *)b, L, has, (const int32_t *)new_size, c->scenes.size, o, OL);
+    hipLaunchKernelGGL(k_scene_restart, dim3(count), dim3(RESTART_T), 0, c->stream, d, (const uint8_t *)b, L, has, (const int32_t *)new_size, c->scenes.size, o, OL, at_dev, AL);
     CHK(c, hipGetLastError());
+    // the classes came back from the per-agent form, or an index moved in a scene that was not named: the whole class array, one byte per
+    // agent, behind the launch (its rows of the named scenes are the bytes the launch wrote) and in front of the call's one synchronisation
+    if (cls_whole) CHK(c, hipMemcpyAsync(c->trk_cls, cls_new.data(), (size_t)n_all, hipMemcpyHostToDevice, c->stream));
     std::vector<int32_t> lp_new;                                       // K3's list: the ORCA3D-LP agents, ascending ids (the block holds the named scenes' policies)
     std::vector<int32_t> size_now = c->scenes.h_size;                  // ... of the rows that are occupied: a vacant row keeps its policy and is in no list
     for (int e = 0; e < count; e++) size_now[scene_ids[e]] = new_size[e];
@@ -1759,6 +1896,39 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
         for (int e = 0; e < count; e++) if (obs_counts[e] >= 0) c->scenes.h_obs_count[scene_ids[e]] = obs_counts[e];
         c->max_obs_radius = std::max(c->max_obs_radius, obs_max_r);    // only grows: a conservative filter (sca_set_scene_obstacles)
     }
+    if (send_solver) {
+        if (ap_first) {
+            c->d.ap = c->ap_dev;
+            if (c->trk_on) c->trk_view.nd_per_agent = c->ap_nd;
+        }
+        // The context's Params are the ENVELOPE of the agents' own while per-agent attributes are in force, and like max_radius,
+        // max_pref_speed and max_obs_radius above the envelope only grows under restarts: with scenes it feeds collide_reach (a
+        // conservative filter of K1's candidate lists and K4's walks) and nothing that reaches a value -- every kernel reads d.ap[a] for
+        // the fields below (agent_params), the grid and SCA_NBR_AUTO's `fits`, which read neighbor_dist, have no scene form.
+        if (env_nd > c->P.neighbor_dist) { c->P.neighbor_dist = env_nd; c->P.range_sq = sca_gm::g_pow2(env_nd); c->grid.inv_cell = grid_inv_cell(env_nd); }
+        c->P.max_speed = std::max(c->P.max_speed, env_ms);
+        c->P.dt_nominal = std::max(c->P.dt_nominal, env_dt);
+    }
+    if (table_on) {
+        c->h_trk_trip.swap(trip_new); c->h_trk_cls.swap(cls_new); c->trk_table = table_new; c->trk_attr_on = true;
+        // the view: the per-agent form beyond the cap; classes (a filter by the class byte, one launch per index in use) for two or more;
+        // one class left: its values in the scalars and no filter (sca_device_tracker_set_agent_params' rule).  R_pa is current for every row.
+        sca_dubins::TrackView &V = c->trk_view;
+        V.R_pa = c->trk_R_pa; V.plo_pa = nullptr; V.phi_pa = nullptr; V.cls = nullptr; V.class_id = 0;
+        V.turning_radius = c->trk_enable_vals[0]; V.pitch_lo = c->trk_enable_vals[1]; V.pitch_hi = c->trk_enable_vals[2];
+        c->trk_classes.clear(); c->trk_many = false;
+        int only = -1;
+        const int used = cu.many ? TRK_CLASS_CAP + 1 : class_table_used(table_new, &only);
+        if (cu.many) { V.plo_pa = c->trk_plo_pa; V.phi_pa = c->trk_phi_pa; c->trk_many = true; }
+        else if (used > 1) {
+            for (int q = 0; q < TRK_CLASS_CAP; q++)
+                if (table_new.users[q] > 0) {
+                    c->trk_classes.resize((size_t)q + 1, std::array<double, 3>{std::nan(""), 0.0, 0.0});   // (an index nobody uses: no launch)
+                    c->trk_classes[q] = {table_new.val[q].R, table_new.val[q].lo, table_new.val[q].hi};
+                }
+            V.cls = c->trk_cls;
+        } else if (used == 1) { V.turning_radius = table_new.val[only].R; V.pitch_lo = table_new.val[only].lo; V.pitch_hi = table_new.val[only].hi; }
+    }
     c->scenes.partial = scenes_any_partial(c->scenes.v.nscenes, off, c->scenes.h_size.data());
     scene_harvest_clear_fresh(c, count, scene_ids);                    // an uncollected harvest of a restarted scene is gone (behind the synchronisation above)
     c->h_pos_valid = false;                                            // (no host mirror of the positions is kept, as in sca_step_host)
@@ -1785,6 +1955,14 @@ int sca_restart_scenes_obstacles(sca_ctx *c, int count, const int32_t *scene_ids
                                  const double *goal_heading) {
     API_ENTER(c);
     return restart_scenes(c, count, scene_ids, sizes, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading, obs_counts, obs_pos, obs_radius);
+}
+int sca_restart_scenes_attrs(sca_ctx *c, int count, const int32_t *scene_ids, const int32_t *sizes, const int32_t *obs_counts, const double *obs_pos,
+                             const double *obs_radius, const sca_restart_attrs *attrs, const double *pos, const float *vel, const double *heading,
+                             const double *radius, const double *pref_speed, const double *goal, const uint8_t *policy, const uint8_t *zaxis,
+                             const double *max_run_dist, const double *goal_heading) {
+    API_ENTER(c);
+    return restart_scenes(c, count, scene_ids, sizes, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading, obs_counts, obs_pos, obs_radius,
+                          attrs);
 }
 int sca_get_scene_sizes(sca_ctx *c, int32_t *size) {
     API_ENTER(c);
@@ -1977,6 +2155,7 @@ static int launch_tracker(sca_ctx *c, bool from_lists, bool in_pass, int &forms)
     // launches once per class of equal values, each with ITS values in the view's scalars; an agent of another class leaves at once
     const int nclass = c->trk_classes.empty() ? 1 : (int)c->trk_classes.size();
     for (int cl = 0; cl < nclass; cl++) {
+        if (!c->trk_classes.empty() && !(c->trk_classes[cl][0] > 0.0)) continue;     // an index no occupied row uses (scene_class_table keeps the others' stable)
         sca_dubins::TrackView V = c->trk_view;
         if (!c->trk_classes.empty()) { V.class_id = cl; V.turning_radius = c->trk_classes[cl][0]; V.pitch_lo = c->trk_classes[cl][1]; V.pitch_hi = c->trk_classes[cl][2]; }
         for (int i = 0; i < R.n; i++) {

@@ -355,6 +355,173 @@ inline RestartObsLayout restart_obstacles_layout(int64_t begin, int max_n, int m
     return L;
 }
 
+// ---- a restart that brings attributes (sca_restart_scenes_attrs) ------------------------------------------------------------------------------------
+// The named scenes' occupied rows take the episode's solver attributes (sca_set_agent_params') and planner attributes
+// (sca_device_tracker_set_agent_params').  Looked at behind scene_restart_check and restart_obstacles_check (ids, sizes and policies are
+// valid then).  A NULL array means the value a context alone would have -- sca_params', the enable call's -- never "what the row had".
+enum RestartAttrFault {
+    RESTART_ATTR_OK = 0,
+    RESTART_ATTR_STRUCT,    // struct_bytes below the leading integers, above the library's struct, or cutting a pointer in two    } SCA_ERR_ARG
+    RESTART_ATTR_RESERVED,  // reserved != 0                                                                                        }
+    RESTART_ATTR_NO_TRACKER,// turning_radius / pitch_lo / pitch_hi given while no device tracker is enabled                       }
+    RESTART_ATTR_SOLVER,    // a solver attribute out of sca_set_agent_params' range (entry: the packed row)                       }
+    RESTART_ATTR_PLANNER    // a tracked row whose turning radius / pitch limits are out of range (entry: the packed row)          }
+};
+// the descriptor as the library reads it: every member the caller's struct_bytes does not reach is NULL
+struct RestartAttrs {
+    const double *neighbor_dist = nullptr; const int32_t *max_neighbors = nullptr;
+    const double *time_step = nullptr, *time_horizon = nullptr, *max_speed = nullptr, *max_heading_change = nullptr, *dt_nominal = nullptr;
+    const double *turning_radius = nullptr, *pitch_lo = nullptr, *pitch_hi = nullptr;
+    bool solver() const { return neighbor_dist || max_neighbors || time_step || time_horizon || max_speed || max_heading_change || dt_nominal; }
+    bool planner() const { return turning_radius || pitch_lo || pitch_hi; }
+};
+// what a NULL array stands for: sca_create's sca_params and sca_device_tracker_enable's values
+struct AttrDefaults {
+    double neighbor_dist, time_step, time_horizon, max_speed, max_heading_change, dt_nominal; int max_neighbors;
+    double turning_radius, pitch_lo, pitch_hi;
+};
+struct RestartAttrCheck { RestartAttrFault fault; int entry; };
+constexpr int RESTART_ATTR_HEAD_BYTES = 8;                              // struct_bytes, reserved
+inline bool restart_attr_positive(double x) { return restart_finite(x) && x > 0.0; }
+// one row's solver attributes by sca_set_agent_params' rule
+inline bool restart_attr_solver_ok(double nd, int mn, double ts, double th, double ms, double mhc, double dt) {
+    return restart_attr_positive(nd) && restart_attr_positive(ts) && restart_attr_positive(th) && restart_attr_positive(ms) && restart_attr_positive(dt) &&
+           mn >= 1 && mn <= SCA_MAX_NEIGHBORS && mhc >= 0.0 && mhc <= 3.14159265358979323846;
+}
+// one tracked row's planner attributes by sca_device_tracker_set_agent_params' rule
+inline bool restart_attr_planner_ok(double R, double lo, double hi) { return restart_attr_positive(R) && restart_finite(lo) && restart_finite(hi) && lo < hi; }
+// in: the caller's struct (not NULL); out: its members as far as struct_bytes reaches.  C, A: what scene_restart_check passed.
+inline RestartAttrCheck restart_attrs_check(const RestartCtx &C, const RestartArgs &A, const sca_restart_attrs *in, const AttrDefaults &D, RestartAttrs *out) {
+    const int sb = in->struct_bytes;
+    if (sb < RESTART_ATTR_HEAD_BYTES || sb > (int)sizeof(sca_restart_attrs) || (sb - RESTART_ATTR_HEAD_BYTES) % (int)sizeof(void *) != 0) return {RESTART_ATTR_STRUCT, -1};
+    if (in->reserved != 0) return {RESTART_ATTR_RESERVED, -1};
+    sca_restart_attrs full{};                                          // (members behind struct_bytes stay NULL)
+    char *to = (char *)&full;
+    const char *from = (const char *)in;
+    for (int i = 0; i < sb; i++) to[i] = from[i];
+    RestartAttrs R;
+    R.neighbor_dist = full.neighbor_dist; R.max_neighbors = full.max_neighbors; R.time_step = full.time_step; R.time_horizon = full.time_horizon;
+    R.max_speed = full.max_speed; R.max_heading_change = full.max_heading_change; R.dt_nominal = full.dt_nominal;
+    R.turning_radius = full.turning_radius; R.pitch_lo = full.pitch_lo; R.pitch_hi = full.pitch_hi;
+    if (R.planner() && !C.tracker_on) return {RESTART_ATTR_NO_TRACKER, -1};
+    const int total = scene_restart_starts(A.count, C.offsets, A.scene_ids, A.sizes, nullptr);
+    if (R.solver())
+        for (int r = 0; r < total; r++)
+            if (!restart_attr_solver_ok(R.neighbor_dist ? R.neighbor_dist[r] : D.neighbor_dist, R.max_neighbors ? R.max_neighbors[r] : D.max_neighbors,
+                                        R.time_step ? R.time_step[r] : D.time_step, R.time_horizon ? R.time_horizon[r] : D.time_horizon,
+                                        R.max_speed ? R.max_speed[r] : D.max_speed, R.max_heading_change ? R.max_heading_change[r] : D.max_heading_change,
+                                        R.dt_nominal ? R.dt_nominal[r] : D.dt_nominal))
+                return {RESTART_ATTR_SOLVER, r};
+    if (R.planner()) {
+        int r = 0;
+        for (int b = 0; b < A.count; b++)
+            for (int a = C.offsets[A.scene_ids[b]], end = a + scene_restart_rows(C.offsets, A.scene_ids, A.sizes, b); a < end; a++, r++) {
+                if (!restart_policy_tracked(A.policy ? A.policy[r] : C.policy_now[a])) continue;          // untracked rows' entries are ignored
+                if (!restart_attr_planner_ok(R.turning_radius ? R.turning_radius[r] : D.turning_radius, R.pitch_lo ? R.pitch_lo[r] : D.pitch_lo,
+                                             R.pitch_hi ? R.pitch_hi[r] : D.pitch_hi))
+                    return {RESTART_ATTR_PLANNER, r};
+            }
+    }
+    *out = R;
+    return {RESTART_ATTR_OK, -1};
+}
+inline int restart_attrs_error_code(RestartAttrFault f) { return f == RESTART_ATTR_OK ? SCA_OK : SCA_ERR_ARG; }
+
+// The attribute sections of the restart's page-locked block, behind the obstacle sections: per packed row one AgentPar record (64 bytes,
+// read as four 16-byte pieces), the row's neighborDist alone (the tracker's array), the planner triple (turning radius, pitch_lo,
+// pitch_hi) and the row's class byte.  Every section starts on a 64-byte boundary; the sizes depend on sca_create's max_agents alone.
+enum RestartAttrSection : int { RA_PAR = 0, RA_ND, RA_TRIPLE, RA_CLASS, RA_SECTIONS };
+constexpr int64_t RA_PAR_BYTES = 64;
+struct RestartAttrLayout { int64_t off[RA_SECTIONS]; int64_t total; };
+inline int64_t restart_attr_row_bytes(int s) { return s == RA_PAR ? RA_PAR_BYTES : s == RA_ND ? 8 : s == RA_TRIPLE ? 24 : 1; }
+// begin: where the sections start in the block (RestartObsLayout::total)
+inline RestartAttrLayout restart_attrs_layout(int64_t begin, int max_n) {
+    RestartAttrLayout L;
+    int64_t at = (begin + RS_ALIGN - 1) / RS_ALIGN * RS_ALIGN;
+    for (int s = 0; s < RA_SECTIONS; s++) {
+        L.off[s] = at;
+        at += (restart_attr_row_bytes(s) * (int64_t)max_n + RS_ALIGN - 1) / RS_ALIGN * RS_ALIGN;
+    }
+    L.total = at;
+    return L;
+}
+// the attribute sections travel / the planner sections travel (the others keep the slot's values: every call without `attrs`)
+constexpr uint32_t RESTART_HAS_ATTRS = 64, RESTART_HAS_PLANNER = 128;
+
+// The tracker's classes under restarts.  The re-plan kernels run once per class of equal (turning radius, pitch_lo, pitch_hi) with the
+// class's values as kernel arguments, and an agent's class byte says which launch plans it (sca_device_tracker_set_agent_params).  A
+// restart changes which triples are in use, so the table is recomputed after every call over the OCCUPIED TRACKED rows -- rows behind a
+// scene's size and rows of untracked policies are not counted -- and a class keeps its index while any such row uses it: the class bytes
+// of the scenes that were not named need not move.  More than TRK_CLASS_CAP distinct triples: the per-agent form (`many`), which reads
+// the per-row arrays and no class byte; back at or below the cap the table is dealt afresh.
+constexpr int TRK_CLASS_CAP = 16;
+struct TrackTriple { double R, lo, hi; };
+inline bool operator==(const TrackTriple &a, const TrackTriple &b) { return a.R == b.R && a.lo == b.lo && a.hi == b.hi; }
+struct ClassTable {
+    TrackTriple val[TRK_CLASS_CAP] = {};
+    int32_t users[TRK_CLASS_CAP] = {};     // occupied tracked rows of the class; 0: the index is free
+    bool many = false;
+};
+// classes: distinct triples in use (TRK_CLASS_CAP + 1: more than the cap); moved: a class byte changed in a row whose byte does not
+// travel with the call (the caller uploads the whole array then)
+struct ClassUpdate { int classes; bool many; bool moved; };
+// policy, trip: [n] as they will be after the restart; size: [nscenes] likewise; cls: [n] the class bytes, rewritten for the occupied
+// tracked rows (untouched while `many`); travels: [n] 1 for the rows whose byte the restart's block carries, or NULL: none does
+inline ClassUpdate scene_class_table(ClassTable &tab, int nscenes, const int32_t *offsets, const int32_t *size, const uint8_t *policy, const TrackTriple *trip,
+                                     uint8_t *cls, const uint8_t *travels) {
+    TrackTriple seen[TRK_CLASS_CAP];
+    int nseen = 0;
+    bool many = false;
+    for (int s = 0; s < nscenes && !many; s++)
+        for (int a = offsets[s]; a < offsets[s] + size[s]; a++) {
+            if (!restart_policy_tracked(policy[a])) continue;
+            int k = 0;
+            while (k < nseen && !(seen[k] == trip[a])) k++;
+            if (k < nseen) continue;
+            if (nseen == TRK_CLASS_CAP) { many = true; break; }
+            seen[nseen++] = trip[a];
+        }
+    if (many) {
+        for (int k = 0; k < TRK_CLASS_CAP; k++) tab.users[k] = 0;
+        tab.many = true;
+        return {TRK_CLASS_CAP + 1, true, false};
+    }
+    bool keep[TRK_CLASS_CAP], placed[TRK_CLASS_CAP];
+    for (int k = 0; k < TRK_CLASS_CAP; k++) {                          // an index stays its class's while a row still uses the class
+        keep[k] = false;
+        if (tab.many || tab.users[k] == 0) continue;
+        for (int j = 0; j < nseen; j++) if (seen[j] == tab.val[k]) keep[k] = true;
+    }
+    for (int j = 0; j < nseen; j++) {
+        placed[j] = false;
+        for (int k = 0; k < TRK_CLASS_CAP; k++) if (keep[k] && tab.val[k] == seen[j]) placed[j] = true;
+    }
+    for (int j = 0, k = 0; j < nseen; j++) {                           // new triples take the lowest free indices, in order of appearance
+        if (placed[j]) continue;
+        while (keep[k]) k++;
+        tab.val[k] = seen[j]; keep[k] = true;
+    }
+    for (int k = 0; k < TRK_CLASS_CAP; k++) tab.users[k] = 0;
+    tab.many = false;
+    bool moved = false;
+    for (int s = 0; s < nscenes; s++)
+        for (int a = offsets[s]; a < offsets[s] + size[s]; a++) {
+            if (!restart_policy_tracked(policy[a])) continue;
+            int k = 0;
+            while (!(keep[k] && tab.val[k] == trip[a])) k++;
+            tab.users[k]++;
+            if (cls[a] != (uint8_t)k) { cls[a] = (uint8_t)k; if (!travels || !travels[a]) moved = true; }
+        }
+    return {nseen, false, moved};
+}
+// the classes in use, and the one index in use where there is exactly one (-1 otherwise)
+inline int class_table_used(const ClassTable &tab, int *only) {
+    int used = 0, last = -1;
+    for (int k = 0; k < TRK_CLASS_CAP; k++) if (tab.users[k] > 0) { used++; last = k; }
+    if (only) *only = used == 1 ? last : -1;
+    return used;
+}
+
 // ---- a trajectory log per scene (sca_scene_history_enable) -------------------------------------------------------------------------------------
 // One allocation of capacity x n rows of SCENE_LOG_ROW_BYTES (HistRow, sca_kernels.hip.h).  Scene s owns rows [capacity * offsets[s],
 // capacity * offsets[s + 1]); inside its part the layout is [row][agent] with pitch n_s, so any window of rows of one scene is one contiguous

@@ -216,8 +216,35 @@ __device__ __forceinline__ void scene_restart_pieces(void *dst, const void *src,
     const restart_piece *from = (const restart_piece *)src;
     for (int64_t w = t; w < pieces; w += RESTART_T) to[w] = from[w];
 }
+// A restart that brings attributes (sca_restart_scenes_attrs): with RESTART_HAS_ATTRS the block's attribute sections (RestartAttrLayout,
+// sca_scenes.h) hold one AgentPar record and one neighborDist per packed row, with RESTART_HAS_PLANNER the planner triple and the class
+// byte; they go to rows [lo, lo + ns) of the context's per-agent arrays -- the rows the episode occupies, and no others: a vacant row
+// keeps its attributes, as it keeps its constants.  The 64-byte records travel as 16-byte pieces like the obstacle records.  Without
+// the bits (every call without `attrs`) nothing of RestartAttrDev is read; its pointers may be null then.
+static_assert(sizeof(AgentPar) == RA_PAR_BYTES, "RestartAttrLayout's records");
+struct RestartAttrDev {
+    AgentPar *ap;                 // [n] DeviceView::ap
+    double *ap_nd;                // [n] TrackView::nd_per_agent
+    double *trk_R, *trk_plo, *trk_phi;   // [n] TrackView::R_pa / plo_pa / phi_pa
+    uint8_t *trk_cls;             // [n] TrackView::cls
+};
+__device__ __forceinline__ void scene_restart_attrs(const RestartAttrDev &at, const uint8_t *blk, const RestartAttrLayout &AL, uint32_t has, int row0, int lo, int ns, int t) {
+    if (has & RESTART_HAS_ATTRS) {
+        scene_restart_pieces(at.ap + lo, blk + AL.off[RA_PAR] + RA_PAR_BYTES * row0, (int64_t)ns * (RA_PAR_BYTES / 16), t);
+        const double *nd = (const double *)(blk + AL.off[RA_ND]) + row0;
+        for (int i = t; i < ns; i += RESTART_T) at.ap_nd[lo + i] = nd[i];
+    }
+    if (has & RESTART_HAS_PLANNER) {
+        const double *trip = (const double *)(blk + AL.off[RA_TRIPLE]) + 3 * (int64_t)row0;
+        const uint8_t *cl = blk + AL.off[RA_CLASS] + row0;
+        for (int i = t; i < ns; i += RESTART_T) {
+            at.trk_R[lo + i] = trip[3 * i]; at.trk_plo[lo + i] = trip[3 * i + 1]; at.trk_phi[lo + i] = trip[3 * i + 2];
+            at.trk_cls[lo + i] = cl[i];
+        }
+    }
+}
 __global__ __launch_bounds__(RESTART_T) void k_scene_restart(RestartDev d, const uint8_t *blk, RestartLayout L, uint32_t has, const int32_t *new_size, int32_t *size,
-                                                             RestartObsDev o, RestartObsLayout OL) {
+                                                             RestartObsDev o, RestartObsLayout OL, RestartAttrDev at, RestartAttrLayout AL) {
     const int b = (int)blockIdx.x, t = (int)threadIdx.x;
     const int s = ((const int32_t *)(blk + L.off[RS_IDS]))[b];
     const int row0 = ((const int32_t *)(blk + L.off[RS_START]))[b];
@@ -225,6 +252,7 @@ __global__ __launch_bounds__(RESTART_T) void k_scene_restart(RestartDev d, const
     scene_restart_fill(d, blk, L, has, row0, lo, ns, t);
     scene_restart_vacate(d, lo + ns, hi, t);
     if (t == 0) { d.live[s * SCENE_LINE] = ns; d.prev[s] = ns; d.steps[s] = 0; size[s] = ns; }
+    scene_restart_attrs(at, blk, AL, has, row0, lo, ns, t);
     const int32_t *head = (const int32_t *)(blk + OL.off[RO_HEAD]) + RO_HEAD_WORDS * b;
     const int k = head[0];
     if (k < 0) return;                                                 // this scene keeps its set (uniform over the workgroup)

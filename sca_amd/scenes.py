@@ -90,6 +90,14 @@ class SceneEnv:
         self._mirror = {k: v[self._lo:hi] for k, v in self._batch._mirror.items()}       # views: refreshed in place by the batch
         self.goal = self._batch.goal[self._lo:hi]
 
+    @property
+    def per_agent_attributes(self):
+        """the attributes the episode's agents disagree on, in MACAEnv.per_agent_attributes' names (read from the agents the slot holds now)"""
+        out = [name for name, (attr, conv) in _ATTRS.items() if len({conv(getattr(a, attr)) for a in self.agents}) > 1]
+        if self._batch._trk_on and len({_planner_triple(a) for a in self.agents if a.policy.needs_external_vpref}) > 1:
+            out.append('turning_radius / pitchlims')
+        return sorted(out)
+
     _stale = property(lambda self: self._batch._stale)
     _paths_on = property(lambda self: self._batch._paths_on)
     _path_stale = property(lambda self: self._batch._path_stale)
@@ -125,8 +133,12 @@ class SceneEnv:
 
 class SceneBatch(_FlatAgents):
     def __init__(self, scenes, obstacles=(), scene_obstacles=None, neighbor_mode=S.NBR_KDTREE, device_tracker=False, history_capacity=0, scene_history=0, device=0,
-                 capacities=None, harvest=False, obstacle_capacities=None):
-        """obstacle_capacities: one obstacle capacity per scene, each >= len(scene_obstacles[s]), or 'max' (every slot holds the largest
+                 capacities=None, harvest=False, obstacle_capacities=None, attribute_slots=False):
+        """attribute_slots: a restarted slot takes the episode's own solver attributes (neighborDist, maxNeighbors, timeStep, timeHorizon,
+        maxSpeed, max_heading_change, dt_nominal) and planner attributes (turning_radius, pitchlims) instead of keeping its own
+        (sca_restart_scenes_attrs): restart() then accepts agents whose attributes differ from the slot's, and agents that change between a
+        tracked and an untracked policy.  A parameter study -- one attribute swept across seeds -- streams through one batch.
+        obstacle_capacities: one obstacle capacity per scene, each >= len(scene_obstacles[s]), or 'max' (every slot holds the largest
         list); None: none.  The scenes' obstacle ranges are then OBSTACLE SLOTS (sca_set_scene_obstacle_slots): the initial lists
         (scene_obstacles; None: every slot starts empty) go through the slots call, and restart(..., obstacles={s: [...]}) brings a new
         episode's own list of up to that many obstacles into a slot.
@@ -166,6 +178,7 @@ class SceneBatch(_FlatAgents):
         self.neighbor_mode = neighbor_mode
         self.device_tracker = bool(device_tracker)
         self.capacity_slots = capacities is not None               # else: a slot keeps its size, as a batch always did
+        self.attribute_slots = bool(attribute_slots)               # else: a slot keeps its attributes, as a batch always did
         self.sizes = np.array([len(a) for a in scenes], np.int32)   # agents each scene holds ...
         caps = self.sizes.copy() if capacities is None else np.array([int(c) for c in capacities], np.int32)
         if len(caps) != len(scenes) or (caps < self.sizes).any():
@@ -296,15 +309,16 @@ class SceneBatch(_FlatAgents):
                 if len(a._path):
                     raise ValueError(f'restart: scene {s}, agent {i} carries a path: waypoint lists cannot be replaced per scene')
                 for name, (attr, conv) in _ATTRS.items():
-                    if conv(getattr(a, attr)) != conv(getattr(old, attr)):
-                        raise ValueError(f"restart: scene {s}, agent {i}: {attr} differs from the slot's (a slot keeps its solver attributes)")
-                if self._trk_trip is not None and bool(a.policy.needs_external_vpref) != bool(old.policy.needs_external_vpref):
+                    if not self.attribute_slots and conv(getattr(a, attr)) != conv(getattr(old, attr)):
+                        raise ValueError(f"restart: scene {s}, agent {i}: {attr} differs from the slot's (a slot keeps its solver attributes; "
+                                         'SceneBatch(attribute_slots=True) makes slots that take the episode\'s own)')
+                if not self.attribute_slots and self._trk_trip is not None and bool(a.policy.needs_external_vpref) != bool(old.policy.needs_external_vpref):
                     raise ValueError(f'restart: scene {s}, agent {i} changes between a tracked (SCA, RVO3D+Dubins) and an untracked policy while the '
                                      "batch carries planner attributes per agent: the tracker's classes are cut by policy")
                 if a.policy.needs_external_vpref and self.device_tracker:
                     if not self._trk_on:
                         raise ValueError(f'restart: scene {s}, agent {i} needs the device tracker, which a batch built without such agents has not enabled')
-                    if _planner_triple(a) != self._planner_of(lo + i):
+                    if not self.attribute_slots and _planner_triple(a) != self._planner_of(lo + i):
                         raise ValueError(f"restart: scene {s}, agent {i}: turning_radius / pitchlims differ from the slot's (a slot keeps its planner attributes)")
         self._send_restart(items, new_obs)
         for s, agents in items:
@@ -336,13 +350,28 @@ class SceneBatch(_FlatAgents):
         policy = np.array([a.policy.policy_id for a in flat], np.uint8)
         # (a batch whose slots are all full, before and after, makes the plain call: sca_restart_scenes)
         full = all(len(agents) == self.offsets[s + 1] - self.offsets[s] for s, agents in items) and (self.sizes == np.diff(self.offsets)).all()
+        attrs = None
+        if self.attribute_slots:                                     # every attribute of every agent: the rows take exactly the episode's
+            attrs = {name: [conv(getattr(a, attr)) for a in flat] for name, (attr, conv) in _ATTRS.items()}
+            if self._trk_on:
+                trip = [_planner_triple(a) for a in flat]
+                attrs.update(turning_radius=[t[0] for t in trip], pitch_lo=[t[1] for t in trip], pitch_hi=[t[2] for t in trip])
         self.solver.restart_scenes([s for s, _ in items], np.array([a._pos for a in flat], dtype=np.float64).reshape(T, 3),
                                    np.array([a._heading for a in flat], dtype=np.float64).reshape(T, 3),
                                    vel=np.array([a._vel for a in flat], dtype=np.float32).reshape(T, 3), radius=[a.radius for a in flat],
                                    pref_speed=[a.pref_speed for a in flat], goal=goal, policy=policy, zaxis=S.zaxis_flags(start, goal6),
                                    max_run_dist=[a.max_run_dist for a in flat], goal_heading=goal6[:, 3:6] if self._trk_on else None,
                                    sizes=None if full else [len(agents) for _, agents in items],
-                                   obstacles=[_obstacle_arrays(new_obs[s]) if s in new_obs else None for s, _ in items] if new_obs else None)
+                                   obstacles=[_obstacle_arrays(new_obs[s]) if s in new_obs else None for s, _ in items] if new_obs else None,
+                                   attrs=attrs)
+        if attrs is not None and self._trk_on:                       # the planner attributes the device holds per row (_planner_of)
+            if self._trk_trip is None:
+                self._trk_trip = [self._trk_first] * len(self._flat)
+            at = 0
+            for s, agents in items:
+                lo = int(self.offsets[s])
+                self._trk_trip[lo:lo + len(agents)] = trip[at:at + len(agents)]
+                at += len(agents)
         at = 0
         for s, agents in items:
             lo, n = int(self.offsets[s]), len(agents)
@@ -486,7 +515,7 @@ def _harvest_policy_time(view, h):
 
 
 def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=None, max_steps=None, stats=None, history_rows=0, capacities=None,
-                 harvest=False, episode_obstacles=None, obstacle_capacities='max'):
+                 harvest=False, episode_obstacles=None, obstacle_capacities='max', attributes=False):
     """Streams a queue of episodes (Agent lists, each numbered 0 .. n - 1) through `slots` scenes of ONE SceneBatch: when a scene finishes,
     its metrics, step count and final state are taken and the slot restarts with the next episode of its size (SceneBatch.restart), while
     the other slots keep running.  Obstacles are one list shared by all episodes (`obstacles`), or -- mutually exclusive with it --
@@ -508,7 +537,9 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
     next_fitting), so a queue that mixes counts streams through one set of slots; ValueError before the first step when an episode fits no
     slot.  live_fraction then counts the slots' capacities as the batch's agent rows.  harvest=True: the same results, on_done order and
     stats, taken from what the finishing step itself handed over (SceneBatch(harvest=True): finished() / harvested()) -- one
-    synchronisation per step and, per finished episode, its own rows instead of a read-back of the whole batch."""
+    synchronisation per step and, per finished episode, its own rows instead of a read-back of the whole batch.  attributes=True: the slots
+    take every episode's own solver and planner attributes (SceneBatch(attribute_slots=True)), so a queue whose episodes differ in them --
+    a sweep of neighborDist across seeds -- streams through one batch instead of raising when such an episode's turn comes."""
     episodes = [list(e) for e in episodes]
     sizes = [len(e) for e in episodes]
     ocaps = None
@@ -539,7 +570,7 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
         raise ValueError('run_episodes: episode %d needs the device tracker, but none of the episodes the slots start with does, so the batch '
                          'would run without one: put a tracked episode among the first %d' % (min(i for i in pending if tracked[i]), len(holding)))
     batch = SceneBatch([episodes[i] for i in holding], obstacles, device_tracker=device_tracker, scene_history=history_rows,
-                       capacities=None if capacities is None else caps, harvest=harvest,
+                       capacities=None if capacities is None else caps, harvest=harvest, attribute_slots=attributes,
                        scene_obstacles=None if ocaps is None else [episode_obstacles[i] for i in holding], obstacle_capacities=ocaps)
     results = [None] * len(episodes)
     batch_steps = served = 0

@@ -18,6 +18,7 @@ FORM_WAYPOINTS = 256                                          # k_waypoint ran (
 FORM_SCENES = 512                                             # scenes are set: forest build, scene forms of K1 / K4
 FORM_SCENE_OBSTACLES = 1024                                   # ... with one obstacle set per scene (set_scene_obstacles)
 K = _lib.K
+_ATTR_NAMES = tuple(name for name, _ in _lib.RestartAttrs._fields_[2:])   # sca_restart_attrs' arrays, in the struct's order
 
 
 class ScaError(RuntimeError):
@@ -257,7 +258,7 @@ class BatchedSolver:
         return out
 
     def restart_scenes(self, ids, pos, heading, vel=None, radius=None, pref_speed=None, goal=None, policy=None, zaxis=None, max_run_dist=None,
-                       goal_heading=None, sizes=None, obstacles=None):
+                       goal_heading=None, sizes=None, obstacles=None, attrs=None):
         """New episodes into the scenes `ids` while the others keep running (sca_restart_scenes).  The arrays hold T rows, the named scenes'
         agents in the order of `ids`; None keeps the slot's values (vel: zero).  Afterwards each named scene is what a context of that
         episode alone is after set_agents + set_state (+ device_tracker_enable); its per-agent attributes stay, and its obstacle set unless
@@ -265,7 +266,13 @@ class BatchedSolver:
         sizes (sca_restart_scenes_sized): the agents each named scene takes, 1 .. its capacity (the length of its range) -- T is their sum,
         and the rows of the range behind them are vacant; None fills every named scene to its capacity.
         obstacles (sca_restart_scenes_obstacles; obstacle slots set): per named scene None -- it keeps its set -- or (pos [m, 3], radius [m])
-        with m at most the slot's obstacle capacity -- its set is replaced.  None: every named scene keeps its set."""
+        with m at most the slot's obstacle capacity -- its set is replaced.  None: every named scene keeps its set.
+        attrs (sca_restart_scenes_attrs): a dict -- the named scenes' rows take the episode's own attributes: neighbor_dist, max_neighbors,
+        time_step, time_horizon, max_speed, max_heading_change, dt_nominal (set_agent_params' names) and, with the device tracker on,
+        turning_radius, pitch_lo, pitch_hi, each an array of T rows or a scalar for all of them.  A name that is absent means the value a
+        context alone would have -- its sca_params, device_tracker_enable's value -- not what the row had; {} puts every named row back
+        on those.  A policy may then move an agent between tracked and untracked.  None: the slots keep their attributes (the entry
+        points above); 'keep': the same through sca_restart_scenes_attrs with attrs == NULL, which is exactly that call."""
         ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
         keep = [ids]
         if obstacles is not None and len(obstacles) != len(ids):
@@ -298,7 +305,28 @@ class BatchedSolver:
         u1 = lambda a: arr(a, np.uint8, C.c_uint8, 0)
         rest = (d3(pos), arr(vel, np.float32, C.c_float, 3), d3(heading), d1(radius), d1(pref_speed), d3(goal), u1(policy), u1(zaxis), d1(max_run_dist),
                 d3(goal_heading))
-        if obstacles is not None:
+        if attrs is not None:
+            keep_attrs = isinstance(attrs, str)
+            if keep_attrs and attrs != 'keep':
+                raise ValueError(f"restart_scenes: attrs is None, 'keep' or a dict, got {attrs!r}")
+            unknown = [] if keep_attrs else sorted(set(attrs) - set(_ATTR_NAMES))
+            if unknown:
+                raise ValueError(f'restart_scenes: attrs names {unknown}, sca_restart_attrs has {list(_ATTR_NAMES)}')
+            desc = _lib.RestartAttrs(struct_bytes=C.sizeof(_lib.RestartAttrs), reserved=0)
+            for name, v in ({} if keep_attrs else attrs).items():
+                if v is None:
+                    continue
+                i32 = name == 'max_neighbors'
+                v = np.asarray(v, np.int32 if i32 else np.float64)
+                if v.ndim == 0 and T is not None:
+                    v = np.full(T, v)
+                setattr(desc, name, arr(v, np.int32 if i32 else np.float64, C.c_int32 if i32 else C.c_double, 0))
+            ocnt, opos, orad = self._pack_obstacle_sets(obstacles, 'restart_scenes') if obstacles is not None else (None, None, None)
+            op = lambda a, ct: None if a is None else _lib.ptr(a, ct)
+            self._chk(self.L.sca_restart_scenes_attrs(self.ctx, len(ids), _lib.ptr(ids, C.c_int32), None if sizes is None else _lib.ptr(sizes, C.c_int32),
+                                                      op(ocnt, C.c_int32), op(opos, C.c_double), op(orad, C.c_double), None if keep_attrs else C.byref(desc), *rest),
+                      'sca_restart_scenes_attrs')
+        elif obstacles is not None:
             ocnt, opos, orad = self._pack_obstacle_sets(obstacles, 'restart_scenes')
             self._chk(self.L.sca_restart_scenes_obstacles(self.ctx, len(ids), _lib.ptr(ids, C.c_int32), None if sizes is None else _lib.ptr(sizes, C.c_int32),
                                                           _lib.ptr(ocnt, C.c_int32), _lib.ptr(opos, C.c_double), _lib.ptr(orad, C.c_double), *rest),

@@ -51,7 +51,23 @@ seeded per episode (candidate c: c mod 3) -- and the queue runs in the two ways 
               (sca_restart_scenes_obstacles)
 Identical final states per episode in both legs (asserted).  Beside them, on one batch of B slots (slot 0 of obstacle capacity 1491, the
 others 8), the wall time of one restart call: sca_restart_scenes_sized naming 1 and B / 4 scenes, sca_restart_scenes_obstacles naming the
-same scenes with 8 obstacles each, with -1 (keep) for each, and naming slot 0 with 1491 obstacles."""
+same scenes with 8 obstacles each, with -1 (keep) for each, and naming slot 0 with 1491 obstacles.
+
+    python tools/bench/scene_refill_cost.py --attributes          # 256 episodes of 100 drones, 64 slots -> profiles/scene_attrs_cost.json
+
+--attributes: a parameter study -- the same queue with `--values` of neighborDist dealt round-robin over the candidates -- in the two ways
+there are, alternated:
+    waves     B episodes at a time, ONE FRESH SceneBatch PER PARAMETER VALUE per wave: what a user had to do while a slot kept its attributes
+    stream    run_episodes(attributes=True): a finished slot takes the next episode and its attributes (sca_restart_scenes_attrs)
+Identical final states per episode in both legs (asserted).  Beside them the wall time of one restart call on one batch of B slots, naming 1
+and 16 scenes, without attrs and with every attribute array: 30 samples each, median, min and max.  --parent-json: the samples of the same
+call measured on the PARENT commit's library on the same machine (--restart-only, below); the record then says whether this build's call
+without attrs lies inside the spread of the parent's own samples (median <= the parent's max).
+
+    python tools/bench/scene_refill_cost.py --restart-only parent.json --package-root <a checkout of the parent commit, built>
+
+--restart-only: nothing but the 30 samples of the restart call without attrs (1 and 16 scenes) on the library found under --package-root --
+only calls every commit since sca_restart_scenes has."""
 import argparse
 import json
 import os
@@ -76,15 +92,21 @@ def main():
     ap.add_argument('--sizes', default='20,50,100', help='--mixed: the agent counts the episodes are drawn from')
     ap.add_argument('--harvest', action='store_true', help='the streamed queue with and without the scene harvest')
     ap.add_argument('--episode-obstacles', action='store_true', help='a queue whose episodes bring their own obstacles: waves of fresh batches against the streamed queue')
-    ap.add_argument('--parent-json', default=None, help="--harvest: the parent commit's scene_refill_cost.json of the same queue on the same machine")
+    ap.add_argument('--parent-json', default=None, help="--harvest: the parent commit's scene_refill_cost.json of the same queue on the same machine; "
+                                                        "--attributes: the parent commit's --restart-only samples")
+    ap.add_argument('--attributes', action='store_true', help='a parameter study: waves of one fresh batch per value against the streamed queue with attribute slots')
+    ap.add_argument('--values', default='5,10,15', help='--attributes: the neighborDist values, dealt round-robin')
+    ap.add_argument('--restart-only', default=None, metavar='OUT', help='write only the samples of one restart call (1 and 16 scenes, no attrs) to OUT')
+    ap.add_argument('--package-root', default=None, help='import sca_amd from this checkout instead of the one the tool stands in')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
-    if args.harvest + args.mixed + args.episode_obstacles > 1:
-        ap.error('--harvest, --mixed and --episode-obstacles are three comparisons: one at a time')
+    if args.harvest + args.mixed + args.episode_obstacles + args.attributes > 1:
+        ap.error('--harvest, --mixed, --episode-obstacles and --attributes are four comparisons: one at a time')
     if args.out is None:
         args.out = os.path.join(REPO, 'profiles', 'scene_harvest_cost.json' if args.harvest else 'scene_sizes_cost.json' if args.mixed else
-                                'scene_obstacle_refill_cost.json' if args.episode_obstacles else 'scene_refill_cost.json')
-    sys.path.insert(0, REPO)
+                                'scene_obstacle_refill_cost.json' if args.episode_obstacles else 'scene_attrs_cost.json' if args.attributes else
+                                'scene_refill_cost.json')
+    sys.path.insert(0, args.package_root or REPO)
     from sca_amd import env as E, scenarios, scenes, solver as sol_mod
     pols = [E.SCAPolicy, E.RVO3DPolicy, E.SRVO3DPolicy, E.ORCA3DPolicy, E.ORCA3DPolicyOfficial, E.RVO3dDubinsPolicy]
     B, n1 = args.slots, args.agents
@@ -94,11 +116,61 @@ def main():
     choices = [int(v) for v in args.sizes.split(',')] if args.mixed else [n1]
     size_of = np.random.default_rng(2024).choice(choices, size=len(candidates))      # the agent count of candidate c
 
+    values = [float(v) for v in args.values.split(',')]
+
+    def value_of(c):
+        return values[c % len(values)]                            # --attributes: candidate c's neighborDist
+
     def episode(c):
         n = int(size_of[c])
         sc = scenarios.random_cube(n, seed=c)
-        return [E.Agent(start_pos=list(sc['start'][i]), goal_pos=list(sc['goal'][i]), vel=[0.0, 0.0, 0.0], radius=0.5, pref_speed=1.0,
-                        policy=pols[c % len(pols)], id=i) for i in range(n)]
+        agents = [E.Agent(start_pos=list(sc['start'][i]), goal_pos=list(sc['goal'][i]), vel=[0.0, 0.0, 0.0], radius=0.5, pref_speed=1.0,
+                          policy=pols[c % len(pols)], id=i) for i in range(n)]
+        if args.attributes:
+            for a in agents:
+                a.neighborDist = value_of(c)
+        return agents
+
+    RESTART_SAMPLES = 30
+
+    def restart_samples(sol, eps, k, attrs=None, sizes=None, obstacles=None):
+        """the wall time of RESTART_SAMPLES restart calls naming scenes 0 .. k - 1 with the episodes eps[0 .. k - 1], in seconds"""
+        ids = list(range(k))
+        flat = [a for s in ids for a in eps[s]]
+        T = len(flat)
+        start = np.array([a.initial_pos for a in flat]).reshape(T, 6)
+        goal6 = np.array([a.goal_pos for a in flat]).reshape(T, 6)
+        kw = dict(vel=np.zeros((T, 3), np.float32), radius=np.full(T, 0.5), pref_speed=np.ones(T), goal=np.ascontiguousarray(goal6[:, :3]),
+                  policy=np.array([a.policy.policy_id for a in flat], np.uint8), zaxis=sol_mod.zaxis_flags(start, goal6),
+                  max_run_dist=np.array([a.max_run_dist for a in flat]), goal_heading=np.ascontiguousarray(goal6[:, 3:6]))
+        if attrs is not None:
+            kw['attrs'] = attrs(flat)
+        pos, head = np.ascontiguousarray(start[:, :3]), np.ascontiguousarray(start[:, 3:6])
+        ts = []
+        for _ in range(RESTART_SAMPLES):
+            t0 = time.perf_counter()
+            sol.restart_scenes(ids, pos, head, sizes=sizes, obstacles=obstacles, **kw)
+            ts.append(time.perf_counter() - t0)
+        return ts
+
+    def spread(ts):
+        return {'median_ms': float(np.median(ts)) * 1e3, 'min_ms': float(min(ts)) * 1e3, 'max_ms': float(max(ts)) * 1e3, 'samples_ms': [t * 1e3 for t in ts]}
+
+    if args.restart_only:
+        # default attributes throughout: the batch and the call every commit since sca_restart_scenes has
+        args.attributes = False
+        eps = [episode(c) for c in range(B + 16)]
+        batch = scenes.SceneBatch(eps[:B], [], device_tracker=True)
+        for _ in range(20):
+            batch.step()
+        doc = {'tool': 'tools/bench/scene_refill_cost.py --restart-only', 'slots': B, 'agents_per_episode': n1, 'samples': RESTART_SAMPLES,
+               'no_attrs': {'scenes_1': spread(restart_samples(batch.solver, eps[B:], 1)), 'scenes_16': spread(restart_samples(batch.solver, eps[B:], 16))}}
+        batch.close()
+        with open(args.restart_only, 'w') as f:
+            json.dump(doc, f, indent=1, sort_keys=True)
+            f.write('\n')
+        print(json.dumps({k: {q: v[q] for q in ('median_ms', 'min_ms', 'max_ms')} for k, v in doc['no_attrs'].items()}), flush=True)
+        return
 
     def spheres(pos, radius):
         return [E.Obstacle(pos=list(map(float, p)), shape_dict={'shape': 'sphere', 'feature': float(r)}, id=i) for i, (p, r) in enumerate(zip(pos, radius))]
@@ -141,20 +213,25 @@ def main():
     def run_waves():
         eps = queue()
         t0 = time.perf_counter()
-        states, steps, served = [], 0, 0
+        states, steps, served, rows = [None] * count, 0, 0, 0
         for w in range(0, count, B):
-            batch = batch_of(chosen[w:w + B], eps[w:w + B])
-            done = False
-            while not done:
-                served += int(batch.active.sum())
-                done = batch.step()
-                steps += 1
-                assert steps < args.max_steps
-            for s in range(len(batch)):
-                lo, hi = int(batch.offsets[s]), int(batch.offsets[s + 1])
-                states.append({k: batch._state(k)[lo:hi].copy() for k in batch._mirror})
-            batch.close()
-        return time.perf_counter() - t0, states, dict(batch_steps=steps, agent_steps=served, live_fraction=served / (steps * B * n1))
+            wave = list(range(w, min(w + B, count)))
+            # --attributes: a slot keeps its attributes, so the wave falls apart into one fresh batch per parameter value
+            groups = [[i for i in wave if value_of(chosen[i]) == v] for v in values] if args.attributes else [wave]
+            for group in [g for g in groups if g]:
+                batch = batch_of([chosen[i] for i in group], [eps[i] for i in group])
+                done = False
+                while not done:
+                    served += int(batch.active.sum())
+                    done = batch.step()
+                    steps += 1
+                    rows += len(group) * n1
+                    assert steps < args.max_steps
+                for s, i in enumerate(group):
+                    lo, hi = int(batch.offsets[s]), int(batch.offsets[s + 1])
+                    states[i] = {k: batch._state(k)[lo:hi].copy() for k in batch._mirror}
+                batch.close()
+        return time.perf_counter() - t0, states, dict(batch_steps=steps, agent_steps=served, live_fraction=served / rows)
 
     # --harvest: the library calls that synchronise, counted at the solver's methods while a leg runs (weights: synchronisations per call)
     SYNCS = dict(env_step=1, scene_state=1, get_state=2, scene_harvest_collect=1, restart_scenes=1)
@@ -180,6 +257,8 @@ def main():
         eps = queue()
         stats = {}
         kw = {} if harvest is None else dict(harvest=harvest)
+        if args.attributes:
+            kw.update(attributes=True)
         if args.episode_obstacles:
             kw.update(episode_obstacles=[obstacles_of(c) for c in chosen], obstacle_capacities='max')
         t0 = time.perf_counter()
@@ -252,9 +331,37 @@ def main():
                    'obstacles_1491': {'scenes_1_ms': restart_ms(1, [many])},
                    'note': 'sca_restart_scenes_sized / sca_restart_scenes_obstacles on one batch of %d slots, slot 0 of obstacle capacity 1491, the others 8; '
                            'median of 30 calls, wall time around the call' % B}
+    if args.attributes:
+        # one restart call, 1 and 16 scenes: without attrs (the call every earlier commit has) and with every attribute array
+        names = dict(neighbor_dist='neighborDist', max_neighbors='maxNeighbors', time_step='timeStep', time_horizon='timeHorizon', max_speed='maxSpeed',
+                     max_heading_change='max_heading_change', dt_nominal='dt_nominal')
+
+        def every(flat):
+            out = {k: [getattr(a, v) for a in flat] for k, v in names.items()}
+            out.update(turning_radius=[a.turning_radius for a in flat], pitch_lo=[a.pitchlims[0] for a in flat], pitch_hi=[a.pitchlims[1] for a in flat])
+            return out
+        same_value = [e for e, c in zip(eps[B:], chosen[B:]) if value_of(c) == value_of(chosen[0])][:16]      # (without attrs a slot keeps its own)
+        plain = scenes.SceneBatch([e for e, c in zip(eps, chosen) if value_of(c) == value_of(chosen[0])][:B], [], device_tracker=True)
+        for _ in range(20):
+            plain.step()
+        call = {'no_attrs': {'scenes_1': spread(restart_samples(plain.solver, same_value, 1)), 'scenes_16': spread(restart_samples(plain.solver, same_value, 16))},
+                'attrs': {'scenes_1': spread(restart_samples(sol, eps[B:], 1, attrs=every)), 'scenes_16': spread(restart_samples(sol, eps[B:], 16, attrs=every))},
+                'step_ms': restart['step_ms'],
+                'note': 'one restart call on a batch of %d slots of %d drones, wall time around the call, %d samples each; no_attrs: sca_restart_scenes on a batch '
+                        'of one parameter value; attrs: sca_restart_scenes_attrs with all ten arrays' % (B, n1, RESTART_SAMPLES)}
+        plain.close()
+        if args.parent_json:
+            with open(args.parent_json) as f:
+                parent = json.load(f)
+            assert (parent['slots'], parent['agents_per_episode']) == (B, n1), 'the parent measured another batch'
+            call['parent_commit_no_attrs'] = parent['no_attrs']
+            call['no_attrs_not_slower_than_parent_beyond_its_spread'] = {
+                k: bool(call['no_attrs'][k]['median_ms'] <= parent['no_attrs'][k]['max_ms']) for k in ('scenes_1', 'scenes_16')}
+        restart = call
     batch.close()
 
-    doc = {'tool': 'tools/bench/scene_refill_cost.py' + (' --mixed' if args.mixed else ' --harvest' if args.harvest else ' --episode-obstacles' if args.episode_obstacles else ''),
+    doc = {'tool': 'tools/bench/scene_refill_cost.py' + (' --mixed' if args.mixed else ' --harvest' if args.harvest else ' --episode-obstacles' if args.episode_obstacles else
+                                                         ' --attributes' if args.attributes else ''),
            'slots': B, 'episodes': count,
            'agents_per_episode': {str(n): int((size_of[chosen] == n).sum()) for n in choices} if args.mixed else n1, 'alternations': args.alternations,
            'episode_cap': args.episode_cap, 'last_seed': chosen[-1], 'seeds_left_out_no_end_within_cap': left_out,
@@ -268,6 +375,9 @@ def main():
         if args.harvest:
             doc['legs'][name].update(ms_per_batch_step=1e3 * wall / st['batch_steps'], syncs_per_batch_step=st['syncs_per_batch_step'],
                                      readback_bytes_per_episode=st['readback_bytes_per_episode'], library_calls=st['calls'])
+    if args.attributes:
+        doc['neighborDist_values'] = values
+        doc['episodes_per_value'] = {str(v): int(sum(value_of(c) == v for c in chosen)) for v in values}
     if args.episode_obstacles:
         doc['obstacles_per_episode'] = {str(m): int(sum(len(obstacles_of(c)) == m for c in chosen)) for m in (0, 1, 2, 3, 4, 5, 8)}
     ratio = 'capacity_over_fixed_episodes_per_s' if args.mixed else 'harvest_over_stream_episodes_per_s' if args.harvest else 'stream_over_waves_episodes_per_s'
