@@ -107,7 +107,8 @@ def _dist(p, q, use_distance):
 
 def pass_rule_csr(off, pts, remaining, now_goal, pos, goal, radius, pref_speed, policy, flags):
     """pass_rule over arrays, for swarms too large for a loop over agents: the lists are the CSR form (off, pts) with remaining[i] elements
-    left.  Returns (remaining, now_goal, vpref_ext, mode) as new arrays.  Equal to pass_rule (tests/test_paths_cpu.py)."""
+    left.  Returns (remaining, now_goal, vpref_ext, mode) as new arrays.  Equal to pass_rule, the sign of a zero included: the oracle's
+    heading comes from atan2 of this v_pref (tests/test_paths_cpu.py, tests/test_form_fuzz_cpu.py)."""
     n = len(off) - 1
     off = np.asarray(off, np.int64)
     pts = np.asarray(pts, dtype=np.float64).reshape(-1, 3)
@@ -137,5 +138,5 @@ def pass_rule_csr(off, pts, remaining, now_goal, pos, goal, radius, pref_speed, 
         with np.errstate(divide='ignore', invalid='ignore'):
             v = dif * np.asarray(pref_speed, dtype=np.float64)[m, None] / nrm[:, None]
         v[_dist(goal[m], pos[m], np.zeros(m.size, bool)) < 0.2] = 0.0
-        vp[m] = np.trunc(v * EPS) / EPS
+        vp[m] = np.trunc(v * EPS) / EPS + 0.0                                    # (int(-0.6) / EPS is 0.0 where trunc(-0.6) / EPS is -0.0)
     return rem.astype(np.int32), ng, vp, mode.astype(np.uint8)

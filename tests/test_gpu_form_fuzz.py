@@ -58,45 +58,100 @@ def planned(H, simds, scene):
     return solve(H, scene['n'], simds=simds, lp=lp, lp_total=lp, t=(C.c_int * len(t))(*t.values())), t
 
 
-def run_against_oracle(S, oracle, scene, steps, nbr, per_agent, plan, ctx, require=0):
-    """one context, `steps` resident steps, everything compared after each (`require`: form bits every pass must report, whatever the plan says);
-    the context is closed before the caller makes the next"""
+def context_of(S, scene, per_agent=None, paths=None, state=True, perm=True):
+    """a context that holds the scene as its oracle run starts from it: obstacles, agents, per-agent attributes, the lists (paths: what
+    form_fuzz.random_paths returned; set_vpref behind set_paths is legal, only a straight-line agent with a list refuses mode 1), the fed
+    v_pref of the tracked agents, the state and the identity permutation (state=False: the caller brings the state, sca_step_host;
+    perm=False: the permutation is left alone, SCA_NBR_GRID builds no tree)"""
     s, n = scene, scene['n']
-    ref = F.oracle_run(oracle, s, steps, per_agent)
-    params = per_agent[1] if per_agent else None
-    sol = S.BatchedSolver(max_agents=n, max_obstacles=max(1, s['m']), params=params)
+    sol = S.BatchedSolver(max_agents=n, max_obstacles=max(1, s['m']), params=per_agent[1] if per_agent else None)
     try:
         sol.set_obstacles(s['obs_pos'], s['obs_radius'])
         sol.set_agents(s['radius'], s['pref_speed'], s['goal'], s['policy'], F.zaxis_of(s), s['max_run_dist'])
         if per_agent and not per_agent[2]:
             sol.set_agent_params(**per_agent[0])
+        if paths is not None:
+            sol.set_paths(paths)
         sol.set_vpref(s['vpref'], s['vmode'])
-        sol.set_state(s['pos'], s['vel'], s['heading'], s['flags'], np.zeros(n), np.zeros(n, np.int32))
-        sol.set_kd_perm(np.arange(n, dtype=np.int32))
-        lp = s['policy'] == 4
+        if state:
+            sol.set_state(s['pos'], s['vel'], s['heading'], s['flags'], np.zeros(n), np.zeros(n, np.int32))
+            if perm:
+                sol.set_kd_perm(np.arange(n, dtype=np.int32))
+    except BaseException:
+        sol.close()
+        raise
+    return sol
+
+
+def compare_with_oracle(sol, r, scene, at, rows=slice(None)):
+    """what a context holds after a step against the oracle's record `r` of it: flags, step counts, the kd permutation, float32 velocities,
+    positions, headings, travelled distance, the action rows, the neighbour lists entry for entry, the decisions' diagnostics.  rows: the
+    agents whose rows are compared (a shard; the permutation is the whole swarm's)"""
+    lp = (scene['policy'] == 4)[rows]
+    g = sol.get_state()
+    assert np.array_equal(g['flags'][rows], r['flags'][rows]), at + ('flags', np.flatnonzero(g['flags'][rows] != r['flags'][rows])[:8])
+    assert np.array_equal(g['step_num'][rows], r['step_num'][rows]), at + ('step_num',)
+    assert np.array_equal(sol.get_kd_perm(), r['perm']), at + ('perm',)
+    assert np.array_equal(g['vel'][rows], r['vel'][rows]), at + ('vel', np.flatnonzero((g['vel'][rows] != r['vel'][rows]).any(axis=1))[:8])
+    for k in ('pos', 'heading', 'total_dist'):
+        assert np.array_equal(g[k][rows], r[k][rows]), at + (k,)
+    compare_pass_with_oracle(sol, r, at, lp, rows)
+
+
+def compare_pass_with_oracle(sol, r, at, lp, rows=slice(None), ref_rows=None, id_base=(0, 0)):
+    """the policy pass's own results: action rows, neighbour lists, diagnostics (lp: the ORCA3D-LP agents among the rows).  rows: the
+    context's rows that are compared, ref_rows: the record's (None: the same rows -- a shard; a scene of a batch is rows [lo, hi) of the
+    context and the whole record of its own run, its ids in the lists global: id_base = (lo, the scene's first obstacle))"""
+    rr = rows if ref_rows is None else ref_rows
+    a = sol.actions()[rows]
+    assert np.array_equal(a, r['action'][rr]), at + ('action', np.flatnonzero((a != r['action'][rr]).any(axis=1))[:8])
+    nb = {k: v[rows] for k, v in sol.neighbors().items()}
+    nb['nbr_id'] = nb['nbr_id'] - np.where(nb['nbr_id'] >= 0, np.where(nb['nbr_kind'] == 1, id_base[1], id_base[0]), 0)
+    valid = r['nbr_valid'][rr].astype(bool)
+    assert np.array_equal(nb['nbr_valid'].astype(bool), valid), at + ('nbr_valid',)
+    for k in ('nbr_n', 'nbr_id', 'nbr_kind', 'nbr_dsq'):
+        assert np.array_equal(nb[k][valid], r[k][rr][valid]), at + (k,)
+    dg, want = sol.diag()['diag'][rows], r['diag'][rr]
+    assert np.array_equal(dg[:, :2], want[:, :2]), at + ('n_suit / fallback', np.flatnonzero((dg[:, :2] != want[:, :2]).any(axis=1))[:8])
+    assert np.array_equal(dg[lp, 3:5], want[lp, 3:5]), at + ('planeFail / lp4',)
+
+
+def check_paths(sol, r, scene, at, rows=slice(None), ref_rows=None):
+    """the waypoint lists behind a pass against the record `r` of an oracle run with lists: what is left of every list and now_goal (NaN rows
+    included) are the rule's, and the v_pref the pass used is the rule's on the served rows it aims at a waypoint and the fed one on the
+    served tracked rows.  rows / ref_rows: as in compare_pass_with_oracle (`scene` is the record's)"""
+    rr = rows if ref_rows is None else ref_rows
+    rem, ng = sol.get_path_state()
+    assert np.array_equal(rem[rows], r['path_left'][rr]), at + ('path_left', np.flatnonzero(rem[rows] != r['path_left'][rr])[:8])
+    assert np.array_equal(ng[rows], r['now_goal'][rr], equal_nan=True), at + ('now_goal',)
+    served = ((r['before'] & 7) == 0)[rr]
+    aimed, tracked = served & r['path_mode'][rr].astype(bool), served & scene['vmode'][rr].astype(bool)
+    vp = sol.diag()['vpref'][rows]
+    differ = (vp != r['vpref_rule'][rr]).any(axis=1)
+    assert not (aimed & differ).any(), at + ('v_pref toward the waypoint', np.flatnonzero(aimed & differ)[:8])
+    assert np.array_equal(vp[tracked], scene['vpref'][rr][tracked]), at + ('fed v_pref of the tracked agents',)
+
+
+def run_against_oracle(S, oracle, scene, steps, nbr, per_agent, plan, ctx, require=0, paths=None):
+    """one context, `steps` resident steps, everything compared after each (`require`: form bits every pass must report, whatever the plan says;
+    paths: the scene's waypoint lists -- the oracle run is the one with lists, every pass reports FORM_WAYPOINTS and the lists, now_goal and
+    the v_pref used are compared too); the context is closed before the caller makes the next"""
+    s, n = scene, scene['n']
+    ref = F.oracle_run(oracle, s, steps, per_agent, paths=paths)
+    if paths is not None:
+        require |= S.FORM_WAYPOINTS
+    sol = context_of(S, s, per_agent, paths)
+    try:
         for t, r in enumerate(ref):
             sol.run_steps(1, nbr)
             sol.synchronize()
             at = ctx + ('n', n, 'step', t)
             forms = sol.pass_forms()
             assert (forms & SOLVE_BITS) == plan['forms'] and (forms & require) == require, at + ('forms', forms, plan)
-            g = sol.get_state()
-            assert np.array_equal(g['flags'], r['flags']), at + ('flags', np.flatnonzero(g['flags'] != r['flags'])[:8])
-            assert np.array_equal(g['step_num'], r['step_num']), at + ('step_num',)
-            assert np.array_equal(sol.get_kd_perm(), r['perm']), at + ('perm',)
-            assert np.array_equal(g['vel'], r['vel']), at + ('vel', np.flatnonzero((g['vel'] != r['vel']).any(axis=1))[:8])
-            for k in ('pos', 'heading', 'total_dist'):
-                assert np.array_equal(g[k], r[k]), at + (k,)
-            a = sol.actions()
-            assert np.array_equal(a, r['action']), at + ('action', np.flatnonzero((a != r['action']).any(axis=1))[:8])
-            nb = sol.neighbors()
-            valid = r['nbr_valid'].astype(bool)
-            assert np.array_equal(nb['nbr_valid'].astype(bool), valid), at + ('nbr_valid',)
-            for k in ('nbr_n', 'nbr_id', 'nbr_kind', 'nbr_dsq'):
-                assert np.array_equal(nb[k][valid], r[k][valid]), at + (k,)
-            dg = sol.diag()['diag']
-            assert np.array_equal(dg[:, :2], r['diag'][:, :2]), at + ('n_suit / fallback', np.flatnonzero((dg[:, :2] != r['diag'][:, :2]).any(axis=1))[:8])
-            assert np.array_equal(dg[lp, 3:5], r['diag'][lp, 3:5]), at + ('planeFail / lp4',)
+            assert paths is not None or not forms & S.FORM_WAYPOINTS, at + ('forms', forms)
+            compare_with_oracle(sol, r, s, at)
+            if paths is not None:
+                check_paths(sol, r, s, at)
     finally:
         sol.close()
 

@@ -22,7 +22,7 @@ import pytest
 
 import form_fuzz as F
 from test_forms_cpu import H, from_env, solve                                       # noqa: F401 (H: fixture)
-from test_gpu_form_fuzz import S, SOLVE_BITS, row_env, simds                        # noqa: F401 (fixtures)
+from test_gpu_form_fuzz import S, SOLVE_BITS, check_paths, context_of, row_env, simds       # noqa: F401 (fixtures)
 from test_grid_rule_cpu import GRID_MAY_REFUSE
 
 pytestmark = pytest.mark.gpu
@@ -39,21 +39,15 @@ def planned(H, simds, scene, part_on=0):
     return solve(H, scene['n'], simds=simds, part_on=part_on, nranks=1, lp=lp, lp_total=lp, t=(C.c_int * len(t))(*t.values()))
 
 
-def run_grid_against_oracle(S, oracle, scene, steps, per_agent, plan, ctx, partition=False, may_refuse=False):
+def run_grid_against_oracle(S, oracle, scene, steps, per_agent, plan, ctx, partition=False, may_refuse=False, paths=None):
     """One context, `steps` resident steps in SCA_NBR_GRID, everything compared with the rule-1 oracle after each.  Returns None where the
-    library refused the scene at its first pass (may_refuse), else the overflowed rows the oracle had per step."""
+    library refused the scene at its first pass (may_refuse), else the overflowed rows the oracle had per step.  paths: the scene's waypoint
+    lists (form_fuzz.random_paths) -- the rule-1 run with lists, and the lists, now_goal and the v_pref used are compared too."""
     s, n = scene, scene['n']
-    ref = F.oracle_run(oracle, s, steps, per_agent, list_rule=1)
-    params = per_agent[1] if per_agent else None
-    sol = S.BatchedSolver(max_agents=n, max_obstacles=max(1, s['m']), params=params)
+    ref = F.oracle_run(oracle, s, steps, per_agent, list_rule=1, paths=paths)
+    sol = context_of(S, s, per_agent, paths, perm=False)
     overflowed = []
     try:
-        sol.set_obstacles(s['obs_pos'], s['obs_radius'])
-        sol.set_agents(s['radius'], s['pref_speed'], s['goal'], s['policy'], F.zaxis_of(s), s['max_run_dist'])
-        if per_agent and not per_agent[2]:
-            sol.set_agent_params(**per_agent[0])
-        sol.set_vpref(s['vpref'], s['vmode'])
-        sol.set_state(s['pos'], s['vel'], s['heading'], s['flags'], np.zeros(n), np.zeros(n, np.int32))
         if partition:
             sol.partition_init(0, 1, axis=0)
             assert sol.partition_counts() == (n, 0), ctx
@@ -71,6 +65,7 @@ def run_grid_against_oracle(S, oracle, scene, steps, per_agent, plan, ctx, parti
                 assert sol.partition_counts() == (n, 0), at
             forms = sol.pass_forms()
             assert (forms & SOLVE_BITS) == plan['forms'], at + ('forms', forms, plan)
+            assert bool(forms & S.FORM_WAYPOINTS) == (paths is not None), at + ('forms', forms)
             g = sol.get_state()
             assert np.array_equal(g['flags'], r['flags']), at + ('flags', np.flatnonzero(g['flags'] != r['flags'])[:8])
             assert np.array_equal(g['step_num'], r['step_num']), at + ('step_num',)
@@ -97,6 +92,8 @@ def run_grid_against_oracle(S, oracle, scene, steps, per_agent, plan, ctx, parti
             collided_now = ((r['flags_policy'] & 2) != 0) & ((r['before'] & 2) == 0)
             assert not (over & ~over_ref & ~collided_now).any(), at + ('spurious overflow', np.flatnonzero(over & ~over_ref & ~collided_now)[:8])
             overflowed.append(int((over_ref & valid).sum()))
+            if paths is not None:
+                check_paths(sol, r, s, at)
     finally:
         sol.close()
     return overflowed

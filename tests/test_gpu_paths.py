@@ -53,48 +53,80 @@ def check_path_state(sol, left, now_goal, ctx):
 NBR = {'kd': 0, 'auto': 3}
 
 
+def run_recorded_episode(S, name, nbr, ctx, grid=False, on_refusal=None, on_overflow=None):
+    """A recorded episode from its start state, nothing fed: sca_run_steps between the recorded steps (two steps per call in the circles), the
+    device tracker inside every pass for the SCA / RVO3D+Dubins agents.  Every recorded step equals the reference's.  grid=True: the mode
+    is SCA_NBR_GRID -- it builds no tree, so the kd permutation is not compared, and the run ends at the first pass in which a list
+    overflows (SCA_ST_NBR_OVERFLOW: from there the grid keeps the nearest max_neighbors where the reference's list depends on its tree's
+    visit order, include/sca_hip.h), after on_overflow(step) where the caller gave one.  on_refusal(error): called where the library refuses the episode's first pass
+    (the episode is then not run); None: a refusal is an error.  Returns the recorded steps compared."""
+    fx = load(name)
+    sol, st = make_solver(S, fx)
+    compared = 0
+    try:
+        if st['vpref_mode'].any():
+            sol.device_tracker_enable(fx['goal6'][:, 3:6], in_pass=True)
+        n = len(st['radius'])
+        sol.set_state(fx['start'][:, :3], np.zeros((n, 3), np.float32), fx['start'][:, 3:6], np.zeros(n, np.uint8))
+        check_path_state(sol, np.diff(fx['path_off']), np.full((n, 3), np.nan), ctx + ('initial',))
+        now = 0
+
+        def run(count):
+            """False: the library refused the episode's first pass and the caller has a word to say about it"""
+            try:
+                sol.run_steps(count, nbr)
+            except S.ScaError as e:
+                if on_refusal is None or now:
+                    raise
+                on_refusal(e)
+                return False
+            sol.synchronize()
+            return True
+        for k, t in enumerate(int(x) for x in fx['step']):
+            at = ctx + (t,)
+            if t > now:
+                if not run(t - now):
+                    return 0
+                now = t
+            s = sol.get_state()
+            for key in ('pos', 'heading', 'total_dist', 'flags'):
+                assert np.array_equal(s[key], fx[key][k]), at + ('before', key)
+            assert np.array_equal(s['vel'], fx['vel'][k]), at + ('before', 'vel')
+            check_path_state(sol, fx['path_left_before'][k], fx['now_goal_before'][k], at + ('before',))
+            if not run(1):
+                return 0
+            now += 1
+            called = fx['called'][k].astype(bool)
+            assert sol.pass_forms() & S.FORM_WAYPOINTS, at
+            dg = sol.diag()
+            if grid and (dg['status'] & 32).any():
+                assert not (dg['status'] & ~32).any(), at
+                if on_overflow is not None:
+                    on_overflow(t)
+                return compared
+            a = sol.actions()
+            assert np.array_equal(a[called], fx['action'][k][called]), at + ('action',)
+            assert np.array_equal(dg['vpref'][called], fx['vpref'][k][called]), at + ('vpref_used',)
+            assert not dg['status'].any(), at
+            s = sol.get_state()
+            for key, want in (('pos', 'pos_after'), ('heading', 'heading_after'), ('total_dist', 'total_dist_after'), ('flags', 'flags_after')):
+                assert np.array_equal(s[key], fx[want][k]), at + ('after', key)
+            assert np.array_equal(s['vel'], fx['vel_after'][k]), at + ('after', 'vel')
+            if not grid:
+                assert np.array_equal(sol.get_kd_perm(), fx['perm_after'][k]), at + ('perm after',)
+            check_path_state(sol, fx['path_left_after'][k], fx['now_goal_after'][k], at + ('after',))
+            compared += 1
+    finally:
+        sol.close()
+    return compared
+
+
 @pytest.mark.parametrize('mode', ['kd', 'auto'])
 @pytest.mark.parametrize('name', FIXTURES)
 def test_free_running_episode_with_paths_is_the_reference(S, name, mode):
     """From the start state, nothing fed: sca_run_steps between the recorded steps (two steps per call in the circles), the device tracker
     inside every pass for the SCA / RVO3D+Dubins agents.  Every recorded step equals the reference's."""
-    fx = load(name)
-    sol, st = make_solver(S, fx)
-    if st['vpref_mode'].any():
-        sol.device_tracker_enable(fx['goal6'][:, 3:6], in_pass=True)
-    n = len(st['radius'])
-    nbr = NBR[mode]
-    sol.set_state(fx['start'][:, :3], np.zeros((n, 3), np.float32), fx['start'][:, 3:6], np.zeros(n, np.uint8))
-    check_path_state(sol, np.diff(fx['path_off']), np.full((n, 3), np.nan), (name, mode, 'initial'))
-    now = 0
-    for k, t in enumerate(int(x) for x in fx['step']):
-        if t > now:
-            sol.run_steps(t - now, nbr)
-            sol.synchronize()
-            now = t
-        ctx = (name, mode, t)
-        s = sol.get_state()
-        for key in ('pos', 'heading', 'total_dist', 'flags'):
-            assert np.array_equal(s[key], fx[key][k]), ctx + ('before', key)
-        assert np.array_equal(s['vel'], fx['vel'][k]), ctx + ('before', 'vel')
-        check_path_state(sol, fx['path_left_before'][k], fx['now_goal_before'][k], ctx + ('before',))
-        sol.run_steps(1, nbr)
-        sol.synchronize()
-        now += 1
-        called = fx['called'][k].astype(bool)
-        assert sol.pass_forms() & S.FORM_WAYPOINTS, ctx
-        a = sol.actions()
-        assert np.array_equal(a[called], fx['action'][k][called]), ctx + ('action',)
-        dg = sol.diag()
-        assert np.array_equal(dg['vpref'][called], fx['vpref'][k][called]), ctx + ('vpref_used',)
-        assert not dg['status'].any(), ctx
-        s = sol.get_state()
-        for key, want in (('pos', 'pos_after'), ('heading', 'heading_after'), ('total_dist', 'total_dist_after'), ('flags', 'flags_after')):
-            assert np.array_equal(s[key], fx[want][k]), ctx + ('after', key)
-        assert np.array_equal(s['vel'], fx['vel_after'][k]), ctx + ('after', 'vel')
-        assert np.array_equal(sol.get_kd_perm(), fx['perm_after'][k]), ctx + ('perm after',)
-        check_path_state(sol, fx['path_left_after'][k], fx['now_goal_after'][k], ctx + ('after',))
-    sol.close()
+    assert run_recorded_episode(S, name, NBR[mode], (name, mode)) == len(load(name)['step'])
 
 
 @pytest.mark.parametrize('mode', ['kd', 'auto'])

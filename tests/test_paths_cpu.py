@@ -186,7 +186,7 @@ def test_array_form_of_the_rule_equals_the_loop(name):
         rem2, ng2, vp2, mode2 = R.pass_rule_csr(off, pts, fx['path_left_before'][k], fx['now_goal_before'][k], fx['pos'][k], goal,
                                                 fx['radius'], fx['pref_speed'], fx['policy'], fx['flags'][k])
         assert np.array_equal(rem2, [len(p) for p in paths]) and same(ng2, ng) and np.array_equal(mode2, mode)
-        assert np.array_equal(vp2[mode2.astype(bool)], vp[mode.astype(bool)])
+        assert vp2[mode2.astype(bool)].tobytes() == vp[mode.astype(bool)].tobytes()                # (bytes: -0.0 is not 0.0)
 
 
 def test_array_form_of_the_rule_equals_the_loop_on_random_swarms():
@@ -203,4 +203,4 @@ def test_array_form_of_the_rule_equals_the_loop_on_random_swarms():
         rem2, ng2, vp2, mode2 = R.pass_rule_csr(off, pts, np.diff(off), ng, pos, goal, radius, ps, policy, flags)
         vp, mode = R.pass_rule(paths, ng, pos, goal, radius, ps, policy, flags, np.diff(off) > 0)
         assert np.array_equal(rem2, [len(p) for p in paths]) and same(ng2, ng) and np.array_equal(mode2, mode)
-        assert np.array_equal(vp2, vp)
+        assert vp2.tobytes() == vp.tobytes()
