@@ -24,6 +24,9 @@ one metrics row per scene -- what a loop over the reference's run_example/run_*.
                                                        # maxSpeed, max_heading_change, dt_nominal, turning_radius); a slot takes the episode's
                                                        # own attributes with the restart (run_episodes(attributes=True)); one row per episode,
                                                        # the value in the row
+    python examples/run_scenes.py --waypoints 3 --seeds 8 --slots 16    # every drone routed through 3 waypoints (Agent.path), the table still
+                                                       # ONE queue: a slot takes the episode's own lists with the restart
+                                                       # (run_episodes(path_slots=...))
 """
 import argparse
 import os
@@ -65,6 +68,16 @@ def random_spheres(sc, seed):
     return spheres(out, [1.0] * len(out))
 
 
+def add_waypoints(agents, k, seed):
+    """every drone gets k waypoints (Agent.path) scattered 1.5 m around its straight line, deterministic per seed; get_trajectory pops from
+    the END of the list, so the list runs from the goal's side to the start's"""
+    rng = np.random.default_rng(2000 + seed)
+    for a in agents:
+        p, g = np.asarray(a.initial_pos[:3], dtype=np.float64), np.asarray(a.goal_pos[:3], dtype=np.float64)
+        fractions = sorted(rng.uniform(0.15, 0.85, k), reverse=True)
+        a.path = [[float(x) for x in np.round(p + (g - p) * f + rng.normal(0, 1.5, 3) * [1, 1, 0.3], 3)] for f in fractions]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--agents', type=int, default=100)
@@ -80,6 +93,8 @@ def main():
     ap.add_argument('--harvest', action='store_true', help='with --slots: finished scenes hand over their result with the step (run_episodes(harvest=True))')
     ap.add_argument('--sweep', default=None, help='with --slots: NAME=v1,v2,...: every scenario once per value of this Agent attribute (%s), '
                                                   'all of them one queue' % ', '.join(SWEEPABLE))
+    ap.add_argument('--waypoints', type=int, default=0, help='route every drone through this many seeded waypoints (Agent.path); with --slots the '
+                                                             "queue's slots take every episode's own lists (run_episodes(path_slots=...))")
     ap.add_argument('--log-dir', default=None, help='write one folder per episode here: env_cfg.json + trajs.npz (the first --max-steps steps of each)')
     args = ap.parse_args()
     if args.map and not (args.slots and args.obstacles):
@@ -135,6 +150,10 @@ def main():
                 names.append((pname, '%s %s=%g' % (what, sweep_name, v)))
                 scenes.append(fresh)
                 obstacles.append(obs)
+    if args.waypoints:
+        for k, agents in enumerate(scenes):
+            add_waypoints(agents, args.waypoints, k)
+
     def folder(k):
         return os.path.join(args.log_dir, '%03d_%s_%s' % (k, names[k][0], names[k][1].replace(' ', '_')))
 
@@ -151,9 +170,11 @@ def main():
                     print('    (the log holds the first %d steps: %d more did not fit --max-steps rows)' % (r['trajectories'].shape[1], r['rows_dropped']))
         run_episodes(scenes, args.slots, device_tracker=True, on_done=row, max_steps=args.max_steps, stats=stats,
                      history_rows=args.max_steps if args.log_dir else 0, capacities=capacities, harvest=args.harvest,
-                     episode_obstacles=obstacles if args.obstacles else None, attributes=bool(sweep_name))
+                     episode_obstacles=obstacles if args.obstacles else None, attributes=bool(sweep_name),
+                     path_slots=args.waypoints or None)
         print('%d episodes through %d slots: %d batch steps, mean live fraction %.2f, %.2f s' %
-              (len(scenes), args.slots, stats['batch_steps'], stats['live_fraction'], time.time() - t0))
+              (len(scenes), args.slots, stats['batch_steps'], stats['live_fraction'], time.time() - t0) +
+              (' (%d waypoints per drone, the lists in slot form)' % args.waypoints if args.waypoints else ''))
         return
     rows = args.max_steps if args.log_dir else 0
     batch = SceneBatch(scenes, scene_obstacles=obstacles, device_tracker=True, scene_history=rows) if args.obstacles else \

@@ -12,6 +12,8 @@
  *   sca_set_state / sca_get_state agent.pos/vel/heading/flags attribute reads  mamp/envs/mampenv.py:34-46
  *   sca_set_vpref                 SCA's Dubins-tracker output fed to intersect mamp/policies/sca/scaPolicy.py:32,264-338
  *   sca_set_paths                 Agent.path + policy.get_trajectory/now_goal  mamp/agents/agent.py:44, rvo3dPolicy.py:71-85, orca3dPolicy.py:298-312
+ *   sca_set_path_slots            the same lists, a room per agent row         mamp/agents/agent.py:44
+ *   sca_restart_scenes_paths      a new episode's Agent.path lists             mamp/agents/agent.py:44, run_example/run_sca.py:174-178
  *   sca_policy_pass               first loop of MACAEnv._take_action:          mamp/envs/mampenv.py:28-40
  *                                 KDTree.buildAgentTree                        mamp/policies/kdTree.py:56-122
  *                                 computeNeighbors / insert*Neighbor           mamp/policies/sca/scaPolicy.py:107-116, mamp/agents/agent.py:79-124
@@ -168,6 +170,24 @@ int sca_set_paths(sca_ctx *ctx, int n, const int32_t *offsets /*n+1*/, const dou
 int sca_get_path_state(sca_ctx *ctx, int32_t *remaining /*n, nullable*/, double *now_goal /*n*3, nullable*/);
 int sca_set_path_state(sca_ctx *ctx, const int32_t *remaining /*n*/, const double *now_goal /*n*3*/);
 
+/* The same lists in SLOT form (Agent.path, agent.py:44; the rule above is unchanged): every agent row owns room for points_per_agent
+ * waypoints, so a row's list has a place that depends on no other row's and sca_restart_scenes_paths (below) can replace the lists of one
+ * scene while the others keep running -- the block form above is one CSR block for the whole context and cannot.  An episode fits if its
+ * longest list is at most points_per_agent.  Costs 24 * points_per_agent bytes of device memory per row of sca_create's max_agents.  Detect
+ * the feature by the symbol (sca_version() is unchanged).
+ *   sca_set_path_slots  sca_set_paths' rules and refusals, the partition's included, over the same CSR arguments; offsets == NULL: every
+ *                       list empty.  Additionally SCA_ERR_ARG, nothing changed: points_per_agent < 1, a list longer than it, or
+ *                       points_per_agent * max_agents above 2^31 / 3 points (not addressable).  Resets every cursor to the full list and
+ *                       now_goal to None.  Works wherever sca_set_paths works -- with or without scenes, shards, bursts (sca_run_steps),
+ *                       sca_step_host, SCA_NBR_GRID, the host build -- because it is per agent: kernel k_waypoint_slots has k_waypoint's
+ *                       place at the head of the pass and its body.
+ *   sca_get_path_slots  *points_per_agent = the room per row, 0 while the context is not in slot form.
+ * sca_set_paths on a context in slot form puts it back into block form; sca_set_paths(0 / NULL) and sca_set_agents clear either form.
+ * sca_get_path_state / sca_set_path_state, the sca_set_vpref rule, SCA_FORM_WAYPOINTS and the partition's refusals are those of the block form. */
+int sca_set_path_slots(sca_ctx *ctx, int points_per_agent, int n, const int32_t *offsets /*n+1, nullable: every list empty*/,
+                       const double *points /*offsets[n]*3*/);
+int sca_get_path_slots(sca_ctx *ctx, int *points_per_agent);
+
 /* Scene batches: ONE context steps many isolated episodes.  Scene s is the contiguous agent range [offsets[s], offsets[s+1]); agents of
  * different scenes never appear in each other's neighbour lists or collision tests, every scene has its own kd-tree, its own carried
  * permutation and its own `done`, and for every scene every value the context produces is bit for bit what a context holding that scene
@@ -229,7 +249,8 @@ int sca_set_scene_obstacles(sca_ctx *ctx, int nscenes, const int32_t *obs_offset
  *   refusals   SCA_ERR_STATE: no scenes, no state yet, between a policy pass and its env update.  SCA_ERR_ARG: count <= 0 or scene_ids
  *              NULL, an id outside 0 .. nscenes-1, a repeated id, pos or heading NULL, any number that is not finite, a policy above
  *              SCA_POLICY_RVO3D_DUBINS, a radius / pref_speed / max_run_dist that is not positive, goal_heading without a device tracker.
- *              SCA_ERR_UNSUPPORTED: waypoint lists are set (sca_set_paths: one block for all agents), or a policy that moves an agent
+ *              SCA_ERR_UNSUPPORTED: waypoint lists are set in block form (sca_set_paths: one block for all agents; in slot form,
+ *              sca_set_path_slots, every restart entry point is accepted -- see sca_restart_scenes_paths), or a policy that moves an agent
  *              between tracked (SCA, RVO3D+Dubins) and untracked while per-agent tracker attributes are set (their classes are cut by
  *              policy).  A refused call has changed nothing.
  *   cost       one kernel launch and one stream synchronisation however many scenes are named (one more small copy where a policy changed
@@ -361,6 +382,32 @@ typedef struct sca_restart_attrs {
 int sca_restart_scenes_attrs(sca_ctx *ctx, int count, const int32_t *scene_ids /*count*/, const int32_t *sizes /*count, nullable: capacities*/,
                              const int32_t *obs_counts /*count, nullable*/, const double *obs_pos, const double *obs_radius,
                              const sca_restart_attrs *attrs /*nullable: the slots keep their attributes*/,
+                             const double *pos /*T*3*/, const float *vel /*T*3, nullable: zero*/, const double *heading /*T*3*/,
+                             const double *radius, const double *pref_speed, const double *goal /*T*3*/, const uint8_t *policy,
+                             const uint8_t *zaxis, const double *max_run_dist,      /* each T, each nullable: keep the slot's */
+                             const double *goal_heading /*T*3, nullable: keep the slot's*/);
+
+/* A restarted slot takes the episode's own WAYPOINT LISTS (Agent.path, agent.py:44; every reference policy's find_next_action starts with
+ * get_trajectory, e.g. rvo3dPolicy.py:71-85), so that a table whose scenarios route the drones through waypoints streams through one set of
+ * slots.  The context's lists must be in slot form (sca_set_path_slots).  Detect the feature by the symbol (sca_version() is unchanged).
+ *   sca_restart_scenes_paths   sca_restart_scenes_attrs plus the lists.  path_offsets: CSR over the call's T packed rows, packed like pos
+ *              (row r's list is path_points[3*path_offsets[r] .. 3*path_offsets[r+1]) in list order).  path_offsets == NULL: exactly
+ *              sca_restart_scenes_attrs.  In slot form EVERY restart entry point is accepted, and a call without path arrays gives the named
+ *              rows empty lists: the episode brings none.  In block form SCA_ERR_UNSUPPORTED stays for every entry point.
+ *              The scene contract extends: after the call a named scene is bit for bit a context of that episode alone after
+ *              sca_set_agents + ... + sca_set_paths(those lists) + sca_set_state -- everything listed at sca_restart_scenes_attrs, and
+ *              `remaining`, now_goal and the v_pref every pass uses -- and no other scene can tell the call happened.  Occupied rows get
+ *              remaining = the list's length and now_goal = None; vacant rows remaining 0 and None.
+ *   refusals   those of sca_restart_scenes_attrs, and SCA_ERR_STATE: path arrays while the context is not in slot form; SCA_ERR_ARG:
+ *              path_offsets[0] != 0, offsets that decrease, a row's list longer than the room per row, path_points NULL with points to
+ *              read, a point that is not finite (the message names the packed row).  A refused call has changed nothing.
+ *   cost       still one kernel launch and one stream synchronisation however many scenes are named: the offsets and the points actually
+ *              present travel packed in the page-locked block (which grows once when slot form, or a larger room, arrives after the
+ *              first restart) and the kernel scatters them to the rows' rooms. */
+int sca_restart_scenes_paths(sca_ctx *ctx, int count, const int32_t *scene_ids /*count*/, const int32_t *sizes /*count, nullable: capacities*/,
+                             const int32_t *obs_counts /*count, nullable*/, const double *obs_pos, const double *obs_radius,
+                             const sca_restart_attrs *attrs /*nullable: the slots keep their attributes*/,
+                             const int32_t *path_offsets /*T+1, nullable: no lists*/, const double *path_points /*path_offsets[T]*3*/,
                              const double *pos /*T*3*/, const float *vel /*T*3, nullable: zero*/, const double *heading /*T*3*/,
                              const double *radius, const double *pref_speed, const double *goal /*T*3*/, const uint8_t *policy,
                              const uint8_t *zaxis, const double *max_run_dist,      /* each T, each nullable: keep the slot's */

@@ -86,6 +86,9 @@ SIGNATURES = {
     'sca_get_scene_obstacle_counts': (C.c_int, [C.c_void_p, ip, ip]),
     'sca_restart_scenes_obstacles': (C.c_int, [C.c_void_p, C.c_int, ip, ip, ip, dp, dp, dp, fp, dp, dp, dp, dp, bp, bp, dp, dp]),
     'sca_restart_scenes_attrs': (C.c_int, [C.c_void_p, C.c_int, ip, ip, ip, dp, dp, C.POINTER(RestartAttrs), dp, fp, dp, dp, dp, dp, bp, bp, dp, dp]),
+    'sca_restart_scenes_paths': (C.c_int, [C.c_void_p, C.c_int, ip, ip, ip, dp, dp, C.POINTER(RestartAttrs), ip, dp, dp, fp, dp, dp, dp, dp, bp, bp, dp, dp]),
+    'sca_set_path_slots': (C.c_int, [C.c_void_p, C.c_int, C.c_int, ip, dp]),
+    'sca_get_path_slots': (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     'sca_scene_history_enable': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_scene_history_rows': (C.c_int, [C.c_void_p, ip, ip]),
     'sca_get_scene_history': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, fp]),

@@ -266,6 +266,30 @@ SCA_HD V3 waypoint_advance(const double *pts, int32_t &rem, V3 now_goal, V3 pos,
     }
     return now_goal;
 }
+// One agent's get_trajectory and the v_pref it leads to: the body k_waypoint and k_waypoint_slots (sca_kernels.hip.h) share, over "where
+// is my list and had it elements as set" -- the CSR block of sca_set_paths, or the row's own room of sca_set_path_slots.  View: the
+// per-agent arrays read and written here (DeviceView; a plain struct of the same members in tests/scene_paths_harness.cpp); rem [n] and
+// now_goal [n * 3] are the cursors of either form.  The straight-line agents that have a path get compute_v_pref(now_goal, agent) through
+// the external channel (vpref_ext, vpref_mode = 1); the tracked agents' lists advance and their v_pref stays the tracker's.
+template <class View>
+SCA_HD void waypoint_agent(const View &d, int agent, const double *list, bool has_path, int32_t *rem_of, double *now_goal_of) {
+    const PubRec me = d.rec[agent];
+    if (me.flags & (FLAG_AT_GOAL | FLAG_COLLISION | FLAG_TIMEOUT)) return;
+    const int pol = d.policy[agent];
+    const bool orca = (pol == POL_ORCA || pol == POL_ORCA_LP);
+    const V3 pA = v3(me.px, me.py, me.pz);
+    const V3 goal = v3(d.goal[agent * 3], d.goal[agent * 3 + 1], d.goal[agent * 3 + 2]);
+    int32_t rem = rem_of[agent];
+    V3 ng = v3(now_goal_of[agent * 3], now_goal_of[agent * 3 + 1], now_goal_of[agent * 3 + 2]);
+    ng = waypoint_advance(list, rem, ng, pA, goal, me.radius, orca);
+    rem_of[agent] = rem;
+    now_goal_of[agent * 3] = ng.x; now_goal_of[agent * 3 + 1] = ng.y; now_goal_of[agent * 3 + 2] = ng.z;
+    if (has_path && pol != POL_SCA && pol != POL_RVO_DUBINS) {
+        const V3 vp = straight_v_pref2(ng, goal, pA, d.pref_speed[agent], orca);
+        d.vpref_ext[agent * 3] = vp.x; d.vpref_ext[agent * 3 + 1] = vp.y; d.vpref_ext[agent * 3 + 2] = vp.z;
+        d.vpref_mode[agent] = 1;
+    }
+}
 
 // ---- posture constraint (util.py:6-20) -----------------------------------------------------------
 // Returns the clamped cosine; the caller compares it with Params::cos_heading_thr, which is the exact

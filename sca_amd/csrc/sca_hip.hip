@@ -292,6 +292,12 @@ struct sca_ctx {
     size_t path_pts_cap = 0;            // doubles path.pts holds
     std::vector<int32_t> h_path_off;    // [n + 1] the CSR offsets as set
     std::vector<uint8_t> h_path_vpref;  // [n] 1: a straight-line agent with a path -- k_waypoint writes its v_pref (vpref_mode = 1)
+    // the lists in slot form (sca_set_path_slots): path_W > 0, k_waypoint_slots runs instead; the cursors are path.rem / path.now_goal
+    int path_W = 0;                     // room per agent row, in waypoints
+    double *pslot_pts = nullptr;        // [3 * pslot_cap] row a's room from 3 * path_slot_index(path_W, a)
+    size_t pslot_cap = 0;               // points pslot_pts holds (>= path_W * max_n)
+    int32_t *pslot_len = nullptr;       // [max_n] the lists' lengths as set
+    std::vector<int32_t> h_path_len;    // [n] host mirror of pslot_len (sca_set_path_state's bound; follows a restart behind its synchronisation)
     // pinned host state block (sca_host_state_get / sca_step_host): allocated once for max_n, freed by sca_destroy
     uint8_t *hs_host = nullptr;         // page-locked, the caller reads and writes it in place
     uint8_t *hs_dev = nullptr;          // the staging buffer of the staged form (Tunables::hs_staged): same size and layout
@@ -312,6 +318,7 @@ struct sca_ctx {
         std::vector<int32_t> h_obs_off; // [nscenes + 1] the obstacle offsets as set: each scene's range is its capacity (sca_set_scene_obstacle_slots)
         std::vector<int32_t> h_obs_count; // [nscenes] the obstacles each scene holds in the first rows of its range; the device's copy stands behind ov.oroot
         uint8_t *rs_host = nullptr;     // sca_restart_scenes' page-locked staging block (RestartLayout of max_n, sca_scenes.h), allocated on first use
+        size_t rs_bytes = 0;            // ... and its size: it grows when the lists' slot form, or a larger room per row, arrives later
         SceneLogView log{};             // the trajectory log per scene (sca_scene_history_enable), rows null: off -- a step then enqueues nothing for it
         uint8_t *hv_host = nullptr;     // the harvest block (sca_scene_harvest_enable; HarvestLayout of nscenes and n, sca_scenes.h), null: off -- a step then enqueues nothing for it
         HarvestLayout hv_layout{};
@@ -320,7 +327,7 @@ struct sca_ctx {
             for (void *p : {(void *)v.scene_of, (void *)v.offsets, (void *)counters, (void *)v.heading_keep, (void *)ov.oroot, (void *)log.rows, (void *)size}) if (p) (void)hipFree(p);
             if (rs_host) (void)hipHostFree(rs_host);
             if (hv_host) (void)hipHostFree(hv_host);
-            v = SceneView{}; counters = nullptr; size = nullptr; ov = SceneObsView{}; rs_host = nullptr; log = SceneLogView{}; hv_host = nullptr;
+            v = SceneView{}; counters = nullptr; size = nullptr; ov = SceneObsView{}; rs_host = nullptr; rs_bytes = 0; log = SceneLogView{}; hv_host = nullptr;
         }
     } scenes;
     std::vector<uint8_t> h_policy;      // [n] the agents' policies as they stand (sca_set_agents, sca_restart_scenes)
@@ -922,7 +929,7 @@ void sca_destroy(sca_ctx *c) {
     if (c->comm) { (void)hipStreamSynchronize(c->stream); (void)g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
     (void)tracker_free(c);
     (void)part_free(c);
-    for (void *p : {(void *)c->path.off, (void *)c->path.pts, (void *)c->path.rem, (void *)c->path.now_goal}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->path.off, (void *)c->path.pts, (void *)c->path.rem, (void *)c->path.now_goal, (void *)c->pslot_pts, (void *)c->pslot_len}) if (p) (void)hipFree(p);
     c->scenes.release();
     if (c->h_done) { (void)hipHostFree(c->h_done); c->h_done = nullptr; }
     if (c->hs_host) { (void)hipHostFree(c->hs_host); c->hs_host = nullptr; }
@@ -1275,7 +1282,15 @@ static int paths_clear(sca_ctx *c, bool reset_mode) {
         CHK(c, hipStreamSynchronize(c->stream));
     }
     c->paths_on = false;
-    c->h_path_off.clear(); c->h_path_vpref.clear();
+    c->path_W = 0;
+    c->h_path_off.clear(); c->h_path_vpref.clear(); c->h_path_len.clear();
+    return 0;
+}
+// the cursors both forms of the lists share
+static int paths_alloc_cursors(sca_ctx *c) {
+    if (c->path.rem) return 0;
+    CHK(c, hipMalloc((void **)&c->path.rem, sizeof(int32_t) * (size_t)c->max_n));
+    CHK(c, hipMalloc((void **)&c->path.now_goal, sizeof(double) * 3 * (size_t)c->max_n));
     return 0;
 }
 int sca_set_paths(sca_ctx *c, int n, const int32_t *offsets, const double *points) {
@@ -1297,11 +1312,8 @@ int sca_set_paths(sca_ctx *c, int n, const int32_t *offsets, const double *point
     CHK(c, hipStreamSynchronize(c->stream));
     if (int r = paths_clear(c, true)) return r;
     PathView &w = c->path;
-    if (!w.off) {
-        CHK(c, hipMalloc((void **)&w.off, sizeof(int32_t) * ((size_t)c->max_n + 1)));
-        CHK(c, hipMalloc((void **)&w.rem, sizeof(int32_t) * (size_t)c->max_n));
-        CHK(c, hipMalloc((void **)&w.now_goal, sizeof(double) * 3 * (size_t)c->max_n));
-    }
+    if (!w.off) CHK(c, hipMalloc((void **)&w.off, sizeof(int32_t) * ((size_t)c->max_n + 1)));
+    if (int r = paths_alloc_cursors(c)) return r;
     if (3 * total > c->path_pts_cap || !w.pts) {
         if (w.pts) { (void)hipFree((void *)w.pts); w.pts = nullptr; c->path_pts_cap = 0; }
         CHK(c, hipMalloc((void **)&w.pts, sizeof(double) * std::max<size_t>(3 * total, 3)));
@@ -1322,6 +1334,69 @@ int sca_set_paths(sca_ctx *c, int n, const int32_t *offsets, const double *point
     c->paths_on = true;
     return 0;
 }
+// The lists in slot form (include/sca_hip.h): sca_set_paths' rules and refusals plus the room's (path_slots_check, sca_scenes.h).  The rows'
+// rooms are uploaded as one block built on the host; room behind a list's length is never read (rem <= len).
+int sca_set_path_slots(sca_ctx *c, int points_per_agent, int n, const int32_t *offsets, const double *points) {
+    API_ENTER(c);
+    const int W = points_per_agent;
+    const PathSlotCheck k = path_slots_check(c->agents_set, c->part_on, c->n, c->max_n, W, n, offsets, points);
+    if (k.fault != PATH_SLOTS_OK) {
+        const std::string at = std::to_string(k.entry);
+        switch (k.fault) {
+        case PATH_SLOTS_NO_AGENTS: c->err = "sca_set_agents first"; break;
+        case PATH_SLOTS_PARTITION: c->err = "sca_set_path_slots under the cell-owner partition: path state does not migrate with the agents"; break;
+        case PATH_SLOTS_BAD_N: c->err = "sca_set_path_slots: n = " + std::to_string(n) + " is not the agent count " + std::to_string(c->n); break;
+        case PATH_SLOTS_BAD_W: c->err = "sca_set_path_slots: points_per_agent = " + std::to_string(W) + " must be at least 1"; break;
+        case PATH_SLOTS_TOO_LARGE: c->err = "sca_set_path_slots: points_per_agent = " + std::to_string(W) + " x max_agents = " + std::to_string(c->max_n) + " points are not addressable (at most " +
+                                            std::to_string(PATH_SLOT_POINTS_MAX) + ")"; break;
+        case PATH_SLOTS_BAD_START: c->err = "sca_set_path_slots: offsets[0] must be 0"; break;
+        case PATH_SLOTS_DECREASING: c->err = "sca_set_path_slots: offsets decrease at agent " + at; break;
+        case PATH_SLOTS_TOO_LONG: c->err = "sca_set_path_slots: agent " + at + " has a list of " + std::to_string(offsets[k.entry + 1] - offsets[k.entry]) + " waypoints, its row has room for " + std::to_string(W); break;
+        case PATH_SLOTS_NO_POINTS: c->err = "sca_set_path_slots: points is NULL"; break;
+        default: c->err = "sca_set_path_slots: waypoint " + at + " is not finite";
+        }
+        return path_slots_error_code(k.fault);
+    }
+    std::vector<uint8_t> pol((size_t)n);
+    CHK(c, hipStreamSynchronize(c->stream));
+    CHK(c, hipMemcpyAsync(pol.data(), c->d.policy, n, hipMemcpyDeviceToHost, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    if (int r = paths_clear(c, true)) return r;
+    if (int r = paths_alloc_cursors(c)) return r;
+    const size_t room = (size_t)W * (size_t)c->max_n;
+    if (room > c->pslot_cap || !c->pslot_pts) {
+        if (c->pslot_pts) { (void)hipFree(c->pslot_pts); c->pslot_pts = nullptr; c->pslot_cap = 0; }
+        CHK(c, hipMalloc((void **)&c->pslot_pts, sizeof(double) * 3 * room));
+        c->pslot_cap = room;
+        CHK(c, hipMemsetAsync(c->pslot_pts, 0, sizeof(double) * 3 * room, c->stream));
+    }
+    if (!c->pslot_len) CHK(c, hipMalloc((void **)&c->pslot_len, sizeof(int32_t) * (size_t)c->max_n));
+    std::vector<int32_t> len((size_t)n, 0);
+    std::vector<double> rooms(3 * (size_t)W * (size_t)n, 0.0);
+    if (offsets)
+        for (int i = 0; i < n; i++) {
+            len[i] = offsets[i + 1] - offsets[i];
+            if (len[i]) std::memcpy(rooms.data() + 3 * path_slot_index(W, i), points + 3 * (size_t)offsets[i], sizeof(double) * 3 * (size_t)len[i]);
+        }
+    const std::vector<double> none(3 * (size_t)n, std::numeric_limits<double>::quiet_NaN());
+    if (k.total) CHK(c, hipMemcpyAsync(c->pslot_pts, rooms.data(), sizeof(double) * rooms.size(), hipMemcpyHostToDevice, c->stream));
+    CHK(c, hipMemcpyAsync(c->pslot_len, len.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
+    CHK(c, hipMemcpyAsync(c->path.rem, len.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
+    CHK(c, hipMemcpyAsync(c->path.now_goal, none.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    c->h_path_vpref.assign((size_t)n, 0);
+    for (int i = 0; i < n; i++) c->h_path_vpref[i] = len[i] > 0 && pol[i] != SCA_POLICY_SCA && pol[i] != SCA_POLICY_RVO3D_DUBINS;
+    c->h_path_len.swap(len);
+    c->path_W = W;
+    c->paths_on = true;
+    return 0;
+}
+int sca_get_path_slots(sca_ctx *c, int *points_per_agent) {
+    API_ENTER(c);
+    ARG(c, points_per_agent);
+    *points_per_agent = c->path_W;
+    return 0;
+}
 int sca_get_path_state(sca_ctx *c, int32_t *remaining, double *now_goal) {
     API_ENTER(c);
     if (!c->paths_on) { c->err = "no waypoint lists (sca_set_paths)"; return SCA_ERR_STATE; }
@@ -1337,7 +1412,7 @@ int sca_set_path_state(sca_ctx *c, const int32_t *remaining, const double *now_g
     ARG(c, remaining && now_goal);
     const int n = c->n;
     for (int i = 0; i < n; i++) {
-        if (remaining[i] < 0 || remaining[i] > c->h_path_off[i + 1] - c->h_path_off[i]) {
+        if (remaining[i] < 0 || remaining[i] > (c->path_W ? c->h_path_len[i] : c->h_path_off[i + 1] - c->h_path_off[i])) {
             c->err = "sca_set_path_state: remaining[" + std::to_string(i) + "] is outside 0 .. the length of the agent's list"; return SCA_ERR_ARG;
         }
         const double *g = now_goal + 3 * (size_t)i;
@@ -1622,12 +1697,12 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
                           const double *radius, const double *pref_speed, const double *goal, const uint8_t *policy, const uint8_t *zaxis,
                           const double *max_run_dist, const double *goal_heading,
                           const int32_t *obs_counts = nullptr, const double *obs_pos = nullptr, const double *obs_radius = nullptr,
-                          const sca_restart_attrs *attrs = nullptr) {
+                          const sca_restart_attrs *attrs = nullptr, const int32_t *path_offsets = nullptr, const double *path_points = nullptr) {
     RestartArgs A{count, scene_ids, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading};
     A.sizes = sizes;
     // (with `attrs` a policy may move an agent between tracked and untracked: the classes are recomputed below, not cut by policy)
     const RestartCtx X{c->scenes.on ? c->scenes.v.nscenes : 0, c->scenes.on ? c->scenes.h_off.data() : nullptr, c->state_set, c->scenes.begun, c->trk_on,
-                       c->paths_on, !attrs && c->trk_on && c->trk_view.R_pa != nullptr, c->h_policy.data()};
+                       restart_refuses_paths(c->paths_on, c->path_W > 0), !attrs && c->trk_on && c->trk_view.R_pa != nullptr, c->h_policy.data()};
     const RestartCheck k = scene_restart_check(X, A);
     if (k.fault != RESTART_OK) {
         const std::string at = std::to_string(k.entry);
@@ -1682,15 +1757,39 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
             return restart_attrs_error_code(ka.fault);
         }
     }
+    // the episodes' waypoint lists (sca_restart_scenes_paths): in slot form every entry point is accepted, and a call without path arrays
+    // gives the named rows empty lists
+    const bool path_slots = c->path_W > 0;
+    const RestartPathCheck kp = restart_paths_check(path_slots, c->path_W, k.total, path_offsets, path_points);
+    if (kp.fault != RESTART_PATHS_OK) {
+        const std::string at = std::to_string(kp.entry);
+        switch (kp.fault) {
+        case RESTART_PATHS_NO_SLOTS: c->err = "sca_restart_scenes_paths: path arrays, but the context's lists are not in slot form -- sca_set_path_slots first"; break;
+        case RESTART_PATHS_BAD_START: c->err = "sca_restart_scenes_paths: path_offsets[0] must be 0"; break;
+        case RESTART_PATHS_DECREASING: c->err = "sca_restart_scenes_paths: path_offsets decrease at row " + at; break;
+        case RESTART_PATHS_TOO_LONG: c->err = "sca_restart_scenes_paths: row " + at + " brings a list of " + std::to_string(path_offsets[kp.entry + 1] - path_offsets[kp.entry]) +
+                                              " waypoints, a row has room for " + std::to_string(c->path_W) + " (sca_set_path_slots)"; break;
+        case RESTART_PATHS_NO_POINTS: c->err = "sca_restart_scenes_paths: path_points is NULL with " + std::to_string(kp.total) + " waypoints"; break;
+        default: c->err = "sca_restart_scenes_paths: row " + at + " has a waypoint that is not finite";
+        }
+        return restart_paths_error_code(kp.fault);
+    }
     const int T = k.total;
     const RestartLayout L = scene_restart_layout(c->max_n);
     const size_t sizes_end = (size_t)L.total + sizeof(int32_t) * (size_t)c->max_n;  // behind the layout's sections: the named scenes' new sizes ...
     const RestartObsLayout OL = restart_obstacles_layout((int64_t)sizes_end, c->max_n, c->max_m);      // ... and behind those the obstacle sections
     const RestartAttrLayout AL = restart_attrs_layout(OL.total, c->max_n);                             // ... and behind those the attribute sections
-    const size_t blk_bytes = (size_t)AL.total;
+    const RestartPathLayout PL = restart_paths_layout(AL.total, c->max_n, c->path_W);                  // ... and behind those the path sections (none: not in slot form)
+    const size_t blk_bytes = (size_t)PL.total;
+    if (c->scenes.rs_host && c->scenes.rs_bytes < blk_bytes) {                   // the slot form, or a larger room per row, arrived behind the first restart: the
+        CHK(c, hipStreamSynchronize(c->stream));                                 // block grows (every call ends with its synchronisation: no launch still reads it)
+        (void)hipHostFree(c->scenes.rs_host);
+        c->scenes.rs_host = nullptr; c->scenes.rs_bytes = 0;
+    }
     if (!c->scenes.rs_host) {                                                    // mapped and coherent, as the host state block is: the kernel reads it in place
         CHK(c, hipHostMalloc((void **)&c->scenes.rs_host, blk_bytes, hipHostMallocMapped | hipHostMallocCoherent));
         std::memset(c->scenes.rs_host, 0, blk_bytes);
+        c->scenes.rs_bytes = blk_bytes;
     }
     uint8_t *b = c->scenes.rs_host;
     int32_t *ids = (int32_t *)(b + L.off[RS_IDS]), *start = (int32_t *)(b + L.off[RS_START]), *new_size = (int32_t *)(b + L.total);
@@ -1720,6 +1819,14 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
     put(RS_PREF_SPEED, pref_speed, sizeof(double) * (size_t)T, RESTART_HAS_PREF_SPEED);
     put(RS_MAX_RUN_DIST, max_run_dist, sizeof(double) * (size_t)T, RESTART_HAS_MAX_RUN_DIST);
     put(RS_ZAXIS, zaxis, (size_t)T, RESTART_HAS_ZAXIS);
+    if (path_slots) {                                                  // the lists travel packed: the offsets and the points actually present
+        has |= RESTART_HAS_PATH_SLOTS;
+        if (path_offsets) {
+            std::memcpy(b + PL.off[RP_OFF], path_offsets, sizeof(int32_t) * ((size_t)T + 1));
+            if (kp.total) std::memcpy(b + PL.off[RP_PTS], path_points, sizeof(double) * 3 * (size_t)kp.total);
+            has |= RESTART_HAS_PATHS;
+        }
+    }
     double obs_max_r = 0;
     {                                                                  // every named scene's head words, and the replaced scenes' trees, built where the kernel reads them
         int32_t *head = (int32_t *)(b + OL.off[RO_HEAD]);
@@ -1859,7 +1966,8 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
     // pointers are null: restart_obstacles_check has refused every count >= 0, so the kernel returns before it reads them.
     RestartObsDev o{};
     if (c->scenes.obs_on) o = RestartObsDev{c->d.obs, c->d.obs_sorted, c->d.operm, c->d.otree, c->d.owide, (int32_t *)c->scenes.ov.oroot, (int32_t *)c->scenes.ov.oroot + c->scenes.v.nscenes};
-    hipLaunchKernelGGL(k_scene_restart, dim3(count), dim3(RESTART_T), 0, c->stream, d, (const uint8_t *)b, L, has, (const int32_t *)new_size, c->scenes.size, o, OL, at_dev, AL);
+    hipLaunchKernelGGL(k_scene_restart, dim3(count), dim3(RESTART_T), 0, c->stream, d, (const uint8_t *)b, L, has, (const int32_t *)new_size, c->scenes.size, o, OL, at_dev, AL,
+                       RestartPathDev{c->pslot_pts, c->pslot_len, c->path.rem, c->path.now_goal, c->path_W}, PL);
     CHK(c, hipGetLastError());
     // the classes came back from the per-agent form, or an index moved in a scene that was not named: the whole class array, one byte per
     // agent, behind the launch (its rows of the named scenes are the bytes the launch wrote) and in front of the call's one synchronisation
@@ -1889,6 +1997,12 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
             if (pref_speed) c->max_pref_speed = std::max(c->max_pref_speed, pref_speed[r]);
         }
         for (int a = off[scene_ids[e]]; a < off[scene_ids[e] + 1]; a++) c->h_perm[a] = a;        // (the vacant rows' too: the identity over the capacity)
+        if (path_slots)                                               // the lists' lengths and the "straight-line agent with a path" bytes (sca_set_vpref, paths_clear)
+            for (int a = off[scene_ids[e]], r = start[e]; a < off[scene_ids[e] + 1]; a++, r++) {
+                const int32_t len = path_offsets && a < off[scene_ids[e]] + new_size[e] ? path_offsets[r + 1] - path_offsets[r] : 0;
+                c->h_path_len[a] = len;
+                c->h_path_vpref[a] = len > 0 && !restart_policy_tracked(pol[r]);       // (len > 0: an occupied row, pol[r] is its policy)
+            }
     }
     if (policy_changed || size_changed) c->h_lp_list.swap(lp_new);
     c->scenes.h_size.swap(size_now);
@@ -1963,6 +2077,14 @@ int sca_restart_scenes_attrs(sca_ctx *c, int count, const int32_t *scene_ids, co
     API_ENTER(c);
     return restart_scenes(c, count, scene_ids, sizes, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading, obs_counts, obs_pos, obs_radius,
                           attrs);
+}
+int sca_restart_scenes_paths(sca_ctx *c, int count, const int32_t *scene_ids, const int32_t *sizes, const int32_t *obs_counts, const double *obs_pos,
+                             const double *obs_radius, const sca_restart_attrs *attrs, const int32_t *path_offsets, const double *path_points,
+                             const double *pos, const float *vel, const double *heading, const double *radius, const double *pref_speed, const double *goal,
+                             const uint8_t *policy, const uint8_t *zaxis, const double *max_run_dist, const double *goal_heading) {
+    API_ENTER(c);
+    return restart_scenes(c, count, scene_ids, sizes, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading, obs_counts, obs_pos, obs_radius,
+                          attrs, path_offsets, path_points);
 }
 int sca_get_scene_sizes(sca_ctx *c, int32_t *size) {
     API_ENTER(c);
@@ -2370,7 +2492,10 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
     // an AUTO build enqueued ahead (aux) computes no prologue.
     if (c->paths_on) {
         if (fork_ready) { c->err = "internal: a fork recorded ahead of k_waypoint"; return SCA_ERR_STATE; }
-        if (d.shard_count > 0) hipLaunchKernelGGL(k_waypoint, dim3((d.shard_count + 255) / 256), dim3(256), 0, c->stream, c->d, c->path);
+        if (d.shard_count > 0 && c->path_W)
+            hipLaunchKernelGGL(k_waypoint_slots, dim3((d.shard_count + 255) / 256), dim3(256), 0, c->stream, c->d,
+                               PathSlotView{c->pslot_pts, c->pslot_len, c->path.rem, c->path.now_goal, c->path_W});
+        else if (d.shard_count > 0) hipLaunchKernelGGL(k_waypoint, dim3((d.shard_count + 255) / 256), dim3(256), 0, c->stream, c->d, c->path);
     }
     const unsigned parity_now = (unsigned)c->trk.parity;
     if (overlap) {

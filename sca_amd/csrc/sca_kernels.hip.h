@@ -20,6 +20,7 @@
 
 #include "sca_core.h"
 #include "sca_constants.h"
+#include "sca_scenes.h"
 
 namespace sca {
 
@@ -1807,6 +1808,7 @@ __global__ __launch_bounds__(64) void k_lp(DeviceView d, Params Pctx, const int3
 
 // Waypoint lists (Agent.path, agent.py:44), set by sca_set_paths: agent i's list is pts[3 * off[i] .. 3 * off[i + 1]) in list order, of
 // which the first rem[i] are still in it; now_goal [n * 3] is policy.now_goal (NaN: None).  Kept out of DeviceView: no other kernel reads it.
+// This is the BLOCK form; the slot form (PathSlotView, below) shares rem and now_goal with it.
 struct PathView {
     const int32_t *off;      // [n + 1]
     const double *pts;       // [3 * off[n]]
@@ -1820,24 +1822,25 @@ struct PathView {
 __global__ __launch_bounds__(256) void k_waypoint(DeviceView d, PathView w) {
     const int agent = d.shard_begin + (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (agent >= d.shard_begin + d.shard_count) return;
-    const PubRec me = d.rec[agent];
-    if (me.flags & (FLAG_AT_GOAL | FLAG_COLLISION | FLAG_TIMEOUT)) return;
-    const int pol = d.policy[agent];
-    const bool orca = (pol == POL_ORCA || pol == POL_ORCA_LP);
-    const V3 pA = v3(me.px, me.py, me.pz);
-    const V3 goal = v3(d.goal[agent * 3], d.goal[agent * 3 + 1], d.goal[agent * 3 + 2]);
     const int o = w.off[agent];
-    const bool has_path = w.off[agent + 1] > o;
-    int32_t rem = w.rem[agent];
-    V3 ng = v3(w.now_goal[agent * 3], w.now_goal[agent * 3 + 1], w.now_goal[agent * 3 + 2]);
-    ng = waypoint_advance(w.pts + 3 * (size_t)o, rem, ng, pA, goal, me.radius, orca);
-    w.rem[agent] = rem;
-    w.now_goal[agent * 3] = ng.x; w.now_goal[agent * 3 + 1] = ng.y; w.now_goal[agent * 3 + 2] = ng.z;
-    if (has_path && pol != POL_SCA && pol != POL_RVO_DUBINS) {
-        const V3 vp = straight_v_pref2(ng, goal, pA, d.pref_speed[agent], orca);
-        d.vpref_ext[agent * 3] = vp.x; d.vpref_ext[agent * 3 + 1] = vp.y; d.vpref_ext[agent * 3 + 2] = vp.z;
-        d.vpref_mode[agent] = 1;
-    }
+    waypoint_agent(d, agent, w.pts + 3 * (size_t)o, w.off[agent + 1] > o, w.rem, w.now_goal);
+}
+
+// The lists in SLOT form (sca_set_path_slots): every agent row owns room for W waypoints, its list is pts[3 * W * a .. 3 * (W * a + len[a]))
+// (path_slot_index, sca_scenes.h), so a row's list has a place that depends on no other row's and a restart (k_scene_restart) rewrites the
+// rows of a scene alone.  len [n] is the length as set, where the block form reads two offsets.  Same place at the head of the pass and
+// the same body as k_waypoint (waypoint_agent, sca_core.h).
+struct PathSlotView {
+    const double *pts;       // [3 * W * max_agents]
+    const int32_t *len;      // [n] the list's length as set, <= W
+    int32_t *rem;            // [n]
+    double *now_goal;        // [n * 3]
+    int W;
+};
+__global__ __launch_bounds__(256) void k_waypoint_slots(DeviceView d, PathSlotView w) {
+    const int agent = d.shard_begin + (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (agent >= d.shard_begin + d.shard_count) return;
+    waypoint_agent(d, agent, w.pts + 3 * path_slot_index(w.W, agent), w.len[agent] > 0, w.rem, w.now_goal);
 }
 
 __global__ __launch_bounds__(256) void k_prep(DeviceView d, Params P) {

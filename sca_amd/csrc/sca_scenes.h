@@ -3,6 +3,8 @@
 //
 // One context holds B scenes; scene s is the contiguous agent range [offsets[s], offsets[s + 1]).  Each scene is one job of k_kd_block
 // (its whole tree by one workgroup in LDS), hence at most KD_WAVE_CAP agents per scene.
+// Also here, because a restart is what needs them: the rules of the waypoint lists' slot form (sca_set_path_slots), which works with or
+// without scenes.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -521,6 +523,113 @@ inline int class_table_used(const ClassTable &tab, int *only) {
     if (only) *only = used == 1 ? last : -1;
     return used;
 }
+
+// ---- waypoint lists in slot form (sca_set_path_slots) and a restart that brings lists (sca_restart_scenes_paths) -----------------------------------
+// In slot form every agent row owns room for W waypoints: row a's list is pts[3 * (W * a + j)], j < len[a] <= W.  A row's list has a place
+// that depends on nothing else, so a restart writes the rows of a scene independently and nothing is compacted; an episode fits a slot if
+// its longest list is at most W.  The price is 24 * W bytes per agent row.
+// the first point of row a's room, in points from the allocation's start.  The kernels that read and write and the host that uploads call this.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int64_t path_slot_index(int W, int a) { return (int64_t)W * (int64_t)a; }
+// W * max_agents points must stay addressable: every coordinate index 3 * (W * a + j) below 2^31
+constexpr int64_t PATH_SLOT_POINTS_MAX = INT32_MAX / 3;
+inline bool path_slots_addressable(int W, int max_agents) { return (int64_t)W * (int64_t)max_agents <= PATH_SLOT_POINTS_MAX; }
+
+enum PathSlotFault {
+    PATH_SLOTS_OK = 0,
+    PATH_SLOTS_NO_AGENTS,   // before sca_set_agents                                                            SCA_ERR_STATE
+    PATH_SLOTS_PARTITION,   // under the cell-owner partition: path state does not migrate with the agents     SCA_ERR_UNSUPPORTED
+    PATH_SLOTS_BAD_N,       // n is not the context's agent count                                              } SCA_ERR_ARG
+    PATH_SLOTS_BAD_W,       // points_per_agent < 1                                                            }
+    PATH_SLOTS_TOO_LARGE,   // points_per_agent * max_agents is not addressable                                }
+    PATH_SLOTS_BAD_START,   // offsets[0] != 0                                                                 }
+    PATH_SLOTS_DECREASING,  // offsets decrease (entry: the agent)                                             }
+    PATH_SLOTS_TOO_LONG,    // a list longer than points_per_agent (entry: the agent)                          }
+    PATH_SLOTS_NO_POINTS,   // points NULL with points to read                                                 }
+    PATH_SLOTS_NOT_FINITE   // a point that is not finite (entry: the point)                                   }
+};
+// total: offsets[n] (0 with offsets == NULL: every list empty), from PATH_SLOTS_NO_POINTS on
+struct PathSlotCheck { PathSlotFault fault; int entry; int total; };
+inline PathSlotCheck path_slots_check(bool agents_set, bool partition_on, int ctx_n, int max_agents, int W, int n, const int32_t *offsets, const double *points) {
+    if (!agents_set) return {PATH_SLOTS_NO_AGENTS, -1, 0};
+    if (partition_on) return {PATH_SLOTS_PARTITION, -1, 0};
+    if (n != ctx_n) return {PATH_SLOTS_BAD_N, -1, 0};
+    if (W < 1) return {PATH_SLOTS_BAD_W, -1, 0};
+    if (!path_slots_addressable(W, max_agents)) return {PATH_SLOTS_TOO_LARGE, -1, 0};
+    if (offsets == nullptr) return {PATH_SLOTS_OK, -1, 0};
+    if (offsets[0] != 0) return {PATH_SLOTS_BAD_START, 0, 0};
+    for (int i = 0; i < n; i++) {
+        if (offsets[i + 1] < offsets[i]) return {PATH_SLOTS_DECREASING, i, 0};
+        if (offsets[i + 1] - offsets[i] > W) return {PATH_SLOTS_TOO_LONG, i, 0};
+    }
+    const int total = offsets[n];                                       // (at most W * n: addressable)
+    if (total > 0 && points == nullptr) return {PATH_SLOTS_NO_POINTS, -1, total};
+    for (int k = 0; k < total; k++)
+        if (!(restart_finite(points[3 * (int64_t)k]) && restart_finite(points[3 * (int64_t)k + 1]) && restart_finite(points[3 * (int64_t)k + 2])))
+            return {PATH_SLOTS_NOT_FINITE, k, total};
+    return {PATH_SLOTS_OK, -1, total};
+}
+inline int path_slots_error_code(PathSlotFault f) {
+    return f == PATH_SLOTS_OK ? SCA_OK : f == PATH_SLOTS_NO_AGENTS ? SCA_ERR_STATE : f == PATH_SLOTS_PARTITION ? SCA_ERR_UNSUPPORTED : SCA_ERR_ARG;
+}
+
+// the block-form refusal (RESTART_PATHS) stands while the lists are one CSR block; in slot form a restart is accepted -- what
+// scene_restart_check is told for RestartCtx::paths_on
+inline bool restart_refuses_paths(bool paths_on, bool slot_form) { return paths_on && !slot_form; }
+
+// path_offsets: CSR over the call's T packed rows, packed like pos; NULL: the call brings no lists (in slot form the named rows then get
+// empty ones).  Looked at behind scene_restart_check (T is known then).
+enum RestartPathFault {
+    RESTART_PATHS_OK = 0,
+    RESTART_PATHS_NO_SLOTS,   // path arrays while the context is not in slot form                              SCA_ERR_STATE
+    RESTART_PATHS_BAD_START,  // path_offsets[0] != 0                                                           } SCA_ERR_ARG
+    RESTART_PATHS_DECREASING, // offsets decrease (entry: the packed row)                                       }
+    RESTART_PATHS_TOO_LONG,   // a row's list longer than W (entry: the packed row)                             }
+    RESTART_PATHS_NO_POINTS,  // path_points NULL with points to read                                           }
+    RESTART_PATHS_NOT_FINITE  // a point that is not finite (entry: the packed row whose list holds it)         }
+};
+// total: path_offsets[T], the points the call brings (RESTART_PATHS_OK and the faults found after the offsets)
+struct RestartPathCheck { RestartPathFault fault; int entry; int total; };
+inline RestartPathCheck restart_paths_check(bool slot_form, int W, int T, const int32_t *path_offsets, const double *path_points) {
+    if (path_offsets == nullptr) return {RESTART_PATHS_OK, -1, 0};
+    if (!slot_form) return {RESTART_PATHS_NO_SLOTS, -1, 0};
+    if (path_offsets[0] != 0) return {RESTART_PATHS_BAD_START, 0, 0};
+    for (int r = 0; r < T; r++) {
+        if (path_offsets[r + 1] < path_offsets[r]) return {RESTART_PATHS_DECREASING, r, 0};
+        if (path_offsets[r + 1] - path_offsets[r] > W) return {RESTART_PATHS_TOO_LONG, r, 0};
+    }
+    const int total = path_offsets[T];
+    if (total > 0 && path_points == nullptr) return {RESTART_PATHS_NO_POINTS, -1, total};
+    for (int r = 0; r < T; r++)
+        for (int64_t k = 3 * (int64_t)path_offsets[r]; k < 3 * (int64_t)path_offsets[r + 1]; k++)
+            if (!restart_finite(path_points[k])) return {RESTART_PATHS_NOT_FINITE, r, total};
+    return {RESTART_PATHS_OK, -1, total};
+}
+inline int restart_paths_error_code(RestartPathFault f) { return f == RESTART_PATHS_OK ? SCA_OK : f == RESTART_PATHS_NO_SLOTS ? SCA_ERR_STATE : SCA_ERR_ARG; }
+
+// The path sections of the restart's page-locked block, behind the attribute sections: the CSR offsets over the call's packed rows
+// (T + 1 <= max_n + 1 words) and the points actually present, packed -- not padded to W; room for the most a call can bring, W per row.
+// Every section starts on a 64-byte boundary.  W == 0 (the context is not in slot form): no room, and the kernel reads neither.
+enum RestartPathSection : int { RP_OFF = 0, RP_PTS, RP_SECTIONS };
+struct RestartPathLayout { int64_t off[RP_SECTIONS]; int64_t total; };
+inline int64_t restart_path_section_bytes(int s, int max_n, int W) {
+    return W <= 0 ? 0 : s == RP_OFF ? 4 * ((int64_t)max_n + 1) : 24 * (int64_t)W * (int64_t)max_n;
+}
+// begin: where the sections start in the block (RestartAttrLayout::total)
+inline RestartPathLayout restart_paths_layout(int64_t begin, int max_n, int W) {
+    RestartPathLayout L;
+    int64_t at = (begin + RS_ALIGN - 1) / RS_ALIGN * RS_ALIGN;
+    for (int s = 0; s < RP_SECTIONS; s++) {
+        L.off[s] = at;
+        at += (restart_path_section_bytes(s, max_n, W) + RS_ALIGN - 1) / RS_ALIGN * RS_ALIGN;
+    }
+    L.total = at;
+    return L;
+}
+// the rows' lists are written (slot form): from the block's path sections, or empty where the call brought none
+constexpr uint32_t RESTART_HAS_PATH_SLOTS = 256, RESTART_HAS_PATHS = 512;
 
 // ---- a trajectory log per scene (sca_scene_history_enable) -------------------------------------------------------------------------------------
 // One allocation of capacity x n rows of SCENE_LOG_ROW_BYTES (HistRow, sca_kernels.hip.h).  Scene s owns rows [capacity * offsets[s],

@@ -21,6 +21,10 @@
 // scene's part of the forest and rewrites that word -- the three kernels above do not change.  k_scene_restart is the ONE restart kernel,
 // behind sca_restart_scenes, _sized and _obstacles alike: a scene filled to its capacity vacates an empty range, a scene that keeps its
 // obstacle set returns behind its agent rows, so the narrower calls are degenerate cases of the widest and need no kernels of their own.
+// Waypoint lists (Agent.path) under restarts: the block form of sca_set_paths is one CSR block for the whole context, which no kernel can
+// edit per scene; in slot form (sca_set_path_slots; PathSlotView and k_waypoint_slots, sca_kernels.hip.h) every agent row owns room for W
+// waypoints, and k_scene_restart also scatters a named scene's lists to its rows' rooms and resets their cursors (scene_restart_paths,
+// behind sca_restart_scenes_paths) -- and gives the rows empty lists where the call brought none.
 #pragma once
 #include "sca_kdbuild.hip.h"
 #include "sca_scenes.h"
@@ -243,8 +247,49 @@ __device__ __forceinline__ void scene_restart_attrs(const RestartAttrDev &at, co
         }
     }
 }
+// A restart that brings waypoint lists (sca_restart_scenes_paths; the context's lists are in slot form, sca_set_path_slots).  With
+// RESTART_HAS_PATH_SLOTS every row of the named scene's range gets its cursors: an occupied row len = rem = its list's length and
+// now_goal = None (NaN x 3) -- what sca_set_paths leaves --, a vacated row len = rem = 0 and None.  With RESTART_HAS_PATHS the block's
+// path sections (RestartPathLayout, sca_scenes.h) hold the CSR offsets over the call's packed rows and the points actually present; the
+// scene's points stand together in the block, so consecutive lanes read consecutive coordinates across the link, and each finds its row
+// by bisection of the scene's offsets, staged in LDS (a scene holds at most KD_WAVE_CAP rows), and writes to the row's own room
+// (path_slot_index).  Without the bit (every entry point without path arrays) the rows get empty lists: the episode brings none.  Room
+// behind a list's length keeps what an earlier list left: rem never exceeds len, nobody reads it.  Without RESTART_HAS_PATH_SLOTS (the
+// context is not in slot form) nothing of RestartPathDev is read; its pointers are null then.
+struct RestartPathDev {
+    double *pts;                  // [3 * W * max_agents] PathSlotView::pts
+    int32_t *len, *rem;           // [n] PathSlotView::len / rem
+    double *now_goal;             // [n * 3]
+    int W;
+};
+__device__ __forceinline__ void scene_restart_paths(const RestartPathDev &p, const uint8_t *blk, const RestartPathLayout &PL, uint32_t has, int row0, int lo, int ns,
+                                                    int hi, int t) {
+    __shared__ int32_t poff[KD_WAVE_CAP + 1];
+    const bool lists = (has & RESTART_HAS_PATHS) != 0;
+    if (lists) {
+        const int32_t *off = (const int32_t *)(blk + PL.off[RP_OFF]) + row0;
+        for (int i = t; i <= ns; i += RESTART_T) poff[i] = off[i];
+    }
+    __syncthreads();                                                   // (`has` is uniform over the grid: every lane of every workgroup arrives)
+    for (int i = t; i < hi - lo; i += RESTART_T) {
+        const int32_t k = lists && i < ns ? poff[i + 1] - poff[i] : 0;
+        p.len[lo + i] = k; p.rem[lo + i] = k;
+    }
+    const double none = __builtin_nan("");
+    for (int64_t g = 3 * (int64_t)lo + t; g < 3 * (int64_t)hi; g += RESTART_T) p.now_goal[g] = none;
+    if (!lists) return;
+    const int32_t first = poff[0], count = poff[ns] - first;           // the scene's points: [first, first + count) of the packed section
+    const double *src = (const double *)(blk + PL.off[RP_PTS]) + 3 * (int64_t)first;
+    for (int w = t; w < 3 * count; w += RESTART_T) {
+        const int32_t k = first + w / 3;
+        int a = 0, b = ns;                                             // poff[a] <= k < poff[b]
+        while (b - a > 1) { const int m = (a + b) >> 1; if (poff[m] <= k) a = m; else b = m; }
+        p.pts[3 * (path_slot_index(p.W, lo + a) + (k - poff[a])) + w % 3] = src[w];
+    }
+}
 __global__ __launch_bounds__(RESTART_T) void k_scene_restart(RestartDev d, const uint8_t *blk, RestartLayout L, uint32_t has, const int32_t *new_size, int32_t *size,
-                                                             RestartObsDev o, RestartObsLayout OL, RestartAttrDev at, RestartAttrLayout AL) {
+                                                             RestartObsDev o, RestartObsLayout OL, RestartAttrDev at, RestartAttrLayout AL,
+                                                             RestartPathDev p, RestartPathLayout PL) {
     const int b = (int)blockIdx.x, t = (int)threadIdx.x;
     const int s = ((const int32_t *)(blk + L.off[RS_IDS]))[b];
     const int row0 = ((const int32_t *)(blk + L.off[RS_START]))[b];
@@ -253,6 +298,7 @@ __global__ __launch_bounds__(RESTART_T) void k_scene_restart(RestartDev d, const
     scene_restart_vacate(d, lo + ns, hi, t);
     if (t == 0) { d.live[s * SCENE_LINE] = ns; d.prev[s] = ns; d.steps[s] = 0; size[s] = ns; }
     scene_restart_attrs(at, blk, AL, has, row0, lo, ns, t);
+    if (has & RESTART_HAS_PATH_SLOTS) scene_restart_paths(p, blk, PL, has, row0, lo, ns, hi, t);
     const int32_t *head = (const int32_t *)(blk + OL.off[RO_HEAD]) + RO_HEAD_WORDS * b;
     const int k = head[0];
     if (k < 0) return;                                                 // this scene keeps its set (uniform over the workgroup)

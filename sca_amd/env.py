@@ -24,7 +24,8 @@ Differences that matter:
   * Agent.path (agent.py:44) is followed on the device (k_waypoint, see include/sca_hip.h sca_set_paths): the lists are uploaded by
     set_agents; `agent.path` then reads the env's mirror (the agent's own list, shortened in place to what the reference's pops leave,
     refreshed on first read after a step) and `agent.policy.now_goal` the device's now_goal (None before the first pass).  ASSIGNING
-    `agent.path = [...]` after set_agents takes effect at the next step; editing the list in place (append, insert, pop) is NOT tracked;
+    `agent.path = [...]` after set_agents takes effect at the next step (in a SceneBatch(path_slots=W) too, through the lists' slot form,
+    sca_set_path_slots); editing the list in place (append, insert, pop) is NOT tracked;
   * history logging (agent.py:126-147, pandas) and the per-step prints are not reproduced.
 There is no CPU path: constructing the env without a GPU raises.
 """
@@ -408,22 +409,30 @@ class _FlatAgents:
         if not self._path_assigned:
             return
         assigned, self._path_assigned = self._path_assigned, set()
-        lists = [a._path for a in self._flat]
+        lists = self._path_lists()
         n = len(lists)
         if self._paths_on:
             self._refresh_paths(skip=assigned)
             ng = self._path_ng.copy()
         else:
-            if not any(len(p) for p in lists):
+            if not any(len(p) for p in lists) and not self._path_slots:
                 return
             ng = np.full((n, 3), np.nan)
             served = self._state('step_num') > 0                   # agents that ran get_trajectory already hold now_goal = goal
             ng[served] = self.goal[served]
-        self.solver.set_paths([[list(map(float, w[:3])) for w in p] for p in lists])
+        self._upload_paths([[list(map(float, w[:3])) for w in p] for p in lists])
         self.solver.set_path_state(np.array([len(p) for p in lists], np.int32), ng)
         self._paths_on = True
         self._path_ng = ng
         self._path_stale = False
+
+    _path_slots = 0                      # SceneBatch(path_slots=W): the lists live in slot form, from the start and with no list at all
+
+    def _path_lists(self):
+        return [a._path for a in self._flat]
+
+    def _upload_paths(self, lists):
+        self.solver.set_paths(lists)
 
     def _now_goal_of(self, i):
         if self._path_stale:

@@ -8,7 +8,8 @@ scene (`scene_obstacles`, sca_set_scene_obstacles): then every scene meets its o
 field with its spheres and two seeds of an obstacle scenario share one batch -- and is still bit for bit the MACAEnv of that scene alone.
 With `obstacle_capacities` a scene's obstacle range is a capacity too (sca_set_scene_obstacle_slots): SceneBatch.restart(..., obstacles=...)
 then brings a new episode's own obstacles into the slot, and run_episodes(episode_obstacles=...) streams a queue whose episodes differ in
-their obstacles.
+their obstacles.  With `path_slots` the waypoint lists (Agent.path) live in slot form -- room for W waypoints per agent row
+(sca_set_path_slots) -- and SceneBatch.restart / run_episodes(path_slots=...) bring every episode's own lists into the slot it takes.
 
     batch = SceneBatch([build_agents(seed) for seed in seeds], obstacles, device_tracker=True)   # each list numbered 0 .. n_s - 1
     while not batch.step():
@@ -133,8 +134,12 @@ class SceneEnv:
 
 class SceneBatch(_FlatAgents):
     def __init__(self, scenes, obstacles=(), scene_obstacles=None, neighbor_mode=S.NBR_KDTREE, device_tracker=False, history_capacity=0, scene_history=0, device=0,
-                 capacities=None, harvest=False, obstacle_capacities=None, attribute_slots=False):
-        """attribute_slots: a restarted slot takes the episode's own solver attributes (neighborDist, maxNeighbors, timeStep, timeHorizon,
+                 capacities=None, harvest=False, obstacle_capacities=None, attribute_slots=False, path_slots=None):
+        """path_slots: W, the waypoints every agent row has room for, or 'max' (the longest list among the initial agents, at least 1);
+        None: the lists are one block, as a batch always had them.  The lists are then uploaded in SLOT form (sca_set_path_slots) and a
+        restarted slot takes the episode's own lists (sca_restart_scenes_paths): restart() accepts agents that carry paths, none longer
+        than W, and a later `agent.path = [...]` keeps working through the slot form.
+        attribute_slots: a restarted slot takes the episode's own solver attributes (neighborDist, maxNeighbors, timeStep, timeHorizon,
         maxSpeed, max_heading_change, dt_nominal) and planner attributes (turning_radius, pitchlims) instead of keeping its own
         (sca_restart_scenes_attrs): restart() then accepts agents whose attributes differ from the slot's, and agents that change between a
         tracked and an untracked policy.  A parameter study -- one attribute swept across seeds -- streams through one batch.
@@ -179,6 +184,14 @@ class SceneBatch(_FlatAgents):
         self.device_tracker = bool(device_tracker)
         self.capacity_slots = capacities is not None               # else: a slot keeps its size, as a batch always did
         self.attribute_slots = bool(attribute_slots)               # else: a slot keeps its attributes, as a batch always did
+        if isinstance(path_slots, str):
+            if path_slots != 'max':
+                raise ValueError(f"path_slots: None, 'max' or the waypoints a row has room for, got {path_slots!r}")
+            path_slots = max([1] + [len(a._path) for agents in scenes for a in agents])
+        self.path_slots = 0 if path_slots is None else int(path_slots)     # 0: the lists are one block, and restart() refuses them
+        if path_slots is not None and self.path_slots < 1:
+            raise ValueError(f'path_slots: a row needs room for at least 1 waypoint, got {path_slots!r}')
+        self._path_slots = self.path_slots
         self.sizes = np.array([len(a) for a in scenes], np.int32)   # agents each scene holds ...
         caps = self.sizes.copy() if capacities is None else np.array([int(c) for c in capacities], np.int32)
         if len(caps) != len(scenes) or (caps < self.sizes).any():
@@ -233,6 +246,33 @@ class SceneBatch(_FlatAgents):
 
     def __len__(self):
         return len(self._envs)
+
+    # ---- the lists in slot form (SceneBatch(path_slots=W)) -----------------------------------------------------------------------------------
+    def _path_lists(self):
+        """the agents' lists, row by row; a vacant row (behind its slot's episode) has none"""
+        lists = [a._path for a in self._flat]
+        if self.path_slots:
+            for i in self._vacant_rows():
+                lists[i] = []
+        return lists
+
+    def _vacant_rows(self):
+        return {i for s in range(len(self.sizes)) for i in range(int(self.offsets[s]) + int(self.sizes[s]), int(self.offsets[s + 1]))}
+
+    def _refresh_paths(self, skip=()):
+        """(the agents that stand in vacant rows belong to an episode that has left its slot: their lists stay what that episode left)"""
+        super()._refresh_paths(set(skip) | self._vacant_rows() if self.path_slots else skip)
+
+    def _upload_paths(self, lists):
+        if not self.path_slots:
+            return super()._upload_paths(lists)
+        self._check_path_room([(i, p) for i, p in enumerate(lists)], 'agent.path')
+        self.solver.set_path_slots(self.path_slots, lists)
+
+    def _check_path_room(self, rows, who):
+        for i, p in rows:
+            if len(p) > self.path_slots:
+                raise ValueError(f'{who}: row {i} carries a list of {len(p)} waypoints, a row has room for {self.path_slots} (SceneBatch(path_slots=...))')
 
     def env(self, s):
         return self._envs[s]
@@ -292,8 +332,9 @@ class SceneBatch(_FlatAgents):
                     raise ValueError(f'restart: scene {s} holds up to {cap} obstacles, the new episode brings {len(obs)} (a slot keeps its obstacle capacity)')
         if not items:
             return
-        if self._paths_on:
-            raise ValueError('restart: waypoint lists are set in this batch (they are one block for all scenes)')
+        if self._paths_on and not self.path_slots:
+            raise ValueError('restart: waypoint lists are set in this batch (they are one block for all scenes; SceneBatch(path_slots=...) '
+                             'gives every row room of its own)')
         for s, agents in items:
             if not 0 <= s < len(self._envs):
                 raise ValueError(f'restart: no scene {s} in a batch of {len(self._envs)}')
@@ -306,8 +347,11 @@ class SceneBatch(_FlatAgents):
             for i, (a, old) in enumerate(zip(agents, self._flat[lo:hi])):     # (over the rows the episode occupies)
                 if a.id != i:
                     raise ValueError(f'restart: scene {s}: agent.id must equal its index in its scene')
-                if len(a._path):
-                    raise ValueError(f'restart: scene {s}, agent {i} carries a path: waypoint lists cannot be replaced per scene')
+                if len(a._path) and not self.path_slots:
+                    raise ValueError(f'restart: scene {s}, agent {i} carries a path: waypoint lists cannot be replaced per scene '
+                                     '(SceneBatch(path_slots=...) makes slots that take the episode\'s own lists)')
+                if len(a._path) > self.path_slots > 0:
+                    raise ValueError(f'restart: scene {s}, agent {i} carries a list of {len(a._path)} waypoints, a row has room for {self.path_slots}')
                 for name, (attr, conv) in _ATTRS.items():
                     if not self.attribute_slots and conv(getattr(a, attr)) != conv(getattr(old, attr)):
                         raise ValueError(f"restart: scene {s}, agent {i}: {attr} differs from the slot's (a slot keeps its solver attributes; "
@@ -331,6 +375,7 @@ class SceneBatch(_FlatAgents):
             view._time_cum = [0.0]
             _bind(agents, view)
         self._stale = True                                           # the mirrors (views of the batch's arrays) refresh in place on first use
+        self._path_stale = self._paths_on                            # (slot form: the new agents' whole lists, now_goal None, read back on first use)
         self._nbr_cache = None
         self._vpref_cache = None
         if self.harvest:                                             # what the restart leaves, without a read-back: all of the episode live, no step taken
@@ -363,7 +408,7 @@ class SceneBatch(_FlatAgents):
                                    max_run_dist=[a.max_run_dist for a in flat], goal_heading=goal6[:, 3:6] if self._trk_on else None,
                                    sizes=None if full else [len(agents) for _, agents in items],
                                    obstacles=[_obstacle_arrays(new_obs[s]) if s in new_obs else None for s, _ in items] if new_obs else None,
-                                   attrs=attrs)
+                                   attrs=attrs, paths=[[list(map(float, w[:3])) for w in a._path] for a in flat] if self.path_slots else None)
         if attrs is not None and self._trk_on:                       # the planner attributes the device holds per row (_planner_of)
             if self._trk_trip is None:
                 self._trk_trip = [self._trk_first] * len(self._flat)
@@ -515,7 +560,7 @@ def _harvest_policy_time(view, h):
 
 
 def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=None, max_steps=None, stats=None, history_rows=0, capacities=None,
-                 harvest=False, episode_obstacles=None, obstacle_capacities='max', attributes=False):
+                 harvest=False, episode_obstacles=None, obstacle_capacities='max', attributes=False, path_slots=None):
     """Streams a queue of episodes (Agent lists, each numbered 0 .. n - 1) through `slots` scenes of ONE SceneBatch: when a scene finishes,
     its metrics, step count and final state are taken and the slot restarts with the next episode of its size (SceneBatch.restart), while
     the other slots keep running.  Obstacles are one list shared by all episodes (`obstacles`), or -- mutually exclusive with it --
@@ -539,8 +584,21 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
     stats, taken from what the finishing step itself handed over (SceneBatch(harvest=True): finished() / harvested()) -- one
     synchronisation per step and, per finished episode, its own rows instead of a read-back of the whole batch.  attributes=True: the slots
     take every episode's own solver and planner attributes (SceneBatch(attribute_slots=True)), so a queue whose episodes differ in them --
-    a sweep of neighborDist across seeds -- streams through one batch instead of raising when such an episode's turn comes."""
+    a sweep of neighborDist across seeds -- streams through one batch instead of raising when such an episode's turn comes.
+    path_slots=W or 'max' (the longest list in the whole queue, at least 1): the slots take every episode's own waypoint lists
+    (SceneBatch(path_slots=W)), so a queue whose drones carry paths streams through one batch; results, on_done order and stats are those
+    of the same queue run as one MACAEnv per episode, and every result gains `path_left`, the waypoints left in each agent's list when the
+    episode finished (the agents' own lists are shortened to that).  ValueError up front for a list longer than W."""
     episodes = [list(e) for e in episodes]
+    if isinstance(path_slots, str):
+        if path_slots != 'max':
+            raise ValueError(f"run_episodes: path_slots is None, 'max' or the waypoints a row has room for, got {path_slots!r}")
+        path_slots = max([1] + [len(a._path) for e in episodes for a in e])
+    if path_slots is not None:
+        for i, e in enumerate(episodes):
+            for a in e:
+                if len(a._path) > int(path_slots):
+                    raise ValueError(f'run_episodes: episode {i}, agent {a.id} carries a list of {len(a._path)} waypoints, path_slots is {path_slots}')
     sizes = [len(e) for e in episodes]
     ocaps = None
     if episode_obstacles is not None:
@@ -570,7 +628,7 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
         raise ValueError('run_episodes: episode %d needs the device tracker, but none of the episodes the slots start with does, so the batch '
                          'would run without one: put a tracked episode among the first %d' % (min(i for i in pending if tracked[i]), len(holding)))
     batch = SceneBatch([episodes[i] for i in holding], obstacles, device_tracker=device_tracker, scene_history=history_rows,
-                       capacities=None if capacities is None else caps, harvest=harvest, attribute_slots=attributes,
+                       capacities=None if capacities is None else caps, harvest=harvest, attribute_slots=attributes, path_slots=path_slots,
                        scene_obstacles=None if ocaps is None else [episode_obstacles[i] for i in holding], obstacle_capacities=ocaps)
     results = [None] * len(episodes)
     batch_steps = served = 0
@@ -579,7 +637,7 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
             served += int(batch.active.sum())
             batch.step()
             batch_steps += 1
-            refill, refill_obs = {}, {}
+            refill, refill_obs, path_rem = {}, {}, None
             # (one step per collect: finished() is in slot order, as the scan of batch.done is)
             for s in (batch.finished() if harvest else [s for s, i in enumerate(holding) if i is not None and batch.done[s]]):
                 i = holding[s]
@@ -594,6 +652,13 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
                     lo, hi = int(batch.offsets[s]), int(batch.offsets[s]) + int(batch.sizes[s])
                     results[i] = dict(episode=i, slot=s, metrics=metrics.episode_metrics(view), steps=int(batch.steps[s]),
                                       state={k: batch._state(k)[lo:hi].copy() for k in batch._mirror})
+                if batch.path_slots:                              # what is left of the episode's lists, before its rows are given away
+                    if path_rem is None:                          # (one read-back per batch step in which a scene finished)
+                        path_rem = batch.solver.get_path_state()[0]
+                    lo = int(batch.offsets[s])
+                    for k, a in enumerate(episodes[i]):
+                        del a._path[int(path_rem[lo + k]):]
+                    results[i]['path_left'] = [len(a._path) for a in episodes[i]]
                 if batch.scene_history:
                     rows, dropped = view.solver.history_rows()
                     results[i].update(trajectories=metrics.trajectories(view, rows=rows), rows_dropped=dropped, info=metrics.episode_info(view, **info_args))

@@ -167,6 +167,23 @@ class BatchedSolver:
         off, pts = paths_csr(paths)
         self._chk(self.L.sca_set_paths(self.ctx, len(paths), _lib.ptr(off, C.c_int32), _lib.ptr(pts, C.c_double)), 'sca_set_paths')
 
+    def set_path_slots(self, W, paths=None):
+        """The lists in SLOT form (sca_set_path_slots): every agent row owns room for W waypoints, so restart_scenes(paths=...) can replace
+        the lists of one scene while the others keep running.  paths: as set_paths', no list longer than W; None: every list empty.
+        Resets every cursor and now_goal (None).  set_paths puts the context back into block form."""
+        if paths is None:
+            self._chk(self.L.sca_set_path_slots(self.ctx, int(W), self.n, None, None), 'sca_set_path_slots')
+            return
+        off, pts = paths_csr(paths)
+        self._chk(self.L.sca_set_path_slots(self.ctx, int(W), len(paths), _lib.ptr(off, C.c_int32), _lib.ptr(pts, C.c_double)), 'sca_set_path_slots')
+
+    @property
+    def path_slots(self):
+        """the room per agent row, in waypoints, while the lists are in slot form; 0 otherwise (sca_get_path_slots)"""
+        w = C.c_int(0)
+        self._chk(self.L.sca_get_path_slots(self.ctx, C.byref(w)), 'sca_get_path_slots')
+        return int(w.value)
+
     def get_path_state(self):
         """(remaining [n] int32: elements still in each list, now_goal [n, 3]: NaN rows = None)"""
         rem = np.zeros(self.n, np.int32)
@@ -258,7 +275,7 @@ class BatchedSolver:
         return out
 
     def restart_scenes(self, ids, pos, heading, vel=None, radius=None, pref_speed=None, goal=None, policy=None, zaxis=None, max_run_dist=None,
-                       goal_heading=None, sizes=None, obstacles=None, attrs=None):
+                       goal_heading=None, sizes=None, obstacles=None, attrs=None, paths=None):
         """New episodes into the scenes `ids` while the others keep running (sca_restart_scenes).  The arrays hold T rows, the named scenes'
         agents in the order of `ids`; None keeps the slot's values (vel: zero).  Afterwards each named scene is what a context of that
         episode alone is after set_agents + set_state (+ device_tracker_enable); its per-agent attributes stay, and its obstacle set unless
@@ -272,7 +289,10 @@ class BatchedSolver:
         turning_radius, pitch_lo, pitch_hi, each an array of T rows or a scalar for all of them.  A name that is absent means the value a
         context alone would have -- its sca_params, device_tracker_enable's value -- not what the row had; {} puts every named row back
         on those.  A policy may then move an agent between tracked and untracked.  None: the slots keep their attributes (the entry
-        points above); 'keep': the same through sca_restart_scenes_attrs with attrs == NULL, which is exactly that call."""
+        points above); 'keep': the same through sca_restart_scenes_attrs with attrs == NULL, which is exactly that call.
+        paths (sca_restart_scenes_paths; the lists in slot form, set_path_slots): one list of [x, y, z] waypoints per packed row, T in all,
+        none longer than the room per row -- the named scenes' rows take the episode's own lists.  None: the call brings none (in slot
+        form the named rows then get empty lists)."""
         ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
         keep = [ids]
         if obstacles is not None and len(obstacles) != len(ids):
@@ -305,6 +325,14 @@ class BatchedSolver:
         u1 = lambda a: arr(a, np.uint8, C.c_uint8, 0)
         rest = (d3(pos), arr(vel, np.float32, C.c_float, 3), d3(heading), d1(radius), d1(pref_speed), d3(goal), u1(policy), u1(zaxis), d1(max_run_dist),
                 d3(goal_heading))
+        path_args = None
+        if paths is not None:
+            if T is not None and len(paths) != T:
+                raise ValueError(f'restart_scenes: {len(paths)} waypoint lists where the named scenes hold {T} agents')
+            poff, ppts = paths_csr(paths)
+            keep += [poff, ppts]
+            path_args = (_lib.ptr(poff, C.c_int32), _lib.ptr(ppts, C.c_double))
+            attrs = 'keep' if attrs is None else attrs                # (sca_restart_scenes_paths with attrs == NULL: the slots keep theirs)
         if attrs is not None:
             keep_attrs = isinstance(attrs, str)
             if keep_attrs and attrs != 'keep':
@@ -323,9 +351,12 @@ class BatchedSolver:
                 setattr(desc, name, arr(v, np.int32 if i32 else np.float64, C.c_int32 if i32 else C.c_double, 0))
             ocnt, opos, orad = self._pack_obstacle_sets(obstacles, 'restart_scenes') if obstacles is not None else (None, None, None)
             op = lambda a, ct: None if a is None else _lib.ptr(a, ct)
-            self._chk(self.L.sca_restart_scenes_attrs(self.ctx, len(ids), _lib.ptr(ids, C.c_int32), None if sizes is None else _lib.ptr(sizes, C.c_int32),
-                                                      op(ocnt, C.c_int32), op(opos, C.c_double), op(orad, C.c_double), None if keep_attrs else C.byref(desc), *rest),
-                      'sca_restart_scenes_attrs')
+            head = (self.ctx, len(ids), _lib.ptr(ids, C.c_int32), None if sizes is None else _lib.ptr(sizes, C.c_int32),
+                    op(ocnt, C.c_int32), op(opos, C.c_double), op(orad, C.c_double), None if keep_attrs else C.byref(desc))
+            if path_args is not None:
+                self._chk(self.L.sca_restart_scenes_paths(*head, *path_args, *rest), 'sca_restart_scenes_paths')
+            else:
+                self._chk(self.L.sca_restart_scenes_attrs(*head, *rest), 'sca_restart_scenes_attrs')
         elif obstacles is not None:
             ocnt, opos, orad = self._pack_obstacle_sets(obstacles, 'restart_scenes')
             self._chk(self.L.sca_restart_scenes_obstacles(self.ctx, len(ids), _lib.ptr(ids, C.c_int32), None if sizes is None else _lib.ptr(sizes, C.c_int32),
@@ -699,10 +730,8 @@ def paths_csr(paths):
     lens = [len(p) for p in paths]
     off = np.zeros(len(paths) + 1, np.int32)
     off[1:] = np.cumsum(lens)
-    pts = np.zeros((int(off[-1]), 3))
-    for i, p in enumerate(paths):
-        if lens[i]:
-            pts[off[i]:off[i + 1]] = np.asarray(p, dtype=np.float64).reshape(lens[i], 3)
+    flat = [w for p in paths for w in p]                           # (one conversion for all lists: a restart brings a list per row)
+    pts = np.asarray(flat, dtype=np.float64).reshape(len(flat), 3) if flat else np.zeros((0, 3))
     return off, pts
 
 

@@ -67,7 +67,17 @@ without attrs lies inside the spread of the parent's own samples (median <= the 
     python tools/bench/scene_refill_cost.py --restart-only parent.json --package-root <a checkout of the parent commit, built>
 
 --restart-only: nothing but the 30 samples of the restart call without attrs (1 and 16 scenes) on the library found under --package-root --
-only calls every commit since sca_restart_scenes has."""
+only calls every commit since sca_restart_scenes has.
+
+    python tools/bench/scene_refill_cost.py --paths               # 256 episodes of 100 drones, 64 slots -> the `queue` entry of profiles/scene_paths_cost.json
+
+--paths: the same queue with every drone carrying 0-5 seeded waypoints (Agent.path), in the two ways a user can run it:
+    waves     B episodes at a time, one fresh SceneBatch per wave (the lists one block): what a user had to do while a slot refused lists
+    stream    run_episodes(path_slots='max'): a finished slot takes the next episode and its lists (sca_restart_scenes_paths)
+alternated, final states per episode identical.  Then one restart call naming 1 and 16 scenes, 30 samples each: on a batch in slot form
+without path arrays and with the episodes' lists, and on a batch that is not in slot form.  --parent-json: the parent commit's
+--restart-only samples; the entry records whether this build's medians without path arrays lie inside the parent's spread.
+"""
 import argparse
 import json
 import os
@@ -96,16 +106,17 @@ def main():
                                                         "--attributes: the parent commit's --restart-only samples")
     ap.add_argument('--attributes', action='store_true', help='a parameter study: waves of one fresh batch per value against the streamed queue with attribute slots')
     ap.add_argument('--values', default='5,10,15', help='--attributes: the neighborDist values, dealt round-robin')
+    ap.add_argument('--paths', action='store_true', help='a queue whose drones carry waypoint lists: waves of fresh batches against the streamed queue with path slots')
     ap.add_argument('--restart-only', default=None, metavar='OUT', help='write only the samples of one restart call (1 and 16 scenes, no attrs) to OUT')
     ap.add_argument('--package-root', default=None, help='import sca_amd from this checkout instead of the one the tool stands in')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
-    if args.harvest + args.mixed + args.episode_obstacles + args.attributes > 1:
-        ap.error('--harvest, --mixed, --episode-obstacles and --attributes are four comparisons: one at a time')
+    if args.harvest + args.mixed + args.episode_obstacles + args.attributes + args.paths > 1:
+        ap.error('--harvest, --mixed, --episode-obstacles, --attributes and --paths are five comparisons: one at a time')
     if args.out is None:
         args.out = os.path.join(REPO, 'profiles', 'scene_harvest_cost.json' if args.harvest else 'scene_sizes_cost.json' if args.mixed else
                                 'scene_obstacle_refill_cost.json' if args.episode_obstacles else 'scene_attrs_cost.json' if args.attributes else
-                                'scene_refill_cost.json')
+                                'scene_paths_cost.json' if args.paths else 'scene_refill_cost.json')
     sys.path.insert(0, args.package_root or REPO)
     from sca_amd import env as E, scenarios, scenes, solver as sol_mod
     pols = [E.SCAPolicy, E.RVO3DPolicy, E.SRVO3DPolicy, E.ORCA3DPolicy, E.ORCA3DPolicyOfficial, E.RVO3dDubinsPolicy]
@@ -121,7 +132,8 @@ def main():
     def value_of(c):
         return values[c % len(values)]                            # --attributes: candidate c's neighborDist
 
-    def episode(c):
+    def episode(c, lists=None):
+        """lists: whether the drones carry waypoints (None: as --paths says)"""
         n = int(size_of[c])
         sc = scenarios.random_cube(n, seed=c)
         agents = [E.Agent(start_pos=list(sc['start'][i]), goal_pos=list(sc['goal'][i]), vel=[0.0, 0.0, 0.0], radius=0.5, pref_speed=1.0,
@@ -129,11 +141,16 @@ def main():
         if args.attributes:
             for a in agents:
                 a.neighborDist = value_of(c)
+        if args.paths if lists is None else lists:                  # 0-5 waypoints around the drone's straight line, seeded by the candidate
+            rng = np.random.default_rng(3000 + c)
+            for a, p, g in zip(agents, sc['start'], sc['goal']):
+                fr = sorted(rng.uniform(0.1, 0.9, int(rng.integers(0, 6))), reverse=True)       # (list.pop() takes the last: the nearest)
+                a.path = [[float(x) for x in np.round(p[:3] + (g[:3] - p[:3]) * f + rng.normal(0, 1.0, 3), 3)] for f in fr]
         return agents
 
     RESTART_SAMPLES = 30
 
-    def restart_samples(sol, eps, k, attrs=None, sizes=None, obstacles=None):
+    def restart_samples(sol, eps, k, attrs=None, sizes=None, obstacles=None, paths=False):
         """the wall time of RESTART_SAMPLES restart calls naming scenes 0 .. k - 1 with the episodes eps[0 .. k - 1], in seconds"""
         ids = list(range(k))
         flat = [a for s in ids for a in eps[s]]
@@ -145,6 +162,8 @@ def main():
                   max_run_dist=np.array([a.max_run_dist for a in flat]), goal_heading=np.ascontiguousarray(goal6[:, 3:6]))
         if attrs is not None:
             kw['attrs'] = attrs(flat)
+        if paths:
+            kw['paths'] = [[list(map(float, w[:3])) for w in a._path] for a in flat]
         pos, head = np.ascontiguousarray(start[:, :3]), np.ascontiguousarray(start[:, 3:6])
         ts = []
         for _ in range(RESTART_SAMPLES):
@@ -158,7 +177,7 @@ def main():
 
     if args.restart_only:
         # default attributes throughout: the batch and the call every commit since sca_restart_scenes has
-        args.attributes = False
+        args.attributes = args.paths = False
         eps = [episode(c) for c in range(B + 16)]
         batch = scenes.SceneBatch(eps[:B], [], device_tracker=True)
         for _ in range(20):
@@ -259,6 +278,8 @@ def main():
         kw = {} if harvest is None else dict(harvest=harvest)
         if args.attributes:
             kw.update(attributes=True)
+        if args.paths:
+            kw.update(path_slots='max')
         if args.episode_obstacles:
             kw.update(episode_obstacles=[obstacles_of(c) for c in chosen], obstacle_capacities='max')
         t0 = time.perf_counter()
@@ -293,7 +314,7 @@ def main():
     if args.episode_obstacles:                                       # slot 0 may hold a map's worth of obstacles, the others a field's
         batch = batch_of(chosen[:B], eps[:B], obstacle_capacities=[1491] + [8] * (B - 1))
     else:
-        batch = scenes.SceneBatch(eps[:B], [], device_tracker=True, capacities=[cap] * B if args.mixed else None)
+        batch = scenes.SceneBatch(eps[:B], [], device_tracker=True, capacities=[cap] * B if args.mixed else None, **(dict(path_slots=5) if args.paths else {}))
     for _ in range(20):
         batch.step()
     sol = batch.solver
@@ -319,7 +340,30 @@ def main():
             sol.restart_scenes(ids, pos, head, sizes=[len(eps[B + s]) for s in ids] if args.mixed else None, obstacles=obstacles, **kw)
             ts.append(time.perf_counter() - t0)
         return float(np.median(ts)) * 1e3
-    restart = {'scenes_1_ms': restart_ms(1), 'scenes_%d_ms' % max(1, B // 4): restart_ms(max(1, B // 4)), 'step_ms': float(np.median(t_step)) * 1e3}
+    if args.paths:
+        # one restart call, 1 and 16 scenes: on the batch in slot form without path arrays (the named rows get empty lists) and with the
+        # episodes' 0-5 waypoints per row, and on a batch without lists that is not in slot form (the call every earlier commit has)
+        bare = [episode(c, lists=False) for c in chosen[:B + 16]]
+        plain = scenes.SceneBatch(bare[:B], [], device_tracker=True)
+        for _ in range(20):
+            plain.step()
+        call = {'slot_form_no_path_arrays': {'scenes_1': spread(restart_samples(sol, eps[B:], 1)), 'scenes_16': spread(restart_samples(sol, eps[B:], 16))},
+                'slot_form_lists_0_5': {'scenes_1': spread(restart_samples(sol, eps[B:], 1, paths=True)), 'scenes_16': spread(restart_samples(sol, eps[B:], 16, paths=True))},
+                'not_slot_form': {'scenes_1': spread(restart_samples(plain.solver, bare[B:], 1)), 'scenes_16': spread(restart_samples(plain.solver, bare[B:], 16))},
+                'step_ms': float(np.median(t_step)) * 1e3,
+                'note': 'one restart call on a batch of %d slots of %d drones, wall time around the Python call, %d samples each; slot form: room for 5 waypoints '
+                        'per row' % (B, n1, RESTART_SAMPLES)}
+        plain.close()
+        if args.parent_json:
+            with open(args.parent_json) as f:
+                parent = json.load(f)
+            assert (parent['slots'], parent['agents_per_episode']) == (B, n1), 'the parent measured another batch'
+            call['parent_commit'] = parent['no_attrs']
+            call['median_inside_parent_spread'] = {case: {k: bool(parent['no_attrs'][k]['min_ms'] <= call[case][k]['median_ms'] <= parent['no_attrs'][k]['max_ms'])
+                                                          for k in ('scenes_1', 'scenes_16')} for case in ('slot_form_no_path_arrays', 'not_slot_form')}
+        restart = call
+    else:
+        restart = {'scenes_1_ms': restart_ms(1), 'scenes_%d_ms' % max(1, B // 4): restart_ms(max(1, B // 4)), 'step_ms': float(np.median(t_step)) * 1e3}
     if args.episode_obstacles:
         rng = np.random.default_rng(7)
         eight = lambda: (rng.uniform(-20.0, 20.0, (8, 3)) + [0.0, 0.0, 30.0], np.ones(8))
@@ -361,7 +405,7 @@ def main():
     batch.close()
 
     doc = {'tool': 'tools/bench/scene_refill_cost.py' + (' --mixed' if args.mixed else ' --harvest' if args.harvest else ' --episode-obstacles' if args.episode_obstacles else
-                                                         ' --attributes' if args.attributes else ''),
+                                                         ' --attributes' if args.attributes else ' --paths' if args.paths else ''),
            'slots': B, 'episodes': count,
            'agents_per_episode': {str(n): int((size_of[chosen] == n).sum()) for n in choices} if args.mixed else n1, 'alternations': args.alternations,
            'episode_cap': args.episode_cap, 'last_seed': chosen[-1], 'seeds_left_out_no_end_within_cap': left_out,
@@ -378,6 +422,8 @@ def main():
     if args.attributes:
         doc['neighborDist_values'] = values
         doc['episodes_per_value'] = {str(v): int(sum(value_of(c) == v for c in chosen)) for v in values}
+    if args.paths:
+        doc['waypoints_per_drone'] = '0-5, seeded by the episode; stream: run_episodes(path_slots="max")'
     if args.episode_obstacles:
         doc['obstacles_per_episode'] = {str(m): int(sum(len(obstacles_of(c)) == m for c in chosen)) for m in (0, 1, 2, 3, 4, 5, 8)}
     ratio = 'capacity_over_fixed_episodes_per_s' if args.mixed else 'harvest_over_stream_episodes_per_s' if args.harvest else 'stream_over_waves_episodes_per_s'
@@ -398,13 +444,20 @@ def main():
                 runs = json.load(f).get('runs', {})
         runs[str(B)] = doc
         doc = {'tool': 'tools/bench/scene_refill_cost.py --harvest', 'runs': runs}
+    if args.paths:                                                   # beside the `step` entry of tools/bench/path_slots_step_cost.py
+        whole = {}
+        if os.path.exists(args.out):
+            with open(args.out) as f:
+                whole = json.load(f)
+        whole['queue'] = doc
+        doc = whole
     if args.mixed:
         doc['restart_call']['note'] = 'sca_restart_scenes_sized, the named slots of capacity %d taking the queue\'s next episodes' % cap
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as f:
         json.dump(doc, f, indent=1, sort_keys=True)
         f.write('\n')
-    shown = doc['runs'][str(B)] if args.harvest else doc
+    shown = doc['runs'][str(B)] if args.harvest else doc['queue'] if args.paths else doc
     print(json.dumps({k: shown[k] for k in ('legs', 'restart_call', ratio, 'parent_commit_stream') if k in shown}), flush=True)
 
 
