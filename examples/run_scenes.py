@@ -27,8 +27,13 @@ one metrics row per scene -- what a loop over the reference's run_example/run_*.
     python examples/run_scenes.py --waypoints 3 --seeds 8 --slots 16    # every drone routed through 3 waypoints (Agent.path), the table still
                                                        # ONE queue: a slot takes the episode's own lists with the restart
                                                        # (run_episodes(path_slots=...))
+    python examples/run_scenes.py --seeds 8 --slots 16 --save-at 150 --save-dir ckpt   # a table across TWO runs: behind 150 batch steps every
+    python examples/run_scenes.py --seeds 8 --slots 16 --resume ckpt                   # running episode is written as a checkpoint (scenes.SceneCheckpoint)
+                                                       # and the run stops; the second run resumes them in their slots and
+                                                       # streams the rest of the queue -- together the rows of one run
 """
 import argparse
+import json
 import os
 import sys
 import time
@@ -37,7 +42,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sca_amd import env as E, metrics, read_map, scenarios            # noqa: E402
-from sca_amd.scenes import SceneBatch, run_episodes                   # noqa: E402
+from sca_amd.scenes import SceneBatch, SceneCheckpoint, run_episodes  # noqa: E402
 
 SWEEPABLE = {'neighborDist': float, 'maxNeighbors': int, 'timeStep': float, 'timeHorizon': float, 'maxSpeed': float, 'max_heading_change': float,
              'dt_nominal': float, 'turning_radius': float}        # the Agent attributes a slot takes with a restart (agent.py:24-41)
@@ -95,6 +100,11 @@ def main():
                                                   'all of them one queue' % ', '.join(SWEEPABLE))
     ap.add_argument('--waypoints', type=int, default=0, help='route every drone through this many seeded waypoints (Agent.path); with --slots the '
                                                              "queue's slots take every episode's own lists (run_episodes(path_slots=...))")
+    ap.add_argument('--save-at', type=int, default=0, help='with --slots and --save-dir: stop behind this many batch steps and write every running '
+                                                           'episode there as a checkpoint')
+    ap.add_argument('--save-dir', default=None, help='where --save-at writes the checkpoints and queue.json')
+    ap.add_argument('--resume', default=None, help='with --slots and the arguments of the run that saved: resume the checkpoints of this directory in '
+                                                   'their slots and stream the rest of the queue')
     ap.add_argument('--log-dir', default=None, help='write one folder per episode here: env_cfg.json + trajs.npz (the first --max-steps steps of each)')
     args = ap.parse_args()
     if args.map and not (args.slots and args.obstacles):
@@ -103,6 +113,10 @@ def main():
         ap.error('--capacity is about the slots of a streamed queue: give --slots')
     if args.harvest and not args.slots:
         ap.error('--harvest is about the streamed queue: give --slots')
+    if (args.save_at or args.save_dir or args.resume) and not args.slots:
+        ap.error('--save-at / --save-dir / --resume are about the streamed queue: give --slots')
+    if bool(args.save_at) != bool(args.save_dir):
+        ap.error('--save-at STEP and --save-dir DIR go together')
     sweep_name, sweep_values = None, [None]
     if args.sweep:
         if not args.slots:
@@ -159,8 +173,16 @@ def main():
 
     if args.slots:
         t0, stats = time.time(), {}
+        queue, queue_obstacles, order = scenes, obstacles, list(range(len(scenes)))
+        if args.resume:                                               # the saved run's slots first, in slot order, then the episodes that never started
+            with open(os.path.join(args.resume, 'queue.json')) as f:
+                saved = json.load(f)
+            order = [i for _, i, _ in saved['checkpoints']] + saved['pending']
+            queue = [SceneCheckpoint.read(os.path.join(args.resume, name)) for _, _, name in saved['checkpoints']] + [scenes[i] for i in saved['pending']]
+            queue_obstacles = [obstacles[i] for i in order]
 
         def row(r):
+            r = dict(r, episode=order[r['episode']])
             pname, what = names[r['episode']]
             print('%-10s %-*s slot %3d steps %5d  ' % (pname, 40 if sweep_name else 20, what, r['slot'], r['steps']) +
                   '  '.join('%s %.4g' % (k, r['metrics'][k]) for k in ('SuccessRate', 'ExtraTime', 'ExtraDistance', 'AverageSpeed')), flush=True)
@@ -168,10 +190,17 @@ def main():
                 metrics.write_log_files(folder(r['episode']), scenes[r['episode']], r['trajectories'], r['info'], xlsx=False)
                 if r['rows_dropped']:
                     print('    (the log holds the first %d steps: %d more did not fit --max-steps rows)' % (r['trajectories'].shape[1], r['rows_dropped']))
-        run_episodes(scenes, args.slots, device_tracker=True, on_done=row, max_steps=args.max_steps, stats=stats,
+        run_episodes(queue, args.slots, device_tracker=True, on_done=row, max_steps=args.max_steps, stats=stats,
                      history_rows=args.max_steps if args.log_dir else 0, capacities=capacities, harvest=args.harvest,
-                     episode_obstacles=obstacles if args.obstacles else None, attributes=bool(sweep_name),
-                     path_slots=args.waypoints or None)
+                     episode_obstacles=queue_obstacles if args.obstacles else None, attributes=bool(sweep_name),
+                     path_slots=args.waypoints or None, checkpoint_at=(args.save_at, args.save_dir) if args.save_at else None)
+        if 'checkpoints' in stats:
+            with open(os.path.join(args.save_dir, 'queue.json'), 'w') as f:
+                json.dump(dict(batch_step=args.save_at, checkpoints=[[s, order[i], os.path.basename(path)] for s, (i, path) in sorted(stats['checkpoints'].items())],
+                               pending=[order[i] for i in stats['pending']]), f)
+            print('stopped behind %d batch steps: %d running episodes written to %s, %d more pending (--resume %s)' %
+                  (args.save_at, len(stats['checkpoints']), args.save_dir, len(stats['pending']), args.save_dir))
+            return
         print('%d episodes through %d slots: %d batch steps, mean live fraction %.2f, %.2f s' %
               (len(scenes), args.slots, stats['batch_steps'], stats['live_fraction'], time.time() - t0) +
               (' (%d waypoints per drone, the lists in slot form)' % args.waypoints if args.waypoints else ''))

@@ -499,6 +499,69 @@ int sca_scene_harvest_enable(sca_ctx *ctx, int on);
 int sca_scene_harvest_get(sca_ctx *ctx, sca_scene_harvest *out, int32_t struct_bytes);
 int sca_scene_harvest_collect(sca_ctx *ctx, int32_t *scene_ids /*nscenes*/, int32_t *count);
 
+/* Scene checkpoints: a running episode out of its slot as a blob of bytes, and back into any slot.  A checkpoint holds the scene's MUTABLE
+ * state only, for the rows the scene occupies; the episode's definition -- constants, attributes, obstacles, waypoint lists, goal headings
+ * -- stays what the restart entry points take.  Resuming is therefore sca_restart_scenes* (any of them, with the episode's definition),
+ * then sca_load_scenes.  The contract extends the scene contract above: after restart(E) + load(a blob taken from a scene holding E after
+ * its k-th step) the named scene is bit for bit the scene the blob was taken from, from there on -- state, float32 action rows, neighbour
+ * lists and their distSq, diagnostics, status, the scene-local permutation, tracker v_pref, plans and re-plan counts, remaining /
+ * now_goal, steps[s] and active[s] -- and no other scene can tell that either call happened.  That holds in the same context, in another
+ * slot with another range, capacity or obstacle base, and in another context or process: the blob is pointer-free and speaks scene-local
+ * terms.  Detect the feature by the symbol (sca_version() is unchanged).
+ *   in the blob  a 64-byte header (magic, format version, sca_version(), size, the tracker record's words, the public record's bytes,
+ *              whether tracker records and path cursors are present, steps / live / prev, the byte count, a 64-bit checksum of everything
+ *              behind the header), then per occupied row: the policy byte (compared with the scene's at the load, not loaded), the public
+ *              record (position, float32 velocity, flags, radius), heading, the heading kept for a finished scene, v_pref as fed / tracked
+ *              and its mode, total_dist, step_num, status, the kd permutation in scene-local terms, and -- with a device tracker and a
+ *              tracked row in the scene -- the first neighbour's distSq the tracker reads and the tracker records (plan, cursor, now_goal,
+ *              v_pref, re-plan count), and -- with waypoint lists set -- remaining and now_goal.  Between the load and the next pass
+ *              sca_get_state, sca_get_kd_perm, sca_get_scene_state, sca_get_path_state, sca_device_tracker_replans,
+ *              sca_device_tracker_debug and sca_active_count return what they returned on the source at the save.
+ *   not in it  the OUTPUTS of the last pass: the action rows (sca_get_actions), the neighbour lists (sca_get_neighbors, sca_get_nbr0) and
+ *              diag / vpref_used of sca_get_diag read what the restart left until the next pass writes them -- every pass writes them for
+ *              every row before it reads them.  `status` does outlive a pass for a row the pass does not serve and IS in the blob.
+ *   sca_scene_checkpoint_layout  byte offsets of the 14 sections (policy, records, heading, kept heading, v_pref, total_dist, step_num,
+ *              status, permutation, v_pref mode, tracker distSq, tracker records, remaining, now_goal; an absent section has length 0) and
+ *              the blob's size, for `size` rows, a tracker record of trk_words 4-byte words (0: none) and has_paths 0 / 1.  Pure.
+ *              SCA_ERR_ARG: size outside 1 .. 1536, negative trk_words, has_paths not 0 / 1, a NULL pointer.
+ *   sca_scene_checkpoint_info    the header's fields, after the WHOLE check of the blob that a load makes without a scene (envelope and
+ *              payload, below).  Pure, no context.  struct_bytes: sca_scene_harvest_get's rule.
+ *   sca_scene_checkpoint_bytes   the size of the blob sca_save_scenes writes for the scene as it stands now.
+ *   sca_save_scenes  out[e] (out_bytes[e] bytes) receives scene scene_ids[e].  A scene below its capacity saves its occupied rows only.
+ *   sca_load_scenes  in[e] (in_bytes[e] bytes) goes into scene scene_ids[e], which must hold the blob's episode: its size and its rows'
+ *              policies are compared.  Clears the named scenes' `fresh` words of the harvest like a restart.
+ *   cost       each call is one kernel launch (a workgroup per named scene) and one stream synchronisation however many scenes are named
+ *              (a save directly behind sca_set_state recounts the scenes' counters first, as sca_get_scene_state does); the bytes travel
+ *              through a page-locked block of the library's own, which grows once when a call needs more.
+ *   log        steps[s] is restored, so the log per scene (sca_scene_history_enable) goes on writing row steps[s] - 1: rows >= k of a
+ *              resumed scene are bit for bit the source's, rows < k are NOT the library's to fill -- they hold what the slot's memory held;
+ *              the caller keeps the source's rows 0 .. k-1 beside the blob if it wants the whole episode.
+ *   refusals   decided on the host before any device work; a refused call has changed nothing.  SCA_ERR_STATE: no scenes, no state yet,
+ *              between a policy pass and its env update.  SCA_ERR_ARG, the call: count <= 0 or a NULL array or buffer, an id outside
+ *              0 .. nscenes-1, a repeated id, an output buffer too small (the message names the bytes needed).  SCA_ERR_ARG at a load,
+ *              the envelope: wrong magic or format version, a byte count that is not the layout's, a checksum mismatch, trk_words or the
+ *              record size not this library's; the blob against the scene: a size other than the scene's current size, policy bytes that
+ *              differ from the scene's rows, tracker records present or absent against what the scene's policies need in this context
+ *              (present exactly when a device tracker is enabled and a row is SCA / RVO3D+Dubins), cursors with remaining > 0 and no
+ *              lists set, remaining[i] outside 0 .. the row's list length as set; the payload: a permutation that is not one of
+ *              0 .. size-1, unknown flag bits, a position that is not finite, a radius that is not positive, counters out of range (live
+ *              must be the number of rows without a flag), any tracker integer a kernel uses as a cursor, count or switch outside its
+ *              range.  A damaged blob never reaches the device. */
+struct sca_scene_checkpoint_info {       /* (a struct tag: the function of the same name fills it) */
+    int32_t struct_bytes, reserved;
+    int32_t format, lib_version;         /* the blob's format version; sca_version() of the library that wrote it */
+    int32_t size, trk_words, record_bytes;
+    int32_t has_tracker, has_paths;      /* 0 / 1 */
+    int32_t steps, live, prev;           /* the scene's counters at the save */
+    int64_t total_bytes;
+    uint64_t checksum;
+};
+int sca_scene_checkpoint_layout(int size, int trk_words, int has_paths, int64_t *offsets /*14*/, int64_t *total_bytes);
+int sca_scene_checkpoint_info(const void *blob, int64_t bytes, struct sca_scene_checkpoint_info *out, int32_t struct_bytes);
+int sca_scene_checkpoint_bytes(sca_ctx *ctx, int scene, int64_t *bytes);
+int sca_save_scenes(sca_ctx *ctx, int count, const int32_t *scene_ids /*count*/, void *const *out /*count*/, const int64_t *out_bytes /*count*/);
+int sca_load_scenes(sca_ctx *ctx, int count, const int32_t *scene_ids /*count*/, const void *const *in /*count*/, const int64_t *in_bytes /*count*/);
+
 /* the hot path ----------------------------------------------------------------------------------- */
 int sca_policy_pass(sca_ctx *ctx, int neighbor_mode);
 int sca_get_actions(sca_ctx *ctx, float *action /*n*7*/);

@@ -57,6 +57,16 @@ class RestartAttrs(C.Structure):
                 ('pitch_hi', dp)]
 
 
+class SceneCheckpointInfo(C.Structure):
+    """struct sca_scene_checkpoint_info: the header of a scene checkpoint (sca_scene_checkpoint_info)"""
+    _fields_ = [('struct_bytes', C.c_int32), ('reserved', C.c_int32), ('format', C.c_int32), ('lib_version', C.c_int32), ('size', C.c_int32),
+                ('trk_words', C.c_int32), ('record_bytes', C.c_int32), ('has_tracker', C.c_int32), ('has_paths', C.c_int32), ('steps', C.c_int32),
+                ('live', C.c_int32), ('prev', C.c_int32), ('total_bytes', C.c_int64), ('checksum', C.c_uint64)]
+
+
+CHECKPOINT_SECTIONS = 14                                          # sca_scene_checkpoint_layout's offsets
+
+
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against include/sca_hip.h
 SIGNATURES = {
     'sca_default_params': (None, [C.c_void_p]),                   # (version-100 form: 56 bytes)
@@ -96,6 +106,11 @@ SIGNATURES = {
     'sca_scene_harvest_enable': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_scene_harvest_get': (C.c_int, [C.c_void_p, C.POINTER(SceneHarvest), C.c_int32]),
     'sca_scene_harvest_collect': (C.c_int, [C.c_void_p, ip, C.POINTER(C.c_int32)]),
+    'sca_scene_checkpoint_layout': (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'sca_scene_checkpoint_info': (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(SceneCheckpointInfo), C.c_int32]),
+    'sca_scene_checkpoint_bytes': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]),
+    'sca_save_scenes': (C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    'sca_load_scenes': (C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     'sca_set_path_state': (C.c_int, [C.c_void_p, ip, dp]),
     'sca_policy_pass': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_get_actions': (C.c_int, [C.c_void_p, fp]),

@@ -323,10 +323,14 @@ struct sca_ctx {
         uint8_t *hv_host = nullptr;     // the harvest block (sca_scene_harvest_enable; HarvestLayout of nscenes and n, sca_scenes.h), null: off -- a step then enqueues nothing for it
         HarvestLayout hv_layout{};
         int32_t hv_batch_step = 0;      // env updates enqueued since the harvest was enabled
+        uint8_t *ck_host = nullptr;     // sca_save_scenes' / sca_load_scenes' page-locked block (CkptEntry table + blobs, sca_scenes.h), allocated on first use
+        size_t ck_bytes = 0;            // ... and its size: it grows when a call needs more
         void release() {                // the device and page-locked allocations, behind a synchronised stream; the flags and host vectors stay
             for (void *p : {(void *)v.scene_of, (void *)v.offsets, (void *)counters, (void *)v.heading_keep, (void *)ov.oroot, (void *)log.rows, (void *)size}) if (p) (void)hipFree(p);
             if (rs_host) (void)hipHostFree(rs_host);
             if (hv_host) (void)hipHostFree(hv_host);
+            if (ck_host) (void)hipHostFree(ck_host);
+            ck_host = nullptr; ck_bytes = 0;
             v = SceneView{}; counters = nullptr; size = nullptr; ov = SceneObsView{}; rs_host = nullptr; rs_bytes = 0; log = SceneLogView{}; hv_host = nullptr;
         }
     } scenes;
@@ -2085,6 +2089,221 @@ int sca_restart_scenes_paths(sca_ctx *c, int count, const int32_t *scene_ids, co
     API_ENTER(c);
     return restart_scenes(c, count, scene_ids, sizes, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading, obs_counts, obs_pos, obs_radius,
                           attrs, path_offsets, path_points);
+}
+// ---- scene checkpoints (include/sca_hip.h; the layout, the check and the calls' rules are sca_scenes.h's, the kernels sca_scenes.hip.h's) ---------
+static_assert(CKPT_LIB_VERSION == 103, "CkptHeader::lib_version is sca_version()");
+static_assert(sizeof(sca_dubins::AgentTrack) % 4 == 0 && sizeof(long) == 8, "the checkpoint moves the tracker record as 4-byte words and reads its cursors as 64-bit");
+static CkptTrackFields ckpt_track_fields() {
+    using sca_dubins::AgentTrack; using sca_dubins::Plan3D; using sca_dubins::Maneuver2D;
+    const int plan = (int)offsetof(AgentTrack, plan);
+    CkptTrackFields F;
+    F.words = (int)(sizeof(AgentTrack) / 4);
+    F.use_dubins = (int)offsetof(AgentTrack, is_use_dubins);
+    F.plan_ok = plan + (int)offsetof(Plan3D, ok);
+    F.h_ok = plan + (int)offsetof(Plan3D, h) + (int)offsetof(Maneuver2D, ok); F.v_ok = plan + (int)offsetof(Plan3D, v) + (int)offsetof(Maneuver2D, ok);
+    F.h_mode = plan + (int)offsetof(Plan3D, h) + (int)offsetof(Maneuver2D, mode); F.v_mode = plan + (int)offsetof(Plan3D, v) + (int)offsetof(Maneuver2D, mode);
+    F.plan_mode = plan + (int)offsetof(Plan3D, mode);
+    F.iters = plan + (int)offsetof(Plan3D, iters); F.rounds = plan + (int)offsetof(Plan3D, rounds); F.replans = (int)offsetof(AgentTrack, replans);
+    F.count = plan + (int)offsetof(Plan3D, count); F.next = (int)offsetof(AgentTrack, next);
+    return F;
+}
+static std::string ckpt_fault_text(const CkptCheck &k) {
+    const std::string at = std::to_string(k.entry);
+    switch (k.fault) {
+    case CKPT_SHORT: return "the blob is NULL or shorter than a checkpoint's header";
+    case CKPT_MAGIC_BAD: return "the blob is not a scene checkpoint (magic)";
+    case CKPT_FORMAT_BAD: return "the blob has another format version than this library writes (" + std::to_string(CKPT_FORMAT) + ")";
+    case CKPT_RECORD: return "the blob's tracker record or public record size is not this library's";
+    case CKPT_SIZE_RANGE: return "the blob's header holds a size outside 1 .. " + std::to_string(KD_WAVE_CAP) + " or a flag word that is not 0 / 1";
+    case CKPT_BYTES: return "the byte count is not the layout's for the blob's size (sca_scene_checkpoint_layout)";
+    case CKPT_CHECKSUM: return "the payload's checksum is not the header's";
+    case CKPT_SCENE_SIZE: return "the blob's size is not the scene's current size: restart the scene with the episode first";
+    case CKPT_POLICY: return "row " + at + " has another policy in the blob than in the scene (or none the library knows): restart the scene with the episode first";
+    case CKPT_TRACKER: return "tracker records are present in the blob and not needed by the scene in this context, or needed and absent";
+    case CKPT_NO_LISTS: return "row " + at + " has waypoints left (rem > 0) and the context has no waypoint lists set";
+    case CKPT_REM_RANGE: return "row " + at + " has a cursor outside 0 .. the length of the row's list as set";
+    case CKPT_PERM: return "the permutation is not one of 0 .. size - 1 (position " + at + ")";
+    case CKPT_FLAGS: return "row " + at + " has unknown flag bits or a v_pref mode other than 0 / 1";
+    case CKPT_NOT_FINITE: return "row " + at + " has a position that is not finite or a radius that is not positive";
+    case CKPT_COUNTERS: return "steps / live / prev or a step count are out of range, or live is not the number of rows without a flag";
+    case CKPT_TRACK_RANGE: return "row " + at + " has a tracker record with a cursor, count or word outside its range";
+    default: return "ok";
+    }
+}
+static int ckpt_call_refuse(sca_ctx *c, const char *who, const CkptCallCheck &k, const int32_t *scene_ids) {
+    const std::string w(who), at = std::to_string(k.entry);
+    switch (k.fault) {
+    case CKPT_CALL_NO_SCENES: c->err = w + ": no scenes -- sca_set_scenes first"; break;
+    case CKPT_CALL_NO_STATE: c->err = w + ": no state yet -- sca_set_state first"; break;
+    case CKPT_CALL_MID_STEP: c->err = w + " between a policy pass and its env update: finish the step first"; break;
+    case CKPT_CALL_BAD_COUNT: c->err = w + ": count must be positive and no array NULL"; break;
+    case CKPT_CALL_BAD_ID: c->err = w + ": scene_ids[" + at + "] = " + std::to_string(scene_ids[k.entry]) + " is not a scene of this context (0 .. " + std::to_string(c->scenes.v.nscenes - 1) + ")"; break;
+    case CKPT_CALL_REPEATED_ID: c->err = w + ": scene_ids[" + at + "] = " + std::to_string(scene_ids[k.entry]) + " is named twice"; break;
+    default: c->err = w + ": buffer " + at + " is NULL";
+    }
+    return scene_checkpoint_call_error_code(k.fault);
+}
+// the words a scene's layout depends on, as the scene stands in this context
+static void ckpt_scene_words(const sca_ctx *c, int s, int *size, int *trk_words, int *has_paths) {
+    const int lo = c->scenes.h_off[s], ns = c->scenes.h_size[s];
+    bool tracked = false;
+    for (int a = lo; a < lo + ns; a++) tracked = tracked || restart_policy_tracked(c->h_policy[a]);
+    *size = ns;
+    *trk_words = c->trk_on && tracked ? (int)(sizeof(sca_dubins::AgentTrack) / 4) : 0;
+    *has_paths = c->paths_on ? 1 : 0;
+}
+static int ckpt_block(sca_ctx *c, size_t bytes) {
+    if (c->scenes.ck_host && c->scenes.ck_bytes >= bytes) return 0;
+    CHK(c, hipStreamSynchronize(c->stream));                            // (every call ends with its synchronisation: no launch still uses the block)
+    if (c->scenes.ck_host) (void)hipHostFree(c->scenes.ck_host);
+    c->scenes.ck_host = nullptr; c->scenes.ck_bytes = 0;
+    CHK(c, hipHostMalloc((void **)&c->scenes.ck_host, bytes, hipHostMallocMapped | hipHostMallocCoherent));
+    c->scenes.ck_bytes = bytes;
+    return 0;
+}
+static CkptDev ckpt_dev(sca_ctx *c) {
+    CkptDev d{};
+    d.rec = c->d.rec; d.heading = c->d.heading; d.heading_keep = c->scenes.v.heading_keep; d.vpref_ext = c->d.vpref_ext; d.total_dist = c->d.total_dist;
+    d.step_num = c->d.step_num; d.status = c->d.status; d.aperm = c->d.aperm; d.vpref_mode = c->d.vpref_mode; d.done_count = c->d.done_count;
+    d.offsets = c->scenes.v.offsets; d.live = c->scenes.v.live; d.prev = c->scenes.v.prev; d.steps = c->scenes.v.steps;
+    if (c->trk_on) { d.trk_nbr0 = c->trk.nbr0; d.trk_st = (restart_u32 *)c->trk.st; }
+    if (c->paths_on) { d.rem = c->path.rem; d.now_goal = c->path.now_goal; }
+    return d;
+}
+int sca_scene_checkpoint_layout(int size, int trk_words, int has_paths, int64_t *offsets, int64_t *total_bytes) {
+    if (size < 1 || size > KD_WAVE_CAP || trk_words < 0 || (has_paths != 0 && has_paths != 1) || !offsets || !total_bytes) return SCA_ERR_ARG;
+    const CkptLayout L = scene_checkpoint_layout(size, trk_words, has_paths);
+    for (int s = 0; s < CK_SECTIONS; s++) offsets[s] = L.off[s];
+    *total_bytes = L.total;
+    return 0;
+}
+int sca_scene_checkpoint_info(const void *blob, int64_t bytes, struct sca_scene_checkpoint_info *out, int32_t struct_bytes) {
+    if (!out || struct_bytes < (int32_t)offsetof(struct sca_scene_checkpoint_info, format) || struct_bytes > (int32_t)sizeof(struct sca_scene_checkpoint_info)) return SCA_ERR_ARG;
+    CkptHeader H;
+    const CkptCheck k = scene_checkpoint_check(blob, bytes, ckpt_track_fields(), nullptr, &H);
+    if (k.fault != CKPT_OK) return scene_checkpoint_error_code(k.fault);
+    struct sca_scene_checkpoint_info I{};
+    I.struct_bytes = struct_bytes; I.reserved = 0; I.format = H.format; I.lib_version = H.lib_version; I.size = H.size; I.trk_words = H.trk_words; I.record_bytes = H.rec_bytes;
+    I.has_tracker = H.has_track; I.has_paths = H.has_paths; I.steps = H.steps; I.live = H.live; I.prev = H.prev; I.total_bytes = H.total_bytes; I.checksum = H.checksum;
+    std::memcpy(out, &I, (size_t)struct_bytes);
+    out->struct_bytes = struct_bytes;
+    return 0;
+}
+int sca_scene_checkpoint_bytes(sca_ctx *c, int scene, int64_t *bytes) {
+    API_ENTER(c);
+    ARG(c, bytes);
+    if (!c->scenes.on) { c->err = "sca_scene_checkpoint_bytes: no scenes -- sca_set_scenes first"; return SCA_ERR_STATE; }
+    if (scene < 0 || scene >= c->scenes.v.nscenes) { c->err = "sca_scene_checkpoint_bytes: scene " + std::to_string(scene) + " is not a scene of this context"; return SCA_ERR_ARG; }
+    int ns, tw, hp;
+    ckpt_scene_words(c, scene, &ns, &tw, &hp);
+    *bytes = scene_checkpoint_layout(ns, tw, hp).total;
+    return 0;
+}
+// One launch of k_scene_save (a workgroup per named scene) into the page-locked block, one synchronisation, then the host completes the
+// headers -- policies, sizes, the checksum -- and copies the blobs out.  Where the state came from outside since the last env update the
+// scenes' counters are recounted first, as every reader of them does (scenes_recount).
+int sca_save_scenes(sca_ctx *c, int count, const int32_t *scene_ids, void *const *out, const int64_t *out_bytes) {
+    API_ENTER(c);
+    const CkptCallCheck k = scene_checkpoint_call_check(c->scenes.on ? c->scenes.v.nscenes : 0, c->state_set, c->scenes.begun, count, scene_ids, (const void *const *)out, out_bytes);
+    if (k.fault != CKPT_CALL_OK) return ckpt_call_refuse(c, "sca_save_scenes", k, scene_ids);
+    std::vector<CkptEntry> tab((size_t)count);
+    int64_t at = ckpt_block_round((int64_t)sizeof(CkptEntry) * count);
+    for (int e = 0; e < count; e++) {
+        CkptEntry &x = tab[(size_t)e];
+        x.scene = scene_ids[e]; x.reserved = 0;
+        ckpt_scene_words(c, x.scene, &x.size, &x.trk_words, &x.has_paths);
+        const int64_t need = scene_checkpoint_layout(x.size, x.trk_words, x.has_paths).total;
+        if (out_bytes[e] < need) {
+            c->err = "sca_save_scenes: buffer " + std::to_string(e) + " holds " + std::to_string(out_bytes[e]) + " bytes, scene " + std::to_string(x.scene) + " needs " + std::to_string(need) +
+                     " (sca_scene_checkpoint_bytes)";
+            return SCA_ERR_ARG;
+        }
+        x.at = at;
+        at = ckpt_block_round(at + need);
+    }
+    if (int r = ckpt_block(c, (size_t)at)) return r;
+    uint8_t *b = c->scenes.ck_host;
+    std::memset(b, 0, (size_t)at);                                       // (the bytes between the sections are part of the sum)
+    std::memcpy(b, tab.data(), sizeof(CkptEntry) * (size_t)count);
+    if (int r = scenes_recount(c, c->stream)) return r;
+    hipLaunchKernelGGL(k_scene_save, dim3(count), dim3(CKPT_T), 0, c->stream, ckpt_dev(c), b);
+    CHK(c, hipGetLastError());
+    CHK(c, hipStreamSynchronize(c->stream));
+    for (int e = 0; e < count; e++) {
+        const CkptEntry &x = tab[(size_t)e];
+        const CkptLayout L = scene_checkpoint_layout(x.size, x.trk_words, x.has_paths);
+        uint8_t *o = b + x.at;
+        const int lo = c->scenes.h_off[x.scene];
+        std::memcpy(o + L.off[CK_POLICY], c->h_policy.data() + lo, (size_t)x.size);
+        if (!c->perm_on_device) {                                       // the live permutation is still the host's (no device build since it was set)
+            int32_t *perm = (int32_t *)(o + L.off[CK_PERM]);
+            for (int i = 0; i < x.size; i++) perm[i] = c->h_perm[lo + i] - lo;
+        }
+        CkptHeader H;
+        std::memcpy(&H, o, sizeof H);                                   // (steps, live, prev: the kernel's)
+        H.magic = CKPT_MAGIC; H.format = CKPT_FORMAT; H.lib_version = sca_version(); H.size = x.size; H.trk_words = x.trk_words; H.rec_bytes = CKPT_REC_BYTES;
+        H.has_track = x.trk_words > 0 ? 1 : 0; H.has_paths = x.has_paths; H.reserved = 0; H.total_bytes = L.total;
+        H.checksum = scene_checkpoint_sum(o + sizeof H, L.total - (int64_t)sizeof H);
+        std::memcpy(o, &H, sizeof H);
+        std::memcpy(out[e], o, (size_t)L.total);
+    }
+    return 0;
+}
+// Every blob is checked whole on the host (scene_checkpoint_check) before any device work; then the blobs go into the page-locked block,
+// ONE launch of k_scene_load scatters them, and the call's one synchronisation follows.  Behind it the host mirrors follow, as after a
+// restart: the permutation while the host holds it, the radius, the harvest's fresh words.
+int sca_load_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const void *const *in, const int64_t *in_bytes) {
+    API_ENTER(c);
+    const CkptCallCheck k = scene_checkpoint_call_check(c->scenes.on ? c->scenes.v.nscenes : 0, c->state_set, c->scenes.begun, count, scene_ids, in, in_bytes);
+    if (k.fault != CKPT_CALL_OK) return ckpt_call_refuse(c, "sca_load_scenes", k, scene_ids);
+    const CkptTrackFields F = ckpt_track_fields();
+    std::vector<CkptEntry> tab((size_t)count);
+    int64_t at = ckpt_block_round((int64_t)sizeof(CkptEntry) * count);
+    for (int e = 0; e < count; e++) {
+        const int s = scene_ids[e], lo = c->scenes.h_off[s];
+        const CkptScene X{c->scenes.h_size[s], c->h_policy.data() + lo, c->trk_on, c->paths_on,
+                          !c->paths_on ? nullptr : c->path_W > 0 ? c->h_path_len.data() + lo : nullptr};
+        std::vector<int32_t> len;
+        CkptScene Y = X;
+        if (c->paths_on && c->path_W == 0) {                            // the block form: lengths from the offsets as set
+            len.resize((size_t)X.size);
+            for (int i = 0; i < X.size; i++) len[(size_t)i] = c->h_path_off[lo + i + 1] - c->h_path_off[lo + i];
+            Y.path_len = len.data();
+        }
+        CkptHeader H;
+        const CkptCheck kc = scene_checkpoint_check(in[e], in_bytes[e], F, &Y, &H);
+        if (kc.fault != CKPT_OK) {
+            c->err = "sca_load_scenes: blob " + std::to_string(e) + " (scene " + std::to_string(s) + "): " + ckpt_fault_text(kc);
+            return scene_checkpoint_error_code(kc.fault);
+        }
+        CkptEntry &x = tab[(size_t)e];
+        x.scene = s; x.size = H.size; x.trk_words = H.trk_words; x.has_paths = H.has_paths; x.reserved = 0; x.at = at;
+        at = ckpt_block_round(at + H.total_bytes);
+    }
+    if (int r = ckpt_block(c, (size_t)at)) return r;
+    uint8_t *b = c->scenes.ck_host;
+    std::memcpy(b, tab.data(), sizeof(CkptEntry) * (size_t)count);
+    for (int e = 0; e < count; e++) std::memcpy(b + tab[(size_t)e].at, in[e], (size_t)in_bytes[e]);
+    hipLaunchKernelGGL(k_scene_load, dim3(count), dim3(CKPT_T), 0, c->stream, ckpt_dev(c), (const uint8_t *)b);
+    CHK(c, hipGetLastError());
+    CHK(c, hipStreamSynchronize(c->stream));
+    for (int e = 0; e < count; e++) {
+        const CkptEntry &x = tab[(size_t)e];
+        const CkptLayout L = scene_checkpoint_layout(x.size, x.trk_words, x.has_paths);
+        const uint8_t *o = b + x.at;
+        const int lo = c->scenes.h_off[x.scene];
+        const int32_t *perm = (const int32_t *)(o + L.off[CK_PERM]);
+        for (int i = 0; i < x.size; i++) {
+            c->h_perm[lo + i] = lo + perm[i];
+            double radius;
+            std::memcpy(&radius, o + L.off[CK_REC] + (size_t)CKPT_REC_BYTES * i + 40, sizeof radius);
+            c->h_rec[lo + i].radius = radius; c->max_radius = std::max(c->max_radius, radius);   // only grows: a conservative filter, as under restarts
+        }
+    }
+    scene_harvest_clear_fresh(c, count, scene_ids);                    // like a restart: what the slot's earlier episode handed over is gone
+    c->h_pos_valid = false;
+    c->near_valid = false;
+    return 0;
 }
 int sca_get_scene_sizes(sca_ctx *c, int32_t *size) {
     API_ENTER(c);

@@ -631,6 +631,217 @@ inline RestartPathLayout restart_paths_layout(int64_t begin, int max_n, int W) {
 // the rows' lists are written (slot form): from the block's path sections, or empty where the call brought none
 constexpr uint32_t RESTART_HAS_PATH_SLOTS = 256, RESTART_HAS_PATHS = 512;
 
+// ---- scene checkpoints (sca_save_scenes / sca_load_scenes) ------------------------------------------------------------------------------------------
+// A scene's whole MUTABLE state as one blob of bytes: what scene_restart_fill / scene_restart_paths reset plus what PartMig carries
+// (sca_partition.hip.h), for the rows the scene occupies.  The episode's definition (constants, attributes, obstacles, waypoint lists, goal
+// headings) is not in it: a resume is a restart with the definition, then a load.  The blob is pointer-free and speaks scene-local terms
+// (the permutation 0 .. size - 1), so it loads into any slot of any context.  Layout: a fixed header, then the sections in the order of
+// CkptSection, each on a 16-byte boundary; a section the blob does not carry (tracker, cursors) has length 0.  Everything per row is whole
+// 4-byte words -- the records 16-byte pieces -- so k_scene_save / k_scene_load (sca_scenes.hip.h) move a section as consecutive words by
+// consecutive lanes; the one byte-sized column, vpref_mode, travels as a word per row for that reason.
+constexpr uint32_t CKPT_MAGIC = 0x504b4353u;       // "SCKP"
+constexpr int32_t CKPT_FORMAT = 1;
+constexpr int32_t CKPT_LIB_VERSION = 103;          // sca_version() (sca_hip.hip asserts it)
+constexpr int64_t CKPT_ALIGN = 16;
+constexpr int32_t CKPT_REC_BYTES = 48;             // sizeof(PubRec): px py pz f64, vx vy vz f32, flags u32, radius f64
+constexpr int32_t CKPT_COUNT_MAX = 1 << 20;        // bound of AgentTrack's sample count / cursor: compute_sampling yields about a thousand samples (finish_plan)
+struct CkptHeader {                                // 64 bytes
+    uint32_t magic; int32_t format, lib_version, size;
+    int32_t trk_words, rec_bytes, has_track, has_paths;
+    int32_t steps, live, prev, reserved;
+    int64_t total_bytes;                           // header + sections
+    uint64_t checksum;                             // scene_checkpoint_sum over the bytes behind the header
+};
+static_assert(sizeof(CkptHeader) == 64, "the checkpoint's header is 64 bytes");
+enum CkptSection : int { CK_POLICY = 0,            // [size] u8: the rows' policies, which the loading scene must have (written by the host)
+                         CK_REC, CK_HEADING, CK_HEADING_KEEP, CK_VPREF_EXT, CK_TOTAL_DIST, CK_STEP_NUM, CK_STATUS, CK_PERM, CK_VPREF_MODE,
+                         CK_TRK_NBR0, CK_TRACK,    // with the tracker's records
+                         CK_REM, CK_NOW_GOAL,      // with the waypoint cursors
+                         CK_SECTIONS };
+struct CkptLayout { int64_t off[CK_SECTIONS]; int64_t len[CK_SECTIONS]; int64_t total; };
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int64_t ckpt_section_row_bytes(int s, int trk_words, int has_paths) {
+    return s == CK_POLICY ? 1 : s == CK_REC ? CKPT_REC_BYTES : s == CK_HEADING || s == CK_HEADING_KEEP || s == CK_VPREF_EXT ? 24
+           : s == CK_TOTAL_DIST ? 8 : s == CK_STEP_NUM || s == CK_STATUS || s == CK_PERM || s == CK_VPREF_MODE ? 4
+           : s == CK_TRK_NBR0 ? (trk_words > 0 ? 8 : 0) : s == CK_TRACK ? (trk_words > 0 ? 4 * (int64_t)trk_words : 0)
+           : s == CK_REM ? (has_paths ? 4 : 0) : (has_paths ? 24 : 0);
+}
+// a pure function of (size, trk_words, has_paths): the kernels and the host both call it
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline CkptLayout scene_checkpoint_layout(int size, int trk_words, int has_paths) {
+    CkptLayout L;
+    int64_t at = (int64_t)sizeof(CkptHeader);
+    for (int s = 0; s < CK_SECTIONS; s++) {
+        L.off[s] = at;
+        L.len[s] = ckpt_section_row_bytes(s, trk_words, has_paths) * (int64_t)size;
+        at += (L.len[s] + CKPT_ALIGN - 1) / CKPT_ALIGN * CKPT_ALIGN;
+    }
+    L.total = at;
+    return L;
+}
+// FNV-1a over 64-bit words (every blob is a whole number of them): any one changed byte changes the sum
+inline uint64_t scene_checkpoint_sum(const void *bytes, int64_t count) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    const unsigned char *p = (const unsigned char *)bytes;
+    for (int64_t i = 0; i + 8 <= count; i += 8) {
+        uint64_t w = 0;
+        for (int k = 0; k < 8; k++) w |= (uint64_t)p[i + k] << (8 * k);
+        h = (h ^ w) * 0x100000001b3ull;
+    }
+    return h;
+}
+// where the integers of one AgentTrack record (sca_dubins.hpp) stand, in bytes from the record's start: the ones a kernel uses as a
+// cursor, a count or a switch.  Filled with offsetof where the type is known (sca_hip.hip, tests/scene_checkpoint_harness.cpp).
+struct CkptTrackFields {
+    int words;                                     // sizeof(AgentTrack) / 4
+    int use_dubins, plan_ok, h_ok, v_ok;           // bool bytes
+    int h_mode, v_mode, plan_mode;                 // char[3], char[3], char[7]: Dubins words, 'L' 'S' 'R' or 0
+    int iters, rounds, replans;                    // int32
+    int count, next;                               // int64 (long)
+};
+enum CkptFault {
+    CKPT_OK = 0,
+    CKPT_SHORT,             // fewer bytes than a header, or a NULL blob                              } the envelope: SCA_ERR_ARG
+    CKPT_MAGIC_BAD,         // not a checkpoint                                                       }
+    CKPT_FORMAT_BAD,        // another format version                                                 }
+    CKPT_RECORD,            // trk_words or the record size are not this library's                    }
+    CKPT_SIZE_RANGE,        // size outside 1 .. KD_WAVE_CAP, or flag words that are not 0 / 1        }
+    CKPT_BYTES,             // the byte count is not the layout's                                     }
+    CKPT_CHECKSUM,          // the payload's sum is not the header's                                  }
+    CKPT_SCENE_SIZE,        // size is not the scene's current size                                   } against the scene: SCA_ERR_ARG
+    CKPT_POLICY,            // a row's policy byte differs from the scene's (entry: the row)          }
+    CKPT_TRACKER,           // tracker records present / absent against what the scene needs here     }
+    CKPT_NO_LISTS,          // a cursor with rem > 0 while no lists are set (entry: the row)          }
+    CKPT_REM_RANGE,         // rem[i] outside 0 .. the row's list length as set (entry: the row)      }
+    CKPT_PERM,              // the permutation is not one of 0 .. size - 1 (entry: the position)      } the payload: SCA_ERR_ARG
+    CKPT_FLAGS,             // unknown flag bits, or a vpref_mode other than 0 / 1 (entry: the row)   }
+    CKPT_NOT_FINITE,        // a position that is not finite, a radius that is not positive (entry: the row) }
+    CKPT_COUNTERS,          // steps / live / prev out of range, or live is not the rows without flags }
+    CKPT_TRACK_RANGE        // an AgentTrack integer outside its range (entry: the row)               }
+};
+struct CkptCheck { CkptFault fault; int entry; };
+// what the rules read of the loading scene; NULL: the envelope and the payload alone (sca_scene_checkpoint_info)
+struct CkptScene {
+    int size;                                      // the rows the scene occupies now
+    const uint8_t *policy;                         // [size] their policies
+    bool tracker_on;                               // the context's device tracker
+    bool paths_on;                                 // waypoint lists are set
+    const int32_t *path_len;                       // [size] the rows' list lengths as set (paths_on)
+};
+inline int64_t ckpt_i64(const unsigned char *p) { int64_t v; unsigned char *q = (unsigned char *)&v; for (int k = 0; k < 8; k++) q[k] = p[k]; return v; }
+inline int32_t ckpt_i32(const unsigned char *p) { int32_t v; unsigned char *q = (unsigned char *)&v; for (int k = 0; k < 4; k++) q[k] = p[k]; return v; }
+inline double ckpt_f64(const unsigned char *p) { double v; unsigned char *q = (unsigned char *)&v; for (int k = 0; k < 8; k++) q[k] = p[k]; return v; }
+inline bool ckpt_word_ok(const unsigned char *m, int n) { for (int k = 0; k < n; k++) if (m[k] != 0 && m[k] != 'L' && m[k] != 'S' && m[k] != 'R') return false; return true; }
+// THE check of a blob, whole: envelope, then the blob against the scene, then every payload value a kernel would use as an index, a count
+// or a switch.  Reads bytes [0, bytes) of `blob` and nothing else; head (nullable) receives the header once the envelope holds.
+inline CkptCheck scene_checkpoint_check(const void *blob, int64_t bytes, const CkptTrackFields &F, const CkptScene *scene, CkptHeader *head) {
+    if (blob == nullptr || bytes < (int64_t)sizeof(CkptHeader)) return {CKPT_SHORT, -1};
+    const unsigned char *b = (const unsigned char *)blob;
+    CkptHeader H;
+    { unsigned char *q = (unsigned char *)&H; for (std::size_t k = 0; k < sizeof(CkptHeader); k++) q[k] = b[k]; }
+    if (H.magic != CKPT_MAGIC) return {CKPT_MAGIC_BAD, -1};
+    if (H.format != CKPT_FORMAT) return {CKPT_FORMAT_BAD, -1};
+    if (H.rec_bytes != CKPT_REC_BYTES || (H.trk_words != 0 && H.trk_words != F.words)) return {CKPT_RECORD, -1};
+    if (H.size < 1 || H.size > KD_WAVE_CAP || (H.has_track != 0 && H.has_track != 1) || (H.has_paths != 0 && H.has_paths != 1) || (H.has_track != 0) != (H.trk_words != 0))
+        return {CKPT_SIZE_RANGE, -1};
+    const CkptLayout L = scene_checkpoint_layout(H.size, H.trk_words, H.has_paths);
+    if (H.total_bytes != L.total || bytes != L.total) return {CKPT_BYTES, -1};
+    if (scene_checkpoint_sum(b + sizeof(CkptHeader), L.total - (int64_t)sizeof(CkptHeader)) != H.checksum) return {CKPT_CHECKSUM, -1};
+    if (head) *head = H;
+    const int N = H.size;
+    const unsigned char *pol = b + L.off[CK_POLICY];
+    if (scene) {
+        if (scene->size != N) return {CKPT_SCENE_SIZE, -1};
+        bool tracked = false;
+        for (int i = 0; i < N; i++) {
+            if (pol[i] != scene->policy[i]) return {CKPT_POLICY, i};
+            tracked = tracked || restart_policy_tracked(pol[i]);
+        }
+        if ((scene->tracker_on && tracked) != (H.has_track != 0)) return {CKPT_TRACKER, -1};
+        for (int i = 0; i < N; i++) {
+            const int rem = H.has_paths ? ckpt_i32(b + L.off[CK_REM] + 4 * (int64_t)i) : 0;
+            const int len = scene->paths_on ? scene->path_len[i] : 0;
+            if (!scene->paths_on && rem > 0) return {CKPT_NO_LISTS, i};
+            if (H.has_paths ? (rem < 0 || rem > len) : len > 0) return {CKPT_REM_RANGE, i};
+        }
+    }
+    for (int i = 0; i < N; i++) if (pol[i] > SCA_POLICY_RVO3D_DUBINS) return {CKPT_POLICY, i};
+    {
+        std::vector<uint8_t> seen((std::size_t)N, (uint8_t)0);
+        for (int p = 0; p < N; p++) {
+            const int32_t a = ckpt_i32(b + L.off[CK_PERM] + 4 * (int64_t)p);
+            if (a < 0 || a >= N || seen[(std::size_t)a]) return {CKPT_PERM, p};
+            seen[(std::size_t)a] = 1;
+        }
+    }
+    int running = 0;
+    for (int i = 0; i < N; i++) {
+        const unsigned char *r = b + L.off[CK_REC] + (int64_t)CKPT_REC_BYTES * i;
+        const uint32_t flags = (uint32_t)ckpt_i32(r + 36);
+        const uint32_t mode = (uint32_t)ckpt_i32(b + L.off[CK_VPREF_MODE] + 4 * (int64_t)i);
+        if ((flags & ~7u) != 0 || mode > 1u) return {CKPT_FLAGS, i};
+        running += (flags & 7u) ? 0 : 1;
+        bool ok = true;
+        for (int k = 0; k < 3; k++) ok = ok && restart_finite(ckpt_f64(r + 8 * k));
+        const double radius = ckpt_f64(r + 40);
+        ok = ok && restart_finite(radius) && radius > 0.0;                // (feeds the conservative reach filters, like a restart's radius)
+        if (!ok) return {CKPT_NOT_FINITE, i};
+        if (ckpt_i32(b + L.off[CK_STEP_NUM] + 4 * (int64_t)i) < 0) return {CKPT_COUNTERS, i};
+    }
+    if (H.steps < 0 || H.prev < 0 || H.prev > N || H.live != running) return {CKPT_COUNTERS, -1};
+    if (H.has_track)
+        for (int i = 0; i < N; i++) {
+            const unsigned char *t = b + L.off[CK_TRACK] + 4 * (int64_t)F.words * i;
+            const int64_t count = ckpt_i64(t + F.count), next = ckpt_i64(t + F.next);
+            const bool ok = t[F.use_dubins] <= 1 && t[F.plan_ok] <= 1 && t[F.h_ok] <= 1 && t[F.v_ok] <= 1 && ckpt_word_ok(t + F.h_mode, 3) && ckpt_word_ok(t + F.v_mode, 3) &&
+                            ckpt_word_ok(t + F.plan_mode, 7) && ckpt_i32(t + F.iters) >= 0 && ckpt_i32(t + F.rounds) >= 0 && ckpt_i32(t + F.replans) >= 0 &&
+                            count >= 0 && count <= CKPT_COUNT_MAX && next >= 0 && next <= count;
+            if (!ok) return {CKPT_TRACK_RANGE, i};
+        }
+    return {CKPT_OK, -1};
+}
+inline int scene_checkpoint_error_code(CkptFault f) { return f == CKPT_OK ? SCA_OK : SCA_ERR_ARG; }
+
+// the call's own rules, for both entry points (op: 0 save, 1 load; bufs / sizes: the callers' arrays)
+enum CkptCallFault {
+    CKPT_CALL_OK = 0,
+    CKPT_CALL_NO_SCENES,    // the context holds no scenes                                            } SCA_ERR_STATE
+    CKPT_CALL_NO_STATE,     // no state yet                                                           }
+    CKPT_CALL_MID_STEP,     // between a policy pass and its env update                               }
+    CKPT_CALL_BAD_COUNT,    // count <= 0 or a NULL array                                             } SCA_ERR_ARG
+    CKPT_CALL_BAD_ID,       // an id outside 0 .. nscenes - 1 (entry: its index)                      }
+    CKPT_CALL_REPEATED_ID,  // an id named twice (entry: the index of the second mention)             }
+    CKPT_CALL_NO_BUFFER     // bufs[entry] is NULL                                                    }
+};
+struct CkptCallCheck { CkptCallFault fault; int entry; };
+inline CkptCallCheck scene_checkpoint_call_check(int nscenes, bool state_set, bool scene_begun, int count, const int32_t *scene_ids, const void *const *bufs,
+                                                 const int64_t *sizes) {
+    if (nscenes <= 0) return {CKPT_CALL_NO_SCENES, -1};
+    if (!state_set) return {CKPT_CALL_NO_STATE, -1};
+    if (scene_begun) return {CKPT_CALL_MID_STEP, -1};
+    if (count <= 0 || scene_ids == nullptr || bufs == nullptr || sizes == nullptr) return {CKPT_CALL_BAD_COUNT, -1};
+    std::vector<uint8_t> named((std::size_t)nscenes, (uint8_t)0);
+    for (int e = 0; e < count; e++) {
+        const int s = scene_ids[e];
+        if (s < 0 || s >= nscenes) return {CKPT_CALL_BAD_ID, e};
+        if (named[(std::size_t)s]) return {CKPT_CALL_REPEATED_ID, e};
+        named[(std::size_t)s] = 1;
+        if (bufs[e] == nullptr) return {CKPT_CALL_NO_BUFFER, e};
+    }
+    return {CKPT_CALL_OK, -1};
+}
+inline int scene_checkpoint_call_error_code(CkptCallFault f) { return f == CKPT_CALL_OK ? SCA_OK : f <= CKPT_CALL_MID_STEP ? SCA_ERR_STATE : SCA_ERR_ARG; }
+// The page-locked block both calls go through: one 32-byte entry per named scene (scene id, occupied rows, the two words the layout
+// depends on, the byte the scene's blob starts at), then the blobs, each on a 128-byte boundary.
+struct CkptEntry { int32_t scene, size, trk_words, has_paths; int64_t at, reserved; };
+static_assert(sizeof(CkptEntry) == 32, "one table entry is two 16-byte pieces");
+constexpr int64_t CKPT_BLOCK_ALIGN = 128;
+inline int64_t ckpt_block_round(int64_t x) { return (x + CKPT_BLOCK_ALIGN - 1) / CKPT_BLOCK_ALIGN * CKPT_BLOCK_ALIGN; }
+
 // ---- a trajectory log per scene (sca_scene_history_enable) -------------------------------------------------------------------------------------
 // One allocation of capacity x n rows of SCENE_LOG_ROW_BYTES (HistRow, sca_kernels.hip.h).  Scene s owns rows [capacity * offsets[s],
 // capacity * offsets[s + 1]); inside its part the layout is [row][agent] with pitch n_s, so any window of rows of one scene is one contiguous

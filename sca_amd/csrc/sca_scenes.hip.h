@@ -503,4 +503,102 @@ __global__ __launch_bounds__(HARVEST_T) void k_scene_harvest(SceneView v, Harves
     ((sca_scene_summary *)(h.blk + h.L.off[HV_SUMMARY]))[s] = r;
 }
 
+
+// ---- scene checkpoints (sca_save_scenes / sca_load_scenes; the blob's layout and its check are sca_scenes.h's) -----------------------------------
+// One workgroup per named scene, between two steps.  k_scene_save gathers the scene's occupied rows into the library's page-locked block
+// (CkptEntry table in front, the blobs behind it), k_scene_load scatters a blob the host has CHECKED (scene_checkpoint_check: sizes,
+// permutation, cursors and tracker integers are in range before this kernel sees them) back into the rows at offsets[s].  The block is host
+// memory: every section travels as consecutive 4-byte words -- the records as 16-byte pieces -- by consecutive lanes, as k_scene_harvest
+// and k_host_egress write theirs.  The permutation is stored in scene-local terms and rebased on the way in; the kd-tree, the neighbour
+// lists, action rows, diag and vpref_used are not state: the next pass rebuilds them from what is here before it reads them.
+// Nothing outside the named scenes' occupied rows and counters is written; the only shared words are K4's striped done_count, adjusted
+// for the rows whose done-ness changes by the rule scene_restart_fill / scene_restart_vacate have.  No other atomics.
+struct CkptDev {
+    PubRec *rec;
+    double *heading, *heading_keep, *vpref_ext, *total_dist;
+    int32_t *step_num, *status, *aperm;
+    uint8_t *vpref_mode;
+    int32_t *done_count;
+    const int32_t *offsets;
+    int32_t *live, *prev, *steps;
+    double *trk_nbr0;               // the device tracker's, null without one
+    restart_u32 *trk_st;
+    int32_t *rem;                   // the waypoint cursors, null without lists
+    double *now_goal;
+};
+static_assert(sizeof(PubRec) == CKPT_REC_BYTES, "CkptLayout's records");
+constexpr int CKPT_T = RESTART_T;
+constexpr int CKPT_HEAD_STEPS = 8;  // CkptHeader::steps, live, prev as words of the header
+__device__ __forceinline__ void ckpt_words(void *dst, const void *src, int64_t words, int t) {
+    restart_u32 *to = (restart_u32 *)dst;
+    const restart_u32 *from = (const restart_u32 *)src;
+    for (int64_t w = t; w < words; w += CKPT_T) to[w] = from[w];
+}
+__global__ __launch_bounds__(CKPT_T) void k_scene_save(CkptDev d, uint8_t *blk) {
+    const int t = (int)threadIdx.x;
+    const CkptEntry e = ((const CkptEntry *)blk)[blockIdx.x];
+    const int s = e.scene, N = e.size, tw = e.trk_words;
+    const int64_t lo = d.offsets[s];
+    const CkptLayout L = scene_checkpoint_layout(N, tw, e.has_paths);
+    uint8_t *o = blk + e.at;
+    scene_restart_pieces(o + L.off[CK_REC], d.rec + lo, (int64_t)N * (CKPT_REC_BYTES / 16), t);
+    ckpt_words(o + L.off[CK_HEADING], d.heading + 3 * lo, 6 * (int64_t)N, t);
+    ckpt_words(o + L.off[CK_HEADING_KEEP], d.heading_keep + 3 * lo, 6 * (int64_t)N, t);
+    ckpt_words(o + L.off[CK_VPREF_EXT], d.vpref_ext + 3 * lo, 6 * (int64_t)N, t);
+    ckpt_words(o + L.off[CK_TOTAL_DIST], d.total_dist + lo, 2 * (int64_t)N, t);
+    ckpt_words(o + L.off[CK_STEP_NUM], d.step_num + lo, N, t);
+    ckpt_words(o + L.off[CK_STATUS], d.status + lo, N, t);
+    int32_t *perm = (int32_t *)(o + L.off[CK_PERM]);
+    restart_u32 *mode = (restart_u32 *)(o + L.off[CK_VPREF_MODE]);
+    for (int i = t; i < N; i += CKPT_T) { perm[i] = d.aperm[lo + i] - (int32_t)lo; mode[i] = d.vpref_mode[lo + i]; }
+    if (tw > 0) {
+        ckpt_words(o + L.off[CK_TRK_NBR0], d.trk_nbr0 + lo, 2 * (int64_t)N, t);
+        ckpt_words(o + L.off[CK_TRACK], d.trk_st + lo * tw, (int64_t)N * tw, t);
+    }
+    if (e.has_paths) {
+        ckpt_words(o + L.off[CK_REM], d.rem + lo, N, t);
+        ckpt_words(o + L.off[CK_NOW_GOAL], d.now_goal + 3 * lo, 6 * (int64_t)N, t);
+    }
+    if (t < 3) ((int32_t *)o)[CKPT_HEAD_STEPS + t] = t == 0 ? d.steps[s] : t == 1 ? d.live[s * SCENE_LINE] : d.prev[s];
+}
+__global__ __launch_bounds__(CKPT_T) void k_scene_load(CkptDev d, const uint8_t *blk) {
+    const int t = (int)threadIdx.x;
+    const CkptEntry e = ((const CkptEntry *)blk)[blockIdx.x];
+    const int s = e.scene, N = e.size, tw = e.trk_words;
+    const int64_t lo = d.offsets[s];
+    const CkptLayout L = scene_checkpoint_layout(N, tw, e.has_paths);
+    const uint8_t *in = blk + e.at;
+    // K4's counters of the last step, before the records are replaced: a row that was done and runs again counts, a row that ran and is done no longer does
+    const restart_u32 *rec_in = (const restart_u32 *)(in + L.off[CK_REC]);
+    constexpr int RW = CKPT_REC_BYTES / 4;
+    constexpr uint32_t DONE = FLAG_AT_GOAL | FLAG_COLLISION | FLAG_TIMEOUT;
+    for (int i = t; i < N; i += CKPT_T) {
+        const bool was = (d.rec[lo + i].flags & DONE) != 0, is = (rec_in[i * RW + 9] & DONE) != 0;
+        if (was != is) atomicAdd(&d.done_count[((lo + i) & 255) * 32], was ? 1 : -1);
+    }
+    __syncthreads();
+    scene_restart_pieces(d.rec + lo, in + L.off[CK_REC], (int64_t)N * (CKPT_REC_BYTES / 16), t);
+    ckpt_words(d.heading + 3 * lo, in + L.off[CK_HEADING], 6 * (int64_t)N, t);
+    ckpt_words(d.heading_keep + 3 * lo, in + L.off[CK_HEADING_KEEP], 6 * (int64_t)N, t);
+    ckpt_words(d.vpref_ext + 3 * lo, in + L.off[CK_VPREF_EXT], 6 * (int64_t)N, t);
+    ckpt_words(d.total_dist + lo, in + L.off[CK_TOTAL_DIST], 2 * (int64_t)N, t);
+    ckpt_words(d.step_num + lo, in + L.off[CK_STEP_NUM], N, t);
+    ckpt_words(d.status + lo, in + L.off[CK_STATUS], N, t);
+    const int32_t *perm = (const int32_t *)(in + L.off[CK_PERM]);
+    const restart_u32 *mode = (const restart_u32 *)(in + L.off[CK_VPREF_MODE]);
+    for (int i = t; i < N; i += CKPT_T) { d.aperm[lo + i] = (int32_t)lo + perm[i]; d.vpref_mode[lo + i] = (uint8_t)mode[i]; }
+    if (tw > 0) {
+        ckpt_words(d.trk_nbr0 + lo, in + L.off[CK_TRK_NBR0], 2 * (int64_t)N, t);
+        ckpt_words(d.trk_st + lo * tw, in + L.off[CK_TRACK], (int64_t)N * tw, t);
+    }
+    if (e.has_paths && d.rem) {
+        ckpt_words(d.rem + lo, in + L.off[CK_REM], N, t);
+        ckpt_words(d.now_goal + 3 * lo, in + L.off[CK_NOW_GOAL], 6 * (int64_t)N, t);
+    }
+    if (t == 0) {
+        const int32_t *head = (const int32_t *)in + CKPT_HEAD_STEPS;
+        d.steps[s] = head[0]; d.live[s * SCENE_LINE] = head[1]; d.prev[s] = head[2];
+    }
+}
+
 }  // namespace sca

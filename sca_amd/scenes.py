@@ -31,6 +31,7 @@ import numpy as np
 
 from . import metrics
 from . import solver as S
+from . import env as _env
 from .env import _ATTRS, _FlatAgents, _bind, _obstacle_arrays, _planner_triple
 
 
@@ -58,7 +59,23 @@ class _SceneLog:
         return int(rows['logged'][self._view.scene]), int(rows['dropped'][self._view.scene])
 
     def history(self, first_row=0, nrows=None, agent_begin=0, agent_count=None):
-        return self._view._batch.solver.scene_history(self._view.scene, first_row, nrows, agent_begin, agent_count)
+        """(a scene resumed from a SceneCheckpoint: the rows of the steps before the save are the checkpoint's, stitched in front of the
+        device's -- the library restores the step count and goes on writing behind them)"""
+        head = self._view._log_head
+        sol, s = self._view._batch.solver, self._view.scene
+        if head is None:
+            return sol.scene_history(s, first_row, nrows, agent_begin, agent_count)
+        k = len(head['pos'])
+        if nrows is None:
+            nrows = self.history_rows()[0] - first_row
+        if agent_count is None:
+            agent_count = len(self._view.agents) - agent_begin
+        end, cols = first_row + nrows, slice(agent_begin, agent_begin + agent_count)
+        saved = {key: v[first_row:min(k, end), cols] for key, v in head.items()}
+        if end <= k:
+            return saved
+        live = sol.scene_history(s, max(first_row, k), end - max(first_row, k), agent_begin, agent_count)
+        return {key: np.concatenate([saved[key], live[key]]) for key in live}
 
 
 class _Assigned:
@@ -81,6 +98,7 @@ class SceneEnv:
         self.kdTree = _SceneKdTree(self)
         self._occupy(agents, hi)
         self._time_cum = [0.0]
+        self._log_head = None                                       # the log rows a SceneCheckpoint brought (restart({s: checkpoint}))
         self._path_assigned = _Assigned(self)
         self.device_tracker = batch.device_tracker
         self.solver = _SceneLog(self)                               # (metrics.trajectories / write_episode_log: needs SceneBatch(scene_history=rows))
@@ -130,6 +148,83 @@ class SceneEnv:
 
     def _neighbors_of(self, i):
         return self._batch._neighbors(self._lo + i, self.agents, self.obstacles, self._lo, self._obs_lo)
+
+
+_POLICIES = {c.policy_id: c for c in (_env.SCAPolicy, _env.RVO3DPolicy, _env.SRVO3DPolicy, _env.ORCA3DPolicy, _env.ORCA3DPolicyOfficial,
+                                      _env.RVO3dDubinsPolicy)}
+_AGENT_SCALARS = ('radius', 'pref_speed', 'turning_radius', 'maxNeighbors', 'neighborDist', 'timeStep', 'timeHorizon', 'maxSpeed', 'dt_nominal',
+                  'min_heading_change', 'max_heading_change', 'max_run_dist', 'group')
+
+
+class SceneCheckpoint:
+    """A running episode out of its slot (SceneBatch.checkpoint(s)): the episode's DEFINITION -- its agents and obstacles, as plain arrays
+    an Agent / Obstacle is rebuilt from through its constructor --, the library's blob of the scene's mutable state (sca_save_scenes),
+    `steps`, and, when the batch keeps a log per scene, the log rows so far.  SceneBatch.restart({s: checkpoint}) resumes it in any slot
+    of any batch that could take the episode; write(path) / read(path) keep it as one .npz of plain arrays (no pickle)."""
+
+    def __init__(self, definition, blob, steps, log=None, time_cum=(0.0,)):
+        self.definition = {k: np.asarray(v) for k, v in definition.items()}
+        self.blob = np.ascontiguousarray(blob, np.uint8)
+        self.steps = int(steps)
+        self.log = None if log is None else {k: np.asarray(v) for k, v in log.items()}
+        self.time_cum = [float(x) for x in time_cum]
+
+    def __len__(self):
+        return len(self.definition['policy_id'])
+
+    @staticmethod
+    def define(agents, path_set, obstacles):
+        """the arrays an episode's agents and obstacles are rebuilt from; path_set: the agents' waypoint lists as they were handed to the
+        device (the agents' own are shortened to what is left)"""
+        d = dict(start=np.array([a.initial_pos for a in agents], np.float64).reshape(len(agents), 6),
+                 goal=np.array([a.goal_pos for a in agents], np.float64).reshape(len(agents), 6),
+                 policy_id=np.array([a.policy.policy_id for a in agents], np.uint8),
+                 pitchlims=np.array([a.pitchlims for a in agents], np.float64).reshape(len(agents), 2),
+                 path_off=np.concatenate([[0], np.cumsum([len(p) for p in path_set])]).astype(np.int32),
+                 path_pts=np.array([w[:3] for p in path_set for w in p], np.float64).reshape(-1, 3))
+        for k in _AGENT_SCALARS:
+            d[k] = np.array([getattr(a, k) for a in agents], np.float64)
+        shapes = sorted({o.shape for o in obstacles})
+        if any(sh != 'sphere' for sh in shapes):
+            raise ValueError(f'SceneCheckpoint: obstacles of shape {shapes} (only spheres are kept as arrays)')
+        d['obs_pos'] = np.array([o.pos_global_frame for o in obstacles], np.float64).reshape(len(obstacles), 3)
+        d['obs_radius'] = np.array([o.radius for o in obstacles], np.float64)
+        return d
+
+    def agents(self):
+        """the episode's agents, fresh through Agent's constructor: at their start, carrying their lists as they were handed to the device"""
+        d = self.definition
+        out = []
+        for i in range(len(self)):
+            a = _env.Agent(start_pos=list(d['start'][i]), goal_pos=list(d['goal'][i]), vel=[0.0, 0.0, 0.0], radius=float(d['radius'][i]),
+                           pref_speed=float(d['pref_speed'][i]), policy=_POLICIES[int(d['policy_id'][i])], id=i)
+            for k in _AGENT_SCALARS:
+                setattr(a, k, int(d[k][i]) if k in ('maxNeighbors', 'group') else float(d[k][i]))
+            a.pitchlims = [float(d['pitchlims'][i][0]), float(d['pitchlims'][i][1])]
+            a._path = [list(map(float, w)) for w in d['path_pts'][d['path_off'][i]:d['path_off'][i + 1]]]
+            out.append(a)
+        return out
+
+    def obstacles(self):
+        d = self.definition
+        return [_env.Obstacle(list(map(float, p)), dict(shape='sphere', feature=float(r)), id=i) for i, (p, r) in enumerate(zip(d['obs_pos'], d['obs_radius']))]
+
+    def write(self, path):
+        """one .npz of plain arrays"""
+        arrays = {'def_' + k: v for k, v in self.definition.items()}
+        arrays.update(blob=self.blob, steps=np.array(self.steps, np.int64), time_cum=np.array(self.time_cum, np.float64), has_log=np.array(self.log is not None))
+        if self.log is not None:
+            arrays.update({'log_' + k: v for k, v in self.log.items()})
+        with open(path, 'wb') as f:
+            np.savez(f, **arrays)
+        return path
+
+    @classmethod
+    def read(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            definition = {k[4:]: z[k] for k in z.files if k.startswith('def_')}
+            log = {k[4:]: z[k] for k in z.files if k.startswith('log_')} if bool(z['has_log']) else None
+            return cls(definition, z['blob'], int(z['steps']), log, z['time_cum'])
 
 
 class SceneBatch(_FlatAgents):
@@ -188,6 +283,7 @@ class SceneBatch(_FlatAgents):
             if path_slots != 'max':
                 raise ValueError(f"path_slots: None, 'max' or the waypoints a row has room for, got {path_slots!r}")
             path_slots = max([1] + [len(a._path) for agents in scenes for a in agents])
+        self._path_set = None                                       # the lists as last handed to the device, row by row (None: never)
         self.path_slots = 0 if path_slots is None else int(path_slots)     # 0: the lists are one block, and restart() refuses them
         if path_slots is not None and self.path_slots < 1:
             raise ValueError(f'path_slots: a row needs room for at least 1 waypoint, got {path_slots!r}')
@@ -264,6 +360,7 @@ class SceneBatch(_FlatAgents):
         super()._refresh_paths(set(skip) | self._vacant_rows() if self.path_slots else skip)
 
     def _upload_paths(self, lists):
+        self._path_set = [[list(w) for w in p] for p in lists]      # the lists as the device holds them (SceneBatch.checkpoint)
         if not self.path_slots:
             return super()._upload_paths(lists)
         self._check_path_room([(i, p) for i, p in enumerate(lists)], 'agent.path')
@@ -308,6 +405,25 @@ class SceneBatch(_FlatAgents):
                                                      'all_distance')}
         return out
 
+    # ---- a running episode out of its slot, and back into any (sca_save_scenes / sca_load_scenes) ---------------------------------------------
+    def checkpoint(self, s):
+        """SceneCheckpoint of scene s as it stands between two steps: the episode's definition, the library's blob, `steps`, and the log
+        rows so far when the batch keeps a log per scene"""
+        s = int(s)
+        if not 0 <= s < len(self._envs):
+            raise ValueError(f'checkpoint: no scene {s} in a batch of {len(self._envs)}')
+        self._sync_paths()                                          # (an `agent.path = [...]` since the last step is part of the episode)
+        view = self._envs[s]
+        lo = int(self.offsets[s])
+        path_set = [[] for _ in view.agents] if self._path_set is None else self._path_set[lo:lo + len(view.agents)]
+        blob = self.solver.save_scenes([s])[0]
+        steps = int(self.solver.scene_checkpoint_info(blob)['steps'])
+        log = None
+        if self.scene_history:
+            rows, _ = view.solver.history_rows()
+            log = view.solver.history(0, rows)
+        return SceneCheckpoint(SceneCheckpoint.define(view.agents, path_set, view.obstacles), blob, steps, log, view._time_cum)
+
     # ---- a new episode into a slot while the others keep running (sca_restart_scenes) -------------------------------------------------------
     def restart(self, scenes, obstacles=None):
         """{s: agents}: scene s starts over with the new Agent list (numbered 0 .. n - 1; n is the slot's count, or, in a batch built with
@@ -319,8 +435,22 @@ class SceneBatch(_FlatAgents):
         most its obstacle capacity; [] for none) -- bit for bit the MACAEnv of the new episode with that list --; a restarted scene absent
         from it keeps its list.  ValueError before any device call for a list above the slot's capacity, a scene that is not restarted, or
         `obstacles` on a batch without obstacle slots."""
-        items = sorted((int(s), list(agents)) for s, agents in dict(scenes).items())
+        resumed = {int(s): x for s, x in dict(scenes).items() if isinstance(x, SceneCheckpoint)}
+        items = sorted((int(s), x.agents() if isinstance(x, SceneCheckpoint) else list(x)) for s, x in dict(scenes).items())
         new_obs = None if obstacles is None else {int(s): list(o) for s, o in dict(obstacles).items()}
+        for s, ck in resumed.items():                                # a checkpoint brings its episode's obstacles: into an obstacle slot, or
+            own = ck.obstacles()                                     # the scene must meet exactly that set already
+            if new_obs is not None and s in new_obs:
+                continue
+            if self.obstacle_slots:
+                new_obs = dict(new_obs or {})
+                new_obs[s] = own
+            elif 0 <= s < len(self._envs) and not (np.array_equal(_obstacle_arrays(own)[0], _obstacle_arrays(self._envs[s].obstacles)[0]) and
+                                                   np.array_equal(_obstacle_arrays(own)[1], _obstacle_arrays(self._envs[s].obstacles)[1])):
+                raise ValueError(f"restart: scene {s}: the checkpoint's episode meets {len(own)} obstacles of its own, which this batch cannot bring "
+                                 'into the slot (SceneBatch(obstacle_capacities=...))')
+            if ck.log is not None and self.scene_history and len(ck.log['pos']) < min(ck.steps, self.scene_history):
+                raise ValueError(f'restart: scene {s}: the checkpoint holds {len(ck.log["pos"])} log rows of its {ck.steps} steps')
         if new_obs is not None:
             if not self.obstacle_slots:
                 raise ValueError('restart: obstacles for a batch without obstacle slots (SceneBatch(obstacle_capacities=...))')
@@ -365,6 +495,9 @@ class SceneBatch(_FlatAgents):
                     if not self.attribute_slots and _planner_triple(a) != self._planner_of(lo + i):
                         raise ValueError(f"restart: scene {s}, agent {i}: turning_radius / pitchlims differ from the slot's (a slot keeps its planner attributes)")
         self._send_restart(items, new_obs)
+        if resumed:                                                  # the episodes are in their slots: now their state, one call
+            ids = sorted(resumed)
+            self.solver.load_scenes(ids, [resumed[s].blob for s in ids])
         for s, agents in items:
             lo = int(self.offsets[s])
             view = self._envs[s]
@@ -372,13 +505,14 @@ class SceneBatch(_FlatAgents):
                 self.scene_obstacles[s] = view.obstacles = new_obs[s]
             self._flat[lo:lo + len(agents)] = agents                 # (the rows behind keep the agents that carry the slot's attributes)
             view._occupy(agents, lo + len(agents))
-            view._time_cum = [0.0]
+            view._time_cum = list(resumed[s].time_cum) if s in resumed else [0.0]
+            view._log_head = resumed[s].log if s in resumed and self.scene_history else None
             _bind(agents, view)
         self._stale = True                                           # the mirrors (views of the batch's arrays) refresh in place on first use
         self._path_stale = self._paths_on                            # (slot form: the new agents' whole lists, now_goal None, read back on first use)
         self._nbr_cache = None
         self._vpref_cache = None
-        if self.harvest:                                             # what the restart leaves, without a read-back: all of the episode live, no step taken
+        if self.harvest and not resumed:                             # what the restart leaves, without a read-back: all of the episode live, no step taken
             for s, agents in items:
                 self.active[s], self.steps[s] = len(agents), 0
         else:
@@ -420,6 +554,9 @@ class SceneBatch(_FlatAgents):
         at = 0
         for s, agents in items:
             lo, n = int(self.offsets[s]), len(agents)
+            if self._path_set is not None:                           # (the rows behind the episode hold no list)
+                self._path_set[lo:int(self.offsets[s + 1])] = [[list(map(float, w[:3])) for w in a._path] if self.path_slots else [] for a in agents] + \
+                    [[] for _ in range(int(self.offsets[s + 1]) - lo - n)]
             self.goal[lo:lo + n] = goal[at:at + n]                   # (view.goal is a view of these rows)
             self.policy_ids[lo:lo + n] = policy[at:at + n]
             self._ext[lo:lo + n] = [a.policy.needs_external_vpref for a in agents]
@@ -560,7 +697,7 @@ def _harvest_policy_time(view, h):
 
 
 def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=None, max_steps=None, stats=None, history_rows=0, capacities=None,
-                 harvest=False, episode_obstacles=None, obstacle_capacities='max', attributes=False, path_slots=None):
+                 harvest=False, episode_obstacles=None, obstacle_capacities='max', attributes=False, path_slots=None, checkpoint_at=None):
     """Streams a queue of episodes (Agent lists, each numbered 0 .. n - 1) through `slots` scenes of ONE SceneBatch: when a scene finishes,
     its metrics, step count and final state are taken and the slot restarts with the next episode of its size (SceneBatch.restart), while
     the other slots keep running.  Obstacles are one list shared by all episodes (`obstacles`), or -- mutually exclusive with it --
@@ -588,8 +725,16 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
     path_slots=W or 'max' (the longest list in the whole queue, at least 1): the slots take every episode's own waypoint lists
     (SceneBatch(path_slots=W)), so a queue whose drones carry paths streams through one batch; results, on_done order and stats are those
     of the same queue run as one MACAEnv per episode, and every result gains `path_left`, the waypoints left in each agent's list when the
-    episode finished (the agents' own lists are shortened to that).  ValueError up front for a list longer than W."""
-    episodes = [list(e) for e in episodes]
+    episode finished (the agents' own lists are shortened to that).  ValueError up front for a list longer than W.
+    A queue entry may be a SceneCheckpoint instead of an Agent list: the episode then enters its slot where the checkpoint left it
+    (SceneBatch.restart({s: checkpoint})), and its result is that of the uninterrupted episode; with episode_obstacles its entry may be
+    None (the checkpoint's own obstacles).  checkpoint_at=(batch_step, directory): behind that many batch steps every slot that still
+    holds an episode is written there as a checkpoint (slotSSS_episodeEEEEE.npz) and the run stops; the results of the episodes that have
+    not finished are None, and `stats` receives `checkpoints` ({slot: (episode, path)}) and `pending` (the episodes that never started) --
+    a second run_episodes over the checkpoints in slot order plus the pending episodes finishes the queue as one run would have."""
+    import os
+    cks = {i: e for i, e in enumerate(episodes) if isinstance(e, SceneCheckpoint)}
+    episodes = [e.agents() if isinstance(e, SceneCheckpoint) else list(e) for e in episodes]
     if isinstance(path_slots, str):
         if path_slots != 'max':
             raise ValueError(f"run_episodes: path_slots is None, 'max' or the waypoints a row has room for, got {path_slots!r}")
@@ -604,7 +749,7 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
     if episode_obstacles is not None:
         if len(obstacles):
             raise ValueError('run_episodes: either `obstacles` (one list shared by all episodes) or `episode_obstacles` (one list per episode)')
-        episode_obstacles = [list(o) for o in episode_obstacles]
+        episode_obstacles = [cks[i].obstacles() if o is None and i in cks else list(o) for i, o in enumerate(episode_obstacles)]
         if len(episode_obstacles) != len(episodes):
             raise ValueError(f'run_episodes: {len(episode_obstacles)} obstacle lists for {len(episodes)} episodes')
         osizes = [len(o) for o in episode_obstacles]
@@ -632,7 +777,11 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
                        scene_obstacles=None if ocaps is None else [episode_obstacles[i] for i in holding], obstacle_capacities=ocaps)
     results = [None] * len(episodes)
     batch_steps = served = 0
+    written = None
     try:
+        if any(i in cks for i in holding):                            # the slots that start with a checkpoint: its state into the episode it was built with
+            batch.restart({s: cks[i] for s, i in enumerate(holding) if i in cks},
+                          obstacles=None if ocaps is None else {s: episode_obstacles[i] for s, i in enumerate(holding) if i in cks})
         while any(h is not None for h in holding) and (max_steps is None or batch_steps < max_steps):
             served += int(batch.active.sum())
             batch.step()
@@ -671,13 +820,22 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
                     k = next_episode(sizes[i], left) if capacities is None else next_fitting(caps[s], left)
                 holding[s] = None if k is None else pending.pop(k)
                 if holding[s] is not None:
-                    refill[s] = episodes[holding[s]]
+                    refill[s] = cks.get(holding[s], episodes[holding[s]])
                     if ocaps is not None:
                         refill_obs[s] = episode_obstacles[holding[s]]
             if refill:
                 batch.restart(refill, obstacles=refill_obs if ocaps is not None else None)
+            if checkpoint_at is not None and batch_steps == int(checkpoint_at[0]):
+                os.makedirs(checkpoint_at[1], exist_ok=True)
+                written = {}
+                for s, i in enumerate(holding):
+                    if i is not None:
+                        written[s] = (i, batch.checkpoint(s).write(os.path.join(checkpoint_at[1], 'slot%03d_episode%05d.npz' % (s, i))))
+                break
     finally:
         batch.close()
+    if stats is not None and written is not None:
+        stats.update(checkpoints=written, pending=list(pending))
     if stats is not None:
         stats.update(batch_steps=batch_steps, agent_steps=served, live_fraction=served / max(1, batch_steps * batch_agents))
     return results

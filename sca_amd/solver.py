@@ -450,6 +450,43 @@ class BatchedSolver:
         self._chk(self.L.sca_scene_harvest_collect(self.ctx, _lib.ptr(ids, C.c_int32), C.byref(count)), 'sca_scene_harvest_collect')
         return [int(s) for s in ids[:count.value]]
 
+    # ---- scene checkpoints (sca_save_scenes / sca_load_scenes) ---------------------------------------------------------------
+    def scene_checkpoint_bytes(self, scene):
+        """the size of the blob save_scenes writes for the scene as it stands now"""
+        out = C.c_int64(0)
+        self._chk(self.L.sca_scene_checkpoint_bytes(self.ctx, int(scene), C.byref(out)), 'sca_scene_checkpoint_bytes')
+        return int(out.value)
+
+    def save_scenes(self, ids):
+        """The named scenes' mutable state, one uint8 array each (include/sca_hip.h: what a blob holds).  One launch, one synchronisation."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        inside = [s for s in ids if self.scene_offsets is not None and 0 <= s < self.nscenes]
+        sizes = {int(s): self.scene_checkpoint_bytes(s) for s in set(inside)}        # (an id the library will refuse still gets a buffer)
+        blobs = [np.zeros(sizes.get(int(s), 64), np.uint8) for s in ids]
+        self._save_into(ids, blobs)
+        return blobs
+
+    def _save_into(self, ids, blobs):
+        ptrs = (C.c_void_p * max(1, len(blobs)))(*[b.ctypes.data for b in blobs])
+        nbytes = np.array([b.size for b in blobs] or [0], np.int64)
+        self._chk(self.L.sca_save_scenes(self.ctx, len(ids), _lib.ptr(ids, C.c_int32), ptrs, _lib.ptr(nbytes, C.c_int64)), 'sca_save_scenes')
+
+    def load_scenes(self, ids, blobs):
+        """blobs[e] (bytes or a uint8 array, from save_scenes of any context) into scene ids[e], which a restart has given the blob's episode.
+        Every blob is checked whole before the device sees it; ScaError (SCA_ERR_ARG) names what is wrong."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        blobs = [np.ascontiguousarray(np.frombuffer(b, np.uint8) if isinstance(b, (bytes, bytearray)) else b, np.uint8).reshape(-1) for b in blobs]
+        if len(blobs) != len(ids):
+            raise ValueError('load_scenes: %d ids and %d blobs' % (len(ids), len(blobs)))
+        ptrs = (C.c_void_p * max(1, len(blobs)))(*[b.ctypes.data for b in blobs])
+        nbytes = np.array([b.size for b in blobs] or [0], np.int64)
+        self._chk(self.L.sca_load_scenes(self.ctx, len(ids), _lib.ptr(ids, C.c_int32), ptrs, _lib.ptr(nbytes, C.c_int64)), 'sca_load_scenes')
+
+    def scene_checkpoint_info(self, blob):
+        """The header of a blob as a dict, after the whole check a load makes without a scene; plus `offsets`, the byte offsets of its
+        sections (sca_scene_checkpoint_layout), and `policy`, the rows' policy bytes."""
+        return scene_checkpoint_info(blob)
+
     # ---- SCA's v_pref tracker on the device (scaPolicy.py:264-338) ---------------------------------------
     def device_tracker_enable(self, goal_heading, turning_radius=1.5, pitchlims=(-math.pi / 4, math.pi / 4), in_pass=True):
         """From now on the SCA / RVO3D+Dubins agents take v_pref from the device tracker: inside every policy pass
@@ -723,6 +760,29 @@ class BatchedSolver:
 
     def comm_destroy(self):
         self._chk(self.L.sca_comm_destroy(self.ctx), 'sca_comm_destroy')
+
+
+def scene_checkpoint_layout(size, trk_words, has_paths):
+    """(offsets [14] int64, total bytes) of a scene checkpoint (sca_scene_checkpoint_layout); pure, no device"""
+    off = np.zeros(_lib.CHECKPOINT_SECTIONS, np.int64)
+    total = C.c_int64(0)
+    rc = _lib.lib().sca_scene_checkpoint_layout(int(size), int(trk_words), int(has_paths), _lib.ptr(off, C.c_int64), C.byref(total))
+    if rc != 0:
+        raise ScaError('sca_scene_checkpoint_layout: bad argument (rc=%d)' % rc)
+    return off, int(total.value)
+
+
+def scene_checkpoint_info(blob):
+    """see BatchedSolver.scene_checkpoint_info; pure, no device"""
+    b = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray)) else blob, np.uint8).reshape(-1)
+    info = _lib.SceneCheckpointInfo()
+    rc = _lib.lib().sca_scene_checkpoint_info(C.c_void_p(b.ctypes.data), b.size, C.byref(info), C.sizeof(info))
+    if rc != 0:
+        raise ScaError('sca_scene_checkpoint_info: not a valid scene checkpoint (rc=%d)' % rc)
+    out = {k: int(getattr(info, k)) for k, _ in info._fields_ if k not in ('struct_bytes', 'reserved')}
+    out['offsets'], _ = scene_checkpoint_layout(out['size'], out['trk_words'], out['has_paths'])
+    out['policy'] = b[out['offsets'][0]:out['offsets'][0] + out['size']].copy()
+    return out
 
 
 def paths_csr(paths):
