@@ -31,6 +31,10 @@ one metrics row per scene -- what a loop over the reference's run_example/run_*.
     python examples/run_scenes.py --seeds 8 --slots 16 --resume ckpt                   # running episode is written as a checkpoint (scenes.SceneCheckpoint)
                                                        # and the run stops; the second run resumes them in their slots and
                                                        # streams the rest of the queue -- together the rows of one run
+    python examples/run_scenes.py --clearance --margin 0.1            # ... and how close the drones came: every row gains the smallest
+                                                       # agent-agent and agent-obstacle clearance (distance - radius sum) and the drones that
+                                                       # came within the margin, kept on the device with the step (sca_scene_clearance_enable);
+                                                       # with or without --slots
 """
 import argparse
 import json
@@ -105,6 +109,9 @@ def main():
     ap.add_argument('--save-dir', default=None, help='where --save-at writes the checkpoints and queue.json')
     ap.add_argument('--resume', default=None, help='with --slots and the arguments of the run that saved: resume the checkpoints of this directory in '
                                                    'their slots and stream the rest of the queue')
+    ap.add_argument('--clearance', action='store_true', help='add MinClearance, MinObstacleClearance and the near-miss count to every row '
+                                                             '(SceneBatch(clearance=True) / run_episodes(clearance=True))')
+    ap.add_argument('--margin', type=float, default=0.0, help='with --clearance: a drone whose smallest clearance is at most this many metres is a near miss')
     ap.add_argument('--log-dir', default=None, help='write one folder per episode here: env_cfg.json + trajs.npz (the first --max-steps steps of each)')
     args = ap.parse_args()
     if args.map and not (args.slots and args.obstacles):
@@ -115,6 +122,8 @@ def main():
         ap.error('--harvest is about the streamed queue: give --slots')
     if (args.save_at or args.save_dir or args.resume) and not args.slots:
         ap.error('--save-at / --save-dir / --resume are about the streamed queue: give --slots')
+    if args.margin and not args.clearance:
+        ap.error('--margin is about --clearance')
     if bool(args.save_at) != bool(args.save_dir):
         ap.error('--save-at STEP and --save-dir DIR go together')
     sweep_name, sweep_values = None, [None]
@@ -168,6 +177,11 @@ def main():
         for k, agents in enumerate(scenes):
             add_waypoints(agents, args.waypoints, k)
 
+    def closest(rec):
+        """the clearance columns of a printed row"""
+        c = metrics.clearance_metrics(rec, args.margin)
+        return '  MinClearance %.5f  MinObstacleClearance %.5f  NearMisses %d' % (c['MinClearance'], c['MinObstacleClearance'], len(c['NearMisses']))
+
     def folder(k):
         return os.path.join(args.log_dir, '%03d_%s_%s' % (k, names[k][0], names[k][1].replace(' ', '_')))
 
@@ -185,7 +199,8 @@ def main():
             r = dict(r, episode=order[r['episode']])
             pname, what = names[r['episode']]
             print('%-10s %-*s slot %3d steps %5d  ' % (pname, 40 if sweep_name else 20, what, r['slot'], r['steps']) +
-                  '  '.join('%s %.4g' % (k, r['metrics'][k]) for k in ('SuccessRate', 'ExtraTime', 'ExtraDistance', 'AverageSpeed')), flush=True)
+                  '  '.join('%s %.4g' % (k, r['metrics'][k]) for k in ('SuccessRate', 'ExtraTime', 'ExtraDistance', 'AverageSpeed')) +
+                  (closest(r['clearance']) if args.clearance else ''), flush=True)
             if args.log_dir:
                 metrics.write_log_files(folder(r['episode']), scenes[r['episode']], r['trajectories'], r['info'], xlsx=False)
                 if r['rows_dropped']:
@@ -193,7 +208,7 @@ def main():
         run_episodes(queue, args.slots, device_tracker=True, on_done=row, max_steps=args.max_steps, stats=stats,
                      history_rows=args.max_steps if args.log_dir else 0, capacities=capacities, harvest=args.harvest,
                      episode_obstacles=queue_obstacles if args.obstacles else None, attributes=bool(sweep_name),
-                     path_slots=args.waypoints or None, checkpoint_at=(args.save_at, args.save_dir) if args.save_at else None)
+                     path_slots=args.waypoints or None, checkpoint_at=(args.save_at, args.save_dir) if args.save_at else None, clearance=args.clearance)
         if 'checkpoints' in stats:
             with open(os.path.join(args.save_dir, 'queue.json'), 'w') as f:
                 json.dump(dict(batch_step=args.save_at, checkpoints=[[s, order[i], os.path.basename(path)] for s, (i, path) in sorted(stats['checkpoints'].items())],
@@ -206,8 +221,8 @@ def main():
               (' (%d waypoints per drone, the lists in slot form)' % args.waypoints if args.waypoints else ''))
         return
     rows = args.max_steps if args.log_dir else 0
-    batch = SceneBatch(scenes, scene_obstacles=obstacles, device_tracker=True, scene_history=rows) if args.obstacles else \
-        SceneBatch(scenes, [], device_tracker=True, scene_history=rows)
+    batch = SceneBatch(scenes, scene_obstacles=obstacles, device_tracker=True, scene_history=rows, clearance=args.clearance) if args.obstacles else \
+        SceneBatch(scenes, [], device_tracker=True, scene_history=rows, clearance=args.clearance)
     t0, steps = time.time(), 0
     while steps < args.max_steps and not batch.step():
         steps += 1
@@ -215,7 +230,8 @@ def main():
     for s, (pname, what) in enumerate(names):
         m = metrics.episode_metrics(batch.env(s))
         print('%-10s %-14s steps %5d %s  ' % (pname, what, batch.steps[s], 'done' if batch.done[s] else 'RUNNING') +
-              '  '.join('%s %.4g' % (k, m[k]) for k in ('SuccessRate', 'ExtraTime', 'ExtraDistance', 'AverageSpeed')))
+              '  '.join('%s %.4g' % (k, m[k]) for k in ('SuccessRate', 'ExtraTime', 'ExtraDistance', 'AverageSpeed')) +
+              (closest(batch.env(s).clearance) if args.clearance else ''))
         if args.log_dir:
             metrics.write_episode_log(batch.env(s), folder(s), xlsx=False)
     batch.close()

@@ -562,6 +562,46 @@ int sca_scene_checkpoint_bytes(sca_ctx *ctx, int scene, int64_t *bytes);
 int sca_save_scenes(sca_ctx *ctx, int count, const int32_t *scene_ids /*count*/, void *const *out /*count*/, const int64_t *out_bytes /*count*/);
 int sca_load_scenes(sca_ctx *ctx, int count, const int32_t *scene_ids /*count*/, const void *const *in /*count*/, const int64_t *in_bytes /*count*/);
 
+/* Closest approach per agent, measured WITH THE STEP.  With the feature on a step enqueues one more kernel beside the log's
+ * (k_scene_clearance, a workgroup per scene, in front of the step's last kernel) that keeps, for every occupied agent row, how close the
+ * agent came to another agent of its scene and to an obstacle of its scene, with whom and at which step -- the column a table of
+ * collision-avoidance episodes lacks, without pulling the trajectory log across the link for an all-pairs search on the host.
+ *   the rule   mirrors the env's own collision test (mampenv.py:61-75, dis <= radius sum).  Row a of scene s is updated at every step of
+ *              the scene's own that the scene began with somebody live and that a ENTERED unfinished (none of at-goal / collision /
+ *              timed-out in its entry flags; the step in which it gains a flag still counts).  For every other occupied row b of the
+ *              scene, whatever its flags (finished drones stay where they are and the reference still collides with them),
+ *              c = l3norm(p_a, p_b) - (r_a + r_b): p the positions the step moved to, l3norm the reference's rounded norm (util.py:104),
+ *              the radius sum formed first.  The step's candidate is the smallest c, the lowest b on equal values; it replaces the record
+ *              only if strictly smaller, so the earliest step wins ties.  The same over the scene's obstacles in their set order -- the
+ *              shared set, the scene's own set, or the first `count` rows of its obstacle slot.  Never a partner: rows behind the scene's
+ *              size (vacant), obstacle rows behind a slot's count, anything of another scene.
+ *   the record 32 bytes per agent row.  Partners are scene-local (agent row - the scene's first row; obstacle index within the scene's
+ *              set), `step` is the scene's own step count, 1-based.  An empty half is +inf, -1, 0: what a one-agent scene and a scene
+ *              without obstacles keep.
+ *   contract   a scene's records are bit for bit those of a context holding that episode alone, in every step form (sca_env_step,
+ *              sca_run_steps, sca_policy_pass + sca_env_update, sca_step_host), and no other scene can tell that a scene finished, was
+ *              restarted or has the feature on.  A context without the feature enqueues exactly what it did.
+ *   cost       one dependent dispatch per step plus O(size^2) rounded norms per LIVE scene (about 10^7 at 1024 scenes of 100 agents);
+ *              a pair takes the exact rounding only while it can still beat the row's record.
+ *   sca_scene_clearance_enable  on != 0: allocates n x 32 bytes, every row empty; records cover the steps from then on (enabling again
+ *              starts over).  on == 0 frees.  SCA_ERR_STATE: no scenes, or between a policy pass and its env update.  Whatever clears
+ *              or redefines the scenes (sca_set_agents, sca_set_scenes) drops it, as it drops the log and the harvest.
+ *   sca_get_scene_clearance     the scene's occupied rows, out[size[scene]], one copy and one synchronisation.  struct_bytes =
+ *              sizeof(sca_scene_clearance).  SCA_ERR_STATE: not enabled (or no scenes).  SCA_ERR_ARG: a scene outside 0 .. nscenes-1, a
+ *              NULL out, a wrong struct_bytes.  A finished scene keeps its records until it is restarted.
+ *   restart    every sca_restart_scenes* entry point empties the records of the scenes it names, over their whole capacity, inside its
+ *              one launch.  sca_load_scenes, sca_set_state and a state from the host block leave the records alone: a caller that
+ *              resumes a checkpoint keeps the source's records beside the blob and merges (field by field, the later one only where
+ *              strictly smaller).
+ * Detect the feature by the symbol (sca_version() and the checkpoint blob are unchanged). */
+typedef struct sca_scene_clearance {     /* 32 bytes */
+    double  agent_clear, obs_clear;      /* the smallest c so far; +inf: none */
+    int32_t agent_partner, agent_step;   /* scene-local row of the other agent (-1: none), the scene's step it happened in (0: none) */
+    int32_t obs_partner, obs_step;       /* index within the scene's obstacle set (-1: none), the step */
+} sca_scene_clearance;
+int sca_scene_clearance_enable(sca_ctx *ctx, int on);
+int sca_get_scene_clearance(sca_ctx *ctx, int scene, sca_scene_clearance *out /*size[scene]*/, int32_t struct_bytes);
+
 /* the hot path ----------------------------------------------------------------------------------- */
 int sca_policy_pass(sca_ctx *ctx, int neighbor_mode);
 int sca_get_actions(sca_ctx *ctx, float *action /*n*7*/);

@@ -64,6 +64,16 @@ class SceneCheckpointInfo(C.Structure):
                 ('live', C.c_int32), ('prev', C.c_int32), ('total_bytes', C.c_int64), ('checksum', C.c_uint64)]
 
 
+class SceneClearance(C.Structure):
+    """sca_scene_clearance: an agent row's closest approach so far (sca_get_scene_clearance), 32 bytes"""
+    _fields_ = [('agent_clear', C.c_double), ('obs_clear', C.c_double), ('agent_partner', C.c_int32), ('agent_step', C.c_int32),
+                ('obs_partner', C.c_int32), ('obs_step', C.c_int32)]
+
+
+CLEARANCE_DTYPE = np.dtype([('agent_clear', np.float64), ('obs_clear', np.float64), ('agent_partner', np.int32), ('agent_step', np.int32),
+                            ('obs_partner', np.int32), ('obs_step', np.int32)])
+
+
 CHECKPOINT_SECTIONS = 14                                          # sca_scene_checkpoint_layout's offsets
 
 
@@ -111,6 +121,8 @@ SIGNATURES = {
     'sca_scene_checkpoint_bytes': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]),
     'sca_save_scenes': (C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     'sca_load_scenes': (C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    'sca_scene_clearance_enable': (C.c_int, [C.c_void_p, C.c_int]),
+    'sca_get_scene_clearance': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SceneClearance), C.c_int32]),
     'sca_set_path_state': (C.c_int, [C.c_void_p, ip, dp]),
     'sca_policy_pass': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_get_actions': (C.c_int, [C.c_void_p, fp]),

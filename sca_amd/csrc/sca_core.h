@@ -155,6 +155,10 @@ SCA_HD double l3norm(V3 a, V3 b, double *k_out = nullptr) {
     s = s + dz * dz;
     return round5_py(sqrt(s), k_out);
 }
+// ... on plain coordinates, as a function object: the norm clearance_pair (sca_scenes.h) takes as a parameter
+struct L3Norm {
+    SCA_HD double operator()(double ax, double ay, double az, double bx, double by, double bz) const { return l3norm(v3(ax, ay, az), v3(bx, by, bz)); }
+};
 // util.py:140 distance
 SCA_HD double distance5(V3 a, V3 b) {
     double dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;

@@ -325,13 +325,14 @@ struct sca_ctx {
         int32_t hv_batch_step = 0;      // env updates enqueued since the harvest was enabled
         uint8_t *ck_host = nullptr;     // sca_save_scenes' / sca_load_scenes' page-locked block (CkptEntry table + blobs, sca_scenes.h), allocated on first use
         size_t ck_bytes = 0;            // ... and its size: it grows when a call needs more
+        sca_scene_clearance *clear = nullptr;   // [n] the closest-approach records (sca_scene_clearance_enable), null: off -- a step then enqueues nothing for them
         void release() {                // the device and page-locked allocations, behind a synchronised stream; the flags and host vectors stay
-            for (void *p : {(void *)v.scene_of, (void *)v.offsets, (void *)counters, (void *)v.heading_keep, (void *)ov.oroot, (void *)log.rows, (void *)size}) if (p) (void)hipFree(p);
+            for (void *p : {(void *)v.scene_of, (void *)v.offsets, (void *)counters, (void *)v.heading_keep, (void *)ov.oroot, (void *)log.rows, (void *)size, (void *)clear}) if (p) (void)hipFree(p);
             if (rs_host) (void)hipHostFree(rs_host);
             if (hv_host) (void)hipHostFree(hv_host);
             if (ck_host) (void)hipHostFree(ck_host);
             ck_host = nullptr; ck_bytes = 0;
-            v = SceneView{}; counters = nullptr; size = nullptr; ov = SceneObsView{}; rs_host = nullptr; rs_bytes = 0; log = SceneLogView{}; hv_host = nullptr;
+            v = SceneView{}; counters = nullptr; size = nullptr; ov = SceneObsView{}; rs_host = nullptr; rs_bytes = 0; log = SceneLogView{}; hv_host = nullptr; clear = nullptr;
         }
     } scenes;
     std::vector<uint8_t> h_policy;      // [n] the agents' policies as they stand (sca_set_agents, sca_restart_scenes)
@@ -1462,6 +1463,14 @@ static int scene_harvest_drop(sca_ctx *c) {
     c->scenes.hv_host = nullptr;
     return 0;
 }
+// ... and the closest-approach records: one per agent row of the scenes as they were cut
+static int scene_clearance_drop(sca_ctx *c) {
+    if (!c->scenes.clear) return 0;
+    CHK(c, hipStreamSynchronize(c->stream));
+    (void)hipFree(c->scenes.clear);
+    c->scenes.clear = nullptr;
+    return 0;
+}
 // the `fresh` words of the harvest, all of them or those of the named scenes.  Host stores into the block: only behind a synchronised
 // stream, when no k_scene_harvest is in flight.
 static void scene_harvest_clear_fresh(sca_ctx *c, int count, const int32_t *scene_ids) {
@@ -1475,6 +1484,7 @@ static int scenes_clear(sca_ctx *c) {
     if (int r = scene_obstacles_drop(c)) return r;
     if (int r = scene_log_drop(c)) return r;
     if (int r = scene_harvest_drop(c)) return r;
+    if (int r = scene_clearance_drop(c)) return r;
     CHK(c, hipStreamSynchronize(c->stream));
     c->scenes.on = false;
     c->scenes.h_off.clear();
@@ -1959,6 +1969,7 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
     d.policy = c->d.policy; d.zaxis = c->d.zaxis; d.vpref_mode = c->d.vpref_mode; d.nbr_valid = c->d.nbr_valid;
     d.aperm = c->d.aperm; d.nbr_n = c->d.nbr_n; d.near_n = c->d.near_n; d.done_count = c->d.done_count;
     d.offsets = c->scenes.v.offsets; d.live = c->scenes.v.live; d.prev = c->scenes.v.prev; d.steps = c->scenes.v.steps;
+    d.clear = c->scenes.clear;                                         // (null while the feature is off: the kernel skips the rows' records)
     if (c->trk_on) {
         static_assert(sizeof(sca_dubins::AgentTrack) % 4 == 0, "k_scene_restart copies the tracker record as 4-byte words");
         d.trk_nbr0 = c->trk.nbr0; d.trk_goal_heading = c->trk_goal_heading;
@@ -2894,6 +2905,7 @@ static int launch_integrate(sca_ctx *c) {
 static int launch_collide_finish(sca_ctx *c, bool timed) {
     DeviceView &d = c->d;
     const int cnt = d.shard_count;
+    const bool passed = c->scenes.on && c->scenes.begun;                   // a policy pass opened this step: coll_new describes it (k_scene_clearance)
     double agent_reach, obs_reach;
     collide_reach(c, agent_reach, obs_reach);
     if (!c->near_valid) CHK(c, hipMemsetAsync(d.done_count, 0, sizeof(int32_t) * 256 * 32, c->stream));   // no policy pass before
@@ -2910,6 +2922,12 @@ static int launch_collide_finish(sca_ctx *c, bool timed) {
     c->near_valid = false;
     if (c->scenes.on && c->scenes.log.rows)                                // the scene log's row of this step: behind k_scene_begin, in front of the step's last kernel
         hipLaunchKernelGGL(k_scene_log, dim3((unsigned)((4 * (int64_t)d.n + SCENE_LOG_T - 1) / SCENE_LOG_T)), dim3(SCENE_LOG_T), 0, c->stream, d, c->scenes.v, c->scenes.log);
+    if (c->scenes.on && c->scenes.clear) {                                 // the closest approach of this step: beside the log's row, on the same records
+        const int T = std::min(256, (c->scenes.largest + 63) / 64 * 64);  // a lane per agent row of the largest scene, whole wavefronts, at most 256
+        hipLaunchKernelGGL(k_scene_clearance, dim3(c->scenes.v.nscenes), dim3(T), (size_t)clearance_lds_bytes(c->scenes.largest), c->stream, d, c->scenes.v,
+                           (const int32_t *)c->scenes.size, c->scenes.clear, c->scenes.obs_on ? c->scenes.ov.oroot : (const int32_t *)nullptr, c->scenes.obs_on ? 0 : d.m,
+                           c->scenes.largest, passed ? (const uint32_t *)d.coll_new : (const uint32_t *)nullptr);
+    }
     const dim3 k4grid((cnt + K4_WAVES * K4_APW - 1) / (K4_WAVES * K4_APW));
     // (the event that rides on the step's last kernel, if sca_run_steps asked for one: the next pass's fork)
     const bool others = c->part_on || cnt < d.n;
@@ -3801,6 +3819,43 @@ int sca_get_scene_history(sca_ctx *c, int scene, int first_row, int nrows, int a
             if (heading) { heading[3 * i] = h.a; heading[3 * i + 1] = h.b; heading[3 * i + 2] = h.g; }
             if (vel) { vel[3 * i] = h.vx; vel[3 * i + 1] = h.vy; vel[3 * i + 2] = h.vz; }
         }
+    return 0;
+}
+
+// ---- closest approach per agent (include/sca_hip.h; the rule is sca_scenes.h's, the kernel is k_scene_clearance, enqueued by
+// launch_collide_finish) -----------------------------------------------------------------------------------------------------------------------
+static int scene_clearance_refuse(sca_ctx *c, const char *who, ClearFault f) {
+    switch (f) {
+    case CLEAR_OK: return 0;
+    case CLEAR_NO_SCENES: c->err = std::string(who) + ": no scenes -- sca_set_scenes first"; break;
+    case CLEAR_MID_STEP: c->err = std::string(who) + ": between a policy pass and its env update"; break;
+    case CLEAR_OFF: c->err = std::string(who) + ": sca_scene_clearance_enable first"; break;
+    case CLEAR_BAD_SCENE: c->err = std::string(who) + ": scene must be 0 .. " + std::to_string(c->scenes.v.nscenes - 1); break;
+    case CLEAR_NO_OUT: c->err = std::string(who) + ": out is NULL"; break;
+    default: c->err = std::string(who) + ": struct_bytes must be sizeof(sca_scene_clearance) = " + std::to_string(sizeof(sca_scene_clearance));
+    }
+    return scene_clearance_error_code(f);
+}
+int sca_scene_clearance_enable(sca_ctx *c, int on) {
+    API_ENTER(c);
+    const int B = c->scenes.on ? c->scenes.v.nscenes : 0;
+    if (int r = scene_clearance_refuse(c, "sca_scene_clearance_enable", scene_clearance_check(false, B, c->scenes.begun, c->scenes.clear != nullptr, 0, true, 0))) return r;
+    if (!on) return scene_clearance_drop(c);
+    sca_scene_clearance *rec = nullptr;
+    CHK(c, hipMalloc((void **)&rec, sizeof(sca_scene_clearance) * (size_t)c->n));     // (before the old records go: a refused call changes nothing)
+    const std::vector<sca_scene_clearance> empty((size_t)c->n, scene_clearance_empty());
+    if (hipMemcpyAsync(rec, empty.data(), sizeof(sca_scene_clearance) * (size_t)c->n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipFree(rec); c->err = "sca_scene_clearance_enable: the upload of the empty records failed"; return SCA_ERR_HIP; }
+    if (int r = scene_clearance_drop(c)) { (void)hipFree(rec); return r; }
+    c->scenes.clear = rec;
+    return 0;
+}
+int sca_get_scene_clearance(sca_ctx *c, int scene, sca_scene_clearance *out, int32_t struct_bytes) {
+    API_ENTER(c);
+    const int B = c->scenes.on ? c->scenes.v.nscenes : 0;
+    if (int r = scene_clearance_refuse(c, "sca_get_scene_clearance", scene_clearance_check(true, B, c->scenes.begun, c->scenes.clear != nullptr, scene, out != nullptr, struct_bytes))) return r;
+    CHK(c, hipMemcpyAsync(out, c->scenes.clear + c->scenes.h_off[scene], sizeof(sca_scene_clearance) * (size_t)c->scenes.h_size[scene], hipMemcpyDeviceToHost, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 

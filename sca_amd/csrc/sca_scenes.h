@@ -958,4 +958,89 @@ inline int scene_harvest_order(int nscenes, const sca_scene_summary *sum, int32_
     return count;
 }
 
+// ---- closest approach per agent, measured with the step (sca_scene_clearance_enable) -----------------------------------------------------------
+// The rule mirrors the env's own collision test (mampenv.py:61-75: dis = l3norm(p_a, p_b), collision where dis <= r_a + r_b).  Agent row a
+// of a scene is updated at every step of the scene's own that the scene began with somebody live and that a ENTERED unfinished (none of
+// at-goal / collision / timed-out in its entry flags -- the step in which it gains one still counts).  For every other occupied row b,
+// whatever its flags (a finished drone stays where it is and the reference still collides with it), c = l3norm(p_a, p_b) - (r_a + r_b):
+// p the positions this step moved to, l3norm the reference's rounded norm (util.py:104; sca_core.h's, the exact one), the radius sum formed
+// first, then subtracted.  The step's candidate is the smallest c, the lowest b on equal values; it replaces the record only where
+// strictly smaller, so the earliest step wins ties.  The same over the scene's obstacles in their set order.  Never a partner: rows behind
+// the scene's size, obstacle rows behind a slot's count, anything of another scene -- the caller passes the scene's occupied rows and its
+// own obstacles, and nothing else.  k_scene_clearance (sca_scenes.hip.h) runs clearance_pair per pair; scene_clearance_step is one step of
+// one scene over plain arrays, for the host (tests/scene_clearance_harness.cpp).  The norm is a parameter -- both pass L3Norm, sca_core.h's
+// l3norm on plain coordinates -- so that this header stays free of the solver's arithmetic and its libm.
+#if defined(__HIPCC__)
+#define SCA_SCENES_HD __host__ __device__ inline
+#else
+#define SCA_SCENES_HD inline
+#endif
+constexpr uint32_t CLEAR_DONE_FLAGS = 7;           // FLAG_AT_GOAL | FLAG_COLLISION | FLAG_TIMEOUT (sca_core.h; sca_scenes.hip.h asserts it)
+static_assert(sizeof(sca_scene_clearance) == 32, "one clearance record is two 16-byte pieces");
+struct ClearPoint { double x, y, z, r; };          // a partner as the kernel stages it in LDS: position and radius, 32 bytes
+SCA_SCENES_HD sca_scene_clearance scene_clearance_empty() {
+    sca_scene_clearance e;
+    e.agent_clear = __builtin_huge_val(); e.obs_clear = __builtin_huge_val();
+    e.agent_partner = -1; e.agent_step = 0; e.obs_partner = -1; e.obs_step = 0;
+    return e;
+}
+// One pair against one half of a record; partners arrive in ascending order, so "strictly smaller" keeps the lowest partner of a step and
+// the earliest step.  The exact rounding (round5_py: a product, an fma, a division) is taken only by a pair that can still beat `clear`:
+// with t = clear + rs + 2e-5, |a - b|^2 > t^2 means l3norm >= |a - b| - 0.5e-5 > clear + rs + 1e-5, far outside what the rounding of t, of
+// its square and of the sum of squares (relative 2^-52 each) can move -- so every skipped pair has c > clear and the stored values are
+// the rule's.  clear == +inf never skips (t^2 = +inf); t <= 0 never skips either.
+template <class Norm>
+SCA_SCENES_HD void clearance_pair(const ClearPoint &a, const ClearPoint &b, int partner, int step, double &clear, int32_t &who, int32_t &when, Norm norm) {
+    const double rs = a.r + b.r;
+    const double dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
+    double s = dx * dx + dy * dy;
+    s = s + dz * dz;                                                   // (l3norm's own sum)
+    const double t = clear + rs + 2e-5;
+    if (t > 0.0 && s > t * t) return;
+    const double c = norm(a.x, a.y, a.z, b.x, b.y, b.z) - rs;
+    if (c < clear) { clear = c; who = partner; when = step; }
+}
+// one step of one scene: pos [size * 3] the moved positions of its occupied rows, radius [size], entry_flags [size] the flags the rows
+// entered the step with, obs_pos [nobs * 3] / obs_radius [nobs] the scene's obstacles in set order, step = steps[s] (1-based), rec [size]
+// updated in place
+template <class Norm>
+SCA_SCENES_HD void scene_clearance_step(int size, const double *pos, const double *radius, const uint32_t *entry_flags, int nobs, const double *obs_pos,
+                                        const double *obs_radius, int step, sca_scene_clearance *rec, Norm norm) {
+    for (int a = 0; a < size; a++) {
+        if (entry_flags[a] & CLEAR_DONE_FLAGS) continue;
+        const ClearPoint pa = {pos[3 * a], pos[3 * a + 1], pos[3 * a + 2], radius[a]};
+        sca_scene_clearance r = rec[a];
+        for (int b = 0; b < size; b++) {
+            if (b == a) continue;
+            const ClearPoint pb = {pos[3 * b], pos[3 * b + 1], pos[3 * b + 2], radius[b]};
+            clearance_pair(pa, pb, b, step, r.agent_clear, r.agent_partner, r.agent_step, norm);
+        }
+        for (int j = 0; j < nobs; j++) {
+            const ClearPoint po = {obs_pos[3 * j], obs_pos[3 * j + 1], obs_pos[3 * j + 2], obs_radius[j]};
+            clearance_pair(pa, po, j, step, r.obs_clear, r.obs_partner, r.obs_step, norm);
+        }
+        rec[a] = r;
+    }
+}
+// sca_scene_clearance_enable / sca_get_scene_clearance
+enum ClearFault {
+    CLEAR_OK = 0,
+    CLEAR_NO_SCENES,        // the context holds no scenes                                                     } SCA_ERR_STATE
+    CLEAR_MID_STEP,         // enable / disable between a policy pass and its env update                       }
+    CLEAR_OFF,              // get: the feature is not enabled                                                 }
+    CLEAR_BAD_SCENE,        // get: a scene outside 0 .. nscenes - 1                                           } SCA_ERR_ARG
+    CLEAR_NO_OUT,           // get: out is NULL                                                                }
+    CLEAR_BAD_STRUCT        // get: struct_bytes is not sizeof(sca_scene_clearance)                            }
+};
+inline ClearFault scene_clearance_check(bool get, int nscenes, bool scene_begun, bool enabled, int scene, bool have_out, int struct_bytes) {
+    if (nscenes <= 0) return CLEAR_NO_SCENES;
+    if (!get) return scene_begun ? CLEAR_MID_STEP : CLEAR_OK;
+    if (!enabled) return CLEAR_OFF;
+    if (scene < 0 || scene >= nscenes) return CLEAR_BAD_SCENE;
+    if (!have_out) return CLEAR_NO_OUT;
+    if (struct_bytes != (int)sizeof(sca_scene_clearance)) return CLEAR_BAD_STRUCT;
+    return CLEAR_OK;
+}
+inline int scene_clearance_error_code(ClearFault f) { return f == CLEAR_OK ? SCA_OK : f <= CLEAR_OFF ? SCA_ERR_STATE : SCA_ERR_ARG; }
+
 }  // namespace sca

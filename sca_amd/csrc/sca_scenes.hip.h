@@ -123,6 +123,7 @@ struct RestartDev {
     restart_u32 *trk_st;            // the AgentTrack records as 4-byte words
     const restart_u32 *trk_init;    // one default-constructed record
     int trk_words;                  // sizeof(AgentTrack) / 4
+    sca_scene_clearance *clear;     // [n] the closest-approach records (sca_scene_clearance_enable), null: off
 };
 constexpr int RESTART_T = 256;
 // rows [lo, lo + ns) of a named scene from the block's rows row0 .. row0 + ns - 1: what a restart writes for a row an agent occupies
@@ -297,6 +298,8 @@ __global__ __launch_bounds__(RESTART_T) void k_scene_restart(RestartDev d, const
     scene_restart_fill(d, blk, L, has, row0, lo, ns, t);
     scene_restart_vacate(d, lo + ns, hi, t);
     if (t == 0) { d.live[s * SCENE_LINE] = ns; d.prev[s] = ns; d.steps[s] = 0; size[s] = ns; }
+    if (d.clear)                                                       // the new episode has met nobody yet: the whole capacity, vacant rows too
+        for (int a = lo + t; a < hi; a += RESTART_T) d.clear[a] = scene_clearance_empty();
     scene_restart_attrs(at, blk, AL, has, row0, lo, ns, t);
     if (has & RESTART_HAS_PATH_SLOTS) scene_restart_paths(p, blk, PL, has, row0, lo, ns, hi, t);
     const int32_t *head = (const int32_t *)(blk + OL.off[RO_HEAD]) + RO_HEAD_WORDS * b;
@@ -417,6 +420,66 @@ __global__ __launch_bounds__(SCENE_LOG_T) void k_scene_log(DeviceView d, SceneVi
     else if (q == 2) { w.x = d.heading[agent * 3 + 1]; w.y = d.heading[agent * 3 + 2]; }
     else __builtin_memcpy(&w, &r->vx, 16);                                         // vx vy vz flags stand in PubRec as they do in HistRow
     reinterpret_cast<scene_log_quarter *>(L.rows + scene_log_index(L.capacity, lo, v.offsets[s + 1] - lo, row, agent - lo))[q] = w;
+}
+
+// ---- closest approach per agent, measured with the step (sca_scene_clearance_enable; the rule and clearance_pair are sca_scenes.h's) ---------
+// Enqueued beside k_scene_log, in front of k_collide_finish_scenes: d.rec_new holds the moved records, prev / steps are final for the step.
+// The flags an agent ENTERED the step with are the moved record's minus one case: the epilogue of this step's policy pass has already put
+// a collision found by the neighbour insertion into the record (action_one, agent.py:84), and K1 sets coll_new[a] for exactly those agents
+// -- unflagged at entry -- and clears it for everybody it skipped.  So an agent entered unfinished where its record has no flag or
+// coll_new[a] is set; coll_new is null for an env update without a policy pass, which changes no flag before this kernel.
+// One workgroup per scene; a scene that had nobody live when the step began returns at
+// once.  The occupied rows' positions and radii are staged in LDS (ClearPoint, 32 bytes a row: at most KD_WAVE_CAP x 32 B = 48 KB; the
+// launch asks for the largest scene's room, not the cap's), the scene's obstacles stream through a tile of CLEAR_OBS_TILE behind them.
+// Every lane owns WHOLE agent rows -- row t, t + T, ... -- and walks all partners in ascending order, every lane of a wavefront reading the
+// same LDS word (a broadcast): the record lives in the lane's registers for the step and goes back as the lane's own two 16-byte vector
+// stores.  No atomics, no reduction across lanes, no order that depends on scheduling.  A scene of more rows than the workgroup has lanes
+// takes several passes and streams its obstacles once per pass.
+// Obstacles: o == null is the shared set (rows 0 .. shared_m - 1 of d.obs, set order); else the scene's own rows of the forest's d.obs,
+// from oroot[s] / 2 (the root record of its tree is 2 x its first row), o[nscenes + s] of them -- a slot's count, never its capacity.
+constexpr int CLEAR_OBS_TILE = 128;
+static_assert(CLEAR_DONE_FLAGS == (FLAG_AT_GOAL | FLAG_COLLISION | FLAG_TIMEOUT), "the flags that finish an agent");
+inline int clearance_lds_bytes(int largest) { return (int)sizeof(ClearPoint) * (largest + CLEAR_OBS_TILE); }
+__global__ __launch_bounds__(256) void k_scene_clearance(DeviceView d, SceneView v, const int32_t *size, sca_scene_clearance *rec, const int32_t *o, int shared_m,
+                                                         int agent_room, const uint32_t *coll_new) {
+    extern __shared__ ClearPoint clear_lds[];
+    const int s = (int)blockIdx.x, t = (int)threadIdx.x, T = (int)blockDim.x;
+    if (v.prev[s] == 0) return;                                        // (uniform over the workgroup)
+    const int lo = v.offsets[s], ns = min(size[s], agent_room), step = v.steps[s];
+    ClearPoint *ag = clear_lds, *ob = clear_lds + agent_room;
+    for (int i = t; i < ns; i += T) {
+        const PubRec *r = d.rec_new + lo + i;
+        ClearPoint p; p.x = r->px; p.y = r->py; p.z = r->pz; p.r = r->radius;
+        ag[i] = p;
+    }
+    const int ocount = o ? o[v.nscenes + s] : shared_m;
+    const ObsRec *obs = d.obs + (o && ocount > 0 ? o[s] >> 1 : 0);
+    __syncthreads();
+    for (int i0 = 0; i0 < ns; i0 += T) {                               // (uniform trip counts: every lane reaches every barrier)
+        const int i = i0 + t;
+        const bool mine = i < ns && (!(d.rec_new[lo + i].flags & CLEAR_DONE_FLAGS) || (coll_new && coll_new[lo + i]));
+        sca_scene_clearance c = scene_clearance_empty();
+        ClearPoint pa = {0.0, 0.0, 0.0, 0.0};
+        if (mine) {
+            c = rec[lo + i];
+            pa = ag[i];
+            for (int b = 0; b < ns; b++)
+                if (b != i) clearance_pair(pa, ag[b], b, step, c.agent_clear, c.agent_partner, c.agent_step, L3Norm{});
+        }
+        for (int j0 = 0; j0 < ocount; j0 += CLEAR_OBS_TILE) {
+            const int nj = min(CLEAR_OBS_TILE, ocount - j0);
+            __syncthreads();                                           // the tile before has been read by everybody
+            for (int j = t; j < nj; j += T) {
+                const ObsRec q = obs[j0 + j];
+                ClearPoint p; p.x = q.px; p.y = q.py; p.z = q.pz; p.r = q.radius;
+                ob[j] = p;
+            }
+            __syncthreads();
+            if (mine)
+                for (int j = 0; j < nj; j++) clearance_pair(pa, ob[j], j0 + j, step, c.obs_clear, c.obs_partner, c.obs_step, L3Norm{});
+        }
+        if (mine) rec[lo + i] = c;
+    }
 }
 
 // ---- finished scenes hand over their result with the step (sca_scene_harvest_enable; the block's layout is sca_scenes.h's) -------------------

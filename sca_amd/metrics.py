@@ -10,6 +10,10 @@
   * `write_episode_log(env, dir)` — `env_cfg.json` + `trajs.npz` (one [rows, 13] array per agent under the reference's
     sheet name `agent<id>`); `trajs.xlsx` as well when openpyxl is importable (it is what the reference writes).
 
+  * `clearance_metrics(view)` / `merge_clearance(before, after)` — how close the drones came (MinClearance, MinObstacleClearance,
+    NearMisses) from the closest-approach records the device keeps with the step (`sca_scene_clearance_enable`; `batch.env(s).clearance`
+    of a SceneBatch(clearance=True)): the column the reference's table lacks, without an all-pairs search over the trajectory log.
+
 AverageCost is the reference's wall time of find_next_action per agent-step (run_sca.py:250): by default the sum of
 `agent.total_time`, which MACAEnv.step maintains (a step's policy wall time shared among the agents it served); a measured
 total can be passed instead.
@@ -82,6 +86,42 @@ def episode_metrics_from_harvest(agents, harvested, total_policy_time_s):
     }
     if steps:
         out['AverageCost'] = 1000 * total_policy_time_s / steps
+    return out
+
+
+def merge_clearance(before, after):
+    """Two closest-approach records of the same agents (structured arrays in sca_scene_clearance's layout), `after` covering later steps
+    than `before` -- a saved episode's record and the record of the slot it was resumed in.  Field by field, `after` wins only where it is
+    strictly smaller: the earlier step keeps a tie, as it does on the device, so the result equals the uninterrupted run's.  Returns a new
+    array."""
+    before, after = np.asarray(before), np.asarray(after)
+    if before.shape != after.shape or before.dtype != after.dtype:
+        raise ValueError('merge_clearance: records of %s %s and %s %s' % (before.shape, before.dtype, after.shape, after.dtype))
+    out = before.copy()
+    for half in ('agent', 'obs'):
+        later = after[half + '_clear'] < before[half + '_clear']
+        for field in ('_clear', '_partner', '_step'):
+            out[half + field][later] = after[half + field][later]
+    return out
+
+
+def clearance_metrics(view, margin=0.0):
+    """How close an episode's drones came, from its closest-approach records: `view` is a scene view of a SceneBatch(clearance=True)
+    (`batch.env(s)`: its `.clearance`) or the structured array itself.  clearance = rounded distance - radius sum, the env's own collision
+    test (mampenv.py:61-75), so a value <= 0 is a touch.  MinClearance with its pair (the agent that holds the record, its partner) and the
+    scene's step; MinObstacleClearance with agent, obstacle (index in the scene's set) and step; on equal values the lowest agent.  An
+    episode of one agent, or without obstacles, has +inf, None, 0 there.  NearMisses: the agents whose smaller clearance is <= margin."""
+    rec = np.asarray(getattr(view, 'clearance', view))
+    out = {'MinClearance': float('inf'), 'MinClearancePair': None, 'MinClearanceStep': 0,
+           'MinObstacleClearance': float('inf'), 'MinObstacleClearanceAgent': None, 'MinObstacleClearanceObstacle': None, 'MinObstacleClearanceStep': 0}
+    if len(rec) and np.isfinite(rec['agent_clear']).any():
+        a = int(np.argmin(rec['agent_clear']))
+        out.update(MinClearance=float(rec['agent_clear'][a]), MinClearancePair=(a, int(rec['agent_partner'][a])), MinClearanceStep=int(rec['agent_step'][a]))
+    if len(rec) and np.isfinite(rec['obs_clear']).any():
+        a = int(np.argmin(rec['obs_clear']))
+        out.update(MinObstacleClearance=float(rec['obs_clear'][a]), MinObstacleClearanceAgent=a, MinObstacleClearanceObstacle=int(rec['obs_partner'][a]),
+                   MinObstacleClearanceStep=int(rec['obs_step'][a]))
+    out['NearMisses'] = [int(i) for i in np.flatnonzero(np.minimum(rec['agent_clear'], rec['obs_clear']) <= margin)]
     return out
 
 

@@ -10,6 +10,8 @@ With `obstacle_capacities` a scene's obstacle range is a capacity too (sca_set_s
 then brings a new episode's own obstacles into the slot, and run_episodes(episode_obstacles=...) streams a queue whose episodes differ in
 their obstacles.  With `path_slots` the waypoint lists (Agent.path) live in slot form -- room for W waypoints per agent row
 (sca_set_path_slots) -- and SceneBatch.restart / run_episodes(path_slots=...) bring every episode's own lists into the slot it takes.
+With `clearance=True` the device keeps every agent's closest approach with the step (sca_scene_clearance_enable): `batch.env(s).clearance`
+is the scene's record, metrics.clearance_metrics(batch.env(s)) the table's missing column -- how close the drones came.
 
     batch = SceneBatch([build_agents(seed) for seed in seeds], obstacles, device_tracker=True)   # each list numbered 0 .. n_s - 1
     while not batch.step():
@@ -99,6 +101,7 @@ class SceneEnv:
         self._occupy(agents, hi)
         self._time_cum = [0.0]
         self._log_head = None                                       # the log rows a SceneCheckpoint brought (restart({s: checkpoint}))
+        self._clear_head = None                                     # ... and the closest-approach records of the steps before its save
         self._path_assigned = _Assigned(self)
         self.device_tracker = batch.device_tracker
         self.solver = _SceneLog(self)                               # (metrics.trajectories / write_episode_log: needs SceneBatch(scene_history=rows))
@@ -134,6 +137,16 @@ class SceneEnv:
     done = property(lambda self: bool(self._batch.done[self.scene]))
     steps = property(lambda self: int(self._batch.steps[self.scene]))
 
+    @property
+    def clearance(self):
+        """The episode's closest-approach records so far (SceneBatch(clearance=True)): one record per agent in sca_scene_clearance's layout
+        (_lib.CLEARANCE_DTYPE), partners and steps in the scene's own terms.  A scene resumed from a SceneCheckpoint: the checkpoint's
+        record merged with the device's (metrics.merge_clearance), which is the uninterrupted episode's."""
+        if not self._batch.clearance:
+            raise RuntimeError('clearance: a SceneBatch(clearance=True) keeps the closest approach per agent; this one was built without')
+        rec = self._batch.solver.scene_clearance(self.scene)
+        return rec if self._clear_head is None else metrics.merge_clearance(self._clear_head, rec)
+
     def _refresh_paths(self):
         self._batch._refresh_paths()
 
@@ -159,15 +172,17 @@ _AGENT_SCALARS = ('radius', 'pref_speed', 'turning_radius', 'maxNeighbors', 'nei
 class SceneCheckpoint:
     """A running episode out of its slot (SceneBatch.checkpoint(s)): the episode's DEFINITION -- its agents and obstacles, as plain arrays
     an Agent / Obstacle is rebuilt from through its constructor --, the library's blob of the scene's mutable state (sca_save_scenes),
-    `steps`, and, when the batch keeps a log per scene, the log rows so far.  SceneBatch.restart({s: checkpoint}) resumes it in any slot
-    of any batch that could take the episode; write(path) / read(path) keep it as one .npz of plain arrays (no pickle)."""
+    `steps`, when the batch keeps a log per scene, the log rows so far, and, when it keeps the closest approach per agent, the record so
+    far.  SceneBatch.restart({s: checkpoint}) resumes it in any slot of any batch that could take the episode; write(path) / read(path)
+    keep it as one .npz of plain arrays (no pickle; a file written without the record still reads)."""
 
-    def __init__(self, definition, blob, steps, log=None, time_cum=(0.0,)):
+    def __init__(self, definition, blob, steps, log=None, time_cum=(0.0,), clearance=None):
         self.definition = {k: np.asarray(v) for k, v in definition.items()}
         self.blob = np.ascontiguousarray(blob, np.uint8)
         self.steps = int(steps)
         self.log = None if log is None else {k: np.asarray(v) for k, v in log.items()}
         self.time_cum = [float(x) for x in time_cum]
+        self.clearance = None if clearance is None else np.array(clearance)
 
     def __len__(self):
         return len(self.definition['policy_id'])
@@ -215,6 +230,8 @@ class SceneCheckpoint:
         arrays.update(blob=self.blob, steps=np.array(self.steps, np.int64), time_cum=np.array(self.time_cum, np.float64), has_log=np.array(self.log is not None))
         if self.log is not None:
             arrays.update({'log_' + k: v for k, v in self.log.items()})
+        if self.clearance is not None:
+            arrays.update(clearance=self.clearance)
         with open(path, 'wb') as f:
             np.savez(f, **arrays)
         return path
@@ -224,13 +241,15 @@ class SceneCheckpoint:
         with np.load(path, allow_pickle=False) as z:
             definition = {k[4:]: z[k] for k in z.files if k.startswith('def_')}
             log = {k[4:]: z[k] for k in z.files if k.startswith('log_')} if bool(z['has_log']) else None
-            return cls(definition, z['blob'], int(z['steps']), log, z['time_cum'])
+            return cls(definition, z['blob'], int(z['steps']), log, z['time_cum'], z['clearance'] if 'clearance' in z.files else None)
 
 
 class SceneBatch(_FlatAgents):
     def __init__(self, scenes, obstacles=(), scene_obstacles=None, neighbor_mode=S.NBR_KDTREE, device_tracker=False, history_capacity=0, scene_history=0, device=0,
-                 capacities=None, harvest=False, obstacle_capacities=None, attribute_slots=False, path_slots=None):
-        """path_slots: W, the waypoints every agent row has room for, or 'max' (the longest list among the initial agents, at least 1);
+                 capacities=None, harvest=False, obstacle_capacities=None, attribute_slots=False, path_slots=None, clearance=False):
+        """clearance: every step also keeps each agent's closest approach to another agent and to an obstacle of its scene
+        (sca_scene_clearance_enable: one more kernel per step, O(size^2) per live scene); env(s).clearance reads a scene's records.
+        path_slots: W, the waypoints every agent row has room for, or 'max' (the longest list among the initial agents, at least 1);
         None: the lists are one block, as a batch always had them.  The lists are then uploaded in SLOT form (sca_set_path_slots) and a
         restarted slot takes the episode's own lists (sca_restart_scenes_paths): restart() accepts agents that carry paths, none longer
         than W, and a later `agent.path = [...]` keeps working through the slot form.
@@ -339,6 +358,9 @@ class SceneBatch(_FlatAgents):
         if self.harvest:
             self.solver.scene_harvest_enable()
             self._harvest = self.solver.scene_harvest()           # views of the block: read behind a step's synchronisation
+        self.clearance = bool(clearance)
+        if self.clearance:                                            # (behind the restart that vacated the spare rows: every row starts empty)
+            self.solver.scene_clearance_enable()
 
     def __len__(self):
         return len(self._envs)
@@ -422,7 +444,8 @@ class SceneBatch(_FlatAgents):
         if self.scene_history:
             rows, _ = view.solver.history_rows()
             log = view.solver.history(0, rows)
-        return SceneCheckpoint(SceneCheckpoint.define(view.agents, path_set, view.obstacles), blob, steps, log, view._time_cum)
+        return SceneCheckpoint(SceneCheckpoint.define(view.agents, path_set, view.obstacles), blob, steps, log, view._time_cum,
+                               view.clearance if self.clearance else None)
 
     # ---- a new episode into a slot while the others keep running (sca_restart_scenes) -------------------------------------------------------
     def restart(self, scenes, obstacles=None):
@@ -507,6 +530,7 @@ class SceneBatch(_FlatAgents):
             view._occupy(agents, lo + len(agents))
             view._time_cum = list(resumed[s].time_cum) if s in resumed else [0.0]
             view._log_head = resumed[s].log if s in resumed and self.scene_history else None
+            view._clear_head = resumed[s].clearance if s in resumed and self.clearance else None      # (the restart emptied the slot's records)
             _bind(agents, view)
         self._stale = True                                           # the mirrors (views of the batch's arrays) refresh in place on first use
         self._path_stale = self._paths_on                            # (slot form: the new agents' whole lists, now_goal None, read back on first use)
@@ -697,7 +721,8 @@ def _harvest_policy_time(view, h):
 
 
 def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=None, max_steps=None, stats=None, history_rows=0, capacities=None,
-                 harvest=False, episode_obstacles=None, obstacle_capacities='max', attributes=False, path_slots=None, checkpoint_at=None):
+                 harvest=False, episode_obstacles=None, obstacle_capacities='max', attributes=False, path_slots=None, checkpoint_at=None,
+                 clearance=False):
     """Streams a queue of episodes (Agent lists, each numbered 0 .. n - 1) through `slots` scenes of ONE SceneBatch: when a scene finishes,
     its metrics, step count and final state are taken and the slot restarts with the next episode of its size (SceneBatch.restart), while
     the other slots keep running.  Obstacles are one list shared by all episodes (`obstacles`), or -- mutually exclusive with it --
@@ -731,7 +756,9 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
     None (the checkpoint's own obstacles).  checkpoint_at=(batch_step, directory): behind that many batch steps every slot that still
     holds an episode is written there as a checkpoint (slotSSS_episodeEEEEE.npz) and the run stops; the results of the episodes that have
     not finished are None, and `stats` receives `checkpoints` ({slot: (episode, path)}) and `pending` (the episodes that never started) --
-    a second run_episodes over the checkpoints in slot order plus the pending episodes finishes the queue as one run would have."""
+    a second run_episodes over the checkpoints in slot order plus the pending episodes finishes the queue as one run would have.
+    clearance=True: every result gains `clearance`, the episode's closest-approach records (SceneBatch(clearance=True); one record per
+    agent, metrics.clearance_metrics reads them), taken when the slot finishes, before it is refilled, with `harvest` on or off."""
     import os
     cks = {i: e for i, e in enumerate(episodes) if isinstance(e, SceneCheckpoint)}
     episodes = [e.agents() if isinstance(e, SceneCheckpoint) else list(e) for e in episodes]
@@ -774,7 +801,7 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
                          'would run without one: put a tracked episode among the first %d' % (min(i for i in pending if tracked[i]), len(holding)))
     batch = SceneBatch([episodes[i] for i in holding], obstacles, device_tracker=device_tracker, scene_history=history_rows,
                        capacities=None if capacities is None else caps, harvest=harvest, attribute_slots=attributes, path_slots=path_slots,
-                       scene_obstacles=None if ocaps is None else [episode_obstacles[i] for i in holding], obstacle_capacities=ocaps)
+                       scene_obstacles=None if ocaps is None else [episode_obstacles[i] for i in holding], obstacle_capacities=ocaps, clearance=clearance)
     results = [None] * len(episodes)
     batch_steps = served = 0
     written = None
@@ -808,6 +835,8 @@ def run_episodes(episodes, slots, obstacles=(), device_tracker=False, on_done=No
                     for k, a in enumerate(episodes[i]):
                         del a._path[int(path_rem[lo + k]):]
                     results[i]['path_left'] = [len(a._path) for a in episodes[i]]
+                if clearance:                                     # a finished scene keeps its records until the restart below
+                    results[i]['clearance'] = view.clearance
                 if batch.scene_history:
                     rows, dropped = view.solver.history_rows()
                     results[i].update(trajectories=metrics.trajectories(view, rows=rows), rows_dropped=dropped, info=metrics.episode_info(view, **info_args))

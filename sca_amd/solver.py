@@ -450,6 +450,23 @@ class BatchedSolver:
         self._chk(self.L.sca_scene_harvest_collect(self.ctx, _lib.ptr(ids, C.c_int32), C.byref(count)), 'sca_scene_harvest_collect')
         return [int(s) for s in ids[:count.value]]
 
+    # ---- closest approach per agent, measured with the step (sca_scene_clearance_enable) ------------------------------------
+    def scene_clearance_enable(self, on=True):
+        """From now on every step runs k_scene_clearance: every occupied agent row keeps how close it came to another agent and to an
+        obstacle of its scene, with whom and at which of the scene's steps (include/sca_hip.h has the rule).  Every row starts empty;
+        on=False frees the records."""
+        self._chk(self.L.sca_scene_clearance_enable(self.ctx, 1 if on else 0), 'sca_scene_clearance_enable')
+
+    def scene_clearance(self, scene):
+        """The records of one scene's occupied rows, a structured array (_lib.CLEARANCE_DTYPE: agent_clear, obs_clear f64, agent_partner,
+        agent_step, obs_partner, obs_step i32; an empty half is +inf, -1, 0).  One copy, one synchronisation."""
+        scene = int(scene)
+        inside = self.scene_offsets is not None and 0 <= scene < self.nscenes
+        out = np.zeros(int(self.scene_sizes()[scene]) if inside else 1, _lib.CLEARANCE_DTYPE)      # (a scene the library will refuse still gets a buffer)
+        self._chk(self.L.sca_get_scene_clearance(self.ctx, scene, out.ctypes.data_as(C.POINTER(_lib.SceneClearance)), _lib.CLEARANCE_DTYPE.itemsize),
+                  'sca_get_scene_clearance')
+        return out
+
     # ---- scene checkpoints (sca_save_scenes / sca_load_scenes) ---------------------------------------------------------------
     def scene_checkpoint_bytes(self, scene):
         """the size of the blob save_scenes writes for the scene as it stands now"""

@@ -36,7 +36,16 @@ and the difference scene_sets - shared_set is the feature's cost (expected: two 
                       parent's figure for the same shapes (entry `log_off_against_parent`: within the two spreads together, or the log-off path moved)
     log_on            the same batch with a log of warm + window rows per scene: one more dispatch per step (k_scene_log), 64 B per live agent
 Both legs are this build's; every window starts from sca_set_scenes (new step counters: the log starts at row 0) and the start states.  Beside
-them the wall time of reading one scene's whole log back (sca_get_scene_history), next to a step of the same batch."""
+them the wall time of reading one scene's whole log back (sca_get_scene_history), next to a step of the same batch.
+
+    python tools/bench/scenes_cost.py --clearance --scenes 16,256,1024 --root /path/to/parent/checkout   # into profiles/scene_clearance_cost.json
+
+--clearance: what the closest approach per agent (sca_scene_clearance_enable) costs.  The circle workloads above, legs
+    clearance_off     the batch without the feature: it enqueues what the parent commit enqueued
+    clearance_on      the same batch with the feature: one more dispatch per step (k_scene_clearance), O(size^2) rounded norms per live scene
+    parent            the same batch through the library of --root in the same process (left out without --root): the off leg has to lie
+                      inside the spread of the parent's own windows (entry `off_against_parent`)
+All legs alternate window by window; every window starts from sca_set_scenes and the start states.  The on leg is reported as measured."""
 import argparse
 import importlib
 import importlib.util
@@ -284,6 +293,64 @@ def log_workloads(args, S, scenarios):
                     sol.close()
 
 
+def clearance_workloads(args, S, scenarios, Sp, scp):
+    out = args.out if args.out_given else os.path.join(REPO, 'profiles', 'scene_clearance_cost.json')
+    sc = scenarios.circle(SCENE_AGENTS)
+    for policy in [p for p in args.policy.split(',') if p]:
+        for B in [int(x) for x in args.scenes.split(',') if x]:
+            legs = {}
+            off = np.arange(B + 1, dtype=np.int32) * SCENE_AGENTS
+            for leg, mod, scn, on in (('clearance_off', S, scenarios, False), ('clearance_on', S, scenarios, True), ('parent', Sp, scp, False)):
+                if mod is None:
+                    continue
+                sol, reset_state = make_context(mod, scn, sc, B, policy, True)
+
+                def reset(sol=sol, reset_state=reset_state, on=on):
+                    sol.set_scenes(off)                               # new step counters; drops the records
+                    reset_state()
+                    if on:
+                        sol.scene_clearance_enable()
+                legs[leg] = ([sol], [reset])
+            rows = time_legs(legs, args, S.NBR_KDTREE)
+            states = {leg: sols[0].get_state() for leg, (sols, _) in legs.items()}     # the feature changes no value
+            for leg in states:
+                for key in states['clearance_off']:
+                    assert np.array_equal(states[leg][key], states['clearance_off'][key]), (leg, key)
+            rec = legs['clearance_on'][0][0].scene_clearance(B // 2)
+            a, b = rows['clearance_on'], rows['clearance_off']
+            margin = (a['spread_ms'][1] - a['spread_ms'][0]) + (b['spread_ms'][1] - b['spread_ms'][0])
+            n = B * SCENE_AGENTS
+            entry = {'workload': '%d x circle of %d, %s' % (B, SCENE_AGENTS, 'SCA + device tracker' if policy == 'sca' else 'ORCA3D'),
+                     'scenes': B, 'agents': n, 'warm_steps': args.warm, 'window_steps': args.window, 'alternations': args.alternations, 'legs': rows,
+                     'pair_norms_per_step_at_most': B * SCENE_AGENTS * (SCENE_AGENTS - 1),
+                     'min_clearance_of_the_middle_scene': float(rec['agent_clear'].min()),
+                     'cost': {'on_minus_off_us': 1e3 * (a['ms_per_step'] - b['ms_per_step']), 'ratio_on_over_off': a['ms_per_step'] / b['ms_per_step'],
+                              'sum_of_spreads_us': 1e3 * margin, 'within_the_spreads': bool(abs(a['ms_per_step'] - b['ms_per_step']) <= margin)}}
+            if 'parent' in rows:
+                p = rows['parent']
+                entry['off_against_parent'] = {'off_minus_parent_us': 1e3 * (b['ms_per_step'] - p['ms_per_step']), 'parent_spread_ms': p['spread_ms'],
+                                               'off_inside_the_parents_spread': bool(p['spread_ms'][0] <= b['ms_per_step'] <= p['spread_ms'][1]),
+                                               'off_not_above_the_parents_spread': bool(b['ms_per_step'] <= p['spread_ms'][1])}
+            try:
+                with open(out) as f:
+                    doc = json.load(f)
+            except (OSError, ValueError):
+                doc = {'tool': 'tools/bench/scenes_cost.py --clearance', 'unit': 'ms per step of all B scenes; median_ms: the median step time of each window', 'workloads': {}}
+            doc['host'] = host()
+            doc['workloads']['%s_x%d' % (policy, B)] = entry
+            os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+            with open(out, 'w') as f:
+                json.dump(doc, f, indent=1, sort_keys=True)
+                f.write('\n')
+            for leg, r in rows.items():
+                print('%-5s B=%-5d %-16s %9.4f ms/step  spread %.4f .. %.4f  active at end %s' % (policy, B, leg, r['ms_per_step'], r['spread_ms'][0],
+                                                                                                r['spread_ms'][1], r['active_at_end'][-1]), flush=True)
+            print(policy, B, json.dumps(entry['cost']), json.dumps(entry.get('off_against_parent')), flush=True)
+            for sols, _ in legs.values():
+                for sol in sols:
+                    sol.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--scenes', default='1,16,256,1024')
@@ -296,6 +363,8 @@ def main():
     ap.add_argument('--batch-only', action='store_true', help='without the one_by_one legs: the batch against batch_root alone (needs --root)')
     ap.add_argument('--obstacles', action='store_true', help='the per-scene obstacle sets against one shared set, instead of the batch against B contexts')
     ap.add_argument('--log', action='store_true', help='the trajectory log per scene off and on in this build, into profiles/scene_log_cost.json')
+    ap.add_argument('--clearance', action='store_true', help='the closest approach per agent off and on in this build, beside the library of --root, '
+                                                             'into profiles/scene_clearance_cost.json')
     args = ap.parse_args()
     args.out_given = args.out is not None
     if not args.out_given:
@@ -313,6 +382,8 @@ def main():
         return obstacle_workloads(args, S, scenarios, Sp, scp)
     if args.log:
         return log_workloads(args, S, scenarios)
+    if args.clearance:
+        return clearance_workloads(args, S, scenarios, Sp, scp)
     KD = S.NBR_KDTREE
     sc = scenarios.circle(SCENE_AGENTS)
 
