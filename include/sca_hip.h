@@ -713,11 +713,13 @@ int sca_comm_destroy(sca_ctx *ctx);
  * (kdTree.py:124-156, agent.py:79-99 on the grid) and the collision check (mampenv.py:61-80) of its agents look at.  Per step
  * it exchanges, with its two slab neighbours only, the old + moved records of the agents next to the cut and the private state
  * (heading, v_pref, distances, tracker record) of agents that crossed it, instead of all N records.  Results equal a single
- * rank's bit for bit (tests/test_gpu_partition.py).
+ * rank's bit for bit (tests/test_gpu_partition.py: 2 / 3 processes against a one-rank run; tests/test_gpu_partition_fuzz.py: up to five ranks
+ * in one process on scenes made for the cuts, every agent after every step against the oracle of the grid's list rule -- owner sets, halo
+ * counts, message headers, and for a migrant everything that travelled with it).
  *   sca_partition_init   after sca_set_agents + sca_set_state with the COMPLETE state on every rank.  cuts: nranks - 1 ascending
  *                        coordinates along the axis, or NULL = equal shares of the agents as they stand; moved onto cell
- *                        boundaries.  cap_halo / cap_mig: entries per message (0 = n / 4, n / 16); an overflow is reported
- *                        by sca_partition_commit.  From then on the per-agent arrays of sca_get_* are meaningful for the owned
+ *                        boundaries.  cap_halo / cap_mig: entries per message (0 = n / 4 and n / 16, at least 1024 and 256); an overflow
+ *                        is reported by sca_partition_commit or the next sca_synchronize.  From then on the per-agent arrays of sca_get_* are meaningful for the owned
  *                        agents only (sca_partition_owned).  sca_set_state (complete again) re-derives the ownership.
  *   one step             sca_step_begin(SCA_NBR_GRID) -> sca_partition_pack into two DEVICE buffers of sca_partition_message_bytes()
  *                        (for the lower / the upper slab neighbour) -> exchange (what a rank packed for its lower neighbour is

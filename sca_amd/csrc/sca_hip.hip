@@ -3323,8 +3323,10 @@ static void part_view(sca_ctx *c) {
     c->d.own = c->d.present = c->part.present[c->part.cur];
     c->d.count_dev = c->part.counts;
     c->d.shard_begin = 0;
-    c->d.shard_count = c->part_counts[0];
-    c->d.n_present = c->part_counts[0] + c->part_counts[1];
+    // launch BOUNDS (the kernels read the exact counts, shard_size / present_count): never 0 -- a rank that owns nothing right after
+    // sca_partition_init or sca_set_state, where the bounds are the exact counts, would otherwise launch empty grids
+    c->d.shard_count = std::max(1, c->part_counts[0]);
+    c->d.n_present = std::max(c->d.shard_count, c->part_counts[0] + c->part_counts[1]);
 }
 static int part_free(sca_ctx *c) {
     if (!c->part_on && !c->part.counts) return 0;

@@ -810,6 +810,7 @@ struct alignas(16) Prep {
                            // numerator of v_pref
 };
 static_assert(sizeof(Prep) == 48, "Prep must be 48 bytes");
+constexpr int PHI_BIAS = 314160;   // get_phi numerators are -314159 .. 628318: + PHI_BIAS they are 1 .. 942478, below the 0xfffff the selection subtracts them from
 
 // the agents whose v_pref the device tracker computes in this pass (mampenv.py:35 + the policy): their prologue is written by the
 // tracker's kernels right behind v_pref (track_store), everybody else's by the neighbour structure's first kernel
@@ -845,9 +846,10 @@ __device__ __forceinline__ void prep_agent(const DeviceView &d, const Params &Pc
     double kn;
     l3norm(vpref, vpref, &kn);
     r.vp_key = pack_key(kn, 0);
-    // util.py:145 of the v_pref candidate (<= 628318): read by shunted_strategy only (SCA, S-RVO3D) -- the other policies' prologue skips
-    // the atan2 (a call into the restated libm since round 6)
-    if (pol == POL_SCA || pol == POL_SRVO) bits |= (unsigned)get_phi_num<LIBM>(vpref.x, vpref.y) << 8;
+    // util.py:145 of the v_pref candidate: read by shunted_strategy only (SCA, S-RVO3D) -- the other policies' prologue skips
+    // the atan2 (a call into the restated libm since round 6).  -314159 .. 628318: get_phi of (x < 0, y = -0.0) is atan2's -pi, because
+    // -0.0 >= 0 holds; kept with PHI_BIAS so that the packed selection compares unsigned numbers
+    if (pol == POL_SCA || pol == POL_SRVO) bits |= (unsigned)((int)get_phi_num<LIBM>(vpref.x, vpref.y) + PHI_BIAS) << 8;
     r.bits = bits;
     out[agent] = r;
 }
@@ -1516,7 +1518,7 @@ __device__ __forceinline__ void solve_fast(const DeviceView &d, const Params &Pc
                 auto consider = [&](unsigned k) {
                     if (k < fail) {                                                      // 0xffffffff (no entry) never is
                         const int ci = (int)(k & 1023u);
-                        const unsigned ph = ci >= T.vp_idx ? (pr.bits >> 8) : (unsigned)T.phi[ci >= T.num_N ? ci - T.num_N : ci];   // <= 628318
+                        const unsigned ph = ci >= T.vp_idx ? (pr.bits >> 8) : (unsigned)((int)T.phi[ci >= T.num_N ? ci - T.num_N : ci] + PHI_BIAS);   // 1 .. 942478
                         const unsigned ih = 0xfffffu - ph;
                         if (ph < pmin || (ph == pmin && k < kpmin)) { pmin = ph; kpmin = k; }
                         if (ih < pmax || (ih == pmax && k < kpmax)) { pmax = ih; kpmax = k; }
@@ -1528,7 +1530,7 @@ __device__ __forceinline__ void solve_fast(const DeviceView &d, const Params &Pc
                 const unsigned wpmin = wave_min_u32(pmin), wpmax = wave_min_u32(pmax);
                 const unsigned kmin = wave_min_u32(pmin == wpmin ? kpmin : 0xffffffffu);
                 const unsigned kmax = wave_min_u32(pmax == wpmax ? kpmax : 0xffffffffu);
-                const double phi_min = (double)wpmin / EPS5, phi_max = (double)(0xfffffu - wpmax) / EPS5;
+                const double phi_min = (double)wpmin / EPS5, phi_max = (double)(0xfffffu - wpmax) / EPS5;      // (only their difference is used: the bias drops out)
                 chosen = (fabs(phi_max - phi_min) <= PI) ? (int)(kmin & 1023u) : (int)(kmax & 1023u);
             }
             dg_chosen = chosen;
@@ -1703,7 +1705,7 @@ __device__ __forceinline__ void solve_pick4(const DeviceView &d, const Params &P
             auto consider = [&](unsigned k) {
                 if (k < fail) {
                     const int ci = (int)(k & 1023u);
-                    const unsigned ph = ci >= T.vp_idx ? (pr.bits >> 8) : (unsigned)T.phi[ci >= T.num_N ? ci - T.num_N : ci];
+                    const unsigned ph = ci >= T.vp_idx ? (pr.bits >> 8) : (unsigned)((int)T.phi[ci >= T.num_N ? ci - T.num_N : ci] + PHI_BIAS);
                     const unsigned ih = 0xfffffu - ph;
                     if (ph < pmin || (ph == pmin && k < kpmin)) { pmin = ph; kpmin = k; }
                     if (ih < pmax || (ih == pmax && k < kpmax)) { pmax = ih; kpmax = k; }

@@ -141,6 +141,218 @@ def switch_scene(n):
                 max_run_dist=3.0 * np.linalg.norm(pos - goal, axis=1) + 1.0, key=('switch', n))
 
 
+CUT_N = (2, 9, 33, 64, 100, 257, 400)
+CUT_SEEDS = (0, 1)                             # per (world, axis): 24 plain cut scenes
+CUT_WORLDS = (2, 3, 4, 5)
+CUT_PER_AGENT = tuple((w, a, 10 + k) for k, (w, a) in enumerate([(2, 0), (3, 1), (4, 2), (5, 0), (2, 1), (3, 2), (4, 0), (5, 1)]))
+CUT_TRACKED = ((2, 0, 22), (2, 2, 20), (4, 1, 21), (4, 0, 24))               # (d): policy 0 agents under the device tracker; 100, 257, 64, 257 agents
+# the cuts in cells per world (two variants by seed): every interior slab of worlds 3 and 4 is two cells wide, the least sca_partition_init
+# accepts, and from world 4 on two such slabs are adjacent; cells below and above zero either way
+_CUT_CELLS = {2: ([-1], [1]), 3: ([-1, 1], [-2, 0]), 4: ([-2, 0, 2], [-3, -1, 1]), 5: ([-3, -1, 1, 3], [-4, -1, 1, 3])}
+
+
+def cut_attributes(seed, n):
+    """per-agent solver attributes for cut_scene(seed, ..., nd=4.0), as per_agent_attributes returns them: neighbor_dist 1.5 / 2.5 / 4.0 with
+    4.0 present (the cell is then about 4 m), time_step up to 0.2, max_speed up to 3.0"""
+    rng = np.random.default_rng(177 + seed)
+    per = dict(neighbor_dist=rng.choice([1.5, 2.5, 4.0], n), max_neighbors=rng.choice([1, 2, 4, 8, 12, 16], n).astype(np.int32),
+               time_step=rng.choice([0.05, 0.1, 0.2], n), time_horizon=rng.choice([1.0, 3.0, 10.0, 20.0], n), max_speed=rng.choice([0.7, 1.0, 1.5, 3.0], n),
+               max_heading_change=rng.choice([0.3, math.pi / 6, math.pi / 4, 1.2, math.pi / 2], n), dt_nominal=rng.choice([0.05, 0.1], n))
+    per['neighbor_dist'][0] = 4.0
+    return per, {}, False
+
+
+def cut_scene(seed, world, axis, nd=10.0, policies=None):
+    """A scene made for the cell-owner partition's cuts, with random_scene's keys: (scene, cuts).  `world` slabs along `axis`, the cuts given
+    in metres somewhere inside the cell they are moved to the boundary of (_CUT_CELLS; the cell is the grid's for the largest neighbor_dist
+    `nd`).  About a third of the agents are uniform in the box; the others are placed, in this order until two thirds of n are used:
+        the empty-rank agents (seed-dependent: an end rank owns nothing and gains its first agents, or holds only agents that leave)
+        head-on pairs straddling a cut, r_a + r_b + 0.1 .. 0.4 apart, one of them about to cross; the same against an obstacle on the cut
+        crossers within 0.4 m of a cut with velocity, heading, fed v_pref and goal across it (the goal far away or 0.2 .. 0.5 m beyond)
+        boundary agents: the first double of cell k and the last one of cell k - 1, for a positive and a negative k
+        returners (goal on the near side, velocity across), finished agents inside the edge layers
+        a clump of 18 .. 24 agents within neighbor_dist of each other, centred on a cut
+    and then more crossers, pairs and returners over all cuts.  policies: the policy values to draw from (None: 0 .. 5)."""
+    import partition_ranks as PR
+    rng = np.random.default_rng([seed, world, axis, 4242])
+    n = int(rng.choice(CUT_N))
+    inv = PR.inv_cell_of(nd)
+    cell = 1.0 / inv
+    ks = _CUT_CELLS[world][seed % 2]
+    cuts = [float((k + rng.uniform(0.05, 0.95)) * cell) for k in ks]
+    bound = [PR.first_double_of_cell(k, inv) for k in ks]                     # where the cuts really are
+    side = float(rng.choice([3.0, 6.0])) * max(1.0, math.sqrt(n / 64.0))          # (the placed agents sit near the cuts: room across)
+    lo, hi = bound[0] - 1.2 * cell, bound[-1] + 1.2 * cell
+    empty = (None, 'gains', 'loses')[(seed + axis) % 3]                       # per world every mode comes with two of the six scenes
+    # (an end rank: the last one for `gains`, the first for `loses`; with two ranks the one whose cells lie further from zero)
+    top = (ks[0] > 0) if world == 2 else empty == 'gains'
+    if empty is not None and top:
+        hi = bound[-1] - 0.5                                                  # that rank owns nothing, or only what is placed there below
+    if empty is not None and not top:
+        lo = bound[0] + 0.5
+    zoff = float(rng.choice([0.0, 1.0, 20.0]))
+    pol_set = np.arange(6) if policies is None else np.asarray(policies)
+
+    def point(x):
+        p = rng.uniform(-side, side, 3)
+        if axis != 2:
+            p[2] = abs(p[2]) + zoff
+        p[axis] = x
+        return p
+
+    pos = np.array([point(rng.uniform(lo, hi)) for _ in range(n)])
+    goal = np.array([point(rng.uniform(lo, hi)) for _ in range(n)])
+    if axis != 2:
+        goal[:, 2] += 1.0
+    v = rng.normal(0, 1, (n, 3))
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    v *= rng.uniform(0, 1, (n, 1))
+    if rng.random() < 0.3:
+        v[rng.random(n) < 0.3] = 0.0
+    head = np.zeros((n, 3))
+    head[:, 0] = rng.uniform(0, 2 * np.pi, n)
+    head[:, 1] = rng.uniform(-0.5, 0.5, n)
+    policy = rng.choice(pol_set, n).astype(np.uint8)
+    flags = ((rng.random(n) < 0.1) * rng.choice([1, 2, 4], n)).astype(np.uint8)
+    radius = rng.choice([0.3, 0.5, 1.0], n)
+    vpx = np.trunc(rng.normal(0, 0.6, (n, 3)) * 1e5) / 1e5
+    obs = [(point(rng.uniform(lo, hi)), float(rng.choice([0.2, 1.0, 2.0]))) for _ in range(int(rng.choice([0, 1, 5])))]
+    e = np.zeros(3)
+    e[axis] = 1.0
+    used = [0]
+    quota = n - n // 3
+
+    def put(x, d, far=True, speed=None, p=None, returner=False):
+        """the next agent at coordinate x along the axis (p: its other coordinates), moving in direction d = +-1 along the axis, its goal
+        on the other side of x + d * (its distance) -- or behind it (returner); False when the quota is used up"""
+        if used[0] >= quota:
+            return -1
+        i = used[0]
+        used[0] += 1
+        pos[i] = point(x) if p is None else p
+        pos[i, axis] = x
+        flags[i] = 0
+        sp = rng.uniform(0.6, 1.0) if speed is None else speed
+        v[i] = d * e * sp
+        head[i] = 0.0
+        if axis == 0:
+            head[i, 0] = 0.0 if d > 0 else np.pi
+        elif axis == 1:
+            head[i, 0] = d * np.pi / 2
+        else:
+            head[i, 1] = d * 0.7                                              # (inside the pitch limits)
+        g = pos[i] + d * e * (rng.uniform(15.0, 40.0) if far else rng.uniform(0.2, 0.5))
+        if returner:
+            g = pos[i] - d * e * rng.uniform(2.0, 20.0)
+        goal[i] = g + (0.0 if not far or returner else 1.0) * rng.normal(0, 0.3, 3) * (1.0 - e)
+        vpx[i] = np.trunc(d * e * rng.uniform(0.7, 1.0) * 1e5) / 1e5
+        return i
+
+    def crosser(b, d, far):
+        """within 0.4 m of boundary b on the side it leaves (d = +1: below it); a near goal lies 0.2 .. 0.5 m beyond the cut"""
+        gap = rng.uniform(0.01, 0.4 if far else 0.15)
+        i = put(b - d * gap, d, far=True)
+        if i >= 0 and not far:
+            goal[i] = pos[i]
+            goal[i, axis] = b + d * rng.uniform(0.2, 0.5)
+        return i
+
+    def pair(b, d):
+        """head on across boundary b: a moves in direction d and is about to cross, c comes the other way on the far side"""
+        ga = rng.uniform(0.01, 0.06)
+        a = put(b - d * ga, d)
+        if a < 0 or used[0] >= quota:
+            return
+        sep = radius[a] + radius[used[0]] + rng.uniform(0.1, 0.4)
+        put(pos[a, axis] + d * sep, -d, p=pos[a].copy())
+
+    def against_obstacle(b, d):
+        r_o = float(rng.choice([0.2, 1.0]))
+        a = put(b - d * rng.uniform(0.01, 0.06), d)
+        if a >= 0:
+            c = pos[a].copy()
+            c[axis] = pos[a, axis] + d * (radius[a] + r_o + rng.uniform(0.1, 0.3))
+            obs.append((c, r_o))
+
+    # ---- the empty rank
+    leavers = []
+    if empty == 'gains':
+        for _ in range(2):
+            crosser(bound[-1] if top else bound[0], +1 if top else -1, True)
+    elif empty == 'loses':
+        for _ in range(2):
+            i = put(bound[-1] + rng.uniform(0.01, 0.05), -1, speed=1.0) if top else put(bound[0] - rng.uniform(0.01, 0.05), +1, speed=1.0)
+            if i >= 0:
+                leavers.append(i)
+                policy[i] = 3 if policies is None else policy[i]             # (ORCA3D, straight-line v_pref at pref_speed: it leaves for certain)
+    order = list(range(len(bound)))
+    for c in order:                                                           # one pair per cut first: the smallest scenes get them
+        pair(bound[c], +1 if (c + seed) % 2 == 0 else -1)
+    for c in order:
+        crosser(bound[c], -1 if (c + seed) % 2 == 0 else +1, far=bool((c + seed) % 2))
+    # ---- boundary agents: the first double of a cell and the last one of the cell below, a positive and a negative k (the cuts when they fit)
+    for k in ([k for k in ks if k > 0][:1] or [1]) + ([k for k in ks if k < 0][:1] or [-1]):
+        b = PR.first_double_of_cell(k, inv)
+        if lo < b < hi:
+            put(b, +1 if rng.random() < 0.5 else -1)
+            put(float(np.nextafter(b, -np.inf)), +1 if rng.random() < 0.5 else -1)
+    for c in order:
+        against_obstacle(bound[c], +1 if (c + seed) % 2 else -1)
+        d = +1 if rng.random() < 0.5 else -1
+        put(bound[c] - d * rng.uniform(0.01, 0.1), d, returner=True)
+        for d in (+1, -1):                                                    # finished from the start inside the edge layers of both sides
+            i = put(bound[c] - d * rng.uniform(0.0, 0.9) * cell, d)
+            if i >= 0 and lo < pos[i, axis] < hi:
+                flags[i] = rng.choice([1, 2, 4])
+    # ---- a clump on a cut: more than 16 within neighbor_dist of one another, members on both sides
+    if quota - used[0] >= 24:
+        b = bound[int(rng.integers(0, len(bound)))]
+        centre = point(b)
+        for _ in range(int(rng.integers(18, 25))):
+            i = put(b, +1)
+            off = rng.normal(0, 1, 3)
+            off *= rng.uniform(0.2, 0.45) * min(nd, 10.0) / np.linalg.norm(off)
+            pos[i] = centre + off
+            d = +1 if pos[i, axis] < b else -1
+            v[i] = d * e * rng.uniform(0.2, 1.0)
+            vpx[i] = np.trunc(v[i] * 1e5) / 1e5
+            goal[i] = centre + d * e * rng.uniform(3.0, 20.0)
+    while used[0] < quota:
+        c = int(rng.integers(0, len(bound)))
+        d = +1 if rng.random() < 0.5 else -1
+        what = rng.integers(0, 4)
+        if what == 0:
+            pair(bound[c], d)
+        elif what == 1:
+            put(bound[c] - d * rng.uniform(0.01, 0.2), d, returner=True)
+        else:
+            crosser(bound[c], d, far=bool(what == 2))
+    # ---- the empty rank stays what it was made: whoever else was placed into it is mirrored at its cut, with what it aims at
+    if empty is not None:
+        b = bound[-1] if top else bound[0]
+        inside = pos[:, axis] >= b if top else pos[:, axis] < b
+        inside[leavers] = False
+        for i in np.flatnonzero(inside):
+            pos[i, axis] = (float(np.nextafter(b, -np.inf)) - (pos[i, axis] - b)) if top else b + (b - pos[i, axis])
+            goal[i, axis] = 2 * b - goal[i, axis]
+            v[i, axis], vpx[i, axis] = -v[i, axis], -vpx[i, axis]
+            if axis == 0:
+                head[i, 0] = np.pi - head[i, 0]
+            else:
+                head[i, int(axis == 2)] = -head[i, int(axis == 2)]
+    if empty == 'loses':                                                      # ... and who comes toward it arrives after its last agent has left
+        late = (np.abs(pos[:, axis] - b) < 0.4) & (v[:, axis] * (1 if top else -1) > 0)
+        late[leavers] = False
+        pos[late, axis] += -0.4 if top else 0.4
+    m = len(obs)
+    obs_pos = np.array([o[0] for o in obs]).reshape(m, 3)
+    obs_radius = np.array([o[1] for o in obs]).reshape(m)
+    return dict(n=n, m=m, pos=pos, goal=goal, heading=head, vel=v.astype(np.float32), radius=radius,
+                pref_speed=rng.choice([1.0, 1.0, 0.8, 1.5], n), policy=policy, flags=flags, obs_pos=obs_pos, obs_radius=obs_radius,
+                vpref=vpx, vmode=np.isin(policy, (0, 5)).astype(np.uint8), max_run_dist=3.0 * np.linalg.norm(pos - goal, axis=1) + 1.0,
+                key=('cut', seed, world, axis, nd, None if policies is None else tuple(policies))), cuts
+
+
 def no_lp(scene):
     """the same scene with the ORCA3D-LP agents (policy 4) as ORCA3D agents (3): a shard without LP agents, which k_solve_fb may take"""
     s = dict(scene)
@@ -161,7 +373,7 @@ _RUNS_MAX = 3 * BLOCK                          # the rows of one block run one a
 
 def oracle_run(oracle, scene, steps, per_agent=None, list_rule=0, paths=None):
     """The free-running oracle trajectory of a scene: policy_step then env_update per step, from the scene's own state.  One dict per step:
-    action, nbr_valid, nbr_n, nbr_id, nbr_kind, nbr_dsq, diag, perm, `before` (the flags the step started from), `flags_policy` (the flags after
+    action, nbr_valid, nbr_n, nbr_id, nbr_kind, nbr_dsq, diag, perm, vpref (the v_pref the pass used), `before` (the flags the step started from), `flags_policy` (the flags after
     the policy pass) and the state after the step (STATE_KEYS).  per_agent: what per_agent_attributes returned.  list_rule: 0 the reference's lists
     (what SCA_NBR_KDTREE and SCA_NBR_AUTO return), 1 the lists SCA_NBR_GRID documents (oracle.set_list_rule); `status` then carries bit 32 on the
     rows that overflowed.  paths: what random_paths returned -- before each policy_step the rule (path_rule.pass_rule_csr) advances the lists; its
@@ -204,7 +416,7 @@ def oracle_run(oracle, scene, steps, per_agent=None, list_rule=0, paths=None):
             perm = r['perm']
             u = oracle.env_update(p, ve, he, s['radius'], r['flags'], s['goal'], r['action'], td, s['max_run_dist'], sn,
                                   s['obs_pos'], s['obs_radius'])
-            step = {k: r[k] for k in ('action', 'nbr_valid', 'nbr_n', 'nbr_id', 'nbr_kind', 'nbr_dsq', 'diag', 'perm', 'status')}
+            step = {k: r[k] for k in ('action', 'nbr_valid', 'nbr_n', 'nbr_id', 'nbr_kind', 'nbr_dsq', 'diag', 'perm', 'status', 'vpref')}
             step['before'], step['flags_policy'] = fl, r['flags']
             step.update(path)
             p, ve, he, fl, td, sn = u['pos'], u['vel'], u['heading'], u['flags'], u['total_dist'], u['step_num']

@@ -39,6 +39,52 @@ def planned(H, simds, scene, part_on=0):
     return solve(H, scene['n'], simds=simds, part_on=part_on, nranks=1, lp=lp, lp_total=lp, t=(C.c_int * len(t))(*t.values()))
 
 
+def compare_grid_step(sol, r, scene, at, rows=None, list_rows=None, vpref=False):
+    """What a context holds after a resident step in SCA_NBR_GRID against the rule-1 oracle's record `r` of that step; failures name the
+    agents.  rows: the ids of the agents whose state (flags, step counts, float32 velocities, positions, headings, travelled distance) and
+    results (action rows, diagnostics, status words) are compared -- None: every agent; under the cell-owner partition the agents the rank owns
+    AFTER the step (a migrant's results travelled with it).  list_rows: the ids whose neighbour lists are compared entry for entry in the
+    grid's own order (None: `rows`; under the partition the agents the rank owned BEFORE the step: it ran the pass).  vpref: the v_pref the
+    pass used is compared too, on the served rows.  Returns how many of list_rows the oracle has overflowed."""
+    rows = np.arange(scene['n']) if rows is None else np.asarray(rows, np.int64)
+    lrows = rows if list_rows is None else np.asarray(list_rows, np.int64)
+
+    def same(bad, what, of=rows, got=None, want=None):
+        """no row of `bad`; else the failure names the place, the quantity, the agents and the first one's two values"""
+        if np.any(bad):
+            k = np.flatnonzero(bad)
+            first = () if got is None else ('agent', int(of[k[0]]), 'holds', got[k[0]].tolist(), 'oracle', want[k[0]].tolist())
+            raise AssertionError(' '.join(str(x) for x in at + (what, 'agents', of[k][:8].tolist()) + first))
+    g = sol.get_state()
+    for k in ('flags', 'step_num', 'vel', 'pos', 'heading', 'total_dist'):
+        got, want = g[k][rows], r[k][rows]
+        same((got != want).reshape(len(rows), got[0].size if len(rows) else 1).any(axis=1), k, got=got, want=want)
+    a = sol.actions()[rows]
+    same((a != r['action'][rows]).any(axis=1), 'action', got=a, want=r['action'][rows])
+    nb = {k: v[lrows] for k, v in sol.neighbors().items()}
+    valid, want_n = r['nbr_valid'][lrows].astype(bool), r['nbr_n'][lrows]
+    same(nb['nbr_valid'].astype(bool) != valid, 'nbr_valid', lrows)
+    same(valid & (nb['nbr_n'] != want_n), 'nbr_n', lrows, nb['nbr_n'], want_n)
+    live = valid[:, None] & (np.arange(K)[None, :] < want_n[:, None])
+    for k in ('nbr_id', 'nbr_kind', 'nbr_dsq'):
+        same((live & (nb[k] != r[k][lrows])).any(axis=1), k, lrows, nb[k], r[k][lrows])
+    dg = sol.diag()
+    lp = (scene['policy'] == 4)[rows]
+    got, want = dg['diag'][rows], r['diag'][rows]
+    same((got[:, :2] != want[:, :2]).any(axis=1), 'n_suit / fallback', got=got, want=want)
+    same(lp & (got[:, 3:5] != want[:, 3:5]).any(axis=1), 'planeFail / lp4', got=got, want=want)
+    st = dg['status'][rows]
+    same((st & ~(OVERFLOW | 64 | 128)) != 0, 'status bits', got=st, want=r['status'][rows])
+    over, over_ref = (st & OVERFLOW) != 0, (r['status'][rows] & OVERFLOW) != 0
+    same(over_ref & ~over, 'overflow not reported')
+    collided_now = (((r['flags_policy'] & 2) != 0) & ((r['before'] & 2) == 0))[rows]
+    same(over & ~over_ref & ~collided_now, 'spurious overflow')
+    if vpref:
+        served = ((r['before'] & 7) == 0)[rows]
+        same(served & (dg['vpref'][rows] != r['vpref'][rows]).any(axis=1), 'v_pref used', got=dg['vpref'][rows], want=r['vpref'][rows])
+    return int((((r['status'][lrows] & OVERFLOW) != 0) & valid).sum())
+
+
 def run_grid_against_oracle(S, oracle, scene, steps, per_agent, plan, ctx, partition=False, may_refuse=False, paths=None):
     """One context, `steps` resident steps in SCA_NBR_GRID, everything compared with the rule-1 oracle after each.  Returns None where the
     library refused the scene at its first pass (may_refuse), else the overflowed rows the oracle had per step.  paths: the scene's waypoint
@@ -51,8 +97,6 @@ def run_grid_against_oracle(S, oracle, scene, steps, per_agent, plan, ctx, parti
         if partition:
             sol.partition_init(0, 1, axis=0)
             assert sol.partition_counts() == (n, 0), ctx
-        lp = s['policy'] == 4
-        col = np.arange(K)[None, :]
         for t, r in enumerate(ref):
             at = ctx + ('n', n, 'step', t)
             try:
@@ -66,32 +110,7 @@ def run_grid_against_oracle(S, oracle, scene, steps, per_agent, plan, ctx, parti
             forms = sol.pass_forms()
             assert (forms & SOLVE_BITS) == plan['forms'], at + ('forms', forms, plan)
             assert bool(forms & S.FORM_WAYPOINTS) == (paths is not None), at + ('forms', forms)
-            g = sol.get_state()
-            assert np.array_equal(g['flags'], r['flags']), at + ('flags', np.flatnonzero(g['flags'] != r['flags'])[:8])
-            assert np.array_equal(g['step_num'], r['step_num']), at + ('step_num',)
-            assert np.array_equal(g['vel'], r['vel']), at + ('vel', np.flatnonzero((g['vel'] != r['vel']).any(axis=1))[:8])
-            for k in ('pos', 'heading', 'total_dist'):
-                assert np.array_equal(g[k], r[k]), at + (k,)
-            a = sol.actions()
-            assert np.array_equal(a, r['action']), at + ('action', np.flatnonzero((a != r['action']).any(axis=1))[:8])
-            nb = sol.neighbors()
-            valid = r['nbr_valid'].astype(bool)
-            assert np.array_equal(nb['nbr_valid'].astype(bool), valid), at + ('nbr_valid',)
-            assert np.array_equal(nb['nbr_n'][valid], r['nbr_n'][valid]), at + ('nbr_n', np.flatnonzero(valid & (nb['nbr_n'] != r['nbr_n']))[:8])
-            live = valid[:, None] & (col < r['nbr_n'][:, None])
-            for k in ('nbr_id', 'nbr_kind', 'nbr_dsq'):
-                differ = live & (nb[k] != r[k])
-                assert not differ.any(), at + (k, np.flatnonzero(differ.any(axis=1))[:8])
-            dg = sol.diag()
-            assert np.array_equal(dg['diag'][:, :2], r['diag'][:, :2]), at + ('n_suit / fallback', np.flatnonzero((dg['diag'][:, :2] != r['diag'][:, :2]).any(axis=1))[:8])
-            assert np.array_equal(dg['diag'][lp, 3:5], r['diag'][lp, 3:5]), at + ('planeFail / lp4',)
-            st = dg['status']
-            assert not (st & ~(OVERFLOW | 64 | 128)).any(), at + ('status bits', np.flatnonzero(st & ~(OVERFLOW | 64 | 128))[:8])
-            over, over_ref = (st & OVERFLOW) != 0, (r['status'] & OVERFLOW) != 0
-            assert not (over_ref & ~over).any(), at + ('overflow not reported', np.flatnonzero(over_ref & ~over)[:8])
-            collided_now = ((r['flags_policy'] & 2) != 0) & ((r['before'] & 2) == 0)
-            assert not (over & ~over_ref & ~collided_now).any(), at + ('spurious overflow', np.flatnonzero(over & ~over_ref & ~collided_now)[:8])
-            overflowed.append(int((over_ref & valid).sum()))
+            overflowed.append(compare_grid_step(sol, r, s, at))
             if paths is not None:
                 check_paths(sol, r, s, at)
     finally:
