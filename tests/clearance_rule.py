@@ -45,7 +45,10 @@ def step_minimum(pa, ra, a, pts, radii, skip_self):
     if skip_self:
         rough[a] = INF
     best, who, ties = INF, -1, 0
-    for b in np.flatnonzero(rough <= rough.min() + 2e-5):
+    known = rough[~np.isnan(rough)]                                # (a partner at a NaN position has a NaN c, which is below nothing: `c < best`)
+    if len(known) == 0:
+        return INF, -1, 0
+    for b in np.flatnonzero(rough <= known.min() + 2e-5):
         c = l3norm([float(x) for x in pa], [float(x) for x in pts[b]]) - float(rs[b])
         if c < best:
             best, who, ties = c, int(b), 1

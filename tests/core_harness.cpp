@@ -13,6 +13,42 @@
 
 using namespace sca;
 
+// ---- lp1 calls that took the parallel branch, counted HERE (tests/test_edge_corpus_cpu.py): sca_core.h has no counter.  lp3 / lp2 are
+// templates over the plane accessor; over this accessor their call of lp1 resolves (argument-dependent lookup prefers the non-template) to
+// the overload below, which walks the call's own loop once to see whether `denominator^2 <= RVO_EPS` was met before the loop ended, and
+// then returns what the real lp1 returns.
+namespace sca {
+struct CountedPlanes {
+    const Plane *p;
+    Plane operator[](int i) const { return p[i]; }
+};
+static int g_lp1_parallel_calls = 0;
+inline bool lp1(const CountedPlanes &pl, int planeNo, V3 lpnt, V3 ldir, double maxSpeed, V3 vpref, bool dir_opt, V3 &nv) {
+    const double dotProduct = dot(lpnt, ldir);
+    const double disc = dotProduct * dotProduct + maxSpeed * maxSpeed - dot(lpnt, lpnt);
+    if (!(disc < 0.0)) {
+        const double sq = sqrt(disc);
+        double tLeft = -dotProduct - sq, tRight = -dotProduct + sq;
+        bool met = false;
+        for (int i = 0; i < planeNo; i++) {
+            const Plane q = pl.p[i];
+            const double numerator = dot(q.p - lpnt, q.n), denominator = dot(ldir, q.n);
+            if (denominator * denominator <= RVO_EPS) {
+                met = true;
+                if (numerator > 0.0) break;
+                continue;
+            }
+            const double t = numerator / denominator;
+            if (denominator >= 0.0) { if (t > tLeft) tLeft = t; }
+            else { if (t < tRight) tRight = t; }
+            if (tLeft > tRight) break;
+        }
+        g_lp1_parallel_calls += met;
+    }
+    return lp1<const Plane *>(pl.p, planeNo, lpnt, ldir, maxSpeed, vpref, dir_opt, nv);
+}
+}  // namespace sca
+
 namespace {
 struct Tab { const double *unit; const double *phi; int num_N; double rad1; int vp_idx; };
 V3 cand_from_idx(const Tab &T, int idx, V3 vpref) {
@@ -182,6 +218,29 @@ int core_solve_agent(const double *par, int pol, int zaxis, double pref_speed, c
     cartesian2spherical(heading[0], heading[1], vpost, pol == POL_ORCA_LP, act);
     for (int k = 0; k < 7; k++) action[k] = (float)act[k];
     return st;
+}
+
+
+// The ORCA3D-LP agent's linearProgram3 over the planes of its recorded neighbours: how many of its lp1 calls took the parallel branch;
+// *plane_fail receives lp3's result (the caller checks it against the recording: the counted run is the recorded one).
+int core_lp1_parallel_calls(const double *par, const double *pos, const float *vel, double radius, const double *vpref, int K,
+                            const double *nb_pos, const float *nb_vel, const double *nb_rad, const uint8_t *nb_obst, int32_t *plane_fail) {
+    Params P{};
+    P.neighbor_dist = par[0]; P.time_step = par[1]; P.time_horizon = par[2]; P.max_speed = par[3];
+    const V3 pA = v3(pos[0], pos[1], pos[2]);
+    F3 vA{vel[0], vel[1], vel[2]};
+    Plane planes[K_MAX];
+    for (int j = 0; j < K; j++) {
+        V3 pB = v3(nb_pos[3 * j], nb_pos[3 * j + 1], nb_pos[3 * j + 2]);
+        F3 vB{nb_vel[3 * j], nb_vel[3 * j + 1], nb_vel[3 * j + 2]};
+        if (nb_obst[j]) vB = F3{0, 0, 0};
+        planes[j] = make_orca(P, pA, vA, radius, pB, vB, nb_rad[j], nb_obst[j] != 0).pl;
+    }
+    g_lp1_parallel_calls = 0;
+    V3 nv = v3(0, 0, 0);
+    CountedPlanes cp{planes};
+    *plane_fail = lp3(cp, K, P.max_speed, v3(vpref[0], vpref[1], vpref[2]), false, nv);
+    return g_lp1_parallel_calls;
 }
 
 }  // extern "C"

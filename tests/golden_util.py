@@ -13,6 +13,19 @@ def episode_fixtures():
                   if 'episode_log' not in p)       # F11_episode_log_*: different schema (tests/test_episode_log.py)
 
 
+def equal_for(name):
+    """How a fixture's arrays are compared with what is computed from them: np.array_equal -- and for the degenerate-geometry family (F20),
+    whose reference rows hold NaN where the reference's own arithmetic divides 0 by 0, NaN equals NaN at the same place and nothing else.
+    The one relaxation of that family, for every test that reads it."""
+    if name.startswith('F20_'):
+        return lambda a, b: np.array_equal(a, b, equal_nan=True)
+    return np.array_equal
+
+
+def edge_fixtures():
+    return [n for n in episode_fixtures() if n.startswith('F20_edge_')]
+
+
 def load(name):
     return dict(np.load(os.path.join(GOLDEN, name + '.npz'), allow_pickle=False))
 

@@ -83,28 +83,29 @@ def context_of(S, scene, per_agent=None, paths=None, state=True, perm=True):
     return sol
 
 
-def compare_with_oracle(sol, r, scene, at, rows=slice(None)):
+def compare_with_oracle(sol, r, scene, at, rows=slice(None), eq=np.array_equal):
     """what a context holds after a step against the oracle's record `r` of it: flags, step counts, the kd permutation, float32 velocities,
     positions, headings, travelled distance, the action rows, the neighbour lists entry for entry, the decisions' diagnostics.  rows: the
-    agents whose rows are compared (a shard; the permutation is the whole swarm's)"""
+    agents whose rows are compared (a shard; the permutation is the whole swarm's).  eq: how the floating-point arrays are compared --
+    np.array_equal; golden_util.equal_for of the degenerate-geometry family lets a NaN equal a NaN at the same place"""
     lp = (scene['policy'] == 4)[rows]
     g = sol.get_state()
     assert np.array_equal(g['flags'][rows], r['flags'][rows]), at + ('flags', np.flatnonzero(g['flags'][rows] != r['flags'][rows])[:8])
     assert np.array_equal(g['step_num'][rows], r['step_num'][rows]), at + ('step_num',)
     assert np.array_equal(sol.get_kd_perm(), r['perm']), at + ('perm',)
-    assert np.array_equal(g['vel'][rows], r['vel'][rows]), at + ('vel', np.flatnonzero((g['vel'][rows] != r['vel'][rows]).any(axis=1))[:8])
+    assert eq(g['vel'][rows], r['vel'][rows]), at + ('vel', np.flatnonzero((g['vel'][rows] != r['vel'][rows]).any(axis=1))[:8])
     for k in ('pos', 'heading', 'total_dist'):
-        assert np.array_equal(g[k][rows], r[k][rows]), at + (k,)
-    compare_pass_with_oracle(sol, r, at, lp, rows)
+        assert eq(g[k][rows], r[k][rows]), at + (k,)
+    compare_pass_with_oracle(sol, r, at, lp, rows, eq=eq)
 
 
-def compare_pass_with_oracle(sol, r, at, lp, rows=slice(None), ref_rows=None, id_base=(0, 0)):
+def compare_pass_with_oracle(sol, r, at, lp, rows=slice(None), ref_rows=None, id_base=(0, 0), eq=np.array_equal):
     """the policy pass's own results: action rows, neighbour lists, diagnostics (lp: the ORCA3D-LP agents among the rows).  rows: the
     context's rows that are compared, ref_rows: the record's (None: the same rows -- a shard; a scene of a batch is rows [lo, hi) of the
     context and the whole record of its own run, its ids in the lists global: id_base = (lo, the scene's first obstacle))"""
     rr = rows if ref_rows is None else ref_rows
     a = sol.actions()[rows]
-    assert np.array_equal(a, r['action'][rr]), at + ('action', np.flatnonzero((a != r['action'][rr]).any(axis=1))[:8])
+    assert eq(a, r['action'][rr]), at + ('action', np.flatnonzero((a != r['action'][rr]).any(axis=1))[:8])
     nb = {k: v[rows] for k, v in sol.neighbors().items()}
     nb['nbr_id'] = nb['nbr_id'] - np.where(nb['nbr_id'] >= 0, np.where(nb['nbr_kind'] == 1, id_base[1], id_base[0]), 0)
     valid = r['nbr_valid'][rr].astype(bool)

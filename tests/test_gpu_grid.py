@@ -9,7 +9,7 @@ bit.  The LP of orca3dPolicyOfficial.py walks the planes in list order: checked 
 import numpy as np
 import pytest
 
-from golden_util import episode_fixtures, fixture_agent_params, fixture_params, load, static_inputs
+from golden_util import episode_fixtures, equal_for, fixture_agent_params, fixture_params, load, static_inputs
 from test_gpu_parity import _scenario_state, make_solver
 
 pytestmark = pytest.mark.gpu
@@ -70,6 +70,7 @@ def test_grid_pass_vs_golden(S, name):
     maxn = fixture_agent_params(fx).get('max_neighbors', fixture_params(fx)[0].get('max_neighbors', 16))      # (F17: an array, one per agent)
     T = len(fx['step'])
     n_over = n_checked = 0
+    all_full = True                                                   # every list of every sampled step holds max_neighbors entries
     for t in range(0, T, max(1, T // 25)):
         sol.set_state(fx['pos'][t], fx['vel'][t], fx['heading'][t], fx['flags'][t], fx['total_dist'][t])
         sol.set_vpref(fx['vpref'][t], st['vpref_mode'])
@@ -98,12 +99,15 @@ def test_grid_pass_vs_golden(S, name):
         lp = st['policy'] == 4
         ok = called & ~over & (~lp | same_order(nb, fx['nbr_n'][t], fx['nbr_id'][t], fx['nbr_kind'][t]) | ~valid)
         a = sol.actions()
-        assert np.array_equal(a[ok, :4], fx['action'][t][ok, :4]), ctx + ('velocity',)
-        assert np.array_equal(a[ok, 4:], fx['action'][t][ok, 4:]), ctx
+        assert equal_for(name)(a[ok, :4], fx['action'][t][ok, :4]), ctx + ('velocity',)
+        assert equal_for(name)(a[ok, 4:], fx['action'][t][ok, 4:]), ctx
         flags = sol.get_state()['flags']
         assert np.array_equal((flags >> 1) & 1, fx['coll_after_policy'][t]), ctx + ('collision',)
         n_over += int((over & valid).sum()); n_checked += int(ok.sum())
-    assert n_checked > 0 or (n_over > 0 and np.min(maxn) < 16)      # F16 scenes with maxNeighbors = 1 .. 2: every list overflows
+        all_full = all_full and bool((fx['nbr_n'][t][valid] == np.broadcast_to(maxn, valid.shape)[valid]).all())
+    # F16 scenes with maxNeighbors = 1 .. 2: every list overflows; the F20 lattices: 26 and 63 agents in range of everybody, every list full
+    # (tests/test_gpu_edge_corpus.py compares their rows with the oracle of the grid's own rule)
+    assert n_checked > 0 or (n_over > 0 and (np.min(maxn) < 16 or all_full))
     sol.close()
 
 

@@ -39,14 +39,22 @@ def planned(H, simds, scene, part_on=0):
     return solve(H, scene['n'], simds=simds, part_on=part_on, nranks=1, lp=lp, lp_total=lp, t=(C.c_int * len(t))(*t.values()))
 
 
-def compare_grid_step(sol, r, scene, at, rows=None, list_rows=None, vpref=False):
+def compare_grid_step(sol, r, scene, at, rows=None, list_rows=None, vpref=False, nan_equal=False):
     """What a context holds after a resident step in SCA_NBR_GRID against the rule-1 oracle's record `r` of that step; failures name the
     agents.  rows: the ids of the agents whose state (flags, step counts, float32 velocities, positions, headings, travelled distance) and
     results (action rows, diagnostics, status words) are compared -- None: every agent; under the cell-owner partition the agents the rank owns
     AFTER the step (a migrant's results travelled with it).  list_rows: the ids whose neighbour lists are compared entry for entry in the
     grid's own order (None: `rows`; under the partition the agents the rank owned BEFORE the step: it ran the pass).  vpref: the v_pref the
-    pass used is compared too, on the served rows.  Returns how many of list_rows the oracle has overflowed."""
+    pass used is compared too, on the served rows.  Returns how many of list_rows the oracle has overflowed.  nan_equal: a NaN equals a NaN
+    at the same place (the degenerate-geometry family's one relaxation, golden_util.equal_for)."""
     rows = np.arange(scene['n']) if rows is None else np.asarray(rows, np.int64)
+
+    def ne(got, want):
+        d = got != want
+        if nan_equal and got.dtype.kind == 'f':
+            d &= ~(np.isnan(got) & np.isnan(want))
+        return d
+
     lrows = rows if list_rows is None else np.asarray(list_rows, np.int64)
 
     def same(bad, what, of=rows, got=None, want=None):
@@ -58,9 +66,9 @@ def compare_grid_step(sol, r, scene, at, rows=None, list_rows=None, vpref=False)
     g = sol.get_state()
     for k in ('flags', 'step_num', 'vel', 'pos', 'heading', 'total_dist'):
         got, want = g[k][rows], r[k][rows]
-        same((got != want).reshape(len(rows), got[0].size if len(rows) else 1).any(axis=1), k, got=got, want=want)
+        same(ne(got, want).reshape(len(rows), got[0].size if len(rows) else 1).any(axis=1), k, got=got, want=want)
     a = sol.actions()[rows]
-    same((a != r['action'][rows]).any(axis=1), 'action', got=a, want=r['action'][rows])
+    same(ne(a, r['action'][rows]).any(axis=1), 'action', got=a, want=r['action'][rows])
     nb = {k: v[lrows] for k, v in sol.neighbors().items()}
     valid, want_n = r['nbr_valid'][lrows].astype(bool), r['nbr_n'][lrows]
     same(nb['nbr_valid'].astype(bool) != valid, 'nbr_valid', lrows)

@@ -123,7 +123,7 @@ def test_reference_only_batch_every_scene_its_own_recorded_obstacles(S):
     """every free-running recorded episode in ONE context, each with its own recorded obstacles, from the start states, 331 steps (the longest
     record): every scene against every record it has of those steps, before and after the step; finished scenes inert; per-scene counters"""
     b = ObsBatch(S, reference_names())
-    assert b.B == 44 and int(b.obs_off[-1]) == sum(len(r) for _, r in b.obs) > 1491
+    assert b.B == 46 and int(b.obs_off[-1]) == sum(len(r) for _, r in b.obs) > 1491
     compared = b.run_and_check(331, label='reference batch')
     assert compared == b.records_up_to(331)
     assert compared >= 331 + 285 + 160                              # (F4_mixed_takeoff16 whole, F4_sca_takeoff16 whole, F10 whole, ...)

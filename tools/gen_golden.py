@@ -203,8 +203,9 @@ def _attr_arrays(agents):
 
 
 def run_env_episode(agent_mod, env_mod, classes, name, pos, goal, policy_ids, obstacles_spec, max_steps,
-                    record_every=1, record_first=0, radius=0.5, pref_speed=1.0, outdir='tests/golden', attrs=None):
-    """radius / pref_speed may be scalars or per-agent sequences; attrs: see _apply_attrs (recorded as attr_* arrays)."""
+                    record_every=1, record_first=0, radius=0.5, pref_speed=1.0, outdir='tests/golden', attrs=None, prepare=None):
+    """radius / pref_speed may be scalars or per-agent sequences; attrs: see _apply_attrs (recorded as attr_* arrays); prepare(agents): called
+    on the Agent objects before the env takes them (F20: float32 velocities and start flags set by hand)."""
     """Runs MACAEnv.step (mampenv.py:22) and records every `record_every`-th step (and the first
     `record_first` steps) completely."""
     global REC
@@ -216,6 +217,8 @@ def run_env_episode(agent_mod, env_mod, classes, name, pos, goal, policy_ids, ob
                               pref_speed=ps_l[i], policy=classes[int(policy_ids[i])], id=i, dt=0.1)
               for i in range(n)]
     _apply_attrs(agents, attrs)
+    if prepare is not None:
+        prepare(agents)
     obstacles = [Obstacle(pos=list(p), shape_dict={'shape': 'sphere', 'feature': r}, id=i)
                  for i, (p, r) in enumerate(obstacles_spec)]
     env = env_mod.MACAEnv()
@@ -243,35 +246,37 @@ def run_env_episode(agent_mod, env_mod, classes, name, pos, goal, policy_ids, ob
     env_mod.update_velocitie = upd
     t0 = time.time()
     done_step = -1
-    for step in range(max_steps):
-        want = (step < record_first) or (step % record_every == 0)
-        REC.reset()
-        first_upd[0] = True
-        pre = _snapshot(agents)
-        perm = np.array(env.kdTree.agentIDs, np.int32)
-        with contextlib.redirect_stdout(io.StringIO()):
-            done = env.step({})
-        post = _snapshot(agents)
-        if want:
-            rec['step'].append(step)
-            for k, v in zip(('pos', 'vel', 'heading', 'flags', 'total_dist', 'goal'), pre):
-                rec[k].append(v)
-            rec['perm'].append(perm)
-            for k in ('vpref', 'called', 'nbr_valid', 'nbr_n', 'nbr_id', 'nbr_kind', 'nbr_dsq', 'n_suit', 'fallback',
-                      'plane_fail', 'lp4', 'vpost'):
-                rec[k].append(getattr(REC, k).copy())
-            rec['action'].append(actions.copy())
-            rec['coll_after_policy'].append(coll_after.copy())
-            rec['pos_after'].append(post[0])
-            rec['vel_after'].append(post[1])
-            rec['heading_after'].append(post[2])
-            rec['flags_after'].append(post[3])
-            rec['total_dist_after'].append(post[4])
-            rec['perm_after'].append(np.array(env.kdTree.agentIDs, np.int32))
-        if done:
-            done_step = step
-            break
-    env_mod.update_velocitie = orig_upd
+    try:
+        for step in range(max_steps):
+            want = (step < record_first) or (step % record_every == 0)
+            REC.reset()
+            first_upd[0] = True
+            pre = _snapshot(agents)
+            perm = np.array(env.kdTree.agentIDs, np.int32)
+            with contextlib.redirect_stdout(io.StringIO()):
+                done = env.step({})
+            post = _snapshot(agents)
+            if want:
+                rec['step'].append(step)
+                for k, v in zip(('pos', 'vel', 'heading', 'flags', 'total_dist', 'goal'), pre):
+                    rec[k].append(v)
+                rec['perm'].append(perm)
+                for k in ('vpref', 'called', 'nbr_valid', 'nbr_n', 'nbr_id', 'nbr_kind', 'nbr_dsq', 'n_suit', 'fallback',
+                          'plane_fail', 'lp4', 'vpost'):
+                    rec[k].append(getattr(REC, k).copy())
+                rec['action'].append(actions.copy())
+                rec['coll_after_policy'].append(coll_after.copy())
+                rec['pos_after'].append(post[0])
+                rec['vel_after'].append(post[1])
+                rec['heading_after'].append(post[2])
+                rec['flags_after'].append(post[3])
+                rec['total_dist_after'].append(post[4])
+                rec['perm_after'].append(np.array(env.kdTree.agentIDs, np.int32))
+            if done:
+                done_step = step
+                break
+    finally:                                             # (a scene the reference raises on leaves the wrapper off too)
+        env_mod.update_velocitie = orig_upd
     out = {k: np.array(v) for k, v in rec.items()}
     out.update(dict(
         name=name, n_steps_run=step + 1, done_step=done_step,
@@ -457,6 +462,252 @@ def single_step_random(agent_mod, env_mod, classes, name, seed, outdir='tests/go
     print(f'{name}: n={n} m={m} side={side} called={int(REC.called.sum())} nbr_n max={REC.nbr_n.max()} '
           f'fallback={int((REC.fallback > 0).sum())} collisions={int(coll_after.sum())} lp4={int((REC.lp4 > 0).sum())} '
           f'{time.time() - t0:.1f} s', flush=True)
+
+
+def edge_steps(agent_mod, env_mod, classes, name, pos, goal, heading, vel, radius, pref_speed, policy, flags, obstacles, steps=1,
+               outdir='tests/golden'):
+    """Degenerate-geometry fixtures (F20): a scene given by explicit arrays -- positions [n, 3], goals [n, 3], headings [n, 3], float32
+    velocities [n, 3], radii, preferred speeds, policies, start flags (1 at goal, 2 collided, 4 timed out) and obstacles [(pos, radius)] --
+    and `steps` env.step of the reference, recorded completely under single_step_random's keys (one row per step)."""
+    n = len(pos)
+    pos6 = [[float(x) for x in pos[i]] + [float(x) for x in heading[i]] for i in range(n)]
+    goal6 = [[float(x) for x in goal[i]] + [0.0, 0.0, 0.0] for i in range(n)]
+    vel32 = np.asarray(vel, np.float32).reshape(n, 3)
+
+    def prepare(agents):
+        for a in agents:
+            a.vel_global_frame = vel32[a.id].copy()
+            a.is_at_goal, a.is_collision, a.is_out_of_max_time = bool(flags[a.id] & 1), bool(flags[a.id] & 2), bool(flags[a.id] & 4)
+    with np.errstate(all='ignore'):                        # 0 / 0 and x / 0 in numpy scalars are the point of these scenes: nan / inf, no raise
+        return run_env_episode(agent_mod, env_mod, classes, name, pos6, goal6, [int(p) for p in policy], list(obstacles), steps,
+                               radius=[float(r) for r in radius], pref_speed=[float(p) for p in pref_speed], outdir=outdir, prepare=prepare)
+
+
+class EdgeScene:
+    """The arrays of one F20 scene, filled agent by agent.  `o` is the origin the next agents are placed from, `pid` their policy."""
+
+    def __init__(self):
+        self.pos, self.goal, self.head, self.vel, self.rad, self.ps, self.pol, self.fl, self.obs = [], [], [], [], [], [], [], [], []
+        self.o = np.zeros(3)
+        self.pid = 0
+
+    def add(self, p, g=None, v=(0.0, 0.0, 0.0), r=0.5, ps=1.0, fl=0, h=None):
+        """an agent at o + p with goal o + g (None: 30 m further along its velocity, or its own position when at rest), heading along the
+        velocity unless given"""
+        p, v = np.asarray(p, np.float64), np.asarray(v, np.float64)
+        sp = float(np.linalg.norm(v))
+        if g is None:
+            g = p + (30.0 * v / sp if sp > 0 else 0.0)
+        if h is None:
+            h = [math.atan2(v[1], v[0]), math.atan2(v[2], math.hypot(v[0], v[1])), 0.0] if sp > 0 else [0.0, 0.0, 0.0]
+        q = self.o + p
+        q[self.o == 0.0] = p[self.o == 0.0]                  # (keeps a -0.0 coordinate what it is)
+        self.pos.append(q)
+        self.goal.append(self.o + np.asarray(g, np.float64))
+        self.head.append(h)
+        self.vel.append(v)
+        self.rad.append(r)
+        self.ps.append(ps)
+        self.pol.append(self.pid)
+        self.fl.append(fl)
+
+    def obstacle(self, p, r):
+        self.obs.append(([float(x) for x in self.o + np.asarray(p, np.float64)], float(r)))
+
+    def each_policy(self, build, policies=range(6), base=(0.0, 0.0, 20.0), shift=(0.0, 0.0, 0.0), stack='y'):
+        """build(self) once per policy, the copies 400 m apart along `stack`: y for the geometries that lie in an x-z plane or on integers, z
+        for the rings in an x-y plane -- the offset then changes no difference of coordinates"""
+        for k, pid in enumerate(policies):
+            self.pid = pid
+            self.o = np.asarray(base, np.float64) + np.asarray(shift, np.float64) + 400.0 * k * np.array([0.0, stack == 'y', stack == 'z'], np.float64)
+            build(self)
+        return self
+
+
+# pair axis -> (its unit vector, the axis the clusters of a scene are spread along).  The pair axis' own base coordinate is 0 in every cluster
+# and copy: 0 + d is d, any other base would round the separation (20 + 1.1 - 20 is not 1.1)
+EDGE_AXES = {'x': (np.array([1.0, 0.0, 0.0]), np.array([0.0, 0.0, 1.0])), 'z': (np.array([0.0, 0.0, 1.0]), np.array([1.0, 0.0, 0.0]))}
+ON_GROUND = (0.0, 0.0, 0.0)                                # each_policy(base=...) of the pairs on the z axis: the lower agent at z = 0
+GRID_CELL = math.sqrt(10.0 * 10.0 + 1.0e-5) * (1.0 + 1.0e-9)          # the hashed grid's cell at neighborDist 10 (1 / grid_inv_cell(10))
+FAR_SHIFTS = {'far1e6': (1.0e6, -3.0e6, 0.0), 'farwrap': (float(math.ceil(2 ** 21 * GRID_CELL)), 0.0, 0.0)}    # (an integer: lattices stay exact)
+
+
+def _ulps(x):
+    return (x, float(np.nextafter(x, np.inf)), float(np.nextafter(x, -np.inf)))
+
+
+UNTRACKED = (POL_RVO, POL_SRVO, POL_ORCA, POL_ORCA_LP)
+
+
+def edge_scenes():
+    """name -> (EdgeScene, steps).  Clusters of one scene are 50 m apart (neighborDist is 10), the per-policy copies 400 m.
+
+    Left out because the reference raises (the scene, or the policy's copy of it, exists nowhere else either):
+      * SCA / RVO3D+Dubins agents whose start pitch or climb the Dubins planner cannot serve -- a goal straight above or below the start, a
+        start heading steeper than pitchlims: `while len(fb) < 2: b *= 2.0` (dubinsmaneuver3d.py:76-78) doubles the radius until
+        `horizontal_radius ** 2` raises OverflowError (34, 'Numerical result out of range') at dubinsmaneuver3d.py:146.  The pairs on the z
+        axis of the far family and the is_zAxis agents of `on_things` therefore carry the four untracked policies only.
+      * SCA / RVO3D+Dubins agents on their goal or 0.2 m from it: the planned path has 1 / 3 points, dubins_path_node_pop takes up to four and
+        scaPolicy.py:278 raises IndexError('pop from empty list').  Untracked policies only in `on_things`.
+      * pref_speed 0, anywhere: Agent.__init__ divides by it, ZeroDivisionError('float division by zero') at agent.py:52.  The pairs that have
+        to stay where they are through a step are at rest with parallel goals instead (both take 0.3 * v_pref, the same vector), or sit on
+        their own goal.
+      * the ORCA3D copies of the rings of 8 and of 16: with v_dif exactly along pAB the cosine rounds to 1.0000000000000002 and
+        orca3dPolicy.py:321 `acos(...)` raises ValueError('math domain error') in the fallback sweep.  The rings hold the other five."""
+    out = {}
+    names = ('sca', 'rvo', 'srvo', 'orca', 'orcalp', 'rvodubins')
+    X = np.array([1.0, 0.0, 0.0])
+
+    # ---- coincident: relPos == 0 (w / wLength with w == 0 when relVel == 0 too), distSq 0 < (rA + rB)^2: a collision inside the policy pass
+    def coincident_a(s):
+        s.add((0, 0, 0), v=(-0.5, 0, 0)); s.add((0, 0, 0), v=(0.5, 0, 0))                       # moving apart
+        s.add((50, 0, 0), v=(0.5, 0, 0)); s.add((50, 0, 0), v=(0.4, 0, 0.3))                    # crossing
+        s.add((100, 0, 0), g=(130, 0, 0)); s.add((100, 0, 0), g=(70, 0, 0))                     # at rest (bootstrap branch)
+
+    def coincident_b(s):
+        s.add((0, 0, 0), v=(0.5, 0, 0)); s.add((0, 0, 0), v=(0.5, 0, 0))                        # relVel == 0 and relPos == 0 together
+        s.add((50, 0, 0), v=(0.5, 0, 0), r=0.3); s.add((50, 0, 0), v=(-0.4, 0, 0.3), r=0.5); s.add((50, 0, 0), v=(0.4, 0, -0.3), r=1.0)
+    out['coincident_a'] = (EdgeScene().each_policy(coincident_a), 1)
+    out['coincident_b'] = (EdgeScene().each_policy(coincident_b), 1)
+
+    # ---- touching: pairs on one axis at exactly rA + rB (mampenv.py:71 `<=`; at rest with parallel goals they keep their distance) and at exactly
+    # (rA + 0.05) + (rB + 0.05) (util.py:33 `dist_pAB <= combined_radius`, the ORCA `distSq > RSq`), and one ulp either side of both
+    def touching_env(axis):
+        e, w = EDGE_AXES[axis]
+
+        def build(s):
+            for k, d in enumerate(_ulps(0.5 + 0.5) + (0.5 + 0.5 + 1e-5, 0.3 + 1.0)):
+                ra, rb = (0.3, 1.0) if k == 4 else (0.5, 0.5)
+                s.add(50.0 * k * w, r=ra, g=50.0 * k * w + 30.0 * X)
+                s.add(50.0 * k * w + d * e, r=rb, g=50.0 * k * w + d * e + 30.0 * X)
+        return build
+
+    def touching_cone(axis):
+        e, w = EDGE_AXES[axis]
+
+        def build(s):
+            cases = [(d, 0.5, 0.5) for d in _ulps((0.5 + 0.05) + (0.5 + 0.05))] + [(0.5 + 0.5, 0.5, 0.5), ((1.0 + 0.05) + (0.3 + 0.05), 0.3, 1.0)]
+            for k, (d, ra, rb) in enumerate(cases):
+                s.add(50.0 * k * w, v=0.5 * e, r=ra)
+                s.add(50.0 * k * w + d * e, v=-0.5 * e, r=rb)
+        return build
+    out['touching_env'] = (EdgeScene().each_policy(touching_env('x')), 4)
+    out['touching_cone'] = (EdgeScene().each_policy(touching_cone('x')), 4)
+
+    def touching_obs(s):
+        for k, d in enumerate(_ulps(0.5 + 1.0)):                                                # the env's agent-obstacle `<=`: at rest on its goal
+            if s.pid in UNTRACKED:
+                s.add((0, 0, 50.0 * k))
+                s.obstacle((d, 0, 50.0 * k), 1.0)
+        for k, d in enumerate(_ulps((1.0 + 0.05) + (0.5 + 0.05)), 3):                           # the cone / the plane at d == R, heading for it
+            s.add((0, 0, 50.0 * k), v=(0.5, 0, 0))
+            s.obstacle((d, 0, 50.0 * k), 1.0)
+    for k, tag in enumerate('abc'):
+        out['touching_obs_' + tag] = (EdgeScene().each_policy(touching_obs, policies=(2 * k, 2 * k + 1)), 1)
+
+    # ---- lattices: integer coordinates, equal velocities -- 6 / 12 / 8 neighbours at equal distSq, 63 in range in the 4x4x4 (ties at the
+    # cut of 16); spacing exactly neighborDist: distSq == rangeSq, nobody in range (`distSq < rangeSq`)
+    def lattice(nx, ny, nz, spacing, v=(0.5, 0.0, 0.0), mixed=False):
+        def build(s):
+            i = 0
+            for a in range(nx):
+                for b in range(ny):
+                    for c in range(nz):
+                        if mixed:
+                            s.pid = i % 6
+                        s.add((spacing * a, spacing * b, spacing * c), v=v)
+                        i += 1
+        return build
+    for k, tag in enumerate('abc'):
+        out['lattice3_s2_' + tag] = (EdgeScene().each_policy(lattice(3, 3, 3, 2.0), policies=(2 * k, 2 * k + 1)), 6)
+    for pid in range(6):
+        out['lattice4_s2_' + names[pid]] = (EdgeScene().each_policy(lattice(4, 4, 4, 2.0), policies=(pid,)), 4 if pid in (POL_SRVO, POL_ORCA_LP) else 1)
+    out['lattice4_s10_mixed'] = (EdgeScene().each_policy(lattice(4, 4, 4, 10.0, mixed=True), policies=(0,)), 1)
+    out['lattice_plane_mixed'] = (EdgeScene().each_policy(lattice(6, 6, 1, 2.0, mixed=True), policies=(0,)), 4)      # z = const: degenerate kd splits
+    out['lattice_line'] = (EdgeScene().each_policy(lattice(10, 1, 1, 1.5)), 4)
+    out['lattice_ground_mixed'] = (EdgeScene().each_policy(lattice(6, 6, 1, 2.0, v=(0.5, 0.0, -0.25), mixed=True), policies=(0,), base=(0.0, 0.0, 0.0)), 4)   # next_z >= 0
+
+    # ---- on things
+    def on_things(s):
+        s.add((0, 0, 0), v=(0.5, 0, 0)); s.obstacle((0, 0, 0), 1.0)                             # at an obstacle's centre
+        if s.pid in UNTRACKED:
+            s.add((50, 0, 0), g=(50, 0, 0), v=(0.5, 0, 0))                                      # exactly on its goal, moving
+            s.add((100, 0, 0), g=(100.2, 0, 0), v=(0.5, 0, 0))                                  # 0.2 m from it (util.reached `<`)
+            s.add((0, 0, 100), g=(1e-5, 0, 110), v=(0, 0, 0.5))                                 # is_zAxis threshold, at it (x itself is 0)
+            s.add((0, 0, 200), g=(float(np.nextafter(1e-5, 1.0)), 0, 210), v=(0, 0, 0.5))       # ... and one ulp above it
+    out['on_things'] = (EdgeScene().each_policy(on_things), 1)
+
+    # ---- mirror: head-on on an axis with v_pref exactly along pAB (candidates with dt * |dt| == g * n2), exactly symmetric rings in an x-y plane
+    def head_on(axis):
+        e, w = EDGE_AXES[axis]
+
+        def build(s):
+            for k, d in enumerate((2.0, 3.0, 8.0)):
+                s.add(50.0 * k * w, v=0.5 * e, g=50.0 * k * w + 32.0 * e)
+                s.add(50.0 * k * w + d * e, v=-0.5 * e, g=50.0 * k * w + (d - 32.0) * e if axis == 'x' else 50.0 * k * w)
+        return build
+
+    def ring(m, rad):
+        def build(s):
+            s.add((0, 0, 0), g=(8, 0, 0))                                                       # at rest in the middle
+            for j in range(m):
+                # the four quadrants from one octant's sines and cosines: exactly symmetric
+                q, t = divmod(j, m // 4)
+                c, sn = rad * math.cos(2 * math.pi * t / m), rad * math.sin(2 * math.pi * t / m)
+                x, y = [(c, sn), (-sn, c), (-c, -sn), (sn, -c)][q]
+                s.add((x, y, 0), v=(-0.125 * x, -0.125 * y, 0), g=(-x, -y, 0))
+        return build
+    out['mirror_head_on'] = (EdgeScene().each_policy(head_on('x')), 6)
+    out['mirror_ring8'] = (EdgeScene().each_policy(ring(8, 4.0), policies=(POL_SCA, POL_RVO, POL_SRVO, POL_ORCA_LP, POL_RVO_DUBINS), stack='z'), 4)
+    out['mirror_ring16_a'] = (EdgeScene().each_policy(ring(16, 4.0), policies=(POL_SCA, POL_RVO, POL_SRVO), stack='z'), 4)
+    # (one step: linearProgram4 among exactly parallel planes gives the four ORCA3D-LP agents on the axes a NaN action row, which the family
+    # keeps -- and with a NaN position the next step raises at orca3dPolicyOfficial.py:350, int(nan))
+    out['mirror_ring16_b'] = (EdgeScene().each_policy(ring(16, 4.0), policies=(POL_ORCA_LP, POL_RVO_DUBINS), stack='z'), 1)
+
+    # ---- parallel planes (ORCA3D-LP): equal and exactly opposite normals, a box of 6 closer than R (LP3 fails: LP4 among parallel planes),
+    # maxSpeed reached exactly
+    def parallel(s):
+        s.add((0, 0, 0), v=(0, 0, 0.5)); s.add((-2, 0, 0), v=(0, 0, 0.5)); s.add((2, 0, 0), v=(0, 0, 0.5))          # opposite normals
+        s.add((50, 0, 0), v=(0.5, 0, 0)); s.add((52, 0, 0), v=(0.5, 0, 0)); s.add((54, 0, 0), v=(0.5, 0, 0))       # collinear: equal normals
+        s.add((100, 0, 0), v=(0.5, 0, 0))                                                                          # the box
+        for d in ((1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1)):
+            s.add(100.0 * X + 0.875 * np.array(d, np.float64), v=tuple(-0.5 * x for x in d))
+        s.add((150, 0, 0), v=(1.0, 0, 0), g=(250, 0, 0)); s.add((153, 0, 0), v=(-1.0, 0, 0), g=(53, 0, 0))        # |v_pref| == maxSpeed
+        s.add((200, 0, 0), v=(0.6, 0, 0.8), g=(260, 0, 80))                                                       # ... alone
+    out['parallel_orcalp'] = (EdgeScene().each_policy(parallel, policies=(POL_ORCA_LP,)), 4)
+
+    # ---- a candidate exactly on a boundary.  cone_edge (RVO3D, S-RVO3D): B at (R, 0, e) from A with e^2 = 0.6 ulp(R^2), so that
+    # |pAB| == R by the square root while dot(pAB, pAB) is one ulp above R * R -- `dist_pAB <= combined_radius` (util.py:33) makes the
+    # bound asin(1); v_pref is straight up, 1e-8 rad inside it, and with vA + vB == 0 it is its own v_dif: hit.  Read `<` for `<=` and the
+    # cone's half-angle falls 1e-8 short of it.  on_plane (ORCA3D): two overlapping agents of equal velocity, every term a short binary
+    # fraction (radius 0.5125: R = 1.125, w = 10, u = 1.25), the plane at x = 1.125 with normal +x and v_pref = (1.125, 0, 0) exactly on it:
+    # `>= 0.0` of is_inORCA (orca3dPolicy.py:330) at equality.
+    def cone_edge(s):
+        R_ = (0.5 + 0.05) + (0.5 + 0.05)
+        e_ = math.sqrt(0.6 * float(np.spacing(R_ * R_)))
+        s.add((0, 0, 20), v=(0, 0, 0.5), g=(0, 0, 50))
+        s.add((R_, 0, 20 + e_), v=(0, 0, -0.5), g=(R_, 0, e_ - 10))
+    out['cone_edge'] = (EdgeScene().each_policy(cone_edge, policies=(POL_RVO, POL_SRVO)), 1)
+
+    def on_plane(s):
+        s.add((0, 0, 0), v=(0.5, 0, 0), g=(30, 0, 0), r=0.5125, ps=1.12501)
+        s.add((-1, 0, 0), v=(0.5, 0, 0), g=(29, 0, 0), r=0.5125)
+    out['on_plane_orca'] = (EdgeScene().each_policy(on_plane, policies=(POL_ORCA,)), 1)
+
+    # ---- far from the origin: the same geometries 1e6 / 3e6 m out and one key wrap of the hashed grid out (21 bits per axis); the pairs
+    # on the z axis there, which the shift leaves alone, the lower agent on the ground (z = 0)
+    for tag, sh in FAR_SHIFTS.items():
+        out[tag + '_touching_env'] = (EdgeScene().each_policy(touching_env('z'), policies=UNTRACKED, base=ON_GROUND, shift=sh), 2)
+        out[tag + '_touching_cone'] = (EdgeScene().each_policy(touching_cone('z'), policies=UNTRACKED, base=ON_GROUND, shift=sh), 4)
+        out[tag + '_lattice3_mixed'] = (EdgeScene().each_policy(lattice(3, 3, 3, 2.0, mixed=True), policies=(0,), shift=sh), 4)
+        out[tag + '_head_on'] = (EdgeScene().each_policy(head_on('z'), policies=UNTRACKED, base=ON_GROUND, shift=sh), 4)
+
+    # ---- straddling zero within one cell: -1e-9, +0.0 and -0.0 as coordinates
+    def straddle(s):
+        for k, (x0, x1) in enumerate(((-1e-9, 0.0), (-0.0, 0.0), (-1e-9, 2.0), (-2.0, -0.0))):
+            s.add((x0, 0, 50.0 * k), v=(0.5, 0, 0)); s.add((x1 + 2.0, 0, 50.0 * k), v=(-0.5, 0, 0))
+    out['straddle_zero'] = (EdgeScene().each_policy(straddle), 2)
+    return out
 
 
 def kat_tables(outdir='tests/golden'):
@@ -901,6 +1152,17 @@ def main():
         pol = [int(x) for x in rng.choice([POL_SCA, POL_SCA, POL_RVO_DUBINS, POL_ORCA_LP, POL_RVO], n)]
         run_env_episode(agent_mod, env_mod, classes, 'F18_hetero_track_mixed36', pos, goal, pol, [([1.0, 0.0, 12.0], 0.8)], 30, radius=rng.choice([0.3, 0.5], n),
                         outdir=od, attrs=_hetero_track(1804, True))
+    # F20: degenerate geometry placed by hand -- the inputs at which the arithmetic branches on an equality or divides by something that can
+    # be zero, which no continuous random draw produces (edge_scenes)
+    if args.only is None or any(o.startswith('F20') for o in args.only):
+        for nm, (sc, steps) in edge_scenes().items():
+            if want('F20_edge_' + nm):
+                try:
+                    edge_steps(agent_mod, env_mod, classes, 'F20_edge_' + nm, sc.pos, sc.goal, sc.head, sc.vel, sc.rad, sc.ps, sc.pol, sc.fl, sc.obs,
+                               steps=steps, outdir=od)
+                except Exception as e:                                         # a scene the reference raises on is not part of the family
+                    import traceback
+                    print('F20_edge_' + nm, 'RAISED', repr(e), traceback.extract_tb(e.__traceback__)[-1], flush=True)
     # F6: ORCA-official N=100 circle, long run, every 10th step (LP4 coverage)
     if want('F6_orcalp_circle100_long'):
         pos, goal, _ = ro.set_circle_pos(100)
