@@ -6,6 +6,7 @@ log files -- only the imports differ (sca_amd.env instead of mamp.*).
     python examples/run_sca.py --scenario takeoff  # exp2: take-off / landing
     python examples/run_sca.py --scenario exp3 --map tests/golden/exp3_map.binvox   # low-altitude search among 1491 spheres
     python examples/run_sca.py --scenario circle --agents 2000 --no-obstacles --policy orca
+    python examples/run_sca.py --clearance --margin 0.2   # ... and how close the drones came (sca_clearance_enable)
 """
 import argparse
 import math
@@ -43,6 +44,9 @@ def main():
     ap.add_argument('--tracker', default='host', choices=['host', 'device'],
                     help='where the Dubins v_pref tracker of SCA / RVO3D+Dubins runs: host = native threads, bit-exact against '
                          'the reference; device = kernels inside every step (large swarms)')
+    ap.add_argument('--clearance', action='store_true',
+                    help='keep every drone\'s closest approach to another drone and to an obstacle with the step, and print the minima')
+    ap.add_argument('--margin', type=float, default=0.0, help='with --clearance: a drone whose smaller clearance is <= this counts as a near miss')
     args = ap.parse_args()
 
     n = args.agents
@@ -70,7 +74,7 @@ def main():
     dubins = pol in (E.SCAPolicy, E.RVO3dDubinsPolicy)          # these two follow a Dubins path (scaPolicy.py:264-338)
     if dubins and args.tracker == 'host':
         v_pref_fn = tracker.DubinsTracker(sc['goal'][:, :3], sc['goal'][:, 3:6], np.ones(n), S.zaxis_flags(sc['start'], sc['goal']))
-    env = E.MACAEnv(v_pref_fn=v_pref_fn, history_capacity=args.max_steps, device_tracker=dubins and args.tracker == 'device')
+    env = E.MACAEnv(v_pref_fn=v_pref_fn, history_capacity=args.max_steps, device_tracker=dubins and args.tracker == 'device', clearance=args.clearance)
     env.set_agents(agents, obstacles=obstacles)
 
     step, t0 = 0, time.time()
@@ -84,6 +88,12 @@ def main():
     paths = metrics.write_episode_log(env, args.log_dir)                  # AverageCost from agent.total_time, as run_sca.py:241-250
     info = metrics.episode_metrics(env)
     print({k: info[k] for k in ('SuccessRate', 'ExtraTime', 'ExtraDistance', 'AverageSpeed', 'AverageCost')})
+    if args.clearance:
+        cm = metrics.clearance_metrics(env, args.margin)
+        print({'MinClearance': cm['MinClearance'], 'MinClearancePair': cm['MinClearancePair'], 'MinClearanceStep': cm['MinClearanceStep'],
+               'MinObstacleClearance': cm['MinObstacleClearance'], 'MinObstacleClearanceAgent': cm['MinObstacleClearanceAgent'],
+               'MinObstacleClearanceObstacle': cm['MinObstacleClearanceObstacle'], 'MinObstacleClearanceStep': cm['MinObstacleClearanceStep'],
+               'NearMisses': len(cm['NearMisses'])})
     print('wrote', ', '.join(sorted(paths.values())))
 
 

@@ -602,6 +602,38 @@ typedef struct sca_scene_clearance {     /* 32 bytes */
 int sca_scene_clearance_enable(sca_ctx *ctx, int on);
 int sca_get_scene_clearance(sca_ctx *ctx, int scene, sca_scene_clearance *out /*size[scene]*/, int32_t struct_bytes);
 
+/* Closest approach per agent for a WHOLE CONTEXT, by kd-tree descent.  The scene feature above is all-pairs inside a scene of at most 1536
+ * agents; a plain context of any size -- the 100 000-agent circle, the take-off / landing field, the drop-in env loop -- keeps the same
+ * 32-byte record per agent with one more kernel per step (k_clearance, a wavefront per agent, in front of the step's last kernel, only
+ * while the feature is on): a nearest-partner search with a shrinking radius on the trees the step already has.
+ *   the rule   the scene rule with the context as the one "scene".  Row a is updated at every step that a ENTERED unfinished (none of
+ *              at-goal / collision / timed-out in its entry flags; the step in which it gains a flag still counts).  For every other agent
+ *              b, whatever its flags, c = l3norm(p_a, p_b) - (r_a + r_b): p the positions the step moved to, l3norm the reference's rounded
+ *              norm, the radius sum formed first.  The step's candidate is the smallest c, the lowest b on equal values; it replaces the
+ *              record only if strictly smaller, so the earliest step wins ties.  The same over the obstacles in set order.
+ *   the record partners are context-global agent ids and obstacle indices; `step` counts the context's env updates since the enable call,
+ *              1-based.  An empty half is +inf, -1, 0.
+ *   the bound  the agent tree holds the positions the step BEGAN with, the rule is over the moved ones: a child whose box lies at dist from
+ *              the agent's moved position cannot give less than dist - max_step - r_a - max_radius - 1e-4 (max_step and max_radius as in
+ *              the collision test's reach; the 1e-4 covers the 5-decimal rounding); the obstacle tree is static: dist - r_a -
+ *              max_obs_radius - 1e-4.  A child is skipped only where that bound is strictly above the best value so far, and the best
+ *              value starts at the row's own record: a step in which nobody can beat the record ends at the root.
+ *   step forms sca_env_step, sca_run_steps, sca_policy_pass + sca_env_update, sca_step_host; SCA_NBR_KDTREE, SCA_NBR_AUTO and
+ *              SCA_NBR_KDTREE_HOSTBUILD; the device tracker, per-agent attributes, waypoint lists.  A context without the feature enqueues
+ *              exactly what it did.  While it is on, SCA_NBR_AUTO builds no tree ahead of the next pass inside sca_run_steps.
+ *   sca_clearance_enable   on != 0: allocates n x 32 bytes, every row empty; records cover the steps from then on (enabling again starts
+ *              over).  on == 0 frees.  SCA_ERR_STATE: no agents or no state yet, or between a policy pass and its env update.
+ *              SCA_ERR_UNSUPPORTED, the message names the reason: scenes are set, a shard with count < n, a communicator, the cell-owner
+ *              partition.
+ *   sca_get_clearance      rows agent_begin .. agent_begin + agent_count - 1, one copy and one synchronisation.  SCA_ERR_STATE: not
+ *              enabled.  SCA_ERR_ARG: a range outside 0 .. n, a NULL out, struct_bytes other than sizeof(sca_scene_clearance).
+ *   while on   SCA_ERR_UNSUPPORTED, before anything is enqueued: a pass or step in SCA_NBR_GRID mode and an env update without a policy
+ *              pass in front of it (neither has an agent tree of this step); a shard with count < n, a communicator, the cell-owner
+ *              partition and scenes, each at its own entry point.  A new agent set drops the records; a new state leaves them alone.
+ * Detect the feature by the symbol (the version number is unchanged). */
+int sca_clearance_enable(sca_ctx *ctx, int on);
+int sca_get_clearance(sca_ctx *ctx, int agent_begin, int agent_count, sca_scene_clearance *out /*agent_count*/, int32_t struct_bytes);
+
 /* the hot path ----------------------------------------------------------------------------------- */
 int sca_policy_pass(sca_ctx *ctx, int neighbor_mode);
 int sca_get_actions(sca_ctx *ctx, float *action /*n*7*/);

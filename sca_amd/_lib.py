@@ -123,6 +123,8 @@ SIGNATURES = {
     'sca_load_scenes': (C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     'sca_scene_clearance_enable': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_get_scene_clearance': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SceneClearance), C.c_int32]),
+    'sca_clearance_enable': (C.c_int, [C.c_void_p, C.c_int]),
+    'sca_get_clearance': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(SceneClearance), C.c_int32]),
     'sca_set_path_state': (C.c_int, [C.c_void_p, ip, dp]),
     'sca_policy_pass': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_get_actions': (C.c_int, [C.c_void_p, fp]),

@@ -26,6 +26,8 @@
 #include "sca_forms.h"
 #include "sca_scenes.h"
 #include "sca_scenes.hip.h"
+#include "sca_clearance.h"
+#include "sca_clearance.hip.h"
 
 using namespace sca;
 
@@ -206,6 +208,8 @@ struct sca_ctx {
     bool agents_set = false, state_set = false;
     bool state_fresh = false;           // flags came from sca_set_state: the next env update checks arrived agents against obstacles once
     bool near_valid = false;            // K1's collision-candidate lists describe the current records
+    sca_scene_clearance *clear = nullptr;   // [n] the closest-approach records of the whole context (sca_clearance_enable), null: off -- a step then enqueues nothing for them
+    int32_t clear_step = 0;             // env updates enqueued since the enable call: k_clearance's step number
     double max_radius = 0, max_obs_radius = 0, max_pref_speed = 0;
     std::string err;
     double *tab = nullptr;
@@ -382,6 +386,9 @@ static int dalloc(sca_ctx *c, T **p, size_t count) {
 // pass leaves the tree build and the kd query of the listed agents there, and the next pass copes with that by itself, as inside a burst of
 // sca_run_steps.  Every OTHER entry point joins first: it may read the tree, the permutation or the lists, or enqueue work that does.
 static int auto_join(sca_ctx *c);
+static int clearance_drop(sca_ctx *c);
+static ClearanceState clearance_state(const sca_ctx *c);
+static int clearance_refuse(sca_ctx *c, const char *who, ClearanceFault f);
 static int api_enter(sca_ctx *c);
 #define API_ENTER(ctx)                                                                          \
     do {                                                                                       \
@@ -936,6 +943,7 @@ void sca_destroy(sca_ctx *c) {
     (void)part_free(c);
     for (void *p : {(void *)c->path.off, (void *)c->path.pts, (void *)c->path.rem, (void *)c->path.now_goal, (void *)c->pslot_pts, (void *)c->pslot_len}) if (p) (void)hipFree(p);
     c->scenes.release();
+    if (c->clear) { (void)hipFree(c->clear); c->clear = nullptr; }
     if (c->h_done) { (void)hipHostFree(c->h_done); c->h_done = nullptr; }
     if (c->hs_host) { (void)hipHostFree(c->hs_host); c->hs_host = nullptr; }
     if (c->hs_dev) { (void)hipFree(c->hs_dev); c->hs_dev = nullptr; }
@@ -1101,6 +1109,7 @@ int sca_set_agents(sca_ctx *c, int n, const double *radius, const double *pref_s
     if (int r = part_free(c)) return r;                               // ... and so do the partition's lists
     if (int r = paths_clear(c, false)) return r;                      // ... and so do the waypoint lists (vpref_mode is reset below)
     if (int r = scenes_clear(c)) return r;                            // ... and so do the scenes
+    if (int r = clearance_drop(c)) return r;                          // ... and so do the closest-approach records
     if (c->comm && n % c->comm_nranks) { c->err = "agent count must be a multiple of the communicator's rank count"; return SCA_ERR_ARG; }
     c->n = n; c->d.n = n; c->d.shard_begin = 0; c->d.shard_count = n;
     if (c->comm) { c->d.shard_count = n / c->comm_nranks; c->d.shard_begin = c->comm_rank * c->d.shard_count; }
@@ -1509,6 +1518,7 @@ int sca_set_scenes(sca_ctx *c, int nscenes, const int32_t *offsets) {
         return scenes_error_code(k.fault);
     }
     if (k.fault == SCENES_NONE) return scenes_clear(c);
+    if (int r = clearance_refuse(c, "sca_set_scenes", clearance_check(CLR_SET_SCENES, clearance_state(c), 0, 0, true, 0))) return r;
     if (c->comm) { c->err = "sca_set_scenes with an active communicator (sca_comm_init): scenes are one rank's"; return SCA_ERR_UNSUPPORTED; }
     if (c->part_on) { c->err = "sca_set_scenes under the cell-owner partition (sca_partition_init): a mode of SCA_NBR_GRID, which has no scene form"; return SCA_ERR_UNSUPPORTED; }
     if (c->d.shard_begin != 0 || c->d.shard_count != n) { c->err = "sca_set_scenes on a shard (sca_set_shard): scenes are stepped by one rank, whole"; return SCA_ERR_UNSUPPORTED; }
@@ -2458,10 +2468,17 @@ static int check_kd_overflow(sca_ctx *c) {
 
 // A pair that touches after the move was within r_a + r_b + 2 * max_step of each other before it (an obstacle:
 // r_a + r_o + max_step); l3norm rounds to 5 dp, hence the 1e-4.  The kernels add the agent's own radius.
+static double collide_max_step(const sca_ctx *c) { return 1.01 * std::max(c->max_pref_speed, c->P.max_speed) * c->P.dt_nominal; }
 static void collide_reach(const sca_ctx *c, double &agent_reach, double &obs_reach) {
-    const double max_step = 1.01 * std::max(c->max_pref_speed, c->P.max_speed) * c->P.dt_nominal;
+    const double max_step = collide_max_step(c);
     agent_reach = c->max_radius + 2.0 * max_step + 1e-4;
     obs_reach = c->max_obs_radius + max_step + 1e-4;
+}
+// k_clearance's bound (clearance_bound, sca_clearance.h): a partner has moved by at most max_step since the tree was built and is at most
+// max_radius wide; the obstacle tree is static.  The kernel adds the agent's own radius.
+static void clearance_reach(const sca_ctx *c, double &agent_reach, double &obs_reach) {
+    agent_reach = collide_max_step(c) + c->max_radius + 1e-4;
+    obs_reach = c->max_obs_radius + 1e-4;
 }
 
 static int pool_event(sca_ctx *c, hipEvent_t *out) {
@@ -2634,6 +2651,7 @@ static int auto_join(sca_ctx *c) {
 }
 
 static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) {
+    if (int r = clearance_refuse(c, "a policy pass", clearance_check(CLR_PASS, clearance_state(c), mode, 0, true, 0))) return r;
     const bool fork_ready = c->fork_ready;
     c->fork_ready = false;
 #ifdef SCA_TIMELINE
@@ -2928,6 +2946,15 @@ static int launch_collide_finish(sca_ctx *c, bool timed) {
                            (const int32_t *)c->scenes.size, c->scenes.clear, c->scenes.obs_on ? c->scenes.ov.oroot : (const int32_t *)nullptr, c->scenes.obs_on ? 0 : d.m,
                            c->scenes.largest, passed ? (const uint32_t *)d.coll_new : (const uint32_t *)nullptr);
     }
+    if (c->clear) {                                                        // the closest approach of this step over the whole context: a wavefront per agent
+        // The agent tree of this step.  A kd pass built it on the pass's own streams, joined into this one in front of the solve -- the order
+        // K4's traversal relies on.  An AUTO pass built it on kd_stream, which nothing of the step waits for (K4 looks into the grid there):
+        // this stream waits for that build here.
+        if (c->auto_ran) { if (int r = auto_join(c)) return r; }
+        double car, cor;
+        clearance_reach(c, car, cor);
+        hipLaunchKernelGGL(k_clearance, dim3((unsigned)((d.n + CLR_WAVES - 1) / CLR_WAVES)), dim3(CLR_WAVES * 64), 0, c->stream, d, c->clear, car, cor, ++c->clear_step);
+    }
     const dim3 k4grid((cnt + K4_WAVES * K4_APW - 1) / (K4_WAVES * K4_APW));
     // (the event that rides on the step's last kernel, if sca_run_steps asked for one: the next pass's fork)
     const bool others = c->part_on || cnt < d.n;
@@ -2983,6 +3010,8 @@ static int read_active(sca_ctx *c, int *active, bool kd_word);
 int sca_env_update(sca_ctx *c, int *all_done) {
     API_ENTER(c);
     if (!c->state_set) { c->err = "sca_set_state first"; return SCA_ERR_STATE; }
+    // (the closest-approach records need this step's agent tree: refused before anything is enqueued)
+    if (int r = clearance_refuse(c, "sca_env_update", clearance_check(CLR_UPDATE, clearance_state(c), c->near_valid ? 1 : 0, c->nbr_mode == SCA_NBR_GRID && !c->auto_ran ? 1 : 0, true, 0))) return r;
     CHK(c, hipEventRecord(c->ev[4], c->stream));
     if (int r = launch_update(c, true)) return r;
     if (all_done) {
@@ -3097,7 +3126,8 @@ static int run_steps_loop(sca_ctx *c, int steps, int neighbor_mode, bool lazy) {
             if (b > 0) CHK(c, hipMemcpyAsync(c->d.rec_new, c->d.rec, sizeof(PubRec) * (size_t)b, hipMemcpyDeviceToDevice, c->stream));
             if (e < c->n) CHK(c, hipMemcpyAsync(c->d.rec_new + e, c->d.rec + e, sizeof(PubRec) * (size_t)(c->n - e), hipMemcpyDeviceToDevice, c->stream));
         }
-        if (neighbor_mode == SCA_NBR_AUTO && c->auto_ran && s + 1 < steps &&
+        // (not with the closest-approach records on: k_clearance reads this step's tree, which a build enqueued ahead would overwrite beside it)
+        if (neighbor_mode == SCA_NBR_AUTO && c->auto_ran && s + 1 < steps && !c->clear &&
             auto_next(c->auto_fits, c->trk_on && c->trk_in_pass, c->part_on, c->kdq_last, c->tun.auto_div, c->auto_backoff, c->d.shard_count)) {
             // SCA_NBR_AUTO: the NEXT pass's kd build needs the moved positions only -- k_collide_finish changes flags, and in an
             // AUTO pass its fallback looks into the grid, not into the tree -- so it starts here, beside the collision check and the
@@ -3296,6 +3326,7 @@ int sca_comm_init(sca_ctx *c, int rank, int nranks, const void *unique_id) {
     if (c->comm) { c->err = "communicator already initialised (sca_comm_destroy first)"; return SCA_ERR_STATE; }
     if (c->part_on) { c->err = "sca_comm_init with the cell-owner partition active"; return SCA_ERR_STATE; }
     if (c->scenes.on) { c->err = "sca_comm_init with scenes set (sca_set_scenes): scenes are one rank's"; return SCA_ERR_UNSUPPORTED; }
+    if (int r = clearance_refuse(c, "sca_comm_init", clearance_check(CLR_COMM_INIT, clearance_state(c), 0, 0, true, 0))) return r;
     if (c->n % nranks) { c->err = "agent count must be a multiple of the rank count"; return SCA_ERR_ARG; }
     if (const char *e = rccl_load()) { c->err = e; return SCA_ERR_UNSUPPORTED; }
     CHK(c, hipSetDevice(c->device));
@@ -3407,6 +3438,7 @@ int sca_partition_init(sca_ctx *c, int rank, int nranks, int axis, const double 
     if (c->comm) { c->err = "sca_partition_init with an active communicator (the all-gather mode)"; return SCA_ERR_STATE; }
     if (c->scenes.on) { c->err = "sca_partition_init with scenes set (sca_set_scenes): a mode of SCA_NBR_GRID, which has no scene form"; return SCA_ERR_UNSUPPORTED; }
     if (c->paths_on) { c->err = "sca_partition_init with waypoint lists set (sca_set_paths): path state does not migrate with the agents"; return SCA_ERR_UNSUPPORTED; }
+    if (int r = clearance_refuse(c, "sca_partition_init", clearance_check(CLR_PARTITION_INIT, clearance_state(c), 0, 0, true, 0))) return r;
     if (int r = part_free(c)) return r;
     const int n = c->n;
     const double inv_cell = grid_inv_cell(c->P.neighbor_dist);
@@ -3522,6 +3554,8 @@ int sca_step_begin(sca_ctx *c, int neighbor_mode) {
 }
 int sca_step_end(sca_ctx *c) {
     API_ENTER(c);
+    // (the closest-approach records need this step's agent tree: sca_env_update's refusal)
+    if (int r = clearance_refuse(c, "sca_step_end", clearance_check(CLR_UPDATE, clearance_state(c), c->near_valid ? 1 : 0, c->nbr_mode == SCA_NBR_GRID && !c->auto_ran ? 1 : 0, true, 0))) return r;
     return launch_collide_finish(c, false);
 }
 
@@ -3861,6 +3895,62 @@ int sca_get_scene_clearance(sca_ctx *c, int scene, sca_scene_clearance *out, int
     return 0;
 }
 
+// ---- closest approach per agent for a whole context (include/sca_hip.h; the rule, the bound, the descent and every refusal are
+// sca_clearance.h's, the kernel is k_clearance, enqueued by launch_collide_finish) --------------------------------------------------------------
+static ClearanceState clearance_state(const sca_ctx *c) {
+    ClearanceState s;
+    s.enabled = c->clear != nullptr; s.agents = c->agents_set; s.state = c->state_set; s.mid_step = c->near_valid;
+    s.scenes = c->scenes.on; s.comm = c->comm != nullptr; s.partition = c->part_on; s.n = c->n; s.shard_count = c->d.shard_count;
+    return s;
+}
+static int clearance_refuse(sca_ctx *c, const char *who, ClearanceFault f) {
+    const std::string w = std::string(who);
+    switch (f) {
+    case CLRF_OK: return 0;
+    case CLRF_NO_AGENTS: c->err = w + ": sca_set_agents first"; break;
+    case CLRF_NO_STATE: c->err = w + ": no state yet -- sca_set_state first"; break;
+    case CLRF_MID_STEP: c->err = w + ": between a policy pass and its env update"; break;
+    case CLRF_OFF: c->err = w + ": sca_clearance_enable first"; break;
+    case CLRF_RANGE: c->err = w + ": agent_begin .. agent_begin + agent_count must lie inside 0 .. " + std::to_string(c->n); break;
+    case CLRF_NO_OUT: c->err = w + ": out is NULL"; break;
+    case CLRF_BAD_STRUCT: c->err = w + ": struct_bytes must be sizeof(sca_scene_clearance) = " + std::to_string(sizeof(sca_scene_clearance)); break;
+    case CLRF_SCENES: c->err = w + ": the closest-approach records of a whole context and scenes (sca_set_scenes) exclude each other -- scenes have sca_scene_clearance_enable"; break;
+    case CLRF_SHARD: c->err = w + ": the closest-approach records (sca_clearance_enable) need the whole swarm on this rank, not a shard with count < n (sca_set_shard)"; break;
+    case CLRF_COMM: c->err = w + ": the closest-approach records (sca_clearance_enable) need the whole swarm on this rank, not a communicator (sca_comm_init)"; break;
+    case CLRF_PARTITION: c->err = w + ": the closest-approach records (sca_clearance_enable) descend the agent kd-tree, which the cell-owner partition (sca_partition_init) never builds"; break;
+    case CLRF_GRID_PASS: c->err = w + ": the closest-approach records are on (sca_clearance_enable) and a pass in SCA_NBR_GRID mode builds no agent tree of this step -- SCA_NBR_KDTREE, SCA_NBR_AUTO or SCA_NBR_KDTREE_HOSTBUILD"; break;
+    default: c->err = w + ": the closest-approach records are on (sca_clearance_enable) and no policy pass opened this step -- there is no agent tree of this step";
+    }
+    return clearance_error_code(f);
+}
+static int clearance_drop(sca_ctx *c) {
+    if (!c->clear) return 0;
+    CHK(c, hipStreamSynchronize(c->stream));
+    (void)hipFree(c->clear);
+    c->clear = nullptr; c->clear_step = 0;
+    return 0;
+}
+int sca_clearance_enable(sca_ctx *c, int on) {
+    API_ENTER(c);
+    if (int r = clearance_refuse(c, "sca_clearance_enable", clearance_check(on ? CLR_ENABLE : CLR_DISABLE, clearance_state(c), 0, 0, true, 0))) return r;
+    if (!on) return clearance_drop(c);
+    sca_scene_clearance *rec = nullptr;
+    CHK(c, hipMalloc((void **)&rec, sizeof(sca_scene_clearance) * (size_t)c->n));     // (before the old records go: a refused call changes nothing)
+    const std::vector<sca_scene_clearance> empty((size_t)c->n, scene_clearance_empty());
+    if (hipMemcpyAsync(rec, empty.data(), sizeof(sca_scene_clearance) * (size_t)c->n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipFree(rec); c->err = "sca_clearance_enable: the upload of the empty records failed"; return SCA_ERR_HIP; }
+    if (int r = clearance_drop(c)) { (void)hipFree(rec); return r; }
+    c->clear = rec; c->clear_step = 0;
+    return 0;
+}
+int sca_get_clearance(sca_ctx *c, int agent_begin, int agent_count, sca_scene_clearance *out, int32_t struct_bytes) {
+    API_ENTER(c);
+    if (int r = clearance_refuse(c, "sca_get_clearance", clearance_check(CLR_GET, clearance_state(c), agent_begin, agent_count, out != nullptr, struct_bytes))) return r;
+    if (agent_count > 0) CHK(c, hipMemcpyAsync(out, c->clear + agent_begin, sizeof(sca_scene_clearance) * (size_t)agent_count, hipMemcpyDeviceToHost, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 // ---- finished scenes hand over their result with the step (include/sca_hip.h; the rules and the layout are sca_scenes.h's, the kernel is
 // k_scene_harvest, enqueued by launch_collide_finish) ------------------------------------------------------------------------------------------
 static int scene_harvest_refuse(sca_ctx *c, const char *who, HarvestFault f) {
@@ -3986,6 +4076,7 @@ int sca_set_shard(sca_ctx *c, int begin, int count) {
     if (c->part_on) { c->err = "sca_set_shard with the cell-owner partition active (sca_partition_disable first)"; return SCA_ERR_STATE; }
     if (c->comm) { c->err = "sca_set_shard with an active communicator (the shard follows from rank / nranks; sca_comm_destroy first)"; return SCA_ERR_STATE; }
     if (c->scenes.on && (begin != 0 || count != c->n)) { c->err = "sca_set_shard with scenes set (sca_set_scenes): scenes are stepped by one rank, whole"; return SCA_ERR_UNSUPPORTED; }
+    if (int r = clearance_refuse(c, "sca_set_shard", clearance_check(CLR_SET_SHARD, clearance_state(c), count, 0, true, 0))) return r;
     c->d.shard_begin = begin; c->d.shard_count = count;
     c->kd_ahead = false; c->kdq_last = -1; c->auto_backoff = 0;           // another shard: the AUTO passes' counts described the old one
     return 0;

@@ -442,8 +442,9 @@ class _FlatAgents:
 
 
 class MACAEnv(_FlatAgents):
-    def __init__(self, v_pref_fn=None, device=0, neighbor_mode=S.NBR_KDTREE, history_capacity=0, device_tracker=False):
+    def __init__(self, v_pref_fn=None, device=0, neighbor_mode=S.NBR_KDTREE, history_capacity=0, device_tracker=False, clearance=False):
         self.agents = None
+        self.clearance_on = bool(clearance)            # every step also keeps each agent's closest approach (sca_clearance_enable): env.clearance
         self.obstacles = []
         self.kdTree = None
         self.solver = None
@@ -493,6 +494,19 @@ class MACAEnv(_FlatAgents):
             self.history_capacity = capped
         if self.history_capacity:
             self.solver.history_enable(self.history_capacity)
+        if self.clearance_on:
+            self.solver.clearance_enable()
+
+    @property
+    def clearance(self):
+        """The closest-approach records of the episode so far (MACAEnv(clearance=True)): one record per agent in sca_scene_clearance's
+        layout (_lib.CLEARANCE_DTYPE), partners are agent ids and indices into the obstacle list, `step` counts env.step() calls from 1.
+        metrics.clearance_metrics(env) reads them."""
+        if not self.clearance_on:
+            raise RuntimeError('clearance: a MACAEnv(clearance=True) keeps the closest approach per agent; this one was built without')
+        if self._row_cache is not None:
+            raise RuntimeError('clearance: between a policy pass and its env update (agent.find_next_action was called): env.step() first')
+        return self.solver.clearance()
 
     pos = property(lambda self: self._state('pos'))
     vel = property(lambda self: self._state('vel'))

@@ -12,7 +12,7 @@
 
   * `clearance_metrics(view)` / `merge_clearance(before, after)` — how close the drones came (MinClearance, MinObstacleClearance,
     NearMisses) from the closest-approach records the device keeps with the step (`sca_scene_clearance_enable`; `batch.env(s).clearance`
-    of a SceneBatch(clearance=True)): the column the reference's table lacks, without an all-pairs search over the trajectory log.
+    of a SceneBatch(clearance=True); `sca_clearance_enable`: `env.clearance` of a MACAEnv(clearance=True), any number of agents): the column the reference's table lacks, without an all-pairs search over the trajectory log.
 
 AverageCost is the reference's wall time of find_next_action per agent-step (run_sca.py:250): by default the sum of
 `agent.total_time`, which MACAEnv.step maintains (a step's policy wall time shared among the agents it served); a measured
@@ -107,7 +107,8 @@ def merge_clearance(before, after):
 
 def clearance_metrics(view, margin=0.0):
     """How close an episode's drones came, from its closest-approach records: `view` is a scene view of a SceneBatch(clearance=True)
-    (`batch.env(s)`: its `.clearance`) or the structured array itself.  clearance = rounded distance - radius sum, the env's own collision
+    (`batch.env(s)`: its `.clearance`), a MACAEnv(clearance=True) (the whole context's records, sca_clearance_enable: partners are agent
+    ids and indices into the env's obstacle list, the step counts env.step() calls) or the structured array itself.  clearance = rounded distance - radius sum, the env's own collision
     test (mampenv.py:61-75), so a value <= 0 is a touch.  MinClearance with its pair (the agent that holds the record, its partner) and the
     scene's step; MinObstacleClearance with agent, obstacle (index in the scene's set) and step; on equal values the lowest agent.  An
     episode of one agent, or without obstacles, has +inf, None, 0 there.  NearMisses: the agents whose smaller clearance is <= margin."""

@@ -467,6 +467,24 @@ class BatchedSolver:
                   'sca_get_scene_clearance')
         return out
 
+    # ---- closest approach per agent for the whole context, by kd-tree descent (sca_clearance_enable) -------------------------
+    def clearance_enable(self, on=True):
+        """From now on every step runs k_clearance: every agent keeps how close it came to another agent and to an obstacle, with whom
+        and at which env update since this call (include/sca_hip.h has the rule and what is refused while it is on).  Every row starts
+        empty; on=False frees the records.  A context with scenes has scene_clearance_enable instead."""
+        self._chk(self.L.sca_clearance_enable(self.ctx, 1 if on else 0), 'sca_clearance_enable')
+
+    def clearance(self, begin=0, count=None):
+        """The records of agents begin .. begin + count - 1 (all from `begin` on by default), a structured array (_lib.CLEARANCE_DTYPE:
+        agent_clear, obs_clear f64, agent_partner, agent_step, obs_partner, obs_step i32; an empty half is +inf, -1, 0).  One copy, one
+        synchronisation."""
+        begin = int(begin)
+        count = max(0, int(self.n) - begin) if count is None else int(count)
+        out = np.zeros(max(count, 1), _lib.CLEARANCE_DTYPE)               # (a range the library will refuse still gets a buffer)
+        self._chk(self.L.sca_get_clearance(self.ctx, begin, count, out.ctypes.data_as(C.POINTER(_lib.SceneClearance)), _lib.CLEARANCE_DTYPE.itemsize),
+                  'sca_get_clearance')
+        return out[:max(count, 0)]
+
     # ---- scene checkpoints (sca_save_scenes / sca_load_scenes) ---------------------------------------------------------------
     def scene_checkpoint_bytes(self, scene):
         """the size of the blob save_scenes writes for the scene as it stands now"""
