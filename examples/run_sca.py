@@ -32,6 +32,30 @@ def build_obstacles():
     return out
 
 
+def lifelong(args, agents, obstacles, pol, dubins):
+    """--lifelong STEPS: ping-pong.  An arrived drone flies back to where its mission began; a collided or timed-out one starts its
+    original mission again."""
+    from sca_amd.lifelong import run_lifelong
+    env = E.MACAEnv(device_tracker=dubins, clearance=args.clearance)
+    env.set_agents(agents, obstacles=obstacles)
+    first = {a.id: (list(a.initial_pos), list(a.goal_pos)) for a in agents}
+
+    def next_mission(agent, row):
+        if int(row['flags']) & S.FLAG_COLLISION or not int(row['flags']) & S.FLAG_AT_GOAL:
+            start, goal = first[agent.id]
+        else:
+            start = list(row['pos']) + list(agent.heading_global_frame)
+            goal = list(agent.initial_pos)
+        return E.Agent(start_pos=start, goal_pos=goal, vel=[0.0, 0.0, 0.0], radius=agent.radius, pref_speed=agent.pref_speed, policy=pol, id=agent.id)
+
+    t0 = time.time()
+    stats = run_lifelong(env, next_mission, args.lifelong)
+    cost = time.time() - t0
+    missions = stats['arrived'] + stats['collided'] + stats['timed_out']
+    print('lifelong:', stats['steps'], 'steps,', f'{cost:.2f} s,', missions, 'missions,', f'{missions / cost:.1f} missions/s')
+    print({k: stats[k] for k in ('arrived', 'collided', 'timed_out', 'respawned', 'retired', 'agent_steps')}, f"live fraction {stats['live_fraction']:.3f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--scenario', default='circle', choices=['circle', 'takeoff', 'exp3', 'sphere', 'random'])
@@ -47,6 +71,9 @@ def main():
     ap.add_argument('--clearance', action='store_true',
                     help='keep every drone\'s closest approach to another drone and to an obstacle with the step, and print the minima')
     ap.add_argument('--margin', type=float, default=0.0, help='with --clearance: a drone whose smaller clearance is <= this counts as a near miss')
+    ap.add_argument('--lifelong', type=int, default=0, metavar='STEPS',
+                    help='continuous traffic for STEPS steps instead of one episode: a drone that arrives flies back, one that collided or '
+                         'timed out starts again from its original start (MACAEnv.respawn; the Dubins tracker then runs on the device)')
     args = ap.parse_args()
 
     n = args.agents
@@ -72,6 +99,8 @@ def main():
 
     v_pref_fn = None
     dubins = pol in (E.SCAPolicy, E.RVO3dDubinsPolicy)          # these two follow a Dubins path (scaPolicy.py:264-338)
+    if args.lifelong > 0:
+        return lifelong(args, agents, obstacles, pol, dubins)
     if dubins and args.tracker == 'host':
         v_pref_fn = tracker.DubinsTracker(sc['goal'][:, :3], sc['goal'][:, 3:6], np.ones(n), S.zaxis_flags(sc['start'], sc['goal']))
     env = E.MACAEnv(v_pref_fn=v_pref_fn, history_capacity=args.max_steps, device_tracker=dubins and args.tracker == 'device', clearance=args.clearance)

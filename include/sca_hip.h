@@ -634,6 +634,56 @@ int sca_get_scene_clearance(sca_ctx *ctx, int scene, sca_scene_clearance *out /*
 int sca_clearance_enable(sca_ctx *ctx, int on);
 int sca_get_clearance(sca_ctx *ctx, int agent_begin, int agent_count, sca_scene_clearance *out /*agent_count*/, int32_t struct_bytes);
 
+/* Respawning agents in place: new missions without redefining the swarm.  A plain context (no scenes) otherwise runs one episode -- an
+ * agent that arrived, collided or timed out stays inert until everybody has finished, and sca_set_agents tears the whole world down (every
+ * Dubins plan, attributes, lists, records, the log, the kd permutation).  The reference's rule is plain Python: assigning pos_global_frame,
+ * goal_global_frame, is_at_goal = False, ... to one Agent object between two env.step() calls (mampenv.py:16-19); the kd-tree keeps its
+ * agentIDs order (kdTree.py:43-45) and every other agent is untouched.
+ *   sca_respawn_agents   the arrays are packed in the order of `ids` (any order, no repeats) and travel through a page-locked block of the
+ *              library's own; ONE launch (k_respawn, a wavefront per named row) and one synchronisation however many rows are named.
+ *              Legal only between two steps.  Afterwards a named row is what sca_set_agents + sca_set_state (+
+ *              sca_device_tracker_enable) leave for an agent with these values: public record (pos, float32 vel, flags 0, radius), heading,
+ *              goal, pref_speed, max_run_dist, zaxis (NULL: the rows keep theirs), total_dist 0, step_num 0, status 0, last pass's list
+ *              invalid (nbr_valid 0, the tracker's first-neighbour distSq -1).  Device tracker on and the row SCA / RVO3D+Dubins: the
+ *              initial tracker record, goal_heading, vpref_mode 1, vpref_ext 0; otherwise the row's fed vpref_ext / vpref_mode stay
+ *              (the caller's input, refreshed through sca_set_vpref).  Waypoint lists in slot form: the row's list from the call's CSR
+ *              arrays (len = rem = its length, now_goal None), without arrays an empty list.  Closest-approach records on: the row's
+ *              record is emptied (+inf, -1, 0), other rows keep it as a partner, the step count runs on.  EVERY OTHER ROW KEEPS EVERY
+ *              WORD IT HAD, and so do the kd permutation, the trajectory log (it goes on) and the form heuristics: forms may differ
+ *              afterwards, values may not.  sca_active_count is right at once (K4's striped counters are adjusted for the rows that
+ *              were done).  The row KEEPS its policy, its per-agent solver attributes (sca_set_agent_params) and its planner attributes
+ *              (sca_device_tracker_set_agent_params): changing them is out of scope here.  Host mirrors follow: the radius a later
+ *              sca_set_state uploads, the largest radius / pref_speed (they only grow), and, where sca_host_state_get has handed out the
+ *              state block, the named rows' six state columns there (a later SCA_HOST_IN_STATE step does not bring the old rows back).
+ *              Works in every neighbour mode and in front of and behind every step form.
+ *   sca_get_finished     the rows that carry any of at-goal / collision / timeout, ascending ids (an ordered compaction on the device: a
+ *              count per tile, a scan, the write; one synchronisation) -- instead of sca_get_state's n records across the link.  *count
+ *              is their number even where it exceeds `capacity`; the first `capacity` are written.  A lifelong loop calls it only when
+ *              sca_env_step's `active` dropped.
+ *   refusals   decided on the host before any device work; a refused call changes nothing.  SCA_ERR_STATE: no agents, no state yet, (respawn)
+ *              between a policy pass and its env update.  SCA_ERR_ARG: count <= 0, a NULL required array (everything but zaxis,
+ *              goal_heading and the path arrays), an id outside 0 .. n-1, a repeated id, a position that is not finite, a radius,
+ *              pref_speed or max_run_dist that is not positive and finite, goal_heading == NULL with a tracked row named under the device
+ *              tracker, only one of the two path arrays, a list longer than the room per row, negative or decreasing offsets, a waypoint
+ *              that is not finite; for sca_get_finished capacity < 0, a NULL count, NULL rows with capacity > 0, struct_bytes other than
+ *              sizeof(sca_finished_row).  SCA_ERR_UNSUPPORTED, the message names the way out: scenes are set (sca_restart_scenes), a shard
+ *              with count < n, a communicator, the cell-owner partition, waypoint lists in block form (sca_set_path_slots), path arrays
+ *              while no slot form is set.
+ * Detect the feature by the symbol (the version number is unchanged). */
+typedef struct sca_finished_row {        /* 48 bytes */
+    int32_t  id;                         /* the agent's row */
+    uint32_t flags;                      /* sca_flag bits */
+    int32_t  step_num, reserved;
+    double   total_dist;
+    double   pos[3];
+} sca_finished_row;
+int sca_respawn_agents(sca_ctx *ctx, int count, const int32_t *ids /*count*/, const double *pos /*count*3*/, const float *vel /*count*3*/,
+                       const double *heading /*count*3*/, const double *radius /*count*/, const double *pref_speed /*count*/,
+                       const double *goal /*count*3*/, const uint8_t *zaxis /*count, nullable*/, const double *max_run_dist /*count*/,
+                       const double *goal_heading /*count*3, nullable*/, const int32_t *path_offsets /*count+1, nullable*/,
+                       const double *path_points /*nullable*/);
+int sca_get_finished(sca_ctx *ctx, sca_finished_row *rows /*capacity*/, int capacity, int *count, int32_t struct_bytes);
+
 /* the hot path ----------------------------------------------------------------------------------- */
 int sca_policy_pass(sca_ctx *ctx, int neighbor_mode);
 int sca_get_actions(sca_ctx *ctx, float *action /*n*7*/);

@@ -74,7 +74,17 @@ CLEARANCE_DTYPE = np.dtype([('agent_clear', np.float64), ('obs_clear', np.float6
                             ('obs_partner', np.int32), ('obs_step', np.int32)])
 
 
-CHECKPOINT_SECTIONS = 14                                          # sca_scene_checkpoint_layout's offsets
+class FinishedRow(C.Structure):
+    """sca_finished_row: a row that carries at-goal / collision / timeout (sca_get_finished), 48 bytes"""
+    _fields_ = [('id', C.c_int32), ('flags', C.c_uint32), ('step_num', C.c_int32), ('reserved', C.c_int32), ('total_dist', C.c_double),
+                ('pos', C.c_double * 3)]
+
+
+FINISHED_DTYPE = np.dtype([('id', np.int32), ('flags', np.uint32), ('step_num', np.int32), ('reserved', np.int32), ('total_dist', np.float64),
+                           ('pos', np.float64, (3,))])
+
+
+CHECKPOINT_SECTIONS = 14                                         # sca_scene_checkpoint_layout's offsets
 
 
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against include/sca_hip.h
@@ -125,6 +135,8 @@ SIGNATURES = {
     'sca_get_scene_clearance': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SceneClearance), C.c_int32]),
     'sca_clearance_enable': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_get_clearance': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(SceneClearance), C.c_int32]),
+    'sca_respawn_agents': (C.c_int, [C.c_void_p, C.c_int, ip, dp, fp, dp, dp, dp, dp, bp, dp, dp, ip, dp]),
+    'sca_get_finished': (C.c_int, [C.c_void_p, C.POINTER(FinishedRow), C.c_int, C.POINTER(C.c_int), C.c_int32]),
     'sca_set_path_state': (C.c_int, [C.c_void_p, ip, dp]),
     'sca_policy_pass': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_get_actions': (C.c_int, [C.c_void_p, fp]),

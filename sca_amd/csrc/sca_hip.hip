@@ -28,6 +28,8 @@
 #include "sca_scenes.hip.h"
 #include "sca_clearance.h"
 #include "sca_clearance.hip.h"
+#include "sca_respawn.h"
+#include "sca_respawn.hip.h"
 
 using namespace sca;
 
@@ -346,6 +348,12 @@ struct sca_ctx {
     std::vector<uint8_t> h_trk_cls;         // [n] trk_cls as the device holds it
     ClassTable trk_table;                   // the classes in use over the occupied tracked rows (scene_class_table)
     bool trk_attr_on = false;               // the table governs trk_classes / trk_many / the view (since the first restart that brought planner attributes)
+    // respawning agents in place (sca_respawn_agents, sca_get_finished; sca_respawn.h): nothing of it exists until the first call
+    uint8_t *rsp_host = nullptr;            // sca_respawn_agents' page-locked block (RespawnLayout of rsp_cap rows and rsp_W waypoints per row)
+    int rsp_cap = 0, rsp_W = 0;
+    uint8_t *fin_host = nullptr;            // sca_get_finished's page-locked block: the count's head, fin_cap rows behind it
+    int fin_cap = 0;
+    int32_t *fin_counts = nullptr;          // device [2 * tiles of max_n]: the tiles' counts, their offsets behind them
 };
 
 #define CHK(ctx, call)                                                                         \
@@ -947,6 +955,9 @@ void sca_destroy(sca_ctx *c) {
     if (c->h_done) { (void)hipHostFree(c->h_done); c->h_done = nullptr; }
     if (c->hs_host) { (void)hipHostFree(c->hs_host); c->hs_host = nullptr; }
     if (c->hs_dev) { (void)hipFree(c->hs_dev); c->hs_dev = nullptr; }
+    if (c->rsp_host) { (void)hipHostFree(c->rsp_host); c->rsp_host = nullptr; }
+    if (c->fin_host) { (void)hipHostFree(c->fin_host); c->fin_host = nullptr; }
+    if (c->fin_counts) { (void)hipFree(c->fin_counts); c->fin_counts = nullptr; }
     if (c->ap_dev) { (void)hipFree(c->ap_dev); (void)hipFree(c->ap_nd); c->ap_dev = nullptr; c->ap_nd = nullptr; }
     void *ptrs[] = {c->rec_own, c->rec_new_own, d.heading, d.goal, d.pref_speed, d.vpref_ext, d.total_dist, d.max_run_dist,
                     d.step_num, d.vpref_mode, d.policy, d.zaxis, d.obs, d.obs_sorted, d.awide, d.owide, d.atree, d.aperm, d.otree, d.operm, d.nbr_n,
@@ -3948,6 +3959,131 @@ int sca_get_clearance(sca_ctx *c, int agent_begin, int agent_count, sca_scene_cl
     if (int r = clearance_refuse(c, "sca_get_clearance", clearance_check(CLR_GET, clearance_state(c), agent_begin, agent_count, out != nullptr, struct_bytes))) return r;
     if (agent_count > 0) CHK(c, hipMemcpyAsync(out, c->clear + agent_begin, sizeof(sca_scene_clearance) * (size_t)agent_count, hipMemcpyDeviceToHost, c->stream));
     CHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- respawning agents in place (include/sca_hip.h; the rules, the block and the scan rule are sca_respawn.h's, the kernels
+// sca_respawn.hip.h's, enqueued here and nowhere else) -----------------------------------------------------------------------------------------
+static RespawnCtx respawn_ctx(const sca_ctx *c) {
+    RespawnCtx X;
+    X.agents = c->agents_set; X.state = c->state_set; X.mid_step = c->near_valid;
+    X.scenes = c->scenes.on; X.comm = c->comm != nullptr; X.partition = c->part_on; X.n = c->n; X.shard_count = c->d.shard_count;
+    X.tracker_on = c->trk_on; X.paths_block = c->paths_on && c->path_W == 0; X.path_W = c->paths_on ? c->path_W : 0;
+    X.policy_now = c->h_policy.data();
+    return X;
+}
+static int respawn_refuse(sca_ctx *c, const char *who, RespawnFault f, int entry) {
+    const std::string w = std::string(who), at = std::to_string(entry);
+    switch (f) {
+    case RSP_OK: return 0;
+    case RSP_NO_AGENTS: c->err = w + ": sca_set_agents first"; break;
+    case RSP_NO_STATE: c->err = w + ": no state yet -- sca_set_state first"; break;
+    case RSP_MID_STEP: c->err = w + " between a policy pass and its env update: finish the step first"; break;
+    case RSP_BAD_COUNT: c->err = w + ": count must be positive"; break;
+    case RSP_NO_ARRAYS: c->err = w + ": ids, pos, vel, heading, radius, pref_speed, goal and max_run_dist must not be NULL"; break;
+    case RSP_BAD_ID: c->err = w + ": ids[" + at + "] is not an agent of this context (0 .. " + std::to_string(c->n - 1) + ")"; break;
+    case RSP_REPEATED_ID: c->err = w + ": ids[" + at + "] is named twice"; break;
+    case RSP_NOT_FINITE: c->err = w + ": row " + at + " has a position that is not finite"; break;
+    case RSP_NOT_POSITIVE: c->err = w + ": row " + at + " has a radius, pref_speed or max_run_dist that is not positive and finite"; break;
+    case RSP_GOAL_HEADING: c->err = w + ": row " + at + " is tracked by the device tracker (sca_device_tracker_enable) and goal_heading is NULL"; break;
+    case RSP_PATH_HALF: c->err = w + ": path_offsets and path_points come together or not at all"; break;
+    case RSP_PATH_OFFSETS: c->err = w + ": path_offsets are negative or decrease at row " + at; break;
+    case RSP_PATH_TOO_LONG: c->err = w + ": row " + at + " brings a list longer than the room per row, " + std::to_string(c->path_W) + " (sca_set_path_slots)"; break;
+    case RSP_PATH_NOT_FINITE: c->err = w + ": waypoint " + at + " is not finite"; break;
+    case RSP_FIN_ARGS: c->err = w + ": capacity must not be negative, count not NULL, rows not NULL with a capacity, struct_bytes sizeof(sca_finished_row) = " + std::to_string(sizeof(sca_finished_row)); break;
+    case RSP_SCENES: c->err = w + " with scenes set (sca_set_scenes): a scene's agents are replaced by sca_restart_scenes"; break;
+    case RSP_SHARD: c->err = w + " on a shard with count < n (sca_set_shard): the call names rows of the whole swarm on one rank"; break;
+    case RSP_COMM: c->err = w + " with an active communicator: the call names rows of the whole swarm on one rank (sca_comm_destroy first)"; break;
+    case RSP_PARTITION: c->err = w + " under the cell-owner partition: the rows' state does not follow the owners (sca_partition_disable first)"; break;
+    case RSP_PATH_BLOCK: c->err = w + " with waypoint lists in block form (sca_set_paths): one row's list cannot be replaced there -- sca_set_path_slots"; break;
+    default: c->err = w + ": path arrays, but the context's lists are not in slot form -- sca_set_path_slots first";
+    }
+    return respawn_error_code(f);
+}
+static_assert(sizeof(sca_finished_row) == FINISHED_ROW_BYTES, "sca_finished_row is 48 bytes");
+int sca_respawn_agents(sca_ctx *c, int count, const int32_t *ids, const double *pos, const float *vel, const double *heading, const double *radius,
+                       const double *pref_speed, const double *goal, const uint8_t *zaxis, const double *max_run_dist, const double *goal_heading,
+                       const int32_t *path_offsets, const double *path_points) {
+    API_ENTER(c);
+    const RespawnCtx X = respawn_ctx(c);
+    const RespawnArgs A{count, ids, pos, vel, heading, radius, pref_speed, goal, zaxis, max_run_dist, goal_heading, path_offsets, path_points};
+    const RespawnCheck k = respawn_check(X, A);
+    if (int r = respawn_refuse(c, "sca_respawn_agents", k.fault, k.entry)) return r;
+    // the block: page-locked, mapped and coherent as the restart block is -- the kernel reads it in place.  It grows when a call names more
+    // rows than any before it (at once to 1024 rows or twice the last size, at most max_agents) or a larger room per row has arrived
+    if (count > c->rsp_cap || X.path_W != c->rsp_W) {
+        const int cap = count > c->rsp_cap ? std::max(count, std::min(c->max_n, std::max(1024, 2 * c->rsp_cap))) : c->rsp_cap;
+        uint8_t *blk = nullptr;
+        CHK(c, hipHostMalloc((void **)&blk, (size_t)respawn_layout(cap, X.path_W).total, hipHostMallocMapped | hipHostMallocCoherent));
+        if (c->rsp_host) (void)hipHostFree(c->rsp_host);              // (every call ends with its synchronisation: no launch still reads it)
+        c->rsp_host = blk; c->rsp_cap = cap; c->rsp_W = X.path_W;
+    }
+    const RespawnLayout L = respawn_layout(c->rsp_cap, c->rsp_W);
+    const bool slots = X.path_W > 0;
+    const uint32_t has = respawn_pack(c->rsp_host, L, X, A, slots ? c->h_path_vpref.data() : nullptr);
+    RespawnDev d{};
+    d.rec = c->d.rec; d.heading = c->d.heading; d.goal = c->d.goal; d.pref_speed = c->d.pref_speed; d.max_run_dist = c->d.max_run_dist;
+    d.total_dist = c->d.total_dist; d.vpref_ext = c->d.vpref_ext; d.step_num = c->d.step_num; d.status = c->d.status; d.nbr_n = c->d.nbr_n;
+    d.near_n = c->d.near_n; d.done_count = c->d.done_count; d.zaxis = c->d.zaxis; d.vpref_mode = c->d.vpref_mode; d.nbr_valid = c->d.nbr_valid;
+    if (c->trk_on) {
+        static_assert(sizeof(sca_dubins::AgentTrack) % 4 == 0, "k_respawn copies the tracker record as 4-byte words");
+        d.trk_nbr0 = c->trk.nbr0; d.trk_goal_heading = c->trk_goal_heading;
+        d.trk_st = (restart_u32 *)c->trk.st; d.trk_init = (const restart_u32 *)c->trk_init; d.trk_words = (int)(sizeof(sca_dubins::AgentTrack) / 4);
+    }
+    if (slots) { d.path_pts = c->pslot_pts; d.now_goal = c->path.now_goal; d.path_len = c->pslot_len; d.path_rem = c->path.rem; d.W = c->path_W; }
+    d.clear = c->clear;
+    d.n = c->n;
+    // on c->stream, behind every reader of the rows: a step's kernels run there or on streams the step joins back before it ends
+    hipLaunchKernelGGL(k_respawn, dim3((count + RESPAWN_WAVES - 1) / RESPAWN_WAVES), dim3(RESPAWN_WAVES * 64), 0, c->stream, d, (const uint8_t *)c->rsp_host, L, has, count);
+    CHK(c, hipGetLastError());
+    CHK(c, hipStreamSynchronize(c->stream));
+    // the device has the new missions: the host mirrors follow (a refused call has left them alone)
+    const HostLayout HL = host_state_layout(c->n);
+    for (int r = 0; r < count; r++) {
+        const int a = ids[r];
+        c->h_rec[a].radius = radius[r];
+        c->max_radius = std::max(c->max_radius, radius[r]);           // the envelope only grows (conservative filters, as under the restarts)
+        c->max_pref_speed = std::max(c->max_pref_speed, pref_speed[r]);
+        if (slots) {
+            const int32_t len = path_offsets ? path_offsets[r + 1] - path_offsets[r] : 0;
+            c->h_path_len[a] = len;
+            c->h_path_vpref[a] = len > 0 && !restart_policy_tracked(c->h_policy[a]);
+        }
+        if (c->hs_host) {                                              // the state block, if the caller has one: a later SCA_HOST_IN_STATE step must not bring the old row back
+            uint8_t *b = c->hs_host;
+            std::memcpy((double *)(b + HL.off[HS_POS]) + 3 * (size_t)a, pos + 3 * (size_t)r, sizeof(double) * 3);
+            std::memcpy((float *)(b + HL.off[HS_VEL]) + 3 * (size_t)a, vel + 3 * (size_t)r, sizeof(float) * 3);
+            std::memcpy((double *)(b + HL.off[HS_HEADING]) + 3 * (size_t)a, heading + 3 * (size_t)r, sizeof(double) * 3);
+            (b + HL.off[HS_FLAGS])[a] = 0;
+            ((double *)(b + HL.off[HS_TOTAL_DIST]))[a] = 0.0;
+            ((int32_t *)(b + HL.off[HS_STEP_NUM]))[a] = 0;
+        }
+    }
+    c->h_pos_valid = false; c->near_valid = false;
+    c->kd_single_hint = 0; c->kd_gen++;                                // positions replaced from outside: the level statistics of older trees do not apply (a sizing hint, no value)
+    return 0;
+}
+int sca_get_finished(sca_ctx *c, sca_finished_row *rows, int capacity, int *count, int32_t struct_bytes) {
+    API_ENTER(c);
+    if (int r = respawn_refuse(c, "sca_get_finished", finished_check(respawn_ctx(c), rows != nullptr, capacity, count != nullptr, struct_bytes), -1)) return r;
+    const int n = c->n, tiles = finished_tiles(n), cap = std::min(capacity, n);
+    if (!c->fin_counts) CHK(c, hipMalloc((void **)&c->fin_counts, sizeof(int32_t) * 2 * (size_t)finished_tiles(c->max_n)));
+    if (!c->fin_host || cap > c->fin_cap) {
+        const int want = std::min(c->max_n, std::max(cap, std::max(1024, 2 * c->fin_cap)));
+        uint8_t *blk = nullptr;
+        CHK(c, hipHostMalloc((void **)&blk, (size_t)FIN_HEAD_BYTES + sizeof(sca_finished_row) * (size_t)want, hipHostMallocMapped | hipHostMallocCoherent));
+        if (c->fin_host) (void)hipHostFree(c->fin_host);              // (every call ends with its synchronisation: no launch still writes it)
+        c->fin_host = blk; c->fin_cap = want;
+    }
+    const FinishedDev f{c->d.rec, c->d.total_dist, c->d.step_num, c->fin_counts, c->fin_counts + finished_tiles(c->max_n), n, tiles};
+    hipLaunchKernelGGL(k_finished_count, dim3(tiles), dim3(FIN_TILE), 0, c->stream, f);
+    hipLaunchKernelGGL(k_finished_scan, dim3(1), dim3(FIN_TILE), 0, c->stream, f, (int32_t *)c->fin_host);
+    hipLaunchKernelGGL(k_finished_write, dim3(tiles), dim3(FIN_TILE), 0, c->stream, f, c->fin_host, cap);
+    CHK(c, hipGetLastError());
+    CHK(c, hipStreamSynchronize(c->stream));
+    const int total = *(const int32_t *)c->fin_host;
+    *count = total;
+    if (std::min(total, cap) > 0) std::memcpy(rows, c->fin_host + FIN_HEAD_BYTES, sizeof(sca_finished_row) * (size_t)std::min(total, cap));
     return 0;
 }
 

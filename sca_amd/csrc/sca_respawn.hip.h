@@ -1,0 +1,153 @@
+// sca_respawn.hip.h -- the kernels behind sca_respawn_agents and sca_get_finished (the rules: sca_respawn.h).  Launched on the context's
+// stream only by those two entry points: a context that never calls them enqueues exactly what it did.
+#pragma once
+#include "sca_kernels.hip.h"
+#include "sca_scenes.hip.h"
+#include "sca_respawn.h"
+
+namespace sca {
+
+// ---- respawning agents in place ----------------------------------------------------------------------------------------------------------
+// One WAVEFRONT per named row; the call's arrays are read across the link from the library's page-locked block (RespawnLayout), as
+// k_scene_restart reads its own.  Afterwards every per-agent word of the row that a later pass READS BEFORE IT WRITES is what
+// sca_set_agents + sca_set_state (+ sca_device_tracker_enable) leave for an agent with the call's values; words of other rows are not
+// touched, the kd permutation neither.  The one shared word written is the row's stripe of K4's done_count (the only atomic).
+//   public record     three 16-byte pieces by lanes 0 .. 2 (restart_piece)
+//   AgentTrack        consecutive 4-byte words by consecutive lanes from the one initial record (tracked rows under the device tracker)
+//   three-component   heading, goal (goal_heading, vpref_ext, now_goal): one component per lane 0 .. 2
+//   scalar fields     lane 0, plain vector stores (respawn_row says which and what)
+//   waypoints         consecutive lanes on consecutive coordinates into the row's own room pts[3 (W a + j)]
+// Null device pointers (no tracker, no lists, no closest-approach records) are skipped by a uniform branch.
+// Not written, as under a scene restart: action, diag, vpref_used, vpost, is_fb, prep, coll_new, nbr_id, nbr_dsq, near_id, the kd nodes --
+// a pass writes each of them for every agent it serves before anybody reads it.
+struct RespawnDev {
+    PubRec *rec;
+    double *heading, *goal, *pref_speed, *max_run_dist, *total_dist, *vpref_ext;
+    int32_t *step_num, *status, *nbr_n, *near_n, *done_count;
+    uint8_t *zaxis, *vpref_mode, *nbr_valid;
+    // the device tracker's, null without one
+    double *trk_nbr0, *trk_goal_heading;
+    restart_u32 *trk_st;
+    const restart_u32 *trk_init;
+    int trk_words;
+    // the lists in slot form, null otherwise
+    double *path_pts, *now_goal;
+    int32_t *path_len, *path_rem;
+    int W;
+    sca_scene_clearance *clear;     // the closest-approach records (sca_clearance_enable), null: off
+    int n;
+};
+constexpr int RESPAWN_WAVES = 4;
+__global__ __launch_bounds__(RESPAWN_WAVES * 64) void k_respawn(RespawnDev d, const uint8_t *blk, RespawnLayout L, uint32_t has, int count) {
+    const int lane = (int)threadIdx.x & 63;
+    const int r = (int)blockIdx.x * RESPAWN_WAVES + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);     // wave-uniform
+    if (r >= count) return;
+    const int a = ((const int32_t *)(blk + L.off[RSB_IDS]))[r];
+    if (a < 0 || a >= d.n) return;                                     // (the host has checked the ids: never taken)
+    const bool lists = (has & RESPAWN_HAS_PATHS) != 0;
+    const int32_t *poff = (const int32_t *)(blk + L.off[RSB_PATH_OFF]);
+    const int32_t first = lists ? poff[r] : 0, len = lists ? poff[r + 1] - first : 0;
+    const uint32_t old_flags = d.rec[a].flags;
+    const RespawnRow w = respawn_row((blk + L.off[RSB_BITS])[r], old_flags, has, len);
+    // K4's counters of the last step, before the record is replaced: a row that was done runs again (sca_active_count between steps)
+    if (lane == 0 && w.done_delta) atomicAdd(&d.done_count[(a & 255) * 32], w.done_delta);
+    if (lane < RSP_REC_BYTES / 16) ((restart_piece *)(d.rec + a))[lane] = ((const restart_piece *)(blk + L.off[RSB_REC] + (int64_t)RSP_REC_BYTES * r))[lane];
+    if (lane < 3) {
+        const int64_t g = 3 * (int64_t)a + lane, s = 3 * (int64_t)r + lane;
+        d.heading[g] = ((const double *)(blk + L.off[RSB_HEADING]))[s];
+        d.goal[g] = ((const double *)(blk + L.off[RSB_GOAL]))[s];
+        if (w.tracked) { d.vpref_ext[g] = 0.0; if (d.trk_goal_heading) d.trk_goal_heading[g] = ((const double *)(blk + L.off[RSB_GOAL_HEADING]))[s]; }
+        if (w.path_len >= 0 && d.now_goal) d.now_goal[g] = __builtin_nan("");
+    }
+    if (lane == 0) {
+        d.total_dist[a] = w.total_dist; d.step_num[a] = w.step_num; d.status[a] = w.status;
+        d.pref_speed[a] = ((const double *)(blk + L.off[RSB_PREF_SPEED]))[r];
+        d.max_run_dist[a] = ((const double *)(blk + L.off[RSB_MAX_RUN_DIST]))[r];
+        if (w.write_zaxis) d.zaxis[a] = (blk + L.off[RSB_ZAXIS])[r];
+        if (w.write_mode) d.vpref_mode[a] = w.mode;
+        d.nbr_n[a] = w.nbr_n; d.nbr_valid[a] = w.nbr_valid; d.near_n[a] = w.near_n;
+        if (d.trk_nbr0) d.trk_nbr0[a] = w.nbr0;
+        if (w.path_len >= 0 && d.path_len) { d.path_len[a] = w.path_len; d.path_rem[a] = w.path_len; }
+        if (d.clear) d.clear[a] = scene_clearance_empty();            // the new mission has met nobody yet; other rows keep this one as a partner
+    }
+    if (w.tracked && d.trk_st)                                         // the AgentTrack record, word by word from the one initial record
+        for (int k = lane; k < d.trk_words; k += 64) d.trk_st[(int64_t)a * d.trk_words + k] = d.trk_init[k];
+    if (w.path_len > 0 && d.path_pts) {                                // the row's list into its own room
+        const double *src = (const double *)(blk + L.off[RSB_PATH_PTS]) + 3 * (int64_t)first;
+        double *dst = d.path_pts + 3 * path_slot_index(d.W, a);
+        for (int k = lane; k < 3 * w.path_len; k += 64) dst[k] = src[k];
+    }
+}
+
+// ---- the finished list -------------------------------------------------------------------------------------------------------------------
+// The ordered compaction of sca_respawn.h in three launches: a count per tile (ballot and popcount per wavefront, the wavefronts' counts
+// summed in LDS), the scan of the counts by one workgroup (finished_offsets' rule: an exclusive prefix sum, the total behind it), and the
+// write -- every tile recomputes its ballots, a finished row stands at its tile's offset + the finished rows of the tile's earlier
+// wavefronts + finished_rank inside its own, and the first `capacity` rows go into the page-locked block as 48-byte rows.  No atomics.
+struct FinishedDev {
+    const PubRec *rec;
+    const double *total_dist;
+    const int32_t *step_num;
+    int32_t *counts, *offsets;      // [tiles]
+    int n, tiles;
+};
+static_assert(FIN_TILE == 256, "k_finished_* run four wavefronts per tile");
+__device__ __forceinline__ unsigned long long finished_ballot(const FinishedDev &f, int row, uint32_t &flags) {
+    flags = row < f.n ? f.rec[row].flags : 0u;
+    return __ballot(finished_flag(flags));
+}
+__global__ __launch_bounds__(FIN_TILE) void k_finished_count(FinishedDev f) {
+    __shared__ int32_t wsum[FIN_TILE / 64];
+    const int t = (int)threadIdx.x, row = (int)blockIdx.x * FIN_TILE + t;
+    uint32_t flags;
+    const unsigned long long mask = finished_ballot(f, row, flags);
+    if ((t & 63) == 0) wsum[t >> 6] = __popcll(mask);
+    __syncthreads();
+    if (t == 0) f.counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+// one workgroup: the tiles in chunks of FIN_TILE, a running carry between the chunks; head[0] = the total
+__global__ __launch_bounds__(FIN_TILE) void k_finished_scan(FinishedDev f, int32_t *head) {
+    __shared__ int32_t part[FIN_TILE];
+    __shared__ int32_t carry;
+    const int t = (int)threadIdx.x;
+    if (t == 0) carry = 0;
+    __syncthreads();
+    for (int base = 0; base < f.tiles; base += FIN_TILE) {
+        const int i = base + t;
+        const int32_t mine = i < f.tiles ? f.counts[i] : 0;
+        part[t] = mine;
+        __syncthreads();
+        for (int step = 1; step < FIN_TILE; step <<= 1) {              // inclusive scan of the chunk
+            const int32_t add = t >= step ? part[t - step] : 0;
+            __syncthreads();
+            part[t] += add;
+            __syncthreads();
+        }
+        if (i < f.tiles) f.offsets[i] = carry + part[t] - mine;
+        __syncthreads();
+        if (t == FIN_TILE - 1) carry += part[t];
+        __syncthreads();
+    }
+    if (t == 0) head[0] = carry;
+}
+constexpr int FIN_HEAD_BYTES = 64;                                     // the block: the count in its first word, the rows behind the head
+__global__ __launch_bounds__(FIN_TILE) void k_finished_write(FinishedDev f, uint8_t *blk, int capacity) {
+    __shared__ int32_t wsum[FIN_TILE / 64];
+    const int t = (int)threadIdx.x, row = (int)blockIdx.x * FIN_TILE + t, wave = t >> 6;
+    uint32_t flags;
+    const unsigned long long mask = finished_ballot(f, row, flags);
+    if ((t & 63) == 0) wsum[wave] = __popcll(mask);
+    __syncthreads();
+    if (!finished_flag(flags)) return;
+    int at = f.offsets[blockIdx.x] + finished_rank(mask, t & 63);
+    for (int k = 0; k < wave; k++) at += wsum[k];
+    if (at >= capacity) return;
+    const PubRec me = f.rec[row];
+    sca_finished_row out;
+    out.id = row; out.flags = flags; out.step_num = f.step_num[row]; out.reserved = 0;
+    out.total_dist = f.total_dist[row];
+    out.pos[0] = me.px; out.pos[1] = me.py; out.pos[2] = me.pz;
+    ((sca_finished_row *)(blk + FIN_HEAD_BYTES))[at] = out;
+}
+
+}  // namespace sca

@@ -442,8 +442,11 @@ class _FlatAgents:
 
 
 class MACAEnv(_FlatAgents):
-    def __init__(self, v_pref_fn=None, device=0, neighbor_mode=S.NBR_KDTREE, history_capacity=0, device_tracker=False, clearance=False):
+    def __init__(self, v_pref_fn=None, device=0, neighbor_mode=S.NBR_KDTREE, history_capacity=0, device_tracker=False, clearance=False,
+                 path_slots=0):
         self.agents = None
+        self._path_slots = int(path_slots)             # W > 0: the waypoint lists live in slot form (sca_set_path_slots), room for W per agent --
+                                                       # what respawn() needs to give one agent a new list while the others keep theirs
         self.clearance_on = bool(clearance)            # every step also keeps each agent's closest approach (sca_clearance_enable): env.clearance
         self.obstacles = []
         self.kdTree = None
@@ -507,6 +510,76 @@ class MACAEnv(_FlatAgents):
         if self._row_cache is not None:
             raise RuntimeError('clearance: between a policy pass and its env update (agent.find_next_action was called): env.step() first')
         return self.solver.clearance()
+
+    def _upload_paths(self, lists):
+        if not self._path_slots:
+            return super()._upload_paths(lists)
+        for i, p in enumerate(lists):
+            if len(p) > self._path_slots:
+                raise ValueError(f'agent {i} has a path of {len(p)} waypoints, MACAEnv(path_slots={self._path_slots}) has room for {self._path_slots}')
+        self.solver.set_path_slots(self._path_slots, lists)
+
+    # ---- new missions without redefining the swarm (sca_respawn_agents / sca_get_finished) ---------------------------------
+    def respawn(self, agents):
+        """New missions for some agents while everybody else flies on: each Agent of `agents` replaces env.agents[agent.id] -- the
+        reference's rule for assigning pos_global_frame, goal_global_frame, is_at_goal = False, ... to an Agent object between two
+        env.step() calls.  Start, goal, velocity, radius, pref_speed, max_run_dist, goal heading, path and the z-axis flag are read off
+        the agent as set_agents reads them; the row keeps its policy and its per-agent attributes, so an agent whose policy or
+        attributes differ from the row's is a ValueError, raised before any device call.  A path needs MACAEnv(path_slots=W)."""
+        if self.agents is None:
+            raise RuntimeError('respawn: set_agents first')
+        if self._row_cache is not None:
+            raise RuntimeError('respawn: between a policy pass and its env update (agent.find_next_action was called): env.step() first')
+        agents = list(agents)
+        if not agents:
+            return
+        n = len(self.agents)
+        ids = [int(a.id) for a in agents]
+        if min(ids) < 0 or max(ids) >= n or len(set(ids)) != len(ids):
+            raise ValueError('respawn: agent.id names a row of this env, 0 .. %d, and no row twice' % (n - 1))
+        for a in agents:
+            old = self.agents[a.id]
+            if a.policy.policy_id != old.policy.policy_id:
+                raise ValueError(f'respawn: agent {a.id} has policy {type(a.policy).__name__}, the row runs {type(old.policy).__name__} (a row keeps its policy)')
+            for attr, conv in _ATTRS.values():
+                if conv(getattr(a, attr)) != conv(getattr(old, attr)):
+                    raise ValueError(f'respawn: agent {a.id} has {attr} = {getattr(a, attr)}, the row has {getattr(old, attr)} (a row keeps its attributes)')
+            if self._trk_on and self._ext[a.id] and _planner_triple(a) != self._planner_of(a.id):
+                raise ValueError(f'respawn: agent {a.id} has turning_radius / pitchlims {_planner_triple(a)}, the row has {self._planner_of(a.id)}')
+            if self.v_pref_fn is not None and self._ext[a.id]:
+                raise ValueError(f'respawn: agent {a.id} takes v_pref from the host-side v_pref_fn, whose per-agent state the env cannot reset '
+                                 '(use MACAEnv(device_tracker=True))')
+            if len(a._path) > self._path_slots:
+                raise ValueError(f'respawn: agent {a.id} brings a path of {len(a._path)} waypoints: MACAEnv(path_slots=W) with W >= that keeps '
+                                 'the lists in slot form, where one agent\'s list can be replaced')
+        if self._paths_on and not self._path_slots:
+            raise ValueError('respawn: the env follows waypoint lists in block form; MACAEnv(path_slots=W) keeps them in slot form, where one '
+                             'agent\'s list can be replaced')
+        self._sync_paths()                                      # lists assigned since the last step go up first
+        was_done = (self._state('flags')[ids] & 7) != 0
+        start = np.array([a.initial_pos for a in agents], dtype=np.float64)
+        goal6 = np.array([a.goal_pos for a in agents], dtype=np.float64)
+        lists = [[list(map(float, w[:3])) for w in a._path] for a in agents] if self._paths_on else None
+        self.solver.respawn(ids, [a._pos for a in agents], [a._vel for a in agents], [a._heading for a in agents], [a.radius for a in agents],
+                            [a.pref_speed for a in agents], goal6[:, :3], [a.max_run_dist for a in agents], zaxis=S.zaxis_flags(start, goal6),
+                            goal_heading=goal6[:, 3:6] if self._trk_on else None, paths=lists)
+        for a in agents:
+            if self.agents[a.id] is not a:
+                self.agents[a.id]._env = None                    # (the replaced object reads its own attributes again)
+            self.agents[a.id] = a
+            self.goal[a.id] = a.goal_global_frame
+            self._path_assigned.discard(a.id)
+        _bind(agents, self)
+        self._active += int(was_done.sum())
+        self._stale = True
+        self._path_stale = self._paths_on
+        self._nbr_cache = None
+        self._vpref_cache = None
+
+    def finished(self, capacity=None):
+        """The rows that carry any of at-goal / collision / timeout, ascending ids, compacted on the device (sca_get_finished): a
+        structured array of _lib.FINISHED_DTYPE (id, flags, step_num, total_dist, pos)."""
+        return self.solver.finished(capacity)
 
     pos = property(lambda self: self._state('pos'))
     vel = property(lambda self: self._state('vel'))

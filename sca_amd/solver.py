@@ -485,6 +485,50 @@ class BatchedSolver:
                   'sca_get_clearance')
         return out[:max(count, 0)]
 
+    # ---- respawning agents in place (sca_respawn_agents / sca_get_finished) ----------------------------------------------------
+    def respawn(self, ids, pos, vel, heading, radius, pref_speed, goal, max_run_dist, zaxis=None, goal_heading=None, paths=None):
+        """New missions for the rows `ids` (any order, no repeats) while every other row keeps every word it had (sca_respawn_agents).
+        The arrays hold len(ids) rows in the order of `ids`.  Afterwards a named row is what set_agents + set_state (+
+        device_tracker_enable) leave for an agent with these values; it keeps its policy and its per-agent attributes.  zaxis None: the
+        rows keep theirs.  goal_heading: needed when a named row is tracked by the device tracker.  paths (the lists in slot form,
+        set_path_slots): one list of [x, y, z] waypoints per named row; None: the named rows' lists become empty.  Only between two
+        steps; one launch and one synchronisation however many rows are named."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        T = len(ids)
+
+        def arr(a, dt, ct, cols):
+            if a is None:
+                return None, None
+            b = np.asarray(a, dt)
+            b = np.ascontiguousarray(np.broadcast_to(b, (T, cols) if cols else (T,)) if b.ndim == 0 else b)
+            if b.size != T * (cols or 1):
+                raise ValueError(f'respawn: an array of {b.size} values where {T} rows x {cols or 1} are named')
+            return b, _lib.ptr(b, ct)
+        keep = [arr(pos, np.float64, C.c_double, 3), arr(vel, np.float32, C.c_float, 3), arr(heading, np.float64, C.c_double, 3),
+                arr(radius, np.float64, C.c_double, 0), arr(pref_speed, np.float64, C.c_double, 0), arr(goal, np.float64, C.c_double, 3),
+                arr(zaxis, np.uint8, C.c_uint8, 0), arr(max_run_dist, np.float64, C.c_double, 0), arr(goal_heading, np.float64, C.c_double, 3)]
+        poff = ppts = None
+        if paths is not None:
+            if len(paths) != T:
+                raise ValueError(f'respawn: {len(paths)} waypoint lists where {T} rows are named')
+            poff, ppts = paths_csr(paths)
+        self._chk(self.L.sca_respawn_agents(self.ctx, T, _lib.ptr(ids, C.c_int32), *[p for _, p in keep],
+                                            None if poff is None else _lib.ptr(poff, C.c_int32), None if ppts is None else _lib.ptr(ppts, C.c_double)),
+                  'sca_respawn_agents')
+
+    def finished(self, capacity=None):
+        """The rows that carry any of at-goal / collision / timeout, ascending ids: a structured array (_lib.FINISHED_DTYPE: id i32, flags
+        u32, step_num i32, reserved, total_dist f64, pos 3 x f64), compacted on the device -- one synchronisation, and only the finished
+        rows cross the link (sca_get_finished).  capacity: at most that many rows are fetched (None: all); `finished_count` holds their
+        number in either case."""
+        cap = int(self.n) if capacity is None else int(capacity)
+        out = np.zeros(max(cap, 1), _lib.FINISHED_DTYPE)
+        cnt = C.c_int(0)
+        self._chk(self.L.sca_get_finished(self.ctx, out.ctypes.data_as(C.POINTER(_lib.FinishedRow)), cap, C.byref(cnt), _lib.FINISHED_DTYPE.itemsize),
+                  'sca_get_finished')
+        self.finished_count = int(cnt.value)
+        return out[:max(0, min(cap, self.finished_count))]
+
     # ---- scene checkpoints (sca_save_scenes / sca_load_scenes) ---------------------------------------------------------------
     def scene_checkpoint_bytes(self, scene):
         """the size of the blob save_scenes writes for the scene as it stands now"""
