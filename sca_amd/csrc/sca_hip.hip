@@ -25,6 +25,7 @@
 #include "sca_hostio.hip.h"
 #include "sca_forms.h"
 #include "sca_scenes.h"
+#include "sca_scene_restart.h"
 #include "sca_scenes.hip.h"
 #include "sca_clearance.h"
 #include "sca_clearance.hip.h"
@@ -719,6 +720,20 @@ int sca_device_tracker_enable(sca_ctx *c, const double *goal_heading, double tur
 // values as kernel arguments (scalar registers throughout the search).  More than that (the reference has no limit, agent.py:24-29): the
 // PER-AGENT form -- every re-plan gets a wavefront of its own (k_replan_group<64> / k_track_group at any count), which loads ITS agent's
 // three values into scalar registers; slower than the lane-per-plan forms for large counts, never refused.
+// The view a set of classes gives (trk_R_pa is current for every row, and where `many`, trk_plo_pa / trk_phi_pa; otherwise trk_cls).
+// classes: by index; an index nobody uses holds a NaN radius and gets no launch.  many: the per-agent arrays.  Two or more classes: a
+// filter by the class byte, one launch per index in use.  One: its values in the scalars and no filter.  None: the enable call's values.
+static void tracker_view_apply(sca_ctx *c, bool many, const std::vector<std::array<double, 3>> &classes) {
+    sca_dubins::TrackView &V = c->trk_view;
+    V.R_pa = c->trk_R_pa; V.plo_pa = nullptr; V.phi_pa = nullptr; V.cls = nullptr; V.class_id = 0;
+    V.turning_radius = c->trk_enable_vals[0]; V.pitch_lo = c->trk_enable_vals[1]; V.pitch_hi = c->trk_enable_vals[2];
+    c->trk_classes.clear(); c->trk_many = many;
+    if (many) { V.plo_pa = c->trk_plo_pa; V.phi_pa = c->trk_phi_pa; return; }
+    int used = 0, only = -1;
+    for (size_t q = 0; q < classes.size(); q++) if (!std::isnan(classes[q][0])) { used++; only = (int)q; }
+    if (used > 1) { c->trk_classes = classes; V.cls = c->trk_cls; }
+    else if (used == 1) { V.turning_radius = classes[only][0]; V.pitch_lo = classes[only][1]; V.pitch_hi = classes[only][2]; }
+}
 constexpr size_t TRK_MAX_CLASSES = 16;
 static_assert(TRK_MAX_CLASSES == (size_t)TRK_CLASS_CAP, "scene_class_table deals the classes sca_device_tracker_set_agent_params deals");
 int sca_device_tracker_set_agent_params(sca_ctx *c, int n, const double *turning_radius, const double *pitch_lo, const double *pitch_hi) {
@@ -770,15 +785,8 @@ int sca_device_tracker_set_agent_params(sca_ctx *c, int n, const double *turning
         }
         CHK(c, hipMemcpy(c->trk_plo_pa, LO.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
         CHK(c, hipMemcpy(c->trk_phi_pa, HI.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-        c->trk_view.plo_pa = c->trk_plo_pa; c->trk_view.phi_pa = c->trk_phi_pa;
-        c->trk_many = true;
-        return 0;
-    }
-    CHK(c, hipMemcpy(c->trk_cls, cls.data(), (size_t)n, hipMemcpyHostToDevice));
-    if (classes.size() > 1) { c->trk_classes = classes; c->trk_view.cls = c->trk_cls; }
-    else if (!classes.empty()) {                                        // one class after all: its values in the scalars, no filter
-        c->trk_view.turning_radius = classes[0][0]; c->trk_view.pitch_lo = classes[0][1]; c->trk_view.pitch_hi = classes[0][2];
-    }
+    } else CHK(c, hipMemcpy(c->trk_cls, cls.data(), (size_t)n, hipMemcpyHostToDevice));
+    tracker_view_apply(c, many, classes);
     return 0;
 }
 int sca_device_tracker_disable(sca_ctx *c) {
@@ -1028,6 +1036,31 @@ static int agent_params_clear(sca_ctx *c) {
     if (c->trk_on) c->trk_view.nd_per_agent = nullptr;
     return 0;
 }
+// One agent's solver record from the per-agent arrays (sca_set_agent_params', sca_restart_scenes_attrs'): a NULL array stands for the
+// context's value, so all NULL is the record Params stands for, cos_heading_thr as sca_create derived it; range_sq by libm's pow, the
+// threshold by the host bisection, looked up first among the values met so far (few distinct ones).  The ranges are the caller's to check
+// (restart_attr_solver_ok): cos_threshold ends for any input.
+struct SolverArrays { const double *neighbor_dist; const int32_t *max_neighbors; const double *time_step, *time_horizon, *max_speed, *max_heading_change, *dt_nominal; };
+using ThrCache = std::vector<std::pair<double, double>>;               // (max_heading_change, its cosine threshold)
+static AgentPar agent_par_row(const Params &P, const SolverArrays &S, int r, ThrCache &thr_cache) {
+    AgentPar a;
+    a.neighbor_dist = S.neighbor_dist ? S.neighbor_dist[r] : P.neighbor_dist;
+    a.time_step = S.time_step ? S.time_step[r] : P.time_step;
+    a.time_horizon = S.time_horizon ? S.time_horizon[r] : P.time_horizon;
+    a.max_speed = S.max_speed ? S.max_speed[r] : P.max_speed;
+    a.dt_nominal = S.dt_nominal ? S.dt_nominal[r] : P.dt_nominal;
+    a.max_neighbors = S.max_neighbors ? S.max_neighbors[r] : P.max_neighbors;
+    a.pad = 0;
+    a.range_sq = sca_gm::g_pow2(a.neighbor_dist);
+    a.cos_heading_thr = P.cos_heading_thr;
+    if (S.max_heading_change) {
+        const double mhc = S.max_heading_change[r];
+        bool hit = false;
+        for (auto &e : thr_cache) if (e.first == mhc) { a.cos_heading_thr = e.second; hit = true; break; }
+        if (!hit) { a.cos_heading_thr = cos_threshold(mhc); thr_cache.push_back({mhc, a.cos_heading_thr}); }
+    }
+    return a;
+}
 // The reference keeps maxNeighbors / neighborDist / timeStep / timeHorizon / maxSpeed / max_heading_change / dt_nominal on every Agent object
 // (agent.py:24-41) and every policy reads its own agent's (scaPolicy.py:112, util.py:8,17, orca3dPolicyOfficial.py:44,98,108, agent.py:87-99,
 // mampenv.py:90-92).  Arrays of n = the agents of sca_set_agents; a NULL array keeps the context's value for everybody; n = 0 (or all NULL)
@@ -1047,31 +1080,16 @@ int sca_set_agent_params(sca_ctx *c, int n, const double *neighbor_dist, const i
     ARG(c, n == c->n);
     std::vector<AgentPar> h((size_t)n);
     std::vector<double> nd((size_t)n);
-    auto pos = [](double x) { return std::isfinite(x) && x > 0.0; };
-    std::vector<std::pair<double, double>> thr_cache;               // (max_heading_change, its cosine threshold): few distinct values
+    const SolverArrays S{neighbor_dist, max_neighbors, time_step, time_horizon, max_speed, max_heading_change, dt_nominal};
+    ThrCache thr_cache;
     Params env = c->P_ctx;
     double nd_max = 0, ms_max = 0, dt_max = 0;
     for (int i = 0; i < n; i++) {
-        AgentPar a;
-        a.neighbor_dist = neighbor_dist ? neighbor_dist[i] : c->P_ctx.neighbor_dist;
-        a.time_step = time_step ? time_step[i] : c->P_ctx.time_step;
-        a.time_horizon = time_horizon ? time_horizon[i] : c->P_ctx.time_horizon;
-        a.max_speed = max_speed ? max_speed[i] : c->P_ctx.max_speed;
-        a.dt_nominal = dt_nominal ? dt_nominal[i] : c->P_ctx.dt_nominal;
-        a.max_neighbors = max_neighbors ? max_neighbors[i] : c->P_ctx.max_neighbors;
-        a.pad = 0;
-        a.range_sq = sca_gm::g_pow2(a.neighbor_dist);
-        const double mhc = max_heading_change ? max_heading_change[i] : c->P_ctx.max_heading_change;
-        if (!pos(a.neighbor_dist) || !pos(a.time_step) || !pos(a.time_horizon) || !pos(a.max_speed) || !pos(a.dt_nominal) ||
-            a.max_neighbors < 1 || a.max_neighbors > SCA_MAX_NEIGHBORS || !(mhc >= 0.0 && mhc <= M_PI)) {
+        const AgentPar a = agent_par_row(c->P_ctx, S, i, thr_cache);
+        if (!restart_attr_solver_ok(a.neighbor_dist, a.max_neighbors, a.time_step, a.time_horizon, a.max_speed,
+                                    max_heading_change ? max_heading_change[i] : c->P_ctx.max_heading_change, a.dt_nominal)) {
             c->err = "sca_set_agent_params: agent " + std::to_string(i) + " has an attribute out of range (see sca_params)";
             return SCA_ERR_ARG;
-        }
-        a.cos_heading_thr = c->P_ctx.cos_heading_thr;
-        if (max_heading_change) {
-            bool hit = false;
-            for (auto &e : thr_cache) if (e.first == mhc) { a.cos_heading_thr = e.second; hit = true; break; }
-            if (!hit) { a.cos_heading_thr = cos_threshold(mhc); thr_cache.push_back({mhc, a.cos_heading_thr}); }
         }
         h[i] = a; nd[i] = a.neighbor_dist;
         nd_max = std::max(nd_max, a.neighbor_dist); ms_max = std::max(ms_max, a.max_speed); dt_max = std::max(dt_max, a.dt_nominal);
@@ -1728,260 +1746,128 @@ int sca_get_scene_state(sca_ctx *c, int32_t *active, int32_t *steps) {
 // and rewrites its root.  Every named scene gets its head words on every call: count -1 -- NULL, or the entry says so -- and the kernel
 // returns behind the scene's agent rows.  So the three entry points are one launch of one kernel, and the two narrower ones its
 // degenerate cases.
-static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const int32_t *sizes, const double *pos, const float *vel, const double *heading,
-                          const double *radius, const double *pref_speed, const double *goal, const uint8_t *policy, const uint8_t *zaxis,
-                          const double *max_run_dist, const double *goal_heading,
-                          const int32_t *obs_counts = nullptr, const double *obs_pos = nullptr, const double *obs_radius = nullptr,
-                          const sca_restart_attrs *attrs = nullptr, const int32_t *path_offsets = nullptr, const double *path_points = nullptr) {
-    RestartArgs A{count, scene_ids, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading};
-    A.sizes = sizes;
-    // (with `attrs` a policy may move an agent between tracked and untracked: the classes are recomputed below, not cut by policy)
-    const RestartCtx X{c->scenes.on ? c->scenes.v.nscenes : 0, c->scenes.on ? c->scenes.h_off.data() : nullptr, c->state_set, c->scenes.begun, c->trk_on,
-                       restart_refuses_paths(c->paths_on, c->path_W > 0), !attrs && c->trk_on && c->trk_view.R_pa != nullptr, c->h_policy.data()};
-    const RestartCheck k = scene_restart_check(X, A);
-    if (k.fault != RESTART_OK) {
-        const std::string at = std::to_string(k.entry);
-        switch (k.fault) {
-        case RESTART_NO_SCENES: c->err = "sca_restart_scenes: no scenes -- sca_set_scenes first"; break;
-        case RESTART_NO_STATE: c->err = "sca_restart_scenes: no state yet -- sca_set_state first"; break;
-        case RESTART_MID_STEP: c->err = "sca_restart_scenes between a policy pass and its env update: finish the step first"; break;
-        case RESTART_BAD_COUNT: c->err = "sca_restart_scenes: count must be positive and scene_ids not NULL"; break;
-        case RESTART_BAD_ID: c->err = "sca_restart_scenes: scene_ids[" + at + "] = " + std::to_string(scene_ids[k.entry]) + " is not a scene of this context (0 .. " + std::to_string(c->scenes.v.nscenes - 1) + ")"; break;
-        case RESTART_REPEATED_ID: c->err = "sca_restart_scenes: scene_ids[" + at + "] = " + std::to_string(scene_ids[k.entry]) + " is named twice"; break;
-        case RESTART_NO_ARRAYS: c->err = "sca_restart_scenes: pos and heading must not be NULL"; break;
-        case RESTART_NOT_FINITE: c->err = "sca_restart_scenes: row " + at + " holds a number that is not finite"; break;
-        case RESTART_BAD_POLICY: c->err = "sca_restart_scenes: row " + at + " has a policy above SCA_POLICY_RVO3D_DUBINS"; break;
-        case RESTART_NOT_POSITIVE: c->err = "sca_restart_scenes: row " + at + " has a radius, pref_speed or max_run_dist that is not positive"; break;
-        case RESTART_GOAL_HEADING: c->err = "sca_restart_scenes: goal_heading without a device tracker (sca_device_tracker_enable)"; break;
-        case RESTART_BAD_SIZE: c->err = "sca_restart_scenes_sized: sizes[" + at + "] = " + std::to_string(sizes[k.entry]) + ": scene " + std::to_string(scene_ids[k.entry]) + " holds 1 .. " +
-                                        std::to_string(c->scenes.h_off[scene_ids[k.entry] + 1] - c->scenes.h_off[scene_ids[k.entry]]) + " agents (its capacity)"; break;
-        case RESTART_PATHS: c->err = "sca_restart_scenes with waypoint lists set (sca_set_paths): the lists are one block, replacing a scene's lists is not available"; break;
-        default: c->err = "sca_restart_scenes: row " + at + " changes an agent between a tracked and an untracked policy while per-agent tracker attributes are set "
-                          "(sca_device_tracker_set_agent_params): the tracker's classes are cut by policy";
-        }
-        return scene_restart_error_code(k.fault);
-    }
-    const RestartObsCheck ko = restart_obstacles_check(c->scenes.obs_on, c->scenes.h_obs_off.data(), count, scene_ids, obs_counts, obs_pos, obs_radius);
-    if (ko.fault != RESTART_OBS_OK) {
-        const std::string at = std::to_string(ko.entry);
-        switch (ko.fault) {
-        case RESTART_OBS_NO_SLOTS: c->err = "sca_restart_scenes_obstacles: obs_counts[" + at + "] = " + std::to_string(obs_counts[ko.entry]) + " but the context has no obstacle slots -- sca_set_scene_obstacle_slots first"; break;
-        case RESTART_OBS_BAD_COUNT: c->err = "sca_restart_scenes_obstacles: obs_counts[" + at + "] = " + std::to_string(obs_counts[ko.entry]) + ": scene " + std::to_string(scene_ids[ko.entry]) +
-                                             " keeps its set (-1) or takes 0 .. its obstacle capacity" + (c->scenes.obs_on ? " " + std::to_string(c->scenes.h_obs_off[scene_ids[ko.entry] + 1] - c->scenes.h_obs_off[scene_ids[ko.entry]]) : std::string()); break;
-        case RESTART_OBS_NO_ARRAYS: c->err = "sca_restart_scenes_obstacles: obs_pos and obs_radius must not be NULL with " + std::to_string(ko.total) + " obstacles"; break;
-        case RESTART_OBS_NOT_FINITE: c->err = "sca_restart_scenes_obstacles: obstacle row " + at + " has a position that is not finite"; break;
-        default: c->err = "sca_restart_scenes_obstacles: obstacle row " + at + " has a radius that is not positive";
-        }
-        return restart_obstacles_error_code(ko.fault);
-    }
-    RestartAttrs RA;                                                   // every member NULL without `attrs`
-    if (attrs) {
-        const AttrDefaults D{c->P_ctx.neighbor_dist, c->P_ctx.time_step, c->P_ctx.time_horizon, c->P_ctx.max_speed, c->P_ctx.max_heading_change, c->P_ctx.dt_nominal,
-                             c->P_ctx.max_neighbors, c->trk_enable_vals[0], c->trk_enable_vals[1], c->trk_enable_vals[2]};
-        const RestartAttrCheck ka = restart_attrs_check(X, A, attrs, D, &RA);
-        if (ka.fault != RESTART_ATTR_OK) {
-            const std::string at = std::to_string(ka.entry);
-            switch (ka.fault) {
-            case RESTART_ATTR_STRUCT: c->err = "sca_restart_scenes_attrs: attrs->struct_bytes = " + std::to_string(attrs->struct_bytes) + " is not a size of sca_restart_attrs (" +
-                                               std::to_string(RESTART_ATTR_HEAD_BYTES) + " .. " + std::to_string(sizeof(sca_restart_attrs)) + ", whole pointers)"; break;
-            case RESTART_ATTR_RESERVED: c->err = "sca_restart_scenes_attrs: attrs->reserved must be 0"; break;
-            case RESTART_ATTR_NO_TRACKER: c->err = "sca_restart_scenes_attrs: turning_radius / pitch_lo / pitch_hi without a device tracker (sca_device_tracker_enable)"; break;
-            case RESTART_ATTR_SOLVER: c->err = "sca_restart_scenes_attrs: row " + at + " has an attribute out of range (see sca_params)"; break;
-            default: c->err = "sca_restart_scenes_attrs: row " + at + " has a turning radius / pitch limits out of range (R > 0, pitch_lo < pitch_hi)";
-            }
-            return restart_attrs_error_code(ka.fault);
-        }
-    }
-    // the episodes' waypoint lists (sca_restart_scenes_paths): in slot form every entry point is accepted, and a call without path arrays
-    // gives the named rows empty lists
-    const bool path_slots = c->path_W > 0;
-    const RestartPathCheck kp = restart_paths_check(path_slots, c->path_W, k.total, path_offsets, path_points);
-    if (kp.fault != RESTART_PATHS_OK) {
-        const std::string at = std::to_string(kp.entry);
-        switch (kp.fault) {
-        case RESTART_PATHS_NO_SLOTS: c->err = "sca_restart_scenes_paths: path arrays, but the context's lists are not in slot form -- sca_set_path_slots first"; break;
-        case RESTART_PATHS_BAD_START: c->err = "sca_restart_scenes_paths: path_offsets[0] must be 0"; break;
-        case RESTART_PATHS_DECREASING: c->err = "sca_restart_scenes_paths: path_offsets decrease at row " + at; break;
-        case RESTART_PATHS_TOO_LONG: c->err = "sca_restart_scenes_paths: row " + at + " brings a list of " + std::to_string(path_offsets[kp.entry + 1] - path_offsets[kp.entry]) +
-                                              " waypoints, a row has room for " + std::to_string(c->path_W) + " (sca_set_path_slots)"; break;
-        case RESTART_PATHS_NO_POINTS: c->err = "sca_restart_scenes_paths: path_points is NULL with " + std::to_string(kp.total) + " waypoints"; break;
-        default: c->err = "sca_restart_scenes_paths: row " + at + " has a waypoint that is not finite";
-        }
-        return restart_paths_error_code(kp.fault);
-    }
-    const int T = k.total;
-    const RestartLayout L = scene_restart_layout(c->max_n);
-    const size_t sizes_end = (size_t)L.total + sizeof(int32_t) * (size_t)c->max_n;  // behind the layout's sections: the named scenes' new sizes ...
-    const RestartObsLayout OL = restart_obstacles_layout((int64_t)sizes_end, c->max_n, c->max_m);      // ... and behind those the obstacle sections
-    const RestartAttrLayout AL = restart_attrs_layout(OL.total, c->max_n);                             // ... and behind those the attribute sections
-    const RestartPathLayout PL = restart_paths_layout(AL.total, c->max_n, c->path_W);                  // ... and behind those the path sections (none: not in slot form)
-    const size_t blk_bytes = (size_t)PL.total;
-    if (c->scenes.rs_host && c->scenes.rs_bytes < blk_bytes) {                   // the slot form, or a larger room per row, arrived behind the first restart: the
+// The stages, in the order restart_scenes() runs them: the four checks (sca_scenes.h; their texts and restart_pack are sca_scene_restart.h's),
+// restart_block, restart_pack with restart_pack_obstacles and restart_pack_attrs, restart_first_use, restart_launch, the copies behind
+// the launch, the synchronisation, restart_commit.
+static int restart_refuse(sca_ctx *c, const std::string &text, int code) { c->err = text; return code; }
+// the staging block of at least `bytes`: mapped and coherent, as the host state block is -- the kernel reads it in place
+static int restart_block(sca_ctx *c, size_t bytes) {
+    if (c->scenes.rs_host && c->scenes.rs_bytes < bytes) {                       // the slot form, or a larger room per row, arrived behind the first restart: the
         CHK(c, hipStreamSynchronize(c->stream));                                 // block grows (every call ends with its synchronisation: no launch still reads it)
         (void)hipHostFree(c->scenes.rs_host);
         c->scenes.rs_host = nullptr; c->scenes.rs_bytes = 0;
     }
-    if (!c->scenes.rs_host) {                                                    // mapped and coherent, as the host state block is: the kernel reads it in place
-        CHK(c, hipHostMalloc((void **)&c->scenes.rs_host, blk_bytes, hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(c->scenes.rs_host, 0, blk_bytes);
-        c->scenes.rs_bytes = blk_bytes;
+    if (!c->scenes.rs_host) {
+        CHK(c, hipHostMalloc((void **)&c->scenes.rs_host, bytes, hipHostMallocMapped | hipHostMallocCoherent));
+        std::memset(c->scenes.rs_host, 0, bytes);
+        c->scenes.rs_bytes = bytes;
     }
-    uint8_t *b = c->scenes.rs_host;
-    int32_t *ids = (int32_t *)(b + L.off[RS_IDS]), *start = (int32_t *)(b + L.off[RS_START]), *new_size = (int32_t *)(b + L.total);
-    uint8_t *pol = b + L.off[RS_POLICY], *mode = b + L.off[RS_VPREF_MODE];
-    const int32_t *off = c->scenes.h_off.data();
-    scene_restart_starts(count, off, scene_ids, sizes, start);
-    bool policy_changed = false, size_changed = false;
-    for (int e = 0; e < count; e++) {
-        const int lo = off[scene_ids[e]], ns = scene_restart_rows(off, scene_ids, sizes, e);
-        ids[e] = scene_ids[e]; new_size[e] = ns;
-        size_changed = size_changed || ns != c->scenes.h_size[scene_ids[e]];
-        for (int a = lo, r = start[e]; a < lo + ns; a++, r++) {
-            const uint8_t p = policy ? policy[r] : c->h_policy[a];
-            policy_changed = policy_changed || p != c->h_policy[a];
-            pol[r] = p;
-            mode[r] = c->trk_on && restart_policy_tracked(p) ? 1 : 0;      // sca_device_tracker_enable's rule; 0 without a tracker (sca_set_agents')
-        }
+    return 0;
+}
+// the replaced scenes' trees, built where the kernel reads them, at the places restart_pack's head words name
+static void restart_pack_obstacles(uint8_t *b, const RestartObsLayout &OL, const RestartArgs &A, RestartPlan &plan) {
+    const int32_t *head = (const int32_t *)(b + OL.off[RO_HEAD]);
+    ObsRec *rec = (ObsRec *)(b + OL.off[RO_REC]), *sorted = (ObsRec *)(b + OL.off[RO_SORTED]);
+    int32_t *perm = (int32_t *)(b + OL.off[RO_PERM]);
+    KdNode *tree = (KdNode *)(b + OL.off[RO_TREE]);
+    KdWide *wide = (KdWide *)(b + OL.off[RO_WIDE]);
+    for (int e = 0; e < A.count; e++) {
+        const int ms = head[RO_HEAD_WORDS * e], base = head[RO_HEAD_WORDS * e + 1], at = head[RO_HEAD_WORDS * e + 2];
+        if (ms <= 0) continue;
+        scene_obstacle_build(base, ms, A.obs_pos + 3 * (size_t)at, A.obs_radius + at, rec + at, sorted + at, perm + at, tree + 2 * (size_t)at, wide + 2 * (size_t)at);
+        for (int i = 0; i < ms; i++) plan.obs_max_radius = std::max(plan.obs_max_radius, A.obs_radius[at + i]);
     }
-    std::memcpy(b + L.off[RS_POS], pos, sizeof(double) * 3 * (size_t)T);
-    std::memcpy(b + L.off[RS_HEADING], heading, sizeof(double) * 3 * (size_t)T);
-    if (vel) std::memcpy(b + L.off[RS_VEL], vel, sizeof(float) * 3 * (size_t)T); else std::memset(b + L.off[RS_VEL], 0, sizeof(float) * 3 * (size_t)T);
-    uint32_t has = 0;
-    const auto put = [&](int sec, const void *src, size_t bytes, uint32_t bit) { if (src) { std::memcpy(b + L.off[sec], src, bytes); has |= bit; } };
-    put(RS_GOAL, goal, sizeof(double) * 3 * (size_t)T, RESTART_HAS_GOAL);
-    put(RS_GOAL_HEADING, goal_heading, sizeof(double) * 3 * (size_t)T, RESTART_HAS_GOAL_HEADING);
-    put(RS_RADIUS, radius, sizeof(double) * (size_t)T, RESTART_HAS_RADIUS);
-    put(RS_PREF_SPEED, pref_speed, sizeof(double) * (size_t)T, RESTART_HAS_PREF_SPEED);
-    put(RS_MAX_RUN_DIST, max_run_dist, sizeof(double) * (size_t)T, RESTART_HAS_MAX_RUN_DIST);
-    put(RS_ZAXIS, zaxis, (size_t)T, RESTART_HAS_ZAXIS);
-    if (path_slots) {                                                  // the lists travel packed: the offsets and the points actually present
-        has |= RESTART_HAS_PATH_SLOTS;
-        if (path_offsets) {
-            std::memcpy(b + PL.off[RP_OFF], path_offsets, sizeof(int32_t) * ((size_t)T + 1));
-            if (kp.total) std::memcpy(b + PL.off[RP_PTS], path_points, sizeof(double) * 3 * (size_t)kp.total);
-            has |= RESTART_HAS_PATHS;
-        }
-    }
-    double obs_max_r = 0;
-    {                                                                  // every named scene's head words, and the replaced scenes' trees, built where the kernel reads them
-        int32_t *head = (int32_t *)(b + OL.off[RO_HEAD]);
-        ObsRec *rec = (ObsRec *)(b + OL.off[RO_REC]), *sorted = (ObsRec *)(b + OL.off[RO_SORTED]);
-        int32_t *perm = (int32_t *)(b + OL.off[RO_PERM]);
-        KdNode *tree = (KdNode *)(b + OL.off[RO_TREE]);
-        KdWide *wide = (KdWide *)(b + OL.off[RO_WIDE]);
-        int at = 0;                                                    // at most max_obstacles in all: the named scenes' capacities are disjoint ranges
-        for (int e = 0; e < count; e++) {
-            const int ms = obs_counts ? obs_counts[e] : -1;            // -1: the scene keeps its set, and the words behind the count are not read
-            const int base = ms >= 0 ? c->scenes.h_obs_off[scene_ids[e]] : 0;
-            head[RO_HEAD_WORDS * e] = ms; head[RO_HEAD_WORDS * e + 1] = base; head[RO_HEAD_WORDS * e + 2] = at; head[RO_HEAD_WORDS * e + 3] = ms > 0 ? 2 * base : -1;
-            if (ms <= 0) continue;
-            scene_obstacle_build(base, ms, obs_pos + 3 * (size_t)at, obs_radius + at, rec + at, sorted + at, perm + at, tree + 2 * (size_t)at, wide + 2 * (size_t)at);
-            for (int i = 0; i < ms; i++) obs_max_r = std::max(obs_max_r, obs_radius[at + i]);
-            at += ms;
-        }
-    }
-    // ---- the episodes' attributes (sca_restart_scenes_attrs) ----
-    // Solver attributes travel when the call names any, or when the context carries per-agent arrays already (a NULL array then means the
-    // context's value, which the rows must take); planner attributes likewise, with a tracker.  A context without per-agent arrays whose
-    // call names none has nothing to write: every row computes from Params / the view's scalars, which ARE the context's values.
-    const int n_all = c->n;
-    const bool send_solver = attrs && (RA.solver() || c->ap_dev);
-    const bool send_planner = attrs && c->trk_on && (RA.planner() || c->trk_attr_on || c->trk_view.R_pa);
-    std::vector<AgentPar> ap_fill;                                     // first use: every row with the context's own values (alive until the synchronisation)
-    std::vector<double> nd_fill, trk_fill[3];
-    bool ap_first = false, cls_whole = false;
-    double env_nd = 0, env_ms = 0, env_dt = 0;
-    if (send_solver) {
-        if (!c->ap_dev) {
-            // From here on every agent of the context reads d.ap[a] instead of Params: the rows of the scenes that are not named get the
-            // record Params stands for -- range_sq and cos_heading_thr as sca_create derived them -- and so compute the bits they computed
-            // before.  Enqueued in front of the launch, and d.ap / nd_per_agent point at the arrays only behind the fill.
-            AgentPar a0;
-            a0.neighbor_dist = c->P_ctx.neighbor_dist; a0.time_step = c->P_ctx.time_step; a0.time_horizon = c->P_ctx.time_horizon; a0.max_speed = c->P_ctx.max_speed;
-            a0.cos_heading_thr = c->P_ctx.cos_heading_thr; a0.dt_nominal = c->P_ctx.dt_nominal; a0.max_neighbors = c->P_ctx.max_neighbors; a0.pad = 0;
-            a0.range_sq = sca_gm::g_pow2(a0.neighbor_dist);
-            ap_fill.assign((size_t)c->max_n, a0); nd_fill.assign((size_t)c->max_n, a0.neighbor_dist);
-            CHK(c, hipMalloc((void **)&c->ap_dev, sizeof(AgentPar) * (size_t)c->max_n));
-            CHK(c, hipMalloc((void **)&c->ap_nd, sizeof(double) * (size_t)c->max_n));
-            CHK(c, hipMemcpyAsync(c->ap_dev, ap_fill.data(), sizeof(AgentPar) * (size_t)c->max_n, hipMemcpyHostToDevice, c->stream));
-            CHK(c, hipMemcpyAsync(c->ap_nd, nd_fill.data(), sizeof(double) * (size_t)c->max_n, hipMemcpyHostToDevice, c->stream));
-            ap_first = true;
-        }
-        AgentPar *par = (AgentPar *)(b + AL.off[RA_PAR]);
-        double *ndv = (double *)(b + AL.off[RA_ND]);
-        std::vector<std::pair<double, double>> thr_cache;              // (max_heading_change, its cosine threshold): few distinct values
-        for (int r = 0; r < T; r++) {                                  // the derived fields exactly as sca_set_agent_params derives them
-            AgentPar a;
-            a.neighbor_dist = RA.neighbor_dist ? RA.neighbor_dist[r] : c->P_ctx.neighbor_dist;
-            a.time_step = RA.time_step ? RA.time_step[r] : c->P_ctx.time_step;
-            a.time_horizon = RA.time_horizon ? RA.time_horizon[r] : c->P_ctx.time_horizon;
-            a.max_speed = RA.max_speed ? RA.max_speed[r] : c->P_ctx.max_speed;
-            a.dt_nominal = RA.dt_nominal ? RA.dt_nominal[r] : c->P_ctx.dt_nominal;
-            a.max_neighbors = RA.max_neighbors ? RA.max_neighbors[r] : c->P_ctx.max_neighbors;
-            a.pad = 0;
-            a.range_sq = sca_gm::g_pow2(a.neighbor_dist);
-            a.cos_heading_thr = c->P_ctx.cos_heading_thr;
-            if (RA.max_heading_change) {
-                const double mhc = RA.max_heading_change[r];
-                bool hit = false;
-                for (auto &e : thr_cache) if (e.first == mhc) { a.cos_heading_thr = e.second; hit = true; break; }
-                if (!hit) { a.cos_heading_thr = cos_threshold(mhc); thr_cache.push_back({mhc, a.cos_heading_thr}); }
-            }
+}
+// ---- the episodes' attributes (sca_restart_scenes_attrs) ----
+// Solver attributes travel when the call names any, or when the context carries per-agent arrays already (a NULL array then means the
+// context's value, which the rows must take); planner attributes likewise, with a tracker.  A context without per-agent arrays whose
+// call names none has nothing to write: every row computes from Params / the view's scalars, which ARE the context's values.
+// The planner's per-row triples and the classes are worked out on the plan's copies, which replace the context's in restart_commit.
+static void restart_pack_attrs(const sca_ctx *c, uint8_t *b, const RestartBlock &B, const RestartArgs &A, bool attrs, const RestartAttrs &RA, RestartPlan &plan) {
+    const int n_all = c->n, count = A.count;
+    const int32_t *off = c->scenes.h_off.data(), *start = (const int32_t *)(b + B.L.off[RS_START]), *new_size = (const int32_t *)(b + B.new_size_off);
+    const uint8_t *pol = b + B.L.off[RS_POLICY];
+    plan.send_solver = attrs && (RA.solver() || c->ap_dev);
+    plan.send_planner = attrs && c->trk_on && (RA.planner() || c->trk_attr_on || c->trk_view.R_pa);
+    plan.ap_first = plan.send_solver && !c->ap_dev;
+    if (plan.send_solver) {
+        AgentPar *par = (AgentPar *)(b + B.AL.off[RA_PAR]);
+        double *ndv = (double *)(b + B.AL.off[RA_ND]);
+        const SolverArrays S{RA.neighbor_dist, RA.max_neighbors, RA.time_step, RA.time_horizon, RA.max_speed, RA.max_heading_change, RA.dt_nominal};
+        ThrCache thr_cache;
+        for (int r = 0; r < plan.T; r++) {
+            const AgentPar a = agent_par_row(c->P_ctx, S, r, thr_cache);
             par[r] = a; ndv[r] = a.neighbor_dist;
-            env_nd = std::max(env_nd, a.neighbor_dist); env_ms = std::max(env_ms, a.max_speed); env_dt = std::max(env_dt, a.dt_nominal);
+            plan.env_nd = std::max(plan.env_nd, a.neighbor_dist); plan.env_ms = std::max(plan.env_ms, a.max_speed); plan.env_dt = std::max(plan.env_dt, a.dt_nominal);
         }
-        has |= RESTART_HAS_ATTRS;
+        plan.has |= RESTART_HAS_ATTRS;
     }
-    // the planner's per-row triples and the classes: worked out on copies, which replace the context's behind the synchronisation
-    std::vector<TrackTriple> trip_new;
-    std::vector<uint8_t> cls_new;
-    ClassTable table_new = c->trk_table;
-    ClassUpdate cu{0, false, false};
-    const bool table_on = send_planner || (c->trk_on && c->trk_attr_on);         // (a call without `attrs` still changes which rows are occupied)
-    if (table_on) {
-        const TrackTriple def{c->trk_enable_vals[0], c->trk_enable_vals[1], c->trk_enable_vals[2]};
-        trip_new = c->h_trk_trip; cls_new = c->h_trk_cls;
-        trip_new.resize((size_t)n_all, def); cls_new.resize((size_t)n_all, 0);
-        std::vector<uint8_t> pol_after = c->h_policy, travels((size_t)n_all, 0);
-        std::vector<int32_t> size_after = c->scenes.h_size;
-        double *trip = (double *)(b + AL.off[RA_TRIPLE]);
-        for (int e = 0; e < count; e++) {
-            size_after[scene_ids[e]] = new_size[e];
-            for (int a = off[scene_ids[e]], r = start[e]; a < off[scene_ids[e]] + new_size[e]; a++, r++) {
-                pol_after[a] = pol[r];
-                if (!send_planner) continue;
-                trip_new[a] = TrackTriple{RA.turning_radius ? RA.turning_radius[r] : def.R, RA.pitch_lo ? RA.pitch_lo[r] : def.lo, RA.pitch_hi ? RA.pitch_hi[r] : def.hi};
-                trip[3 * r] = trip_new[a].R; trip[3 * r + 1] = trip_new[a].lo; trip[3 * r + 2] = trip_new[a].hi;
-                travels[a] = 1;
-            }
+    plan.table_new = c->trk_table;
+    plan.table_on = plan.send_planner || (c->trk_on && c->trk_attr_on);          // (a call without `attrs` still changes which rows are occupied)
+    if (!plan.table_on) return;
+    const TrackTriple def{c->trk_enable_vals[0], c->trk_enable_vals[1], c->trk_enable_vals[2]};
+    plan.trip_new = c->h_trk_trip; plan.cls_new = c->h_trk_cls;
+    plan.trip_new.resize((size_t)n_all, def); plan.cls_new.resize((size_t)n_all, 0);
+    std::vector<uint8_t> pol_after = c->h_policy, travels((size_t)n_all, 0);
+    double *trip = (double *)(b + B.AL.off[RA_TRIPLE]);
+    for (int e = 0; e < count; e++)
+        for (int a = off[A.scene_ids[e]], r = start[e]; a < off[A.scene_ids[e]] + new_size[e]; a++, r++) {
+            pol_after[a] = pol[r];
+            if (!plan.send_planner) continue;
+            plan.trip_new[a] = TrackTriple{RA.turning_radius ? RA.turning_radius[r] : def.R, RA.pitch_lo ? RA.pitch_lo[r] : def.lo, RA.pitch_hi ? RA.pitch_hi[r] : def.hi};
+            trip[3 * r] = plan.trip_new[a].R; trip[3 * r + 1] = plan.trip_new[a].lo; trip[3 * r + 2] = plan.trip_new[a].hi;
+            travels[a] = 1;
         }
-        if (!c->trk_attr_on) table_new.many = true;                   // first use: whatever classes an earlier call dealt, the table starts afresh
-        cu = scene_class_table(table_new, c->scenes.v.nscenes, off, size_after.data(), pol_after.data(), trip_new.data(), cls_new.data(), travels.data());
-        cls_whole = cu.moved || !c->trk_attr_on;                      // (first use: the device's bytes are an earlier call's, or none)
-        if (send_planner) {
-            uint8_t *cl = b + AL.off[RA_CLASS];
-            for (int e = 0; e < count; e++)
-                for (int a = off[scene_ids[e]], r = start[e]; a < off[scene_ids[e]] + new_size[e]; a++, r++) cl[r] = cls_new[a];
-            has |= RESTART_HAS_PLANNER;
-        }
-        if (!c->trk_attr_on) {
-            // first use: the four per-row arrays exist from here on and are current for EVERY row -- the per-agent form (more classes than
-            // launches are worth) reads them the moment the count passes the cap.  The rows of this call are overwritten by the launch.
-            if (!c->trk_R_pa) { CHK(c, hipMalloc((void **)&c->trk_R_pa, sizeof(double) * (size_t)c->max_n)); CHK(c, hipMalloc((void **)&c->trk_cls, (size_t)c->max_n)); }
-            if (!c->trk_plo_pa) {
-                CHK(c, hipMalloc((void **)&c->trk_plo_pa, sizeof(double) * (size_t)c->max_n));
-                CHK(c, hipMalloc((void **)&c->trk_phi_pa, sizeof(double) * (size_t)c->max_n));
-            }
-            for (auto &v : trk_fill) v.resize((size_t)n_all);
-            for (int a = 0; a < n_all; a++) {
-                const TrackTriple &x = trip_new[a];
-                trk_fill[0][a] = x.R; trk_fill[1][a] = x.lo; trk_fill[2][a] = x.hi;
-            }
-            CHK(c, hipMemcpyAsync(c->trk_R_pa, trk_fill[0].data(), sizeof(double) * (size_t)n_all, hipMemcpyHostToDevice, c->stream));
-            CHK(c, hipMemcpyAsync(c->trk_plo_pa, trk_fill[1].data(), sizeof(double) * (size_t)n_all, hipMemcpyHostToDevice, c->stream));
-            CHK(c, hipMemcpyAsync(c->trk_phi_pa, trk_fill[2].data(), sizeof(double) * (size_t)n_all, hipMemcpyHostToDevice, c->stream));
-        }
+    if (!c->trk_attr_on) plan.table_new.many = true;                  // first use: whatever classes an earlier call dealt, the table starts afresh
+    plan.cu = scene_class_table(plan.table_new, c->scenes.v.nscenes, off, plan.size_now.data(), pol_after.data(), plan.trip_new.data(), plan.cls_new.data(), travels.data());
+    plan.cls_whole = plan.cu.moved || !c->trk_attr_on;                // (first use: the device's bytes are an earlier call's, or none)
+    if (plan.send_planner) {
+        uint8_t *cl = b + B.AL.off[RA_CLASS];
+        for (int e = 0; e < count; e++)
+            for (int a = off[A.scene_ids[e]], r = start[e]; a < off[A.scene_ids[e]] + new_size[e]; a++, r++) cl[r] = plan.cls_new[a];
+        plan.has |= RESTART_HAS_PLANNER;
     }
+}
+// what the first-use fills are copied from: alive until the call's synchronisation
+struct RestartFills { std::vector<AgentPar> ap; std::vector<double> nd, trk[3]; };
+// The first call that sends solver attributes, and the first that deals classes, allocate the per-row arrays and fill them for EVERY row
+// with the context's own values, enqueued in front of the launch (which overwrites the rows of this call).
+static int restart_first_use(sca_ctx *c, const RestartPlan &plan, RestartFills &F) {
+    if (plan.ap_first) {
+        // From here on every agent of the context reads d.ap[a] instead of Params: the rows of the scenes that are not named get the
+        // record Params stands for -- range_sq and cos_heading_thr as sca_create derived them -- and so compute the bits they computed
+        // before.  d.ap / nd_per_agent point at the arrays only in restart_commit.
+        ThrCache none;
+        const AgentPar a0 = agent_par_row(c->P_ctx, SolverArrays{}, 0, none);
+        F.ap.assign((size_t)c->max_n, a0); F.nd.assign((size_t)c->max_n, a0.neighbor_dist);
+        CHK(c, hipMalloc((void **)&c->ap_dev, sizeof(AgentPar) * (size_t)c->max_n));
+        CHK(c, hipMalloc((void **)&c->ap_nd, sizeof(double) * (size_t)c->max_n));
+        CHK(c, hipMemcpyAsync(c->ap_dev, F.ap.data(), sizeof(AgentPar) * (size_t)c->max_n, hipMemcpyHostToDevice, c->stream));
+        CHK(c, hipMemcpyAsync(c->ap_nd, F.nd.data(), sizeof(double) * (size_t)c->max_n, hipMemcpyHostToDevice, c->stream));
+    }
+    if (plan.table_on && !c->trk_attr_on) {
+        // the four per-row arrays exist from here on and are current for EVERY row -- the per-agent form (more classes than launches are
+        // worth) reads them the moment the count passes the cap
+        const size_t n_all = (size_t)c->n;
+        if (!c->trk_R_pa) { CHK(c, hipMalloc((void **)&c->trk_R_pa, sizeof(double) * (size_t)c->max_n)); CHK(c, hipMalloc((void **)&c->trk_cls, (size_t)c->max_n)); }
+        if (!c->trk_plo_pa) {
+            CHK(c, hipMalloc((void **)&c->trk_plo_pa, sizeof(double) * (size_t)c->max_n));
+            CHK(c, hipMalloc((void **)&c->trk_phi_pa, sizeof(double) * (size_t)c->max_n));
+        }
+        for (auto &v : F.trk) v.resize(n_all);
+        for (size_t a = 0; a < n_all; a++) {
+            const TrackTriple &x = plan.trip_new[a];
+            F.trk[0][a] = x.R; F.trk[1][a] = x.lo; F.trk[2][a] = x.hi;
+        }
+        CHK(c, hipMemcpyAsync(c->trk_R_pa, F.trk[0].data(), sizeof(double) * n_all, hipMemcpyHostToDevice, c->stream));
+        CHK(c, hipMemcpyAsync(c->trk_plo_pa, F.trk[1].data(), sizeof(double) * n_all, hipMemcpyHostToDevice, c->stream));
+        CHK(c, hipMemcpyAsync(c->trk_phi_pa, F.trk[2].data(), sizeof(double) * n_all, hipMemcpyHostToDevice, c->stream));
+    }
+    return 0;
+}
+// ONE launch of k_scene_restart, a workgroup per named scene, over the block
+static int restart_launch(sca_ctx *c, int count, const RestartBlock &B, uint32_t has) {
+    const uint8_t *b = c->scenes.rs_host;
     RestartAttrDev at_dev{c->ap_dev, c->ap_nd, c->trk_R_pa, c->trk_plo_pa, c->trk_phi_pa, c->trk_cls};
     RestartDev d{};
     d.rec = c->d.rec;
@@ -2002,52 +1888,40 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
     // pointers are null: restart_obstacles_check has refused every count >= 0, so the kernel returns before it reads them.
     RestartObsDev o{};
     if (c->scenes.obs_on) o = RestartObsDev{c->d.obs, c->d.obs_sorted, c->d.operm, c->d.otree, c->d.owide, (int32_t *)c->scenes.ov.oroot, (int32_t *)c->scenes.ov.oroot + c->scenes.v.nscenes};
-    hipLaunchKernelGGL(k_scene_restart, dim3(count), dim3(RESTART_T), 0, c->stream, d, (const uint8_t *)b, L, has, (const int32_t *)new_size, c->scenes.size, o, OL, at_dev, AL,
-                       RestartPathDev{c->pslot_pts, c->pslot_len, c->path.rem, c->path.now_goal, c->path_W}, PL);
+    hipLaunchKernelGGL(k_scene_restart, dim3(count), dim3(RESTART_T), 0, c->stream, d, b, B.L, has, (const int32_t *)(b + B.new_size_off), c->scenes.size, o, B.OL, at_dev, B.AL,
+                       RestartPathDev{c->pslot_pts, c->pslot_len, c->path.rem, c->path.now_goal, c->path_W}, B.PL);
     CHK(c, hipGetLastError());
-    // the classes came back from the per-agent form, or an index moved in a scene that was not named: the whole class array, one byte per
-    // agent, behind the launch (its rows of the named scenes are the bytes the launch wrote) and in front of the call's one synchronisation
-    if (cls_whole) CHK(c, hipMemcpyAsync(c->trk_cls, cls_new.data(), (size_t)n_all, hipMemcpyHostToDevice, c->stream));
-    std::vector<int32_t> lp_new;                                       // K3's list: the ORCA3D-LP agents, ascending ids (the block holds the named scenes' policies)
-    std::vector<int32_t> size_now = c->scenes.h_size;                  // ... of the rows that are occupied: a vacant row keeps its policy and is in no list
-    for (int e = 0; e < count; e++) size_now[scene_ids[e]] = new_size[e];
-    if (policy_changed || size_changed) {
-        std::vector<uint8_t> now = c->h_policy;
-        for (int e = 0; e < count; e++)
-            for (int a = off[scene_ids[e]], r = start[e]; a < off[scene_ids[e]] + new_size[e]; a++, r++) now[a] = pol[r];
-        for (int sc = 0; sc < c->scenes.v.nscenes; sc++)
-            for (int i = off[sc]; i < off[sc] + size_now[sc]; i++) if (now[i] == SCA_POLICY_ORCA3D_LP) lp_new.push_back(i);
-        if (!lp_new.empty())
-            CHK(c, hipMemcpyAsync(c->lp_list, lp_new.data(), sizeof(int32_t) * lp_new.size(), hipMemcpyHostToDevice, c->stream));
-    }
-    CHK(c, hipStreamSynchronize(c->stream));
-    // the device has the new episodes: now the host mirrors follow (a call that failed above has left them alone) -- policies, the radius a
-    // later sca_set_state uploads, the kd permutation while the host holds it; the maxima only grow (conservative filters).  "A refused call
-    // changes nothing" is about the refusals above.  A runtime error of the list copy or the synchronisation behind the launch is not one: the
-    // device may then hold the new episode while h_policy, h_rec and h_perm hold the old -- as after any failed HIP call, the context is to
-    // be set up again (sca_set_agents), not stepped on.
-    for (int e = 0; e < count; e++) {
-        for (int a = off[scene_ids[e]], r = start[e]; a < off[scene_ids[e]] + new_size[e]; a++, r++) {
+    return 0;
+}
+// The device has the new episodes: now the host mirrors follow (a call that failed before has left them alone) -- policies, the radius a
+// later sca_set_state uploads, the kd permutation while the host holds it; the maxima only grow (conservative filters).  "A refused call
+// changes nothing" is about the refusals of the checks.  A runtime error of the list copy or the synchronisation behind the launch is not
+// one: the device may then hold the new episode while h_policy, h_rec and h_perm hold the old -- as after any failed HIP call, the context
+// is to be set up again (sca_set_agents), not stepped on.
+static void restart_commit(sca_ctx *c, const RestartBlock &B, const RestartArgs &A, RestartPlan &plan) {
+    const uint8_t *b = c->scenes.rs_host;
+    const int32_t *off = c->scenes.h_off.data(), *start = (const int32_t *)(b + B.L.off[RS_START]), *new_size = (const int32_t *)(b + B.new_size_off);
+    const uint8_t *pol = b + B.L.off[RS_POLICY];
+    for (int e = 0, k = 0; e < A.count; e++) {
+        const int lo = off[A.scene_ids[e]], hi = off[A.scene_ids[e] + 1];
+        for (int a = lo, r = start[e]; a < lo + new_size[e]; a++, r++) {
             c->h_policy[a] = pol[r];
-            if (radius) { c->h_rec[a].radius = radius[r]; c->max_radius = std::max(c->max_radius, radius[r]); }
-            if (pref_speed) c->max_pref_speed = std::max(c->max_pref_speed, pref_speed[r]);
+            if (A.radius) c->h_rec[a].radius = A.radius[r];
         }
-        for (int a = off[scene_ids[e]]; a < off[scene_ids[e] + 1]; a++) c->h_perm[a] = a;        // (the vacant rows' too: the identity over the capacity)
-        if (path_slots)                                               // the lists' lengths and the "straight-line agent with a path" bytes (sca_set_vpref, paths_clear)
-            for (int a = off[scene_ids[e]], r = start[e]; a < off[scene_ids[e] + 1]; a++, r++) {
-                const int32_t len = path_offsets && a < off[scene_ids[e]] + new_size[e] ? path_offsets[r + 1] - path_offsets[r] : 0;
-                c->h_path_len[a] = len;
-                c->h_path_vpref[a] = len > 0 && !restart_policy_tracked(pol[r]);       // (len > 0: an occupied row, pol[r] is its policy)
-            }
+        for (int a = lo; a < hi; a++) c->h_perm[a] = a;                // (the vacant rows' too: the identity over the capacity)
+        if (c->path_W > 0)                                            // the lists' lengths and the "straight-line agent with a path" bytes, over the capacity
+            for (int a = lo; a < hi; a++, k++) { c->h_path_len[a] = plan.path_len[k]; c->h_path_vpref[a] = plan.path_vpref[k]; }
     }
-    if (policy_changed || size_changed) c->h_lp_list.swap(lp_new);
-    c->scenes.h_size.swap(size_now);
-    if (ko.replaced > 0) {
-        for (int e = 0; e < count; e++) if (obs_counts[e] >= 0) c->scenes.h_obs_count[scene_ids[e]] = obs_counts[e];
-        c->max_obs_radius = std::max(c->max_obs_radius, obs_max_r);    // only grows: a conservative filter (sca_set_scene_obstacles)
+    c->max_radius = std::max(c->max_radius, plan.max_radius);
+    c->max_pref_speed = std::max(c->max_pref_speed, plan.max_pref_speed);
+    if (plan.policy_changed || plan.size_changed) c->h_lp_list.swap(plan.lp_list);
+    c->scenes.h_size.swap(plan.size_now);
+    if (plan.obs_replaced > 0) {
+        for (int e = 0; e < A.count; e++) if (A.obs_counts[e] >= 0) c->scenes.h_obs_count[A.scene_ids[e]] = A.obs_counts[e];
+        c->max_obs_radius = std::max(c->max_obs_radius, plan.obs_max_radius);    // only grows: a conservative filter (sca_set_scene_obstacles)
     }
-    if (send_solver) {
-        if (ap_first) {
+    if (plan.send_solver) {
+        if (plan.ap_first) {
             c->d.ap = c->ap_dev;
             if (c->trk_on) c->trk_view.nd_per_agent = c->ap_nd;
         }
@@ -2055,72 +1929,100 @@ static int restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const
         // max_pref_speed and max_obs_radius above the envelope only grows under restarts: with scenes it feeds collide_reach (a
         // conservative filter of K1's candidate lists and K4's walks) and nothing that reaches a value -- every kernel reads d.ap[a] for
         // the fields below (agent_params), the grid and SCA_NBR_AUTO's `fits`, which read neighbor_dist, have no scene form.
-        if (env_nd > c->P.neighbor_dist) { c->P.neighbor_dist = env_nd; c->P.range_sq = sca_gm::g_pow2(env_nd); c->grid.inv_cell = grid_inv_cell(env_nd); }
-        c->P.max_speed = std::max(c->P.max_speed, env_ms);
-        c->P.dt_nominal = std::max(c->P.dt_nominal, env_dt);
+        if (plan.env_nd > c->P.neighbor_dist) { c->P.neighbor_dist = plan.env_nd; c->P.range_sq = sca_gm::g_pow2(plan.env_nd); c->grid.inv_cell = grid_inv_cell(plan.env_nd); }
+        c->P.max_speed = std::max(c->P.max_speed, plan.env_ms);
+        c->P.dt_nominal = std::max(c->P.dt_nominal, plan.env_dt);
     }
-    if (table_on) {
-        c->h_trk_trip.swap(trip_new); c->h_trk_cls.swap(cls_new); c->trk_table = table_new; c->trk_attr_on = true;
-        // the view: the per-agent form beyond the cap; classes (a filter by the class byte, one launch per index in use) for two or more;
-        // one class left: its values in the scalars and no filter (sca_device_tracker_set_agent_params' rule).  R_pa is current for every row.
-        sca_dubins::TrackView &V = c->trk_view;
-        V.R_pa = c->trk_R_pa; V.plo_pa = nullptr; V.phi_pa = nullptr; V.cls = nullptr; V.class_id = 0;
-        V.turning_radius = c->trk_enable_vals[0]; V.pitch_lo = c->trk_enable_vals[1]; V.pitch_hi = c->trk_enable_vals[2];
-        c->trk_classes.clear(); c->trk_many = false;
-        int only = -1;
-        const int used = cu.many ? TRK_CLASS_CAP + 1 : class_table_used(table_new, &only);
-        if (cu.many) { V.plo_pa = c->trk_plo_pa; V.phi_pa = c->trk_phi_pa; c->trk_many = true; }
-        else if (used > 1) {
-            for (int q = 0; q < TRK_CLASS_CAP; q++)
-                if (table_new.users[q] > 0) {
-                    c->trk_classes.resize((size_t)q + 1, std::array<double, 3>{std::nan(""), 0.0, 0.0});   // (an index nobody uses: no launch)
-                    c->trk_classes[q] = {table_new.val[q].R, table_new.val[q].lo, table_new.val[q].hi};
-                }
-            V.cls = c->trk_cls;
-        } else if (used == 1) { V.turning_radius = table_new.val[only].R; V.pitch_lo = table_new.val[only].lo; V.pitch_hi = table_new.val[only].hi; }
+    if (plan.table_on) {
+        c->h_trk_trip.swap(plan.trip_new); c->h_trk_cls.swap(plan.cls_new); c->trk_table = plan.table_new; c->trk_attr_on = true;
+        std::vector<std::array<double, 3>> classes;                    // by index: one the table does not use holds NaN
+        for (int q = 0; q < TRK_CLASS_CAP && !plan.cu.many; q++)
+            if (plan.table_new.users[q] > 0) {
+                classes.resize((size_t)q + 1, std::array<double, 3>{std::nan(""), 0.0, 0.0});
+                classes[q] = {plan.table_new.val[q].R, plan.table_new.val[q].lo, plan.table_new.val[q].hi};
+            }
+        tracker_view_apply(c, plan.cu.many, classes);
     }
     c->scenes.partial = scenes_any_partial(c->scenes.v.nscenes, off, c->scenes.h_size.data());
-    scene_harvest_clear_fresh(c, count, scene_ids);                    // an uncollected harvest of a restarted scene is gone (behind the synchronisation above)
+    scene_harvest_clear_fresh(c, A.count, A.scene_ids);                // an uncollected harvest of a restarted scene is gone (behind the call's synchronisation)
     c->h_pos_valid = false;                                            // (no host mirror of the positions is kept, as in sca_step_host)
     c->near_valid = false;
     // (scene_live_valid stays what it is: the kernel wrote the named scenes' counters itself, and where the others' are stale the recount
     // that is due anyway finds n_s live agents in a restarted scene too)
+}
+// A: the caller's arrays as the entry point took them (an entry point that does not take an array leaves it NULL); attrs: NULL but for
+// sca_restart_scenes_attrs / _paths
+static int restart_scenes(sca_ctx *c, const RestartArgs &A, const sca_restart_attrs *attrs = nullptr) {
+    // (with `attrs` a policy may move an agent between tracked and untracked: the classes are recomputed, not cut by policy)
+    const RestartCtx X{c->scenes.on ? c->scenes.v.nscenes : 0, c->scenes.on ? c->scenes.h_off.data() : nullptr, c->state_set, c->scenes.begun, c->trk_on,
+                       restart_refuses_paths(c->paths_on, c->path_W > 0), !attrs && c->trk_on && c->trk_view.R_pa != nullptr, c->h_policy.data()};
+    const RestartCheck k = scene_restart_check(X, A);
+    if (k.fault != RESTART_OK) return restart_refuse(c, restart_fault_text(k, X, A), scene_restart_error_code(k.fault));
+    const int32_t *obs_cap = c->scenes.obs_on ? c->scenes.h_obs_off.data() : nullptr;
+    const RestartObsCheck ko = restart_obstacles_check(obs_cap != nullptr, obs_cap, A.count, A.scene_ids, A.obs_counts, A.obs_pos, A.obs_radius);
+    if (ko.fault != RESTART_OBS_OK) return restart_refuse(c, restart_obstacles_fault_text(ko, A, obs_cap), restart_obstacles_error_code(ko.fault));
+    RestartAttrs RA;                                                   // every member NULL without `attrs`
+    if (attrs) {
+        const AttrDefaults D{c->P_ctx.neighbor_dist, c->P_ctx.time_step, c->P_ctx.time_horizon, c->P_ctx.max_speed, c->P_ctx.max_heading_change, c->P_ctx.dt_nominal,
+                             c->P_ctx.max_neighbors, c->trk_enable_vals[0], c->trk_enable_vals[1], c->trk_enable_vals[2]};
+        const RestartAttrCheck ka = restart_attrs_check(X, A, attrs, D, &RA);
+        if (ka.fault != RESTART_ATTR_OK) return restart_refuse(c, restart_attrs_fault_text(ka, attrs), restart_attrs_error_code(ka.fault));
+    }
+    // the episodes' waypoint lists (sca_restart_scenes_paths): in slot form every entry point is accepted, and a call without path arrays
+    // gives the named rows empty lists
+    const RestartPathCheck kp = restart_paths_check(c->path_W > 0, c->path_W, k.total, A.path_offsets, A.path_points);
+    if (kp.fault != RESTART_PATHS_OK) return restart_refuse(c, restart_paths_fault_text(kp, A, c->path_W), restart_paths_error_code(kp.fault));
+
+    const RestartBlock B = restart_block_layout(c->max_n, c->max_m, c->path_W);
+    if (int r = restart_block(c, (size_t)B.total)) return r;
+    uint8_t *b = c->scenes.rs_host;
+    RestartPlan plan = restart_pack(b, B, X, A, c->scenes.h_size.data(), obs_cap, c->path_W);
+    plan.obs_replaced = ko.replaced;
+    restart_pack_obstacles(b, B.OL, A, plan);
+    restart_pack_attrs(c, b, B, A, attrs != nullptr, RA, plan);
+    RestartFills fills;
+    if (int r = restart_first_use(c, plan, fills)) return r;
+    if (int r = restart_launch(c, A.count, B, plan.has)) return r;
+    // the classes came back from the per-agent form, or an index moved in a scene that was not named: the whole class array, one byte per
+    // agent, behind the launch (its rows of the named scenes are the bytes the launch wrote) and in front of the call's one synchronisation
+    if (plan.cls_whole) CHK(c, hipMemcpyAsync(c->trk_cls, plan.cls_new.data(), (size_t)c->n, hipMemcpyHostToDevice, c->stream));
+    if (!plan.lp_list.empty()) CHK(c, hipMemcpyAsync(c->lp_list, plan.lp_list.data(), sizeof(int32_t) * plan.lp_list.size(), hipMemcpyHostToDevice, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    restart_commit(c, B, A, plan);
     return 0;
 }
 int sca_restart_scenes(sca_ctx *c, int count, const int32_t *scene_ids, const double *pos, const float *vel, const double *heading,
                        const double *radius, const double *pref_speed, const double *goal, const uint8_t *policy, const uint8_t *zaxis,
                        const double *max_run_dist, const double *goal_heading) {
     API_ENTER(c);
-    return restart_scenes(c, count, scene_ids, nullptr, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading);
+    return restart_scenes(c, RestartArgs{count, scene_ids, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading});
 }
 int sca_restart_scenes_sized(sca_ctx *c, int count, const int32_t *scene_ids, const int32_t *sizes, const double *pos, const float *vel,
                              const double *heading, const double *radius, const double *pref_speed, const double *goal, const uint8_t *policy,
                              const uint8_t *zaxis, const double *max_run_dist, const double *goal_heading) {
     API_ENTER(c);
-    return restart_scenes(c, count, scene_ids, sizes, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading);
+    return restart_scenes(c, RestartArgs{count, scene_ids, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading, sizes});
 }
 int sca_restart_scenes_obstacles(sca_ctx *c, int count, const int32_t *scene_ids, const int32_t *sizes, const int32_t *obs_counts, const double *obs_pos,
                                  const double *obs_radius, const double *pos, const float *vel, const double *heading, const double *radius,
                                  const double *pref_speed, const double *goal, const uint8_t *policy, const uint8_t *zaxis, const double *max_run_dist,
                                  const double *goal_heading) {
     API_ENTER(c);
-    return restart_scenes(c, count, scene_ids, sizes, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading, obs_counts, obs_pos, obs_radius);
+    return restart_scenes(c, RestartArgs{count, scene_ids, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading, sizes, obs_counts, obs_pos, obs_radius});
 }
 int sca_restart_scenes_attrs(sca_ctx *c, int count, const int32_t *scene_ids, const int32_t *sizes, const int32_t *obs_counts, const double *obs_pos,
                              const double *obs_radius, const sca_restart_attrs *attrs, const double *pos, const float *vel, const double *heading,
                              const double *radius, const double *pref_speed, const double *goal, const uint8_t *policy, const uint8_t *zaxis,
                              const double *max_run_dist, const double *goal_heading) {
     API_ENTER(c);
-    return restart_scenes(c, count, scene_ids, sizes, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading, obs_counts, obs_pos, obs_radius,
-                          attrs);
+    return restart_scenes(c, RestartArgs{count, scene_ids, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading, sizes, obs_counts, obs_pos, obs_radius}, attrs);
 }
 int sca_restart_scenes_paths(sca_ctx *c, int count, const int32_t *scene_ids, const int32_t *sizes, const int32_t *obs_counts, const double *obs_pos,
                              const double *obs_radius, const sca_restart_attrs *attrs, const int32_t *path_offsets, const double *path_points,
                              const double *pos, const float *vel, const double *heading, const double *radius, const double *pref_speed, const double *goal,
                              const uint8_t *policy, const uint8_t *zaxis, const double *max_run_dist, const double *goal_heading) {
     API_ENTER(c);
-    return restart_scenes(c, count, scene_ids, sizes, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading, obs_counts, obs_pos, obs_radius,
-                          attrs, path_offsets, path_points);
+    return restart_scenes(c, RestartArgs{count, scene_ids, pos, vel, heading, radius, pref_speed, goal, policy, zaxis, max_run_dist, goal_heading, sizes, obs_counts, obs_pos, obs_radius, path_offsets, path_points}, attrs);
 }
 // ---- scene checkpoints (include/sca_hip.h; the layout, the check and the calls' rules are sca_scenes.h's, the kernels sca_scenes.hip.h's) ---------
 static_assert(CKPT_LIB_VERSION == 103, "CkptHeader::lib_version is sca_version()");

@@ -140,6 +140,8 @@ struct RestartArgs {
     const double *pos; const float *vel; const double *heading, *radius, *pref_speed, *goal; const uint8_t *policy, *zaxis;
     const double *max_run_dist, *goal_heading;
     const int32_t *sizes = nullptr;            // [count] sca_restart_scenes_sized: the rows each named scene brings; NULL: its capacity
+    const int32_t *obs_counts = nullptr; const double *obs_pos = nullptr, *obs_radius = nullptr;   // sca_restart_scenes_obstacles (restart_obstacles_check)
+    const int32_t *path_offsets = nullptr; const double *path_points = nullptr;                    // sca_restart_scenes_paths (restart_paths_check)
 };
 // what the rules read of the context
 struct RestartCtx {
@@ -630,6 +632,21 @@ inline RestartPathLayout restart_paths_layout(int64_t begin, int max_n, int W) {
 }
 // the rows' lists are written (slot form): from the block's path sections, or empty where the call brought none
 constexpr uint32_t RESTART_HAS_PATH_SLOTS = 256, RESTART_HAS_PATHS = 512;
+
+// The whole staging block: the agent sections, behind them the named scenes' new sizes (one int32 per named scene, at most max_n of them),
+// then the obstacle, attribute and path sections.  The ONE place that knows the order of the parts: sca_restart_scenes allocates `total`
+// bytes and launches with the members, the harnesses walk the same value.
+struct RestartBlock { RestartLayout L; int64_t new_size_off; RestartObsLayout OL; RestartAttrLayout AL; RestartPathLayout PL; int64_t total; };
+inline RestartBlock restart_block_layout(int max_n, int max_m, int W) {
+    RestartBlock B;
+    B.L = scene_restart_layout(max_n);
+    B.new_size_off = B.L.total;
+    B.OL = restart_obstacles_layout(B.new_size_off + (int64_t)sizeof(int32_t) * (int64_t)max_n, max_n, max_m);
+    B.AL = restart_attrs_layout(B.OL.total, max_n);
+    B.PL = restart_paths_layout(B.AL.total, max_n, W);
+    B.total = B.PL.total;
+    return B;
+}
 
 // ---- scene checkpoints (sca_save_scenes / sca_load_scenes) ------------------------------------------------------------------------------------------
 // A scene's whole MUTABLE state as one blob of bytes: what scene_restart_fill / scene_restart_paths reset plus what PartMig carries

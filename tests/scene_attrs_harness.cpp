@@ -42,14 +42,12 @@ int attrs_struct_bytes(void) { return (int)sizeof(sca_restart_attrs); }
 // the new sizes, the obstacle sections and the attribute sections, in that order; returns the section count, *total: the block's bytes
 int block_sections(int max_n, int max_m, int64_t *begin, int64_t *bytes, int64_t *total) {
     int k = 0;
-    const RestartLayout L = scene_restart_layout(max_n);
-    for (int s = 0; s < RS_SECTIONS; s++, k++) { begin[k] = L.off[s]; bytes[k] = restart_section_row_bytes(s) * (int64_t)max_n; }
-    begin[k] = L.total; bytes[k] = 4 * (int64_t)max_n; k++;
-    const RestartObsLayout OL = restart_obstacles_layout(L.total + 4 * (int64_t)max_n, max_n, max_m);
-    for (int s = 0; s < RO_SECTIONS; s++, k++) { begin[k] = OL.off[s]; bytes[k] = restart_obs_section_bytes(s, max_n, max_m); }
-    const RestartAttrLayout AL = restart_attrs_layout(OL.total, max_n);
-    for (int s = 0; s < RA_SECTIONS; s++, k++) { begin[k] = AL.off[s]; bytes[k] = restart_attr_row_bytes(s) * (int64_t)max_n; }
-    *total = AL.total;
+    const RestartBlock B = restart_block_layout(max_n, max_m, 0);      // (no slot form: the path sections behind are empty, the block ends with the attributes')
+    for (int s = 0; s < RS_SECTIONS; s++, k++) { begin[k] = B.L.off[s]; bytes[k] = restart_section_row_bytes(s) * (int64_t)max_n; }
+    begin[k] = B.new_size_off; bytes[k] = (int64_t)sizeof(int32_t) * max_n; k++;
+    for (int s = 0; s < RO_SECTIONS; s++, k++) { begin[k] = B.OL.off[s]; bytes[k] = restart_obs_section_bytes(s, max_n, max_m); }
+    for (int s = 0; s < RA_SECTIONS; s++, k++) { begin[k] = B.AL.off[s]; bytes[k] = restart_attr_row_bytes(s) * (int64_t)max_n; }
+    *total = B.AL.total;
     return k;
 }
 int attr_section_count(void) { return RA_SECTIONS; }

@@ -33,11 +33,10 @@ void restart_obs_check(int slots_on, const int32_t *cap_offsets, int count, cons
 // off: [RO_SECTIONS + 1] the sections' offsets and the block's end; bytes: [RO_SECTIONS] what each section must hold; returns where the
 // agent sections and the sizes behind them end (what the obstacle sections are laid behind)
 long long obs_layout(int max_n, int max_obstacles, long long *off, long long *bytes) {
-    const int64_t begin = scene_restart_layout(max_n).total + 4 * (int64_t)max_n;
-    const RestartObsLayout L = restart_obstacles_layout(begin, max_n, max_obstacles);
-    for (int s = 0; s < RO_SECTIONS; s++) { off[s] = L.off[s]; bytes[s] = restart_obs_section_bytes(s, max_n, max_obstacles); }
-    off[RO_SECTIONS] = L.total;
-    return begin;
+    const RestartBlock B = restart_block_layout(max_n, max_obstacles, 0);
+    for (int s = 0; s < RO_SECTIONS; s++) { off[s] = B.OL.off[s]; bytes[s] = restart_obs_section_bytes(s, max_n, max_obstacles); }
+    off[RO_SECTIONS] = B.OL.total;
+    return B.new_size_off + (int64_t)sizeof(int32_t) * max_n;          // one int32 per named scene, at most max_n of them
 }
 void obs_layout_constants(int *out6) {
     out6[0] = RO_SECTIONS; out6[1] = RO_HEAD_WORDS; out6[2] = (int)RO_REC_BYTES; out6[3] = (int)RO_TREE_BYTES; out6[4] = (int)RO_WIDE_BYTES; out6[5] = (int)RS_ALIGN;
@@ -99,9 +98,9 @@ int main() {
     }
     {   // the block's obstacle sections
         for (int max_n : {1, 16, 100}) for (int max_m : {0, 1, 8, 1491}) {
-            const int64_t begin = scene_restart_layout(max_n).total + 4 * (int64_t)max_n;
-            const RestartObsLayout L = restart_obstacles_layout(begin, max_n, max_m);
-            EXPECT(L.off[0] >= begin);
+            const RestartBlock B = restart_block_layout(max_n, max_m, 0);
+            const RestartObsLayout &L = B.OL;
+            EXPECT(L.off[0] >= B.new_size_off + (int64_t)sizeof(int32_t) * max_n);
             for (int s = 0; s < RO_SECTIONS; s++) {
                 EXPECT(L.off[s] % 16 == 0);
                 EXPECT(L.off[s] + restart_obs_section_bytes(s, max_n, max_m) <= (s + 1 < RO_SECTIONS ? L.off[s + 1] : L.total));

@@ -55,16 +55,13 @@ uint32_t path_bits() { return RESTART_HAS_PATH_SLOTS | RESTART_HAS_PATHS; }
 // every section of the restart's block as sca_restart_scenes lays it out: begin / size per section, in order; returns how many
 int block_sections(int max_n, int max_m, int W, int64_t *begin, int64_t *size, int64_t *total) {
     int k = 0;
-    const RestartLayout L = scene_restart_layout(max_n);
-    for (int s = 0; s < RS_SECTIONS; s++, k++) { begin[k] = L.off[s]; size[k] = restart_section_row_bytes(s) * (int64_t)max_n; }
-    begin[k] = L.total; size[k] = 4 * (int64_t)max_n; k++;                                  // the new sizes
-    const RestartObsLayout OL = restart_obstacles_layout(L.total + 4 * (int64_t)max_n, max_n, max_m);
-    for (int s = 0; s < RO_SECTIONS; s++, k++) { begin[k] = OL.off[s]; size[k] = restart_obs_section_bytes(s, max_n, max_m); }
-    const RestartAttrLayout AL = restart_attrs_layout(OL.total, max_n);
-    for (int s = 0; s < RA_SECTIONS; s++, k++) { begin[k] = AL.off[s]; size[k] = restart_attr_row_bytes(s) * (int64_t)max_n; }
-    const RestartPathLayout PL = restart_paths_layout(AL.total, max_n, W);
-    for (int s = 0; s < RP_SECTIONS; s++, k++) { begin[k] = PL.off[s]; size[k] = restart_path_section_bytes(s, max_n, W); }
-    *total = PL.total;
+    const RestartBlock B = restart_block_layout(max_n, max_m, W);
+    for (int s = 0; s < RS_SECTIONS; s++, k++) { begin[k] = B.L.off[s]; size[k] = restart_section_row_bytes(s) * (int64_t)max_n; }
+    begin[k] = B.new_size_off; size[k] = (int64_t)sizeof(int32_t) * max_n; k++;              // the new sizes
+    for (int s = 0; s < RO_SECTIONS; s++, k++) { begin[k] = B.OL.off[s]; size[k] = restart_obs_section_bytes(s, max_n, max_m); }
+    for (int s = 0; s < RA_SECTIONS; s++, k++) { begin[k] = B.AL.off[s]; size[k] = restart_attr_row_bytes(s) * (int64_t)max_n; }
+    for (int s = 0; s < RP_SECTIONS; s++, k++) { begin[k] = B.PL.off[s]; size[k] = restart_path_section_bytes(s, max_n, W); }
+    *total = B.total;
     return k;
 }
 

@@ -7,7 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from scene_util import Slots, assert_scene_equals_alone, circle_scene, context, everything, load_any, observe, rc_of, restart_all
+from scene_util import (Slots, assert_scene_equals_alone, assert_slots_equal_alone, assert_vacant, circle_scene, context, everything, load_any, observe, rc_of,
+                        restart_all)
 
 pytestmark = pytest.mark.gpu
 
@@ -264,3 +265,64 @@ def test_refusals_by_state(S):
     restart_all(sol, [0], [new], goal_heading=None)                                              # ... and without them it is taken
     assert sol.scene_state()['steps'].tolist() == [0, 3]
     sol.close()
+
+
+def _alone(S, e, obstacles=None, solver=None, planner=None, lists=None):
+    """a fresh context of the episode alone with what a restart can bring: its obstacle set, attributes and waypoint lists"""
+    n = e['n']
+    sol = S.BatchedSolver(max_agents=n, max_obstacles=max(len(obstacles[1]) if obstacles else 0, 1))
+    sol.set_agents(e['radius'], e['pref_speed'], e['goal'], e['policy'], e['zaxis'], e['max_run_dist'])
+    if solver:
+        sol.set_agent_params(**solver)
+    sol.set_scenes(np.array([0, n], np.int32))
+    if obstacles and len(obstacles[1]):
+        sol.set_scene_obstacles([obstacles])
+    if lists is not None:
+        sol.set_paths(lists)
+    sol.set_state(e['pos'], e['vel'], e['heading'], np.zeros(n, np.uint8))
+    sol.device_tracker_enable(e['goal_heading'], in_pass=True)
+    if planner:
+        sol.device_tracker_set_agent_params(**planner)
+    return sol
+
+
+def test_first_uses_in_one_context(S):
+    """The three allocate-and-fill stages around the launch, crossed in ONE context: scenes of capacities 3, 1 and 4, the tracker, obstacle
+    slots and path slots (W = 2) on, tracked, ORCA3D-LP and other policies mixed.  Scene 2 is restarted five times -- plain; sized (2 of 4);
+    with 2 obstacles; with attributes (the first use of the per-agent solver records and of the planner's per-row arrays and classes);
+    with lists -- and after each restart and two steps every scene equals a fresh context of its episode alone, every value: the scenes
+    that are never named run on through the first-use fills as if nothing had happened."""
+    cap, obs_cap, obs_lo = [3, 1, 4], [2, 0, 2], [0, 2, 2]
+    ep = lambda n, policy, turn=0: circle_scene(S, n, np.asarray(policy, np.uint8), rad=3.0, turn=turn)
+    spheres = lambda k, z: (np.array([[0.5 * i, 0.25, z] for i in range(k)]), np.full(k, 0.4))
+    base = [ep(3, [0, 4, 1]), ep(1, [5]), ep(4, [4, 0, 3, 2])]
+    set0 = spheres(1, 10.0)
+    sol, off = context(S, base, obstacles=[set0, None, None], obs_slots=obs_cap)
+    sol.set_path_slots(2)
+    assert np.diff(off).tolist() == cap
+    solos = {0: _alone(S, base[0], obstacles=set0), 1: _alone(S, base[1])}
+    held = {0: base[0], 1: base[1]}
+    solver = dict(neighbor_dist=np.array([6.0, 10.0, 4.0, 8.0]), max_neighbors=np.array([3, 16, 2, 5], np.int32), max_heading_change=np.array([0.5, 0.7, 0.5, 0.9]))
+    planner = dict(turning_radius=np.array([1.5, 2.0, 1.0, 1.0]), pitch_lo=np.full(4, -0.5), pitch_hi=np.array([0.5, 0.6, 0.5, 0.5]))
+    lists = [[], [[1.0, 0.5, 10.0]], [[0.0, 1.0, 10.0], [2.0, 2.0, 10.5]], [[-1.0, 0.0, 9.5]]]
+    two = spheres(2, 10.2)
+    # (the episode, what the call brings, what the fresh context is given).  The obstacles of stage 3 and the attributes of stage 4 stay
+    # with the slot; behind stage 4 a call without attributes must keep every row tracked or untracked as it was.
+    stages = [('plain', ep(4, [0, 4, 5, 1], 1), {}, {}),
+              ('sized', ep(2, [4, 0], 2), dict(sizes=[2]), {}),
+              ('obstacles', ep(3, [5, 4, 2], 3), dict(sizes=[3], obstacles=[two]), dict(obstacles=two)),
+              ('attrs', ep(4, [0, 5, 4, 1], 4), dict(attrs=dict(solver, **planner)), dict(obstacles=two, solver=solver, planner=planner)),
+              ('lists', ep(4, [5, 0, 1, 4], 5), dict(paths=lists), dict(obstacles=two, solver=solver, planner=planner, lists=lists))]
+    for k, (name, e, brings, alone_kw) in enumerate(stages):
+        restart_all(sol, [2], [e], **brings)
+        assert sol.scene_sizes().tolist() == [3, 1, e['n']], name
+        held[2], solos[2] = e, _alone(S, e, **alone_kw)
+        for x in [sol] + list(solos.values()):
+            x.run_steps(2, S.NBR_KDTREE)
+            x.synchronize()
+        got = assert_slots_equal_alone(sol, off, held, solos, ('stage', k, name), obs_lo=obs_lo)
+        assert_vacant(got, off, [3, 1, e['n']], ('stage', k, name))
+        assert sol.scene_state()['steps'].tolist() == [2 * (k + 1), 2 * (k + 1), 2], name
+        solos.pop(2).close()
+    for x in [sol] + list(solos.values()):
+        x.close()

@@ -16,7 +16,7 @@ ERR_ARG = -1                                                                    
 
 @pytest.fixture(scope='module')
 def H():
-    return load_harness('scenes_harness', ('sca_forms.h', 'sca_scenes.h'))
+    return load_harness('scenes_harness', ('sca_forms.h', 'sca_scenes.h', 'sca_scene_restart.h'))
 
 
 def i32(a):

@@ -18,7 +18,7 @@ POLICY_NOW = [0, 1, 2, 3, 4, 5, 0, 1, 2, 3]
 
 @pytest.fixture(scope='module')
 def H():
-    return load_harness('scenes_harness', ('sca_forms.h', 'sca_scenes.h'))
+    return load_harness('scenes_harness', ('sca_forms.h', 'sca_scenes.h', 'sca_scene_restart.h'))
 
 
 def episode(T):

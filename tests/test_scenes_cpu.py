@@ -15,7 +15,7 @@ NBR_KDTREE, NBR_GRID, NBR_HOSTBUILD, NBR_AUTO = 0, 1, 2, 3
 
 @pytest.fixture(scope='module')
 def H():
-    return load_harness('scenes_harness', ('sca_forms.h', 'sca_scenes.h'))
+    return load_harness('scenes_harness', ('sca_forms.h', 'sca_scenes.h', 'sca_scene_restart.h'))
 
 
 def i32(a):
