@@ -97,7 +97,7 @@ inline void tunables_from_env(Tunables &t, int simds, TunWhen when) {
 // not run twice.
 constexpr int AUTO_BACKOFF_PASSES = 256;
 inline bool auto_lists_too_many(int kdq_last, int auto_div, int shard_count) { return kdq_last >= 0 && (long long)kdq_last * auto_div > (long long)shard_count; }
-// auto_pass (false: a plain SCA_NBR_KDTREE pass) | the context's auto_backoff and kdq_last after this decision | workgroups of
+// auto_pass (false: a plain SCA_NBR_KDTREE pass) | the context's Auto::backoff and Auto::last after this decision | workgroups of
 // k_neighbors_kd_auto, should the listed agents' kd query be a launch
 struct AutoPlan { bool auto_pass; int auto_backoff, kdq_last, kdq_blocks; };
 inline AutoPlan plan_auto(bool fits, bool tracked_pass, bool kd_ahead, int kdq_last, int auto_div, int auto_backoff, int shard_count) {
@@ -117,7 +117,65 @@ inline bool auto_next(bool fits, bool tracked_pass, bool part_on, int kdq_last, 
 // the launch-free form of the listed agents' kd query (the grid query's own last workgroup answers them, KdTail) for the build of pass `seq`:
 // while the list lengths that have come back say "nobody" (auto_tail_max), and only with the wait-value form of the pass's wait
 inline bool auto_tail_form(bool tail_ok, bool waitvalue, unsigned seq, int kdq_last, int auto_tail_max) {
-    return tail_ok && waitvalue && seq != 0 && kdq_last >= 0 && kdq_last <= auto_tail_max;
+    return tail_ok && waitvalue && seq != 0 && kdq_last >= 0 && kdq_last <= auto_tail_max;   // (seq wraps: the pass numbered 0 never takes the tail form)
+}
+
+// ---- the slot rule of an AUTO pass ---------------------------------------------------------------------------------------------------------------
+// Pass `seq` (sca_ctx::Auto::seq + 1 while it is being enqueued; unsigned, it wraps) owns three slots.  Its list is the one of parity
+// seq & 1: the pass two before filled and read the same one.  Event slot seq & 3 of Auto::ev_kdq fires when its kd query is through:
+// recorded behind k_neighbors_kd_auto on the kd stream (the launch form), or behind its build's k_kd_block (the tail form, where the grid
+// query's own last workgroup answers on the pass's stream).  `on_kd` has bit s set while the pass that last recorded slot s ran the launch
+// form: only then must the list's next user wait for that slot before it resets and refills the list.  Slot builds & 1 of Auto::ev_gather
+// is recorded behind every build's gather, the last kernel that reads a record buffer.
+constexpr int AUTO_NO_SLOT = -1;
+inline bool auto_on_kd(unsigned on_kd, unsigned slot) { return (on_kd >> (slot & 3u)) & 1u; }
+// the build of pass seq = auto_seq + 1, enqueued inside that pass or ahead of it
+struct AutoBuildPlan {
+    unsigned seq;
+    bool tail;          // auto_tail_form: the build's k_kd_block takes a KdTail and the pass launches no kd query
+    int record_slot;    // ev_kdq slot recorded behind k_kd_block (the tail form only)
+    int wait_slot;      // ev_kdq slot the PASS's stream waits on before this build is enqueued (the tail form only): the list's last reader
+    int gather_slot;    // ev_gather slot recorded behind this build's gather (Auto::builds counts it afterwards)
+};
+inline AutoBuildPlan plan_auto_build(bool tail_ok, bool waitvalue, unsigned auto_seq, int kdq_last, int auto_tail_max, unsigned on_kd, unsigned builds) {
+    AutoBuildPlan b{auto_seq + 1u, false, AUTO_NO_SLOT, AUTO_NO_SLOT, (int)(builds & 1u)};
+    b.tail = auto_tail_form(tail_ok, waitvalue, b.seq, kdq_last, auto_tail_max);
+    if (!b.tail) return b;
+    b.record_slot = (int)(b.seq & 3u);
+    // (seq wraps: passes 1 and 2 behind the wrap skip the wait like a context's first two, pass 0 never gets here)
+    if (b.seq >= 3u && auto_on_kd(on_kd, b.seq - 2u)) b.wait_slot = (int)((b.seq - 2u) & 3u);
+    return b;
+}
+enum AutoWait { AUTO_WAIT_NONE, AUTO_WAIT_VALUE, AUTO_WAIT_EVENT };   // how the pass's stream learns that the lists are final
+struct AutoPassPlan {
+    unsigned seq;       // what Auto::seq becomes with this pass
+    int parity;         // the list this pass fills and reads
+    int reuse_slot;     // ev_kdq slot the pass's stream waits on in front of its grid build (the kd query of two passes ago), or none
+    bool tail;          // this pass's build was enqueued in the tail form: no kd query launch
+    int kdq_slot;       // ev_kdq slot of this pass: recorded behind its kd query (on_kd_stream) or, by its build, behind k_kd_block
+    bool on_kd_stream;  // the kd query is a launch on the kd stream: what bit kdq_slot of Auto::on_kd becomes
+    unsigned on_kd;     // Auto::on_kd behind this pass
+    bool copy_count;    // the list length is copied back behind this pass's kd query
+    unsigned passes;    // Auto::passes behind this pass (it stands still while a copy is pending)
+    int wait;           // AutoWait
+    int gather_slot;    // ev_gather slot the integrate stage waits on: the build BEFORE this pass's read the buffer it writes
+};
+// after this pass's build has been enqueued (tail_seq and builds include it)
+inline AutoPassPlan plan_auto_pass(unsigned auto_seq, unsigned tail_seq, unsigned on_kd, bool waitvalue, bool count_pending, unsigned passes, unsigned builds) {
+    AutoPassPlan p{};
+    p.seq = auto_seq + 1u;
+    p.parity = (int)(p.seq & 1u);
+    p.tail = tail_seq == p.seq && tail_seq != 0u;
+    // (a build enqueued in the tail form has made the pass's stream wait already; seq wraps: pass 0 waits unless tail_seq is 0, passes 1 and 2 behind it do not)
+    p.reuse_slot = auto_seq >= 2u && tail_seq != p.seq && auto_on_kd(on_kd, p.seq - 2u) ? (int)((p.seq - 2u) & 3u) : AUTO_NO_SLOT;
+    p.kdq_slot = (int)(p.seq & 3u);
+    p.on_kd_stream = !p.tail;
+    p.on_kd = (on_kd & ~(1u << p.kdq_slot)) | ((p.on_kd_stream ? 1u : 0u) << p.kdq_slot);
+    p.copy_count = !count_pending && (passes & 3u) == 0u;
+    p.passes = count_pending ? passes : passes + 1u;
+    p.wait = p.tail ? AUTO_WAIT_NONE : waitvalue ? AUTO_WAIT_VALUE : AUTO_WAIT_EVENT;
+    p.gather_slot = (int)(builds & 1u);              // [builds & 1] = the one before the last
+    return p;
 }
 
 // ---- the solve and its neighbours ------------------------------------------------------------------------------------------------------------

@@ -226,7 +226,6 @@ struct sca_ctx {
                                         // structure (K0) and the neighbour query (K1) of the pass run on this one beside them
     hipEvent_t trk_fork = nullptr, trk_join = nullptr;
     hipStream_t nbr_stream = nullptr;   // where K0 / K1 of the current pass go: trk_stream when overlapped, else the main stream
-    bool kd_ahead_enqueue = false;      // (timeline builds: the build being enqueued belongs to the next pass)
     Params P_ctx{};                     // sca_create's parameters; P holds the ENVELOPE of the agents' own while sca_set_agent_params is in force
     AgentPar *ap_dev = nullptr;         // [n] per-agent solver attributes on the device (DeviceView::ap), null: one value per context
     double *ap_nd = nullptr;            // [n] the agents' neighborDist alone, for the tracker (TrackView::nd_per_agent)
@@ -260,32 +259,40 @@ struct sca_ctx {
     int kd_rank_capacity = 1 << 30;     // workgroups of k_kd_lv_rank the device holds at once (occupancy x CUs)
     // SCA_NBR_AUTO: the grid query for everybody, the kd query for the agents it lists; the kd BUILD (the permutation is history: it
     // runs every step) on a stream of its own beside the grid build and query
-    hipStream_t kd_stream = nullptr;
-    hipEvent_t ev_auto_fork = nullptr, ev_auto_k1g = nullptr, ev_auto_kd = nullptr, ev_auto_moved = nullptr, ev_auto_cnt = nullptr;
-    int32_t *kdq_list = nullptr, *kdq_count = nullptr;
-    int *auto_ticket = nullptr;         // k_neighbors_kd_auto's last-workgroup ticket
-    unsigned *auto_busy = nullptr;      // device word, bit 0: somebody is listed for the kd query and it has not answered yet (hipStreamWaitValue32)
-    unsigned auto_seq = 0;
-    bool auto_waitvalue = true;         // false once hipStreamWaitValue32 was refused: an event wait behind the kd query instead (the build is then on every pass's path)
-    hipEvent_t ev_auto_kdq[4] = {nullptr, nullptr, nullptr, nullptr};   // [seq & 3] behind the kd query of pass seq (a launch on kd_stream) or, in the
-                                                         // launch-free form, behind its build's last kernel; the pass two on reuses the list: [(seq - 2) & 3]
-    unsigned *auto_sync = nullptr;      // device words of the launch-free form (KdTail): [0] k_kd_block's ticket, [1] the last pass whose tree is complete, [2] the grid query's ticket
-    bool auto_tail_ok = false;          // the tail form is available (with the wait-value form of the pass's wait; Tunables::auto_no_tail: never)
-    unsigned kd_tail_seq = 0;           // the pass whose build was enqueued in the tail form (0: none)
-    bool kdq_on_kd_stream[4] = {false, false, false, false};   // [seq & 3]: pass seq's kd query was a launch on kd_stream (its list's next user must wait for it)
-    KdTail kd_tail_arg = {};            // what the build being enqueued hands its k_kd_block (seq = 0 outside an AUTO build)
-    hipEvent_t kd_block_stop = nullptr; // ... and the event to record behind it
-    hipEvent_t ev_auto_gather[2] = {nullptr, nullptr};   // the gather kernel of the last two builds: the integrate stage must not write into
-    unsigned auto_builds = 0;                            // the record buffer a build's gather still reads (the two buffers alternate)
-    bool lazy_join = false;             // sca_env_step left kd_stream unjoined: the next entry point other than sca_env_step joins (API_ENTER)
-    bool auto_unjoined = false;         // kd_stream may still be working on the last AUTO pass's tree / kd query
-    int *kdq_host = nullptr;            // pinned: the list length of an earlier pass (never waited for)
-    bool kdq_pending = false;
-    int kdq_last = -1;                  // -1: unknown
-    int auto_backoff = 0;               // passes left to run as plain SCA_NBR_KDTREE (the grid listed too many agents: ties everywhere)
-    bool auto_ran = false, auto_fits = false;   // the last pass was an AUTO pass / the grid's candidate lists cover the collision reach
-    bool kd_ahead = false;              // the kd build of the NEXT pass is already enqueued on kd_stream (sca_run_steps, behind the integrate stage)
-    unsigned auto_passes = 0;
+    struct Auto {                       // (the slot rule -- which event and list a pass takes -- is plan_auto_build / plan_auto_pass, sca_forms.h)
+        hipStream_t stream = nullptr;   // the kd stream
+        hipEvent_t ev_fork = nullptr, ev_k1g = nullptr, ev_kd = nullptr, ev_moved = nullptr, ev_cnt = nullptr;
+        int32_t *list = nullptr, *count = nullptr;   // two lists and their lengths, alternating by pass (DeviceView::kdq_list / kdq_count point at this pass's)
+        int *ticket = nullptr;          // k_neighbors_kd_auto's last-workgroup ticket
+        unsigned *busy = nullptr;       // device word, bit 0: somebody is listed for the kd query and it has not answered yet (hipStreamWaitValue32)
+        unsigned seq = 0;               // AUTO passes so far (it may wrap)
+        bool waitvalue = true;          // false once hipStreamWaitValue32 was refused: an event wait behind the kd query instead (the build is then on every pass's path)
+        hipEvent_t ev_kdq[4] = {nullptr, nullptr, nullptr, nullptr};   // [seq & 3] behind the kd query of pass seq (a launch on the kd stream) or, in the launch-free form, behind its build's last kernel
+        unsigned *sync = nullptr;       // device words of the launch-free form (KdTail): [0] k_kd_block's ticket, [1] the last pass whose tree is complete, [2] the grid query's ticket
+        bool tail_ok = false;           // the tail form is available (with the wait-value form of the pass's wait; Tunables::auto_no_tail: never)
+        unsigned tail_seq = 0;          // the pass whose build was enqueued in the tail form (0: none)
+        unsigned on_kd = 0;             // bit [seq & 3]: pass seq's kd query was a launch on the kd stream (its list's next user must wait for it)
+        hipEvent_t ev_gather[2] = {nullptr, nullptr};   // the gather kernel of the last two builds: the integrate stage must not write into
+        unsigned builds = 0;                            // the record buffer a build's gather still reads (the two buffers alternate)
+        bool lazy_join = false;         // sca_env_step left the kd stream unjoined: the next entry point other than sca_env_step joins (API_ENTER)
+        bool unjoined = false;          // the kd stream may still be working on the last AUTO pass's tree / kd query
+        int *count_host = nullptr;      // pinned: the list length of an earlier pass (never waited for)
+        bool count_pending = false;
+        int last = -1;                  // that length; -1: unknown
+        int backoff = 0;                // passes left to run as plain SCA_NBR_KDTREE (the grid listed too many agents: ties everywhere)
+        bool ran = false, fits = false; // the last pass was an AUTO pass / the grid's candidate lists cover the collision reach
+        bool ahead = false;             // the kd build of the NEXT pass is already enqueued on the kd stream (sca_run_steps, behind the integrate stage)
+        unsigned passes = 0;
+        int fill(sca_ctx *c);           // the stream, the events and the device words, on first use
+        void forget() { ahead = false; last = -1; backoff = 0; }   // the counts say nothing any more, and no tree is built ahead
+        void release() {                // behind a synchronised context; (ev_kd aliases ev_kdq[])
+            if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+            for (hipEvent_t e : {ev_fork, ev_k1g, ev_moved, ev_cnt, ev_gather[0], ev_gather[1], ev_kdq[0], ev_kdq[1], ev_kdq[2], ev_kdq[3]}) if (e) (void)hipEventDestroy(e);
+            for (void *p : {(void *)list, (void *)count, (void *)busy, (void *)sync, (void *)ticket}) if (p) (void)hipFree(p);
+            if (count_host) (void)hipHostFree(count_host);
+            *this = Auto{};
+        }
+    } au;
     hipEvent_t action_stop = nullptr;   // sca_run_steps: the event to record behind this pass's k_action (the moved positions), if any
     hipEvent_t finish_stop = nullptr;   // sca_run_steps: the event to record behind the step's last kernel (the next pass's fork), if any
     bool fork_ready = false;            // ... it was: the pass that follows at once does not record its fork
@@ -390,8 +397,26 @@ static int dalloc(sca_ctx *c, T **p, size_t count) {
     CHK(c, hipMemsetAsync(*p, 0, sizeof(T) * (count ? count : 1), c->stream));
     return 0;
 }
+// positions replaced from outside (sca_set_state ...): the level statistics of older trees do not apply
+static void positions_replaced(sca_ctx *c) { c->kd_single_hint = 0; c->kd_gen++; }
+// the next event of a profiling pool that grows on demand, up to `cap` in use (beyond it: *e stays as it is)
+static int pool_take(sca_ctx *c, std::vector<hipEvent_t> &pool, int &used, int cap, hipEvent_t *e) {
+    if (used >= cap) return 0;
+    if (used == (int)pool.size()) { hipEvent_t n_; CHK(c, hipEventCreate(&n_)); pool.push_back(n_); }
+    *e = pool[used++];
+    return 0;
+}
+static int pool_event(sca_ctx *c, hipEvent_t *out) { return pool_take(c, c->pool, c->pool_used, 4 * 4096, out); }
+// the mean time from event `at` to event `at + 1` over every `stride` events a pool has handed out
+static int pool_mean_ms(sca_ctx *c, const std::vector<hipEvent_t> &pool, int used, int stride, int at, float *ms) {
+    double sum = 0;
+    const int k = used / stride;
+    for (int s = 0; s < k; s++) { float t = 0; CHK(c, hipEventElapsedTime(&t, pool[stride * s + at], pool[stride * s + at + 1])); sum += t; }
+    *ms = (float)(sum / k);
+    return 0;
+}
 
-// sca_env_step (the drop-in loop's one call per step) returns without putting kd_stream in front of the context's stream -- an SCA_NBR_AUTO
+// sca_env_step (the drop-in loop's one call per step) returns without putting the kd stream in front of the context's stream -- an SCA_NBR_AUTO
 // pass leaves the tree build and the kd query of the listed agents there, and the next pass copes with that by itself, as inside a burst of
 // sca_run_steps.  Every OTHER entry point joins first: it may read the tree, the permutation or the lists, or enqueue work that does.
 static int auto_join(sca_ctx *c);
@@ -976,21 +1001,9 @@ void sca_destroy(sca_ctx *c) {
                     c->grid.gid, c->grid.gkey, c->lp_list, d.sw_slot, d.sw_surv, d.sw_n};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
-    for (auto &e : c->pool) (void)hipEventDestroy(e);
-    for (auto &e : c->pool_trk) (void)hipEventDestroy(e);
-    for (auto &e : c->pool_xch) (void)hipEventDestroy(e);
-    for (auto &e : c->pool_kd) (void)hipEventDestroy(e);
-    if (c->kd_stream) { (void)hipStreamSynchronize(c->kd_stream); (void)hipStreamDestroy(c->kd_stream); }
-    for (hipEvent_t e : {c->ev_auto_fork, c->ev_auto_k1g, c->ev_auto_moved, c->ev_auto_cnt}) if (e) (void)hipEventDestroy(e);   // (ev_auto_kd aliases ev_auto_kdq[])
-    if (c->kdq_list) (void)hipFree(c->kdq_list);
-    if (c->kdq_count) (void)hipFree(c->kdq_count);
-    if (c->kdq_host) (void)hipHostFree(c->kdq_host);
-    if (c->auto_busy) (void)hipFree(c->auto_busy);
-    if (c->auto_sync) (void)hipFree(c->auto_sync);
-    if (c->auto_ticket) (void)hipFree(c->auto_ticket);
+    for (auto *pool : {&c->pool, &c->pool_trk, &c->pool_xch, &c->pool_kd}) for (hipEvent_t e : *pool) (void)hipEventDestroy(e);
+    c->au.release();
     if (c->d.kdq_stats) (void)hipFree(c->d.kdq_stats);
-    for (hipEvent_t e : c->ev_auto_gather) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_auto_kdq) if (e) (void)hipEventDestroy(e);
     if (c->kd_ev) (void)hipEventDestroy(c->kd_ev);
     if (c->kd_host_counts) (void)hipHostFree(c->kd_host_counts);
     if (c->stream_own) (void)hipStreamDestroy(c->stream_own);
@@ -1170,7 +1183,7 @@ int sca_set_agents(sca_ctx *c, int n, const double *radius, const double *pref_s
     CHK(c, hipMemsetAsync(c->d.step_num, 0, sizeof(int32_t) * n, c->stream));
     CHK(c, hipStreamSynchronize(c->stream));
     c->agents_set = true; c->state_set = false; c->h_pos_valid = false;
-    c->kdq_last = -1; c->auto_backoff = 0; c->kd_ahead = false; c->auto_ran = false;
+    c->au.forget(); c->au.ran = false;
     return 0;
 }
 
@@ -1188,9 +1201,8 @@ int sca_set_state(sca_ctx *c, const double *pos, const float *vel, const double 
         r.flags = flags[i];
     }
     c->h_pos.assign(pos, pos + 3 * (size_t)n);
-    c->kd_single_hint = 0; c->kd_gen++;   // a new state: the previous trees' depth profile says nothing
-    c->kd_ahead = false; c->kdq_last = -1; c->auto_backoff = 0;           // ... and neither do the AUTO passes' counts (no tree is built ahead
-                                                                          // across calls: sca_run_steps consumes its own or abandons it)
+    positions_replaced(c);                // a new state: the previous trees' depth profile says nothing
+    c->au.forget();                       // ... and neither do the AUTO passes' counts (no tree is built ahead across calls: sca_run_steps consumes its own or abandons it)
     c->h_pos_valid = true;
     c->near_valid = false;
     CHK(c, hipMemcpyAsync(c->d.rec, c->h_rec.data(), sizeof(PubRec) * n, hipMemcpyHostToDevice, c->stream));
@@ -1580,7 +1592,7 @@ int sca_set_scenes(sca_ctx *c, int nscenes, const int32_t *offsets) {
     for (int i = 0; i < n; i++) c->h_perm[i] = i;                     // every scene's kdTree.agentIDs starts as 0 .. n_s - 1 (kdTree.py:43-45)
     c->perm_on_device = false;
     c->scenes.live_valid = false; c->scenes.begun = false;
-    c->kd_single_hint = 0; c->kd_gen++; c->kd_ahead = false; c->kdq_last = -1; c->auto_backoff = 0; c->near_valid = false;
+    positions_replaced(c); c->au.forget(); c->near_valid = false;
     c->nbr_mode = SCA_NBR_KDTREE;
     c->scenes.on = true;
     return 0;
@@ -2275,8 +2287,18 @@ static int build_agent_tree(sca_ctx *c) {
 }
 
 // KDTree.buildAgentTree on the device (sca_kdbuild.hip.h): gather, one launch per level of large nodes, one launch
-// that finishes every small subtree.  Everything is enqueued on the context's stream; nothing comes back to the host.
-static int build_agent_tree_device(sca_ctx *c, hipStream_t ks, const DeviceView &d) {
+// that finishes every small subtree.  Everything is enqueued on `ks`; nothing comes back to the host.
+struct KdBuildArgs {                     // what an SCA_NBR_AUTO build adds (auto_enqueue_kd_build); a build inside a kd pass takes the defaults
+    KdTail tail = {};                    // what the build hands its k_kd_block (seq = 0: not the tail form)
+    hipEvent_t block_stop = nullptr;     // ... and the event to record behind it, if any
+    int aux = 0;                         // KdScratch::aux
+    hipEvent_t gather_stop = nullptr;    // the event to record behind the gather, the last kernel of the build that reads the record buffer
+    bool next_pass = false;              // (timeline builds: the build belongs to the next pass)
+};
+static int build_agent_tree_device(sca_ctx *c, hipStream_t ks, DeviceView d, const KdBuildArgs &a = {}) {
+#ifdef SCA_TIMELINE
+    if (a.next_pass) d.tl_step++;
+#endif
     const int n = c->n;
     // poll: the level statistics of an earlier build, if they have arrived (never waited for)
     if (c->kd_ev_pending && hipEventQuery(c->kd_ev) == hipSuccess) {
@@ -2305,34 +2327,33 @@ static int build_agent_tree_device(sca_ctx *c, hipStream_t ks, const DeviceView 
         c->perm_on_device = true;
     }
     c->kd.wave_max = B.wave_max;
+    KdScratch kd = c->kd;                                               // (by value into every kernel of the build)
+    kd.aux = a.aux;
     hipEvent_t kb0 = nullptr, kb1 = nullptr;                            // profiling: the build's device time on the stream it runs on, every 16th build
     if (c->profiling && (c->kd_builds & 15u) == 0 && c->pool_kd_used + 2 <= 2 * 1024) {
-        for (hipEvent_t *ev : {&kb0, &kb1}) {
-            if (c->pool_kd_used == (int)c->pool_kd.size()) { hipEvent_t n_; CHK(c, hipEventCreate(&n_)); c->pool_kd.push_back(n_); }
-            *ev = c->pool_kd[c->pool_kd_used++];
-        }
+        for (hipEvent_t *ev : {&kb0, &kb1}) if (int r = pool_take(c, c->pool_kd, c->pool_kd_used, 2 * 1024, ev)) return r;
         CHK(c, hipEventRecord(kb0, ks));
     }
-    if (c->kd.aux) {                                                    // SCA_NBR_AUTO: the last kernel of the build that reads the record buffer
-        LAUNCH_REC(c, c->ev_auto_gather[c->auto_builds & 1u], k_kd_gather, dim3((n + 255) / 256), dim3(256), ks, d, c->kd, c->P);
-        c->auto_builds++;
-    } else hipLaunchKernelGGL(k_kd_gather, dim3((n + 255) / 256), dim3(256), 0, ks, d, c->kd, c->P);
+    if (a.gather_stop) {                                                // SCA_NBR_AUTO
+        LAUNCH_REC(c, a.gather_stop, k_kd_gather, dim3((n + 255) / 256), dim3(256), ks, d, kd, c->P);
+        c->au.builds++;
+    } else hipLaunchKernelGGL(k_kd_gather, dim3((n + 255) / 256), dim3(256), 0, ks, d, kd, c->P);
     if (c->scenes.on) {
         // the forest's job table behind the gather (which rewrites the single root job and the counts on every build); opens the step
-        hipLaunchKernelGGL(k_kd_scene_jobs, dim3((c->scenes.v.nscenes + 255) / 256), dim3(256), 0, ks, c->kd, c->scenes.v, (const int32_t *)c->scenes.size, c->scenes.begun ? 0 : 1);
+        hipLaunchKernelGGL(k_kd_scene_jobs, dim3((c->scenes.v.nscenes + 255) / 256), dim3(256), 0, ks, kd, c->scenes.v, (const int32_t *)c->scenes.size, c->scenes.begun ? 0 : 1);
         c->scenes.begun = true;
     }
-    if (B.top && B.levels) hipLaunchKernelGGL(k_kd_top, dim3(1), dim3(KT_T), 0, ks, d, c->kd);
+    if (B.top && B.levels) hipLaunchKernelGGL(k_kd_top, dim3(1), dim3(KT_T), 0, ks, d, kd);
     if (B.level_passes) {
         for (int l = 0; l < B.first_single; l++) {
-            if (B.ticket) hipLaunchKernelGGL(k_kd_lv_rank<true>, dim3(B.grid), dim3(KD_LV_T), 0, ks, c->kd, l, ++c->kd_token);
-            else hipLaunchKernelGGL(k_kd_lv_rank<false>, dim3(B.grid), dim3(KD_LV_T), 0, ks, c->kd, l, ++c->kd_token);
-            hipLaunchKernelGGL(k_kd_lv_swap, dim3(B.grid), dim3(KD_LV_T + 64), 0, ks, d, c->kd, l);   // + the bookkeeping wavefront
+            if (B.ticket) hipLaunchKernelGGL(k_kd_lv_rank<true>, dim3(B.grid), dim3(KD_LV_T), 0, ks, kd, l, ++c->kd_token);
+            else hipLaunchKernelGGL(k_kd_lv_rank<false>, dim3(B.grid), dim3(KD_LV_T), 0, ks, kd, l, ++c->kd_token);
+            hipLaunchKernelGGL(k_kd_lv_swap, dim3(B.grid), dim3(KD_LV_T + 64), 0, ks, d, kd, l);   // + the bookkeeping wavefront
         }
-        hipLaunchKernelGGL(k_kd_level_tail, dim3(B.grid), dim3(KD_LV_T), 0, ks, d, c->kd, B.first_single, ++c->kd_token);
+        hipLaunchKernelGGL(k_kd_level_tail, dim3(B.grid), dim3(KD_LV_T), 0, ks, d, kd, B.first_single, ++c->kd_token);
     }
     // one workgroup per subtree, in LDS (LAUNCH_OPT: an AUTO build in the tail form records the pass's kd-query event behind this kernel)
-#define KD_BLOCK(M) LAUNCH_OPT(c, c->kd_block_stop, (k_kd_block<M, M / 2>), dim3(B.sgrid), dim3(M / 2), ks, d, c->kd, B.levels, c->kd_tail_arg)
+#define KD_BLOCK(M) LAUNCH_OPT(c, a.block_stop, (k_kd_block<M, M / 2>), dim3(B.sgrid), dim3(M / 2), ks, d, kd, B.levels, a.tail)
     switch (B.block) {
     case 256: KD_BLOCK(256); break;
     case 512: KD_BLOCK(512); break;
@@ -2394,16 +2415,6 @@ static void clearance_reach(const sca_ctx *c, double &agent_reach, double &obs_r
     obs_reach = c->max_obs_radius + 1e-4;
 }
 
-static int pool_event(sca_ctx *c, hipEvent_t *out) {
-    if (c->pool_used == (int)c->pool.size()) {
-        hipEvent_t e;
-        CHK(c, hipEventCreate(&e));
-        c->pool.push_back(e);
-    }
-    *out = c->pool[c->pool_used++];
-    return 0;
-}
-
 // v_pref of the SCA / RVO3D+Dubins agents of the shard, before anything of the pass reads it (the per-agent prologue does).
 // in_pass = true (a policy pass with the tracker inside): agent.neighbors[0] comes from trk.nbr0, which the previous pass's
 // epilogue saved -- so nothing here reads the neighbour lists, and the neighbour query of this pass may run beside it.
@@ -2427,10 +2438,7 @@ static int launch_tracker(sca_ctx *c, bool from_lists, bool in_pass, int &forms)
     hipStream_t rs = c->stream;
     hipEvent_t t0 = nullptr, t1 = nullptr;
     if (c->profiling && (c->prof_tick & 15u) == 0 && c->pool_trk_used + 2 <= 2 * 4096) {
-        for (hipEvent_t *e : {&t0, &t1}) {
-            if (c->pool_trk_used == (int)c->pool_trk.size()) { hipEvent_t n_; CHK(c, hipEventCreate(&n_)); c->pool_trk.push_back(n_); }
-            *e = c->pool_trk[c->pool_trk_used++];
-        }
+        for (hipEvent_t *e : {&t0, &t1}) if (int r = pool_take(c, c->pool_trk, c->pool_trk_used, 2 * 4096, e)) return r;
         CHK(c, hipEventRecord(t0, rs));
     }
     // tracked agents whose turning radius / pitch limits differ (sca_device_tracker_set_agent_params) are planned class by class: the same
@@ -2464,7 +2472,6 @@ static int launch_tracker(sca_ctx *c, bool from_lists, bool in_pass, int &forms)
     return 0;
 }
 
-// SCA_NBR_AUTO's resources, on first use
 // An SCA_NBR_AUTO step is bound by what the HOST needs to enqueue it (tools/gpu/exp_host.py: 79 us per step of 91 at N = 4096 -- twelve
 // launches at ~2.3 us and ten event operations at ~5 us), so a cross-stream wait is only enqueued when the event it would wait for has
 // not fired yet (in the steady state the kd stream is a whole pass ahead of what these guards protect; the query costs < 1 us).
@@ -2482,140 +2489,143 @@ static int wait_if_pending(sca_ctx *c, hipStream_t s, hipEvent_t e) {
     CHK(c, hipStreamWaitEvent(s, e, 0));
     return 0;
 }
-static int auto_prepare(sca_ctx *c) {
-    if (c->kd_stream) return 0;
-    CHK(c, hipStreamCreateWithFlags(&c->kd_stream, hipStreamNonBlocking));
-    for (hipEvent_t *e : {&c->ev_auto_fork, &c->ev_auto_k1g, &c->ev_auto_moved, &c->ev_auto_cnt})
-        CHK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+// SCA_NBR_AUTO's resources, on first use
+int sca_ctx::Auto::fill(sca_ctx *c) {
+    if (stream) return 0;
+    CHK(c, hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    for (hipEvent_t *e : {&ev_fork, &ev_k1g, &ev_moved, &ev_cnt}) CHK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
     // two lists, alternating by pass: a pass's kd query may still be reading its list's length (to find it empty) when the next
     // pass's grid build resets and refills the other one
-    CHK(c, hipMalloc((void **)&c->kdq_list, 2 * sizeof(int32_t) * (size_t)c->max_n));
-    CHK(c, hipMalloc((void **)&c->kdq_count, 2 * sizeof(int32_t)));
-    CHK(c, hipMemsetAsync(c->kdq_count, 0, 2 * sizeof(int32_t), c->stream));
-    CHK(c, hipMalloc((void **)&c->auto_busy, sizeof(unsigned)));
-    CHK(c, hipMemsetAsync(c->auto_busy, 0, sizeof(unsigned), c->stream));
-    CHK(c, hipMalloc((void **)&c->d.kdq_stats, sizeof(unsigned long long) * 4));
-    CHK(c, hipMemsetAsync(c->d.kdq_stats, 0, sizeof(unsigned long long) * 4, c->stream));
-    CHK(c, hipMalloc((void **)&c->auto_ticket, sizeof(int)));
-    CHK(c, hipMemsetAsync(c->auto_ticket, 0, sizeof(int), c->stream));
-    CHK(c, hipMalloc((void **)&c->auto_sync, 8 * sizeof(unsigned)));
-    CHK(c, hipMemsetAsync(c->auto_sync, 0, 8 * sizeof(unsigned), c->stream));
+    CHK(c, hipMalloc((void **)&list, 2 * sizeof(int32_t) * (size_t)c->max_n));
+    if (int r = dalloc(c, &count, 2)) return r;
+    if (int r = dalloc(c, &busy, 1)) return r;
+    if (int r = dalloc(c, &c->d.kdq_stats, 4)) return r;
+    if (int r = dalloc(c, &ticket, 1)) return r;
+    if (int r = dalloc(c, &sync, 8)) return r;
     CHK(c, hipStreamSynchronize(c->stream));
-    for (hipEvent_t &e : c->ev_auto_gather) CHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (hipEvent_t &e : c->ev_auto_kdq) CHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    c->auto_seq = 0; c->auto_builds = 0;
-    c->auto_waitvalue = true;
-    c->auto_tail_ok = !c->tun.auto_no_tail;
-    c->kd_tail_seq = 0;
-
-    CHK(c, hipHostMalloc((void **)&c->kdq_host, sizeof(int)));
-    c->d.kdq_list = c->kdq_list; c->d.kdq_count = c->kdq_count; c->d.kdq_busy = c->auto_busy;
-    c->kdq_pending = false; c->kdq_last = -1; c->auto_backoff = 0; c->kd_ahead = false;
+    for (hipEvent_t &e : ev_gather) CHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (hipEvent_t &e : ev_kdq) CHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    seq = 0; builds = 0; tail_seq = 0; waitvalue = true; count_pending = false;
+    tail_ok = !c->tun.auto_no_tail;
+    CHK(c, hipHostMalloc((void **)&count_host, sizeof(int)));
+    c->d.kdq_list = list; c->d.kdq_count = count; c->d.kdq_busy = busy;
+    forget();
     return 0;
 }
-// the kd build of a pass on kd_stream, beside whatever runs on the other streams (aux: it leaves the step's counters and the solve's
-// prologue to the grid's kernels).  `positions`: the record buffer that holds the positions to build from.
-static int auto_enqueue_kd_build(sca_ctx *c, hipEvent_t after, const PubRec *positions) {
-    CHK(c, hipStreamWaitEvent(c->kd_stream, after, 0));
+// the kd build of a pass on the kd stream, beside whatever runs on the other streams (aux: it leaves the step's counters and the solve's
+// prologue to the grid's kernels).  `positions`: the record buffer that holds the positions to build from; `ahead`: enqueued by
+// sca_run_steps behind the previous step's integrate stage.
+static int auto_enqueue_kd_build(sca_ctx *c, hipEvent_t after, const PubRec *positions, bool ahead) {
+    sca_ctx::Auto &A = c->au;
+    CHK(c, hipStreamWaitEvent(A.stream, after, 0));
     DeviceView v = c->d;
     v.rec = const_cast<PubRec *>(positions);
-#ifdef SCA_TIMELINE
-    if (c->kd_ahead_enqueue) v.tl_step = c->d.tl_step + 1;              // a build enqueued ahead belongs to the NEXT pass
-#endif
-    const int keep_skip = c->kd.skip_prep;
-    c->kd.aux = 1;
     // The kd query of the agents this pass's grid query will list: answered by that query's own last workgroup, once this build's last
     // kernel has published its tree (KdTail), while the list lengths that have come back say "nobody" -- otherwise a launch of
-    // its own behind the build (launch_policy).  The build belongs to the pass whose grid query comes next: auto_seq + 1, whether it is
+    // its own behind the build (pass_query_auto).  The build belongs to the pass whose grid query comes next: seq + 1, whether it is
     // enqueued inside that pass or ahead of it (sca_run_steps) -- in front of that grid query in the host's order either way.
-    const unsigned seq = c->auto_seq + 1;
-    c->kd_tail_arg = KdTail{};
-    c->kd_block_stop = nullptr;
-    if (auto_tail_form(c->auto_tail_ok, c->auto_waitvalue, seq, c->kdq_last, c->tun.auto_tail_max)) {
+    const AutoBuildPlan B = plan_auto_build(A.tail_ok, A.waitvalue, A.seq, A.last, c->tun.auto_tail_max, A.on_kd, A.builds);
+    KdBuildArgs a;
+    a.aux = 1; a.next_pass = ahead; a.gather_stop = A.ev_gather[B.gather_slot];
+    if (B.tail) {
         // (the list of this parity was last read by the kd query of two passes ago, whose event slot is about to be recorded anew: the
         // pass's stream waits for it HERE instead of in front of its grid build)
-        // (... if that query was a launch on kd_stream; in the launch-free form it ran inside the pass's own grid query, on this stream)
-        if (seq >= 3 && c->kdq_on_kd_stream[(seq - 2) & 3u]) { if (int r = wait_if_pending(c, c->stream, c->ev_auto_kdq[(seq - 2) & 3u])) return r; }
-        KdTail T;
-        T.seq = seq; T.sync = c->auto_sync;
-        c->kd_tail_arg = T;
-        c->kd_tail_seq = seq;
-        c->kd_block_stop = c->ev_auto_kdq[seq & 3u];
+        // (... if that query was a launch on the kd stream; in the launch-free form it ran inside the pass's own grid query, on this stream)
+        if (B.wait_slot != AUTO_NO_SLOT) { if (int r = wait_if_pending(c, c->stream, A.ev_kdq[B.wait_slot])) return r; }
+        a.tail.seq = B.seq; a.tail.sync = A.sync;
+        A.tail_seq = B.seq;
+        a.block_stop = A.ev_kdq[B.record_slot];
     }
-    const int r = build_agent_tree_device(c, c->kd_stream, v);
-    c->kd_tail_arg = KdTail{}; c->kd_block_stop = nullptr;
-    c->kd.aux = 0; c->kd.skip_prep = keep_skip;
-    return r;
+    return build_agent_tree_device(c, A.stream, v, a);
 }
 
-// everything kd_stream was given has to be through before a caller reads the tree, the permutation or the lists, and before a pass that
+// everything the kd stream was given has to be through before a caller reads the tree, the permutation or the lists, and before a pass that
 // is not an AUTO pass builds in place: the context's stream waits for the last kd query
-static int api_enter(sca_ctx *c) {
-    if (!c->lazy_join) return 0;
-    c->lazy_join = false;
-    return auto_join(c);
-}
+static int api_enter(sca_ctx *c) { return c->au.lazy_join ? auto_join(c) : 0; }
 static int auto_join(sca_ctx *c) {
-    c->lazy_join = false;
-    if (!c->auto_unjoined) return 0;
-    CHK(c, hipStreamWaitEvent(c->stream, c->ev_auto_kd, 0));
-    c->auto_unjoined = false;
+    c->au.lazy_join = false;
+    if (!c->au.unjoined) return 0;
+    CHK(c, hipStreamWaitEvent(c->stream, c->au.ev_kd, 0));
+    c->au.unjoined = false;
     return 0;
 }
 
-static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) {
+// ---- a policy pass: what its stages share, then the stages in the order launch_policy runs them ---------------------------------------------------
+struct PassPlan {
+    bool timed = false, fuse_integrate = false;   // launch_policy's arguments
+    int mode = 0;                       // the neighbour mode as resolved: SCA_NBR_AUTO has become SCA_NBR_KDTREE where it is a plain kd pass
+    bool auto_mode = false;             // an AUTO pass
+    bool kd_prebuilt = false;           // ... whose tree sca_run_steps has enqueued ahead
+    AutoPassPlan A{};                   // ... and its slots (sca_forms.h), planned behind its build; A.tail: the grid query's last workgroup answers the listed agents
+    int kdq_blocks = KDQ_BLOCKS;
+    bool tracked = false;               // the tracker runs inside the pass
+    bool overlap = false;               // ... and the neighbour branch beside its re-plans, on trk_stream
+    bool fork_ready = false;            // the fork rode on the previous step's last kernel (sca_run_steps)
+    unsigned parity_now = 0;            // TrackDev::parity in front of the tracker's launches
+    int lp_lo = 0, lp_hi = 0;           // the shard's LP agents: [lp_lo, lp_hi) of lp_ids (under the partition ownership is dynamic: the LP
+    const int32_t *lp_ids = nullptr;    // kernels walk all owned agents and skip the others)
+    int cnt = 0;                        // agents of the shard
+    SolvePlan S{};
+    int forms = 0;                      // SCA_FORM_* as they accumulate
+    bool prof = false;                  // this pass carries the profiling pool's event pairs
+    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};   // [e0, e1] = K1, [e2, e3] = the solve, when timed or prof
+    hipEvent_t k1_stop = nullptr, sweep_stop = nullptr;       // the join as the stop event of the side stream's last kernel
+    double agent_reach = 0, obs_reach = 0;                    // collide_reach: K1's and K4's collision candidates
+};
+
+// the refusals, the SCA_NBR_AUTO decision, the LP range and the solve's forms; nothing is launched (a pass that is not an AUTO pass joins the kd stream)
+static int pass_resolve(sca_ctx *c, int mode, PassPlan &p) {
     if (int r = clearance_refuse(c, "a policy pass", clearance_check(CLR_PASS, clearance_state(c), mode, 0, true, 0))) return r;
-    const bool fork_ready = c->fork_ready;
+    p.fork_ready = c->fork_ready;
     c->fork_ready = false;
 #ifdef SCA_TIMELINE
     c->d.tl_step++;
 #endif
     // the tracker's re-plans overlap the device kd build and the neighbour query; the per-agent prologue (which reads
     // v_pref) of the tracker's agents then moves from k_kd_gather to the tracker's kernels (track_store)
-    const bool tracked = c->trk_on && c->trk_in_pass;
-    // SCA_NBR_AUTO: an AUTO pass, or a plain kd pass where that cannot help (plan_auto; the cell-owner partition has its own structures)
-    bool auto_mode = false;
-    int kdq_blocks = KDQ_BLOCKS;
+    p.tracked = c->trk_on && c->trk_in_pass;
     if (c->scenes.on && scenes_neighbor_mode(mode) < 0) {
         c->err = "scenes are set (sca_set_scenes): the scene form of the neighbour search is SCA_NBR_KDTREE (SCA_NBR_AUTO resolves to it)";
         return SCA_ERR_UNSUPPORTED;
     }
+    // SCA_NBR_AUTO: an AUTO pass, or a plain kd pass where that cannot help (plan_auto; the cell-owner partition has its own structures)
+    sca_ctx::Auto &A = c->au;
+    double &ar = p.agent_reach, &orr = p.obs_reach;
+    collide_reach(c, ar, orr);
     if (mode == SCA_NBR_AUTO) {
-        double ar, orr;
-        collide_reach(c, ar, orr);
         // (scenes: the grid's cell key carries no scene id -- one more place where it cannot help)
         const bool fits = !c->scenes.on && c->max_radius + ar <= c->P.neighbor_dist && c->max_radius + orr <= c->P.neighbor_dist;
         if (c->part_on) { c->err = "the cell-owner partition is a mode of SCA_NBR_GRID"; return SCA_ERR_UNSUPPORTED; }
-        if (int r = auto_prepare(c)) return r;
-        if (c->kdq_pending && hipEventQuery(c->ev_auto_cnt) == hipSuccess) { c->kdq_last = c->kdq_host[0]; c->kdq_pending = false; }   // poll
+        if (int r = A.fill(c)) return r;
+        if (A.count_pending && hipEventQuery(A.ev_cnt) == hipSuccess) { A.last = A.count_host[0]; A.count_pending = false; }   // poll
         // (sca_run_steps only builds ahead when auto_next() holds)
-        const AutoPlan A = plan_auto(fits, tracked, c->kd_ahead, c->kdq_last, c->tun.auto_div, c->auto_backoff, c->d.shard_count);
-        c->auto_backoff = A.auto_backoff; c->kdq_last = A.kdq_last; kdq_blocks = A.kdq_blocks;
-        auto_mode = A.auto_pass;
-        if (!auto_mode) mode = SCA_NBR_KDTREE;
-        c->auto_fits = fits;
+        const AutoPlan P = plan_auto(fits, p.tracked, A.ahead, A.last, c->tun.auto_div, A.backoff, c->d.shard_count);
+        A.backoff = P.auto_backoff; A.last = P.kdq_last; p.kdq_blocks = P.kdq_blocks;
+        p.auto_mode = P.auto_pass;
+        if (!p.auto_mode) mode = SCA_NBR_KDTREE;
+        A.fits = fits;
     }
-    const bool kd_prebuilt = auto_mode && c->kd_ahead;
-    c->kd_ahead = false;
-    c->auto_ran = auto_mode;
-    if (!auto_mode) { if (int r = auto_join(c)) return r; }            // (a pass that builds its tree in place: kd_stream must be through)
+    p.mode = mode;
+    p.kd_prebuilt = p.auto_mode && A.ahead;
+    A.ahead = false;
+    A.ran = p.auto_mode;
+    if (!p.auto_mode) { if (int r = auto_join(c)) return r; }          // (a pass that builds its tree in place: the kd stream must be through)
     const DeviceView &d = c->d;
-    const int cnt = d.shard_count;
-    // the shard's LP agents: [lp_lo, lp_hi) of lp_ids (under the partition ownership is dynamic: the LP kernels walk all owned agents and skip the others)
-    int lp_lo = 0, lp_hi = c->h_lp_list.empty() ? 0 : cnt;
-    const int32_t *lp_ids = c->part_on ? d.own : c->lp_list;
+    const int cnt = p.cnt = d.shard_count;
+    p.lp_hi = c->h_lp_list.empty() ? 0 : cnt;
+    p.lp_ids = c->part_on ? d.own : c->lp_list;
     if (!c->part_on) {
-        lp_lo = (int)(std::lower_bound(c->h_lp_list.begin(), c->h_lp_list.end(), d.shard_begin) - c->h_lp_list.begin());
-        lp_hi = (int)(std::lower_bound(c->h_lp_list.begin(), c->h_lp_list.end(), d.shard_begin + cnt) - c->h_lp_list.begin());
+        p.lp_lo = (int)(std::lower_bound(c->h_lp_list.begin(), c->h_lp_list.end(), d.shard_begin) - c->h_lp_list.begin());
+        p.lp_hi = (int)(std::lower_bound(c->h_lp_list.begin(), c->h_lp_list.end(), d.shard_begin + cnt) - c->h_lp_list.begin());
     }
-    const bool overlap = tracked && (mode == SCA_NBR_KDTREE || mode == SCA_NBR_GRID || auto_mode);
+    p.overlap = p.tracked && (mode == SCA_NBR_KDTREE || mode == SCA_NBR_GRID || p.auto_mode);
     // plan: K1's form, k_solve's (its v_pref-independent half right behind the neighbour query, i.e. beside the re-plans when they are
     // overlapped; or the form that finishes its own fallbacks), K3's and the epilogue's
     const auto plan = [&](bool no_scratch) {
-        return plan_solve(c->tun, c->simds, cnt, c->part_on, c->part_nranks, (long long)c->h_lp_list.size(), lp_hi - lp_lo, overlap, c->trk_last_count, no_scratch);
+        return plan_solve(c->tun, c->simds, cnt, c->part_on, c->part_nranks, (long long)c->h_lp_list.size(), p.lp_hi - p.lp_lo, p.overlap, c->trk_last_count, no_scratch);
     };
-    SolvePlan S = plan(false);
-    if (S.split && !c->d.sw_slot) {
+    p.S = plan(false);
+    if (p.S.split && !c->d.sw_slot) {
         // scratch of the two-launch solve (cones + survivor lists, ~2 KB per agent): all three buffers or none, and a pass that
         // cannot have them runs the one-launch k_solve instead of failing
         const size_t N = (size_t)c->max_n;
@@ -2624,98 +2634,137 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
                         hipMalloc((void **)&b, sizeof(uint16_t) * N * 512) == hipSuccess &&
                         hipMalloc((void **)&e, sizeof(int32_t) * N) == hipSuccess;
         if (ok) { c->d.sw_slot = a; c->d.sw_surv = b; c->d.sw_n = e; }
-        else { (void)hipGetLastError(); if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (e) (void)hipFree(e); S = plan(true); }
+        else { (void)hipGetLastError(); if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (e) (void)hipFree(e); p.S = plan(true); }
     }
-    const bool split = S.split, solve_fb = S.solve_fb;
-    c->d.lp_kernel = S.lp_kernel;
-    int forms = S.forms | (c->paths_on ? SCA_FORM_WAYPOINTS : 0) | (c->scenes.on ? SCA_FORM_SCENES : 0) |
-                (c->scenes.obs_on ? SCA_FORM_SCENE_OBSTACLES : 0);     // (the waypoint and scene bits are state, not a choice)
-    c->kd.skip_prep = overlap ? 1 : 0;
-    c->grid.skip_prep = overlap ? 1 : 0;
-    if (mode == SCA_NBR_GRID) {
-        // K4's candidate lists and its fallback cover one cell around the agent: the collision reach must fit into it
-        double agent_reach, obs_reach;
-        collide_reach(c, agent_reach, obs_reach);
-        if (c->max_radius + agent_reach > c->P.neighbor_dist || c->max_radius + obs_reach > c->P.neighbor_dist) {
-            c->err = "SCA_NBR_GRID needs radius + collision reach <= neighbor_dist"; return SCA_ERR_UNSUPPORTED;
-        }
+    c->d.lp_kernel = p.S.lp_kernel;
+    p.forms = p.S.forms | (c->paths_on ? SCA_FORM_WAYPOINTS : 0) | (c->scenes.on ? SCA_FORM_SCENES : 0) |
+              (c->scenes.obs_on ? SCA_FORM_SCENE_OBSTACLES : 0);       // (the waypoint and scene bits are state, not a choice)
+    c->kd.skip_prep = c->grid.skip_prep = p.overlap ? 1 : 0;
+    // K4's candidate lists and its fallback cover one cell around the agent: the collision reach must fit into it
+    if (mode == SCA_NBR_GRID && (c->max_radius + ar > c->P.neighbor_dist || c->max_radius + orr > c->P.neighbor_dist)) {
+        c->err = "SCA_NBR_GRID needs radius + collision reach <= neighbor_dist"; return SCA_ERR_UNSUPPORTED;
     }
+    return 0;
+}
+// k_waypoint*, the fork onto the side stream, the AUTO pass's kd build
+static int pass_fork(sca_ctx *c, PassPlan &p) {
     // Streams.  Without the tracker everything is one chain on the main stream.  With it (overlap): the pass's critical path
     // k_track -> re-plans -> prologue -> pick stays on the main stream, and the neighbour structure + query (+ the sweep half of
     // k_solve), which depend on nothing of the tracker -- it reads agent.neighbors[0] from what the previous pass's epilogue
     // saved, not from the lists K1 overwrites -- run beside them on trk_stream:
     //   main: [fork] k_track re-plans (or k_track_replan) ........ [wait join] k_solve / k_solve_pick4 ...
     //   side: [wait fork] K0 ...... K1 (k_solve_sweep) [join]
-    c->nbr_stream = overlap ? c->trk_stream : c->stream;
+    c->nbr_stream = p.overlap ? c->trk_stream : c->stream;
     // waypoint lists: get_trajectory (the head of every find_next_action) on the main stream, in front of the fork below and of the AUTO
     // build's -- so in front of every prologue site on every stream (k_kd_gather / the grid's first kernel on either stream, k_prep, k_solve*,
     // track_store).  sca_run_steps records no fork on the previous step's last kernel while paths are set (fork_ready is false here then);
     // an AUTO build enqueued ahead (aux) computes no prologue.
     if (c->paths_on) {
-        if (fork_ready) { c->err = "internal: a fork recorded ahead of k_waypoint"; return SCA_ERR_STATE; }
-        if (d.shard_count > 0 && c->path_W)
-            hipLaunchKernelGGL(k_waypoint_slots, dim3((d.shard_count + 255) / 256), dim3(256), 0, c->stream, c->d,
+        if (p.fork_ready) { c->err = "internal: a fork recorded ahead of k_waypoint"; return SCA_ERR_STATE; }
+        if (p.cnt > 0 && c->path_W)
+            hipLaunchKernelGGL(k_waypoint_slots, dim3((p.cnt + 255) / 256), dim3(256), 0, c->stream, c->d,
                                PathSlotView{c->pslot_pts, c->pslot_len, c->path.rem, c->path.now_goal, c->path_W});
-        else if (d.shard_count > 0) hipLaunchKernelGGL(k_waypoint, dim3((d.shard_count + 255) / 256), dim3(256), 0, c->stream, c->d, c->path);
+        else if (p.cnt > 0) hipLaunchKernelGGL(k_waypoint, dim3((p.cnt + 255) / 256), dim3(256), 0, c->stream, c->d, c->path);
     }
-    const unsigned parity_now = (unsigned)c->trk.parity;
-    if (overlap) {
-        if (!fork_ready) CHK(c, hipEventRecord(c->trk_fork, c->stream));   // (fork_ready: it rode on the previous step's last kernel, sca_run_steps)
+    p.parity_now = (unsigned)c->trk.parity;
+    if (p.overlap) {
+        if (!p.fork_ready) CHK(c, hipEventRecord(c->trk_fork, c->stream));   // (fork_ready: it rode on the previous step's last kernel, sca_run_steps)
         CHK(c, hipStreamWaitEvent(c->trk_stream, c->trk_fork, 0));
     }
-    if (auto_mode && !kd_prebuilt) {
-        // SCA_NBR_AUTO: the kd build (its permutation is history: every step) on a stream of its own, from the pass's start
-        CHK(c, hipEventRecord(c->ev_auto_fork, c->stream));
-        if (int r = auto_enqueue_kd_build(c, c->ev_auto_fork, c->d.rec)) return r;
+    sca_ctx::Auto &A = c->au;
+    if (p.auto_mode && !p.kd_prebuilt) {   // SCA_NBR_AUTO: the kd build (its permutation is history: every step) on a stream of its own, from the pass's start
+        CHK(c, hipEventRecord(A.ev_fork, c->stream));
+        if (int r = auto_enqueue_kd_build(c, A.ev_fork, c->d.rec, false)) return r;
     }
-    c->trk.prep = overlap ? 1 : 0;
-    c->trk.P = c->P;
-    if (tracked) { int f = 0; if (int r = launch_tracker(c, true, true, f)) return r; forms |= f; }
-    c->nbr_mode = auto_mode ? (int)SCA_NBR_GRID : mode;               // (what K4's fallback looks into: the grid in an AUTO pass)
-    if (auto_mode) {
+    if (p.auto_mode)                    // (A.tail, the launch-free form: the grid query's last workgroup answers whoever is listed, from the tree its pass's build publishes)
+        p.A = plan_auto_pass(A.seq, A.tail_seq, A.on_kd, A.waitvalue, A.count_pending, A.passes, A.builds);
+    c->trk.prep = p.overlap ? 1 : 0; c->trk.P = c->P;
+    return 0;
+}
+// K0: the neighbour structure of the pass, on nbr_stream
+static int pass_structure(sca_ctx *c, const PassPlan &p) {
+    c->nbr_mode = p.auto_mode ? (int)SCA_NBR_GRID : p.mode;           // (what K4's fallback looks into: the grid in an AUTO pass)
+    if (p.auto_mode) {
         c->d.kdq_cap = std::max(1, c->d.shard_count / c->tun.auto_div);
-        {   // this pass's list (the previous pass's kd query may still be looking at the other one's length)
-            const unsigned par = (c->auto_seq + 1) & 1u;
-            c->d.kdq_list = c->kdq_list + (size_t)par * c->max_n;
-            c->d.kdq_count = c->kdq_count + par;
-            // ... which the kd query of two passes ago must be through with (it is, unless the kd stream lags by two whole passes)
-            // (slot [(seq - 2) & 3], seq = auto_seq + 1; a build enqueued in the tail form has made the pass's stream wait already)
-            if (c->auto_seq >= 2 && c->kd_tail_seq != c->auto_seq + 1 && c->kdq_on_kd_stream[(c->auto_seq - 1) & 3u]) { if (int r = wait_if_pending(c, c->nbr_stream, c->ev_auto_kdq[(c->auto_seq - 1) & 3u])) return r; }
-        }
-        if (int r = build_agent_grid_device(c)) return r;
+        // this pass's list (the previous pass's kd query may still be looking at the other one's length)
+        c->d.kdq_list = c->au.list + (size_t)p.A.parity * c->max_n;
+        c->d.kdq_count = c->au.count + p.A.parity;
+        // ... which the kd query of two passes ago must be through with (it is, unless the kd stream lags by two whole passes)
+        if (p.A.reuse_slot != AUTO_NO_SLOT) { if (int r = wait_if_pending(c, c->nbr_stream, c->au.ev_kdq[p.A.reuse_slot])) return r; }
+        return build_agent_grid_device(c);
     }
-    else if (mode == SCA_NBR_KDTREE) { if (int r = build_agent_tree_device(c, c->nbr_stream, c->d)) return r; }
-    else if (mode == SCA_NBR_GRID) { if (int r = build_agent_grid_device(c)) return r; }
-    else if (mode == SCA_NBR_KDTREE_HOSTBUILD) {
-        if (c->perm_on_device) {
-            CHK(c, hipMemcpyAsync(c->h_perm.data(), c->d.aperm, sizeof(int32_t) * c->n, hipMemcpyDeviceToHost, c->stream));
-            CHK(c, hipStreamSynchronize(c->stream));
-            c->perm_on_device = false;
-        }
-        if (int r = build_agent_tree(c)) return r;
-        hipLaunchKernelGGL(k_prep, dim3((c->n + 255) / 256), dim3(256), 0, c->stream, c->d, c->P);
-    } else { c->err = "neighbor mode not available in this build"; return SCA_ERR_UNSUPPORTED; }
+    if (p.mode == SCA_NBR_KDTREE) return build_agent_tree_device(c, c->nbr_stream, c->d);
+    if (p.mode == SCA_NBR_GRID) return build_agent_grid_device(c);
+    if (p.mode != SCA_NBR_KDTREE_HOSTBUILD) { c->err = "neighbor mode not available in this build"; return SCA_ERR_UNSUPPORTED; }
+    if (c->perm_on_device) {
+        CHK(c, hipMemcpyAsync(c->h_perm.data(), c->d.aperm, sizeof(int32_t) * c->n, hipMemcpyDeviceToHost, c->stream));
+        CHK(c, hipStreamSynchronize(c->stream));
+        c->perm_on_device = false;
+    }
+    if (int r = build_agent_tree(c)) return r;
+    hipLaunchKernelGGL(k_prep, dim3((c->n + 255) / 256), dim3(256), 0, c->stream, c->d, c->P);
+    return 0;
+}
+// the listed agents of an AUTO pass: their kd query, the list length's copy, the wait for final lists
+static int pass_query_auto(sca_ctx *c, PassPlan &p) {
+    sca_ctx::Auto &A = c->au;
     hipStream_t ns = c->nbr_stream;
-    hipEvent_t e0 = c->ev[0], e1 = c->ev[1], e2 = c->ev[2], e3 = c->ev[3];
-    const bool prof = !timed && c->profiling && (c->prof_tick++ & 15u) == 0 && c->pool_used + 4 <= 4 * 4096;
-    if (prof) { if (pool_event(c, &e0) || pool_event(c, &e1) || pool_event(c, &e2) || pool_event(c, &e3)) return SCA_ERR_HIP; }
-    if (timed || prof) CHK(c, hipEventRecord(e0, ns));
-    double agent_reach, obs_reach;
-    collide_reach(c, agent_reach, obs_reach);
+    // the agents the grid query listed (more than max_neighbors in range, equal distances) get the kd-tree's answer: behind the
+    // build on the kd stream, and nothing reads a list before that query is through
+    A.seq = p.A.seq;                                                   // (its parity picked the list; it may wrap)
+    A.on_kd = p.A.on_kd;
+    // (the launch-free form: the grid query's own last workgroup has answered the listed agents from this pass's tree (KdTail) -- no
+    // launch, no cross-stream wait on the build's stream, no stream wait operation on this one)
+    if (p.A.tail) p.forms |= SCA_FORM_AUTO_TAIL;
+    else {
+        CHK(c, hipStreamWaitEvent(A.stream, A.ev_k1g, 0));            // (recorded behind the grid query)
+        // (ev_kdq: also "the last kd query": auto_join and the event form of the wait)
+        LAUNCH_REC(c, A.ev_kdq[p.A.kdq_slot], k_neighbors_kd_auto, dim3(p.kdq_blocks), dim3(K1_WAVES * 64), A.stream, c->d, c->P, p.agent_reach, p.obs_reach, c->max_radius, A.ticket);
+    }
+    // (ADVICE.md questions this copy's place on the kd stream, behind the build: moving it is a behaviour change for a pull request of its own)
+    if (p.A.copy_count) {                                              // how many were listed: for later passes' choice, never waited for
+        CHK(c, hipMemcpyAsync(A.count_host, c->d.kdq_count, sizeof(int), hipMemcpyDeviceToHost, A.stream));
+        CHK(c, hipEventRecord(A.ev_cnt, A.stream));
+        A.count_pending = true;
+    }
+    A.passes = p.A.passes;
+    A.ev_kd = A.ev_kdq[p.A.kdq_slot];
+    // (AUTO_WAIT_NONE, the launch-free form: the lists are final when the grid query's launch ends -- its last workgroup answered whoever was listed)
+    if (p.A.wait == AUTO_WAIT_VALUE) {
+        // lists final: at once when the grid query listed nobody, else behind the kd query (see k_neighbors_kd_auto)
+        if (hipStreamWaitValue32(ns, A.busy, 0u, hipStreamWaitValueEq, 1u) != hipSuccess) {
+            (void)hipGetLastError();                                  // a platform without stream memory operations: the event wait from now on
+            A.waitvalue = false;
+            CHK(c, hipStreamWaitEvent(ns, A.ev_kd, 0));
+        }
+    } else if (p.A.wait == AUTO_WAIT_EVENT) CHK(c, hipStreamWaitEvent(ns, A.ev_kd, 0));
+    // [e0, e1] of an AUTO pass: the grid query AND the wait for the kd query of the listed agents behind it (the lists are final here)
+    if (p.timed || p.prof) CHK(c, hipEventRecord(p.e[1], ns));
+    return 0;
+}
+// K1 in its forms, on nbr_stream
+static int pass_query(sca_ctx *c, PassPlan &p) {
+    const DeviceView &d = c->d;
+    const int cnt = p.cnt;
+    const SolvePlan &S = p.S;
+    hipStream_t ns = c->nbr_stream;
+    for (int i = 0; i < 4; i++) p.e[i] = c->ev[i];
+    p.prof = !p.timed && c->profiling && (c->prof_tick++ & 15u) == 0 && c->pool_used + 4 <= 4 * 4096;
+    if (p.prof) { for (hipEvent_t &e : p.e) if (pool_event(c, &e)) return SCA_ERR_HIP; }
+    if (p.timed || p.prof) CHK(c, hipEventRecord(p.e[0], ns));
+    const double agent_reach = p.agent_reach, obs_reach = p.obs_reach;
     // (overlapped: the join rides on the side stream's last kernel -- the neighbour query, or the sweep behind it)
-    const hipEvent_t k1_stop = overlap && !split && c->tun.ext_stop ? c->trk_join : nullptr;
-    const hipEvent_t sweep_stop = overlap && split && c->tun.ext_stop ? c->trk_join : nullptr;
+    const hipEvent_t k1_stop = p.k1_stop = p.overlap && !S.split && c->tun.ext_stop ? c->trk_join : nullptr;
+    p.sweep_stop = p.overlap && S.split && c->tun.ext_stop ? c->trk_join : nullptr;
     const bool obs = d.m > 0;                                           // (scenes without obstacles: the K1 forms without the obstacle phase, see neighbors_one)
-    // (the launch-free form: the grid query's last workgroup answers whoever is listed, from the tree its pass's build publishes)
-    const bool tail = auto_mode && c->kd_tail_seq == c->auto_seq + 1 && c->kd_tail_seq != 0;
     const dim3 k1p_grid((cnt + K1P_WAVES * K1P_APW - 1) / (K1P_WAVES * K1P_APW)), k1p_block(K1P_WAVES * 64);
-    if (auto_mode) {
-        c->d.auto_sync = tail ? c->auto_sync : nullptr;                 // (d is c->d)
-        c->d.auto_pass_seq = c->auto_seq + 1;
+    if (p.auto_mode) {
+        c->d.auto_sync = p.A.tail ? c->au.sync : nullptr;                 // (d is c->d)
+        c->d.auto_pass_seq = p.A.seq;
         c->d.auto_err = c->kd.counts + KD_MAX_LEVELS + 1;
         const auto k1 = obs ? k_neighbors_grid<true, true> : k_neighbors_grid<true, false>;
-        LAUNCH_REC(c, c->ev_auto_k1g, k1, k1p_grid, k1p_block, ns, d, c->grid, c->P, agent_reach, obs_reach, c->max_radius);
-    } else if (mode == SCA_NBR_GRID) {
+        LAUNCH_REC(c, c->au.ev_k1g, k1, k1p_grid, k1p_block, ns, d, c->grid, c->P, agent_reach, obs_reach, c->max_radius);
+    } else if (p.mode == SCA_NBR_GRID) {
         const auto k1 = obs ? k_neighbors_grid<false, true> : k_neighbors_grid<false, false>;
         LAUNCH_OPT(c, k1_stop, k1, k1p_grid, k1p_block, ns, d, c->grid, c->P, agent_reach, obs_reach, c->max_radius);
     } else if (c->scenes.on) {                                          // (obs_on: per-scene sets with at least one obstacle, always the obstacle phase)
@@ -2734,94 +2783,82 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
         LAUNCH_OPT(c, k1_stop, k1, dim3(std::min((cnt + K1_WAVES - 1) / K1_WAVES, MAX_GRID)), dim3(K1_WAVES * 64), ns, d, c->P, agent_reach, obs_reach, c->max_radius);
     }
     c->near_valid = true;
-    if ((timed || prof) && !auto_mode) CHK(c, hipEventRecord(e1, ns));    // [e0, e1] = K1
-    if (auto_mode) {
-        // the agents the grid query listed (more than max_neighbors in range, equal distances) get the kd-tree's answer: behind the
-        // build on kd_stream, and nothing reads a list before that query is through
-        const unsigned seq = ++c->auto_seq;                            // (its parity picks the list; it may wrap)
-        c->kdq_on_kd_stream[seq & 3u] = !tail;
-        if (tail) {
-            // the launch-free form: the grid query's own last workgroup has answered the listed agents from this pass's tree (KdTail) -- no
-            // launch, no cross-stream wait on the build's stream, no stream wait operation on this one
-            forms |= SCA_FORM_AUTO_TAIL;
-        } else {
-            CHK(c, hipStreamWaitEvent(c->kd_stream, c->ev_auto_k1g, 0));     // (recorded behind the grid query above)
-            // (ev_auto_kdq: also "the last kd query": auto_join and the event form of the wait)
-            LAUNCH_REC(c, c->ev_auto_kdq[seq & 3u], k_neighbors_kd_auto, dim3(kdq_blocks), dim3(K1_WAVES * 64), c->kd_stream, d, c->P, agent_reach, obs_reach, c->max_radius, c->auto_ticket);
-        }
-        // (ADVICE.md questions this copy's place on kd_stream, behind the build: moving it is a behaviour change for a pull request of its own)
-        if (!c->kdq_pending && (c->auto_passes++ & 3u) == 0) {       // how many were listed: for later passes' choice, never waited for
-            CHK(c, hipMemcpyAsync(c->kdq_host, d.kdq_count, sizeof(int), hipMemcpyDeviceToHost, c->kd_stream));
-            CHK(c, hipEventRecord(c->ev_auto_cnt, c->kd_stream));
-            c->kdq_pending = true;
-        }
-        c->ev_auto_kd = c->ev_auto_kdq[seq & 3u];
-        if (tail) {
-            // (the launch-free form: the lists are final when the grid query's launch ends -- its last workgroup answered whoever was listed)
-        } else if (c->auto_waitvalue) {
-            // lists final: at once when the grid query listed nobody, else behind the kd query (see k_neighbors_kd_auto)
-            if (hipStreamWaitValue32(ns, c->auto_busy, 0u, hipStreamWaitValueEq, 1u) != hipSuccess) {
-                (void)hipGetLastError();                              // a platform without stream memory operations: the event wait from now on
-                c->auto_waitvalue = false;
-                CHK(c, hipStreamWaitEvent(ns, c->ev_auto_kd, 0));
-            }
-        } else CHK(c, hipStreamWaitEvent(ns, c->ev_auto_kd, 0));
-        if (timed || prof) CHK(c, hipEventRecord(e1, ns));               // [e0, e1] of an AUTO pass: the grid query AND the wait for the kd query
-                                                                        // of the listed agents behind it (the lists are final here)
-    }
-    if (split) {
-        LAUNCH_OPT(c, sweep_stop, k_solve_sweep, dim3((cnt + SOLVE_WAVES - 1) / SOLVE_WAVES), dim3(SOLVE_WAVES * 64), ns, d, c->P);
-    }
-    if (overlap) {
+    if (p.auto_mode) return pass_query_auto(c, p);
+    if (p.timed || p.prof) CHK(c, hipEventRecord(p.e[1], ns));          // [e0, e1] = K1
+    return 0;
+}
+// the sweep half of a split solve, the re-plan count's copy, the join of the side stream
+static int pass_join(sca_ctx *c, const PassPlan &p) {
+    hipStream_t ns = c->nbr_stream;
+    if (p.S.split) LAUNCH_OPT(c, p.sweep_stop, k_solve_sweep, dim3((p.cnt + SOLVE_WAVES - 1) / SOLVE_WAVES), dim3(SOLVE_WAVES * 64), ns, c->d, c->P);
+    if (p.overlap) {
         // the re-plan count of this pass for a later pass's launch decision: on the side stream, every 4th pass, never waited for
         const unsigned pass = c->trk_passes++;
         if (!c->trk_count_pending && (pass & 3u) == 1) {                    // the previous pass's slot: final since before the fork
                                                                             // (first at the second pass: the forms settle within three)
-            CHK(c, hipMemcpyAsync(c->trk_host_count, c->trk.count + ((parity_now + 3u) & 3u), sizeof(int), hipMemcpyDeviceToHost, ns));
+            CHK(c, hipMemcpyAsync(c->trk_host_count, c->trk.count + ((p.parity_now + 3u) & 3u), sizeof(int), hipMemcpyDeviceToHost, ns));
             CHK(c, hipEventRecord(c->trk_count_ev, ns));
             c->trk_count_pending = true;
         }
-        if (!k1_stop && !sweep_stop) CHK(c, hipEventRecord(c->trk_join, ns));
+        if (!p.k1_stop && !p.sweep_stop) CHK(c, hipEventRecord(c->trk_join, ns));
         CHK(c, hipStreamWaitEvent(c->stream, c->trk_join, 0));                // (the prologue: track_store / the gather)
     }
-    if (timed || prof) CHK(c, hipEventRecord(e2, c->stream));
-    if (split) {
-        const int per_block = SOLVE_WAVES * PICK_APW;
-        hipLaunchKernelGGL(k_solve_pick4, dim3((cnt + per_block - 1) / per_block), dim3(SOLVE_WAVES * 64), 0, c->stream, d, c->P);
-    }
-    else if (solve_fb) hipLaunchKernelGGL(k_solve_fb, dim3((cnt + SOLVE_WAVES - 1) / SOLVE_WAVES), dim3(SOLVE_WAVES * 64), 0, c->stream, d, c->P);
+    if (p.timed || p.prof) CHK(c, hipEventRecord(p.e[2], c->stream));
+    return 0;
+}
+// k_solve in its forms and K3, on the main stream
+static int pass_solve(sca_ctx *c, const PassPlan &p) {
+    const DeviceView &d = c->d;
+    const int cnt = p.cnt;
+    if (p.S.split) hipLaunchKernelGGL(k_solve_pick4, dim3((cnt + SOLVE_WAVES * PICK_APW - 1) / (SOLVE_WAVES * PICK_APW)), dim3(SOLVE_WAVES * 64), 0, c->stream, d, c->P);
+    else if (p.S.solve_fb) hipLaunchKernelGGL(k_solve_fb, dim3((cnt + SOLVE_WAVES - 1) / SOLVE_WAVES), dim3(SOLVE_WAVES * 64), 0, c->stream, d, c->P);
     else {
         hipLaunchKernelGGL(k_solve, dim3((cnt + SOLVE_WAVES - 1) / SOLVE_WAVES), dim3(SOLVE_WAVES * 64), 0, c->stream, d, c->P);
-        if (S.lpw)                                                    // K3, one wavefront per LP agent (few of them)
-            hipLaunchKernelGGL(k_solve_lpw, dim3((lp_hi - lp_lo + SOLVE_WAVES - 1) / SOLVE_WAVES), dim3(SOLVE_WAVES * 64), 0, c->stream, d, c->P,
-                               lp_ids, lp_lo, lp_hi);
+        if (p.S.lpw)                                                  // K3, one wavefront per LP agent (few of them)
+            hipLaunchKernelGGL(k_solve_lpw, dim3((p.lp_hi - p.lp_lo + SOLVE_WAVES - 1) / SOLVE_WAVES), dim3(SOLVE_WAVES * 64), 0, c->stream, d, c->P,
+                               p.lp_ids, p.lp_lo, p.lp_hi);
     }
-    if (S.lp_kernel)                                                  // K3: the LP agents of the shard, one lane each
-        hipLaunchKernelGGL(k_lp, dim3((lp_hi - lp_lo + 63) / 64), dim3(64), 0, c->stream, d, c->P, lp_ids, lp_lo, lp_hi);
-    if (timed || prof) CHK(c, hipEventRecord(e3, c->stream));         // [e2, e3] = k_solve (+ k_lp) (what rocprofv3 reports for them)
-    // the agents without any suitable candidate (rare; one wavefront each), then the epilogue (one lane per agent)
-    const int ablocks = (cnt + 255) / 256;
-    if (auto_mode && c->auto_waitvalue) {
+    if (p.S.lp_kernel)                                                // K3: the LP agents of the shard, one lane each
+        hipLaunchKernelGGL(k_lp, dim3((p.lp_hi - p.lp_lo + 63) / 64), dim3(64), 0, c->stream, d, c->P, p.lp_ids, p.lp_lo, p.lp_hi);
+    if (p.timed || p.prof) CHK(c, hipEventRecord(p.e[3], c->stream));  // [e2, e3] = k_solve (+ k_lp) (what rocprofv3 reports for them)
+    return 0;
+}
+// the agents without any suitable candidate (rare; one wavefront each), then the epilogue (one lane per agent)
+static int pass_epilogue(sca_ctx *c, const PassPlan &p) {
+    const DeviceView &d = c->d;
+    const int ablocks = (p.cnt + 255) / 256;
+    if (p.auto_mode && c->au.waitvalue) {
         // nothing of this pass waited for the kd build any more.  Two things still must: (i) the integrate stage writes the record
         // buffer that the build BEFORE this pass's read its positions from (the two buffers alternate): wait for that build's gather;
-        if (int r = wait_if_pending(c, c->stream, c->ev_auto_gather[c->auto_builds & 1u])) return r;       // [builds & 1] = the one before the last
-        c->auto_unjoined = true;                                        // (ii) see auto_join
+        if (int r = wait_if_pending(c, c->stream, c->au.ev_gather[p.A.gather_slot])) return r;
+        c->au.unjoined = true;                                          // (ii) see auto_join
     }
     // (small shards: the fallback sweep rides in the epilogue's launch -- k_action_fb -- instead of in front of it)
-    const hipEvent_t action_stop = fuse_integrate ? c->action_stop : nullptr;
-    if (S.action_fb) {
-        const auto k = fuse_integrate ? k_action_fb<true> : k_action_fb<false>;
+    const hipEvent_t action_stop = p.fuse_integrate ? c->action_stop : nullptr;
+    if (p.S.action_fb) {
+        const auto k = p.fuse_integrate ? k_action_fb<true> : k_action_fb<false>;
         LAUNCH_OPT(c, action_stop, k, dim3(ablocks + FB_BLOCKS_SMALL), dim3(SOLVE_WAVES * 64), c->stream, d, c->P, ablocks);
     } else {
-        const auto kf = fuse_integrate ? k_fallback<true> : k_fallback<false>;
-        const auto ka = fuse_integrate ? k_action<true> : k_action<false>;
-        if (!solve_fb) hipLaunchKernelGGL(kf, dim3(FB_BLOCKS), dim3(SOLVE_WAVES * 64), 0, c->stream, d, c->P);
+        const auto kf = p.fuse_integrate ? k_fallback<true> : k_fallback<false>;
+        const auto ka = p.fuse_integrate ? k_action<true> : k_action<false>;
+        if (!p.S.solve_fb) hipLaunchKernelGGL(kf, dim3(FB_BLOCKS), dim3(SOLVE_WAVES * 64), 0, c->stream, d, c->P);
         LAUNCH_OPT(c, action_stop, ka, dim3(ablocks), dim3(256), c->stream, d, c->P);
     }
-    c->forms = forms;
+    c->forms = p.forms;
     CHK(c, hipGetLastError());
-    if (fuse_integrate && c->d.hist) c->d.hist_row++;
+    if (p.fuse_integrate && c->d.hist) c->d.hist_row++;
     return 0;
+}
+static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) {
+    PassPlan p{timed, fuse_integrate};
+    if (int r = pass_resolve(c, mode, p)) return r;
+    if (int r = pass_fork(c, p)) return r;
+    if (p.tracked) { int f = 0; if (int r = launch_tracker(c, true, true, f)) return r; p.forms |= f; }
+    if (int r = pass_structure(c, p)) return r;
+    if (int r = pass_query(c, p)) return r;
+    if (int r = pass_join(c, p)) return r;
+    if (int r = pass_solve(c, p)) return r;
+    return pass_epilogue(c, p);
 }
 
 static int launch_integrate(sca_ctx *c) {
@@ -2861,9 +2898,9 @@ static int launch_collide_finish(sca_ctx *c, bool timed) {
     }
     if (c->clear) {                                                        // the closest approach of this step over the whole context: a wavefront per agent
         // The agent tree of this step.  A kd pass built it on the pass's own streams, joined into this one in front of the solve -- the order
-        // K4's traversal relies on.  An AUTO pass built it on kd_stream, which nothing of the step waits for (K4 looks into the grid there):
+        // K4's traversal relies on.  An AUTO pass built it on the kd stream, which nothing of the step waits for (K4 looks into the grid there):
         // this stream waits for that build here.
-        if (c->auto_ran) { if (int r = auto_join(c)) return r; }
+        if (c->au.ran) { if (int r = auto_join(c)) return r; }
         double car, cor;
         clearance_reach(c, car, cor);
         hipLaunchKernelGGL(k_clearance, dim3((unsigned)((d.n + CLR_WAVES - 1) / CLR_WAVES)), dim3(CLR_WAVES * 64), 0, c->stream, d, c->clear, car, cor, ++c->clear_step);
@@ -2924,7 +2961,7 @@ int sca_env_update(sca_ctx *c, int *all_done) {
     API_ENTER(c);
     if (!c->state_set) { c->err = "sca_set_state first"; return SCA_ERR_STATE; }
     // (the closest-approach records need this step's agent tree: refused before anything is enqueued)
-    if (int r = clearance_refuse(c, "sca_env_update", clearance_check(CLR_UPDATE, clearance_state(c), c->near_valid ? 1 : 0, c->nbr_mode == SCA_NBR_GRID && !c->auto_ran ? 1 : 0, true, 0))) return r;
+    if (int r = clearance_refuse(c, "sca_env_update", clearance_check(CLR_UPDATE, clearance_state(c), c->near_valid ? 1 : 0, c->nbr_mode == SCA_NBR_GRID && !c->au.ran ? 1 : 0, true, 0))) return r;
     CHK(c, hipEventRecord(c->ev[4], c->stream));
     if (int r = launch_update(c, true)) return r;
     if (all_done) {
@@ -2963,10 +3000,7 @@ static int exchange_moved_records(sca_ctx *c) {
     const size_t bytes = sizeof(PubRec) * (size_t)c->d.shard_count;
     hipEvent_t x0 = nullptr, x1 = nullptr;
     if (c->profiling && c->pool_xch_used + 2 <= 2 * 4096) {              // the collective's device time, on the stream it is enqueued on
-        for (hipEvent_t *ev : {&x0, &x1}) {
-            if (c->pool_xch_used == (int)c->pool_xch.size()) { hipEvent_t n_; CHK(c, hipEventCreate(&n_)); c->pool_xch.push_back(n_); }
-            *ev = c->pool_xch[c->pool_xch_used++];
-        }
+        for (hipEvent_t *ev : {&x0, &x1}) if (int r = pool_take(c, c->pool_xch, c->pool_xch_used, 2 * 4096, ev)) return r;
         CHK(c, hipEventRecord(x0, c->stream));
     }
     const ncclResult_t e = g_rccl.AllGather((const char *)c->d.rec_new + sizeof(PubRec) * (size_t)c->d.shard_begin, c->d.rec_new, bytes,
@@ -2979,20 +3013,18 @@ static int exchange_moved_records(sca_ctx *c) {
 static int run_steps_loop(sca_ctx *c, int steps, int neighbor_mode, bool lazy);
 // A failure in the middle of the loop (an exchange, a launch, a partition commit) must not leave the AUTO bookkeeping pointing at a tree
 // built ahead from positions the caller is about to replace: forget the build-ahead, let the context's stream wait for whatever
-// kd_stream still holds, and have the next AUTO pass decide afresh.
+// the kd stream still holds, and have the next AUTO pass decide afresh.
 static void auto_abandon(sca_ctx *c) {
-    c->lazy_join = false;
-    c->kd_ahead = false; c->kdq_last = -1; c->kdq_pending = false; c->auto_backoff = 0;
-    c->kd_tail_seq = 0;
-    for (bool &b : c->kdq_on_kd_stream) b = false;
-    if (c->kd_stream) { (void)hipStreamSynchronize(c->kd_stream); (void)hipGetLastError(); }
-    if (c->auto_sync) {
+    c->au.forget();
+    c->au.lazy_join = false; c->au.count_pending = false; c->au.tail_seq = 0; c->au.on_kd = 0;
+    if (c->au.stream) { (void)hipStreamSynchronize(c->au.stream); (void)hipGetLastError(); }
+    if (c->au.sync) {
         // (tickets of a pass that was cut short: the words start from zero again)
         (void)hipStreamSynchronize(c->stream);
-        (void)hipMemset(c->auto_sync, 0, 8 * sizeof(unsigned));
+        (void)hipMemset(c->au.sync, 0, 8 * sizeof(unsigned));
         (void)hipGetLastError();
     }
-    c->auto_unjoined = false;
+    c->au.unjoined = false;
 }
 static int run_steps_guarded(sca_ctx *c, int steps, int neighbor_mode, bool lazy) {
     const int r = run_steps_loop(c, steps, neighbor_mode, lazy);
@@ -3022,8 +3054,8 @@ static int run_steps_loop(sca_ctx *c, int steps, int neighbor_mode, bool lazy) {
     if (c->part_on && neighbor_mode != SCA_NBR_GRID) { c->err = "the cell-owner partition is a mode of SCA_NBR_GRID"; return SCA_ERR_UNSUPPORTED; }
     for (int s = 0; s < steps; s++) {
         // (SCA_NBR_AUTO, another step to follow: the moved positions' event rides on k_action -- the next pass's kd build waits on it)
-        c->action_stop = neighbor_mode == SCA_NBR_AUTO && s + 1 < steps && c->kd_stream && c->tun.ext_stop && !c->comm && c->d.shard_count == c->n
-                             ? c->ev_auto_moved : nullptr;                      // (a shard: the records of the others arrive after k_action)
+        c->action_stop = neighbor_mode == SCA_NBR_AUTO && s + 1 < steps && c->au.stream && c->tun.ext_stop && !c->comm && c->d.shard_count == c->n
+                             ? c->au.ev_moved : nullptr;                      // (a shard: the records of the others arrive after k_action)
         const int rp = launch_policy(c, neighbor_mode, false, true);           // integrate fused into k_solve
         const bool moved_recorded = c->action_stop != nullptr;
         c->action_stop = nullptr;
@@ -3040,21 +3072,18 @@ static int run_steps_loop(sca_ctx *c, int steps, int neighbor_mode, bool lazy) {
             if (e < c->n) CHK(c, hipMemcpyAsync(c->d.rec_new + e, c->d.rec + e, sizeof(PubRec) * (size_t)(c->n - e), hipMemcpyDeviceToDevice, c->stream));
         }
         // (not with the closest-approach records on: k_clearance reads this step's tree, which a build enqueued ahead would overwrite beside it)
-        if (neighbor_mode == SCA_NBR_AUTO && c->auto_ran && s + 1 < steps && !c->clear &&
-            auto_next(c->auto_fits, c->trk_on && c->trk_in_pass, c->part_on, c->kdq_last, c->tun.auto_div, c->auto_backoff, c->d.shard_count)) {
+        if (neighbor_mode == SCA_NBR_AUTO && c->au.ran && s + 1 < steps && !c->clear &&
+            auto_next(c->au.fits, c->trk_on && c->trk_in_pass, c->part_on, c->au.last, c->tun.auto_div, c->au.backoff, c->d.shard_count)) {
             // SCA_NBR_AUTO: the NEXT pass's kd build needs the moved positions only -- k_collide_finish changes flags, and in an
             // AUTO pass its fallback looks into the grid, not into the tree -- so it starts here, beside the collision check and the
             // next pass's grid build and query.  Only inside one call: a caller who reads the permutation between calls sees as many
             // builds as steps.
             // (the collision check goes to its stream FIRST: the host needs ~5 us per launch, and the build's eight or more launches in
             // front of it left the main stream idle for 50 us at N = 4096)
-            if (!moved_recorded) CHK(c, hipEventRecord(c->ev_auto_moved, c->stream));
+            if (!moved_recorded) CHK(c, hipEventRecord(c->au.ev_moved, c->stream));
             if (int r = launch_collide_finish(c, false)) return r;                 // ((no tracker in an AUTO pass: no fork to carry) swaps the record buffers: the moved ones are c->d.rec now)
-            c->kd_ahead_enqueue = true;
-            const int rb = auto_enqueue_kd_build(c, c->ev_auto_moved, c->d.rec);
-            c->kd_ahead_enqueue = false;
-            if (rb) return rb;
-            c->kd_ahead = true;
+            if (int r = auto_enqueue_kd_build(c, c->au.ev_moved, c->d.rec, true)) return r;
+            c->au.ahead = true;
             continue;
         }
         // the next pass's fork (tracker in the pass, its neighbour branch on the side stream) rides on this step's last kernel
@@ -3065,14 +3094,14 @@ static int run_steps_loop(sca_ctx *c, int steps, int neighbor_mode, bool lazy) {
         c->finish_stop = nullptr;
         if (rf) return rf;
     }
-    if (lazy && c->auto_unjoined && c->auto_ran) { c->lazy_join = true; return 0; }   // (sca_env_step: see API_ENTER)
+    if (lazy && c->au.unjoined && c->au.ran) { c->au.lazy_join = true; return 0; }   // (sca_env_step: see API_ENTER)
     return auto_join(c);
 }
 int sca_env_step(sca_ctx *c, int neighbor_mode, int *active) {
     if (!c) return SCA_ERR_ARG;                                           // (not API_ENTER: a step after a step needs no join)
     ARG(c, active);
     if (int r = run_steps_guarded(c, 1, neighbor_mode, true)) return r;
-    // (the kd build's error word is read from the context's stream: a build still running on kd_stream is seen one step later)
+    // (the kd build's error word is read from the context's stream: a build still running on the kd stream is seen one step later)
     return read_active(c, active, c->perm_on_device);
 }
 // ---- the env loop with the host as the owner of the state (mampenv.py:27-59): a pinned state block and one call per step ------------------
@@ -3160,10 +3189,8 @@ int sca_step_host(sca_ctx *c, int neighbor_mode, uint32_t in_mask, int *active) 
         hipLaunchKernelGGL(k_host_ingest, grid, block, 0, c->stream, io, (const uint8_t *)blk, n, in_mask);
         CHK(c, hipGetLastError());
         if (in_mask & SCA_HOST_IN_STATE) {                                 // sca_set_state's bookkeeping (no host mirror of the positions is kept)
-            c->kd_single_hint = 0; c->kd_gen++;
-            c->kd_ahead = false; c->kdq_last = -1; c->auto_backoff = 0;
-            c->h_pos_valid = false;
-            c->near_valid = false;
+            positions_replaced(c); c->au.forget();
+            c->h_pos_valid = false; c->near_valid = false;
             c->state_set = true; c->state_fresh = true;
             c->scenes.live_valid = false; c->scenes.begun = false;
         }
@@ -3201,7 +3228,7 @@ int sca_auto_stats(sca_ctx *c, int64_t *out4, int reset) {
     ARG(c, out4);
     for (int k = 0; k < 4; k++) out4[k] = 0;
     if (!c->d.kdq_stats) return 0;                                       // no SCA_NBR_AUTO pass has run
-    if (c->kd_stream) CHK(c, hipStreamSynchronize(c->kd_stream));
+    if (c->au.stream) CHK(c, hipStreamSynchronize(c->au.stream));
     unsigned long long h[4];
     CHK(c, hipMemcpy(h, c->d.kdq_stats, sizeof(h), hipMemcpyDeviceToHost));
     for (int k = 0; k < 4; k++) out4[k] = (int64_t)h[k];
@@ -3468,7 +3495,7 @@ int sca_step_begin(sca_ctx *c, int neighbor_mode) {
 int sca_step_end(sca_ctx *c) {
     API_ENTER(c);
     // (the closest-approach records need this step's agent tree: sca_env_update's refusal)
-    if (int r = clearance_refuse(c, "sca_step_end", clearance_check(CLR_UPDATE, clearance_state(c), c->near_valid ? 1 : 0, c->nbr_mode == SCA_NBR_GRID && !c->auto_ran ? 1 : 0, true, 0))) return r;
+    if (int r = clearance_refuse(c, "sca_step_end", clearance_check(CLR_UPDATE, clearance_state(c), c->near_valid ? 1 : 0, c->nbr_mode == SCA_NBR_GRID && !c->au.ran ? 1 : 0, true, 0))) return r;
     return launch_collide_finish(c, false);
 }
 
@@ -3478,51 +3505,23 @@ int sca_synchronize(sca_ctx *c) {
     if (c->part_on) { int h[5]; CHK(c, hipMemcpy(h, c->part.counts, sizeof(h), hipMemcpyDeviceToHost)); if (int r = part_report(c, h[4])) return r; }
     if (c->perm_on_device) { if (int r = check_kd_overflow(c)) return r; }
     if (c->profiling && c->pool_used >= 4) {
-        double a = 0, b = 0;
-        const int steps = c->pool_used / 4;
-        for (int s = 0; s < steps; s++) {
-            float t0 = 0, t1 = 0;
-            CHK(c, hipEventElapsedTime(&t0, c->pool[4 * s], c->pool[4 * s + 1]));          // K1, on the stream it ran on
-            CHK(c, hipEventElapsedTime(&t1, c->pool[4 * s + 2], c->pool[4 * s + 3]));      // k_solve (+ k_lp)
-            a += t0; b += t1;
-        }
-        c->ms_nbr = (float)(a / steps); c->ms_solve = (float)(b / steps);
+        if (int r = pool_mean_ms(c, c->pool, c->pool_used, 4, 0, &c->ms_nbr)) return r;        // K1, on the stream it ran on
+        if (int r = pool_mean_ms(c, c->pool, c->pool_used, 4, 2, &c->ms_solve)) return r;      // k_solve (+ k_lp)
         c->pool_used = 0;
     }
     if (c->profiling && c->pool_kd_used >= 2) {
-        if (c->kd_stream) CHK(c, hipStreamSynchronize(c->kd_stream));
+        if (c->au.stream) CHK(c, hipStreamSynchronize(c->au.stream));
         if (c->trk_stream) CHK(c, hipStreamSynchronize(c->trk_stream));
-        double a = 0;
-        const int builds = c->pool_kd_used / 2;
-        for (int s = 0; s < builds; s++) {
-            float t = 0;
-            CHK(c, hipEventElapsedTime(&t, c->pool_kd[2 * s], c->pool_kd[2 * s + 1]));
-            a += t;
-        }
-        c->ms_kd_build = (float)(a / builds);
+        if (int r = pool_mean_ms(c, c->pool_kd, c->pool_kd_used, 2, 0, &c->ms_kd_build)) return r;
         c->pool_kd_used = 0;
     }
     if (c->profiling && c->pool_xch_used >= 2) {
-        double a = 0;
-        const int steps = c->pool_xch_used / 2;
-        for (int s = 0; s < steps; s++) {
-            float t = 0;
-            CHK(c, hipEventElapsedTime(&t, c->pool_xch[2 * s], c->pool_xch[2 * s + 1]));
-            a += t;
-        }
-        c->ms_exchange = (float)(a / steps);
+        if (int r = pool_mean_ms(c, c->pool_xch, c->pool_xch_used, 2, 0, &c->ms_exchange)) return r;
         c->pool_xch_used = 0;
     }
     if (c->profiling && c->pool_trk_used >= 2) {
         if (c->trk_stream) CHK(c, hipStreamSynchronize(c->trk_stream));
-        double a = 0;
-        const int steps = c->pool_trk_used / 2;
-        for (int s = 0; s < steps; s++) {
-            float t = 0;
-            CHK(c, hipEventElapsedTime(&t, c->pool_trk[2 * s], c->pool_trk[2 * s + 1]));
-            a += t;
-        }
-        c->ms_replan = (float)(a / steps);
+        if (int r = pool_mean_ms(c, c->pool_trk, c->pool_trk_used, 2, 0, &c->ms_replan)) return r;
         c->pool_trk_used = 0;
     }
     return 0;
@@ -3531,10 +3530,7 @@ int sca_synchronize(sca_ctx *c) {
 int sca_set_profiling(sca_ctx *c, int on) {
     API_ENTER(c);
     c->profiling = on != 0;
-    c->pool_used = 0;
-    c->pool_trk_used = 0;
-    c->pool_xch_used = 0;
-    c->pool_kd_used = 0;
+    c->pool_used = c->pool_trk_used = c->pool_xch_used = c->pool_kd_used = 0;
     c->prof_tick = 0;
     return 0;
 }
@@ -3962,7 +3958,7 @@ int sca_respawn_agents(sca_ctx *c, int count, const int32_t *ids, const double *
         }
     }
     c->h_pos_valid = false; c->near_valid = false;
-    c->kd_single_hint = 0; c->kd_gen++;                                // positions replaced from outside: the level statistics of older trees do not apply (a sizing hint, no value)
+    positions_replaced(c);                                             // (a sizing hint, no value; the form heuristics, the AUTO passes' counts among them, are left alone)
     return 0;
 }
 int sca_get_finished(sca_ctx *c, sca_finished_row *rows, int capacity, int *count, int32_t struct_bytes) {
@@ -4116,7 +4112,7 @@ int sca_set_shard(sca_ctx *c, int begin, int count) {
     if (c->scenes.on && (begin != 0 || count != c->n)) { c->err = "sca_set_shard with scenes set (sca_set_scenes): scenes are stepped by one rank, whole"; return SCA_ERR_UNSUPPORTED; }
     if (int r = clearance_refuse(c, "sca_set_shard", clearance_check(CLR_SET_SHARD, clearance_state(c), count, 0, true, 0))) return r;
     c->d.shard_begin = begin; c->d.shard_count = count;
-    c->kd_ahead = false; c->kdq_last = -1; c->auto_backoff = 0;           // another shard: the AUTO passes' counts described the old one
+    c->au.forget();                                                       // another shard: the AUTO passes' counts described the old one
     return 0;
 }
 int sca_public_records(sca_ctx *c, int which, void **device_ptr, int64_t *bytes_per_agent) {

@@ -92,7 +92,7 @@ struct KdScratch {
 // "nobody" (sca_forms.h: auto_tail_max = 0); a list that appears is answered here by this one workgroup for the few passes until the
 // host has seen its length, then by the launch form with its 64 .. 1024 workgroups.
 struct KdTail {
-    unsigned seq;             // the pass this build belongs to (sca_ctx::auto_seq of its grid query); 0: publish nothing
+    unsigned seq;             // the pass this build belongs to (sca_ctx::Auto::seq of its grid query); 0: publish nothing
     unsigned *sync;           // [0] k_kd_block's ticket, [1] the last pass whose tree is complete, [2] the grid query's ticket
 };
 
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256) void k_kd_gather(DeviceView d, KdScratch s, Pa
         const int id = d.aperm[p];
         // the three position fields and nothing else of the record: a build beside a pass (aux, SCA_NBR_AUTO's build-ahead in
         // sca_run_steps) runs while k_collide_finish / k_goal_flags_others / the next k_action write `.flags` (and the velocity) of the same
-        // records on the main stream -- the positions are final by then (ev_auto_moved), the rest is not this kernel's to look at
+        // records on the main stream -- the positions are final by then (Auto::ev_moved), the rest is not this kernel's to look at
         static_assert(offsetof(PubRec, px) == 0 && offsetof(PubRec, py) == 8 && offsetof(PubRec, pz) == 16, "PubRec starts with the position");
         const double *rp = &d.rec[id].px;
         const double rx = rp[0], ry = rp[1], rz = rp[2];

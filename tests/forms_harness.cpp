@@ -48,6 +48,19 @@ int forms_auto_tail_form(int tail_ok, int waitvalue, unsigned seq, int kdq_last,
     return auto_tail_form(tail_ok, waitvalue, seq, kdq_last, auto_tail_max);
 }
 
+// out: seq, tail, record_slot, wait_slot, gather_slot (a slot that is none: -1)
+void forms_plan_auto_build(int tail_ok, int waitvalue, unsigned auto_seq, int kdq_last, int auto_tail_max, unsigned on_kd, unsigned builds, long long *out5) {
+    const AutoBuildPlan b = plan_auto_build(tail_ok, waitvalue, auto_seq, kdq_last, auto_tail_max, on_kd, builds);
+    const long long v[5] = {b.seq, b.tail, b.record_slot, b.wait_slot, b.gather_slot};
+    std::memcpy(out5, v, sizeof(v));
+}
+// out: seq, parity, reuse_slot, tail, kdq_slot, on_kd_stream, on_kd, copy_count, passes, wait, gather_slot
+void forms_plan_auto_pass(unsigned auto_seq, unsigned tail_seq, unsigned on_kd, int waitvalue, int count_pending, unsigned passes, unsigned builds, long long *out11) {
+    const AutoPassPlan p = plan_auto_pass(auto_seq, tail_seq, on_kd, waitvalue, count_pending, passes, builds);
+    const long long v[11] = {p.seq, p.parity, p.reuse_slot, p.tail, p.kdq_slot, p.on_kd_stream, p.on_kd, p.copy_count, p.passes, p.wait, p.gather_slot};
+    std::memcpy(out11, v, sizeof(v));
+}
+
 int forms_choose_solve_split(const int *tun, int simds, int overlap, int cnt, int trk_last_count) {
     return choose_solve_split(tun_of(tun), simds, overlap, cnt, trk_last_count);
 }
@@ -75,3 +88,42 @@ void forms_plan_kd_build(const int *tun, int n, int beside, int single_hint, int
 }
 
 }  // extern "C"
+
+#ifdef FORMS_MAIN
+// The harness as a program of its own (tests/test_forms_cpu.py builds it with -fsanitize=address,undefined): every entry point above into
+// heap arrays of exactly the length it documents, the two AUTO plans over every slot state on both sides of the wrap of `seq`.
+#include <cstdio>
+#include <memory>
+int main() {
+    std::unique_ptr<int[]> tun(new int[NTUN]), k7(new int[7]), o4(new int[4]), o7(new int[7]), o9(new int[9]), o29(new int[29]);
+    std::unique_ptr<long long[]> b5(new long long[5]), p11(new long long[11]);
+    forms_tunables_from_env(1024, tun.get());
+    forms_tunables_tracker_again(512, tun.get());
+    forms_tunables_from_env(1024, tun.get());
+    forms_constants(k7.get());
+    long long sum = forms_tunable_count() + (forms_tunable_name(NTUN - 1) != nullptr) + k7[6];
+    for (int last : {-1, 0, 126, 1 << 30}) {
+        forms_plan_auto(1, 0, last & 1, last, 8, last == 0 ? 3 : 0, 1000, o4.get());
+        sum += o4[0] + o4[3] + forms_auto_next(1, 0, 0, last, 8, 0, 1000) + forms_auto_tail_form(1, 1, 7u, last, 0);
+    }
+    for (unsigned at : {0u, 0xFFFFFFF0u})
+        for (unsigned i = 0; i < 32; i++)
+            for (unsigned on_kd = 0; on_kd < 16; on_kd++)
+                for (int form = 0; form < 4; form++) {       // kdq_last -1 / 0, the wait-value form on / off
+                    const unsigned seq = at + i;
+                    forms_plan_auto_build(1, form & 2, seq, (form & 1) - 1, 0, on_kd, i, b5.get());
+                    forms_plan_auto_pass(seq, b5[1] ? (unsigned)b5[0] : seq - 1u, on_kd, form & 2, i & 1, i, i + 1, p11.get());
+                    if (p11[4] != (long long)((seq + 1u) & 3u) || p11[6] < 0 || p11[6] > 15 || b5[3] > 3 || p11[2] > 3) { std::printf("forms_harness: a slot out of range\n"); return 1; }
+                    sum += b5[2] + b5[3] + b5[4] + p11[1] + p11[2] + p11[8] + p11[9] + p11[10];
+                }
+    for (int cnt : {1, 2048, 30000, 100000, 2000000}) {
+        sum += forms_choose_solve_split(tun.get(), 1024, 1, cnt, cnt / 2);
+        forms_plan_solve(tun.get(), 1024, cnt, 0, 1, cnt / 3, cnt / 3, cnt & 1, -1, 0, o7.get());
+        forms_plan_replans(tun.get(), cnt, -1, 0, 1, 0, o29.get());
+        forms_plan_kd_build(tun.get(), cnt, 0, 0, 1 << 30, 1 << 30, o9.get());
+        sum += o7[6] + o29[3] + o9[8];
+    }
+    std::printf("forms_harness: ok (%lld)\n", sum);
+    return 0;
+}
+#endif

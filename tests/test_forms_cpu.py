@@ -272,6 +272,170 @@ def test_plan_auto(H):
     assert [tail(last=k, mx=8) for k in (-1, 0, 8, 9)] == [0, 1, 1, 0]
 
 
+# ---- SCA_NBR_AUTO: the slot rule -------------------------------------------------------------------------------------------------------------------
+# From the comments of sca_ctx::Auto: pass `seq` fills and reads the list of parity seq & 1; event slot [seq & 3] of ev_kdq is recorded behind
+# its kd query (a launch on the kd stream) or, in the launch-free (tail) form, behind its build's last kernel; the pass two on reuses the list
+# and waits for slot [(seq - 2) & 3] if that query was a launch on the kd stream (bit [seq & 3] of on_kd); the gather kernels of the last two
+# builds alternate between the two slots of ev_gather, and the integrate stage waits for the build before the last.
+NONE = -1
+WAIT_NONE, WAIT_VALUE, WAIT_EVENT = 0, 1, 2
+U32 = 1 << 32
+
+
+def abuild(H, auto_seq, on_kd=0, builds=0, last=-1, tail_ok=1, wv=1, tail_max=0):
+    out = (C.c_longlong * 5)()
+    H.forms_plan_auto_build(tail_ok, wv, C.c_uint(auto_seq % U32), last, tail_max, C.c_uint(on_kd), C.c_uint(builds), out)
+    return dict(zip(('seq', 'tail', 'record', 'wait', 'gather'), out))
+
+
+def apass(H, auto_seq, tail_seq=0, on_kd=0, wv=1, pending=0, passes=0, builds=0):
+    out = (C.c_longlong * 11)()
+    H.forms_plan_auto_pass(C.c_uint(auto_seq % U32), C.c_uint(tail_seq % U32), C.c_uint(on_kd), wv, pending, C.c_uint(passes), C.c_uint(builds), out)
+    return dict(zip(('seq', 'parity', 'reuse', 'tail', 'slot', 'on_kd_stream', 'on_kd', 'copy', 'passes', 'wait', 'gather'), out))
+
+
+def test_auto_slots_first_five_passes_in_the_launch_form(H):
+    """no list length has come back (last = -1): every build without a tail, every kd query a launch on the kd stream"""
+    for k in (1, 2, 3, 4, 5):
+        assert abuild(H, k - 1, on_kd=0b1111, builds=k - 1) == dict(seq=k, tail=0, record=NONE, wait=NONE, gather=(k - 1) & 1), k
+    on_kd_before = {1: 0b0000, 2: 0b0010, 3: 0b0110, 4: 0b1110, 5: 0b1111}
+    want = {1: dict(parity=1, reuse=NONE, slot=1, on_kd=0b0010, gather=1), 2: dict(parity=0, reuse=NONE, slot=2, on_kd=0b0110, gather=0),
+            3: dict(parity=1, reuse=1, slot=3, on_kd=0b1110, gather=1), 4: dict(parity=0, reuse=2, slot=0, on_kd=0b1111, gather=0),
+            5: dict(parity=1, reuse=3, slot=1, on_kd=0b1111, gather=1)}
+    for k, w in want.items():
+        got = apass(H, k - 1, on_kd=on_kd_before[k], builds=k, passes=k - 1, pending=1)
+        assert got == dict(w, seq=k, tail=0, on_kd_stream=1, copy=0, passes=k - 1, wait=WAIT_VALUE), k
+
+
+def test_auto_slots_first_five_passes_in_the_tail_form(H):
+    """lengths of 0 have come back: every build records its pass's slot behind its last kernel, no pass launches a kd query or waits"""
+    for k in (1, 2, 3, 4, 5):
+        assert abuild(H, k - 1, builds=k - 1, last=0) == dict(seq=k, tail=1, record=k & 3, wait=NONE, gather=(k - 1) & 1), k
+        assert apass(H, k - 1, tail_seq=k, builds=k, passes=1, pending=1) == dict(
+            seq=k, parity=k & 1, reuse=NONE, tail=1, slot=k & 3, on_kd_stream=0, on_kd=0, copy=0, passes=1, wait=WAIT_NONE, gather=k & 1), k
+    assert abuild(H, 4, last=0, tail_ok=0)['tail'] == 0 and abuild(H, 4, last=0, wv=0)['tail'] == 0 and abuild(H, 4, last=1)['tail'] == 0
+    assert abuild(H, 4, last=1, tail_max=1)['tail'] == 1
+
+
+def test_auto_slots_where_the_two_forms_meet(H):
+    # pass 3 a launch (bit 3), pass 5 in the tail form: the wait for slot 3 is due, at the build; the pass itself does not wait again
+    assert abuild(H, 4, on_kd=0b1000, builds=4, last=0) == dict(seq=5, tail=1, record=1, wait=3, gather=0)
+    got = apass(H, 4, tail_seq=5, on_kd=0b1010, builds=5)
+    assert (got['reuse'], got['tail'], got['on_kd_stream'], got['on_kd'], got['wait']) == (NONE, 1, 0, 0b1000, WAIT_NONE)
+    # ... also when that build was enqueued ahead: nothing but tail_seq tells the pass
+    assert apass(H, 4, tail_seq=0, on_kd=0b1000, builds=5)['reuse'] == 3 and apass(H, 4, tail_seq=5, on_kd=0b1000, builds=5)['reuse'] == NONE
+    # pass 3 in the tail form (it ran inside the pass's own grid query), pass 5 a launch: no wait
+    got = apass(H, 4, tail_seq=3, on_kd=0b0101, builds=5)
+    assert (got['reuse'], got['tail'], got['slot'], got['on_kd_stream'], got['on_kd']) == (NONE, 0, 1, 1, 0b0111)
+    assert abuild(H, 4, on_kd=0b0111, last=0)['wait'] == NONE
+    # a tail form's stale tail_seq is no tail pass
+    assert apass(H, 6, tail_seq=5)['tail'] == 0 and apass(H, 6, tail_seq=7)['tail'] == 1
+
+
+def test_auto_count_copy_every_fourth_pass_and_never_while_one_is_pending(H):
+    got = [(apass(H, 7, passes=k)['copy'], apass(H, 7, passes=k)['passes']) for k in range(10)]
+    assert got == [(1, 1), (0, 2), (0, 3), (0, 4), (1, 5), (0, 6), (0, 7), (0, 8), (1, 9), (0, 10)]
+    assert [(apass(H, 7, passes=k, pending=1)['copy'], apass(H, 7, passes=k, pending=1)['passes']) for k in (0, 4, 8)] == [(0, 0), (0, 4), (0, 8)]
+
+
+def test_auto_wait_forms(H):
+    assert apass(H, 7, tail_seq=8, wv=1)['wait'] == WAIT_NONE
+    assert apass(H, 7, tail_seq=0, wv=1)['wait'] == WAIT_VALUE
+    assert apass(H, 7, tail_seq=0, wv=0)['wait'] == WAIT_EVENT
+
+
+def test_auto_slots_around_the_wrap_of_seq(H):
+    """seq = 2^32 - 2 .. 2 with every earlier kd query a launch: what the guards give there today (a pass numbered 0 never takes the tail form
+    and reads tail_seq = 0 as "this pass's build made the stream wait"; passes 1 and 2 skip the reuse wait like a context's first two)"""
+    seqs = (U32 - 2, U32 - 1, 0, 1, 2)
+    assert [(b['seq'], b['tail'], b['record'], b['wait']) for b in (abuild(H, s - 1, on_kd=0b1111, last=0) for s in seqs)] == [
+        (U32 - 2, 1, 2, 0), (U32 - 1, 1, 3, 1), (0, 0, NONE, NONE), (1, 1, 1, NONE), (2, 1, 2, NONE)]
+    got = [apass(H, s - 1, tail_seq=U32 - 4, on_kd=0b1111) for s in seqs]
+    assert [(p['seq'], p['parity'], p['reuse'], p['tail'], p['slot']) for p in got] == [
+        (U32 - 2, 0, 0, 0, 2), (U32 - 1, 1, 1, 0, 3), (0, 0, 2, 0, 0), (1, 1, NONE, 0, 1), (2, 0, NONE, 0, 2)]
+    zero = apass(H, U32 - 1, tail_seq=0, on_kd=0b1111)
+    assert (zero['seq'], zero['tail'], zero['reuse']) == (0, 0, NONE)
+
+
+def test_auto_slot_model_no_list_refilled_and_no_record_buffer_written_under_a_reader(H):
+    """A few hundred passes, each in the tail or the launch form, its build inside the pass or ahead of it (fixed seed), on a model of the two
+    streams: the kd stream runs what it is given in order, so "the pass's stream has waited for an event" means everything the kd stream was
+    given up to that event's record is through.  The wait-value form counts as no wait at all (it returns at once when nobody is listed).
+    (i) a list is never reset and refilled before the kd query that last read it has been waited for, or ran on the pass's own stream;
+    (ii) the integrate stage never writes the record buffer that an unwaited gather still reads."""
+    import random
+    rng = random.Random(20240607)
+    kd_pos = 0                                   # operations the kd stream has been given
+    synced = 0                                   # ... of which the pass's stream has waited for this many
+    ev_kdq, ev_gather = [0] * 4, [0] * 2         # where each event was last recorded (0: never, fires at once)
+    list_reader = [None, None]                   # per list parity: the kd stream position of the query that read it last, 'own': on the pass's stream
+    buf_reader = [0, 0]                          # per record buffer: the kd stream position of the gather that read it last
+    cur = 0                                      # the record buffer that holds the current positions
+    st = dict(seq=0, tail_seq=0, on_kd=0, builds=0, passes=0, pending=0, wv=1)
+    seen = dict(tail=0, launch=0, ahead=0, reuse=0, build_wait=0)
+
+    def build(last):
+        nonlocal kd_pos, synced
+        b = abuild(H, st['seq'], on_kd=st['on_kd'], builds=st['builds'], last=last, wv=st['wv'])
+        assert b['seq'] == st['seq'] + 1
+        if b['wait'] != NONE:
+            synced = max(synced, ev_kdq[b['wait']]); seen['build_wait'] += 1
+        kd_pos += 1; ev_gather[b['gather']] = kd_pos; buf_reader[cur] = kd_pos; st['builds'] += 1       # the gather
+        kd_pos += 1                                                                                  # ... the build's last kernel
+        if b['tail']:
+            ev_kdq[b['record']] = kd_pos; st['tail_seq'] = b['seq']
+
+    ahead = False
+    for n in range(1, 401):
+        if not ahead:
+            build(rng.choice((-1, 0)))
+        p = apass(H, st['seq'], tail_seq=st['tail_seq'], on_kd=st['on_kd'], wv=st['wv'], pending=st['pending'], passes=st['passes'], builds=st['builds'])
+        assert p['seq'] == n and p['on_kd_stream'] == (not p['tail'])
+        if p['reuse'] != NONE:
+            synced = max(synced, ev_kdq[p['reuse']]); seen['reuse'] += 1
+        r = list_reader[p['parity']]             # (i): the grid build resets this list now
+        assert r is None or r == 'own' or synced >= r, (n, p, r, synced)
+        if p['tail']:
+            list_reader[p['parity']] = 'own'; seen['tail'] += 1
+        else:
+            kd_pos += 1; ev_kdq[p['slot']] = kd_pos; list_reader[p['parity']] = kd_pos; seen['launch'] += 1
+        if p['copy']:
+            st['pending'] = 1
+        elif st['pending'] and rng.random() < 0.4:
+            st['pending'] = 0                    # the copy has arrived
+        wait = p['wait']
+        if wait == WAIT_VALUE and n >= 300:
+            st['wv'], wait = 0, WAIT_EVENT       # hipStreamWaitValue32 refused: the event wait in its place, and from here on
+        if wait == WAIT_EVENT:
+            synced = max(synced, ev_kdq[p['slot']])
+        if st['wv']:                             # (the event form has waited for this pass's build with its kd query)
+            synced = max(synced, ev_gather[p['gather']])
+        g = buf_reader[1 - cur]                  # (ii): the integrate stage writes the other buffer now
+        assert synced >= g, (n, p, g, synced)
+        cur = 1 - cur
+        st.update(seq=p['seq'], on_kd=p['on_kd'], passes=p['passes'])
+        ahead = rng.random() < 0.5
+        if ahead:
+            build(rng.choice((-1, 0))); seen['ahead'] += 1
+    assert min(seen.values()) > 20, seen         # every branch of the model ran
+
+
+def test_forms_harness_standalone_under_sanitizers():
+    """the plan functions as a program of their own (FORMS_MAIN: every entry point into heap arrays of exactly the documented length, the two
+    AUTO plans over every slot state on both sides of the wrap) under -fsanitize=address,undefined.  Host code only; nothing of it is loaded
+    into python."""
+    import subprocess
+    import harness_util
+    exe = os.path.join(harness_util.BUILD, 'forms_harness_san')
+    os.makedirs(harness_util.BUILD, exist_ok=True)
+    subprocess.check_call(['g++', '-std=c++17', '-O1', '-g', '-fno-omit-frame-pointer', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-static-libasan',
+                           '-static-libubsan', '-DFORMS_MAIN', '-Wall', '-Wextra', '-Werror', '-I' + harness_util.CSRC, '-o', exe,
+                           os.path.join(harness_util.ROOT, 'tests', 'forms_harness.cpp')])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert 'forms_harness: ok' in r.stdout and 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr
+
+
 # ---- the kd build -----------------------------------------------------------------------------------------------------------------------------------
 
 def test_plan_kd_build(H, clean_env):

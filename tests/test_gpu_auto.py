@@ -182,6 +182,70 @@ def test_tail_form_answers_the_listed_agents(kind, n, burst, div, monkeypatch):
     a.close(); b.close()
 
 
+def test_every_site_that_touches_the_auto_books_keeps_auto_equal_to_kdtree(monkeypatch):
+    """Two contexts side by side, SCA_NBR_KDTREE and SCA_NBR_AUTO, through every entry point that resets or reads the AUTO pipeline's books
+    (sca_ctx::Auto: forget(), positions_replaced(), auto_abandon, the lazy join): bursts (builds ahead), sca_env_step, sca_set_state,
+    sca_set_shard, sca_step_host with the state taken from the block, sca_respawn_agents, a refused sca_run_steps.  After every item the
+    states are the same bits.  Once with the defaults, once with SCA_AUTO_TAIL_MAX raised: every reset sends the passes back to the launch
+    form until a list length has come back, so the two forms alternate."""
+    from sca_amd import scenarios, solver as S
+    keys = ('pos', 'vel', 'heading', 'flags', 'total_dist', 'step_num')
+    for tail_max in (None, 1 << 30):
+        if tail_max is not None:
+            monkeypatch.setenv('SCA_AUTO_TAIL_MAX', str(tail_max))
+            monkeypatch.setenv('SCA_AUTO_BACKOFF_DIV', '1')
+        for kind, n in (('dense', 600), ('cube', 512)):
+            sc, pol, n = _scene(kind, n, seed=7)
+            sols = ((_solver(sc, pol, n, False), S.NBR_KDTREE), (_solver(sc, pol, n, False), S.NBR_AUTO))
+            a, b = sols[0][0], sols[1][0]
+            start = a.get_state()
+            tails = 0
+
+            def same(item):
+                nonlocal tails
+                tails += bool(b.pass_forms() & S.FORM_AUTO_TAIL)
+                sa, sb = a.get_state(), b.get_state()
+                for k in keys:
+                    assert np.array_equal(sa[k], sb[k]), (kind, tail_max, item, k, int((sa[k] != sb[k]).sum()))
+
+            def burst(item):
+                for sol, mode in sols:
+                    sol.run_steps(5, mode)
+                same(item)
+
+            burst(1)
+            assert a.env_step(S.NBR_KDTREE) == b.env_step(S.NBR_AUTO); same(2)
+            for sol, _ in sols:
+                sol.set_state(*(start[k] for k in keys))
+            same(3)
+            burst(4)
+            for sol, _ in sols:
+                sol.set_shard(n // 3, n // 2); sol.set_shard(0, n)
+            same(5)
+            burst(6)
+            for sol, mode in sols:
+                st, blk = sol.get_state(), sol.host_state()
+                for k in keys:
+                    blk[k][:] = st[k]
+                sol.step_host(mode, state=True)
+            same(7)
+            ids = np.array([n - 1, 3, n // 2], np.int32)
+            for sol, _ in sols:
+                sol.respawn(ids, sc['start'][ids, :3], np.zeros((3, 3), np.float32), sc['start'][ids, 3:6], np.full(3, 0.5), np.ones(3),
+                            sc['goal'][ids, :3], scenarios.max_run_dist(sc['start'], sc['goal'])[ids])
+            same(8)
+            burst(9)
+            for sol, mode in sols:
+                with pytest.raises(S.ScaError, match='steps must not be negative'):
+                    sol.run_steps(-1, mode)
+            same(10)
+            burst(11)
+            st = b.auto_stats()
+            print(kind, 'SCA_AUTO_TAIL_MAX', tail_max, 'bursts that ended on a launch-free pass:', tails, st)
+            assert st['auto_passes'] > 0, (kind, tail_max, st)
+            a.close(); b.close()
+
+
 def test_tail_form_off_equals_on(monkeypatch):
     """SCA_AUTO_NO_TAIL=1 (the launch form on every pass) against the default on c3's own scene: the same bits, and the default takes the tail"""
     from sca_amd import solver as S
