@@ -178,6 +178,89 @@ inline AutoPassPlan plan_auto_pass(unsigned auto_seq, unsigned tail_seq, unsigne
     return p;
 }
 
+// ---- a step of a burst: the events that ride --------------------------------------------------------------------------------------------------
+// sca_run_steps knows, inside one call, what follows a step, and lets three things ride on kernels the step launches anyway (stop events
+// of their dispatches, Tunables::ext_stop) or start early.  The single-step entry points plan none of them.
+struct StepIn {
+    int mode;                   // the neighbour mode the burst was called with
+    int step, steps;            // this step of so many
+    bool kd_stream;             // sca_ctx::Auto::stream exists (the first AUTO pass of a context creates it)
+    bool ext_stop;              // Tunables::ext_stop
+    bool comm;                  // a communicator is active
+    bool whole;                 // the shard is the whole swarm
+    bool trk_on, trk_in_pass, trk_fork;   // the tracker is enabled | runs inside the pass | its fork event exists
+    bool paths_on;              // waypoint lists are set
+    bool clear_on;              // the closest-approach records of the whole context are on
+    bool auto_ran;              // the pass of this step was an AUTO pass
+    bool fits, part_on; int kdq_last, auto_div, auto_backoff, shard_count;   // auto_next's inputs (tracked_pass is trk_on && trk_in_pass)
+};
+struct StepPlan {
+    bool moved_on_action;       // k_action carries Auto::ev_moved.  None of its inputs is a result of the step's pass: asked in front of it
+    bool build_ahead;           // the next pass's kd build is enqueued behind this step's collision check ...
+    bool fork_rides;            // ... or the next pass's fork rides on this step's last kernel (plan_finish); both asked behind the pass
+};
+inline StepPlan plan_step(const StepIn &i) {
+    StepPlan p{};
+    const bool more = i.step + 1 < i.steps;
+    // (SCA_NBR_AUTO, another step to follow: the moved positions' event rides on k_action -- the next pass's kd build waits on it)
+    // (a shard: the records of the others arrive after k_action)
+    p.moved_on_action = i.mode == SCA_NBR_AUTO && more && i.kd_stream && i.ext_stop && !i.comm && i.whole;
+    // SCA_NBR_AUTO: the NEXT pass's kd build needs the moved positions only -- k_collide_finish changes flags, and in an AUTO pass its
+    // fallback looks into the grid, not into the tree -- so it starts beside the collision check and the next pass's grid build and query.
+    // Only inside one call: a caller who reads the permutation between calls sees as many builds as steps.
+    // (not with the closest-approach records on: k_clearance reads this step's tree, which a build enqueued ahead would overwrite beside it)
+    p.build_ahead = i.mode == SCA_NBR_AUTO && i.auto_ran && more && !i.clear_on &&
+                    auto_next(i.fits, i.trk_on && i.trk_in_pass, i.part_on, i.kdq_last, i.auto_div, i.auto_backoff, i.shard_count);
+    // the next pass's fork (tracker in the pass, its neighbour branch on the side stream) rides on this step's last kernel
+    // (not while waypoint lists are set: the next pass's k_waypoint must come before its fork)
+    // (a step that builds ahead took the other branch: no tracker in an AUTO pass, no fork to carry)
+    p.fork_rides = !p.build_ahead && more && i.ext_stop && i.trk_on && i.trk_in_pass && i.trk_fork && !i.paths_on;
+    return p;
+}
+// the env update's launches: which K4 instance runs, what follows it, and which of them is the step's last kernel -- the one that carries the
+// event sca_run_steps hands over (plan_step's fork), if it hands one over
+enum FinishK4 { K4_SCENE_OBS, K4_SCENES, K4_GRID, K4_PLAIN };              // k_collide_finish_scenes<SceneObsRoots | SceneRoots>, _grid, k_collide_finish
+enum FinishCarrier { CARRY_K4, CARRY_HARVEST, CARRY_OTHERS };             // K4 | k_scene_harvest | k_goal_flags_others
+struct FinishPlan { int k4, carrier; bool harvest, others; };
+// harvest_on: the harvest block exists; last_mode: the neighbour structure of the last pass (sca_ctx::nbr_mode: K4's fallback looks there)
+inline FinishPlan plan_finish(bool scenes_on, bool obs_on, bool harvest_on, bool part_on, bool shard_below_n, int last_mode) {
+    FinishPlan p{};
+    p.k4 = scenes_on ? (obs_on ? K4_SCENE_OBS : K4_SCENES) : last_mode == SCA_NBR_GRID ? K4_GRID : K4_PLAIN;
+    p.others = part_on || shard_below_n;            // k_goal_flags_others behind K4 (and behind the harvest)
+    p.harvest = scenes_on && harvest_on;            // (with the harvest the step's last kernel is k_scene_harvest, and the event rides on that one)
+    p.carrier = p.others ? CARRY_OTHERS : p.harvest ? CARRY_HARVEST : CARRY_K4;
+    return p;
+}
+
+// ---- the refusals of the entry points that step --------------------------------------------------------------------------------------------
+// One list, in the order sca_run_steps makes them; an entry point names the checks it makes (sca_step_begin: no step count, and a mode out
+// of range is the pass's to refuse; sca_step_host: the mode alone, under its own name) and its prefix.
+enum StepCheck { STEP_CHK_STATE = 1, STEP_CHK_STEPS = 2, STEP_CHK_MODE = 4, STEP_CHK_RANKS = 8, STEP_CHK_PART_MODE = 16, STEP_CHK_ALL = 31 };
+enum StepFault { STEPF_OK, STEPF_NO_STATE, STEPF_NEGATIVE_STEPS, STEPF_MODE, STEPF_PART_RANKS, STEPF_PART_MODE };
+// part_ranks_apart: the partition spans several ranks and shard emulation is off
+inline StepFault step_check(int checks, bool state_set, int steps, int mode, bool part_on, bool part_ranks_apart) {
+    if ((checks & STEP_CHK_STATE) && !state_set) return STEPF_NO_STATE;
+    if ((checks & STEP_CHK_STEPS) && steps < 0) return STEPF_NEGATIVE_STEPS;
+    if ((checks & STEP_CHK_MODE) && (mode < SCA_NBR_KDTREE || mode > SCA_NBR_AUTO)) return STEPF_MODE;   // (also for steps == 0: a wrong mode is a wrong call)
+    if ((checks & STEP_CHK_RANKS) && part_on && part_ranks_apart) return STEPF_PART_RANKS;
+    if ((checks & STEP_CHK_PART_MODE) && part_on && mode != SCA_NBR_GRID) return STEPF_PART_MODE;
+    return STEPF_OK;
+}
+inline const char *step_fault_text(StepFault f) {
+    switch (f) {
+    case STEPF_NO_STATE: return "sca_set_state first";
+    case STEPF_NEGATIVE_STEPS: return "steps must not be negative";
+    case STEPF_MODE: return "neighbor mode not available in this build";
+    case STEPF_PART_RANKS: return "cell-owner partition over several ranks: drive the step with sca_step_begin / sca_partition_pack / [exchange] / "
+                                  "sca_partition_unpack / sca_partition_commit / sca_step_end (sca_amd.distributed.PartitionedStepper)";
+    case STEPF_PART_MODE: return "the cell-owner partition is a mode of SCA_NBR_GRID";
+    default: return "";
+    }
+}
+inline int step_fault_code(StepFault f) {
+    return f == STEPF_OK ? 0 : f == STEPF_NEGATIVE_STEPS ? SCA_ERR_ARG : f == STEPF_MODE || f == STEPF_PART_MODE ? SCA_ERR_UNSUPPORTED : SCA_ERR_STATE;
+}
+
 // ---- the solve and its neighbours ------------------------------------------------------------------------------------------------------------
 // K3 form: one lane per agent (k_lp) once the shard has enough LP agents to fill the chip that way -- measured: 100 000 agents 65 vs 106 us,
 // 4096 agents 23 vs 12 us (a lane alone needs ~12 us for its 16 planes and the LP) --, else the wave-per-agent form (k_solve_lpw).

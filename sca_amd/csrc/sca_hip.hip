@@ -293,9 +293,6 @@ struct sca_ctx {
             *this = Auto{};
         }
     } au;
-    hipEvent_t action_stop = nullptr;   // sca_run_steps: the event to record behind this pass's k_action (the moved positions), if any
-    hipEvent_t finish_stop = nullptr;   // sca_run_steps: the event to record behind the step's last kernel (the next pass's fork), if any
-    bool fork_ready = false;            // ... it was: the pass that follows at once does not record its fork
     unsigned prof_tick = 0;             // with profiling on, every 16th pass carries the event pairs (six records, ~35 us on that pass)
     // multi-GPU exchange inside the library (sca_comm_init): one ncclAllGather of the shard's moved records per step
     ncclComm_t comm = nullptr;
@@ -399,6 +396,12 @@ static int dalloc(sca_ctx *c, T **p, size_t count) {
 }
 // positions replaced from outside (sca_set_state ...): the level statistics of older trees do not apply
 static void positions_replaced(sca_ctx *c) { c->kd_single_hint = 0; c->kd_gen++; }
+// a whole state arrived from outside (sca_set_state, sca_step_host with SCA_HOST_IN_STATE).  h_pos_valid is the caller's: only sca_set_state keeps a host mirror
+static void state_replaced(sca_ctx *c) {
+    positions_replaced(c);                // a new state: the previous trees' depth profile says nothing
+    c->au.forget();                       // ... and neither do the AUTO passes' counts (no tree is built ahead across calls: sca_run_steps consumes its own or abandons it)
+    c->near_valid = false; c->state_set = true; c->state_fresh = true; c->scenes.live_valid = false; c->scenes.begun = false;
+}
 // the next event of a profiling pool that grows on demand, up to `cap` in use (beyond it: *e stays as it is)
 static int pool_take(sca_ctx *c, std::vector<hipEvent_t> &pool, int &used, int cap, hipEvent_t *e) {
     if (used >= cap) return 0;
@@ -1201,17 +1204,13 @@ int sca_set_state(sca_ctx *c, const double *pos, const float *vel, const double 
         r.flags = flags[i];
     }
     c->h_pos.assign(pos, pos + 3 * (size_t)n);
-    positions_replaced(c);                // a new state: the previous trees' depth profile says nothing
-    c->au.forget();                       // ... and neither do the AUTO passes' counts (no tree is built ahead across calls: sca_run_steps consumes its own or abandons it)
     c->h_pos_valid = true;
-    c->near_valid = false;
     CHK(c, hipMemcpyAsync(c->d.rec, c->h_rec.data(), sizeof(PubRec) * n, hipMemcpyHostToDevice, c->stream));
     CHK(c, hipMemcpyAsync(c->d.heading, heading, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
     if (total_dist) CHK(c, hipMemcpyAsync(c->d.total_dist, total_dist, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
     if (step_num) CHK(c, hipMemcpyAsync(c->d.step_num, step_num, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
     CHK(c, hipStreamSynchronize(c->stream));
-    c->state_set = true; c->state_fresh = true;
-    c->scenes.live_valid = false; c->scenes.begun = false;
+    state_replaced(c);
     scene_harvest_clear_fresh(c, 0, nullptr);                             // (a state from outside: nothing that finished before it is reported after it)
     if (c->part_on) return part_classify(c);                              // a complete state again: ownership follows from it
     return 0;
@@ -1592,7 +1591,7 @@ int sca_set_scenes(sca_ctx *c, int nscenes, const int32_t *offsets) {
     for (int i = 0; i < n; i++) c->h_perm[i] = i;                     // every scene's kdTree.agentIDs starts as 0 .. n_s - 1 (kdTree.py:43-45)
     c->perm_on_device = false;
     c->scenes.live_valid = false; c->scenes.begun = false;
-    positions_replaced(c); c->au.forget(); c->near_valid = false;
+    positions_replaced(c); c->au.forget(); c->near_valid = false;      // (not state_replaced: no state arrived, state_set and state_fresh stay as they are)
     c->nbr_mode = SCA_NBR_KDTREE;
     c->scenes.on = true;
     return 0;
@@ -2550,17 +2549,24 @@ static int auto_join(sca_ctx *c) {
     return 0;
 }
 
+// the refusals of the entry points that step (step_check, sca_forms.h): `checks` names the ones this caller makes, `who` is its prefix
+static int step_refuse(sca_ctx *c, const char *who, int checks, int steps, int mode) {
+    const StepFault f = step_check(checks, c->state_set, steps, mode, c->part_on, c->part_nranks > 1 && !c->shard_emulation);
+    if (f != STEPF_OK) c->err = std::string(who) + step_fault_text(f);
+    return step_fault_code(f);
+}
 // ---- a policy pass: what its stages share, then the stages in the order launch_policy runs them ---------------------------------------------------
 struct PassPlan {
     bool timed = false, fuse_integrate = false;   // launch_policy's arguments
-    int mode = 0;                       // the neighbour mode as resolved: SCA_NBR_AUTO has become SCA_NBR_KDTREE where it is a plain kd pass
+    hipEvent_t action_stop = nullptr;   // ... PassRide: the event to record behind k_action (the moved positions), if any
+    bool fork_ready = false;            // ... PassRide: the fork rode on the previous step's last kernel
+    int mode = 0;                      // the neighbour mode as resolved: SCA_NBR_AUTO has become SCA_NBR_KDTREE where it is a plain kd pass
     bool auto_mode = false;             // an AUTO pass
     bool kd_prebuilt = false;           // ... whose tree sca_run_steps has enqueued ahead
     AutoPassPlan A{};                   // ... and its slots (sca_forms.h), planned behind its build; A.tail: the grid query's last workgroup answers the listed agents
     int kdq_blocks = KDQ_BLOCKS;
     bool tracked = false;               // the tracker runs inside the pass
     bool overlap = false;               // ... and the neighbour branch beside its re-plans, on trk_stream
-    bool fork_ready = false;            // the fork rode on the previous step's last kernel (sca_run_steps)
     unsigned parity_now = 0;            // TrackDev::parity in front of the tracker's launches
     int lp_lo = 0, lp_hi = 0;           // the shard's LP agents: [lp_lo, lp_hi) of lp_ids (under the partition ownership is dynamic: the LP
     const int32_t *lp_ids = nullptr;    // kernels walk all owned agents and skip the others)
@@ -2576,8 +2582,6 @@ struct PassPlan {
 // the refusals, the SCA_NBR_AUTO decision, the LP range and the solve's forms; nothing is launched (a pass that is not an AUTO pass joins the kd stream)
 static int pass_resolve(sca_ctx *c, int mode, PassPlan &p) {
     if (int r = clearance_refuse(c, "a policy pass", clearance_check(CLR_PASS, clearance_state(c), mode, 0, true, 0))) return r;
-    p.fork_ready = c->fork_ready;
-    c->fork_ready = false;
 #ifdef SCA_TIMELINE
     c->d.tl_step++;
 #endif
@@ -2595,7 +2599,7 @@ static int pass_resolve(sca_ctx *c, int mode, PassPlan &p) {
     if (mode == SCA_NBR_AUTO) {
         // (scenes: the grid's cell key carries no scene id -- one more place where it cannot help)
         const bool fits = !c->scenes.on && c->max_radius + ar <= c->P.neighbor_dist && c->max_radius + orr <= c->P.neighbor_dist;
-        if (c->part_on) { c->err = "the cell-owner partition is a mode of SCA_NBR_GRID"; return SCA_ERR_UNSUPPORTED; }
+        if (int r = step_refuse(c, "", STEP_CHK_PART_MODE, 0, mode)) return r;
         if (int r = A.fill(c)) return r;
         if (A.count_pending && hipEventQuery(A.ev_cnt) == hipSuccess) { A.last = A.count_host[0]; A.count_pending = false; }   // poll
         // (sca_run_steps only builds ahead when auto_next() holds)
@@ -2834,7 +2838,7 @@ static int pass_epilogue(sca_ctx *c, const PassPlan &p) {
         c->au.unjoined = true;                                          // (ii) see auto_join
     }
     // (small shards: the fallback sweep rides in the epilogue's launch -- k_action_fb -- instead of in front of it)
-    const hipEvent_t action_stop = p.fuse_integrate ? c->action_stop : nullptr;
+    const hipEvent_t action_stop = p.fuse_integrate ? p.action_stop : nullptr;
     if (p.S.action_fb) {
         const auto k = p.fuse_integrate ? k_action_fb<true> : k_action_fb<false>;
         LAUNCH_OPT(c, action_stop, k, dim3(ablocks + FB_BLOCKS_SMALL), dim3(SOLVE_WAVES * 64), c->stream, d, c->P, ablocks);
@@ -2849,8 +2853,9 @@ static int pass_epilogue(sca_ctx *c, const PassPlan &p) {
     if (p.fuse_integrate && c->d.hist) c->d.hist_row++;
     return 0;
 }
-static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) {
-    PassPlan p{timed, fuse_integrate};
+struct PassRide { hipEvent_t action_stop = nullptr; bool fork_ready = false; };   // what a step of a burst hands to its pass (plan_step); every other caller hands over nothing
+static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate, const PassRide &ride) {
+    PassPlan p{timed, fuse_integrate, ride.action_stop, ride.fork_ready};
     if (int r = pass_resolve(c, mode, p)) return r;
     if (int r = pass_fork(c, p)) return r;
     if (p.tracked) { int f = 0; if (int r = launch_tracker(c, true, true, f)) return r; p.forms |= f; }
@@ -2862,20 +2867,15 @@ static int launch_policy(sca_ctx *c, int mode, bool timed, bool fuse_integrate) 
 }
 
 static int launch_integrate(sca_ctx *c) {
-    const DeviceView &d = c->d;
-    const int cnt = d.shard_count;
-    hipLaunchKernelGGL(k_integrate, dim3((cnt + 255) / 256), dim3(256), 0, c->stream, d, c->P);
+    hipLaunchKernelGGL(k_integrate, dim3((c->d.shard_count + 255) / 256), dim3(256), 0, c->stream, c->d, c->P);
     CHK(c, hipGetLastError());
     if (c->d.hist) c->d.hist_row++;
     return 0;
 }
-// check_agent_state + is_done; afterwards the moved records become the current ones (buffer swap, no copy)
-static int launch_collide_finish(sca_ctx *c, bool timed) {
+// ---- the env update (check_agent_state + is_done): its stages in the order launch_collide_finish runs them ---------------------------------------
+// no policy pass before: the counters, the candidate lists, the grid and the scenes' step are the update's own to prepare
+static int finish_prepare(sca_ctx *c) {
     DeviceView &d = c->d;
-    const int cnt = d.shard_count;
-    const bool passed = c->scenes.on && c->scenes.begun;                   // a policy pass opened this step: coll_new describes it (k_scene_clearance)
-    double agent_reach, obs_reach;
-    collide_reach(c, agent_reach, obs_reach);
     if (!c->near_valid) CHK(c, hipMemsetAsync(d.done_count, 0, sizeof(int32_t) * 256 * 32, c->stream));   // no policy pass before
     if (!c->near_valid) hipLaunchKernelGGL(k_invalidate_near, dim3((d.n + 255) / 256), dim3(256), 0, c->stream, d);
     if (!c->near_valid && c->nbr_mode == SCA_NBR_GRID) {                  // the fallback reads the grid: make it describe these records
@@ -2888,6 +2888,12 @@ static int launch_collide_finish(sca_ctx *c, bool timed) {
         hipLaunchKernelGGL(k_scene_begin, dim3((c->scenes.v.nscenes + 255) / 256), dim3(256), 0, c->stream, c->scenes.v);
     }
     c->near_valid = false;
+    return 0;
+}
+// what watches the step: a scene's log and closest approach, then the closest approach over the whole context
+static int finish_observers(sca_ctx *c) {
+    const DeviceView &d = c->d;
+    const bool passed = c->scenes.on && c->scenes.begun;                   // a policy pass opened this step: coll_new describes it (k_scene_clearance)
     if (c->scenes.on && c->scenes.log.rows)                                // the scene log's row of this step: behind k_scene_begin, in front of the step's last kernel
         hipLaunchKernelGGL(k_scene_log, dim3((unsigned)((4 * (int64_t)d.n + SCENE_LOG_T - 1) / SCENE_LOG_T)), dim3(SCENE_LOG_T), 0, c->stream, d, c->scenes.v, c->scenes.log);
     if (c->scenes.on && c->scenes.clear) {                                 // the closest approach of this step: beside the log's row, on the same records
@@ -2896,80 +2902,69 @@ static int launch_collide_finish(sca_ctx *c, bool timed) {
                            (const int32_t *)c->scenes.size, c->scenes.clear, c->scenes.obs_on ? c->scenes.ov.oroot : (const int32_t *)nullptr, c->scenes.obs_on ? 0 : d.m,
                            c->scenes.largest, passed ? (const uint32_t *)d.coll_new : (const uint32_t *)nullptr);
     }
-    if (c->clear) {                                                        // the closest approach of this step over the whole context: a wavefront per agent
-        // The agent tree of this step.  A kd pass built it on the pass's own streams, joined into this one in front of the solve -- the order
-        // K4's traversal relies on.  An AUTO pass built it on the kd stream, which nothing of the step waits for (K4 looks into the grid there):
-        // this stream waits for that build here.
-        if (c->au.ran) { if (int r = auto_join(c)) return r; }
-        double car, cor;
-        clearance_reach(c, car, cor);
-        hipLaunchKernelGGL(k_clearance, dim3((unsigned)((d.n + CLR_WAVES - 1) / CLR_WAVES)), dim3(CLR_WAVES * 64), 0, c->stream, d, c->clear, car, cor, ++c->clear_step);
+    if (!c->clear) return 0;                                               // the closest approach of this step over the whole context: a wavefront per agent
+    // The agent tree of this step.  A kd pass built it on the pass's own streams, joined into this one in front of the solve -- the order
+    // K4's traversal relies on.  An AUTO pass built it on the kd stream, which nothing of the step waits for (K4 looks into the grid there):
+    // this stream waits for that build here.
+    if (c->au.ran) { if (int r = auto_join(c)) return r; }
+    double car, cor; clearance_reach(c, car, cor);
+    hipLaunchKernelGGL(k_clearance, dim3((unsigned)((d.n + CLR_WAVES - 1) / CLR_WAVES)), dim3(CLR_WAVES * 64), 0, c->stream, d, c->clear, car, cor, ++c->clear_step);
+    return 0;
+}
+// K4 in the instance plan_finish chose
+static int finish_k4(sca_ctx *c, int k4, hipEvent_t stop) {
+    const DeviceView &d = c->d;
+    double agent_reach, obs_reach; collide_reach(c, agent_reach, obs_reach);
+    const dim3 grid((d.shard_count + K4_WAVES * K4_APW - 1) / (K4_WAVES * K4_APW)), block(K4_WAVES * 64);
+    const int fresh = c->state_fresh ? 1 : 0;                             // (flags came from sca_set_state: arrived agents are checked against obstacles once)
+    switch (k4) {
+    case K4_SCENE_OBS: LAUNCH_OPT(c, stop, k_collide_finish_scenes<SceneObsRoots>, grid, block, c->stream, d, c->P, agent_reach, obs_reach, fresh, SceneObsRoots{c->scenes.v, c->scenes.ov}); break;
+    case K4_SCENES: LAUNCH_OPT(c, stop, k_collide_finish_scenes<SceneRoots>, grid, block, c->stream, d, c->P, agent_reach, obs_reach, fresh, SceneRoots{c->scenes.v}); break;
+    case K4_GRID: LAUNCH_OPT(c, stop, k_collide_finish_grid, grid, block, c->stream, d, c->grid, c->P, agent_reach, obs_reach, fresh); break;
+    default: LAUNCH_OPT(c, stop, k_collide_finish, grid, block, c->stream, d, c->P, agent_reach, obs_reach, fresh);
     }
-    const dim3 k4grid((cnt + K4_WAVES * K4_APW - 1) / (K4_WAVES * K4_APW));
-    // (the event that rides on the step's last kernel, if sca_run_steps asked for one: the next pass's fork)
-    const bool others = c->part_on || cnt < d.n;
-    // (with the harvest the step's last kernel is k_scene_harvest, and the event rides on that one)
-    const bool harvest = c->scenes.on && c->scenes.hv_host != nullptr;
-    const hipEvent_t last_stop = others ? nullptr : c->finish_stop, others_stop = others ? c->finish_stop : nullptr;
-    const hipEvent_t k4_stop = harvest ? nullptr : last_stop;
-    const int fresh = c->state_fresh ? 1 : 0;
-    if (c->scenes.on) {
-        if (c->scenes.obs_on) LAUNCH_OPT(c, k4_stop, k_collide_finish_scenes<SceneObsRoots>, k4grid, dim3(K4_WAVES * 64), c->stream, d, c->P, agent_reach, obs_reach, fresh, SceneObsRoots{c->scenes.v, c->scenes.ov});
-        else LAUNCH_OPT(c, k4_stop, k_collide_finish_scenes<SceneRoots>, k4grid, dim3(K4_WAVES * 64), c->stream, d, c->P, agent_reach, obs_reach, fresh, SceneRoots{c->scenes.v});
-        c->scenes.begun = false; c->scenes.live_valid = true;
-        if (harvest) {                                                      // d.rec_new: what K4 just wrote, the current records behind the swap below
-            const HarvestDev h{d.rec_new, d.heading, d.total_dist, d.step_num, c->scenes.size, c->scenes.hv_host, c->scenes.hv_layout, ++c->scenes.hv_batch_step};
-            LAUNCH_OPT(c, last_stop, k_scene_harvest, dim3(c->scenes.v.nscenes), dim3(HARVEST_T), c->stream, c->scenes.v, h);
-        }
-    } else if (c->nbr_mode == SCA_NBR_GRID)
-        LAUNCH_OPT(c, k4_stop, k_collide_finish_grid, k4grid, dim3(K4_WAVES * 64), c->stream, d, c->grid, c->P, agent_reach, obs_reach, fresh);
-    else
-        LAUNCH_OPT(c, k4_stop, k_collide_finish, k4grid, dim3(K4_WAVES * 64), c->stream, d, c->P, agent_reach, obs_reach, fresh);
+    return 0;
+}
+// `ride`: the event for the step's last kernel, if sca_run_steps hands one over (the next pass's fork).  Afterwards the moved records are the current ones (buffer swap, no copy)
+static int launch_collide_finish(sca_ctx *c, bool timed, hipEvent_t ride) {
+    DeviceView &d = c->d;
+    const FinishPlan f = plan_finish(c->scenes.on, c->scenes.obs_on, c->scenes.hv_host != nullptr, c->part_on, d.shard_count < d.n, c->nbr_mode);
+    const auto stop_of = [&](int carrier) { return f.carrier == carrier ? ride : nullptr; };
+    if (int r = finish_prepare(c)) return r;
+    if (int r = finish_observers(c)) return r;
+    if (int r = finish_k4(c, f.k4, stop_of(CARRY_K4))) return r;
+    if (c->scenes.on) { c->scenes.begun = false; c->scenes.live_valid = true; }
+    if (f.harvest) {                    // the scenes that finished in this step hand over their result; d.rec_new: what K4 just wrote, the current records behind the swap below
+        const HarvestDev h{d.rec_new, d.heading, d.total_dist, d.step_num, c->scenes.size, c->scenes.hv_host, c->scenes.hv_layout, ++c->scenes.hv_batch_step};
+        LAUNCH_OPT(c, stop_of(CARRY_HARVEST), k_scene_harvest, dim3(c->scenes.v.nscenes), dim3(HARVEST_T), c->stream, c->scenes.v, h);
+    }
     c->state_fresh = false;
-    if (c->part_on) {
-        // sized with the whole present bound: d.shard_count and d.n_present are the host's UPPER bounds (part_bounds clamps the halo
-        // bound to n - owned bound, i.e. to 0 for small swarms), so their difference says nothing about the halo count -- the kernel
-        // reads the exact counts and returns beyond them (halo copies that arrived at their goal kept flying for their
-        // neighbours on this rank for one step)
-        LAUNCH_OPT(c, others_stop, k_goal_flags_others, dim3((std::max(1, d.n_present) + 255) / 256), dim3(256), c->stream, d, c->P);
-    } else if (cnt < d.n) LAUNCH_OPT(c, others_stop, k_goal_flags_others, dim3((d.n + 255) / 256), dim3(256), c->stream, d, c->P);
+    if (f.others) {                     // the goal flags of the agents that are not this shard's
+        // the partition, sized with the whole present bound: d.shard_count and d.n_present are the host's UPPER bounds (part_bounds clamps the halo bound
+        // to n - owned bound, i.e. to 0 for small swarms), so their difference says nothing about the halo count -- the kernel reads the exact counts and
+        // returns beyond them (halo copies that arrived at their goal kept flying for their neighbours on this rank for one step)
+        const int rows = c->part_on ? std::max(1, d.n_present) : d.n;
+        LAUNCH_OPT(c, stop_of(CARRY_OTHERS), k_goal_flags_others, dim3((rows + 255) / 256), dim3(256), c->stream, d, c->P);
+    }
     if (timed) CHK(c, hipEventRecord(c->ev[5], c->stream));
     CHK(c, hipGetLastError());
     std::swap(d.rec, d.rec_new);
     c->h_pos_valid = false;
     return 0;
 }
-static int launch_update(sca_ctx *c, bool timed) {
-    if (int r = launch_integrate(c)) return r;
-    return launch_collide_finish(c, timed);
+static int update_refuse(sca_ctx *c, const char *who) {                    // (the closest-approach records need this step's agent tree: refused before anything is enqueued)
+    return clearance_refuse(c, who, clearance_check(CLR_UPDATE, clearance_state(c), c->near_valid ? 1 : 0, c->nbr_mode == SCA_NBR_GRID && !c->au.ran ? 1 : 0, true, 0));
 }
 
 int sca_policy_pass(sca_ctx *c, int neighbor_mode) {
     API_ENTER(c);
-    if (!c->state_set) { c->err = "sca_set_state first"; return SCA_ERR_STATE; }
-    if (int r = launch_policy(c, neighbor_mode, true, false)) return r;
+    if (int r = step_refuse(c, "", STEP_CHK_STATE, 0, neighbor_mode)) return r;
+    if (int r = launch_policy(c, neighbor_mode, true, false, PassRide{})) return r;
     if (int r = auto_join(c)) return r;
     CHK(c, hipStreamSynchronize(c->stream));
     if (neighbor_mode == SCA_NBR_KDTREE || neighbor_mode == SCA_NBR_AUTO) { if (int r = check_kd_overflow(c)) return r; }
     CHK(c, hipEventElapsedTime(&c->ms_nbr, c->ev[0], c->ev[1]));
     CHK(c, hipEventElapsedTime(&c->ms_solve, c->ev[2], c->ev[3]));
-    return 0;
-}
-
-static int read_active(sca_ctx *c, int *active, bool kd_word);
-int sca_env_update(sca_ctx *c, int *all_done) {
-    API_ENTER(c);
-    if (!c->state_set) { c->err = "sca_set_state first"; return SCA_ERR_STATE; }
-    // (the closest-approach records need this step's agent tree: refused before anything is enqueued)
-    if (int r = clearance_refuse(c, "sca_env_update", clearance_check(CLR_UPDATE, clearance_state(c), c->near_valid ? 1 : 0, c->nbr_mode == SCA_NBR_GRID && !c->au.ran ? 1 : 0, true, 0))) return r;
-    CHK(c, hipEventRecord(c->ev[4], c->stream));
-    if (int r = launch_update(c, true)) return r;
-    if (all_done) {
-        int active = 0;
-        if (int r = read_active(c, &active, false)) return r;
-        CHK(c, hipEventElapsedTime(&c->ms_update, c->ev[4], c->ev[5]));
-        *all_done = (active == 0);
-    }
     return 0;
 }
 
@@ -2988,10 +2983,25 @@ static int read_active(sca_ctx *c, int *active, bool kd_word) {
     *active = n;
     return 0;
 }
+int sca_env_update(sca_ctx *c, int *all_done) {
+    API_ENTER(c);
+    if (int r = step_refuse(c, "", STEP_CHK_STATE, 0, 0)) return r;
+    if (int r = update_refuse(c, "sca_env_update")) return r;
+    CHK(c, hipEventRecord(c->ev[4], c->stream));
+    if (int r = launch_integrate(c)) return r;
+    if (int r = launch_collide_finish(c, true, nullptr)) return r;
+    if (all_done) {
+        int active = 0;
+        if (int r = read_active(c, &active, false)) return r;
+        CHK(c, hipEventElapsedTime(&c->ms_update, c->ev[4], c->ev[5]));
+        *all_done = (active == 0);
+    }
+    return 0;
+}
 int sca_active_count(sca_ctx *c, int *active) {
     API_ENTER(c);
     ARG(c, active);
-    if (!c->state_set) { c->err = "sca_set_state first"; return SCA_ERR_STATE; }
+    if (int r = step_refuse(c, "", STEP_CHK_STATE, 0, 0)) return r;
     return read_active(c, active, c->perm_on_device);
 }
 
@@ -3010,7 +3020,6 @@ static int exchange_moved_records(sca_ctx *c) {
     return 0;
 }
 
-static int run_steps_loop(sca_ctx *c, int steps, int neighbor_mode, bool lazy);
 // A failure in the middle of the loop (an exchange, a launch, a partition commit) must not leave the AUTO bookkeeping pointing at a tree
 // built ahead from positions the caller is about to replace: forget the build-ahead, let the context's stream wait for whatever
 // the kd stream still holds, and have the next AUTO pass decide afresh.
@@ -3026,6 +3035,53 @@ static void auto_abandon(sca_ctx *c) {
     }
     c->au.unjoined = false;
 }
+// what plan_step asks of the context, as it stands when it is asked
+static StepIn step_in(const sca_ctx *c, int mode, int s, int steps) {
+    return StepIn{mode, s, steps, c->au.stream != nullptr, c->tun.ext_stop != 0, c->comm != nullptr, c->d.shard_count == c->n, c->trk_on, c->trk_in_pass, c->trk_fork != nullptr,
+                  c->paths_on, c->clear != nullptr, c->au.ran, c->au.fits, c->part_on, c->au.last, c->tun.auto_div, c->au.backoff, c->d.shard_count};
+}
+// between the pass and the update: what the shard moved reaches the others, or what stands in for that
+static int step_exchange(sca_ctx *c) {
+    if (c->part_on) {                                                      // one rank (or one rank alone, emulation): nobody to exchange with
+        if (c->part_nranks > 1) { if (int r = sca_partition_pack(c, c->part_scratch[0], c->part_scratch[1])) return r; }
+        if (int r = sca_partition_commit(c)) return r;
+    }
+    if (c->comm) return exchange_moved_records(c);
+    if (c->shard_emulation && !c->part_on && c->d.shard_count < c->n) {      // (partition: the halo copies stand still by themselves)
+        // stand-in for the all-gather's arrivals: the other ranks' agents stand still (their records are copied over)
+        const int b = c->d.shard_begin, e = b + c->d.shard_count;
+        if (b > 0) CHK(c, hipMemcpyAsync(c->d.rec_new, c->d.rec, sizeof(PubRec) * (size_t)b, hipMemcpyDeviceToDevice, c->stream));
+        if (e < c->n) CHK(c, hipMemcpyAsync(c->d.rec_new + e, c->d.rec + e, sizeof(PubRec) * (size_t)(c->n - e), hipMemcpyDeviceToDevice, c->stream));
+    }
+    return 0;
+}
+// the update, then the NEXT pass's kd build from the moved positions (plan_step says why it may start here)
+static int finish_then_build_ahead(sca_ctx *c, bool moved_recorded) {
+    // (the collision check goes to its stream FIRST: the host needs ~5 us per launch, and the build's eight or more launches in
+    // front of it left the main stream idle for 50 us at N = 4096)
+    if (!moved_recorded) CHK(c, hipEventRecord(c->au.ev_moved, c->stream));
+    if (int r = launch_collide_finish(c, false, nullptr)) return r;       // (swaps the record buffers: the moved ones are c->d.rec now)
+    if (int r = auto_enqueue_kd_build(c, c->au.ev_moved, c->d.rec, true)) return r;
+    c->au.ahead = true;
+    return 0;
+}
+static int run_steps_loop(sca_ctx *c, int steps, int neighbor_mode, bool lazy) {
+    if (int r = step_refuse(c, "", STEP_CHK_ALL, steps, neighbor_mode)) return r;
+    for (int k = 0; k < 2 && c->part_on && c->part_nranks > 1; k++)          // emulation: this rank alone, its messages go nowhere
+        if (!c->part_scratch[k]) CHK(c, hipMalloc((void **)&c->part_scratch[k], part_message_bytes(c->part.cap_halo, c->part.cap_mig)));
+    bool fork_ready = false;                                               // the fork of step s rode on the last kernel of step s - 1
+    for (int s = 0; s < steps; s++) {
+        const bool moved = plan_step(step_in(c, neighbor_mode, s, steps)).moved_on_action;
+        if (int r = launch_policy(c, neighbor_mode, false, true, PassRide{moved ? c->au.ev_moved : nullptr, fork_ready})) return r;   // integrate fused into k_solve
+        if (int r = step_exchange(c)) return r;
+        const StepPlan p = plan_step(step_in(c, neighbor_mode, s, steps));  // (behind the pass: Auto::ran and auto_next's inputs are its results)
+        fork_ready = p.fork_rides;
+        if (p.build_ahead) { if (int r = finish_then_build_ahead(c, moved)) return r; }
+        else if (int r = launch_collide_finish(c, false, p.fork_rides ? c->trk_fork : nullptr)) return r;
+    }
+    if (lazy && c->au.unjoined && c->au.ran) { c->au.lazy_join = true; return 0; }   // (sca_env_step: see API_ENTER)
+    return auto_join(c);
+}
 static int run_steps_guarded(sca_ctx *c, int steps, int neighbor_mode, bool lazy) {
     const int r = run_steps_loop(c, steps, neighbor_mode, lazy);
     if (r != 0) { const std::string keep = c->err; auto_abandon(c); c->err = keep; }
@@ -3034,68 +3090,6 @@ static int run_steps_guarded(sca_ctx *c, int steps, int neighbor_mode, bool lazy
 int sca_run_steps(sca_ctx *c, int steps, int neighbor_mode) {
     API_ENTER(c);
     return run_steps_guarded(c, steps, neighbor_mode, false);
-}
-static int run_steps_loop(sca_ctx *c, int steps, int neighbor_mode, bool lazy) {
-    c->fork_ready = false; c->finish_stop = nullptr; c->action_stop = nullptr;
-    if (!c->state_set) { c->err = "sca_set_state first"; return SCA_ERR_STATE; }
-    if (steps < 0) { c->err = "steps must not be negative"; return SCA_ERR_ARG; }
-    if (neighbor_mode < SCA_NBR_KDTREE || neighbor_mode > SCA_NBR_AUTO) {     // (also for steps == 0: a wrong mode is a wrong call)
-        c->err = "neighbor mode not available in this build"; return SCA_ERR_UNSUPPORTED;
-    }
-    if (c->part_on && c->part_nranks > 1 && !c->shard_emulation) {
-        c->err = "cell-owner partition over several ranks: drive the step with sca_step_begin / sca_partition_pack / [exchange] / "
-                 "sca_partition_unpack / sca_partition_commit / sca_step_end (sca_amd.distributed.PartitionedStepper)";
-        return SCA_ERR_STATE;
-    }
-    if (c->part_on && c->part_nranks > 1) {                                 // emulation: this rank alone, its messages go nowhere
-        for (int k = 0; k < 2; k++)
-            if (!c->part_scratch[k]) CHK(c, hipMalloc((void **)&c->part_scratch[k], part_message_bytes(c->part.cap_halo, c->part.cap_mig)));
-    }
-    if (c->part_on && neighbor_mode != SCA_NBR_GRID) { c->err = "the cell-owner partition is a mode of SCA_NBR_GRID"; return SCA_ERR_UNSUPPORTED; }
-    for (int s = 0; s < steps; s++) {
-        // (SCA_NBR_AUTO, another step to follow: the moved positions' event rides on k_action -- the next pass's kd build waits on it)
-        c->action_stop = neighbor_mode == SCA_NBR_AUTO && s + 1 < steps && c->au.stream && c->tun.ext_stop && !c->comm && c->d.shard_count == c->n
-                             ? c->au.ev_moved : nullptr;                      // (a shard: the records of the others arrive after k_action)
-        const int rp = launch_policy(c, neighbor_mode, false, true);           // integrate fused into k_solve
-        const bool moved_recorded = c->action_stop != nullptr;
-        c->action_stop = nullptr;
-        if (rp) return rp;
-        if (c->part_on) {                                                      // one rank (or one rank alone, emulation): nobody to exchange with
-            if (c->part_nranks > 1) { if (int r = sca_partition_pack(c, c->part_scratch[0], c->part_scratch[1])) return r; }
-            if (int r = sca_partition_commit(c)) return r;
-        }
-        if (c->comm) { if (int r = exchange_moved_records(c)) return r; }
-        else if (c->shard_emulation && !c->part_on && c->d.shard_count < c->n) {      // (partition: the halo copies stand still by themselves)
-            // stand-in for the all-gather's arrivals: the other ranks' agents stand still (their records are copied over)
-            const int b = c->d.shard_begin, e = b + c->d.shard_count;
-            if (b > 0) CHK(c, hipMemcpyAsync(c->d.rec_new, c->d.rec, sizeof(PubRec) * (size_t)b, hipMemcpyDeviceToDevice, c->stream));
-            if (e < c->n) CHK(c, hipMemcpyAsync(c->d.rec_new + e, c->d.rec + e, sizeof(PubRec) * (size_t)(c->n - e), hipMemcpyDeviceToDevice, c->stream));
-        }
-        // (not with the closest-approach records on: k_clearance reads this step's tree, which a build enqueued ahead would overwrite beside it)
-        if (neighbor_mode == SCA_NBR_AUTO && c->au.ran && s + 1 < steps && !c->clear &&
-            auto_next(c->au.fits, c->trk_on && c->trk_in_pass, c->part_on, c->au.last, c->tun.auto_div, c->au.backoff, c->d.shard_count)) {
-            // SCA_NBR_AUTO: the NEXT pass's kd build needs the moved positions only -- k_collide_finish changes flags, and in an
-            // AUTO pass its fallback looks into the grid, not into the tree -- so it starts here, beside the collision check and the
-            // next pass's grid build and query.  Only inside one call: a caller who reads the permutation between calls sees as many
-            // builds as steps.
-            // (the collision check goes to its stream FIRST: the host needs ~5 us per launch, and the build's eight or more launches in
-            // front of it left the main stream idle for 50 us at N = 4096)
-            if (!moved_recorded) CHK(c, hipEventRecord(c->au.ev_moved, c->stream));
-            if (int r = launch_collide_finish(c, false)) return r;                 // ((no tracker in an AUTO pass: no fork to carry) swaps the record buffers: the moved ones are c->d.rec now)
-            if (int r = auto_enqueue_kd_build(c, c->au.ev_moved, c->d.rec, true)) return r;
-            c->au.ahead = true;
-            continue;
-        }
-        // the next pass's fork (tracker in the pass, its neighbour branch on the side stream) rides on this step's last kernel
-        // (not while waypoint lists are set: the next pass's k_waypoint must come before its fork)
-        c->finish_stop = s + 1 < steps && c->tun.ext_stop && c->trk_on && c->trk_in_pass && c->trk_fork && !c->paths_on ? c->trk_fork : nullptr;
-        const int rf = launch_collide_finish(c, false);
-        c->fork_ready = rf == 0 && c->finish_stop != nullptr;
-        c->finish_stop = nullptr;
-        if (rf) return rf;
-    }
-    if (lazy && c->au.unjoined && c->au.ran) { c->au.lazy_join = true; return 0; }   // (sca_env_step: see API_ENTER)
-    return auto_join(c);
 }
 int sca_env_step(sca_ctx *c, int neighbor_mode, int *active) {
     if (!c) return SCA_ERR_ARG;                                           // (not API_ENTER: a step after a step needs no join)
@@ -3149,12 +3143,10 @@ int sca_host_state_get(sca_ctx *c, sca_host_state *out, int32_t struct_bytes) {
     std::memcpy(out, &h, fit);
     return 0;
 }
-int sca_step_host(sca_ctx *c, int neighbor_mode, uint32_t in_mask, int *active) {
-    API_ENTER(c);                                                         // (the block replaces or reads state: an AUTO pass's kd stream is joined first)
-    ARG(c, active);
-    ARG(c, (in_mask & ~(uint32_t)(SCA_HOST_IN_STATE | SCA_HOST_IN_VPREF)) == 0);
+// sca_step_host's refusals (and the block's allocation among them, where it always was)
+static int host_step_refuse(sca_ctx *c, int neighbor_mode, uint32_t in_mask) {
     if (!c->agents_set) { c->err = "sca_step_host: sca_set_agents first"; return SCA_ERR_STATE; }
-    if (neighbor_mode < SCA_NBR_KDTREE || neighbor_mode > SCA_NBR_AUTO) { c->err = "sca_step_host: neighbor mode not available in this build"; return SCA_ERR_UNSUPPORTED; }
+    if (int r = step_refuse(c, "sca_step_host: ", STEP_CHK_MODE, 0, neighbor_mode)) return r;
     if (c->comm) { c->err = "sca_step_host with an active communicator: the block is the whole swarm's state on one rank (sca_comm_destroy first)"; return SCA_ERR_UNSUPPORTED; }
     if (c->part_on) { c->err = "sca_step_host under the cell-owner partition: the block is the whole swarm's state on one rank (sca_partition_disable first)"; return SCA_ERR_UNSUPPORTED; }
     if (c->d.shard_count < c->n) { c->err = "sca_step_host on a shard (sca_set_shard with count < n): the block is the whole swarm's state on one rank"; return SCA_ERR_STATE; }
@@ -3162,47 +3154,56 @@ int sca_step_host(sca_ctx *c, int neighbor_mode, uint32_t in_mask, int *active) 
     if (!(in_mask & SCA_HOST_IN_STATE) && !c->state_set) { c->err = "sca_step_host: no state yet -- write the block and pass SCA_HOST_IN_STATE (or sca_set_state first)"; return SCA_ERR_STATE; }
     if (in_mask && !c->hs_host) { c->err = "sca_step_host: sca_host_state_get first -- nothing can have been written to a block nobody has fetched"; return SCA_ERR_STATE; }
     if (int r = host_block_alloc(c)) return r;
-    const int n = c->n;
-    const HostLayout L = host_state_layout(n);
     if ((in_mask & SCA_HOST_IN_VPREF) && c->paths_on) {                    // sca_set_vpref's rule, on the block's vpref_mode
-        const uint8_t *mode = c->hs_host + L.off[HS_VPREF_MODE];
-        for (int i = 0; i < n; i++)
+        const uint8_t *mode = c->hs_host + host_state_layout(c->n).off[HS_VPREF_MODE];
+        for (int i = 0; i < c->n; i++)
             if (mode[i] && c->h_path_vpref[i]) {
                 c->err = "sca_set_vpref: agent " + std::to_string(i) + " follows a waypoint list (sca_set_paths): its v_pref is its policy's, toward the waypoint";
                 return SCA_ERR_ARG;
             }
     }
-    const HostIoDev io{c->d.rec, c->d.heading, c->d.total_dist, c->d.step_num, c->d.vpref_ext, c->d.vpref_mode, c->d.action};
-    const dim3 grid((n + HIO_TILE - 1) / HIO_TILE), block(HIO_TILE);
-    uint8_t *blk = c->tun.hs_staged ? c->hs_dev : c->hs_host;               // what the two kernels read and write
+    return 0;
+}
+// the device side of the block's two kernels, on the current records; what they read and write is the staging buffer in the staged form
+static HostIoDev host_io(const sca_ctx *c) { return HostIoDev{c->d.rec, c->d.heading, c->d.total_dist, c->d.step_num, c->d.vpref_ext, c->d.vpref_mode, c->d.action}; }
+static uint8_t *host_io_block(const sca_ctx *c) { return c->tun.hs_staged ? c->hs_dev : c->hs_host; }
+// the sections the caller wrote, into the device's arrays
+static int host_ingest(sca_ctx *c, uint32_t in_mask) {
+    const int n = c->n; const HostLayout L = host_state_layout(n);
     if ((in_mask & SCA_HOST_IN_STATE) && c->scenes.hv_host) {              // sca_set_state's rule for the harvest; the words are the host's to
         CHK(c, hipStreamSynchronize(c->stream));                           // write only while no step is in flight (idle behind a sca_step_host)
         scene_harvest_clear_fresh(c, 0, nullptr);
     }
-    if (in_mask) {
-        // (staged form: the up-going sections are contiguous, [pos .. step_num] [vpref, vpref_mode] -- one copy takes what was written)
-        const int64_t lo = (in_mask & SCA_HOST_IN_STATE) ? L.off[HS_POS] : L.off[HS_VPREF];
-        const int64_t hi = (in_mask & SCA_HOST_IN_VPREF) ? L.off[HS_ACTION] : L.off[HS_VPREF];
-        if ((in_mask & SCA_HOST_IN_STATE) && !c->state_set)               // the first state of this agent set: `radius` reaches the device with it
-            CHK(c, hipMemcpyAsync(c->d.rec, c->h_rec.data(), sizeof(PubRec) * n, hipMemcpyHostToDevice, c->stream));
-        if (c->tun.hs_staged) CHK(c, hipMemcpyAsync(c->hs_dev + lo, c->hs_host + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_host_ingest, grid, block, 0, c->stream, io, (const uint8_t *)blk, n, in_mask);
-        CHK(c, hipGetLastError());
-        if (in_mask & SCA_HOST_IN_STATE) {                                 // sca_set_state's bookkeeping (no host mirror of the positions is kept)
-            positions_replaced(c); c->au.forget();
-            c->h_pos_valid = false; c->near_valid = false;
-            c->state_set = true; c->state_fresh = true;
-            c->scenes.live_valid = false; c->scenes.begun = false;
-        }
-    }
-    if (int r = run_steps_guarded(c, 1, neighbor_mode, false)) return r;  // integrate fused into the pass, k_collide_finish; joins the kd stream
-    HostIoDev out = io;
-    out.rec = c->d.rec;                                                   // (the step swapped the record arrays: the moved ones are current)
-    hipLaunchKernelGGL(k_host_egress, grid, block, 0, c->stream, out, blk, n);
+    if (!in_mask) return 0;
+    // (staged form: the up-going sections are contiguous, [pos .. step_num] [vpref, vpref_mode] -- one copy takes what was written)
+    const int64_t lo = (in_mask & SCA_HOST_IN_STATE) ? L.off[HS_POS] : L.off[HS_VPREF];
+    const int64_t hi = (in_mask & SCA_HOST_IN_VPREF) ? L.off[HS_ACTION] : L.off[HS_VPREF];
+    if ((in_mask & SCA_HOST_IN_STATE) && !c->state_set)                   // the first state of this agent set: `radius` reaches the device with it
+        CHK(c, hipMemcpyAsync(c->d.rec, c->h_rec.data(), sizeof(PubRec) * n, hipMemcpyHostToDevice, c->stream));
+    if (c->tun.hs_staged) CHK(c, hipMemcpyAsync(c->hs_dev + lo, c->hs_host + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_host_ingest, dim3((n + HIO_TILE - 1) / HIO_TILE), dim3(HIO_TILE), 0, c->stream, host_io(c), (const uint8_t *)host_io_block(c), n, in_mask);
+    CHK(c, hipGetLastError());
+    if (in_mask & SCA_HOST_IN_STATE) { state_replaced(c); c->h_pos_valid = false; }   // (no host mirror of the positions is kept)
+    return 0;
+}
+// the moved state and the action rows, into the block (the step swapped the record arrays: host_io takes the current ones)
+static int host_egress(sca_ctx *c) {
+    const int n = c->n; const HostLayout L = host_state_layout(n);
+    hipLaunchKernelGGL(k_host_egress, dim3((n + HIO_TILE - 1) / HIO_TILE), dim3(HIO_TILE), 0, c->stream, host_io(c), host_io_block(c), n);
     CHK(c, hipGetLastError());
     // (staged form, down: the state sections and the action rows; the caller's v_pref sections between them are never written)
     if (c->tun.hs_staged) CHK(c, hipMemcpyAsync(c->hs_host + L.off[HS_POS], c->hs_dev + L.off[HS_POS], (size_t)(L.off[HS_VPREF] - L.off[HS_POS]), hipMemcpyDeviceToHost, c->stream));
     if (c->tun.hs_staged) CHK(c, hipMemcpyAsync(c->hs_host + L.off[HS_ACTION], c->hs_dev + L.off[HS_ACTION], (size_t)(L.total - L.off[HS_ACTION]), hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+int sca_step_host(sca_ctx *c, int neighbor_mode, uint32_t in_mask, int *active) {
+    API_ENTER(c);                                                         // (the block replaces or reads state: an AUTO pass's kd stream is joined first)
+    ARG(c, active);
+    ARG(c, (in_mask & ~(uint32_t)(SCA_HOST_IN_STATE | SCA_HOST_IN_VPREF)) == 0);
+    if (int r = host_step_refuse(c, neighbor_mode, in_mask)) return r;
+    if (int r = host_ingest(c, in_mask)) return r;
+    if (int r = run_steps_guarded(c, 1, neighbor_mode, false)) return r;  // integrate fused into the pass, k_collide_finish; joins the kd stream
+    if (int r = host_egress(c)) return r;
     return read_active(c, active, c->perm_on_device);                     // ... and the count (and the kd build's error word): the call's one synchronisation
 }
 int sca_set_shard_emulation(sca_ctx *c, int on) {
@@ -3487,16 +3488,14 @@ int sca_partition_commit(sca_ctx *c) {
 
 int sca_step_begin(sca_ctx *c, int neighbor_mode) {
     API_ENTER(c);
-    if (!c->state_set) { c->err = "sca_set_state first"; return SCA_ERR_STATE; }
-    if (c->part_on && neighbor_mode != SCA_NBR_GRID) { c->err = "the cell-owner partition is a mode of SCA_NBR_GRID"; return SCA_ERR_UNSUPPORTED; }
-    if (int r = launch_policy(c, neighbor_mode, false, true)) return r;
+    if (int r = step_refuse(c, "", STEP_CHK_STATE | STEP_CHK_PART_MODE, 0, neighbor_mode)) return r;   // (a mode out of range: the pass refuses it)
+    if (int r = launch_policy(c, neighbor_mode, false, true, PassRide{})) return r;
     return auto_join(c);                                                  // (the caller may read anything between the two halves of a step)
 }
 int sca_step_end(sca_ctx *c) {
     API_ENTER(c);
-    // (the closest-approach records need this step's agent tree: sca_env_update's refusal)
-    if (int r = clearance_refuse(c, "sca_step_end", clearance_check(CLR_UPDATE, clearance_state(c), c->near_valid ? 1 : 0, c->nbr_mode == SCA_NBR_GRID && !c->au.ran ? 1 : 0, true, 0))) return r;
-    return launch_collide_finish(c, false);
+    if (int r = update_refuse(c, "sca_step_end")) return r;
+    return launch_collide_finish(c, false, nullptr);
 }
 
 int sca_synchronize(sca_ctx *c) {
@@ -3958,7 +3957,7 @@ int sca_respawn_agents(sca_ctx *c, int count, const int32_t *ids, const double *
         }
     }
     c->h_pos_valid = false; c->near_valid = false;
-    positions_replaced(c);                                             // (a sizing hint, no value; the form heuristics, the AUTO passes' counts among them, are left alone)
+    positions_replaced(c);                                             // (a sizing hint, no value; not state_replaced: the form heuristics, the AUTO passes' counts among them, are left alone)
     return 0;
 }
 int sca_get_finished(sca_ctx *c, sca_finished_row *rows, int capacity, int *count, int32_t struct_bytes) {

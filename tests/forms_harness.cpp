@@ -61,6 +61,28 @@ void forms_plan_auto_pass(unsigned auto_seq, unsigned tail_seq, unsigned on_kd, 
     std::memcpy(out11, v, sizeof(v));
 }
 
+// in19: StepIn's members in their order; out: moved_on_action, build_ahead, fork_rides
+void forms_plan_step(const int *in19, int *out3) {
+    const int *v = in19;
+    const StepIn i{v[0], v[1], v[2], v[3] != 0, v[4] != 0, v[5] != 0, v[6] != 0, v[7] != 0, v[8] != 0, v[9] != 0, v[10] != 0, v[11] != 0, v[12] != 0,
+                   v[13] != 0, v[14] != 0, v[15], v[16], v[17], v[18]};
+    const StepPlan p = plan_step(i);
+    out3[0] = p.moved_on_action; out3[1] = p.build_ahead; out3[2] = p.fork_rides;
+}
+// out: k4 (FinishK4), carrier (FinishCarrier), harvest, others
+void forms_plan_finish(int scenes_on, int obs_on, int harvest_on, int part_on, int shard_below_n, int last_mode, int *out4) {
+    const FinishPlan p = plan_finish(scenes_on, obs_on, harvest_on, part_on, shard_below_n, last_mode);
+    out4[0] = p.k4; out4[1] = p.carrier; out4[2] = p.harvest; out4[3] = p.others;
+}
+// the fault (StepFault) of an entry point that makes `checks`; out2: its error code and the length of its text, which goes to text[cap]
+int forms_step_check(int checks, int state_set, int steps, int mode, int part_on, int part_ranks_apart, int *out2, char *text, int cap) {
+    const StepFault f = step_check(checks, state_set, steps, mode, part_on, part_ranks_apart);
+    const char *t = step_fault_text(f);
+    out2[0] = step_fault_code(f); out2[1] = (int)std::strlen(t);
+    if (cap > 0) { const size_t k = std::min((size_t)out2[1], (size_t)cap - 1); std::memcpy(text, t, k); text[k] = 0; }
+    return f;
+}
+
 int forms_choose_solve_split(const int *tun, int simds, int overlap, int cnt, int trk_last_count) {
     return choose_solve_split(tun_of(tun), simds, overlap, cnt, trk_last_count);
 }
@@ -116,6 +138,30 @@ int main() {
                     if (p11[4] != (long long)((seq + 1u) & 3u) || p11[6] < 0 || p11[6] > 15 || b5[3] > 3 || p11[2] > 3) { std::printf("forms_harness: a slot out of range\n"); return 1; }
                     sum += b5[2] + b5[3] + b5[4] + p11[1] + p11[2] + p11[8] + p11[9] + p11[10];
                 }
+    // the step's plans over every combination of their flags (bursts of 3, every mode), the refusals into a text buffer of exactly their length
+    std::unique_ptr<int[]> in19(new int[19]), o3(new int[3]), o2(new int[2]);
+    for (int mode = SCA_NBR_KDTREE; mode <= SCA_NBR_AUTO; mode++)
+        for (int s = 0; s < 3; s++)
+            for (unsigned bits = 0; bits < (1u << 12); bits++) {
+                const int v[19] = {mode, s, 3, (int)(bits & 1), (int)(bits >> 1 & 1), (int)(bits >> 2 & 1), (int)(bits >> 3 & 1), (int)(bits >> 4 & 1), (int)(bits >> 5 & 1),
+                                   (int)(bits >> 6 & 1), (int)(bits >> 7 & 1), (int)(bits >> 8 & 1), (int)(bits >> 9 & 1), (int)(bits >> 10 & 1), (int)(bits >> 11 & 1), -1, 8, 0, 1000};
+                std::memcpy(in19.get(), v, sizeof(v));
+                forms_plan_step(in19.get(), o3.get());
+                if (o3[1] && o3[2]) { std::printf("forms_harness: a step builds ahead and carries a fork\n"); return 1; }
+                sum += o3[0] + o3[1] + o3[2];
+            }
+    for (int bits = 0; bits < 32; bits++)
+        for (int mode = SCA_NBR_KDTREE; mode <= SCA_NBR_AUTO; mode++) {
+            forms_plan_finish(bits & 1, bits >> 1 & 1, bits >> 2 & 1, bits >> 3 & 1, bits >> 4 & 1, mode, o4.get());
+            if (o4[0] < K4_SCENE_OBS || o4[0] > K4_PLAIN || o4[1] < CARRY_K4 || o4[1] > CARRY_OTHERS) { std::printf("forms_harness: a finish plan out of range\n"); return 1; }
+            sum += o4[0] + o4[1] + o4[2] + o4[3];
+        }
+    for (int checks = 0; checks <= STEP_CHK_ALL; checks++)
+        for (int bits = 0; bits < 16; bits++) {
+            forms_step_check(checks, bits & 1, (bits >> 1 & 1) - 1, SCA_NBR_KDTREE - 1 + 3 * (bits >> 2 & 1), 1, bits >> 3 & 1, o2.get(), nullptr, 0);
+            std::unique_ptr<char[]> text(new char[(size_t)o2[1] + 1]);
+            sum += forms_step_check(checks, bits & 1, (bits >> 1 & 1) - 1, SCA_NBR_KDTREE - 1 + 3 * (bits >> 2 & 1), 1, bits >> 3 & 1, o2.get(), text.get(), o2[1] + 1) + (int)std::strlen(text.get());
+        }
     for (int cnt : {1, 2048, 30000, 100000, 2000000}) {
         sum += forms_choose_solve_split(tun.get(), 1024, 1, cnt, cnt / 2);
         forms_plan_solve(tun.get(), 1024, cnt, 0, 1, cnt / 3, cnt / 3, cnt & 1, -1, 0, o7.get());

@@ -420,6 +420,161 @@ def test_auto_slot_model_no_list_refilled_and_no_record_buffer_written_under_a_r
     assert min(seen.values()) > 20, seen         # every branch of the model ran
 
 
+# ---- a step of a burst: the events that ride ---------------------------------------------------------------------------------------------------------
+# From sca_run_steps' loop and launch_collide_finish as they stood before plan_step / plan_finish existed (the conditions are quoted in the tests).
+KD, GRID, HOSTBUILD, AUTO = 0, 1, 2, 3                                                          # include/sca_hip.h
+STEP_IN = ('mode', 'step', 'steps', 'kd_stream', 'ext_stop', 'comm', 'whole', 'trk_on', 'trk_in_pass', 'trk_fork', 'paths_on', 'clear_on', 'auto_ran',
+           'fits', 'part_on', 'kdq_last', 'auto_div', 'auto_backoff', 'shard_count')
+AUTO_BURST = dict(mode=AUTO, step=0, steps=3, kd_stream=1, ext_stop=1, comm=0, whole=1, trk_on=0, trk_in_pass=0, trk_fork=0, paths_on=0, clear_on=0,
+                  auto_ran=1, fits=1, part_on=0, kdq_last=-1, auto_div=8, auto_backoff=0, shard_count=1000)
+TRACKED_BURST = dict(AUTO_BURST, mode=KD, kd_stream=0, auto_ran=0, trk_on=1, trk_in_pass=1, trk_fork=1)
+K4_SCENE_OBS, K4_SCENES, K4_GRID, K4_PLAIN = range(4)
+ON_K4, ON_HARVEST, ON_OTHERS = range(3)
+
+
+def step(H, base, **over):
+    d = dict(base, **over)
+    out = (C.c_int * 3)()
+    H.forms_plan_step((C.c_int * 19)(*[d[k] for k in STEP_IN]), out)
+    return tuple(out)                                                                          # (ev_moved on k_action, build ahead, fork on the last kernel)
+
+
+def finish(H, scenes=0, obs=0, harvest=0, part=0, below=0, mode=KD):
+    out = (C.c_int * 4)()
+    H.forms_plan_finish(scenes, obs, harvest, part, below, mode, out)
+    return tuple(out)                                                                          # (K4 instance, carrier, harvest runs, k_goal_flags_others runs)
+
+
+def test_plan_step_the_moved_event_on_k_action(H):
+    """mode == AUTO && s + 1 < steps && the kd stream && ext_stop && !comm && shard_count == n"""
+    assert step(H, AUTO_BURST) == (1, 1, 0) and step(H, AUTO_BURST, step=1) == (1, 1, 0)
+    assert step(H, AUTO_BURST, step=2) == (0, 0, 0) and step(H, AUTO_BURST, steps=1) == (0, 0, 0)    # the last step of a burst: no event, nothing ahead
+    assert step(H, AUTO_BURST, whole=0) == (0, 1, 0)                                            # a shard: the records of the others arrive after k_action
+    assert step(H, AUTO_BURST, comm=1) == (0, 1, 0)
+    assert step(H, AUTO_BURST, kd_stream=0) == (0, 1, 0)                                        # (a context's first AUTO pass creates the stream: a record of its own then)
+    assert step(H, AUTO_BURST, ext_stop=0) == (0, 1, 0)
+    assert [step(H, AUTO_BURST, mode=m, auto_ran=0)[0] for m in (KD, GRID, HOSTBUILD)] == [0, 0, 0]
+    assert step(H, AUTO_BURST, clear_on=1)[0] == 1 and step(H, AUTO_BURST, auto_ran=0)[0] == 1  # (none of the build-ahead's own terms is one of this event's)
+
+
+def test_plan_step_the_build_ahead(H):
+    """mode == AUTO && au.ran && s + 1 < steps && !clear && auto_next(fits, trk_on && trk_in_pass, part_on, last, auto_div, backoff, shard_count)"""
+    assert step(H, AUTO_BURST, clear_on=1) == (1, 0, 0)                                         # k_clearance reads this step's tree
+    assert step(H, AUTO_BURST, auto_ran=0) == (1, 0, 0)
+    assert step(H, AUTO_BURST, mode=KD)[1] == 0 and step(H, AUTO_BURST, mode=GRID)[1] == 0
+    assert [step(H, AUTO_BURST, **{k: v})[1] for k, v in (('fits', 0), ('part_on', 1), ('auto_backoff', 1), ('kdq_last', 126), ('kdq_last', 125))] == [0, 0, 0, 0, 1]
+    assert step(H, AUTO_BURST, kdq_last=300, auto_div=1)[1] == 1 and step(H, AUTO_BURST, kdq_last=300, auto_div=4)[1] == 0
+    assert step(H, AUTO_BURST, trk_on=1, trk_in_pass=1)[1] == 0 and step(H, AUTO_BURST, trk_on=1, trk_in_pass=0)[1] == 1      # a tracked pass is a plain kd pass
+    assert step(H, AUTO_BURST, trk_on=0, trk_in_pass=1)[1] == 1
+
+
+def test_plan_step_the_fork_on_the_last_kernel(H):
+    """(no build ahead: that branch ends the step) s + 1 < steps && ext_stop && trk_on && trk_in_pass && trk_fork && !paths_on"""
+    assert step(H, TRACKED_BURST) == (0, 0, 1) and step(H, TRACKED_BURST, mode=GRID) == (0, 0, 1)
+    assert step(H, TRACKED_BURST, step=2) == (0, 0, 0)
+    assert step(H, TRACKED_BURST, paths_on=1) == (0, 0, 0)                                      # the next pass's k_waypoint must come before its fork
+    assert [step(H, TRACKED_BURST, **{k: 0})[2] for k in ('ext_stop', 'trk_on', 'trk_in_pass', 'trk_fork')] == [0, 0, 0, 0]
+    assert step(H, TRACKED_BURST, clear_on=1, comm=1, whole=0, part_on=1) == (0, 0, 1)          # none of them is a term of the fork's
+    assert step(H, TRACKED_BURST, mode=AUTO, kd_stream=1, auto_ran=1) == (1, 0, 1)              # AUTO with the tracker in the pass: kd passes, which fork
+    # with a build ahead the fork does not ride -- over every flag combination (the tracker's terms exclude auto_next's)
+    flags = [k for k in STEP_IN if k not in ('mode', 'step', 'steps', 'kdq_last', 'auto_div', 'auto_backoff', 'shard_count')]
+    for bits in itertools.product((0, 1), repeat=len(flags)):
+        got = step(H, AUTO_BURST, **dict(zip(flags, bits)))
+        assert not (got[1] and got[2]), (bits, got)
+
+
+def test_plan_finish_which_kernel_carries_the_event_and_which_k4_runs(H):
+    """others = part_on || cnt < n; harvest = scenes.on && hv_host; the event: k_goal_flags_others if others, else k_scene_harvest if harvest, else K4.
+    K4: scenes.on ? (obs_on ? <SceneObsRoots> : <SceneRoots>) : nbr_mode == SCA_NBR_GRID ? _grid : plain"""
+    assert finish(H) == (K4_PLAIN, ON_K4, 0, 0) and finish(H, mode=HOSTBUILD) == (K4_PLAIN, ON_K4, 0, 0)
+    assert finish(H, mode=GRID) == (K4_GRID, ON_K4, 0, 0)
+    assert finish(H, scenes=1) == (K4_SCENES, ON_K4, 0, 0) and finish(H, scenes=1, mode=GRID) == (K4_SCENES, ON_K4, 0, 0)
+    assert finish(H, scenes=1, obs=1) == (K4_SCENE_OBS, ON_K4, 0, 0)
+    assert finish(H, obs=1) == (K4_PLAIN, ON_K4, 0, 0) and finish(H, obs=1, mode=GRID) == (K4_GRID, ON_K4, 0, 0)      # obstacle sets per scene are a scene form
+    assert finish(H, scenes=1, harvest=1) == (K4_SCENES, ON_HARVEST, 1, 0) and finish(H, scenes=1, obs=1, harvest=1) == (K4_SCENE_OBS, ON_HARVEST, 1, 0)
+    assert finish(H, harvest=1) == (K4_PLAIN, ON_K4, 0, 0)                                      # (a harvest block without scenes: nothing to launch)
+    assert finish(H, part=1, mode=GRID) == (K4_GRID, ON_OTHERS, 0, 1) and finish(H, below=1) == (K4_PLAIN, ON_OTHERS, 0, 1)
+    assert finish(H, part=1, below=1) == (K4_PLAIN, ON_OTHERS, 0, 1)
+    assert finish(H, scenes=1, harvest=1, below=1) == (K4_SCENES, ON_OTHERS, 1, 1)              # k_goal_flags_others is behind the harvest: the step's last
+
+
+def test_step_model_bursts_of_one_to_six_over_every_flag_combination(H):
+    """A burst of S steps as sca_run_steps runs it, for every combination of the boolean inputs of both plans in every mode: the fork is ready for
+    step s + 1 exactly when step s's update carried it; at most one kernel of a step carries it, and that kernel is launched; an event is chosen
+    only where ext_stop and its owner (the kd stream, trk_fork) exist; the plan of step s depends on nothing after s but "another step follows"."""
+    flags = [k for k in STEP_IN if k not in ('mode', 'step', 'steps', 'kdq_last', 'auto_div', 'auto_backoff', 'shard_count')]
+    arr, out = (C.c_int * 19)(*[AUTO_BURST[k] for k in STEP_IN]), (C.c_int * 3)()
+    at = {k: STEP_IN.index(k) for k in STEP_IN}
+    fin = {key: finish(H, *key) for key in itertools.product((0, 1), (0, 1), (0, 1), (0, 1), (0, 1), (KD, GRID, HOSTBUILD, AUTO))}
+    checked = carried = 0
+    for mode in (KD, GRID, HOSTBUILD, AUTO):
+        arr[at['mode']] = mode
+        for bits in itertools.product((0, 1), repeat=len(flags)):
+            d = dict(zip(flags, bits))
+            for k, v in d.items():
+                arr[at[k]] = v
+            by_more = {}
+            for S in range(1, 7):
+                for s in range(S):
+                    arr[at['step']], arr[at['steps']] = s, S
+                    H.forms_plan_step(arr, out)
+                    moved, ahead, fork = out
+                    assert by_more.setdefault(s + 1 < S, (moved, ahead, fork)) == (moved, ahead, fork), (mode, d, s, S)
+                    assert not (ahead and fork) and (s + 1 < S or (moved, ahead, fork) == (0, 0, 0)), (mode, d, s, S)
+                    assert not moved or (d['ext_stop'] and d['kd_stream']), (mode, d)
+                    assert not fork or (d['ext_stop'] and d['trk_fork']), (mode, d)
+                    # the update of this step, in every scene / harvest form (the shard and the partition are the step's own flags)
+                    # (fork: what the loop hands to the pass of step s + 1 as "the fork is ready")
+                    for scenes, obs, harvest in ((0, 0, 0), (1, 0, 0), (1, 1, 1), (0, 0, 1)):
+                        k4, carrier, hv, others = fin[(scenes, obs, harvest, d['part_on'], 1 - d['whole'], GRID if mode in (GRID, AUTO) else mode)]
+                        launched = {ON_K4: 1, ON_HARVEST: hv, ON_OTHERS: others}
+                        carriers = [kern for kern in (ON_K4, ON_HARVEST, ON_OTHERS) if fork and carrier == kern and launched[kern]]
+                        assert len(carriers) == (1 if fork else 0), (mode, d, scenes, obs, harvest)
+                        assert not fork or carriers[0] == (ON_OTHERS if others else ON_HARVEST if hv else ON_K4)      # ... and it is the step's LAST kernel
+                    carried += fork
+                    checked += 1
+                assert not fork                                                                # nothing is left over for the next call
+    assert checked == 4 * 2 ** len(flags) * 21 and carried > 1000
+
+
+def test_step_refusals_say_what_they_said_in_the_order_they_were_made(H):
+    """step_check / step_fault_text against the literals of sca_run_steps, sca_step_begin and sca_step_host as they stood (state, steps, mode,
+    several ranks, the partition's mode -- in this order); each entry point's mask picks its own."""
+    STATE, STEPS, MODE, RANKS, PART_MODE, ALL = 1, 2, 4, 8, 16, 31
+    RANKS_TEXT = ('cell-owner partition over several ranks: drive the step with sca_step_begin / sca_partition_pack / [exchange] / '
+                  'sca_partition_unpack / sca_partition_commit / sca_step_end (sca_amd.distributed.PartitionedStepper)')
+    ARG, ST, UNSUPPORTED = -1, -3, -5
+
+    def check(checks, state=1, steps=1, mode=KD, part=0, apart=0):
+        out, text = (C.c_int * 2)(), C.create_string_buffer(256)
+        H.forms_step_check(checks, state, steps, mode, part, apart, out, text, 256)
+        assert out[1] == len(text.value)
+        return out[0], text.value.decode()
+    assert check(ALL) == (0, '') and check(ALL, steps=0, mode=AUTO) == (0, '')
+    assert check(ALL, state=0, steps=-1, mode=7, part=1, apart=1) == (ST, 'sca_set_state first')
+    assert check(ALL, steps=-1, mode=7, part=1, apart=1) == (ARG, 'steps must not be negative')
+    assert [check(ALL, steps=0, mode=m, part=1, apart=1) for m in (-1, 4)] == [(UNSUPPORTED, 'neighbor mode not available in this build')] * 2
+    assert check(ALL, mode=KD, part=1, apart=1) == (ST, RANKS_TEXT) and check(ALL, mode=GRID, part=1, apart=1) == (ST, RANKS_TEXT)
+    assert check(ALL, mode=GRID, part=0, apart=1) == (0, '')
+    assert [check(ALL, mode=m, part=1) for m in (KD, HOSTBUILD, AUTO)] == [(UNSUPPORTED, 'the cell-owner partition is a mode of SCA_NBR_GRID')] * 3
+    assert check(ALL, mode=GRID, part=1) == (0, '')
+    # sca_step_begin: the state and the partition's mode; a mode out of range is the pass's to refuse, behind its first launches as ever
+    assert check(STATE | PART_MODE, state=0, mode=7, part=1) == (ST, 'sca_set_state first')
+    assert check(STATE | PART_MODE, mode=7) == (0, '') and check(STATE | PART_MODE, steps=-1, part=1, apart=1, mode=GRID) == (0, '')
+    assert check(STATE | PART_MODE, mode=AUTO, part=1) == (UNSUPPORTED, 'the cell-owner partition is a mode of SCA_NBR_GRID')
+    # sca_policy_pass, sca_env_update, sca_active_count: the state alone; sca_step_host: the mode alone, under its own name
+    assert check(STATE, state=0) == (ST, 'sca_set_state first') and check(STATE, steps=-1, mode=7, part=1, apart=1) == (0, '')
+    assert check(MODE, state=0, steps=-1, mode=4, part=1, apart=1) == (UNSUPPORTED, 'neighbor mode not available in this build')
+    assert check(MODE, state=0, steps=-1, mode=AUTO, part=1, apart=1) == (0, '') and check(0, state=0, steps=-1, mode=9, part=1, apart=1) == (0, '')
+    src = open(os.path.join(CSRC, 'sca_hip.hip')).read()
+    assert 'step_refuse(c, "sca_step_host: ", STEP_CHK_MODE, 0, neighbor_mode)' in src
+    counts = {'"sca_set_state first"': 1, '"steps must not be negative"': 0, '"the cell-owner partition is a mode of SCA_NBR_GRID"': 0, 'CLR_UPDATE': 1}
+    for literal, times in counts.items():                                                      # one place each (sca_get_scene_state keeps a text of its own)
+        assert src.count(literal) == times, literal
+    for member in ('action_stop', 'finish_stop', 'fork_ready'):
+        assert not re.search(r'c->' + member + r'\b', src), member                              # arguments, no longer members of the context
+
+
 def test_forms_harness_standalone_under_sanitizers():
     """the plan functions as a program of their own (FORMS_MAIN: every entry point into heap arrays of exactly the documented length, the two
     AUTO plans over every slot state on both sides of the wrap) under -fsanitize=address,undefined.  Host code only; nothing of it is loaded
