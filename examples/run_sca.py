@@ -49,11 +49,14 @@ def lifelong(args, agents, obstacles, pol, dubins):
         return E.Agent(start_pos=start, goal_pos=goal, vel=[0.0, 0.0, 0.0], radius=agent.radius, pref_speed=agent.pref_speed, policy=pol, id=agent.id)
 
     t0 = time.time()
-    stats = run_lifelong(env, next_mission, args.lifelong)
+    stats = run_lifelong(env, next_mission, args.lifelong) if args.spawn_margin is None else \
+        run_lifelong(env, next_mission, args.lifelong, spawn_margin=args.spawn_margin)
     cost = time.time() - t0
     missions = stats['arrived'] + stats['collided'] + stats['timed_out']
     print('lifelong:', stats['steps'], 'steps,', f'{cost:.2f} s,', missions, 'missions,', f'{missions / cost:.1f} missions/s')
     print({k: stats[k] for k in ('arrived', 'collided', 'timed_out', 'respawned', 'retired', 'agent_steps')}, f"live fraction {stats['live_fraction']:.3f}")
+    if args.spawn_margin is not None:
+        print('spawn margin', args.spawn_margin, 'm:', stats['deferred'], 'refusals,', stats['waiting'], 'missions still waiting')
 
 
 def main():
@@ -74,6 +77,9 @@ def main():
     ap.add_argument('--lifelong', type=int, default=0, metavar='STEPS',
                     help='continuous traffic for STEPS steps instead of one episode: a drone that arrives flies back, one that collided or '
                          'timed out starts again from its original start (MACAEnv.respawn; the Dubins tracker then runs on the device)')
+    ap.add_argument('--spawn-margin', type=float, default=None, metavar='M',
+                    help='with --lifelong: a drone is respawned only where its start is free by M metres (of every other drone, of every '
+                         'obstacle and of the drones admitted with it); otherwise its mission waits and is offered again after every step')
     args = ap.parse_args()
 
     n = args.agents

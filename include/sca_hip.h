@@ -684,6 +684,56 @@ int sca_respawn_agents(sca_ctx *ctx, int count, const int32_t *ids /*count*/, co
                        const double *path_points /*nullable*/);
 int sca_get_finished(sca_ctx *ctx, sca_finished_row *rows /*capacity*/, int capacity, int *count, int32_t struct_bytes);
 
+/* Spawn admission: how free is this point NOW, and respawning only the rows whose start is free.  sca_respawn_agents puts a drone wherever
+ * it is told to, also inside another one; the closest-approach records (sca_clearance_enable) cover the agents' own positions inside a
+ * step, from a tree that is one step old.  A spawn test needs arbitrary points, between two steps, against the records as they are now --
+ * right after a respawn or a sca_set_state too, and in SCA_NBR_GRID mode, where there is no agent tree at all.
+ *   the rule   query q is a sphere of radius[q] at pos[q].  out[q].agent_clear is the smallest c = l3norm(p_q, p_b) - (r_q + r_b) over
+ *              every agent row b of the context except ignore[q] (-1, or a NULL ignore: nobody is excluded): p_b and r_b from the row's
+ *              current public record whatever its flags, l3norm the reference's rounded norm, the radius sum formed first;
+ *              agent_partner is the lowest id with that value.  The same over the obstacles in set order.  Both step fields are 0, an
+ *              empty half is +inf, -1, 0.  For a query at agent a's own position and radius with ignore = a this is that agent's
+ *              candidate of the closest-approach rule.
+ *   the search brute force over the records, on purpose: between two steps the agent tree has no known age (a respawn or a new state has
+ *              moved rows arbitrarily, an AUTO burst may have built ahead, the grid has no tree); the records are the one thing that is
+ *              right at every legal call point.  The partners (agents, then obstacles) are cut into fixed tiles, the queries into
+ *              chunks of 64 -- one per lane; k_spawn_probe stages a tile in LDS and leaves one partial per (tile, query), k_spawn_reduce
+ *              folds them into a page-locked block.  No atomics: the minimum on (c, id) depends neither on the tiling nor on the
+ *              scheduling.  The scratch is allocated at the first call and grows like the respawn block; a context that never probes
+ *              allocates and enqueues nothing new.  One synchronisation per call.
+ *   sca_probe_clearance   legal between two steps, in every neighbour mode, with or without the tracker, lists and records; changes
+ *              nothing.  SCA_ERR_STATE: no agents, no state yet, between a policy pass and its env update.  SCA_ERR_ARG: count <= 0, a
+ *              NULL pos, radius or out, a position that is not finite, a radius that is negative or not finite (0 is a point probe), an
+ *              ignore outside -1 .. n-1, struct_bytes other than sizeof(sca_scene_clearance).  SCA_ERR_UNSUPPORTED, as for
+ *              sca_respawn_agents: scenes, a shard with count < n, a communicator, the cell-owner partition.
+ *   sca_respawn_agents_gated   sca_respawn_agents' arguments, then a margin, the verdict per named row, (nullable) the world test's
+ *              records and (nullable) the number of admitted rows.  With the rows in the call's order:
+ *              world test  row r probes pos[r] / radius[r] with ignore = ids[r]: every other agent row at its current record -- the
+ *                          other named rows where they stand NOW, a refused row stays a body -- and every obstacle.  r is world-clear
+ *                          where neither half is <= margin (an empty half never blocks).
+ *              entry test  for every EARLIER row r' < r of the call that is world-clear, c = l3norm(pos[r], pos[r']) - (radius[r] +
+ *                          radius[r']); r is blocked where any such c <= margin.  An earlier row the world blocked blocks nobody.  A
+ *                          conservative, fully parallel and deterministic stand-in for the sequential greedy: in a chain a < b < c where
+ *                          b conflicts with both, c is refused although b was.
+ *              verdict     the first that applies: SCA_SPAWN_BLOCKED_AGENT, SCA_SPAWN_BLOCKED_OBSTACLE, SCA_SPAWN_BLOCKED_ENTRY, else
+ *                          SCA_SPAWN_ADMITTED.
+ *              Afterwards every device and host word is what sca_respawn_agents leaves when it names exactly the admitted rows, in the
+ *              call's order, with their arrays (the waypoint CSR cut down to them); a refused row keeps every word it had; a call that
+ *              admits nobody changes nothing and returns SCA_OK.  The probe, the fold, the gate (k_spawn_gate: a wavefront per row over
+ *              the earlier rows) and k_respawn run on the context's stream behind ONE synchronisation.  Refusals: everything
+ *              sca_respawn_agents refuses, with the same codes; SCA_ERR_ARG for a margin that is negative or not finite and for a NULL
+ *              verdict.
+ * Detect the feature by the symbols (the version number is unchanged). */
+enum sca_spawn_verdict { SCA_SPAWN_ADMITTED = 0, SCA_SPAWN_BLOCKED_AGENT = 1, SCA_SPAWN_BLOCKED_OBSTACLE = 2, SCA_SPAWN_BLOCKED_ENTRY = 3 };
+int sca_probe_clearance(sca_ctx *ctx, int count, const double *pos /*count*3*/, const double *radius /*count*/,
+                        const int32_t *ignore /*count, nullable*/, sca_scene_clearance *out /*count*/, int32_t struct_bytes);
+int sca_respawn_agents_gated(sca_ctx *ctx, int count, const int32_t *ids /*count*/, const double *pos /*count*3*/, const float *vel /*count*3*/,
+                             const double *heading /*count*3*/, const double *radius /*count*/, const double *pref_speed /*count*/,
+                             const double *goal /*count*3*/, const uint8_t *zaxis /*count, nullable*/, const double *max_run_dist /*count*/,
+                             const double *goal_heading /*count*3, nullable*/, const int32_t *path_offsets /*count+1, nullable*/,
+                             const double *path_points /*nullable*/, double margin, int32_t *verdict /*count*/,
+                             sca_scene_clearance *probe /*count, nullable*/, int32_t *admitted /*nullable: how many*/);
+
 /* the hot path ----------------------------------------------------------------------------------- */
 int sca_policy_pass(sca_ctx *ctx, int neighbor_mode);
 int sca_get_actions(sca_ctx *ctx, float *action /*n*7*/);

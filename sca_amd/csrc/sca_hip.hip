@@ -31,6 +31,8 @@
 #include "sca_clearance.hip.h"
 #include "sca_respawn.h"
 #include "sca_respawn.hip.h"
+#include "sca_spawn.h"
+#include "sca_spawn.hip.h"
 
 using namespace sca;
 
@@ -359,6 +361,12 @@ struct sca_ctx {
     uint8_t *fin_host = nullptr;            // sca_get_finished's page-locked block: the count's head, fin_cap rows behind it
     int fin_cap = 0;
     int32_t *fin_counts = nullptr;          // device [2 * tiles of max_n]: the tiles' counts, their offsets behind them
+    // spawn admission (sca_probe_clearance, sca_respawn_agents_gated; sca_spawn.h): nothing of it exists until the first call
+    uint8_t *spn_host = nullptr;            // the page-locked block (SpawnLayout of spn_cap queries)
+    uint8_t *spn_dev = nullptr;             // device: the copy of the block's query sections, the world words and the verdict words behind it
+    int spn_cap = 0;
+    SpawnPartial *spn_partials = nullptr;   // device [tiles][spn_cap]
+    int64_t spn_partials_room = 0;          // ... how many it has room for
 };
 
 #define CHK(ctx, call)                                                                         \
@@ -994,6 +1002,9 @@ void sca_destroy(sca_ctx *c) {
     if (c->rsp_host) { (void)hipHostFree(c->rsp_host); c->rsp_host = nullptr; }
     if (c->fin_host) { (void)hipHostFree(c->fin_host); c->fin_host = nullptr; }
     if (c->fin_counts) { (void)hipFree(c->fin_counts); c->fin_counts = nullptr; }
+    if (c->spn_host) { (void)hipHostFree(c->spn_host); c->spn_host = nullptr; }
+    if (c->spn_dev) { (void)hipFree(c->spn_dev); c->spn_dev = nullptr; }
+    if (c->spn_partials) { (void)hipFree(c->spn_partials); c->spn_partials = nullptr; }
     if (c->ap_dev) { (void)hipFree(c->ap_dev); (void)hipFree(c->ap_nd); c->ap_dev = nullptr; c->ap_nd = nullptr; }
     void *ptrs[] = {c->rec_own, c->rec_new_own, d.heading, d.goal, d.pref_speed, d.vpref_ext, d.total_dist, d.max_run_dist,
                     d.step_num, d.vpref_mode, d.policy, d.zaxis, d.obs, d.obs_sorted, d.awide, d.owide, d.atree, d.aperm, d.otree, d.operm, d.nbr_n,
@@ -3898,6 +3909,88 @@ static int respawn_refuse(sca_ctx *c, const char *who, RespawnFault f, int entry
     return respawn_error_code(f);
 }
 static_assert(sizeof(sca_finished_row) == FINISHED_ROW_BYTES, "sca_finished_row is 48 bytes");
+// ---- spawn admission (include/sca_hip.h; the rules, the tiling and the block are sca_spawn.h's, the kernels sca_spawn.hip.h's) --------------
+static int spawn_refuse(sca_ctx *c, const char *who, SpawnFault f, int entry) {
+    const std::string w = std::string(who), at = std::to_string(entry);
+    switch (f) {
+    case SPF_OK: return 0;
+    case SPF_NO_AGENTS: c->err = w + ": sca_set_agents first"; break;
+    case SPF_NO_STATE: c->err = w + ": no state yet -- sca_set_state first"; break;
+    case SPF_MID_STEP: c->err = w + " between a policy pass and its env update: finish the step first"; break;
+    case SPF_BAD_COUNT: c->err = w + ": count must be positive"; break;
+    case SPF_NO_ARRAYS: c->err = w + ": pos, radius and out must not be NULL"; break;
+    case SPF_NOT_FINITE: c->err = w + ": query " + at + " has a position that is not finite"; break;
+    case SPF_BAD_RADIUS: c->err = w + ": query " + at + " has a radius that is negative or not finite"; break;
+    case SPF_BAD_IGNORE: c->err = w + ": ignore[" + at + "] is neither -1 nor an agent of this context (0 .. " + std::to_string(c->n - 1) + ")"; break;
+    case SPF_BAD_STRUCT: c->err = w + ": struct_bytes must be sizeof(sca_scene_clearance) = " + std::to_string(sizeof(sca_scene_clearance)); break;
+    case SPF_BAD_MARGIN: c->err = w + ": margin must be finite and not negative"; break;
+    case SPF_NO_VERDICT: c->err = w + ": verdict must not be NULL"; break;
+    case SPF_SCENES: c->err = w + " with scenes set (sca_set_scenes): probing per scene is not supported"; break;
+    case SPF_SHARD: c->err = w + " on a shard with count < n (sca_set_shard): the probe reads the records of the whole swarm on one rank"; break;
+    case SPF_COMM: c->err = w + " with an active communicator: the probe reads the records of the whole swarm on one rank (sca_comm_destroy first)"; break;
+    default: c->err = w + " under the cell-owner partition: the rows' state does not follow the owners (sca_partition_disable first)";
+    }
+    return spawn_error_code(f);
+}
+// the block and the scratch for `count` queries against the records as they are: allocated on first use, grown like the respawn block
+static int spawn_room(sca_ctx *c, int count) {
+    if (count > c->spn_cap) {
+        const int cap = std::max(count, std::max(1024, 2 * c->spn_cap));
+        const SpawnLayout L = spawn_layout(cap);
+        uint8_t *blk = nullptr, *dev = nullptr;
+        CHK(c, hipHostMalloc((void **)&blk, (size_t)L.total, hipHostMallocMapped | hipHostMallocCoherent));
+        if (hipMalloc((void **)&dev, (size_t)L.off[SPB_OUT] + 2 * sizeof(int32_t) * (size_t)cap) != hipSuccess) { (void)hipHostFree(blk); c->err = "spawn admission: no device memory for the queries"; return SCA_ERR_HIP; }
+        if (c->spn_host) (void)hipHostFree(c->spn_host);              // (every call ends with its synchronisation: no launch still uses them)
+        if (c->spn_dev) (void)hipFree(c->spn_dev);
+        c->spn_host = blk; c->spn_dev = dev; c->spn_cap = cap;
+    }
+    const int64_t want = spawn_partials(c->n, c->d.m, spawn_batch_room(c->spn_cap), SPAWN_TILE);
+    if (want > c->spn_partials_room) {
+        SpawnPartial *p = nullptr;
+        CHK(c, hipMalloc((void **)&p, sizeof(SpawnPartial) * (size_t)want));
+        if (c->spn_partials) (void)hipFree(c->spn_partials);
+        c->spn_partials = p; c->spn_partials_room = want;
+    }
+    return 0;
+}
+// the queries are in the block: their copy to the device, k_spawn_probe, k_spawn_reduce and, gated, k_spawn_gate on c->stream, no synchronisation
+static int spawn_enqueue(sca_ctx *c, int count, bool gated, double margin, SpawnDev &s) {
+    const SpawnLayout L = spawn_layout(c->spn_cap);
+    s = SpawnDev{};
+    s.rec = c->d.rec; s.obs = c->d.obs;
+    s.query = (const ClearPoint *)(c->spn_dev + L.off[SPB_QUERY]); s.ignore = (const int32_t *)(c->spn_dev + L.off[SPB_IGNORE]);
+    s.partials = c->spn_partials;
+    s.world = (int32_t *)(c->spn_dev + L.off[SPB_OUT]); s.verdict = s.world + c->spn_cap;
+    s.n = c->n; s.m = c->d.m; s.tiles = spawn_tiles(c->n, c->d.m, SPAWN_TILE);
+    s.cap = spawn_batch_room(c->spn_cap);
+    CHK(c, hipMemcpyAsync(c->spn_dev, c->spn_host, (size_t)L.off[SPB_IGNORE] + sizeof(int32_t) * (size_t)count, hipMemcpyHostToDevice, c->stream));
+    for (int first = 0; first < count; first += SPAWN_BATCH) {        // (stream order: a batch's fold has read the partials before the next probe writes them)
+        s.first = first; s.count = std::min(SPAWN_BATCH, count - first);
+        hipLaunchKernelGGL(k_spawn_probe, dim3(s.tiles, spawn_chunks(s.count)), dim3(SPAWN_WAVES * 64), 0, c->stream, s);
+        hipLaunchKernelGGL(k_spawn_reduce, dim3((s.count + 255) / 256), dim3(256), 0, c->stream, s, c->spn_host, L, margin, gated ? 1 : 0);
+    }
+    s.first = 0; s.count = count;
+    if (gated) hipLaunchKernelGGL(k_spawn_gate, dim3((count + SPAWN_GATE_WAVES - 1) / SPAWN_GATE_WAVES), dim3(SPAWN_GATE_WAVES * 64), 0, c->stream, s, c->spn_host, L, margin);
+    CHK(c, hipGetLastError());
+    return 0;
+}
+int sca_probe_clearance(sca_ctx *c, int count, const double *pos, const double *radius, const int32_t *ignore, sca_scene_clearance *out, int32_t struct_bytes) {
+    API_ENTER(c);
+    const SpawnCheck k = spawn_check(respawn_ctx(c), count, pos, radius, ignore, out != nullptr, struct_bytes);
+    if (int r = spawn_refuse(c, "sca_probe_clearance", k.fault, k.entry)) return r;
+    if (int r = spawn_room(c, count)) return r;
+    const SpawnLayout L = spawn_layout(c->spn_cap);
+    spawn_pack(c->spn_host, L, count, pos, radius, ignore);
+    SpawnDev s;
+    if (int r = spawn_enqueue(c, count, false, 0.0, s)) return r;
+    CHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(out, c->spn_host + L.off[SPB_OUT], sizeof(sca_scene_clearance) * (size_t)count);
+    return 0;
+}
+
+// sca_respawn_agents and sca_respawn_agents_gated (gate != nullptr) behind their refusals
+struct RespawnGate { double margin; int32_t *verdict; sca_scene_clearance *probe; int32_t *admitted; };
+static int respawn_run(sca_ctx *c, const RespawnCtx &X, const RespawnArgs &A, const RespawnGate *gate);
 int sca_respawn_agents(sca_ctx *c, int count, const int32_t *ids, const double *pos, const float *vel, const double *heading, const double *radius,
                        const double *pref_speed, const double *goal, const uint8_t *zaxis, const double *max_run_dist, const double *goal_heading,
                        const int32_t *path_offsets, const double *path_points) {
@@ -3906,6 +3999,27 @@ int sca_respawn_agents(sca_ctx *c, int count, const int32_t *ids, const double *
     const RespawnArgs A{count, ids, pos, vel, heading, radius, pref_speed, goal, zaxis, max_run_dist, goal_heading, path_offsets, path_points};
     const RespawnCheck k = respawn_check(X, A);
     if (int r = respawn_refuse(c, "sca_respawn_agents", k.fault, k.entry)) return r;
+    return respawn_run(c, X, A, nullptr);
+}
+int sca_respawn_agents_gated(sca_ctx *c, int count, const int32_t *ids, const double *pos, const float *vel, const double *heading, const double *radius,
+                             const double *pref_speed, const double *goal, const uint8_t *zaxis, const double *max_run_dist, const double *goal_heading,
+                             const int32_t *path_offsets, const double *path_points, double margin, int32_t *verdict, sca_scene_clearance *probe,
+                             int32_t *admitted) {
+    API_ENTER(c);
+    const RespawnCtx X = respawn_ctx(c);
+    const RespawnArgs A{count, ids, pos, vel, heading, radius, pref_speed, goal, zaxis, max_run_dist, goal_heading, path_offsets, path_points};
+    const RespawnCheck k = respawn_check(X, A);
+    if (int r = respawn_refuse(c, "sca_respawn_agents_gated", k.fault, k.entry)) return r;
+    if (int r = spawn_refuse(c, "sca_respawn_agents_gated", spawn_gate_check(margin, verdict != nullptr), -1)) return r;
+    const RespawnGate gate{margin, verdict, probe, admitted};
+    return respawn_run(c, X, A, &gate);
+}
+static int respawn_run(sca_ctx *c, const RespawnCtx &X, const RespawnArgs &A, const RespawnGate *gate) {
+    const int count = A.count;
+    const int32_t *ids = A.ids, *path_offsets = A.path_offsets;
+    const double *pos = A.pos, *heading = A.heading, *radius = A.radius, *pref_speed = A.pref_speed;
+    const float *vel = A.vel;
+    if (gate) if (int r = spawn_room(c, count)) return r;
     // the block: page-locked, mapped and coherent as the restart block is -- the kernel reads it in place.  It grows when a call names more
     // rows than any before it (at once to 1024 rows or twice the last size, at most max_agents) or a larger room per row has arrived
     if (count > c->rsp_cap || X.path_W != c->rsp_W) {
@@ -3931,12 +4045,32 @@ int sca_respawn_agents(sca_ctx *c, int count, const int32_t *ids, const double *
     d.clear = c->clear;
     d.n = c->n;
     // on c->stream, behind every reader of the rows: a step's kernels run there or on streams the step joins back before it ends
-    hipLaunchKernelGGL(k_respawn, dim3((count + RESPAWN_WAVES - 1) / RESPAWN_WAVES), dim3(RESPAWN_WAVES * 64), 0, c->stream, d, (const uint8_t *)c->rsp_host, L, has, count);
+    // the gate in front of it: the world test of every named start (the row itself ignored), the entry test among the call's rows
+    SpawnDev sd{};
+    SpawnLayout SL{};
+    if (gate) {
+        SL = spawn_layout(c->spn_cap);
+        spawn_pack(c->spn_host, SL, count, pos, radius, ids);
+        if (int r = spawn_enqueue(c, count, true, gate->margin, sd)) return r;
+    }
+    hipLaunchKernelGGL(k_respawn, dim3((count + RESPAWN_WAVES - 1) / RESPAWN_WAVES), dim3(RESPAWN_WAVES * 64), 0, c->stream, d, (const uint8_t *)c->rsp_host, L, has, count,
+                       (const int32_t *)(gate ? sd.verdict : nullptr));
     CHK(c, hipGetLastError());
     CHK(c, hipStreamSynchronize(c->stream));
-    // the device has the new missions: the host mirrors follow (a refused call has left them alone)
+    const int32_t *verdict = nullptr;
+    if (gate) {
+        verdict = (const int32_t *)(c->spn_host + SL.off[SPB_VERDICT]);
+        int in = 0;
+        for (int r = 0; r < count; r++) in += verdict[r] == SCA_SPAWN_ADMITTED;
+        std::memcpy(gate->verdict, verdict, sizeof(int32_t) * (size_t)count);
+        if (gate->probe) std::memcpy(gate->probe, c->spn_host + SL.off[SPB_OUT], sizeof(sca_scene_clearance) * (size_t)count);
+        if (gate->admitted) *gate->admitted = in;
+        if (in == 0) return 0;                                         // nobody admitted: nothing has changed, on the device or here
+    }
+    // the device has the new missions: the host mirrors follow the rows that were written (a refused call has left them alone)
     const HostLayout HL = host_state_layout(c->n);
     for (int r = 0; r < count; r++) {
+        if (verdict && verdict[r] != SCA_SPAWN_ADMITTED) continue;
         const int a = ids[r];
         c->h_rec[a].radius = radius[r];
         c->max_radius = std::max(c->max_radius, radius[r]);           // the envelope only grows (conservative filters, as under the restarts)

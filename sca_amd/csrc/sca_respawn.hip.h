@@ -38,10 +38,13 @@ struct RespawnDev {
     int n;
 };
 constexpr int RESPAWN_WAVES = 4;
-__global__ __launch_bounds__(RESPAWN_WAVES * 64) void k_respawn(RespawnDev d, const uint8_t *blk, RespawnLayout L, uint32_t has, int count) {
+// verdict (nullable): the gated call's word per named row (sca_spawn.h) -- a row whose word is not 0 returns before it touches anything,
+// its done_count stripe included; null: every named row is written.
+__global__ __launch_bounds__(RESPAWN_WAVES * 64) void k_respawn(RespawnDev d, const uint8_t *blk, RespawnLayout L, uint32_t has, int count, const int32_t *verdict) {
     const int lane = (int)threadIdx.x & 63;
     const int r = (int)blockIdx.x * RESPAWN_WAVES + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);     // wave-uniform
     if (r >= count) return;
+    if (verdict && verdict[r] != 0) return;                            // (wave-uniform: one row per wavefront)
     const int a = ((const int32_t *)(blk + L.off[RSB_IDS]))[r];
     if (a < 0 || a >= d.n) return;                                     // (the host has checked the ids: never taken)
     const bool lists = (has & RESPAWN_HAS_PATHS) != 0;

@@ -520,19 +520,33 @@ class MACAEnv(_FlatAgents):
         self.solver.set_path_slots(self._path_slots, lists)
 
     # ---- new missions without redefining the swarm (sca_respawn_agents / sca_get_finished) ---------------------------------
-    def respawn(self, agents):
+    def probe(self, pos, radius, ignore=None):
+        """How free is each point now (sca_probe_clearance): spheres of `radius` at `pos` (Q, 3) against every agent where it stands --
+        but ignore[q], None or -1: nobody is excluded -- and every obstacle.  A structured array of _lib.CLEARANCE_DTYPE (agent_clear,
+        obs_clear, agent_partner, obs_partner; an empty half is +inf, -1).  Between two env.step() calls; changes nothing."""
+        if self.agents is None:
+            raise RuntimeError('probe: set_agents first')
+        if self._row_cache is not None:
+            raise RuntimeError('probe: between a policy pass and its env update (agent.find_next_action was called): env.step() first')
+        return self.solver.probe_clearance(pos, radius, ignore)
+
+    def respawn(self, agents, margin=None):
         """New missions for some agents while everybody else flies on: each Agent of `agents` replaces env.agents[agent.id] -- the
         reference's rule for assigning pos_global_frame, goal_global_frame, is_at_goal = False, ... to an Agent object between two
         env.step() calls.  Start, goal, velocity, radius, pref_speed, max_run_dist, goal heading, path and the z-axis flag are read off
         the agent as set_agents reads them; the row keeps its policy and its per-agent attributes, so an agent whose policy or
-        attributes differ from the row's is a ValueError, raised before any device call.  A path needs MACAEnv(path_slots=W)."""
+        attributes differ from the row's is a ValueError, raised before any device call.  A path needs MACAEnv(path_slots=W).
+        margin (None: no gate, returns None): only the agents whose start is free by `margin` metres are admitted
+        (sca_respawn_agents_gated: clear of every other agent where it stands now, of every obstacle, and of the admitted agents earlier
+        in `agents`); they replace their rows and are returned as a list, `last_spawn` holds (verdict, probe) of the call; a refused
+        agent leaves env.agents and its row untouched."""
         if self.agents is None:
             raise RuntimeError('respawn: set_agents first')
         if self._row_cache is not None:
             raise RuntimeError('respawn: between a policy pass and its env update (agent.find_next_action was called): env.step() first')
         agents = list(agents)
         if not agents:
-            return
+            return None if margin is None else []
         n = len(self.agents)
         ids = [int(a.id) for a in agents]
         if min(ids) < 0 or max(ids) >= n or len(set(ids)) != len(ids):
@@ -560,9 +574,16 @@ class MACAEnv(_FlatAgents):
         start = np.array([a.initial_pos for a in agents], dtype=np.float64)
         goal6 = np.array([a.goal_pos for a in agents], dtype=np.float64)
         lists = [[list(map(float, w[:3])) for w in a._path] for a in agents] if self._paths_on else None
-        self.solver.respawn(ids, [a._pos for a in agents], [a._vel for a in agents], [a._heading for a in agents], [a.radius for a in agents],
-                            [a.pref_speed for a in agents], goal6[:, :3], [a.max_run_dist for a in agents], zaxis=S.zaxis_flags(start, goal6),
-                            goal_heading=goal6[:, 3:6] if self._trk_on else None, paths=lists)
+        got = self.solver.respawn(ids, [a._pos for a in agents], [a._vel for a in agents], [a._heading for a in agents], [a.radius for a in agents],
+                                  [a.pref_speed for a in agents], goal6[:, :3], [a.max_run_dist for a in agents], zaxis=S.zaxis_flags(start, goal6),
+                                  goal_heading=goal6[:, 3:6] if self._trk_on else None, paths=lists, margin=margin)
+        if margin is not None:
+            self.last_spawn = got
+            admitted = got[0] == S.SPAWN_ADMITTED
+            agents = [a for a, ok in zip(agents, admitted) if ok]
+            was_done = was_done[admitted]
+            if not agents:
+                return []
         for a in agents:
             if self.agents[a.id] is not a:
                 self.agents[a.id]._env = None                    # (the replaced object reads its own attributes again)
@@ -575,6 +596,7 @@ class MACAEnv(_FlatAgents):
         self._path_stale = self._paths_on
         self._nbr_cache = None
         self._vpref_cache = None
+        return None if margin is None else agents
 
     def finished(self, capacity=None):
         """The rows that carry any of at-goal / collision / timeout, ascending ids, compacted on the device (sca_get_finished): a

@@ -1,21 +1,31 @@
 """Continuous traffic on one MACAEnv: drones land, new ones take off (MACAEnv.respawn / MACAEnv.finished).
 
-    stats = run_lifelong(env, next_mission, steps, on_done=None)
+    stats = run_lifelong(env, next_mission, steps, on_done=None, spawn_margin=None)
 
 steps the env; whenever the number of running agents dropped it reads the finished rows from the device (sca_get_finished: only those
 rows cross the link), hands each to on_done(agent, row) and respawns it with the Agent next_mission(agent, row) returns -- None retires
 the agent, which then stays where it is for the rest of the run.  `row` is one record of _lib.FINISHED_DTYPE (id, flags, step_num,
-total_dist, pos)."""
+total_dist, pos).
+
+spawn_margin (metres): an admission gate in front of every respawn (MACAEnv.respawn(margin=), sca_respawn_agents_gated) -- a mission
+whose start is not free by that margin WAITS: its row stays finished where it is, and the mission is offered again in front of every
+later step, together with that step's new ones, waiting ones first, in ascending id."""
 from . import solver as S
 
 
-def run_lifelong(env, next_mission, steps, on_done=None):
+def run_lifelong(env, next_mission, steps, on_done=None, spawn_margin=None):
     """Returns dict(steps, arrived, collided, timed_out: missions that ended that way (a collision wins over an arrival, an arrival over a
     time-out), respawned, retired, agent_steps: agents served summed over the steps, live_fraction: agent_steps / (agents x steps)).
-    The run ends early when every agent is retired."""
+    The run ends early when every agent is retired.  With spawn_margin the dict gains `deferred`, the refusals counted per attempt, and
+    `waiting`, the missions still pending at the end: arrived + collided + timed_out == respawned + retired + waiting; the run then ends
+    early too when nobody runs: the world is then still, and who waits would wait for ever."""
     n = len(env.agents)
     stats = dict(steps=0, arrived=0, collided=0, timed_out=0, respawned=0, retired=0, agent_steps=0, live_fraction=0.0)
+    gated = spawn_margin is not None
+    if gated:
+        stats.update(deferred=0, waiting=0)
     retired = set()
+    waiting = {}                                                 # id -> the Agent whose start was not free
     active = env._active
     for _ in range(int(steps)):
         if active == 0:
@@ -23,11 +33,11 @@ def run_lifelong(env, next_mission, steps, on_done=None):
         stats['agent_steps'] += active
         env.step()
         stats['steps'] += 1
+        new = []
         if env._active < active:                                 # somebody finished in this step
-            new = []
             for row in env.finished():
                 i = int(row['id'])
-                if i in retired:
+                if i in retired or i in waiting:
                     continue
                 f = int(row['flags'])
                 stats['collided' if f & S.FLAG_COLLISION else 'arrived' if f & S.FLAG_AT_GOAL else 'timed_out'] += 1
@@ -40,9 +50,20 @@ def run_lifelong(env, next_mission, steps, on_done=None):
                     stats['retired'] += 1
                 else:
                     new.append(nxt)
-            if new:
-                env.respawn(new)
-                stats['respawned'] += len(new)
+        if gated:
+            offer = [waiting[i] for i in sorted(waiting)] + new  # the waiting ones first, in ascending id, then this step's new ones
+            if offer:
+                admitted = env.respawn(offer, margin=spawn_margin)
+                stats['respawned'] += len(admitted)
+                stats['deferred'] += len(offer) - len(admitted)
+                waiting = {a.id: a for a in offer}
+                for a in admitted:
+                    del waiting[a.id]
+        elif new:
+            env.respawn(new)
+            stats['respawned'] += len(new)
         active = env._active
+    if gated:
+        stats['waiting'] = len(waiting)
     stats['live_fraction'] = stats['agent_steps'] / float(n * stats['steps']) if stats['steps'] else 0.0
     return stats

@@ -12,6 +12,7 @@ from . import _lib
 
 POL_SCA, POL_RVO3D, POL_SRVO3D, POL_ORCA3D, POL_ORCA3D_LP, POL_RVO3D_DUBINS = range(6)
 FLAG_AT_GOAL, FLAG_COLLISION, FLAG_TIMEOUT = 1, 2, 4
+SPAWN_ADMITTED, SPAWN_BLOCKED_AGENT, SPAWN_BLOCKED_OBSTACLE, SPAWN_BLOCKED_ENTRY = 0, 1, 2, 3      # SCA_SPAWN_*: a gated respawn's verdict per row
 NBR_KDTREE, NBR_GRID, NBR_KDTREE_HOSTBUILD, NBR_AUTO = 0, 1, 2, 3
 FORM_SOLVE_SPLIT, FORM_TRACK_FUSED, FORM_REPLAN_LANE, FORM_REPLAN_FEW, FORM_LP_LANE, FORM_SOLVE_FB, FORM_ACTION_FB, FORM_AUTO_TAIL = 1, 2, 4, 8, 16, 32, 64, 128   # sca_last_pass_forms
 FORM_WAYPOINTS = 256                                          # k_waypoint ran (waypoint lists are set)
@@ -486,8 +487,12 @@ class BatchedSolver:
         return out[:max(count, 0)]
 
     # ---- respawning agents in place (sca_respawn_agents / sca_get_finished) ----------------------------------------------------
-    def respawn(self, ids, pos, vel, heading, radius, pref_speed, goal, max_run_dist, zaxis=None, goal_heading=None, paths=None):
+    def respawn(self, ids, pos, vel, heading, radius, pref_speed, goal, max_run_dist, zaxis=None, goal_heading=None, paths=None, margin=None):
         """New missions for the rows `ids` (any order, no repeats) while every other row keeps every word it had (sca_respawn_agents).
+        margin (None: no gate, returns None): only the rows whose start is free are respawned (sca_respawn_agents_gated; the admission rule
+        is include/sca_hip.h's) and the call returns (verdict, probe): an int32 word per named row -- SPAWN_ADMITTED 0, SPAWN_BLOCKED_AGENT 1,
+        SPAWN_BLOCKED_OBSTACLE 2, SPAWN_BLOCKED_ENTRY 3 -- and the world test's records (_lib.CLEARANCE_DTYPE); a refused row keeps every
+        word it had.
         The arrays hold len(ids) rows in the order of `ids`.  Afterwards a named row is what set_agents + set_state (+
         device_tracker_enable) leave for an agent with these values; it keeps its policy and its per-agent attributes.  zaxis None: the
         rows keep theirs.  goal_heading: needed when a named row is tracked by the device tracker.  paths (the lists in slot form,
@@ -512,9 +517,31 @@ class BatchedSolver:
             if len(paths) != T:
                 raise ValueError(f'respawn: {len(paths)} waypoint lists where {T} rows are named')
             poff, ppts = paths_csr(paths)
-        self._chk(self.L.sca_respawn_agents(self.ctx, T, _lib.ptr(ids, C.c_int32), *[p for _, p in keep],
-                                            None if poff is None else _lib.ptr(poff, C.c_int32), None if ppts is None else _lib.ptr(ppts, C.c_double)),
-                  'sca_respawn_agents')
+        args = [self.ctx, T, _lib.ptr(ids, C.c_int32)] + [p for _, p in keep] + \
+            [None if poff is None else _lib.ptr(poff, C.c_int32), None if ppts is None else _lib.ptr(ppts, C.c_double)]
+        if margin is None:
+            self._chk(self.L.sca_respawn_agents(*args), 'sca_respawn_agents')
+            return None
+        verdict, probe = np.zeros(max(T, 1), np.int32), np.zeros(max(T, 1), _lib.CLEARANCE_DTYPE)
+        self._chk(self.L.sca_respawn_agents_gated(*args, float(margin), _lib.ptr(verdict, C.c_int32), probe.ctypes.data_as(C.POINTER(_lib.SceneClearance)), None),
+                  'sca_respawn_agents_gated')
+        return verdict[:T], probe[:T]
+
+    def probe_clearance(self, pos, radius, ignore=None):
+        """How free is each point now: spheres of `radius` (a scalar or one per point) at `pos` (Q, 3) against every agent row's current
+        record but ignore[q] (None or -1: nobody is excluded) and against every obstacle (sca_probe_clearance).  A structured array of
+        _lib.CLEARANCE_DTYPE: agent_clear / obs_clear the smallest l3norm - (radius sum), agent_partner / obs_partner the lowest id with it,
+        both step fields 0, an empty half +inf, -1, 0.  Only between two steps; changes nothing; one synchronisation."""
+        pos = np.ascontiguousarray(pos, np.float64).reshape(-1, 3)
+        Q = len(pos)
+        radius = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float64), (Q,)))
+        if ignore is not None:
+            ignore = np.ascontiguousarray(np.broadcast_to(np.asarray(ignore, np.int32), (Q,)))
+        out = np.zeros(max(Q, 1), _lib.CLEARANCE_DTYPE)                   # (a count the library will refuse still gets a buffer)
+        self._chk(self.L.sca_probe_clearance(self.ctx, Q, _lib.ptr(pos, C.c_double), _lib.ptr(radius, C.c_double),
+                                             None if ignore is None else _lib.ptr(ignore, C.c_int32), out.ctypes.data_as(C.POINTER(_lib.SceneClearance)),
+                                             _lib.CLEARANCE_DTYPE.itemsize), 'sca_probe_clearance')
+        return out[:Q]
 
     def finished(self, capacity=None):
         """The rows that carry any of at-goal / collision / timeout, ascending ids: a structured array (_lib.FINISHED_DTYPE: id i32, flags
