@@ -49,8 +49,20 @@ def lifelong(args, agents, obstacles, pol, dubins):
         return E.Agent(start_pos=start, goal_pos=goal, vel=[0.0, 0.0, 0.0], radius=agent.radius, pref_speed=agent.pref_speed, policy=pol, id=agent.id)
 
     t0 = time.time()
-    stats = run_lifelong(env, next_mission, args.lifelong) if args.spawn_margin is None else \
-        run_lifelong(env, next_mission, args.lifelong, spawn_margin=args.spawn_margin)
+    if args.device_missions:
+        # the same rule as a table of three entries per drone, taken on the device inside the step (MACAEnv.set_missions): from where it
+        # stands to its start, from where it stands to its goal, and the original mission again as every failure's successor
+        from sca_amd.lifelong import run_missions
+
+        def entry(i, start, goal):
+            a = agents[i]
+            return E.Agent(start_pos=start, goal_pos=goal, vel=[0.0, 0.0, 0.0], radius=a.radius, pref_speed=a.pref_speed, policy=pol, id=i)
+        tables = {i: E.MissionTable([entry(i, goal, start), entry(i, start, goal), entry(i, start, goal)], next_ok=[1, 0, 0], next_fail=[2, 2, 2],
+                                    first_ok=0, first_fail=2, start_here=[True, True, False]) for i, (start, goal) in first.items()}
+        stats = run_missions(env, tables, args.lifelong, burst=args.burst)
+    else:
+        stats = run_lifelong(env, next_mission, args.lifelong) if args.spawn_margin is None else \
+            run_lifelong(env, next_mission, args.lifelong, spawn_margin=args.spawn_margin)
     cost = time.time() - t0
     missions = stats['arrived'] + stats['collided'] + stats['timed_out']
     print('lifelong:', stats['steps'], 'steps,', f'{cost:.2f} s,', missions, 'missions,', f'{missions / cost:.1f} missions/s')
@@ -80,7 +92,13 @@ def main():
     ap.add_argument('--spawn-margin', type=float, default=None, metavar='M',
                     help='with --lifelong: a drone is respawned only where its start is free by M metres (of every other drone, of every '
                          'obstacle and of the drones admitted with it); otherwise its mission waits and is offered again after every step')
+    ap.add_argument('--device-missions', action='store_true',
+                    help='with --lifelong: the ping-pong rule as a mission table per drone on the device -- a drone that ends takes its next '
+                         'mission inside the step, no host call per step (MACAEnv.set_missions)')
+    ap.add_argument('--burst', type=int, default=1, metavar='K', help='with --device-missions: K resident steps per library call')
     args = ap.parse_args()
+    if args.device_missions and (args.lifelong <= 0 or args.spawn_margin is not None):
+        ap.error('--device-missions goes with --lifelong STEPS and without --spawn-margin (the admission gate is a host call)')
 
     n = args.agents
     if args.scenario == 'circle':

@@ -734,6 +734,80 @@ int sca_respawn_agents_gated(sca_ctx *ctx, int count, const int32_t *ids /*count
                              const double *path_points /*nullable*/, double margin, int32_t *verdict /*count*/,
                              sca_scene_clearance *probe /*count, nullable*/, int32_t *admitted /*nullable: how many*/);
 
+/* Mission tables: a finished row takes its next mission INSIDE the step.  sca_respawn_agents and sca_get_finished are host calls between
+ * two steps, so continuous traffic costs a synchronisation per step and sca_run_steps(k) cannot run it at all (a burst keeps stepping
+ * rows that stay finished).  Here every agent row carries its upcoming missions on the device; the step's last kernel (k_mission_advance,
+ * behind K4 and in front of the buffer swap, enqueued only while tables are set) hands a row that ENDED in this step its next mission by
+ * exactly sca_respawn_agents' rule, with no host round trip -- bursts run traffic.  The admission gate stays a host call: a table says per
+ * outcome whether the device goes on or the row stays finished for the host.
+ *   sca_set_missions   every row gets room for M entries (1 .. 127) and R result records (1 .. 65536); slot form, entries[M a + j], as the
+ *              path slots are laid out.  An entry is a 128-byte sca_mission; next_ok / next_fail name entries of the SAME row (-1: stop).
+ *              SCA_MISSION_START_HERE: the row keeps the position and heading it has (pos / heading are ignored); SCA_MISSION_KEEP_ZAXIS:
+ *              it keeps its zaxis byte.  The radius, the policy and the per-agent solver and planner attributes stay the row's, as under
+ *              sca_respawn_agents.  first_ok[a] / first_fail[a] are the successors of the flight that is in the air when the table
+ *              arrives; a row with first_ok = first_fail = -1 has no table and behaves as without the feature.  entries == NULL with
+ *              M = 0 drops the feature, sca_set_agents drops it too, sca_set_state leaves tables and cursors alone.  The largest
+ *              pref_speed among the reachable entries is folded into the context's envelope at once (it only grows).
+ *   taking     a row ENDED in a step when it entered it without any of at-goal / collision / timeout and leaves K4 with one.  Outcome:
+ *              collided if the collision bit is set, else arrived if at-goal is set, else timed out.  Successor: next_ok for arrived,
+ *              next_fail otherwise -- those of the entry under the row's cursor, first_ok / first_fail while the cursor is -1.
+ *              -1: the row stays finished as it is (sca_get_finished lists it, the host may respawn it, gated or not; the cursor stays,
+ *              so a later ending of that host-given flight follows the same successors again).  j >= 0: the row becomes what
+ *              sca_respawn_agents naming it with entry j's values leaves, word for word (for START_HERE: with the pos / heading
+ *              sca_get_state returns) -- flags 0, total_dist 0, step_num 0, status 0, list invalid, under the device tracker the initial
+ *              record with goal_heading, vpref_mode 1 and vpref_ext 0 for SCA / RVO3D+Dubins rows, the closest-approach record emptied,
+ *              sca_active_count right at once -- and the cursor becomes j.  A self-successor (next_fail == j) is legal: "retry".  Rows
+ *              already finished when the table arrives are never taken.
+ *   results    every ending of a row that has a table writes one 96-byte sca_mission_result into the row's ring at ended[a] % R; ended[a]
+ *              counts endings and nothing ever blocks: a host that collects too rarely sees from `ended` how many it lost.
+ *              sca_get_mission_results hands out the results not yet collected, ascending id, within a row oldest first (the ordered
+ *              compaction of sca_get_finished with a count per row; no atomic cursor; one synchronisation) and marks them collected.
+ *              *count is their number; where it exceeds `capacity` NOTHING is written or marked (call again with room; n x R always
+ *              suffices).  sca_get_mission_totals: 64-bit counters since sca_set_missions, kept by integer atomics (one per wavefront per
+ *              step and counter, only where non-zero), over ALL rows: env updates, agent-steps (rows that entered a step unfinished),
+ *              endings arrived / collided / timed out, taken, stopped (an ending without a successor, rows without a table included).
+ *              sca_get_mission_state copies the cursor and `ended` words of rows begin .. begin + count - 1.
+ *   ordering   while tables are set sca_run_steps starts nothing of the next pass from positions the mission kernel may still replace
+ *              (no kd build ahead, no event riding on k_action or on the step's last kernel): forms may differ, values may not.
+ *   refusals   decided on the host before any device work; a refused call changes nothing.  SCA_ERR_STATE: no agents, between a policy
+ *              pass and its env update, a getter while no tables are set.  SCA_ERR_ARG: M or R out of range, n other than the agent
+ *              count, a NULL array, M x n or R x n above 2^24, a successor outside -1 .. M-1, a REACHABLE entry (from first_ok /
+ *              first_fail through successors) with a position, heading, goal or velocity that is not finite, a pref_speed or
+ *              max_run_dist that is not positive and finite, a zaxis byte above 1 without KEEP_ZAXIS, unknown flag bits; bad
+ *              struct_bytes, capacity, range or NULL outputs in the getters.  SCA_ERR_UNSUPPORTED, in either order of the calls:
+ *              everything sca_respawn_agents refuses (scenes, a shard with count < n, a communicator, the partition), waypoint lists in
+ *              either form (their host mirrors cannot follow a device-side respawn), and sca_step_host while tables are set (the host
+ *              owns the state there).
+ * Detect the feature by the symbols (the version number is unchanged). */
+enum sca_mission_flag { SCA_MISSION_START_HERE = 1, SCA_MISSION_KEEP_ZAXIS = 2 };
+typedef struct sca_mission {             /* 128 bytes */
+    double  pos[3], heading[3];          /* the start (ignored with SCA_MISSION_START_HERE) */
+    double  goal[3], goal_heading[3];    /* goal_heading: read for rows the device tracker tracks */
+    double  pref_speed, max_run_dist;
+    float   vel[3];
+    int8_t  next_ok, next_fail;          /* entries of the same row, -1: stop */
+    uint8_t zaxis, flags;                /* flags: sca_mission_flag bits */
+} sca_mission;
+typedef struct sca_mission_result {      /* 96 bytes */
+    int32_t  id;                         /* the agent's row */
+    int32_t  entry;                      /* the entry it flew; -1: the flight in the air at sca_set_missions, or one the host gave */
+    uint32_t flags;                      /* sca_flag bits the flight ended with */
+    int32_t  step_num;
+    double   total_dist;
+    double   pos[3];                     /* where it ended */
+    int64_t  update;                     /* the env update it ended in, counted from sca_set_missions (1-based) */
+    int32_t  next, reserved;             /* the successor taken, -1: stopped */
+    sca_scene_clearance clear;           /* the row's closest-approach record before it was emptied (+inf, -1, 0 without sca_clearance_enable) */
+} sca_mission_result;
+typedef struct sca_mission_totals {      /* 64 bytes */
+    uint64_t updates, agent_steps, arrived, collided, timed_out, taken, stopped, reserved;
+} sca_mission_totals;
+int sca_set_missions(sca_ctx *ctx, int M, int R, int n, const sca_mission *entries /*M*n*/, const int32_t *first_ok /*n*/,
+                     const int32_t *first_fail /*n*/);
+int sca_get_mission_results(sca_ctx *ctx, sca_mission_result *out /*capacity*/, int capacity, int *count, int32_t struct_bytes);
+int sca_get_mission_totals(sca_ctx *ctx, sca_mission_totals *out, int32_t struct_bytes);
+int sca_get_mission_state(sca_ctx *ctx, int begin, int count, int32_t *cursor /*count*/, int32_t *ended /*count*/);
+
 /* the hot path ----------------------------------------------------------------------------------- */
 int sca_policy_pass(sca_ctx *ctx, int neighbor_mode);
 int sca_get_actions(sca_ctx *ctx, float *action /*n*7*/);

@@ -84,6 +84,33 @@ FINISHED_DTYPE = np.dtype([('id', np.int32), ('flags', np.uint32), ('step_num', 
                            ('pos', np.float64, (3,))])
 
 
+class Mission(C.Structure):
+    """sca_mission: one entry of a row's mission table (sca_set_missions), 128 bytes"""
+    _fields_ = [('pos', C.c_double * 3), ('heading', C.c_double * 3), ('goal', C.c_double * 3), ('goal_heading', C.c_double * 3),
+                ('pref_speed', C.c_double), ('max_run_dist', C.c_double), ('vel', C.c_float * 3), ('next_ok', C.c_int8), ('next_fail', C.c_int8),
+                ('zaxis', C.c_uint8), ('flags', C.c_uint8)]
+
+
+MISSION_DTYPE = np.dtype([('pos', np.float64, (3,)), ('heading', np.float64, (3,)), ('goal', np.float64, (3,)), ('goal_heading', np.float64, (3,)),
+                          ('pref_speed', np.float64), ('max_run_dist', np.float64), ('vel', np.float32, (3,)), ('next_ok', np.int8),
+                          ('next_fail', np.int8), ('zaxis', np.uint8), ('flags', np.uint8)])
+
+
+class MissionResult(C.Structure):
+    """sca_mission_result: one ending of a row that has a table (sca_get_mission_results), 96 bytes"""
+    _fields_ = [('id', C.c_int32), ('entry', C.c_int32), ('flags', C.c_uint32), ('step_num', C.c_int32), ('total_dist', C.c_double),
+                ('pos', C.c_double * 3), ('update', C.c_int64), ('next', C.c_int32), ('reserved', C.c_int32), ('clear', SceneClearance)]
+
+
+MISSION_RESULT_DTYPE = np.dtype([('id', np.int32), ('entry', np.int32), ('flags', np.uint32), ('step_num', np.int32), ('total_dist', np.float64),
+                                 ('pos', np.float64, (3,)), ('update', np.int64), ('next', np.int32), ('reserved', np.int32), ('clear', CLEARANCE_DTYPE)])
+
+
+class MissionTotals(C.Structure):
+    """sca_mission_totals: the counters since sca_set_missions (sca_get_mission_totals), 64 bytes"""
+    _fields_ = [(k, C.c_uint64) for k in ('updates', 'agent_steps', 'arrived', 'collided', 'timed_out', 'taken', 'stopped', 'reserved')]
+
+
 CHECKPOINT_SECTIONS = 14                                         # sca_scene_checkpoint_layout's offsets
 
 
@@ -139,6 +166,10 @@ SIGNATURES = {
     'sca_get_finished': (C.c_int, [C.c_void_p, C.POINTER(FinishedRow), C.c_int, C.POINTER(C.c_int), C.c_int32]),
     'sca_probe_clearance': (C.c_int, [C.c_void_p, C.c_int, dp, dp, ip, C.POINTER(SceneClearance), C.c_int32]),
     'sca_respawn_agents_gated': (C.c_int, [C.c_void_p, C.c_int, ip, dp, fp, dp, dp, dp, dp, bp, dp, dp, ip, dp, C.c_double, ip, C.POINTER(SceneClearance), ip]),
+    'sca_set_missions': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Mission), ip, ip]),
+    'sca_get_mission_results': (C.c_int, [C.c_void_p, C.POINTER(MissionResult), C.c_int, C.POINTER(C.c_int), C.c_int32]),
+    'sca_get_mission_totals': (C.c_int, [C.c_void_p, C.POINTER(MissionTotals), C.c_int32]),
+    'sca_get_mission_state': (C.c_int, [C.c_void_p, C.c_int, C.c_int, ip, ip]),
     'sca_set_path_state': (C.c_int, [C.c_void_p, ip, dp]),
     'sca_policy_pass': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_get_actions': (C.c_int, [C.c_void_p, fp]),

@@ -193,6 +193,7 @@ struct StepIn {
     bool clear_on;              // the closest-approach records of the whole context are on
     bool auto_ran;              // the pass of this step was an AUTO pass
     bool fits, part_on; int kdq_last, auto_div, auto_backoff, shard_count;   // auto_next's inputs (tracked_pass is trk_on && trk_in_pass)
+    bool missions_on = false;   // mission tables are set (sca_set_missions): the step's last kernel may still replace rows
 };
 struct StepPlan {
     bool moved_on_action;       // k_action carries Auto::ev_moved.  None of its inputs is a result of the step's pass: asked in front of it
@@ -215,6 +216,9 @@ inline StepPlan plan_step(const StepIn &i) {
     // (not while waypoint lists are set: the next pass's k_waypoint must come before its fork)
     // (a step that builds ahead took the other branch: no tracker in an AUTO pass, no fork to carry)
     p.fork_rides = !p.build_ahead && more && i.ext_stop && i.trk_on && i.trk_in_pass && i.trk_fork && !i.paths_on;
+    // mission tables: k_mission_advance, behind K4, may replace a row's position, heading and tracker record -- nothing of the next pass
+    // starts from the moved positions before it has run, and the step's last kernel is not the one the fork would ride on
+    if (i.missions_on) p = StepPlan{};
     return p;
 }
 // the env update's launches: which K4 instance runs, what follows it, and which of them is the step's last kernel -- the one that carries the

@@ -31,6 +31,8 @@
 #include "sca_clearance.hip.h"
 #include "sca_respawn.h"
 #include "sca_respawn.hip.h"
+#include "sca_missions.h"
+#include "sca_missions.hip.h"
 #include "sca_spawn.h"
 #include "sca_spawn.hip.h"
 
@@ -367,6 +369,19 @@ struct sca_ctx {
     int spn_cap = 0;
     SpawnPartial *spn_partials = nullptr;   // device [tiles][spn_cap]
     int64_t spn_partials_room = 0;          // ... how many it has room for
+    // mission tables (sca_set_missions; sca_missions.h): nothing of it exists while no tables are set
+    struct Missions {
+        bool on = false;
+        int M = 0, R = 0;
+        sca_mission *entries = nullptr;     // device [M n]
+        int32_t *words = nullptr;           // device [7 n]: first_ok, first_fail, cursor, flying, ended, collected, live
+        sca_mission_result *results = nullptr;   // device [R n]: the rows' rings
+        unsigned long long *totals = nullptr;    // device [MST_WORDS]
+        int32_t *counts = nullptr;          // device [2 tiles + 1]: the collect's counts per tile, their offsets, the total
+        uint8_t *host = nullptr;            // the collect's page-locked block: the count's head, host_cap results behind it
+        int64_t host_cap = 0;
+        long long updates = 0;              // env updates enqueued since sca_set_missions
+    } ms;
 };
 
 #define CHK(ctx, call)                                                                         \
@@ -432,6 +447,10 @@ static int pool_mean_ms(sca_ctx *c, const std::vector<hipEvent_t> &pool, int use
 // sca_run_steps.  Every OTHER entry point joins first: it may read the tree, the permutation or the lists, or enqueue work that does.
 static int auto_join(sca_ctx *c);
 static int clearance_drop(sca_ctx *c);
+static int missions_drop(sca_ctx *c);
+static int missions_standing(sca_ctx *c, const char *who, MissionFault f);
+static int missions_refresh_live(sca_ctx *c);
+static int missions_host_flight(sca_ctx *c, const int32_t *ids, const int32_t *verdict, int count);
 static ClearanceState clearance_state(const sca_ctx *c);
 static int clearance_refuse(sca_ctx *c, const char *who, ClearanceFault f);
 static int api_enter(sca_ctx *c);
@@ -1002,6 +1021,7 @@ void sca_destroy(sca_ctx *c) {
     if (c->rsp_host) { (void)hipHostFree(c->rsp_host); c->rsp_host = nullptr; }
     if (c->fin_host) { (void)hipHostFree(c->fin_host); c->fin_host = nullptr; }
     if (c->fin_counts) { (void)hipFree(c->fin_counts); c->fin_counts = nullptr; }
+    (void)missions_drop(c);
     if (c->spn_host) { (void)hipHostFree(c->spn_host); c->spn_host = nullptr; }
     if (c->spn_dev) { (void)hipFree(c->spn_dev); c->spn_dev = nullptr; }
     if (c->spn_partials) { (void)hipFree(c->spn_partials); c->spn_partials = nullptr; }
@@ -1166,6 +1186,7 @@ int sca_set_agents(sca_ctx *c, int n, const double *radius, const double *pref_s
     if (int r = paths_clear(c, false)) return r;                      // ... and so do the waypoint lists (vpref_mode is reset below)
     if (int r = scenes_clear(c)) return r;                            // ... and so do the scenes
     if (int r = clearance_drop(c)) return r;                          // ... and so do the closest-approach records
+    if (int r = missions_drop(c)) return r;                           // ... and so do the mission tables
     if (c->comm && n % c->comm_nranks) { c->err = "agent count must be a multiple of the communicator's rank count"; return SCA_ERR_ARG; }
     c->n = n; c->d.n = n; c->d.shard_begin = 0; c->d.shard_count = n;
     if (c->comm) { c->d.shard_count = n / c->comm_nranks; c->d.shard_begin = c->comm_rank * c->d.shard_count; }
@@ -1222,6 +1243,7 @@ int sca_set_state(sca_ctx *c, const double *pos, const float *vel, const double 
     if (step_num) CHK(c, hipMemcpyAsync(c->d.step_num, step_num, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
     CHK(c, hipStreamSynchronize(c->stream));
     state_replaced(c);
+    if (int r = missions_refresh_live(c)) return r;                       // (mission tables stay; which rows enter the next step running follows the new flags)
     scene_harvest_clear_fresh(c, 0, nullptr);                             // (a state from outside: nothing that finished before it is reported after it)
     if (c->part_on) return part_classify(c);                              // a complete state again: ownership follows from it
     return 0;
@@ -1362,6 +1384,7 @@ int sca_set_paths(sca_ctx *c, int n, const int32_t *offsets, const double *point
     API_ENTER(c);
     if (!c->agents_set) { c->err = "sca_set_agents first"; return SCA_ERR_STATE; }
     if (n == 0 || !offsets) return paths_clear(c, true);
+    if (int r = missions_standing(c, "sca_set_paths", MSF_PATHS)) return r;
     if (c->part_on) { c->err = "sca_set_paths under the cell-owner partition: path state does not migrate with the agents"; return SCA_ERR_UNSUPPORTED; }
     if (n != c->n) { c->err = "sca_set_paths: n = " + std::to_string(n) + " is not the agent count " + std::to_string(c->n); return SCA_ERR_ARG; }
     if (offsets[0] != 0) { c->err = "sca_set_paths: offsets[0] must be 0"; return SCA_ERR_ARG; }
@@ -1404,6 +1427,7 @@ int sca_set_paths(sca_ctx *c, int n, const int32_t *offsets, const double *point
 int sca_set_path_slots(sca_ctx *c, int points_per_agent, int n, const int32_t *offsets, const double *points) {
     API_ENTER(c);
     const int W = points_per_agent;
+    if (W > 0) if (int r = missions_standing(c, "sca_set_path_slots", MSF_PATHS)) return r;    // (W <= 0 is path_slots_check's SCA_ERR_ARG, tables or not)
     const PathSlotCheck k = path_slots_check(c->agents_set, c->part_on, c->n, c->max_n, W, n, offsets, points);
     if (k.fault != PATH_SLOTS_OK) {
         const std::string at = std::to_string(k.entry);
@@ -1570,6 +1594,7 @@ int sca_set_scenes(sca_ctx *c, int nscenes, const int32_t *offsets) {
     }
     if (k.fault == SCENES_NONE) return scenes_clear(c);
     if (int r = clearance_refuse(c, "sca_set_scenes", clearance_check(CLR_SET_SCENES, clearance_state(c), 0, 0, true, 0))) return r;
+    if (int r = missions_standing(c, "sca_set_scenes", MSF_SCENES)) return r;
     if (c->comm) { c->err = "sca_set_scenes with an active communicator (sca_comm_init): scenes are one rank's"; return SCA_ERR_UNSUPPORTED; }
     if (c->part_on) { c->err = "sca_set_scenes under the cell-owner partition (sca_partition_init): a mode of SCA_NBR_GRID, which has no scene form"; return SCA_ERR_UNSUPPORTED; }
     if (c->d.shard_begin != 0 || c->d.shard_count != n) { c->err = "sca_set_scenes on a shard (sca_set_shard): scenes are stepped by one rank, whole"; return SCA_ERR_UNSUPPORTED; }
@@ -2936,6 +2961,7 @@ static int finish_k4(sca_ctx *c, int k4, hipEvent_t stop) {
     }
     return 0;
 }
+static int missions_advance(sca_ctx *c);
 // `ride`: the event for the step's last kernel, if sca_run_steps hands one over (the next pass's fork).  Afterwards the moved records are the current ones (buffer swap, no copy)
 static int launch_collide_finish(sca_ctx *c, bool timed, hipEvent_t ride) {
     DeviceView &d = c->d;
@@ -2957,6 +2983,7 @@ static int launch_collide_finish(sca_ctx *c, bool timed, hipEvent_t ride) {
         const int rows = c->part_on ? std::max(1, d.n_present) : d.n;
         LAUNCH_OPT(c, stop_of(CARRY_OTHERS), k_goal_flags_others, dim3((rows + 255) / 256), dim3(256), c->stream, d, c->P);
     }
+    if (c->ms.on) if (int r = missions_advance(c)) return r;    // the rows that ended in this step take their next mission: behind K4, on the records it wrote, in front of the swap
     if (timed) CHK(c, hipEventRecord(c->ev[5], c->stream));
     CHK(c, hipGetLastError());
     std::swap(d.rec, d.rec_new);
@@ -3049,7 +3076,7 @@ static void auto_abandon(sca_ctx *c) {
 // what plan_step asks of the context, as it stands when it is asked
 static StepIn step_in(const sca_ctx *c, int mode, int s, int steps) {
     return StepIn{mode, s, steps, c->au.stream != nullptr, c->tun.ext_stop != 0, c->comm != nullptr, c->d.shard_count == c->n, c->trk_on, c->trk_in_pass, c->trk_fork != nullptr,
-                  c->paths_on, c->clear != nullptr, c->au.ran, c->au.fits, c->part_on, c->au.last, c->tun.auto_div, c->au.backoff, c->d.shard_count};
+                  c->paths_on, c->clear != nullptr, c->au.ran, c->au.fits, c->part_on, c->au.last, c->tun.auto_div, c->au.backoff, c->d.shard_count, c->ms.on};
 }
 // between the pass and the update: what the shard moved reaches the others, or what stands in for that
 static int step_exchange(sca_ctx *c) {
@@ -3211,6 +3238,7 @@ int sca_step_host(sca_ctx *c, int neighbor_mode, uint32_t in_mask, int *active) 
     API_ENTER(c);                                                         // (the block replaces or reads state: an AUTO pass's kd stream is joined first)
     ARG(c, active);
     ARG(c, (in_mask & ~(uint32_t)(SCA_HOST_IN_STATE | SCA_HOST_IN_VPREF)) == 0);
+    if (int r = missions_standing(c, "sca_step_host", MSF_STEP_HOST)) return r;
     if (int r = host_step_refuse(c, neighbor_mode, in_mask)) return r;
     if (int r = host_ingest(c, in_mask)) return r;
     if (int r = run_steps_guarded(c, 1, neighbor_mode, false)) return r;  // integrate fused into the pass, k_collide_finish; joins the kd stream
@@ -3279,6 +3307,7 @@ int sca_comm_init(sca_ctx *c, int rank, int nranks, const void *unique_id) {
     if (c->part_on) { c->err = "sca_comm_init with the cell-owner partition active"; return SCA_ERR_STATE; }
     if (c->scenes.on) { c->err = "sca_comm_init with scenes set (sca_set_scenes): scenes are one rank's"; return SCA_ERR_UNSUPPORTED; }
     if (int r = clearance_refuse(c, "sca_comm_init", clearance_check(CLR_COMM_INIT, clearance_state(c), 0, 0, true, 0))) return r;
+    if (int r = missions_standing(c, "sca_comm_init", MSF_COMM)) return r;
     if (c->n % nranks) { c->err = "agent count must be a multiple of the rank count"; return SCA_ERR_ARG; }
     if (const char *e = rccl_load()) { c->err = e; return SCA_ERR_UNSUPPORTED; }
     CHK(c, hipSetDevice(c->device));
@@ -3391,6 +3420,7 @@ int sca_partition_init(sca_ctx *c, int rank, int nranks, int axis, const double 
     if (c->scenes.on) { c->err = "sca_partition_init with scenes set (sca_set_scenes): a mode of SCA_NBR_GRID, which has no scene form"; return SCA_ERR_UNSUPPORTED; }
     if (c->paths_on) { c->err = "sca_partition_init with waypoint lists set (sca_set_paths): path state does not migrate with the agents"; return SCA_ERR_UNSUPPORTED; }
     if (int r = clearance_refuse(c, "sca_partition_init", clearance_check(CLR_PARTITION_INIT, clearance_state(c), 0, 0, true, 0))) return r;
+    if (int r = missions_standing(c, "sca_partition_init", MSF_PARTITION)) return r;
     if (int r = part_free(c)) return r;
     const int n = c->n;
     const double inv_cell = grid_inv_cell(c->P.neighbor_dist);
@@ -4056,6 +4086,8 @@ static int respawn_run(sca_ctx *c, const RespawnCtx &X, const RespawnArgs &A, co
     hipLaunchKernelGGL(k_respawn, dim3((count + RESPAWN_WAVES - 1) / RESPAWN_WAVES), dim3(RESPAWN_WAVES * 64), 0, c->stream, d, (const uint8_t *)c->rsp_host, L, has, count,
                        (const int32_t *)(gate ? sd.verdict : nullptr));
     CHK(c, hipGetLastError());
+    // (mission tables: the named rows -- a gated call's admitted ones -- fly a flight that is not an entry and enter the next step running)
+    if (int r = missions_host_flight(c, (const int32_t *)(c->rsp_host + L.off[RSB_IDS]), gate ? (const int32_t *)sd.verdict : nullptr, count)) return r;
     CHK(c, hipStreamSynchronize(c->stream));
     const int32_t *verdict = nullptr;
     if (gate) {
@@ -4115,6 +4147,167 @@ int sca_get_finished(sca_ctx *c, sca_finished_row *rows, int capacity, int *coun
     const int total = *(const int32_t *)c->fin_host;
     *count = total;
     if (std::min(total, cap) > 0) std::memcpy(rows, c->fin_host + FIN_HEAD_BYTES, sizeof(sca_finished_row) * (size_t)std::min(total, cap));
+    return 0;
+}
+
+// ---- mission tables (include/sca_hip.h; the rules are sca_missions.h's, the kernels sca_missions.hip.h's; k_mission_advance is enqueued by
+// launch_collide_finish, the collect's kernels here and nowhere else) ---------------------------------------------------------------------------
+static int mission_refuse(sca_ctx *c, const char *who, MissionFault f, int64_t entry) {
+    const std::string w = std::string(who), at = std::to_string(entry);
+    switch (f) {
+    case MSF_OK: return 0;
+    case MSF_NO_AGENTS: c->err = w + ": sca_set_agents first"; break;
+    case MSF_MID_STEP: c->err = w + " between a policy pass and its env update: finish the step first"; break;
+    case MSF_OFF: c->err = w + ": no mission tables are set -- sca_set_missions first"; break;
+    case MSF_BAD_M: c->err = w + ": M must be 1 .. " + std::to_string(MISSION_MAX_M) + " (0 with entries == NULL drops the tables)"; break;
+    case MSF_BAD_R: c->err = w + ": R must be 1 .. " + std::to_string(MISSION_MAX_R); break;
+    case MSF_BAD_N: c->err = w + ": n is not the agent count " + std::to_string(c->n); break;
+    case MSF_NO_ARRAYS: c->err = w + ": entries, first_ok and first_fail must not be NULL"; break;
+    case MSF_TOO_LARGE: c->err = w + ": M x n and R x n must not exceed " + std::to_string(MISSION_MAX_SLOTS); break;
+    case MSF_BAD_SUCCESSOR: c->err = w + ": a successor outside -1 .. M - 1 at " + at + " (a row of first_ok / first_fail, else the flat entry index)"; break;
+    case MSF_NOT_FINITE: c->err = w + ": reachable entry " + at + " has a position, heading, goal or velocity that is not finite"; break;
+    case MSF_NOT_POSITIVE: c->err = w + ": reachable entry " + at + " has a pref_speed or max_run_dist that is not positive and finite"; break;
+    case MSF_BAD_ZAXIS: c->err = w + ": reachable entry " + at + " has a zaxis byte above 1 without SCA_MISSION_KEEP_ZAXIS"; break;
+    case MSF_BAD_FLAGS: c->err = w + ": reachable entry " + at + " has unknown flag bits"; break;
+    case MSF_GET_ARGS: c->err = w + ": a NULL output, a negative capacity, a range outside 0 .. n or struct_bytes other than the struct's size"; break;
+    case MSF_SCENES: c->err = w + ": mission tables and scenes (sca_set_scenes) exclude each other: a scene's agents are replaced by sca_restart_scenes"; break;
+    case MSF_SHARD: c->err = w + ": mission tables and a shard with count < n (sca_set_shard) exclude each other: the tables name rows of the whole swarm on one rank"; break;
+    case MSF_COMM: c->err = w + ": mission tables and a communicator exclude each other (sca_comm_destroy first)"; break;
+    case MSF_PARTITION: c->err = w + ": mission tables and the cell-owner partition exclude each other: the rows' state does not follow the owners"; break;
+    case MSF_PATHS: c->err = w + ": mission tables and waypoint lists exclude each other: the lists' host mirrors cannot follow a device-side respawn"; break;
+    default: c->err = w + " while mission tables are set: the host owns the state there (drop the tables: sca_set_missions with M = 0)";
+    }
+    return mission_error_code(f);
+}
+// an entry point that would bring what tables exclude, while tables stand
+static int missions_standing(sca_ctx *c, const char *who, MissionFault f) { return c->ms.on ? mission_refuse(c, who, f, -1) : 0; }
+static int missions_drop(sca_ctx *c) {
+    sca_ctx::Missions &m = c->ms;
+    if (!m.entries && !m.host) { m = sca_ctx::Missions{}; return 0; }
+    (void)hipStreamSynchronize(c->stream);                             // (no launch still uses them)
+    if (m.entries) (void)hipFree(m.entries);
+    if (m.words) (void)hipFree(m.words);
+    if (m.results) (void)hipFree(m.results);
+    if (m.totals) (void)hipFree(m.totals);
+    if (m.counts) (void)hipFree(m.counts);
+    if (m.host) (void)hipHostFree(m.host);
+    m = sca_ctx::Missions{};
+    return 0;
+}
+enum MissionWord { MSW_FIRST_OK = 0, MSW_FIRST_FAIL, MSW_CURSOR, MSW_FLYING, MSW_ENDED, MSW_COLLECTED, MSW_LIVE, MSW_WORDS };
+// flags changed between two steps (a new state, a respawn, the tables' arrival): which rows enter the next step without a done flag
+static int missions_refresh_live(sca_ctx *c) {
+    if (!c->ms.on || !c->state_set) return 0;
+    hipLaunchKernelGGL(k_mission_live, dim3((c->n + MISSION_T - 1) / MISSION_T), dim3(MISSION_T), 0, c->stream, (const PubRec *)c->d.rec, c->ms.words + (size_t)MSW_LIVE * c->n, c->n);
+    CHK(c, hipGetLastError());
+    return 0;
+}
+// a host respawn while tables stand, behind its k_respawn on c->stream: `ids` / `verdict` as that kernel reads them (device-visible)
+static int missions_host_flight(sca_ctx *c, const int32_t *ids, const int32_t *verdict, int count) {
+    if (!c->ms.on) return 0;
+    hipLaunchKernelGGL(k_mission_host_flight, dim3((count + MISSION_T - 1) / MISSION_T), dim3(MISSION_T), 0, c->stream, ids, verdict, count, c->n, c->ms.words + (size_t)MSW_FLYING * c->n);
+    CHK(c, hipGetLastError());
+    return missions_refresh_live(c);
+}
+static int missions_advance(sca_ctx *c) {
+    const sca_ctx::Missions &s = c->ms;
+    const int n = c->n;
+    MissionDev m{};
+    RespawnDev &d = m.row;
+    d.rec = c->d.rec_new; d.heading = c->d.heading; d.goal = c->d.goal; d.pref_speed = c->d.pref_speed; d.max_run_dist = c->d.max_run_dist;
+    d.total_dist = c->d.total_dist; d.vpref_ext = c->d.vpref_ext; d.step_num = c->d.step_num; d.status = c->d.status; d.nbr_n = c->d.nbr_n;
+    d.near_n = c->d.near_n; d.done_count = c->d.done_count; d.zaxis = c->d.zaxis; d.vpref_mode = c->d.vpref_mode; d.nbr_valid = c->d.nbr_valid;
+    if (c->trk_on) {
+        d.trk_nbr0 = c->trk.nbr0; d.trk_goal_heading = c->trk_goal_heading;
+        d.trk_st = (restart_u32 *)c->trk.st; d.trk_init = (const restart_u32 *)c->trk_init; d.trk_words = (int)(sizeof(sca_dubins::AgentTrack) / 4);
+    }
+    d.clear = c->clear;
+    d.n = n;
+    m.live = s.words + (size_t)MSW_LIVE * n; m.policy = c->d.policy; m.entries = s.entries;
+    m.first_ok = s.words + (size_t)MSW_FIRST_OK * n; m.first_fail = s.words + (size_t)MSW_FIRST_FAIL * n;
+    m.cursor = s.words + (size_t)MSW_CURSOR * n; m.flying = s.words + (size_t)MSW_FLYING * n; m.ended = (uint32_t *)(s.words + (size_t)MSW_ENDED * n);
+    m.results = s.results; m.totals = s.totals; m.update = ++c->ms.updates; m.M = s.M; m.R = s.R;
+    hipLaunchKernelGGL(k_mission_advance, dim3((n + MISSION_T - 1) / MISSION_T), dim3(MISSION_T), 0, c->stream, m);
+    CHK(c, hipGetLastError());
+    positions_replaced(c);                // a taken row may stand anywhere now and the host does not learn of it: no sizing hint from older trees (no value)
+    return 0;
+}
+int sca_set_missions(sca_ctx *c, int M, int R, int n, const sca_mission *entries, const int32_t *first_ok, const int32_t *first_fail) {
+    API_ENTER(c);
+    if (!entries && M == 0) return missions_drop(c);
+    MissionCtx X;
+    X.agents = c->agents_set; X.mid_step = c->near_valid; X.scenes = c->scenes.on; X.comm = c->comm != nullptr; X.partition = c->part_on;
+    X.paths = c->paths_on; X.n = c->n; X.shard_count = c->d.shard_count;
+    const MissionCheck k = mission_check(X, MissionArgs{M, R, n, entries, first_ok, first_fail});
+    if (int r = mission_refuse(c, "sca_set_missions", k.fault, k.entry)) return r;
+    if (int r = missions_drop(c)) return r;
+    sca_ctx::Missions &m = c->ms;
+    const int tiles = finished_tiles(n);
+    std::vector<int32_t> words((size_t)MSW_WORDS * n, 0);
+    for (int a = 0; a < n; a++) {
+        words[(size_t)MSW_FIRST_OK * n + a] = first_ok[a]; words[(size_t)MSW_FIRST_FAIL * n + a] = first_fail[a];
+        words[(size_t)MSW_CURSOR * n + a] = -1; words[(size_t)MSW_FLYING * n + a] = -1;
+    }
+    const auto fail = [&](hipError_t e, const char *what) { c->err = std::string("sca_set_missions: ") + what + ": " + hipGetErrorString(e); (void)missions_drop(c); return SCA_ERR_HIP; };
+    hipError_t e;
+    if ((e = hipMalloc((void **)&m.entries, sizeof(sca_mission) * (size_t)M * n)) != hipSuccess) return fail(e, "no device memory for the tables");
+    if ((e = hipMalloc((void **)&m.words, sizeof(int32_t) * words.size())) != hipSuccess) return fail(e, "no device memory for the cursors");
+    if ((e = hipMalloc((void **)&m.results, sizeof(sca_mission_result) * (size_t)R * n)) != hipSuccess) return fail(e, "no device memory for the results");
+    if ((e = hipMalloc((void **)&m.totals, sizeof(unsigned long long) * MST_WORDS)) != hipSuccess) return fail(e, "no device memory for the totals");
+    if ((e = hipMalloc((void **)&m.counts, sizeof(int32_t) * (2 * (size_t)tiles + 1))) != hipSuccess) return fail(e, "no device memory for the collect");
+    if ((e = hipMemcpyAsync(m.entries, entries, sizeof(sca_mission) * (size_t)M * n, hipMemcpyHostToDevice, c->stream)) != hipSuccess) return fail(e, "the upload of the tables");
+    if ((e = hipMemcpyAsync(m.words, words.data(), sizeof(int32_t) * words.size(), hipMemcpyHostToDevice, c->stream)) != hipSuccess) return fail(e, "the upload of the cursors");
+    if ((e = hipMemsetAsync(m.results, 0, sizeof(sca_mission_result) * (size_t)R * n, c->stream)) != hipSuccess) return fail(e, "clearing the results");
+    if ((e = hipMemsetAsync(m.totals, 0, sizeof(unsigned long long) * MST_WORDS, c->stream)) != hipSuccess) return fail(e, "clearing the totals");
+    m.M = M; m.R = R; m.updates = 0; m.on = true;
+    if (missions_refresh_live(c)) { (void)missions_drop(c); return SCA_ERR_HIP; }
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return fail(e, "the upload");
+    c->max_pref_speed = std::max(c->max_pref_speed, k.max_pref_speed);   // the envelope only grows, as under respawns
+    return 0;
+}
+int sca_get_mission_results(sca_ctx *c, sca_mission_result *out, int capacity, int *count, int32_t struct_bytes) {
+    API_ENTER(c);
+    if (int r = mission_refuse(c, "sca_get_mission_results", mission_results_check(c->agents_set, c->ms.on, out != nullptr, capacity, count != nullptr, struct_bytes), -1)) return r;
+    sca_ctx::Missions &m = c->ms;
+    const int n = c->n, tiles = finished_tiles(n);
+    const int64_t cap = std::min((int64_t)capacity, (int64_t)m.R * n);
+    if (!m.host || cap > m.host_cap) {
+        const int64_t want = std::min((int64_t)m.R * n, std::max(cap, std::max((int64_t)1024, 2 * m.host_cap)));
+        uint8_t *blk = nullptr;
+        CHK(c, hipHostMalloc((void **)&blk, (size_t)MISSION_HEAD_BYTES + sizeof(sca_mission_result) * (size_t)want, hipHostMallocMapped | hipHostMallocCoherent));
+        if (m.host) (void)hipHostFree(m.host);                         // (every call ends with its synchronisation: no launch still writes it)
+        m.host = blk; m.host_cap = want;
+    }
+    const MissionCollectDev k{(const uint32_t *)(m.words + (size_t)MSW_ENDED * n), (uint32_t *)(m.words + (size_t)MSW_COLLECTED * n), m.results, m.counts, m.counts + tiles,
+                              m.counts + 2 * tiles, n, tiles, m.R};
+    const FinishedDev f{nullptr, nullptr, nullptr, k.counts, k.offsets, n, tiles};
+    hipLaunchKernelGGL(k_mission_count, dim3(tiles), dim3(FIN_TILE), 0, c->stream, k);
+    hipLaunchKernelGGL(k_finished_scan, dim3(1), dim3(FIN_TILE), 0, c->stream, f, k.total);
+    hipLaunchKernelGGL(k_mission_write, dim3(tiles), dim3(FIN_TILE), 0, c->stream, k, m.host, (int)cap);
+    CHK(c, hipGetLastError());
+    CHK(c, hipStreamSynchronize(c->stream));
+    const int total = *(const int32_t *)m.host;
+    *count = total;
+    if (total > 0 && total <= cap) std::memcpy(out, m.host + MISSION_HEAD_BYTES, sizeof(sca_mission_result) * (size_t)total);
+    return 0;
+}
+int sca_get_mission_totals(sca_ctx *c, sca_mission_totals *out, int32_t struct_bytes) {
+    API_ENTER(c);
+    if (int r = mission_refuse(c, "sca_get_mission_totals", mission_totals_check(c->agents_set, c->ms.on, out != nullptr, struct_bytes), -1)) return r;
+    static_assert(sizeof(sca_mission_totals) == sizeof(unsigned long long) * MST_WORDS, "the totals are the device's eight words");
+    CHK(c, hipMemcpyAsync(out, c->ms.totals, sizeof(sca_mission_totals), hipMemcpyDeviceToHost, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+int sca_get_mission_state(sca_ctx *c, int begin, int count, int32_t *cursor, int32_t *ended) {
+    API_ENTER(c);
+    if (int r = mission_refuse(c, "sca_get_mission_state", mission_state_check(c->agents_set, c->ms.on, c->n, begin, count, cursor != nullptr, ended != nullptr), -1)) return r;
+    const int n = c->n;
+    if (count > 0) {
+        CHK(c, hipMemcpyAsync(cursor, c->ms.words + (size_t)MSW_CURSOR * n + begin, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, c->stream));
+        CHK(c, hipMemcpyAsync(ended, c->ms.words + (size_t)MSW_ENDED * n + begin, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, c->stream));
+    }
+    CHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 
@@ -4244,6 +4437,7 @@ int sca_set_shard(sca_ctx *c, int begin, int count) {
     if (c->comm) { c->err = "sca_set_shard with an active communicator (the shard follows from rank / nranks; sca_comm_destroy first)"; return SCA_ERR_STATE; }
     if (c->scenes.on && (begin != 0 || count != c->n)) { c->err = "sca_set_shard with scenes set (sca_set_scenes): scenes are stepped by one rank, whole"; return SCA_ERR_UNSUPPORTED; }
     if (int r = clearance_refuse(c, "sca_set_shard", clearance_check(CLR_SET_SHARD, clearance_state(c), count, 0, true, 0))) return r;
+    if (count < c->n) if (int r = missions_standing(c, "sca_set_shard", MSF_SHARD)) return r;
     c->d.shard_begin = begin; c->d.shard_count = count;
     c->au.forget();                                                       // another shard: the AUTO passes' counts described the old one
     return 0;

@@ -1,0 +1,206 @@
+// sca_missions.h -- mission tables: a row that ends inside a step takes its next mission there (sca_set_missions, sca_get_mission_results,
+// sca_get_mission_totals, sca_get_mission_state; include/sca_hip.h).
+//
+// Every agent row has room for M entries (slot form, entry[M a + j], as the path slots are laid out) and a ring of R result records.  The
+// step's last kernel (k_mission_advance, sca_missions.hip.h) finds the rows that ENDED in the step, writes a result for each and, where the
+// ended flight names a successor, makes the row what sca_respawn_agents naming that row with the entry's values leaves -- through the one
+// row write the respawn kernel uses (respawn_write_row, sca_respawn.h).
+//
+// Everything here is pure and compiles for the host (tests/missions_harness.cpp):
+//   mission_check       every refusal of sca_set_missions and of the getters, with its code; which entries are reachable
+//   mission_ended       did a row end in this step (the flag words in front of and behind K4)
+//   mission_take        the outcome of an ended row and the successor it names
+//   MissionSrc          an entry as the source of respawn_write_row's values
+//   mission_new         how many results of a row's ring have not been collected (the collect's count per row)
+#pragma once
+#include <cstddef>
+#include <cstring>
+#include <vector>
+
+#include "sca_respawn.h"
+
+namespace sca {
+
+static_assert(sizeof(sca_mission) == 128, "sca_mission is 128 bytes: eight 16-byte pieces");
+static_assert(sizeof(sca_mission_result) == 96, "sca_mission_result is 96 bytes: six 16-byte pieces");
+static_assert(sizeof(sca_mission_totals) == 64, "sca_mission_totals is eight 64-bit counters");
+static_assert(offsetof(PubRec, px) == 0 && offsetof(PubRec, py) == 8 && offsetof(PubRec, pz) == 16 && offsetof(PubRec, vx) == 24 && offsetof(PubRec, vy) == 28 &&
+              offsetof(PubRec, vz) == 32 && offsetof(PubRec, flags) == 36 && offsetof(PubRec, radius) == 40, "MissionSrc::piece builds the public record's three pieces");
+static_assert(offsetof(sca_mission_result, total_dist) == 16 && offsetof(sca_mission_result, update) == 48 && offsetof(sca_mission_result, clear) == 64 &&
+              offsetof(sca_scene_clearance, agent_partner) == 16, "k_mission_advance builds the result's six pieces");
+constexpr int MISSION_MAX_M = 127;                 // successors are int8 entry indices of the same row
+constexpr int MISSION_MAX_R = 1 << 16;
+constexpr int64_t MISSION_MAX_SLOTS = 1 << 24;     // M x n and R x n: the tables and the rings stay below 2 GiB each
+constexpr uint8_t MISSION_KNOWN_FLAGS = SCA_MISSION_START_HERE | SCA_MISSION_KEEP_ZAXIS;
+
+// ---- the refusals ------------------------------------------------------------------------------------------------------------------------
+enum MissionFault {
+    MSF_OK = 0,
+    MSF_NO_AGENTS,          // sca_set_agents first                                                           } SCA_ERR_STATE
+    MSF_MID_STEP,           // between a policy pass and its env update                                       }
+    MSF_OFF,                // a getter while no tables are set                                               }
+    MSF_BAD_M,              // M outside 1 .. MISSION_MAX_M                                                   } SCA_ERR_ARG
+    MSF_BAD_R,              // R outside 1 .. MISSION_MAX_R                                                   }
+    MSF_BAD_N,              // n other than the agent count                                                   }
+    MSF_NO_ARRAYS,          // a NULL array                                                                   }
+    MSF_TOO_LARGE,          // M x n or R x n not addressable                                                 }
+    MSF_BAD_SUCCESSOR,      // a successor outside -1 .. M - 1 (entry: the row, or the flat entry index)      }
+    MSF_NOT_FINITE,         // a reachable entry with a position, heading, goal or velocity that is not finite }
+    MSF_NOT_POSITIVE,       // a reachable entry whose pref_speed or max_run_dist is not positive and finite  }
+    MSF_BAD_ZAXIS,          // a reachable entry with a zaxis byte above 1 and no KEEP_ZAXIS                  }
+    MSF_BAD_FLAGS,          // a reachable entry with unknown flag bits                                       }
+    MSF_GET_ARGS,           // a getter: bad struct_bytes, capacity, range or a NULL output                   }
+    MSF_SCENES,             // scenes are set                                                                 } SCA_ERR_UNSUPPORTED
+    MSF_SHARD,              // a shard with count < n                                                         }
+    MSF_COMM,               // a communicator                                                                 }
+    MSF_PARTITION,          // the cell-owner partition                                                       }
+    MSF_PATHS,              // waypoint lists in either form                                                  }
+    MSF_STEP_HOST           // sca_step_host while tables are set                                             }
+};
+inline int mission_error_code(MissionFault f) {
+    return f == MSF_OK ? SCA_OK : f <= MSF_OFF ? SCA_ERR_STATE : f <= MSF_GET_ARGS ? SCA_ERR_ARG : SCA_ERR_UNSUPPORTED;
+}
+// what the rules read of the context
+struct MissionCtx {
+    bool agents, mid_step, scenes, comm, partition, paths;
+    int n, shard_count;
+};
+struct MissionArgs { int M, R, n; const sca_mission *entries; const int32_t *first_ok, *first_fail; };
+// fault: which rule failed; entry: where (a row for first_ok / first_fail, else the flat entry index M a + j; -1: nowhere in particular);
+// max_pref_speed: the largest pref_speed among the reachable entries (0: none reachable)
+struct MissionCheck { MissionFault fault; int64_t entry; double max_pref_speed; };
+
+// what else the context runs: the part that is also asked the other way round (an entry point that would bring scenes, a shard, a
+// communicator, the partition or lists while tables stand refuses with the same fault)
+inline MissionFault mission_context_check(const MissionCtx &C) {
+    if (C.scenes) return MSF_SCENES;
+    if (C.comm) return MSF_COMM;
+    if (C.partition) return MSF_PARTITION;
+    if (C.shard_count < C.n) return MSF_SHARD;
+    if (C.paths) return MSF_PATHS;
+    return MSF_OK;
+}
+inline MissionFault mission_entry_check(const sca_mission &e) {
+    if (e.flags & ~MISSION_KNOWN_FLAGS) return MSF_BAD_FLAGS;
+    const bool here = (e.flags & SCA_MISSION_START_HERE) != 0;
+    for (int k = 0; k < 3; k++) {
+        if (!here && (!restart_finite(e.pos[k]) || !restart_finite(e.heading[k]))) return MSF_NOT_FINITE;
+        if (!restart_finite(e.goal[k]) || !restart_finite(e.goal_heading[k]) || !restart_finite((double)e.vel[k])) return MSF_NOT_FINITE;
+    }
+    if (!(e.pref_speed > 0.0) || !restart_finite(e.pref_speed) || !(e.max_run_dist > 0.0) || !restart_finite(e.max_run_dist)) return MSF_NOT_POSITIVE;
+    if (!(e.flags & SCA_MISSION_KEEP_ZAXIS) && e.zaxis > 1) return MSF_BAD_ZAXIS;
+    return MSF_OK;
+}
+// reached (nullable): [M n] 1 where an entry is reachable from its row's first_ok / first_fail through successors
+inline MissionCheck mission_check(const MissionCtx &C, const MissionArgs &A, uint8_t *reached = nullptr) {
+    if (!C.agents) return {MSF_NO_AGENTS, -1, 0.0};
+    if (C.mid_step) return {MSF_MID_STEP, -1, 0.0};
+    if (const MissionFault f = mission_context_check(C)) return {f, -1, 0.0};
+    if (A.M < 1 || A.M > MISSION_MAX_M) return {MSF_BAD_M, -1, 0.0};
+    if (A.R < 1 || A.R > MISSION_MAX_R) return {MSF_BAD_R, -1, 0.0};
+    if (A.n != C.n) return {MSF_BAD_N, -1, 0.0};
+    if (!A.entries || !A.first_ok || !A.first_fail) return {MSF_NO_ARRAYS, -1, 0.0};
+    if ((int64_t)A.M * A.n > MISSION_MAX_SLOTS || (int64_t)A.R * A.n > MISSION_MAX_SLOTS) return {MSF_TOO_LARGE, -1, 0.0};
+    const int M = A.M;
+    for (int a = 0; a < A.n; a++)
+        if (A.first_ok[a] < -1 || A.first_ok[a] >= M || A.first_fail[a] < -1 || A.first_fail[a] >= M) return {MSF_BAD_SUCCESSOR, a, 0.0};
+    for (int64_t e = 0; e < (int64_t)M * A.n; e++)                       // (every entry's successors, reachable or not: the kernel never reads an index it could not follow)
+        if (A.entries[e].next_ok < -1 || A.entries[e].next_ok >= M || A.entries[e].next_fail < -1 || A.entries[e].next_fail >= M) return {MSF_BAD_SUCCESSOR, e, 0.0};
+    double top = 0.0;
+    std::vector<int> todo;
+    std::vector<uint8_t> seen((std::size_t)M);
+    for (int a = 0; a < A.n; a++) {
+        std::fill(seen.begin(), seen.end(), (uint8_t)0);
+        todo.clear();
+        const auto push = [&](int j) { if (j >= 0 && !seen[(std::size_t)j]) { seen[(std::size_t)j] = 1; todo.push_back(j); } };
+        push(A.first_ok[a]); push(A.first_fail[a]);
+        while (!todo.empty()) {
+            const int j = todo.back();
+            todo.pop_back();
+            const sca_mission &e = A.entries[(int64_t)M * a + j];
+            push(e.next_ok); push(e.next_fail);
+        }
+        for (int j = 0; j < M; j++) {                                    // (in entry order: the first fault reported is the lowest flat index)
+            if (reached) reached[(int64_t)M * a + j] = seen[(std::size_t)j];
+            if (!seen[(std::size_t)j]) continue;
+            const sca_mission &e = A.entries[(int64_t)M * a + j];
+            if (const MissionFault f = mission_entry_check(e)) return {f, (int64_t)M * a + j, 0.0};
+            if (e.pref_speed > top) top = e.pref_speed;
+        }
+    }
+    return {MSF_OK, -1, top};
+}
+// the getters
+inline MissionFault mission_results_check(bool agents, bool on, bool have_out, int capacity, bool have_count, int struct_bytes) {
+    if (!agents) return MSF_NO_AGENTS;
+    if (!on) return MSF_OFF;
+    if (capacity < 0 || !have_count || (capacity > 0 && !have_out) || struct_bytes != (int)sizeof(sca_mission_result)) return MSF_GET_ARGS;
+    return MSF_OK;
+}
+inline MissionFault mission_totals_check(bool agents, bool on, bool have_out, int struct_bytes) {
+    if (!agents) return MSF_NO_AGENTS;
+    if (!on) return MSF_OFF;
+    if (!have_out || struct_bytes != (int)sizeof(sca_mission_totals)) return MSF_GET_ARGS;
+    return MSF_OK;
+}
+inline MissionFault mission_state_check(bool agents, bool on, int n, int begin, int count, bool have_cursor, bool have_ended) {
+    if (!agents) return MSF_NO_AGENTS;
+    if (!on) return MSF_OFF;
+    if (begin < 0 || count < 0 || begin > n || count > n - begin || (count > 0 && (!have_cursor || !have_ended))) return MSF_GET_ARGS;
+    return MSF_OK;
+}
+
+// ---- taking a mission --------------------------------------------------------------------------------------------------------------------
+// A row ENDED in a step when it entered the step without any of at-goal / collision / timeout (old: the flags it entered with -- NOT the old
+// record's at the end of the step, where the pass has set the collision bit of a row it served; the kernel keeps a word per row) and leaves
+// K4 with one (now: d.rec_new).
+SCA_HD bool mission_ended(uint32_t old_flags, uint32_t new_flags) { return !(old_flags & RSP_DONE_FLAGS) && (new_flags & RSP_DONE_FLAGS); }
+enum MissionOutcome { MISSION_ARRIVED = 0, MISSION_COLLIDED = 1, MISSION_TIMED_OUT = 2 };
+struct MissionTake { int outcome, next; };
+// flags: an ended row's flag word.  A collision wins over an arrival, an arrival over a time-out (lifelong.run_lifelong's precedence); the
+// successor is `ok` for an arrival and `fail` otherwise; -1: the row stays finished as it is.
+SCA_HD MissionTake mission_take(uint32_t flags, int ok, int fail) {
+    MissionTake t;
+    t.outcome = (flags & FLAG_COLLISION) ? MISSION_COLLIDED : (flags & FLAG_AT_GOAL) ? MISSION_ARRIVED : MISSION_TIMED_OUT;
+    t.next = t.outcome == MISSION_ARRIVED ? ok : fail;
+    return t;
+}
+// a row has a table where either successor of the flight in the air at sca_set_missions is an entry
+SCA_HD bool mission_has_table(int first_ok, int first_fail) { return first_ok >= 0 || first_fail >= 0; }
+
+// ---- an entry as the source of a row write -------------------------------------------------------------------------------------------------
+// respawn_write_row's second source (the first: the call's block, RespawnBlockSrc).  START_HERE: the position comes from the record the
+// row holds (piece) and the heading is not written; the radius is always the row's.
+struct MissionSrc {
+    const sca_mission *e;
+    SCA_HD RespawnPiece piece(int lane, const PubRec *cur) const {
+        const bool here = (e->flags & SCA_MISSION_START_HERE) != 0;
+        RespawnPiece q;
+        if (lane == 0) { piece_put64(q, 0, here ? cur->px : e->pos[0]); piece_put64(q, 1, here ? cur->py : e->pos[1]); }
+        else if (lane == 1) { piece_put64(q, 0, here ? cur->pz : e->pos[2]); q.w[2] = piece_bits32(e->vel[0]); q.w[3] = piece_bits32(e->vel[1]); }
+        else { q.w[0] = piece_bits32(e->vel[2]); q.w[1] = 0u; piece_put64(q, 1, cur->radius); }      // (flags 0; the radius stays the row's)
+        return q;
+    }
+    SCA_HD bool writes_heading() const { return !(e->flags & SCA_MISSION_START_HERE); }
+    SCA_HD double heading(int k) const { return e->heading[k]; }
+    SCA_HD double goal(int k) const { return e->goal[k]; }
+    SCA_HD double goal_heading(int k) const { return e->goal_heading[k]; }
+    SCA_HD double pref_speed() const { return e->pref_speed; }
+    SCA_HD double max_run_dist() const { return e->max_run_dist; }
+    SCA_HD uint8_t zaxis() const { return e->zaxis; }
+};
+// the `has` word and the bits byte respawn_row reads for a row taken from entry e (lists are refused with tables: no RSP_BIT_MODE_RESET)
+SCA_HD uint32_t mission_has(const sca_mission &e) { return (e.flags & SCA_MISSION_KEEP_ZAXIS) ? 0u : RESPAWN_HAS_ZAXIS; }
+SCA_HD uint8_t mission_bits(uint8_t policy, bool tracker_on) {      // (restart_policy_tracked's rule, for the device too)
+    return tracker_on && (policy == SCA_POLICY_SCA || policy == SCA_POLICY_RVO3D_DUBINS) ? RSP_BIT_TRACKED : 0;
+}
+
+// ---- the results ---------------------------------------------------------------------------------------------------------------------------
+// A row's ring holds its last R results: the result of ending number e (0-based) stands at e % R.  ended counts the endings, collected the
+// value of ended at the last collect: the results not yet collected are the last min(ended - collected, R), oldest first.
+SCA_HD int mission_new(uint32_t ended, uint32_t collected, int R) { const uint32_t d = ended - collected; return d < (uint32_t)R ? (int)d : R; }
+SCA_HD int mission_ring_slot(uint32_t ended, int fresh, int k, int R) { return (int)((ended - (uint32_t)fresh + (uint32_t)k) % (uint32_t)R); }
+constexpr int MISSION_HEAD_BYTES = 64;             // the collect's page-locked block: the count in its first word, the results behind the head
+enum MissionTotal { MST_UPDATES = 0, MST_AGENT_STEPS, MST_ARRIVED, MST_COLLIDED, MST_TIMED_OUT, MST_TAKEN, MST_STOPPED, MST_WORDS = 8 };
+
+}  // namespace sca

@@ -229,6 +229,55 @@ SCA_HD RespawnRow respawn_row(uint8_t bits, uint32_t old_flags, uint32_t has, in
     return w;
 }
 
+// ---- the row write -------------------------------------------------------------------------------------------------------------------------
+// What one lane of the wavefront that serves row `a` stores (lane 0 .. 63), shared by k_respawn (the source of the values: the call's
+// block, RespawnBlockSrc) and k_mission_advance (the row's table entry, MissionSrc in sca_missions.h), so that the two cannot drift apart:
+//   public record     three 16-byte pieces by lanes 0 .. 2
+//   three-component   heading, goal (goal_heading, vpref_ext, now_goal): one component per lane 0 .. 2
+//   scalar fields     lane 0 (respawn_row says which and what)
+//   AgentTrack        consecutive 4-byte words by consecutive lanes from the one initial record (tracked rows under the device tracker)
+// Dev: the arrays a respawn writes (RespawnDev in sca_respawn.hip.h; plain host arrays in the tests' harnesses); null pointers (no tracker,
+// no lists, no closest-approach records) are skipped.  Not here: the done_count stripe (an atomic) and the waypoints (the block's alone).
+struct __attribute__((may_alias, aligned(16))) RespawnPiece { uint32_t w[4]; };
+// a piece from its values, word by word (no local array whose address is taken: nothing of it goes to scratch)
+SCA_HD void piece_put64(RespawnPiece &q, int half, double x) { uint64_t u; __builtin_memcpy(&u, &x, 8); q.w[2 * half] = (uint32_t)u; q.w[2 * half + 1] = (uint32_t)(u >> 32); }
+SCA_HD uint32_t piece_bits32(float x) { uint32_t u; __builtin_memcpy(&u, &x, 4); return u; }
+struct RespawnBlockSrc {
+    const uint8_t *blk; const RespawnLayout &L; int r;
+    SCA_HD RespawnPiece piece(int lane, const PubRec *) const { return ((const RespawnPiece *)(blk + L.off[RSB_REC] + (int64_t)RSP_REC_BYTES * r))[lane]; }
+    SCA_HD bool writes_heading() const { return true; }
+    SCA_HD double heading(int k) const { return ((const double *)(blk + L.off[RSB_HEADING]))[3 * (int64_t)r + k]; }
+    SCA_HD double goal(int k) const { return ((const double *)(blk + L.off[RSB_GOAL]))[3 * (int64_t)r + k]; }
+    SCA_HD double goal_heading(int k) const { return ((const double *)(blk + L.off[RSB_GOAL_HEADING]))[3 * (int64_t)r + k]; }
+    SCA_HD double pref_speed() const { return ((const double *)(blk + L.off[RSB_PREF_SPEED]))[r]; }
+    SCA_HD double max_run_dist() const { return ((const double *)(blk + L.off[RSB_MAX_RUN_DIST]))[r]; }
+    SCA_HD uint8_t zaxis() const { return (blk + L.off[RSB_ZAXIS])[r]; }
+};
+template <class Dev, class Src>
+SCA_HD void respawn_write_row(const Dev &d, int a, int lane, const RespawnRow &w, const Src &s) {
+    if (lane < RSP_REC_BYTES / 16) ((RespawnPiece *)(d.rec + a))[lane] = s.piece(lane, d.rec + a);
+    if (lane < 3) {
+        const int64_t g = 3 * (int64_t)a + lane;
+        if (s.writes_heading()) d.heading[g] = s.heading(lane);
+        d.goal[g] = s.goal(lane);
+        if (w.tracked) { d.vpref_ext[g] = 0.0; if (d.trk_goal_heading) d.trk_goal_heading[g] = s.goal_heading(lane); }
+        if (w.path_len >= 0 && d.now_goal) d.now_goal[g] = __builtin_nan("");
+    }
+    if (lane == 0) {
+        d.total_dist[a] = w.total_dist; d.step_num[a] = w.step_num; d.status[a] = w.status;
+        d.pref_speed[a] = s.pref_speed();
+        d.max_run_dist[a] = s.max_run_dist();
+        if (w.write_zaxis) d.zaxis[a] = s.zaxis();
+        if (w.write_mode) d.vpref_mode[a] = w.mode;
+        d.nbr_n[a] = w.nbr_n; d.nbr_valid[a] = w.nbr_valid; d.near_n[a] = w.near_n;
+        if (d.trk_nbr0) d.trk_nbr0[a] = w.nbr0;
+        if (w.path_len >= 0 && d.path_len) { d.path_len[a] = w.path_len; d.path_rem[a] = w.path_len; }
+        if (d.clear) d.clear[a] = scene_clearance_empty();            // the new mission has met nobody yet; other rows keep this one as a partner
+    }
+    if (w.tracked && d.trk_st)                                         // the AgentTrack record, word by word from the one initial record
+        for (int k = lane; k < d.trk_words; k += 64) d.trk_st[(int64_t)a * d.trk_words + k] = d.trk_init[k];
+}
+
 // ---- the finished list -------------------------------------------------------------------------------------------------------------------
 // An ORDERED compaction: the rows that carry any of at-goal / collision / timeout, ascending ids.  The swarm is cut into tiles of
 // FIN_TILE consecutive rows (one workgroup each); a tile counts its finished rows, finished_offsets turns the counts into each tile's first

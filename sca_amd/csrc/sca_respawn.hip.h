@@ -54,28 +54,8 @@ __global__ __launch_bounds__(RESPAWN_WAVES * 64) void k_respawn(RespawnDev d, co
     const RespawnRow w = respawn_row((blk + L.off[RSB_BITS])[r], old_flags, has, len);
     // K4's counters of the last step, before the record is replaced: a row that was done runs again (sca_active_count between steps)
     if (lane == 0 && w.done_delta) atomicAdd(&d.done_count[(a & 255) * 32], w.done_delta);
-    if (lane < RSP_REC_BYTES / 16) ((restart_piece *)(d.rec + a))[lane] = ((const restart_piece *)(blk + L.off[RSB_REC] + (int64_t)RSP_REC_BYTES * r))[lane];
-    if (lane < 3) {
-        const int64_t g = 3 * (int64_t)a + lane, s = 3 * (int64_t)r + lane;
-        d.heading[g] = ((const double *)(blk + L.off[RSB_HEADING]))[s];
-        d.goal[g] = ((const double *)(blk + L.off[RSB_GOAL]))[s];
-        if (w.tracked) { d.vpref_ext[g] = 0.0; if (d.trk_goal_heading) d.trk_goal_heading[g] = ((const double *)(blk + L.off[RSB_GOAL_HEADING]))[s]; }
-        if (w.path_len >= 0 && d.now_goal) d.now_goal[g] = __builtin_nan("");
-    }
-    if (lane == 0) {
-        d.total_dist[a] = w.total_dist; d.step_num[a] = w.step_num; d.status[a] = w.status;
-        d.pref_speed[a] = ((const double *)(blk + L.off[RSB_PREF_SPEED]))[r];
-        d.max_run_dist[a] = ((const double *)(blk + L.off[RSB_MAX_RUN_DIST]))[r];
-        if (w.write_zaxis) d.zaxis[a] = (blk + L.off[RSB_ZAXIS])[r];
-        if (w.write_mode) d.vpref_mode[a] = w.mode;
-        d.nbr_n[a] = w.nbr_n; d.nbr_valid[a] = w.nbr_valid; d.near_n[a] = w.near_n;
-        if (d.trk_nbr0) d.trk_nbr0[a] = w.nbr0;
-        if (w.path_len >= 0 && d.path_len) { d.path_len[a] = w.path_len; d.path_rem[a] = w.path_len; }
-        if (d.clear) d.clear[a] = scene_clearance_empty();            // the new mission has met nobody yet; other rows keep this one as a partner
-    }
-    if (w.tracked && d.trk_st)                                         // the AgentTrack record, word by word from the one initial record
-        for (int k = lane; k < d.trk_words; k += 64) d.trk_st[(int64_t)a * d.trk_words + k] = d.trk_init[k];
-    if (w.path_len > 0 && d.path_pts) {                                // the row's list into its own room
+    respawn_write_row(d, a, lane, w, RespawnBlockSrc{blk, L, r});      // (sca_respawn.h: the row write k_mission_advance shares)
+    if (w.path_len > 0 && d.path_pts) {                              // the row's list into its own room
         const double *src = (const double *)(blk + L.off[RSB_PATH_PTS]) + 3 * (int64_t)first;
         double *dst = d.path_pts + 3 * path_slot_index(d.W, a);
         for (int k = lane; k < 3 * w.path_len; k += 64) dst[k] = src[k];

@@ -33,6 +33,7 @@ import math
 
 import numpy as np
 
+from . import _lib
 from . import scenarios as _sc
 from . import solver as S
 
@@ -269,6 +270,43 @@ class Agent:
         return self._env._neighbors_of(self.id)
 
 
+class MissionTable:
+    """One agent row's upcoming missions (MACAEnv.set_missions).  entries: Agent-like objects (start, goal, velocity, pref_speed,
+    max_run_dist and goal heading are read off them as respawn() reads them; the id is ignored).  Per entry: start_here -- the row
+    keeps the position and heading it has, the entry's start is ignored; keep_zaxis -- it keeps its z-axis flag; next_ok / next_fail
+    -- the entry flown after an arrival / after a collision or time-out, -1: the row stays finished for the host.  first_ok /
+    first_fail: the successors of the flight that is in the air when the table is set."""
+    def __init__(self, entries, next_ok, next_fail, first_ok=0, first_fail=-1, start_here=True, keep_zaxis=False):
+        k = len(entries)
+        here = [bool(start_here)] * k if isinstance(start_here, (bool, int)) else [bool(x) for x in start_here]
+        keep = [bool(keep_zaxis)] * k if isinstance(keep_zaxis, (bool, int)) else [bool(x) for x in keep_zaxis]
+        self.entries = [(a, here[j], keep[j]) for j, a in enumerate(entries)]
+        self.next_ok, self.next_fail = [int(x) for x in next_ok], [int(x) for x in next_fail]
+        self.first_ok, self.first_fail = int(first_ok), int(first_fail)
+        for x in self.next_ok + self.next_fail + [self.first_ok, self.first_fail]:
+            if not -1 <= x < k:
+                raise ValueError(f'MissionTable: successor {x} names no entry (-1 .. {k - 1})')
+        if k < 1 or len(self.next_ok) != k or len(self.next_fail) != k or len(here) != k or len(keep) != k:
+            raise ValueError('MissionTable: one next_ok, next_fail, start_here and keep_zaxis per entry, and at least one entry')
+
+    @staticmethod
+    def _fail(on_fail, j):
+        return -1 if on_fail == 'stop' else j if on_fail == 'retry' else int(on_fail)
+
+    @classmethod
+    def chain(cls, entries, on_fail='stop', **kw):
+        """entry 0, then 1, ... each after an arrival, the last one stops; on_fail: 'stop', 'retry' (the same entry again) or an index"""
+        k = len(entries)
+        return cls(entries, [j + 1 if j + 1 < k else -1 for j in range(k)], [cls._fail(on_fail, j) for j in range(k)],
+                   first_ok=0, first_fail=cls._fail(on_fail, 0), **kw)
+
+    @classmethod
+    def cycle(cls, entries, on_fail='stop', **kw):
+        """as chain, but the last entry is followed by entry 0 again"""
+        k = len(entries)
+        return cls(entries, [(j + 1) % k for j in range(k)], [cls._fail(on_fail, j) for j in range(k)], first_ok=0, first_fail=cls._fail(on_fail, 0), **kw)
+
+
 class _KdTreeView:
     """Stand-in for mamp.policies.kdTree.KDTree: the tree itself lives on the device; the permutation the reference
     carries from step to step (kdTree.py:43-45) is readable."""
@@ -468,6 +506,7 @@ class MACAEnv(_FlatAgents):
         self._paths_on = False
         self._path_stale = False
         self._path_assigned = set()
+        self._missions = None           # the tables of set_missions (None: none stand)
 
     def set_agents(self, agents, obstacles=None):
         if obstacles is None:
@@ -477,6 +516,7 @@ class MACAEnv(_FlatAgents):
                 raise ValueError('agent.id must equal its list index (kdTree.py:64)')
         self.agents = agents
         self.obstacles = obstacles
+        self._missions = None           # (a new agent set drops the mission tables, here as in the library)
         n = len(agents)
         # which attributes the agents disagree on (empty: one value per context)
         self.per_agent_attributes = self._create(agents, self.device, len(obstacles), obstacles)
@@ -602,6 +642,92 @@ class MACAEnv(_FlatAgents):
         """The rows that carry any of at-goal / collision / timeout, ascending ids, compacted on the device (sca_get_finished): a
         structured array of _lib.FINISHED_DTYPE (id, flags, step_num, total_dist, pos)."""
         return self.solver.finished(capacity)
+
+    # ---- mission tables: finished rows take their next mission inside the step (sca_set_missions) ---------------------------
+    def set_missions(self, tables, results=4):
+        """tables: a dict from agent id to a MissionTable (rows that are not named have no table); results: the room of every row's
+        result ring -- at least the endings a row can have between two mission_results() calls.  From now on a row that ends inside a
+        step takes the successor its table names there, by respawn()'s rule and without a host round trip, so run_steps(k) runs
+        traffic; a row whose ended flight names no successor stays finished (finished() lists it, respawn() may restart it).  The
+        entries are read off Agent-like objects as respawn() reads them; a row keeps its radius, its policy and its attributes, so an
+        entry whose policy differs from the row's is a ValueError.  None or {} drops the tables.
+        An entry's zaxis byte (start and goal share x and y) is worked out from the entry's OWN start and goal, as respawn() does.  For a
+        start_here entry that is its nominal start (the Agent-like object's initial_pos), not the spot the row will stand on when it
+        takes the entry, which nobody knows yet: where the two may differ in x or y by more than the rule's 1e-5, give the entry
+        keep_zaxis, or a nominal start that says what the leg is."""
+        if self.agents is None:
+            raise RuntimeError('set_missions: set_agents first')
+        if self._row_cache is not None:
+            raise RuntimeError('set_missions: between a policy pass and its env update (agent.find_next_action was called): env.step() first')
+        if not tables:
+            self.solver.set_missions(0, 0, None, None, None)
+            self._missions = None
+            return
+        n = len(self.agents)
+        M = max(len(t.entries) for t in tables.values())
+        e = np.zeros((n, M), _lib.MISSION_DTYPE)
+        e['pref_speed'] = e['max_run_dist'] = 1.0                     # (rows and slots nobody reaches: legal values, never read)
+        e['next_ok'] = e['next_fail'] = -1
+        first_ok, first_fail = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+        for i, t in tables.items():
+            if not 0 <= int(i) < n:
+                raise ValueError('set_missions: %r names no row of this env, 0 .. %d' % (i, n - 1))
+            old = self.agents[i]
+            for j, (a, here, keep) in enumerate(t.entries):
+                if a.policy.policy_id != old.policy.policy_id:
+                    raise ValueError(f'set_missions: entry {j} of agent {i} has policy {type(a.policy).__name__}, the row runs {type(old.policy).__name__} (a row keeps its policy)')
+                if len(a._path):
+                    raise ValueError(f'set_missions: entry {j} of agent {i} brings a path: waypoint lists and mission tables exclude each other')
+                start, goal6 = np.asarray(a.initial_pos, np.float64), np.asarray(a.goal_pos, np.float64)
+                r = e[i, j]
+                r['pos'], r['heading'], r['goal'], r['goal_heading'], r['vel'] = a._pos, a._heading, goal6[:3], goal6[3:6], a._vel
+                r['pref_speed'], r['max_run_dist'] = a.pref_speed, a.max_run_dist
+                r['zaxis'] = S.zaxis_flags(start[None, :], goal6[None, :])[0]
+                r['flags'] = (S.MISSION_START_HERE if here else 0) | (S.MISSION_KEEP_ZAXIS if keep else 0)
+                r['next_ok'], r['next_fail'] = t.next_ok[j], t.next_fail[j]
+            first_ok[i], first_fail[i] = t.first_ok, t.first_fail
+        self.solver.set_missions(M, int(results), e, first_ok, first_fail)
+        self._missions = dict(tables)
+
+    def mission_results(self):
+        """The results not yet collected (sca_get_mission_results): a structured array of _lib.MISSION_RESULT_DTYPE, ascending id and
+        within a row oldest first.  env.agents[i]'s goal / start mirrors move to the entry the row flies now (the Agent object stays:
+        its state views read the device)."""
+        if self._missions is None:
+            raise RuntimeError('mission_results: no mission tables are set -- set_missions first')
+        res = self.solver.mission_results()
+        for r in res:
+            i, j = int(r['id']), int(r['next'])
+            if j < 0:
+                continue
+            a, (src, here, _) = self.agents[i], self._missions[i].entries[j]
+            a.goal_pos, a.goal_global_frame, a.goal_heading_frame = src.goal_pos.copy(), src.goal_global_frame.copy(), src.goal_heading_frame.copy()
+            a.initial_pos = np.concatenate([r['pos'], a.initial_pos[3:]]) if here else src.initial_pos.copy()
+            a.pref_speed, a.max_run_dist = src.pref_speed, src.max_run_dist
+            self.goal[i] = a.goal_global_frame
+        if len(res):
+            self._stale = True
+        return res
+
+    def run_steps(self, k):
+        """k resident steps in one library call (sca_run_steps) and one synchronisation; with mission tables set the rows that end on
+        the way take their next missions there.  Returns the number of running agents."""
+        import time
+        if self._row_cache is not None or self.v_pref_fn is not None:
+            raise RuntimeError('run_steps: the steps are resident -- not between a policy pass and its env update, not with a host-side v_pref_fn')
+        self._sync_paths()
+        t0 = time.perf_counter()
+        served = max(1, self._active)
+        self.solver.run_steps(int(k), self.neighbor_mode)
+        self._active = self.solver.active_count()                  # (synchronises: the burst is over when this returns)
+        per_step = (time.perf_counter() - t0) / max(1, int(k)) / served
+        for _ in range(int(k)):
+            self._time_cum.append(self._time_cum[-1] + per_step)
+        self._stale = True
+        self._path_stale = self._paths_on
+        self._nbr_cache = None
+        self._vpref_cache = None
+        return self._active
 
     pos = property(lambda self: self._state('pos'))
     vel = property(lambda self: self._state('vel'))

@@ -9,7 +9,13 @@ total_dist, pos).
 
 spawn_margin (metres): an admission gate in front of every respawn (MACAEnv.respawn(margin=), sca_respawn_agents_gated) -- a mission
 whose start is not free by that margin WAITS: its row stays finished where it is, and the mission is offered again in front of every
-later step, together with that step's new ones, waiting ones first, in ascending id."""
+later step, together with that step's new ones, waiting ones first, in ascending id.
+
+    stats = run_missions(env, tables, steps, burst=1, on_result=None)
+
+is the same traffic with the missions on the device (MACAEnv.set_missions, sca_set_missions): a row that ends takes its table's
+successor inside the step, so the env is stepped in bursts of `burst` resident steps with one synchronisation each, and only the results
+cross the link."""
 from . import solver as S
 
 
@@ -65,5 +71,29 @@ def run_lifelong(env, next_mission, steps, on_done=None, spawn_margin=None):
         active = env._active
     if gated:
         stats['waiting'] = len(waiting)
+    stats['live_fraction'] = stats['agent_steps'] / float(n * stats['steps']) if stats['steps'] else 0.0
+    return stats
+
+
+def run_missions(env, tables, steps, burst=1, on_result=None):
+    """tables: a dict from agent id to an env.MissionTable.  Steps the env in env.run_steps(burst) chunks and collects the results behind
+    each chunk (on_result(agent, result) per result, a record of _lib.MISSION_RESULT_DTYPE).  Returns run_lifelong's stats keys from the
+    device's totals: `respawned` the missions taken, `retired` the endings without a successor (such a row stays finished; the host may
+    respawn it).  The run ends early, at a chunk's end, when nobody runs."""
+    n = len(env.agents)
+    burst = max(1, int(burst))
+    env.set_missions(tables, results=max(4, burst))
+    done = 0
+    while done < int(steps) and env._active > 0:
+        k = min(burst, int(steps) - done)
+        env.run_steps(k)
+        done += k
+        res = env.mission_results()
+        if on_result is not None:
+            for r in res:
+                on_result(env.agents[int(r['id'])], r)
+    t = env.solver.mission_totals()
+    stats = dict(steps=t['updates'], arrived=t['arrived'], collided=t['collided'], timed_out=t['timed_out'], respawned=t['taken'], retired=t['stopped'],
+                 agent_steps=t['agent_steps'], live_fraction=0.0)
     stats['live_fraction'] = stats['agent_steps'] / float(n * stats['steps']) if stats['steps'] else 0.0
     return stats

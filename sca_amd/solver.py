@@ -12,6 +12,7 @@ from . import _lib
 
 POL_SCA, POL_RVO3D, POL_SRVO3D, POL_ORCA3D, POL_ORCA3D_LP, POL_RVO3D_DUBINS = range(6)
 FLAG_AT_GOAL, FLAG_COLLISION, FLAG_TIMEOUT = 1, 2, 4
+MISSION_START_HERE, MISSION_KEEP_ZAXIS = 1, 2                  # sca_mission_flag
 SPAWN_ADMITTED, SPAWN_BLOCKED_AGENT, SPAWN_BLOCKED_OBSTACLE, SPAWN_BLOCKED_ENTRY = 0, 1, 2, 3      # SCA_SPAWN_*: a gated respawn's verdict per row
 NBR_KDTREE, NBR_GRID, NBR_KDTREE_HOSTBUILD, NBR_AUTO = 0, 1, 2, 3
 FORM_SOLVE_SPLIT, FORM_TRACK_FUSED, FORM_REPLAN_LANE, FORM_REPLAN_FEW, FORM_LP_LANE, FORM_SOLVE_FB, FORM_ACTION_FB, FORM_AUTO_TAIL = 1, 2, 4, 8, 16, 32, 64, 128   # sca_last_pass_forms
@@ -555,6 +556,53 @@ class BatchedSolver:
                   'sca_get_finished')
         self.finished_count = int(cnt.value)
         return out[:max(0, min(cap, self.finished_count))]
+
+    # ---- mission tables: finished rows take their next mission inside the step (sca_set_missions) ------------------------------
+    def set_missions(self, M, R, entries, first_ok, first_fail):
+        """Every row gets room for M mission entries and a ring of R result records (sca_set_missions; include/sca_hip.h has the rule and
+        what is refused).  entries: a structured array of _lib.MISSION_DTYPE, (n, M) or flat in slot form entries[M a + j]; first_ok /
+        first_fail: per row the successors of the flight in the air (-1 / -1: the row has no table).  M = 0 with entries None drops the
+        tables."""
+        if entries is None and int(M) == 0:
+            self._chk(self.L.sca_set_missions(self.ctx, 0, 0, 0, None, None, None), 'sca_set_missions')
+            self._missions = None
+            return
+        entries = np.ascontiguousarray(entries, _lib.MISSION_DTYPE).reshape(-1)
+        first_ok = np.ascontiguousarray(first_ok, np.int32).reshape(-1)
+        first_fail = np.ascontiguousarray(first_fail, np.int32).reshape(-1)
+        if len(entries) != int(M) * len(first_ok) or len(first_fail) != len(first_ok):
+            raise ValueError(f'set_missions: {len(entries)} entries, {len(first_ok)} / {len(first_fail)} first successors where M = {M}')
+        self._chk(self.L.sca_set_missions(self.ctx, int(M), int(R), len(first_ok), entries.ctypes.data_as(C.POINTER(_lib.Mission)),
+                                          _lib.ptr(first_ok, C.c_int32), _lib.ptr(first_fail, C.c_int32)), 'sca_set_missions')
+        self._missions = (int(M), int(R))
+
+    def mission_results(self, capacity=None):
+        """The results not yet collected, ascending id and within a row oldest first: a structured array of _lib.MISSION_RESULT_DTYPE
+        (id, entry, flags, step_num, total_dist, pos, update, next, clear); they are marked collected.  capacity None: room for every
+        ring.  `mission_result_count` holds their number; where it exceeds `capacity` nothing is handed out or marked."""
+        R = (getattr(self, '_missions', None) or (0, 1))[1]
+        cap = int(self.n) * R if capacity is None else int(capacity)
+        out = np.zeros(max(cap, 1), _lib.MISSION_RESULT_DTYPE)
+        cnt = C.c_int(0)
+        self._chk(self.L.sca_get_mission_results(self.ctx, out.ctypes.data_as(C.POINTER(_lib.MissionResult)), cap, C.byref(cnt),
+                                                 _lib.MISSION_RESULT_DTYPE.itemsize), 'sca_get_mission_results')
+        self.mission_result_count = int(cnt.value)
+        return out[:self.mission_result_count if self.mission_result_count <= cap else 0]
+
+    def mission_totals(self):
+        """dict(updates, agent_steps, arrived, collided, timed_out, taken, stopped): 64-bit counters since set_missions, over all rows"""
+        t = _lib.MissionTotals()
+        self._chk(self.L.sca_get_mission_totals(self.ctx, C.byref(t), C.sizeof(t)), 'sca_get_mission_totals')
+        return {k: int(getattr(t, k)) for k, _ in _lib.MissionTotals._fields_ if k != 'reserved'}
+
+    def mission_state(self, begin=0, count=None):
+        """(cursor, ended) of rows begin .. begin + count - 1: the entry whose successors the row's next ending follows (-1: first_ok /
+        first_fail) and the number of its endings so far, int32 each"""
+        begin = int(begin)
+        count = max(0, int(self.n) - begin) if count is None else int(count)
+        cursor, ended = np.zeros(max(count, 1), np.int32), np.zeros(max(count, 1), np.int32)
+        self._chk(self.L.sca_get_mission_state(self.ctx, begin, count, _lib.ptr(cursor, C.c_int32), _lib.ptr(ended, C.c_int32)), 'sca_get_mission_state')
+        return cursor[:max(count, 0)], ended[:max(count, 0)]
 
     # ---- scene checkpoints (sca_save_scenes / sca_load_scenes) ---------------------------------------------------------------
     def scene_checkpoint_bytes(self, scene):

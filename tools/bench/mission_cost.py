@@ -1,0 +1,210 @@
+#!/usr/bin/env python
+"""What mission tables (sca_set_missions: finished rows take their next mission inside the step) cost.  ONE process; the parent commit's
+library is loaded beside this build's (--root: the parent's checkout, built).  Four parts, merged into profiles/mission_cost.json:
+
+    step      the step time of a context that NEVER sets tables, parent against this build: the two enqueue the same kernels.  The legs are
+              alternated window by window (spawn_probe_cost.py's part_step; --here-first swaps the context that is made first); reported:
+              the windows, medians, and whether this build's median lies inside the parent's own min-max -- no fixed number.
+    tables    this build, tables set and nobody ending against no tables, alternated the same way, in two step forms: `burst` (one
+              sca_run_steps of the window: with tables an AUTO burst builds no tree ahead and lets no event ride) and `stepwise`
+              (sca_run_steps(1) per step, which plans none of that in either leg: what is left is the dispatch and the read of the flag words).
+    lifelong  the ping-pong circle at N = 4096 ORCA3D for `--lifelong-steps` steps under ONE rule (the three-entry table of
+              examples/run_sca.py --device-missions): run_lifelong driven by that rule on the host, run_missions at burst 1 and at burst 64;
+              steps/s, missions/s and whether the three stats are identical.
+    collect   sca_get_mission_results with 0 / 64 / all rows holding a new result beside sca_get_finished listing as many rows, N = 4096.
+
+workloads: respawn_cost.py's (c3_auto: circle N = 4096 ORCA3D SCA_NBR_AUTO; c4: circle N = 100 000 SCA, device tracker, SCA_NBR_KDTREE)"""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, HERE)
+from respawn_cost import WORKLOADS, make_leg, step_window, summary                    # noqa: E402
+from scenes_cost import host, load_package                                            # noqa: E402
+from spawn_probe_cost import part_step                                                # noqa: E402
+
+
+def idle_tables(_lib, sc, n):
+    """one entry per row that nobody takes before the window ends: from where it stands to its start, after an arrival"""
+    e = np.zeros((n, 1), _lib.MISSION_DTYPE)
+    e['goal'][:, 0], e['goal_heading'][:, 0] = sc['start'][:, :3], sc['start'][:, 3:6]
+    e['pref_speed'], e['max_run_dist'], e['flags'] = 1.0, 1e6, 1
+    e['next_ok'], e['next_fail'] = 0, 0
+    return e, np.zeros(n, np.int32), np.zeros(n, np.int32)
+
+
+def stepwise_window(leg, args):
+    leg['reset']()
+    sol, mode = leg['sol'], leg['mode']
+    for _ in range(args.warm):
+        sol.run_steps(1, mode)
+    sol.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.window):
+        sol.run_steps(1, mode)
+    sol.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / args.window
+
+
+def part_tables(here, w, args):
+    S, scenarios = here[0], here[1]
+    _lib = importlib.import_module('sca_here._lib')
+    order = ['on', 'off'] if args.here_first else ['off', 'on']
+    legs = {k: make_leg(S, scenarios, w) for k in order}
+    e, ok, fail = idle_tables(_lib, legs['on']['sc'], legs['on']['n'])
+    legs['on']['sol'].set_missions(1, 1, e, ok, fail)
+    out = {'order': order}
+    for form, window in (('burst', step_window), ('stepwise', stepwise_window)):
+        for leg in legs.values():
+            window(leg, args)
+        ms = {k: [] for k in legs}
+        for _ in range(args.alternations):
+            for k, leg in legs.items():
+                ms[k].append(window(leg, args))
+        o = {k: summary(v) for k, v in ms.items()}
+        o['on_minus_off_ms'] = round(o['on']['median_ms'] - o['off']['median_ms'], 5)
+        o['inside_off_spread'] = bool(o['off']['min_ms'] <= o['on']['median_ms'] <= o['off']['max_ms'])
+        out[form] = o
+    t = legs['on']['sol'].mission_totals()
+    out['endings_in_the_on_leg'] = t['arrived'] + t['collided'] + t['timed_out']
+    for leg in legs.values():
+        leg['sol'].close()
+    return out
+
+
+def part_lifelong(args):
+    n, steps = 4096, args.lifelong_steps
+    E = importlib.import_module('sca_here.env')
+    LL = importlib.import_module('sca_here.lifelong')
+
+    def world():
+        env = E.MACAEnv()
+        agents = E.build_circle_agents(n, policy=E.ORCA3DPolicy)
+        env.set_agents(agents, obstacles=[])
+        first = {a.id: (list(a.initial_pos), list(a.goal_pos)) for a in agents}
+
+        def entry(i, start, goal):
+            return E.Agent(start_pos=start, goal_pos=goal, vel=[0.0, 0.0, 0.0], radius=agents[i].radius, pref_speed=agents[i].pref_speed, policy=E.ORCA3DPolicy, id=i)
+        tables = {i: E.MissionTable([entry(i, goal, start), entry(i, start, goal), entry(i, start, goal)], next_ok=[1, 0, 0], next_fail=[2, 2, 2], first_ok=0, first_fail=2,
+                                    start_here=[True, True, False]) for i, (start, goal) in first.items()}
+        return env, tables, entry
+    out = {}
+    for name in ('run_lifelong', 'run_missions_burst_1', 'run_missions_burst_64'):
+        env, T, entry = world()
+        t0 = time.perf_counter()
+        if name == 'run_lifelong':
+            state = dict.fromkeys(T, -1)
+
+            def next_mission(a, row):
+                f = int(row['flags'])
+                arrived = bool(f & 1) and not f & 2
+                t, c = T[a.id], state[a.id]
+                j = (t.first_ok if arrived else t.first_fail) if c < 0 else (t.next_ok[c] if arrived else t.next_fail[c])
+                state[a.id] = j
+                src, here, _ = t.entries[j]
+                new = entry(a.id, list(row['pos']) + list(a.heading_global_frame) if here else list(src.initial_pos), list(src.goal_pos))
+                new.max_run_dist = src.max_run_dist
+                return new
+            stats = LL.run_lifelong(env, next_mission, steps)
+        else:
+            stats = LL.run_missions(env, T, steps, burst=int(name.rsplit('_', 1)[1]))
+        dt = time.perf_counter() - t0
+        missions = stats['arrived'] + stats['collided'] + stats['timed_out']
+        out[name] = dict(stats, seconds=round(dt, 3), missions=missions, missions_per_s=round(missions / dt, 2), steps_per_s=round(stats['steps'] / dt, 1))
+        env.solver.close()
+    keys = ('steps', 'arrived', 'collided', 'timed_out', 'respawned', 'retired', 'agent_steps', 'live_fraction')
+    out['stats_identical'] = all(out[a][k] == out['run_lifelong'][k] for a in out for k in keys)
+    return out
+
+
+def part_collect(here, args):
+    S, scenarios = here[0], here[1]
+    _lib = importlib.import_module('sca_here._lib')
+    n = 4096
+    sc = scenarios.circle(n)
+    zaxis = S.zaxis_flags(sc['start'], sc['goal'])
+    out = {}
+    for count in (0, 64, n):
+        mrd = np.full(n, 1e6)
+        mrd[np.linspace(0, n - 1, count).astype(int) if count else []] = 0.05          # these rows time out in their first step and stop
+        sol = S.BatchedSolver(max_agents=n, max_obstacles=1)
+        sol.set_obstacles(np.zeros((0, 3)), np.zeros(0))
+        sol.set_agents(np.full(n, 0.5), np.ones(n), sc['goal'][:, :3], np.full(n, 3, np.uint8), zaxis, mrd)
+        e, ok, fail = idle_tables(_lib, sc, n)
+        e['next_ok'], e['next_fail'] = -1, -1
+        sol.set_missions(1, 1, e, np.where(mrd < 1.0, 0, -1).astype(np.int32), np.full(n, -1, np.int32))   # (these rows have a table; a failure stops them)
+        fin, res = [], []
+        for s in range(args.samples + 1):
+            sol.set_state(sc['start'][:, :3], np.zeros((n, 3), np.float32), sc['start'][:, 3:6], np.zeros(n, np.uint8), np.zeros(n), np.zeros(n, np.int32))
+            sol.run_steps(2, S.NBR_KDTREE)
+            sol.synchronize()
+            t0 = time.perf_counter()
+            f = sol.finished()
+            t1 = time.perf_counter()
+            r = sol.mission_results()
+            t2 = time.perf_counter()
+            if s:
+                fin.append((t1 - t0) * 1e3)
+                res.append((t2 - t1) * 1e3)
+            got = len(r)
+        out[str(count)] = {'get_finished': summary(fin), 'get_mission_results': summary(res), 'results': got, 'finished_rows': len(f)}
+        sol.close()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--root', default=None, help="the parent commit's checkout (built)")
+    ap.add_argument('--parts', default='step,tables,lifelong,collect')
+    ap.add_argument('--workloads', default=','.join(WORKLOADS))
+    ap.add_argument('--window', type=int, default=200)
+    ap.add_argument('--warm', type=int, default=20)
+    ap.add_argument('--alternations', type=int, default=5)
+    ap.add_argument('--samples', type=int, default=30)
+    ap.add_argument('--here-first', action='store_true', help='step and tables parts: this build\'s (the tables\') context is made and timed first')
+    ap.add_argument('--lifelong-steps', type=int, default=20000)
+    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'mission_cost.json'))
+    args = ap.parse_args()
+    here = load_package(REPO, 'sca_here')
+    parent = load_package(args.root, 'sca_parent') if args.root else None
+    result = json.load(open(args.out)) if os.path.exists(args.out) else {}
+    result.update(host=host(), window_steps=args.window, warm_steps=args.warm, alternations=args.alternations, samples=args.samples)
+    parts = args.parts.split(',')
+    suffix = '_here_first' if args.here_first else ''
+
+    def save():                                                                       # after every part: a later part that fails loses nothing
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, 'w') as f:
+            json.dump(result, f, indent=1, sort_keys=True)
+            f.write('\n')
+    for name in args.workloads.split(','):
+        w = WORKLOADS[name]
+        entry = result.setdefault('workloads', {}).setdefault(name, {'desc': w['desc'], 'n': w['n']})
+        if 'step' in parts:
+            entry['step' + suffix] = part_step(here, parent, w, args)
+            print(name, 'step', json.dumps(entry['step' + suffix]), flush=True)
+            save()
+        if 'tables' in parts:
+            entry['tables' + suffix] = part_tables(here, w, args)
+            print(name, 'tables', json.dumps(entry['tables' + suffix]), flush=True)
+            save()
+    if 'lifelong' in parts:
+        key = 'lifelong_circle_4096_%d_steps' % args.lifelong_steps
+        result[key] = part_lifelong(args)
+        print(key, json.dumps(result[key]), flush=True)
+        save()
+    if 'collect' in parts:
+        result['collect_4096'] = part_collect(here, args)
+        print('collect', json.dumps(result['collect_4096']), flush=True)
+    save()
+
+
+if __name__ == '__main__':
+    main()
