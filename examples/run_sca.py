@@ -59,7 +59,7 @@ def lifelong(args, agents, obstacles, pol, dubins):
             return E.Agent(start_pos=start, goal_pos=goal, vel=[0.0, 0.0, 0.0], radius=a.radius, pref_speed=a.pref_speed, policy=pol, id=i)
         tables = {i: E.MissionTable([entry(i, goal, start), entry(i, start, goal), entry(i, start, goal)], next_ok=[1, 0, 0], next_fail=[2, 2, 2],
                                     first_ok=0, first_fail=2, start_here=[True, True, False]) for i, (start, goal) in first.items()}
-        stats = run_missions(env, tables, args.lifelong, burst=args.burst)
+        stats = run_missions(env, tables, args.lifelong, burst=args.burst, spawn_margin=args.spawn_margin)
     else:
         stats = run_lifelong(env, next_mission, args.lifelong) if args.spawn_margin is None else \
             run_lifelong(env, next_mission, args.lifelong, spawn_margin=args.spawn_margin)
@@ -91,14 +91,15 @@ def main():
                          'timed out starts again from its original start (MACAEnv.respawn; the Dubins tracker then runs on the device)')
     ap.add_argument('--spawn-margin', type=float, default=None, metavar='M',
                     help='with --lifelong: a drone is respawned only where its start is free by M metres (of every other drone, of every '
-                         'obstacle and of the drones admitted with it); otherwise its mission waits and is offered again after every step')
+                         'obstacle and of the drones admitted with it); otherwise its mission waits and is offered again after every step '
+                         '(with --device-missions the gate runs on the device too: MACAEnv.set_missions(spawn_margin=))')
     ap.add_argument('--device-missions', action='store_true',
                     help='with --lifelong: the ping-pong rule as a mission table per drone on the device -- a drone that ends takes its next '
                          'mission inside the step, no host call per step (MACAEnv.set_missions)')
     ap.add_argument('--burst', type=int, default=1, metavar='K', help='with --device-missions: K resident steps per library call')
     args = ap.parse_args()
-    if args.device_missions and (args.lifelong <= 0 or args.spawn_margin is not None):
-        ap.error('--device-missions goes with --lifelong STEPS and without --spawn-margin (the admission gate is a host call)')
+    if args.device_missions and args.lifelong <= 0:
+        ap.error('--device-missions goes with --lifelong STEPS')
 
     n = args.agents
     if args.scenario == 'circle':

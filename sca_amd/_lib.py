@@ -111,6 +111,11 @@ class MissionTotals(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ('updates', 'agent_steps', 'arrived', 'collided', 'timed_out', 'taken', 'stopped', 'reserved')]
 
 
+class MissionGateTotals(C.Structure):
+    """sca_mission_gate_totals: the gate's counters (sca_get_mission_gate_totals), 64 bytes"""
+    _fields_ = [(k, C.c_uint64) for k in ('offered', 'admitted', 'blocked_agent', 'blocked_obstacle', 'blocked_entry', 'over_cap', 'dropped', 'reserved')]
+
+
 CHECKPOINT_SECTIONS = 14                                         # sca_scene_checkpoint_layout's offsets
 
 
@@ -170,6 +175,9 @@ SIGNATURES = {
     'sca_get_mission_results': (C.c_int, [C.c_void_p, C.POINTER(MissionResult), C.c_int, C.POINTER(C.c_int), C.c_int32]),
     'sca_get_mission_totals': (C.c_int, [C.c_void_p, C.POINTER(MissionTotals), C.c_int32]),
     'sca_get_mission_state': (C.c_int, [C.c_void_p, C.c_int, C.c_int, ip, ip]),
+    'sca_set_mission_gate': (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int32]),
+    'sca_get_mission_gate_state': (C.c_int, [C.c_void_p, C.c_int, C.c_int, ip, ip, ip]),
+    'sca_get_mission_gate_totals': (C.c_int, [C.c_void_p, C.POINTER(MissionGateTotals), C.c_int32]),
     'sca_set_path_state': (C.c_int, [C.c_void_p, ip, dp]),
     'sca_policy_pass': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_get_actions': (C.c_int, [C.c_void_p, fp]),

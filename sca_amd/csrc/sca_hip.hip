@@ -33,6 +33,7 @@
 #include "sca_respawn.hip.h"
 #include "sca_missions.h"
 #include "sca_missions.hip.h"
+#include "sca_mission_gate.hip.h"
 #include "sca_spawn.h"
 #include "sca_spawn.hip.h"
 
@@ -381,6 +382,18 @@ struct sca_ctx {
         uint8_t *host = nullptr;            // the collect's page-locked block: the count's head, host_cap results behind it
         int64_t host_cap = 0;
         long long updates = 0;              // env updates enqueued since sca_set_missions
+        // the admission gate (sca_set_mission_gate): nothing of it exists until a gate is set; freed with the tables
+        struct Gate {
+            bool on = false;
+            double margin = 0.0;
+            int cap = 0;
+            int32_t *words = nullptr;       // device [4 n]: waiting, verdict, refusals, fresh
+            unsigned long long *totals = nullptr;    // device [MGT_WORDS]
+            int32_t *list = nullptr;        // device: the count (16 words), the tiles' counts [2 tiles], ids / entry / world [cap] each
+            ClearPoint *query = nullptr;    // device [cap]
+            SpawnPartial *partials = nullptr;        // device [ptiles][cap]
+            int64_t partials_room = 0;      // ... how many it has room for
+        } gate;
     } ms;
 };
 
@@ -451,6 +464,8 @@ static int missions_drop(sca_ctx *c);
 static int missions_standing(sca_ctx *c, const char *who, MissionFault f);
 static int missions_refresh_live(sca_ctx *c);
 static int missions_host_flight(sca_ctx *c, const int32_t *ids, const int32_t *verdict, int count);
+static int missions_gate_new_state(sca_ctx *c);
+static int missions_gate_partials(sca_ctx *c, int m);
 static ClearanceState clearance_state(const sca_ctx *c);
 static int clearance_refuse(sca_ctx *c, const char *who, ClearanceFault f);
 static int api_enter(sca_ctx *c);
@@ -1049,6 +1064,7 @@ int sca_set_obstacles(sca_ctx *c, int m, const double *pos, const double *radius
     API_ENTER(c);
     ARG(c, m >= 0 && m <= c->max_m);
     ARG(c, m == 0 || (pos && radius));
+    if (c->ms.gate.on) if (int r = missions_gate_partials(c, m)) return r;    // (a mission gate probes every obstacle: its partials follow the set, or the call is refused with nothing changed)
     if (int r = scene_obstacles_drop(c)) return r;                     // one shared set again (sca_set_scene_obstacles)
     c->m = m; c->d.m = m;
     c->max_obs_radius = 0;
@@ -1244,6 +1260,7 @@ int sca_set_state(sca_ctx *c, const double *pos, const float *vel, const double 
     CHK(c, hipStreamSynchronize(c->stream));
     state_replaced(c);
     if (int r = missions_refresh_live(c)) return r;                       // (mission tables stay; which rows enter the next step running follows the new flags)
+    if (int r = missions_gate_new_state(c)) return r;                     // (a gate: the rows that are unfinished now lose their pending mission)
     scene_harvest_clear_fresh(c, 0, nullptr);                             // (a state from outside: nothing that finished before it is reported after it)
     if (c->part_on) return part_classify(c);                              // a complete state again: ownership follows from it
     return 0;
@@ -4181,6 +4198,12 @@ static int mission_refuse(sca_ctx *c, const char *who, MissionFault f, int64_t e
 }
 // an entry point that would bring what tables exclude, while tables stand
 static int missions_standing(sca_ctx *c, const char *who, MissionFault f) { return c->ms.on ? mission_refuse(c, who, f, -1) : 0; }
+static void missions_gate_free_scratch(sca_ctx::Missions::Gate &g) {
+    if (g.list) (void)hipFree(g.list);
+    if (g.query) (void)hipFree(g.query);
+    if (g.partials) (void)hipFree(g.partials);
+    g.list = nullptr; g.query = nullptr; g.partials = nullptr; g.partials_room = 0;
+}
 static int missions_drop(sca_ctx *c) {
     sca_ctx::Missions &m = c->ms;
     if (!m.entries && !m.host) { m = sca_ctx::Missions{}; return 0; }
@@ -4191,9 +4214,14 @@ static int missions_drop(sca_ctx *c) {
     if (m.totals) (void)hipFree(m.totals);
     if (m.counts) (void)hipFree(m.counts);
     if (m.host) (void)hipHostFree(m.host);
+    missions_gate_free_scratch(m.gate);
+    if (m.gate.words) (void)hipFree(m.gate.words);
+    if (m.gate.totals) (void)hipFree(m.gate.totals);
     m = sca_ctx::Missions{};
     return 0;
 }
+enum MissionGateWord { MGW_WAITING = 0, MGW_VERDICT, MGW_REFUSALS, MGW_FRESH, MGW_WORDS };
+constexpr int MGL_HEAD = 16;               // the gate's list: the count in its first word, the tiles' counts behind the head
 enum MissionWord { MSW_FIRST_OK = 0, MSW_FIRST_FAIL, MSW_CURSOR, MSW_FLYING, MSW_ENDED, MSW_COLLECTED, MSW_LIVE, MSW_WORDS };
 // flags changed between two steps (a new state, a respawn, the tables' arrival): which rows enter the next step without a done flag
 static int missions_refresh_live(sca_ctx *c) {
@@ -4207,7 +4235,33 @@ static int missions_host_flight(sca_ctx *c, const int32_t *ids, const int32_t *v
     if (!c->ms.on) return 0;
     hipLaunchKernelGGL(k_mission_host_flight, dim3((count + MISSION_T - 1) / MISSION_T), dim3(MISSION_T), 0, c->stream, ids, verdict, count, c->n, c->ms.words + (size_t)MSW_FLYING * c->n);
     CHK(c, hipGetLastError());
+    if (c->ms.gate.on) {                                                   // a gate: a named row the call wrote loses its pending mission
+        hipLaunchKernelGGL(k_mission_gate_named, dim3((count + MISSION_T - 1) / MISSION_T), dim3(MISSION_T), 0, c->stream, ids, verdict, count, c->n,
+                           c->ms.gate.words + (size_t)MGW_WAITING * c->n, c->ms.gate.totals);
+        CHK(c, hipGetLastError());
+    }
     return missions_refresh_live(c);
+}
+static int missions_gate_new_state(sca_ctx *c) {
+    if (!c->ms.on || !c->ms.gate.on) return 0;
+    hipLaunchKernelGGL(k_mission_gate_clear, dim3((c->n + MISSION_T - 1) / MISSION_T), dim3(MISSION_T), 0, c->stream, (const PubRec *)c->d.rec,
+                       c->ms.gate.words + (size_t)MGW_WAITING * c->n, c->n, c->ms.gate.totals);
+    CHK(c, hipGetLastError());
+    return 0;
+}
+// The partials for m obstacles: sized by sca_set_mission_gate for the set as it stands and by sca_set_obstacles, in front of everything
+// else it does, when a larger set arrives under a standing gate -- never inside a step.  A refusal changes nothing.
+static int missions_gate_partials(sca_ctx *c, int m) {
+    sca_ctx::Missions::Gate &g = c->ms.gate;
+    const int64_t want = spawn_partials(c->n, m, g.cap, SPAWN_TILE);
+    if (want <= g.partials_room) return 0;
+    if (want * (int64_t)sizeof(SpawnPartial) > MISSION_GATE_MAX_SCRATCH) { c->err = "sca_set_obstacles: with this many obstacles the mission gate's scratch (partner tiles x max_per_step x 32 bytes) would exceed 1 GiB -- set the gate again with a smaller max_per_step first"; return SCA_ERR_ARG; }
+    SpawnPartial *p = nullptr;
+    CHK(c, hipStreamSynchronize(c->stream));                              // (no launch still uses the old ones)
+    CHK(c, hipMalloc((void **)&p, sizeof(SpawnPartial) * (size_t)want));
+    if (g.partials) (void)hipFree(g.partials);
+    g.partials = p; g.partials_room = want;
+    return 0;
 }
 static int missions_advance(sca_ctx *c) {
     const sca_ctx::Missions &s = c->ms;
@@ -4227,7 +4281,24 @@ static int missions_advance(sca_ctx *c) {
     m.first_ok = s.words + (size_t)MSW_FIRST_OK * n; m.first_fail = s.words + (size_t)MSW_FIRST_FAIL * n;
     m.cursor = s.words + (size_t)MSW_CURSOR * n; m.flying = s.words + (size_t)MSW_FLYING * n; m.ended = (uint32_t *)(s.words + (size_t)MSW_ENDED * n);
     m.results = s.results; m.totals = s.totals; m.update = ++c->ms.updates; m.M = s.M; m.R = s.R;
-    hipLaunchKernelGGL(k_mission_advance, dim3((n + MISSION_T - 1) / MISSION_T), dim3(MISSION_T), 0, c->stream, m);
+    if (s.gate.on) {                      // the gate: the endings, the candidates' places, their probe, the world words, the gate and the take
+        const sca_ctx::Missions::Gate &q = s.gate;
+        MissionGateDev g{};
+        const int tiles = finished_tiles(n);
+        g.m = m; g.obs = c->d.obs;
+        g.waiting = q.words + (size_t)MGW_WAITING * n; g.verdict = q.words + (size_t)MGW_VERDICT * n; g.refusals = q.words + (size_t)MGW_REFUSALS * n;
+        g.fresh = q.words + (size_t)MGW_FRESH * n;
+        g.count = q.list; g.tile_counts = q.list + MGL_HEAD; g.ids = g.tile_counts + 2 * (size_t)tiles; g.entry = g.ids + q.cap; g.world = g.entry + q.cap;
+        g.query = q.query; g.partials = q.partials; g.totals = q.totals; g.margin = q.margin;
+        g.n_obs = c->d.m; g.cap = q.cap; g.tiles = tiles; g.ptiles = spawn_tiles(n, c->d.m, SPAWN_TILE);
+        hipLaunchKernelGGL(k_mission_gate_end, dim3(tiles), dim3(MISSION_T), 0, c->stream, g);
+        hipLaunchKernelGGL(k_mission_gate_place, dim3(tiles), dim3(MISSION_T), 0, c->stream, g);
+        hipLaunchKernelGGL(k_mission_gate_probe, dim3(g.ptiles, std::min(MISSION_GATE_SLOTS, spawn_chunks(q.cap))), dim3(SPAWN_WAVES * 64), 0, c->stream, g);
+        hipLaunchKernelGGL(k_mission_gate_fold, dim3((q.cap + 255) / 256), dim3(256), 0, c->stream, g);
+        hipLaunchKernelGGL(k_mission_gate_take, dim3((q.cap + MISSION_GATE_WAVES - 1) / MISSION_GATE_WAVES), dim3(MISSION_GATE_WAVES * 64), 0, c->stream, g);
+    } else {
+        hipLaunchKernelGGL(k_mission_advance, dim3((n + MISSION_T - 1) / MISSION_T), dim3(MISSION_T), 0, c->stream, m);
+    }
     CHK(c, hipGetLastError());
     positions_replaced(c);                // a taken row may stand anywhere now and the host does not learn of it: no sizing hint from older trees (no value)
     return 0;
@@ -4296,6 +4367,104 @@ int sca_get_mission_totals(sca_ctx *c, sca_mission_totals *out, int32_t struct_b
     if (int r = mission_refuse(c, "sca_get_mission_totals", mission_totals_check(c->agents_set, c->ms.on, out != nullptr, struct_bytes), -1)) return r;
     static_assert(sizeof(sca_mission_totals) == sizeof(unsigned long long) * MST_WORDS, "the totals are the device's eight words");
     CHK(c, hipMemcpyAsync(out, c->ms.totals, sizeof(sca_mission_totals), hipMemcpyDeviceToHost, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+// ---- the admission gate in front of the take (the rules: sca_missions.h; the kernels: sca_mission_gate.hip.h) --------------------------------
+static int mission_gate_refuse(sca_ctx *c, const char *who, MissionGateFault f) {
+    const std::string w = std::string(who);
+    switch (f) {
+    case MGF_OK: return 0;
+    case MGF_NO_TABLES: c->err = w + ": no mission tables are set -- sca_set_missions first"; break;
+    case MGF_MID_STEP: c->err = w + " between a policy pass and its env update: finish the step first"; break;
+    case MGF_NEVER_SET: c->err = w + ": no gate has been set since the tables arrived -- sca_set_mission_gate first"; break;
+    case MGF_BAD_MARGIN: c->err = w + ": margin must be finite and not negative"; break;
+    case MGF_BAD_CAP: c->err = w + ": max_per_step must be 0 (min(n, " + std::to_string(SPAWN_BATCH) + ")) or 1 .. " + std::to_string(c->n); break;
+    case MGF_TOO_LARGE: c->err = w + ": the probe's scratch (partner tiles x max_per_step x 32 bytes) would exceed 1 GiB: a smaller max_per_step"; break;
+    default: c->err = w + ": a NULL output, a range outside 0 .. n or struct_bytes other than the struct's size";
+    }
+    return mission_gate_error_code(f);
+}
+int sca_set_mission_gate(sca_ctx *c, int on, double margin, int32_t max_per_step) {
+    API_ENTER(c);
+    const MissionGateCheck k = mission_gate_check(c->ms.on, c->near_valid, c->n, c->d.m, on, margin, max_per_step);
+    if (int r = mission_gate_refuse(c, "sca_set_mission_gate", k.fault)) return r;
+    sca_ctx::Missions::Gate &g = c->ms.gate;
+    const int n = c->n;
+    if (!on) {
+        if (!g.on) return 0;
+        hipLaunchKernelGGL(k_mission_gate_clear, dim3((n + MISSION_T - 1) / MISSION_T), dim3(MISSION_T), 0, c->stream, (const PubRec *)nullptr,
+                           g.words + (size_t)MGW_WAITING * n, n, g.totals);
+        CHK(c, hipGetLastError());
+        CHK(c, hipStreamSynchronize(c->stream));
+        g.on = false;
+        return 0;
+    }
+    // A call that fails leaves the gate as it stood -- on or off, its scratch, its cap and its margin: everything new is allocated into
+    // locals and taken over at the end, so that rows waiting under a standing gate are neither stranded nor lost to `dropped`.
+    CHK(c, hipStreamSynchronize(c->stream));                              // (no launch still uses the scratch of an earlier gate)
+    const auto fail = [&](hipError_t e, const char *what) { c->err = std::string("sca_set_mission_gate: ") + what + ": " + hipGetErrorString(e); return SCA_ERR_HIP; };
+    hipError_t e;
+    int32_t *w = nullptr, *list = nullptr;
+    unsigned long long *t = nullptr;
+    ClearPoint *query = nullptr;
+    SpawnPartial *partials = nullptr;
+    const auto undo = [&](hipError_t err, const char *what) {
+        if (w) (void)hipFree(w);
+        if (t) (void)hipFree(t);
+        if (list) (void)hipFree(list);
+        if (query) (void)hipFree(query);
+        if (partials) (void)hipFree(partials);
+        return fail(err, what);
+    };
+    if (!g.words) {                                                        // the first gate behind these tables: nobody waits, nothing is counted
+        std::vector<int32_t> words((size_t)MGW_WORDS * n, 0);
+        std::fill(words.begin() + (size_t)MGW_WAITING * n, words.begin() + (size_t)(MGW_WAITING + 1) * n, -1);
+        if ((e = hipMalloc((void **)&w, sizeof(int32_t) * words.size())) != hipSuccess) return undo(e, "no device memory for the words");
+        if ((e = hipMalloc((void **)&t, sizeof(unsigned long long) * MGT_WORDS)) != hipSuccess) return undo(e, "no device memory for the totals");
+        if ((e = hipMemcpyAsync(w, words.data(), sizeof(int32_t) * words.size(), hipMemcpyHostToDevice, c->stream)) == hipSuccess &&
+            (e = hipMemsetAsync(t, 0, sizeof(unsigned long long) * MGT_WORDS, c->stream)) == hipSuccess)
+            e = hipStreamSynchronize(c->stream);                           // (`words` is the host's: the upload has read it when this returns)
+        if (e != hipSuccess) return undo(e, "the upload of the words");
+    }
+    const bool fresh = k.cap != g.cap || !g.list;
+    const int64_t want = spawn_partials(n, c->d.m, k.cap, SPAWN_TILE);    // (mission_gate_check has held it against MISSION_GATE_MAX_SCRATCH)
+    if (fresh) {                                                           // another cap: a list, queries and partials of its own
+        const size_t words = (size_t)MGL_HEAD + 2 * (size_t)finished_tiles(n) + 3 * (size_t)k.cap;
+        if ((e = hipMalloc((void **)&list, sizeof(int32_t) * words)) != hipSuccess) return undo(e, "no device memory for the candidates");
+        if ((e = hipMemsetAsync(list, 0, sizeof(int32_t) * words, c->stream)) != hipSuccess || (e = hipStreamSynchronize(c->stream)) != hipSuccess) return undo(e, "clearing the candidates");
+        if ((e = hipMalloc((void **)&query, sizeof(ClearPoint) * (size_t)k.cap)) != hipSuccess) return undo(e, "no device memory for the queries");
+        if ((e = hipMalloc((void **)&partials, sizeof(SpawnPartial) * (size_t)std::max<int64_t>(want, 1))) != hipSuccess) return undo(e, "no device memory for the probe's partials");
+    } else if (int r = missions_gate_partials(c, c->d.m)) {               // the same cap: the partials only grow (a failure leaves the old ones)
+        (void)undo(hipSuccess, "");
+        return r;
+    }
+    if (w) { g.words = w; g.totals = t; }                                  // nothing can fail from here on
+    if (fresh) {
+        missions_gate_free_scratch(g);
+        g.list = list; g.query = query; g.partials = partials; g.partials_room = want; g.cap = k.cap;
+    }
+    g.margin = margin; g.on = true;
+    return 0;
+}
+int sca_get_mission_gate_state(sca_ctx *c, int begin, int count, int32_t *waiting, int32_t *verdict, int32_t *refusals) {
+    API_ENTER(c);
+    const sca_ctx::Missions::Gate &g = c->ms.gate;
+    if (int r = mission_gate_refuse(c, "sca_get_mission_gate_state", mission_gate_state_check(c->ms.on, g.words != nullptr, c->n, begin, count, waiting && verdict && refusals))) return r;
+    const int n = c->n;
+    if (count > 0) {
+        CHK(c, hipMemcpyAsync(waiting, g.words + (size_t)MGW_WAITING * n + begin, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, c->stream));
+        CHK(c, hipMemcpyAsync(verdict, g.words + (size_t)MGW_VERDICT * n + begin, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, c->stream));
+        CHK(c, hipMemcpyAsync(refusals, g.words + (size_t)MGW_REFUSALS * n + begin, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, c->stream));
+    }
+    CHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+int sca_get_mission_gate_totals(sca_ctx *c, sca_mission_gate_totals *out, int32_t struct_bytes) {
+    API_ENTER(c);
+    const sca_ctx::Missions::Gate &g = c->ms.gate;
+    if (int r = mission_gate_refuse(c, "sca_get_mission_gate_totals", mission_gate_totals_check(c->ms.on, g.words != nullptr, out != nullptr, struct_bytes))) return r;
+    CHK(c, hipMemcpyAsync(out, g.totals, sizeof(sca_mission_gate_totals), hipMemcpyDeviceToHost, c->stream));
     CHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

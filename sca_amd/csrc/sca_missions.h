@@ -12,12 +12,18 @@
 //   mission_take        the outcome of an ended row and the successor it names
 //   MissionSrc          an entry as the source of respawn_write_row's values
 //   mission_new         how many results of a row's ring have not been collected (the collect's count per row)
+// and the admission gate in front of the take (sca_set_mission_gate; the kernels: sca_mission_gate.hip.h):
+//   mission_gate_check  every refusal of sca_set_mission_gate and of the gate's getters, the cap and the scratch a gate needs
+//   mission_gate_place  a candidate's place in the step's offer order from its class, its rank in the class and the waiting rows' count
+//   mission_gate_query  the sphere a candidate is tested as (START_HERE: where the row stands)
+//   mission_gate_settle a verdict into the row's waiting / verdict / refusal words and the counter that moves
 #pragma once
 #include <cstddef>
 #include <cstring>
 #include <vector>
 
 #include "sca_respawn.h"
+#include "sca_spawn.h"
 
 namespace sca {
 
@@ -202,5 +208,82 @@ SCA_HD int mission_new(uint32_t ended, uint32_t collected, int R) { const uint32
 SCA_HD int mission_ring_slot(uint32_t ended, int fresh, int k, int R) { return (int)((ended - (uint32_t)fresh + (uint32_t)k) % (uint32_t)R); }
 constexpr int MISSION_HEAD_BYTES = 64;             // the collect's page-locked block: the count in its first word, the results behind the head
 enum MissionTotal { MST_UPDATES = 0, MST_AGENT_STEPS, MST_ARRIVED, MST_COLLIDED, MST_TIMED_OUT, MST_TAKEN, MST_STOPPED, MST_WORDS = 8 };
+
+// ---- the admission gate in front of the take ---------------------------------------------------------------------------------------------
+// While a gate is set an ended row whose flight names successor j does not take it at once: it becomes a CANDIDATE for entry j.  A step's
+// candidates are offered in this order: the rows WAITING since an earlier step in ascending id, then the step's NEW candidates in
+// ascending id (lifelong.run_lifelong's offer order).  The first `cap` of them are tested by sca_respawn_agents_gated's rule (sca_spawn.h:
+// spawn_world, spawn_entry_blocks, spawn_verdict), the others wait with SCA_SPAWN_OVER_CAP.  An admitted row is written by
+// respawn_write_row; a refused row keeps every word and waits: waiting[a] = j, verdict[a] the word, refusals[a] + 1.
+enum MissionGateFault {
+    MGF_OK = 0,
+    MGF_NO_TABLES,          // no mission tables are set                                                      } SCA_ERR_STATE
+    MGF_MID_STEP,           // between a policy pass and its env update                                       }
+    MGF_NEVER_SET,          // a getter while no gate has been set since the tables arrived                   }
+    MGF_BAD_MARGIN,         // a margin that is negative or not finite                                        } SCA_ERR_ARG
+    MGF_BAD_CAP,            // max_per_step outside 0 .. n                                                    }
+    MGF_TOO_LARGE,          // the partials (spawn_tiles x cap x 32 bytes) above MISSION_GATE_MAX_SCRATCH     }
+    MGF_GET_ARGS            // a getter: bad struct_bytes, range or a NULL output                             }
+};
+inline int mission_gate_error_code(MissionGateFault f) { return f == MGF_OK ? SCA_OK : f <= MGF_NEVER_SET ? SCA_ERR_STATE : SCA_ERR_ARG; }
+constexpr int64_t MISSION_GATE_MAX_SCRATCH = (int64_t)1 << 30;
+// cap: the candidates tested per step (0 asked: min(n, SPAWN_BATCH)); scratch: the partials' bytes for n agents and m obstacles
+struct MissionGateCheck { MissionGateFault fault; int cap; int64_t scratch; };
+SCA_HD int mission_gate_cap(int n, int32_t max_per_step) { return max_per_step > 0 ? max_per_step : n < SPAWN_BATCH ? n : SPAWN_BATCH; }
+inline int64_t mission_gate_scratch(int n, int m, int cap) { return spawn_partials(n, m, cap, SPAWN_TILE) * (int64_t)sizeof(SpawnPartial); }
+// sca_set_mission_gate(on, margin, max_per_step): `on` 0 reads neither the margin nor the cap
+inline MissionGateCheck mission_gate_check(bool tables, bool mid_step, int n, int m, int on, double margin, int32_t max_per_step) {
+    if (!tables) return {MGF_NO_TABLES, 0, 0};
+    if (mid_step) return {MGF_MID_STEP, 0, 0};
+    if (!on) return {MGF_OK, 0, 0};
+    if (!(margin >= 0.0) || !restart_finite(margin)) return {MGF_BAD_MARGIN, 0, 0};
+    if (max_per_step < 0 || max_per_step > n) return {MGF_BAD_CAP, 0, 0};
+    const int cap = mission_gate_cap(n, max_per_step);
+    const int64_t scratch = mission_gate_scratch(n, m, cap);
+    if (scratch > MISSION_GATE_MAX_SCRATCH) return {MGF_TOO_LARGE, cap, scratch};
+    return {MGF_OK, cap, scratch};
+}
+inline MissionGateFault mission_gate_state_check(bool tables, bool ever, int n, int begin, int count, bool have_outputs) {
+    if (!tables) return MGF_NO_TABLES;
+    if (!ever) return MGF_NEVER_SET;
+    if (begin < 0 || count < 0 || begin > n || count > n - begin || (count > 0 && !have_outputs)) return MGF_GET_ARGS;
+    return MGF_OK;
+}
+inline MissionGateFault mission_gate_totals_check(bool tables, bool ever, bool have_out, int struct_bytes) {
+    if (!tables) return MGF_NO_TABLES;
+    if (!ever) return MGF_NEVER_SET;
+    if (!have_out || struct_bytes != (int)sizeof(sca_mission_gate_totals)) return MGF_GET_ARGS;
+    return MGF_OK;
+}
+// a row's class in a step: `waiting` its waiting word behind the endings (the entry it is a candidate for, -1: none), fresh: it ended in
+// this very step
+enum MissionGateClass { MGC_NONE = 0, MGC_WAITING = 1, MGC_NEW = 2 };
+SCA_HD int mission_gate_class(int32_t waiting, bool fresh) { return waiting < 0 ? MGC_NONE : fresh ? MGC_NEW : MGC_WAITING; }
+// rank: the candidates of the same class with a lower id; waiting_total: the context's waiting candidates
+SCA_HD int mission_gate_place(int cls, int rank, int waiting_total) { return cls == MGC_NEW ? waiting_total + rank : rank; }
+// the candidate's sphere: the row's own radius at the entry's start, with START_HERE where the row stands now
+SCA_HD ClearPoint mission_gate_query(const sca_mission &e, const PubRec &cur) {
+    const bool here = (e.flags & SCA_MISSION_START_HERE) != 0;
+    ClearPoint q;
+    q.x = here ? cur.px : e.pos[0]; q.y = here ? cur.py : e.pos[1]; q.z = here ? cur.pz : e.pos[2]; q.r = cur.radius;
+    return q;
+}
+// the gate's totals: the device's eight words in sca_mission_gate_totals' order; a verdict v moves word MGT_ADMITTED + v
+enum MissionGateTotal { MGT_OFFERED = 0, MGT_ADMITTED, MGT_BLOCKED_AGENT, MGT_BLOCKED_OBSTACLE, MGT_BLOCKED_ENTRY, MGT_OVER_CAP, MGT_DROPPED, MGT_WORDS = 8 };
+static_assert(MGT_ADMITTED + SCA_SPAWN_BLOCKED_AGENT == MGT_BLOCKED_AGENT && MGT_ADMITTED + SCA_SPAWN_BLOCKED_OBSTACLE == MGT_BLOCKED_OBSTACLE &&
+              MGT_ADMITTED + SCA_SPAWN_BLOCKED_ENTRY == MGT_BLOCKED_ENTRY && MGT_ADMITTED + SCA_SPAWN_OVER_CAP == MGT_OVER_CAP, "a verdict names its counter");
+static_assert(sizeof(sca_mission_gate_totals) == 8 * MGT_WORDS, "sca_mission_gate_totals is eight 64-bit counters");
+// what a verdict leaves of the candidate for entry j: take -- the row is written (cursor = flying = j, live 1, its done_count stripe + 1,
+// MST_TAKEN + 1); else the row keeps every word and waits.  counter: the gate's total that moves by one.
+struct MissionGateSettle { int32_t waiting, verdict, refusals; int counter; bool take; };
+SCA_HD MissionGateSettle mission_gate_settle(int32_t verdict, int32_t entry, int32_t refusals) {
+    MissionGateSettle s;
+    s.take = verdict == SCA_SPAWN_ADMITTED;
+    s.waiting = s.take ? -1 : entry;
+    s.verdict = verdict;
+    s.refusals = s.take ? refusals : refusals + 1;
+    s.counter = MGT_ADMITTED + verdict;
+    return s;
+}
 
 }  // namespace sca

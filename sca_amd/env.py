@@ -507,6 +507,8 @@ class MACAEnv(_FlatAgents):
         self._path_stale = False
         self._path_assigned = set()
         self._missions = None           # the tables of set_missions (None: none stand)
+        self._mission_gate = False      # set_missions(spawn_margin=): the admission gate on the device
+        self._mission_pending = {}      # ... id -> (entry, where the flight that named it ended): named, not known to be admitted yet
 
     def set_agents(self, agents, obstacles=None):
         if obstacles is None:
@@ -517,6 +519,7 @@ class MACAEnv(_FlatAgents):
         self.agents = agents
         self.obstacles = obstacles
         self._missions = None           # (a new agent set drops the mission tables, here as in the library)
+        self._mission_gate, self._mission_pending = False, {}
         n = len(agents)
         # which attributes the agents disagree on (empty: one value per context)
         self.per_agent_attributes = self._create(agents, self.device, len(obstacles), obstacles)
@@ -629,6 +632,7 @@ class MACAEnv(_FlatAgents):
                 self.agents[a.id]._env = None                    # (the replaced object reads its own attributes again)
             self.agents[a.id] = a
             self.goal[a.id] = a.goal_global_frame
+            self._mission_pending.pop(a.id, None)                # (a mission gate: the row's pending mission is gone with this respawn)
             self._path_assigned.discard(a.id)
         _bind(agents, self)
         self._active += int(was_done.sum())
@@ -644,7 +648,7 @@ class MACAEnv(_FlatAgents):
         return self.solver.finished(capacity)
 
     # ---- mission tables: finished rows take their next mission inside the step (sca_set_missions) ---------------------------
-    def set_missions(self, tables, results=4):
+    def set_missions(self, tables, results=4, spawn_margin=None, max_per_step=None):
         """tables: a dict from agent id to a MissionTable (rows that are not named have no table); results: the room of every row's
         result ring -- at least the endings a row can have between two mission_results() calls.  From now on a row that ends inside a
         step takes the successor its table names there, by respawn()'s rule and without a host round trip, so run_steps(k) runs
@@ -654,7 +658,10 @@ class MACAEnv(_FlatAgents):
         An entry's zaxis byte (start and goal share x and y) is worked out from the entry's OWN start and goal, as respawn() does.  For a
         start_here entry that is its nominal start (the Agent-like object's initial_pos), not the spot the row will stand on when it
         takes the entry, which nobody knows yet: where the two may differ in x or y by more than the rule's 1e-5, give the entry
-        keep_zaxis, or a nominal start that says what the leg is."""
+        keep_zaxis, or a nominal start that says what the leg is.
+        spawn_margin (metres): the admission gate on the device (sca_set_mission_gate) -- a row takes its successor only where the
+        start is free by that margin, as respawn(margin=) decides it; a refused row stays finished and is offered again behind every
+        step, waiting rows first.  max_per_step: the candidates tested per step (None: min(n, 4096))."""
         if self.agents is None:
             raise RuntimeError('set_missions: set_agents first')
         if self._row_cache is not None:
@@ -662,6 +669,7 @@ class MACAEnv(_FlatAgents):
         if not tables:
             self.solver.set_missions(0, 0, None, None, None)
             self._missions = None
+            self._mission_gate, self._mission_pending = False, {}
             return
         n = len(self.agents)
         M = max(len(t.entries) for t in tables.values())
@@ -688,6 +696,9 @@ class MACAEnv(_FlatAgents):
             first_ok[i], first_fail[i] = t.first_ok, t.first_fail
         self.solver.set_missions(M, int(results), e, first_ok, first_fail)
         self._missions = dict(tables)
+        self._mission_gate, self._mission_pending = spawn_margin is not None, {}
+        if self._mission_gate:
+            self.solver.set_mission_gate(spawn_margin, 0 if max_per_step is None else int(max_per_step))
 
     def mission_results(self):
         """The results not yet collected (sca_get_mission_results): a structured array of _lib.MISSION_RESULT_DTYPE, ascending id and
@@ -696,16 +707,35 @@ class MACAEnv(_FlatAgents):
         if self._missions is None:
             raise RuntimeError('mission_results: no mission tables are set -- set_missions first')
         res = self.solver.mission_results()
-        for r in res:
-            i, j = int(r['id']), int(r['next'])
+        if self._mission_gate:
+            # A named successor may still be waiting: a row's mirrors move when it is ADMITTED.  The results are in ascending id and within
+            # a row oldest first, and a waiting row cannot end: a row that ended again was admitted in between (a self-successor too, whose
+            # cursor does not change), and the last named entry of a row was admitted if the row does not wait now.  A start_here entry
+            # starts where the flight that named it ended.
+            moved, pending = [], self._mission_pending
+            for r in res:
+                i = int(r['id'])
+                if i in pending:
+                    moved.append((i,) + pending.pop(i))
+                if int(r['next']) >= 0:
+                    pending[i] = (int(r['next']), r['pos'].copy())
+            if pending:
+                waiting = self.solver.mission_gate_state()[0]
+                for i in sorted(pending):
+                    if waiting[i] < 0:
+                        moved.append((i,) + pending.pop(i))
+        else:
+            moved = [(int(r['id']), int(r['next']), r['pos']) for r in res]
+        for i, j, pos in moved:
             if j < 0:
                 continue
+            r = dict(pos=pos)
             a, (src, here, _) = self.agents[i], self._missions[i].entries[j]
             a.goal_pos, a.goal_global_frame, a.goal_heading_frame = src.goal_pos.copy(), src.goal_global_frame.copy(), src.goal_heading_frame.copy()
             a.initial_pos = np.concatenate([r['pos'], a.initial_pos[3:]]) if here else src.initial_pos.copy()
             a.pref_speed, a.max_run_dist = src.pref_speed, src.max_run_dist
             self.goal[i] = a.goal_global_frame
-        if len(res):
+        if len(res) or moved:
             self._stale = True
         return res
 

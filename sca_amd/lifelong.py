@@ -11,11 +11,12 @@ spawn_margin (metres): an admission gate in front of every respawn (MACAEnv.resp
 whose start is not free by that margin WAITS: its row stays finished where it is, and the mission is offered again in front of every
 later step, together with that step's new ones, waiting ones first, in ascending id.
 
-    stats = run_missions(env, tables, steps, burst=1, on_result=None)
+    stats = run_missions(env, tables, steps, burst=1, on_result=None, spawn_margin=None)
 
 is the same traffic with the missions on the device (MACAEnv.set_missions, sca_set_missions): a row that ends takes its table's
 successor inside the step, so the env is stepped in bursts of `burst` resident steps with one synchronisation each, and only the results
-cross the link."""
+cross the link.  spawn_margin: the same admission gate on the device (MACAEnv.set_missions(spawn_margin=), sca_set_mission_gate), with
+run_lifelong's offer order: the traffic is the host loop's under the same rule."""
 from . import solver as S
 
 
@@ -75,14 +76,15 @@ def run_lifelong(env, next_mission, steps, on_done=None, spawn_margin=None):
     return stats
 
 
-def run_missions(env, tables, steps, burst=1, on_result=None):
+def run_missions(env, tables, steps, burst=1, on_result=None, spawn_margin=None):
     """tables: a dict from agent id to an env.MissionTable.  Steps the env in env.run_steps(burst) chunks and collects the results behind
     each chunk (on_result(agent, result) per result, a record of _lib.MISSION_RESULT_DTYPE).  Returns run_lifelong's stats keys from the
     device's totals: `respawned` the missions taken, `retired` the endings without a successor (such a row stays finished; the host may
-    respawn it).  The run ends early, at a chunk's end, when nobody runs."""
+    respawn it).  The run ends early, at a chunk's end, when nobody runs.  With spawn_margin the dict gains `deferred`, the refusals
+    counted per attempt (offered - admitted), and `waiting`, the missions still pending at the end, as run_lifelong's does."""
     n = len(env.agents)
     burst = max(1, int(burst))
-    env.set_missions(tables, results=max(4, burst))
+    env.set_missions(tables, results=max(4, burst), spawn_margin=spawn_margin)
     done = 0
     while done < int(steps) and env._active > 0:
         k = min(burst, int(steps) - done)
@@ -95,5 +97,8 @@ def run_missions(env, tables, steps, burst=1, on_result=None):
     t = env.solver.mission_totals()
     stats = dict(steps=t['updates'], arrived=t['arrived'], collided=t['collided'], timed_out=t['timed_out'], respawned=t['taken'], retired=t['stopped'],
                  agent_steps=t['agent_steps'], live_fraction=0.0)
+    if spawn_margin is not None:
+        g = env.solver.mission_gate_totals()
+        stats.update(deferred=g['offered'] - g['admitted'], waiting=int((env.solver.mission_gate_state()[0] >= 0).sum()))
     stats['live_fraction'] = stats['agent_steps'] / float(n * stats['steps']) if stats['steps'] else 0.0
     return stats

@@ -14,6 +14,7 @@ POL_SCA, POL_RVO3D, POL_SRVO3D, POL_ORCA3D, POL_ORCA3D_LP, POL_RVO3D_DUBINS = ra
 FLAG_AT_GOAL, FLAG_COLLISION, FLAG_TIMEOUT = 1, 2, 4
 MISSION_START_HERE, MISSION_KEEP_ZAXIS = 1, 2                  # sca_mission_flag
 SPAWN_ADMITTED, SPAWN_BLOCKED_AGENT, SPAWN_BLOCKED_OBSTACLE, SPAWN_BLOCKED_ENTRY = 0, 1, 2, 3      # SCA_SPAWN_*: a gated respawn's verdict per row
+SPAWN_OVER_CAP = 4                                               # ... and, under set_mission_gate only, "not tested in this step"
 NBR_KDTREE, NBR_GRID, NBR_KDTREE_HOSTBUILD, NBR_AUTO = 0, 1, 2, 3
 FORM_SOLVE_SPLIT, FORM_TRACK_FUSED, FORM_REPLAN_LANE, FORM_REPLAN_FEW, FORM_LP_LANE, FORM_SOLVE_FB, FORM_ACTION_FB, FORM_AUTO_TAIL = 1, 2, 4, 8, 16, 32, 64, 128   # sca_last_pass_forms
 FORM_WAYPOINTS = 256                                          # k_waypoint ran (waypoint lists are set)
@@ -603,6 +604,32 @@ class BatchedSolver:
         cursor, ended = np.zeros(max(count, 1), np.int32), np.zeros(max(count, 1), np.int32)
         self._chk(self.L.sca_get_mission_state(self.ctx, begin, count, _lib.ptr(cursor, C.c_int32), _lib.ptr(ended, C.c_int32)), 'sca_get_mission_state')
         return cursor[:max(count, 0)], ended[:max(count, 0)]
+
+    # ---- the admission gate in front of the take (sca_set_mission_gate) --------------------------------------------------------
+    def set_mission_gate(self, margin, max_per_step=0):
+        """While tables stand a row takes its next mission only where its start is free by `margin` metres (sca_set_mission_gate; the
+        rule is sca_respawn_agents_gated's, include/sca_hip.h); a refused row waits and is offered again behind every step.
+        max_per_step: the candidates tested per step (0: min(n, 4096)).  margin None: the gate goes off, pending missions are dropped."""
+        if margin is None:
+            self._chk(self.L.sca_set_mission_gate(self.ctx, 0, 0.0, 0), 'sca_set_mission_gate')
+        else:
+            self._chk(self.L.sca_set_mission_gate(self.ctx, 1, float(margin), int(max_per_step)), 'sca_set_mission_gate')
+
+    def mission_gate_state(self, begin=0, count=None):
+        """(waiting, verdict, refusals) of rows begin .. begin + count - 1, int32 each: the entry a row waits for (-1: none), the word of
+        its last test (SPAWN_*) and how often it has been refused"""
+        begin = int(begin)
+        count = max(0, int(self.n) - begin) if count is None else int(count)
+        out = [np.zeros(max(count, 1), np.int32) for _ in range(3)]
+        self._chk(self.L.sca_get_mission_gate_state(self.ctx, begin, count, *[_lib.ptr(a, C.c_int32) for a in out]), 'sca_get_mission_gate_state')
+        return tuple(a[:max(count, 0)] for a in out)
+
+    def mission_gate_totals(self):
+        """dict(offered, admitted, blocked_agent, blocked_obstacle, blocked_entry, over_cap, dropped): 64-bit counters since the first
+        gate behind the tables; offered == admitted + blocked_* + over_cap"""
+        t = _lib.MissionGateTotals()
+        self._chk(self.L.sca_get_mission_gate_totals(self.ctx, C.byref(t), C.sizeof(t)), 'sca_get_mission_gate_totals')
+        return {k: int(getattr(t, k)) for k, _ in _lib.MissionGateTotals._fields_ if k != 'reserved'}
 
     # ---- scene checkpoints (sca_save_scenes / sca_load_scenes) ---------------------------------------------------------------
     def scene_checkpoint_bytes(self, scene):

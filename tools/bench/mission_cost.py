@@ -13,6 +13,15 @@ library is loaded beside this build's (--root: the parent's checkout, built).  F
               steps/s, missions/s and whether the three stats are identical.
     collect   sca_get_mission_results with 0 / 64 / all rows holding a new result beside sca_get_finished listing as many rows, N = 4096.
 
+--gate (the admission gate on the device, sca_set_mission_gate; merged into profiles/mission_gate_cost.json):
+    step      as above, and beside it `step_tables`: both builds with idle tables set and no gate -- they enqueue the same kernels
+    tables    becomes `gate`: idle tables in both legs, the gate (margin 0.5) on against off, nobody ending: the five kernels in place of
+              k_mission_advance, four dependent dispatches more
+    lifelong  run_lifelong(spawn_margin=0.5) against run_missions(spawn_margin=0.5) at burst 1 and 64, refusals and waiting beside the rates
+    collect   left out
+    bench     (only when named in --parts, with --root) `bench.py --gpus 1 --steps 200 --warmup 20` as a child process, the parent's checkout and
+              this one alternated twice, in front of everything else: the ms_per_step of each run's JSON line
+
 workloads: respawn_cost.py's (c3_auto: circle N = 4096 ORCA3D SCA_NBR_AUTO; c4: circle N = 100 000 SCA, device tracker, SCA_NBR_KDTREE)"""
 import argparse
 import importlib
@@ -53,6 +62,31 @@ def stepwise_window(leg, args):
     return (time.perf_counter() - t0) * 1e3 / args.window
 
 
+def part_step_tables(here, parent, w, args):
+    """part_step with idle tables set in both builds' contexts and no gate anywhere"""
+    order = [('here', here), ('parent', parent)] if args.here_first else [('parent', parent), ('here', here)]
+    legs = {}
+    for k, pkg in order:
+        leg = make_leg(pkg[0], pkg[1], w)
+        e, ok, fail = idle_tables(importlib.import_module('sca_here._lib'), leg['sc'], leg['n'])
+        leg['sol'].set_missions(1, 1, e, ok, fail)
+        legs[k] = leg
+    for leg in legs.values():
+        step_window(leg, args)
+    ms = {k: [] for k in legs}
+    for _ in range(args.alternations):
+        for k, leg in legs.items():
+            ms[k].append(step_window(leg, args))
+    out = {k: summary(v) for k, v in ms.items()}
+    out['order'] = list(legs)
+    p, h = out['parent'], out['here']
+    out['here_against_parent'] = {'here_median_ms': h['median_ms'], 'parent_median_ms': p['median_ms'], 'difference_ms': round(h['median_ms'] - p['median_ms'], 5),
+                                  'parent_min_ms': p['min_ms'], 'parent_max_ms': p['max_ms'], 'inside_parent_spread': bool(p['min_ms'] <= h['median_ms'] <= p['max_ms'])}
+    for leg in legs.values():
+        leg['sol'].close()
+    return out
+
+
 def part_tables(here, w, args):
     S, scenarios = here[0], here[1]
     _lib = importlib.import_module('sca_here._lib')
@@ -60,6 +94,9 @@ def part_tables(here, w, args):
     legs = {k: make_leg(S, scenarios, w) for k in order}
     e, ok, fail = idle_tables(_lib, legs['on']['sc'], legs['on']['n'])
     legs['on']['sol'].set_missions(1, 1, e, ok, fail)
+    if args.gate:                                                                     # tables in both legs, the gate in one
+        legs['off']['sol'].set_missions(1, 1, e, ok, fail)
+        legs['on']['sol'].set_mission_gate(0.5)
     out = {'order': order}
     for form, window in (('burst', step_window), ('stepwise', stepwise_window)):
         for leg in legs.values():
@@ -74,6 +111,9 @@ def part_tables(here, w, args):
         out[form] = o
     t = legs['on']['sol'].mission_totals()
     out['endings_in_the_on_leg'] = t['arrived'] + t['collided'] + t['timed_out']
+    if args.gate:
+        out['offered_in_the_on_leg'] = legs['on']['sol'].mission_gate_totals()['offered']
+        out['added_dependent_dispatches'] = 4
     for leg in legs.values():
         leg['sol'].close()
     return out
@@ -112,15 +152,29 @@ def part_lifelong(args):
                 new = entry(a.id, list(row['pos']) + list(a.heading_global_frame) if here else list(src.initial_pos), list(src.goal_pos))
                 new.max_run_dist = src.max_run_dist
                 return new
-            stats = LL.run_lifelong(env, next_mission, steps)
+            stats = LL.run_lifelong(env, next_mission, steps, **({'spawn_margin': 0.5} if args.gate else {}))
         else:
-            stats = LL.run_missions(env, T, steps, burst=int(name.rsplit('_', 1)[1]))
+            stats = LL.run_missions(env, T, steps, burst=int(name.rsplit('_', 1)[1]), **({'spawn_margin': 0.5} if args.gate else {}))
         dt = time.perf_counter() - t0
         missions = stats['arrived'] + stats['collided'] + stats['timed_out']
         out[name] = dict(stats, seconds=round(dt, 3), missions=missions, missions_per_s=round(missions / dt, 2), steps_per_s=round(stats['steps'] / dt, 1))
         env.solver.close()
-    keys = ('steps', 'arrived', 'collided', 'timed_out', 'respawned', 'retired', 'agent_steps', 'live_fraction')
+    keys = ('steps', 'arrived', 'collided', 'timed_out', 'respawned', 'retired', 'agent_steps', 'live_fraction') + (('deferred', 'waiting') if args.gate else ())
     out['stats_identical'] = all(out[a][k] == out['run_lifelong'][k] for a in out for k in keys)
+    return out
+
+
+def part_bench(args):
+    """bench.py of both checkouts as child processes, parent / here alternated twice"""
+    import subprocess
+    out = {'order': [], 'parent': [], 'here': [], 'command': 'bench.py --gpus 1 --steps 200 --warmup 20'}
+    for _ in range(2):
+        for name, root in (('parent', os.path.abspath(args.root)), ('here', REPO)):
+            r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '200', '--warmup', '20'], cwd=root, capture_output=True, text=True,
+                               check=True)
+            line = [x for x in r.stdout.splitlines() if x.startswith('{"metric"')][-1]
+            out['order'].append(name)
+            out[name].append(json.loads(line)['ms_per_step'])
     return out
 
 
@@ -170,13 +224,20 @@ def main():
     ap.add_argument('--samples', type=int, default=30)
     ap.add_argument('--here-first', action='store_true', help='step and tables parts: this build\'s (the tables\') context is made and timed first')
     ap.add_argument('--lifelong-steps', type=int, default=20000)
-    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'mission_cost.json'))
+    ap.add_argument('--gate', action='store_true', help='the admission gate on the device: see above; --out defaults to profiles/mission_gate_cost.json')
+    ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(REPO, 'profiles', 'mission_gate_cost.json' if args.gate else 'mission_cost.json')
+    bench = part_bench(args) if 'bench' in args.parts.split(',') and args.root else None      # (in front of everything that opens the GPU here)
     here = load_package(REPO, 'sca_here')
     parent = load_package(args.root, 'sca_parent') if args.root else None
     result = json.load(open(args.out)) if os.path.exists(args.out) else {}
     result.update(host=host(), window_steps=args.window, warm_steps=args.warm, alternations=args.alternations, samples=args.samples)
     parts = args.parts.split(',')
+    if bench:
+        result['bench_py_gpus_1_steps_200_warmup_20_ms_per_step'] = bench
+        print('bench', json.dumps(bench), flush=True)
     suffix = '_here_first' if args.here_first else ''
 
     def save():                                                                       # after every part: a later part that fails loses nothing
@@ -191,16 +252,21 @@ def main():
             entry['step' + suffix] = part_step(here, parent, w, args)
             print(name, 'step', json.dumps(entry['step' + suffix]), flush=True)
             save()
+            if args.gate and parent:
+                entry['step_tables' + suffix] = part_step_tables(here, parent, w, args)
+                print(name, 'step_tables', json.dumps(entry['step_tables' + suffix]), flush=True)
+                save()
         if 'tables' in parts:
-            entry['tables' + suffix] = part_tables(here, w, args)
-            print(name, 'tables', json.dumps(entry['tables' + suffix]), flush=True)
+            key = ('gate' if args.gate else 'tables') + suffix
+            entry[key] = part_tables(here, w, args)
+            print(name, key, json.dumps(entry[key]), flush=True)
             save()
     if 'lifelong' in parts:
-        key = 'lifelong_circle_4096_%d_steps' % args.lifelong_steps
+        key = 'lifelong_circle_4096_%d_steps' % args.lifelong_steps + ('_margin_0.5' if args.gate else '')
         result[key] = part_lifelong(args)
         print(key, json.dumps(result[key]), flush=True)
         save()
-    if 'collect' in parts:
+    if 'collect' in parts and not args.gate:
         result['collect_4096'] = part_collect(here, args)
         print('collect', json.dumps(result['collect_4096']), flush=True)
     save()
