@@ -34,19 +34,37 @@ def build_obstacles():
 
 def lifelong(args, agents, obstacles, pol, dubins):
     """--lifelong STEPS: ping-pong.  An arrived drone flies back to where its mission began; a collided or timed-out one starts its
-    original mission again."""
+    original mission again.  --waypoints K: every leg follows a route of K seeded waypoints (Agent.path), reversed on the way back."""
     from sca_amd.lifelong import run_lifelong
-    env = E.MACAEnv(device_tracker=dubins, clearance=args.clearance)
-    env.set_agents(agents, obstacles=obstacles)
+    K = args.waypoints
+    env = E.MACAEnv(device_tracker=dubins, clearance=args.clearance, path_slots=K)
     first = {a.id: (list(a.initial_pos), list(a.goal_pos)) for a in agents}
+    route = {}                                                     # id -> the K waypoints from its start to its goal, in flying order
+    for i, (start, goal) in first.items():
+        rng = np.random.default_rng(1000 + i)
+        p, g = np.asarray(start[:3], float), np.asarray(goal[:3], float)
+        route[i] = [[float(x) for x in np.round(p + (g - p) * (k + 1) / (K + 1) + rng.normal(0.0, 0.5, 3), 3)] for k in range(K)]
+    out_list = {i: r[::-1] for i, r in route.items()}              # (get_trajectory pops from the end: the first waypoint stands last)
+    back_list = {i: r[:] for i, r in route.items()}
+    if K:
+        for a in agents:
+            a.path = [w[:] for w in out_list[a.id]]
+    env.set_agents(agents, obstacles=obstacles)
 
     def next_mission(agent, row):
+        i = agent.id
         if int(row['flags']) & S.FLAG_COLLISION or not int(row['flags']) & S.FLAG_AT_GOAL:
-            start, goal = first[agent.id]
+            start, goal = first[i]
+            back = False
         else:
             start = list(row['pos']) + list(agent.heading_global_frame)
             goal = list(agent.initial_pos)
-        return E.Agent(start_pos=start, goal_pos=goal, vel=[0.0, 0.0, 0.0], radius=agent.radius, pref_speed=agent.pref_speed, policy=pol, id=agent.id)
+            g, (s0, g0) = np.asarray(goal[:3], float), first[i]
+            back = np.linalg.norm(g - np.asarray(s0[:3], float)) <= np.linalg.norm(g - np.asarray(g0[:3], float))
+        new = E.Agent(start_pos=start, goal_pos=goal, vel=[0.0, 0.0, 0.0], radius=agent.radius, pref_speed=agent.pref_speed, policy=pol, id=i)
+        if K:
+            new.path = [w[:] for w in (back_list if back else out_list)[i]]
+        return new
 
     t0 = time.time()
     if args.device_missions:
@@ -58,7 +76,8 @@ def lifelong(args, agents, obstacles, pol, dubins):
             a = agents[i]
             return E.Agent(start_pos=start, goal_pos=goal, vel=[0.0, 0.0, 0.0], radius=a.radius, pref_speed=a.pref_speed, policy=pol, id=i)
         tables = {i: E.MissionTable([entry(i, goal, start), entry(i, start, goal), entry(i, start, goal)], next_ok=[1, 0, 0], next_fail=[2, 2, 2],
-                                    first_ok=0, first_fail=2, start_here=[True, True, False]) for i, (start, goal) in first.items()}
+                                    first_ok=0, first_fail=2, start_here=[True, True, False], path=[back_list[i], out_list[i], out_list[i]] if K else None)
+                  for i, (start, goal) in first.items()}
         stats = run_missions(env, tables, args.lifelong, burst=args.burst, spawn_margin=args.spawn_margin)
     else:
         stats = run_lifelong(env, next_mission, args.lifelong) if args.spawn_margin is None else \
@@ -97,9 +116,14 @@ def main():
                     help='with --lifelong: the ping-pong rule as a mission table per drone on the device -- a drone that ends takes its next '
                          'mission inside the step, no host call per step (MACAEnv.set_missions)')
     ap.add_argument('--burst', type=int, default=1, metavar='K', help='with --device-missions: K resident steps per library call')
+    ap.add_argument('--waypoints', type=int, default=0, metavar='K',
+                    help='with --lifelong: every leg follows a route of K seeded waypoints, reversed on the way back (with --device-missions '
+                         'the entries bring the routes: MissionTable(path=), sca_set_missions_paths)')
     args = ap.parse_args()
     if args.device_missions and args.lifelong <= 0:
         ap.error('--device-missions goes with --lifelong STEPS')
+    if args.waypoints < 0 or (args.waypoints and args.lifelong <= 0):
+        ap.error('--waypoints K (K >= 0) goes with --lifelong STEPS')
 
     n = args.agents
     if args.scenario == 'circle':

@@ -168,6 +168,11 @@ int sca_set_vpref(sca_ctx *ctx, const double *vpref /*n*3*/, const uint8_t *mode
  * SCA_FORM_WAYPOINTS. */
 int sca_set_paths(sca_ctx *ctx, int n, const int32_t *offsets /*n+1*/, const double *points /*offsets[n]*3*/);
 int sca_get_path_state(sca_ctx *ctx, int32_t *remaining /*n, nullable*/, double *now_goal /*n*3, nullable*/);
+/* Read-only views of what the device holds, behind one synchronisation.  sca_get_path_slot_lists (slot form only, else SCA_ERR_STATE): the
+ * lists' lengths as set and the rows' rooms whole, W points per row -- row a's list is rooms[3 W a .. 3 (W a + len[a])), what stands
+ * behind it is whatever an earlier list left there.  sca_get_vpref_mode: the rows' vpref_mode bytes as the next pass will read them. */
+int sca_get_path_slot_lists(sca_ctx *ctx, int32_t *len /*n, nullable*/, double *rooms /*n*W*3, nullable*/);
+int sca_get_vpref_mode(sca_ctx *ctx, uint8_t *mode /*n*/);
 int sca_set_path_state(sca_ctx *ctx, const int32_t *remaining /*n*/, const double *now_goal /*n*3*/);
 
 /* The same lists in SLOT form (Agent.path, agent.py:44; the rule above is unchanged): every agent row owns room for points_per_agent
@@ -781,8 +786,8 @@ int sca_respawn_agents_gated(sca_ctx *ctx, int count, const int32_t *ids /*count
  *              max_run_dist that is not positive and finite, a zaxis byte above 1 without KEEP_ZAXIS, unknown flag bits; bad
  *              struct_bytes, capacity, range or NULL outputs in the getters.  SCA_ERR_UNSUPPORTED, in either order of the calls:
  *              everything sca_respawn_agents refuses (scenes, a shard with count < n, a communicator, the partition), waypoint lists in
- *              either form (their host mirrors cannot follow a device-side respawn), and sca_step_host while tables are set (the host
- *              owns the state there).
+ *              either form for sca_set_missions itself (tables whose entries bring their own lists: sca_set_missions_paths, below), and
+ *              sca_step_host while tables are set (the host owns the state there).
  * Detect the feature by the symbols (the version number is unchanged). */
 enum sca_mission_flag { SCA_MISSION_START_HERE = 1, SCA_MISSION_KEEP_ZAXIS = 2 };
 typedef struct sca_mission {             /* 128 bytes */
@@ -812,6 +817,40 @@ int sca_set_missions(sca_ctx *ctx, int M, int R, int n, const sca_mission *entri
 int sca_get_mission_results(sca_ctx *ctx, sca_mission_result *out /*capacity*/, int capacity, int *count, int32_t struct_bytes);
 int sca_get_mission_totals(sca_ctx *ctx, sca_mission_totals *out, int32_t struct_bytes);
 int sca_get_mission_state(sca_ctx *ctx, int begin, int count, int32_t *cursor /*count*/, int32_t *ended /*count*/);
+
+/* Mission tables whose entries bring their own waypoint lists: continuous traffic ALONG ROUTES, in bursts, on the device.
+ * sca_set_missions_paths is sca_set_missions plus one packed CSR of lists over the FLAT entry index M a + j: entry j of row a has the list
+ * path_points[3 path_offsets[M a + j] .. 3 path_offsets[M a + j + 1]), in sca_set_paths' list order (pop() takes the last element).  The
+ * lists live on the device as the call brought them, immutable until the tables are replaced.
+ *   precondition  the context's lists are in SLOT form (sca_set_path_slots(W, ...) earlier); the flight in the air keeps its list, its
+ *              cursors and now_goal.  Not in slot form: with path_offsets == NULL the call IS sca_set_missions, with path_offsets it is
+ *              SCA_ERR_STATE; lists in block form: SCA_ERR_UNSUPPORTED.  Slot form with path_offsets == NULL: every entry brings the empty
+ *              list.  sca_set_missions itself keeps refusing a context with lists; sca_set_paths and sca_set_path_slots keep refusing
+ *              while tables stand, sca_step_host too.
+ *   the rule   nothing changes about endings, results, totals, the gate's order or its verdicts.  Where the step TAKES entry j for row a
+ *              -- on the plain path and for the gate's admitted row -- the row becomes word for word what sca_respawn_agents naming it
+ *              with entry j's values AND entry j's list as its path arrays leaves: the list in the row's room, len = rem = its length,
+ *              now_goal None; a straight-line row that had a list (len[a] > 0 in front of the take) gets vpref_mode 0 and the next pass's
+ *              k_waypoint_slots sets it back where the new list is not empty; a tracked row keeps mode 1 and the tracker's v_pref, its
+ *              list advances.  A candidate that waits at the gate keeps every word, list and cursors included; a stop (-1) leaves the
+ *              list as it is.  The next pass pops from the new list: k_waypoint_slots runs on the context's stream at the head of the
+ *              pass, behind the mission kernel, in every step form.
+ *   mirrors    a take moves a row's list length on the device.  While tables with lists stand the host entry points that read the
+ *              lengths (sca_set_vpref's mode-1 refusal, sca_set_path_state's bound, sca_respawn_agents' mode bit, clearing the lists)
+ *              first read them back: one copy of n words behind a synchronisation, never inside a step.
+ *   dropping   sca_set_missions_paths(M = 0, entries = NULL), sca_set_missions(M = 0) and sca_set_agents drop tables and their lists; the
+ *              slot form and the rows' current lists stay.  While tables WITH lists stand sca_set_paths(0 / NULL) is SCA_ERR_UNSUPPORTED:
+ *              it would take the rooms away under the step.
+ *   refusals   decided on the host before any device work, a refused call changes nothing: everything sca_set_missions refuses, with
+ *              its codes, and SCA_ERR_ARG for path_offsets[0] != 0, offsets that decrease, path_points == NULL with points to read,
+ *              more than 2^31 / 3 points, a REACHABLE entry whose list is longer than W or holds a point that is not finite (an entry
+ *              nobody reaches is not inspected beyond its offsets).
+ * sca_get_mission_paths: W and the points the tables' lists hold; 0 / 0 for tables without lists.  sca_mission stays 128 bytes and the
+ * version number is unchanged: detect the feature by the symbol. */
+int sca_set_missions_paths(sca_ctx *ctx, int M, int R, int n, const sca_mission *entries /*M*n*/, const int32_t *first_ok /*n*/,
+                           const int32_t *first_fail /*n*/, const int32_t *path_offsets /*M*n+1, nullable*/,
+                           const double *path_points /*path_offsets[M*n]*3*/);
+int sca_get_mission_paths(sca_ctx *ctx, int *points_per_agent, int64_t *total_points);
 
 /* The admission gate on the device: a row takes its next mission only where its start is free.  sca_set_missions puts a row wherever its
  * table says, also inside another drone; sca_respawn_agents_gated refuses such a start, but as a host call between two steps.  With a gate

@@ -138,6 +138,8 @@ SIGNATURES = {
     'sca_set_vpref': (C.c_int, [C.c_void_p, dp, bp]),
     'sca_set_paths': (C.c_int, [C.c_void_p, C.c_int, ip, dp]),
     'sca_get_path_state': (C.c_int, [C.c_void_p, ip, dp]),
+    'sca_get_path_slot_lists': (C.c_int, [C.c_void_p, ip, dp]),
+    'sca_get_vpref_mode': (C.c_int, [C.c_void_p, bp]),
     'sca_set_scenes': (C.c_int, [C.c_void_p, C.c_int, ip]),
     'sca_get_scene_state': (C.c_int, [C.c_void_p, ip, ip]),
     'sca_set_scene_obstacles': (C.c_int, [C.c_void_p, C.c_int, ip, dp, dp]),
@@ -172,6 +174,8 @@ SIGNATURES = {
     'sca_probe_clearance': (C.c_int, [C.c_void_p, C.c_int, dp, dp, ip, C.POINTER(SceneClearance), C.c_int32]),
     'sca_respawn_agents_gated': (C.c_int, [C.c_void_p, C.c_int, ip, dp, fp, dp, dp, dp, dp, bp, dp, dp, ip, dp, C.c_double, ip, C.POINTER(SceneClearance), ip]),
     'sca_set_missions': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Mission), ip, ip]),
+    'sca_set_missions_paths': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Mission), ip, ip, ip, dp]),
+    'sca_get_mission_paths': (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     'sca_get_mission_results': (C.c_int, [C.c_void_p, C.POINTER(MissionResult), C.c_int, C.POINTER(C.c_int), C.c_int32]),
     'sca_get_mission_totals': (C.c_int, [C.c_void_p, C.POINTER(MissionTotals), C.c_int32]),
     'sca_get_mission_state': (C.c_int, [C.c_void_p, C.c_int, C.c_int, ip, ip]),

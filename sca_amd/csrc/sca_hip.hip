@@ -382,6 +382,12 @@ struct sca_ctx {
         uint8_t *host = nullptr;            // the collect's page-locked block: the count's head, host_cap results behind it
         int64_t host_cap = 0;
         long long updates = 0;              // env updates enqueued since sca_set_missions
+        // tables with lists (sca_set_missions_paths on a context in slot form): a take brings the entry's list into the row's room.  Nothing
+        // of it exists for tables without lists
+        bool lists = false;
+        int32_t *path_store = nullptr;      // device, one allocation: the offsets [M n + 1] (padded to 8 bytes), the points behind them; null: every entry brings the empty list
+        double *path_pts = nullptr;         // ... the points inside it
+        int64_t path_total = 0;             // points the lists hold
         // the admission gate (sca_set_mission_gate): nothing of it exists until a gate is set; freed with the tables
         struct Gate {
             bool on = false;
@@ -462,10 +468,12 @@ static int auto_join(sca_ctx *c);
 static int clearance_drop(sca_ctx *c);
 static int missions_drop(sca_ctx *c);
 static int missions_standing(sca_ctx *c, const char *who, MissionFault f);
+static int mission_refuse(sca_ctx *c, const char *who, MissionFault f, int64_t entry);
 static int missions_refresh_live(sca_ctx *c);
 static int missions_host_flight(sca_ctx *c, const int32_t *ids, const int32_t *verdict, int count);
 static int missions_gate_new_state(sca_ctx *c);
 static int missions_gate_partials(sca_ctx *c, int m);
+static int missions_path_mirrors(sca_ctx *c);
 static ClearanceState clearance_state(const sca_ctx *c);
 static int clearance_refuse(sca_ctx *c, const char *who, ClearanceFault f);
 static int api_enter(sca_ctx *c);
@@ -1027,6 +1035,7 @@ void sca_destroy(sca_ctx *c) {
     if (c->comm) { (void)hipStreamSynchronize(c->stream); (void)g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
     (void)tracker_free(c);
     (void)part_free(c);
+    (void)missions_drop(c);                                            // (in front of the lists: tables with lists read the rows' lengths back once more)
     for (void *p : {(void *)c->path.off, (void *)c->path.pts, (void *)c->path.rem, (void *)c->path.now_goal, (void *)c->pslot_pts, (void *)c->pslot_len}) if (p) (void)hipFree(p);
     c->scenes.release();
     if (c->clear) { (void)hipFree(c->clear); c->clear = nullptr; }
@@ -1036,7 +1045,6 @@ void sca_destroy(sca_ctx *c) {
     if (c->rsp_host) { (void)hipHostFree(c->rsp_host); c->rsp_host = nullptr; }
     if (c->fin_host) { (void)hipHostFree(c->fin_host); c->fin_host = nullptr; }
     if (c->fin_counts) { (void)hipFree(c->fin_counts); c->fin_counts = nullptr; }
-    (void)missions_drop(c);
     if (c->spn_host) { (void)hipHostFree(c->spn_host); c->spn_host = nullptr; }
     if (c->spn_dev) { (void)hipFree(c->spn_dev); c->spn_dev = nullptr; }
     if (c->spn_partials) { (void)hipFree(c->spn_partials); c->spn_partials = nullptr; }
@@ -1360,6 +1368,7 @@ int sca_get_kd_tree(sca_ctx *c, double *tree_out) {
 int sca_set_vpref(sca_ctx *c, const double *vpref, const uint8_t *mode) {
     API_ENTER(c);
     ARG(c, vpref && mode && c->agents_set);
+    if (int r = missions_path_mirrors(c)) return r;                    // (tables with lists: which rows follow a list now is the device's to say)
     if (c->paths_on)
         for (int i = 0; i < c->n; i++)
             if (mode[i] && c->h_path_vpref[i]) {
@@ -1376,6 +1385,7 @@ int sca_set_vpref(sca_ctx *c, const double *vpref, const uint8_t *mode) {
 // reset_mode: the straight-line agents that had a path take v_pref from their policy's own rule again (k_waypoint set vpref_mode = 1 for them)
 static int paths_clear(sca_ctx *c, bool reset_mode) {
     if (!c->paths_on) return 0;
+    if (int r = missions_path_mirrors(c)) return r;                    // (tables with lists: the rows that had a list are the device's to say)
     CHK(c, hipStreamSynchronize(c->stream));
     if (reset_mode && c->n > 0) {
         std::vector<uint8_t> mode((size_t)c->n);
@@ -1400,6 +1410,7 @@ static int paths_alloc_cursors(sca_ctx *c) {
 int sca_set_paths(sca_ctx *c, int n, const int32_t *offsets, const double *points) {
     API_ENTER(c);
     if (!c->agents_set) { c->err = "sca_set_agents first"; return SCA_ERR_STATE; }
+    if ((n == 0 || !offsets) && c->ms.on && c->ms.lists) return mission_refuse(c, "sca_set_paths", MSF_PATH_CLEAR, -1);
     if (n == 0 || !offsets) return paths_clear(c, true);
     if (int r = missions_standing(c, "sca_set_paths", MSF_PATHS)) return r;
     if (c->part_on) { c->err = "sca_set_paths under the cell-owner partition: path state does not migrate with the agents"; return SCA_ERR_UNSUPPORTED; }
@@ -1512,10 +1523,33 @@ int sca_get_path_state(sca_ctx *c, int32_t *remaining, double *now_goal) {
     CHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
+// read-only: the lists as the rows hold them in slot form -- the lengths as set (by sca_set_path_slots, a respawn, a restart or a take) and
+// the rooms whole, W points per row (what stands behind a list's length is whatever an earlier list left there)
+int sca_get_path_slot_lists(sca_ctx *c, int32_t *len, double *rooms) {
+    API_ENTER(c);
+    if (!c->paths_on || c->path_W <= 0) { c->err = "sca_get_path_slot_lists: the lists are not in slot form (sca_set_path_slots)"; return SCA_ERR_STATE; }
+    ARG(c, len || rooms);
+    CHK(c, hipStreamSynchronize(c->stream));
+    if (len) CHK(c, hipMemcpyAsync(len, c->pslot_len, sizeof(int32_t) * (size_t)c->n, hipMemcpyDeviceToHost, c->stream));
+    if (rooms) CHK(c, hipMemcpyAsync(rooms, c->pslot_pts, sizeof(double) * 3 * (size_t)c->path_W * (size_t)c->n, hipMemcpyDeviceToHost, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+// read-only: the rows' vpref_mode bytes as the next pass will read them (fed by sca_set_vpref, 1 where a pass aimed a straight-line row at
+// its waypoint or the device tracker tracks the row, 0 behind a respawn or a take that reset it)
+int sca_get_vpref_mode(sca_ctx *c, uint8_t *mode) {
+    API_ENTER(c);
+    ARG(c, mode && c->agents_set);
+    CHK(c, hipStreamSynchronize(c->stream));
+    CHK(c, hipMemcpyAsync(mode, c->d.vpref_mode, (size_t)c->n, hipMemcpyDeviceToHost, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
 int sca_set_path_state(sca_ctx *c, const int32_t *remaining, const double *now_goal) {
     API_ENTER(c);
     if (!c->paths_on) { c->err = "no waypoint lists (sca_set_paths)"; return SCA_ERR_STATE; }
     ARG(c, remaining && now_goal);
+    if (int r = missions_path_mirrors(c)) return r;                    // (tables with lists: the bound is the device's lengths)
     const int n = c->n;
     for (int i = 0; i < n; i++) {
         if (remaining[i] < 0 || remaining[i] > (c->path_W ? c->h_path_len[i] : c->h_path_off[i + 1] - c->h_path_off[i])) {
@@ -4078,6 +4112,7 @@ static int respawn_run(sca_ctx *c, const RespawnCtx &X, const RespawnArgs &A, co
     }
     const RespawnLayout L = respawn_layout(c->rsp_cap, c->rsp_W);
     const bool slots = X.path_W > 0;
+    if (int r = missions_path_mirrors(c)) return r;                    // (tables with lists: the named rows' mode bit follows the lists they hold NOW)
     const uint32_t has = respawn_pack(c->rsp_host, L, X, A, slots ? c->h_path_vpref.data() : nullptr);
     RespawnDev d{};
     d.rec = c->d.rec; d.heading = c->d.heading; d.goal = c->d.goal; d.pref_speed = c->d.pref_speed; d.max_run_dist = c->d.max_run_dist;
@@ -4191,7 +4226,15 @@ static int mission_refuse(sca_ctx *c, const char *who, MissionFault f, int64_t e
     case MSF_SHARD: c->err = w + ": mission tables and a shard with count < n (sca_set_shard) exclude each other: the tables name rows of the whole swarm on one rank"; break;
     case MSF_COMM: c->err = w + ": mission tables and a communicator exclude each other (sca_comm_destroy first)"; break;
     case MSF_PARTITION: c->err = w + ": mission tables and the cell-owner partition exclude each other: the rows' state does not follow the owners"; break;
-    case MSF_PATHS: c->err = w + ": mission tables and waypoint lists exclude each other: the lists' host mirrors cannot follow a device-side respawn"; break;
+    case MSF_PATHS: c->err = w + ": these mission tables and waypoint lists exclude each other: tables whose entries bring their own lists come through sca_set_missions_paths, on a context whose lists are in slot form (sca_set_path_slots) before the tables arrive"; break;
+    case MSF_PATH_NO_SLOTS: c->err = w + ": path_offsets, but the context's lists are not in slot form -- sca_set_path_slots first"; break;
+    case MSF_PATH_START: c->err = w + ": path_offsets[0] must be 0"; break;
+    case MSF_PATH_DECREASING: c->err = w + ": path_offsets decrease at the flat entry index " + at; break;
+    case MSF_PATH_NO_POINTS: c->err = w + ": path_points is NULL"; break;
+    case MSF_PATH_TOTAL: c->err = w + ": the lists hold more than " + std::to_string(MISSION_PATH_MAX_POINTS) + " points"; break;
+    case MSF_PATH_TOO_LONG: c->err = w + ": reachable entry " + at + " brings a list longer than the room per row, " + std::to_string(c->path_W) + " (sca_set_path_slots)"; break;
+    case MSF_PATH_NOT_FINITE: c->err = w + ": reachable entry " + at + " brings a waypoint that is not finite"; break;
+    case MSF_PATH_CLEAR: c->err = w + ": clearing the waypoint lists while mission tables with lists stand would take the rows' rooms away under the step (drop the tables first: sca_set_missions with M = 0)"; break;
     default: c->err = w + " while mission tables are set: the host owns the state there (drop the tables: sca_set_missions with M = 0)";
     }
     return mission_error_code(f);
@@ -4206,8 +4249,10 @@ static void missions_gate_free_scratch(sca_ctx::Missions::Gate &g) {
 }
 static int missions_drop(sca_ctx *c) {
     sca_ctx::Missions &m = c->ms;
-    if (!m.entries && !m.host) { m = sca_ctx::Missions{}; return 0; }
+    if (!m.entries && !m.host && !m.path_store) { m = sca_ctx::Missions{}; return 0; }
     (void)hipStreamSynchronize(c->stream);                             // (no launch still uses them)
+    (void)missions_path_mirrors(c);                                    // (tables with lists: the rows' current lists stay, and from here on the host follows them again)
+    if (m.path_store) (void)hipFree(m.path_store);
     if (m.entries) (void)hipFree(m.entries);
     if (m.words) (void)hipFree(m.words);
     if (m.results) (void)hipFree(m.results);
@@ -4275,6 +4320,10 @@ static int missions_advance(sca_ctx *c) {
         d.trk_nbr0 = c->trk.nbr0; d.trk_goal_heading = c->trk_goal_heading;
         d.trk_st = (restart_u32 *)c->trk.st; d.trk_init = (const restart_u32 *)c->trk_init; d.trk_words = (int)(sizeof(sca_dubins::AgentTrack) / 4);
     }
+    if (s.lists) {                        // tables with lists: the rows' rooms, lengths and cursors, as respawn_run hands them to k_respawn
+        d.path_pts = c->pslot_pts; d.now_goal = c->path.now_goal; d.path_len = c->pslot_len; d.path_rem = c->path.rem; d.W = c->path_W;
+        m.path_off = s.path_store; m.path_pts = s.path_pts;
+    }
     d.clear = c->clear;
     d.n = n;
     m.live = s.words + (size_t)MSW_LIVE * n; m.policy = c->d.policy; m.entries = s.entries;
@@ -4303,6 +4352,10 @@ static int missions_advance(sca_ctx *c) {
     positions_replaced(c);                // a taken row may stand anywhere now and the host does not learn of it: no sizing hint from older trees (no value)
     return 0;
 }
+// The tables' arrival, behind the check of the entry point that brings them (`who`).  lists: the context is in slot form and the call is
+// sca_set_missions_paths -- path_offsets (nullable: every entry brings the empty list) / path_points are its packed CSR of `total` points.
+static int missions_set(sca_ctx *c, const char *who, int M, int R, int n, const sca_mission *entries, const int32_t *first_ok, const int32_t *first_fail,
+                        double max_pref_speed, bool lists, const int32_t *path_offsets, const double *path_points, int64_t total);
 int sca_set_missions(sca_ctx *c, int M, int R, int n, const sca_mission *entries, const int32_t *first_ok, const int32_t *first_fail) {
     API_ENTER(c);
     if (!entries && M == 0) return missions_drop(c);
@@ -4311,6 +4364,40 @@ int sca_set_missions(sca_ctx *c, int M, int R, int n, const sca_mission *entries
     X.paths = c->paths_on; X.n = c->n; X.shard_count = c->d.shard_count;
     const MissionCheck k = mission_check(X, MissionArgs{M, R, n, entries, first_ok, first_fail});
     if (int r = mission_refuse(c, "sca_set_missions", k.fault, k.entry)) return r;
+    return missions_set(c, "sca_set_missions", M, R, n, entries, first_ok, first_fail, k.max_pref_speed, false, nullptr, nullptr, 0);
+}
+int sca_set_missions_paths(sca_ctx *c, int M, int R, int n, const sca_mission *entries, const int32_t *first_ok, const int32_t *first_fail,
+                           const int32_t *path_offsets, const double *path_points) {
+    API_ENTER(c);
+    if (!entries && M == 0) return missions_drop(c);
+    MissionCtx X;
+    X.agents = c->agents_set; X.mid_step = c->near_valid; X.scenes = c->scenes.on; X.comm = c->comm != nullptr; X.partition = c->part_on;
+    X.paths = c->paths_on; X.n = c->n; X.shard_count = c->d.shard_count; X.path_W = c->paths_on ? c->path_W : 0;
+    const MissionPathsCheck k = mission_paths_check(X, MissionArgs{M, R, n, entries, first_ok, first_fail}, MissionPathArgs{path_offsets, path_points});
+    if (int r = mission_refuse(c, "sca_set_missions_paths", k.fault, k.entry)) return r;
+    return missions_set(c, "sca_set_missions_paths", M, R, n, entries, first_ok, first_fail, k.max_pref_speed, X.path_W > 0, path_offsets, path_points, k.total);
+}
+int sca_get_mission_paths(sca_ctx *c, int *points_per_agent, int64_t *total_points) {
+    API_ENTER(c);
+    if (int r = mission_refuse(c, "sca_get_mission_paths", mission_paths_get_check(c->agents_set, c->ms.on, points_per_agent && total_points), -1)) return r;
+    *points_per_agent = c->ms.lists ? c->path_W : 0;
+    *total_points = c->ms.lists ? c->ms.path_total : 0;
+    return 0;
+}
+// While tables with lists stand a take moves len[a] on the device without the host knowing: the two host mirrors of the lists (h_path_len,
+// sca_set_path_state's bound; h_path_vpref, "a straight-line agent with a list at the moment") are read back from the device's lengths at
+// the head of every host entry point that reads them -- one copy of n words behind a synchronisation, never inside a step.
+static int missions_path_mirrors(sca_ctx *c) {
+    if (!c->ms.on || !c->ms.lists || !c->paths_on || c->path_W <= 0 || c->n <= 0) return 0;
+    c->h_path_len.resize((size_t)c->n); c->h_path_vpref.resize((size_t)c->n);
+    CHK(c, hipStreamSynchronize(c->stream));
+    CHK(c, hipMemcpyAsync(c->h_path_len.data(), c->pslot_len, sizeof(int32_t) * (size_t)c->n, hipMemcpyDeviceToHost, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < c->n; i++) c->h_path_vpref[i] = c->h_path_len[i] > 0 && !restart_policy_tracked(c->h_policy[i]);
+    return 0;
+}
+static int missions_set(sca_ctx *c, const char *who, int M, int R, int n, const sca_mission *entries, const int32_t *first_ok, const int32_t *first_fail,
+                        double max_pref_speed, bool lists, const int32_t *path_offsets, const double *path_points, int64_t total) {
     if (int r = missions_drop(c)) return r;
     sca_ctx::Missions &m = c->ms;
     const int tiles = finished_tiles(n);
@@ -4319,8 +4406,17 @@ int sca_set_missions(sca_ctx *c, int M, int R, int n, const sca_mission *entries
         words[(size_t)MSW_FIRST_OK * n + a] = first_ok[a]; words[(size_t)MSW_FIRST_FAIL * n + a] = first_fail[a];
         words[(size_t)MSW_CURSOR * n + a] = -1; words[(size_t)MSW_FLYING * n + a] = -1;
     }
-    const auto fail = [&](hipError_t e, const char *what) { c->err = std::string("sca_set_missions: ") + what + ": " + hipGetErrorString(e); (void)missions_drop(c); return SCA_ERR_HIP; };
+    const auto fail = [&](hipError_t e, const char *what) { c->err = std::string(who) + ": " + what + ": " + hipGetErrorString(e); (void)missions_drop(c); return SCA_ERR_HIP; };
     hipError_t e;
+    if (lists && path_offsets) {          // the packed lists: the offsets, padded to 8 bytes, and the points behind them in one allocation
+        const size_t off_bytes = (sizeof(int32_t) * ((size_t)M * n + 1) + 7) / 8 * 8;
+        if ((e = hipMalloc((void **)&m.path_store, off_bytes + sizeof(double) * 3 * (size_t)std::max<int64_t>(total, 1))) != hipSuccess) return fail(e, "no device memory for the lists");
+        m.path_pts = (double *)((uint8_t *)m.path_store + off_bytes);
+        if ((e = hipMemcpyAsync(m.path_store, path_offsets, sizeof(int32_t) * ((size_t)M * n + 1), hipMemcpyHostToDevice, c->stream)) != hipSuccess) return fail(e, "the upload of the lists' offsets");
+        if (total > 0 && (e = hipMemcpyAsync(m.path_pts, path_points, sizeof(double) * 3 * (size_t)total, hipMemcpyHostToDevice, c->stream)) != hipSuccess) return fail(e, "the upload of the lists");
+        m.path_total = total;
+    }
+    m.lists = lists;
     if ((e = hipMalloc((void **)&m.entries, sizeof(sca_mission) * (size_t)M * n)) != hipSuccess) return fail(e, "no device memory for the tables");
     if ((e = hipMalloc((void **)&m.words, sizeof(int32_t) * words.size())) != hipSuccess) return fail(e, "no device memory for the cursors");
     if ((e = hipMalloc((void **)&m.results, sizeof(sca_mission_result) * (size_t)R * n)) != hipSuccess) return fail(e, "no device memory for the results");
@@ -4333,7 +4429,7 @@ int sca_set_missions(sca_ctx *c, int M, int R, int n, const sca_mission *entries
     m.M = M; m.R = R; m.updates = 0; m.on = true;
     if (missions_refresh_live(c)) { (void)missions_drop(c); return SCA_ERR_HIP; }
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return fail(e, "the upload");
-    c->max_pref_speed = std::max(c->max_pref_speed, k.max_pref_speed);   // the envelope only grows, as under respawns
+    c->max_pref_speed = std::max(c->max_pref_speed, max_pref_speed);     // the envelope only grows, as under respawns
     return 0;
 }
 int sca_get_mission_results(sca_ctx *c, sca_mission_result *out, int capacity, int *count, int32_t struct_bytes) {

@@ -231,10 +231,7 @@ __global__ __launch_bounds__(MISSION_GATE_WAVES * 64) void k_mission_gate_take(M
     const MissionGateSettle s = mission_gate_settle(v, j, g.refusals[a]);
     if (s.take) {
         const uint32_t flags = m.row.rec[a].flags;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");            // (the row's loads stay in front of its stores: k_mission_advance's note)
-        const sca_mission *e = m.entries + ((int64_t)m.M * a + j);
-        const RespawnRow w = respawn_row(mission_bits(m.policy[a], m.row.trk_st != nullptr), flags, mission_has(*e), 0);
-        respawn_write_row(m.row, a, lane, w, MissionSrc{e});
+        const RespawnRow w = mission_take_row(m, a, j, flags, lane);      // (the row's loads stay in front of its stores: mission_take_row's note)
         if (lane == 0) {
             m.cursor[a] = j; m.flying[a] = j; m.live[a] = 1;
             if (w.done_delta) atomicAdd(&m.row.done_count[(a & 255) * 32], w.done_delta);

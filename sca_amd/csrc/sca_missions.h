@@ -8,9 +8,11 @@
 //
 // Everything here is pure and compiles for the host (tests/missions_harness.cpp):
 //   mission_check       every refusal of sca_set_missions and of the getters, with its code; which entries are reachable
+//   mission_paths_check every refusal of sca_set_missions_paths: mission_check's, then the lists' (one packed CSR over the flat entry index)
 //   mission_ended       did a row end in this step (the flag words in front of and behind K4)
 //   mission_take        the outcome of an ended row and the successor it names
 //   MissionSrc          an entry as the source of respawn_write_row's values
+//   mission_take_bits   the bits byte and the `has` word respawn_row reads for a taken row, with and without lists (mission_take_has)
 //   mission_new         how many results of a row's ring have not been collected (the collect's count per row)
 // and the admission gate in front of the take (sca_set_mission_gate; the kernels: sca_mission_gate.hip.h):
 //   mission_gate_check  every refusal of sca_set_mission_gate and of the gate's getters, the cap and the scratch a gate needs
@@ -61,15 +63,27 @@ enum MissionFault {
     MSF_COMM,               // a communicator                                                                 }
     MSF_PARTITION,          // the cell-owner partition                                                       }
     MSF_PATHS,              // waypoint lists in either form                                                  }
-    MSF_STEP_HOST           // sca_step_host while tables are set                                             }
+    MSF_STEP_HOST,          // sca_step_host while tables are set                                             }
+    // sca_set_missions_paths' own (behind the older values, which keep their numbers)
+    MSF_PATH_NO_SLOTS,      // path_offsets while the context's lists are not in slot form                    } SCA_ERR_STATE
+    MSF_PATH_START,         // path_offsets[0] != 0                                                           } SCA_ERR_ARG
+    MSF_PATH_DECREASING,    // offsets that decrease (entry: the flat entry index)                            }
+    MSF_PATH_NO_POINTS,     // path_points == NULL with points to read                                        }
+    MSF_PATH_TOTAL,         // more than MISSION_PATH_MAX_POINTS points                                       }
+    MSF_PATH_TOO_LONG,      // a reachable entry whose list is longer than the room per row                   }
+    MSF_PATH_NOT_FINITE,    // a reachable entry whose list holds a point that is not finite                  }
+    MSF_PATH_CLEAR          // sca_set_paths(0 / NULL) while tables with lists stand                          } SCA_ERR_UNSUPPORTED
 };
 inline int mission_error_code(MissionFault f) {
+    if (f > MSF_STEP_HOST) return f == MSF_PATH_NO_SLOTS ? SCA_ERR_STATE : f <= MSF_PATH_NOT_FINITE ? SCA_ERR_ARG : SCA_ERR_UNSUPPORTED;
     return f == MSF_OK ? SCA_OK : f <= MSF_OFF ? SCA_ERR_STATE : f <= MSF_GET_ARGS ? SCA_ERR_ARG : SCA_ERR_UNSUPPORTED;
 }
-// what the rules read of the context
+// what the rules read of the context (path_W: read by mission_paths_check alone -- the room per row while the lists are in slot form, 0:
+// no slot form; `paths` stays "lists in either form")
 struct MissionCtx {
     bool agents, mid_step, scenes, comm, partition, paths;
     int n, shard_count;
+    int path_W = 0;
 };
 struct MissionArgs { int M, R, n; const sca_mission *entries; const int32_t *first_ok, *first_fail; };
 // fault: which rule failed; entry: where (a row for first_ok / first_fail, else the flat entry index M a + j; -1: nowhere in particular);
@@ -136,6 +150,46 @@ inline MissionCheck mission_check(const MissionCtx &C, const MissionArgs &A, uin
     }
     return {MSF_OK, -1, top};
 }
+// sca_set_missions_paths(M, R, n, entries, first_ok, first_fail, path_offsets, path_points): one packed CSR of lists over the flat entry
+// index M a + j.  Decided in this order: mission_check's context faults (lists in SLOT form are no fault here, lists in block form are
+// MSF_PATHS), offsets without a slot form, mission_check's argument faults, then the lists' own -- the offsets of every entry, the lengths
+// and the points of the REACHABLE entries only, lowest flat index first (an entry nobody reaches is not inspected beyond its offsets, as
+// its values are not).  path_offsets == NULL: every entry brings the empty list.
+constexpr int64_t MISSION_PATH_MAX_POINTS = ((int64_t)1 << 31) / 3;    // every coordinate index 3 k + 2 stays below 2^31
+struct MissionPathArgs { const int32_t *path_offsets; const double *path_points; };
+// total: the points the call brings; the rest as MissionCheck
+struct MissionPathsCheck { MissionFault fault; int64_t entry; double max_pref_speed; int64_t total; };
+inline MissionPathsCheck mission_paths_check(const MissionCtx &C, const MissionArgs &A, const MissionPathArgs &P, uint8_t *reached = nullptr) {
+    MissionCtx B = C;
+    if (C.path_W > 0) B.paths = false;
+    std::vector<uint8_t> own;
+    if (!reached && A.M >= 1 && A.M <= MISSION_MAX_M && A.n == C.n && A.n > 0 && (int64_t)A.M * A.n <= MISSION_MAX_SLOTS) { own.assign((std::size_t)A.M * (std::size_t)A.n, 0); reached = own.data(); }
+    const MissionCheck k = mission_check(B, A, reached);
+    if (k.fault != MSF_OK && mission_error_code(k.fault) != SCA_ERR_ARG) return {k.fault, k.entry, 0.0, 0};
+    if (P.path_offsets && C.path_W <= 0) return {MSF_PATH_NO_SLOTS, -1, 0.0, 0};
+    if (k.fault != MSF_OK) return {k.fault, k.entry, 0.0, 0};
+    if (!P.path_offsets) return {MSF_OK, -1, k.max_pref_speed, 0};
+    const int64_t E = (int64_t)A.M * A.n;
+    if (P.path_offsets[0] != 0) return {MSF_PATH_START, -1, 0.0, 0};
+    for (int64_t e = 0; e < E; e++) if (P.path_offsets[e + 1] < P.path_offsets[e]) return {MSF_PATH_DECREASING, e, 0.0, 0};
+    const int64_t total = P.path_offsets[E];
+    if (total > 0 && !P.path_points) return {MSF_PATH_NO_POINTS, -1, 0.0, total};
+    if (total > MISSION_PATH_MAX_POINTS) return {MSF_PATH_TOTAL, -1, 0.0, total};
+    for (int64_t e = 0; e < E; e++) {
+        if (!reached[e]) continue;
+        const int64_t lo = P.path_offsets[e], hi = P.path_offsets[e + 1];
+        if (hi - lo > C.path_W) return {MSF_PATH_TOO_LONG, e, 0.0, total};
+        for (int64_t q = 3 * lo; q < 3 * hi; q++) if (!restart_finite(P.path_points[q])) return {MSF_PATH_NOT_FINITE, e, 0.0, total};
+    }
+    return {MSF_OK, -1, k.max_pref_speed, total};
+}
+// sca_get_mission_paths(points_per_agent, total_points)
+inline MissionFault mission_paths_get_check(bool agents, bool on, bool have_outputs) {
+    if (!agents) return MSF_NO_AGENTS;
+    if (!on) return MSF_OFF;
+    if (!have_outputs) return MSF_GET_ARGS;
+    return MSF_OK;
+}
 // the getters
 inline MissionFault mission_results_check(bool agents, bool on, bool have_out, int capacity, bool have_count, int struct_bytes) {
     if (!agents) return MSF_NO_AGENTS;
@@ -195,10 +249,41 @@ struct MissionSrc {
     SCA_HD double max_run_dist() const { return e->max_run_dist; }
     SCA_HD uint8_t zaxis() const { return e->zaxis; }
 };
-// the `has` word and the bits byte respawn_row reads for a row taken from entry e (lists are refused with tables: no RSP_BIT_MODE_RESET)
+// the `has` word and the bits byte respawn_row reads for a row taken from entry e of tables WITHOUT lists (no path word is touched)
 SCA_HD uint32_t mission_has(const sca_mission &e) { return (e.flags & SCA_MISSION_KEEP_ZAXIS) ? 0u : RESPAWN_HAS_ZAXIS; }
 SCA_HD uint8_t mission_bits(uint8_t policy, bool tracker_on) {      // (restart_policy_tracked's rule, for the device too)
     return tracker_on && (policy == SCA_POLICY_SCA || policy == SCA_POLICY_RVO3D_DUBINS) ? RSP_BIT_TRACKED : 0;
+}
+// ... and of tables WITH lists (sca_set_missions_paths in slot form): the entry brings its list as a respawn's path arrays do, and a
+// straight-line row that HAD a list (old_len: len[a] in front of the take -- what the host's "straight-line agent with a list" byte mirrors,
+// respawn_pack) goes back to its policy's own v_pref rule until k_waypoint_slots finds the new list not empty
+SCA_HD uint32_t mission_take_has(const sca_mission &e, bool lists) { return mission_has(e) | (lists ? RESPAWN_HAS_PATH_SLOTS | RESPAWN_HAS_PATHS : 0u); }
+SCA_HD uint8_t mission_take_bits(uint8_t policy, bool tracker_on, int32_t old_len) {
+    const bool straight = !(policy == SCA_POLICY_SCA || policy == SCA_POLICY_RVO3D_DUBINS);
+    return (uint8_t)(mission_bits(policy, tracker_on) | (straight && old_len > 0 ? RSP_BIT_MODE_RESET : 0));
+}
+// entry fe's list in the tables' packed CSR (off null: every entry brings the empty list)
+struct MissionList { int32_t first, len; };
+SCA_HD MissionList mission_list(const int32_t *off, int64_t fe) {
+    MissionList l;
+    l.first = off ? off[fe] : 0;
+    l.len = off ? off[fe + 1] - l.first : 0;
+    return l;
+}
+// What one lane of the wavefront that serves row `a` stores where the step takes entry e (flat index fe) for it: the shared row write with
+// the entry as its source, then -- tables with lists -- the entry's list into the row's room.  old_len: len[a], loaded in front of every
+// store of the row.  Dev: RespawnDev (the kernels) or plain host arrays with the same members (tests/mission_paths_harness.cpp).
+template <class Dev>
+SCA_HD RespawnRow mission_take_write(const Dev &d, int a, int lane, uint8_t policy, uint32_t flags, const sca_mission *e, bool lists, int32_t old_len,
+                                     const int32_t *path_off, const double *path_pts, int64_t fe) {
+    MissionList l = mission_list(lists ? path_off : nullptr, fe);
+    if (lists && l.len > d.W) l.len = d.W;                                 // (never taken: mission_paths_check holds every reachable list against the room)
+    const bool tracker_on = d.trk_st != nullptr;
+    const uint8_t bits = lists ? mission_take_bits(policy, tracker_on, old_len) : mission_bits(policy, tracker_on);
+    const RespawnRow w = respawn_row(bits, flags, mission_take_has(*e, lists), l.len);
+    respawn_write_row(d, a, lane, w, MissionSrc{e});
+    if (w.path_len > 0) respawn_write_list(d.path_pts, d.W, a, lane, path_pts + 3 * (int64_t)l.first, w.path_len);
+    return w;
 }
 
 // ---- the results ---------------------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 // sca_missions.hip.h -- the kernels behind the mission tables (the rules: sca_missions.h).  k_mission_advance is enqueued by
 // launch_collide_finish behind K4 and in front of the buffer swap, only while tables are set; k_mission_count / k_mission_write only by
 // sca_get_mission_results, k_mission_live / k_mission_host_flight by the host calls that change flags between two steps: a context without tables enqueues exactly what it did.
+// Tables whose entries bring their own waypoint lists (sca_set_missions_paths) add no kernel: the take (mission_take_row, shared with
+// k_mission_gate_take) also copies the entry's list into the row's room, through the copy k_respawn makes (respawn_write_list).
 #pragma once
 #include "sca_respawn.hip.h"
 #include "sca_missions.h"
@@ -32,7 +34,30 @@ struct MissionDev {
     unsigned long long *totals;     // [MST_WORDS]
     long long update;               // the env update this launch belongs to, counted from sca_set_missions (1-based)
     int M, R;
+    // tables with lists (sca_set_missions_paths in slot form; row.path_len .. row.W are set with them, null / 0 otherwise): the packed CSR
+    // the call brought, immutable until the tables are replaced -- path_off [M n + 1] over the flat entry index (null: every entry brings
+    // the empty list), path_pts the points
+    const int32_t *path_off;
+    const double *path_pts;
 };
+// The take of entry nx by row a, by the whole wavefront (everything wave-uniform): the row becomes what sca_respawn_agents naming it with the
+// entry's values -- and, with lists, the entry's list as its path arrays -- leaves.  flags: the flag word the row ended with.  The caller
+// has fenced its own loads of the row's old words; the old length is loaded here in front of every store of the row (see below).
+__device__ __forceinline__ RespawnRow mission_take_row(const MissionDev &m, int a, int nx, uint32_t flags, int lane) {
+    const bool lists = m.row.path_len != nullptr;
+    const int32_t old_len = lists ? m.row.path_len[a] : 0;
+    // The loads of the row's old words (the result's, the flag word, the old length) stand in front of the row's stores in the ONE
+    // wavefront that does both.  For the result's per-lane VECTOR loads the argument is the older one: the wavefront's vector memory
+    // instructions issue in program order and go down one path to the same cache, and the fence only keeps the compiler from moving the
+    // stores up.  The old length is different: its address is the same for the whole wavefront, so the compiler may fetch it through the
+    // SCALAR path, which is not ordered against the vector stores.  It is held by two things that ARE relied on: every store of a path
+    // word and of vpref_mode is issued behind the fence, and the seq_cst fence at workgroup scope makes the compiler wait for every
+    // outstanding load, scalar ones included, before anything behind it issues; and `bits`, which decides the mode store, is computed
+    // from the loaded value.
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    const int64_t fe = (int64_t)m.M * a + nx;
+    return mission_take_write(m.row, a, lane, m.policy[a], flags, m.entries + fe, lists, old_len, m.path_off, m.path_pts, fe);
+}
 constexpr int MISSION_T = 256;
 __device__ __forceinline__ void mission_total(unsigned long long *totals, int which, unsigned long long mask, int lane) {
     if (lane == 0 && mask) atomicAdd(&totals[which], (unsigned long long)__popcll(mask));
@@ -94,13 +119,7 @@ __global__ __launch_bounds__(MISSION_T) void k_mission_advance(MissionDev m) {
             ((RespawnPiece *)out)[lane] = q;
         }
         if (nx < 0) continue;                                              // the row stays finished as it is
-        // The result's loads of the row's old words stand in front of the row's stores in the ONE wavefront that does both: its memory
-        // instructions issue in program order and go down one path to the same cache, which is what keeps the loads ahead.  The fence
-        // only keeps the compiler from moving the stores up over the loads; it is not relied on for a wait of its own.
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        const sca_mission *e = m.entries + ((int64_t)m.M * a + nx);
-        const RespawnRow w = respawn_row(mission_bits(m.policy[a], m.row.trk_st != nullptr), flags, mission_has(*e), 0);
-        respawn_write_row(m.row, a, lane, w, MissionSrc{e});
+        (void)mission_take_row(m, a, nx, flags, lane);                     // (the result's loads above stay in front of the row's stores: its note)
     }
     if (in) m.live[row] = next >= 0 || !(fn & RSP_DONE_FLAGS) ? 1 : 0;
     if (ended && table) {

@@ -237,7 +237,7 @@ SCA_HD RespawnRow respawn_row(uint8_t bits, uint32_t old_flags, uint32_t has, in
 //   scalar fields     lane 0 (respawn_row says which and what)
 //   AgentTrack        consecutive 4-byte words by consecutive lanes from the one initial record (tracked rows under the device tracker)
 // Dev: the arrays a respawn writes (RespawnDev in sca_respawn.hip.h; plain host arrays in the tests' harnesses); null pointers (no tracker,
-// no lists, no closest-approach records) are skipped.  Not here: the done_count stripe (an atomic) and the waypoints (the block's alone).
+// no lists, no closest-approach records) are skipped.  Not here: the done_count stripe (an atomic) and the waypoints (respawn_write_list).
 struct __attribute__((may_alias, aligned(16))) RespawnPiece { uint32_t w[4]; };
 // a piece from its values, word by word (no local array whose address is taken: nothing of it goes to scratch)
 SCA_HD void piece_put64(RespawnPiece &q, int half, double x) { uint64_t u; __builtin_memcpy(&u, &x, 8); q.w[2 * half] = (uint32_t)u; q.w[2 * half + 1] = (uint32_t)(u >> 32); }
@@ -276,6 +276,16 @@ SCA_HD void respawn_write_row(const Dev &d, int a, int lane, const RespawnRow &w
     }
     if (w.tracked && d.trk_st)                                         // the AgentTrack record, word by word from the one initial record
         for (int k = lane; k < d.trk_words; k += 64) d.trk_st[(int64_t)a * d.trk_words + k] = d.trk_init[k];
+}
+
+// ---- the list write --------------------------------------------------------------------------------------------------------------------------
+// A row's new list into its own room pts[3 (W a + k)]: consecutive lanes of the wavefront that serves row `a` on consecutive coordinates,
+// behind respawn_write_row (which has written len = rem = `len` and now_goal None).  src: the list's first coordinate -- in the call's block
+// (k_respawn) or in the tables' packed lists (k_mission_advance, k_mission_gate_take): the three share this copy so that they cannot drift
+// apart.  Room behind the list's length is never read (rem <= len) and is left as it is.
+SCA_HD void respawn_write_list(double *pts, int W, int a, int lane, const double *src, int32_t len) {
+    double *dst = pts + 3 * path_slot_index(W, a);
+    for (int k = lane; k < 3 * len; k += 64) dst[k] = src[k];
 }
 
 // ---- the finished list -------------------------------------------------------------------------------------------------------------------

@@ -16,7 +16,7 @@ namespace sca {
 //   AgentTrack        consecutive 4-byte words by consecutive lanes from the one initial record (tracked rows under the device tracker)
 //   three-component   heading, goal (goal_heading, vpref_ext, now_goal): one component per lane 0 .. 2
 //   scalar fields     lane 0, plain vector stores (respawn_row says which and what)
-//   waypoints         consecutive lanes on consecutive coordinates into the row's own room pts[3 (W a + j)]
+//   waypoints         consecutive lanes on consecutive coordinates into the row's own room pts[3 (W a + j)] (respawn_write_list, sca_respawn.h)
 // Null device pointers (no tracker, no lists, no closest-approach records) are skipped by a uniform branch.
 // Not written, as under a scene restart: action, diag, vpref_used, vpost, is_fb, prep, coll_new, nbr_id, nbr_dsq, near_id, the kd nodes --
 // a pass writes each of them for every agent it serves before anybody reads it.
@@ -55,11 +55,8 @@ __global__ __launch_bounds__(RESPAWN_WAVES * 64) void k_respawn(RespawnDev d, co
     // K4's counters of the last step, before the record is replaced: a row that was done runs again (sca_active_count between steps)
     if (lane == 0 && w.done_delta) atomicAdd(&d.done_count[(a & 255) * 32], w.done_delta);
     respawn_write_row(d, a, lane, w, RespawnBlockSrc{blk, L, r});      // (sca_respawn.h: the row write k_mission_advance shares)
-    if (w.path_len > 0 && d.path_pts) {                              // the row's list into its own room
-        const double *src = (const double *)(blk + L.off[RSB_PATH_PTS]) + 3 * (int64_t)first;
-        double *dst = d.path_pts + 3 * path_slot_index(d.W, a);
-        for (int k = lane; k < 3 * w.path_len; k += 64) dst[k] = src[k];
-    }
+    if (w.path_len > 0 && d.path_pts)                                // the row's list into its own room
+        respawn_write_list(d.path_pts, d.W, a, lane, (const double *)(blk + L.off[RSB_PATH_PTS]) + 3 * (int64_t)first, w.path_len);
 }
 
 // ---- the finished list -------------------------------------------------------------------------------------------------------------------

@@ -213,8 +213,12 @@ class Agent:
 
     @path.setter
     def path(self, value):
-        self._path = value
         env = self._env
+        if env is not None and getattr(env, '_missions', None) is not None and env._path_slots:
+            # (the upload would be sca_set_path_slots, which the library refuses while tables stand -- in the middle of the next step)
+            raise RuntimeError('agent.path is read-only while mission tables stand on a MACAEnv(path_slots=W): the rows take their lists from '
+                               'the tables\' entries (MissionTable(path=...)); drop the tables first (set_missions(None))')
+        self._path = value
         if env is not None:
             env._path_assigned.add(self.id)               # uploaded in front of the next step
 
@@ -275,9 +279,14 @@ class MissionTable:
     max_run_dist and goal heading are read off them as respawn() reads them; the id is ignored).  Per entry: start_here -- the row
     keeps the position and heading it has, the entry's start is ignored; keep_zaxis -- it keeps its z-axis flag; next_ok / next_fail
     -- the entry flown after an arrival / after a collision or time-out, -1: the row stays finished for the host.  first_ok /
-    first_fail: the successors of the flight that is in the air when the table is set."""
-    def __init__(self, entries, next_ok, next_fail, first_ok=0, first_fail=-1, start_here=True, keep_zaxis=False):
+    first_fail: the successors of the flight that is in the air when the table is set.
+    path: one waypoint list per entry (None: each entry's own Agent.path, usually empty) -- the route the row follows while it flies the
+    entry, in Agent.path's order (get_trajectory pops from the end).  Needs MACAEnv(path_slots=W) with W >= the longest list."""
+    def __init__(self, entries, next_ok, next_fail, first_ok=0, first_fail=-1, start_here=True, keep_zaxis=False, path=None):
         k = len(entries)
+        if path is not None and len(path) != k:
+            raise ValueError('MissionTable: one path per entry (an empty list for an entry without a route)')
+        self.paths = [[list(map(float, w[:3])) for w in (a._path if path is None else path[j])] for j, a in enumerate(entries)]
         here = [bool(start_here)] * k if isinstance(start_here, (bool, int)) else [bool(x) for x in start_here]
         keep = [bool(keep_zaxis)] * k if isinstance(keep_zaxis, (bool, int)) else [bool(x) for x in keep_zaxis]
         self.entries = [(a, here[j], keep[j]) for j, a in enumerate(entries)]
@@ -661,7 +670,11 @@ class MACAEnv(_FlatAgents):
         keep_zaxis, or a nominal start that says what the leg is.
         spawn_margin (metres): the admission gate on the device (sca_set_mission_gate) -- a row takes its successor only where the
         start is free by that margin, as respawn(margin=) decides it; a refused row stays finished and is offered again behind every
-        step, waiting rows first.  max_per_step: the candidates tested per step (None: min(n, 4096))."""
+        step, waiting rows first.  max_per_step: the candidates tested per step (None: min(n, 4096)).
+        Routes: an entry's waypoint list (MissionTable(path=...) or the entry's own Agent.path) needs MACAEnv(path_slots=W) -- a row that
+        takes the entry gets the list as under respawn() (sca_set_missions_paths); a list above W is a ValueError before any device
+        call.  mission_results() then sets agent.path to the taken entry's list, cut to what the passes since have left of it.  While
+        such tables stand agent.path is read-only: assigning it raises a RuntimeError (drop the tables first)."""
         if self.agents is None:
             raise RuntimeError('set_missions: set_agents first')
         if self._row_cache is not None:
@@ -677,6 +690,7 @@ class MACAEnv(_FlatAgents):
         e['pref_speed'] = e['max_run_dist'] = 1.0                     # (rows and slots nobody reaches: legal values, never read)
         e['next_ok'] = e['next_fail'] = -1
         first_ok, first_fail = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+        lists = {}                                                    # MACAEnv(path_slots=W): (row, entry) -> the entry's waypoint list
         for i, t in tables.items():
             if not 0 <= int(i) < n:
                 raise ValueError('set_missions: %r names no row of this env, 0 .. %d' % (i, n - 1))
@@ -684,8 +698,11 @@ class MACAEnv(_FlatAgents):
             for j, (a, here, keep) in enumerate(t.entries):
                 if a.policy.policy_id != old.policy.policy_id:
                     raise ValueError(f'set_missions: entry {j} of agent {i} has policy {type(a.policy).__name__}, the row runs {type(old.policy).__name__} (a row keeps its policy)')
-                if len(a._path):
-                    raise ValueError(f'set_missions: entry {j} of agent {i} brings a path: waypoint lists and mission tables exclude each other')
+                if len(t.paths[j]) > self._path_slots:
+                    raise ValueError(f'set_missions: entry {j} of agent {i} brings a path of {len(t.paths[j])} waypoints: MACAEnv(path_slots=W) with W >= that '
+                                     'keeps the lists in slot form, where a row that takes an entry gets the entry\'s list')
+                if self._path_slots:
+                    lists[(int(i), j)] = t.paths[j]
                 start, goal6 = np.asarray(a.initial_pos, np.float64), np.asarray(a.goal_pos, np.float64)
                 r = e[i, j]
                 r['pos'], r['heading'], r['goal'], r['goal_heading'], r['vel'] = a._pos, a._heading, goal6[:3], goal6[3:6], a._vel
@@ -694,7 +711,11 @@ class MACAEnv(_FlatAgents):
                 r['flags'] = (S.MISSION_START_HERE if here else 0) | (S.MISSION_KEEP_ZAXIS if keep else 0)
                 r['next_ok'], r['next_fail'] = t.next_ok[j], t.next_fail[j]
             first_ok[i], first_fail[i] = t.first_ok, t.first_fail
-        self.solver.set_missions(M, int(results), e, first_ok, first_fail)
+        if self._path_slots:                                          # the lists live in slot form: every entry brings its list, the empty one too
+            self._sync_paths()                                        # (lists assigned since the last step go up first: the flight in the air keeps its own)
+            self.solver.set_missions(M, int(results), e, first_ok, first_fail, paths=lists)
+        else:
+            self.solver.set_missions(M, int(results), e, first_ok, first_fail)
         self._missions = dict(tables)
         self._mission_gate, self._mission_pending = spawn_margin is not None, {}
         if self._mission_gate:
@@ -735,8 +756,12 @@ class MACAEnv(_FlatAgents):
             a.initial_pos = np.concatenate([r['pos'], a.initial_pos[3:]]) if here else src.initial_pos.copy()
             a.pref_speed, a.max_run_dist = src.pref_speed, src.max_run_dist
             self.goal[i] = a.goal_global_frame
+            if self._path_slots:                                      # the entry's whole list; the next read cuts it to what the passes since have left
+                a._path = [list(w) for w in self._missions[i].paths[j]]
+                self._path_assigned.discard(i)
         if len(res) or moved:
             self._stale = True
+            self._path_stale = self._paths_on
         return res
 
     def run_steps(self, k):

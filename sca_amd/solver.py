@@ -194,6 +194,20 @@ class BatchedSolver:
         self._chk(self.L.sca_get_path_state(self.ctx, _lib.ptr(rem, C.c_int32), _lib.ptr(ng, C.c_double)), 'sca_get_path_state')
         return rem, ng
 
+    def path_slot_lists(self):
+        """(len [n] int32, rooms [n, W, 3]): the lists as the rows hold them in slot form (sca_get_path_slot_lists) -- row a's list is
+        rooms[a, :len[a]], in list order; what stands behind it is whatever an earlier list left there"""
+        W = self.path_slots
+        ln, rooms = np.zeros(self.n, np.int32), np.zeros((self.n, max(W, 1), 3))
+        self._chk(self.L.sca_get_path_slot_lists(self.ctx, _lib.ptr(ln, C.c_int32), _lib.ptr(rooms, C.c_double)), 'sca_get_path_slot_lists')
+        return ln, rooms
+
+    def vpref_mode(self):
+        """the rows' vpref_mode bytes as the next pass will read them (sca_get_vpref_mode)"""
+        mode = np.zeros(self.n, np.uint8)
+        self._chk(self.L.sca_get_vpref_mode(self.ctx, _lib.ptr(mode, C.c_uint8)), 'sca_get_vpref_mode')
+        return mode
+
     def set_path_state(self, remaining, now_goal):
         rem = np.ascontiguousarray(remaining, np.int32).reshape(self.n)
         ng = _lib.as_d(now_goal).reshape(self.n, 3)
@@ -559,11 +573,14 @@ class BatchedSolver:
         return out[:max(0, min(cap, self.finished_count))]
 
     # ---- mission tables: finished rows take their next mission inside the step (sca_set_missions) ------------------------------
-    def set_missions(self, M, R, entries, first_ok, first_fail):
+    def set_missions(self, M, R, entries, first_ok, first_fail, paths=None):
         """Every row gets room for M mission entries and a ring of R result records (sca_set_missions; include/sca_hip.h has the rule and
         what is refused).  entries: a structured array of _lib.MISSION_DTYPE, (n, M) or flat in slot form entries[M a + j]; first_ok /
         first_fail: per row the successors of the flight in the air (-1 / -1: the row has no table).  M = 0 with entries None drops the
-        tables."""
+        tables.
+        paths (sca_set_missions_paths; the lists in slot form, set_path_slots first): every entry brings its own waypoint list, which a
+        row that takes the entry gets as under respawn(paths=...).  One list of [x, y, z] waypoints per FLAT entry M a + j (list order:
+        the reference pops from the end), or a dict {(row, j): [...]} whose missing entries bring the empty list."""
         if entries is None and int(M) == 0:
             self._chk(self.L.sca_set_missions(self.ctx, 0, 0, 0, None, None, None), 'sca_set_missions')
             self._missions = None
@@ -573,9 +590,30 @@ class BatchedSolver:
         first_fail = np.ascontiguousarray(first_fail, np.int32).reshape(-1)
         if len(entries) != int(M) * len(first_ok) or len(first_fail) != len(first_ok):
             raise ValueError(f'set_missions: {len(entries)} entries, {len(first_ok)} / {len(first_fail)} first successors where M = {M}')
-        self._chk(self.L.sca_set_missions(self.ctx, int(M), int(R), len(first_ok), entries.ctypes.data_as(C.POINTER(_lib.Mission)),
-                                          _lib.ptr(first_ok, C.c_int32), _lib.ptr(first_fail, C.c_int32)), 'sca_set_missions')
+        if paths is None:
+            self._chk(self.L.sca_set_missions(self.ctx, int(M), int(R), len(first_ok), entries.ctypes.data_as(C.POINTER(_lib.Mission)),
+                                              _lib.ptr(first_ok, C.c_int32), _lib.ptr(first_fail, C.c_int32)), 'sca_set_missions')
+        else:
+            if isinstance(paths, dict):
+                flat = [[] for _ in range(len(entries))]
+                for (a, j), lst in paths.items():
+                    if not (0 <= int(a) < len(first_ok) and 0 <= int(j) < int(M)):
+                        raise ValueError(f'set_missions: paths names entry ({a}, {j}) where there are {len(first_ok)} rows of M = {M} entries')
+                    flat[int(M) * int(a) + int(j)] = lst
+                paths = flat
+            if len(paths) != len(entries):
+                raise ValueError(f'set_missions: {len(paths)} waypoint lists where there are {len(entries)} entries')
+            off, pts = paths_csr(paths)
+            self._chk(self.L.sca_set_missions_paths(self.ctx, int(M), int(R), len(first_ok), entries.ctypes.data_as(C.POINTER(_lib.Mission)),
+                                                    _lib.ptr(first_ok, C.c_int32), _lib.ptr(first_fail, C.c_int32), _lib.ptr(off, C.c_int32),
+                                                    _lib.ptr(pts, C.c_double)), 'sca_set_missions_paths')
         self._missions = (int(M), int(R))
+
+    def mission_paths(self):
+        """(W, total): the room per row and the points the tables' lists hold (sca_get_mission_paths); (0, 0) for tables without lists"""
+        w, total = C.c_int(0), C.c_int64(0)
+        self._chk(self.L.sca_get_mission_paths(self.ctx, C.byref(w), C.byref(total)), 'sca_get_mission_paths')
+        return int(w.value), int(total.value)
 
     def mission_results(self, capacity=None):
         """The results not yet collected, ascending id and within a row oldest first: a structured array of _lib.MISSION_RESULT_DTYPE

@@ -22,6 +22,17 @@ library is loaded beside this build's (--root: the parent's checkout, built).  F
     bench     (only when named in --parts, with --root) `bench.py --gpus 1 --steps 200 --warmup 20` as a child process, the parent's checkout and
               this one alternated twice, in front of everything else: the ms_per_step of each run's JSON line
 
+--paths (tables whose entries bring their own waypoint lists, sca_set_missions_paths; merged into profiles/mission_paths_cost.json):
+    step      as above, and `step_tables` as under --gate: idle tables WITHOUT lists in both builds -- the same kernels apart from the changed
+              symbols (k_mission_advance's take goes through the shared helper)
+    tables    becomes `paths`: both legs in slot form (W = 2, every row holds a list of two points, so k_waypoint_slots runs in both) with
+              idle tables set through sca_set_missions_paths, nobody ending -- `off`: every entry brings the empty list,
+              `on`: every entry brings a list of two points.  The two enqueue the same kernels: the work rides in the take
+    lifelong  the circle with routes of two waypoints per leg, reversed on the way back (examples/run_sca.py --waypoints 2): run_lifelong
+              whose next_mission hands out the routes against run_missions whose entries bring them, at burst 1 and 64
+    collect   left out
+    bench     as under --gate
+
 workloads: respawn_cost.py's (c3_auto: circle N = 4096 ORCA3D SCA_NBR_AUTO; c4: circle N = 100 000 SCA, device tracker, SCA_NBR_KDTREE)"""
 import argparse
 import importlib
@@ -93,7 +104,16 @@ def part_tables(here, w, args):
     order = ['on', 'off'] if args.here_first else ['off', 'on']
     legs = {k: make_leg(S, scenarios, w) for k in order}
     e, ok, fail = idle_tables(_lib, legs['on']['sc'], legs['on']['n'])
-    legs['on']['sol'].set_missions(1, 1, e, ok, fail)
+    if args.paths:                                                                    # slot form and tables in both legs, the entries' lists in one
+        for k, leg in legs.items():
+            sc, n = leg['sc'], leg['n']
+            mid = [[list(map(float, sc['start'][i, :3] + (sc['goal'][i, :3] - sc['start'][i, :3]) * f)) for f in (0.7, 0.3)] for i in range(n)]
+            leg['sol'].set_path_slots(2, mid)
+            leg['sol'].set_missions(1, 1, e, ok, fail, paths=mid if k == 'on' else {})
+            reset = leg['reset']
+            leg['reset'] = lambda reset=reset, sol=leg['sol'], n=n: (reset(), sol.set_path_state(np.full(n, 2, np.int32), np.full((n, 3), np.nan)))
+    else:
+        legs['on']['sol'].set_missions(1, 1, e, ok, fail)
     if args.gate:                                                                     # tables in both legs, the gate in one
         legs['off']['sol'].set_missions(1, 1, e, ok, fail)
         legs['on']['sol'].set_mission_gate(0.5)
@@ -125,15 +145,24 @@ def part_lifelong(args):
     LL = importlib.import_module('sca_here.lifelong')
 
     def world():
-        env = E.MACAEnv()
+        env = E.MACAEnv(path_slots=2) if args.paths else E.MACAEnv()
         agents = E.build_circle_agents(n, policy=E.ORCA3DPolicy)
-        env.set_agents(agents, obstacles=[])
         first = {a.id: (list(a.initial_pos), list(a.goal_pos)) for a in agents}
+        route = {}
+        if args.paths:                                                                # two seeded waypoints per leg, reversed on the way back (the example's --waypoints 2)
+            for i, (s, g) in first.items():
+                rng = np.random.default_rng(1000 + i)
+                p, q = np.asarray(s[:3], float), np.asarray(g[:3], float)
+                route[i] = [[float(x) for x in np.round(p + (q - p) * (k + 1) / 3 + rng.normal(0.0, 0.5, 3), 3)] for k in range(2)]
+            for a in agents:
+                a.path = route[a.id][::-1]
+        env.set_agents(agents, obstacles=[])
 
         def entry(i, start, goal):
             return E.Agent(start_pos=start, goal_pos=goal, vel=[0.0, 0.0, 0.0], radius=agents[i].radius, pref_speed=agents[i].pref_speed, policy=E.ORCA3DPolicy, id=i)
         tables = {i: E.MissionTable([entry(i, goal, start), entry(i, start, goal), entry(i, start, goal)], next_ok=[1, 0, 0], next_fail=[2, 2, 2], first_ok=0, first_fail=2,
-                                    start_here=[True, True, False]) for i, (start, goal) in first.items()}
+                                    start_here=[True, True, False], path=[route[i][:], route[i][::-1], route[i][::-1]] if args.paths else None)
+                  for i, (start, goal) in first.items()}
         return env, tables, entry
     out = {}
     for name in ('run_lifelong', 'run_missions_burst_1', 'run_missions_burst_64'):
@@ -151,6 +180,8 @@ def part_lifelong(args):
                 src, here, _ = t.entries[j]
                 new = entry(a.id, list(row['pos']) + list(a.heading_global_frame) if here else list(src.initial_pos), list(src.goal_pos))
                 new.max_run_dist = src.max_run_dist
+                if args.paths:
+                    new.path = [w[:] for w in t.paths[j]]
                 return new
             stats = LL.run_lifelong(env, next_mission, steps, **({'spawn_margin': 0.5} if args.gate else {}))
         else:
@@ -225,10 +256,13 @@ def main():
     ap.add_argument('--here-first', action='store_true', help='step and tables parts: this build\'s (the tables\') context is made and timed first')
     ap.add_argument('--lifelong-steps', type=int, default=20000)
     ap.add_argument('--gate', action='store_true', help='the admission gate on the device: see above; --out defaults to profiles/mission_gate_cost.json')
+    ap.add_argument('--paths', action='store_true', help='tables whose entries bring waypoint lists: see above; --out defaults to profiles/mission_paths_cost.json')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    if args.gate and args.paths:
+        ap.error('--gate and --paths are two legs: one at a time')
     if args.out is None:
-        args.out = os.path.join(REPO, 'profiles', 'mission_gate_cost.json' if args.gate else 'mission_cost.json')
+        args.out = os.path.join(REPO, 'profiles', 'mission_gate_cost.json' if args.gate else 'mission_paths_cost.json' if args.paths else 'mission_cost.json')
     bench = part_bench(args) if 'bench' in args.parts.split(',') and args.root else None      # (in front of everything that opens the GPU here)
     here = load_package(REPO, 'sca_here')
     parent = load_package(args.root, 'sca_parent') if args.root else None
@@ -252,21 +286,21 @@ def main():
             entry['step' + suffix] = part_step(here, parent, w, args)
             print(name, 'step', json.dumps(entry['step' + suffix]), flush=True)
             save()
-            if args.gate and parent:
+            if (args.gate or args.paths) and parent:
                 entry['step_tables' + suffix] = part_step_tables(here, parent, w, args)
                 print(name, 'step_tables', json.dumps(entry['step_tables' + suffix]), flush=True)
                 save()
         if 'tables' in parts:
-            key = ('gate' if args.gate else 'tables') + suffix
+            key = ('gate' if args.gate else 'paths' if args.paths else 'tables') + suffix
             entry[key] = part_tables(here, w, args)
             print(name, key, json.dumps(entry[key]), flush=True)
             save()
     if 'lifelong' in parts:
-        key = 'lifelong_circle_4096_%d_steps' % args.lifelong_steps + ('_margin_0.5' if args.gate else '')
+        key = 'lifelong_circle_4096_%d_steps' % args.lifelong_steps + ('_margin_0.5' if args.gate else '_waypoints_2' if args.paths else '')
         result[key] = part_lifelong(args)
         print(key, json.dumps(result[key]), flush=True)
         save()
-    if 'collect' in parts and not args.gate:
+    if 'collect' in parts and not args.gate and not args.paths:
         result['collect_4096'] = part_collect(here, args)
         print('collect', json.dumps(result['collect_4096']), flush=True)
     save()
