@@ -78,7 +78,16 @@ def lifelong(args, agents, obstacles, pol, dubins):
         tables = {i: E.MissionTable([entry(i, goal, start), entry(i, start, goal), entry(i, start, goal)], next_ok=[1, 0, 0], next_fail=[2, 2, 2],
                                     first_ok=0, first_fail=2, start_here=[True, True, False], path=[back_list[i], out_list[i], out_list[i]] if K else None)
                   for i, (start, goal) in first.items()}
-        stats = run_missions(env, tables, args.lifelong, burst=args.burst, spawn_margin=args.spawn_margin)
+        if args.resume:                                            # the env as --save-at left it; its tables stand, the run goes on for what is left
+            from sca_amd.checkpoint import ContextCheckpoint
+            ck = ContextCheckpoint.read(args.resume)
+            env = E.MACAEnv.from_checkpoint(ck)
+            stats = run_missions(env, None, args.lifelong - ck.steps, burst=args.burst)
+        else:
+            stats = run_missions(env, tables, args.lifelong, burst=args.burst, spawn_margin=args.spawn_margin,
+                                 checkpoint_at=(args.save_at, args.save_file) if args.save_at else None)
+            if args.save_at:
+                print('saved behind step', args.save_at, 'as', args.save_file)
     else:
         stats = run_lifelong(env, next_mission, args.lifelong) if args.spawn_margin is None else \
             run_lifelong(env, next_mission, args.lifelong, spawn_margin=args.spawn_margin)
@@ -119,7 +128,14 @@ def main():
     ap.add_argument('--waypoints', type=int, default=0, metavar='K',
                     help='with --lifelong: every leg follows a route of K seeded waypoints, reversed on the way back (with --device-missions '
                          'the entries bring the routes: MissionTable(path=), sca_set_missions_paths)')
+    ap.add_argument('--save-at', type=int, default=0, metavar='K', help='with --device-missions: stop behind step K and write the running env '
+                    '(MACAEnv.checkpoint: definition + sca_save_context) to --save-file')
+    ap.add_argument('--save-file', default='run_sca_checkpoint.npz', metavar='F')
+    ap.add_argument('--resume', default=None, metavar='F', help='with --lifelong S --device-missions: go on from the file --save-at wrote, up to step S '
+                    '(MACAEnv.from_checkpoint); the last line is that of the run that was never cut')
     args = ap.parse_args()
+    if (args.save_at or args.resume) and not args.device_missions:
+        ap.error('--save-at / --resume go with --lifelong STEPS --device-missions')
     if args.device_missions and args.lifelong <= 0:
         ap.error('--device-missions goes with --lifelong STEPS')
     if args.waypoints < 0 or (args.waypoints and args.lifelong <= 0):

@@ -567,6 +567,89 @@ int sca_scene_checkpoint_bytes(sca_ctx *ctx, int scene, int64_t *bytes);
 int sca_save_scenes(sca_ctx *ctx, int count, const int32_t *scene_ids /*count*/, void *const *out /*count*/, const int64_t *out_bytes /*count*/);
 int sca_load_scenes(sca_ctx *ctx, int count, const int32_t *scene_ids /*count*/, const void *const *in /*count*/, const int64_t *in_bytes /*count*/);
 
+/* Context checkpoints: a running PLAIN context -- no scenes -- out as one blob of bytes, and back into a fresh context.  What the scene
+ * checkpoints above are to an episode, this is to a whole swarm with everything a long run leaves in it: respawned rows, missions taken
+ * from the tables, lists rewritten by takes, rows waiting at the gate, results not yet collected, closest-approach records.  The blob holds
+ * the MUTABLE state only; the run's DEFINITION stays the caller's and is set up before the load: sca_create's parameters, sca_set_agents
+ * (n and the policies must match; every other value is overwritten from the blob), sca_set_agent_params, sca_set_obstacles, any
+ * sca_set_state, sca_device_tracker_enable + sca_device_tracker_set_agent_params, the list form (sca_set_paths with the same lists, or
+ * sca_set_path_slots(W)), sca_set_missions[_paths] with the same tables, sca_set_mission_gate, sca_clearance_enable.  The contract: after
+ * the definition + sca_load_context(B, blob), where blob = sca_save_context(A) was taken behind A's k-th env update, B is bit for bit A
+ * from there on -- state, float32 action rows, neighbour lists and their distSq, diag, status, the kd permutation, sca_active_count,
+ * sca_get_finished, tracker v_pref, plans and re-plan counts, remaining / now_goal / the rooms / vpref_mode, mission cursors, `ended`,
+ * results (collected marks included), totals, gate words, verdicts and totals, closest-approach records -- in the same process, in
+ * another process, and in a context of another size (max_agents >= n).  FORMS may differ (SCA_NBR_AUTO's counts, the kd build's sizing
+ * hints and the tracker's form heuristics start over, as behind sca_set_state); values may not.  Detect the feature by the symbol
+ * (sca_version() is unchanged).
+ *              One bit is not a value: in SCA_NBR_GRID, SCA_ST_NBR_OVERFLOW in the status word of a row that COLLIDES in the pass may also
+ *              stand because the list was full before the first colliding object was met (the grid's list rule above).  That depends on the
+ *              order in which a cell hands its agents out -- the arrival order of the grid build's atomics, which no state fixes, in one
+ *              context run twice as little as in two.  No kernel reads the bit, and the next pass clears it (the row is finished: the
+ *              grid pass writes 0 for a row it lists nothing for).  Every other bit of `status`, and this bit on every other row, is held.
+ *   in the blob  a 128-byte header (magic, format version, sca_version(), n, the tracker record's words, the public record's bytes, what
+ *              is present, the list form and W, M and R, k_clearance's step number, the missions' update count, whether the one-time
+ *              obstacle check behind sca_set_state is still pending, the byte count, a 64-bit checksum of everything behind the header),
+ *              then sections of whole 4-byte words, each on a 16-byte boundary, offsets 64-bit.  Per row, always: the policy byte
+ *              (compared at the load, not loaded), the public record, heading, goal, pref_speed, max_run_dist, the z-axis byte, v_pref as
+ *              fed / tracked and its mode, total_dist, step_num, status, the kd permutation.  With the device tracker: goal_heading, the
+ *              first neighbour's distSq the tracker reads, the tracker records.  With lists: remaining and now_goal; in slot form also
+ *              the lengths and the rooms whole, W points a row (what stands behind a list's length travels as it stands).  With tables:
+ *              the seven words per row, the R-ring per row, the totals; with a gate its four words per row and its totals.  With
+ *              closest-approach records: the 32-byte record per row.  Between the load and the next pass every getter that reads state
+ *              returns what it returned on the source at the save.
+ *   not in it  the OUTPUTS of the last pass (action rows, neighbour lists, diag, vpref_used: they follow with the next pass), the
+ *              trajectory log (a resumed context's log starts at its own row 0; the rows before k are the caller's to keep),
+ *              sca_agent_steps, every form heuristic, and the definition: table entries and their lists, the lists of the block form.
+ *   sca_context_checkpoint_layout  byte offsets of the SCA_CONTEXT_CHECKPOINT_SECTIONS sections (an absent section has length 0: its offset
+ *              is the next section's) and the blob's size for a shape.  Pure.  SCA_ERR_ARG: a NULL pointer, struct_bytes other than
+ *              sizeof(sca_context_checkpoint_shape), n < 1, negative trk_words, list_form outside 0 .. 2, W < 1 in slot form or != 0
+ *              elsewhere, M outside 0 .. 127, R < 1 with tables or != 0 without, a gate without tables, a flag that is not 0 / 1.
+ *   sca_context_checkpoint_info    the header's fields, after the WHOLE check of the blob that a load makes without a context (envelope and
+ *              payload, below).  Pure, no context.  struct_bytes: sca_scene_harvest_get's rule.
+ *   sca_context_checkpoint_bytes   the size of the blob sca_save_context writes for the context as it stands now; refused where a save is.
+ *   sca_save_context   out (out_bytes bytes) receives the blob.
+ *   sca_load_context   in (in_bytes bytes) goes into the context, which must hold the blob's definition: what the blob carries is compared
+ *              with what the context has on.  K4's counters follow the loaded flags, so sca_active_count is right at once.
+ *   cost       each call is one kernel launch and one stream synchronisation at any n; the kernel stores straight into (reads straight
+ *              from) a page-locked block of the library's own, allocated at the first call, which grows when a call needs more.  A context
+ *              that never calls these entry points allocates nothing for them and enqueues what it did.
+ *   refusals   decided on the host before any device work; a refused call has changed nothing; a damaged blob never reaches the device.
+ *              SCA_ERR_STATE: no agents, no state yet, between a policy pass and its env update.  SCA_ERR_UNSUPPORTED: scenes (they have
+ *              sca_save_scenes / sca_load_scenes), a shard with count < n, a communicator, the cell-owner partition.  SCA_ERR_ARG: a NULL
+ *              buffer, an output buffer too small (the message names the bytes needed); at a load, the envelope: short, wrong magic or
+ *              format version, trk_words or the record size not this library's, header words out of range, a byte count that is not the
+ *              layout's, a checksum mismatch; the blob against the context, each named in the message: n, a row's policy, the tracker,
+ *              the lists (form, W, in block form a cursor beyond the list's length as set), the tables (M, R), the gate, the
+ *              closest-approach records; the payload: a permutation that is not one of 0 .. n-1, unknown flag bits, a vpref_mode or
+ *              z-axis word other than 0 / 1, a position that is not finite, a radius, pref_speed or max_run_dist that is not positive,
+ *              a negative step count, len outside 0 .. W, remaining outside 0 .. len, a successor / cursor / flying / waiting word outside
+ *              -1 .. M-1, collected above ended, a verdict word above SCA_SPAWN_OVER_CAP, a closest-approach partner outside its range,
+ *              any tracker integer a kernel uses as a cursor, count or switch outside its range. */
+#define SCA_CONTEXT_CHECKPOINT_SECTIONS 26
+enum sca_context_checkpoint_lists { SCA_CHECKPOINT_LISTS_NONE = 0, SCA_CHECKPOINT_LISTS_BLOCK = 1, SCA_CHECKPOINT_LISTS_SLOTS = 2 };
+typedef struct sca_context_checkpoint_shape {   /* what a blob's layout depends on */
+    int32_t struct_bytes;
+    int32_t n, trk_words;                /* agents; the tracker record's 4-byte words (0: no device tracker) */
+    int32_t list_form, W;                /* sca_context_checkpoint_lists; the room per row in slot form, else 0 */
+    int32_t M, R;                        /* the tables' (0, 0: none) */
+    int32_t has_gate, has_clearance;     /* 0 / 1 */
+} sca_context_checkpoint_shape;
+struct sca_context_checkpoint_info {     /* (a struct tag: the function of the same name fills it) */
+    int32_t struct_bytes, reserved;
+    int32_t format, lib_version;         /* the blob's format version; sca_version() of the library that wrote it */
+    int32_t n, trk_words, record_bytes;
+    int32_t has_tracker, list_form, W, M, R, has_gate, has_clearance;
+    int32_t clear_step, state_fresh;     /* k_clearance's step number; 1: saved directly behind sca_set_state */
+    int64_t updates;                     /* env updates since sca_set_missions */
+    int64_t total_bytes;
+    uint64_t checksum;
+};
+int sca_context_checkpoint_layout(const sca_context_checkpoint_shape *shape, int64_t *offsets /*SCA_CONTEXT_CHECKPOINT_SECTIONS*/, int64_t *total_bytes);
+int sca_context_checkpoint_info(const void *blob, int64_t bytes, struct sca_context_checkpoint_info *out, int32_t struct_bytes);
+int sca_context_checkpoint_bytes(sca_ctx *ctx, int64_t *bytes);
+int sca_save_context(sca_ctx *ctx, void *out, int64_t out_bytes);
+int sca_load_context(sca_ctx *ctx, const void *in, int64_t in_bytes);
+
 /* Closest approach per agent, measured WITH THE STEP.  With the feature on a step enqueues one more kernel beside the log's
  * (k_scene_clearance, a workgroup per scene, in front of the step's last kernel) that keeps, for every occupied agent row, how close the
  * agent came to another agent of its scene and to an obstacle of its scene, with whom and at which step -- the column a table of

@@ -64,6 +64,20 @@ class SceneCheckpointInfo(C.Structure):
                 ('live', C.c_int32), ('prev', C.c_int32), ('total_bytes', C.c_int64), ('checksum', C.c_uint64)]
 
 
+class ContextCheckpointShape(C.Structure):
+    """sca_context_checkpoint_shape: what a context checkpoint's layout depends on (sca_context_checkpoint_layout)"""
+    _fields_ = [('struct_bytes', C.c_int32), ('n', C.c_int32), ('trk_words', C.c_int32), ('list_form', C.c_int32), ('W', C.c_int32), ('M', C.c_int32),
+                ('R', C.c_int32), ('has_gate', C.c_int32), ('has_clearance', C.c_int32)]
+
+
+class ContextCheckpointInfo(C.Structure):
+    """struct sca_context_checkpoint_info: the header of a context checkpoint (sca_context_checkpoint_info)"""
+    _fields_ = [('struct_bytes', C.c_int32), ('reserved', C.c_int32), ('format', C.c_int32), ('lib_version', C.c_int32), ('n', C.c_int32),
+                ('trk_words', C.c_int32), ('record_bytes', C.c_int32), ('has_tracker', C.c_int32), ('list_form', C.c_int32), ('W', C.c_int32),
+                ('M', C.c_int32), ('R', C.c_int32), ('has_gate', C.c_int32), ('has_clearance', C.c_int32), ('clear_step', C.c_int32),
+                ('state_fresh', C.c_int32), ('updates', C.c_int64), ('total_bytes', C.c_int64), ('checksum', C.c_uint64)]
+
+
 class SceneClearance(C.Structure):
     """sca_scene_clearance: an agent row's closest approach so far (sca_get_scene_clearance), 32 bytes"""
     _fields_ = [('agent_clear', C.c_double), ('obs_clear', C.c_double), ('agent_partner', C.c_int32), ('agent_step', C.c_int32),
@@ -117,6 +131,7 @@ class MissionGateTotals(C.Structure):
 
 
 CHECKPOINT_SECTIONS = 14                                         # sca_scene_checkpoint_layout's offsets
+CONTEXT_CHECKPOINT_SECTIONS = 26                                 # sca_context_checkpoint_layout's offsets (SCA_CONTEXT_CHECKPOINT_SECTIONS)
 
 
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against include/sca_hip.h
@@ -165,6 +180,11 @@ SIGNATURES = {
     'sca_scene_checkpoint_bytes': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]),
     'sca_save_scenes': (C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     'sca_load_scenes': (C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    'sca_context_checkpoint_layout': (C.c_int, [C.POINTER(ContextCheckpointShape), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'sca_context_checkpoint_info': (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(ContextCheckpointInfo), C.c_int32]),
+    'sca_context_checkpoint_bytes': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    'sca_save_context': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    'sca_load_context': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     'sca_scene_clearance_enable': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_get_scene_clearance': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SceneClearance), C.c_int32]),
     'sca_clearance_enable': (C.c_int, [C.c_void_p, C.c_int]),

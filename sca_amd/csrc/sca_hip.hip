@@ -36,6 +36,8 @@
 #include "sca_mission_gate.hip.h"
 #include "sca_spawn.h"
 #include "sca_spawn.hip.h"
+#include "sca_checkpoint.h"
+#include "sca_checkpoint.hip.h"
 
 using namespace sca;
 
@@ -370,6 +372,9 @@ struct sca_ctx {
     int spn_cap = 0;
     SpawnPartial *spn_partials = nullptr;   // device [tiles][spn_cap]
     int64_t spn_partials_room = 0;          // ... how many it has room for
+    // context checkpoints (sca_save_context, sca_load_context; sca_checkpoint.h): nothing of it exists until the first call
+    uint8_t *cx_host = nullptr;             // the page-locked block both calls go through: the blob, the load's done_count stripes behind it
+    size_t cx_bytes = 0;                    // ... and its size: it grows when a call needs more
     // mission tables (sca_set_missions; sca_missions.h): nothing of it exists while no tables are set
     struct Missions {
         bool on = false;
@@ -1048,6 +1053,7 @@ void sca_destroy(sca_ctx *c) {
     if (c->spn_host) { (void)hipHostFree(c->spn_host); c->spn_host = nullptr; }
     if (c->spn_dev) { (void)hipFree(c->spn_dev); c->spn_dev = nullptr; }
     if (c->spn_partials) { (void)hipFree(c->spn_partials); c->spn_partials = nullptr; }
+    if (c->cx_host) { (void)hipHostFree(c->cx_host); c->cx_host = nullptr; c->cx_bytes = 0; }
     if (c->ap_dev) { (void)hipFree(c->ap_dev); (void)hipFree(c->ap_nd); c->ap_dev = nullptr; c->ap_nd = nullptr; }
     void *ptrs[] = {c->rec_own, c->rec_new_own, d.heading, d.goal, d.pref_speed, d.vpref_ext, d.total_dist, d.max_run_dist,
                     d.step_num, d.vpref_mode, d.policy, d.zaxis, d.obs, d.obs_sorted, d.awide, d.owide, d.atree, d.aperm, d.otree, d.operm, d.nbr_n,
@@ -4573,6 +4579,225 @@ int sca_get_mission_state(sca_ctx *c, int begin, int count, int32_t *cursor, int
         CHK(c, hipMemcpyAsync(ended, c->ms.words + (size_t)MSW_ENDED * n + begin, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, c->stream));
     }
     CHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- context checkpoints (include/sca_hip.h; the layout, the check, the calls' rules and the row move are sca_checkpoint.h's, the kernels
+// sca_checkpoint.hip.h's, enqueued here and nowhere else) -----------------------------------------------------------------------------------------
+static_assert(CTXCK_MS_WORDS == MSW_WORDS && CTXCK_MS_LIVE == MSW_LIVE && CTXCK_MS_FIRST_OK == MSW_FIRST_OK && CTXCK_MS_FIRST_FAIL == MSW_FIRST_FAIL &&
+              CTXCK_MS_CURSOR == MSW_CURSOR && CTXCK_MS_FLYING == MSW_FLYING && CTXCK_MS_ENDED == MSW_ENDED && CTXCK_MS_COLLECTED == MSW_COLLECTED, "the blob's mission words are the device's");
+static_assert(CTXCK_GATE_WORDS == MGW_WORDS && CTXCK_GATE_WAITING == MGW_WAITING && CTXCK_GATE_VERDICT == MGW_VERDICT && CTXCK_GATE_REFUSALS == MGW_REFUSALS, "the blob's gate words are the device's");
+static_assert(CTXCK_TOTAL_WORDS == MST_WORDS && CTXCK_TOTAL_WORDS == MGT_WORDS && MISSION_MAX_M == 127, "the blob's totals are the device's eight words; ctx_shape_ok's bound of M");
+static_assert(sizeof(sca_context_checkpoint_shape) == 4 + sizeof(CtxShape) && CX_SECTIONS == SCA_CONTEXT_CHECKPOINT_SECTIONS, "sca_context_checkpoint_shape is struct_bytes + CtxShape");
+// the context as a layout sees it
+static CtxShape ctx_ckpt_shape(const sca_ctx *c) {
+    CtxShape S{};
+    S.n = c->n; S.trk_words = c->trk_on ? (int)(sizeof(sca_dubins::AgentTrack) / 4) : 0;
+    S.list_form = !c->paths_on ? CTXCK_LISTS_NONE : c->path_W > 0 ? CTXCK_LISTS_SLOTS : CTXCK_LISTS_BLOCK;
+    S.W = c->paths_on ? c->path_W : 0;
+    S.M = c->ms.on ? c->ms.M : 0; S.R = c->ms.on ? c->ms.R : 0;
+    S.has_gate = c->ms.on && c->ms.gate.words ? 1 : 0;                    // (the words and totals outlive a gate that was switched off)
+    S.has_clearance = c->clear ? 1 : 0;
+    return S;
+}
+static CtxDev ctx_ckpt_dev(sca_ctx *c) {
+    CtxDev d{};
+    d.rec = c->d.rec; d.heading = c->d.heading; d.goal = c->d.goal; d.pref_speed = c->d.pref_speed; d.max_run_dist = c->d.max_run_dist; d.vpref_ext = c->d.vpref_ext;
+    d.total_dist = c->d.total_dist; d.step_num = c->d.step_num; d.status = c->d.status; d.aperm = c->d.aperm; d.zaxis = c->d.zaxis; d.vpref_mode = c->d.vpref_mode;
+    d.done_count = c->d.done_count;
+    if (c->trk_on) { d.trk_goal_heading = c->trk_goal_heading; d.trk_nbr0 = c->trk.nbr0; d.trk_st = (ctx_u32 *)c->trk.st; }
+    if (c->paths_on) { d.rem = c->path.rem; d.now_goal = c->path.now_goal; }
+    if (c->paths_on && c->path_W > 0) { d.len = c->pslot_len; d.rooms = c->pslot_pts; }
+    if (c->ms.on) { d.ms_words = c->ms.words; d.ms_results = c->ms.results; d.ms_totals = c->ms.totals; }
+    if (c->ms.on && c->ms.gate.words) { d.gate_words = c->ms.gate.words; d.gate_totals = c->ms.gate.totals; }
+    d.clear = c->clear;
+    return d;
+}
+static int ctx_ckpt_call_refuse(sca_ctx *c, const char *who, bool buffer) {
+    const CtxCallState s{c->agents_set, c->state_set, c->near_valid, c->scenes.on, c->comm != nullptr, c->part_on, c->n, c->d.shard_count};
+    const CtxCallFault f = ctx_checkpoint_call_check(s, buffer);
+    const std::string w(who);
+    switch (f) {
+    case CXC_OK: return 0;
+    case CXC_NO_AGENTS: c->err = w + ": sca_set_agents first"; break;
+    case CXC_NO_STATE: c->err = w + ": no state yet -- sca_set_state first"; break;
+    case CXC_MID_STEP: c->err = w + " between a policy pass and its env update: finish the step first"; break;
+    case CXC_SCENES: c->err = w + " with scenes set (sca_set_scenes): scenes have checkpoints of their own -- sca_save_scenes / sca_load_scenes"; break;
+    case CXC_SHARD: c->err = w + " on a shard with count < n (sca_set_shard): the blob is the whole swarm's, on one rank"; break;
+    case CXC_COMM: c->err = w + " with an active communicator: the blob is the whole swarm's, on one rank (sca_comm_destroy first)"; break;
+    case CXC_PARTITION: c->err = w + " under the cell-owner partition: the rows' state does not follow the owners (sca_partition_disable first)"; break;
+    default: c->err = w + ": the buffer is NULL";
+    }
+    return ctx_checkpoint_call_error_code(f);
+}
+static std::string ctx_ckpt_fault_text(const CtxCheck &k) {
+    const std::string at = std::to_string(k.entry);
+    switch (k.fault) {
+    case CXF_SHORT: return "the blob is NULL or shorter than a context checkpoint's header";
+    case CXF_MAGIC: return "the blob is not a context checkpoint (magic)";
+    case CXF_FORMAT: return "the blob has another format version than this library writes (" + std::to_string(CTXCK_FORMAT) + ")";
+    case CXF_RECORD: return "the blob's tracker record or public record size is not this library's";
+    case CXF_HEADER_RANGE: return "the blob's header holds n < 1, unknown bits, or words that contradict each other (list form / W, M / R, the gate without tables)";
+    case CXF_BYTES: return "the byte count is not the layout's for the blob's header (sca_context_checkpoint_layout)";
+    case CXF_CHECKSUM: return "the payload's checksum is not the header's";
+    case CXF_N: return "n: the blob's agent count is not the context's";
+    case CXF_POLICY: return "policy: row " + at + " has another policy in the blob than in the context (or none the library knows)";
+    case CXF_TRACKER: return "tracker: tracker records are present in the blob and the context has no device tracker, or absent and it has one (sca_device_tracker_enable)";
+    case CXF_LISTS: return "lists: the blob's waypoint lists are absent, in block form or in slot form, and the context's are not the same (sca_set_paths / sca_set_path_slots)";
+    case CXF_LIST_W: return "lists, W: the blob's room per row is not the context's (sca_set_path_slots)";
+    case CXF_TABLES: return "tables: the blob's mission tables are present or absent against the context's, or have another M or R (sca_set_missions)";
+    case CXF_GATE: return "gate: the mission gate's words are present in the blob and the context has never set a gate, or absent and it has (sca_set_mission_gate)";
+    case CXF_CLEARANCE: return "clearance: closest-approach records are present in the blob and off in the context, or absent and on (sca_clearance_enable)";
+    case CXF_PERM: return "the permutation is not one of 0 .. n - 1 (position " + at + ")";
+    case CXF_FLAGS: return "row " + at + " has unknown flag bits, or a v_pref mode or z-axis word other than 0 / 1";
+    case CXF_NOT_FINITE: return "row " + at + " has a position that is not finite";
+    case CXF_NOT_POSITIVE: return "row " + at + " has a radius, pref_speed or max_run_dist that is not positive and finite";
+    case CXF_COUNTERS: return "a step count is negative (row " + at + "; -1: the header's clear_step or updates)";
+    case CXF_LEN_RANGE: return "row " + at + " has a list length outside 0 .. W";
+    case CXF_REM_RANGE: return "row " + at + " has a cursor outside 0 .. the length of the row's list";
+    case CXF_MISSION_RANGE: return "row " + at + " has a successor, cursor, flying or waiting word outside -1 .. M - 1";
+    case CXF_COLLECTED: return "row " + at + " has more results collected than endings";
+    case CXF_VERDICT: return "row " + at + " has a verdict word above SCA_SPAWN_OVER_CAP or a negative refusal count";
+    case CXF_CLEAR_PARTNER: return "row " + at + " has a closest-approach partner outside its range or a negative step";
+    case CXF_TRACK_RANGE: return "row " + at + " has a tracker record with a cursor, count or word outside its range";
+    default: return "ok";
+    }
+}
+// the block for a blob of `bytes` and the load's stripes behind it
+static int64_t ctx_ckpt_stripes_at(int64_t bytes) { return ckpt_block_round(bytes); }
+static int ctx_ckpt_block(sca_ctx *c, int64_t bytes) {
+    const size_t want = (size_t)(ctx_ckpt_stripes_at(bytes) + (int64_t)sizeof(int32_t) * CTXCK_STRIPES);
+    if (c->cx_host && c->cx_bytes >= want) return 0;
+    CHK(c, hipStreamSynchronize(c->stream));                              // (every call ends with its synchronisation: no launch still uses the block)
+    uint8_t *blk = nullptr;
+    CHK(c, hipHostMalloc((void **)&blk, want, hipHostMallocMapped | hipHostMallocCoherent));
+    if (c->cx_host) (void)hipHostFree(c->cx_host);
+    c->cx_host = blk; c->cx_bytes = want;
+    return 0;
+}
+static CtxShape ctx_ckpt_public_shape(const sca_context_checkpoint_shape *s) {
+    return CtxShape{s->n, s->trk_words, s->list_form, s->W, s->M, s->R, s->has_gate, s->has_clearance};
+}
+int sca_context_checkpoint_layout(const sca_context_checkpoint_shape *shape, int64_t *offsets, int64_t *total_bytes) {
+    if (!shape || shape->struct_bytes != (int32_t)sizeof(sca_context_checkpoint_shape) || !offsets || !total_bytes) return SCA_ERR_ARG;
+    const CtxShape S = ctx_ckpt_public_shape(shape);
+    if (!ctx_shape_ok(S)) return SCA_ERR_ARG;
+    const CtxLayout L = ctx_checkpoint_layout(S);
+    for (int s = 0; s < CX_SECTIONS; s++) offsets[s] = L.off[s];
+    *total_bytes = L.total;
+    return 0;
+}
+int sca_context_checkpoint_info(const void *blob, int64_t bytes, struct sca_context_checkpoint_info *out, int32_t struct_bytes) {
+    if (!out || struct_bytes < (int32_t)offsetof(struct sca_context_checkpoint_info, format) || struct_bytes > (int32_t)sizeof(struct sca_context_checkpoint_info)) return SCA_ERR_ARG;
+    CtxHeader H;
+    const CtxCheck k = ctx_checkpoint_check(blob, bytes, ckpt_track_fields(), nullptr, &H);
+    if (k.fault != CXF_OK) return ctx_checkpoint_error_code(k.fault);
+    struct sca_context_checkpoint_info I{};
+    I.struct_bytes = struct_bytes; I.reserved = 0; I.format = H.format; I.lib_version = H.lib_version; I.n = H.n; I.trk_words = H.trk_words; I.record_bytes = H.rec_bytes;
+    I.has_tracker = (H.present & CTXCK_HAS_TRACKER) ? 1 : 0; I.list_form = H.list_form; I.W = H.W; I.M = H.M; I.R = H.R;
+    I.has_gate = (H.present & CTXCK_HAS_GATE) ? 1 : 0; I.has_clearance = (H.present & CTXCK_HAS_CLEARANCE) ? 1 : 0; I.clear_step = H.clear_step; I.state_fresh = H.state_fresh;
+    I.updates = H.updates; I.total_bytes = H.total_bytes; I.checksum = H.checksum;
+    std::memcpy(out, &I, (size_t)struct_bytes);
+    out->struct_bytes = struct_bytes;
+    return 0;
+}
+int sca_context_checkpoint_bytes(sca_ctx *c, int64_t *bytes) {
+    API_ENTER(c);
+    ARG(c, bytes);
+    if (int r = ctx_ckpt_call_refuse(c, "sca_context_checkpoint_bytes", true)) return r;    // (a size only where a save is possible)
+    *bytes = ctx_checkpoint_layout(ctx_ckpt_shape(c)).total;
+    return 0;
+}
+// One launch of k_ctx_save into the page-locked block, one synchronisation, then the host completes the blob -- the policies, the
+// permutation while the host still holds it, the header, the checksum -- and copies it out.
+int sca_save_context(sca_ctx *c, void *out, int64_t out_bytes) {
+    API_ENTER(c);
+    if (int r = ctx_ckpt_call_refuse(c, "sca_save_context", out != nullptr)) return r;
+    const CtxShape S = ctx_ckpt_shape(c);
+    const CtxLayout L = ctx_checkpoint_layout(S);
+    if (out_bytes < L.total) {
+        c->err = "sca_save_context: the buffer holds " + std::to_string(out_bytes) + " bytes, the context needs " + std::to_string(L.total) + " (sca_context_checkpoint_bytes)";
+        return SCA_ERR_ARG;
+    }
+    if (int r = ctx_ckpt_block(c, L.total)) return r;
+    uint8_t *b = c->cx_host;
+    for (int s = 0; s < CX_SECTIONS; s++) {                              // the bytes between the sections are part of the sum: at most 15 behind each,
+        const int64_t end = L.off[s] + L.len[s], next = s + 1 < CX_SECTIONS ? L.off[s + 1] : L.total;   // the sections themselves are written whole
+        if (next > end) std::memset(b + end, 0, (size_t)(next - end));
+    }
+    hipLaunchKernelGGL(k_ctx_save, dim3(ctx_checkpoint_blocks(L.total)), dim3(CTXCK_T), 0, c->stream, ctx_ckpt_dev(c), b, L, S);
+    CHK(c, hipGetLastError());
+    CHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(b + L.off[CX_POLICY], c->h_policy.data(), (size_t)S.n);
+    if (!c->perm_on_device) std::memcpy(b + L.off[CX_PERM], c->h_perm.data(), sizeof(int32_t) * (size_t)S.n);   // the live permutation is still the host's (no device build since it was set)
+    CtxHeader H{};
+    H.magic = CTXCK_MAGIC; H.format = CTXCK_FORMAT; H.lib_version = sca_version(); H.n = S.n; H.trk_words = S.trk_words; H.rec_bytes = CKPT_REC_BYTES;
+    H.present = ctx_shape_present(S); H.list_form = S.list_form; H.W = S.W; H.M = S.M; H.R = S.R; H.clear_step = c->clear ? c->clear_step : 0;
+    H.state_fresh = c->state_fresh ? 1 : 0; H.updates = c->ms.on ? (int64_t)c->ms.updates : 0; H.total_bytes = L.total;
+    H.checksum = scene_checkpoint_sum(b + sizeof H, L.total - (int64_t)sizeof H);
+    std::memcpy(b, &H, sizeof H);
+    std::memcpy(out, b, (size_t)L.total);
+    return 0;
+}
+// The blob is checked whole on the host (ctx_checkpoint_check) before any device work; then it goes into the page-locked block with K4's
+// counters for its flags behind it, ONE launch of k_ctx_load scatters it, and the call's one synchronisation follows.  Behind it the host
+// mirrors follow, as after sca_respawn_agents: the radius mirror, the envelopes (they only grow), the permutation, the lists' lengths, the
+// host state block where one exists.  state_replaced's effects apply, except that state_fresh takes the blob's value.
+int sca_load_context(sca_ctx *c, const void *in, int64_t in_bytes) {
+    API_ENTER(c);
+    if (int r = ctx_ckpt_call_refuse(c, "sca_load_context", in != nullptr)) return r;
+    CtxExpect X{};
+    X.shape = ctx_ckpt_shape(c); X.policy = c->h_policy.data(); X.n_obs = c->d.m;
+    std::vector<int32_t> block_len;
+    if (X.shape.list_form == CTXCK_LISTS_BLOCK) {
+        block_len.resize((size_t)c->n);
+        for (int i = 0; i < c->n; i++) block_len[(size_t)i] = c->h_path_off[i + 1] - c->h_path_off[i];
+        X.block_len = block_len.data();
+    }
+    CtxHeader H;
+    const CtxCheck k = ctx_checkpoint_check(in, in_bytes, ckpt_track_fields(), &X, &H);
+    if (k.fault != CXF_OK) { c->err = "sca_load_context: " + ctx_ckpt_fault_text(k); return ctx_checkpoint_error_code(k.fault); }
+    const CtxShape S = X.shape;
+    const CtxLayout L = ctx_checkpoint_layout(S);
+    if (int r = ctx_ckpt_block(c, L.total)) return r;
+    uint8_t *b = c->cx_host;
+    std::memcpy(b, in, (size_t)L.total);
+    int32_t *stripes = (int32_t *)(b + ctx_ckpt_stripes_at(L.total));
+    ctx_checkpoint_stripes(b, L, S.n, stripes);
+    hipLaunchKernelGGL(k_ctx_load, dim3(ctx_checkpoint_blocks(L.total)), dim3(CTXCK_T), 0, c->stream, ctx_ckpt_dev(c), (const uint8_t *)b, L, S, (const int32_t *)stripes);
+    CHK(c, hipGetLastError());
+    CHK(c, hipStreamSynchronize(c->stream));
+    const int n = S.n;
+    std::memcpy(c->h_perm.data(), b + L.off[CX_PERM], sizeof(int32_t) * (size_t)n);
+    c->perm_on_device = false;                                          // (as behind sca_set_kd_perm: the next build takes the host's)
+    const double *ps = (const double *)(b + L.off[CX_PREF_SPEED]);
+    const int32_t *len = S.list_form == CTXCK_LISTS_SLOTS ? (const int32_t *)(b + L.off[CX_LEN]) : nullptr;
+    if (len) { c->h_path_len.resize((size_t)n); c->h_path_vpref.resize((size_t)n); }
+    const HostLayout HL = host_state_layout(n);
+    for (int a = 0; a < n; a++) {
+        PubRec r;
+        std::memcpy(&r, b + L.off[CX_REC] + (size_t)CKPT_REC_BYTES * a, sizeof r);
+        c->h_rec[a].radius = r.radius;
+        c->max_radius = std::max(c->max_radius, r.radius);             // the envelopes only grow (conservative filters, as under respawns)
+        c->max_pref_speed = std::max(c->max_pref_speed, ps[a]);
+        if (len) { c->h_path_len[a] = len[a]; c->h_path_vpref[a] = len[a] > 0 && !restart_policy_tracked(c->h_policy[a]); }
+        if (c->hs_host) {                                              // the state block, if the caller has one: a later SCA_HOST_IN_STATE step must not bring the old rows back
+            uint8_t *h = c->hs_host;
+            const double pos[3] = {r.px, r.py, r.pz};
+            const float vel[3] = {r.vx, r.vy, r.vz};
+            std::memcpy((double *)(h + HL.off[HS_POS]) + 3 * (size_t)a, pos, sizeof pos);
+            std::memcpy((float *)(h + HL.off[HS_VEL]) + 3 * (size_t)a, vel, sizeof vel);
+            std::memcpy((double *)(h + HL.off[HS_HEADING]) + 3 * (size_t)a, b + L.off[CX_HEADING] + 24 * (size_t)a, 24);
+            (h + HL.off[HS_FLAGS])[a] = (uint8_t)r.flags;
+            std::memcpy((double *)(h + HL.off[HS_TOTAL_DIST]) + a, b + L.off[CX_TOTAL_DIST] + 8 * (size_t)a, 8);
+            std::memcpy((int32_t *)(h + HL.off[HS_STEP_NUM]) + a, b + L.off[CX_STEP_NUM] + 4 * (size_t)a, 4);
+        }
+    }
+    if (c->clear) c->clear_step = H.clear_step;
+    if (c->ms.on) c->ms.updates = (long long)H.updates;
+    c->h_pos_valid = false;
+    state_replaced(c);
+    c->state_fresh = H.state_fresh != 0;
     return 0;
 }
 

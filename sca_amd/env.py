@@ -467,7 +467,8 @@ class _FlatAgents:
             ng = np.full((n, 3), np.nan)
             served = self._state('step_num') > 0                   # agents that ran get_trajectory already hold now_goal = goal
             ng[served] = self.goal[served]
-        self._upload_paths([[list(map(float, w[:3])) for w in p] for p in lists])
+        self._lists_set = [[list(map(float, w[:3])) for w in p] for p in lists]     # as the device holds them (block form: what a checkpoint's definition keeps)
+        self._upload_paths(self._lists_set)
         self.solver.set_path_state(np.array([len(p) for p in lists], np.int32), ng)
         self._paths_on = True
         self._path_ng = ng
@@ -518,6 +519,7 @@ class MACAEnv(_FlatAgents):
         self._missions = None           # the tables of set_missions (None: none stand)
         self._mission_gate = False      # set_missions(spawn_margin=): the admission gate on the device
         self._mission_pending = {}      # ... id -> (entry, where the flight that named it ended): named, not known to be admitted yet
+        self._mission_args = None       # (results, spawn_margin, max_per_step) of set_missions: what a checkpoint keeps beside the tables
 
     def set_agents(self, agents, obstacles=None):
         if obstacles is None:
@@ -717,6 +719,7 @@ class MACAEnv(_FlatAgents):
         else:
             self.solver.set_missions(M, int(results), e, first_ok, first_fail)
         self._missions = dict(tables)
+        self._mission_args = (int(results), spawn_margin, max_per_step)
         self._mission_gate, self._mission_pending = spawn_margin is not None, {}
         if self._mission_gate:
             self.solver.set_mission_gate(spawn_margin, 0 if max_per_step is None else int(max_per_step))
@@ -763,6 +766,24 @@ class MACAEnv(_FlatAgents):
             self._stale = True
             self._path_stale = self._paths_on
         return res
+
+    # ---- context checkpoints: the running env out as one object, and back as a fresh env (sca_save_context / sca_load_context) ------------
+    def checkpoint(self):
+        """The env as it stands between two env.step() calls, as a checkpoint.ContextCheckpoint: the definition -- the agents with every
+        attribute, the obstacles, the env's options, the waypoint lists, the mission tables with their lists, results room and gate -- as
+        plain arrays, the library's blob of the context's whole mutable state (sca_save_context) and the steps so far.
+        MACAEnv.from_checkpoint() resumes it in this or another process; write(path) / read(path) keep it as one .npz without pickle.
+        Not kept: the trajectory log (a resumed env's log starts at its own row 0) and a host-side v_pref_fn's state (a RuntimeError)."""
+        from . import checkpoint as _ck
+        return _ck.env_checkpoint(self)
+
+    @classmethod
+    def from_checkpoint(cls, ckpt, device=0):
+        """A fresh MACAEnv that is bit for bit the env ckpt was taken from, from there on: the definition set up, the blob loaded.  Its
+        `agents` mirrors (start, goal, radius, pref_speed, path, flags, position ...) show the checkpoint's values at once; mission tables
+        stand as they stood, so lifelong.run_missions(env, None, steps) goes on with them."""
+        from . import checkpoint as _ck
+        return _ck.env_from_checkpoint(cls, ckpt, device)
 
     def run_steps(self, k):
         """k resident steps in one library call (sca_run_steps) and one synchronisation; with mission tables set the rows that end on

@@ -11,12 +11,18 @@ spawn_margin (metres): an admission gate in front of every respawn (MACAEnv.resp
 whose start is not free by that margin WAITS: its row stays finished where it is, and the mission is offered again in front of every
 later step, together with that step's new ones, waiting ones first, in ascending id.
 
-    stats = run_missions(env, tables, steps, burst=1, on_result=None, spawn_margin=None)
+    stats = run_missions(env, tables, steps, burst=1, on_result=None, spawn_margin=None, checkpoint_at=None)
 
 is the same traffic with the missions on the device (MACAEnv.set_missions, sca_set_missions): a row that ends takes its table's
 successor inside the step, so the env is stepped in bursts of `burst` resident steps with one synchronisation each, and only the results
 cross the link.  spawn_margin: the same admission gate on the device (MACAEnv.set_missions(spawn_margin=), sca_set_mission_gate), with
-run_lifelong's offer order: the traffic is the host loop's under the same rule."""
+run_lifelong's offer order: the traffic is the host loop's under the same rule.
+
+Interrupting such a run: run_missions(..., checkpoint_at=(step, path)) cuts the run at that step and writes the running env
+(MACAEnv.checkpoint: the definition as plain arrays beside the library's blob, sca_save_context) as one .npz; MACAEnv.from_checkpoint
+brings it back, in this or another process, and run_missions(env, None, the remaining steps) goes on with the standing tables and returns
+the stats of the run that was never cut.  run_lifelong's host loop is out of scope for checkpoints: its waiting and retired sets are
+Python objects of the caller's rule, which no blob can carry."""
 from . import solver as S
 
 
@@ -76,28 +82,45 @@ def run_lifelong(env, next_mission, steps, on_done=None, spawn_margin=None):
     return stats
 
 
-def run_missions(env, tables, steps, burst=1, on_result=None, spawn_margin=None):
+def run_missions(env, tables, steps, burst=1, on_result=None, spawn_margin=None, checkpoint_at=None):
     """tables: a dict from agent id to an env.MissionTable.  Steps the env in env.run_steps(burst) chunks and collects the results behind
     each chunk (on_result(agent, result) per result, a record of _lib.MISSION_RESULT_DTYPE).  Returns run_lifelong's stats keys from the
     device's totals: `respawned` the missions taken, `retired` the endings without a successor (such a row stays finished; the host may
     respawn it).  The run ends early, at a chunk's end, when nobody runs.  With spawn_margin the dict gains `deferred`, the refusals
-    counted per attempt (offered - admitted), and `waiting`, the missions still pending at the end, as run_lifelong's does."""
+    counted per attempt (offered - admitted), and `waiting`, the missions still pending at the end, as run_lifelong's does.
+    tables=None: the run goes on with the tables that stand (an env from MACAEnv.from_checkpoint, or one an earlier call left), which are
+    not set again: cursors, results and totals continue, and so do the stats -- the device's totals since the tables were set; whether
+    `deferred` / `waiting` are reported then follows the standing gate.
+    checkpoint_at=(step, path): the chunk is cut at that step of this call; behind it the results are collected, env.checkpoint() is
+    written to `path` and the stats so far are returned.  MACAEnv.from_checkpoint(ContextCheckpoint.read(path)) and run_missions(env,
+    None, the remaining steps) then return the stats of the run that was never cut."""
     n = len(env.agents)
     burst = max(1, int(burst))
-    env.set_missions(tables, results=max(4, burst), spawn_margin=spawn_margin)
+    if tables is None:
+        if env._missions is None:
+            raise RuntimeError('run_missions(tables=None): no mission tables stand -- pass the tables')
+    else:
+        env.set_missions(tables, results=max(4, burst), spawn_margin=spawn_margin)
+    gated = env._mission_gate
+    cut = None if checkpoint_at is None else int(checkpoint_at[0])
     done = 0
     while done < int(steps) and env._active > 0:
         k = min(burst, int(steps) - done)
+        if cut is not None and done < cut:
+            k = min(k, cut - done)
         env.run_steps(k)
         done += k
         res = env.mission_results()
         if on_result is not None:
             for r in res:
                 on_result(env.agents[int(r['id'])], r)
+        if cut is not None and done == cut:
+            env.checkpoint().write(checkpoint_at[1])
+            break
     t = env.solver.mission_totals()
     stats = dict(steps=t['updates'], arrived=t['arrived'], collided=t['collided'], timed_out=t['timed_out'], respawned=t['taken'], retired=t['stopped'],
                  agent_steps=t['agent_steps'], live_fraction=0.0)
-    if spawn_margin is not None:
+    if gated:
         g = env.solver.mission_gate_totals()
         stats.update(deferred=g['offered'] - g['admitted'], waiting=int((env.solver.mission_gate_state()[0] >= 0).sum()))
     stats['live_fraction'] = stats['agent_steps'] / float(n * stats['steps']) if stats['steps'] else 0.0

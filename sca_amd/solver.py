@@ -706,6 +706,30 @@ class BatchedSolver:
         sections (sca_scene_checkpoint_layout), and `policy`, the rows' policy bytes."""
         return scene_checkpoint_info(blob)
 
+    # ---- context checkpoints (sca_save_context / sca_load_context) -------------------------------------------------------------
+    def context_checkpoint_bytes(self):
+        """the size of the blob save_context writes for the context as it stands now"""
+        out = C.c_int64(0)
+        self._chk(self.L.sca_context_checkpoint_bytes(self.ctx, C.byref(out)), 'sca_context_checkpoint_bytes')
+        return int(out.value)
+
+    def save_context(self):
+        """The whole context's mutable state as one uint8 array (include/sca_hip.h: what a blob holds).  One launch, one synchronisation."""
+        blob = np.zeros(self.context_checkpoint_bytes(), np.uint8)
+        self._chk(self.L.sca_save_context(self.ctx, C.c_void_p(blob.ctypes.data), blob.size), 'sca_save_context')
+        return blob
+
+    def load_context(self, blob):
+        """blob (bytes or a uint8 array, from save_context of any context) into this context, which has been given the run's definition.
+        The blob is checked whole before the device sees it; ScaError (SCA_ERR_ARG) names what is wrong."""
+        b = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray)) else blob, np.uint8).reshape(-1)
+        self._chk(self.L.sca_load_context(self.ctx, C.c_void_p(b.ctypes.data), b.size), 'sca_load_context')
+
+    def context_checkpoint_info(self, blob):
+        """The header of a blob as a dict, after the whole check a load makes without a context; plus `offsets`, the byte offsets of its
+        sections (sca_context_checkpoint_layout), and `policy`, the rows' policy bytes."""
+        return context_checkpoint_info(blob)
+
     # ---- SCA's v_pref tracker on the device (scaPolicy.py:264-338) ---------------------------------------
     def device_tracker_enable(self, goal_heading, turning_radius=1.5, pitchlims=(-math.pi / 4, math.pi / 4), in_pass=True):
         """From now on the SCA / RVO3D+Dubins agents take v_pref from the device tracker: inside every policy pass
@@ -1001,6 +1025,31 @@ def scene_checkpoint_info(blob):
     out = {k: int(getattr(info, k)) for k, _ in info._fields_ if k not in ('struct_bytes', 'reserved')}
     out['offsets'], _ = scene_checkpoint_layout(out['size'], out['trk_words'], out['has_paths'])
     out['policy'] = b[out['offsets'][0]:out['offsets'][0] + out['size']].copy()
+    return out
+
+
+def context_checkpoint_layout(n, trk_words=0, list_form=0, W=0, M=0, R=0, has_gate=0, has_clearance=0):
+    """(offsets [26] int64, total bytes) of a context checkpoint (sca_context_checkpoint_layout); pure, no device"""
+    shape = _lib.ContextCheckpointShape(C.sizeof(_lib.ContextCheckpointShape), int(n), int(trk_words), int(list_form), int(W), int(M), int(R),
+                                        int(has_gate), int(has_clearance))
+    off = np.zeros(_lib.CONTEXT_CHECKPOINT_SECTIONS, np.int64)
+    total = C.c_int64(0)
+    rc = _lib.lib().sca_context_checkpoint_layout(C.byref(shape), _lib.ptr(off, C.c_int64), C.byref(total))
+    if rc != 0:
+        raise ScaError('sca_context_checkpoint_layout: bad argument (rc=%d)' % rc)
+    return off, int(total.value)
+
+
+def context_checkpoint_info(blob):
+    """see BatchedSolver.context_checkpoint_info; pure, no device"""
+    b = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray)) else blob, np.uint8).reshape(-1)
+    info = _lib.ContextCheckpointInfo()
+    rc = _lib.lib().sca_context_checkpoint_info(C.c_void_p(b.ctypes.data), b.size, C.byref(info), C.sizeof(info))
+    if rc != 0:
+        raise ScaError('sca_context_checkpoint_info: not a valid context checkpoint (rc=%d)' % rc)
+    out = {k: int(getattr(info, k)) for k, _ in info._fields_ if k not in ('struct_bytes', 'reserved')}
+    out['offsets'], _ = context_checkpoint_layout(out['n'], out['trk_words'], out['list_form'], out['W'], out['M'], out['R'], out['has_gate'], out['has_clearance'])
+    out['policy'] = b[out['offsets'][0]:out['offsets'][0] + out['n']].copy()
     return out
 
 
