@@ -7,6 +7,7 @@ log files -- only the imports differ (sca_amd.env instead of mamp.*).
     python examples/run_sca.py --scenario exp3 --map tests/golden/exp3_map.binvox   # low-altitude search among 1491 spheres
     python examples/run_sca.py --scenario circle --agents 2000 --no-obstacles --policy orca
     python examples/run_sca.py --clearance --margin 0.2   # ... and how close the drones came (sca_clearance_enable)
+    python examples/run_sca.py --lifelong 2000 --traffic 0.05 --spawn-margin 0.5   # drones leave when they arrive, new ones enter where there is room
 """
 import argparse
 import math
@@ -88,6 +89,28 @@ def lifelong(args, agents, obstacles, pol, dubins):
                                  checkpoint_at=(args.save_at, args.save_file) if args.save_at else None)
             if args.save_at:
                 print('saved behind step', args.save_at, 'as', args.save_file)
+    elif args.traffic is not None:
+        # a changing population: an arrived drone leaves the airspace (its row becomes vacant, MACAEnv.retire), and seeded arrivals -- a
+        # Poisson number per step -- enter at vacant rows with those rows' original missions; with --spawn-margin only where the start is free
+        from sca_amd.lifelong import RETIRE
+        trng = np.random.default_rng(2024)
+
+        def leave_or_restart(agent, row):
+            f = int(row['flags'])
+            return RETIRE if f & S.FLAG_AT_GOAL and not f & S.FLAG_COLLISION else next_mission(agent, row)
+
+        def arrivals(step, vacant_ids):
+            k = min(len(vacant_ids), int(trng.poisson(args.traffic)))
+            out = []
+            for i in sorted(int(x) for x in trng.permutation(vacant_ids)[:k]):
+                start, goal = first[i]
+                old = env.agents[i]
+                new = E.Agent(start_pos=start, goal_pos=goal, vel=[0.0, 0.0, 0.0], radius=old.radius, pref_speed=old.pref_speed, policy=pol, id=i)
+                if K:
+                    new.path = [w[:] for w in out_list[i]]
+                out.append(new)
+            return out
+        stats = run_lifelong(env, leave_or_restart, args.lifelong, spawn_margin=args.spawn_margin, arrivals=arrivals)
     else:
         stats = run_lifelong(env, next_mission, args.lifelong) if args.spawn_margin is None else \
             run_lifelong(env, next_mission, args.lifelong, spawn_margin=args.spawn_margin)
@@ -97,6 +120,9 @@ def lifelong(args, agents, obstacles, pol, dubins):
     print({k: stats[k] for k in ('arrived', 'collided', 'timed_out', 'respawned', 'retired', 'agent_steps')}, f"live fraction {stats['live_fraction']:.3f}")
     if args.spawn_margin is not None:
         print('spawn margin', args.spawn_margin, 'm:', stats['deferred'], 'refusals,', stats['waiting'], 'missions still waiting')
+    if args.traffic is not None:
+        print('traffic', args.traffic, 'arrivals/step:', stats['retired_rows'], 'drones left,', stats['admitted'], 'entered, population',
+              stats['population_min'], '..', stats['population_max'], f"(mean {stats['population_mean']:.1f})")
 
 
 def main():
@@ -121,6 +147,9 @@ def main():
                     help='with --lifelong: a drone is respawned only where its start is free by M metres (of every other drone, of every '
                          'obstacle and of the drones admitted with it); otherwise its mission waits and is offered again after every step '
                          '(with --device-missions the gate runs on the device too: MACAEnv.set_missions(spawn_margin=))')
+    ap.add_argument('--traffic', type=float, default=None, metavar='RATE',
+                    help='with --lifelong: a changing population -- a drone that arrives leaves the airspace (MACAEnv.retire), and a seeded '
+                         'Poisson number of new drones, RATE per step on average, enters at vacant rows (with --spawn-margin only where free)')
     ap.add_argument('--device-missions', action='store_true',
                     help='with --lifelong: the ping-pong rule as a mission table per drone on the device -- a drone that ends takes its next '
                          'mission inside the step, no host call per step (MACAEnv.set_missions)')
@@ -138,6 +167,8 @@ def main():
         ap.error('--save-at / --resume go with --lifelong STEPS --device-missions')
     if args.device_missions and args.lifelong <= 0:
         ap.error('--device-missions goes with --lifelong STEPS')
+    if args.traffic is not None and (args.lifelong <= 0 or args.device_missions or args.traffic < 0):
+        ap.error('--traffic RATE (RATE >= 0) goes with --lifelong STEPS, without --device-missions')
     if args.waypoints < 0 or (args.waypoints and args.lifelong <= 0):
         ap.error('--waypoints K (K >= 0) goes with --lifelong STEPS')
 

@@ -67,7 +67,8 @@ enum sca_policy {                 /* which find_next_action the agent runs */
     SCA_POLICY_RVO3D_DUBINS = 5   /* mamp/policies/sca/rvo3dDubinsPolicy.py (RVO3D selection, v_pref supplied) */
 };
 
-enum sca_flag { SCA_FLAG_AT_GOAL = 1, SCA_FLAG_COLLISION = 2, SCA_FLAG_TIMEOUT = 4 };   /* agent.py:70-72 */
+enum sca_flag { SCA_FLAG_AT_GOAL = 1, SCA_FLAG_COLLISION = 2, SCA_FLAG_TIMEOUT = 4,     /* agent.py:70-72 */
+                SCA_FLAG_VACANT = 8 };   /* the library's own: a vacant row (sca_retire_agents) shows at-goal | collision | vacant = 11 */
 
 enum sca_neighbor_mode {
     SCA_NBR_KDTREE = 0,           /* replica of the reference kd-tree (built and queried on the device): exact lists */
@@ -772,6 +773,50 @@ int sca_respawn_agents(sca_ctx *ctx, int count, const int32_t *ids /*count*/, co
                        const double *path_points /*nullable*/);
 int sca_get_finished(sca_ctx *ctx, sca_finished_row *rows /*capacity*/, int capacity, int *count, int32_t struct_bytes);
 
+/* Vacant rows in a plain context: drones leave the airspace and re-enter.  A plain context otherwise always holds exactly n bodies: a drone
+ * that arrived, collided or timed out stays where it is, and the reference's rule keeps colliding with it.  The reference indexes
+ * agents[agentIDs[i]] by id and has no removal in place; the library defines vacancy as the plain list edit on kdTree.agentIDs: retiring id
+ * a is agentIDs.remove(a), admitting it agentIDs.append(a), nothing else of the order moves.
+ *   contract   at any moment the occupied rows are, bit for bit, a context that holds only those agents, renumbered in ascending id, behind
+ *              sca_set_agents (+ attributes, obstacles, lists), sca_set_state and sca_set_kd_perm(the occupied prefix of the permutation,
+ *              mapped through the same renumbering) -- from there on, step for step: state, action rows, neighbour lists entry for entry,
+ *              diag, status, the permutation's prefix, sca_active_count, sca_get_finished.  No occupied row that was not named in a call can
+ *              tell that the call happened, except that the retired drone is nobody's neighbour, collision, clearance or probe partner.
+ *   a vacant row   flags at-goal | collision | SCA_FLAG_VACANT (sca_get_state shows 11), zero velocity, heading, total_dist and step_num, a
+ *              zero action row, status 0, an invalid neighbour list, diag -1; in slot form an empty list (len = rem = 0, now_goal None); its
+ *              closest-approach record emptied.  It KEEPS its position, radius, goal, pref_speed, max_run_dist, policy, zaxis, v_pref mode and
+ *              fed v_pref, solver and planner attributes, its tracker record (unowned: the tracker wants flags 0), its mission table and
+ *              cursor.  It stands in no tree, hence in no neighbour list, near list, collision walk or clearance descent; sca_active_count
+ *              does not count it, sca_get_finished does not list it, mission tables never take it (it never "ends"), sca_probe_clearance,
+ *              both gated respawns' world tests and the mission gate's probe pass over it.  The trajectory log writes its row as it stands.
+ *   the permutation   positions [0, m) hold the occupied ids in carried order, [m, n) the vacant ids ascending; sca_get_kd_perm returns it
+ *              whole.  A retire deletes the named ids from the prefix (stable); a respawn appends the vacant ids it admits in the call's
+ *              order (a gated call only the admitted ones).
+ *   sca_retire_agents   any occupied rows, live or finished; one synchronisation however many are named.  K4's striped counters are adjusted
+ *              for the rows that were live.  Mission tables: a retired row in flight writes no result and moves no total, a row waiting at
+ *              the gate loses its pending mission (`dropped` + 1).
+ *   sca_respawn_agents / sca_respawn_agents_gated   naming a vacant row admits it: the row becomes word for word what the respawn leaves for
+ *              the call's values.  In the gated call a vacant named row is no body for the others, and a refused vacant row stays vacant
+ *              with every word it had.  A call may mix occupied and vacant rows.
+ *   sca_get_vacant      the vacant ids, ascending (sca_get_finished's ordered compaction; one synchronisation; none while no row is vacant).
+ *              *count is their number even where it exceeds `capacity`; the first `capacity` are written.
+ *   sca_get_population  the occupied rows, m (host arithmetic).
+ *   refusals   decided on the host before any device work; a refused call changes nothing.  SCA_ERR_STATE: no agents, no state yet, (retire)
+ *              between a policy pass and its env update.  SCA_ERR_ARG: count <= 0, ids NULL, an id outside 0 .. n-1, a repeated id, an id
+ *              that is vacant already, a call that would leave no occupied row (m >= 1 always); for sca_get_vacant capacity < 0, a NULL
+ *              count, NULL ids with a capacity.  SCA_ERR_UNSUPPORTED: what sca_respawn_agents refuses (scenes, a shard with count < n, a
+ *              communicator, the partition, lists in block form).
+ *   while a row is vacant   SCA_ERR_UNSUPPORTED, the message names the reason: a pass in SCA_NBR_GRID, sca_step_host, sca_set_state,
+ *              sca_set_kd_perm, sca_get_kd_tree, sca_save_context / sca_load_context / sca_context_checkpoint_bytes, sca_set_shard with
+ *              count < n, sca_comm_init, sca_partition_init, sca_set_scenes, and the lists for the whole id range: sca_set_paths,
+ *              sca_set_path_slots, sca_set_path_state (a vacant row's list is empty and its now_goal None; clearing the lists with
+ *              sca_set_paths(0, NULL) stays legal).  SCA_NBR_AUTO resolves to the kd pass, as with scenes, and a
+ *              pass reports SCA_FORM_VACANCY.  Everything works again once every row is occupied.  sca_set_agents drops all vacancy.
+ * A context that never retires allocates nothing of this and enqueues the kernels it did.  Detect the feature by the symbol. */
+int sca_retire_agents(sca_ctx *ctx, int count, const int32_t *ids /*count*/);
+int sca_get_vacant(sca_ctx *ctx, int32_t *ids /*capacity*/, int capacity, int *count);
+int sca_get_population(sca_ctx *ctx, int *occupied);
+
 /* Spawn admission: how free is this point NOW, and respawning only the rows whose start is free.  sca_respawn_agents puts a drone wherever
  * it is told to, also inside another one; the closest-approach records (sca_clearance_enable) cover the agents' own positions inside a
  * step, from a tree that is one step old.  A spawn test needs arbitrary points, between two steps, against the records as they are now --
@@ -1143,7 +1188,8 @@ int sca_last_exchange_ms(sca_ctx *ctx, float *exchange_ms);
  *                          build publishes): no k_neighbors_kd_auto launch, no stream wait in front of the solve
  *   SCA_FORM_WAYPOINTS     k_waypoint ran at the head of the pass (waypoint lists are set: sca_set_paths)
  *   SCA_FORM_SCENES        scenes are set (sca_set_scenes): the forest build and the scene forms of the neighbour query ran
- *   SCA_FORM_SCENE_OBSTACLES  ... with one obstacle set per scene (sca_set_scene_obstacles): the obstacle walks started at each scene's own root */
+ *   SCA_FORM_SCENE_OBSTACLES  ... with one obstacle set per scene (sca_set_scene_obstacles): the obstacle walks started at each scene's own root
+ *   SCA_FORM_VACANCY       a row is vacant (sca_retire_agents): the kd build took the occupied rows for its size, and SCA_NBR_AUTO was the plain kd pass */
 #define SCA_FORM_SOLVE_SPLIT 1
 #define SCA_FORM_TRACK_FUSED 2
 #define SCA_FORM_REPLAN_LANE 4
@@ -1155,6 +1201,7 @@ int sca_last_exchange_ms(sca_ctx *ctx, float *exchange_ms);
 #define SCA_FORM_WAYPOINTS 256
 #define SCA_FORM_SCENES 512
 #define SCA_FORM_SCENE_OBSTACLES 1024
+#define SCA_FORM_VACANCY 2048
 int sca_last_pass_forms(sca_ctx *ctx, int *forms);
 /* SCA_NBR_AUTO statistics since the last reset: out4 = {AUTO passes, agents the grid query listed for the kd query (sum over the passes), the
  * largest list, passes in which somebody was listed}.  A pass with nobody listed never waits for the kd stream. */

@@ -191,6 +191,9 @@ SIGNATURES = {
     'sca_get_clearance': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(SceneClearance), C.c_int32]),
     'sca_respawn_agents': (C.c_int, [C.c_void_p, C.c_int, ip, dp, fp, dp, dp, dp, dp, bp, dp, dp, ip, dp]),
     'sca_get_finished': (C.c_int, [C.c_void_p, C.POINTER(FinishedRow), C.c_int, C.POINTER(C.c_int), C.c_int32]),
+    'sca_retire_agents': (C.c_int, [C.c_void_p, C.c_int, ip]),
+    'sca_get_vacant': (C.c_int, [C.c_void_p, ip, C.c_int, C.POINTER(C.c_int)]),
+    'sca_get_population': (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     'sca_probe_clearance': (C.c_int, [C.c_void_p, C.c_int, dp, dp, ip, C.POINTER(SceneClearance), C.c_int32]),
     'sca_respawn_agents_gated': (C.c_int, [C.c_void_p, C.c_int, ip, dp, fp, dp, dp, dp, dp, bp, dp, dp, ip, dp, C.c_double, ip, C.POINTER(SceneClearance), ip]),
     'sca_set_missions': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Mission), ip, ip]),

@@ -51,7 +51,8 @@ constexpr double PI = 3.141592653589793;
 constexpr double TWO_PI = 6.283185307179586;   // 2 * pi as Python evaluates it
 
 enum Policy : int { POL_SCA = 0, POL_RVO = 1, POL_SRVO = 2, POL_ORCA = 3, POL_ORCA_LP = 4, POL_RVO_DUBINS = 5 };
-enum Flags : uint32_t { FLAG_AT_GOAL = 1, FLAG_COLLISION = 2, FLAG_TIMEOUT = 4 };
+enum Flags : uint32_t { FLAG_AT_GOAL = 1, FLAG_COLLISION = 2, FLAG_TIMEOUT = 4,
+                        FLAG_VACANT = 8 };   // a vacant row of a plain context (sca_vacancy.h): always with FLAG_AT_GOAL | FLAG_COLLISION
 enum Status : int32_t {
     ST_SQRT_DOMAIN = 2,        // reference would raise ValueError in math.sqrt (scaPolicy.py:159)
     ST_BAD_PREF_SPEED = 4,     // np.arange(0.5, ps+0.03, ps-0.5) not of length 2 (scaPolicy.py:195)

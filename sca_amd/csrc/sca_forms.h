@@ -100,8 +100,12 @@ inline bool auto_lists_too_many(int kdq_last, int auto_div, int shard_count) { r
 // auto_pass (false: a plain SCA_NBR_KDTREE pass) | the context's Auto::backoff and Auto::last after this decision | workgroups of
 // k_neighbors_kd_auto, should the listed agents' kd query be a launch
 struct AutoPlan { bool auto_pass; int auto_backoff, kdq_last, kdq_blocks; };
-inline AutoPlan plan_auto(bool fits, bool tracked_pass, bool kd_ahead, int kdq_last, int auto_div, int auto_backoff, int shard_count) {
+// vacancy_on: a row of the plain context is vacant (sca_vacancy.h) -- the grid build does not skip vacant rows, so the pass is the plain kd
+// pass, as with scenes; nothing of the back-off is touched, and AUTO passes come back with the last admission (no tree is ever built ahead
+// across a call, so kd_ahead is false there)
+inline AutoPlan plan_auto(bool fits, bool tracked_pass, bool kd_ahead, int kdq_last, int auto_div, int auto_backoff, int shard_count, bool vacancy_on = false) {
     AutoPlan p{true, auto_backoff, kdq_last, KDQ_BLOCKS};
+    if (vacancy_on) { p.auto_pass = false; return p; }
     if (!kd_ahead && auto_backoff == 0 && auto_lists_too_many(kdq_last, auto_div, shard_count)) { p.auto_backoff = AUTO_BACKOFF_PASSES; p.kdq_last = -1; }
     if (!kd_ahead && (!fits || tracked_pass || p.auto_backoff > 0)) {
         if (p.auto_backoff > 0) p.auto_backoff--;
@@ -111,8 +115,8 @@ inline AutoPlan plan_auto(bool fits, bool tracked_pass, bool kd_ahead, int kdq_l
     return p;
 }
 // will the next pass of an SCA_NBR_AUTO run be an AUTO pass (and not a plain kd pass)?  Decides whether its tree may be built ahead.
-inline bool auto_next(bool fits, bool tracked_pass, bool part_on, int kdq_last, int auto_div, int auto_backoff, int shard_count) {
-    return fits && auto_backoff == 0 && !part_on && !tracked_pass && !auto_lists_too_many(kdq_last, auto_div, shard_count);
+inline bool auto_next(bool fits, bool tracked_pass, bool part_on, int kdq_last, int auto_div, int auto_backoff, int shard_count, bool vacancy_on = false) {
+    return !vacancy_on && fits && auto_backoff == 0 && !part_on && !tracked_pass && !auto_lists_too_many(kdq_last, auto_div, shard_count);
 }
 // the launch-free form of the listed agents' kd query (the grid query's own last workgroup answers them, KdTail) for the build of pass `seq`:
 // while the list lengths that have come back say "nobody" (auto_tail_max), and only with the wait-value form of the pass's wait
@@ -194,6 +198,7 @@ struct StepIn {
     bool auto_ran;              // the pass of this step was an AUTO pass
     bool fits, part_on; int kdq_last, auto_div, auto_backoff, shard_count;   // auto_next's inputs (tracked_pass is trk_on && trk_in_pass)
     bool missions_on = false;   // mission tables are set (sca_set_missions): the step's last kernel may still replace rows
+    bool vacancy_on = false;    // a row is vacant (sca_retire_agents): every pass is the plain kd pass, nothing of SCA_NBR_AUTO rides or starts early
 };
 struct StepPlan {
     bool moved_on_action;       // k_action carries Auto::ev_moved.  None of its inputs is a result of the step's pass: asked in front of it
@@ -205,13 +210,13 @@ inline StepPlan plan_step(const StepIn &i) {
     const bool more = i.step + 1 < i.steps;
     // (SCA_NBR_AUTO, another step to follow: the moved positions' event rides on k_action -- the next pass's kd build waits on it)
     // (a shard: the records of the others arrive after k_action)
-    p.moved_on_action = i.mode == SCA_NBR_AUTO && more && i.kd_stream && i.ext_stop && !i.comm && i.whole;
+    p.moved_on_action = i.mode == SCA_NBR_AUTO && !i.vacancy_on && more && i.kd_stream && i.ext_stop && !i.comm && i.whole;
     // SCA_NBR_AUTO: the NEXT pass's kd build needs the moved positions only -- k_collide_finish changes flags, and in an AUTO pass its
     // fallback looks into the grid, not into the tree -- so it starts beside the collision check and the next pass's grid build and query.
     // Only inside one call: a caller who reads the permutation between calls sees as many builds as steps.
     // (not with the closest-approach records on: k_clearance reads this step's tree, which a build enqueued ahead would overwrite beside it)
     p.build_ahead = i.mode == SCA_NBR_AUTO && i.auto_ran && more && !i.clear_on &&
-                    auto_next(i.fits, i.trk_on && i.trk_in_pass, i.part_on, i.kdq_last, i.auto_div, i.auto_backoff, i.shard_count);
+                    auto_next(i.fits, i.trk_on && i.trk_in_pass, i.part_on, i.kdq_last, i.auto_div, i.auto_backoff, i.shard_count, i.vacancy_on);
     // the next pass's fork (tracker in the pass, its neighbour branch on the side stream) rides on this step's last kernel
     // (not while waypoint lists are set: the next pass's k_waypoint must come before its fork)
     // (a step that builds ahead took the other branch: no tracker in an AUTO pass, no fork to carry)

@@ -31,6 +31,8 @@
 #include "sca_clearance.hip.h"
 #include "sca_respawn.h"
 #include "sca_respawn.hip.h"
+#include "sca_vacancy.h"
+#include "sca_vacancy.hip.h"
 #include "sca_missions.h"
 #include "sca_missions.hip.h"
 #include "sca_mission_gate.hip.h"
@@ -366,6 +368,14 @@ struct sca_ctx {
     uint8_t *fin_host = nullptr;            // sca_get_finished's page-locked block: the count's head, fin_cap rows behind it
     int fin_cap = 0;
     int32_t *fin_counts = nullptr;          // device [2 * tiles of max_n]: the tiles' counts, their offsets behind them
+    // vacant rows (sca_retire_agents, sca_get_vacant; sca_vacancy.h): nothing of it exists until the first retire
+    struct Vacancy {
+        bool on = false;                    // a row is vacant: m < n
+        int m = 0;                          // the occupied rows while on (else the context's n)
+        std::vector<uint8_t> h;             // [n] 1 where the row is vacant (empty until the first retire)
+        int32_t *dev = nullptr;             // device: [max_n] the named ids of a retire, [max_n] the edited prefix, the tiles' counts and offsets, one head word
+        uint8_t *host = nullptr;            // sca_get_vacant's page-locked block: the count's head, max_n ids behind it
+    } vac;
     // spawn admission (sca_probe_clearance, sca_respawn_agents_gated; sca_spawn.h): nothing of it exists until the first call
     uint8_t *spn_host = nullptr;            // the page-locked block (SpawnLayout of spn_cap queries)
     uint8_t *spn_dev = nullptr;             // device: the copy of the block's query sections, the world words and the verdict words behind it
@@ -476,6 +486,7 @@ static int missions_standing(sca_ctx *c, const char *who, MissionFault f);
 static int mission_refuse(sca_ctx *c, const char *who, MissionFault f, int64_t entry);
 static int missions_refresh_live(sca_ctx *c);
 static int missions_host_flight(sca_ctx *c, const int32_t *ids, const int32_t *verdict, int count);
+static int missions_retired(sca_ctx *c, const int32_t *ids, int count);
 static int missions_gate_new_state(sca_ctx *c);
 static int missions_gate_partials(sca_ctx *c, int m);
 static int missions_path_mirrors(sca_ctx *c);
@@ -1050,6 +1061,8 @@ void sca_destroy(sca_ctx *c) {
     if (c->rsp_host) { (void)hipHostFree(c->rsp_host); c->rsp_host = nullptr; }
     if (c->fin_host) { (void)hipHostFree(c->fin_host); c->fin_host = nullptr; }
     if (c->fin_counts) { (void)hipFree(c->fin_counts); c->fin_counts = nullptr; }
+    if (c->vac.dev) { (void)hipFree(c->vac.dev); c->vac.dev = nullptr; }
+    if (c->vac.host) { (void)hipHostFree(c->vac.host); c->vac.host = nullptr; }
     if (c->spn_host) { (void)hipHostFree(c->spn_host); c->spn_host = nullptr; }
     if (c->spn_dev) { (void)hipFree(c->spn_dev); c->spn_dev = nullptr; }
     if (c->spn_partials) { (void)hipFree(c->spn_partials); c->spn_partials = nullptr; }
@@ -1192,6 +1205,13 @@ int sca_set_agent_params(sca_ctx *c, int n, const double *neighbor_dist, const i
 
 static int scenes_clear(sca_ctx *c);
 static void scene_harvest_clear_fresh(sca_ctx *c, int count, const int32_t *scene_ids);
+// what works on whole id ranges, while a row of the plain context is vacant (sca_retire_agents): it works again once every row is occupied
+static int vacancy_refuse(sca_ctx *c, const char *who) {
+    if (!c->vac.on) return 0;
+    c->err = std::string(who) + ": " + std::to_string(c->n - c->vac.m) + " of the context's rows are vacant (sca_retire_agents) -- the call works on the whole id range, "
+             "which cannot say which rows are; admit every vacant row first (a respawn that names it)";
+    return SCA_ERR_UNSUPPORTED;
+}
 // a whole-context state from outside while a scene is below its capacity (sca_restart_scenes_sized): the vacant rows are the library's
 static int scenes_refuse_partial(sca_ctx *c, const char *who) {
     if (!c->scenes.on || !c->scenes.partial) return 0;
@@ -1217,6 +1237,7 @@ int sca_set_agents(sca_ctx *c, int n, const double *radius, const double *pref_s
     if (int r = scenes_clear(c)) return r;                            // ... and so do the scenes
     if (int r = clearance_drop(c)) return r;                          // ... and so do the closest-approach records
     if (int r = missions_drop(c)) return r;                           // ... and so do the mission tables
+    c->vac.on = false; c->vac.m = 0; c->vac.h.clear();                // ... and so does every vacancy: the new set occupies all its rows
     if (c->comm && n % c->comm_nranks) { c->err = "agent count must be a multiple of the communicator's rank count"; return SCA_ERR_ARG; }
     c->n = n; c->d.n = n; c->d.shard_begin = 0; c->d.shard_count = n;
     if (c->comm) { c->d.shard_count = n / c->comm_nranks; c->d.shard_begin = c->comm_rank * c->d.shard_count; }
@@ -1258,6 +1279,7 @@ int sca_set_state(sca_ctx *c, const double *pos, const float *vel, const double 
     if (!c->agents_set) { c->err = "sca_set_agents first"; return SCA_ERR_STATE; }
     ARG(c, pos && vel && heading && flags);
     if (int r = scenes_refuse_partial(c, "sca_set_state")) return r;
+    if (int r = vacancy_refuse(c, "sca_set_state")) return r;
     const int n = c->n;
     for (int i = 0; i < n; i++) {
         PubRec &r = c->h_rec[i];
@@ -1309,6 +1331,7 @@ int sca_set_kd_perm(sca_ctx *c, const int32_t *perm) {
     API_ENTER(c);
     ARG(c, perm && c->agents_set);
     if (int r = scenes_refuse_partial(c, "sca_set_kd_perm")) return r;
+    if (int r = vacancy_refuse(c, "sca_set_kd_perm")) return r;
     if (c->scenes.on) {
         const int at = scenes_perm_fault(c->scenes.v.nscenes, c->scenes.h_off.data(), perm);
         if (at >= 0) {
@@ -1335,6 +1358,7 @@ int sca_get_kd_tree(sca_ctx *c, double *tree_out) {
     API_ENTER(c);
     ARG(c, tree_out && c->agents_set);
     if (c->scenes.on) { c->err = "sca_get_kd_tree with scenes set (sca_set_scenes): the context holds a forest, one tree per scene"; return SCA_ERR_UNSUPPORTED; }
+    if (int r = vacancy_refuse(c, "sca_get_kd_tree")) return r;
     const int n = c->n;
     std::vector<KdNode> t((size_t)2 * n, KdNode{});
     if (!c->perm_on_device) {
@@ -1418,6 +1442,8 @@ int sca_set_paths(sca_ctx *c, int n, const int32_t *offsets, const double *point
     if (!c->agents_set) { c->err = "sca_set_agents first"; return SCA_ERR_STATE; }
     if ((n == 0 || !offsets) && c->ms.on && c->ms.lists) return mission_refuse(c, "sca_set_paths", MSF_PATH_CLEAR, -1);
     if (n == 0 || !offsets) return paths_clear(c, true);
+    // (lists for the whole id range would give a vacant row a list; in block form no vacant row could be admitted again.  Clearing stays legal)
+    if (int r = vacancy_refuse(c, "sca_set_paths")) return r;
     if (int r = missions_standing(c, "sca_set_paths", MSF_PATHS)) return r;
     if (c->part_on) { c->err = "sca_set_paths under the cell-owner partition: path state does not migrate with the agents"; return SCA_ERR_UNSUPPORTED; }
     if (n != c->n) { c->err = "sca_set_paths: n = " + std::to_string(n) + " is not the agent count " + std::to_string(c->n); return SCA_ERR_ARG; }
@@ -1461,6 +1487,7 @@ int sca_set_paths(sca_ctx *c, int n, const int32_t *offsets, const double *point
 int sca_set_path_slots(sca_ctx *c, int points_per_agent, int n, const int32_t *offsets, const double *points) {
     API_ENTER(c);
     const int W = points_per_agent;
+    if (int r = vacancy_refuse(c, "sca_set_path_slots")) return r;      // (a vacant row's list is empty, and a list per row for the whole range cannot say so)
     if (W > 0) if (int r = missions_standing(c, "sca_set_path_slots", MSF_PATHS)) return r;    // (W <= 0 is path_slots_check's SCA_ERR_ARG, tables or not)
     const PathSlotCheck k = path_slots_check(c->agents_set, c->part_on, c->n, c->max_n, W, n, offsets, points);
     if (k.fault != PATH_SLOTS_OK) {
@@ -1555,6 +1582,7 @@ int sca_set_path_state(sca_ctx *c, const int32_t *remaining, const double *now_g
     API_ENTER(c);
     if (!c->paths_on) { c->err = "no waypoint lists (sca_set_paths)"; return SCA_ERR_STATE; }
     ARG(c, remaining && now_goal);
+    if (int r = vacancy_refuse(c, "sca_set_path_state")) return r;      // (a vacant row's now_goal is None)
     if (int r = missions_path_mirrors(c)) return r;                    // (tables with lists: the bound is the device's lengths)
     const int n = c->n;
     for (int i = 0; i < n; i++) {
@@ -1636,6 +1664,7 @@ static int scenes_clear(sca_ctx *c) {
 int sca_set_scenes(sca_ctx *c, int nscenes, const int32_t *offsets) {
     API_ENTER(c);
     if (!c->agents_set) { c->err = "sca_set_agents first"; return SCA_ERR_STATE; }
+    if (int r = vacancy_refuse(c, "sca_set_scenes")) return r;
     const int n = c->n;
     const SceneCheck k = scenes_check(n, nscenes, offsets);
     if (k.fault != SCENES_OK && k.fault != SCENES_NONE) {
@@ -2354,13 +2383,14 @@ int sca_get_scene_sizes(sca_ctx *c, int32_t *size) {
 // KDTree.buildAgentTree (mampenv.py:28) on the HOST from a position read-back (SCA_NBR_KDTREE_HOSTBUILD: the A/B reference of
 // the device build below, which is what SCA_NBR_KDTREE runs).
 static int build_agent_tree(sca_ctx *c) {
-    const int n = c->n;
     if (!c->h_pos_valid) {
         if (int r = fetch_records(c)) return r;
-        c->h_pos.resize(3 * (size_t)n);
-        for (int i = 0; i < n; i++) { c->h_pos[3 * i] = c->h_rec[i].px; c->h_pos[3 * i + 1] = c->h_rec[i].py; c->h_pos[3 * i + 2] = c->h_rec[i].pz; }
+        c->h_pos.resize(3 * (size_t)c->n);
+        for (int i = 0; i < c->n; i++) { c->h_pos[3 * i] = c->h_rec[i].px; c->h_pos[3 * i + 1] = c->h_rec[i].py; c->h_pos[3 * i + 2] = c->h_rec[i].pz; }
         c->h_pos_valid = true;
     }
+    // (vacant rows, sca_vacancy.h: the tree holds the occupied prefix of the permutation and nothing else; the vacant tail stays as it is)
+    const int n = c->vac.on ? c->vac.m : c->n;
     kd_build_host(n, c->h_pos.data(), c->h_perm.data(), c->h_tree);
     CHK(c, hipMemcpyAsync(c->d.atree, c->h_tree.data(), sizeof(KdNode) * (2 * n - 1), hipMemcpyHostToDevice, c->stream));
     CHK(c, hipMemcpyAsync(c->d.aperm, c->h_perm.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
@@ -2391,7 +2421,10 @@ static int build_agent_tree_device(sca_ctx *c, hipStream_t ks, DeviceView d, con
 #ifdef SCA_TIMELINE
     if (a.next_pass) d.tl_step++;
 #endif
-    const int n = c->n;
+    // the tree's size: the occupied rows (sca_vacancy.h) -- the build kernels read DeviceView::n as the tree's size and as nothing else
+    // (k_kd_gather, k_kd_top), so the view they get says m; the vacant tail of the permutation, behind m, is nobody's to touch
+    const int n = c->vac.on ? c->vac.m : c->n;
+    d.n = n;
     // poll: the level statistics of an earlier build, if they have arrived (never waited for)
     if (c->kd_ev_pending && hipEventQuery(c->kd_ev) == hipSuccess) {
         if (c->kd_ev_gen == c->kd_gen) {
@@ -2415,7 +2448,7 @@ static int build_agent_tree_device(sca_ctx *c, hipStream_t ks, DeviceView d, con
     if (B.top && KT_M / (B.wave_max + 1) >= KT_NODES) { c->err = "k_kd_top: wave_max below its table bound"; return SCA_ERR_STATE; }   // (static_assert'ed unreachable)
     // enqueue
     if (!c->perm_on_device) {
-        CHK(c, hipMemcpyAsync(d.aperm, c->h_perm.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ks));
+        CHK(c, hipMemcpyAsync(d.aperm, c->h_perm.data(), sizeof(int32_t) * c->n, hipMemcpyHostToDevice, ks));
         c->perm_on_device = true;
     }
     c->kd.wave_max = B.wave_max;
@@ -2685,6 +2718,7 @@ static int pass_resolve(sca_ctx *c, int mode, PassPlan &p) {
         c->err = "scenes are set (sca_set_scenes): the scene form of the neighbour search is SCA_NBR_KDTREE (SCA_NBR_AUTO resolves to it)";
         return SCA_ERR_UNSUPPORTED;
     }
+    if (mode == SCA_NBR_GRID) if (int r = vacancy_refuse(c, "a pass in SCA_NBR_GRID")) return r;   // (the grid build does not skip vacant rows)
     // SCA_NBR_AUTO: an AUTO pass, or a plain kd pass where that cannot help (plan_auto; the cell-owner partition has its own structures)
     sca_ctx::Auto &A = c->au;
     double &ar = p.agent_reach, &orr = p.obs_reach;
@@ -2696,7 +2730,7 @@ static int pass_resolve(sca_ctx *c, int mode, PassPlan &p) {
         if (int r = A.fill(c)) return r;
         if (A.count_pending && hipEventQuery(A.ev_cnt) == hipSuccess) { A.last = A.count_host[0]; A.count_pending = false; }   // poll
         // (sca_run_steps only builds ahead when auto_next() holds)
-        const AutoPlan P = plan_auto(fits, p.tracked, A.ahead, A.last, c->tun.auto_div, A.backoff, c->d.shard_count);
+        const AutoPlan P = plan_auto(fits, p.tracked, A.ahead, A.last, c->tun.auto_div, A.backoff, c->d.shard_count, c->vac.on);
         A.backoff = P.auto_backoff; A.last = P.kdq_last; p.kdq_blocks = P.kdq_blocks;
         p.auto_mode = P.auto_pass;
         if (!p.auto_mode) mode = SCA_NBR_KDTREE;
@@ -2735,7 +2769,7 @@ static int pass_resolve(sca_ctx *c, int mode, PassPlan &p) {
     }
     c->d.lp_kernel = p.S.lp_kernel;
     p.forms = p.S.forms | (c->paths_on ? SCA_FORM_WAYPOINTS : 0) | (c->scenes.on ? SCA_FORM_SCENES : 0) |
-              (c->scenes.obs_on ? SCA_FORM_SCENE_OBSTACLES : 0);       // (the waypoint and scene bits are state, not a choice)
+              (c->scenes.obs_on ? SCA_FORM_SCENE_OBSTACLES : 0) | (c->vac.on ? SCA_FORM_VACANCY : 0);   // (the waypoint, scene and vacancy bits are state, not a choice)
     c->kd.skip_prep = c->grid.skip_prep = p.overlap ? 1 : 0;
     // K4's candidate lists and its fallback cover one cell around the agent: the collision reach must fit into it
     if (mode == SCA_NBR_GRID && (c->max_radius + ar > c->P.neighbor_dist || c->max_radius + orr > c->P.neighbor_dist)) {
@@ -3133,7 +3167,7 @@ static void auto_abandon(sca_ctx *c) {
 // what plan_step asks of the context, as it stands when it is asked
 static StepIn step_in(const sca_ctx *c, int mode, int s, int steps) {
     return StepIn{mode, s, steps, c->au.stream != nullptr, c->tun.ext_stop != 0, c->comm != nullptr, c->d.shard_count == c->n, c->trk_on, c->trk_in_pass, c->trk_fork != nullptr,
-                  c->paths_on, c->clear != nullptr, c->au.ran, c->au.fits, c->part_on, c->au.last, c->tun.auto_div, c->au.backoff, c->d.shard_count, c->ms.on};
+                  c->paths_on, c->clear != nullptr, c->au.ran, c->au.fits, c->part_on, c->au.last, c->tun.auto_div, c->au.backoff, c->d.shard_count, c->ms.on, c->vac.on};
 }
 // between the pass and the update: what the shard moved reaches the others, or what stands in for that
 static int step_exchange(sca_ctx *c) {
@@ -3296,6 +3330,7 @@ int sca_step_host(sca_ctx *c, int neighbor_mode, uint32_t in_mask, int *active) 
     ARG(c, active);
     ARG(c, (in_mask & ~(uint32_t)(SCA_HOST_IN_STATE | SCA_HOST_IN_VPREF)) == 0);
     if (int r = missions_standing(c, "sca_step_host", MSF_STEP_HOST)) return r;
+    if (int r = vacancy_refuse(c, "sca_step_host")) return r;
     if (int r = host_step_refuse(c, neighbor_mode, in_mask)) return r;
     if (int r = host_ingest(c, in_mask)) return r;
     if (int r = run_steps_guarded(c, 1, neighbor_mode, false)) return r;  // integrate fused into the pass, k_collide_finish; joins the kd stream
@@ -3363,6 +3398,7 @@ int sca_comm_init(sca_ctx *c, int rank, int nranks, const void *unique_id) {
     if (c->comm) { c->err = "communicator already initialised (sca_comm_destroy first)"; return SCA_ERR_STATE; }
     if (c->part_on) { c->err = "sca_comm_init with the cell-owner partition active"; return SCA_ERR_STATE; }
     if (c->scenes.on) { c->err = "sca_comm_init with scenes set (sca_set_scenes): scenes are one rank's"; return SCA_ERR_UNSUPPORTED; }
+    if (int r = vacancy_refuse(c, "sca_comm_init")) return r;
     if (int r = clearance_refuse(c, "sca_comm_init", clearance_check(CLR_COMM_INIT, clearance_state(c), 0, 0, true, 0))) return r;
     if (int r = missions_standing(c, "sca_comm_init", MSF_COMM)) return r;
     if (c->n % nranks) { c->err = "agent count must be a multiple of the rank count"; return SCA_ERR_ARG; }
@@ -3474,6 +3510,7 @@ int sca_partition_init(sca_ctx *c, int rank, int nranks, int axis, const double 
     ARG(c, nranks >= 1 && rank >= 0 && rank < nranks && axis >= 0 && axis <= 2 && cap_halo >= 0 && cap_mig >= 0);
     if (!c->agents_set || !c->state_set) { c->err = "sca_set_agents and sca_set_state (the complete state, on every rank) first"; return SCA_ERR_STATE; }
     if (c->comm) { c->err = "sca_partition_init with an active communicator (the all-gather mode)"; return SCA_ERR_STATE; }
+    if (int r = vacancy_refuse(c, "sca_partition_init")) return r;
     if (c->scenes.on) { c->err = "sca_partition_init with scenes set (sca_set_scenes): a mode of SCA_NBR_GRID, which has no scene form"; return SCA_ERR_UNSUPPORTED; }
     if (c->paths_on) { c->err = "sca_partition_init with waypoint lists set (sca_set_paths): path state does not migrate with the agents"; return SCA_ERR_UNSUPPORTED; }
     if (int r = clearance_refuse(c, "sca_partition_init", clearance_check(CLR_PARTITION_INIT, clearance_state(c), 0, 0, true, 0))) return r;
@@ -4075,6 +4112,64 @@ int sca_probe_clearance(sca_ctx *c, int count, const double *pos, const double *
     return 0;
 }
 
+// ---- vacant rows (include/sca_hip.h; the rules and the tiled edit are sca_vacancy.h's, the kernels sca_vacancy.hip.h's, enqueued here and
+// nowhere else) ------------------------------------------------------------------------------------------------------------------------------
+static int vacancy_call_refuse(sca_ctx *c, const char *who, VacancyFault f, int entry) {
+    const std::string w = std::string(who), at = std::to_string(entry);
+    switch (f) {
+    case VCF_OK: return 0;
+    case VCF_NO_AGENTS: c->err = w + ": sca_set_agents first"; break;
+    case VCF_NO_STATE: c->err = w + ": no state yet -- sca_set_state first"; break;
+    case VCF_MID_STEP: c->err = w + " between a policy pass and its env update: finish the step first"; break;
+    case VCF_BAD_COUNT: c->err = w + ": count must be positive"; break;
+    case VCF_NO_IDS: c->err = w + ": ids must not be NULL"; break;
+    case VCF_BAD_ID: c->err = w + ": ids[" + at + "] is not an agent of this context (0 .. " + std::to_string(c->n - 1) + ")"; break;
+    case VCF_REPEATED_ID: c->err = w + ": ids[" + at + "] is named twice"; break;
+    case VCF_ALREADY_VACANT: c->err = w + ": ids[" + at + "] is vacant already"; break;
+    case VCF_LAST_ROW: c->err = w + ": the call would leave no occupied row (a context keeps at least one)"; break;
+    case VCF_LIST_ARGS: c->err = w + ": capacity must not be negative, count not NULL, ids not NULL with a capacity"; break;
+    case VCF_SCENES: c->err = w + " with scenes set (sca_set_scenes): a scene's rows are vacated by sca_restart_scenes_sized"; break;
+    case VCF_SHARD: c->err = w + " on a shard with count < n (sca_set_shard): the call names rows of the whole swarm on one rank"; break;
+    case VCF_COMM: c->err = w + " with an active communicator: the call names rows of the whole swarm on one rank (sca_comm_destroy first)"; break;
+    case VCF_PARTITION: c->err = w + " under the cell-owner partition: the rows' state does not follow the owners (sca_partition_disable first)"; break;
+    default: c->err = w + " with waypoint lists in block form (sca_set_paths): one row's list cannot be emptied there -- sca_set_path_slots";
+    }
+    return vacancy_error_code(f);
+}
+// the device scratch of the permutation edit, allocated by the first retire
+struct VacScratch { int32_t *ids, *tmp, *counts, *offsets, *head; };
+static VacScratch vacancy_scratch(const sca_ctx *c) {
+    const size_t N = (size_t)c->max_n, T = (size_t)finished_tiles(c->max_n) + 1;
+    return VacScratch{c->vac.dev, c->vac.dev + N, c->vac.dev + 2 * N, c->vac.dev + 2 * N + T, c->vac.dev + 2 * N + 2 * T};
+}
+static int vacancy_room(sca_ctx *c) {
+    if (c->vac.dev) return 0;
+    const size_t N = (size_t)c->max_n, T = (size_t)finished_tiles(c->max_n) + 1;
+    CHK(c, hipMalloc((void **)&c->vac.dev, sizeof(int32_t) * (2 * N + 2 * T + 16)));
+    return 0;
+}
+// the live permutation onto the device, where it is still the host's: the edit runs there
+static int vacancy_perm_to_device(sca_ctx *c) {
+    if (c->perm_on_device) return 0;
+    CHK(c, hipMemcpyAsync(c->d.aperm, c->h_perm.data(), sizeof(int32_t) * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
+    c->perm_on_device = true;
+    return 0;
+}
+// one ordered compaction of sca_vacancy.h on c->stream, no synchronisation: the picked ids to out[base + (base_dev ? *base_dev : 0) + place]
+// below `cap`, their number to head[0] (device memory, or the page-locked block)
+static int vacancy_compact_enqueue(sca_ctx *c, const VacView &v, int mode, int32_t *out, int base, const int32_t *base_dev, int cap, int32_t *head) {
+    const int items = vac_items(v, mode), tiles = vac_tiles(items, FIN_TILE);
+    const VacScratch s = vacancy_scratch(c);
+    const VacEditDev e{v, s.counts, s.offsets, out, base_dev, base, cap, mode};
+    const FinishedDev f{nullptr, nullptr, nullptr, s.counts, s.offsets, items, tiles};
+    if (tiles > 0) hipLaunchKernelGGL(k_vac_count, dim3(tiles), dim3(FIN_TILE), 0, c->stream, e);
+    hipLaunchKernelGGL(k_finished_scan, dim3(1), dim3(FIN_TILE), 0, c->stream, f, head);      // (no tiles: the total is 0)
+    if (tiles > 0) hipLaunchKernelGGL(k_vac_write, dim3(tiles), dim3(FIN_TILE), 0, c->stream, e);
+    CHK(c, hipGetLastError());
+    return 0;
+}
+static int vacancy_occupied(const sca_ctx *c) { return c->vac.on ? c->vac.m : c->n; }
+
 // sca_respawn_agents and sca_respawn_agents_gated (gate != nullptr) behind their refusals
 struct RespawnGate { double margin; int32_t *verdict; sca_scene_clearance *probe; int32_t *admitted; };
 static int respawn_run(sca_ctx *c, const RespawnCtx &X, const RespawnArgs &A, const RespawnGate *gate);
@@ -4132,6 +4227,12 @@ static int respawn_run(sca_ctx *c, const RespawnCtx &X, const RespawnArgs &A, co
     if (slots) { d.path_pts = c->pslot_pts; d.now_goal = c->path.now_goal; d.path_len = c->pslot_len; d.path_rem = c->path.rem; d.W = c->path_W; }
     d.clear = c->clear;
     d.n = c->n;
+    // vacant rows among the named ones (sca_vacancy.h): the call admits them -- their ids are appended to the permutation's occupied prefix in
+    // the call's order, in front of k_respawn (which clears their vacant bit), and the vacant tail behind the prefix is written again behind it
+    int vac_named = 0;
+    if (c->vac.on) for (int r = 0; r < count; r++) vac_named += c->vac.h[(size_t)ids[r]];
+    if (vac_named) if (int r = vacancy_perm_to_device(c)) return r;
+    const VacView vv{c->d.rec, c->d.aperm, (const int32_t *)(c->rsp_host + L.off[RSB_IDS]), nullptr, c->n, vacancy_occupied(c), count};
     // on c->stream, behind every reader of the rows: a step's kernels run there or on streams the step joins back before it ends
     // the gate in front of it: the world test of every named start (the row itself ignored), the entry test among the call's rows
     SpawnDev sd{};
@@ -4141,9 +4242,18 @@ static int respawn_run(sca_ctx *c, const RespawnCtx &X, const RespawnArgs &A, co
         spawn_pack(c->spn_host, SL, count, pos, radius, ids);
         if (int r = spawn_enqueue(c, count, true, gate->margin, sd)) return r;
     }
+    if (vac_named) {                                                   // (a gated call: the verdict decides on the device which ids are appended)
+        VacView va = vv;
+        va.verdict = gate ? (const int32_t *)sd.verdict : nullptr;
+        if (int r = vacancy_compact_enqueue(c, va, VAC_ADMIT, c->d.aperm, vv.m, nullptr, c->n, vacancy_scratch(c).head)) return r;
+    }
     hipLaunchKernelGGL(k_respawn, dim3((count + RESPAWN_WAVES - 1) / RESPAWN_WAVES), dim3(RESPAWN_WAVES * 64), 0, c->stream, d, (const uint8_t *)c->rsp_host, L, has, count,
                        (const int32_t *)(gate ? sd.verdict : nullptr));
     CHK(c, hipGetLastError());
+    if (vac_named) {                                                   // the rows that are still vacant, ascending, behind the admitted ones
+        const VacScratch vs = vacancy_scratch(c);
+        if (int r = vacancy_compact_enqueue(c, vv, VAC_TAIL, c->d.aperm, vv.m, vs.head, c->n, vs.head + 1)) return r;
+    }
     // (mission tables: the named rows -- a gated call's admitted ones -- fly a flight that is not an entry and enter the next step running)
     if (int r = missions_host_flight(c, (const int32_t *)(c->rsp_host + L.off[RSB_IDS]), gate ? (const int32_t *)sd.verdict : nullptr, count)) return r;
     CHK(c, hipStreamSynchronize(c->stream));
@@ -4162,6 +4272,7 @@ static int respawn_run(sca_ctx *c, const RespawnCtx &X, const RespawnArgs &A, co
     for (int r = 0; r < count; r++) {
         if (verdict && verdict[r] != SCA_SPAWN_ADMITTED) continue;
         const int a = ids[r];
+        if (vac_named && c->vac.h[(size_t)a]) { c->vac.h[(size_t)a] = 0; c->vac.m++; }   // admitted
         c->h_rec[a].radius = radius[r];
         c->max_radius = std::max(c->max_radius, radius[r]);           // the envelope only grows (conservative filters, as under the restarts)
         c->max_pref_speed = std::max(c->max_pref_speed, pref_speed[r]);
@@ -4181,6 +4292,7 @@ static int respawn_run(sca_ctx *c, const RespawnCtx &X, const RespawnArgs &A, co
         }
     }
     c->h_pos_valid = false; c->near_valid = false;
+    if (c->vac.on && c->vac.m == c->n) c->vac.on = false;              // every row is occupied again: whatever vacancy refused works again
     positions_replaced(c);                                             // (a sizing hint, no value; not state_replaced: the form heuristics, the AUTO passes' counts among them, are left alone)
     return 0;
 }
@@ -4205,6 +4317,80 @@ int sca_get_finished(sca_ctx *c, sca_finished_row *rows, int capacity, int *coun
     const int total = *(const int32_t *)c->fin_host;
     *count = total;
     if (std::min(total, cap) > 0) std::memcpy(rows, c->fin_host + FIN_HEAD_BYTES, sizeof(sca_finished_row) * (size_t)std::min(total, cap));
+    return 0;
+}
+
+// One launch of k_vacate, the stable deletion of the named ids from the permutation's occupied prefix (into scratch, copied back), the
+// ascending vacant tail behind it, one synchronisation.
+int sca_retire_agents(sca_ctx *c, int count, const int32_t *ids) {
+    API_ENTER(c);
+    const RespawnCtx X = respawn_ctx(c);
+    const int n = c->n, m = vacancy_occupied(c);
+    const VacancyCheck k = vacancy_check(X, c->vac.on ? c->vac.h.data() : nullptr, m, count, ids);
+    if (int r = vacancy_call_refuse(c, "sca_retire_agents", k.fault, k.entry)) return r;
+    if (int r = vacancy_room(c)) return r;
+    if (int r = missions_path_mirrors(c)) return r;                    // (tables with lists: the host's mirrors of the lengths follow the rows as they are NOW)
+    const VacScratch s = vacancy_scratch(c);
+    const int m_new = m - count;
+    const bool slots = X.path_W > 0;
+    CHK(c, hipMemcpyAsync(s.ids, ids, sizeof(int32_t) * (size_t)count, hipMemcpyHostToDevice, c->stream));
+    if (int r = vacancy_perm_to_device(c)) return r;
+    VacateDev d{};
+    d.rec = c->d.rec; d.heading = c->d.heading; d.total_dist = c->d.total_dist; d.action = c->d.action; d.diag = c->d.diag;
+    d.step_num = c->d.step_num; d.status = c->d.status; d.nbr_n = c->d.nbr_n; d.near_n = c->d.near_n; d.done_count = c->d.done_count;
+    d.nbr_valid = c->d.nbr_valid;
+    if (slots) { d.now_goal = c->path.now_goal; d.path_len = c->pslot_len; d.path_rem = c->path.rem; }
+    d.clear = c->clear;
+    d.n = n;
+    // on c->stream, behind every reader of the rows (as k_respawn)
+    hipLaunchKernelGGL(k_vacate, dim3((count + RESPAWN_WAVES - 1) / RESPAWN_WAVES), dim3(RESPAWN_WAVES * 64), 0, c->stream, d, (const int32_t *)s.ids, count);
+    CHK(c, hipGetLastError());
+    const VacView v{c->d.rec, c->d.aperm, nullptr, nullptr, n, m, 0};
+    if (int r = vacancy_compact_enqueue(c, v, VAC_KEEP, s.tmp, 0, nullptr, n, s.head + 1)) return r;
+    if (int r = vacancy_compact_enqueue(c, v, VAC_TAIL, c->d.aperm, m_new, nullptr, n, s.head + 1)) return r;
+    CHK(c, hipMemcpyAsync(c->d.aperm, s.tmp, sizeof(int32_t) * (size_t)m_new, hipMemcpyDeviceToDevice, c->stream));
+    if (int r = missions_retired(c, s.ids, count)) return r;           // (mission tables: a waiting word is dropped, the rows enter the next step done)
+    CHK(c, hipStreamSynchronize(c->stream));
+    // the host's mirrors follow
+    if (c->vac.h.size() != (size_t)n) c->vac.h.assign((size_t)n, 0);
+    const HostLayout HL = host_state_layout(n);
+    for (int r = 0; r < count; r++) {
+        const int a = ids[r];
+        c->vac.h[(size_t)a] = 1;
+        if (slots) { c->h_path_len[a] = 0; c->h_path_vpref[a] = 0; }
+        if (c->hs_host) {                                              // the state block, if the caller has one (sca_step_host is refused while a row is vacant; the block stays true)
+            uint8_t *b = c->hs_host;
+            std::memset((float *)(b + HL.off[HS_VEL]) + 3 * (size_t)a, 0, sizeof(float) * 3);
+            std::memset((double *)(b + HL.off[HS_HEADING]) + 3 * (size_t)a, 0, sizeof(double) * 3);
+            (b + HL.off[HS_FLAGS])[a] = (uint8_t)VACANT_FLAGS;
+            ((double *)(b + HL.off[HS_TOTAL_DIST]))[a] = 0.0;
+            ((int32_t *)(b + HL.off[HS_STEP_NUM]))[a] = 0;
+        }
+    }
+    c->vac.on = true; c->vac.m = m_new;
+    c->h_pos_valid = false;
+    positions_replaced(c);                                             // (the tree's size has changed: no sizing hint from older trees)
+    return 0;
+}
+int sca_get_vacant(sca_ctx *c, int32_t *ids, int capacity, int *count) {
+    API_ENTER(c);
+    if (int r = vacancy_call_refuse(c, "sca_get_vacant", vacant_list_check(respawn_ctx(c), ids != nullptr, capacity, count != nullptr), -1)) return r;
+    if (!c->vac.on) { *count = 0; return 0; }                          // (a context that never retires enqueues nothing)
+    const int n = c->n, cap = std::min(capacity, n);
+    if (!c->vac.host) CHK(c, hipHostMalloc((void **)&c->vac.host, (size_t)FIN_HEAD_BYTES + sizeof(int32_t) * (size_t)c->max_n, hipHostMallocMapped | hipHostMallocCoherent));
+    const VacView v{c->d.rec, c->d.aperm, nullptr, nullptr, n, c->vac.m, 0};
+    if (int r = vacancy_compact_enqueue(c, v, VAC_TAIL, (int32_t *)(c->vac.host + FIN_HEAD_BYTES), 0, nullptr, cap, (int32_t *)c->vac.host)) return r;
+    CHK(c, hipStreamSynchronize(c->stream));
+    const int total = *(const int32_t *)c->vac.host;
+    *count = total;
+    if (std::min(total, cap) > 0) std::memcpy(ids, c->vac.host + FIN_HEAD_BYTES, sizeof(int32_t) * (size_t)std::min(total, cap));
+    return 0;
+}
+int sca_get_population(sca_ctx *c, int *occupied) {
+    API_ENTER(c);
+    ARG(c, occupied);
+    if (!c->agents_set) { c->err = "sca_get_population: sca_set_agents first"; return SCA_ERR_STATE; }
+    *occupied = vacancy_occupied(c);
     return 0;
 }
 
@@ -4288,6 +4474,18 @@ static int missions_host_flight(sca_ctx *c, const int32_t *ids, const int32_t *v
     CHK(c, hipGetLastError());
     if (c->ms.gate.on) {                                                   // a gate: a named row the call wrote loses its pending mission
         hipLaunchKernelGGL(k_mission_gate_named, dim3((count + MISSION_T - 1) / MISSION_T), dim3(MISSION_T), 0, c->stream, ids, verdict, count, c->n,
+                           c->ms.gate.words + (size_t)MGW_WAITING * c->n, c->ms.gate.totals);
+        CHK(c, hipGetLastError());
+    }
+    return missions_refresh_live(c);
+}
+// sca_retire_agents while tables stand, behind its k_vacate on c->stream: a retired row waiting at the gate loses its pending mission
+// (`dropped` + 1); a row retired in flight writes no result and moves no total -- it enters the next step done (k_mission_live), so the
+// step's last kernel sees no ending -- and never ends again, so no table takes it.  ids: device memory.
+static int missions_retired(sca_ctx *c, const int32_t *ids, int count) {
+    if (!c->ms.on) return 0;
+    if (c->ms.gate.on) {
+        hipLaunchKernelGGL(k_mission_gate_named, dim3((count + MISSION_T - 1) / MISSION_T), dim3(MISSION_T), 0, c->stream, ids, (const int32_t *)nullptr, count, c->n,
                            c->ms.gate.words + (size_t)MGW_WAITING * c->n, c->ms.gate.totals);
         CHK(c, hipGetLastError());
     }
@@ -4704,6 +4902,7 @@ int sca_context_checkpoint_info(const void *blob, int64_t bytes, struct sca_cont
 int sca_context_checkpoint_bytes(sca_ctx *c, int64_t *bytes) {
     API_ENTER(c);
     ARG(c, bytes);
+    if (int r = vacancy_refuse(c, "sca_context_checkpoint_bytes")) return r;
     if (int r = ctx_ckpt_call_refuse(c, "sca_context_checkpoint_bytes", true)) return r;    // (a size only where a save is possible)
     *bytes = ctx_checkpoint_layout(ctx_ckpt_shape(c)).total;
     return 0;
@@ -4712,6 +4911,7 @@ int sca_context_checkpoint_bytes(sca_ctx *c, int64_t *bytes) {
 // permutation while the host still holds it, the header, the checksum -- and copies it out.
 int sca_save_context(sca_ctx *c, void *out, int64_t out_bytes) {
     API_ENTER(c);
+    if (int r = vacancy_refuse(c, "sca_save_context")) return r;       // (vacancy is not in the blob)
     if (int r = ctx_ckpt_call_refuse(c, "sca_save_context", out != nullptr)) return r;
     const CtxShape S = ctx_ckpt_shape(c);
     const CtxLayout L = ctx_checkpoint_layout(S);
@@ -4745,6 +4945,7 @@ int sca_save_context(sca_ctx *c, void *out, int64_t out_bytes) {
 // host state block where one exists.  state_replaced's effects apply, except that state_fresh takes the blob's value.
 int sca_load_context(sca_ctx *c, const void *in, int64_t in_bytes) {
     API_ENTER(c);
+    if (int r = vacancy_refuse(c, "sca_load_context")) return r;
     if (int r = ctx_ckpt_call_refuse(c, "sca_load_context", in != nullptr)) return r;
     CtxExpect X{};
     X.shape = ctx_ckpt_shape(c); X.policy = c->h_policy.data(); X.n_obs = c->d.m;
@@ -4926,6 +5127,7 @@ int sca_set_shard(sca_ctx *c, int begin, int count) {
     if (c->part_on) { c->err = "sca_set_shard with the cell-owner partition active (sca_partition_disable first)"; return SCA_ERR_STATE; }
     if (c->comm) { c->err = "sca_set_shard with an active communicator (the shard follows from rank / nranks; sca_comm_destroy first)"; return SCA_ERR_STATE; }
     if (c->scenes.on && (begin != 0 || count != c->n)) { c->err = "sca_set_shard with scenes set (sca_set_scenes): scenes are stepped by one rank, whole"; return SCA_ERR_UNSUPPORTED; }
+    if (count < c->n) if (int r = vacancy_refuse(c, "sca_set_shard with count < n")) return r;
     if (int r = clearance_refuse(c, "sca_set_shard", clearance_check(CLR_SET_SHARD, clearance_state(c), count, 0, true, 0))) return r;
     if (count < c->n) if (int r = missions_standing(c, "sca_set_shard", MSF_SHARD)) return r;
     c->d.shard_begin = begin; c->d.shard_count = count;

@@ -185,7 +185,7 @@ __global__ __launch_bounds__(SPAWN_WAVES * 64) void k_mission_gate_probe(Mission
         if (p < n) { const PubRec a = g.m.row.rec[p]; c.x = a.px; c.y = a.py; c.z = a.pz; c.r = a.radius; }
         else { const ObsRec o = g.obs[p - n]; c.x = o.px; c.y = o.py; c.z = o.pz; c.r = o.radius; }
         pts[j] = c;
-        ids[j] = spawn_partner_id(p, n);
+        ids[j] = p < n && (g.m.row.rec[p].flags & FLAG_VACANT) ? SPAWN_VACANT_ID : spawn_partner_id(p, n);
     }
     __syncthreads();
     for (int chunk = (int)blockIdx.y; chunk < chunks; chunk += (int)gridDim.y) {      // (uniform over the workgroup)

@@ -296,6 +296,8 @@ SCA_HD void respawn_write_list(double *pts, int W, int a, int lane, const double
 constexpr int FIN_TILE = 256;
 inline int finished_tiles(int n) { return (n + FIN_TILE - 1) / FIN_TILE; }
 SCA_HD bool finished_flag(uint32_t flags) { return (flags & RSP_DONE_FLAGS) != 0; }
+// what the list holds: a vacant row (sca_vacancy.h) is settled for good but has not "finished" -- nobody is to give it a new mission by this list
+SCA_HD bool finished_listed(uint32_t flags) { return finished_flag(flags) && !(flags & FLAG_VACANT); }
 // offsets[t] = counts[0] + .. + counts[t - 1]; returns the total
 SCA_HD int finished_offsets(const int32_t *counts, int tiles, int32_t *offsets) {
     int at = 0;

@@ -74,7 +74,7 @@ struct FinishedDev {
 static_assert(FIN_TILE == 256, "k_finished_* run four wavefronts per tile");
 __device__ __forceinline__ unsigned long long finished_ballot(const FinishedDev &f, int row, uint32_t &flags) {
     flags = row < f.n ? f.rec[row].flags : 0u;
-    return __ballot(finished_flag(flags));
+    return __ballot(finished_listed(flags));
 }
 __global__ __launch_bounds__(FIN_TILE) void k_finished_count(FinishedDev f) {
     __shared__ int32_t wsum[FIN_TILE / 64];
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(FIN_TILE) void k_finished_write(FinishedDev f, uint
     const unsigned long long mask = finished_ballot(f, row, flags);
     if ((t & 63) == 0) wsum[wave] = __popcll(mask);
     __syncthreads();
-    if (!finished_flag(flags)) return;
+    if (!finished_listed(flags)) return;
     int at = f.offsets[blockIdx.x] + finished_rank(mask, t & 63);
     for (int k = 0; k < wave; k++) at += wsum[k];
     if (at >= capacity) return;

@@ -87,6 +87,8 @@ SCA_SCENES_HD int spawn_chunks(int count) { return (count + SPAWN_CHUNK - 1) / S
 SCA_SCENES_HD int64_t spawn_partial_index(int tile, int query, int cap) { return (int64_t)tile * cap + query; }
 // a staged partner's id: the agent row or the obstacle's place in the set
 SCA_SCENES_HD int32_t spawn_partner_id(int64_t g, int n) { return (int32_t)(g < n ? g : g - n); }
+// what the staging puts in the place of a vacant row's id (sca_vacancy.h): spawn_tile_partial passes over it, so a vacant row is nobody's partner
+constexpr int32_t SPAWN_VACANT_ID = INT32_MIN;
 
 // One query's running minimum, both halves: what a lane holds in registers and what a partial stores (32 bytes, the record's own layout
 // with the step words unused).
@@ -104,7 +106,7 @@ SCA_SCENES_HD void spawn_tile_partial(const ClearPoint &q, int32_t ignore, const
     for (int j = begin; j < end; j++) {
         const int32_t id = ids[j];
         if (g0 + j < n) {
-            if (id == ignore) continue;
+            if (id == ignore || id == SPAWN_VACANT_ID) continue;
             spawn_merge(acc.agent, clearance_member(q, pts[j], id, acc.agent.c, norm));
         } else {
             spawn_merge(acc.obs, clearance_member(q, pts[j], id, acc.obs.c, norm));

@@ -37,7 +37,7 @@ __global__ __launch_bounds__(SPAWN_WAVES * 64) void k_spawn_probe(SpawnDev s) {
         if (g < s.n) { const PubRec a = s.rec[g]; p.x = a.px; p.y = a.py; p.z = a.pz; p.r = a.radius; }
         else { const ObsRec o = s.obs[g - s.n]; p.x = o.px; p.y = o.py; p.z = o.pz; p.r = o.radius; }
         pts[j] = p;
-        ids[j] = spawn_partner_id(g, s.n);
+        ids[j] = g < s.n && (s.rec[g].flags & FLAG_VACANT) ? SPAWN_VACANT_ID : spawn_partner_id(g, s.n);
     }
     __syncthreads();
     const int q = (int)blockIdx.y * SPAWN_CHUNK + lane;

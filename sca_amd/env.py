@@ -263,6 +263,11 @@ class Agent:
         return self._flag(S.FLAG_TIMEOUT)
 
     @property
+    def is_vacant(self):
+        """the row is vacant (MACAEnv.retire): out of the world until a respawn names it; its flags read 11"""
+        return self._flag(S.FLAG_VACANT)
+
+    @property
     def is_run_done(self):
         return self.is_at_goal or self.is_collision or self.is_out_of_max_time
 
@@ -655,8 +660,45 @@ class MACAEnv(_FlatAgents):
 
     def finished(self, capacity=None):
         """The rows that carry any of at-goal / collision / timeout, ascending ids, compacted on the device (sca_get_finished): a
-        structured array of _lib.FINISHED_DTYPE (id, flags, step_num, total_dist, pos)."""
+        structured array of _lib.FINISHED_DTYPE (id, flags, step_num, total_dist, pos).  Vacant rows are not among them."""
         return self.solver.finished(capacity)
+
+    def retire(self, agents):
+        """The drones leave the airspace (sca_retire_agents): `agents` are Agent objects of this env or row ids, occupied, live or finished.
+        Their rows become vacant -- env.agents keeps the objects, which read is_vacant, flags 11, zero velocity and heading -- and are
+        nobody's neighbour, collision, clearance or probe partner any more; everybody else flies on untouched.  respawn() with an Agent
+        whose id is a vacant row admits a drone there.  At least one row stays occupied."""
+        if self.agents is None:
+            raise RuntimeError('retire: set_agents first')
+        if self._row_cache is not None:
+            raise RuntimeError('retire: between a policy pass and its env update (agent.find_next_action was called): env.step() first')
+        ids = [int(getattr(a, 'id', a)) for a in agents]
+        if not ids:
+            return
+        n = len(self.agents)
+        if min(ids) < 0 or max(ids) >= n or len(set(ids)) != len(ids):
+            raise ValueError('retire: a row of this env, 0 .. %d, and no row twice' % (n - 1))
+        self._sync_paths()
+        live = (self._state('flags')[ids] & 7) == 0
+        self.solver.retire(ids)
+        for i in ids:
+            self._mission_pending.pop(i, None)
+            self._path_assigned.discard(i)
+        self._active -= int(live.sum())
+        self._stale = True
+        self._path_stale = self._paths_on
+        self._nbr_cache = None
+        self._vpref_cache = None
+
+    @property
+    def vacant(self):
+        """the vacant rows' ids, ascending (sca_get_vacant)"""
+        return self.solver.vacant()
+
+    @property
+    def population(self):
+        """the occupied rows (sca_get_population)"""
+        return self.solver.population()
 
     # ---- mission tables: finished rows take their next mission inside the step (sca_set_missions) ---------------------------
     def set_missions(self, tables, results=4, spawn_margin=None, max_per_step=None):

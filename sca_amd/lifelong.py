@@ -11,6 +11,11 @@ spawn_margin (metres): an admission gate in front of every respawn (MACAEnv.resp
 whose start is not free by that margin WAITS: its row stays finished where it is, and the mission is offered again in front of every
 later step, together with that step's new ones, waiting ones first, in ascending id.
 
+A changing population (MACAEnv.retire, sca_retire_agents): next_mission may return lifelong.RETIRE -- the drone leaves the airspace, its
+row becomes vacant and is nobody's neighbour or collision partner any more -- and arrivals(step, vacant_ids) -> [Agent] offers new drones
+for vacant rows (Agent.id names the row) behind every step; they go through spawn_margin when it is set, and a refused arrival waits as a
+refused mission does.
+
     stats = run_missions(env, tables, steps, burst=1, on_result=None, spawn_margin=None, checkpoint_at=None)
 
 is the same traffic with the missions on the device (MACAEnv.set_missions, sca_set_missions): a row that ends takes its table's
@@ -25,13 +30,19 @@ the stats of the run that was never cut.  run_lifelong's host loop is out of sco
 Python objects of the caller's rule, which no blob can carry."""
 from . import solver as S
 
+RETIRE = object()                                                # what next_mission returns for a drone that leaves the airspace (MACAEnv.retire)
 
-def run_lifelong(env, next_mission, steps, on_done=None, spawn_margin=None):
+
+def run_lifelong(env, next_mission, steps, on_done=None, spawn_margin=None, arrivals=None):
     """Returns dict(steps, arrived, collided, timed_out: missions that ended that way (a collision wins over an arrival, an arrival over a
     time-out), respawned, retired, agent_steps: agents served summed over the steps, live_fraction: agent_steps / (agents x steps)).
     The run ends early when every agent is retired.  With spawn_margin the dict gains `deferred`, the refusals counted per attempt, and
     `waiting`, the missions still pending at the end: arrived + collided + timed_out == respawned + retired + waiting; the run then ends
-    early too when nobody runs: the world is then still, and who waits would wait for ever."""
+    early too when nobody runs: the world is then still, and who waits would wait for ever.
+    A changing population -- next_mission returned RETIRE at least once, or `arrivals` is given -- adds retired_rows (rows vacated: such an
+    ending counts in `retired` too), admitted (arrivals that entered; not in `respawned`), arrivals_waiting (with spawn_margin: arrivals
+    still refused at the end; `waiting` counts missions only) and population_min / population_max / population_mean over the steps.  With
+    `arrivals` the run does not end early while nobody runs: the next arrival may change that."""
     n = len(env.agents)
     stats = dict(steps=0, arrived=0, collided=0, timed_out=0, respawned=0, retired=0, agent_steps=0, live_fraction=0.0)
     gated = spawn_margin is not None
@@ -39,14 +50,17 @@ def run_lifelong(env, next_mission, steps, on_done=None, spawn_margin=None):
         stats.update(deferred=0, waiting=0)
     retired = set()
     waiting = {}                                                 # id -> the Agent whose start was not free
+    vacant = set(int(i) for i in env.vacant) if arrivals is not None else set()   # the vacant rows, followed here
+    arriving = set()                                             # ids in `waiting` that are arrivals, not missions
+    traffic = dict(retired_rows=0, admitted=0, changing=arrivals is not None, pop_min=n - len(vacant), pop_max=n - len(vacant), pop_sum=0)
     active = env._active
     for _ in range(int(steps)):
-        if active == 0:
+        if active == 0 and arrivals is None:
             break
         stats['agent_steps'] += active
         env.step()
         stats['steps'] += 1
-        new = []
+        new, leaving = [], []
         if env._active < active:                                 # somebody finished in this step
             for row in env.finished():
                 i = int(row['id'])
@@ -61,8 +75,24 @@ def run_lifelong(env, next_mission, steps, on_done=None, spawn_margin=None):
                 if nxt is None:
                     retired.add(i)
                     stats['retired'] += 1
+                elif nxt is RETIRE:
+                    leaving.append(i)
+                    stats['retired'] += 1
                 else:
                     new.append(nxt)
+        if leaving:                                              # (the last occupied row stays: a context keeps one)
+            if len(leaving) >= n - len(vacant):
+                retired.add(leaving.pop())
+            if leaving:
+                env.retire(leaving)
+                vacant.update(leaving)
+                traffic['retired_rows'] += len(leaving)
+                traffic['changing'] = True
+        if arrivals is not None:
+            free = sorted(vacant - set(waiting))
+            came = list(arrivals(stats['steps'], free)) if free else []
+            arriving.update(int(a.id) for a in came)
+            new = new + came
         if gated:
             offer = [waiting[i] for i in sorted(waiting)] + new  # the waiting ones first, in ascending id, then this step's new ones
             if offer:
@@ -72,12 +102,30 @@ def run_lifelong(env, next_mission, steps, on_done=None, spawn_margin=None):
                 waiting = {a.id: a for a in offer}
                 for a in admitted:
                     del waiting[a.id]
+                entered = [a.id for a in admitted if a.id in arriving]
+                stats['respawned'] -= len(entered)               # (an arrival that entered is no mission taken)
+                stats['deferred'] -= sum(1 for i in waiting if i in arriving)
+                traffic['admitted'] += len(entered)
+                vacant.difference_update(entered)
+                arriving.difference_update(entered)
         elif new:
             env.respawn(new)
-            stats['respawned'] += len(new)
+            entered = [a.id for a in new if a.id in arriving]
+            stats['respawned'] += len(new) - len(entered)
+            traffic['admitted'] += len(entered)
+            vacant.difference_update(entered)
+            arriving.difference_update(entered)
         active = env._active
+        pop = n - len(vacant)
+        traffic['pop_min'], traffic['pop_max'] = min(traffic['pop_min'], pop), max(traffic['pop_max'], pop)
+        traffic['pop_sum'] += pop
     if gated:
-        stats['waiting'] = len(waiting)
+        stats['waiting'] = len(waiting) - len(arriving)
+    if traffic['changing']:
+        stats.update(retired_rows=traffic['retired_rows'], admitted=traffic['admitted'], population_min=traffic['pop_min'], population_max=traffic['pop_max'],
+                     population_mean=traffic['pop_sum'] / float(stats['steps']) if stats['steps'] else float(n - len(vacant)))
+        if gated:
+            stats['arrivals_waiting'] = len(arriving)
     stats['live_fraction'] = stats['agent_steps'] / float(n * stats['steps']) if stats['steps'] else 0.0
     return stats
 

@@ -12,6 +12,7 @@ from . import _lib
 
 POL_SCA, POL_RVO3D, POL_SRVO3D, POL_ORCA3D, POL_ORCA3D_LP, POL_RVO3D_DUBINS = range(6)
 FLAG_AT_GOAL, FLAG_COLLISION, FLAG_TIMEOUT = 1, 2, 4
+FLAG_VACANT = 8                                                 # a vacant row (retire): always with at-goal | collision, get_state shows 11
 MISSION_START_HERE, MISSION_KEEP_ZAXIS = 1, 2                  # sca_mission_flag
 SPAWN_ADMITTED, SPAWN_BLOCKED_AGENT, SPAWN_BLOCKED_OBSTACLE, SPAWN_BLOCKED_ENTRY = 0, 1, 2, 3      # SCA_SPAWN_*: a gated respawn's verdict per row
 SPAWN_OVER_CAP = 4                                               # ... and, under set_mission_gate only, "not tested in this step"
@@ -20,6 +21,7 @@ FORM_SOLVE_SPLIT, FORM_TRACK_FUSED, FORM_REPLAN_LANE, FORM_REPLAN_FEW, FORM_LP_L
 FORM_WAYPOINTS = 256                                          # k_waypoint ran (waypoint lists are set)
 FORM_SCENES = 512                                             # scenes are set: forest build, scene forms of K1 / K4
 FORM_SCENE_OBSTACLES = 1024                                   # ... with one obstacle set per scene (set_scene_obstacles)
+FORM_VACANCY = 2048                                           # a row is vacant (retire): the tree holds the occupied rows, NBR_AUTO was the kd pass
 K = _lib.K
 _ATTR_NAMES = tuple(name for name, _ in _lib.RestartAttrs._fields_[2:])   # sca_restart_attrs' arrays, in the struct's order
 
@@ -571,6 +573,32 @@ class BatchedSolver:
                   'sca_get_finished')
         self.finished_count = int(cnt.value)
         return out[:max(0, min(cap, self.finished_count))]
+
+    # ---- vacant rows: drones leave the airspace and re-enter (sca_retire_agents / sca_get_vacant / sca_get_population) ---------
+    def retire(self, ids):
+        """Takes the occupied rows `ids` (any order, no repeats; live or finished) out of the world (sca_retire_agents): each becomes a
+        vacant row -- flags 11 (at-goal | collision | FLAG_VACANT), zero velocity, heading, travelled distance and step count, position and
+        constants kept -- that stands in no tree and is nobody's neighbour, collision, clearance or probe partner; every other row keeps
+        every word it had.  The kd permutation keeps the occupied ids in carried order in front and the vacant ids ascending behind them.
+        `respawn` with a vacant id admits the row again.  Only between two steps; one synchronisation however many rows are named."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        self._chk(self.L.sca_retire_agents(self.ctx, len(ids), _lib.ptr(ids, C.c_int32)), 'sca_retire_agents')
+
+    def vacant(self, capacity=None):
+        """The vacant rows' ids, ascending (sca_get_vacant: compacted on the device, one synchronisation; nothing is enqueued while no row
+        is vacant).  capacity: at most that many ids are fetched (None: all); `vacant_count` holds their number in either case."""
+        cap = int(self.n) if capacity is None else int(capacity)
+        out = np.zeros(max(cap, 1), np.int32)
+        cnt = C.c_int(0)
+        self._chk(self.L.sca_get_vacant(self.ctx, _lib.ptr(out, C.c_int32), cap, C.byref(cnt)), 'sca_get_vacant')
+        self.vacant_count = int(cnt.value)
+        return out[:max(0, min(cap, self.vacant_count))]
+
+    def population(self):
+        """The occupied rows, m <= n (sca_get_population)."""
+        m = C.c_int(0)
+        self._chk(self.L.sca_get_population(self.ctx, C.byref(m)), 'sca_get_population')
+        return int(m.value)
 
     # ---- mission tables: finished rows take their next mission inside the step (sca_set_missions) ------------------------------
     def set_missions(self, M, R, entries, first_ok, first_fail, paths=None):
