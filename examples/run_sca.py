@@ -38,7 +38,28 @@ def lifelong(args, agents, obstacles, pol, dubins):
     original mission again.  --waypoints K: every leg follows a route of K seeded waypoints (Agent.path), reversed on the way back."""
     from sca_amd.lifelong import run_lifelong
     K = args.waypoints
-    env = E.MACAEnv(device_tracker=dubins, clearance=args.clearance, path_slots=K)
+    fleet = [POLICIES[name] for name in args.fleet.split(',')] if args.fleet else None
+    if fleet:                                                      # a mixed fleet: an arriving drone brings its own policy (MACAEnv(attribute_slots=True))
+        dubins = dubins or any(p in (E.SCAPolicy, E.RVO3dDubinsPolicy) for p in fleet)
+        env = E.MACAEnv(device_tracker=dubins, clearance=args.clearance, path_slots=K, attribute_slots=True)
+    else:
+        env = E.MACAEnv(device_tracker=dubins, clearance=args.clearance, path_slots=K)
+    per_policy = {p.__name__: dict(entered=0, arrived=0, collided=0, timed_out=0) for p in fleet or ()}
+
+    def line_of(agent):
+        return per_policy.setdefault(type(agent.policy).__name__, dict(entered=0, arrived=0, collided=0, timed_out=0))
+    if fleet:                                                      # entered: counted where env.respawn admits an arrival (a vacant row's new drone)
+        respawn = env.respawn
+
+        def counting_respawn(new, margin=None):
+            new = list(new)
+            were_vacant = {a.id for a in new if env.agents[a.id].is_vacant}
+            got = respawn(new, margin=margin)
+            for a in (new if margin is None else got):
+                if a.id in were_vacant:
+                    line_of(a)['entered'] += 1
+            return got
+        env.respawn = counting_respawn
     first = {a.id: (list(a.initial_pos), list(a.goal_pos)) for a in agents}
     route = {}                                                     # id -> the K waypoints from its start to its goal, in flying order
     for i, (start, goal) in first.items():
@@ -62,7 +83,8 @@ def lifelong(args, agents, obstacles, pol, dubins):
             goal = list(agent.initial_pos)
             g, (s0, g0) = np.asarray(goal[:3], float), first[i]
             back = np.linalg.norm(g - np.asarray(s0[:3], float)) <= np.linalg.norm(g - np.asarray(g0[:3], float))
-        new = E.Agent(start_pos=start, goal_pos=goal, vel=[0.0, 0.0, 0.0], radius=agent.radius, pref_speed=agent.pref_speed, policy=pol, id=i)
+        new = E.Agent(start_pos=start, goal_pos=goal, vel=[0.0, 0.0, 0.0], radius=agent.radius, pref_speed=agent.pref_speed,
+                      policy=type(agent.policy) if fleet else pol, id=i)          # (a mixed fleet: the drone keeps the policy it came with)
         if K:
             new.path = [w[:] for w in (back_list if back else out_list)[i]]
         return new
@@ -97,6 +119,8 @@ def lifelong(args, agents, obstacles, pol, dubins):
 
         def leave_or_restart(agent, row):
             f = int(row['flags'])
+            if fleet:
+                line_of(agent)['collided' if f & S.FLAG_COLLISION else 'arrived' if f & S.FLAG_AT_GOAL else 'timed_out'] += 1
             return RETIRE if f & S.FLAG_AT_GOAL and not f & S.FLAG_COLLISION else next_mission(agent, row)
 
         def arrivals(step, vacant_ids):
@@ -105,7 +129,8 @@ def lifelong(args, agents, obstacles, pol, dubins):
             for i in sorted(int(x) for x in trng.permutation(vacant_ids)[:k]):
                 start, goal = first[i]
                 old = env.agents[i]
-                new = E.Agent(start_pos=start, goal_pos=goal, vel=[0.0, 0.0, 0.0], radius=old.radius, pref_speed=old.pref_speed, policy=pol, id=i)
+                kind = fleet[int(trng.integers(len(fleet)))] if fleet else pol        # (seeded: the arrival's policy is drawn from --fleet)
+                new = E.Agent(start_pos=start, goal_pos=goal, vel=[0.0, 0.0, 0.0], radius=old.radius, pref_speed=old.pref_speed, policy=kind, id=i)
                 if K:
                     new.path = [w[:] for w in out_list[i]]
                 out.append(new)
@@ -123,6 +148,8 @@ def lifelong(args, agents, obstacles, pol, dubins):
     if args.traffic is not None:
         print('traffic', args.traffic, 'arrivals/step:', stats['retired_rows'], 'drones left,', stats['admitted'], 'entered, population',
               stats['population_min'], '..', stats['population_max'], f"(mean {stats['population_mean']:.1f})")
+    for name in sorted(per_policy):
+        print(f'  {name}:', per_policy[name]['entered'], 'entered,', per_policy[name]['arrived'], 'arrived,', per_policy[name]['collided'], 'collided')
 
 
 def main():
@@ -150,6 +177,9 @@ def main():
     ap.add_argument('--traffic', type=float, default=None, metavar='RATE',
                     help='with --lifelong: a changing population -- a drone that arrives leaves the airspace (MACAEnv.retire), and a seeded '
                          'Poisson number of new drones, RATE per step on average, enters at vacant rows (with --spawn-margin only where free)')
+    ap.add_argument('--fleet', default=None, metavar='P,P,...',
+                    help='with --traffic: a mixed fleet -- every arriving drone draws its policy (seeded) from this comma-separated list of '
+                         '--policy names and brings it into whatever row is vacant (MACAEnv(attribute_slots=True)); the summary gains a line per policy')
     ap.add_argument('--device-missions', action='store_true',
                     help='with --lifelong: the ping-pong rule as a mission table per drone on the device -- a drone that ends takes its next '
                          'mission inside the step, no host call per step (MACAEnv.set_missions)')
@@ -169,6 +199,8 @@ def main():
         ap.error('--device-missions goes with --lifelong STEPS')
     if args.traffic is not None and (args.lifelong <= 0 or args.device_missions or args.traffic < 0):
         ap.error('--traffic RATE (RATE >= 0) goes with --lifelong STEPS, without --device-missions')
+    if args.fleet is not None and (args.traffic is None or not args.fleet or any(name not in POLICIES for name in args.fleet.split(','))):
+        ap.error('--fleet P,P,... (names of --policy) goes with --lifelong STEPS --traffic RATE')
     if args.waypoints < 0 or (args.waypoints and args.lifelong <= 0):
         ap.error('--waypoints K (K >= 0) goes with --lifelong STEPS')
 

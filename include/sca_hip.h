@@ -872,6 +872,61 @@ int sca_respawn_agents_gated(sca_ctx *ctx, int count, const int32_t *ids /*count
                              const double *path_points /*nullable*/, double margin, int32_t *verdict /*count*/,
                              sca_scene_clearance *probe /*count, nullable*/, int32_t *admitted /*nullable: how many*/);
 
+/* An arriving drone brings its own POLICY, SOLVER and PLANNER ATTRIBUTES.  sca_respawn_agents keeps the row's; the reference keeps policy and every
+ * solver attribute as plain fields of the Agent object (agent.py:24-41), assigned between two env.step() calls like a new start, so a row
+ * that was an ORCA3D drone with neighborDist 10 can be re-entered by a Dubins-tracked SCA drone with neighborDist 4 and another turning
+ * radius -- a mixed fleet in one airspace.
+ *   sca_respawn_agents_attrs   two arguments in front of sca_respawn_agents' arrays, which keep their order and meaning.  policy: one byte
+ *              per named row (NULL: the rows keep theirs).  attrs: sca_restart_attrs as sca_restart_scenes_attrs reads it (NULL: the rows
+ *              keep their attributes): struct_bytes and reserved by its rules; with a descriptor a NULL array stands for the CONTEXT's
+ *              value for every named row -- sca_create's sca_params value, sca_device_tracker_enable's value -- NOT what the row had.
+ *              Planner arrays are ignored for rows whose new policy is untracked.  policy == NULL && attrs == NULL is exactly
+ *              sca_respawn_agents: the same launches are enqueued.
+ *   contract   afterwards a named row is what sca_set_agents(that policy) + sca_set_agent_params(those values) + sca_set_state
+ *              (+ sca_device_tracker_enable + sca_device_tracker_set_agent_params) leave for such an agent: everything
+ *              sca_respawn_agents writes, the policy byte, the 64-byte record sca_set_agent_params derives, the row's neighborDist in
+ *              the tracker's array, the planner triple and the class byte.  Under the device tracker a row
+ *              whose NEW policy is SCA / RVO3D+Dubins takes the initial tracker record, goal_heading, vpref_mode 1 and vpref_ext 0; a row
+ *              that LEAVES those policies takes what sca_restart_scenes leaves for that transition: vpref_mode 0, vpref_ext 0, the
+ *              initial tracker record.  EVERY OTHER ROW KEEPS EVERY WORD.  A fresh context built from the merged definition is bit for
+ *              bit equal from there on; with vacant rows, the occupied rows are a context of those agents with their CURRENT policies
+ *              and attributes.  Mission tables keep their rule: a later take keeps the row's policy and attributes -- the new ones.
+ *   host side  the policy mirror, the ORCA3D-LP list (uploaded again only when a row entered or left that policy) and the lists' v_pref
+ *              bytes follow.  The tracker's classes are dealt again by sca_restart_scenes_attrs' rule over the plain context's tracked
+ *              rows (vacant rows counted: they keep their triple and class byte): more than 16 triples go to the per-agent form, 16
+ *              or fewer come back, one class goes into the scalars; a class keeps its index while a row uses it, and the whole class
+ *              array goes up again only where another row's byte moved or on first use.  The first call that brings attributes into a context without per-agent arrays allocates them and fills
+ *              every row with the context's own values, from which the rows not named compute the bits they computed before.  The
+ *              context's envelope (largest neighbor_dist, max_speed, dt_nominal) only grows, as the largest radius does: forms may
+ *              differ afterwards, values may not.
+ *   cost       ONE launch (k_respawn_attrs, a wavefront per named row) and one synchronisation, the list's and the class bytes' copies in
+ *              front of it.  The gated form: still one synchronisation; only the ADMITTED rows take anything, the classes are dealt
+ *              over what they brought, and the two copies are enqueued behind the synchronisation on the context's stream.
+ *   refusals   everything sca_respawn_agents (or its gated form) refuses, with its codes -- goal_heading == NULL is judged by the NEW
+ *              policy.  SCA_ERR_ARG: a policy byte above 5, a struct_bytes or reserved that sca_restart_scenes_attrs refuses, planner
+ *              arrays without a device tracker, a named row whose solver attributes break sca_set_agent_params' rules (the message names
+ *              the packed row), a row whose NEW policy is tracked and whose planner attributes break
+ *              sca_device_tracker_set_agent_params' rules.  A refused call changes nothing.
+ * A context that never calls these allocates nothing new and enqueues what it did.  Detect the feature by the symbols (sca_version() is
+ * unchanged). */
+int sca_respawn_agents_attrs(sca_ctx *ctx, int count, const int32_t *ids /*count*/,
+                             const uint8_t *policy /*count, nullable: the rows keep theirs*/,
+                             const sca_restart_attrs *attrs /*nullable: the rows keep their attributes*/,
+                             const double *pos /*count*3*/, const float *vel /*count*3*/,
+                             const double *heading /*count*3*/, const double *radius /*count*/, const double *pref_speed /*count*/,
+                             const double *goal /*count*3*/, const uint8_t *zaxis /*count, nullable*/, const double *max_run_dist /*count*/,
+                             const double *goal_heading /*count*3, nullable*/, const int32_t *path_offsets /*count+1, nullable*/,
+                             const double *path_points /*nullable*/);
+int sca_respawn_agents_gated_attrs(sca_ctx *ctx, int count, const int32_t *ids /*count*/,
+                             const uint8_t *policy /*count, nullable: the rows keep theirs*/,
+                             const sca_restart_attrs *attrs /*nullable: the rows keep their attributes*/,
+                             const double *pos /*count*3*/, const float *vel /*count*3*/,
+                             const double *heading /*count*3*/, const double *radius /*count*/, const double *pref_speed /*count*/,
+                             const double *goal /*count*3*/, const uint8_t *zaxis /*count, nullable*/, const double *max_run_dist /*count*/,
+                             const double *goal_heading /*count*3, nullable*/, const int32_t *path_offsets /*count+1, nullable*/,
+                             const double *path_points /*nullable*/, double margin, int32_t *verdict /*count*/,
+                             sca_scene_clearance *probe /*count, nullable*/, int32_t *admitted /*nullable: how many*/);
+
 /* Mission tables: a finished row takes its next mission INSIDE the step.  sca_respawn_agents and sca_get_finished are host calls between
  * two steps, so continuous traffic costs a synchronisation per step and sca_run_steps(k) cannot run it at all (a burst keeps stepping
  * rows that stay finished).  Here every agent row carries its upcoming missions on the device; the step's last kernel (k_mission_advance,

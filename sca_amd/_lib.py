@@ -196,6 +196,9 @@ SIGNATURES = {
     'sca_get_population': (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     'sca_probe_clearance': (C.c_int, [C.c_void_p, C.c_int, dp, dp, ip, C.POINTER(SceneClearance), C.c_int32]),
     'sca_respawn_agents_gated': (C.c_int, [C.c_void_p, C.c_int, ip, dp, fp, dp, dp, dp, dp, bp, dp, dp, ip, dp, C.c_double, ip, C.POINTER(SceneClearance), ip]),
+    'sca_respawn_agents_attrs': (C.c_int, [C.c_void_p, C.c_int, ip, bp, C.POINTER(RestartAttrs), dp, fp, dp, dp, dp, dp, bp, dp, dp, ip, dp]),
+    'sca_respawn_agents_gated_attrs': (C.c_int, [C.c_void_p, C.c_int, ip, bp, C.POINTER(RestartAttrs), dp, fp, dp, dp, dp, dp, bp, dp, dp, ip, dp, C.c_double, ip,
+                                                 C.POINTER(SceneClearance), ip]),
     'sca_set_missions': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Mission), ip, ip]),
     'sca_set_missions_paths': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Mission), ip, ip, ip, dp]),
     'sca_get_mission_paths': (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),

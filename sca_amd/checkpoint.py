@@ -187,7 +187,10 @@ def env_checkpoint(env):
     else:                                                            # slot form: lengths and rooms travel in the blob
         lists = [[list(map(float, w[:3])) for w in a._path] for a in env.agents]
     d = _prefixed('agents_', _scenes.SceneCheckpoint.define(env.agents, lists, env.obstacles))
-    d['env_options'] = np.array([int(env.neighbor_mode), int(env.device_tracker), int(env.clearance_on), int(env._path_slots), int(env._paths_on)], np.int32)
+    # (the agents above are the CURRENT ones: an attribute respawn's policies and attributes.  A sixth option only for an env with
+    # attribute_slots: every other env writes the five it always wrote)
+    d['env_options'] = np.array([int(env.neighbor_mode), int(env.device_tracker), int(env.clearance_on), int(env._path_slots), int(env._paths_on)] +
+                                ([1] if env._attr_slots else []), np.int32)
     d['env_time_cum'] = np.asarray(env._time_cum, np.float64)
     if env._missions is not None:
         ids = sorted(env._missions)
@@ -215,10 +218,11 @@ def env_from_checkpoint(cls, ckpt, device=0):
     d = ckpt.definition
     if 'env_options' not in d:
         raise ValueError('from_checkpoint: the checkpoint holds a solver-level definition (ContextCheckpoint.define), not an env -- .solver() resumes it')
-    mode, tracker, clearance, slots, paths_on = (int(x) for x in d['env_options'])
+    mode, tracker, clearance, slots, paths_on = (int(x) for x in d['env_options'][:5])
+    attr_slots = len(d['env_options']) > 5 and bool(d['env_options'][5])      # (a checkpoint from before attribute_slots holds five options)
     whole = _scenes.SceneCheckpoint(_unprefixed('agents_', d), np.zeros(0, np.uint8), 0)
     agents = whole.agents()
-    env = cls(device=device, neighbor_mode=mode, device_tracker=bool(tracker), clearance=bool(clearance), path_slots=slots)
+    env = cls(device=device, neighbor_mode=mode, device_tracker=bool(tracker), clearance=bool(clearance), path_slots=slots, attribute_slots=attr_slots)
     env.set_agents(agents, obstacles=whole.obstacles())
     if 'tables_ids' in d:
         ents = _scenes.SceneCheckpoint(_unprefixed('entries_', d), np.zeros(0, np.uint8), 0).agents()

@@ -365,6 +365,17 @@ struct sca_ctx {
     // respawning agents in place (sca_respawn_agents, sca_get_finished; sca_respawn.h): nothing of it exists until the first call
     uint8_t *rsp_host = nullptr;            // sca_respawn_agents' page-locked block (RespawnLayout of rsp_cap rows and rsp_W waypoints per row)
     int rsp_cap = 0, rsp_W = 0;
+    // ... that brings a policy or attributes (sca_respawn_agents_attrs; sca_respawn_attrs.h): nothing of it exists until the first such call
+    uint8_t *rspa_host = nullptr;           // the page-locked block of the policy bytes and AgentPar records (RespawnAttrLayout of rspa_cap rows)
+    int rspa_cap = 0;
+    std::vector<int32_t> rspa_lp[2];        // what the ORCA3D-LP list is uploaded from, by turns: a gated call's copy runs behind its synchronisation
+    int rspa_turn = 0;                      //   and is over before the call after the next touches its source (every call synchronises once)
+    std::vector<AgentPar> rspa_fill_ap;     // the first-use fill of ap_dev / ap_nd: the context's own values for every row
+    std::vector<double> rspa_fill_nd;
+    AgentPar *rspa_ap_new = nullptr;        // the first-use arrays until the call that made them has come through: they become ap_dev / ap_nd only
+    double *rspa_nd_new = nullptr;          //   behind its synchronisation, so ap_dev != nullptr always means "per-agent arrays in force"
+    std::vector<double> rspa_fill_trk[3];   // the first-use fill of the planner's per-row arrays
+    std::vector<uint8_t> rspa_cls[2];       // what the class bytes are uploaded from, by turns like rspa_lp
     uint8_t *fin_host = nullptr;            // sca_get_finished's page-locked block: the count's head, fin_cap rows behind it
     int fin_cap = 0;
     int32_t *fin_counts = nullptr;          // device [2 * tiles of max_n]: the tiles' counts, their offsets behind them
@@ -1059,6 +1070,8 @@ void sca_destroy(sca_ctx *c) {
     if (c->hs_host) { (void)hipHostFree(c->hs_host); c->hs_host = nullptr; }
     if (c->hs_dev) { (void)hipFree(c->hs_dev); c->hs_dev = nullptr; }
     if (c->rsp_host) { (void)hipHostFree(c->rsp_host); c->rsp_host = nullptr; }
+    if (c->rspa_host) { (void)hipHostFree(c->rspa_host); c->rspa_host = nullptr; }
+    if (c->rspa_ap_new) { (void)hipFree(c->rspa_ap_new); (void)hipFree(c->rspa_nd_new); c->rspa_ap_new = nullptr; c->rspa_nd_new = nullptr; }
     if (c->fin_host) { (void)hipHostFree(c->fin_host); c->fin_host = nullptr; }
     if (c->fin_counts) { (void)hipFree(c->fin_counts); c->fin_counts = nullptr; }
     if (c->vac.dev) { (void)hipFree(c->vac.dev); c->vac.dev = nullptr; }
@@ -4172,7 +4185,87 @@ static int vacancy_occupied(const sca_ctx *c) { return c->vac.on ? c->vac.m : c-
 
 // sca_respawn_agents and sca_respawn_agents_gated (gate != nullptr) behind their refusals
 struct RespawnGate { double margin; int32_t *verdict; sca_scene_clearance *probe; int32_t *admitted; };
-static int respawn_run(sca_ctx *c, const RespawnCtx &X, const RespawnArgs &A, const RespawnGate *gate);
+// what sca_respawn_agents_attrs / _gated_attrs bring beside the other arrays (null: the two entry points as they always were)
+struct RespawnBrings {
+    const uint8_t *policy = nullptr;        // [count] the call's policy bytes, null: the rows keep theirs
+    bool send_solver = false;               // the rows take AgentPar records ...
+    std::vector<AgentPar> par;              // ... [count], derived as sca_set_agent_params derives them
+    std::vector<uint8_t> merged;            // [n] the policies behind a call that writes every named row
+    bool send_planner = false;              // the rows take planner triples and class bytes ...
+    std::vector<TrackTriple> trip;          // ... [count]: the call's values, sca_device_tracker_enable's where an array is NULL
+    bool table_on = false;                  // the tracker's classes are recomputed (the call changes which triples the tracked rows use)
+};
+static int respawn_run(sca_ctx *c, const RespawnCtx &X, const RespawnArgs &A, const RespawnGate *gate, const RespawnBrings *brings = nullptr);
+// the refusals the _attrs entry points add (sca_respawn_attrs.h), and what the call brings
+static int respawn_brings(sca_ctx *c, const char *who, const RespawnCtx &X, const RespawnArgs &A, const uint8_t *policy, const sca_restart_attrs *attrs, RespawnBrings &B) {
+    const AttrDefaults D{c->P_ctx.neighbor_dist, c->P_ctx.time_step, c->P_ctx.time_horizon, c->P_ctx.max_speed, c->P_ctx.max_heading_change, c->P_ctx.dt_nominal,
+                         c->P_ctx.max_neighbors, c->trk_enable_vals[0], c->trk_enable_vals[1], c->trk_enable_vals[2]};
+    RestartAttrs RA;
+    const RespawnAttrCheck k = respawn_attrs_check(X, A, policy, attrs, D, B.merged, &RA);
+    if (int r = respawn_refuse(c, who, k.base.fault, k.base.entry)) return r;
+    const std::string w = std::string(who), at = std::to_string(k.entry);
+    switch (k.fault) {
+    case RSA_OK: break;
+    case RSA_BAD_POLICY: c->err = w + ": row " + at + " has a policy byte above SCA_POLICY_RVO3D_DUBINS"; break;
+    case RSA_STRUCT: c->err = w + ": attrs->struct_bytes = " + std::to_string(attrs->struct_bytes) + " is not a size of sca_restart_attrs (" +
+                              std::to_string(RESTART_ATTR_HEAD_BYTES) + " .. " + std::to_string(sizeof(sca_restart_attrs)) + ", whole pointers)"; break;
+    case RSA_RESERVED: c->err = w + ": attrs->reserved must be 0"; break;
+    case RSA_NO_TRACKER: c->err = w + ": turning_radius / pitch_lo / pitch_hi without a device tracker (sca_device_tracker_enable)"; break;
+    case RSA_SOLVER: c->err = w + ": row " + at + " has an attribute out of range (see sca_params)"; break;
+    default: c->err = w + ": row " + at + " has a turning radius / pitch limits out of range (R > 0, pitch_lo < pitch_hi)";
+    }
+    if (k.fault != RSA_OK) return respawn_attrs_error_code(k.fault);
+    B.policy = policy;
+    // (as under sca_restart_scenes_attrs: a descriptor of NULL arrays in a context without per-agent arrays has nothing to write -- every
+    // row computes from Params, which ARE the context's values)
+    B.send_solver = attrs && (RA.solver() || c->d.ap);
+    if (B.send_solver) {
+        const SolverArrays S{RA.neighbor_dist, RA.max_neighbors, RA.time_step, RA.time_horizon, RA.max_speed, RA.max_heading_change, RA.dt_nominal};
+        ThrCache thr_cache;
+        B.par.resize((size_t)A.count);
+        for (int r = 0; r < A.count; r++) B.par[(size_t)r] = agent_par_row(c->P_ctx, S, r, thr_cache);
+    }
+    // (as under sca_restart_scenes_attrs) planner attributes travel when the call names any, or when the tracker carries per-row arrays
+    // already -- a NULL array then means sca_device_tracker_enable's value, which the rows must take; and the classes are dealt again
+    // whenever per-row triples are in force and the call may change which of them the tracked rows use
+    const bool per_row = c->trk_on && (c->trk_attr_on || c->trk_view.R_pa);
+    B.send_planner = attrs && c->trk_on && (RA.planner() || per_row);
+    B.table_on = B.send_planner || (per_row && policy);
+    if (B.send_planner) {
+        B.trip.resize((size_t)A.count);
+        for (int r = 0; r < A.count; r++)
+            B.trip[(size_t)r] = TrackTriple{RA.turning_radius ? RA.turning_radius[r] : D.turning_radius, RA.pitch_lo ? RA.pitch_lo[r] : D.pitch_lo,
+                                            RA.pitch_hi ? RA.pitch_hi[r] : D.pitch_hi};
+    }
+    return 0;
+}
+int sca_respawn_agents_attrs(sca_ctx *c, int count, const int32_t *ids, const uint8_t *policy, const sca_restart_attrs *attrs, const double *pos, const float *vel,
+                             const double *heading, const double *radius, const double *pref_speed, const double *goal, const uint8_t *zaxis,
+                             const double *max_run_dist, const double *goal_heading, const int32_t *path_offsets, const double *path_points) {
+    if (!policy && !attrs) return sca_respawn_agents(c, count, ids, pos, vel, heading, radius, pref_speed, goal, zaxis, max_run_dist, goal_heading, path_offsets, path_points);
+    API_ENTER(c);
+    const RespawnCtx X = respawn_ctx(c);
+    const RespawnArgs A{count, ids, pos, vel, heading, radius, pref_speed, goal, zaxis, max_run_dist, goal_heading, path_offsets, path_points};
+    RespawnBrings B;
+    if (int r = respawn_brings(c, "sca_respawn_agents_attrs", X, A, policy, attrs, B)) return r;
+    return respawn_run(c, X, A, nullptr, &B);
+}
+int sca_respawn_agents_gated_attrs(sca_ctx *c, int count, const int32_t *ids, const uint8_t *policy, const sca_restart_attrs *attrs, const double *pos,
+                                   const float *vel, const double *heading, const double *radius, const double *pref_speed, const double *goal,
+                                   const uint8_t *zaxis, const double *max_run_dist, const double *goal_heading, const int32_t *path_offsets,
+                                   const double *path_points, double margin, int32_t *verdict, sca_scene_clearance *probe, int32_t *admitted) {
+    if (!policy && !attrs)
+        return sca_respawn_agents_gated(c, count, ids, pos, vel, heading, radius, pref_speed, goal, zaxis, max_run_dist, goal_heading, path_offsets, path_points, margin,
+                                        verdict, probe, admitted);
+    API_ENTER(c);
+    const RespawnCtx X = respawn_ctx(c);
+    const RespawnArgs A{count, ids, pos, vel, heading, radius, pref_speed, goal, zaxis, max_run_dist, goal_heading, path_offsets, path_points};
+    RespawnBrings B;
+    if (int r = respawn_brings(c, "sca_respawn_agents_gated_attrs", X, A, policy, attrs, B)) return r;
+    if (int r = spawn_refuse(c, "sca_respawn_agents_gated_attrs", spawn_gate_check(margin, verdict != nullptr), -1)) return r;
+    const RespawnGate gate{margin, verdict, probe, admitted};
+    return respawn_run(c, X, A, &gate, &B);
+}
 int sca_respawn_agents(sca_ctx *c, int count, const int32_t *ids, const double *pos, const float *vel, const double *heading, const double *radius,
                        const double *pref_speed, const double *goal, const uint8_t *zaxis, const double *max_run_dist, const double *goal_heading,
                        const int32_t *path_offsets, const double *path_points) {
@@ -4196,7 +4289,10 @@ int sca_respawn_agents_gated(sca_ctx *c, int count, const int32_t *ids, const do
     const RespawnGate gate{margin, verdict, probe, admitted};
     return respawn_run(c, X, A, &gate);
 }
-static int respawn_run(sca_ctx *c, const RespawnCtx &X, const RespawnArgs &A, const RespawnGate *gate) {
+static int respawn_run(sca_ctx *c, const RespawnCtx &X0, const RespawnArgs &A, const RespawnGate *gate, const RespawnBrings *brings) {
+    // (a call that brings policies: the rows' bits -- tracked, mode reset -- and their lists' v_pref bytes follow the NEW policies)
+    RespawnCtx X = X0;
+    if (brings && brings->policy) X.policy_now = brings->merged.data();
     const int count = A.count;
     const int32_t *ids = A.ids, *path_offsets = A.path_offsets;
     const double *pos = A.pos, *heading = A.heading, *radius = A.radius, *pref_speed = A.pref_speed;
@@ -4214,7 +4310,68 @@ static int respawn_run(sca_ctx *c, const RespawnCtx &X, const RespawnArgs &A, co
     const RespawnLayout L = respawn_layout(c->rsp_cap, c->rsp_W);
     const bool slots = X.path_W > 0;
     if (int r = missions_path_mirrors(c)) return r;                    // (tables with lists: the named rows' mode bit follows the lists they hold NOW)
-    const uint32_t has = respawn_pack(c->rsp_host, L, X, A, slots ? c->h_path_vpref.data() : nullptr);
+    uint32_t has = respawn_pack(c->rsp_host, L, X, A, slots ? c->h_path_vpref.data() : nullptr);
+    // the policy bytes and the AgentPar records in a block of their own, which exists from the first call that brings any
+    RespawnAttrLayout AL{};
+    struct { std::vector<TrackTriple> trip, old_trip; std::vector<uint8_t> cls, old_cls, row_cls; ClassTable table, old_table; ClassUpdate cu{0, false, false}; bool first = false; } T;
+    const int turn = c->rspa_turn;                                     // this call's upload sources (the ORCA3D-LP list, the class bytes)
+    if (brings) c->rspa_turn ^= 1;
+    if (brings) {
+        if (count > c->rspa_cap) {
+            const int cap = std::max(count, std::min(c->max_n, std::max(1024, 2 * c->rspa_cap)));
+            uint8_t *blk = nullptr;
+            CHK(c, hipHostMalloc((void **)&blk, (size_t)respawn_attrs_layout(cap).total, hipHostMallocMapped | hipHostMallocCoherent));
+            if (c->rspa_host) (void)hipHostFree(c->rspa_host);        // (every call ends with its synchronisation: no launch still reads it)
+            c->rspa_host = blk; c->rspa_cap = cap;
+        }
+        AL = respawn_attrs_layout(c->rspa_cap);
+        if (brings->table_on) {
+            // The tracker's classes behind a call that writes every named row (scene_class_table's rule over the plain context, every row
+            // counted: a vacant row keeps its triple and its class byte, and a plain respawn that admits it later deals no classes).  The
+            // named rows' bytes travel with the call; where another row's byte moved, or on first use, the whole array goes up.
+            const TrackTriple def{c->trk_enable_vals[0], c->trk_enable_vals[1], c->trk_enable_vals[2]};
+            T.trip = c->h_trk_trip; T.cls = c->h_trk_cls; T.table = c->trk_table;
+            T.trip.resize((size_t)c->n, def); T.cls.resize((size_t)c->n, 0);
+            T.first = !c->trk_attr_on;
+            if (T.first) {                                             // the four per-row arrays exist from here on and are current for EVERY row
+                T.table.many = true;                                   // (whatever classes an earlier call dealt, the table starts afresh)
+                if (!c->trk_R_pa) { CHK(c, hipMalloc((void **)&c->trk_R_pa, sizeof(double) * (size_t)c->max_n)); CHK(c, hipMalloc((void **)&c->trk_cls, (size_t)c->max_n)); }
+                if (!c->trk_plo_pa) {
+                    CHK(c, hipMalloc((void **)&c->trk_plo_pa, sizeof(double) * (size_t)c->max_n));
+                    CHK(c, hipMalloc((void **)&c->trk_phi_pa, sizeof(double) * (size_t)c->max_n));
+                }
+                for (auto &v : c->rspa_fill_trk) v.resize((size_t)c->n);
+                for (size_t a = 0; a < (size_t)c->n; a++) { c->rspa_fill_trk[0][a] = T.trip[a].R; c->rspa_fill_trk[1][a] = T.trip[a].lo; c->rspa_fill_trk[2][a] = T.trip[a].hi; }
+                CHK(c, hipMemcpyAsync(c->trk_R_pa, c->rspa_fill_trk[0].data(), sizeof(double) * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
+                CHK(c, hipMemcpyAsync(c->trk_plo_pa, c->rspa_fill_trk[1].data(), sizeof(double) * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
+                CHK(c, hipMemcpyAsync(c->trk_phi_pa, c->rspa_fill_trk[2].data(), sizeof(double) * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
+            }
+            T.old_trip = T.trip; T.old_cls = T.cls; T.old_table = T.table;
+            std::vector<uint8_t> travels((size_t)c->n, 0);
+            if (brings->send_planner) for (int r = 0; r < count; r++) { T.trip[(size_t)ids[r]] = brings->trip[(size_t)r]; travels[(size_t)ids[r]] = 1; }
+            T.cu = plain_class_table(T.table, c->n, nullptr, X.policy_now, T.trip.data(), T.cls.data(), brings->send_planner ? travels.data() : nullptr);
+            if (brings->send_planner) { T.row_cls.resize((size_t)count); for (int r = 0; r < count; r++) T.row_cls[(size_t)r] = T.cls[(size_t)ids[r]]; }
+        }
+        has |= respawn_attrs_pack(c->rspa_host, AL, count, brings->policy, brings->send_solver ? brings->par.data() : nullptr,
+                                  brings->send_planner ? brings->trip.data() : nullptr, brings->send_planner ? T.row_cls.data() : nullptr);
+        if (brings->policy) respawn_attrs_bits(c->rsp_host + L.off[RSB_BITS], count, ids, c->h_policy.data(), brings->merged.data(), X.tracker_on);
+        if (brings->send_solver && !c->d.ap) {
+            // The first attributes in a context without per-agent arrays: from here on every agent reads d.ap[a] instead of Params, so every
+            // row gets the record Params stands for -- range_sq and cos_heading_thr as sca_create derived them -- in front of the launch that
+            // overwrites the named rows: the others compute the bits they computed before.  d.ap points at the array behind the synchronisation.
+            ThrCache none;
+            const AgentPar a0 = agent_par_row(c->P_ctx, SolverArrays{}, 0, none);
+            c->rspa_fill_ap.assign((size_t)c->max_n, a0); c->rspa_fill_nd.assign((size_t)c->max_n, a0.neighbor_dist);
+            if (!c->rspa_ap_new) {
+                CHK(c, hipMalloc((void **)&c->rspa_ap_new, sizeof(AgentPar) * (size_t)c->max_n));
+                if (hipMalloc((void **)&c->rspa_nd_new, sizeof(double) * (size_t)c->max_n) != hipSuccess) {
+                    (void)hipFree(c->rspa_ap_new); c->rspa_ap_new = nullptr; c->err = "sca_respawn_agents_attrs: no device memory for the per-agent arrays"; return SCA_ERR_HIP;
+                }
+            }
+            CHK(c, hipMemcpyAsync(c->rspa_ap_new, c->rspa_fill_ap.data(), sizeof(AgentPar) * (size_t)c->max_n, hipMemcpyHostToDevice, c->stream));
+            CHK(c, hipMemcpyAsync(c->rspa_nd_new, c->rspa_fill_nd.data(), sizeof(double) * (size_t)c->max_n, hipMemcpyHostToDevice, c->stream));
+        }
+    }
     RespawnDev d{};
     d.rec = c->d.rec; d.heading = c->d.heading; d.goal = c->d.goal; d.pref_speed = c->d.pref_speed; d.max_run_dist = c->d.max_run_dist;
     d.total_dist = c->d.total_dist; d.vpref_ext = c->d.vpref_ext; d.step_num = c->d.step_num; d.status = c->d.status; d.nbr_n = c->d.nbr_n;
@@ -4247,9 +4404,30 @@ static int respawn_run(sca_ctx *c, const RespawnCtx &X, const RespawnArgs &A, co
         va.verdict = gate ? (const int32_t *)sd.verdict : nullptr;
         if (int r = vacancy_compact_enqueue(c, va, VAC_ADMIT, c->d.aperm, vv.m, nullptr, c->n, vacancy_scratch(c).head)) return r;
     }
-    hipLaunchKernelGGL(k_respawn, dim3((count + RESPAWN_WAVES - 1) / RESPAWN_WAVES), dim3(RESPAWN_WAVES * 64), 0, c->stream, d, (const uint8_t *)c->rsp_host, L, has, count,
-                       (const int32_t *)(gate ? sd.verdict : nullptr));
+    if (!brings)
+        hipLaunchKernelGGL(k_respawn, dim3((count + RESPAWN_WAVES - 1) / RESPAWN_WAVES), dim3(RESPAWN_WAVES * 64), 0, c->stream, d, (const uint8_t *)c->rsp_host, L, has, count,
+                           (const int32_t *)(gate ? sd.verdict : nullptr));
+    else
+        hipLaunchKernelGGL(k_respawn_attrs, dim3((count + RESPAWN_WAVES - 1) / RESPAWN_WAVES), dim3(RESPAWN_WAVES * 64), 0, c->stream, d,
+                           RespawnAttrDev{c->d.policy, c->d.ap ? c->ap_dev : c->rspa_ap_new, c->d.ap ? c->ap_nd : c->rspa_nd_new, c->trk_R_pa, c->trk_plo_pa, c->trk_phi_pa,
+                                          c->trk_cls}, (const uint8_t *)c->rsp_host, L, (const uint8_t *)c->rspa_host, AL, has, count,
+                           (const int32_t *)(gate ? sd.verdict : nullptr));
     CHK(c, hipGetLastError());
+    // The ORCA3D-LP list (ascending ids), uploaded again only where a row entered or left that policy.  An ungated call writes every named
+    // row, so the list goes up in front of the synchronisation; a gated call learns the verdicts there and enqueues it behind (below).
+    bool lp_moves = false;
+    if (brings && brings->policy)
+        for (int r = 0; r < count && !lp_moves; r++) lp_moves = (brings->policy[r] == SCA_POLICY_ORCA3D_LP) != (c->h_policy[(size_t)ids[r]] == SCA_POLICY_ORCA3D_LP);
+    std::vector<int32_t> &lp_up = c->rspa_lp[turn];
+    std::vector<uint8_t> &cls_up = c->rspa_cls[turn];
+    if (brings && brings->table_on && !gate && !T.cu.many && (T.cu.moved || T.first)) {       // (the per-agent form reads no class byte)
+        cls_up = T.cls;
+        CHK(c, hipMemcpyAsync(c->trk_cls, cls_up.data(), (size_t)c->n, hipMemcpyHostToDevice, c->stream));
+    }
+    if (lp_moves && !gate) {
+        respawn_lp_list(brings->merged.data(), c->n, c->h_lp_list, lp_up);
+        if (!lp_up.empty()) CHK(c, hipMemcpyAsync(c->lp_list, lp_up.data(), sizeof(int32_t) * lp_up.size(), hipMemcpyHostToDevice, c->stream));
+    }
     if (vac_named) {                                                   // the rows that are still vacant, ascending, behind the admitted ones
         const VacScratch vs = vacancy_scratch(c);
         if (int r = vacancy_compact_enqueue(c, vv, VAC_TAIL, c->d.aperm, vv.m, vs.head, c->n, vs.head + 1)) return r;
@@ -4265,13 +4443,30 @@ static int respawn_run(sca_ctx *c, const RespawnCtx &X, const RespawnArgs &A, co
         std::memcpy(gate->verdict, verdict, sizeof(int32_t) * (size_t)count);
         if (gate->probe) std::memcpy(gate->probe, c->spn_host + SL.off[SPB_OUT], sizeof(sca_scene_clearance) * (size_t)count);
         if (gate->admitted) *gate->admitted = in;
-        if (in == 0) return 0;                                         // nobody admitted: nothing has changed, on the device or here
+        if (in == 0) {                                                 // nobody admitted: nothing has changed, on the device or here
+            return 0;                                                  // (first-use arrays this call made wait, unused, for the next call that brings attributes)
+        }
+    }
+    if (brings && brings->send_solver && !c->d.ap) {                   // first use: every row holds the context's values or, named and admitted, its own
+        c->ap_dev = c->rspa_ap_new; c->ap_nd = c->rspa_nd_new; c->rspa_ap_new = nullptr; c->rspa_nd_new = nullptr;
+        c->d.ap = c->ap_dev;
+        if (c->trk_on) c->trk_view.nd_per_agent = c->ap_nd;
     }
     // the device has the new missions: the host mirrors follow the rows that were written (a refused call has left them alone)
     const HostLayout HL = host_state_layout(c->n);
     for (int r = 0; r < count; r++) {
         if (verdict && verdict[r] != SCA_SPAWN_ADMITTED) continue;
         const int a = ids[r];
+        if (brings && brings->policy) c->h_policy[(size_t)a] = brings->policy[r];
+        if (brings && brings->send_solver) {
+            // The context's Params are the ENVELOPE of the agents' own while per-agent attributes are in force, and like max_radius it only
+            // grows under respawns.  Every kernel reads d.ap[a] for these fields; the envelope sizes the grid's cells, feeds SCA_NBR_AUTO's
+            // `fits`, the collision reach and the clearance descent's bound -- conservative filters, no values.
+            const AgentPar &p = brings->par[(size_t)r];
+            if (p.neighbor_dist > c->P.neighbor_dist) { c->P.neighbor_dist = p.neighbor_dist; c->P.range_sq = sca_gm::g_pow2(p.neighbor_dist); c->grid.inv_cell = grid_inv_cell(p.neighbor_dist); }
+            c->P.max_speed = std::max(c->P.max_speed, p.max_speed);
+            c->P.dt_nominal = std::max(c->P.dt_nominal, p.dt_nominal);
+        }
         if (vac_named && c->vac.h[(size_t)a]) { c->vac.h[(size_t)a] = 0; c->vac.m++; }   // admitted
         c->h_rec[a].radius = radius[r];
         c->max_radius = std::max(c->max_radius, radius[r]);           // the envelope only grows (conservative filters, as under the restarts)
@@ -4290,6 +4485,34 @@ static int respawn_run(sca_ctx *c, const RespawnCtx &X, const RespawnArgs &A, co
             ((double *)(b + HL.off[HS_TOTAL_DIST]))[a] = 0.0;
             ((int32_t *)(b + HL.off[HS_STEP_NUM]))[a] = 0;
         }
+    }
+    if (brings && brings->table_on) {
+        if (gate) {
+            // gated: the classes over what the ADMITTED rows brought -- dealt again from the table as it stood, the whole class array
+            // enqueued behind the synchronisation on the context's stream (the kernel wrote the admitted rows' triples itself)
+            T.trip = T.old_trip; T.cls = T.old_cls; T.table = T.old_table;
+            if (brings->send_planner) for (int r = 0; r < count; r++) if (verdict[r] == SCA_SPAWN_ADMITTED) T.trip[(size_t)ids[r]] = brings->trip[(size_t)r];
+            T.cu = plain_class_table(T.table, c->n, nullptr, c->h_policy.data(), T.trip.data(), T.cls.data(), nullptr);
+            if (!T.cu.many) {
+                cls_up = T.cls;
+                CHK(c, hipMemcpyAsync(c->trk_cls, cls_up.data(), (size_t)c->n, hipMemcpyHostToDevice, c->stream));
+            }
+        }
+        c->h_trk_trip.swap(T.trip); c->h_trk_cls.swap(T.cls); c->trk_table = T.table; c->trk_attr_on = true;
+        std::vector<std::array<double, 3>> classes;                    // by index: one the table does not use holds NaN
+        for (int q = 0; q < TRK_CLASS_CAP && !T.cu.many; q++)
+            if (T.table.users[q] > 0) {
+                classes.resize((size_t)q + 1, std::array<double, 3>{std::nan(""), 0.0, 0.0});
+                classes[q] = {T.table.val[q].R, T.table.val[q].lo, T.table.val[q].hi};
+            }
+        tracker_view_apply(c, T.cu.many, classes);
+    }
+    if (lp_moves) {
+        // gated: the list over the ADMITTED rows' new policies, enqueued behind the synchronisation on the context's stream -- the next pass
+        // runs there behind it; its source is a member of the context, which no call touches before another synchronisation has passed
+        if (gate && respawn_lp_list(c->h_policy.data(), c->n, c->h_lp_list, lp_up) && !lp_up.empty())
+            CHK(c, hipMemcpyAsync(c->lp_list, lp_up.data(), sizeof(int32_t) * lp_up.size(), hipMemcpyHostToDevice, c->stream));
+        c->h_lp_list = lp_up;
     }
     c->h_pos_valid = false; c->near_valid = false;
     if (c->vac.on && c->vac.m == c->n) c->vac.on = false;              // every row is occupied again: whatever vacancy refused works again

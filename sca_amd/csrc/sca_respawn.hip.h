@@ -4,6 +4,7 @@
 #include "sca_kernels.hip.h"
 #include "sca_scenes.hip.h"
 #include "sca_respawn.h"
+#include "sca_respawn_attrs.h"
 
 namespace sca {
 
@@ -56,6 +57,41 @@ __global__ __launch_bounds__(RESPAWN_WAVES * 64) void k_respawn(RespawnDev d, co
     if (lane == 0 && w.done_delta) atomicAdd(&d.done_count[(a & 255) * 32], w.done_delta);
     respawn_write_row(d, a, lane, w, RespawnBlockSrc{blk, L, r});      // (sca_respawn.h: the row write k_mission_advance shares)
     if (w.path_len > 0 && d.path_pts)                                // the row's list into its own room
+        respawn_write_list(d.path_pts, d.W, a, lane, (const double *)(blk + L.off[RSB_PATH_PTS]) + 3 * (int64_t)first, w.path_len);
+}
+
+// ---- a respawn that brings the agent's own policy and attributes (sca_respawn_agents_attrs, sca_respawn_agents_gated_attrs) ---------------
+// k_respawn's launch shape and row rule (the same shared functions, so that the two cannot drift apart), and beside them, from a second
+// page-locked block (RespawnAttrLayout, sca_respawn_attrs.h): the row's policy byte, its 64-byte AgentPar record as four 16-byte pieces by
+// lanes 0 .. 3, its neighborDist in the tracker's array, its planner triple by lanes 0 .. 2 and its class byte, and for a row that
+// leaves the tracked policies under the device tracker what k_scene_restart leaves there (vpref_ext 0, the initial AgentTrack; vpref_mode 0 by RSP_BIT_MODE_RESET).  Plain vector stores; no LDS, no
+// scratch, and the done_count stripe stays the one atomic.  A kernel of its own rather than a nullable argument of k_respawn: that kernel,
+// and with it every context that never brings attributes, stays instruction for instruction what it was.
+struct RespawnAttrDev {
+    uint8_t *policy;                // [n] DeviceView::policy
+    AgentPar *ap;                   // [n] DeviceView::ap
+    double *ap_nd;                  // [n] TrackView::nd_per_agent
+    double *trk_R, *trk_plo, *trk_phi;   // [n] TrackView::R_pa / plo_pa / phi_pa (read only with RESPAWN_HAS_PLANNER)
+    uint8_t *trk_cls;               // [n] TrackView::cls
+};
+__global__ __launch_bounds__(RESPAWN_WAVES * 64) void k_respawn_attrs(RespawnDev d, RespawnAttrDev at, const uint8_t *blk, RespawnLayout L, const uint8_t *ablk,
+                                                                      RespawnAttrLayout AL, uint32_t has, int count, const int32_t *verdict) {
+    const int lane = (int)threadIdx.x & 63;
+    const int r = (int)blockIdx.x * RESPAWN_WAVES + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);     // wave-uniform
+    if (r >= count) return;
+    if (verdict && verdict[r] != 0) return;                            // a refused row keeps every word, policy and attributes included
+    const int a = ((const int32_t *)(blk + L.off[RSB_IDS]))[r];
+    if (a < 0 || a >= d.n) return;                                     // (the host has checked the ids: never taken)
+    const bool lists = (has & RESPAWN_HAS_PATHS) != 0;
+    const int32_t *poff = (const int32_t *)(blk + L.off[RSB_PATH_OFF]);
+    const int32_t first = lists ? poff[r] : 0, len = lists ? poff[r + 1] - first : 0;
+    const uint32_t old_flags = d.rec[a].flags;
+    const uint8_t bits = (blk + L.off[RSB_BITS])[r];
+    const RespawnRow w = respawn_row(bits, old_flags, has, len);
+    if (lane == 0 && w.done_delta) atomicAdd(&d.done_count[(a & 255) * 32], w.done_delta);
+    respawn_write_row(d, a, lane, w, RespawnBlockSrc{blk, L, r});
+    respawn_attrs_write_row(d, at, a, lane, bits, has, RespawnAttrSrc{ablk, AL, r});
+    if (w.path_len > 0 && d.path_pts)
         respawn_write_list(d.path_pts, d.W, a, lane, (const double *)(blk + L.off[RSB_PATH_PTS]) + 3 * (int64_t)first, w.path_len);
 }
 

@@ -399,7 +399,8 @@ class _FlatAgents:
         # the first tracked agent's planner attributes become the tracker's defaults, and where the tracked agents differ every agent's own go
         # over (classes of equal values on the device).  _trk_*: what a later agent of a slot is held against (SceneBatch.restart)
         self._trk_on, self._trk_first, self._trk_trip = False, None, None
-        if self.device_tracker and self._ext.any():
+        # (attribute_slots: a tracked drone may arrive later in a fleet that starts without one -- the tracker stands from the start)
+        if self.device_tracker and (self._ext.any() or getattr(self, '_attr_slots', False)):
             trip = [_planner_triple(a) for a in flat]
             first = trip[int(np.argmax(self._ext))]
             sol.device_tracker_enable(goal6[:, 3:6], turning_radius=first[0], pitchlims=(first[1], first[2]))
@@ -496,8 +497,10 @@ class _FlatAgents:
 
 class MACAEnv(_FlatAgents):
     def __init__(self, v_pref_fn=None, device=0, neighbor_mode=S.NBR_KDTREE, history_capacity=0, device_tracker=False, clearance=False,
-                 path_slots=0):
+                 path_slots=0, attribute_slots=False):
         self.agents = None
+        self._attr_slots = bool(attribute_slots)       # respawn() takes agents whose policy or solver attributes differ from the row's
+                                                       # (sca_respawn_agents_attrs; SceneBatch's name for the same thing)
         self._path_slots = int(path_slots)             # W > 0: the waypoint lists live in slot form (sca_set_path_slots), room for W per agent --
                                                        # what respawn() needs to give one agent a new list while the others keep theirs
         self.clearance_on = bool(clearance)            # every step also keeps each agent's closest approach (sca_clearance_enable): env.clearance
@@ -595,6 +598,10 @@ class MACAEnv(_FlatAgents):
         env.step() calls.  Start, goal, velocity, radius, pref_speed, max_run_dist, goal heading, path and the z-axis flag are read off
         the agent as set_agents reads them; the row keeps its policy and its per-agent attributes, so an agent whose policy or
         attributes differ from the row's is a ValueError, raised before any device call.  A path needs MACAEnv(path_slots=W).
+        MACAEnv(attribute_slots=True): the arriving agent brings its own policy, solver attributes and, under the device tracker, its
+        turning_radius / pitchlims (sca_respawn_agents_attrs) -- an ORCA3D row can be re-entered by a Dubins-tracked SCA drone with
+        another neighborDist and turning radius; env.agents[i], policy_ids, per_agent_attributes and the v_pref and planner mirrors
+        follow the admitted agents.
         margin (None: no gate, returns None): only the agents whose start is free by `margin` metres are admitted
         (sca_respawn_agents_gated: clear of every other agent where it stands now, of every obstacle, and of the admitted agents earlier
         in `agents`); they replace their rows and are returned as a list, `last_spawn` holds (verdict, probe) of the call; a refused
@@ -612,14 +619,16 @@ class MACAEnv(_FlatAgents):
             raise ValueError('respawn: agent.id names a row of this env, 0 .. %d, and no row twice' % (n - 1))
         for a in agents:
             old = self.agents[a.id]
-            if a.policy.policy_id != old.policy.policy_id:
-                raise ValueError(f'respawn: agent {a.id} has policy {type(a.policy).__name__}, the row runs {type(old.policy).__name__} (a row keeps its policy)')
-            for attr, conv in _ATTRS.values():
-                if conv(getattr(a, attr)) != conv(getattr(old, attr)):
-                    raise ValueError(f'respawn: agent {a.id} has {attr} = {getattr(a, attr)}, the row has {getattr(old, attr)} (a row keeps its attributes)')
-            if self._trk_on and self._ext[a.id] and _planner_triple(a) != self._planner_of(a.id):
+            ext = bool(a.policy.needs_external_vpref) if self._attr_slots else bool(self._ext[a.id])
+            if not self._attr_slots:
+                if a.policy.policy_id != old.policy.policy_id:
+                    raise ValueError(f'respawn: agent {a.id} has policy {type(a.policy).__name__}, the row runs {type(old.policy).__name__} (a row keeps its policy)')
+                for attr, conv in _ATTRS.values():
+                    if conv(getattr(a, attr)) != conv(getattr(old, attr)):
+                        raise ValueError(f'respawn: agent {a.id} has {attr} = {getattr(a, attr)}, the row has {getattr(old, attr)} (a row keeps its attributes)')
+            if not self._attr_slots and self._trk_on and ext and _planner_triple(a) != self._planner_of(a.id):
                 raise ValueError(f'respawn: agent {a.id} has turning_radius / pitchlims {_planner_triple(a)}, the row has {self._planner_of(a.id)}')
-            if self.v_pref_fn is not None and self._ext[a.id]:
+            if self.v_pref_fn is not None and ext:
                 raise ValueError(f'respawn: agent {a.id} takes v_pref from the host-side v_pref_fn, whose per-agent state the env cannot reset '
                                  '(use MACAEnv(device_tracker=True))')
             if len(a._path) > self._path_slots:
@@ -635,7 +644,7 @@ class MACAEnv(_FlatAgents):
         lists = [[list(map(float, w[:3])) for w in a._path] for a in agents] if self._paths_on else None
         got = self.solver.respawn(ids, [a._pos for a in agents], [a._vel for a in agents], [a._heading for a in agents], [a.radius for a in agents],
                                   [a.pref_speed for a in agents], goal6[:, :3], [a.max_run_dist for a in agents], zaxis=S.zaxis_flags(start, goal6),
-                                  goal_heading=goal6[:, 3:6] if self._trk_on else None, paths=lists, margin=margin)
+                                  goal_heading=goal6[:, 3:6] if self._trk_on else None, paths=lists, margin=margin, **self._brings(agents))
         if margin is not None:
             self.last_spawn = got
             admitted = got[0] == S.SPAWN_ADMITTED
@@ -650,6 +659,16 @@ class MACAEnv(_FlatAgents):
             self.goal[a.id] = a.goal_global_frame
             self._mission_pending.pop(a.id, None)                # (a mission gate: the row's pending mission is gone with this respawn)
             self._path_assigned.discard(a.id)
+            if self._attr_slots:                                 # the mirrors follow the admitted agents only
+                self.policy_ids[a.id] = a.policy.policy_id
+                self._ext[a.id] = bool(a.policy.needs_external_vpref)
+                if self._trk_on and (self._trk_trip is not None or (self._ext[a.id] and _planner_triple(a) != self._trk_first)):
+                    if self._trk_trip is None:
+                        self._trk_trip = [self._trk_first] * len(self.agents)
+                    self._trk_trip[a.id] = _planner_triple(a)
+        if self._attr_slots:
+            differ = [name for name, (attr, conv) in _ATTRS.items() if len({conv(getattr(b, attr)) for b in self.agents}) > 1]
+            self.per_agent_attributes = sorted(differ + (['turning_radius / pitchlims'] if self._trk_trip is not None else []))
         _bind(agents, self)
         self._active += int(was_done.sum())
         self._stale = True
@@ -657,6 +676,17 @@ class MACAEnv(_FlatAgents):
         self._nbr_cache = None
         self._vpref_cache = None
         return None if margin is None else agents
+
+    def _brings(self, agents):
+        """what respawn() hands BatchedSolver.respawn beside the missions: nothing, or with attribute_slots the agents' policies and a full
+        row of solver attributes each and, under the device tracker, of planner attributes"""
+        if not self._attr_slots:
+            return {}
+        attrs = {name: [conv(getattr(a, attr)) for a in agents] for name, (attr, conv) in _ATTRS.items()}
+        if self._trk_on:
+            trip = [_planner_triple(a) for a in agents]
+            attrs.update(turning_radius=[t[0] for t in trip], pitch_lo=[t[1] for t in trip], pitch_hi=[t[2] for t in trip])
+        return dict(policy=[a.policy.policy_id for a in agents], attrs=attrs)
 
     def finished(self, capacity=None):
         """The rows that carry any of at-goal / collision / timeout, ascending ids, compacted on the device (sca_get_finished): a

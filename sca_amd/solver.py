@@ -505,7 +505,8 @@ class BatchedSolver:
         return out[:max(count, 0)]
 
     # ---- respawning agents in place (sca_respawn_agents / sca_get_finished) ----------------------------------------------------
-    def respawn(self, ids, pos, vel, heading, radius, pref_speed, goal, max_run_dist, zaxis=None, goal_heading=None, paths=None, margin=None):
+    def respawn(self, ids, pos, vel, heading, radius, pref_speed, goal, max_run_dist, zaxis=None, goal_heading=None, paths=None, margin=None,
+                policy=None, attrs=None):
         """New missions for the rows `ids` (any order, no repeats) while every other row keeps every word it had (sca_respawn_agents).
         margin (None: no gate, returns None): only the rows whose start is free are respawned (sca_respawn_agents_gated; the admission rule
         is include/sca_hip.h's) and the call returns (verdict, probe): an int32 word per named row -- SPAWN_ADMITTED 0, SPAWN_BLOCKED_AGENT 1,
@@ -515,7 +516,11 @@ class BatchedSolver:
         device_tracker_enable) leave for an agent with these values; it keeps its policy and its per-agent attributes.  zaxis None: the
         rows keep theirs.  goal_heading: needed when a named row is tracked by the device tracker.  paths (the lists in slot form,
         set_path_slots): one list of [x, y, z] waypoints per named row; None: the named rows' lists become empty.  Only between two
-        steps; one launch and one synchronisation however many rows are named."""
+        steps; one launch and one synchronisation however many rows are named.
+        policy (one byte per named row) / attrs (a dict of set_agent_params' names, one value per named row or a scalar): the arriving
+        agents' own policy and solver attributes (sca_respawn_agents_attrs / _gated_attrs).  None: the rows keep theirs; with a dict, a name
+        that is missing or None stands for the CONTEXT's value for every named row, not for what the row had.  The planner's names
+        (turning_radius, pitch_lo, pitch_hi) need the device tracker; they are read for the rows whose new policy is tracked."""
         ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
         T = len(ids)
 
@@ -535,14 +540,33 @@ class BatchedSolver:
             if len(paths) != T:
                 raise ValueError(f'respawn: {len(paths)} waypoint lists where {T} rows are named')
             poff, ppts = paths_csr(paths)
-        args = [self.ctx, T, _lib.ptr(ids, C.c_int32)] + [p for _, p in keep] + \
+        brings = []
+        if policy is not None or attrs is not None:
+            desc = None
+            if attrs is not None:
+                unknown = sorted(set(attrs) - set(_ATTR_NAMES))
+                if unknown:
+                    raise ValueError(f'respawn: attrs names {unknown}, sca_restart_attrs has {list(_ATTR_NAMES)}')
+                desc = _lib.RestartAttrs(struct_bytes=C.sizeof(_lib.RestartAttrs), reserved=0)
+                for name, v in attrs.items():
+                    if v is None:
+                        continue
+                    i32 = name == 'max_neighbors'
+                    held = arr(v, np.int32 if i32 else np.float64, C.c_int32 if i32 else C.c_double, 0)
+                    keep.append(held)                                  # (alive until the call returns)
+                    setattr(desc, name, held[1])
+            pol = arr(policy, np.uint8, C.c_uint8, 0)
+            keep.append(pol)
+            brings = [pol[1], None if desc is None else C.byref(desc)]
+        rows = keep[:9]
+        args = [self.ctx, T, _lib.ptr(ids, C.c_int32)] + brings + [p for _, p in rows] + \
             [None if poff is None else _lib.ptr(poff, C.c_int32), None if ppts is None else _lib.ptr(ppts, C.c_double)]
+        plain, gated = ('sca_respawn_agents_attrs', 'sca_respawn_agents_gated_attrs') if brings else ('sca_respawn_agents', 'sca_respawn_agents_gated')
         if margin is None:
-            self._chk(self.L.sca_respawn_agents(*args), 'sca_respawn_agents')
+            self._chk(getattr(self.L, plain)(*args), plain)
             return None
         verdict, probe = np.zeros(max(T, 1), np.int32), np.zeros(max(T, 1), _lib.CLEARANCE_DTYPE)
-        self._chk(self.L.sca_respawn_agents_gated(*args, float(margin), _lib.ptr(verdict, C.c_int32), probe.ctypes.data_as(C.POINTER(_lib.SceneClearance)), None),
-                  'sca_respawn_agents_gated')
+        self._chk(getattr(self.L, gated)(*args, float(margin), _lib.ptr(verdict, C.c_int32), probe.ctypes.data_as(C.POINTER(_lib.SceneClearance)), None), gated)
         return verdict[:T], probe[:T]
 
     def probe_clearance(self, pos, radius, ignore=None):
