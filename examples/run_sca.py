@@ -8,6 +8,8 @@ log files -- only the imports differ (sca_amd.env instead of mamp.*).
     python examples/run_sca.py --scenario circle --agents 2000 --no-obstacles --policy orca
     python examples/run_sca.py --clearance --margin 0.2   # ... and how close the drones came (sca_clearance_enable)
     python examples/run_sca.py --lifelong 2000 --traffic 0.05 --spawn-margin 0.5   # drones leave when they arrive, new ones enter where there is room
+    python examples/run_sca.py --lifelong 2000 --traffic 0.05 --save-at 1000 --save-file cut.npz   # ... cut behind step 1000, vacant rows and all,
+    python examples/run_sca.py --lifelong 2000 --traffic 0.05 --resume cut.npz                     # and taken up again: the uncut run's summary
 """
 import argparse
 import math
@@ -39,7 +41,12 @@ def lifelong(args, agents, obstacles, pol, dubins):
     from sca_amd.lifelong import run_lifelong
     K = args.waypoints
     fleet = [POLICIES[name] for name in args.fleet.split(',')] if args.fleet else None
-    if fleet:                                                      # a mixed fleet: an arriving drone brings its own policy (MACAEnv(attribute_slots=True))
+    ck = None
+    if args.resume and args.traffic is not None:                   # the env as --save-at left it, vacant rows and all; the host loop's state is in the file too
+        from sca_amd.checkpoint import ContextCheckpoint
+        ck = ContextCheckpoint.read(args.resume)
+        env = E.MACAEnv.from_checkpoint(ck)
+    elif fleet:                                                      # a mixed fleet: an arriving drone brings its own policy (MACAEnv(attribute_slots=True))
         dubins = dubins or any(p in (E.SCAPolicy, E.RVO3dDubinsPolicy) for p in fleet)
         env = E.MACAEnv(device_tracker=dubins, clearance=args.clearance, path_slots=K, attribute_slots=True)
     else:
@@ -71,7 +78,8 @@ def lifelong(args, agents, obstacles, pol, dubins):
     if K:
         for a in agents:
             a.path = [w[:] for w in out_list[a.id]]
-    env.set_agents(agents, obstacles=obstacles)
+    if ck is None:
+        env.set_agents(agents, obstacles=obstacles)
 
     def next_mission(agent, row):
         i = agent.id
@@ -114,8 +122,13 @@ def lifelong(args, agents, obstacles, pol, dubins):
     elif args.traffic is not None:
         # a changing population: an arrived drone leaves the airspace (its row becomes vacant, MACAEnv.retire), and seeded arrivals -- a
         # Poisson number per step -- enter at vacant rows with those rows' original missions; with --spawn-margin only where the start is free
-        from sca_amd.lifelong import RETIRE
+        import json
+        from sca_amd.lifelong import RETIRE, resume_user_state
         trng = np.random.default_rng(2024)
+        if ck is not None:                                         # the arrivals' generator and the per-policy lines go on where they were cut
+            kept = json.loads(resume_user_state(ck))
+            trng.bit_generator.state = kept['trng']
+            per_policy.update(kept['per_policy'])
 
         def leave_or_restart(agent, row):
             f = int(row['flags'])
@@ -135,7 +148,11 @@ def lifelong(args, agents, obstacles, pol, dubins):
                     new.path = [w[:] for w in out_list[i]]
                 out.append(new)
             return out
-        stats = run_lifelong(env, leave_or_restart, args.lifelong, spawn_margin=args.spawn_margin, arrivals=arrivals)
+        stats = run_lifelong(env, leave_or_restart, args.lifelong - (ck.steps if ck is not None else 0), spawn_margin=args.spawn_margin, arrivals=arrivals,
+                             checkpoint_at=(args.save_at, args.save_file) if args.save_at else None, resume=ck,
+                             user_state=lambda: json.dumps(dict(trng=trng.bit_generator.state, per_policy=per_policy)))
+        if args.save_at:
+            print('saved behind step', args.save_at, 'as', args.save_file)
     else:
         stats = run_lifelong(env, next_mission, args.lifelong) if args.spawn_margin is None else \
             run_lifelong(env, next_mission, args.lifelong, spawn_margin=args.spawn_margin)
@@ -187,14 +204,14 @@ def main():
     ap.add_argument('--waypoints', type=int, default=0, metavar='K',
                     help='with --lifelong: every leg follows a route of K seeded waypoints, reversed on the way back (with --device-missions '
                          'the entries bring the routes: MissionTable(path=), sca_set_missions_paths)')
-    ap.add_argument('--save-at', type=int, default=0, metavar='K', help='with --device-missions: stop behind step K and write the running env '
-                    '(MACAEnv.checkpoint: definition + sca_save_context) to --save-file')
+    ap.add_argument('--save-at', type=int, default=0, metavar='K', help='with --device-missions or --traffic: stop behind step K and write the running env '
+                    '(MACAEnv.checkpoint: definition + sca_save_context; with --traffic the vacant rows and the host loop\'s state too) to --save-file')
     ap.add_argument('--save-file', default='run_sca_checkpoint.npz', metavar='F')
-    ap.add_argument('--resume', default=None, metavar='F', help='with --lifelong S --device-missions: go on from the file --save-at wrote, up to step S '
+    ap.add_argument('--resume', default=None, metavar='F', help='with --lifelong S and --device-missions or --traffic: go on from the file --save-at wrote, up to step S '
                     '(MACAEnv.from_checkpoint); the last line is that of the run that was never cut')
     args = ap.parse_args()
-    if (args.save_at or args.resume) and not args.device_missions:
-        ap.error('--save-at / --resume go with --lifelong STEPS --device-missions')
+    if (args.save_at or args.resume) and not (args.device_missions or args.traffic is not None):
+        ap.error('--save-at / --resume go with --lifelong STEPS --device-missions or --lifelong STEPS --traffic RATE')
     if args.device_missions and args.lifelong <= 0:
         ap.error('--device-missions goes with --lifelong STEPS')
     if args.traffic is not None and (args.lifelong <= 0 or args.device_missions or args.traffic < 0):

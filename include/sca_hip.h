@@ -644,12 +644,40 @@ struct sca_context_checkpoint_info {     /* (a struct tag: the function of the s
     int64_t updates;                     /* env updates since sca_set_missions */
     int64_t total_bytes;
     uint64_t checksum;
+    int32_t occupied, reserved1;         /* the occupied rows at the save: n for a blob without vacant rows (a caller compiled before the
+                                            field passes the smaller struct_bytes and does not receive it) */
 };
 int sca_context_checkpoint_layout(const sca_context_checkpoint_shape *shape, int64_t *offsets /*SCA_CONTEXT_CHECKPOINT_SECTIONS*/, int64_t *total_bytes);
 int sca_context_checkpoint_info(const void *blob, int64_t bytes, struct sca_context_checkpoint_info *out, int32_t struct_bytes);
 int sca_context_checkpoint_bytes(sca_ctx *ctx, int64_t *bytes);
 int sca_save_context(sca_ctx *ctx, void *out, int64_t out_bytes);
 int sca_load_context(sca_ctx *ctx, const void *in, int64_t in_bytes);
+/* The same three calls with an options word, for a context whose population changes (sca_retire_agents, below).  options == 0 is the call
+ * without the word in every respect, the refusal while a row is vacant included; an unknown bit is SCA_ERR_ARG.
+ *   SCA_CHECKPOINT_VACANCY   a save works while rows are vacant, a load takes a blob that holds vacant rows, and a load works on a context
+ *              that itself has vacant rows: it replaces vacancy wholesale.  The contract above then also covers sca_get_vacant,
+ *              sca_get_population, SCA_FORM_VACANCY, every refusal vacancy causes and its lifting once every row is occupied, and every
+ *              later retire, admitting respawn (plain, gated, _attrs), mission take and gate verdict.  A vacant row keeps its policy and
+ *              attributes, so the DEFINITION holds the policies and attributes as they stand at the save (a respawn may have brought
+ *              new ones: sca_respawn_agents_attrs).
+ *   in the blob  no new section and the same format: a vacant row's flag word (11), the permutation (occupied ids, then the vacant ids
+ *              ascending), the row's constants, tracker record, table words and cursor travel as every row's.  The header's `present`
+ *              word gains bit 32 and a reserved word holds the occupied count m, both only when m < n at the save: a blob saved with
+ *              the option from a context without vacant rows is byte for byte sca_save_context's, and sca_load_context loads it.
+ *              sca_context_checkpoint_info accepts both and reports `occupied`.
+ *   the outputs  of the last pass are not in a blob, and a vacant row gets no pass: the load leaves every vacant row's action row zero,
+ *              its neighbour counts 0 (near: -1) and its diag -1, as the retire left them.  One launch (k_ctx_load_vacancy) and one
+ *              synchronisation at any n, as before; the scratch a first retire allocates is allocated where the blob holds vacant rows.
+ *   refusals   every refusal of the calls without the word, with its code and in its order; then, SCA_ERR_ARG and before any device work:
+ *              the header's vacancy bit with occupied outside 1 .. n-1, or occupied != 0 without it; a row with flag bit 8 whose flag word
+ *              is not 11; a count of vacant rows other than n - occupied; a permutation with a vacant id in front of position m or whose
+ *              positions m .. n-1 are not the vacant ids ascending; vacant rows with lists in block form; a vacant row with a velocity,
+ *              heading or total_dist that is not zero, in slot form a len or rem that is not 0, or a gate's waiting word other than -1.
+ *              Without the option flag bit 8 and the header's bit stay the refusals they were. */
+enum { SCA_CHECKPOINT_VACANCY = 1 };
+int sca_context_checkpoint_bytes_opt(sca_ctx *ctx, uint32_t options, int64_t *bytes);
+int sca_save_context_opt(sca_ctx *ctx, uint32_t options, void *out, int64_t out_bytes);
+int sca_load_context_opt(sca_ctx *ctx, uint32_t options, const void *in, int64_t in_bytes);
 
 /* Closest approach per agent, measured WITH THE STEP.  With the feature on a step enqueues one more kernel beside the log's
  * (k_scene_clearance, a workgroup per scene, in front of the step's last kernel) that keeps, for every occupied agent row, how close the
@@ -807,8 +835,8 @@ int sca_get_finished(sca_ctx *ctx, sca_finished_row *rows /*capacity*/, int capa
  *              count, NULL ids with a capacity.  SCA_ERR_UNSUPPORTED: what sca_respawn_agents refuses (scenes, a shard with count < n, a
  *              communicator, the partition, lists in block form).
  *   while a row is vacant   SCA_ERR_UNSUPPORTED, the message names the reason: a pass in SCA_NBR_GRID, sca_step_host, sca_set_state,
- *              sca_set_kd_perm, sca_get_kd_tree, sca_save_context / sca_load_context / sca_context_checkpoint_bytes, sca_set_shard with
- *              count < n, sca_comm_init, sca_partition_init, sca_set_scenes, and the lists for the whole id range: sca_set_paths,
+ *              sca_set_kd_perm, sca_get_kd_tree, sca_save_context / sca_load_context / sca_context_checkpoint_bytes (each has an _opt form that takes
+ *              SCA_CHECKPOINT_VACANCY and then works: a checkpoint carries vacant rows), sca_set_shard with count < n, sca_comm_init, sca_partition_init, sca_set_scenes, and the lists for the whole id range: sca_set_paths,
  *              sca_set_path_slots, sca_set_path_state (a vacant row's list is empty and its now_goal None; clearing the lists with
  *              sca_set_paths(0, NULL) stays legal).  SCA_NBR_AUTO resolves to the kd pass, as with scenes, and a
  *              pass reports SCA_FORM_VACANCY.  Everything works again once every row is occupied.  sca_set_agents drops all vacancy.

@@ -75,7 +75,8 @@ class ContextCheckpointInfo(C.Structure):
     _fields_ = [('struct_bytes', C.c_int32), ('reserved', C.c_int32), ('format', C.c_int32), ('lib_version', C.c_int32), ('n', C.c_int32),
                 ('trk_words', C.c_int32), ('record_bytes', C.c_int32), ('has_tracker', C.c_int32), ('list_form', C.c_int32), ('W', C.c_int32),
                 ('M', C.c_int32), ('R', C.c_int32), ('has_gate', C.c_int32), ('has_clearance', C.c_int32), ('clear_step', C.c_int32),
-                ('state_fresh', C.c_int32), ('updates', C.c_int64), ('total_bytes', C.c_int64), ('checksum', C.c_uint64)]
+                ('state_fresh', C.c_int32), ('updates', C.c_int64), ('total_bytes', C.c_int64), ('checksum', C.c_uint64),
+                ('occupied', C.c_int32), ('reserved1', C.c_int32)]
 
 
 class SceneClearance(C.Structure):
@@ -185,6 +186,9 @@ SIGNATURES = {
     'sca_context_checkpoint_bytes': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     'sca_save_context': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     'sca_load_context': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    'sca_context_checkpoint_bytes_opt': (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_int64)]),
+    'sca_save_context_opt': (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64]),
+    'sca_load_context_opt': (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64]),
     'sca_scene_clearance_enable': (C.c_int, [C.c_void_p, C.c_int]),
     'sca_get_scene_clearance': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SceneClearance), C.c_int32]),
     'sca_clearance_enable': (C.c_int, [C.c_void_p, C.c_int]),

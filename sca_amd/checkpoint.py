@@ -9,7 +9,9 @@ count in one .npz, no pickle.
 The blob holds the mutable state only (include/sca_hip.h: what a blob holds); the definition is what the caller set the context up with
 and stays the caller's to keep -- this class keeps it as arrays: policies, attributes, obstacles, the state it was first given, the fed
 v_pref, tracker parameters, the list form and W with the block form's lists, the mission tables and their lists, the gate's margin and
-cap, whether closest-approach records are on, the neighbour mode the run steps with."""
+cap, whether closest-approach records are on, the neighbour mode the run steps with.  A blob may hold vacant rows (BatchedSolver.retire):
+solver() and MACAEnv.from_checkpoint load with vacancy=True, and a vacant row keeps its policy and attributes, so the definition holds them
+as they stand at the save."""
 import numpy as np
 
 from . import _lib
@@ -130,7 +132,7 @@ class ContextCheckpoint:
             if 'gate' in d:
                 sol.set_mission_gate(float(d['gate'][0]), int(d['gate'][1]))
             if self.blob is not None:
-                sol.load_context(self.blob)
+                sol.load_context(self.blob, vacancy=True)            # (a blob may hold vacant rows; one without is what it always was)
         except BaseException:
             sol.close()
             raise
@@ -209,7 +211,8 @@ def env_checkpoint(env):
         d['pending_ids'] = np.array(pend, np.int32)
         d['pending_entry'] = np.array([env._mission_pending[i][0] for i in pend], np.int32)
         d['pending_pos'] = np.array([env._mission_pending[i][1] for i in pend], np.float64).reshape(len(pend), 3)
-    return ContextCheckpoint(d, env.solver.save_context(), len(env._time_cum) - 1)
+    # (vacant rows, MACAEnv.retire: they are in the blob; env.agents keeps their objects, so the definition has their policies and attributes)
+    return ContextCheckpoint(d, env.solver.save_context(vacancy=True), len(env._time_cum) - 1)
 
 
 def env_from_checkpoint(cls, ckpt, device=0):
@@ -238,7 +241,7 @@ def env_from_checkpoint(cls, ckpt, device=0):
         results, margin, cap = d['tables_args']
         env.set_missions(tables, results=int(results), spawn_margin=None if margin < 0 else float(margin), max_per_step=None if cap < 0 else int(cap))
         env._mission_pending = {int(i): (int(j), np.array(p, np.float64)) for i, j, p in zip(d['pending_ids'], d['pending_entry'], d['pending_pos'])}
-    env.solver.load_context(ckpt.blob)
+    env.solver.load_context(ckpt.blob, vacancy=True)                # (the mirrors are stale from here: Agent.is_vacant, env.vacant and env.population read the loaded rows)
     env._time_cum = [float(x) for x in d['env_time_cum']]
     env._active = env.solver.active_count()
     env._path_assigned = set()

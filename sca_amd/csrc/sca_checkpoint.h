@@ -19,18 +19,21 @@
 #include "../../include/sca_hip.h"
 #include "sca_core.h"
 #include "sca_scenes.h"
+#include "sca_vacancy.h"
 
 namespace sca {
 
 constexpr uint32_t CTXCK_MAGIC = 0x504b4343u;      // "CCKP"
 constexpr int32_t CTXCK_FORMAT = 1;
-enum CtxPresent : uint32_t { CTXCK_HAS_TRACKER = 1, CTXCK_HAS_LISTS = 2, CTXCK_HAS_TABLES = 4, CTXCK_HAS_GATE = 8, CTXCK_HAS_CLEARANCE = 16, CTXCK_HAS_ALL = 31 };
+enum CtxPresent : uint32_t { CTXCK_HAS_TRACKER = 1, CTXCK_HAS_LISTS = 2, CTXCK_HAS_TABLES = 4, CTXCK_HAS_GATE = 8, CTXCK_HAS_CLEARANCE = 16, CTXCK_HAS_ALL = 31,
+                             CTXCK_HAS_VACANCY = 32 };     // rows of the blob are vacant (sca_vacancy.h): set exactly when occupied < n at the save, by the _opt entry points alone
 enum CtxListForm : int32_t { CTXCK_LISTS_NONE = 0, CTXCK_LISTS_BLOCK = 1, CTXCK_LISTS_SLOTS = 2 };
 struct CtxHeader {                                 // 128 bytes
     uint32_t magic; int32_t format, lib_version, n;
     int32_t trk_words, rec_bytes; uint32_t present; int32_t list_form;
     int32_t W, M, R, clear_step;                   // room per row (slot form), the tables' M and R, k_clearance's step number
-    int32_t state_fresh, reserved0;                // 1: taken directly behind sca_set_state -- the one-time obstacle check is still pending
+    int32_t state_fresh, occupied;                 // 1: taken directly behind sca_set_state -- the one-time obstacle check is still pending; the occupied rows m with
+                                                   // CTXCK_HAS_VACANCY (1 .. n-1), else 0 -- the word was reserved and 0 before: a blob without vacant rows is what it always was
     int64_t updates;                               // env updates since sca_set_missions
     int64_t total_bytes;                           // header + sections
     uint64_t checksum;                             // scene_checkpoint_sum over the bytes behind the header
@@ -102,6 +105,7 @@ inline CtxShape ctx_header_shape(const CtxHeader &H) {
     return CtxShape{H.n, H.trk_words, H.list_form, H.W, H.M, H.R, (H.present & CTXCK_HAS_GATE) ? 1 : 0, (H.present & CTXCK_HAS_CLEARANCE) ? 1 : 0};
 }
 inline uint32_t ctx_shape_present(const CtxShape &S) {
+    // (without CTXCK_HAS_VACANCY, which is no part of a shape: it changes no section)
     return (S.trk_words > 0 ? CTXCK_HAS_TRACKER : 0u) | (S.list_form != CTXCK_LISTS_NONE ? CTXCK_HAS_LISTS : 0u) | (S.M > 0 ? CTXCK_HAS_TABLES : 0u) |
            (S.has_gate ? CTXCK_HAS_GATE : 0u) | (S.has_clearance ? CTXCK_HAS_CLEARANCE : 0u);
 }
@@ -134,7 +138,13 @@ enum CtxFault {
     CXF_COLLECTED,          // collected above ended                                                   }
     CXF_VERDICT,            // a verdict word above SCA_SPAWN_OVER_CAP, or negative refusals           }
     CXF_CLEAR_PARTNER,      // a closest-approach partner outside its range, or a negative step        }
-    CXF_TRACK_RANGE         // an AgentTrack integer outside its range (entry: the row)                }
+    CXF_TRACK_RANGE,        // an AgentTrack integer outside its range (entry: the row)                }
+    // with vacancy allowed (the _opt entry points with SCA_CHECKPOINT_VACANCY; without it bit 8 is CXF_FLAGS and the header's bit CXF_HEADER_RANGE)
+    CXF_VACANT_FLAGS,       // a row with the vacant bit whose flag word is not 11 (entry: the row)    } the payload: SCA_ERR_ARG
+    CXF_VACANT_COUNT,       // the rows with the vacant bit are not n - occupied                       }
+    CXF_VACANT_PERM,        // a position < m names a vacant id, or [m, n) is not the vacant ids ascending (entry: the position)   }
+    CXF_VACANT_BLOCK,       // vacant rows together with lists in block form, which a retire refuses   }
+    CXF_VACANT_WORDS        // a vacant row whose words are not a retired row's (entry: the row)       }
 };
 struct CtxCheck { CtxFault fault; int64_t entry; };
 inline int ctx_checkpoint_error_code(CtxFault f) { return f == CXF_OK ? SCA_OK : SCA_ERR_ARG; }
@@ -145,9 +155,33 @@ struct CtxExpect {
     const int32_t *block_len;                      // [n] block form: the lists' lengths as set
     int32_t n_obs;                                 // obstacles set (a closest-approach partner's bound)
 };
+// A vacant row of a blob must be what sca_retire_agents leaves (vacant_row, vacate_write_row, missions_retired) and what every later step
+// keeps, wherever a kernel or the host would act on the word.  Checked, beside the flag word (11: every policy kernel, K4, the tracker
+// and the compactions go by it):
+//   velocity, heading   zero: the integrate stage and the host state block carry them on as they stand
+//   total_dist          0.0: K4 adds no flag to a settled row only because 0 never passes max_run_dist
+//   len, rem            0 in slot form: a take and the host's length mirrors go by them; a respawn that admits the row writes them anew
+//   gate waiting        -1: k_mission_gate_take would admit a mission into a row that is not in the airspace
+// Not checked, because nothing acts on them while the row is vacant and an admitting respawn writes them: step_num, status, now_goal (no
+// kernel reads a list of length 0), the mission words other than the gate's (the row is done and "entered live" is 0: k_mission_advance
+// passes over it; a retire keeps them too), the closest-approach record (k_clearance measures occupied rows only; a value, not an index --
+// its partners' ranges are checked for every row), the tracker record (tracker_owns wants flags 0; its integers are in range as every
+// row's).  Kept by a retire and checked as for every row: position, radius, goal, pref_speed, max_run_dist, z-axis, the v_pref mode.
+inline bool ctx_vacant_row_fault(const unsigned char *b, const CtxLayout &L, const CtxShape &S, int i) {
+    const unsigned char *r = b + L.off[CX_REC] + (int64_t)CKPT_REC_BYTES * i;
+    if (!vacant_flag((uint32_t)ckpt_i32(r + 36))) return false;
+    for (int k = 0; k < 3; k++) if ((ckpt_i32(r + 24 + 4 * k) & 0x7fffffff) != 0) return true;                       // vx, vy, vz: +-0
+    for (int k = 0; k < 3; k++) if ((ckpt_i64(b + L.off[CX_HEADING] + 24 * (int64_t)i + 8 * k) & INT64_MAX) != 0) return true;
+    if (ckpt_i64(b + L.off[CX_TOTAL_DIST] + 8 * (int64_t)i) != 0) return true;
+    if (S.list_form == CTXCK_LISTS_SLOTS && (ckpt_i32(b + L.off[CX_LEN] + 4 * (int64_t)i) != 0 || ckpt_i32(b + L.off[CX_REM] + 4 * (int64_t)i) != 0)) return true;
+    if (S.has_gate && ckpt_i32(b + L.off[CX_GATE_WORDS] + 4 * ((int64_t)CTXCK_GATE_WAITING * S.n + i)) != -1) return true;
+    return false;
+}
 // THE check of a blob, whole: envelope, then the blob against the context, then every payload value a kernel would use as an index, a
 // count or a switch.  Reads bytes [0, bytes) of `blob` and nothing else; head (nullable) receives the header once the envelope holds.
-inline CtxCheck ctx_checkpoint_check(const void *blob, int64_t bytes, const CkptTrackFields &F, const CtxExpect *X, CtxHeader *head) {
+// allow_vacancy: the blob may hold vacant rows (CTXCK_HAS_VACANCY, flag bit 8), which then must be what sca_retire_agents leaves and every
+// later step keeps -- see ctx_vacant_row_fault for the words.
+inline CtxCheck ctx_checkpoint_check(const void *blob, int64_t bytes, const CkptTrackFields &F, const CtxExpect *X, CtxHeader *head, bool allow_vacancy = false) {
     if (blob == nullptr || bytes < (int64_t)sizeof(CtxHeader)) return {CXF_SHORT, -1};
     const unsigned char *b = (const unsigned char *)blob;
     CtxHeader H;
@@ -156,13 +190,16 @@ inline CtxCheck ctx_checkpoint_check(const void *blob, int64_t bytes, const Ckpt
     if (H.format != CTXCK_FORMAT) return {CXF_FORMAT, -1};
     if (H.rec_bytes != CKPT_REC_BYTES || (H.trk_words != 0 && H.trk_words != F.words)) return {CXF_RECORD, -1};
     const CtxShape S = ctx_header_shape(H);
-    if ((H.present & ~(uint32_t)CTXCK_HAS_ALL) != 0 || !ctx_shape_ok(S) || ctx_shape_present(S) != H.present || (H.state_fresh != 0 && H.state_fresh != 1) || H.reserved0 != 0)
+    const uint32_t known = (uint32_t)CTXCK_HAS_ALL | (allow_vacancy ? (uint32_t)CTXCK_HAS_VACANCY : 0u);
+    const bool vacancy = (H.present & CTXCK_HAS_VACANCY) != 0;
+    if ((H.present & ~known) != 0 || !ctx_shape_ok(S) || ctx_shape_present(S) != (H.present & (uint32_t)CTXCK_HAS_ALL) || (H.state_fresh != 0 && H.state_fresh != 1) ||
+        (vacancy ? H.occupied < 1 || H.occupied >= H.n : H.occupied != 0))
         return {CXF_HEADER_RANGE, -1};
     const CtxLayout L = ctx_checkpoint_layout(S);
     if (H.total_bytes != L.total || bytes != L.total) return {CXF_BYTES, -1};
     if (scene_checkpoint_sum(b + sizeof(CtxHeader), L.total - (int64_t)sizeof(CtxHeader)) != H.checksum) return {CXF_CHECKSUM, -1};
     if (head) *head = H;
-    const int N = H.n, M = H.M;
+    const int N = H.n, M = H.M, occupied = vacancy ? H.occupied : N;
     const unsigned char *pol = b + L.off[CX_POLICY];
     if (X) {
         const CtxShape &C = X->shape;
@@ -189,11 +226,30 @@ inline CtxCheck ctx_checkpoint_check(const void *blob, int64_t bytes, const Ckpt
         const unsigned char *r = b + L.off[CX_REC] + (int64_t)CKPT_REC_BYTES * i;
         const uint32_t flags = (uint32_t)ckpt_i32(r + 36);
         const uint32_t mode = (uint32_t)ckpt_i32(b + L.off[CX_VPREF_MODE] + 4 * (int64_t)i), z = (uint32_t)ckpt_i32(b + L.off[CX_ZAXIS] + 4 * (int64_t)i);
-        if ((flags & ~7u) != 0 || mode > 1u || z > 1u) return {CXF_FLAGS, i};
+        if ((flags & ~(allow_vacancy ? 15u : 7u)) != 0 || mode > 1u || z > 1u) return {CXF_FLAGS, i};
+        if (vacant_flag(flags) && flags != VACANT_FLAGS) return {CXF_VACANT_FLAGS, i};
         for (int k = 0; k < 3; k++) if (!restart_finite(ckpt_f64(r + 8 * k))) return {CXF_NOT_FINITE, i};
         const double radius = ckpt_f64(r + 40), ps = ckpt_f64(b + L.off[CX_PREF_SPEED] + 8 * (int64_t)i), mrd = ckpt_f64(b + L.off[CX_MAX_RUN_DIST] + 8 * (int64_t)i);
         if (!(restart_finite(radius) && radius > 0.0 && restart_finite(ps) && ps > 0.0 && restart_finite(mrd) && mrd > 0.0)) return {CXF_NOT_POSITIVE, i};
         if (ckpt_i32(b + L.off[CX_STEP_NUM] + 4 * (int64_t)i) < 0) return {CXF_COUNTERS, i};
+    }
+    if (allow_vacancy) {
+        const auto vacant = [&](int a) { return vacant_flag((uint32_t)ckpt_i32(b + L.off[CX_REC] + (int64_t)CKPT_REC_BYTES * a + 36)); };
+        int count = 0;
+        for (int i = 0; i < N; i++) count += vacant(i) ? 1 : 0;
+        if (count != N - occupied) return {CXF_VACANT_COUNT, -1};
+        if (count > 0) {
+            // sca_vacancy.h's contract: [0, m) the occupied ids in carried order, [m, n) the vacant ids ascending
+            int next = 0;
+            for (int p = 0; p < N; p++) {
+                const int32_t a = ckpt_i32(b + L.off[CX_PERM] + 4 * (int64_t)p);
+                if (p < occupied) { if (vacant(a)) return {CXF_VACANT_PERM, p}; continue; }
+                while (next < N && !vacant(next)) next++;
+                if (a != next) return {CXF_VACANT_PERM, p};
+                next++;
+            }
+            if (S.list_form == CTXCK_LISTS_BLOCK) return {CXF_VACANT_BLOCK, -1};
+        }
     }
     if (S.list_form != CTXCK_LISTS_NONE)
         for (int i = 0; i < N; i++) {
@@ -238,6 +294,8 @@ inline CtxCheck ctx_checkpoint_check(const void *blob, int64_t bytes, const Ckpt
                             count >= 0 && count <= CKPT_COUNT_MAX && next >= 0 && next <= count;
             if (!ok) return {CXF_TRACK_RANGE, i};
         }
+    if (vacancy)
+        for (int i = 0; i < N; i++) if (ctx_vacant_row_fault(b, L, S, i)) return {CXF_VACANT_WORDS, i};
     return {CXF_OK, -1};
 }
 
@@ -357,6 +415,28 @@ template <bool LOAD> SCA_HD void ctx_checkpoint_move(const CtxDev &d, uint8_t *b
     }
     if (S.has_clearance) ctx_pieces<LOAD>(d.clear, blob + L.off[CX_CLEAR], L.len[CX_CLEAR], tid, stride);
     if (LOAD) for (int64_t s = tid; s < CTXCK_STRIPES; s += stride) d.done_count[s * CTXCK_STRIPE_PITCH] = stripes[s];
+}
+
+// ---- the load with vacant rows ----------------------------------------------------------------------------------------------------------------
+// The outputs of the last pass are not in a blob: they follow with the next pass.  A vacant row never gets one, so a load that brings
+// vacant rows leaves for each of them what vacate_write_row left on the source and no pass has touched since: a zero action row, nbr_n 0,
+// nbr_valid 0, near_n -1, diag -1 (vacate_write_outputs, sca_vacancy.h).  Which rows: the flag word of the CHECKED blob, one 4-byte read
+// per row at the record's stride, as the "entered live" column takes it; never the rows' own records, which other threads of the same
+// launch are writing.  A thread serves a row's eight lanes: two runs of 32 bytes and three words per vacant row, vector stores, no atomics.
+struct CtxVacDev {
+    float *action;                  // [n*8]
+    int32_t *diag;                  // [n*8]
+    int32_t *nbr_n, *near_n;
+    uint8_t *nbr_valid;
+};
+SCA_HD void ctx_checkpoint_move_vacancy(const CtxDev &d, const CtxVacDev &o, uint8_t *blob, const CtxLayout &L, const CtxShape &S, const int32_t *stripes, int64_t tid, int64_t stride) {
+    ctx_checkpoint_move<true>(d, blob, L, S, stripes, tid, stride);
+    const ctx_u32 *rec = (const ctx_u32 *)(blob + L.off[CX_REC]);
+    const VacantRow w = vacant_row(VACANT_FLAGS, S.list_form == CTXCK_LISTS_SLOTS);
+    for (int64_t a = tid; a < (int64_t)S.n; a += stride) {
+        if (!vacant_flag(rec[a * (CKPT_REC_BYTES / 4) + 9])) continue;
+        for (int lane = 0; lane < 8; lane++) vacate_write_outputs(o, a, lane, w);
+    }
 }
 
 }  // namespace sca

@@ -24,6 +24,12 @@ __global__ __launch_bounds__(CTXCK_T) void k_ctx_save(CtxDev d, uint8_t *blob, C
 __global__ __launch_bounds__(CTXCK_T) void k_ctx_load(CtxDev d, const uint8_t *blob, CtxLayout L, CtxShape S, const int32_t *stripes) {
     ctx_checkpoint_move<true>(d, const_cast<uint8_t *>(blob), L, S, stripes, (int64_t)blockIdx.x * CTXCK_T + (int64_t)threadIdx.x, (int64_t)gridDim.x * CTXCK_T);
 }
+// sca_load_context_opt with SCA_CHECKPOINT_VACANCY: k_ctx_load's move plus, for every vacant row of the checked blob, the outputs a retire
+// left and no pass writes again (ctx_checkpoint_move_vacancy).  A symbol of its own, so that k_ctx_load stays what it was; still one
+// launch and one synchronisation at any n.
+__global__ __launch_bounds__(CTXCK_T) void k_ctx_load_vacancy(CtxDev d, CtxVacDev o, const uint8_t *blob, CtxLayout L, CtxShape S, const int32_t *stripes) {
+    ctx_checkpoint_move_vacancy(d, o, const_cast<uint8_t *>(blob), L, S, stripes, (int64_t)blockIdx.x * CTXCK_T + (int64_t)threadIdx.x, (int64_t)gridDim.x * CTXCK_T);
+}
 // workgroups for a blob of `bytes`: a lane per 16 bytes, capped
 inline int ctx_checkpoint_blocks(int64_t bytes) {
     const int64_t want = (bytes / 16 + CTXCK_T - 1) / CTXCK_T;

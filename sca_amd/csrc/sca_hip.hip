@@ -5058,7 +5058,7 @@ static std::string ctx_ckpt_fault_text(const CtxCheck &k) {
     case CXF_MAGIC: return "the blob is not a context checkpoint (magic)";
     case CXF_FORMAT: return "the blob has another format version than this library writes (" + std::to_string(CTXCK_FORMAT) + ")";
     case CXF_RECORD: return "the blob's tracker record or public record size is not this library's";
-    case CXF_HEADER_RANGE: return "the blob's header holds n < 1, unknown bits, or words that contradict each other (list form / W, M / R, the gate without tables)";
+    case CXF_HEADER_RANGE: return "the blob's header holds n < 1, unknown bits, or words that contradict each other (list form / W, M / R, the gate without tables, the vacancy bit / occupied)";
     case CXF_BYTES: return "the byte count is not the layout's for the blob's header (sca_context_checkpoint_layout)";
     case CXF_CHECKSUM: return "the payload's checksum is not the header's";
     case CXF_N: return "n: the blob's agent count is not the context's";
@@ -5081,6 +5081,11 @@ static std::string ctx_ckpt_fault_text(const CtxCheck &k) {
     case CXF_VERDICT: return "row " + at + " has a verdict word above SCA_SPAWN_OVER_CAP or a negative refusal count";
     case CXF_CLEAR_PARTNER: return "row " + at + " has a closest-approach partner outside its range or a negative step";
     case CXF_TRACK_RANGE: return "row " + at + " has a tracker record with a cursor, count or word outside its range";
+    case CXF_VACANT_FLAGS: return "row " + at + " has the vacant bit and a flag word other than 11";
+    case CXF_VACANT_COUNT: return "the rows with the vacant bit are not n - occupied of the header";
+    case CXF_VACANT_PERM: return "the permutation does not hold the occupied ids in front of the vacant ids ascending (position " + at + ")";
+    case CXF_VACANT_BLOCK: return "vacant rows with waypoint lists in block form, which sca_retire_agents refuses";
+    case CXF_VACANT_WORDS: return "vacant row " + at + " is not as sca_retire_agents leaves a row: a velocity, heading or total_dist that is not zero, a list that is not empty or a mission waiting at the gate";
     default: return "ok";
     }
 }
@@ -5111,35 +5116,53 @@ int sca_context_checkpoint_layout(const sca_context_checkpoint_shape *shape, int
 int sca_context_checkpoint_info(const void *blob, int64_t bytes, struct sca_context_checkpoint_info *out, int32_t struct_bytes) {
     if (!out || struct_bytes < (int32_t)offsetof(struct sca_context_checkpoint_info, format) || struct_bytes > (int32_t)sizeof(struct sca_context_checkpoint_info)) return SCA_ERR_ARG;
     CtxHeader H;
-    const CtxCheck k = ctx_checkpoint_check(blob, bytes, ckpt_track_fields(), nullptr, &H);
+    const CtxCheck k = ctx_checkpoint_check(blob, bytes, ckpt_track_fields(), nullptr, &H, true);
     if (k.fault != CXF_OK) return ctx_checkpoint_error_code(k.fault);
     struct sca_context_checkpoint_info I{};
     I.struct_bytes = struct_bytes; I.reserved = 0; I.format = H.format; I.lib_version = H.lib_version; I.n = H.n; I.trk_words = H.trk_words; I.record_bytes = H.rec_bytes;
     I.has_tracker = (H.present & CTXCK_HAS_TRACKER) ? 1 : 0; I.list_form = H.list_form; I.W = H.W; I.M = H.M; I.R = H.R;
     I.has_gate = (H.present & CTXCK_HAS_GATE) ? 1 : 0; I.has_clearance = (H.present & CTXCK_HAS_CLEARANCE) ? 1 : 0; I.clear_step = H.clear_step; I.state_fresh = H.state_fresh;
     I.updates = H.updates; I.total_bytes = H.total_bytes; I.checksum = H.checksum;
+    I.occupied = (H.present & CTXCK_HAS_VACANCY) ? H.occupied : H.n; I.reserved1 = 0;
     std::memcpy(out, &I, (size_t)struct_bytes);
     out->struct_bytes = struct_bytes;
     return 0;
 }
-int sca_context_checkpoint_bytes(sca_ctx *c, int64_t *bytes) {
-    API_ENTER(c);
+// The three calls behind both forms of their entry points: `options` is 0 for sca_context_checkpoint_bytes / sca_save_context /
+// sca_load_context, which stay what they were -- the vacancy refusal included -- and what the caller passed for the _opt forms.
+static int ctx_ckpt_options_refuse(sca_ctx *c, const char *who, uint32_t options) {
+    if ((options & ~(uint32_t)SCA_CHECKPOINT_VACANCY) != 0) { c->err = std::string(who) + ": unknown option bits (SCA_CHECKPOINT_VACANCY is the only one)"; return SCA_ERR_ARG; }
+    if (!(options & SCA_CHECKPOINT_VACANCY)) return vacancy_refuse(c, who);                 // (vacancy is in the blob only where the caller asks for it)
+    return 0;
+}
+static int ctx_ckpt_bytes(sca_ctx *c, const char *who, uint32_t options, int64_t *bytes) {
     ARG(c, bytes);
-    if (int r = vacancy_refuse(c, "sca_context_checkpoint_bytes")) return r;
-    if (int r = ctx_ckpt_call_refuse(c, "sca_context_checkpoint_bytes", true)) return r;    // (a size only where a save is possible)
+    if (int r = ctx_ckpt_options_refuse(c, who, options)) return r;
+    if (int r = ctx_ckpt_call_refuse(c, who, true)) return r;             // (a size only where a save is possible)
     *bytes = ctx_checkpoint_layout(ctx_ckpt_shape(c)).total;
     return 0;
 }
+int sca_context_checkpoint_bytes(sca_ctx *c, int64_t *bytes) {
+    API_ENTER(c);
+    return ctx_ckpt_bytes(c, "sca_context_checkpoint_bytes", 0, bytes);
+}
+int sca_context_checkpoint_bytes_opt(sca_ctx *c, uint32_t options, int64_t *bytes) {
+    API_ENTER(c);
+    return ctx_ckpt_bytes(c, "sca_context_checkpoint_bytes_opt", options, bytes);
+}
 // One launch of k_ctx_save into the page-locked block, one synchronisation, then the host completes the blob -- the policies, the
 // permutation while the host still holds it, the header, the checksum -- and copies it out.
-int sca_save_context(sca_ctx *c, void *out, int64_t out_bytes) {
-    API_ENTER(c);
-    if (int r = vacancy_refuse(c, "sca_save_context")) return r;       // (vacancy is not in the blob)
-    if (int r = ctx_ckpt_call_refuse(c, "sca_save_context", out != nullptr)) return r;
+// With vacant rows (SCA_CHECKPOINT_VACANCY) the kernel and the launch are the same: a vacant row's flag word, the permutation with its
+// occupied prefix and ascending vacant tail, the row's constants, tracker record, table words and cursor are sections the blob always had;
+// the host adds CTXCK_HAS_VACANCY and the occupied count to the header.  With no vacant row the header, and so the blob, is the old one.
+static int ctx_ckpt_save(sca_ctx *c, const char *who_, uint32_t options, void *out, int64_t out_bytes) {
+    const std::string who(who_);
+    if (int r = ctx_ckpt_options_refuse(c, who_, options)) return r;
+    if (int r = ctx_ckpt_call_refuse(c, who_, out != nullptr)) return r;
     const CtxShape S = ctx_ckpt_shape(c);
     const CtxLayout L = ctx_checkpoint_layout(S);
     if (out_bytes < L.total) {
-        c->err = "sca_save_context: the buffer holds " + std::to_string(out_bytes) + " bytes, the context needs " + std::to_string(L.total) + " (sca_context_checkpoint_bytes)";
+        c->err = who + ": the buffer holds " + std::to_string(out_bytes) + " bytes, the context needs " + std::to_string(L.total) + " (sca_context_checkpoint_bytes)";
         return SCA_ERR_ARG;
     }
     if (int r = ctx_ckpt_block(c, L.total)) return r;
@@ -5155,21 +5178,33 @@ int sca_save_context(sca_ctx *c, void *out, int64_t out_bytes) {
     if (!c->perm_on_device) std::memcpy(b + L.off[CX_PERM], c->h_perm.data(), sizeof(int32_t) * (size_t)S.n);   // the live permutation is still the host's (no device build since it was set)
     CtxHeader H{};
     H.magic = CTXCK_MAGIC; H.format = CTXCK_FORMAT; H.lib_version = sca_version(); H.n = S.n; H.trk_words = S.trk_words; H.rec_bytes = CKPT_REC_BYTES;
-    H.present = ctx_shape_present(S); H.list_form = S.list_form; H.W = S.W; H.M = S.M; H.R = S.R; H.clear_step = c->clear ? c->clear_step : 0;
+    H.present = ctx_shape_present(S) | (c->vac.on ? (uint32_t)CTXCK_HAS_VACANCY : 0u); H.occupied = c->vac.on ? c->vac.m : 0; H.list_form = S.list_form; H.W = S.W; H.M = S.M; H.R = S.R; H.clear_step = c->clear ? c->clear_step : 0;
     H.state_fresh = c->state_fresh ? 1 : 0; H.updates = c->ms.on ? (int64_t)c->ms.updates : 0; H.total_bytes = L.total;
     H.checksum = scene_checkpoint_sum(b + sizeof H, L.total - (int64_t)sizeof H);
     std::memcpy(b, &H, sizeof H);
     std::memcpy(out, b, (size_t)L.total);
     return 0;
 }
+int sca_save_context(sca_ctx *c, void *out, int64_t out_bytes) {
+    API_ENTER(c);
+    return ctx_ckpt_save(c, "sca_save_context", 0, out, out_bytes);
+}
+int sca_save_context_opt(sca_ctx *c, uint32_t options, void *out, int64_t out_bytes) {
+    API_ENTER(c);
+    return ctx_ckpt_save(c, "sca_save_context_opt", options, out, out_bytes);
+}
 // The blob is checked whole on the host (ctx_checkpoint_check) before any device work; then it goes into the page-locked block with K4's
 // counters for its flags behind it, ONE launch of k_ctx_load scatters it, and the call's one synchronisation follows.  Behind it the host
 // mirrors follow, as after sca_respawn_agents: the radius mirror, the envelopes (they only grow), the permutation, the lists' lengths, the
 // host state block where one exists.  state_replaced's effects apply, except that state_fresh takes the blob's value.
-int sca_load_context(sca_ctx *c, const void *in, int64_t in_bytes) {
-    API_ENTER(c);
-    if (int r = vacancy_refuse(c, "sca_load_context")) return r;
-    if (int r = ctx_ckpt_call_refuse(c, "sca_load_context", in != nullptr)) return r;
+// With SCA_CHECKPOINT_VACANCY the blob may hold vacant rows and so may the context: the load replaces vacancy wholesale.  The launch is
+// then k_ctx_load_vacancy, which also leaves the vacant rows' outputs as a retire left them; the host's vacancy mirrors (which rows, how
+// many are occupied) come from the checked blob, the retire's scratch is allocated in front of any device work where the blob needs it.
+static int ctx_ckpt_load(sca_ctx *c, const char *who_, uint32_t options, const void *in, int64_t in_bytes) {
+    const std::string who(who_);
+    const bool vacancy = (options & SCA_CHECKPOINT_VACANCY) != 0;
+    if (int r = ctx_ckpt_options_refuse(c, who_, options)) return r;
+    if (int r = ctx_ckpt_call_refuse(c, who_, in != nullptr)) return r;
     CtxExpect X{};
     X.shape = ctx_ckpt_shape(c); X.policy = c->h_policy.data(); X.n_obs = c->d.m;
     std::vector<int32_t> block_len;
@@ -5179,8 +5214,10 @@ int sca_load_context(sca_ctx *c, const void *in, int64_t in_bytes) {
         X.block_len = block_len.data();
     }
     CtxHeader H;
-    const CtxCheck k = ctx_checkpoint_check(in, in_bytes, ckpt_track_fields(), &X, &H);
-    if (k.fault != CXF_OK) { c->err = "sca_load_context: " + ctx_ckpt_fault_text(k); return ctx_checkpoint_error_code(k.fault); }
+    const CtxCheck k = ctx_checkpoint_check(in, in_bytes, ckpt_track_fields(), &X, &H, vacancy);
+    if (k.fault != CXF_OK) { c->err = who + ": " + ctx_ckpt_fault_text(k); return ctx_checkpoint_error_code(k.fault); }
+    const bool brings_vacant = (H.present & CTXCK_HAS_VACANCY) != 0;
+    if (brings_vacant) if (int r = vacancy_room(c)) return r;          // (as the first retire allocates it: a respawn that admits a row edits the permutation there)
     const CtxShape S = X.shape;
     const CtxLayout L = ctx_checkpoint_layout(S);
     if (int r = ctx_ckpt_block(c, L.total)) return r;
@@ -5188,7 +5225,11 @@ int sca_load_context(sca_ctx *c, const void *in, int64_t in_bytes) {
     std::memcpy(b, in, (size_t)L.total);
     int32_t *stripes = (int32_t *)(b + ctx_ckpt_stripes_at(L.total));
     ctx_checkpoint_stripes(b, L, S.n, stripes);
-    hipLaunchKernelGGL(k_ctx_load, dim3(ctx_checkpoint_blocks(L.total)), dim3(CTXCK_T), 0, c->stream, ctx_ckpt_dev(c), (const uint8_t *)b, L, S, (const int32_t *)stripes);
+    if (vacancy)
+        hipLaunchKernelGGL(k_ctx_load_vacancy, dim3(ctx_checkpoint_blocks(L.total)), dim3(CTXCK_T), 0, c->stream, ctx_ckpt_dev(c),
+                           CtxVacDev{c->d.action, c->d.diag, c->d.nbr_n, c->d.near_n, c->d.nbr_valid}, (const uint8_t *)b, L, S, (const int32_t *)stripes);
+    else
+        hipLaunchKernelGGL(k_ctx_load, dim3(ctx_checkpoint_blocks(L.total)), dim3(CTXCK_T), 0, c->stream, ctx_ckpt_dev(c), (const uint8_t *)b, L, S, (const int32_t *)stripes);
     CHK(c, hipGetLastError());
     CHK(c, hipStreamSynchronize(c->stream));
     const int n = S.n;
@@ -5198,9 +5239,14 @@ int sca_load_context(sca_ctx *c, const void *in, int64_t in_bytes) {
     const int32_t *len = S.list_form == CTXCK_LISTS_SLOTS ? (const int32_t *)(b + L.off[CX_LEN]) : nullptr;
     if (len) { c->h_path_len.resize((size_t)n); c->h_path_vpref.resize((size_t)n); }
     const HostLayout HL = host_state_layout(n);
+    if (vacancy) {                                                      // vacancy is replaced wholesale (sca_set_agents' words where the blob brings none)
+        c->vac.on = brings_vacant; c->vac.m = brings_vacant ? H.occupied : 0;
+        if (brings_vacant) c->vac.h.assign((size_t)n, 0); else c->vac.h.clear();
+    }
     for (int a = 0; a < n; a++) {
         PubRec r;
         std::memcpy(&r, b + L.off[CX_REC] + (size_t)CKPT_REC_BYTES * a, sizeof r);
+        if (brings_vacant) c->vac.h[(size_t)a] = vacant_flag(r.flags) ? 1 : 0;
         c->h_rec[a].radius = r.radius;
         c->max_radius = std::max(c->max_radius, r.radius);             // the envelopes only grow (conservative filters, as under respawns)
         c->max_pref_speed = std::max(c->max_pref_speed, ps[a]);
@@ -5223,6 +5269,14 @@ int sca_load_context(sca_ctx *c, const void *in, int64_t in_bytes) {
     state_replaced(c);
     c->state_fresh = H.state_fresh != 0;
     return 0;
+}
+int sca_load_context(sca_ctx *c, const void *in, int64_t in_bytes) {
+    API_ENTER(c);
+    return ctx_ckpt_load(c, "sca_load_context", 0, in, in_bytes);
+}
+int sca_load_context_opt(sca_ctx *c, uint32_t options, const void *in, int64_t in_bytes) {
+    API_ENTER(c);
+    return ctx_ckpt_load(c, "sca_load_context_opt", options, in, in_bytes);
 }
 
 // ---- finished scenes hand over their result with the step (include/sca_hip.h; the rules and the layout are sca_scenes.h's, the kernel is

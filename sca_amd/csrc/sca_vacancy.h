@@ -116,6 +116,15 @@ SCA_HD VacantRow vacant_row(uint32_t old_flags, bool slots) {
 // Dev: RespawnDev (sca_respawn.hip.h) plus action and diag; plain host arrays in the tests' harness.  Not here: the done_count stripe.
 static_assert(offsetof(PubRec, pz) == 16 && offsetof(PubRec, vx) == 24 && offsetof(PubRec, vz) == 32 && offsetof(PubRec, flags) == 36 && offsetof(PubRec, radius) == 40,
               "vacate_write_row edits the record's second and third 16-byte piece");
+// the outputs of the last pass, which no later pass writes for a vacant row (lanes 0 .. 7): vacate_write_row's part that a context
+// checkpoint's load repeats for the vacant rows of its blob (sca_checkpoint.h: the outputs are not in a blob).  Dev: action, diag, nbr_n,
+// nbr_valid, near_n
+template <class Dev>
+SCA_HD void vacate_write_outputs(const Dev &d, int64_t a, int lane, const VacantRow &w) {
+    if (lane < 7) d.action[8 * a + lane] = 0.0f;
+    if (lane < 8) d.diag[8 * a + lane] = w.diag;
+    if (lane == 0) { d.nbr_n[a] = w.nbr_n; d.nbr_valid[a] = w.nbr_valid; d.near_n[a] = w.near_n; }
+}
 template <class Dev>
 SCA_HD void vacate_write_row(const Dev &d, int a, int lane, const VacantRow &w) {
     if (lane == 1 || lane == 2) {
@@ -130,11 +139,9 @@ SCA_HD void vacate_write_row(const Dev &d, int a, int lane, const VacantRow &w) 
         d.heading[g] = 0.0;
         if (w.path_len >= 0 && d.now_goal) d.now_goal[g] = __builtin_nan("");
     }
-    if (lane < 7) d.action[8 * (int64_t)a + lane] = 0.0f;
-    if (lane < 8) d.diag[8 * (int64_t)a + lane] = w.diag;
+    vacate_write_outputs(d, (int64_t)a, lane, w);
     if (lane == 0) {
         d.total_dist[a] = w.total_dist; d.step_num[a] = w.step_num; d.status[a] = w.status;
-        d.nbr_n[a] = w.nbr_n; d.nbr_valid[a] = w.nbr_valid; d.near_n[a] = w.near_n;
         if (w.path_len >= 0 && d.path_len) { d.path_len[a] = w.path_len; d.path_rem[a] = w.path_len; }
         if (d.clear) d.clear[a] = scene_clearance_empty();
     }

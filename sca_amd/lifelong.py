@@ -26,14 +26,59 @@ run_lifelong's offer order: the traffic is the host loop's under the same rule.
 Interrupting such a run: run_missions(..., checkpoint_at=(step, path)) cuts the run at that step and writes the running env
 (MACAEnv.checkpoint: the definition as plain arrays beside the library's blob, sca_save_context) as one .npz; MACAEnv.from_checkpoint
 brings it back, in this or another process, and run_missions(env, None, the remaining steps) goes on with the standing tables and returns
-the stats of the run that was never cut.  run_lifelong's host loop is out of scope for checkpoints: its waiting and retired sets are
-Python objects of the caller's rule, which no blob can carry."""
+the stats of the run that was never cut.
+
+run_lifelong(..., checkpoint_at=(step, path)) cuts the host loop the same way, behind the whole iteration of that step -- its retire and
+respawn calls included -- with vacant rows in the blob (sca_save_context_opt) and the loop's own state beside it as plain arrays: the
+stats and traffic counters, the retired, vacant and arriving id sets, the waiting missions as the fields MACAEnv.respawn reads of an Agent,
+and the string user_state() returns (the caller's rule: a generator's state, say).  run_lifelong(MACAEnv.from_checkpoint(ck), next_mission,
+the remaining steps, ..., resume=ck) goes on and returns the stats of the run that was never cut; `arrivals` keeps seeing the run's step
+numbers; resume_user_state(ck) hands the string back."""
+import numpy as np
+
 from . import solver as S
 
 RETIRE = object()                                                # what next_mission returns for a drone that leaves the airspace (MACAEnv.retire)
 
 
-def run_lifelong(env, next_mission, steps, on_done=None, spawn_margin=None, arrivals=None):
+_STAT_KEYS = ('steps', 'arrived', 'collided', 'timed_out', 'respawned', 'retired', 'agent_steps', 'deferred')
+_TRAFFIC_KEYS = ('retired_rows', 'admitted', 'changing', 'pop_min', 'pop_max', 'pop_sum')
+
+
+def _loop_state(stats, traffic, retired, vacant, arriving, waiting, active, user):
+    """the host loop's state as plain arrays, under the `lifelong_` keys of a checkpoint's definition"""
+    from . import scenes as _scenes
+    ids = sorted(waiting)
+    ents = [waiting[i] for i in ids]
+    d = {'lifelong_stats': np.array([stats.get(k, 0) for k in _STAT_KEYS], np.int64), 'lifelong_traffic': np.array([int(traffic[k]) for k in _TRAFFIC_KEYS], np.int64),
+         'lifelong_active': np.array([active], np.int64), 'lifelong_retired': np.array(sorted(retired), np.int32), 'lifelong_vacant': np.array(sorted(vacant), np.int32),
+         'lifelong_arriving': np.array(sorted(arriving), np.int32), 'lifelong_waiting_ids': np.array(ids, np.int32),
+         'lifelong_waiting_vel': np.array([a._vel for a in ents], np.float32).reshape(len(ents), 3),
+         'lifelong_user': np.frombuffer(('' if user is None else str(user)).encode(), np.uint8).copy()}
+    d.update({'lifelong_waiting_' + k: np.asarray(v) for k, v in _scenes.SceneCheckpoint.define(ents, [a._path for a in ents], []).items()})
+    return d
+
+
+def resume_user_state(ckpt):
+    """the string user_state() returned at the cut ('' where there was none)"""
+    return bytes(ckpt.definition['lifelong_user'].astype(np.uint8)).decode() if 'lifelong_user' in ckpt.definition else ''
+
+
+def _loop_resume(ckpt):
+    from . import scenes as _scenes
+    d = ckpt.definition
+    if 'lifelong_stats' not in d:
+        raise ValueError('run_lifelong(resume=): the checkpoint was not written by run_lifelong(checkpoint_at=)')
+    pre = 'lifelong_waiting_'
+    ents = _scenes.SceneCheckpoint({k[len(pre):]: v for k, v in d.items() if k.startswith(pre) and k[len(pre):] not in ('ids', 'vel')}, np.zeros(0, np.uint8), 0).agents()
+    for a, i, v in zip(ents, d[pre + 'ids'], d[pre + 'vel']):
+        a.id, a._vel = int(i), np.array(v, np.float32)
+    sets = [set(int(i) for i in d['lifelong_' + k]) for k in ('retired', 'vacant', 'arriving')]
+    return ({k: int(v) for k, v in zip(_STAT_KEYS, d['lifelong_stats'])}, {k: int(v) for k, v in zip(_TRAFFIC_KEYS, d['lifelong_traffic'])}, sets,
+            {a.id: a for a in ents}, int(d['lifelong_active'][0]))
+
+
+def run_lifelong(env, next_mission, steps, on_done=None, spawn_margin=None, arrivals=None, checkpoint_at=None, resume=None, user_state=None):
     """Returns dict(steps, arrived, collided, timed_out: missions that ended that way (a collision wins over an arrival, an arrival over a
     time-out), respawned, retired, agent_steps: agents served summed over the steps, live_fraction: agent_steps / (agents x steps)).
     The run ends early when every agent is retired.  With spawn_margin the dict gains `deferred`, the refusals counted per attempt, and
@@ -42,7 +87,12 @@ def run_lifelong(env, next_mission, steps, on_done=None, spawn_margin=None, arri
     A changing population -- next_mission returned RETIRE at least once, or `arrivals` is given -- adds retired_rows (rows vacated: such an
     ending counts in `retired` too), admitted (arrivals that entered; not in `respawned`), arrivals_waiting (with spawn_margin: arrivals
     still refused at the end; `waiting` counts missions only) and population_min / population_max / population_mean over the steps.  With
-    `arrivals` the run does not end early while nobody runs: the next arrival may change that."""
+    `arrivals` the run does not end early while nobody runs: the next arrival may change that.
+    checkpoint_at=(step, path): behind the whole iteration of that step of the RUN the env (MACAEnv.checkpoint) and the loop's state are
+    written to `path` as one .npz and the stats so far are returned.  resume=ckpt (ContextCheckpoint.read(path), with env =
+    MACAEnv.from_checkpoint(ckpt)): the loop goes on where it was cut for `steps` more steps, with the same next_mission / on_done /
+    spawn_margin / arrivals, and returns the stats of the run that was never cut.  user_state(): a string kept in the file for the caller
+    (resume_user_state)"""
     n = len(env.agents)
     stats = dict(steps=0, arrived=0, collided=0, timed_out=0, respawned=0, retired=0, agent_steps=0, live_fraction=0.0)
     gated = spawn_margin is not None
@@ -54,6 +104,11 @@ def run_lifelong(env, next_mission, steps, on_done=None, spawn_margin=None, arri
     arriving = set()                                             # ids in `waiting` that are arrivals, not missions
     traffic = dict(retired_rows=0, admitted=0, changing=arrivals is not None, pop_min=n - len(vacant), pop_max=n - len(vacant), pop_sum=0)
     active = env._active
+    if resume is not None:
+        kept, tr, (retired, vacant, arriving), waiting, active = _loop_resume(resume)
+        stats.update({k: v for k, v in kept.items() if k in stats})
+        traffic.update(tr, changing=bool(tr['changing']))
+    cut = None if checkpoint_at is None else int(checkpoint_at[0])
     for _ in range(int(steps)):
         if active == 0 and arrivals is None:
             break
@@ -119,6 +174,11 @@ def run_lifelong(env, next_mission, steps, on_done=None, spawn_margin=None, arri
         pop = n - len(vacant)
         traffic['pop_min'], traffic['pop_max'] = min(traffic['pop_min'], pop), max(traffic['pop_max'], pop)
         traffic['pop_sum'] += pop
+        if cut is not None and stats['steps'] == cut:
+            ck = env.checkpoint()
+            ck.definition.update(_loop_state(stats, traffic, retired, vacant, arriving, waiting, active, user_state() if user_state is not None else None))
+            ck.write(checkpoint_at[1])
+            break
     if gated:
         stats['waiting'] = len(waiting) - len(arriving)
     if traffic['changing']:

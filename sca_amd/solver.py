@@ -12,6 +12,7 @@ from . import _lib
 
 POL_SCA, POL_RVO3D, POL_SRVO3D, POL_ORCA3D, POL_ORCA3D_LP, POL_RVO3D_DUBINS = range(6)
 FLAG_AT_GOAL, FLAG_COLLISION, FLAG_TIMEOUT = 1, 2, 4
+CHECKPOINT_VACANCY = 1                                          # SCA_CHECKPOINT_VACANCY: a context checkpoint that carries vacant rows
 FLAG_VACANT = 8                                                 # a vacant row (retire): always with at-goal | collision, get_state shows 11
 MISSION_START_HERE, MISSION_KEEP_ZAXIS = 1, 2                  # sca_mission_flag
 SPAWN_ADMITTED, SPAWN_BLOCKED_AGENT, SPAWN_BLOCKED_OBSTACLE, SPAWN_BLOCKED_ENTRY = 0, 1, 2, 3      # SCA_SPAWN_*: a gated respawn's verdict per row
@@ -759,23 +760,34 @@ class BatchedSolver:
         return scene_checkpoint_info(blob)
 
     # ---- context checkpoints (sca_save_context / sca_load_context) -------------------------------------------------------------
-    def context_checkpoint_bytes(self):
+    # vacancy=True: the _opt entry points with SCA_CHECKPOINT_VACANCY -- the checkpoint carries vacant rows (retire_agents); without it each
+    # call is the entry point it always was, refused while a row is vacant
+    def context_checkpoint_bytes(self, vacancy=False):
         """the size of the blob save_context writes for the context as it stands now"""
         out = C.c_int64(0)
-        self._chk(self.L.sca_context_checkpoint_bytes(self.ctx, C.byref(out)), 'sca_context_checkpoint_bytes')
+        if vacancy:
+            self._chk(self.L.sca_context_checkpoint_bytes_opt(self.ctx, CHECKPOINT_VACANCY, C.byref(out)), 'sca_context_checkpoint_bytes_opt')
+        else:
+            self._chk(self.L.sca_context_checkpoint_bytes(self.ctx, C.byref(out)), 'sca_context_checkpoint_bytes')
         return int(out.value)
 
-    def save_context(self):
+    def save_context(self, vacancy=False):
         """The whole context's mutable state as one uint8 array (include/sca_hip.h: what a blob holds).  One launch, one synchronisation."""
-        blob = np.zeros(self.context_checkpoint_bytes(), np.uint8)
-        self._chk(self.L.sca_save_context(self.ctx, C.c_void_p(blob.ctypes.data), blob.size), 'sca_save_context')
+        blob = np.zeros(self.context_checkpoint_bytes(vacancy), np.uint8)
+        if vacancy:
+            self._chk(self.L.sca_save_context_opt(self.ctx, CHECKPOINT_VACANCY, C.c_void_p(blob.ctypes.data), blob.size), 'sca_save_context_opt')
+        else:
+            self._chk(self.L.sca_save_context(self.ctx, C.c_void_p(blob.ctypes.data), blob.size), 'sca_save_context')
         return blob
 
-    def load_context(self, blob):
+    def load_context(self, blob, vacancy=False):
         """blob (bytes or a uint8 array, from save_context of any context) into this context, which has been given the run's definition.
         The blob is checked whole before the device sees it; ScaError (SCA_ERR_ARG) names what is wrong."""
         b = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray)) else blob, np.uint8).reshape(-1)
-        self._chk(self.L.sca_load_context(self.ctx, C.c_void_p(b.ctypes.data), b.size), 'sca_load_context')
+        if vacancy:
+            self._chk(self.L.sca_load_context_opt(self.ctx, CHECKPOINT_VACANCY, C.c_void_p(b.ctypes.data), b.size), 'sca_load_context_opt')
+        else:
+            self._chk(self.L.sca_load_context(self.ctx, C.c_void_p(b.ctypes.data), b.size), 'sca_load_context')
 
     def context_checkpoint_info(self, blob):
         """The header of a blob as a dict, after the whole check a load makes without a context; plus `offsets`, the byte offsets of its
@@ -1099,7 +1111,7 @@ def context_checkpoint_info(blob):
     rc = _lib.lib().sca_context_checkpoint_info(C.c_void_p(b.ctypes.data), b.size, C.byref(info), C.sizeof(info))
     if rc != 0:
         raise ScaError('sca_context_checkpoint_info: not a valid context checkpoint (rc=%d)' % rc)
-    out = {k: int(getattr(info, k)) for k, _ in info._fields_ if k not in ('struct_bytes', 'reserved')}
+    out = {k: int(getattr(info, k)) for k, _ in info._fields_ if k not in ('struct_bytes', 'reserved', 'reserved1')}
     out['offsets'], _ = context_checkpoint_layout(out['n'], out['trk_words'], out['list_form'], out['W'], out['M'], out['R'], out['has_gate'], out['has_clearance'])
     out['policy'] = b[out['offsets'][0]:out['offsets'][0] + out['n']].copy()
     return out

@@ -11,6 +11,12 @@ build's (--root: the parent's checkout, built).  Three parts, merged into profil
     bench     `bench.py --gpus 1 --steps 200 --warmup 20` as a child process, the parent's checkout and this one alternated twice, in front
               of everything else: the ms_per_step of each run's JSON line.
 
+--vacancy: one more part, into profiles/context_checkpoint_vacancy_cost.json (reported only):
+
+    vacancy   this build: save_context(vacancy=True) and load_context(blob, vacancy=True) with every second row vacant, beside the same
+              two calls with no vacant row (the blob is then sca_save_context's; the load is k_ctx_load_vacancy's launch all the same),
+              the old calls on that context and one step of each; the wall time around the Python call, 21 samples each.
+
 workloads: respawn_cost.py's (c3_auto: circle N = 4096 ORCA3D SCA_NBR_AUTO; c4: circle N = 100 000 SCA, device tracker, SCA_NBR_KDTREE)"""
 import argparse
 import json
@@ -56,6 +62,48 @@ def part_calls(here, w, args):
     return out
 
 
+def part_vacancy(here, w, args):
+    import numpy as np
+    out = {}
+    for name, retire in (('no_vacant_row', False), ('every_second_row_vacant', True)):
+        leg = make_leg(here[0], here[1], w)
+        sol, mode = leg['sol'], leg['mode']
+        leg['reset']()
+        sol.run_steps(args.warm, mode)
+        sol.synchronize()
+        if retire:
+            sol.retire(np.arange(1, sol.n, 2, dtype=np.int32))
+            sol.run_steps(2, mode)
+            sol.synchronize()
+        ms = {'save_context_vacancy': [], 'load_context_vacancy': [], 'one_step': []}
+        if not retire:
+            ms.update(save_context=[], load_context=[])
+        sol.load_context(sol.save_context(vacancy=True), vacancy=True)              # (untimed: the page-locked block's allocation)
+        for _ in range(args.samples):
+            t0 = time.perf_counter()
+            blob = sol.save_context(vacancy=True)
+            t1 = time.perf_counter()
+            sol.load_context(blob, vacancy=True)
+            t2 = time.perf_counter()
+            sol.run_steps(1, mode)
+            sol.synchronize()
+            t3 = time.perf_counter()
+            for k, dt in zip(('save_context_vacancy', 'load_context_vacancy', 'one_step'), (t1 - t0, t2 - t1, t3 - t2)):
+                ms[k].append(dt * 1e3)
+            if not retire:
+                t0 = time.perf_counter()
+                old = sol.save_context()
+                t1 = time.perf_counter()
+                sol.load_context(old)
+                t2 = time.perf_counter()
+                ms['save_context'].append((t1 - t0) * 1e3)
+                ms['load_context'].append((t2 - t1) * 1e3)
+        out[name] = {k: summary(v) for k, v in ms.items()}
+        out[name].update(blob_bytes=int(blob.size), occupied=int(sol.population()))
+        sol.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--root', default=None, help="the parent commit's checkout (built)")
@@ -65,9 +113,11 @@ def main():
     ap.add_argument('--warm', type=int, default=20)
     ap.add_argument('--alternations', type=int, default=5)
     ap.add_argument('--samples', type=int, default=21)
-    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'context_checkpoint_cost.json'))
+    ap.add_argument('--vacancy', action='store_true', help='the vacancy part alone, into profiles/context_checkpoint_vacancy_cost.json')
+    ap.add_argument('--out', default=None)
     args = ap.parse_args()
-    parts = args.parts.split(',')
+    args.out = args.out or os.path.join(REPO, 'profiles', 'context_checkpoint_vacancy_cost.json' if args.vacancy else 'context_checkpoint_cost.json')
+    parts = ['vacancy'] if args.vacancy else args.parts.split(',')
     bench = part_bench(args) if 'bench' in parts and args.root else None             # (in front of everything that opens the GPU here)
     here = load_package(REPO, 'sca_here')
     parent = load_package(args.root, 'sca_parent') if args.root else None
@@ -92,6 +142,10 @@ def main():
                 entry[key] = part_step(here, parent, w, args)
                 print(name, key, json.dumps(entry[key]), flush=True)
                 save()
+        if 'vacancy' in parts:
+            entry['vacancy'] = part_vacancy(here, w, args)
+            print(name, 'vacancy', json.dumps(entry['vacancy']), flush=True)
+            save()
         if 'calls' in parts:
             entry['calls'] = part_calls(here, w, args)
             print(name, 'calls', json.dumps(entry['calls']), flush=True)
