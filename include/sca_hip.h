@@ -97,7 +97,13 @@ enum sca_neighbor_mode {
 enum sca_status_bit {             /* per-agent status word of the last policy pass */
     SCA_ST_SQRT_DOMAIN = 2,       /* reference would raise ValueError (scaPolicy.py:159); clamped here */
     SCA_ST_BAD_PREF_SPEED = 4,    /* np.arange(0.5, ps+0.03, ps-0.5) does not have 2 elements (scaPolicy.py:195) */
-    SCA_ST_KD_STACK = 16,         /* kd traversal stack overflow (tree deeper than 48) */
+    SCA_ST_KD_STACK = 16,         /* a kd walk had more subtrees waiting than its stack holds and dropped one.  The stack holds the children
+                                     queued while the nearer one is walked -- a count of QUEUED SUBTREES, not the tree's depth: 48 in the
+                                     one-wavefront neighbour query and the kd answer of SCA_NBR_AUTO, 64 in the packed neighbour query,
+                                     the grid's obstacle walk, the env update's fallback walk (which ORs the bit into the walked agent's
+                                     word) and the closest-approach descent.  A uniform swarm queues about 10; k agents or obstacles on
+                                     ONE point queue about k - 10 for everybody within neighborDist.  A row with the bit has walked
+                                     an incomplete tree: its neighbour list, its action row and its collision flag are invalid */
     SCA_ST_NBR_OVERFLOW = 32,     /* grid mode: > max_neighbors in range, reference list is visit-order dependent */
     SCA_ST_VPREF_EDGE = 128,      /* reserved, never set.  Round 5 marked agent-steps whose straight-line v_pref (rvo3dPolicy.py:182-196)
                                      had a 5-decimal rounding within 1e-9 of flipping, because positions of a free-running episode

@@ -474,7 +474,9 @@ __global__ __launch_bounds__(K4_WAVES * 64) void k_collide_finish_grid(DeviceVie
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     collide_finish_body(d, P, check_arrived, [&](int ag, bool obs_only) {
-        bool r = collide_traverse(d, agent_reach, obs_reach, stacks[wid], ag, lane, true);      // obstacles: their kd-tree
+        int st = 0;
+        bool r = collide_traverse(d, agent_reach, obs_reach, stacks[wid], ag, lane, true, st);  // obstacles: their kd-tree
+        collide_flag_walk(d, ag, lane, st);
         if (!obs_only && !r) {
             PubRec me_old;
             const CollideCtx c = collide_ctx(d, ag, me_old);

@@ -2018,24 +2018,30 @@ __device__ __forceinline__ CollideCtx collide_ctx(const DeviceView &d, int agent
     c.me_goal = (c.me.flags & FLAG_AT_GOAL) != 0;
     return c;
 }
-// whole wavefront, one agent: range queries in both trees (wave-uniform agent)
+// whole wavefront, one agent: range queries in both trees (wave-uniform agent).  `st` gathers the walks' status (ST_KD_STACK where a full
+// stack dropped a subtree: the answer may then miss a partner) -- never silently: collide_flag_walk puts it into the agent's status word
 __device__ __forceinline__ bool collide_traverse(const DeviceView &d, double agent_reach, double obs_reach, int *stack, int agent, int lane,
-                                                 bool obstacles_only, int aroot = 0, int oroot = 0) {
+                                                 bool obstacles_only, int &st, int aroot = 0, int oroot = 0) {
     PubRec me_old;
     const CollideCtx c = collide_ctx(d, agent, me_old);
     bool hit = false;
     if (d.m > 0 && oroot >= 0) {                                     // (oroot: as in neighbors_one)
         const double rq = c.me.radius + obs_reach;
-        kd_traverse(d.owide, c.p, rq * rq, stack, lane, [&](int begin, int end) {
+        st |= kd_traverse(d.owide, c.p, rq * rq, stack, lane, [&](int begin, int end) {
             if (lane < end - begin) hit = hit || collide_obstacle(d, c, d.operm[begin + lane]);
         }, oroot);
     }
     if (obstacles_only) return __ballot(hit) != 0;                   // wave-uniform
     const double rq = c.me.radius + agent_reach;
-    kd_traverse(d.awide, c.p_old, rq * rq, stack, lane, [&](int begin, int end) {
+    st |= kd_traverse(d.awide, c.p_old, rq * rq, stack, lane, [&](int begin, int end) {
         if (lane < end - begin) { const int j = d.aperm[begin + lane]; if (j != agent) hit = hit || collide_agent(d, c, j); }
     }, aroot);
     return __ballot(hit) != 0;
+}
+// the walked agent's status word takes what its fallback walk reported (wave-uniform `st`, zero but for a full stack; only this wavefront
+// writes the agent's word here: as k_clearance does at its end)
+__device__ __forceinline__ void collide_flag_walk(const DeviceView &d, int agent, int lane, int st) {
+    if (st && lane == 0) d.status[agent] |= st;
 }
 
 constexpr int K4_WAVES = 4;
@@ -2102,7 +2108,10 @@ __global__ __launch_bounds__(K4_WAVES * 64) void k_collide_finish(DeviceView d, 
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     collide_finish_body(d, P, check_arrived, [&](int ag, bool obs_only) {
-        return collide_traverse(d, agent_reach, obs_reach, stacks[wid], ag, lane, obs_only);
+        int st = 0;
+        const bool r = collide_traverse(d, agent_reach, obs_reach, stacks[wid], ag, lane, obs_only, st);
+        collide_flag_walk(d, ag, lane, st);
+        return r;
     });
 }
 

@@ -385,8 +385,11 @@ __global__ __launch_bounds__(K4_WAVES * 64) void k_collide_finish_scenes(DeviceV
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     collide_finish_body(d, P, check_arrived, [&](int ag, bool obs_only) {
-        return collide_traverse(d, agent_reach, obs_reach, stacks[wid], ag, lane, obs_only, __builtin_amdgcn_readfirstlane(r(ag)),
-                                __builtin_amdgcn_readfirstlane(r.obstacles(ag)));
+        int st = 0;
+        const bool hit = collide_traverse(d, agent_reach, obs_reach, stacks[wid], ag, lane, obs_only, st, __builtin_amdgcn_readfirstlane(r(ag)),
+                                          __builtin_amdgcn_readfirstlane(r.obstacles(ag)));
+        collide_flag_walk(d, ag, lane, st);
+        return hit;
     }, SceneCount{d, r.v});
 }
 

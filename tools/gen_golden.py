@@ -1163,6 +1163,22 @@ def main():
                 except Exception as e:                                         # a scene the reference raises on is not part of the family
                     import traceback
                     print('F20_edge_' + nm, 'RAISED', repr(e), traceback.extract_tb(e.__traceback__)[-1], flush=True)
+    # F21: deep kd-trees -- a pile of finished agents (or of obstacles) on one point with six live agents around it (tests/kd_shapes.py holds
+    # the scenes: the generator records the very arrays the tests build).  The lists' order there is the tree's visit order and nothing else.
+    # The reference raised on none of the five.
+    if args.only is None or any(o.startswith('F21') for o in args.only):
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests'))
+        import kd_shapes
+        for nm, scene_name in kd_shapes.FIXTURES.items():
+            if want(nm):
+                sc = kd_shapes.scene(scene_name)
+                try:
+                    edge_steps(agent_mod, env_mod, classes, nm, sc['pos'], sc['goal'], sc['heading'], sc['vel'], sc['radius'], sc['pref_speed'], sc['policy'],
+                               sc['flags'], [([float(x) for x in p], float(r)) for p, r in zip(sc['obs_pos'], sc['obs_radius'])],
+                               steps=kd_shapes.FIXTURE_STEPS, outdir=od)
+                except Exception as e:
+                    import traceback
+                    print(nm, 'RAISED', repr(e), traceback.extract_tb(e.__traceback__)[-1], flush=True)
     # F6: ORCA-official N=100 circle, long run, every 10th step (LP4 coverage)
     if want('F6_orcalp_circle100_long'):
         pos, goal, _ = ro.set_circle_pos(100)
